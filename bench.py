@@ -29,14 +29,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# HIP multiplexes streams onto 4 hardware queues by default.  The engine uses 4 streams of its own (3
-# slots + the accumulation stream); with torch's and RCCL's streams on top, two of them would share a
-# queue and a slot's reduction would serialise in front of the next accumulation kernel (1.2 ms bubbles,
-# tools/gaps.py).  Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 DEGREE = 1 << 20
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E 8 TB/s
 # Integer multiply-add ceiling measured on MI355X (tools/microbench mix, profiles/r01_microbench_mix.jsonl): a bare
 # loop of independent 32x32+64 multiply-adds reaches 33.4 T/s chip-wide and nothing hides behind it.
 VALU_MAD_PEAK_T = 33.4
@@ -223,6 +217,15 @@ def batch_of_openings(eng, limbs, n, degree, golden, dev, torch, np, K):
                                     "host_pointer: the same through kzg_open_batch (PCIe copies inside, one polynomial per stream slot at this size)"}
 
 
+def dump_commitments(out_dir, points, np):
+    """--dump-outputs: the B commitments of the last timed step, as a caller receives them, in their canonical
+    48-byte compressed encoding (src/curves.rs) -> [B][48] float64 holding the byte values (exact, comparable across
+    builds whatever projective form a build returns)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = [np.frombuffer(p.compress(), dtype=np.uint8) for p in points]
+    np.save(os.path.join(out_dir, "commitments.npy"), np.stack(rows).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -242,7 +245,11 @@ def main():
                     help="rehearsal: put every rank on this device instead of LOCAL_RANK (needs --backend gloo)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even at world size 1: exercises the exchange path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the commitments of the last step to DIR/commitments.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -353,6 +360,8 @@ def main():
         elapsed = float(tt.item())
 
     assert len(results) == args.steps * batch
+    if args.dump_outputs and rank == 0:
+        dump_commitments(args.dump_outputs, results[-batch:], np)
     ok = all(r.compress().hex() == want for r in results) if want else None
     if want and not ok:
         raise SystemExit("rank %d: commitment differs from tests/golden (degree %d)" % (rank, degree))

@@ -537,14 +537,6 @@ __global__ void k_tail_nonzero(const uint32_t* __restrict__ c, uint64_t from, ui
     if (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) *flag = 1u;  // (host-mapped word: plain store, every writer stores 1)
 }
 
-// HIP multiplexes the streams of a process onto 4 hardware queues by default.  A context uses 4 streams of its own
-// (3 slots + the accumulation stream); as soon as the host application (or RCCL, or torch) has streams too, two of
-// them share a queue and a slot's reduction serialises in front of the next accumulation kernel (1.2 ms bubbles,
-// tools/gaps.py).  The variable is read when the HIP runtime initialises, so it is set when this library is loaded
-// (never overriding the user's own setting); a host that initialises HIP before loading the library has to export
-// GPU_MAX_HW_QUEUES=8 itself.
-__attribute__((constructor)) static void kzg_library_loaded() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
-
 // asynchronous / device-pointer entry points belong to ONE device: refused on a multi-device context
 #define KZG_SINGLE_DEVICE_ONLY(ctx)                                                                        \
     do {                                                                                                     \

@@ -4,15 +4,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_emits_one_contract_line():
+def test_bench_emits_one_contract_line(tmp_path, golden):
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-                          "--cpu-sample", "256"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-sample", "256", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -37,3 +40,8 @@ def test_bench_emits_one_contract_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["cores"] == 1 and c["host_cores"] >= 1
+    # --dump-outputs: the last step's commitment, its compressed bytes as float64
+    got = np.load(dump / "commitments.npy")
+    assert got.dtype == np.float64 and got.shape == (1, 48)
+    want = next(b["commit"] for b in golden["bench"] if b["degree"] == d["config"]["degree"])
+    assert bytes(got[0].astype(np.uint8)).hex() == want

@@ -178,6 +178,45 @@ int kzg_quotient(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, const u
 int kzg_evaluate(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, const uint64_t z[4],
                  uint64_t out_y[4]);
 
+/* ---- multiproofs: one G1 element proves P at k points -------------------------------------
+ * The next step of the article the reference follows (reference README.md) after single-point proofs.  With
+ * Z = prod_i (X - z_i) and I the interpolant of the pairs (z_i, y_i) (degree < k), the proof is [q(s)]G1 with
+ * q = (P - I) / Z, and a verifier checks  e(proof, [Z(s)]G2) == e(commitment - [I(s)]G1, G2).
+ * The device computes q by partial fractions, q = sum_i w_i Q_i (Q_i the single-point quotient at z_i,
+ * w_i = 1 / prod_{j != i} (z_i - z_j)): k independent scans, one MSM of n - k terms.
+ * zs, ys: k x blst_fr (Montgomery), point i at zs + 4 i.
+ * Arguments: 1 <= k <= KZG_MAX_OPEN_POINTS and points distinct as field elements, else (or on a NULL pointer)
+ *   KZG_ERR_INVALID_ARG.  n' = n without trailing zero coefficients (the reference's truncation).
+ * Errors, in kzg_open's order: any P(z_i) != y_i -> KZG_ERR_REMAINDER; otherwise n' - k > kzg_srs_len (some
+ *   coefficient at index >= srs_len + k is non-zero) -> KZG_ERR_DEGREE_TOO_HIGH.  n' <= k with every claim right ->
+ *   infinity (q = 0).  There is NO constant-polynomial error: a constant P gives infinity when c0 == y_i for all i
+ *   and KZG_ERR_REMAINDER otherwise, where kzg_open returns KZG_ERR_CONSTANT_POLY.  For k = 1 and n' >= 2 the proof
+ *   is kzg_open's bit for bit (the same kernels run).
+ * Multi-device contexts: a replicated SRS forwards the call to one device; a range-split SRS returns
+ *   KZG_ERR_INVALID_ARG (kzg_last_error says why).  kzg_quotient_points / kzg_evaluate_points run on devices[0]. */
+#define KZG_MAX_OPEN_POINTS 64
+/* host pointers, synchronous; takes one of the context's stream slots like kzg_open */
+int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, const uint64_t* zs, const uint64_t* ys,
+                    size_t k, uint64_t out_p1[18]);
+/* d_coeffs is a DEVICE pointer; collected by kzg_wait (single-device contexts only, like kzg_open_submit) */
+int kzg_open_points_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, const uint64_t* zs,
+                           const uint64_t* ys, size_t k);
+/* q alone (the element-wise test hook, counterpart of kzg_quotient): out_q needs room for n - k entries; *out_qn
+ * receives n' - k (0 when n' <= k).  KZG_ERR_REMAINDER as above; no SRS needed. */
+int kzg_quotient_points(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, const uint64_t* zs, const uint64_t* ys,
+                        size_t k, uint64_t* out_q, size_t* out_qn);
+/* the prover's first step: out_ys[4 i ..] = P(z_i), the same scans without a quotient; no SRS needed */
+int kzg_evaluate_points(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, const uint64_t* zs, size_t k,
+                        uint64_t* out_ys);
+/* Host only, no context (like kzg_verify_proof): reads SRS G1 entries [0, k) (blst_p1 at setup_g1 + j * g1_stride_bytes)
+ * and the G2 powers [s^j]G2, j in [0, k] (blst_p2 at setup_g2 + j * g2_stride_bytes): the Rust shim passes &srs[0].g1
+ * and &srs[0].g2 of its Vec<SetupArtifact> with stride size_of::<SetupArtifact>().  *valid = 1 accepted, 0 rejected.
+ * KZG_ERR_INVALID_ARG for k out of range, equal points, a G1 input off the curve or a G2 input off the twist (no
+ * subgroup checks, as kzg_verify_proof).  Cost: k G1 and k + 1 G2 scalar multiplications and one two-pair pairing. */
+int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,
+                      size_t k, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                      int* valid);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

@@ -87,6 +87,12 @@ class SetupArtifacts {  // owns one engine context = one GPU with the SRS reside
         check(kzg_srs_g2_at(secret_be.data(), index, out.data()));
         return out;
     }
+    // SRS entries [index, index + count) back as blst_p1 (Z = 1)
+    std::vector<G1Point> read_g1(size_t index, size_t count) const {
+        std::vector<G1Point> out(count);
+        check(kzg_srs_read_g1(ctx_, index, count, reinterpret_cast<uint64_t*>(out.data())), ctx_);
+        return out;
+    }
     kzg_ctx* ctx() const { return ctx_; }
 
    private:
@@ -160,6 +166,49 @@ struct Evaluation {  // src/polynomial.rs:249-253
     bool verify_proof(const G1Point& proof, const G1Point& commitment, const uint64_t s_g2[36]) const {
         int valid = 0;
         check(kzg_verify_proof(commitment.p1.data(), proof.p1.data(), point.l.data(), result.l.data(), s_g2, &valid), nullptr);
+        return valid == 1;
+    }
+};
+
+// Multiproofs (kzg_open_points): one proof for P at several points.  points / results: k Scalars each.
+struct Evaluations {
+    std::vector<Scalar> points, results;
+    // the prover's first step: results = P(points), the device scans without a quotient
+    static Evaluations at(const Polynomial& polynomial, std::vector<Scalar> points, const SetupArtifacts& setup) {
+        Evaluations ev{std::move(points), {}};
+        ev.results.resize(ev.points.size());
+        const auto& c = polynomial.coefficients();
+        check(kzg_evaluate_points(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), c.size(),
+                                  reinterpret_cast<const uint64_t*>(ev.points.data()), ev.points.size(),
+                                  reinterpret_cast<uint64_t*>(ev.results.data())), setup.ctx());
+        return ev;
+    }
+    G1Point generate_proof(const Polynomial& polynomial, const SetupArtifacts& setup) const {
+        G1Point out;
+        const auto& c = polynomial.coefficients();
+        check(kzg_open_points(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), c.size(),
+                              reinterpret_cast<const uint64_t*>(points.data()), reinterpret_cast<const uint64_t*>(results.data()),
+                              points.size(), out.p1.data()), setup.ctx());
+        return out;
+    }
+    // the quotient alone (n' - k coefficients), e.g. to check it element-wise
+    std::vector<Scalar> quotient(const Polynomial& polynomial, const SetupArtifacts& setup) const {
+        const auto& c = polynomial.coefficients();
+        std::vector<Scalar> q(c.size() > points.size() ? c.size() - points.size() : 1);
+        size_t qn = 0;
+        check(kzg_quotient_points(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), c.size(),
+                                  reinterpret_cast<const uint64_t*>(points.data()), reinterpret_cast<const uint64_t*>(results.data()),
+                                  points.size(), reinterpret_cast<uint64_t*>(q.data()), &qn), setup.ctx());
+        q.resize(qn);
+        return q;
+    }
+    // host-side check; g1: SRS entries [0, k) as blst_p1 (e.g. read back with kzg_srs_read_g1), g2: [s^j]G2 for j <= k
+    bool verify_proof(const G1Point& proof, const G1Point& commitment, const std::vector<G1Point>& g1,
+                      const std::vector<std::array<uint64_t, 36>>& g2) const {
+        int valid = 0;
+        check(kzg_verify_points(commitment.p1.data(), proof.p1.data(), reinterpret_cast<const uint64_t*>(points.data()),
+                                reinterpret_cast<const uint64_t*>(results.data()), points.size(), g1.data(), sizeof(G1Point),
+                                g2.data(), sizeof(g2[0]), &valid), nullptr);
         return valid == 1;
     }
 };

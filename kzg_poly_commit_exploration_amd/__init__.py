@@ -18,6 +18,7 @@ import numpy as np
 __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
+    "verify_points", "KZG_MAX_OPEN_POINTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,7 +49,9 @@ ABI_SYMBOLS = [
     "kzg_open_batch_submit", "kzg_wait_open_batch", "kzg_g1_uncompress",
     "kzg_dev_alloc", "kzg_dev_free", "kzg_dev_upload", "kzg_dev_download",
     "kzg_g1_sum", "kzg_g1_compress", "kzg_srs_g2_at", "kzg_verify_proof", "kzg_verify_proof_batch", "kzg_set_timing", "kzg_get_times", "kzg_msm_config",
+    "kzg_open_points", "kzg_open_points_submit", "kzg_quotient_points", "kzg_evaluate_points", "kzg_verify_points",
 ]
+KZG_MAX_OPEN_POINTS = 64
 
 
 class KzgError(Exception):
@@ -133,6 +136,11 @@ def load_library():
         "kzg_verify_proof": (i, [vp, vp, vp, vp, vp, C.POINTER(i)]),
         "kzg_verify_proof_batch": (i, [vp, vp, vp, vp, vp, sz, vp]),
         "kzg_msm_config": (i, [vp, C.POINTER(i), C.POINTER(i), C.POINTER(sz), C.POINTER(i)]),
+        "kzg_open_points": (i, [vp, vp, sz, vp, vp, sz, vp]),
+        "kzg_open_points_submit": (i, [vp, i, vp, sz, vp, vp, sz]),
+        "kzg_quotient_points": (i, [vp, vp, sz, vp, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_evaluate_points": (i, [vp, vp, sz, vp, sz, vp]),
+        "kzg_verify_points": (i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -414,6 +422,34 @@ class Engine:
         _check(self._lib.kzg_evaluate(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(out)), self._h)
         return Scalar.from_limbs(out)
 
+    # -- multiproofs: one proof for P at k points (zs, ys: sequences of Scalar) --
+    def open_points_limbs(self, coeffs, zs, ys):
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        zl, yl = _scalar_rows(zs), _scalar_rows(ys)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_open_points(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), len(zs), _ptr(out)), self._h)
+        return G1Point(out)
+
+    def open_points_submit(self, slot, dptr, n, zs, ys):
+        zl, yl = _scalar_rows(zs), _scalar_rows(ys)
+        _check(self._lib.kzg_open_points_submit(self._h, slot, C.c_void_p(dptr), n, _ptr(zl), _ptr(yl), len(zs)), self._h)
+
+    def quotient_points_limbs(self, coeffs, zs, ys):
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        zl, yl = _scalar_rows(zs), _scalar_rows(ys)
+        q = np.zeros((max(a.shape[0] - len(zs), 1), 4), dtype=np.uint64)
+        qn = C.c_size_t(0)
+        _check(self._lib.kzg_quotient_points(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), len(zs), _ptr(q), C.byref(qn)),
+               self._h)
+        return q[: qn.value].copy()
+
+    def evaluate_points_limbs(self, coeffs, zs):
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        zl = _scalar_rows(zs)
+        out = np.zeros((max(len(zs), 1), 4), dtype=np.uint64)
+        _check(self._lib.kzg_evaluate_points(self._h, _ptr(a), a.shape[0], _ptr(zl), len(zs), _ptr(out)), self._h)
+        return [Scalar.from_limbs(out[i]) for i in range(len(zs))]
+
     # -- device-resident, pipelined --
     def num_slots(self):
         return int(self._lib.kzg_num_slots(self._h))
@@ -586,6 +622,25 @@ def verify_proof_batch(commitments, proofs, zs, ys, s_g2):
     ok = np.zeros(max(n, 1), dtype=np.int32)
     _check(lib.kzg_verify_proof_batch(_ptr(cs), _ptr(ps), _ptr(zl), _ptr(yl), _ptr(g2), n, _ptr(ok)))
     return [bool(v) for v in ok[:n]]
+
+
+def _scalar_rows(values):
+    """k Scalars -> k x 4 uint64 (blst_fr images, Montgomery), contiguous"""
+    return np.ascontiguousarray(np.stack([v.limbs() for v in values]) if len(values) else np.zeros((1, 4)), dtype=np.uint64)
+
+
+def verify_points(commitment, proof, zs, ys, setup_g1, setup_g2):
+    """kzg_verify_points: e(proof, [Z(s)]G2) == e(commitment - [I(s)]G1, G2) on the host.  setup_g1: at least k
+    blst_p1 rows ([s^j]G1, j < k); setup_g2: k + 1 blst_p2 rows ([s^j]G2, j <= k), e.g. from srs_g2_at."""
+    lib = load_library()
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    k = len(zs)
+    assert len(ys) == k and g1.shape[0] >= k and g2.shape[0] >= k + 1
+    ok = C.c_int(0)
+    _check(lib.kzg_verify_points(_ptr(commitment.p1), _ptr(proof.p1), _ptr(_scalar_rows(zs)), _ptr(_scalar_rows(ys)), k,
+                                 _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
 
 
 # ---------------------------------------------------------------------------------------------

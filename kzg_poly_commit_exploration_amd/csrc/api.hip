@@ -62,7 +62,8 @@ struct ReducePlan {
 // [section][polynomial][record]; reading it as a single job would return a wrong point with KZG_OK)
 // SLOT_RESERVED: owned by a synchronous host-pointer call between its steps (upload -> submit -> wait), during which the
 // context mutex is NOT held: N caller threads occupy N slots and their jobs pipeline like explicit submits do.
-enum SlotKind { SLOT_IDLE = 0, SLOT_COMMIT = 1, SLOT_OPEN = 2, SLOT_TRIVIAL = 3, SLOT_COMMIT_BATCH = 4, SLOT_OPEN_BATCH = 5, SLOT_RESERVED = 6 };
+enum SlotKind { SLOT_IDLE = 0, SLOT_COMMIT = 1, SLOT_OPEN = 2, SLOT_TRIVIAL = 3, SLOT_COMMIT_BATCH = 4, SLOT_OPEN_BATCH = 5, SLOT_RESERVED = 6,
+                SLOT_OPEN_POINTS = 7 /* a multiproof: trivial or not, collected by kzg_wait */ };
 
 struct Slot {
     hipStream_t stream = nullptr;
@@ -101,6 +102,17 @@ struct Slot {
     uint32_t* h_bsmall = nullptr;
     size_t bsmall_cap = 0;
     std::vector<uint32_t> open_ys;  // y of every polynomial of a batched opening (8 words each)
+    // multiproofs (kzg_open_points): the per-root multipliers go through a pinned staging area to a device buffer, copied
+    // on the slot's stream (a slot holds one job at a time, so nothing in flight reads them while they are rewritten);
+    // the k values P(z_i) land in pinned mapped memory like the flag words; d_pblock: k x nblocks aggregates
+    void* h_roots = nullptr;
+    void* d_roots = nullptr;
+    uint32_t* h_pvals = nullptr;
+    uint32_t* d_pvals = nullptr;
+    uint32_t* d_pblock = nullptr;
+    size_t pblock_words = 0;
+    std::vector<uint32_t> pts_ys;  // the claims (8 words each)
+    size_t pts_nq = 0;             // terms of the job's MSM (0: the proof is infinity once the claims hold)
     // state of the job in flight
     SlotKind kind = SLOT_IDLE;
     size_t job_n = 0;
@@ -526,6 +538,68 @@ bool host_tail_nonzero(const uint64_t* coeffs, size_t from, size_t n) {
     return false;
 }
 
+// ---- multiproofs (kzg_open_points and friends) ---------------------------------------------------------------------
+// 1 <= k <= KZG_MAX_OPEN_POINTS and pairwise-distinct points; ws receives w_i = 1 / prod_{j != i} (z_i - z_j)
+int points_weights(kzg_ctx* ctx, const uint64_t* zs, size_t k, uint64_t* ws /* 4 k */) {
+    if (k < 1 || k > KZG_MAX_OPEN_POINTS) {
+        ctx->last_error = "multiproof: k must be in [1, KZG_MAX_OPEN_POINTS]";
+        return KZG_ERR_INVALID_ARG;
+    }
+    hf::Fr z[KZG_MAX_OPEN_POINTS], w[KZG_MAX_OPEN_POINTS];
+    std::memcpy(z, zs, 32 * k);
+    if (!hf::fr_point_weights(z, k, w)) {
+        ctx->last_error = "multiproof: two of the points are equal";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::memcpy(ws, w, 32 * k);
+    return KZG_OK;
+}
+// the slot's multiproof buffers for k roots over n coefficients (slot basics already there)
+int ensure_points(kzg_ctx* ctx, Slot& s, size_t n, size_t k) {
+    if (!s.h_roots) {
+        HIP_TRY(ctx, hipHostMalloc(&s.h_roots, KZG_MAX_OPEN_POINTS * points_root_bytes(), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc(&s.d_roots, KZG_MAX_OPEN_POINTS * points_root_bytes()));
+        HIP_TRY(ctx, hipHostMalloc(&s.h_pvals, KZG_MAX_OPEN_POINTS * 32, hipHostMallocMapped));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_pvals, s.h_pvals, 0));
+    }
+    const size_t words = k * poly_block_words((uint32_t)(n ? n : 1));
+    if (words > s.pblock_words) {
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        hipFree(s.d_pblock);
+        s.d_pblock = nullptr;
+        s.pblock_words = 0;
+        HIP_TRY(ctx, hipMalloc(&s.d_pblock, words * 4));
+        s.pblock_words = words;
+    }
+    return KZG_OK;
+}
+// where the scan of a multiproof leaves P(z_i): the single-root kernels (k == 1) write the slot's flag words
+const uint32_t* points_values(const Slot& s, size_t k) { return k == 1 ? s.h_small + 8 : s.h_pvals; }
+// enqueues the scan of P at the k points on the slot's stream: q[0 .. nq) to s.d_q when want_q, the values as above.
+// k == 1 takes the single-root kernels unchanged (w_0 = 1), so its proofs are kzg_open's bit for bit.
+int enqueue_points_scan(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, const uint64_t* zs, const uint64_t* ws,
+                        size_t k, size_t nq, bool want_q) {
+    std::memset(s.h_small, 0, 64 * 4);  // (the slot holds no job in flight: nothing writes them now)
+    std::memset(s.h_pvals, 0, 32 * k);
+    if (n == 0) return KZG_OK;           // P = 0: every value is zero
+    if (k == 1) {
+        uint32_t zw[8];
+        std::memcpy(zw, zs, 32);
+        uint32_t* q = want_q && n > 1 ? s.d_q : nullptr;
+        if (!launch_quotient_single(s.stream, d_coeffs, (uint32_t)n, zw, q, s.d_small)) {
+            PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
+            launch_quotient(s.stream, d_coeffs, (uint32_t)n, zw, q, sc);
+        }
+    } else {
+        points_fill_roots(s.h_roots, zs, ws, (uint32_t)k, (uint32_t)n);
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_roots, s.h_roots, k * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
+        launch_quotient_points(s.stream, d_coeffs, (uint32_t)n, s.d_roots, (uint32_t)k, want_q ? s.d_q : nullptr, (uint32_t)nq,
+                               s.d_pblock, s.d_pvals);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
 }  // namespace
 
 // a tiny kernel for the device-pointer entry points: any non-zero Fr in [from, n)?
@@ -607,7 +681,7 @@ int kzg_ctx_create(int device, kzg_ctx** out) {
         ctx->small_lds_bytes = small_msm_lds_bytes();
     else
         (void)hipGetLastError();  // stays at 48 KiB: two workgroups may then share a CU (slower, not wrong)
-    if (!poly_prepare_device()) {
+    if (!poly_prepare_device() || !points_prepare_device()) {
         delete ctx;
         return KZG_ERR_HIP;  // the quotient kernels could not be launched on this device
     }
@@ -635,6 +709,10 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
         free_slot_poly(s);
         if (s.h_small) hipHostFree(s.h_small);
         if (s.h_bsmall) hipHostFree(s.h_bsmall);
+        if (s.h_roots) hipHostFree(s.h_roots);
+        if (s.h_pvals) hipHostFree(s.h_pvals);
+        hipFree(s.d_roots);
+        hipFree(s.d_pblock);
         for (auto& e : s.ev)
             if (e) hipEventDestroy(e);
         if (s.done) hipEventDestroy(s.done);
@@ -1038,6 +1116,58 @@ int kzg_open_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, cons
     return submit_open_locked(ctx, slot, (const uint32_t*)d_coeffs, n, z, y);
 }
 
+// A multiproof on slot `slot`: the scan of P at the k points, the degree check of the quotient (n' - k <= srs_len: no
+// non-zero coefficient at index >= srs_len + k), the MSM over q[0 .. n - k).  wait_locked checks the claims first.
+static int submit_points_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, size_t n, const uint64_t* zs,
+                                const uint64_t* ys, size_t k, bool owned = false) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind != (owned ? SLOT_RESERVED : SLOT_IDLE)) return KZG_ERR_BUSY;
+    uint64_t ws[4 * KZG_MAX_OPEN_POINTS];
+    int rc = points_weights(ctx, zs, k, ws);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // (an owned slot's coefficients already sit in its staging buffer, sized by the owner: ensure_poly is a no-op then)
+    rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = ensure_points(ctx, s, n, k);
+    if (rc) return rc;
+    s.timing = ctx->timing;
+    s.job_n = n;
+    s.job_batch = 1;
+    s.has_quotient = true;
+    s.tail_checked = false;
+    s.pts_ys.assign((const uint32_t*)ys, (const uint32_t*)ys + 8 * k);
+    std::memset(&s.times, 0, sizeof s.times);
+    size_t nq = n > k ? n - k : 0;
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
+    rc = enqueue_points_scan(ctx, s, d_coeffs, n, zs, ws, k, nq, nq > 0);
+    if (rc) return rc;
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
+    if (nq > ctx->n) {
+        const uint64_t from = ctx->n + k, cnt = n - from;
+        hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, d_coeffs, from,
+                           (uint64_t)n, s.d_small + 24);
+        nq = ctx->n;
+    }
+    if (nq > 0) {
+        rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+        if (rc) return rc;
+    }
+    s.pts_nq = nq;
+    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    s.kind = SLOT_OPEN_POINTS;
+    return KZG_OK;
+}
+
+int kzg_open_points_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, const uint64_t* zs, const uint64_t* ys,
+                           size_t k) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !zs || !ys || (!d_coeffs && n) || n > kMaxCoefficients) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return submit_points_locked(ctx, slot, (const uint32_t*)d_coeffs, n, zs, ys, k);
+}
+
 static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
     if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
     Slot& s = ctx->slots[slot];
@@ -1051,8 +1181,9 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
     SlotKind kind = s.kind;
     slot_idle(ctx, s);
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    if (kind != SLOT_TRIVIAL) fill_device_times(s);
-    if (s.timing && kind != SLOT_TRIVIAL) {
+    const bool ran_msm = kind != SLOT_TRIVIAL && !(kind == SLOT_OPEN_POINTS && s.pts_nq == 0);
+    if (ran_msm) fill_device_times(s);
+    if (s.timing && ran_msm) {
         float ms = 0;
         hipEventElapsedTime(&ms, s.ev[0], s.ev[1]); s.times.digits_ms = ms;
         hipEventElapsedTime(&ms, s.ev[2], s.ev[3]); s.times.scatter_ms = ms;
@@ -1067,6 +1198,15 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
     }
     const uint32_t* hs = s.h_small;
     hf::P1 inf = hf::p1_inf();
+    if (kind == SLOT_OPEN_POINTS) {  // every claim first, then the degree (kzg_open's order), then the MSM
+        const size_t k = s.pts_ys.size() / 8;
+        const uint32_t* vals = points_values(s, k);
+        for (size_t i = 0; i < k; i++)
+            if (std::memcmp(vals + 8 * i, s.pts_ys.data() + 8 * i, 32) != 0) return KZG_ERR_REMAINDER;
+        if (hs[24]) return KZG_ERR_DEGREE_TOO_HIGH;
+        write_p1(out_p1, s.pts_nq ? finish_msm(ctx, s) : inf);
+        return KZG_OK;
+    }
     if (s.has_quotient) {
         // reference order: sub -> divide_by_root (its two errors) -> commit (degree error)
         const size_t n = s.job_n;
@@ -1403,6 +1543,28 @@ int kzg_open(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t z[4]
     return rc;
 }
 
+int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,
+                    uint64_t out_p1[18]) {
+    if (!ctx || !out_p1 || !zs || !ys || (!coeffs && n) || n > kMaxCoefficients) return KZG_ERR_INVALID_ARG;
+    if (k < 1 || k > KZG_MAX_OPEN_POINTS) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return multi_open_points(ctx->multi, coeffs, n, zs, ys, k, out_p1);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, 0, coeffs, n);
+    if (rc == KZG_OK) rc = submit_points_locked(ctx, slot, s.d_stage, n, zs, ys, k, true);
+    if (rc == KZG_OK) {
+        await_unlocked(lk, s);
+        rc = wait_locked(ctx, slot, out_p1);
+    }
+    release_owned(ctx, slot);
+    return rc;
+}
+
 // ---- host-pointer batches (BASELINE config 5: many openings against one SRS) ----------------------------------------
 namespace {
 struct BatchInFlight {
@@ -1655,6 +1817,64 @@ int kzg_evaluate(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t 
     return KZG_OK;
 }
 
+// the multiproof scan alone on a slot of the context (no SRS needed): coefficients uploaded, values (and q) computed,
+// the stream drained.  Claims and truncation are the caller's business.
+static int points_scan_host(kzg_ctx* ctx, Slot& s, const uint64_t* coeffs, size_t n, const uint64_t* zs, size_t k, bool want_q) {
+    uint64_t ws[4 * KZG_MAX_OPEN_POINTS];
+    int rc = points_weights(ctx, zs, k, ws);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = ensure_points(ctx, s, n, k);
+    if (rc) return rc;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
+    rc = enqueue_points_scan(ctx, s, s.d_stage, n, zs, ws, k, n > k ? n - k : 0, want_q && n > k);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    return KZG_OK;
+}
+
+int kzg_quotient_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,
+                        uint64_t* out_q, size_t* out_qn) {
+    if (!ctx || !zs || !ys || !out_qn || (!coeffs && n) || (!out_q && n > k) || n > kMaxCoefficients) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_quotient_points(multi_kid(ctx->multi, 0), coeffs, n, zs, ys, k, out_q, out_qn);  // needs no SRS
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    *out_qn = 0;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = points_scan_host(ctx, s, coeffs, n, zs, k, true);
+    if (rc) return rc;
+    const uint32_t* vals = points_values(s, k);
+    for (size_t i = 0; i < k; i++)
+        if (std::memcmp(vals + 8 * i, ys + 4 * i, 32) != 0) return KZG_ERR_REMAINDER;
+    // q of the truncated polynomial: n' - k coefficients (none when n' <= k)
+    size_t n_eff = n;
+    while (n_eff > 0 && !(coeffs[4 * (n_eff - 1)] | coeffs[4 * (n_eff - 1) + 1] | coeffs[4 * (n_eff - 1) + 2] |
+                          coeffs[4 * (n_eff - 1) + 3]))
+        n_eff--;
+    if (n_eff <= k) return KZG_OK;
+    HIP_TRY(ctx, hipMemcpy(out_q, s.d_q, (n_eff - k) * 32, hipMemcpyDeviceToHost));
+    *out_qn = n_eff - k;
+    return KZG_OK;
+}
+
+int kzg_evaluate_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* zs, size_t k, uint64_t* out_ys) {
+    if (!ctx || !zs || !out_ys || (!coeffs && n) || n > kMaxCoefficients) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_evaluate_points(multi_kid(ctx->multi, 0), coeffs, n, zs, k, out_ys);  // needs no SRS
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = points_scan_host(ctx, s, coeffs, n, zs, k, false);
+    if (rc) return rc;
+    std::memcpy(out_ys, points_values(s, k), 32 * k);
+    return KZG_OK;
+}
+
 // ---- raw device memory -----------------------------------------------------------------------
 
 int kzg_dev_alloc(kzg_ctx* ctx, size_t bytes, void** out) {
@@ -1753,6 +1973,17 @@ int kzg_verify_proof_batch(const uint64_t* commitments_p1, const uint64_t* proof
         if (results[i] < 0) return KZG_ERR_INVALID_ARG;
         valid[i] = results[i];
     }
+    return KZG_OK;
+}
+
+int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,
+                      size_t k, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                      int* valid) {
+    if (!commitment_p1 || !proof_p1 || !zs || !ys || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    const int r = hf::verify_points(commitment_p1, proof_p1, zs, ys, k, (const uint8_t*)setup_g1, g1_stride_bytes,
+                                    (const uint8_t*)setup_g2, g2_stride_bytes);
+    if (r < 0) return KZG_ERR_INVALID_ARG;
+    *valid = r;
     return KZG_OK;
 }
 

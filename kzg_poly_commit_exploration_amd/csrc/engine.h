@@ -191,6 +191,8 @@ int multi_open(MultiState* m, const uint64_t* coeffs, size_t n, const uint64_t z
 int multi_commit_batch(MultiState* m, const uint64_t* coeffs, size_t n, size_t batch, size_t stride_coeffs, uint64_t* out_p1s);
 int multi_open_batch(MultiState* m, const uint64_t* coeffs, size_t n, size_t batch, size_t stride_coeffs, const uint64_t* zs,
                      const uint64_t* ys, uint64_t* out_p1s, int* statuses);
+int multi_open_points(MultiState* m, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,
+                      uint64_t out_p1[18]);
 int multi_set_max_batch(MultiState* m, size_t max_batch);
 uint32_t multi_mode(const MultiState* m);
 
@@ -213,5 +215,15 @@ bool launch_quotient_single(hipStream_t s, const uint32_t* d_coeffs, uint32_t n,
                             uint32_t* d_small);
 void launch_quotient(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const uint32_t z_mont[8],
                      uint32_t* d_q, PolyScratch scratch);
+// Several roots at once (KZG multiproofs): q = sum_i w_i Q_i with Q_i the single-root quotient at z_i and
+// w_i = 1 / prod_{j != i} (z_i - z_j); P(z_i) is written to d_vals[8 i .. 8 i + 8) (canonical blst_fr image).
+// The per-root multipliers live in device memory: points_fill_roots writes k records of points_root_bytes() each into
+// host memory (z_i, w_i in Montgomery form, 4 x u64 each), the caller copies them to d_roots.  d_block:
+// k * poly_block_words(n) words.  q[0 .. nq) is written when d_q != nullptr and nq > 0 (nq <= n - 1).
+bool points_prepare_device();
+size_t points_root_bytes();
+void points_fill_roots(void* h_roots, const uint64_t* zs_mont, const uint64_t* ws_mont, uint32_t k, uint32_t n);
+void launch_quotient_points(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
+                            uint32_t nq, uint32_t* d_block, uint32_t* d_vals);
 
 }  // namespace kzg

@@ -1,7 +1,8 @@
 // host_fr.hpp -- scalar field Fr on the host (4 x u64, Montgomery R = 2^256: the blst_fr memory image that crosses
 // the C-ABI).  Used by the multi-device context for the K-step carry recurrence of a range-sharded opening
 // (multi.hip); everything O(n) stays on the devices.  Mirrors the operations the reference takes from blst through
-// `Scalar` (src/scalar.rs:111-117, 192-218): add, sub, mul, pow.
+// `Scalar` (src/scalar.rs:111-117, 192-218): add, sub, mul, pow; the inverse and the barycentric weights of a
+// multiproof's points (api.hip: kzg_open_points and kzg_verify_points).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -80,6 +81,54 @@ inline Fr fr_pow(Fr base, uint64_t e) {
         e >>= 1;
     }
     return acc;
+}
+
+inline Fr fr_sub(const Fr& a, const Fr& b) {
+    uint64_t br;
+    Fr d = fr_raw_sub(a, b, br);
+    if (br) {
+        unsigned __int128 c = 0;
+        for (int i = 0; i < 4; ++i) {
+            c += (unsigned __int128)d.l[i] + kFrMod.l[i];
+            d.l[i] = (uint64_t)c;
+            c >>= 64;
+        }
+    }
+    return d;
+}
+// a^(r-2) = 1/a (0 for a = 0)
+inline Fr fr_inv(const Fr& a) {
+    static const uint64_t e[4] = {0xfffffffeffffffffULL, 0x53bda402fffe5bfeULL, 0x3339d80809a1d805ULL, 0x73eda753299d7d48ULL};
+    Fr acc = kFrOne;
+    for (int i = 255; i >= 0; --i) {
+        acc = fr_mul(acc, acc);
+        if ((e[i >> 6] >> (i & 63)) & 1) acc = fr_mul(acc, a);
+    }
+    return acc;
+}
+// the barycentric weights of k <= 64 distinct points: w_i = 1 / prod_{j != i} (z_i - z_j).  false when two points coincide.
+inline bool fr_point_weights(const Fr* zs, size_t k, Fr* ws) {
+    for (size_t i = 0; i < k; ++i) {
+        Fr d = kFrOne;
+        for (size_t j = 0; j < k; ++j)
+            if (j != i) d = fr_mul(d, fr_sub(zs[i], zs[j]));
+        if (d.is_zero()) return false;
+        ws[i] = d;
+    }
+    // one inversion for all of them (prefix products)
+    Fr run = kFrOne;
+    Fr pre[64];
+    for (size_t i = 0; i < k; ++i) {
+        pre[i] = run;
+        run = fr_mul(run, ws[i]);
+    }
+    Fr inv = fr_inv(run);
+    for (size_t i = k; i-- > 0;) {
+        const Fr wi = fr_mul(inv, pre[i]);
+        inv = fr_mul(inv, ws[i]);
+        ws[i] = wi;
+    }
+    return true;
 }
 
 }  // namespace kzg_host

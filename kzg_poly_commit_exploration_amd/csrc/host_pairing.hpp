@@ -14,6 +14,7 @@
 // line functions by elements of proper subfields (killed by the final exponentiation) do not matter.
 #pragma once
 #include "host_field.hpp"
+#include "host_fr.hpp"
 
 namespace kzg_host {
 
@@ -495,6 +496,83 @@ inline int verify_proof(const uint64_t* commitment, const uint64_t* proof, const
     P1 rhs = p1_add(p1_add(p1_mul(Pi, z), C), p1_neg(p1_mul(p1_generator(), y)));
     const G2Affine qs[2] = {sg2, g2_generator()};
     const P1 ps[2] = {Pi, p1_neg(rhs)};
+    bool ok = true;
+    const F12 f = multi_miller_loop(qs, ps, 2, ok);
+    if (!ok) return 0;
+    return f12_is_one(f12_final_exp(f)) ? 1 : 0;
+}
+
+// Jacobian y^2 = x^3 + 4 z^6 (infinity passes)
+inline bool p1_on_curve(const P1& p) {
+    if (p.is_inf()) return true;
+    Fp four = kOne + kOne;
+    four = four + four;
+    const Fp z2 = sqr(p.z), z6 = sqr(z2) * z2;
+    return sqr(p.y) == sqr(p.x) * p.x + four * z6;
+}
+
+// The multiproof check (one G1 element proves P at k points):
+//        e(proof, [Z(s)]G2) == e(commitment - [I(s)]G1, G2),   Z = prod (X - z_i),  I = the interpolant of (z_i, y_i).
+// I's coefficients come from the barycentric form I = sum_i y_i w_i Z / (X - z_i) (O(k^2) Fr products), [I(s)]G1 from the
+// SRS entries [s^j]G1 (j < k), [Z(s)]G2 from the G2 powers [s^j]G2 (j <= k); one Miller loop over both pairs, rearranged
+// as in verify_proof.  Returns 1 accepted, 0 rejected, -1 malformed input (1 <= k <= 64, distinct points, G1 inputs on
+// the curve, G2 inputs on the twist; no subgroup checks).
+inline int verify_points(const uint64_t* commitment, const uint64_t* proof, const uint64_t* zs_mont, const uint64_t* ys_mont,
+                         size_t k, const uint8_t* setup_g1, size_t g1_stride, const uint8_t* setup_g2, size_t g2_stride) {
+    if (k < 1 || k > 64) return -1;
+    Fr z[64], w[64], zc[65], ic[64];
+    for (size_t i = 0; i < k; ++i) std::memcpy(z[i].l, zs_mont + 4 * i, 32);
+    if (!fr_point_weights(z, k, w)) return -1;
+    // Z(X): multiply by (X - z_i) one point at a time
+    std::memset(zc, 0, sizeof zc);
+    zc[0] = kFrOne;
+    const Fr fr0 = {{0, 0, 0, 0}};
+    for (size_t i = 0; i < k; ++i) {  // degree i -> i + 1: new[j] = old[j - 1] - z_i old[j]
+        for (size_t j = i + 1; j > 0; --j) zc[j] = fr_sub(zc[j - 1], fr_mul(z[i], zc[j]));
+        zc[0] = fr_sub(fr0, fr_mul(z[i], zc[0]));
+    }
+    // I(X) = sum_i (y_i w_i) Z(X) / (X - z_i): synthetic division of Z by each root
+    std::memset(ic, 0, sizeof ic);
+    for (size_t i = 0; i < k; ++i) {
+        Fr y;
+        std::memcpy(y.l, ys_mont + 4 * i, 32);
+        const Fr t = fr_mul(y, w[i]);
+        Fr b = zc[k];  // coefficient k - 1 of Z / (X - z_i)
+        for (size_t j = k; j-- > 0;) {
+            ic[j] = fr_add(ic[j], fr_mul(t, b));
+            if (j) b = fr_add(zc[j], fr_mul(z[i], b));
+        }
+    }
+    P1 C, Pi;
+    std::memcpy(&C, commitment, sizeof C);
+    std::memcpy(&Pi, proof, sizeof Pi);
+    if (!p1_on_curve(C) || !p1_on_curve(Pi)) return -1;
+    P1 is = p1_inf();
+    for (size_t j = 0; j < k; ++j) {
+        P1 g;
+        std::memcpy(&g, setup_g1 + j * g1_stride, sizeof g);
+        if (!p1_on_curve(g)) return -1;
+        uint64_t e[4];
+        fr_from_mont(ic[j].l, e);
+        is = p1_add(is, p1_mul(g, e));
+    }
+    P2 zs2 = p2_inf();
+    for (size_t j = 0; j <= k; ++j) {
+        uint64_t raw[36];
+        std::memcpy(raw, setup_g2 + j * g2_stride, sizeof raw);
+        if (!g2_on_curve(g2_from_p2(raw))) return -1;
+        P2 q;
+        std::memcpy(&q, raw, sizeof q);
+        uint64_t e[4];
+        fr_from_mont(zc[j].l, e);
+        zs2 = p2_add(zs2, p2_mul(q, e));
+    }
+    const P2 zn = p2_normalize(zs2);
+    uint64_t zraw[36];
+    std::memcpy(zraw, &zn, sizeof zraw);
+    // e(proof, [Z(s)]G2) * e(-(commitment - [I(s)]G1), G2) == 1
+    const G2Affine qs[2] = {g2_from_p2(zraw), g2_generator()};
+    const P1 ps[2] = {Pi, p1_neg(p1_add(C, p1_neg(is)))};
     bool ok = true;
     const F12 f = multi_miller_loop(qs, ps, 2, ok);
     if (!ok) return 0;

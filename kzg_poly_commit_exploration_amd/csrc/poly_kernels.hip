@@ -444,13 +444,11 @@ bool launch_quotient_single(hipStream_t s, const uint32_t* d_coeffs, uint32_t n,
     return true;
 }
 
-void launch_quotient(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const uint32_t z_mont[8], uint32_t* d_q,
-                     PolyScratch sc) {
-    if (n == 0) return;
+// every multiplier the two-launch scan of n coefficients at z needs (~60 host Fr products)
+static void poly_powers(PolyPowers& pw, const uint32_t z_mont[8], uint32_t n) {
     namespace hf = kzg_host;
     const uint32_t nblocks = (n + kPolyTile - 1) / kPolyTile;
     const uint32_t per = (nblocks + kPolyBlock - 1) / kPolyBlock;  // blocks per lane of the block stage
-    PolyPowers pw;
     auto put = [](FrArg& dst, const hf::Fr& v) {  // the multiplier's form: digits of v * 2^270
         const Fr30 d = fr30_arg_from_mont256(v);
         std::memcpy(dst.d, d.d, sizeof dst.d);
@@ -485,6 +483,14 @@ void launch_quotient(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const 
         bb = hf::fr_mul(bb, m);
     }
     put(pw.zb256, ba);  // (zb^16)^16
+}
+
+void launch_quotient(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const uint32_t z_mont[8], uint32_t* d_q,
+                     PolyScratch sc) {
+    if (n == 0) return;
+    const uint32_t nblocks = (n + kPolyTile - 1) / kPolyTile;
+    PolyPowers pw;
+    poly_powers(pw, z_mont, n);
     constexpr uint32_t tile_lds = kPolyTileLds;
     hipLaunchKernelGGL(k_poly_chunks, dim3(nblocks), dim3(kPolyBlock), tile_lds, s, d_coeffs, n, pw, sc.d_chunk, sc.d_block, sc.d_flags);
     const int direct = nblocks <= kPolyDirectBlocks;
@@ -493,6 +499,173 @@ void launch_quotient(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const 
     if (q || direct)  // (without a quotient: one workgroup that leaves P(z))
         hipLaunchKernelGGL(k_poly_apply, dim3(q ? nblocks : 1), dim3(kPolyBlock), q ? tile_lds : 0u, s, d_coeffs, n, pw, sc.d_chunk,
                            sc.d_block, nblocks, direct, q, sc.d_result);
+}
+
+// ---- several roots at once: the quotient of a KZG multiproof --------------------------------------------------------
+// q = (P - I) / Z with Z = prod (X - z_i) and I the interpolant of the claims is, by partial fractions,
+//        q = sum_i w_i Q_i,      w_i = 1 / prod_{j != i} (z_i - z_j),      Q_i[j] = S_i[j+1]  (the single-root quotient),
+// exactly and coefficient by coefficient (1/Z = sum w_i / (X - z_i), and I/Z = sum w_i y_i / (X - z_i) only moves the
+// remainders).  The k scans are independent, so the two launches above extend to k roots without any k x k state:
+//   1. k_points_chunks: the tile is staged once; per root the chunk Horner and the in-workgroup scan, whose aggregate
+//      is written to that root's row of d_block (k x nblocks records);
+//   2. k_points_apply: the tile is staged once; per root the chunk Horner and the scan are REDONE (storing k x lanes
+//      chunk values would take ~400 MB at k = 64 and 2^20), the carry comes from that root's aggregates as in
+//      k_poly_apply, the replay yields S_i at the lane's 8 coefficients, and w_i S_i is added to the lane's 8
+//      accumulators (lazy digits: 64 products of magnitude r / 2 stay far inside the 270-bit digit range).  The sums go out
+//      one coefficient lower, q[0 .. nq), after a product by one brings them under r / 2.  Workgroup 0 writes P(z_i).
+// Beyond kPolyDirectBlocks blocks k_points_blocks runs the block stage of every root, one workgroup per root.
+// The multipliers of root i (its PolyPowers and w_i) are prepared on the host and sit in device memory (PointsRoot[k]).
+struct PointsRoot {
+    PolyPowers pw;
+    FrArg w;
+};
+size_t points_root_bytes() { return sizeof(PointsRoot); }
+
+// the replay of root i over the lane's chunk (coefficient C down to 0) with w_i S_i added to the accumulators, and the
+// accumulators' way out; templates rather than loops, so that every index into acc[] is a constant and it stays in VGPRs
+template <int C>
+KZG_DEV void points_replay(Fr30 (&acc)[kPolyL], Fr30& h, const Fr30& z, const Fr30& w, const uint4* __restrict__ lds_wave,
+                           uint32_t lane) {
+    h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, C));
+    acc[C] = fr30_add(acc[C], fr30_mul(h, w));
+    __builtin_amdgcn_sched_barrier(0);  // one step at a time: hoisted LDS reads and interleaved products cost registers
+    if constexpr (C > 0) points_replay<C - 1>(acc, h, z, w, lds_wave, lane);
+}
+template <int C>
+KZG_DEV void points_store_sums(const Fr30 (&acc)[kPolyL], const Fr30& one, uint4* __restrict__ lds_wave, uint32_t lane) {
+    uint32_t l[8];
+    fr30_to_limbs(fr30_mul(acc[C], one), l);  // (a product by one brings a sum of k terms under r / 2)
+    lds_wave[17u * lane + 2u * (uint32_t)C] = make_uint4(l[0], l[1], l[2], l[3]);
+    lds_wave[17u * lane + 2u * (uint32_t)C + 1u] = make_uint4(l[4], l[5], l[6], l[7]);
+    if constexpr (C > 0) points_store_sums<C - 1>(acc, one, lds_wave, lane);
+}
+
+__global__ void __launch_bounds__(kPolyBlock) k_points_chunks(const uint32_t* __restrict__ coeffs, uint32_t n,
+                                                              const PointsRoot* __restrict__ roots, uint32_t k,
+                                                              uint32_t* __restrict__ d_block) {
+    extern __shared__ uint4 lds_tile[];
+    __shared__ uint32_t lds[kPolyScanWords];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint4* lds_wave = lds_tile + wave * kPolyWaveLds;
+    const uint64_t wave_first = ((uint64_t)blockIdx.x * kPolyBlock + wave * 64u) * kPolyL;
+    poly_stage_in(coeffs, wave_first, n, lds_wave, lane);
+    for (uint32_t r = 0; r < k; r++) {
+        const Fr30 z = fr_from_arg(roots[r].pw.z);
+        Fr30 h = fr30_zero();
+#pragma unroll
+        for (int c = kPolyL - 1; c >= 0; c--) h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, c));
+        h = block_suffix_scan<kPolyBlock>(h, roots[r].pw.zl_sq, lds);
+        if (threadIdx.x == 0) store_rec(d_block + ((size_t)r * gridDim.x + blockIdx.x) * kPolyRec, h);
+    }
+}
+
+__global__ void __launch_bounds__(kPolyBlock) k_points_blocks(uint32_t* __restrict__ d_block, uint32_t nblocks,
+                                                              const PointsRoot* __restrict__ roots,
+                                                              uint32_t* __restrict__ d_vals) {
+    __shared__ uint32_t lds[kPolyScanWords];
+    const uint32_t r = blockIdx.x;
+    poly_block_stage(d_block + (size_t)r * nblocks * kPolyRec, nblocks, roots[r].pw, d_vals + 8 * r, lds);
+}
+
+// direct != 0: d_block holds the aggregates (workgroup 0 writes P(z_i) to d_vals[8 i ..]); direct == 0: the carries
+// (k_points_blocks ran and wrote P(z_i)).  d_q == nullptr: only the values are wanted (one workgroup, direct only).
+// nq: coefficients of q written (n - k; the ones above are exact zeros).
+__global__ void __launch_bounds__(kPolyBlock) k_points_apply(const uint32_t* __restrict__ coeffs, uint32_t n,
+                                                             const PointsRoot* __restrict__ roots, uint32_t k,
+                                                             const uint32_t* __restrict__ d_block, uint32_t nblocks, int direct,
+                                                             uint32_t* __restrict__ d_q, uint32_t nq,
+                                                             uint32_t* __restrict__ d_vals) {
+    extern __shared__ uint4 lds_tile[];
+    __shared__ uint32_t lds[kPolyScanWords];
+    const int tl = threadIdx.x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint4* lds_wave = lds_tile + wave * kPolyWaveLds;
+    const uint64_t wave_first = ((uint64_t)blockIdx.x * kPolyBlock + wave * 64u) * kPolyL;
+    if (d_q) poly_stage_in(coeffs, wave_first, n, lds_wave, lane);
+    const uint32_t dist = (uint32_t)(kPolyBlock - 1 - tl);  // chunks between the next chunk and the block end
+    Fr30 acc[kPolyL];
+#pragma unroll
+    for (int c = 0; c < kPolyL; c++) acc[c] = fr30_zero();
+    for (uint32_t r = 0; r < k; r++) {
+        const PolyPowers& pw = roots[r].pw;
+        const uint32_t* blk = d_block + (size_t)r * nblocks * kPolyRec;
+        Fr30 blk_carry;
+        if (direct) {
+            blk_carry = poly_carry_from_aggregates(blk, nblocks, blockIdx.x + 1, pw, lds);
+            if (blockIdx.x == 0 && tl == 0) {  // P(z_i) = A_0 + zb C_0, brought under r / 2 by a product with one
+                const Fr30 s0 = fr30_mul_add(blk_carry, fr_from_arg(pw.zb), load_rec(blk));
+                store_canonical(d_vals + 8 * r, fr30_mul(s0, fr_from_arg(pw.one)));
+            }
+        } else {
+            blk_carry = load_rec(blk + (size_t)blockIdx.x * kPolyRec);
+        }
+        if (!d_q) continue;
+        // the chunk Horner and the in-workgroup scan of launch 1 again: S at the first coefficient of every chunk
+        const Fr30 z = fr_from_arg(pw.z);
+        Fr30 h = fr30_zero();
+#pragma unroll
+        for (int c = kPolyL - 1; c >= 0; c--) h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, c));
+        h = block_suffix_scan<kPolyBlock>(h, pw.zl_sq, lds);
+#pragma unroll
+        for (int i = 0; i < kR9; i++) lds[i * kPolyBlock + tl] = (uint32_t)h.d[i];
+        __syncthreads();
+        Fr30 next = fr30_zero();  // the next lane's value: S at the first coefficient of the next chunk, without the carry
+        if (tl + 1 < kPolyBlock) {
+#pragma unroll
+            for (int i = 0; i < kR9; i++) next.d[i] = (int32_t)lds[i * kPolyBlock + tl + 1];
+        }
+        __syncthreads();
+        const Fr30 pa = fr_from_arg(pw.pa[dist >> 4]), pb = fr_from_arg(pw.pb[dist & 15]);  // (z^L)^dist = pa * pb
+        h = fr30_add(next, fr30_mul(blk_carry, fr30_mul(pa, pb)));
+        points_replay<kPolyL - 1>(acc, h, z, fr_from_arg(roots[r].w), lds_wave, lane);
+    }
+    if (!d_q) return;
+    // the sums, canonical, into the lane's own LDS words (the coefficients are no longer needed), then out one lower
+    points_store_sums<kPolyL - 1>(acc, fr_from_arg(roots[0].pw.one), lds_wave, lane);
+    poly_wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(d_q) + 2 * wave_first;  // word g of the region belongs at dst[g - 2]
+    const uint64_t end = 2 * ((uint64_t)nq + 1);                   // words of the region up to coefficient nq
+    const uint64_t valid = wave_first < nq + 1 ? end - 2 * wave_first : 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const uint32_t g = (uint32_t)i * 64u + lane;
+        if (g < valid && (wave_first != 0 || g >= 2)) dst[(int64_t)g - 2] = lds_wave[poly_lds_slot(g)];
+    }
+}
+
+bool points_prepare_device() {
+    const bool a = hipFuncSetAttribute((const void*)k_points_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolyTileLds) == hipSuccess;
+    const bool b = hipFuncSetAttribute((const void*)k_points_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolyTileLds) == hipSuccess;
+    if (!(a && b)) (void)hipGetLastError();
+    return a && b;
+}
+
+void points_fill_roots(void* h_roots, const uint64_t* zs_mont, const uint64_t* ws_mont, uint32_t k, uint32_t n) {
+    PointsRoot* roots = static_cast<PointsRoot*>(h_roots);
+    for (uint32_t r = 0; r < k; r++) {
+        std::memset(&roots[r], 0, sizeof roots[r]);
+        uint32_t zw[8];
+        std::memcpy(zw, zs_mont + 4 * r, 32);
+        poly_powers(roots[r].pw, zw, n);
+        kzg_host::Fr w;
+        std::memcpy(w.l, ws_mont + 4 * r, 32);
+        const Fr30 d = fr30_arg_from_mont256(w);
+        std::memcpy(roots[r].w.d, d.d, sizeof d.d);
+    }
+}
+
+void launch_quotient_points(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
+                            uint32_t nq, uint32_t* d_block, uint32_t* d_vals) {
+    if (n == 0 || k == 0) return;
+    const PointsRoot* roots = static_cast<const PointsRoot*>(d_roots);
+    const uint32_t nblocks = (n + kPolyTile - 1) / kPolyTile;
+    hipLaunchKernelGGL(k_points_chunks, dim3(nblocks), dim3(kPolyBlock), kPolyTileLds, s, d_coeffs, n, roots, k, d_block);
+    const int direct = nblocks <= kPolyDirectBlocks;
+    if (!direct) hipLaunchKernelGGL(k_points_blocks, dim3(k), dim3(kPolyBlock), 0, s, d_block, nblocks, roots, d_vals);
+    uint32_t* q = (d_q && nq > 0) ? d_q : nullptr;
+    if (q || direct)
+        hipLaunchKernelGGL(k_points_apply, dim3(q ? nblocks : 1), dim3(kPolyBlock), q ? kPolyTileLds : 0u, s, d_coeffs, n, roots, k,
+                           d_block, nblocks, direct, q, nq, d_vals);
 }
 
 }  // namespace kzg

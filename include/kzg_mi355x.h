@@ -217,6 +217,37 @@ int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[
                       size_t k, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
                       int* valid);
 
+/* ---- polynomials in evaluation form: NTT over power-of-two domains ------------------------
+ * Most KZG data (blob-style commitments, proof systems) holds a polynomial as its values over a subgroup of roots of
+ * unity.  These entry points take those values directly; until now a caller had to interpolate on the host first.
+ * Domain of size n = 2^k, 0 <= k <= 22 (the largest SRS): {w_n^i}, w_n = 7^((r - 1) / n) mod r, 7 the multiplicative
+ * generator blst, c-kzg and EIP-4844 use.  NATURAL order on both sides: evals[i] = P(w_n^i) for P = sum_j c[j] X^j.
+ * Nothing is bit-reversed at the boundary: a caller holding bit-reversed values (c-kzg's blob order) permutes them on
+ * the host first.  Every scalar is a blst_fr image (Montgomery), outputs fully reduced.
+ * Errors: n not a power of two or above 2^22 -> KZG_ERR_INVALID_ARG.  The commit / open calls treat the interpolated
+ * coefficients exactly as kzg_commit / kzg_open do (n above kzg_srs_len with a non-zero coefficient beyond it ->
+ * KZG_ERR_DEGREE_TOO_HIGH, a wrong y -> KZG_ERR_REMAINDER); z may lie inside or outside the domain.
+ * Multi-device contexts: kzg_ntt runs on devices[0]; the commit / open calls forward to one device of a replicated SRS
+ * and return KZG_ERR_INVALID_ARG on a range-split one. */
+#define KZG_NTT_MAX_LOG 22
+/* host only: w_n for n = 2^log_n, log_n <= 32 (out: blst_fr) */
+int kzg_domain_root(unsigned log_n, uint64_t out_mont[4]);
+/* out = NTT(in) (inverse = 0: coefficients -> evaluations) or its inverse (inverse != 0, includes the 1/n);
+ * host arrays of n blst_fr, in == out allowed; synchronous; no SRS needed.  Replaces the host interpolation a caller
+ * with evaluations had to run before kzg_commit. */
+int kzg_ntt(kzg_ctx* ctx, const uint64_t* in, size_t n, int inverse, uint64_t* out);
+/* the same on kzg_dev_alloc buffers of the context's GPU (single-device contexts); d_in == d_out allowed; returns when
+ * the result is in d_out */
+int kzg_ntt_device(kzg_ctx* ctx, const void* d_in, void* d_out, size_t n, int inverse);
+/* kzg_commit of the interpolated coefficients, bit for bit: one upload, the inverse NTT into the slot's staging
+ * buffer, the same MSM */
+int kzg_commit_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, uint64_t out_p1[18]);
+/* d_evals is a DEVICE pointer; collected by kzg_wait (single-device contexts only, like kzg_commit_submit) */
+int kzg_commit_evaluations_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n);
+/* kzg_open of the interpolated coefficients at z, claimed value y (P(w_n^i) = evals[i] for z in the domain) */
+int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, const uint64_t z[4], const uint64_t y[4],
+                         uint64_t out_p1[18]);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

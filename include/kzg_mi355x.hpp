@@ -170,6 +170,36 @@ struct Evaluation {  // src/polynomial.rs:249-253
     }
 };
 
+// Polynomials in evaluation form over the domain {w^i} of size n = 2^k (kzg_ntt and friends; natural order:
+// values[i] = P(w^i), w = Domain::root(k)).
+struct Domain {
+    static Scalar root(unsigned log_n) {
+        Scalar w;
+        check(kzg_domain_root(log_n, w.l.data()));
+        return w;
+    }
+    // coefficients -> values (inverse = false) or values -> coefficients (inverse = true); n a power of two <= 2^22
+    static std::vector<Scalar> ntt(const std::vector<Scalar>& in, bool inverse, const SetupArtifacts& setup) {
+        std::vector<Scalar> out(in.size());
+        check(kzg_ntt(setup.ctx(), reinterpret_cast<const uint64_t*>(in.data()), in.size(), inverse ? 1 : 0,
+                      reinterpret_cast<uint64_t*>(out.data())), setup.ctx());
+        return out;
+    }
+    // the commitment / proof of the P with these values: kzg_commit / kzg_open of the interpolated coefficients
+    static G1Point commit(const std::vector<Scalar>& values, const SetupArtifacts& setup) {
+        G1Point out;
+        check(kzg_commit_evaluations(setup.ctx(), reinterpret_cast<const uint64_t*>(values.data()), values.size(), out.p1.data()),
+              setup.ctx());
+        return out;
+    }
+    static G1Point generate_proof(const std::vector<Scalar>& values, const Scalar& z, const Scalar& y, const SetupArtifacts& setup) {
+        G1Point out;
+        check(kzg_open_evaluations(setup.ctx(), reinterpret_cast<const uint64_t*>(values.data()), values.size(), z.l.data(),
+                                   y.l.data(), out.p1.data()), setup.ctx());
+        return out;
+    }
+};
+
 // Multiproofs (kzg_open_points): one proof for P at several points.  points / results: k Scalars each.
 struct Evaluations {
     std::vector<Scalar> points, results;

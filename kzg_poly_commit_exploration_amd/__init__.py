@@ -18,7 +18,7 @@ import numpy as np
 __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
-    "verify_points", "KZG_MAX_OPEN_POINTS",
+    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "domain_root",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,8 +50,11 @@ ABI_SYMBOLS = [
     "kzg_dev_alloc", "kzg_dev_free", "kzg_dev_upload", "kzg_dev_download",
     "kzg_g1_sum", "kzg_g1_compress", "kzg_srs_g2_at", "kzg_verify_proof", "kzg_verify_proof_batch", "kzg_set_timing", "kzg_get_times", "kzg_msm_config",
     "kzg_open_points", "kzg_open_points_submit", "kzg_quotient_points", "kzg_evaluate_points", "kzg_verify_points",
+    "kzg_domain_root", "kzg_ntt", "kzg_ntt_device", "kzg_commit_evaluations", "kzg_commit_evaluations_submit",
+    "kzg_open_evaluations",
 ]
 KZG_MAX_OPEN_POINTS = 64
+KZG_NTT_MAX_LOG = 22
 
 
 class KzgError(Exception):
@@ -141,6 +144,12 @@ def load_library():
         "kzg_quotient_points": (i, [vp, vp, sz, vp, vp, sz, vp, C.POINTER(sz)]),
         "kzg_evaluate_points": (i, [vp, vp, sz, vp, sz, vp]),
         "kzg_verify_points": (i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, C.POINTER(i)]),
+        "kzg_domain_root": (i, [C.c_uint, vp]),
+        "kzg_ntt": (i, [vp, vp, sz, i, vp]),
+        "kzg_ntt_device": (i, [vp, vp, vp, sz, i]),
+        "kzg_commit_evaluations": (i, [vp, vp, sz, vp]),
+        "kzg_commit_evaluations_submit": (i, [vp, i, vp, sz]),
+        "kzg_open_evaluations": (i, [vp, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -450,6 +459,40 @@ class Engine:
         _check(self._lib.kzg_evaluate_points(self._h, _ptr(a), a.shape[0], _ptr(zl), len(zs), _ptr(out)), self._h)
         return [Scalar.from_limbs(out[i]) for i in range(len(zs))]
 
+    # -- polynomials in evaluation form over the domain {w^i} of size n = 2^k (natural order, see domain_root) --
+    def _ntt(self, values, inverse):
+        a = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros_like(a)
+        _check(self._lib.kzg_ntt(self._h, _ptr(a), a.shape[0], 1 if inverse else 0, _ptr(out)), self._h)
+        return out
+
+    def ntt_limbs(self, coeffs):
+        """coefficients -> evaluations: out[i] = P(w^i)"""
+        return self._ntt(coeffs, False)
+
+    def intt_limbs(self, evals):
+        """evaluations -> coefficients (the interpolation, 1/n included)"""
+        return self._ntt(evals, True)
+
+    def ntt_device(self, d_in, d_out, n, inverse=False):
+        _check(self._lib.kzg_ntt_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n, 1 if inverse else 0), self._h)
+
+    def commit_evaluations_limbs(self, evals):
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_commit_evaluations(self._h, _ptr(a), a.shape[0], _ptr(out)), self._h)
+        return G1Point(out)
+
+    def commit_evaluations_submit(self, slot, dptr, n):
+        _check(self._lib.kzg_commit_evaluations_submit(self._h, slot, C.c_void_p(dptr), n), self._h)
+
+    def open_evaluations_limbs(self, evals, z, y):
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        zl, yl = z.limbs(), y.limbs()
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_open_evaluations(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), _ptr(out)), self._h)
+        return G1Point(out)
+
     # -- device-resident, pipelined --
     def num_slots(self):
         return int(self._lib.kzg_num_slots(self._h))
@@ -590,6 +633,13 @@ class SetupArtifactsGenerator:
         return eng
 
 
+def domain_root(log_n):
+    """w_n for n = 2^log_n: 7^((r - 1) / n) mod r, as a Scalar (host only)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _check(load_library().kzg_domain_root(log_n, _ptr(out)))
+    return Scalar.from_limbs(out)
+
+
 def srs_g2_at(secret_be, index=1):
     """kzg_srs_g2_at: the G2 half of SetupArtifact `index`, [s^index]G2, as a blst_p2 (36 x uint64) -- what
     Evaluation::verify_proof reads from setup_artifacts[1] (src/polynomial.rs:284)."""
@@ -673,6 +723,12 @@ class Polynomial:
         nz = np.flatnonzero(a.any(axis=1))
         last = int(nz[-1]) if nz.size else 0
         return Polynomial(a[: last + 1] if a.shape[0] else a)
+
+    @staticmethod
+    def from_evaluations(evals, setup):
+        """The polynomial whose values over the domain of size n = len(evals) (a power of two) are evals, in natural
+        order: evals[i] = P(w_n^i) (domain_root).  Interpolated on the device (setup: an Engine)."""
+        return Polynomial.from_limbs(setup.intt_limbs(evals))
 
     def degree(self):  # src/polynomial.rs:93-98
         return 0 if self.limbs.shape[0] == 0 else self.limbs.shape[0] - 1

@@ -27,6 +27,7 @@
 #include "engine.h"
 #include "host_field.hpp"
 #include "host_fr.hpp"
+#include "fr30_host.hpp"
 #include "host_pairing.hpp"
 
 using namespace kzg;
@@ -144,6 +145,7 @@ struct kzg_ctx {
     size_t n = 0;  // points
     MsmConfig cfg = {};
     void* d_table = nullptr;  // W * n affine points
+    void* d_ntt_tw = nullptr;  // NTT twiddles, built on first use: forward lo, forward hi, inverse lo, inverse hi (ntt_kernels.hip)
     ReducePlan plan;
     size_t arena_records = 0, final_records = 0;  // per polynomial of a batch
     uint32_t max_batch = 1;                        // polynomials per submit the workspaces are sized for
@@ -722,6 +724,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     }
     if (ctx->heavy_stream) hipStreamDestroy(ctx->heavy_stream);
     if (ctx->d_table) hipFree(ctx->d_table);
+    if (ctx->d_ntt_tw) hipFree(ctx->d_ntt_tw);
     delete ctx;
 }
 
@@ -1873,6 +1876,212 @@ int kzg_evaluate_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const ui
     if (rc) return rc;
     std::memcpy(out_ys, points_values(s, k), 32 * k);
     return KZG_OK;
+}
+
+// ---- polynomials in evaluation form (NTT over power-of-two domains) -------------------------------------------------
+
+// log2 n for a domain size the transform supports (a power of two up to 2^22); false otherwise
+static bool ntt_log(size_t n, uint32_t* lg) {
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << kNttMaxLog)) return false;
+    uint32_t k = 0;
+    while (((size_t)1 << k) < n) k++;
+    *lg = k;
+    return true;
+}
+// the context's twiddle tables (ctx->mu held): one set for every size, w = w_(2^22) and its inverse, 4 x 2048 Fr30
+// (the caller has made ctx->device current, as for everything that allocates or launches below)
+static int ensure_ntt(kzg_ctx* ctx) {
+    if (ctx->d_ntt_tw) return KZG_OK;
+    if (!ntt_prepare_device()) {
+        (void)hipGetLastError();
+        ctx->last_error = "ntt: the pass kernel's LDS limit could not be raised";
+        return KZG_ERR_HIP;
+    }
+    std::vector<Fr30> h(4 * kNttTableLen);
+    const hf::Fr w = hf::fr_domain_root(kNttMaxLog);
+    for (int dir = 0; dir < 2; dir++) {
+        const hf::Fr base = dir ? hf::fr_inv(w) : w;
+        const hf::Fr step_hi = hf::fr_pow(base, kNttTableLen);
+        hf::Fr lo = hf::kFrOne, hi = hf::kFrOne;
+        for (uint32_t i = 0; i < kNttTableLen; i++) {
+            h[2 * dir * kNttTableLen + i] = fr30_arg_from_mont256(lo);
+            h[(2 * dir + 1) * kNttTableLen + i] = fr30_arg_from_mont256(hi);
+            lo = hf::fr_mul(lo, base);
+            hi = hf::fr_mul(hi, step_hi);
+        }
+    }
+    void* d = nullptr;
+    HIP_TRY(ctx, hipMalloc(&d, h.size() * sizeof(Fr30)));
+    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        ctx->last_error = std::string("hipMemcpy (ntt twiddles): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    ctx->d_ntt_tw = d;
+    return KZG_OK;
+}
+// enqueues the transform of 2^lg values on stream st: d_in -> d_out through the scratch buffers a, b (launch_ntt)
+static int enqueue_ntt(kzg_ctx* ctx, hipStream_t st, const uint32_t* d_in, uint32_t* d_out, uint32_t lg, bool inverse,
+                       uint32_t* d_a, uint32_t* d_b) {
+    hf::Fr c = hf::kFrOne;  // the last pass's multiplier: 1, or 1/n
+    if (inverse) {
+        hf::Fr n = hf::kFrOne;
+        for (uint32_t i = 0; i < lg; i++) n = hf::fr_add(n, n);
+        c = hf::fr_inv(n);
+    }
+    const Fr30 last_c = fr30_arg_from_mont256(c);
+    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw + (inverse ? 2 * kNttTableLen : 0);
+    launch_ntt(st, d_in, d_out, lg, tw, last_c, d_a, d_b);
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// Transforms that end in a slot's staging buffer use the slot's two polynomial buffers as the pass chain: with three
+// passes the chain is q -> stage -> q -> stage, otherwise stage (-> q) -> stage.  Host data goes in at ntt_slot_input.
+static uint32_t* ntt_slot_input(Slot& s, uint32_t lg) { return ntt_plan(lg).passes == 3 ? s.d_q : s.d_stage; }
+static int ntt_into_stage(kzg_ctx* ctx, Slot& s, const uint32_t* d_in, uint32_t lg, bool inverse) {
+    const bool three = ntt_plan(lg).passes == 3;
+    return enqueue_ntt(ctx, s.stream, d_in, s.d_stage, lg, inverse, three ? s.d_stage : s.d_q, s.d_q);
+}
+// a slot reserved by the caller, ready for a transform of n values (ctx->mu held, twiddles built)
+static int ntt_slot_ready(kzg_ctx* ctx, Slot& s, size_t n) {
+    int rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
+    return rc;
+}
+
+int kzg_domain_root(unsigned log_n, uint64_t out_mont[4]) {
+    if (!out_mont || log_n > 32) return KZG_ERR_INVALID_ARG;
+    const hf::Fr w = hf::fr_domain_root(log_n);
+    std::memcpy(out_mont, w.l, 32);
+    return KZG_OK;
+}
+
+int kzg_ntt(kzg_ctx* ctx, const uint64_t* in, size_t n, int inverse, uint64_t* out) {
+    uint32_t lg = 0;
+    if (!ctx || !in || !out || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_ntt(multi_kid(ctx->multi, 0), in, n, inverse, out);  // needs no SRS
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ntt_slot_ready(ctx, s, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ntt_slot_input(s, lg), in, n * 32, hipMemcpyHostToDevice, s.stream));
+    rc = ntt_into_stage(ctx, s, ntt_slot_input(s, lg), lg, inverse != 0);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, s.d_stage, n * 32, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    return KZG_OK;
+}
+
+int kzg_ntt_device(kzg_ctx* ctx, const void* d_in, void* d_out, size_t n, int inverse) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    uint32_t lg = 0;
+    if (!ctx || !d_in || !d_out || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ntt_slot_ready(ctx, s, n);
+    if (rc) return rc;
+    // the caller's buffers are neither of the slot's: d_in -> stage (-> q) -> d_out
+    rc = enqueue_ntt(ctx, s.stream, (const uint32_t*)d_in, (uint32_t*)d_out, lg, inverse != 0, s.d_stage, s.d_q);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    return KZG_OK;
+}
+
+int kzg_commit_evaluations_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    uint32_t lg = 0;
+    if (!ctx || !d_evals || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind != SLOT_IDLE) return KZG_ERR_BUSY;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc == KZG_OK) rc = ntt_slot_ready(ctx, s, n);
+    if (rc == KZG_OK) rc = ntt_into_stage(ctx, s, (const uint32_t*)d_evals, lg, true);
+    if (rc) return rc;
+    // n above the SRS: the coefficients beyond it are checked on the device, as for kzg_commit_submit
+    return submit_commit_locked(ctx, slot, s.d_stage, 1, n, false);
+}
+
+// the synchronous host-pointer forms: upload -> inverse NTT -> kzg_commit's / kzg_open's submit, on a reserved slot
+static int evaluations_host(kzg_ctx* ctx, const uint64_t* evals, size_t n, uint32_t lg, const uint64_t* z, const uint64_t* y,
+                            uint64_t out_p1[18]) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ntt_slot_ready(ctx, s, n);
+    if (rc) return rc;
+    uint32_t* dst = ntt_slot_input(s, lg);
+    lk.unlock();
+    const hipError_t e = hipMemcpyAsync(dst, evals, n * 32, hipMemcpyHostToDevice, s.stream);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMemcpyAsync (evaluations): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    rc = ntt_into_stage(ctx, s, dst, lg, true);
+    if (rc) return rc;
+    rc = z ? submit_open_locked(ctx, slot, s.d_stage, n, z, y, true)
+           : submit_commit_locked(ctx, slot, s.d_stage, 1, n, false, true);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    return wait_locked(ctx, slot, out_p1);
+}
+// a multi-device context: a replicated SRS forwards to one device, a range-split one cannot take a whole-domain transform
+static kzg_ctx* evaluations_kid(kzg_ctx* ctx, int* rc) {
+    if (multi_mode(ctx->multi) != kMultiReplicate) {
+        *rc = KZG_ERR_INVALID_ARG;
+        return nullptr;
+    }
+    if (!multi_srs_len(ctx->multi)) {
+        *rc = KZG_ERR_NO_SRS;
+        return nullptr;
+    }
+    return multi_kid(ctx->multi, 0);
+}
+
+int kzg_commit_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, uint64_t out_p1[18]) {
+    uint32_t lg = 0;
+    if (!ctx || !evals || !out_p1 || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = evaluations_kid(ctx, &rc);
+        return kid ? kzg_commit_evaluations(kid, evals, n, out_p1) : rc;
+    }
+    return evaluations_host(ctx, evals, n, lg, nullptr, nullptr, out_p1);
+}
+
+int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, const uint64_t z[4], const uint64_t y[4],
+                         uint64_t out_p1[18]) {
+    uint32_t lg = 0;
+    if (!ctx || !evals || !z || !y || !out_p1 || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = evaluations_kid(ctx, &rc);
+        return kid ? kzg_open_evaluations(kid, evals, n, z, y, out_p1) : rc;
+    }
+    return evaluations_host(ctx, evals, n, lg, z, y, out_p1);
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

@@ -146,6 +146,26 @@ void launch_uncompress(hipStream_t s, const void* d_compressed, uint32_t n, void
 // native table entries -> blst_p1 (Z = Montgomery one / all zero for infinity)
 void launch_affine_to_p1(hipStream_t s, const void* d_affine, uint32_t n, void* d_p1_out);
 
+// ---- ntt_kernels.hip: NTT over the subgroup of 2^k-th roots of unity, natural order in and out, x 2^256 form ----------
+struct Fr30;
+constexpr uint32_t kNttMaxLog = 22;        // largest domain (the largest SRS)
+constexpr uint32_t kNttTableLen = 2048;    // entries of each twiddle table (lo: w^i, hi: w^(2048 i), w = w_(2^22))
+constexpr uint32_t kNttTileLog = 11;       // values per workgroup tile (nine LDS digit planes: 72 KiB)
+constexpr uint32_t kNttTile = 1u << kNttTileLog;
+constexpr uint32_t kNttMaxRadixLog = 9;    // radix of a pass when there are several (tile = 2^(11 - m) runs of 2^m values)
+struct NttPlan {
+    uint32_t passes;
+    uint32_t m[3];  // log radix of each pass
+};
+NttPlan ntt_plan(uint32_t log_n);
+// raises the dynamic-LDS limit of the pass kernel on the current device; false when refused
+bool ntt_prepare_device();
+// d_tw: the direction's lo[2048] then hi[2048] tables (Fr30, multiplier form); last_c: the multiplier of the last pass in
+// the same form (1, or 1/n for the inverse).  Pass i < passes - 1 writes d_buf_a (i even) or d_buf_b (i odd), the last
+// pass writes d_out.  No intermediate may alias the buffer its pass reads; d_in == d_out only for a single pass.
+void launch_ntt(hipStream_t s, const uint32_t* d_in, uint32_t* d_out, uint32_t log_n, const void* d_tw, const Fr30& last_c,
+                uint32_t* d_buf_a, uint32_t* d_buf_b);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

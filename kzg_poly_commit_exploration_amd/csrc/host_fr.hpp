@@ -106,6 +106,20 @@ inline Fr fr_inv(const Fr& a) {
     }
     return acc;
 }
+// w_n for n = 2^log_n (log_n <= 32): 7^((r - 1) / n), 7 the multiplicative generator of blst / c-kzg / EIP-4844.
+// r - 1 = 2^32 t with t odd: w_(2^32) = 7^t, then 32 - log_n squarings.
+inline Fr fr_domain_root(unsigned log_n) {
+    static const uint64_t t[4] = {0xfffe5bfeffffffffULL, 0x09a1d80553bda402ULL, 0x299d7d483339d808ULL, 0x0000000073eda753ULL};
+    Fr seven = kFrOne;
+    for (int i = 0; i < 6; i++) seven = fr_add(seven, kFrOne);
+    Fr acc = kFrOne;
+    for (int i = 255; i >= 0; --i) {
+        acc = fr_mul(acc, acc);
+        if ((t[i >> 6] >> (i & 63)) & 1) acc = fr_mul(acc, seven);
+    }
+    for (unsigned i = log_n; i < 32; i++) acc = fr_mul(acc, acc);
+    return acc;
+}
 // the barycentric weights of k <= 64 distinct points: w_i = 1 / prod_{j != i} (z_i - z_j).  false when two points coincide.
 inline bool fr_point_weights(const Fr* zs, size_t k, Fr* ws) {
     for (size_t i = 0; i < k; ++i) {

@@ -248,6 +248,35 @@ int kzg_commit_evaluations_submit(kzg_ctx* ctx, int slot, const void* d_evals, s
 int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, const uint64_t z[4], const uint64_t y[4],
                          uint64_t out_p1[18]);
 
+/* ---- every cell of a domain and its multiproof ----------------------------------------------
+ * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
+ * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what
+ * kzg_open_points returns for its l points and values (for l = 1: kzg_open's at w_N^j), all N / l of them from one
+ * call: the quotients are stride-l synthetic divisions on the device and the proofs batched MSMs over the SRS.
+ * n' = n without trailing zeros.  Errors: log_domain > KZG_NTT_MAX_LOG, log_cell > KZG_MAX_CELL_LOG, log_cell >
+ *   log_domain, n > N, a required pointer NULL (evaluations: n not a power of two) -> KZG_ERR_INVALID_ARG; then no SRS
+ *   -> KZG_ERR_NO_SRS; n' - l > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH.  n' <= l gives infinity proofs, n = 0 zero cells
+ *   too; there is no constant-polynomial error.  Thread-safe on one context like the other host-pointer calls.
+ * Sampling specs list the N values in bit-reversed order (brp_b: b-bit bit reversal, K = log_domain, t = log_cell):
+ *   their cell c (positions c l .. c l + l - 1) is this API's cell brp_(K-t)(c), its values are out_cells of that cell
+ *   in brp_t(i) order, and its proof is identical.  Nothing is bit-reversed at the boundary (as for kzg_ntt).
+ * Multi-device contexts: a replicated SRS forwards the call to one device; a range-split SRS returns
+ *   KZG_ERR_INVALID_ARG (kzg_last_error says why).  kzg_quotient_cells runs on devices[0]. */
+#define KZG_MAX_CELL_LOG 6 /* l <= 64 = KZG_MAX_OPEN_POINTS */
+/* P by coefficients (n x blst_fr, Montgomery), N = 2^log_domain, l = 2^log_cell.
+ * out_cells (may be NULL): N x 4 u64, cell-major: out_cells[4 (j l + i) ..] = P(w_N^(j + (N/l) i)).
+ * out_proofs: (N/l) x 18 u64 (blst_p1, normalised like kzg_open's output, all-zero = infinity). */
+int kzg_cells_and_proofs(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, unsigned log_domain, unsigned log_cell,
+                         uint64_t* out_cells, uint64_t* out_proofs);
+/* P by its values over the n-domain (n a power of two <= N, natural order, as kzg_commit_evaluations takes them),
+ * extended to N on the device */
+int kzg_cells_and_proofs_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, unsigned log_domain,
+                                     unsigned log_cell, uint64_t* out_cells, uint64_t* out_proofs);
+/* test hook, like kzg_quotient_points: quotients of cells [first_cell, first_cell + count), cell c at
+ * out_q + 4 (c - first_cell) (n - l); *out_qn = max(n' - l, 0) (entries past it are zero); no SRS needed */
+int kzg_quotient_cells(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, unsigned log_domain, unsigned log_cell,
+                       size_t first_cell, size_t count, uint64_t* out_q, size_t* out_qn);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

@@ -243,4 +243,47 @@ struct Evaluations {
     }
 };
 
+// Every cell of the domain of N = 2^log_domain points and its multiproof (kzg_cells_and_proofs): cell j holds the
+// l = 2^log_cell values P(w_N^(j + (N/l) i)), i < l, at values[j l + i]; proofs[j] is kzg_open_points' proof for them.
+struct Cells {
+    std::vector<Scalar> values;
+    std::vector<G1Point> proofs;
+    static Cells of(const Polynomial& polynomial, unsigned log_domain, unsigned log_cell, const SetupArtifacts& setup) {
+        const auto& c = polynomial.coefficients();
+        Cells out = sized(log_domain, log_cell);
+        check(kzg_cells_and_proofs(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), c.size(), log_domain, log_cell,
+                                   reinterpret_cast<uint64_t*>(out.values.data()), out.proofs.front().p1.data()), setup.ctx());
+        return out;
+    }
+    // P by its values over the domain of values.size() points (a power of two <= N)
+    static Cells of_evaluations(const std::vector<Scalar>& values, unsigned log_domain, unsigned log_cell, const SetupArtifacts& setup) {
+        Cells out = sized(log_domain, log_cell);
+        check(kzg_cells_and_proofs_evaluations(setup.ctx(), reinterpret_cast<const uint64_t*>(values.data()), values.size(),
+                                               log_domain, log_cell, reinterpret_cast<uint64_t*>(out.values.data()),
+                                               out.proofs.front().p1.data()), setup.ctx());
+        return out;
+    }
+    // the quotients of cells [first_cell, first_cell + count), n' - l coefficients each, e.g. to check them element-wise
+    static std::vector<std::vector<Scalar>> quotients(const Polynomial& polynomial, unsigned log_domain, unsigned log_cell,
+                                                      size_t first_cell, size_t count, const SetupArtifacts& setup) {
+        const auto& c = polynomial.coefficients();
+        const size_t l = (size_t)1 << log_cell, stride = c.size() > l ? c.size() - l : 0;
+        std::vector<Scalar> q(count * stride + 1);
+        size_t qn = 0;
+        check(kzg_quotient_cells(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), c.size(), log_domain, log_cell,
+                                 first_cell, count, reinterpret_cast<uint64_t*>(q.data()), &qn), setup.ctx());
+        std::vector<std::vector<Scalar>> out(count);
+        for (size_t j = 0; j < count; j++) out[j].assign(q.begin() + j * stride, q.begin() + j * stride + qn);
+        return out;
+    }
+
+  private:
+    static Cells sized(unsigned log_domain, unsigned log_cell) {
+        Cells out;
+        out.values.resize((size_t)1 << log_domain);
+        out.proofs.resize(log_cell <= log_domain ? (size_t)1 << (log_domain - log_cell) : 1);
+        return out;
+    }
+};
+
 }  // namespace kzg_api

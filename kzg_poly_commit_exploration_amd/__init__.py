@@ -51,10 +51,11 @@ ABI_SYMBOLS = [
     "kzg_g1_sum", "kzg_g1_compress", "kzg_srs_g2_at", "kzg_verify_proof", "kzg_verify_proof_batch", "kzg_set_timing", "kzg_get_times", "kzg_msm_config",
     "kzg_open_points", "kzg_open_points_submit", "kzg_quotient_points", "kzg_evaluate_points", "kzg_verify_points",
     "kzg_domain_root", "kzg_ntt", "kzg_ntt_device", "kzg_commit_evaluations", "kzg_commit_evaluations_submit",
-    "kzg_open_evaluations",
+    "kzg_open_evaluations", "kzg_cells_and_proofs", "kzg_cells_and_proofs_evaluations", "kzg_quotient_cells",
 ]
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
+KZG_MAX_CELL_LOG = 6
 
 
 class KzgError(Exception):
@@ -150,6 +151,9 @@ def load_library():
         "kzg_commit_evaluations": (i, [vp, vp, sz, vp]),
         "kzg_commit_evaluations_submit": (i, [vp, i, vp, sz]),
         "kzg_open_evaluations": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
+        "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
+        "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -458,6 +462,34 @@ class Engine:
         out = np.zeros((max(len(zs), 1), 4), dtype=np.uint64)
         _check(self._lib.kzg_evaluate_points(self._h, _ptr(a), a.shape[0], _ptr(zl), len(zs), _ptr(out)), self._h)
         return [Scalar.from_limbs(out[i]) for i in range(len(zs))]
+
+    # -- every cell of the domain of N = 2^log_domain points and its multiproof (cells of 2^log_cell points) --
+    def _cells(self, fn, values, log_domain, log_cell):
+        a = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        cells = np.zeros((1 << log_domain, 4), dtype=np.uint64)
+        proofs = np.zeros((max(1 << max(log_domain - log_cell, 0), 1), 18), dtype=np.uint64)
+        _check(fn(self._h, _ptr(a), a.shape[0], log_domain, log_cell, _ptr(cells), _ptr(proofs)), self._h)
+        return cells, [G1Point(p) for p in proofs[: 1 << max(log_domain - log_cell, 0)]]
+
+    def cells_and_proofs_limbs(self, coeffs, log_domain, log_cell):
+        """(cells, proofs): cells[j l + i] = P(w_N^(j + (N/l) i)) as an (N, 4) array, proofs[j] the multiproof of cell j"""
+        return self._cells(self._lib.kzg_cells_and_proofs, coeffs, log_domain, log_cell)
+
+    def cells_and_proofs_from_evaluations_limbs(self, evals, log_domain, log_cell):
+        """the same for P given by its values over the len(evals)-point domain (a power of two <= N)"""
+        return self._cells(self._lib.kzg_cells_and_proofs_evaluations, evals, log_domain, log_cell)
+
+    def quotient_cells_limbs(self, coeffs, log_domain, log_cell, first_cell=0, count=None):
+        """quotients of cells [first_cell, first_cell + count): an array (count, n' - l, 4)"""
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        n, l = a.shape[0], 1 << log_cell
+        if count is None:
+            count = (1 << log_domain >> log_cell) - first_cell
+        q = np.zeros((max(count, 1), max(n - l, 1), 4), dtype=np.uint64)
+        qn = C.c_size_t(0)
+        _check(self._lib.kzg_quotient_cells(self._h, _ptr(a), n, log_domain, log_cell, first_cell, count, _ptr(q), C.byref(qn)),
+               self._h)
+        return q[:count, : qn.value].copy()
 
     # -- polynomials in evaluation form over the domain {w^i} of size n = 2^k (natural order, see domain_root) --
     def _ntt(self, values, inverse):

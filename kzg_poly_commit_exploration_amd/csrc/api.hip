@@ -114,6 +114,13 @@ struct Slot {
     size_t pblock_words = 0;
     std::vector<uint32_t> pts_ys;  // the claims (8 words each)
     size_t pts_nq = 0;             // terms of the job's MSM (0: the proof is infinity once the claims hold)
+    // cells of a domain (kzg_cells_and_proofs): P for the whole call in d_cpoly (read by the sub-batches of every slot the call
+    // holds, after cells_ev), the chunk aggregates of the cell quotients in d_cagg
+    uint32_t* d_cpoly = nullptr;
+    size_t cpoly_cap = 0;
+    uint32_t* d_cagg = nullptr;
+    uint64_t cagg_words = 0;
+    hipEvent_t cells_ev = nullptr;
     // state of the job in flight
     SlotKind kind = SLOT_IDLE;
     size_t job_n = 0;
@@ -715,6 +722,9 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
         if (s.h_pvals) hipHostFree(s.h_pvals);
         hipFree(s.d_roots);
         hipFree(s.d_pblock);
+        hipFree(s.d_cpoly);
+        hipFree(s.d_cagg);
+        if (s.cells_ev) hipEventDestroy(s.cells_ev);
         for (auto& e : s.ev)
             if (e) hipEventDestroy(e);
         if (s.done) hipEventDestroy(s.done);
@@ -2082,6 +2092,262 @@ int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, const ui
         return kid ? kzg_open_evaluations(kid, evals, n, z, y, out_p1) : rc;
     }
     return evaluations_host(ctx, evals, n, lg, z, y, out_p1);
+}
+
+// ---- every cell of a domain and its multiproof (cell_kernels.hip) ---------------------------------
+// Cell j of the domain of N = 2^log_n points is {w_N^(j + (N/l) i) : i < l}, l = 2^log_l; its proof is the commitment to
+// q_j = (P - I_j) / (X^l - w_N^(j l)).  The call holds one slot for its whole length: P sits in that slot's d_cpoly, the cells
+// come from its stream, and the N/l quotients flow through it and any other free slot in sub-batches of at most
+// ctx->max_batch cells (one batched MSM each), the kernels of one sub-batch overlapping the MSMs of the others.
+namespace {
+struct CellsShape {
+    uint32_t log_n = 0, log_l = 0;
+    size_t N = 0, l = 0, cells = 0;
+};
+bool cells_shape(size_t n, unsigned log_domain, unsigned log_cell, CellsShape* sh) {
+    if (log_domain > kNttMaxLog || log_cell > KZG_MAX_CELL_LOG || log_cell > log_domain) return false;
+    sh->log_n = log_domain;
+    sh->log_l = log_cell;
+    sh->N = (size_t)1 << log_domain;
+    sh->l = (size_t)1 << log_cell;
+    sh->cells = sh->N >> log_cell;
+    return n <= sh->N;
+}
+// n without trailing zero coefficients
+size_t cells_trim(const uint64_t* c, size_t n) {
+    while (n > 0 && !(c[4 * (n - 1)] | c[4 * (n - 1) + 1] | c[4 * (n - 1) + 2] | c[4 * (n - 1) + 3])) n--;
+    return n;
+}
+}  // namespace
+
+// the slot's buffer for P (cap coefficients) and its hand-off event (ctx->mu held, slot owned by the caller)
+static int ensure_cells_poly(kzg_ctx* ctx, Slot& s, size_t cap) {
+    if (!s.cells_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&s.cells_ev, hipEventDisableTiming));
+    if (cap <= s.cpoly_cap && s.d_cpoly) return KZG_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    hipFree(s.d_cpoly);
+    s.d_cpoly = nullptr;
+    s.cpoly_cap = 0;
+    if (cap < 1024) cap = 1024;
+    HIP_TRY(ctx, hipMalloc(&s.d_cpoly, cap * 32));
+    s.cpoly_cap = cap;
+    return KZG_OK;
+}
+static int ensure_cells_agg(kzg_ctx* ctx, Slot& s, uint64_t words) {
+    if (words <= s.cagg_words && s.d_cagg) return KZG_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    hipFree(s.d_cagg);
+    s.d_cagg = nullptr;
+    s.cagg_words = 0;
+    HIP_TRY(ctx, hipMalloc(&s.d_cagg, words * 4));
+    s.cagg_words = words;
+    return KZG_OK;
+}
+// a host -> device copy on the slot's stream without the mutex
+static int copy_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, void* dst, const void* src, size_t bytes) {
+    if (!bytes) return KZG_OK;
+    lk.unlock();
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s.stream);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMemcpyAsync (cells): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+// the quotients of cells [first, first + polys) on slot `slot` (owned), then their batched MSM; P in s0.d_cpoly
+static int cells_submit(kzg_ctx* ctx, int slot, Slot& s0, const CellsShape& sh, size_t nq, size_t first, size_t polys) {
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_poly(ctx, s, polys * nq);
+    if (rc == KZG_OK) rc = ensure_cells_agg(ctx, s, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)polys));
+    if (rc) return rc;
+    if (&s != &s0) HIP_TRY(ctx, hipStreamWaitEvent(s.stream, s0.cells_ev, 0));
+    launch_cell_quotients(s.stream, s0.d_cpoly, (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first, (uint32_t)polys,
+                          ctx->d_ntt_tw, s.d_cagg, s.d_q, nq);
+    HIP_TRY(ctx, hipGetLastError());
+    return commit_batch_submit_locked(ctx, slot, s.d_q, nq, polys, nq, true);
+}
+// P sits in s0.d_cpoly: n_eff coefficients, zero up to N when the cells are wanted.  Cells first, then the proofs.
+static int cells_run(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot0, const CellsShape& sh, size_t n_eff,
+                     uint64_t* out_cells, uint64_t* out_proofs) {
+    Slot& s0 = ctx->slots[slot0];
+    HIP_TRY(ctx, hipEventRecord(s0.cells_ev, s0.stream));
+    int rc = KZG_OK;
+    if (out_cells) {
+        // forward NTT of P padded to N (d_cpoly -> stage, through q), gathered into cell-major order in q
+        rc = ensure_poly(ctx, s0, sh.N);
+        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.d_cpoly, sh.log_n, false);
+        if (rc) return rc;
+        launch_cells_gather(s0.stream, s0.d_stage, s0.d_q, sh.log_n, sh.log_l);
+        HIP_TRY(ctx, hipGetLastError());
+        lk.unlock();
+        hipError_t e = hipMemcpyAsync(out_cells, s0.d_q, sh.N * 32, hipMemcpyDeviceToHost, s0.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s0.stream);
+        lk.lock();
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("cells: ") + hipGetErrorString(e);
+            return KZG_ERR_HIP;
+        }
+    }
+    const size_t nq = n_eff > sh.l ? n_eff - sh.l : 0;
+    if (!nq) {  // P has at most l coefficients: it is its own interpolant on every cell
+        const hf::P1 inf = hf::p1_inf();
+        for (size_t j = 0; j < sh.cells; j++) write_p1(out_proofs + 18 * j, inf);
+        return KZG_OK;
+    }
+    const size_t chunk = host_batch_chunk(ctx, sh.cells, nq);
+    std::deque<BatchInFlight> fifo;
+    bool busy[kNumSlots] = {};
+    // keep: the slot stays the caller's (SLOT_RESERVED) for the next sub-batch; slot0 always does
+    auto collect_oldest = [&](bool keep) -> int {
+        const BatchInFlight b = fifo.front();
+        fifo.pop_front();
+        Slot& s = ctx->slots[b.slot];
+        await_unlocked(lk, s);
+        const int r = wait_batch_locked(ctx, b.slot, out_proofs + 18 * b.first_poly, b.polys);
+        busy[b.slot] = false;
+        if (keep || b.slot == slot0) s.kind = SLOT_RESERVED;  // (the mutex was held since wait_batch_locked marked it idle)
+        else release_owned(ctx, b.slot);
+        return r;
+    };
+    for (size_t at = 0; at < sh.cells && rc == KZG_OK; at += chunk) {
+        const size_t polys = sh.cells - at < chunk ? sh.cells - at : chunk;
+        int slot = busy[slot0] ? reserve_slot(ctx, lk, false) : slot0;
+        if (slot < 0) {
+            slot = fifo.front().slot;
+            rc = collect_oldest(true);
+            if (rc) {
+                if (slot != slot0) release_owned(ctx, slot);
+                break;
+            }
+        }
+        rc = cells_submit(ctx, slot, s0, sh, nq, at, polys);
+        if (rc) {
+            if (slot != slot0) release_owned(ctx, slot);
+            break;
+        }
+        busy[slot] = true;
+        fifo.push_back({slot, at, polys});
+    }
+    while (!fifo.empty()) {
+        const int r = collect_oldest(false);
+        if (rc == KZG_OK) rc = r;
+    }
+    return rc;
+}
+// the synchronous forms: P by coefficients (coeffs, n_eff trimmed) or by its values over the n-domain (evals, n)
+static int cells_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n_eff, const uint64_t* evals, size_t n, const CellsShape& sh,
+                      uint64_t* out_cells, uint64_t* out_proofs) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (!evals && n_eff > sh.l && n_eff - sh.l > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot0 = reserve_slot(ctx, lk, true);
+    if (slot0 < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot0};
+    Slot& s0 = ctx->slots[slot0];
+    rc = ensure_cells_poly(ctx, s0, sh.N);
+    if (rc) return rc;
+    if (evals) {
+        // values -> d_cpoly -> inverse NTT into stage -> back to d_cpoly; the coefficients also go to the host once, for n'
+        uint32_t lg = 0;
+        (void)ntt_log(n, &lg);
+        rc = ntt_slot_ready(ctx, s0, n);
+        if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s0, s0.d_cpoly, evals, n * 32);
+        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.d_cpoly, lg, true);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(s0.d_cpoly, s0.d_stage, n * 32, hipMemcpyDeviceToDevice, s0.stream));
+        std::vector<uint64_t> c(4 * n);
+        lk.unlock();
+        hipError_t e = hipMemcpyAsync(c.data(), s0.d_stage, n * 32, hipMemcpyDeviceToHost, s0.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s0.stream);
+        lk.lock();
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("cells (interpolation): ") + hipGetErrorString(e);
+            return KZG_ERR_HIP;
+        }
+        n_eff = cells_trim(c.data(), n);
+        if (n_eff > sh.l && n_eff - sh.l > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    } else {
+        rc = copy_unlocked(ctx, lk, s0, s0.d_cpoly, coeffs, n_eff * 32);
+        if (rc) return rc;
+    }
+    if (out_cells && n_eff < sh.N)
+        HIP_TRY(ctx, hipMemsetAsync(s0.d_cpoly + 8 * n_eff, 0, (sh.N - n_eff) * 32, s0.stream));
+    return cells_run(ctx, lk, slot0, sh, n_eff, out_cells, out_proofs);
+}
+// a multi-device context: a replicated SRS forwards to one device; a range-split one holds no device with the whole SRS
+static kzg_ctx* cells_kid(kzg_ctx* ctx, int* rc) {
+    if (multi_mode(ctx->multi) != kMultiReplicate) {
+        ctx->last_error = "cells: a range-split multi-device context cannot prove cells (replicate the SRS instead)";
+        *rc = KZG_ERR_INVALID_ARG;
+        return nullptr;
+    }
+    return multi_kid(ctx->multi, 0);
+}
+
+int kzg_cells_and_proofs(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, unsigned log_domain, unsigned log_cell,
+                         uint64_t* out_cells, uint64_t* out_proofs) {
+    CellsShape sh;
+    if (!ctx || !out_proofs || (!coeffs && n) || !cells_shape(n, log_domain, log_cell, &sh)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? kzg_cells_and_proofs(kid, coeffs, n, log_domain, log_cell, out_cells, out_proofs) : rc;
+    }
+    return cells_host(ctx, coeffs, n ? cells_trim(coeffs, n) : 0, nullptr, 0, sh, out_cells, out_proofs);
+}
+
+int kzg_cells_and_proofs_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, unsigned log_domain, unsigned log_cell,
+                                     uint64_t* out_cells, uint64_t* out_proofs) {
+    CellsShape sh;
+    uint32_t lg = 0;
+    if (!ctx || !evals || !out_proofs || !ntt_log(n, &lg) || !cells_shape(n, log_domain, log_cell, &sh)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? kzg_cells_and_proofs_evaluations(kid, evals, n, log_domain, log_cell, out_cells, out_proofs) : rc;
+    }
+    return cells_host(ctx, nullptr, 0, evals, n, sh, out_cells, out_proofs);
+}
+
+int kzg_quotient_cells(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, unsigned log_domain, unsigned log_cell, size_t first_cell,
+                       size_t count, uint64_t* out_q, size_t* out_qn) {
+    CellsShape sh;
+    if (!ctx || !out_qn || (!coeffs && n) || !cells_shape(n, log_domain, log_cell, &sh)) return KZG_ERR_INVALID_ARG;
+    if (first_cell > sh.cells || count > sh.cells - first_cell || (!out_q && n > sh.l && count)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_quotient_cells(multi_kid(ctx->multi, 0), coeffs, n, log_domain, log_cell, first_cell, count, out_q, out_qn);
+    const size_t n_eff = n ? cells_trim(coeffs, n) : 0;
+    const size_t nq = n_eff > sh.l ? n_eff - sh.l : 0;
+    *out_qn = 0;
+    if (n > sh.l && count) std::memset(out_q, 0, count * (n - sh.l) * 32);
+    if (!nq || !count) {
+        *out_qn = nq;
+        return KZG_OK;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ensure_slot_basics(ctx, s);  // needs no SRS
+    if (rc == KZG_OK) rc = ensure_cells_poly(ctx, s, n_eff);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, count * nq);
+    if (rc == KZG_OK) rc = ensure_cells_agg(ctx, s, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)count));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_cpoly, coeffs, n_eff * 32, hipMemcpyHostToDevice, s.stream));
+    launch_cell_quotients(s.stream, s.d_cpoly, (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first_cell, (uint32_t)count,
+                          ctx->d_ntt_tw, s.d_cagg, s.d_q, nq);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy2DAsync(out_q, (n - sh.l) * 32, s.d_q, nq * 32, nq * 32, count, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    *out_qn = nq;
+    return KZG_OK;
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

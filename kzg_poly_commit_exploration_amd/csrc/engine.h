@@ -166,6 +166,17 @@ bool ntt_prepare_device();
 void launch_ntt(hipStream_t s, const uint32_t* d_in, uint32_t* d_out, uint32_t log_n, const void* d_tw, const Fr30& last_c,
                 uint32_t* d_buf_a, uint32_t* d_buf_b);
 
+// ---- cell_kernels.hip: quotients of P by X^l - w_N^(j l) for the cells j of a domain of N = 2^log_n points, l = 2^log_l ----
+// cells [first_cell, first_cell + cells): q of cell first_cell + p at d_q + 8 p stride words, nq values each (nq = n' - l,
+// d_coeffs holds at least nq + l coefficients); d_tw: the context's forward NTT twiddles; d_agg: cells_agg_words() words
+uint32_t cells_chunk_log(uint32_t nq, uint32_t log_l);
+uint64_t cells_agg_words(uint32_t nq, uint32_t log_l, uint32_t cells);
+void launch_cell_quotients(hipStream_t s, const uint32_t* d_coeffs, uint32_t nq, uint32_t log_n, uint32_t log_l,
+                           uint32_t first_cell, uint32_t cells, const void* d_tw, uint32_t* d_agg, uint32_t* d_q,
+                           uint64_t stride);
+// out[j l + i] = evals[j + (N / l) i] (N values)
+void launch_cells_gather(hipStream_t s, const uint32_t* d_evals, uint32_t* d_out, uint32_t log_n, uint32_t log_l);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

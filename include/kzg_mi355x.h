@@ -277,6 +277,30 @@ int kzg_cells_and_proofs_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont
 int kzg_quotient_cells(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, unsigned log_domain, unsigned log_cell,
                        size_t first_cell, size_t count, uint64_t* out_q, size_t* out_qn);
 
+/* ---- every cell proof of many polynomials by FK20 -------------------------------------------
+ * kzg_cells_and_proofs for `batch` polynomials of n coefficients (polynomial b at coeffs + 4*b*stride_coeffs), by FK20:
+ * the N/l proofs are a G1 DFT of size N/l of l Toeplitz products, O(n log n) group operations instead of N (n - l) / l
+ * MSM terms.  out_cells (may be NULL): batch x N x 4 u64; out_proofs: batch x (N/l) x 18 u64.
+ * Every output equals what kzg_cells_and_proofs returns for that polynomial, bit for bit, error codes included (n' per
+ * polynomial; a degree error anywhere fails the whole call and kzg_last_error names the polynomial).  batch = 0 does
+ * nothing; stride_coeffs < n with batch > 1 -> KZG_ERR_INVALID_ARG.  One exception to the cells call's acceptance: a
+ * shape whose circulant length L (the power of two >= 2 ceil(n_max / l), n_max the largest n' of the batch) exceeds
+ * 2^22 = the largest root of the twiddle tables returns KZG_ERR_INVALID_ARG; that needs l = 1 and n' > 2^21.
+ * The SRS-side transforms for (L, l) are built on first use (or by kzg_fk20_prepare) and kept per context, one shape at
+ * a time, until the SRS is replaced: l L x 256 B of transforms, plus their comb tables (l L x 64 KiB: 512 MiB at n = 4096,
+ * l = 64) when those fit KZG_FK20_TABLE_MB, by default a quarter of the free device memory up to 16 GiB.  Larger shapes
+ * build the comb tables per call, 8192 bases at a time, and free them again; no size is refused for memory.  A kept
+ * transform of the same l and up to twice the needed L serves shorter polynomials without a rebuild.  Thread-safe: FK20
+ * calls on one context run one after the other, other calls go on while one waits for the device. */
+int kzg_cells_and_proofs_fk20(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t batch, size_t stride_coeffs,
+                              unsigned log_domain, unsigned log_cell, uint64_t* out_cells, uint64_t* out_proofs);
+/* optional: build the SRS-side cache for polynomials of n coefficients and cells of 2^log_cell points now */
+int kzg_fk20_prepare(kzg_ctx* ctx, size_t n, unsigned log_cell);
+/* test hook: DFT (inverse != 0: inverse DFT incl. 1/m) of m = 2^k <= 2^22 host blst_p1 points over w_m, normalised
+ * output (out_p1[j] = sum_i [w_m^(i j)] in_p1[i]); needs no SRS.  The points must lie in G1 (the order-r subgroup): the
+ * twiddle products use the endomorphism (x, y) -> (beta x, y) = [z^2 - 1](x, y), which holds there only; nothing checks it */
+int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint64_t* out_p1);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

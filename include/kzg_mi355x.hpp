@@ -8,6 +8,7 @@
 //   Evaluation::generate_proof  src/polynomial.rs:260-269
 // Errors are thrown as kzg::Error carrying the reference's anyhow message (kzg_strerror).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -275,6 +276,33 @@ struct Cells {
         std::vector<std::vector<Scalar>> out(count);
         for (size_t j = 0; j < count; j++) out[j].assign(q.begin() + j * stride, q.begin() + j * stride + qn);
         return out;
+    }
+
+    // the same for many polynomials at once by FK20 (kzg_cells_and_proofs_fk20): every result equals of()'s for that
+    // polynomial; the polynomials may differ in length (each is zero-padded to the longest)
+    static std::vector<Cells> of_many_fk20(const std::vector<Polynomial>& polynomials, unsigned log_domain, unsigned log_cell,
+                                           const SetupArtifacts& setup) {
+        size_t n = 0;
+        for (const auto& p : polynomials) n = p.coefficients().size() > n ? p.coefficients().size() : n;
+        std::vector<Scalar> c(polynomials.size() * n + 1, Scalar{});
+        for (size_t b = 0; b < polynomials.size(); b++)
+            std::copy(polynomials[b].coefficients().begin(), polynomials[b].coefficients().end(), c.begin() + b * n);
+        const size_t N = (size_t)1 << log_domain, M = log_cell <= log_domain ? N >> log_cell : 1;
+        std::vector<Scalar> values(polynomials.size() * N + 1);
+        std::vector<G1Point> proofs(polynomials.size() * M + 1);
+        check(kzg_cells_and_proofs_fk20(setup.ctx(), reinterpret_cast<const uint64_t*>(c.data()), n, polynomials.size(), n,
+                                        log_domain, log_cell, reinterpret_cast<uint64_t*>(values.data()),
+                                        proofs.front().p1.data()), setup.ctx());
+        std::vector<Cells> out(polynomials.size());
+        for (size_t b = 0; b < polynomials.size(); b++) {
+            out[b].values.assign(values.begin() + b * N, values.begin() + (b + 1) * N);
+            out[b].proofs.assign(proofs.begin() + b * M, proofs.begin() + (b + 1) * M);
+        }
+        return out;
+    }
+    // builds the SRS-side FK20 transforms for polynomials of n coefficients now (otherwise the first call does)
+    static void prepare_fk20(size_t n, unsigned log_cell, const SetupArtifacts& setup) {
+        check(kzg_fk20_prepare(setup.ctx(), n, log_cell), setup.ctx());
     }
 
   private:

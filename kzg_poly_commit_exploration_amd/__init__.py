@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "kzg_open_points", "kzg_open_points_submit", "kzg_quotient_points", "kzg_evaluate_points", "kzg_verify_points",
     "kzg_domain_root", "kzg_ntt", "kzg_ntt_device", "kzg_commit_evaluations", "kzg_commit_evaluations_submit",
     "kzg_open_evaluations", "kzg_cells_and_proofs", "kzg_cells_and_proofs_evaluations", "kzg_quotient_cells",
+    "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft",
 ]
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
@@ -154,6 +155,9 @@ def load_library():
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
+        "kzg_cells_and_proofs_fk20": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp, vp]),
+        "kzg_fk20_prepare": (i, [vp, sz, C.c_uint]),
+        "kzg_g1_dft": (i, [vp, vp, sz, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -478,6 +482,33 @@ class Engine:
     def cells_and_proofs_from_evaluations_limbs(self, evals, log_domain, log_cell):
         """the same for P given by its values over the len(evals)-point domain (a power of two <= N)"""
         return self._cells(self._lib.kzg_cells_and_proofs_evaluations, evals, log_domain, log_cell)
+
+    def cells_and_proofs_fk20(self, coeffs, log_domain, log_cell, cells=True):
+        """FK20 for a batch: coeffs is a (batch, n, 4) array (or one (n, 4) polynomial).  Returns (cells, proofs):
+        cells a (batch, N, 4) array (None when cells=False), proofs[b][j] the multiproof of cell j of polynomial b --
+        each equal to what cells_and_proofs_limbs returns for that polynomial"""
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if a.ndim != 3:
+            a = a.reshape(1, a.size // 4, 4)
+        batch, n = a.shape[0], a.shape[1]
+        M = 1 << max(log_domain - log_cell, 0)
+        out_cells = np.zeros((batch, 1 << log_domain, 4), dtype=np.uint64) if cells else None
+        proofs = np.zeros((max(batch, 1), M, 18), dtype=np.uint64)
+        _check(self._lib.kzg_cells_and_proofs_fk20(self._h, _ptr(a), n, batch, n, log_domain, log_cell,
+                                                   _ptr(out_cells) if cells else None, _ptr(proofs)), self._h)
+        return out_cells, [[G1Point(p) for p in proofs[b]] for b in range(batch)]
+
+    def fk20_prepare(self, n, log_cell):
+        """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""
+        _check(self._lib.kzg_fk20_prepare(self._h, n, log_cell), self._h)
+
+    def g1_dft(self, points, inverse=False):
+        """DFT of m = 2^k G1 points (G1Point or blst_p1 rows) over w_m: out[j] = sum_i [w_m^(i j)] points[i];
+        inverse: the inverse transform, 1/m included"""
+        a = np.ascontiguousarray([p.p1 if isinstance(p, G1Point) else p for p in points], dtype=np.uint64).reshape(-1, 18)
+        out = np.zeros_like(a)
+        _check(self._lib.kzg_g1_dft(self._h, _ptr(a), a.shape[0], 1 if inverse else 0, _ptr(out)), self._h)
+        return [G1Point(p) for p in out]
 
     def quotient_cells_limbs(self, coeffs, log_domain, log_cell, first_cell=0, count=None):
         """quotients of cells [first_cell, first_cell + count): an array (count, n' - l, 4)"""

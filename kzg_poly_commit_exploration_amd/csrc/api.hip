@@ -171,6 +171,18 @@ struct kzg_ctx {
     bool small_msm_off = false;              // KZG_SMALL_MSM=0: small jobs take the general multi-launch path (A/B, tests)
     bool slots_ready = false;
     bool timing = false;
+    // FK20 (kzg_cells_and_proofs_fk20), all under fk20_mu (taken before mu): the GLV-split twiddles
+    // of w_(2^glv_log), built on first use and grown; the SRS side of one shape (L = 2^fk20_log_L, l = 2^fk20_log_l): the
+    // transforms DFT_L(S_r) in d_fk20_B and, when they fit the budget, their comb tables in d_fk20_tab (both dropped with
+    // the SRS); workspaces grown on demand
+    std::mutex fk20_mu;
+    void* d_glv = nullptr;
+    uint32_t glv_log = 0;
+    void* d_fk20_B = nullptr;
+    void* d_fk20_tab = nullptr;
+    uint32_t fk20_log_L = 0, fk20_log_l = 0;
+    void* fk20_ws[11] = {};
+    size_t fk20_ws_bytes[11] = {};
 };
 
 namespace {
@@ -365,6 +377,11 @@ int srs_prepare(kzg_ctx* ctx, size_t n) {
     if (ctx->d_table) {
         hipFree(ctx->d_table);
         ctx->d_table = nullptr;
+    }
+    if (ctx->d_fk20_B) {  // the FK20 cache holds transforms of the old SRS
+        hipFree(ctx->d_fk20_B);
+        hipFree(ctx->d_fk20_tab);
+        ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
     }
     ctx->n = 0;
     // The opt-in NAF recoding wants a 255-level table (engine.h); it may take up to 60 % of the HBM that is free
@@ -735,6 +752,10 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     if (ctx->heavy_stream) hipStreamDestroy(ctx->heavy_stream);
     if (ctx->d_table) hipFree(ctx->d_table);
     if (ctx->d_ntt_tw) hipFree(ctx->d_ntt_tw);
+    if (ctx->d_glv) hipFree(ctx->d_glv);
+    if (ctx->d_fk20_B) hipFree(ctx->d_fk20_B);
+    if (ctx->d_fk20_tab) hipFree(ctx->d_fk20_tab);
+    for (void* p : ctx->fk20_ws) hipFree(p);
     delete ctx;
 }
 
@@ -2348,6 +2369,369 @@ int kzg_quotient_cells(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, unsigned 
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     *out_qn = nq;
     return KZG_OK;
+}
+
+// ---- FK20: every cell proof of a batch of polynomials through G1 DFTs (fk20_kernels.hip) ----------
+// The call holds the context's mutex and one slot (for its stream and the cells' NTT buffers) for its whole length: other
+// calls on the context wait for it, and an SRS replacement waits for the slot like for any other call.
+namespace {
+// lambda = z^2 - 1, z = -0xd201000000010000: [lambda](x, y) = (beta x, y) on G1 (fk20_kernels.hip), r = lambda^2 + lambda + 1
+const unsigned __int128 kGlvLambda = ((unsigned __int128)0xac45a4010001a402ULL << 64) | 0x00000000ffffffffULL;
+// w (blst_fr, Montgomery) = k1 + k2 lambda with k1 = w mod lambda, k2 = w div lambda: both below 2^128 since w < r
+Glv glv_split(const hf::Fr& mont) {
+    const hf::Fr one_raw = {{1, 0, 0, 0}};
+    const hf::Fr v = hf::fr_mul(mont, one_raw);  // the plain integer
+    unsigned __int128 rem = 0, q = 0;
+    for (int bit = 255; bit >= 0; bit--) {
+        const bool over = (uint64_t)(rem >> 127) != 0;  // rem << 1 leaves 128 bits: it is above lambda then
+        rem = (rem << 1) | ((v.l[bit >> 6] >> (bit & 63)) & 1);
+        q <<= 1;
+        if (over || rem >= kGlvLambda) {
+            rem -= kGlvLambda;
+            q |= 1;
+        }
+    }
+    Glv g;
+    g.k1[0] = (uint64_t)rem;
+    g.k1[1] = (uint64_t)(rem >> 64);
+    g.k2[0] = (uint64_t)q;
+    g.k2[1] = (uint64_t)(q >> 64);
+    return g;
+}
+hf::Fr fr_pow2(uint32_t lg) {
+    hf::Fr v = hf::kFrOne;
+    for (uint32_t i = 0; i < lg; i++) v = hf::fr_add(v, v);
+    return v;
+}
+enum : int { kWsCoef = 0, kWsScalA, kWsScalB, kWsPart, kWsX1, kWsX2, kWsX3, kWsAff, kWsPrefix, kWsP1, kWsCount };
+constexpr size_t kFk20MaxBatch = 64;              // polynomials per pass through the workspaces, at most
+constexpr size_t kFk20WsBudget = (size_t)4 << 30;  // ... and fewer when their workspaces would pass this
+constexpr uint32_t kFk20CombChunk = 8192;         // bases per comb-table launch (XYZZ temporaries: 1 GiB) and per streamed chunk
+uint32_t log2_ceil(size_t v) {
+    uint32_t k = 0;
+    while (((size_t)1 << k) < v) k++;
+    return k;
+}
+// what the comb tables of all l L bases may occupy to be kept: KZG_FK20_TABLE_MB, else a quarter of the free memory up to
+// 16 GiB.  Above it the tables are built per call, a chunk of positions at a time, and freed again.
+size_t fk20_table_budget() {
+    if (const char* v = std::getenv("KZG_FK20_TABLE_MB")) return (size_t)std::strtoull(v, nullptr, 10) << 20;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const size_t cap = (size_t)16 << 30;
+    return free_b / 4 < cap ? free_b / 4 : cap;
+}
+}  // namespace
+
+static int fk20_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
+    if (bytes > ctx->fk20_ws_bytes[i] || !ctx->fk20_ws[i]) {
+        hipFree(ctx->fk20_ws[i]);
+        ctx->fk20_ws[i] = nullptr;
+        ctx->fk20_ws_bytes[i] = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->fk20_ws[i], bytes ? bytes : 256));
+        ctx->fk20_ws_bytes[i] = bytes;
+    }
+    *out = ctx->fk20_ws[i];
+    return KZG_OK;
+}
+// waits for the stream without ctx->mu, so that the context's other calls go on meanwhile (the caller's slot keeps an
+// SRS replacement out, fk20_mu the other FK20 calls)
+static int fk20_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(st);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("fk20: ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+// the split twiddles w_(2^lg)^e, e < 2^lg, for every transform of at most 2^lg points (device current)
+static int ensure_glv(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, uint32_t lg, hipStream_t st) {
+    if (lg < 1) lg = 1;
+    if (ctx->d_glv && ctx->glv_log >= lg) return KZG_OK;
+    const size_t len = (size_t)1 << lg;
+    std::vector<Glv> h(len);
+    const hf::Fr w = hf::fr_domain_root(lg);
+    hf::Fr v = hf::kFrOne;
+    for (size_t e = 0; e < len; e++) {
+        h[e] = glv_split(v);
+        v = hf::fr_mul(v, w);
+    }
+    int rc = fk20_sync(ctx, lk, st);  // nothing in flight reads the old table
+    if (rc) return rc;
+    hipFree(ctx->d_glv);
+    ctx->d_glv = nullptr;
+    HIP_TRY(ctx, hipMalloc(&ctx->d_glv, len * sizeof(Glv)));
+    ctx->glv_log = lg;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glv, h.data(), len * sizeof(Glv), hipMemcpyHostToDevice, st));
+    return fk20_sync(ctx, lk, st);  // h goes out of scope
+}
+// comb tables of bases [first, first + count) ((i, r) order) into dst, through tmp / prefix (kFk20CombChunk bases each)
+static void enqueue_comb(kzg_ctx* ctx, hipStream_t st, uint32_t log_L, uint32_t log_l, uint64_t first, uint64_t count,
+                         void* dst, void* tmp, void* prefix) {
+    for (uint64_t f = 0; f < count; f += kFk20CombChunk) {
+        const uint32_t c = (uint32_t)(count - f < kFk20CombChunk ? count - f : kFk20CombChunk);
+        launch_fk20_comb(st, ctx->d_fk20_B, log_L, log_l, first + f, c, tmp);
+        launch_xyzz_to_affine(st, tmp, c * kFk20CombEntries, (char*)dst + f * kFk20CombEntries * kAffineBytes, prefix);
+    }
+}
+// the SRS side of (L, l): B_r = DFT_L(S_r), r < l, and their comb tables when they fit fk20_table_budget()
+static int ensure_fk20_table(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, uint32_t log_L, uint32_t log_l) {
+    if (ctx->d_fk20_B && ctx->fk20_log_L == log_L && ctx->fk20_log_l == log_l) return KZG_OK;
+    int rc = fk20_sync(ctx, lk, st);
+    if (rc) return rc;
+    hipFree(ctx->d_fk20_B);
+    hipFree(ctx->d_fk20_tab);
+    ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
+    const size_t bases = (size_t)1 << (log_L + log_l);
+    const size_t tab_bytes = bases * kFk20CombEntries * kAffineBytes;
+    DevBuf S, B1, B2;
+    HIP_TRY(ctx, hipMalloc(&S.p, bases * kXyzzBytes));
+    HIP_TRY(ctx, hipMalloc(&B1.p, bases * kXyzzBytes));
+    HIP_TRY(ctx, hipMalloc(&B2.p, bases * kXyzzBytes));
+    launch_fk20_srs_gather(st, ctx->d_table, ctx->n, log_L, log_l, S.p);
+    const void* B = launch_g1_dft(st, S.p, B1.p, B2.p, log_L, (uint64_t)1 << log_l, (const Glv*)ctx->d_glv, ctx->glv_log, false);
+    ctx->d_fk20_B = (B == B1.p) ? B1.p : B2.p;
+    (B == B1.p ? B1.p : B2.p) = nullptr;  // kept
+    ctx->fk20_log_L = log_L;
+    ctx->fk20_log_l = log_l;
+    if (tab_bytes <= fk20_table_budget()) {
+        void* tab = nullptr;
+        if (hipMalloc(&tab, tab_bytes) == hipSuccess) {
+            DevBuf tmp, prefix;
+            const size_t chunk = bases < kFk20CombChunk ? bases : kFk20CombChunk;
+            HIP_TRY(ctx, hipMalloc(&tmp.p, chunk * kFk20CombEntries * kXyzzBytes));
+            HIP_TRY(ctx, hipMalloc(&prefix.p, chunk * kFk20CombEntries * 64));
+            ctx->d_fk20_tab = tab;
+            enqueue_comb(ctx, st, log_L, log_l, 0, bases, tab, tmp.p, prefix.p);
+            HIP_TRY(ctx, hipGetLastError());
+            return fk20_sync(ctx, lk, st);  // before the temporaries go
+        }
+        (void)hipGetLastError();  // no room after all: the tables are streamed per call
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return fk20_sync(ctx, lk, st);
+}
+// shape of the Toeplitz step for polynomials of at most n' coefficients (n' > l): m = ceil(n' / l), L = 2^log_L >= 2m
+static bool fk20_shape(kzg_ctx* ctx, size_t n_max, uint32_t log_l, uint32_t* m, uint32_t* log_L) {
+    const size_t mm = (n_max + ((size_t)1 << log_l) - 1) >> log_l;
+    *m = (uint32_t)mm;
+    *log_L = log2_ceil(2 * mm);
+    if (*log_L > kNttMaxLog) {
+        ctx->last_error = "fk20: the circulant of this shape would exceed 2^22 points (l = 1 with n' > 2^21)";
+        return false;
+    }
+    // any L >= 2m works: a cached transform of the same l up to twice as long serves instead of being rebuilt
+    if (ctx->d_fk20_B && ctx->fk20_log_l == log_l && ctx->fk20_log_L >= *log_L && ctx->fk20_log_L <= *log_L + 1)
+        *log_L = ctx->fk20_log_L;
+    return true;
+}
+// positions per streamed chunk when the comb tables are not kept
+static uint32_t fk20_stream_positions(uint32_t log_L, uint32_t log_l) {
+    const uint32_t ci = kFk20CombChunk >> log_l;
+    return ci < (1u << log_L) ? ci : (1u << log_L);
+}
+
+// `batch` polynomials (coefficients at c, n_max per polynomial, contiguous) -> proofs (batch x 2^log_M blst_p1)
+static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const uint64_t* coeffs, size_t stride,
+                       size_t batch, size_t n_max, uint32_t m, uint32_t log_L, uint32_t log_l, uint32_t log_M,
+                       uint64_t* out_proofs, void* stream_tab, void* stream_tmp, void* stream_prefix) {
+    const size_t L = (size_t)1 << log_L, l = (size_t)1 << log_l, M = (size_t)1 << log_M;
+    const size_t X = L > M ? L : M;
+    const bool kept = ctx->d_fk20_tab != nullptr;
+    const uint32_t ci = kept ? (uint32_t)L : fk20_stream_positions(log_L, log_l);
+    void *coef, *sa, *sb, *part, *x1, *x2, *x3, *aff, *prefix, *p1;
+    int rc = fk20_ws(ctx, kWsCoef, batch * n_max * 32, &coef);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsScalA, batch * l * L * 32, &sa);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsScalB, batch * l * L * 32, &sb);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPart, l > 1 ? batch * l * ci * kXyzzBytes : 0, &part);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX1, batch * X * kXyzzBytes, &x1);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX2, batch * X * kXyzzBytes, &x2);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX3, batch * X * kXyzzBytes, &x3);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsAff, batch * M * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPrefix, batch * M * 64, &prefix);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsP1, batch * M * 144, &p1);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, coeffs, stride * 32, n_max * 32, batch, hipMemcpyHostToDevice, st));
+    const Fr30 inv_L = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(log_L)));
+    const uint32_t* scal = launch_fk20_fr_side(st, (const uint32_t*)coef, (uint32_t)n_max, m, log_L, log_l, batch, ctx->d_ntt_tw,
+                                               inv_L, (uint32_t*)sa, (uint32_t*)sb);
+    if (kept) {
+        launch_fk20_pointwise(st, scal, ctx->d_fk20_tab, log_L, log_l, 0, (uint32_t)L, batch, part, x1);
+    } else {  // the comb tables of one chunk of positions at a time
+        for (uint32_t i0 = 0; i0 < L; i0 += ci) {
+            enqueue_comb(ctx, st, log_L, log_l, (uint64_t)i0 << log_l, (uint64_t)ci << log_l, stream_tab, stream_tmp, stream_prefix);
+            launch_fk20_pointwise(st, scal, stream_tab, log_L, log_l, i0, ci, batch, part, x1);
+        }
+    }
+    const Glv* tw = (const Glv*)ctx->d_glv;
+    const void* conv = launch_g1_dft(st, x1, x2, x3, log_L, batch, tw, ctx->glv_log, true);  // 1/L went into the scalars
+    // log_L >= 2: conv is x2 or x3; the second DFT ping-pongs through x1 and conv, free once the selection has read it
+    void* h = conv == x2 ? x3 : x2;
+    launch_fk20_select(st, conv, log_L, m, log_M, batch, h);
+    const void* res = launch_g1_dft(st, h, x1, (void*)conv, log_M, batch, tw, ctx->glv_log, false);
+    launch_xyzz_to_affine(st, res, (uint32_t)(batch * M), aff, prefix);
+    launch_affine_to_p1(st, aff, (uint32_t)(batch * M), p1);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = fk20_sync(ctx, lk, st);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_proofs, p1, batch * M * 144, hipMemcpyDeviceToHost, st));
+    return fk20_sync(ctx, lk, st);
+}
+
+static int fk20_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batch, size_t stride, const CellsShape& sh,
+                     uint64_t* out_cells, uint64_t* out_proofs) {
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    std::vector<size_t> neff(batch);
+    size_t n_max = 0;
+    for (size_t b = 0; b < batch; b++) {
+        neff[b] = n ? cells_trim(coeffs + 4 * b * stride, n) : 0;
+        if (neff[b] > sh.l && neff[b] - sh.l > ctx->n) {
+            ctx->last_error = "fk20: polynomial " + std::to_string(b) + ": n' - l = " + std::to_string(neff[b] - sh.l) +
+                              " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+            return KZG_ERR_DEGREE_TOO_HIGH;
+        }
+        if (neff[b] > n_max) n_max = neff[b];
+    }
+    uint32_t m = 0, log_L = 0;
+    if (n_max > sh.l && !fk20_shape(ctx, n_max, sh.log_l, &m, &log_L)) return KZG_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot0 = reserve_slot(ctx, lk, true);
+    if (slot0 < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot0};
+    Slot& s0 = ctx->slots[slot0];
+    if (out_cells) {  // per polynomial: forward NTT of P padded to N, gathered into cell-major order (as kzg_cells_and_proofs)
+        rc = ensure_cells_poly(ctx, s0, sh.N);
+        if (rc == KZG_OK) rc = ensure_poly(ctx, s0, sh.N);
+        if (rc) return rc;
+        for (size_t b = 0; b < batch; b++) {
+            if (neff[b]) HIP_TRY(ctx, hipMemcpyAsync(s0.d_cpoly, coeffs + 4 * b * stride, neff[b] * 32, hipMemcpyHostToDevice, s0.stream));
+            if (neff[b] < sh.N) HIP_TRY(ctx, hipMemsetAsync(s0.d_cpoly + 8 * neff[b], 0, (sh.N - neff[b]) * 32, s0.stream));
+            rc = ntt_into_stage(ctx, s0, s0.d_cpoly, sh.log_n, false);
+            if (rc) return rc;
+            launch_cells_gather(s0.stream, s0.d_stage, s0.d_q, sh.log_n, sh.log_l);
+            HIP_TRY(ctx, hipGetLastError());
+            rc = fk20_sync(ctx, lk, s0.stream);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * sh.N * b, s0.d_q, sh.N * 32, hipMemcpyDeviceToHost, s0.stream));
+            rc = fk20_sync(ctx, lk, s0.stream);
+            if (rc) return rc;
+        }
+    }
+    if (n_max <= sh.l) {  // every polynomial is its own interpolant on every cell
+        const hf::P1 inf = hf::p1_inf();
+        for (size_t j = 0; j < batch * sh.cells; j++) write_p1(out_proofs + 18 * j, inf);
+        return KZG_OK;
+    }
+    const uint32_t log_M = sh.log_n - sh.log_l;
+    rc = ensure_glv(ctx, lk, log_L > log_M ? log_L : log_M, s0.stream);
+    if (rc == KZG_OK) rc = ensure_fk20_table(ctx, lk, s0.stream, log_L, sh.log_l);
+    if (rc) return rc;
+    // polynomials per pass: at most kFk20MaxBatch, fewer when their workspaces would pass kFk20WsBudget
+    const size_t L = (size_t)1 << log_L, M = (size_t)1 << log_M, X = L > M ? L : M;
+    const bool kept = ctx->d_fk20_tab != nullptr;
+    const size_t ci = kept ? L : fk20_stream_positions(log_L, sh.log_l);
+    const size_t per_poly = n_max * 32 + sh.l * L * 64 + (sh.l > 1 ? sh.l * ci * kXyzzBytes : 0) + 3 * X * kXyzzBytes + M * 336;
+    size_t chunk = kFk20WsBudget / per_poly;
+    chunk = chunk < 1 ? 1 : (chunk > kFk20MaxBatch ? kFk20MaxBatch : chunk);
+    DevBuf stab, stmp, spre;  // the streamed comb tables of one chunk of positions, freed with the call
+    if (!kept) {
+        const size_t sb = ci << sh.log_l;
+        HIP_TRY(ctx, hipMalloc(&stab.p, sb * kFk20CombEntries * kAffineBytes));
+        HIP_TRY(ctx, hipMalloc(&stmp.p, sb * kFk20CombEntries * kXyzzBytes));
+        HIP_TRY(ctx, hipMalloc(&spre.p, sb * kFk20CombEntries * 64));
+    }
+    for (size_t b0 = 0; b0 < batch && rc == KZG_OK; b0 += chunk) {
+        const size_t bc = batch - b0 < chunk ? batch - b0 : chunk;
+        rc = fk20_proofs(ctx, lk, s0.stream, coeffs + 4 * b0 * stride, stride, bc, n_max, m, log_L, sh.log_l, log_M,
+                         out_proofs + 18 * sh.cells * b0, stab.p, stmp.p, spre.p);
+    }
+    if (!kept) {  // the DevBufs free when the call returns; nothing in flight may still read them
+        const int r2 = fk20_sync(ctx, lk, s0.stream);
+        if (rc == KZG_OK) rc = r2;
+    }
+    return rc;
+}
+
+int kzg_cells_and_proofs_fk20(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batch, size_t stride_coeffs,
+                              unsigned log_domain, unsigned log_cell, uint64_t* out_cells, uint64_t* out_proofs) {
+    CellsShape sh;
+    if (!ctx || (!out_proofs && batch) || (!coeffs && n && batch) || !cells_shape(n, log_domain, log_cell, &sh))
+        return KZG_ERR_INVALID_ARG;
+    if (batch > 1 && stride_coeffs < n) {
+        ctx->last_error = "fk20: stride_coeffs is below n";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? kzg_cells_and_proofs_fk20(kid, coeffs, n, batch, stride_coeffs, log_domain, log_cell, out_cells, out_proofs) : rc;
+    }
+    if (!batch) return KZG_OK;
+    return fk20_host(ctx, coeffs, n, batch, batch > 1 ? stride_coeffs : n, sh, out_cells, out_proofs);
+}
+
+int kzg_fk20_prepare(kzg_ctx* ctx, size_t n, unsigned log_cell) {
+    if (!ctx || log_cell > KZG_MAX_CELL_LOG) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? kzg_fk20_prepare(kid, n, log_cell) : rc;
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n <= ((size_t)1 << log_cell)) return KZG_OK;  // such polynomials have infinity proofs: nothing to build
+    uint32_t m = 0, log_L = 0;
+    if (!fk20_shape(ctx, n, log_cell, &m, &log_L)) return KZG_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_glv(ctx, lk, log_L, s.stream);
+    if (rc == KZG_OK) rc = ensure_fk20_table(ctx, lk, s.stream, log_L, log_cell);
+    return rc;
+}
+
+int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint64_t* out_p1) {
+    uint32_t lg = 0;
+    if (!ctx || !in_p1 || !out_p1 || !ntt_log(m, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_g1_dft(multi_kid(ctx->multi, 0), in_p1, m, inverse, out_p1);  // needs no SRS
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);  // needs no SRS
+    if (rc == KZG_OK) rc = ensure_glv(ctx, lk, lg, s.stream);
+    void *jac, *aff, *prefix, *x1, *x2, *x3;
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsP1, m * 144, &jac);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsAff, m * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPrefix, m * 64, &prefix);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX1, m * kXyzzBytes, &x1);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX2, m * kXyzzBytes, &x2);
+    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX3, m * kXyzzBytes, &x3);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(jac, in_p1, m * 144, hipMemcpyHostToDevice, s.stream));
+    launch_jacobian_to_affine(s.stream, jac, (uint32_t)m, aff, prefix);
+    launch_affine_to_xyzz(s.stream, aff, m, x1);
+    void* res = (void*)launch_g1_dft(s.stream, x1, x2, x3, lg, 1, (const Glv*)ctx->d_glv, ctx->glv_log, inverse != 0);
+    if (inverse) launch_g1_scale(s.stream, res, m, glv_split(hf::fr_inv(fr_pow2(lg))));
+    launch_xyzz_to_affine(s.stream, res, (uint32_t)m, aff, prefix);
+    launch_affine_to_p1(s.stream, aff, (uint32_t)m, jac);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = fk20_sync(ctx, lk, s.stream);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_p1, jac, m * 144, hipMemcpyDeviceToHost, s.stream));
+    return fk20_sync(ctx, lk, s.stream);
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

@@ -177,6 +177,43 @@ void launch_cell_quotients(hipStream_t s, const uint32_t* d_coeffs, uint32_t nq,
 // out[j l + i] = evals[j + (N / l) i] (N values)
 void launch_cells_gather(hipStream_t s, const uint32_t* d_evals, uint32_t* d_out, uint32_t log_n, uint32_t log_l);
 
+// ---- fk20_kernels.hip: G1 DFTs and the FK20 proofs of all cells ----------------------------------
+// A twiddle w split as w = k1 + k2 lambda (lambda = z^2 - 1, k1, k2 < 2^128 as plain integers, little-endian u64)
+struct Glv {
+    uint64_t k1[2], k2[2];
+};
+// comb tables of the SRS side: entry (j, d - 1) = d 16^j B, j < 64 windows of 4 bits, d = 1..8 (signed digits)
+constexpr uint32_t kFk20CombWindows = 64;
+constexpr uint32_t kFk20CombDigits = 8;
+constexpr uint32_t kFk20CombEntries = kFk20CombWindows * kFk20CombDigits;
+// `batch` DFTs of 2^log_len XYZZ records (vector b at d_in + b 2^log_len records), natural order in and out, unnormalised
+// (no 1/len); the stages ping-pong through d_a, d_b (neither may alias d_in); returns the buffer holding the result (d_in
+// when log_len = 0).  d_tw: w_(2^log_tw)^e for e < 2^log_tw, log_tw >= log_len.
+const void* launch_g1_dft(hipStream_t s, const void* d_in, void* d_a, void* d_b, uint32_t log_len, uint64_t batch,
+                          const Glv* d_tw, uint32_t log_tw, bool inverse);
+void launch_g1_scale(hipStream_t s, void* d_io, uint64_t n, const Glv& k);
+// S_r[v] (r < l, v < L; out[r L + v]) from the table's level 0: SRS[v l + r] for v < L/2 inside the SRS, else infinity
+void launch_fk20_srs_gather(hipStream_t s, const void* d_table, uint64_t srs_n, uint32_t log_L, uint32_t log_l, void* d_out);
+// bases [first, first + count) in (i, r) order (base i l + r is d_bases[r L + i]) -> d_tmp: kFk20CombEntries XYZZ records
+// per base (normalise them for the table)
+void launch_fk20_comb(hipStream_t s, const void* d_bases, uint32_t log_L, uint32_t log_l, uint64_t first, uint32_t count,
+                      void* d_tmp);
+// R_r of `batch` polynomials (n coefficients each, contiguous) and their forward Fr DFTs of 2^log_L values, times inv_L
+// (multiplier form), as plain integers: returns d_a or d_b
+const uint32_t* launch_fk20_fr_side(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t m, uint32_t log_L,
+                                    uint32_t log_l, uint64_t batch, const void* d_tw, const Fr30& inv_L, uint32_t* d_a,
+                                    uint32_t* d_b);
+// d_out[b L + i] = sum_r [A_(b,r)[i]] B_r[i] for i in [i0, i0 + ci) over the comb tables d_tab of bases
+// [i0 l, (i0 + ci) l); d_part: batch ci l XYZZ records (unused for l = 1)
+void launch_fk20_pointwise(hipStream_t s, const uint32_t* d_scal, const void* d_tab, uint32_t log_L, uint32_t log_l,
+                           uint32_t i0, uint32_t ci, uint64_t batch, void* d_part, void* d_out);
+// H[b M + d] = conv[b L + m - 1 - d] (d <= m - 2), infinity up to M = 2^log_M
+void launch_fk20_select(hipStream_t s, const void* d_conv, uint32_t log_L, uint32_t m, uint32_t log_M, uint64_t batch, void* d_H);
+// native affine table records -> XYZZ records
+void launch_affine_to_xyzz(hipStream_t s, const void* d_affine, uint64_t n, void* d_out);
+// srs_kernels.hip: XYZZ records -> native affine records (one inversion per 32 points; d_prefix: 64 B per point)
+void launch_xyzz_to_affine(hipStream_t s, const void* d_xyzz, uint32_t n, void* d_out, void* d_prefix);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

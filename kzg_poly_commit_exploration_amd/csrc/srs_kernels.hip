@@ -205,7 +205,7 @@ void launch_jacobian_to_affine(hipStream_t s, const void* d_jac, uint32_t n, voi
     hipLaunchKernelGGL(k_normalize<0>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const uint4*)d_jac, n, (uint4*)d_out,
                        (uint4*)d_prefix);
 }
-static void launch_xyzz_to_affine(hipStream_t s, const void* d_xyzz, uint32_t n, void* d_out, void* d_prefix) {
+void launch_xyzz_to_affine(hipStream_t s, const void* d_xyzz, uint32_t n, void* d_out, void* d_prefix) {
     if (!n) return;
     const uint32_t lanes = (n + kNormK - 1) / kNormK;
     hipLaunchKernelGGL(k_normalize<1>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const uint4*)d_xyzz, n, (uint4*)d_out,

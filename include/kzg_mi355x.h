@@ -296,6 +296,36 @@ int kzg_cells_and_proofs_fk20(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size
                               unsigned log_domain, unsigned log_cell, uint64_t* out_cells, uint64_t* out_proofs);
 /* optional: build the SRS-side cache for polynomials of n coefficients and cells of 2^log_cell points now */
 int kzg_fk20_prepare(kzg_ctx* ctx, size_t n, unsigned log_cell);
+
+/* ---- recovery of every cell and proof from part of the cells --------------------------------
+ * Cells as in kzg_cells_and_proofs: N = 2^log_domain, l = 2^log_cell, M = N / l cells, value i of cell j is
+ * P(w_N^(j + M i)).  Given k distinct received cells (cell_ids[t] < M, any order) of `batch` polynomials of n coefficients,
+ * with k l >= n, the call rebuilds each polynomial on the device (an erasure decode over the coset 7 <w_N>, DESIGN.md
+ * section 4.9) and returns what is requested:
+ *   out_coeffs (may be NULL): batch x n x 4 u64, canonical; entries past n' are zero.
+ *   out_cells  (may be NULL): batch x N x 4 u64, cell-major;  out_proofs (may be NULL): batch x M x 18 u64 (blst_p1).
+ *   Both are bit for bit what kzg_cells_and_proofs_fk20 (= kzg_cells_and_proofs) returns for the recovered coefficients,
+ *   so the received cells come back unchanged.  All three NULL only validates.
+ * Input: value i of received cell t (cell cell_ids[t]) of polynomial b at cells + 4 ((b k + t) l + i).  One set of cell
+ *   ids serves the whole batch (the blobs of one block arrive with the same indices); callers with different sets make one
+ *   call per set.  Sampling specs that list the N values in bit-reversed order: their cell c is this API's cell
+ *   brp_(K-t)(c) and its values are in brp_t(i) order (as for kzg_cells_and_proofs).
+ * Errors, in this order:
+ *   KZG_ERR_INVALID_ARG: log_domain > KZG_NTT_MAX_LOG, log_cell > KZG_MAX_CELL_LOG, log_cell > log_domain,
+ *     log_domain - log_cell > KZG_RECOVER_MAX_LOG_CELLS; n = 0 or n > N; k l < n; a cell id >= M or a duplicate; a
+ *     required pointer NULL; an input value >= r (checked on the host: recovery input comes from the network;
+ *     kzg_last_error names the polynomial and the cell).
+ *   KZG_ERR_NO_SRS: out_proofs requested without an SRS (coefficients and cells need none).
+ *   KZG_ERR_REMAINDER: the received values of some polynomial are not those of a polynomial of fewer than n coefficients
+ *     (its decoded coefficients at [n, N) are not all zero); kzg_last_error names the first one, the whole call fails.
+ *   KZG_ERR_DEGREE_TOO_HIGH: as kzg_cells_and_proofs_fk20 returns it when proofs are requested (n' - l > kzg_srs_len).
+ * batch = 0 does nothing.  Thread safety and multi-device contexts as kzg_cells_and_proofs_fk20 (a replicated SRS forwards
+ * to one device, a range-split one returns KZG_ERR_INVALID_ARG).  The cost of the vanishing evaluations grows as M (N - k l)
+ * / l, hence the cap on M. */
+#define KZG_RECOVER_MAX_LOG_CELLS 13 /* M = N / l <= 8192 */
+int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, unsigned log_cell, const uint32_t* cell_ids,
+                                 size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells,
+                                 uint64_t* out_proofs);
 /* test hook: DFT (inverse != 0: inverse DFT incl. 1/m) of m = 2^k <= 2^22 host blst_p1 points over w_m, normalised
  * output (out_p1[j] = sum_i [w_m^(i j)] in_p1[i]); needs no SRS.  The points must lie in G1 (the order-r subgroup): the
  * twiddle products use the endomorphism (x, y) -> (beta x, y) = [z^2 - 1](x, y), which holds there only; nothing checks it */

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "kzg_open_points", "kzg_open_points_submit", "kzg_quotient_points", "kzg_evaluate_points", "kzg_verify_points",
     "kzg_domain_root", "kzg_ntt", "kzg_ntt_device", "kzg_commit_evaluations", "kzg_commit_evaluations_submit",
     "kzg_open_evaluations", "kzg_cells_and_proofs", "kzg_cells_and_proofs_evaluations", "kzg_quotient_cells",
-    "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft",
+    "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft", "kzg_recover_cells_and_proofs",
 ]
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
@@ -158,6 +158,7 @@ def load_library():
         "kzg_cells_and_proofs_fk20": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_fk20_prepare": (i, [vp, sz, C.c_uint]),
         "kzg_g1_dft": (i, [vp, vp, sz, i, vp]),
+        "kzg_recover_cells_and_proofs": (i, [vp, sz, C.c_uint, C.c_uint, vp, sz, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -497,6 +498,25 @@ class Engine:
         _check(self._lib.kzg_cells_and_proofs_fk20(self._h, _ptr(a), n, batch, n, log_domain, log_cell,
                                                    _ptr(out_cells) if cells else None, _ptr(proofs)), self._h)
         return out_cells, [[G1Point(p) for p in proofs[b]] for b in range(batch)]
+
+    def recover_cells_and_proofs(self, n, log_domain, log_cell, cell_ids, cells, coeffs=True, cells_out=True, proofs=True):
+        """Rebuilds polynomials of n coefficients from k of their N/l cells: cell_ids lists the k distinct received cells (any
+        order, shared by the batch), cells is a (batch, k, l, 4) array (or (k, l, 4) for one polynomial), row t holding cell
+        cell_ids[t].  Returns (coeffs, cells, proofs) shaped as cells_and_proofs_fk20 returns them -- coeffs (batch, n, 4),
+        cells (batch, N, 4), proofs[b][j] -- each None when not requested"""
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        a = np.ascontiguousarray(cells, dtype=np.uint64)
+        if a.ndim != 4:
+            a = a.reshape(1, len(ids), 1 << log_cell, 4)
+        batch = a.shape[0]
+        M = 1 << max(log_domain - log_cell, 0)
+        out_c = np.zeros((batch, n, 4), dtype=np.uint64) if coeffs else None
+        out_v = np.zeros((batch, 1 << log_domain, 4), dtype=np.uint64) if cells_out else None
+        out_p = np.zeros((max(batch, 1), M, 18), dtype=np.uint64) if proofs else None
+        opt = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(self._lib.kzg_recover_cells_and_proofs(self._h, n, log_domain, log_cell, _ptr(ids), len(ids), _ptr(a), batch,
+                                                      opt(out_c), opt(out_v), opt(out_p)), self._h)
+        return out_c, out_v, ([[G1Point(p) for p in out_p[b]] for b in range(batch)] if proofs else None)
 
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""

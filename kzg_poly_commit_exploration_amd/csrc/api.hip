@@ -183,6 +183,12 @@ struct kzg_ctx {
     uint32_t fk20_log_L = 0, fk20_log_l = 0;
     void* fk20_ws[11] = {};
     size_t fk20_ws_bytes[11] = {};
+    // recovery (kzg_recover_cells_and_proofs), under recover_mu (taken before mu): the g-power tables
+    // g^i, g^-i (g = 7) in the NTT twiddles' lo / hi shape, built on first use; workspaces grown on demand
+    std::mutex recover_mu;
+    void* d_rec_g = nullptr;
+    void* rec_ws[9] = {};
+    size_t rec_ws_bytes[9] = {};
 };
 
 namespace {
@@ -756,6 +762,8 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     if (ctx->d_fk20_B) hipFree(ctx->d_fk20_B);
     if (ctx->d_fk20_tab) hipFree(ctx->d_fk20_tab);
     for (void* p : ctx->fk20_ws) hipFree(p);
+    if (ctx->d_rec_g) hipFree(ctx->d_rec_g);
+    for (void* p : ctx->rec_ws) hipFree(p);
     delete ctx;
 }
 
@@ -2732,6 +2740,207 @@ int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint6
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_p1, jac, m * 144, hipMemcpyDeviceToHost, s.stream));
     return fk20_sync(ctx, lk, s.stream);
+}
+
+// ---- recovery of every cell and proof from part of the cells (recover_kernels.hip) -----------------
+// The decode holds recover_mu, then the context's mutex and one slot for its stream, dropping the mutex while it waits for the
+// device; the cells come from the same pass.  Proofs go through fk20_host afterwards with the recovered coefficients (one more
+// upload of them).
+namespace {
+enum : int { kRecIn = 0, kRecA, kRecB, kRecCoef, kRecFlags, kRecPos, kRecMissing, kRecPart, kRecZ, kRecCount };
+constexpr size_t kRecMaxBatch = 64;               // polynomials per pass through the workspaces, at most
+constexpr size_t kRecWsBudget = (size_t)2 << 30;  // ... and fewer when their workspaces would pass this
+hf::Fr fr_seven() {
+    hf::Fr g = hf::kFrOne;
+    for (int i = 0; i < 6; i++) g = hf::fr_add(g, hf::kFrOne);
+    return g;
+}
+}  // namespace
+
+static int rec_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
+    if (bytes > ctx->rec_ws_bytes[i] || !ctx->rec_ws[i]) {
+        hipFree(ctx->rec_ws[i]);
+        ctx->rec_ws[i] = nullptr;
+        ctx->rec_ws_bytes[i] = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->rec_ws[i], bytes ? bytes : 256));
+        ctx->rec_ws_bytes[i] = bytes;
+    }
+    *out = ctx->rec_ws[i];
+    return KZG_OK;
+}
+static int rec_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(st);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("recover: ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+// g^i and g^-i tables (ctx->mu held, device current): forward lo, forward hi, inverse lo, inverse hi, as ensure_ntt's
+static int ensure_recover_g(kzg_ctx* ctx) {
+    if (ctx->d_rec_g) return KZG_OK;
+    std::vector<Fr30> h(4 * kNttTableLen);
+    const hf::Fr g = fr_seven();
+    for (int dir = 0; dir < 2; dir++) {
+        const hf::Fr base = dir ? hf::fr_inv(g) : g;
+        const hf::Fr step_hi = hf::fr_pow(base, kNttTableLen);
+        hf::Fr lo = hf::kFrOne, hi = hf::kFrOne;
+        for (uint32_t i = 0; i < kNttTableLen; i++) {
+            h[2 * dir * kNttTableLen + i] = fr30_arg_from_mont256(lo);
+            h[(2 * dir + 1) * kNttTableLen + i] = fr30_arg_from_mont256(hi);
+            lo = hf::fr_mul(lo, base);
+            hi = hf::fr_mul(hi, step_hi);
+        }
+    }
+    void* d = nullptr;
+    HIP_TRY(ctx, hipMalloc(&d, h.size() * sizeof(Fr30)));
+    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        ctx->last_error = std::string("hipMemcpy (recovery tables): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    ctx->d_rec_g = d;
+    return KZG_OK;
+}
+
+// the decode of `batch` validated polynomials: coefficients to out_coeffs, cells to out_cells (either may be null);
+// KZG_ERR_REMAINDER names the first polynomial whose coefficients at [n, N) are not all zero
+static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int32_t* pos, const std::vector<uint32_t>& missing,
+                        size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells) {
+    std::lock_guard<std::mutex> lkr(ctx->recover_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc == KZG_OK) rc = ensure_recover_g(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ensure_slot_basics(ctx, s);  // needs no SRS
+    if (rc) return rc;
+    const size_t N = sh.N, M = sh.cells, l = sh.l;
+    const size_t per_poly = 2 * N * 32 + n * 32;
+    size_t chunk = kRecWsBudget / per_poly;
+    chunk = chunk < 1 ? 1 : (chunk > kRecMaxBatch ? kRecMaxBatch : chunk);
+    if (chunk > batch) chunk = batch;
+    const uint32_t parts = recover_vanish_parts((uint32_t)missing.size());
+    void *in, *a, *b, *coef, *flags, *dpos, *dmiss, *part, *z;
+    rc = rec_ws(ctx, kRecIn, batch * k * l * 32, &in);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecA, chunk * N * 32, &a);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecB, chunk * N * 32, &b);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecCoef, chunk * n * 32, &coef);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecFlags, chunk * 4, &flags);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecPos, M * 4, &dpos);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecMissing, missing.size() * 4, &dmiss);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecPart, (size_t)parts * 2 * M * 32, &part);
+    if (rc == KZG_OK) rc = rec_ws(ctx, kRecZ, 2 * M * 32, &z);
+    if (rc) return rc;
+    rc = copy_unlocked(ctx, lk, s, in, cells, batch * k * l * 32);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dpos, pos, M * 4);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dmiss, missing.data(), missing.size() * 4);
+    if (rc) return rc;
+    const Fr30 gl = fr30_arg_from_mont256(hf::fr_pow(fr_seven(), l));
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.log_n)));
+    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
+    const Fr30* gt = (const Fr30*)ctx->d_rec_g;
+    launch_recover_vanishing(s.stream, (const uint32_t*)dmiss, (uint32_t)missing.size(), tw, sh.log_n, sh.log_l, gl,
+                             (uint32_t*)part, (uint32_t*)z);
+    std::vector<uint32_t> hflags(chunk);
+    uint32_t *A = (uint32_t*)a, *B = (uint32_t*)b;
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t bc = batch - b0 < chunk ? batch - b0 : chunk;
+        HIP_TRY(ctx, hipMemsetAsync(flags, 0, bc * 4, s.stream));
+        launch_recover_scatter(s.stream, (const uint32_t*)in + 8 * b0 * k * l, (const int32_t*)dpos, (const uint32_t*)z, (uint32_t)k,
+                               sh.log_n, sh.log_l, bc, A);
+        uint32_t* cur = const_cast<uint32_t*>(launch_fr_dft(s.stream, A, A, B, sh.log_n, bc, tw + 2 * kNttTableLen));
+        launch_recover_twist(s.stream, cur, sh.log_n, bc, gt, inv_n);
+        cur = const_cast<uint32_t*>(launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw));
+        launch_recover_divide(s.stream, cur, sh.log_n, sh.log_l, bc, (const uint32_t*)z + 8 * M);
+        cur = const_cast<uint32_t*>(launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw + 2 * kNttTableLen));
+        launch_recover_untwist(s.stream, cur, sh.log_n, (uint32_t)n, bc, gt + 2 * kNttTableLen, inv_n, (uint32_t*)coef,
+                               out_cells != nullptr, (uint32_t*)flags);
+        const uint32_t* cells_dev = nullptr;
+        if (out_cells) {
+            const uint32_t* ev = launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw);
+            uint32_t* dst = ev == A ? B : A;
+            launch_recover_gather(s.stream, ev, dst, sh.log_n, sh.log_l, bc);
+            cells_dev = dst;
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        rc = rec_sync(ctx, lk, s.stream);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(hflags.data(), flags, bc * 4, hipMemcpyDeviceToHost, s.stream));
+        if (out_coeffs) HIP_TRY(ctx, hipMemcpyAsync(out_coeffs + 4 * n * b0, coef, bc * n * 32, hipMemcpyDeviceToHost, s.stream));
+        if (cells_dev) HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * N * b0, cells_dev, bc * N * 32, hipMemcpyDeviceToHost, s.stream));
+        rc = rec_sync(ctx, lk, s.stream);
+        if (rc) return rc;
+        for (size_t i = 0; i < bc; i++)
+            if (hflags[i]) {
+                ctx->last_error = "recover: polynomial " + std::to_string(b0 + i) + ": the received values are not those of a "
+                                  "polynomial of fewer than " + std::to_string(n) + " coefficients";
+                return KZG_ERR_REMAINDER;
+            }
+    }
+    return KZG_OK;
+}
+
+int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, unsigned log_cell, const uint32_t* cell_ids,
+                                 size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells,
+                                 uint64_t* out_proofs) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "recover: " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    CellsShape sh;
+    if (!cells_shape(n, log_domain, log_cell, &sh)) return invalid("unsupported shape (log_domain, log_cell) or n > N");
+    if (log_domain - log_cell > KZG_RECOVER_MAX_LOG_CELLS) return invalid("more than 2^KZG_RECOVER_MAX_LOG_CELLS cells");
+    if (n == 0) return invalid("n = 0");
+    if (k > sh.cells || k * sh.l < n) return invalid("k l must be at least n, with at most N / l cells");
+    if (!cell_ids || (!cells && batch)) return invalid("a required pointer is NULL");
+    std::vector<int32_t> pos(sh.cells, -1);
+    for (size_t t = 0; t < k; t++) {
+        if (cell_ids[t] >= sh.cells) return invalid("cell id " + std::to_string(cell_ids[t]) + " is not below N / l");
+        if (pos[cell_ids[t]] >= 0) return invalid("cell id " + std::to_string(cell_ids[t]) + " appears twice");
+        pos[cell_ids[t]] = (int32_t)t;
+    }
+    for (size_t b = 0; b < batch; b++)
+        for (size_t t = 0; t < k; t++)
+            for (size_t i = 0; i < sh.l; i++) {
+                hf::Fr v;
+                std::memcpy(v.l, cells + 4 * ((b * k + t) * sh.l + i), 32);
+                if (hf::fr_geq(v, hf::kFrMod))
+                    return invalid("polynomial " + std::to_string(b) + ", cell " + std::to_string(cell_ids[t]) + ": value " +
+                                   std::to_string(i) + " is not below r");
+            }
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? kzg_recover_cells_and_proofs(kid, n, log_domain, log_cell, cell_ids, k, cells, batch, out_coeffs, out_cells,
+                                                  out_proofs)
+                   : rc;
+    }
+    if (!batch) return KZG_OK;
+    if (out_proofs) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    }
+    std::vector<uint32_t> missing;
+    for (size_t j = 0; j < sh.cells; j++)
+        if (pos[j] < 0) missing.push_back((uint32_t)j);
+    std::vector<uint64_t> own;  // the coefficients FK20 needs when the caller does not want them
+    uint64_t* coeffs = out_coeffs;
+    if (!coeffs && out_proofs) {
+        own.resize(batch * n * 4);
+        coeffs = own.data();
+    }
+    const int rc = recover_host(ctx, sh, n, pos.data(), missing, k, cells, batch, coeffs, out_cells);
+    if (rc || !out_proofs) return rc;
+    return fk20_host(ctx, coeffs, n, batch, n, sh, nullptr, out_proofs);
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

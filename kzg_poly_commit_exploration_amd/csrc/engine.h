@@ -213,6 +213,32 @@ void launch_fk20_select(hipStream_t s, const void* d_conv, uint32_t log_L, uint3
 void launch_affine_to_xyzz(hipStream_t s, const void* d_affine, uint64_t n, void* d_out);
 // srs_kernels.hip: XYZZ records -> native affine records (one inversion per 32 points; d_prefix: 64 B per point)
 void launch_xyzz_to_affine(hipStream_t s, const void* d_xyzz, uint32_t n, void* d_out, void* d_prefix);
+// `batch` Fr DFTs of 2^log_len canonical values each (vector b at d_in + 8 b 2^log_len words), natural order in and out,
+// unnormalised; d_tw: one direction's lo / hi twiddle tables (the inverse ones give the inverse DFT without 1/len).  The
+// stages (k_fr_stage) alternate between d_a and d_b, never writing the buffer they read; returns the buffer holding the result
+// (d_in when log_len = 0).
+const uint32_t* launch_fr_dft(hipStream_t s, const uint32_t* d_in, uint32_t* d_a, uint32_t* d_b, uint32_t log_len, uint64_t batch,
+                              const void* d_tw);
+
+// ---- recover_kernels.hip: all coefficients of a batch of polynomials from part of their cells --------
+// Domain of N = 2^log_n points, cells of l = 2^log_l, M = N / l.  Stored multipliers are canonical 8 x u32 of the "x 2^270"
+// form.  The vanishing evaluations: d_z[p] = Z'(w_M^p) for p < M and 1 / Z'(g^l w_M^(p - M)) for M <= p < 2M, Z' over the
+// n_missing cells in d_missing; gl = g^l (multiplier form); d_part: recover_vanish_parts(n_missing) 2M x 8 words.
+uint32_t recover_vanish_parts(uint32_t n_missing);
+void launch_recover_vanishing(hipStream_t s, const uint32_t* d_missing, uint32_t n_missing, const void* d_tw, uint32_t log_n,
+                              uint32_t log_l, const Fr30& gl, uint32_t* d_part, uint32_t* d_z);
+// d_out[b N + j + M i] = cells[(b k + d_pos[j]) l + i] d_zrecv[j], 0 where d_pos[j] < 0
+void launch_recover_scatter(hipStream_t s, const uint32_t* d_cells, const int32_t* d_pos, const uint32_t* d_zrecv, uint32_t k,
+                            uint32_t log_n, uint32_t log_l, uint64_t batch, uint32_t* d_out);
+// in place, value i of every vector times g^i c; d_gtab: the g^i tables (lo / hi as the NTT twiddles)
+void launch_recover_twist(hipStream_t s, uint32_t* d_io, uint32_t log_n, uint64_t batch, const void* d_gtab, const Fr30& c);
+// in place, value e of every vector times d_zinv[e mod M]
+void launch_recover_divide(hipStream_t s, uint32_t* d_io, uint32_t log_n, uint32_t log_l, uint64_t batch, const uint32_t* d_zinv);
+// P_i = v_i g^-i c: i < n to d_coef[b n + i]; pad: P padded to N in place; a non-zero P_i with i >= n sets d_flags[b]
+void launch_recover_untwist(hipStream_t s, uint32_t* d_io, uint32_t log_n, uint32_t n, uint64_t batch, const void* d_ginv,
+                            const Fr30& c, uint32_t* d_coef, bool pad, uint32_t* d_flags);
+// d_out[b N + j l + i] = d_in[b N + j + M i]
+void launch_recover_gather(hipStream_t s, const uint32_t* d_in, uint32_t* d_out, uint32_t log_n, uint32_t log_l, uint64_t batch);
 
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg

@@ -389,6 +389,19 @@ const uint32_t* launch_fk20_fr_side(hipStream_t s, const uint32_t* d_coeffs, uin
     return cur;
 }
 
+const uint32_t* launch_fr_dft(hipStream_t s, const uint32_t* d_in, uint32_t* d_a, uint32_t* d_b, uint32_t log_len, uint64_t batch,
+                              const void* d_tw) {
+    const uint64_t lanes = batch << (log_len ? log_len - 1 : 0);
+    const uint32_t* cur = d_in;
+    for (uint32_t st = 0; st < log_len; st++) {
+        uint32_t* dst = cur == d_a ? d_b : d_a;
+        hipLaunchKernelGGL(k_fr_stage, grid_for(lanes, 256), dim3(256), 0, s, cur, dst, log_len, st, lanes, (const Fr30*)d_tw, 0,
+                           fr30_zero());
+        cur = dst;
+    }
+    return cur;
+}
+
 void launch_fk20_pointwise(hipStream_t s, const uint32_t* d_scal, const void* d_tab, uint32_t log_L, uint32_t log_l,
                            uint32_t i0, uint32_t ci, uint64_t batch, void* d_part, void* d_out) {
     const uint64_t lanes = (batch * ci) << log_l;

@@ -326,6 +326,42 @@ int kzg_fk20_prepare(kzg_ctx* ctx, size_t n, unsigned log_cell);
 int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, unsigned log_cell, const uint32_t* cell_ids,
                                  size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells,
                                  uint64_t* out_proofs);
+/* ---- batch verification of cell proofs: one pairing check for many cells ------------------------------------------
+ * Cells as in kzg_cells_and_proofs: N = 2^log_domain, l = 2^log_cell, M = N / l; value i of cell j is P(w_N^(j + M i)), cell j
+ * is the coset h_j <w_l> with h_j = w_N^j and X^l = a_j = w_M^j on it.  Record t (t < k) claims that commitment
+ * commitment_idx[t] opens to the l values at cells + 4 (t l + i) (blst_fr, Montgomery) on cell cell_ids[t], with the proof at
+ * proofs_p1 + 18 t:  e(pi_t, [s^l - a_j]G2) == e(C_b - [I_t(s)]G1, G2), I_t the interpolant of the values on the coset.
+ * The call checks all records at once: with weights rho_t = a_t + b_t lambda (a_t, b_t uniform
+ * 64-bit from the OS CSPRNG, getrandom(2), fresh on every call; lambda = z^2 - 1) it forms on the device
+ *     LHS = sum_t rho_t pi_t,    RHS = sum_b U_b C_b - [A(s)]G1 + sum_j [a_j] T_j
+ * (U_b = sum of the weights of b's records, T_j = sum_{t: j_t = j} rho_t pi_t, A = sum_t rho_t I_t) and pairs once on the host:
+ * e(LHS, [s^l]G2) == e(RHS, G2).  *valid = 1 when every record is valid; a batch with an invalid record is accepted with
+ * probability at most 2^-128.  The weights are not the Fiat-Shamir weights of the sampling specs (no hashing of the
+ * inputs): the boolean answer is the same, the randomness is the caller's process's.
+ * Inputs: points are blst_p1 (all-zero: infinity); [s^t]G1 for t < l comes from the context's SRS; setup_g2 is read at indices
+ * 0 ([1]G2) and l ([s^l]G2), g2_stride_bytes apart, as kzg_verify_points reads it.  Repeated records and repeated cell ids
+ * are allowed; k = 0 gives *valid = 1.  Sampling specs that list the N values in bit-reversed order: their cell c is this
+ * API's cell brp_(log_domain - log_cell)(c) and its values are in brp_(log_cell)(i) order (as for kzg_cells_and_proofs).
+ * Errors (kzg_last_error names the record or the commitment):
+ *   KZG_ERR_INVALID_ARG: log_domain > KZG_NTT_MAX_LOG, log_cell > KZG_MAX_CELL_LOG, log_cell > log_domain; k or
+ *     num_commitments > KZG_VERIFY_MAX_CELLS; a required pointer NULL; commitment_idx[t] >= num_commitments; cell_ids[t] >= M;
+ *     a value >= r (checked on the host); a G1 coordinate not below p; a G2 input off the twist; then, from the device, a
+ *     proof or commitment off the curve or outside G1 (the order-r subgroup; infinity passes).
+ *   KZG_ERR_NO_SRS: the SRS holds fewer than l points.
+ *   KZG_ERR_HIP: a device call failed, or the OS random source did.
+ * Thread safety as kzg_cells_and_proofs_fk20 (the call holds one slot and waits without the context lock); a replicated
+ * multi-device context forwards to one device, a range-split one returns KZG_ERR_INVALID_ARG. */
+#define KZG_VERIFY_MAX_CELLS (1u << 20)
+int kzg_verify_cells_batch(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                           const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k, unsigned log_domain,
+                           unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes, int* valid);
+/* test hook: the same with the caller's weights (k x blst_fr, any field elements below r) instead of random ones; returns the
+ * two G1 sides, normalised like kzg_open's output (Z = Montgomery one, or all zero for infinity), and *valid from the same
+ * pairing */
+int kzg_verify_cells_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                             const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k,
+                             unsigned log_domain, unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes,
+                             const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid);
 /* test hook: DFT (inverse != 0: inverse DFT incl. 1/m) of m = 2^k <= 2^22 host blst_p1 points over w_m, normalised
  * output (out_p1[j] = sum_i [w_m^(i j)] in_p1[i]); needs no SRS.  The points must lie in G1 (the order-r subgroup): the
  * twiddle products use the endomorphism (x, y) -> (beta x, y) = [z^2 - 1](x, y), which holds there only; nothing checks it */

@@ -300,6 +300,26 @@ struct Cells {
         }
         return out;
     }
+    // kzg_verify_cells_batch: record t claims that commitments[commitment_idx[t]] opens to the l values
+    // values[t l .. t l + l) on cell cell_ids[t] with proofs[t]; all records are checked at once with random weights and one
+    // pairing.  setup_g2: [s^j]G2 for j <= l (SetupArtifacts::g2_at).  True when every record is valid.
+    static bool verify_batch(const std::vector<G1Point>& commitments, const std::vector<uint32_t>& commitment_idx,
+                             const std::vector<uint32_t>& cell_ids, const std::vector<Scalar>& values,
+                             const std::vector<G1Point>& proofs, unsigned log_domain, unsigned log_cell,
+                             const std::vector<std::array<uint64_t, 36>>& setup_g2, const SetupArtifacts& setup) {
+        const size_t k = cell_ids.size();
+        if (commitment_idx.size() != k || proofs.size() != k || values.size() != (k << log_cell) ||
+            setup_g2.size() <= ((size_t)1 << log_cell))
+            throw Error(KZG_ERR_INVALID_ARG, "Cells::verify_batch: one commitment index, cell id, l values and proof per record, "
+                                             "and l + 1 G2 powers");
+        int valid = 0;
+        check(kzg_verify_cells_batch(setup.ctx(), commitments.empty() ? nullptr : commitments.front().p1.data(), commitments.size(),
+                                     commitment_idx.data(), cell_ids.data(), reinterpret_cast<const uint64_t*>(values.data()),
+                                     proofs.empty() ? nullptr : proofs.front().p1.data(), k, log_domain, log_cell,
+                                     setup_g2.front().data(), sizeof(setup_g2.front()), &valid),
+              setup.ctx());
+        return valid != 0;
+    }
     // builds the SRS-side FK20 transforms for polynomials of n coefficients now (otherwise the first call does)
     static void prepare_fk20(size_t n, unsigned log_cell, const SetupArtifacts& setup) {
         check(kzg_fk20_prepare(setup.ctx(), n, log_cell), setup.ctx());

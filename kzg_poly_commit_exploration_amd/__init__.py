@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "kzg_domain_root", "kzg_ntt", "kzg_ntt_device", "kzg_commit_evaluations", "kzg_commit_evaluations_submit",
     "kzg_open_evaluations", "kzg_cells_and_proofs", "kzg_cells_and_proofs_evaluations", "kzg_quotient_cells",
     "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft", "kzg_recover_cells_and_proofs",
+    "kzg_verify_cells_batch", "kzg_verify_cells_lincomb",
 ]
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
@@ -159,6 +160,8 @@ def load_library():
         "kzg_fk20_prepare": (i, [vp, sz, C.c_uint]),
         "kzg_g1_dft": (i, [vp, vp, sz, i, vp]),
         "kzg_recover_cells_and_proofs": (i, [vp, sz, C.c_uint, C.c_uint, vp, sz, vp, sz, vp, vp, vp]),
+        "kzg_verify_cells_batch": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, vp, sz, C.POINTER(i)]),
+        "kzg_verify_cells_lincomb": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, vp, sz, vp, vp, vp, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -517,6 +520,44 @@ class Engine:
         _check(self._lib.kzg_recover_cells_and_proofs(self._h, n, log_domain, log_cell, _ptr(ids), len(ids), _ptr(a), batch,
                                                       opt(out_c), opt(out_v), opt(out_p)), self._h)
         return out_c, out_v, ([[G1Point(p) for p in out_p[b]] for b in range(batch)] if proofs else None)
+
+    def _verify_cells_args(self, commitments, commitment_idx, cell_ids, cells, proofs, log_cell, setup_g2):
+        rows = lambda pts, w: np.ascontiguousarray(  # noqa: E731
+            np.stack([p.p1 if isinstance(p, G1Point) else np.asarray(p, dtype=np.uint64) for p in pts])
+            if len(pts) else np.zeros((0, w), dtype=np.uint64), dtype=np.uint64).reshape(-1, w)
+        com = rows(list(commitments), 18)
+        prf = rows(list(proofs), 18)
+        idx = np.ascontiguousarray(commitment_idx, dtype=np.uint32).reshape(-1)
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        k = len(ids)
+        vals = np.ascontiguousarray(cells, dtype=np.uint64).reshape(k, 1 << log_cell, 4) if k else np.zeros((1, 4), np.uint64)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert len(idx) == k and prf.shape[0] == k, "one commitment index, cell id, value row and proof per record"
+        keep = (com, prf, idx, ids, vals, g2)
+        return keep, (_ptr(com) if com.size else None, com.shape[0], _ptr(idx) if k else None, _ptr(ids) if k else None,
+                      _ptr(vals) if k else None, _ptr(prf) if k else None, k)
+
+    def verify_cells_batch(self, commitments, commitment_idx, cell_ids, cells, proofs, log_domain, log_cell, setup_g2):
+        """kzg_verify_cells_batch: checks k cell records at once with one pairing (random weights).  commitments: G1Points
+        (or blst_p1 rows); record t claims that commitments[commitment_idx[t]] opens to cells[t] (l x 4 limbs) on cell
+        cell_ids[t] with proofs[t]; setup_g2: blst_p2 rows [s^j]G2 for j <= l.  Returns True when every record is valid"""
+        keep, a = self._verify_cells_args(commitments, commitment_idx, cell_ids, cells, proofs, log_cell, setup_g2)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_cells_batch(self._h, *a, log_domain, log_cell, _ptr(keep[5]), 288, C.byref(ok)), self._h)
+        return bool(ok.value)
+
+    def verify_cells_lincomb(self, commitments, commitment_idx, cell_ids, cells, proofs, log_domain, log_cell, setup_g2, weights):
+        """the test hook kzg_verify_cells_lincomb: the same check with the given weights (k blst_fr rows, or Scalars).
+        Returns (lhs, rhs, valid): the two G1 sides as G1Points and the pairing's answer"""
+        keep, a = self._verify_cells_args(commitments, commitment_idx, cell_ids, cells, proofs, log_cell, setup_g2)
+        w = (np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4) if isinstance(weights, np.ndarray)
+             else _scalar_rows(weights))
+        lhs = np.zeros(18, dtype=np.uint64)
+        rhs = np.zeros(18, dtype=np.uint64)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_cells_lincomb(self._h, *a, log_domain, log_cell, _ptr(keep[5]), 288, _ptr(w), _ptr(lhs),
+                                                  _ptr(rhs), C.byref(ok)), self._h)
+        return G1Point(lhs), G1Point(rhs), bool(ok.value)
 
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""

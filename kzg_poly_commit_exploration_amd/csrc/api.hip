@@ -9,8 +9,11 @@
 // Nothing here falls back to the CPU for the MSM or the division: without a device the context
 // cannot be created.
 #include <hip/hip_runtime.h>
+#include <sys/random.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -189,6 +192,10 @@ struct kzg_ctx {
     void* d_rec_g = nullptr;
     void* rec_ws[9] = {};
     size_t rec_ws_bytes[9] = {};
+    // batch verification of cells (kzg_verify_cells_batch): workspaces grown on demand, under fk20_mu
+    // (the call reads the split twiddles d_glv, which an FK20 call may grow)
+    void* vc_ws[16] = {};
+    size_t vc_ws_bytes[16] = {};
 };
 
 namespace {
@@ -764,6 +771,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (void* p : ctx->fk20_ws) hipFree(p);
     if (ctx->d_rec_g) hipFree(ctx->d_rec_g);
     for (void* p : ctx->rec_ws) hipFree(p);
+    for (void* p : ctx->vc_ws) hipFree(p);
     delete ctx;
 }
 
@@ -2941,6 +2949,397 @@ int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, un
     const int rc = recover_host(ctx, sh, n, pos.data(), missing, k, cells, batch, coeffs, out_cells);
     if (rc || !out_proofs) return rc;
     return fk20_host(ctx, coeffs, n, batch, n, sh, nullptr, out_proofs);
+}
+
+// ---- batch verification of cell proofs (verify_kernels.hip) --------------------------------------
+// One random linear combination of all records: the device forms both G1 sides, the host pairs them once.  The call holds
+// fk20_mu (it reads the split twiddles d_glv), then the context's mutex and one slot for its stream, dropping the mutex
+// while it waits for the device.
+namespace {
+enum : int {
+    kVcCells = 0, kVcFrA, kVcFrB, kVcCoefA, kVcOrder, kVcRho, kVcIds, kVcStarts, kVcP1, kVcAff, kVcPrefix, kVcSrc, kVcGlv,
+    kVcGlvSrs, kVcG1, kVcScratch
+};
+static_assert(kVcScratch < 16, "kzg_ctx::vc_ws");
+constexpr uint32_t kVcFold = 16;  // terms one lane adds per level of a segmented sum, at most
+// levels of a segmented sum over consecutive segments of the given lengths (each >= 1): per level the start of every
+// group of at most kVcFold entries inside one segment, plus the end; stops when every segment is one entry (one level at
+// least, so the result always lands in the level's output)
+using VcPlan = std::vector<std::vector<uint32_t>>;
+void vc_plan(std::vector<uint32_t> lens, VcPlan* levels) {
+    levels->clear();
+    for (;;) {
+        std::vector<uint32_t> starts{0};
+        bool more = false;
+        for (uint32_t& len : lens) {
+            const uint32_t groups = (len + kVcFold - 1) / kVcFold;
+            for (uint32_t g = 0; g < groups; g++) starts.push_back(starts.back() + std::min(kVcFold, len - g * kVcFold));
+            len = groups;
+            more |= groups > 1;
+        }
+        levels->push_back(std::move(starts));
+        if (!more) return;
+    }
+}
+// uniform random bytes from the OS CSPRNG (getrandom(2)); false if it fails
+bool vc_random(void* out, size_t bytes) {
+    uint8_t* p = (uint8_t*)out;
+    while (bytes) {
+        const ssize_t got = getrandom(p, bytes, 0);
+        if (got < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        p += got;
+        bytes -= (size_t)got;
+    }
+    return true;
+}
+const hf::Fr kFrR2 = {{0xc999e990f3f29c6dULL, 0x2b6cedcb87925c23ULL, 0x05d314967254398fULL, 0x0748d9d99f59ff11ULL}};  // 2^512 mod r
+}  // namespace
+
+static int vc_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
+    if (bytes > ctx->vc_ws_bytes[i] || !ctx->vc_ws[i]) {
+        hipFree(ctx->vc_ws[i]);
+        ctx->vc_ws[i] = nullptr;
+        ctx->vc_ws_bytes[i] = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->vc_ws[i], bytes ? bytes : 256));
+        ctx->vc_ws_bytes[i] = bytes;
+    }
+    *out = ctx->vc_ws[i];
+    return KZG_OK;
+}
+static int vc_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(st);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("verify cells: ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+
+namespace {
+// the validated records of one call, sorted by cell id
+struct VcBatch {
+    const CellsShape* sh;
+    size_t k, B;
+    const uint64_t* commitments;
+    const uint64_t* cells;
+    const uint64_t* proofs;
+    std::vector<uint32_t> order;  // record at sorted position t'
+    std::vector<uint32_t> ids;    // the D distinct cell ids, ascending
+    std::vector<uint32_t> lens;   // records per distinct id
+    std::vector<Glv> glv;         // per record (input order): its weight as k1 + k2 lambda
+    std::vector<Fr30> rho30;      // per sorted position: the weight in multiplier form
+    std::vector<hf::Fr> U;        // per commitment: the sum of its records' weights (Montgomery)
+};
+}  // namespace
+
+// the two sides of the check, normalised blst_p1, into out_lhs / out_rhs
+static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint64_t out_rhs[18]) {
+    const CellsShape& sh = *vb.sh;
+    const size_t K = vb.k, B = vb.B, l = sh.l, D = vb.ids.size();
+    const uint32_t log_M = sh.log_n - sh.log_l;
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready || ctx->n < l) {
+        ctx->last_error = "verify cells: the SRS holds fewer than l points";
+        return KZG_ERR_NO_SRS;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = ensure_glv(ctx, lk, log_M, s.stream);
+    if (rc) return rc;
+    // plans: T_j by cell id; the column sums of the twisted rows (one segment of D); the two sides over [T | C | S | AT]
+    VcPlan plan_t, plan_col, plan_fin;
+    vc_plan(vb.lens, &plan_t);
+    vc_plan({(uint32_t)D}, &plan_col);
+    vc_plan({(uint32_t)D, (uint32_t)(B + l + D)}, &plan_fin);
+    std::vector<uint32_t> starts;
+    std::vector<size_t> at_t, at_col, at_fin;  // offsets of each level's starts in the upload
+    for (auto* pl : {&plan_t, &plan_col, &plan_fin}) {
+        auto& at = pl == &plan_t ? at_t : (pl == &plan_col ? at_col : at_fin);
+        for (const auto& lv : *pl) {
+            at.push_back(starts.size());
+            starts.insert(starts.end(), lv.begin(), lv.end());
+        }
+    }
+    const size_t g0 = plan_t[0].size() - 1;  // rows after the first level (>= D)
+    const size_t gmax = std::max(g0, plan_fin[0].size() - 1);
+    const size_t lanes = K + B;
+    std::vector<uint32_t> src(lanes);
+    std::vector<Glv> glv(lanes);
+    for (size_t t = 0; t < K; t++) {
+        src[t] = vb.order[t];
+        glv[t] = vb.glv[vb.order[t]];
+    }
+    for (size_t b = 0; b < B; b++) {
+        src[K + b] = (uint32_t)(K + b);
+        glv[K + b] = glv_split(vb.U[b]);
+    }
+    void *cells, *fa, *fb, *coef, *order, *rho, *ids, *dstarts, *p1, *aff, *prefix, *dsrc, *dglv, *dglvs, *g1, *scratch;
+    rc = vc_ws(ctx, kVcCells, K * l * 32, &cells);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrA, g0 * l * 32, &fa);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrB, g0 * l * 32, &fb);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, l * 32 + 8, &coef);  // + the two error words
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcOrder, K * 4, &order);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcRho, K * sizeof(Fr30), &rho);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcIds, D * 4, &ids);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcStarts, starts.size() * 4, &dstarts);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcP1, lanes * 144, &p1);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcAff, lanes * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcPrefix, lanes * 64, &prefix);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcSrc, lanes * 4, &dsrc);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlv, lanes * sizeof(Glv), &dglv);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlvSrs, l * sizeof(Glv), &dglvs);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcG1, (K + 2 * D + B + l + 2) * kXyzzBytes, &g1);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    HIP_TRY(ctx, hipMemcpyAsync(cells, vb.cells, K * l * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(order, vb.order.data(), K * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(rho, vb.rho30.data(), K * sizeof(Fr30), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ids, vb.ids.data(), D * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dstarts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(p1, vb.proofs, K * 144, hipMemcpyHostToDevice, st));
+    if (B) HIP_TRY(ctx, hipMemcpyAsync((char*)p1 + K * 144, vb.commitments, B * 144, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dsrc, src.data(), lanes * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dglv, glv.data(), lanes * sizeof(Glv), hipMemcpyHostToDevice, st));
+    uint32_t* err = (uint32_t*)((char*)coef + l * 32);
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, 8, st));
+    const uint32_t* dst_ = (const uint32_t*)dstarts;
+    // Fr side: V_j (weighted first level), the inverse transforms, the twist, the column sums -> A's l coefficients
+    uint32_t *FA = (uint32_t*)fa, *FB = (uint32_t*)fb;
+    const uint32_t* cur = (const uint32_t*)cells;
+    for (size_t lv = 0; lv < plan_t.size(); lv++) {
+        uint32_t* dst = cur == FA ? FB : FA;
+        launch_vc_fr_sum(st, cur, lv ? nullptr : (const uint32_t*)order, lv ? nullptr : (const Fr30*)rho, dst_ + at_t[lv],
+                         (uint32_t)(plan_t[lv].size() - 1), sh.log_l, dst);
+        cur = dst;
+    }
+    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
+    uint32_t* y = const_cast<uint32_t*>(launch_fr_dft(st, cur, FA, FB, sh.log_l, D, tw + 2 * kNttTableLen));
+    launch_vc_fr_twist(st, y, (const uint32_t*)ids, (uint32_t)D, tw + 2 * kNttTableLen, sh.log_n, sh.log_l,
+                       fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.log_l))));
+    cur = y;
+    for (size_t lv = 0; lv < plan_col.size(); lv++) {
+        uint32_t* dst = lv + 1 == plan_col.size() ? (uint32_t*)coef : (cur == FA ? FB : FA);
+        launch_vc_fr_sum(st, cur, nullptr, nullptr, dst_ + at_col[lv], (uint32_t)(plan_col[lv].size() - 1), sh.log_l, dst);
+        cur = dst;
+    }
+    // G1: [P: K | T: D | C: B | S: l | AT: D | the two sides]
+    const size_t oT = K, oC = K + D, oS = oC + B, oAT = oS + l, oOut = oAT + D;
+    auto rec = [&](size_t i) { return (void*)((char*)g1 + i * kXyzzBytes); };
+    void* X[2] = {scratch, (char*)scratch + gmax * kXyzzBytes};
+    launch_jacobian_to_affine(st, p1, (uint32_t)lanes, aff, prefix);
+    launch_vc_ladder(st, aff, (const uint32_t*)dsrc, (const Glv*)dglv, (uint32_t)lanes, (uint32_t)lanes, (uint32_t)K, rec(0), rec(oC),
+                     err);
+    auto g1_plan = [&](const VcPlan& plan, const std::vector<size_t>& at, const void* in, void* out) {
+        const void* c = in;
+        for (size_t lv = 0; lv < plan.size(); lv++) {
+            void* dst = lv + 1 == plan.size() ? out : (c == X[0] ? X[1] : X[0]);
+            launch_vc_g1_sum(st, c, dst_ + at[lv], (uint32_t)(plan[lv].size() - 1), dst);
+            c = dst;
+        }
+    };
+    g1_plan(plan_t, at_t, rec(0), rec(oT));
+    launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, (const Glv*)ctx->d_glv, ctx->glv_log - log_M, rec(oAT));
+    HIP_TRY(ctx, hipGetLastError());
+    rc = vc_sync(ctx, lk, st);
+    if (rc) return rc;
+    std::vector<hf::Fr> A(l);
+    uint32_t herr[2];
+    HIP_TRY(ctx, hipMemcpyAsync(A.data(), coef, l * 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(herr, err, 8, hipMemcpyDeviceToHost, st));
+    rc = vc_sync(ctx, lk, st);
+    if (rc) return rc;
+    for (int e = 0; e < 2; e++)
+        if (herr[e] != 0xffffffffu) {
+            const std::string what = herr[e] < K ? "the proof of record " + std::to_string(herr[e])
+                                                 : "commitment " + std::to_string(herr[e] - K);
+            ctx->last_error = "verify cells: " + what + (e ? " is not in G1" : " is not on the curve");
+            return KZG_ERR_INVALID_ARG;
+        }
+    // -[A(s)]G1 = sum_i [-A_i] [s^i]G1
+    std::vector<Glv> gs(l);
+    const hf::Fr zero = {{0, 0, 0, 0}};
+    for (size_t i = 0; i < l; i++) gs[i] = glv_split(hf::fr_sub(zero, A[i]));
+    HIP_TRY(ctx, hipMemcpyAsync(dglvs, gs.data(), l * sizeof(Glv), hipMemcpyHostToDevice, st));
+    launch_vc_ladder(st, ctx->d_table, nullptr, (const Glv*)dglvs, (uint32_t)l, 0, 0, nullptr, rec(oS), err);
+    g1_plan(plan_fin, at_fin, rec(oT), rec(oOut));
+    launch_xyzz_to_affine(st, rec(oOut), 2, aff, prefix);
+    launch_affine_to_p1(st, aff, 2, p1);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = vc_sync(ctx, lk, st);  // gs goes out of scope
+    if (rc) return rc;
+    uint64_t sides[36];
+    HIP_TRY(ctx, hipMemcpyAsync(sides, p1, 2 * 144, hipMemcpyDeviceToHost, st));
+    rc = vc_sync(ctx, lk, st);
+    if (rc) return rc;
+    std::memcpy(out_lhs, sides, 144);
+    std::memcpy(out_rhs, sides + 18, 144);
+    return KZG_OK;
+}
+
+// weights: k blst_fr given by the caller (the test hook), or null for fresh random ones
+static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                             const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k,
+                             unsigned log_domain, unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes,
+                             const uint64_t* weights, bool want_weights, uint64_t* out_lhs, uint64_t* out_rhs, int* valid) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "verify cells: " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    CellsShape sh;
+    if (!cells_shape(0, log_domain, log_cell, &sh)) return invalid("unsupported shape (log_domain, log_cell)");
+    if (k > KZG_VERIFY_MAX_CELLS) return invalid("more than KZG_VERIFY_MAX_CELLS records");
+    if (num_commitments > KZG_VERIFY_MAX_CELLS) return invalid("more than KZG_VERIFY_MAX_CELLS commitments");
+    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !commitments_p1) ||
+        (k && (!commitment_idx || !cell_ids || !cells || !proofs_p1 || !setup_g2 || (want_weights && !weights))))
+        return invalid("a required pointer is NULL");
+    if (!k) {
+        if (want_weights) {
+            const hf::P1 inf = hf::p1_inf();
+            write_p1(out_lhs, inf);
+            write_p1(out_rhs, inf);
+        }
+        *valid = 1;
+        return KZG_OK;
+    }
+    for (size_t t = 0; t < k; t++) {
+        if (commitment_idx[t] >= num_commitments)
+            return invalid("record " + std::to_string(t) + ": commitment index " + std::to_string(commitment_idx[t]) +
+                           " is not below num_commitments");
+        if (cell_ids[t] >= sh.cells)
+            return invalid("record " + std::to_string(t) + ": cell id " + std::to_string(cell_ids[t]) + " is not below N / l");
+    }
+    for (size_t t = 0; t < k; t++)
+        for (size_t i = 0; i < sh.l; i++) {
+            hf::Fr v;
+            std::memcpy(v.l, cells + 4 * (t * sh.l + i), 32);
+            if (hf::fr_geq(v, hf::kFrMod))
+                return invalid("record " + std::to_string(t) + ": value " + std::to_string(i) + " is not below r");
+        }
+    if (want_weights)
+        for (size_t t = 0; t < k; t++) {
+            hf::Fr v;
+            std::memcpy(v.l, weights + 4 * t, 32);
+            if (hf::fr_geq(v, hf::kFrMod)) return invalid("weight " + std::to_string(t) + " is not below r");
+        }
+    // G1 inputs: canonical coordinates, and not the all-zero affine image of a finite point (the device's infinity);
+    // the curve and subgroup checks run on the device
+    auto p1_malformed = [](const uint64_t* w) {
+        hf::P1 p;
+        std::memcpy(&p, w, sizeof p);
+        if (!hf::geq(p.x, hf::kP) && !hf::geq(p.y, hf::kP) && !hf::geq(p.z, hf::kP))
+            return !p.z.is_zero() && p.x.is_zero() && p.y.is_zero();
+        return true;
+    };
+    for (size_t t = 0; t < k; t++)
+        if (p1_malformed(proofs_p1 + 18 * t)) return invalid("the proof of record " + std::to_string(t) + " is not on the curve");
+    for (size_t b = 0; b < num_commitments; b++)
+        if (p1_malformed(commitments_p1 + 18 * b)) return invalid("commitment " + std::to_string(b) + " is not on the curve");
+    hf::G2Affine g2[2];
+    for (int i = 0; i < 2; i++) {
+        uint64_t raw[36];
+        std::memcpy(raw, (const uint8_t*)setup_g2 + (i ? sh.l : 0) * g2_stride_bytes, sizeof raw);
+        g2[i] = hf::g2_from_p2(raw);
+        if (!hf::g2_on_curve(g2[i])) return invalid(std::string("setup_g2[") + (i ? "l" : "0") + "] is not on the twist");
+    }
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? verify_cells_impl(kid, commitments_p1, num_commitments, commitment_idx, cell_ids, cells, proofs_p1, k, log_domain,
+                                       log_cell, setup_g2, g2_stride_bytes, weights, want_weights, out_lhs, out_rhs, valid)
+                   : rc;
+    }
+    VcBatch vb;
+    vb.sh = &sh;
+    vb.k = k;
+    vb.B = num_commitments;
+    vb.commitments = commitments_p1;
+    vb.cells = cells;
+    vb.proofs = proofs_p1;
+    // weights: rho = a + b lambda with a, b uniform 64-bit from the OS CSPRNG (a plain integer below 2^193 < r), or given
+    std::vector<hf::Fr> rho(k);
+    vb.glv.resize(k);
+    if (want_weights) {
+        for (size_t t = 0; t < k; t++) {
+            std::memcpy(rho[t].l, weights + 4 * t, 32);
+            vb.glv[t] = glv_split(rho[t]);
+        }
+    } else {
+        std::vector<uint64_t> ab(2 * k);
+        if (!vc_random(ab.data(), ab.size() * 8)) {
+            ctx->last_error = std::string("verify cells: getrandom: ") + std::strerror(errno);
+            return KZG_ERR_HIP;
+        }
+        for (size_t t = 0; t < k; t++) {
+            const uint64_t a = ab[2 * t], b = ab[2 * t + 1];
+            const unsigned __int128 lo = (unsigned __int128)b * (uint64_t)kGlvLambda + a;
+            const unsigned __int128 hi = (unsigned __int128)b * (uint64_t)(kGlvLambda >> 64) + (uint64_t)(lo >> 64);
+            const hf::Fr raw = {{(uint64_t)lo, (uint64_t)hi, (uint64_t)(hi >> 64), 0}};
+            rho[t] = hf::fr_mul(raw, kFrR2);  // Montgomery
+            vb.glv[t] = Glv{{a, 0}, {b, 0}};
+        }
+    }
+    // records sorted by cell id (counting sort), the distinct ids and their counts
+    std::vector<uint32_t> count(sh.cells + 1, 0);
+    for (size_t t = 0; t < k; t++) count[cell_ids[t] + 1]++;
+    for (size_t j = 0; j < sh.cells; j++) {
+        if (count[j + 1]) {
+            vb.ids.push_back((uint32_t)j);
+            vb.lens.push_back(count[j + 1]);
+        }
+        count[j + 1] += count[j];
+    }
+    vb.order.resize(k);
+    for (size_t t = 0; t < k; t++) vb.order[count[cell_ids[t]]++] = (uint32_t)t;
+    vb.rho30.resize(k);
+    for (size_t t = 0; t < k; t++) vb.rho30[t] = fr30_arg_from_mont256(rho[vb.order[t]]);
+    const hf::Fr zero = {{0, 0, 0, 0}};
+    vb.U.assign(num_commitments, zero);
+    for (size_t t = 0; t < k; t++) vb.U[commitment_idx[t]] = hf::fr_add(vb.U[commitment_idx[t]], rho[t]);
+    uint64_t lhs[18], rhs[18];
+    const int rc = vc_device(ctx, vb, lhs, rhs);
+    if (rc) return rc;
+    if (want_weights) {
+        std::memcpy(out_lhs, lhs, sizeof lhs);
+        std::memcpy(out_rhs, rhs, sizeof rhs);
+    }
+    // e(LHS, [s^l]G2) == e(RHS, G2):  e(LHS, [s^l]G2) e(-RHS, G2) == 1
+    hf::P1 L, R;
+    std::memcpy(&L, lhs, sizeof L);
+    std::memcpy(&R, rhs, sizeof R);
+    const hf::G2Affine qs[2] = {g2[1], g2[0]};
+    const hf::P1 ps[2] = {L, hf::p1_neg(R)};
+    bool ok = true;
+    const hf::F12 f = hf::multi_miller_loop(qs, ps, 2, ok);
+    *valid = ok && hf::f12_is_one(hf::f12_final_exp(f)) ? 1 : 0;
+    return KZG_OK;
+}
+
+int kzg_verify_cells_batch(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                           const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k, unsigned log_domain,
+                           unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    return verify_cells_impl(ctx, commitments_p1, num_commitments, commitment_idx, cell_ids, cells, proofs_p1, k, log_domain, log_cell,
+                             setup_g2, g2_stride_bytes, nullptr, false, nullptr, nullptr, valid);
+}
+
+int kzg_verify_cells_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                             const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k,
+                             unsigned log_domain, unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes,
+                             const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid) {
+    return verify_cells_impl(ctx, commitments_p1, num_commitments, commitment_idx, cell_ids, cells, proofs_p1, k, log_domain, log_cell,
+                             setup_g2, g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid);
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

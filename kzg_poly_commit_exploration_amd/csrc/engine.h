@@ -240,6 +240,24 @@ void launch_recover_untwist(hipStream_t s, uint32_t* d_io, uint32_t log_n, uint3
 // d_out[b N + j l + i] = d_in[b N + j + M i]
 void launch_recover_gather(hipStream_t s, const uint32_t* d_in, uint32_t* d_out, uint32_t log_n, uint32_t log_l, uint64_t batch);
 
+// ---- verify_kernels.hip: one random-linear-combination check of many cell proofs ------------------
+// lane t < lanes: P = d_rec[d_src ? d_src[t] : t] (affine records); lanes below n_check are checked to lie on the curve
+// (else atomicMin(d_err[0], index)) and in G1 (else atomicMin(d_err[1], index)); [d_glv[t]] P (XYZZ) to d_out_a[t] for
+// t < split, d_out_b[t - split] otherwise
+void launch_vc_ladder(hipStream_t s, const void* d_rec, const uint32_t* d_src, const Glv* d_glv, uint32_t lanes, uint32_t n_check,
+                      uint32_t split, void* d_out_a, void* d_out_b, uint32_t* d_err);
+// d_out[d] = [w_M^(d_ids[d])] d_T[d], the power read from split twiddles d_tw[d_ids[d] << shift]
+void launch_vc_cell_scale(hipStream_t s, const void* d_T, const uint32_t* d_ids, uint32_t D, const Glv* d_tw, uint32_t shift,
+                          void* d_out);
+// one level of a segmented sum: d_out[g] = sum of the XYZZ records d_in[d_starts[g] .. d_starts[g + 1])
+void launch_vc_g1_sum(hipStream_t s, const void* d_in, const uint32_t* d_starts, uint32_t groups, void* d_out);
+// the same over rows of 2^log_l canonical Fr values; with d_rho, row q is d_in's row d_order[q] times d_rho[q] (multiplier form)
+void launch_vc_fr_sum(hipStream_t s, const uint32_t* d_in, const uint32_t* d_order, const Fr30* d_rho, const uint32_t* d_starts,
+                      uint32_t groups, uint32_t log_l, uint32_t* d_out);
+// in place, value i of row d times w_N^-(d_ids[d] i) inv_l; d_itw: the inverse NTT twiddles
+void launch_vc_fr_twist(hipStream_t s, uint32_t* d_io, const uint32_t* d_ids, uint32_t D, const void* d_itw, uint32_t log_n,
+                        uint32_t log_l, const Fr30& inv_l);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

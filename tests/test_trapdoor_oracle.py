@@ -6,8 +6,11 @@ import numpy as np
 import pytest
 
 import bigint_twin as T
+import cells_oracle as CO
+import ntt_oracle as NO
 import open_points_oracle as OPO
 import trapdoor_oracle as TO
+import verify_cells_oracle as VO
 
 R = TO.R
 
@@ -145,3 +148,106 @@ def test_cube_root_of_unity():
         u = pow(7, (R - 1) >> k, R)
         assert pow(u, 1 << k, R) == 1 and pow(u, 1 << (k - 1), R) != 1
     assert T.R == R
+
+
+# ---- the data-availability references (tests/test_das_boundaries_gpu.py) ---------------------------------------------------
+def _w(k):
+    return NO.domain_root(k)
+
+
+def _degenerate_secrets(K, t, L):
+    """the secrets of the DAS boundary tests: 0, 1, r - 1, a cube root of unity, 2, a point of the domain (w_N^5: s^l = a_5
+    when M > 5), an l-th root of unity (s^l = a_0 = 1), w_L (the FK20 convolution size) and one generic secret"""
+    return {"0": 0, "1": 1, "r-1": R - 1, "omega3": pow(7, (R - 1) // 3, R), "2": 2, "w_N^5": pow(_w(K), 5, R),
+            "w_l": _w(t), "w_L": _w(NO.log2_exact(L)), "generic": 0x1234567890ABCDEF}
+
+
+@pytest.mark.parametrize("t", range(7))
+def test_cell_proof_scalars_fast_against_fk20_oracle(t):
+    """every cell, every degenerate secret, at shapes with one and several cells, n' at and below N"""
+    import fk20_oracle as FO
+
+    rnd = random.Random(100 + t)
+    for K in sorted({t, t + 1, t + 3}):
+        N, l = 1 << K, 1 << t
+        for n in sorted({N, max(1, N - l + 1), min(N, l + 1)}):
+            vals = [rnd.randrange(R) for _ in range(n)]
+            L = FO.shape(n, t)[2]
+            for name, s in _degenerate_secrets(K, t, L).items():
+                want = FO.cell_proof_scalars(vals, K, t, s)
+                got = TO.cell_proof_scalars_fast(vals, K, t, s)
+                assert [got[j] for j in range(N >> t)] == want, (K, t, n, name)
+            assert TO.cell_proof_scalars_fast(vals, K, t, 5, cells=[0])[0] == FO.cell_proof_scalars(vals, K, t, 5)[0]
+
+
+def test_cell_proof_scalars_fast_takes_the_fallback():
+    """s a point of cell 5 (s^l = a_5): the barycentric form would divide by zero there, the other cells keep it"""
+    K, t = 8, 3
+    s = pow(_w(K), 5 + 32 * 3, R)  # x_3 of cell 5
+    assert pow(s, 8, R) == CO.cell_root(K, t, 5)
+    vals = list(range(1, 200))
+    got = TO.cell_proof_scalars_fast(vals, K, t, s)
+    assert got[5] == CO.poly_eval(CO.stride_quotient(vals, 8, CO.cell_root(K, t, 5)), s)
+    assert got[6] == CO.poly_eval(CO.stride_quotient(vals, 8, CO.cell_root(K, t, 6)), s)
+
+
+@pytest.mark.parametrize("k", range(7))
+def test_srs_dft_closed_form(k):
+    m = 1 << k
+    w = _w(k)
+    for s in (0, 1, R - 1, 2, pow(7, (R - 1) // 3, R), 0xDEADBEEF, w, pow(w, m - 1, R), pow(w, 3 * (m > 3), R)):
+        srs = [pow(s, i, R) for i in range(m)]
+        want = NO.ntt(srs)
+        assert TO.srs_dft_scalars(s, m) == want, (k, s)
+    for j0 in range(m):  # s = w^-j0: m at j0, zero elsewhere
+        got = TO.srs_dft_scalars(pow(w, (m - j0) % m, R), m)
+        assert got[j0] == m % R and not any(got[:j0] + got[j0 + 1:])
+
+
+def test_torsion_points_have_the_stated_orders():
+    pts = TO.torsion_points()
+    assert sorted(pts) == list(TO.TORSION_ORDERS)
+    h = TO.H1
+    for q in TO.TORSION_ORDERS:
+        while h % q == 0:
+            h //= q
+    assert h == 1 and TO.H1 % 3 == 0 and TO.H1 % 9 != 0
+    g = T.srs_g1(T.BENCH_SECRET_BE, 2)[1]
+    for q, pt in list(pts.items()) + [(3, TO.ORDER3[0]), (3, TO.ORDER3[1])]:
+        assert pt is not T.INF and T.g1_is_on_curve(pt)
+        assert T.g1_mul(pt, q) is T.INF, q  # q prime: the order is q exactly
+        assert not VO.g1_in_subgroup(pt) and not VO.g1_in_subgroup_by_order(pt), q
+        bad = T.g1_add(g, pt)
+        assert T.g1_is_on_curve(bad)
+        assert not VO.g1_in_subgroup(bad) and not VO.g1_in_subgroup_by_order(bad), q
+    assert VO.g1_in_subgroup(g)
+
+
+@pytest.mark.parametrize("t", [0, 2, 3, 6])
+def test_verification_algebra_under_degenerate_secrets(t):
+    """LHS s^l = RHS for honest records, whatever the secret: s = 0, s^l = a_j, a root of unity, w_L"""
+    import fk20_oracle as FO
+
+    K = t + 3
+    l, M = 1 << t, 8
+    rnd = random.Random(t)
+    polys = [[rnd.randrange(R) for _ in range(1 << K)], [R - 1] * (4 * l), [0] * (l - 1) + [1]]
+    L = FO.shape(1 << K, t)[2]
+    for name, s in _degenerate_secrets(K, t, L).items():
+        coms, idx, ids, vals, prfs = [], [], [], [], []
+        for b, p in enumerate(polys):
+            coms.append(TO.poly_eval(p, s))
+            cells = CO.cells(p, K, t)
+            q = TO.cell_proof_scalars_fast(p, K, t, s)
+            for j in range(M):
+                idx.append(b)
+                ids.append(j)
+                vals.append(cells[j * l:(j + 1) * l])
+                prfs.append(q[j])
+        w = [rnd.randrange(R) for _ in ids]
+        lhs, rhs = VO.scalar_sides(K, t, coms, idx, ids, vals, prfs, w, s)
+        assert rhs == pow(s, l, R) * lhs % R, name
+        v2 = [list(v) for v in vals]
+        v2[3][0] = (v2[3][0] + 1) % R
+        lhs2, rhs2 = VO.scalar_sides(K, t, coms, idx, ids, v2, prfs, w, s)
+        assert rhs2 != pow(s, l, R) * lhs2 % R, name  # s = 0 too: the value enters through I(0)

@@ -6,7 +6,12 @@ terms in seconds:
   * commitment  [P(s)]G
   * proof       [(P(s) - y) / (s - z)]G             (s = z: [P'(z)]G, the quotient's value there)
   * multiproof  [(P(s) - I(s)) / Z(s)]G              I the interpolant of the claims, Z = prod (X - z_i)
+  * cell proof  [(P(s) - I_j(s)) / (s^l - a_j)]G       one per cell of a domain (s^l = a_j: the stride quotient at s)
+  * G1 DFT      of the SRS [s^i]G: [(s^m - 1) / (s w^j - 1)]G   (s w^j = 1: [m]G)
 The only group operation is one scalar multiplication of the generator by the C oracle (oracle_p1_mult).
+
+Torsion: points of each small prime order of the G1 cofactor h1, for the subgroup checks of the verifier
+(tests/test_das_boundaries_gpu.py).
 
 Recoding model: a restatement of the windowed recoding of the sort kernels and of the accumulation geometry, so that the
 tests can say which reference lands where and how many references (mixed additions) a job has:
@@ -16,6 +21,8 @@ tests can say which reference lands where and how many references (mixed additio
   * serial_span / group_span_limit ...  msm_finalize.hip: k_bucket_finalize, k_bucket_finalize_group, launch_small_msm
 """
 import bigint_twin as T
+import cells_oracle as CO
+import ntt_oracle as NO
 
 R = T.R
 HALF = (R - 1) // 2  # the largest folded magnitude
@@ -108,6 +115,91 @@ def multiproof(oracle, vals, zs, s, ys=None):
 
 def secret_be(s):
     return (s % R).to_bytes(32, "big")
+
+
+def cell_proof_scalars_fast(vals, K, t, s, cells=None):
+    """q_j(s) for the cells of a domain of N = 2^K points, cells of l = 2^t (cells_oracle order), O(N) in all: with
+    a_j = w_N^(j l) and the cell's points x_i = w_N^(j + M i),
+        q_j(s) = (P(s) - I_j(s)) / (s^l - a_j),   I_j(s) = (s^l - a_j) / (l a_j) sum_i v_i x_i / (s - x_i)
+    (barycentric over the coset {x : x^l = a_j}), so q_j(s) = P(s) / (s^l - a_j) - 1 / (l a_j) sum_i v_i x_i / (s - x_i).
+    When s^l = a_j (s is a point of cell j) the stride-l division of cells_oracle at s.  cells: the cell ids wanted
+    (all when None).  Returns {j: q_j(s)}."""
+    s %= R
+    N, l = 1 << K, 1 << t
+    M = N >> t
+    ids = range(M) if cells is None else cells
+    v = CO.cells(vals, K, t)
+    ps = poly_eval(vals, s)
+    sl = pow(s, l, R)
+    w = NO.domain_root(K)
+    l_inv = pow(l, R - 2, R)
+    out = {}
+    for j in ids:
+        a = CO.cell_root(K, t, j)
+        if sl == a:
+            out[j] = CO.poly_eval(CO.stride_quotient(vals, l, a), s)
+            continue
+        xs = [pow(w, j + M * i, R) for i in range(l)]
+        inv = NO.batch_inverse([(s - x) % R for x in xs] + [(sl - a) % R, a * l % R])
+        acc = sum(vi * x % R * d for vi, x, d in zip(v[j * l:(j + 1) * l], xs, inv)) % R
+        out[j] = (ps * inv[l] - acc * inv[l + 1]) % R
+    return out
+
+
+def srs_dft_scalars(s, m):
+    """the G1 DFT of the SRS (x_i = [s^i]G, i < m) over w_m: out_j = sum_i (s w^j)^i = (s^m - 1) / (s w^j - 1), and m
+    where s w^j = 1"""
+    s %= R
+    w = NO.domain_root(NO.log2_exact(m))
+    num = (pow(s, m, R) - 1) % R
+    out, x = [], s
+    dens = []
+    for j in range(m):
+        dens.append((x - 1) % R)
+        x = x * w % R
+    inv = NO.batch_inverse([d if d else 1 for d in dens])
+    for d, di in zip(dens, inv):
+        out.append(num * di % R if d else m % R)
+    return out
+
+
+# ---------------------------------------------------------------- torsion of E(Fp) outside G1
+Z_ABS = 0xD201000000010000
+H1 = (Z_ABS + 1) ** 2 // 3  # the G1 cofactor: #E(Fp) = h1 r
+TORSION_ORDERS = (3, 11, 10177, 859267, 52437899)  # h1 = 3 * 11^2 * 10177^2 * 859267^2 * 52437899^2
+
+
+def _curve_point(x):
+    """the point of y^2 = x^3 + 4 with the smallest abscissa >= x"""
+    while True:
+        y2 = (x * x * x + 4) % T.P
+        if pow(y2, (T.P - 1) // 2, T.P) == 1:
+            return x, pow(y2, (T.P + 1) // 4, T.P)
+        x += 1
+
+
+def torsion_points():
+    """{q: a point of order exactly q} for each prime q of the cofactor: [h1 r / q^e] R (q^e the q-part of h1) for curve
+    points R until one is not infinity, then multiplied by q while that leaves it finite (E(Fp) holds all of E[q] for the
+    squared primes, so [h1 r / q] R would always be infinity there)"""
+    out = {}
+    for q in TORSION_ORDERS:
+        qe = 1
+        while H1 % (qe * q) == 0:
+            qe *= q
+        x = 1
+        while True:
+            pt = T.g1_mul(_curve_point(x), H1 // qe * R)
+            if pt is not T.INF:
+                while T.g1_mul(pt, q) is not T.INF:
+                    pt = T.g1_mul(pt, q)
+                out[q] = pt
+                break
+            x += 1
+    return out
+
+
+ORDER3 = ((0, 2), (0, T.P - 2))  # x = 0: y^2 = 4
 
 
 # ---------------------------------------------------------------- recoding model (msm_sort.hip)

@@ -362,6 +362,57 @@ int kzg_verify_cells_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
                              const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k,
                              unsigned log_domain, unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes,
                              const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid);
+/* ---- openings at arbitrary points: evaluation of polynomials in evaluation form, one pairing for many openings ---------
+ * (DESIGN.md section 4.11).
+ * kzg_evaluate_evaluations_batch: P_b by its values over the n-domain (n = 2^k <= 2^KZG_NTT_MAX_LOG, natural order, as
+ * kzg_commit_evaluations takes them), polynomial b at evals + 4 b stride; out_ys[4 b ..] = P_b(z_b), canonical blst_fr.  The
+ * barycentric formula P(z) = (z^n - 1) / n sum_i f_i w^i / (z - w^i) on the device, no interpolation; a point inside the domain
+ * returns the value held there.  Needs no SRS.  Batches larger than a slot's staging buffers run in chunks.
+ * Errors: KZG_ERR_INVALID_ARG: n not a power of two or too large; a required pointer NULL; stride < n with batch > 1; a point
+ * or a value >= r (checked on the host; kzg_last_error names the polynomial).  batch = 0 does nothing; n = 1 returns the
+ * constant.  Thread safety as kzg_ntt (one slot per call); multi-device contexts run it on their first device. */
+int kzg_evaluate_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                   const uint64_t* zs, uint64_t* out_ys);
+/* kzg_verify_openings_batch: record t (t < k) claims that commitment commitment_idx[t] opens to ys + 4 t at the point zs + 4 t
+ * (blst_fr, Montgomery, any field elements: challenges, not domain indices) with the proof at proofs_p1 + 18 t -- the claim
+ * kzg_verify_proof checks with two pairings per record.  With the weights of kzg_verify_cells_batch (rho_t = a_t + b_t lambda,
+ * a_t, b_t uniform 64-bit from getrandom(2), fresh on every call) the device forms
+ *     LHS = sum_t rho_t pi_t,    RHS = sum_b U_b C_b - [sum_t rho_t y_t]G1 + sum_z [z] T_z,    T_z = sum_{t: z_t = z} rho_t pi_t
+ * and the host pairs once: e(LHS, [s]G2) == e(RHS, G2).  *valid = 1 when every record is valid; a batch with an invalid
+ * record is accepted with probability at most 2^-128.  The records are grouped by distinct point: one point shared by many
+ * polynomials costs one full scalar multiplication, every record a 64-step one.
+ * Inputs: points are blst_p1 (all-zero: infinity); [1]G1 is the context's SRS[0]; setup_g2 is read at indices 0 ([1]G2) and 1
+ * ([s]G2), g2_stride_bytes apart, as kzg_verify_points reads it.  Repeated records and repeated points are allowed; k = 0
+ * gives *valid = 1.
+ * Errors (kzg_last_error names the record or the commitment):
+ *   KZG_ERR_INVALID_ARG: k or num_commitments > KZG_VERIFY_MAX_OPENINGS; a required pointer NULL; commitment_idx[t] >=
+ *     num_commitments; a point or a value >= r (checked on the host); a G1 coordinate not below p; a G2 input off the twist;
+ *     then, from the device, a proof or commitment off the curve or outside G1 (the order-r subgroup; infinity passes).
+ *   KZG_ERR_NO_SRS: the SRS is empty.
+ *   KZG_ERR_HIP: a device call failed, or the OS random source did.
+ * Thread safety and multi-device contexts as kzg_verify_cells_batch (a replicated SRS forwards to one device, a range-split one
+ * returns KZG_ERR_INVALID_ARG).  A call costs about 10 ms whatever k is up to some thousand records, so for few records
+ * kzg_verify_proof_batch on the host (min(hardware threads, n) threads) stays the faster route.  Measured crossover (DESIGN.md
+ * section 5.0f): between 32 and 48 records with the process held to 16 CPUs, between 256 and 384 records with all 256 CPUs
+ * of the same box open to it.  Below it keep using the host batch. */
+#define KZG_VERIFY_MAX_OPENINGS (1u << 20)
+int kzg_verify_openings_batch(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                              const uint64_t* zs, const uint64_t* ys, const uint64_t* proofs_p1, size_t k, const void* setup_g2,
+                              size_t g2_stride_bytes, int* valid);
+/* test hook: the same with the caller's weights (k x blst_fr, any field elements below r) instead of random ones; returns the
+ * two G1 sides, normalised like kzg_open's output, and *valid from the same pairing */
+int kzg_verify_openings_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                                const uint64_t* zs, const uint64_t* ys, const uint64_t* proofs_p1, size_t k, const void* setup_g2,
+                                size_t g2_stride_bytes, const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18],
+                                int* valid);
+/* The two together, for a verifier that holds the polynomials in evaluation form (blobs): polynomial b (laid out as for
+ * kzg_evaluate_evaluations_batch) is claimed to have commitment commitments_p1 + 18 b and the opening proof proofs_p1 + 18 b at
+ * the caller's challenge zs + 4 b.  The values y_b = P_b(z_b) are computed on the device and go into the check without
+ * leaving it; out_ys (batch x blst_fr, may be NULL) receives them.  The challenges are the caller's (no hashing here).
+ * Errors: those of the two calls above (batch in the place of k and of num_commitments). */
+int kzg_verify_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                 const uint64_t* commitments_p1, const uint64_t* zs, const uint64_t* proofs_p1,
+                                 const void* setup_g2, size_t g2_stride_bytes, uint64_t* out_ys, int* valid);
 /* test hook: DFT (inverse != 0: inverse DFT incl. 1/m) of m = 2^k <= 2^22 host blst_p1 points over w_m, normalised
  * output (out_p1[j] = sum_i [w_m^(i j)] in_p1[i]); needs no SRS.  The points must lie in G1 (the order-r subgroup): the
  * twiddle products use the endomorphism (x, y) -> (beta x, y) = [z^2 - 1](x, y), which holds there only; nothing checks it */

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "kzg_open_evaluations", "kzg_cells_and_proofs", "kzg_cells_and_proofs_evaluations", "kzg_quotient_cells",
     "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft", "kzg_recover_cells_and_proofs",
     "kzg_verify_cells_batch", "kzg_verify_cells_lincomb",
+    "kzg_evaluate_evaluations_batch", "kzg_verify_openings_batch", "kzg_verify_openings_lincomb", "kzg_verify_evaluations_batch",
 ]
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
@@ -162,6 +163,10 @@ def load_library():
         "kzg_recover_cells_and_proofs": (i, [vp, sz, C.c_uint, C.c_uint, vp, sz, vp, sz, vp, vp, vp]),
         "kzg_verify_cells_batch": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, vp, sz, C.POINTER(i)]),
         "kzg_verify_cells_lincomb": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, vp, sz, vp, vp, vp, C.POINTER(i)]),
+        "kzg_evaluate_evaluations_batch": (i, [vp, vp, sz, sz, sz, vp, vp]),
+        "kzg_verify_openings_batch": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
+        "kzg_verify_openings_lincomb": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, C.POINTER(i)]),
+        "kzg_verify_evaluations_batch": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp, sz, vp, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -558,6 +563,87 @@ class Engine:
         _check(self._lib.kzg_verify_cells_lincomb(self._h, *a, log_domain, log_cell, _ptr(keep[5]), 288, _ptr(w), _ptr(lhs),
                                                   _ptr(rhs), C.byref(ok)), self._h)
         return G1Point(lhs), G1Point(rhs), bool(ok.value)
+
+    # -- openings at arbitrary points --
+    @staticmethod
+    def _fr_rows(values):
+        """Scalars or blst_fr rows -> (k, 4) uint64"""
+        if isinstance(values, np.ndarray):
+            return np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        return _scalar_rows(list(values)) if len(values) else np.zeros((0, 4), dtype=np.uint64)
+
+    @staticmethod
+    def _p1_rows(pts):
+        pts = list(pts)
+        if not pts:
+            return np.zeros((0, 18), dtype=np.uint64)
+        return np.ascontiguousarray(np.stack([p.p1 if isinstance(p, G1Point) else np.asarray(p, dtype=np.uint64) for p in pts]),
+                                    dtype=np.uint64).reshape(-1, 18)
+
+    def evaluate_evaluations_batch(self, evals, zs):
+        """kzg_evaluate_evaluations_batch: evals a (batch, n, 4) array (or one (n, 4) polynomial) of values over the n-domain,
+        zs one point per polynomial (Scalars or blst_fr rows).  Returns the P_b(z_b) as a list of Scalars"""
+        a = np.ascontiguousarray(evals, dtype=np.uint64)
+        if a.ndim != 3:
+            a = a.reshape(1, a.size // 4, 4)
+        batch, n = a.shape[0], a.shape[1]
+        zl = self._fr_rows(zs)
+        assert zl.shape[0] == batch, "one point per polynomial"
+        out = np.zeros((max(batch, 1), 4), dtype=np.uint64)
+        _check(self._lib.kzg_evaluate_evaluations_batch(self._h, _ptr(a), n, batch, n, _ptr(zl) if batch else None, _ptr(out)),
+               self._h)
+        return [Scalar.from_limbs(out[b]) for b in range(batch)]
+
+    def _verify_openings_args(self, commitments, commitment_idx, zs, ys, proofs, setup_g2):
+        com, prf = self._p1_rows(commitments), self._p1_rows(proofs)
+        idx = np.ascontiguousarray(commitment_idx, dtype=np.uint32).reshape(-1)
+        zl, yl = self._fr_rows(zs), self._fr_rows(ys)
+        k = len(idx)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert zl.shape[0] == k and yl.shape[0] == k and prf.shape[0] == k, "one index, point, value and proof per record"
+        keep = (com, prf, idx, zl, yl, g2)
+        return keep, (_ptr(com) if com.size else None, com.shape[0], _ptr(idx) if k else None, _ptr(zl) if k else None,
+                      _ptr(yl) if k else None, _ptr(prf) if k else None, k, _ptr(g2), 288)
+
+    def verify_openings_batch(self, commitments, commitment_idx, zs, ys, proofs, setup_g2):
+        """kzg_verify_openings_batch: checks k openings at arbitrary points with one pairing (random weights).  Record t
+        claims that commitments[commitment_idx[t]] opens to ys[t] at zs[t] with proofs[t]; setup_g2: blst_p2 rows [1]G2,
+        [s]G2.  Returns True when every record is valid"""
+        keep, a = self._verify_openings_args(commitments, commitment_idx, zs, ys, proofs, setup_g2)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_openings_batch(self._h, *a, C.byref(ok)), self._h)
+        return bool(ok.value)
+
+    def verify_openings_lincomb(self, commitments, commitment_idx, zs, ys, proofs, setup_g2, weights):
+        """the test hook kzg_verify_openings_lincomb: the same check with the given weights (k blst_fr rows, or Scalars).
+        Returns (lhs, rhs, valid): the two G1 sides as G1Points and the pairing's answer"""
+        keep, a = self._verify_openings_args(commitments, commitment_idx, zs, ys, proofs, setup_g2)
+        w = self._fr_rows(weights)
+        if not w.shape[0]:
+            w = np.zeros((1, 4), dtype=np.uint64)
+        lhs = np.zeros(18, dtype=np.uint64)
+        rhs = np.zeros(18, dtype=np.uint64)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_openings_lincomb(self._h, *a, _ptr(w), _ptr(lhs), _ptr(rhs), C.byref(ok)), self._h)
+        return G1Point(lhs), G1Point(rhs), bool(ok.value)
+
+    def verify_evaluations_batch(self, evals, commitments, zs, proofs, setup_g2, want_ys=True):
+        """kzg_verify_evaluations_batch: polynomial b of evals ((batch, n, 4) values over the n-domain) is claimed to have
+        commitments[b] and the opening proofs[b] at zs[b].  Returns (valid, ys): ys the values P_b(z_b) the device computed
+        (None when want_ys is False)"""
+        a = np.ascontiguousarray(evals, dtype=np.uint64)
+        if a.ndim != 3:
+            a = a.reshape(1, a.size // 4, 4)
+        batch, n = a.shape[0], a.shape[1]
+        com, prf, zl = self._p1_rows(commitments), self._p1_rows(proofs), self._fr_rows(zs)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert com.shape[0] == batch and prf.shape[0] == batch and zl.shape[0] == batch
+        out = np.zeros((max(batch, 1), 4), dtype=np.uint64) if want_ys else None
+        ok = C.c_int(0)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        _check(self._lib.kzg_verify_evaluations_batch(self._h, _ptr(a), n, batch, n, opt(com), opt(zl), opt(prf), _ptr(g2), 288,
+                                                      opt(out), C.byref(ok)), self._h)
+        return bool(ok.value), ([Scalar.from_limbs(out[b]) for b in range(batch)] if want_ys else None)
 
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""

@@ -3009,12 +3009,12 @@ static int vc_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
     *out = ctx->vc_ws[i];
     return KZG_OK;
 }
-static int vc_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
+static int vc_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const char* what = "verify cells") {
     lk.unlock();
     const hipError_t e = hipStreamSynchronize(st);
     lk.lock();
     if (e != hipSuccess) {
-        ctx->last_error = std::string("verify cells: ") + hipGetErrorString(e);
+        ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
         return KZG_ERR_HIP;
     }
     return KZG_OK;
@@ -3034,6 +3034,13 @@ struct VcBatch {
     std::vector<Glv> glv;         // per record (input order): its weight as k1 + k2 lambda
     std::vector<Fr30> rho30;      // per sorted position: the weight in multiplier form
     std::vector<hf::Fr> U;        // per commitment: the sum of its records' weights (Montgomery)
+    // openings at arbitrary points (kzg_verify_openings_batch) run the same plan with l = 1: the
+    // records are grouped by distinct point, ids = 0 .. D - 1, and [z_d] T_d reads points[d], the split z_d, where the cells
+    // read the context's split twiddles
+    std::vector<Glv> points;
+    const uint32_t* d_values = nullptr;  // the values are on the device already (in the kVcCells workspace): no upload
+    bool fk20_held = false;              // the caller holds ctx->fk20_mu
+    const char* what = "verify cells";
 };
 }  // namespace
 
@@ -3042,20 +3049,26 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     const CellsShape& sh = *vb.sh;
     const size_t K = vb.k, B = vb.B, l = sh.l, D = vb.ids.size();
     const uint32_t log_M = sh.log_n - sh.log_l;
-    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    const bool pts = !vb.points.empty();
+    const std::string what = vb.what;
+    // fk20_mu guards the workspaces (and d_glv).  kzg_verify_evaluations_batch takes it itself, before it puts the values into
+    // the kVcCells workspace, and keeps it until this call returns: then vb.fk20_held is set and it is not taken again here.
+    std::unique_lock<std::mutex> lkf(ctx->fk20_mu, std::defer_lock);
+    if (!vb.fk20_held) lkf.lock();
     std::unique_lock<std::mutex> lk(ctx->mu);
     if (!ctx->n || !ctx->slots_ready || ctx->n < l) {
-        ctx->last_error = "verify cells: the SRS holds fewer than l points";
+        ctx->last_error = what + (pts ? ": the SRS is empty" : ": the SRS holds fewer than l points");
         return KZG_ERR_NO_SRS;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_ntt(ctx);
+    int rc = pts ? KZG_OK : ensure_ntt(ctx);
     if (rc) return rc;
     const int slot = reserve_slot(ctx, lk, true);
     if (slot < 0) return KZG_ERR_BUSY;
     SlotLease lease{ctx, slot};
     Slot& s = ctx->slots[slot];
-    rc = ensure_glv(ctx, lk, log_M, s.stream);
+    rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK && !pts) rc = ensure_glv(ctx, lk, log_M, s.stream);
     if (rc) return rc;
     // plans: T_j by cell id; the column sums of the twisted rows (one segment of D); the two sides over [T | C | S | AT]
     VcPlan plan_t, plan_col, plan_fin;
@@ -3085,7 +3098,10 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
         glv[K + b] = glv_split(vb.U[b]);
     }
     void *cells, *fa, *fb, *coef, *order, *rho, *ids, *dstarts, *p1, *aff, *prefix, *dsrc, *dglv, *dglvs, *g1, *scratch;
-    rc = vc_ws(ctx, kVcCells, K * l * 32, &cells);
+    // values already on the device ARE the kVcCells workspace: asking for it again could free and reallocate it (vc_ws drops
+    // the contents when it grows)
+    if (vb.d_values) cells = (void*)vb.d_values;
+    else rc = vc_ws(ctx, kVcCells, K * l * 32, &cells);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrA, g0 * l * 32, &fa);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrB, g0 * l * 32, &fb);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, l * 32 + 8, &coef);  // + the two error words
@@ -3098,12 +3114,14 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcPrefix, lanes * 64, &prefix);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcSrc, lanes * 4, &dsrc);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlv, lanes * sizeof(Glv), &dglv);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlvSrs, l * sizeof(Glv), &dglvs);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlvSrs, (l + vb.points.size()) * sizeof(Glv), &dglvs);  // then the split points
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcG1, (K + 2 * D + B + l + 2) * kXyzzBytes, &g1);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
     if (rc) return rc;
     const hipStream_t st = s.stream;
-    HIP_TRY(ctx, hipMemcpyAsync(cells, vb.cells, K * l * 32, hipMemcpyHostToDevice, st));
+    if (!vb.d_values) HIP_TRY(ctx, hipMemcpyAsync(cells, vb.cells, K * l * 32, hipMemcpyHostToDevice, st));
+    Glv* dpoints = (Glv*)dglvs + l;
+    if (pts) HIP_TRY(ctx, hipMemcpyAsync(dpoints, vb.points.data(), D * sizeof(Glv), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(order, vb.order.data(), K * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(rho, vb.rho30.data(), K * sizeof(Fr30), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(ids, vb.ids.data(), D * 4, hipMemcpyHostToDevice, st));
@@ -3125,10 +3143,12 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
         cur = dst;
     }
     const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
-    uint32_t* y = const_cast<uint32_t*>(launch_fr_dft(st, cur, FA, FB, sh.log_l, D, tw + 2 * kNttTableLen));
-    launch_vc_fr_twist(st, y, (const uint32_t*)ids, (uint32_t)D, tw + 2 * kNttTableLen, sh.log_n, sh.log_l,
-                       fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.log_l))));
-    cur = y;
+    if (!pts) {  // (a point's "interpolant" is its value: nothing to transform)
+        uint32_t* y = const_cast<uint32_t*>(launch_fr_dft(st, cur, FA, FB, sh.log_l, D, tw + 2 * kNttTableLen));
+        launch_vc_fr_twist(st, y, (const uint32_t*)ids, (uint32_t)D, tw + 2 * kNttTableLen, sh.log_n, sh.log_l,
+                           fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.log_l))));
+        cur = y;
+    }
     for (size_t lv = 0; lv < plan_col.size(); lv++) {
         uint32_t* dst = lv + 1 == plan_col.size() ? (uint32_t*)coef : (cur == FA ? FB : FA);
         launch_vc_fr_sum(st, cur, nullptr, nullptr, dst_ + at_col[lv], (uint32_t)(plan_col[lv].size() - 1), sh.log_l, dst);
@@ -3150,9 +3170,10 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
         }
     };
     g1_plan(plan_t, at_t, rec(0), rec(oT));
-    launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, (const Glv*)ctx->d_glv, ctx->glv_log - log_M, rec(oAT));
+    if (pts) launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, dpoints, 0, rec(oAT));
+    else launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, (const Glv*)ctx->d_glv, ctx->glv_log - log_M, rec(oAT));
     HIP_TRY(ctx, hipGetLastError());
-    rc = vc_sync(ctx, lk, st);
+    rc = vc_sync(ctx, lk, st, what.c_str());
     if (rc) return rc;
     std::vector<hf::Fr> A(l);
     uint32_t herr[2];
@@ -3162,9 +3183,9 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     if (rc) return rc;
     for (int e = 0; e < 2; e++)
         if (herr[e] != 0xffffffffu) {
-            const std::string what = herr[e] < K ? "the proof of record " + std::to_string(herr[e])
+            const std::string who = herr[e] < K ? "the proof of record " + std::to_string(herr[e])
                                                  : "commitment " + std::to_string(herr[e] - K);
-            ctx->last_error = "verify cells: " + what + (e ? " is not in G1" : " is not on the curve");
+            ctx->last_error = what + ": " + who + (e ? " is not in G1" : " is not on the curve");
             return KZG_ERR_INVALID_ARG;
         }
     // -[A(s)]G1 = sum_i [-A_i] [s^i]G1
@@ -3185,6 +3206,84 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     if (rc) return rc;
     std::memcpy(out_lhs, sides, 144);
     std::memcpy(out_rhs, sides + 18, 144);
+    return KZG_OK;
+}
+
+// G1 inputs: canonical coordinates, and not the all-zero affine image of a finite point (the device's infinity); the curve
+// and subgroup checks run on the device
+static bool vc_p1_malformed(const uint64_t* w) {
+    hf::P1 p;
+    std::memcpy(&p, w, sizeof p);
+    if (!hf::geq(p.x, hf::kP) && !hf::geq(p.y, hf::kP) && !hf::geq(p.z, hf::kP))
+        return !p.z.is_zero() && p.x.is_zero() && p.y.is_zero();
+    return true;
+}
+// the weights of k records: rho = a + b lambda with a, b uniform 64-bit from the OS CSPRNG (a plain integer below 2^193 < r),
+// or the caller's (validated below r); rho in Montgomery form, glv its split
+static int vc_weights(kzg_ctx* ctx, const char* what, const uint64_t* weights, size_t k, std::vector<hf::Fr>* rho,
+                      std::vector<Glv>* glv) {
+    rho->resize(k);
+    glv->resize(k);
+    if (weights) {
+        for (size_t t = 0; t < k; t++) {
+            std::memcpy((*rho)[t].l, weights + 4 * t, 32);
+            (*glv)[t] = glv_split((*rho)[t]);
+        }
+        return KZG_OK;
+    }
+    std::vector<uint64_t> ab(2 * k);
+    if (!vc_random(ab.data(), ab.size() * 8)) {
+        ctx->last_error = std::string(what) + ": getrandom: " + std::strerror(errno);
+        return KZG_ERR_HIP;
+    }
+    for (size_t t = 0; t < k; t++) {
+        const uint64_t a = ab[2 * t], b = ab[2 * t + 1];
+        const unsigned __int128 lo = (unsigned __int128)b * (uint64_t)kGlvLambda + a;
+        const unsigned __int128 hi = (unsigned __int128)b * (uint64_t)(kGlvLambda >> 64) + (uint64_t)(lo >> 64);
+        const hf::Fr raw = {{(uint64_t)lo, (uint64_t)hi, (uint64_t)(hi >> 64), 0}};
+        (*rho)[t] = hf::fr_mul(raw, kFrR2);  // Montgomery
+        (*glv)[t] = Glv{{a, 0}, {b, 0}};
+    }
+    return KZG_OK;
+}
+// e(LHS, Q) == e(RHS, G2):  e(LHS, Q) e(-RHS, G2) == 1
+static int vc_pair(const uint64_t lhs[18], const uint64_t rhs[18], const hf::G2Affine& q, const hf::G2Affine& g2_one) {
+    hf::P1 L, R;
+    std::memcpy(&L, lhs, sizeof L);
+    std::memcpy(&R, rhs, sizeof R);
+    const hf::G2Affine qs[2] = {q, g2_one};
+    const hf::P1 ps[2] = {L, hf::p1_neg(R)};
+    bool ok = true;
+    const hf::F12 f = hf::multi_miller_loop(qs, ps, 2, ok);
+    return ok && hf::f12_is_one(hf::f12_final_exp(f)) ? 1 : 0;
+}
+
+// what the two verifiers check alike on the host: the caller's weights below r (weights null: random ones will be drawn), the
+// G1 inputs well formed, setup_g2[0] and setup_g2[second] on the twist (into g2[0], g2[1]); second_name: how the error text
+// calls that index
+static int vc_check_inputs(kzg_ctx* ctx, const char* what, const uint64_t* weights, const uint64_t* proofs_p1, size_t k,
+                           const uint64_t* commitments_p1, size_t num_commitments, const void* setup_g2, size_t g2_stride_bytes,
+                           size_t second, const char* second_name, hf::G2Affine g2[2]) {
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (weights)
+        for (size_t t = 0; t < k; t++) {
+            hf::Fr v;
+            std::memcpy(v.l, weights + 4 * t, 32);
+            if (hf::fr_geq(v, hf::kFrMod)) return invalid("weight " + std::to_string(t) + " is not below r");
+        }
+    for (size_t t = 0; t < k; t++)
+        if (vc_p1_malformed(proofs_p1 + 18 * t)) return invalid("the proof of record " + std::to_string(t) + " is not on the curve");
+    for (size_t b = 0; b < num_commitments; b++)
+        if (vc_p1_malformed(commitments_p1 + 18 * b)) return invalid("commitment " + std::to_string(b) + " is not on the curve");
+    for (int i = 0; i < 2; i++) {
+        uint64_t raw[36];
+        std::memcpy(raw, (const uint8_t*)setup_g2 + (i ? second : 0) * g2_stride_bytes, sizeof raw);
+        g2[i] = hf::g2_from_p2(raw);
+        if (!hf::g2_on_curve(g2[i])) return invalid(std::string("setup_g2[") + (i ? second_name : "0") + "] is not on the twist");
+    }
     return KZG_OK;
 }
 
@@ -3228,31 +3327,11 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
             if (hf::fr_geq(v, hf::kFrMod))
                 return invalid("record " + std::to_string(t) + ": value " + std::to_string(i) + " is not below r");
         }
-    if (want_weights)
-        for (size_t t = 0; t < k; t++) {
-            hf::Fr v;
-            std::memcpy(v.l, weights + 4 * t, 32);
-            if (hf::fr_geq(v, hf::kFrMod)) return invalid("weight " + std::to_string(t) + " is not below r");
-        }
-    // G1 inputs: canonical coordinates, and not the all-zero affine image of a finite point (the device's infinity);
-    // the curve and subgroup checks run on the device
-    auto p1_malformed = [](const uint64_t* w) {
-        hf::P1 p;
-        std::memcpy(&p, w, sizeof p);
-        if (!hf::geq(p.x, hf::kP) && !hf::geq(p.y, hf::kP) && !hf::geq(p.z, hf::kP))
-            return !p.z.is_zero() && p.x.is_zero() && p.y.is_zero();
-        return true;
-    };
-    for (size_t t = 0; t < k; t++)
-        if (p1_malformed(proofs_p1 + 18 * t)) return invalid("the proof of record " + std::to_string(t) + " is not on the curve");
-    for (size_t b = 0; b < num_commitments; b++)
-        if (p1_malformed(commitments_p1 + 18 * b)) return invalid("commitment " + std::to_string(b) + " is not on the curve");
     hf::G2Affine g2[2];
-    for (int i = 0; i < 2; i++) {
-        uint64_t raw[36];
-        std::memcpy(raw, (const uint8_t*)setup_g2 + (i ? sh.l : 0) * g2_stride_bytes, sizeof raw);
-        g2[i] = hf::g2_from_p2(raw);
-        if (!hf::g2_on_curve(g2[i])) return invalid(std::string("setup_g2[") + (i ? "l" : "0") + "] is not on the twist");
+    {
+        const int rci = vc_check_inputs(ctx, "verify cells", want_weights ? weights : nullptr, proofs_p1, k, commitments_p1,
+                                        num_commitments, setup_g2, g2_stride_bytes, sh.l, "l", g2);
+        if (rci) return rci;
     }
     if (ctx->multi) {
         int rc = KZG_OK;
@@ -3268,28 +3347,10 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
     vb.commitments = commitments_p1;
     vb.cells = cells;
     vb.proofs = proofs_p1;
-    // weights: rho = a + b lambda with a, b uniform 64-bit from the OS CSPRNG (a plain integer below 2^193 < r), or given
-    std::vector<hf::Fr> rho(k);
-    vb.glv.resize(k);
-    if (want_weights) {
-        for (size_t t = 0; t < k; t++) {
-            std::memcpy(rho[t].l, weights + 4 * t, 32);
-            vb.glv[t] = glv_split(rho[t]);
-        }
-    } else {
-        std::vector<uint64_t> ab(2 * k);
-        if (!vc_random(ab.data(), ab.size() * 8)) {
-            ctx->last_error = std::string("verify cells: getrandom: ") + std::strerror(errno);
-            return KZG_ERR_HIP;
-        }
-        for (size_t t = 0; t < k; t++) {
-            const uint64_t a = ab[2 * t], b = ab[2 * t + 1];
-            const unsigned __int128 lo = (unsigned __int128)b * (uint64_t)kGlvLambda + a;
-            const unsigned __int128 hi = (unsigned __int128)b * (uint64_t)(kGlvLambda >> 64) + (uint64_t)(lo >> 64);
-            const hf::Fr raw = {{(uint64_t)lo, (uint64_t)hi, (uint64_t)(hi >> 64), 0}};
-            rho[t] = hf::fr_mul(raw, kFrR2);  // Montgomery
-            vb.glv[t] = Glv{{a, 0}, {b, 0}};
-        }
+    std::vector<hf::Fr> rho;
+    {
+        const int rcw = vc_weights(ctx, "verify cells", want_weights ? weights : nullptr, k, &rho, &vb.glv);
+        if (rcw) return rcw;
     }
     // records sorted by cell id (counting sort), the distinct ids and their counts
     std::vector<uint32_t> count(sh.cells + 1, 0);
@@ -3315,15 +3376,7 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
         std::memcpy(out_lhs, lhs, sizeof lhs);
         std::memcpy(out_rhs, rhs, sizeof rhs);
     }
-    // e(LHS, [s^l]G2) == e(RHS, G2):  e(LHS, [s^l]G2) e(-RHS, G2) == 1
-    hf::P1 L, R;
-    std::memcpy(&L, lhs, sizeof L);
-    std::memcpy(&R, rhs, sizeof R);
-    const hf::G2Affine qs[2] = {g2[1], g2[0]};
-    const hf::P1 ps[2] = {L, hf::p1_neg(R)};
-    bool ok = true;
-    const hf::F12 f = hf::multi_miller_loop(qs, ps, 2, ok);
-    *valid = ok && hf::f12_is_one(hf::f12_final_exp(f)) ? 1 : 0;
+    *valid = vc_pair(lhs, rhs, g2[1], g2[0]);  // e(LHS, [s^l]G2) == e(RHS, G2)
     return KZG_OK;
 }
 
@@ -3340,6 +3393,297 @@ int kzg_verify_cells_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
                              const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid) {
     return verify_cells_impl(ctx, commitments_p1, num_commitments, commitment_idx, cell_ids, cells, proofs_p1, k, log_domain, log_cell,
                              setup_g2, g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid);
+}
+
+// ---- openings at arbitrary points: barycentric evaluation and one pairing for many openings (bary_kernels.hip, the kernels
+// of verify_kernels.hip) ------------------------------------------------------------------------------
+namespace {
+constexpr size_t kBaryChunkValues = (size_t)1 << kNttMaxLog;  // values one pass of the evaluation stages in a slot, at most
+constexpr size_t kBaryMinValues = 8;  // staging room per polynomial, in values: its partials, its point and its result fit
+}  // namespace
+
+// P_b(z_b) for every polynomial of the batch, in chunks through one slot's staging buffers.  d_ys (device, 8 words per
+// polynomial) receives the values when given; out_ys (host) when given.  Validated arguments, single-device context.
+static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t batch, size_t stride, const uint64_t* zs,
+                     uint32_t* d_ys, uint64_t* out_ys) {
+    const size_t n = (size_t)1 << lg;
+    std::vector<Fr30> z30(batch);
+    for (size_t b = 0; b < batch; b++) {
+        hf::Fr z;
+        std::memcpy(z.l, zs + 4 * b, 32);
+        z30[b] = fr30_arg_from_mont256(z);
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    const size_t per = std::max(n, kBaryMinValues);
+    const size_t chunk = std::min(batch, std::max<size_t>(1, kBaryChunkValues / per));
+    rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, chunk * per);
+    if (rc) return rc;
+    const uint32_t tiles = bary_tiles(lg);
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
+    // d_q: [partials: chunk x tiles records | points: chunk Fr30 | results: chunk x 8 words]
+    uint32_t* partial = s.d_q;
+    Fr30* dz = (Fr30*)(partial + chunk * tiles * kBaryPartialWords);
+    uint32_t* res = (uint32_t*)(dz + chunk);
+    res += (4 - ((res - s.d_q) & 3)) & 3;  // 16-byte aligned
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t bc = std::min(chunk, batch - b0);
+        if (stride == n || bc == 1)
+            HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, evals + 4 * b0 * stride, bc * n * 32, hipMemcpyHostToDevice, s.stream));
+        else
+            HIP_TRY(ctx, hipMemcpy2DAsync(s.d_stage, n * 32, evals + 4 * b0 * stride, stride * 32, n * 32, bc, hipMemcpyHostToDevice,
+                                          s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dz, z30.data() + b0, bc * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+        uint32_t* out = d_ys ? d_ys + 8 * b0 : res;
+        launch_bary(s.stream, s.d_stage, lg, (uint32_t)bc, dz, ctx->d_ntt_tw, inv_n, partial, out);
+        HIP_TRY(ctx, hipGetLastError());
+        if (out_ys) HIP_TRY(ctx, hipMemcpyAsync(out_ys + 4 * b0, out, bc * 32, hipMemcpyDeviceToHost, s.stream));
+        rc = vc_sync(ctx, lk, s.stream, "evaluate evaluations");
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+
+// a call forwarded to a device's context before its inputs were checked: the parent reports what that context found
+static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
+    if (rc) ctx->last_error = kid->last_error;
+    return rc;
+}
+
+// the arguments of the two evaluation-form entry points; *lg receives log2 n
+static int bary_check(kzg_ctx* ctx, const char* what, const uint64_t* evals, size_t n, size_t batch, size_t stride,
+                      const uint64_t* zs, uint32_t* lg) {
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (!ntt_log(n, lg)) return invalid("n is not a power of two up to 2^KZG_NTT_MAX_LOG");
+    if (batch && (!evals || !zs)) return invalid("a required pointer is NULL");
+    if (batch > 1 && stride < n) return invalid("stride < n");
+    return KZG_OK;
+}
+// ... and their points and values below r (after a multi-device context has forwarded: its device's context checks them)
+static int bary_check_values(kzg_ctx* ctx, const char* what, const uint64_t* evals, size_t n, size_t batch, size_t stride,
+                             const uint64_t* zs) {
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    for (size_t b = 0; b < batch; b++) {
+        hf::Fr v;
+        std::memcpy(v.l, zs + 4 * b, 32);
+        if (hf::fr_geq(v, hf::kFrMod)) return invalid("polynomial " + std::to_string(b) + ": the point is not below r");
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(v.l, evals + 4 * (b * stride + i), 32);
+            if (hf::fr_geq(v, hf::kFrMod))
+                return invalid("polynomial " + std::to_string(b) + ": value " + std::to_string(i) + " is not below r");
+        }
+    }
+    return KZG_OK;
+}
+
+int kzg_evaluate_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                   const uint64_t* zs, uint64_t* out_ys) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    uint32_t lg = 0;
+    const int rc = bary_check(ctx, "evaluate evaluations", evals_fr_mont, n, batch, stride, zs, &lg);
+    if (rc) return rc;
+    if (batch && !out_ys) {
+        ctx->last_error = "evaluate evaluations: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!batch) return KZG_OK;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_evaluate_evaluations_batch(kid, evals_fr_mont, n, batch, stride, zs, out_ys));
+    }
+    const int rcv = bary_check_values(ctx, "evaluate evaluations", evals_fr_mont, n, batch, stride, zs);
+    if (rcv) return rcv;
+    return bary_host(ctx, evals_fr_mont, lg, batch, stride, zs, nullptr, out_ys);
+}
+
+// Record t: commitment commitment_idx[t] (t itself when commitment_idx is null) opens to y_t at z_t with proof t.  ys on the
+// host, or d_ys: the k values in the kVcCells workspace already (fk20_mu held by the caller).  weights as verify_cells_impl.
+static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                                const uint64_t* zs, const uint64_t* ys, const uint32_t* d_ys, const uint64_t* proofs_p1, size_t k,
+                                const void* setup_g2, size_t g2_stride_bytes, const uint64_t* weights, bool want_weights,
+                                uint64_t* out_lhs, uint64_t* out_rhs, int* valid) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    const char* what = "verify openings";
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (k > KZG_VERIFY_MAX_OPENINGS) return invalid("more than KZG_VERIFY_MAX_OPENINGS records");
+    if (num_commitments > KZG_VERIFY_MAX_OPENINGS) return invalid("more than KZG_VERIFY_MAX_OPENINGS commitments");
+    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !commitments_p1) ||
+        (k && ((!commitment_idx && !d_ys) || !zs || (!ys && !d_ys) || !proofs_p1 || !setup_g2 || (want_weights && !weights))))
+        return invalid("a required pointer is NULL");
+    if (!k) {
+        if (want_weights) {
+            const hf::P1 inf = hf::p1_inf();
+            write_p1(out_lhs, inf);
+            write_p1(out_rhs, inf);
+        }
+        *valid = 1;
+        return KZG_OK;
+    }
+    if (ctx->multi) {  // before the O(k) checks, which the device's context makes (kzg_verify_evaluations_batch forwards itself)
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, verify_openings_impl(kid, commitments_p1, num_commitments, commitment_idx, zs, ys, d_ys,
+                                                              proofs_p1, k, setup_g2, g2_stride_bytes, weights, want_weights,
+                                                              out_lhs, out_rhs, valid))
+                   : rc;
+    }
+    if (commitment_idx)
+        for (size_t t = 0; t < k; t++)
+            if (commitment_idx[t] >= num_commitments)
+                return invalid("record " + std::to_string(t) + ": commitment index " + std::to_string(commitment_idx[t]) +
+                               " is not below num_commitments");
+    if (ys)  // (with d_ys the caller has checked the points and the device has made the values)
+        for (size_t t = 0; t < k; t++) {
+            hf::Fr v;
+            std::memcpy(v.l, zs + 4 * t, 32);
+            if (hf::fr_geq(v, hf::kFrMod)) return invalid("record " + std::to_string(t) + ": the point is not below r");
+            std::memcpy(v.l, ys + 4 * t, 32);
+            if (hf::fr_geq(v, hf::kFrMod)) return invalid("record " + std::to_string(t) + ": the value is not below r");
+        }
+    hf::G2Affine g2[2];
+    {
+        const int rci = vc_check_inputs(ctx, what, want_weights ? weights : nullptr, proofs_p1, k, commitments_p1, num_commitments,
+                                        setup_g2, g2_stride_bytes, 1, "1", g2);
+        if (rci) return rci;
+    }
+    CellsShape sh;
+    cells_shape(0, 0, 0, &sh);  // l = 1
+    VcBatch vb;
+    vb.sh = &sh;
+    vb.k = k;
+    vb.B = num_commitments;
+    vb.commitments = commitments_p1;
+    vb.cells = ys;
+    vb.d_values = d_ys;
+    vb.fk20_held = d_ys != nullptr;
+    vb.proofs = proofs_p1;
+    vb.what = what;
+    std::vector<hf::Fr> rho;
+    {
+        const int rcw = vc_weights(ctx, what, want_weights ? weights : nullptr, k, &rho, &vb.glv);
+        if (rcw) return rcw;
+    }
+    // records sorted by point (the 32-byte images, ties by record), the distinct points and their counts
+    vb.order.resize(k);
+    for (size_t t = 0; t < k; t++) vb.order[t] = (uint32_t)t;
+    std::sort(vb.order.begin(), vb.order.end(), [&](uint32_t a, uint32_t b) {
+        const int c = std::memcmp(zs + 4 * a, zs + 4 * b, 32);
+        return c ? c < 0 : a < b;
+    });
+    for (size_t t = 0; t < k; t++) {
+        const uint64_t* z = zs + 4 * vb.order[t];
+        if (t && !std::memcmp(z, zs + 4 * vb.order[t - 1], 32)) {
+            vb.lens.back()++;
+            continue;
+        }
+        hf::Fr v;
+        std::memcpy(v.l, z, 32);
+        vb.ids.push_back((uint32_t)vb.ids.size());
+        vb.lens.push_back(1);
+        vb.points.push_back(glv_split(v));
+    }
+    vb.rho30.resize(k);
+    for (size_t t = 0; t < k; t++) vb.rho30[t] = fr30_arg_from_mont256(rho[vb.order[t]]);
+    const hf::Fr zero = {{0, 0, 0, 0}};
+    vb.U.assign(num_commitments, zero);
+    for (size_t t = 0; t < k; t++) {
+        const size_t b = commitment_idx ? commitment_idx[t] : t;
+        vb.U[b] = hf::fr_add(vb.U[b], rho[t]);
+    }
+    uint64_t lhs[18], rhs[18];
+    const int rc = vc_device(ctx, vb, lhs, rhs);
+    if (rc) return rc;
+    if (want_weights) {
+        std::memcpy(out_lhs, lhs, sizeof lhs);
+        std::memcpy(out_rhs, rhs, sizeof rhs);
+    }
+    *valid = vc_pair(lhs, rhs, g2[1], g2[0]);  // e(LHS, [s]G2) == e(RHS, G2)
+    return KZG_OK;
+}
+
+int kzg_verify_openings_batch(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                              const uint64_t* zs, const uint64_t* ys, const uint64_t* proofs_p1, size_t k, const void* setup_g2,
+                              size_t g2_stride_bytes, int* valid) {
+    if (ctx && k && (!commitment_idx || !ys)) {
+        ctx->last_error = "verify openings: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return verify_openings_impl(ctx, commitments_p1, num_commitments, commitment_idx, zs, ys, nullptr, proofs_p1, k, setup_g2,
+                                g2_stride_bytes, nullptr, false, nullptr, nullptr, valid);
+}
+
+int kzg_verify_openings_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
+                                const uint64_t* zs, const uint64_t* ys, const uint64_t* proofs_p1, size_t k, const void* setup_g2,
+                                size_t g2_stride_bytes, const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18],
+                                int* valid) {
+    if (ctx && k && (!commitment_idx || !ys)) {
+        ctx->last_error = "verify openings: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return verify_openings_impl(ctx, commitments_p1, num_commitments, commitment_idx, zs, ys, nullptr, proofs_p1, k, setup_g2,
+                                g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid);
+}
+
+int kzg_verify_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                 const uint64_t* commitments_p1, const uint64_t* zs, const uint64_t* proofs_p1, const void* setup_g2,
+                                 size_t g2_stride_bytes, uint64_t* out_ys, int* valid) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    uint32_t lg = 0;
+    int rc = bary_check(ctx, "verify evaluations", evals_fr_mont, n, batch, stride, zs, &lg);
+    if (rc) return rc;
+    if (batch > KZG_VERIFY_MAX_OPENINGS) {
+        ctx->last_error = "verify evaluations: more than KZG_VERIFY_MAX_OPENINGS polynomials";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!valid || (batch && (!commitments_p1 || !proofs_p1 || !setup_g2))) {
+        ctx->last_error = "verify evaluations: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!batch) {
+        *valid = 1;
+        return KZG_OK;
+    }
+    if (ctx->multi) {
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_verify_evaluations_batch(kid, evals_fr_mont, n, batch, stride, commitments_p1, zs,
+                                                                      proofs_p1, setup_g2, g2_stride_bytes, out_ys, valid))
+                   : rc;
+    }
+    rc = bary_check_values(ctx, "verify evaluations", evals_fr_mont, n, batch, stride, zs);
+    if (rc) return rc;
+    // the values go from the evaluation straight into the verifier's value buffer: fk20_mu guards that workspace for both
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    void* d_ys = nullptr;
+    {
+        std::unique_lock<std::mutex> lk(ctx->mu);
+        if (!ctx->n || !ctx->slots_ready) {
+            ctx->last_error = "verify evaluations: the SRS is empty";
+            return KZG_ERR_NO_SRS;
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = vc_ws(ctx, kVcCells, batch * 32, &d_ys);
+        if (rc) return rc;
+    }
+    rc = bary_host(ctx, evals_fr_mont, lg, batch, stride, zs, (uint32_t*)d_ys, out_ys);
+    if (rc) return rc;
+    return verify_openings_impl(ctx, commitments_p1, batch, nullptr, zs, nullptr, (const uint32_t*)d_ys, proofs_p1, batch, setup_g2,
+                                g2_stride_bytes, nullptr, false, nullptr, nullptr, valid);
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

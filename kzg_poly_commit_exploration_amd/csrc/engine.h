@@ -258,6 +258,18 @@ void launch_vc_fr_sum(hipStream_t s, const uint32_t* d_in, const uint32_t* d_ord
 void launch_vc_fr_twist(hipStream_t s, uint32_t* d_io, const uint32_t* d_ids, uint32_t D, const void* d_itw, uint32_t log_n,
                         uint32_t log_l, const Fr30& inv_l);
 
+// ---- bary_kernels.hip: barycentric evaluation of polynomials in evaluation form --------------------
+constexpr uint32_t kBaryThreads = 256;       // lanes of a workgroup of the partial kernel
+constexpr uint32_t kBaryRun = 4;             // indices per lane
+constexpr uint32_t kBaryTile = kBaryThreads * kBaryRun;  // indices per workgroup: one Fr inversion each
+constexpr uint32_t kBaryPartialWords = 12;   // a tile's record: nine digits of its sum, the index where z = w^i, padding
+inline uint32_t bary_tiles(uint32_t log_n) { return (uint32_t)((((uint64_t)1 << log_n) + kBaryTile - 1) / kBaryTile); }
+// d_out[b] = P_b(z_b) (canonical blst_fr) for polynomial b given by its 2^log_n values at d_evals + 8 b 2^log_n; d_zs: the
+// points in multiplier form; d_tw: the forward NTT twiddles; inv_n: 1 / n in multiplier form; d_partial: batch x
+// bary_tiles(log_n) records of kBaryPartialWords words
+void launch_bary(hipStream_t s, const uint32_t* d_evals, uint32_t log_n, uint32_t batch, const Fr30* d_zs, const void* d_tw,
+                 const Fr30& inv_n, uint32_t* d_partial, uint32_t* d_out);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

@@ -237,4 +237,34 @@ KZG_HD Fr30 fr30_const_r2_540() {
     return r;
 }
 
+// 1 / a for a value that carries the factor 2^270 (a = x * 2^270 -> x^-1 * 2^270; 0 -> 0): Fermat's a^(r - 2) with a fixed
+// window of two bits -- 254 squarings and at most 127 products by a, a^2 or a^3 chosen digit by digit, so that the three
+// table entries stay in registers (a four-bit window saves ~60 products and costs 12 more entries: 108 registers).
+// Operand: carry-normalised digits, any magnitude fr30_mul takes; result |v| <= 0.5001 r like every product.
+// The top window of r - 2 (bits 255:254) is 01.
+KZG_HD Fr30 fr30_inv(const Fr30& a) {
+    constexpr uint64_t E0 = 0xfffffffeffffffffULL, E1 = 0x53bda402fffe5bfeULL, E2 = 0x3339d80809a1d805ULL,
+                       E3 = 0x73eda753299d7d48ULL;  // r - 2
+    const Fr30 a2 = fr30_mul(a, a);
+    const Fr30 a3 = fr30_mul(a2, a);
+    Fr30 acc = a;
+#ifdef __HIP_DEVICE_COMPILE__
+#pragma unroll 1
+#endif
+    for (int w = 126; w >= 0; w--) {
+        acc = fr30_mul(acc, acc);
+        acc = fr30_mul(acc, acc);
+        const int q = w >> 5;
+        const uint64_t limb = q == 3 ? E3 : (q == 2 ? E2 : (q == 1 ? E1 : E0));
+        const uint32_t dgt = (uint32_t)(limb >> (2 * (w & 31))) & 3u;
+        if (dgt) {
+            Fr30 m;
+#pragma unroll
+            for (int i = 0; i < kR9; i++) m.d[i] = dgt == 1 ? a.d[i] : (dgt == 2 ? a2.d[i] : a3.d[i]);
+            acc = fr30_mul(acc, m);
+        }
+    }
+    return acc;
+}
+
 }  // namespace kzg

@@ -418,6 +418,67 @@ int kzg_verify_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, si
  * twiddle products use the endomorphism (x, y) -> (beta x, y) = [z^2 - 1](x, y), which holds there only; nothing checks it */
 int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint64_t* out_p1);
 
+/* ---- the batch verifiers on inputs as they travel ------------------------------------------------
+ * A sampling node receives commitments and proofs as 48-byte compressed G1 points (ZCash encoding, as kzg_g1_compress writes
+ * them), field elements as 32-byte big-endian strings, and cells and blobs in the bit-reversed order of the sampling specs.
+ * The calls below take exactly that: the bytes are uploaded as received and decoded on the device (one lane per point: the
+ * 381-bit square root; one lane per value) straight into the buffers the verifiers read, instead of one kzg_g1_uncompress
+ * per point and a conversion per value on the host.  For inputs that decode, each returns what its sibling without _bytes
+ * returns on the decoded inputs: the same *valid, and the same two sides bit for bit from the _lincomb hooks.
+ * order: KZG_ORDER_NATURAL -- cells, their values and a blob's values as this API defines them; KZG_ORDER_BIT_REVERSED -- the
+ * sampling specs' view of the same data: cell_ids[t] = c names this API's cell brp(c) (bit reversal over log_domain -
+ * log_cell bits), its values arrive with value i at this API's position brp(i) (log_cell bits), and value i of a blob of n
+ * values is this API's value brp(i) (log2 n bits).
+ * Decoding: a point is accepted as blst_p1_uncompress accepts it (compressed flag set; infinity is 0xc0 followed by zeros;
+ * otherwise x < p and x^3 + 4 a square; the sign bit chooses y), membership in G1 is then checked as in the siblings; a scalar
+ * must be below r.  The points zs of the openings are decoded on the host (it groups the records by point), all else on the
+ * device.
+ * Errors: those of the siblings, in their order, up to where they read a G1 coordinate or a value; an order that is neither
+ * constant is KZG_ERR_INVALID_ARG; then KZG_ERR_INVALID_ARG with kzg_last_error naming the input: "the proof of record t" /
+ * "commitment b" "is not a valid compressed point" (flag bits, malformed infinity, x >= p, x not on the curve) or "is not in
+ * G1"; "record t: value i" (i as sent), "record t: the point z", "record t: the claimed y", "polynomial b: value i" /
+ * "polynomial b: the point z" "is not below r" (these are the _bytes calls' wordings; the siblings, which check decoded
+ * scalars on the host, say "record t: the point" / "record t: the value").  When several inputs are bad, one of them is named.  A flipped sign bit is the
+ * valid point -P: KZG_OK with *valid = 0.  Infinity passes wherever the siblings let it pass.
+ * Thread safety and multi-device contexts as the siblings (one slot per call; a replicated SRS forwards to one device, a
+ * range-split one returns KZG_ERR_INVALID_ARG); kzg_verify_blobs_batch_bytes runs large batches in chunks as
+ * kzg_evaluate_evaluations_batch does.  What the decode costs against the host route: DESIGN.md section 5.0g. */
+#define KZG_ORDER_NATURAL 0u
+#define KZG_ORDER_BIT_REVERSED 1u
+/* kzg_verify_cells_batch on k records of cells_be + 32 (t l + i) (k x l x 32 bytes), proofs48 + 48 t, commitments48 + 48 b */
+int kzg_verify_cells_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                 const uint32_t* cell_ids, const uint8_t* cells_be, const uint8_t* proofs48, size_t k,
+                                 unsigned log_domain, unsigned log_cell, unsigned order, const void* setup_g2, size_t g2_stride_bytes,
+                                 int* valid);
+/* test hook, as kzg_verify_cells_lincomb: the caller's weights (k x blst_fr), the two sides out */
+int kzg_verify_cells_lincomb_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                   const uint32_t* cell_ids, const uint8_t* cells_be, const uint8_t* proofs48, size_t k,
+                                   unsigned log_domain, unsigned log_cell, unsigned order, const void* setup_g2,
+                                   size_t g2_stride_bytes, const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18],
+                                   int* valid);
+/* kzg_verify_openings_batch on zs_be + 32 t, ys_be + 32 t, proofs48 + 48 t, commitments48 + 48 b */
+int kzg_verify_openings_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                    const uint8_t* zs_be, const uint8_t* ys_be, const uint8_t* proofs48, size_t k,
+                                    const void* setup_g2, size_t g2_stride_bytes, int* valid);
+int kzg_verify_openings_lincomb_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments,
+                                      const uint32_t* commitment_idx, const uint8_t* zs_be, const uint8_t* ys_be,
+                                      const uint8_t* proofs48, size_t k, const void* setup_g2, size_t g2_stride_bytes,
+                                      const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid);
+/* kzg_verify_evaluations_batch for blobs as they travel: blob b is n x 32 big-endian bytes at blobs_be + 32 b stride (stride in
+ * values, >= n), its commitment at commitments48 + 48 b, its proof at proofs48 + 48 b, the challenge at zs_be + 32 b.
+ * out_ys_be (batch x 32 bytes, may be NULL) receives the big-endian image of what kzg_verify_evaluations_batch writes to
+ * out_ys. */
+int kzg_verify_blobs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                 const uint8_t* commitments48, const uint8_t* zs_be, const uint8_t* proofs48, const void* setup_g2,
+                                 size_t g2_stride_bytes, uint8_t* out_ys_be, int* valid);
+/* building blocks and test hooks: n compressed points -> n blst_p1 (Z = Montgomery one, all zero = infinity) decoded on the
+ * device, each equal to what kzg_g1_uncompress returns; check_subgroup != 0 also requires each to lie in G1.  n x 32
+ * big-endian bytes -> n blst_fr.  On a bad input: KZG_ERR_INVALID_ARG and *bad_index = the least bad index ((size_t)-1
+ * otherwise; bad_index may be NULL).  n = 0 does nothing.  They need no SRS; thread safety as kzg_g1_dft; multi-device
+ * contexts run them on their first device. */
+int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup, uint64_t* out_p1, size_t* bad_index);
+int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint64_t* out_fr_mont, size_t* bad_index);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

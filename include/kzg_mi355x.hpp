@@ -320,6 +320,25 @@ struct Cells {
               setup.ctx());
         return valid != 0;
     }
+    // kzg_verify_cells_batch_bytes: verify_batch on the records as they travel -- commitments48 / proofs48: 48-byte
+    // compressed points, cells_be: k x l x 32 big-endian bytes; order: KZG_ORDER_NATURAL, or KZG_ORDER_BIT_REVERSED for cell
+    // ids and values in the sampling specs' order.  The bytes are decoded on the device.
+    static bool verify_batch_bytes(const std::vector<uint8_t>& commitments48, const std::vector<uint32_t>& commitment_idx,
+                                   const std::vector<uint32_t>& cell_ids, const std::vector<uint8_t>& cells_be,
+                                   const std::vector<uint8_t>& proofs48, unsigned log_domain, unsigned log_cell, unsigned order,
+                                   const std::vector<std::array<uint64_t, 36>>& setup_g2, const SetupArtifacts& setup) {
+        const size_t k = cell_ids.size();
+        if (commitment_idx.size() != k || proofs48.size() != 48 * k || cells_be.size() != ((32 * k) << log_cell) ||
+            commitments48.size() % 48 || setup_g2.size() <= ((size_t)1 << log_cell))
+            throw Error(KZG_ERR_INVALID_ARG, "Cells::verify_batch_bytes: one commitment index, cell id, l values and proof per "
+                                             "record, and l + 1 G2 powers");
+        int valid = 0;
+        check(kzg_verify_cells_batch_bytes(setup.ctx(), commitments48.data(), commitments48.size() / 48, commitment_idx.data(),
+                                           cell_ids.data(), cells_be.data(), proofs48.data(), k, log_domain, log_cell, order,
+                                           setup_g2.front().data(), sizeof(setup_g2.front()), &valid),
+              setup.ctx());
+        return valid != 0;
+    }
     // builds the SRS-side FK20 transforms for polynomials of n coefficients now (otherwise the first call does)
     static void prepare_fk20(size_t n, unsigned log_cell, const SetupArtifacts& setup) {
         check(kzg_fk20_prepare(setup.ctx(), n, log_cell), setup.ctx());
@@ -330,6 +349,62 @@ struct Cells {
         Cells out;
         out.values.resize((size_t)1 << log_domain);
         out.proofs.resize(log_cell <= log_domain ? (size_t)1 << (log_domain - log_cell) : 1);
+        return out;
+    }
+};
+
+// The other verifiers on inputs as they travel (kzg_mi355x.h, "the batch verifiers on inputs as they travel").
+struct Wire {
+    // kzg_verify_openings_batch_bytes: record t claims that commitment commitment_idx[t] opens to ys_be[32 t ..] at zs_be[32 t ..]
+    // with proofs48[48 t ..]; setup_g2: [1]G2, [s]G2
+    static bool verify_openings(const std::vector<uint8_t>& commitments48, const std::vector<uint32_t>& commitment_idx,
+                                const std::vector<uint8_t>& zs_be, const std::vector<uint8_t>& ys_be,
+                                const std::vector<uint8_t>& proofs48, const std::vector<std::array<uint64_t, 36>>& setup_g2,
+                                const SetupArtifacts& setup) {
+        const size_t k = commitment_idx.size();
+        if (zs_be.size() != 32 * k || ys_be.size() != 32 * k || proofs48.size() != 48 * k || commitments48.size() % 48 ||
+            setup_g2.size() < 2)
+            throw Error(KZG_ERR_INVALID_ARG, "Wire::verify_openings: one index, point, value and proof per record, two G2 powers");
+        int valid = 0;
+        check(kzg_verify_openings_batch_bytes(setup.ctx(), commitments48.data(), commitments48.size() / 48, commitment_idx.data(),
+                                              zs_be.data(), ys_be.data(), proofs48.data(), k, setup_g2.front().data(),
+                                              sizeof(setup_g2.front()), &valid),
+              setup.ctx());
+        return valid != 0;
+    }
+    // kzg_verify_blobs_batch_bytes: blob b (n x 32 big-endian bytes, one after the other) has commitment b and the opening
+    // proof b at the challenge zs_be[32 b ..]; out_ys_be (may be null) receives the values P_b(z_b) as big-endian bytes
+    static bool verify_blobs(const std::vector<uint8_t>& blobs_be, size_t n, unsigned order, const std::vector<uint8_t>& commitments48,
+                             const std::vector<uint8_t>& zs_be, const std::vector<uint8_t>& proofs48,
+                             const std::vector<std::array<uint64_t, 36>>& setup_g2, const SetupArtifacts& setup,
+                             std::vector<uint8_t>* out_ys_be = nullptr) {
+        const size_t batch = zs_be.size() / 32;
+        if (!n || blobs_be.size() != 32 * n * batch || zs_be.size() % 32 || commitments48.size() != 48 * batch ||
+            proofs48.size() != 48 * batch || setup_g2.size() < 2)
+            throw Error(KZG_ERR_INVALID_ARG, "Wire::verify_blobs: one commitment, challenge and proof per blob of n values");
+        if (out_ys_be) out_ys_be->assign(32 * batch, 0);
+        int valid = 0;
+        check(kzg_verify_blobs_batch_bytes(setup.ctx(), blobs_be.data(), n, batch, n, order, commitments48.data(), zs_be.data(),
+                                           proofs48.data(), setup_g2.front().data(), sizeof(setup_g2.front()),
+                                           out_ys_be && batch ? out_ys_be->data() : nullptr, &valid),
+              setup.ctx());
+        return valid != 0;
+    }
+    // kzg_g1_uncompress_batch / kzg_fr_from_bytes_batch: the decoders on their own
+    static std::vector<G1Point> g1_uncompress_batch(const std::vector<uint8_t>& in48, bool check_subgroup, const SetupArtifacts& setup) {
+        if (in48.size() % 48) throw Error(KZG_ERR_INVALID_ARG, "Wire::g1_uncompress_batch: 48 bytes per point");
+        std::vector<G1Point> out(in48.size() / 48 + 1);
+        check(kzg_g1_uncompress_batch(setup.ctx(), in48.data(), in48.size() / 48, check_subgroup ? 1 : 0, out.front().p1.data(), nullptr),
+              setup.ctx());
+        out.pop_back();
+        return out;
+    }
+    static std::vector<Scalar> fr_from_bytes_batch(const std::vector<uint8_t>& in32_be, const SetupArtifacts& setup) {
+        if (in32_be.size() % 32) throw Error(KZG_ERR_INVALID_ARG, "Wire::fr_from_bytes_batch: 32 bytes per value");
+        std::vector<Scalar> out(in32_be.size() / 32 + 1);
+        check(kzg_fr_from_bytes_batch(setup.ctx(), in32_be.data(), in32_be.size() / 32, reinterpret_cast<uint64_t*>(out.data()), nullptr),
+              setup.ctx());
+        out.pop_back();
         return out;
     }
 };

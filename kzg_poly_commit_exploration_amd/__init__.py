@@ -55,7 +55,11 @@ ABI_SYMBOLS = [
     "kzg_cells_and_proofs_fk20", "kzg_fk20_prepare", "kzg_g1_dft", "kzg_recover_cells_and_proofs",
     "kzg_verify_cells_batch", "kzg_verify_cells_lincomb",
     "kzg_evaluate_evaluations_batch", "kzg_verify_openings_batch", "kzg_verify_openings_lincomb", "kzg_verify_evaluations_batch",
+    "kzg_verify_cells_batch_bytes", "kzg_verify_cells_lincomb_bytes", "kzg_verify_openings_batch_bytes",
+    "kzg_verify_openings_lincomb_bytes", "kzg_verify_blobs_batch_bytes", "kzg_g1_uncompress_batch", "kzg_fr_from_bytes_batch",
 ]
+KZG_ORDER_NATURAL = 0
+KZG_ORDER_BIT_REVERSED = 1
 KZG_MAX_OPEN_POINTS = 64
 KZG_NTT_MAX_LOG = 22
 KZG_MAX_CELL_LOG = 6
@@ -167,6 +171,14 @@ def load_library():
         "kzg_verify_openings_batch": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
         "kzg_verify_openings_lincomb": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, C.POINTER(i)]),
         "kzg_verify_evaluations_batch": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp, sz, vp, C.POINTER(i)]),
+        "kzg_verify_cells_batch_bytes": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, C.c_uint, vp, sz, C.POINTER(i)]),
+        "kzg_verify_cells_lincomb_bytes": (i, [vp, vp, sz, vp, vp, vp, vp, sz, C.c_uint, C.c_uint, C.c_uint, vp, sz, vp, vp, vp,
+                                               C.POINTER(i)]),
+        "kzg_verify_openings_batch_bytes": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
+        "kzg_verify_openings_lincomb_bytes": (i, [vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, C.POINTER(i)]),
+        "kzg_verify_blobs_batch_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp, vp, sz, vp, C.POINTER(i)]),
+        "kzg_g1_uncompress_batch": (i, [vp, vp, sz, i, vp, C.POINTER(sz)]),
+        "kzg_fr_from_bytes_batch": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -644,6 +656,129 @@ class Engine:
         _check(self._lib.kzg_verify_evaluations_batch(self._h, _ptr(a), n, batch, n, opt(com), opt(zl), opt(prf), _ptr(g2), 288,
                                                       opt(out), C.byref(ok)), self._h)
         return bool(ok.value), ([Scalar.from_limbs(out[b]) for b in range(batch)] if want_ys else None)
+
+    # -- the verifiers on inputs as they travel --
+    @staticmethod
+    def _wire(data, width):
+        """bytes, or anything numpy reads as uint8 -> a contiguous (count, width) uint8 array"""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(data, dtype=np.uint8)
+        assert a.size % width == 0, "a whole number of %d-byte strings" % width
+        return np.ascontiguousarray(a).reshape(-1, width)
+
+    def g1_uncompress_batch(self, data, check_subgroup=False):
+        """kzg_g1_uncompress_batch: n x 48 bytes of compressed points -> (n, 18) blst_p1 rows, decoded on the device.  A
+        point that does not decode (or, with check_subgroup, lies outside G1) raises KzgError; its index is in .bad_index"""
+        a = self._wire(data, 48)
+        out = np.zeros((max(a.shape[0], 1), 18), dtype=np.uint64)
+        bad = C.c_size_t(0)
+        rc = self._lib.kzg_g1_uncompress_batch(self._h, _ptr(a) if a.size else None, a.shape[0], 1 if check_subgroup else 0,
+                                               _ptr(out), C.byref(bad))
+        self._check_bad(rc, bad)
+        return out[:a.shape[0]]
+
+    def fr_from_bytes_batch(self, data):
+        """kzg_fr_from_bytes_batch: n x 32 big-endian bytes -> (n, 4) blst_fr rows; a value not below r raises KzgError with
+        its index in .bad_index"""
+        a = self._wire(data, 32)
+        out = np.zeros((max(a.shape[0], 1), 4), dtype=np.uint64)
+        bad = C.c_size_t(0)
+        rc = self._lib.kzg_fr_from_bytes_batch(self._h, _ptr(a) if a.size else None, a.shape[0], _ptr(out), C.byref(bad))
+        self._check_bad(rc, bad)
+        return out[:a.shape[0]]
+
+    def _check_bad(self, rc, bad):
+        try:
+            _check(rc, self._h)
+        except KzgError as e:
+            e.bad_index = None if bad.value == C.c_size_t(-1).value else bad.value
+            raise
+
+    def _verify_cells_bytes_args(self, commitments48, commitment_idx, cell_ids, cells_be, proofs48, log_cell, setup_g2):
+        com, prf = self._wire(commitments48, 48), self._wire(proofs48, 48)
+        idx = np.ascontiguousarray(commitment_idx, dtype=np.uint32).reshape(-1)
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        k = len(ids)
+        vals = self._wire(cells_be, 32)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert len(idx) == k and prf.shape[0] == k and vals.shape[0] == k << log_cell, \
+            "one commitment index, cell id, row of l values and proof per record"
+        keep = (com, prf, idx, ids, vals, g2)
+        return keep, (_ptr(com) if com.size else None, com.shape[0], _ptr(idx) if k else None, _ptr(ids) if k else None,
+                      _ptr(vals) if k else None, _ptr(prf) if k else None, k)
+
+    def verify_cells_batch_bytes(self, commitments48, commitment_idx, cell_ids, cells_be, proofs48, log_domain, log_cell,
+                                 setup_g2, order=KZG_ORDER_NATURAL):
+        """kzg_verify_cells_batch_bytes: verify_cells_batch on the wire forms -- commitments48 / proofs48: 48-byte compressed
+        points, cells_be: k x l x 32 big-endian bytes (bytes or uint8 arrays); order KZG_ORDER_BIT_REVERSED: cell ids and
+        values in the sampling specs' bit-reversed order"""
+        keep, a = self._verify_cells_bytes_args(commitments48, commitment_idx, cell_ids, cells_be, proofs48, log_cell, setup_g2)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_cells_batch_bytes(self._h, *a, log_domain, log_cell, order, _ptr(keep[5]), 288,
+                                                      C.byref(ok)), self._h)
+        return bool(ok.value)
+
+    def verify_cells_lincomb_bytes(self, commitments48, commitment_idx, cell_ids, cells_be, proofs48, log_domain, log_cell,
+                                   setup_g2, weights, order=KZG_ORDER_NATURAL):
+        """the test hook kzg_verify_cells_lincomb_bytes; returns (lhs, rhs, valid) as verify_cells_lincomb"""
+        keep, a = self._verify_cells_bytes_args(commitments48, commitment_idx, cell_ids, cells_be, proofs48, log_cell, setup_g2)
+        w = self._fr_rows(weights)
+        if not w.shape[0]:
+            w = np.zeros((1, 4), dtype=np.uint64)
+        lhs = np.zeros(18, dtype=np.uint64)
+        rhs = np.zeros(18, dtype=np.uint64)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_cells_lincomb_bytes(self._h, *a, log_domain, log_cell, order, _ptr(keep[5]), 288, _ptr(w),
+                                                        _ptr(lhs), _ptr(rhs), C.byref(ok)), self._h)
+        return G1Point(lhs), G1Point(rhs), bool(ok.value)
+
+    def _verify_openings_bytes_args(self, commitments48, commitment_idx, zs_be, ys_be, proofs48, setup_g2):
+        com, prf = self._wire(commitments48, 48), self._wire(proofs48, 48)
+        idx = np.ascontiguousarray(commitment_idx, dtype=np.uint32).reshape(-1)
+        zl, yl = self._wire(zs_be, 32), self._wire(ys_be, 32)
+        k = len(idx)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert zl.shape[0] == k and yl.shape[0] == k and prf.shape[0] == k, "one index, point, value and proof per record"
+        keep = (com, prf, idx, zl, yl, g2)
+        return keep, (_ptr(com) if com.size else None, com.shape[0], _ptr(idx) if k else None, _ptr(zl) if k else None,
+                      _ptr(yl) if k else None, _ptr(prf) if k else None, k, _ptr(g2), 288)
+
+    def verify_openings_batch_bytes(self, commitments48, commitment_idx, zs_be, ys_be, proofs48, setup_g2):
+        """kzg_verify_openings_batch_bytes: verify_openings_batch on 48-byte compressed points and 32-byte big-endian scalars"""
+        keep, a = self._verify_openings_bytes_args(commitments48, commitment_idx, zs_be, ys_be, proofs48, setup_g2)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_openings_batch_bytes(self._h, *a, C.byref(ok)), self._h)
+        return bool(ok.value)
+
+    def verify_openings_lincomb_bytes(self, commitments48, commitment_idx, zs_be, ys_be, proofs48, setup_g2, weights):
+        """the test hook kzg_verify_openings_lincomb_bytes; returns (lhs, rhs, valid) as verify_openings_lincomb"""
+        keep, a = self._verify_openings_bytes_args(commitments48, commitment_idx, zs_be, ys_be, proofs48, setup_g2)
+        w = self._fr_rows(weights)
+        if not w.shape[0]:
+            w = np.zeros((1, 4), dtype=np.uint64)
+        lhs = np.zeros(18, dtype=np.uint64)
+        rhs = np.zeros(18, dtype=np.uint64)
+        ok = C.c_int(0)
+        _check(self._lib.kzg_verify_openings_lincomb_bytes(self._h, *a, _ptr(w), _ptr(lhs), _ptr(rhs), C.byref(ok)), self._h)
+        return G1Point(lhs), G1Point(rhs), bool(ok.value)
+
+    def verify_blobs_batch_bytes(self, blobs_be, n, commitments48, zs_be, proofs48, setup_g2, order=KZG_ORDER_NATURAL,
+                                 want_ys=True):
+        """kzg_verify_blobs_batch_bytes: verify_evaluations_batch for blobs as they travel -- blobs_be: batch x n x 32
+        big-endian bytes.  Returns (valid, ys_be): the values P_b(z_b) as batch x 32 big-endian bytes (None when want_ys is
+        False)"""
+        a = self._wire(blobs_be, 32)
+        assert n and a.shape[0] % n == 0, "whole blobs of n values"
+        batch = a.shape[0] // n
+        com, prf, zl = self._wire(commitments48, 48), self._wire(proofs48, 48), self._wire(zs_be, 32)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert com.shape[0] == batch and prf.shape[0] == batch and zl.shape[0] == batch
+        out = np.zeros((max(batch, 1), 32), dtype=np.uint8) if want_ys else None
+        ok = C.c_int(0)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        _check(self._lib.kzg_verify_blobs_batch_bytes(self._h, opt(a), n, batch, n, order, opt(com), opt(zl), opt(prf), _ptr(g2),
+                                                      288, opt(out), C.byref(ok)), self._h)
+        return bool(ok.value), (out[:batch].tobytes() if want_ys else None)
 
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""

@@ -32,6 +32,7 @@
 #include "host_fr.hpp"
 #include "fr30_host.hpp"
 #include "host_pairing.hpp"
+#include "wire30.hip.h"
 
 using namespace kzg;
 namespace hf = kzg_host;
@@ -194,8 +195,8 @@ struct kzg_ctx {
     size_t rec_ws_bytes[9] = {};
     // batch verification of cells (kzg_verify_cells_batch): workspaces grown on demand, under fk20_mu
     // (the call reads the split twiddles d_glv, which an FK20 call may grow)
-    void* vc_ws[16] = {};
-    size_t vc_ws_bytes[16] = {};
+    void* vc_ws[17] = {};
+    size_t vc_ws_bytes[17] = {};
 };
 
 namespace {
@@ -2958,9 +2959,12 @@ int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, un
 namespace {
 enum : int {
     kVcCells = 0, kVcFrA, kVcFrB, kVcCoefA, kVcOrder, kVcRho, kVcIds, kVcStarts, kVcP1, kVcAff, kVcPrefix, kVcSrc, kVcGlv,
-    kVcGlvSrs, kVcG1, kVcScratch
+    kVcGlvSrs, kVcG1, kVcScratch, kVcWire
 };
-static_assert(kVcScratch < 16, "kzg_ctx::vc_ws");
+static_assert(kVcWire < 17, "kzg_ctx::vc_ws");
+// the error words of one call, behind the l coefficients in the kVcCoefA workspace: the ladder's two (a point off the curve,
+// outside G1), then one per class of wire input (section 4.12): proofs, commitments, values
+enum : int { kVcErrCurve = 0, kVcErrG1, kVcErrWireProof, kVcErrWireCommitment, kVcErrWireValue, kVcErrWords = 8 };
 constexpr uint32_t kVcFold = 16;  // terms one lane adds per level of a segmented sum, at most
 // levels of a segmented sum over consecutive segments of the given lengths (each >= 1): per level the start of every
 // group of at most kVcFold entries inside one segment, plus the end; stops when every segment is one entry (one level at
@@ -3041,7 +3045,43 @@ struct VcBatch {
     const uint32_t* d_values = nullptr;  // the values are on the device already (in the kVcCells workspace): no upload
     bool fk20_held = false;              // the caller holds ctx->fk20_mu
     const char* what = "verify cells";
+    // inputs as wire bytes (section 4.12), decoded on the device in place of the uploads of proofs / commitments / cells:
+    // 48-byte compressed points (both or neither), k x l 32-byte big-endian values, every row of l in bit-reversed order or not
+    const uint8_t* wire_commitments = nullptr;
+    const uint8_t* wire_proofs = nullptr;
+    const uint8_t* wire_values = nullptr;
+    bool bit_reversed = false;
 };
+// the same arguments as the entry points see them; null members: that input comes decoded, as the siblings take it
+struct VcWire {
+    const uint8_t* commitments48 = nullptr;
+    const uint8_t* proofs48 = nullptr;
+    const uint8_t* values_be = nullptr;
+    const uint8_t* zs_be = nullptr;
+    unsigned order = KZG_ORDER_NATURAL;
+};
+// a 32-byte big-endian scalar on the host: false when it is not below r; out: its blst_fr image
+bool wire_fr_host(const uint8_t* be, uint64_t out[4]) {
+    hf::Fr v;
+    for (int i = 0; i < 4; i++) {
+        uint64_t w = 0;
+        for (int j = 0; j < 8; j++) w = (w << 8) | be[8 * (3 - i) + j];
+        v.l[i] = w;
+    }
+    if (hf::fr_geq(v, hf::kFrMod)) return false;
+    const hf::Fr m = hf::fr_mul(v, kFrR2);
+    std::memcpy(out, m.l, 32);
+    return true;
+}
+// ... and back: the big-endian bytes of a blst_fr image
+void wire_fr_to_be(const uint64_t mont[4], uint8_t out[32]) {
+    hf::Fr m;
+    std::memcpy(m.l, mont, 32);
+    const hf::Fr one_raw = {{1, 0, 0, 0}};
+    const hf::Fr v = hf::fr_mul(m, one_raw);
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 8; j++) out[8 * (3 - i) + j] = (uint8_t)(v.l[i] >> (8 * (7 - j)));
+}
 }  // namespace
 
 // the two sides of the check, normalised blst_p1, into out_lhs / out_rhs
@@ -3098,13 +3138,15 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
         glv[K + b] = glv_split(vb.U[b]);
     }
     void *cells, *fa, *fb, *coef, *order, *rho, *ids, *dstarts, *p1, *aff, *prefix, *dsrc, *dglv, *dglvs, *g1, *scratch;
+    void* wire = nullptr;  // the values' bytes (the points' go through the p1 workspace, which is free until the sides land in it)
     // values already on the device ARE the kVcCells workspace: asking for it again could free and reallocate it (vc_ws drops
     // the contents when it grows)
     if (vb.d_values) cells = (void*)vb.d_values;
     else rc = vc_ws(ctx, kVcCells, K * l * 32, &cells);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrA, g0 * l * 32, &fa);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrB, g0 * l * 32, &fb);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, l * 32 + 8, &coef);  // + the two error words
+    if (rc == KZG_OK && vb.wire_values) rc = vc_ws(ctx, kVcWire, K * l * 32, &wire);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, l * 32 + kVcErrWords * 4, &coef);  // + the error words
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcOrder, K * 4, &order);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcRho, K * sizeof(Fr30), &rho);
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcIds, D * 4, &ids);
@@ -3119,19 +3161,29 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     if (rc == KZG_OK) rc = vc_ws(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
     if (rc) return rc;
     const hipStream_t st = s.stream;
-    if (!vb.d_values) HIP_TRY(ctx, hipMemcpyAsync(cells, vb.cells, K * l * 32, hipMemcpyHostToDevice, st));
+    uint32_t* err = (uint32_t*)((char*)coef + l * 32);
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kVcErrWords * 4, st));
+    if (vb.wire_values) {
+        HIP_TRY(ctx, hipMemcpyAsync(wire, vb.wire_values, K * l * 32, hipMemcpyHostToDevice, st));
+        launch_wire_fr(st, wire, (uint32_t)(K * l), sh.log_l, vb.bit_reversed, cells, err + kVcErrWireValue);
+    } else if (!vb.d_values) {
+        HIP_TRY(ctx, hipMemcpyAsync(cells, vb.cells, K * l * 32, hipMemcpyHostToDevice, st));
+    }
     Glv* dpoints = (Glv*)dglvs + l;
     if (pts) HIP_TRY(ctx, hipMemcpyAsync(dpoints, vb.points.data(), D * sizeof(Glv), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(order, vb.order.data(), K * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(rho, vb.rho30.data(), K * sizeof(Fr30), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(ids, vb.ids.data(), D * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dstarts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(p1, vb.proofs, K * 144, hipMemcpyHostToDevice, st));
-    if (B) HIP_TRY(ctx, hipMemcpyAsync((char*)p1 + K * 144, vb.commitments, B * 144, hipMemcpyHostToDevice, st));
+    if (vb.wire_proofs) {
+        HIP_TRY(ctx, hipMemcpyAsync(p1, vb.wire_proofs, K * 48, hipMemcpyHostToDevice, st));
+        if (B) HIP_TRY(ctx, hipMemcpyAsync((char*)p1 + K * 48, vb.wire_commitments, B * 48, hipMemcpyHostToDevice, st));
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(p1, vb.proofs, K * 144, hipMemcpyHostToDevice, st));
+        if (B) HIP_TRY(ctx, hipMemcpyAsync((char*)p1 + K * 144, vb.commitments, B * 144, hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(ctx, hipMemcpyAsync(dsrc, src.data(), lanes * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dglv, glv.data(), lanes * sizeof(Glv), hipMemcpyHostToDevice, st));
-    uint32_t* err = (uint32_t*)((char*)coef + l * 32);
-    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, 8, st));
     const uint32_t* dst_ = (const uint32_t*)dstarts;
     // Fr side: V_j (weighted first level), the inverse transforms, the twist, the column sums -> A's l coefficients
     uint32_t *FA = (uint32_t*)fa, *FB = (uint32_t*)fb;
@@ -3158,7 +3210,13 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     const size_t oT = K, oC = K + D, oS = oC + B, oAT = oS + l, oOut = oAT + D;
     auto rec = [&](size_t i) { return (void*)((char*)g1 + i * kXyzzBytes); };
     void* X[2] = {scratch, (char*)scratch + gmax * kXyzzBytes};
-    launch_jacobian_to_affine(st, p1, (uint32_t)lanes, aff, prefix);
+    if (vb.wire_proofs) {  // straight into the records the ladder reads, in input order: no normalisation to run
+        launch_wire_g1(st, p1, nullptr, (uint32_t)K, aff, (uint32_t)kAffineBytes, err + kVcErrWireProof);
+        launch_wire_g1(st, (char*)p1 + K * 48, nullptr, (uint32_t)B, (char*)aff + K * kAffineBytes, (uint32_t)kAffineBytes,
+                       err + kVcErrWireCommitment);
+    } else {
+        launch_jacobian_to_affine(st, p1, (uint32_t)lanes, aff, prefix);
+    }
     launch_vc_ladder(st, aff, (const uint32_t*)dsrc, (const Glv*)dglv, (uint32_t)lanes, (uint32_t)lanes, (uint32_t)K, rec(0), rec(oC),
                      err);
     auto g1_plan = [&](const VcPlan& plan, const std::vector<size_t>& at, const void* in, void* out) {
@@ -3176,11 +3234,24 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     rc = vc_sync(ctx, lk, st, what.c_str());
     if (rc) return rc;
     std::vector<hf::Fr> A(l);
-    uint32_t herr[2];
+    uint32_t herr[kVcErrWords];
     HIP_TRY(ctx, hipMemcpyAsync(A.data(), coef, l * 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(herr, err, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, st));
     rc = vc_sync(ctx, lk, st);
     if (rc) return rc;
+    if (herr[kVcErrWireProof] != 0xffffffffu || herr[kVcErrWireCommitment] != 0xffffffffu) {
+        const bool proof = herr[kVcErrWireProof] != 0xffffffffu;
+        ctx->last_error = what + ": " + (proof ? "the proof of record " + std::to_string(herr[kVcErrWireProof])
+                                               : "commitment " + std::to_string(herr[kVcErrWireCommitment])) +
+                          " is not a valid compressed point";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (herr[kVcErrWireValue] != 0xffffffffu) {
+        const uint32_t g = herr[kVcErrWireValue];
+        ctx->last_error = what + ": record " + std::to_string(g >> sh.log_l) +
+                          (pts ? ": the claimed y" : ": value " + std::to_string(g & (l - 1))) + " is not below r";
+        return KZG_ERR_INVALID_ARG;
+    }
     for (int e = 0; e < 2; e++)
         if (herr[e] != 0xffffffffu) {
             const std::string who = herr[e] < K ? "the proof of record " + std::to_string(herr[e])
@@ -3263,7 +3334,7 @@ static int vc_pair(const uint64_t lhs[18], const uint64_t rhs[18], const hf::G2A
 // calls that index
 static int vc_check_inputs(kzg_ctx* ctx, const char* what, const uint64_t* weights, const uint64_t* proofs_p1, size_t k,
                            const uint64_t* commitments_p1, size_t num_commitments, const void* setup_g2, size_t g2_stride_bytes,
-                           size_t second, const char* second_name, hf::G2Affine g2[2]) {
+                           size_t second, const char* second_name, hf::G2Affine g2[2], bool wire_points = false) {
     auto invalid = [&](const std::string& why) {
         ctx->last_error = std::string(what) + ": " + why;
         return KZG_ERR_INVALID_ARG;
@@ -3274,9 +3345,9 @@ static int vc_check_inputs(kzg_ctx* ctx, const char* what, const uint64_t* weigh
             std::memcpy(v.l, weights + 4 * t, 32);
             if (hf::fr_geq(v, hf::kFrMod)) return invalid("weight " + std::to_string(t) + " is not below r");
         }
-    for (size_t t = 0; t < k; t++)
+    for (size_t t = 0; t < k && !wire_points; t++)  // (compressed points: the device's decoder checks them)
         if (vc_p1_malformed(proofs_p1 + 18 * t)) return invalid("the proof of record " + std::to_string(t) + " is not on the curve");
-    for (size_t b = 0; b < num_commitments; b++)
+    for (size_t b = 0; b < num_commitments && !wire_points; b++)
         if (vc_p1_malformed(commitments_p1 + 18 * b)) return invalid("commitment " + std::to_string(b) + " is not on the curve");
     for (int i = 0; i < 2; i++) {
         uint64_t raw[36];
@@ -3287,11 +3358,19 @@ static int vc_check_inputs(kzg_ctx* ctx, const char* what, const uint64_t* weigh
     return KZG_OK;
 }
 
-// weights: k blst_fr given by the caller (the test hook), or null for fresh random ones
+// a call forwarded to a device's context before its inputs were checked: the parent reports what that context found
+static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
+    if (rc) ctx->last_error = kid->last_error;
+    return rc;
+}
+
+// weights: k blst_fr given by the caller (the test hook), or null for fresh random ones.  wire: the commitments, proofs and
+// cells are its byte strings (section 4.12) and commitments_p1 / cells / proofs_p1 are null
 static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
                              const uint32_t* cell_ids, const uint64_t* cells, const uint64_t* proofs_p1, size_t k,
                              unsigned log_domain, unsigned log_cell, const void* setup_g2, size_t g2_stride_bytes,
-                             const uint64_t* weights, bool want_weights, uint64_t* out_lhs, uint64_t* out_rhs, int* valid) {
+                             const uint64_t* weights, bool want_weights, uint64_t* out_lhs, uint64_t* out_rhs, int* valid,
+                             const VcWire* wire = nullptr) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
     auto invalid = [&](const std::string& why) {
         ctx->last_error = "verify cells: " + why;
@@ -3299,10 +3378,15 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
     };
     CellsShape sh;
     if (!cells_shape(0, log_domain, log_cell, &sh)) return invalid("unsupported shape (log_domain, log_cell)");
+    if (wire && wire->order != KZG_ORDER_NATURAL && wire->order != KZG_ORDER_BIT_REVERSED)
+        return invalid("order is neither KZG_ORDER_NATURAL nor KZG_ORDER_BIT_REVERSED");
     if (k > KZG_VERIFY_MAX_CELLS) return invalid("more than KZG_VERIFY_MAX_CELLS records");
     if (num_commitments > KZG_VERIFY_MAX_CELLS) return invalid("more than KZG_VERIFY_MAX_CELLS commitments");
-    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !commitments_p1) ||
-        (k && (!commitment_idx || !cell_ids || !cells || !proofs_p1 || !setup_g2 || (want_weights && !weights))))
+    const void* in_commitments = wire ? (const void*)wire->commitments48 : commitments_p1;
+    const void* in_cells = wire ? (const void*)wire->values_be : cells;
+    const void* in_proofs = wire ? (const void*)wire->proofs48 : proofs_p1;
+    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !in_commitments) ||
+        (k && (!commitment_idx || !cell_ids || !in_cells || !in_proofs || !setup_g2 || (want_weights && !weights))))
         return invalid("a required pointer is NULL");
     if (!k) {
         if (want_weights) {
@@ -3320,7 +3404,7 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
         if (cell_ids[t] >= sh.cells)
             return invalid("record " + std::to_string(t) + ": cell id " + std::to_string(cell_ids[t]) + " is not below N / l");
     }
-    for (size_t t = 0; t < k; t++)
+    for (size_t t = 0; t < k && !wire; t++)  // (byte strings: the device's decoder checks them)
         for (size_t i = 0; i < sh.l; i++) {
             hf::Fr v;
             std::memcpy(v.l, cells + 4 * (t * sh.l + i), 32);
@@ -3330,14 +3414,15 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
     hf::G2Affine g2[2];
     {
         const int rci = vc_check_inputs(ctx, "verify cells", want_weights ? weights : nullptr, proofs_p1, k, commitments_p1,
-                                        num_commitments, setup_g2, g2_stride_bytes, sh.l, "l", g2);
+                                        num_commitments, setup_g2, g2_stride_bytes, sh.l, "l", g2, wire != nullptr);
         if (rci) return rci;
     }
     if (ctx->multi) {
         int rc = KZG_OK;
         kzg_ctx* kid = cells_kid(ctx, &rc);
-        return kid ? verify_cells_impl(kid, commitments_p1, num_commitments, commitment_idx, cell_ids, cells, proofs_p1, k, log_domain,
-                                       log_cell, setup_g2, g2_stride_bytes, weights, want_weights, out_lhs, out_rhs, valid)
+        return kid ? forwarded(ctx, kid, verify_cells_impl(kid, commitments_p1, num_commitments, commitment_idx, cell_ids, cells,
+                                                           proofs_p1, k, log_domain, log_cell, setup_g2, g2_stride_bytes, weights,
+                                                           want_weights, out_lhs, out_rhs, valid, wire))
                    : rc;
     }
     VcBatch vb;
@@ -3347,6 +3432,18 @@ static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_
     vb.commitments = commitments_p1;
     vb.cells = cells;
     vb.proofs = proofs_p1;
+    std::vector<uint32_t> own_ids;
+    if (wire) {
+        vb.wire_commitments = wire->commitments48;
+        vb.wire_proofs = wire->proofs48;
+        vb.wire_values = wire->values_be;
+        vb.bit_reversed = wire->order == KZG_ORDER_BIT_REVERSED;
+        if (vb.bit_reversed) {  // the sampling specs' cell c is this API's cell brp(c) over the N / l cells
+            own_ids.resize(k);
+            for (size_t t = 0; t < k; t++) own_ids[t] = wire_brp(cell_ids[t], sh.log_n - sh.log_l);
+            cell_ids = own_ids.data();
+        }
+    }
     std::vector<hf::Fr> rho;
     {
         const int rcw = vc_weights(ctx, "verify cells", want_weights ? weights : nullptr, k, &rho, &vb.glv);
@@ -3404,8 +3501,12 @@ constexpr size_t kBaryMinValues = 8;  // staging room per polynomial, in values:
 
 // P_b(z_b) for every polynomial of the batch, in chunks through one slot's staging buffers.  d_ys (device, 8 words per
 // polynomial) receives the values when given; out_ys (host) when given.  Validated arguments, single-device context.
+// wire_be: the values are 32-byte big-endian strings at a stride of 32 x stride bytes per polynomial (evals null), decoded on
+// the device through the kVcWire workspace -- the caller holds fk20_mu -- and read in bit-reversed order when asked; a value
+// not below r is KZG_ERR_INVALID_ARG, named under `what`.
 static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t batch, size_t stride, const uint64_t* zs,
-                     uint32_t* d_ys, uint64_t* out_ys) {
+                     uint32_t* d_ys, uint64_t* out_ys, const uint8_t* wire_be = nullptr, bool bit_reversed = false,
+                     const char* what = "evaluate evaluations") {
     const size_t n = (size_t)1 << lg;
     std::vector<Fr30> z30(batch);
     for (size_t b = 0; b < batch; b++) {
@@ -3425,6 +3526,8 @@ static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t ba
     const size_t chunk = std::min(batch, std::max<size_t>(1, kBaryChunkValues / per));
     rc = ensure_slot_basics(ctx, s);
     if (rc == KZG_OK) rc = ensure_poly(ctx, s, chunk * per);
+    void* wire = nullptr;  // a chunk's bytes, then the error word
+    if (rc == KZG_OK && wire_be) rc = vc_ws(ctx, kVcWire, chunk * n * 32 + 16, &wire);
     if (rc) return rc;
     const uint32_t tiles = bary_tiles(lg);
     const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
@@ -3435,7 +3538,16 @@ static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t ba
     res += (4 - ((res - s.d_q) & 3)) & 3;  // 16-byte aligned
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t bc = std::min(chunk, batch - b0);
-        if (stride == n || bc == 1)
+        uint32_t herr = 0xffffffffu;
+        if (wire_be) {
+            uint32_t* d_err = (uint32_t*)((char*)wire + chunk * n * 32);
+            const uint8_t* src = wire_be + 32 * b0 * stride;
+            if (stride == n || bc == 1) HIP_TRY(ctx, hipMemcpyAsync(wire, src, bc * n * 32, hipMemcpyHostToDevice, s.stream));
+            else HIP_TRY(ctx, hipMemcpy2DAsync(wire, n * 32, src, stride * 32, n * 32, bc, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_err, 0xff, 4, s.stream));
+            launch_wire_fr(s.stream, wire, (uint32_t)(bc * n), lg, bit_reversed, s.d_stage, d_err);
+            HIP_TRY(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s.stream));
+        } else if (stride == n || bc == 1)
             HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, evals + 4 * b0 * stride, bc * n * 32, hipMemcpyHostToDevice, s.stream));
         else
             HIP_TRY(ctx, hipMemcpy2DAsync(s.d_stage, n * 32, evals + 4 * b0 * stride, stride * 32, n * 32, bc, hipMemcpyHostToDevice,
@@ -3445,16 +3557,15 @@ static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t ba
         launch_bary(s.stream, s.d_stage, lg, (uint32_t)bc, dz, ctx->d_ntt_tw, inv_n, partial, out);
         HIP_TRY(ctx, hipGetLastError());
         if (out_ys) HIP_TRY(ctx, hipMemcpyAsync(out_ys + 4 * b0, out, bc * 32, hipMemcpyDeviceToHost, s.stream));
-        rc = vc_sync(ctx, lk, s.stream, "evaluate evaluations");
+        rc = vc_sync(ctx, lk, s.stream, what);
         if (rc) return rc;
+        if (herr != 0xffffffffu) {
+            ctx->last_error = std::string(what) + ": polynomial " + std::to_string(b0 + (herr >> lg)) + ": value " +
+                              std::to_string(herr & (n - 1)) + " is not below r";
+            return KZG_ERR_INVALID_ARG;
+        }
     }
     return KZG_OK;
-}
-
-// a call forwarded to a device's context before its inputs were checked: the parent reports what that context found
-static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
-    if (rc) ctx->last_error = kid->last_error;
-    return rc;
 }
 
 // the arguments of the two evaluation-form entry points; *lg receives log2 n
@@ -3514,7 +3625,7 @@ int kzg_evaluate_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, 
 static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
                                 const uint64_t* zs, const uint64_t* ys, const uint32_t* d_ys, const uint64_t* proofs_p1, size_t k,
                                 const void* setup_g2, size_t g2_stride_bytes, const uint64_t* weights, bool want_weights,
-                                uint64_t* out_lhs, uint64_t* out_rhs, int* valid) {
+                                uint64_t* out_lhs, uint64_t* out_rhs, int* valid, const VcWire* wire = nullptr) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
     const char* what = "verify openings";
     auto invalid = [&](const std::string& why) {
@@ -3523,8 +3634,14 @@ static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, si
     };
     if (k > KZG_VERIFY_MAX_OPENINGS) return invalid("more than KZG_VERIFY_MAX_OPENINGS records");
     if (num_commitments > KZG_VERIFY_MAX_OPENINGS) return invalid("more than KZG_VERIFY_MAX_OPENINGS commitments");
-    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !commitments_p1) ||
-        (k && ((!commitment_idx && !d_ys) || !zs || (!ys && !d_ys) || !proofs_p1 || !setup_g2 || (want_weights && !weights))))
+    // wire (section 4.12): the commitments and proofs are its byte strings, and so are the points and the claimed values
+    // unless they come decoded (zs) or on the device (d_ys), as from kzg_verify_blobs_batch_bytes
+    const void* in_commitments = wire ? (const void*)wire->commitments48 : commitments_p1;
+    const void* in_proofs = wire ? (const void*)wire->proofs48 : proofs_p1;
+    const void* in_zs = wire && wire->zs_be ? (const void*)wire->zs_be : zs;
+    const void* in_ys = wire ? (const void*)wire->values_be : ys;
+    if (!valid || (want_weights && (!out_lhs || !out_rhs)) || (num_commitments && !in_commitments) ||
+        (k && ((!commitment_idx && !d_ys) || !in_zs || (!in_ys && !d_ys) || !in_proofs || !setup_g2 || (want_weights && !weights))))
         return invalid("a required pointer is NULL");
     if (!k) {
         if (want_weights) {
@@ -3540,7 +3657,7 @@ static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, si
         kzg_ctx* kid = cells_kid(ctx, &rc);
         return kid ? forwarded(ctx, kid, verify_openings_impl(kid, commitments_p1, num_commitments, commitment_idx, zs, ys, d_ys,
                                                               proofs_p1, k, setup_g2, g2_stride_bytes, weights, want_weights,
-                                                              out_lhs, out_rhs, valid))
+                                                              out_lhs, out_rhs, valid, wire))
                    : rc;
     }
     if (commitment_idx)
@@ -3548,6 +3665,14 @@ static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, si
             if (commitment_idx[t] >= num_commitments)
                 return invalid("record " + std::to_string(t) + ": commitment index " + std::to_string(commitment_idx[t]) +
                                " is not below num_commitments");
+    std::vector<uint64_t> own_zs;
+    if (wire && wire->zs_be) {  // the host groups the records by point and splits the points: it decodes them
+        own_zs.resize(4 * k);
+        for (size_t t = 0; t < k; t++)
+            if (!wire_fr_host(wire->zs_be + 32 * t, own_zs.data() + 4 * t))
+                return invalid("record " + std::to_string(t) + ": the point z is not below r");
+        zs = own_zs.data();
+    }
     if (ys)  // (with d_ys the caller has checked the points and the device has made the values)
         for (size_t t = 0; t < k; t++) {
             hf::Fr v;
@@ -3559,7 +3684,7 @@ static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, si
     hf::G2Affine g2[2];
     {
         const int rci = vc_check_inputs(ctx, what, want_weights ? weights : nullptr, proofs_p1, k, commitments_p1, num_commitments,
-                                        setup_g2, g2_stride_bytes, 1, "1", g2);
+                                        setup_g2, g2_stride_bytes, 1, "1", g2, wire != nullptr);
         if (rci) return rci;
     }
     CellsShape sh;
@@ -3574,6 +3699,11 @@ static int verify_openings_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, si
     vb.fk20_held = d_ys != nullptr;
     vb.proofs = proofs_p1;
     vb.what = what;
+    if (wire) {
+        vb.wire_commitments = wire->commitments48;
+        vb.wire_proofs = wire->proofs48;
+        vb.wire_values = d_ys ? nullptr : wire->values_be;
+    }
     std::vector<hf::Fr> rho;
     {
         const int rcw = vc_weights(ctx, what, want_weights ? weights : nullptr, k, &rho, &vb.glv);
@@ -3640,50 +3770,261 @@ int kzg_verify_openings_lincomb(kzg_ctx* ctx, const uint64_t* commitments_p1, si
                                 g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid);
 }
 
-int kzg_verify_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
-                                 const uint64_t* commitments_p1, const uint64_t* zs, const uint64_t* proofs_p1, const void* setup_g2,
-                                 size_t g2_stride_bytes, uint64_t* out_ys, int* valid) {
+namespace {
+// kzg_verify_blobs_batch_bytes's inputs (section 4.12); evals_fr_mont, commitments_p1, zs, proofs_p1 and out_ys are null then
+struct BlobWire {
+    const uint8_t* blobs_be;
+    unsigned order;
+    const uint8_t* commitments48;
+    const uint8_t* zs_be;
+    const uint8_t* proofs48;
+    uint8_t* out_ys_be;
+};
+}  // namespace
+
+static int verify_evaluations_impl(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                   const uint64_t* commitments_p1, const uint64_t* zs, const uint64_t* proofs_p1, const void* setup_g2,
+                                   size_t g2_stride_bytes, uint64_t* out_ys, int* valid, const BlobWire* wire) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
+    const char* what = wire ? "verify blobs" : "verify evaluations";
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
     uint32_t lg = 0;
-    int rc = bary_check(ctx, "verify evaluations", evals_fr_mont, n, batch, stride, zs, &lg);
+    int rc = bary_check(ctx, what, wire ? (const uint64_t*)wire->blobs_be : evals_fr_mont, n, batch, stride,
+                        wire ? (const uint64_t*)wire->zs_be : zs, &lg);
     if (rc) return rc;
-    if (batch > KZG_VERIFY_MAX_OPENINGS) {
-        ctx->last_error = "verify evaluations: more than KZG_VERIFY_MAX_OPENINGS polynomials";
-        return KZG_ERR_INVALID_ARG;
-    }
-    if (!valid || (batch && (!commitments_p1 || !proofs_p1 || !setup_g2))) {
-        ctx->last_error = "verify evaluations: a required pointer is NULL";
-        return KZG_ERR_INVALID_ARG;
-    }
+    if (wire && wire->order != KZG_ORDER_NATURAL && wire->order != KZG_ORDER_BIT_REVERSED)
+        return invalid("order is neither KZG_ORDER_NATURAL nor KZG_ORDER_BIT_REVERSED");
+    if (batch > KZG_VERIFY_MAX_OPENINGS) return invalid("more than KZG_VERIFY_MAX_OPENINGS polynomials");
+    if (!valid || (batch && (!(wire ? (const void*)wire->commitments48 : commitments_p1) ||
+                             !(wire ? (const void*)wire->proofs48 : proofs_p1) || !setup_g2)))
+        return invalid("a required pointer is NULL");
     if (!batch) {
         *valid = 1;
         return KZG_OK;
     }
     if (ctx->multi) {
         kzg_ctx* kid = cells_kid(ctx, &rc);
-        return kid ? forwarded(ctx, kid, kzg_verify_evaluations_batch(kid, evals_fr_mont, n, batch, stride, commitments_p1, zs,
-                                                                      proofs_p1, setup_g2, g2_stride_bytes, out_ys, valid))
+        return kid ? forwarded(ctx, kid, verify_evaluations_impl(kid, evals_fr_mont, n, batch, stride, commitments_p1, zs, proofs_p1,
+                                                                 setup_g2, g2_stride_bytes, out_ys, valid, wire))
                    : rc;
     }
-    rc = bary_check_values(ctx, "verify evaluations", evals_fr_mont, n, batch, stride, zs);
-    if (rc) return rc;
+    std::vector<uint64_t> own_zs, own_ys;
+    if (wire) {  // the points on the host (the verifier groups and splits them); the values on the device, chunk by chunk
+        own_zs.resize(4 * batch);
+        for (size_t b = 0; b < batch; b++)
+            if (!wire_fr_host(wire->zs_be + 32 * b, own_zs.data() + 4 * b))
+                return invalid("polynomial " + std::to_string(b) + ": the point z is not below r");
+        zs = own_zs.data();
+        if (wire->out_ys_be) {
+            own_ys.resize(4 * batch);
+            out_ys = own_ys.data();
+        }
+    } else {
+        rc = bary_check_values(ctx, what, evals_fr_mont, n, batch, stride, zs);
+        if (rc) return rc;
+    }
     // the values go from the evaluation straight into the verifier's value buffer: fk20_mu guards that workspace for both
     std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
     void* d_ys = nullptr;
     {
         std::unique_lock<std::mutex> lk(ctx->mu);
         if (!ctx->n || !ctx->slots_ready) {
-            ctx->last_error = "verify evaluations: the SRS is empty";
+            ctx->last_error = std::string(what) + ": the SRS is empty";
             return KZG_ERR_NO_SRS;
         }
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         rc = vc_ws(ctx, kVcCells, batch * 32, &d_ys);
         if (rc) return rc;
     }
-    rc = bary_host(ctx, evals_fr_mont, lg, batch, stride, zs, (uint32_t*)d_ys, out_ys);
+    rc = bary_host(ctx, evals_fr_mont, lg, batch, stride, zs, (uint32_t*)d_ys, out_ys, wire ? wire->blobs_be : nullptr,
+                   wire && wire->order == KZG_ORDER_BIT_REVERSED, what);
     if (rc) return rc;
+    if (wire && wire->out_ys_be)
+        for (size_t b = 0; b < batch; b++) wire_fr_to_be(own_ys.data() + 4 * b, wire->out_ys_be + 32 * b);
+    VcWire vw;
+    if (wire) {
+        vw.commitments48 = wire->commitments48;
+        vw.proofs48 = wire->proofs48;
+    }
     return verify_openings_impl(ctx, commitments_p1, batch, nullptr, zs, nullptr, (const uint32_t*)d_ys, proofs_p1, batch, setup_g2,
-                                g2_stride_bytes, nullptr, false, nullptr, nullptr, valid);
+                                g2_stride_bytes, nullptr, false, nullptr, nullptr, valid, wire ? &vw : nullptr);
+}
+
+int kzg_verify_evaluations_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride,
+                                 const uint64_t* commitments_p1, const uint64_t* zs, const uint64_t* proofs_p1, const void* setup_g2,
+                                 size_t g2_stride_bytes, uint64_t* out_ys, int* valid) {
+    return verify_evaluations_impl(ctx, evals_fr_mont, n, batch, stride, commitments_p1, zs, proofs_p1, setup_g2, g2_stride_bytes,
+                                   out_ys, valid, nullptr);
+}
+
+// ---- the verifiers on inputs as they travel (wire_kernels.hip) -------------------------------------------
+
+int kzg_verify_cells_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                 const uint32_t* cell_ids, const uint8_t* cells_be, const uint8_t* proofs48, size_t k,
+                                 unsigned log_domain, unsigned log_cell, unsigned order, const void* setup_g2, size_t g2_stride_bytes,
+                                 int* valid) {
+    VcWire w;
+    w.commitments48 = commitments48;
+    w.proofs48 = proofs48;
+    w.values_be = cells_be;
+    w.order = order;
+    return verify_cells_impl(ctx, nullptr, num_commitments, commitment_idx, cell_ids, nullptr, nullptr, k, log_domain, log_cell,
+                             setup_g2, g2_stride_bytes, nullptr, false, nullptr, nullptr, valid, &w);
+}
+
+int kzg_verify_cells_lincomb_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                   const uint32_t* cell_ids, const uint8_t* cells_be, const uint8_t* proofs48, size_t k,
+                                   unsigned log_domain, unsigned log_cell, unsigned order, const void* setup_g2,
+                                   size_t g2_stride_bytes, const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18],
+                                   int* valid) {
+    VcWire w;
+    w.commitments48 = commitments48;
+    w.proofs48 = proofs48;
+    w.values_be = cells_be;
+    w.order = order;
+    return verify_cells_impl(ctx, nullptr, num_commitments, commitment_idx, cell_ids, nullptr, nullptr, k, log_domain, log_cell,
+                             setup_g2, g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid, &w);
+}
+
+static int verify_openings_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                 const uint8_t* zs_be, const uint8_t* ys_be, const uint8_t* proofs48, size_t k, const void* setup_g2,
+                                 size_t g2_stride_bytes, const uint64_t* weights, bool want_weights, uint64_t* out_lhs,
+                                 uint64_t* out_rhs, int* valid) {
+    if (ctx && k && (!commitment_idx || !ys_be)) {
+        ctx->last_error = "verify openings: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    VcWire w;
+    w.commitments48 = commitments48;
+    w.proofs48 = proofs48;
+    w.values_be = ys_be;
+    w.zs_be = zs_be;
+    return verify_openings_impl(ctx, nullptr, num_commitments, commitment_idx, nullptr, nullptr, nullptr, nullptr, k, setup_g2,
+                                g2_stride_bytes, weights, want_weights, out_lhs, out_rhs, valid, &w);
+}
+
+int kzg_verify_openings_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments, const uint32_t* commitment_idx,
+                                    const uint8_t* zs_be, const uint8_t* ys_be, const uint8_t* proofs48, size_t k,
+                                    const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    return verify_openings_bytes(ctx, commitments48, num_commitments, commitment_idx, zs_be, ys_be, proofs48, k, setup_g2,
+                                 g2_stride_bytes, nullptr, false, nullptr, nullptr, valid);
+}
+
+int kzg_verify_openings_lincomb_bytes(kzg_ctx* ctx, const uint8_t* commitments48, size_t num_commitments,
+                                      const uint32_t* commitment_idx, const uint8_t* zs_be, const uint8_t* ys_be,
+                                      const uint8_t* proofs48, size_t k, const void* setup_g2, size_t g2_stride_bytes,
+                                      const uint64_t* weights, uint64_t out_lhs_p1[18], uint64_t out_rhs_p1[18], int* valid) {
+    return verify_openings_bytes(ctx, commitments48, num_commitments, commitment_idx, zs_be, ys_be, proofs48, k, setup_g2,
+                                 g2_stride_bytes, weights, true, out_lhs_p1, out_rhs_p1, valid);
+}
+
+int kzg_verify_blobs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                 const uint8_t* commitments48, const uint8_t* zs_be, const uint8_t* proofs48, const void* setup_g2,
+                                 size_t g2_stride_bytes, uint8_t* out_ys_be, int* valid) {
+    const BlobWire w = {blobs_be, order, commitments48, zs_be, proofs48, out_ys_be};
+    return verify_evaluations_impl(ctx, nullptr, n, batch, stride, nullptr, nullptr, nullptr, setup_g2, g2_stride_bytes, nullptr,
+                                   valid, &w);
+}
+
+// the decoders on their own: building blocks and test hooks; they need no SRS
+int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup, uint64_t* out_p1, size_t* bad_index) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (n > kMaxCoefficients - 1 || (n && (!in48 || !out_p1))) {
+        ctx->last_error = "g1 uncompress: a required pointer is NULL or n does not fit 32 bits";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!n) return KZG_OK;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_g1_uncompress_batch(kid, in48, n, check_subgroup, out_p1, bad_index));
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    void *p1 = nullptr, *aff = nullptr, *coef = nullptr, *dglv = nullptr, *g1 = nullptr;
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcP1, n * 144, &p1);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcAff, n * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, kVcErrWords * 4, &coef);
+    if (rc == KZG_OK && check_subgroup) rc = vc_ws(ctx, kVcGlv, n * sizeof(Glv), &dglv);
+    if (rc == KZG_OK && check_subgroup) rc = vc_ws(ctx, kVcG1, n * kXyzzBytes, &g1);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    uint32_t* err = (uint32_t*)coef;
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kVcErrWords * 4, st));
+    HIP_TRY(ctx, hipMemcpyAsync(p1, in48, n * 48, hipMemcpyHostToDevice, st));
+    launch_wire_g1(st, p1, nullptr, (uint32_t)n, aff, (uint32_t)kAffineBytes, err + kVcErrWireProof);
+    if (check_subgroup) {  // the ladder's membership test with a weight of zero: [0] P costs nothing
+        HIP_TRY(ctx, hipMemsetAsync(dglv, 0, n * sizeof(Glv), st));
+        launch_vc_ladder(st, aff, nullptr, (const Glv*)dglv, (uint32_t)n, (uint32_t)n, (uint32_t)n, g1, g1, err);
+    }
+    launch_affine_to_p1(st, aff, (uint32_t)n, p1);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t herr[kVcErrWords];
+    HIP_TRY(ctx, hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_p1, p1, n * 144, hipMemcpyDeviceToHost, st));
+    rc = vc_sync(ctx, lk, st, "g1 uncompress");
+    if (rc) return rc;
+    const uint32_t enc = herr[kVcErrWireProof], grp = std::min(herr[kVcErrCurve], herr[kVcErrG1]);
+    if (enc != 0xffffffffu || grp != 0xffffffffu) {
+        const uint32_t bad = std::min(enc, grp);
+        if (bad_index) *bad_index = bad;
+        ctx->last_error = "g1 uncompress: point " + std::to_string(bad) + (bad == enc ? " is not a valid compressed point" : " is not in G1");
+        return KZG_ERR_INVALID_ARG;
+    }
+    return KZG_OK;
+}
+
+int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint64_t* out_fr_mont, size_t* bad_index) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (n > kMaxCoefficients - 1 || (n && (!in32_be || !out_fr_mont))) {
+        ctx->last_error = "fr from bytes: a required pointer is NULL or n does not fit 32 bits";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!n) return KZG_OK;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_fr_from_bytes_batch(kid, in32_be, n, out_fr_mont, bad_index));
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    void *wire = nullptr, *vals = nullptr, *coef = nullptr;
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcWire, n * 32, &wire);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCells, n * 32, &vals);
+    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, kVcErrWords * 4, &coef);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    uint32_t* err = (uint32_t*)coef;
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kVcErrWords * 4, st));
+    HIP_TRY(ctx, hipMemcpyAsync(wire, in32_be, n * 32, hipMemcpyHostToDevice, st));
+    launch_wire_fr(st, wire, (uint32_t)n, 0, false, vals, err + kVcErrWireValue);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t herr = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&herr, err + kVcErrWireValue, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_fr_mont, vals, n * 32, hipMemcpyDeviceToHost, st));
+    rc = vc_sync(ctx, lk, st, "fr from bytes");
+    if (rc) return rc;
+    if (herr != 0xffffffffu) {
+        if (bad_index) *bad_index = herr;
+        ctx->last_error = "fr from bytes: value " + std::to_string(herr) + " is not below r";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return KZG_OK;
 }
 
 // ---- raw device memory -----------------------------------------------------------------------

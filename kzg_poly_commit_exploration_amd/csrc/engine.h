@@ -142,6 +142,16 @@ void launch_affine96_to_table(hipStream_t s, const void* d_affine96, uint32_t n,
 // index + 1 of the first malformed point
 void launch_uncompress(hipStream_t s, const void* d_compressed, uint32_t n, void* d_table, uint32_t* d_status);
 
+// ---- wire_kernels.hip: inputs decoded from their wire bytes (wire30.hip.h; 16-byte aligned arrays) ----------------------
+// n compressed points (48 bytes each; point d_src[i] when d_src is given) -> affine table records at d_records + i *
+// stride_bytes (a multiple of 16, >= 128), infinity for a point that does not decode; *d_err (pre-set to 0xffffffff)
+// receives the least source index that did not decode
+void launch_wire_g1(hipStream_t s, const void* d_in48, const uint32_t* d_src, uint32_t n, void* d_records, uint32_t stride_bytes,
+                    uint32_t* d_err);
+// n big-endian scalars (32 bytes each) -> blst_fr images; bit_reversed: value i of every row of 2^log_row values goes to
+// position brp_(log_row)(i) of its row (n a multiple of the row length); *d_err: the least input index not below r
+void launch_wire_fr(hipStream_t s, const void* d_in32, uint32_t n, uint32_t log_row, bool bit_reversed, void* d_out, uint32_t* d_err);
+
 // ---- msm_accum.hip (table format) ---------------------------------------------------------
 // native table entries -> blst_p1 (Z = Montgomery one / all zero for infinity)
 void launch_affine_to_p1(hipStream_t s, const void* d_affine, uint32_t n, void* d_p1_out);

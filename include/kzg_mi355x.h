@@ -479,6 +479,57 @@ int kzg_verify_blobs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n
 int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup, uint64_t* out_p1, size_t* bad_index);
 int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint64_t* out_fr_mont, size_t* bad_index);
 
+/* ---- the producing side on blobs as they travel ----------------------------------------------------
+ * The mirror of the section above: a block builder or a node that reconstructs data holds blobs as bytes, in evaluation form,
+ * and wants 48-byte commitments, 48-byte proofs and cell bytes.  The calls below take the blob bytes as they are and return
+ * exactly those: the values are decoded on the device, interpolated there (one batched inverse transform), and the coefficients
+ * stay resident for the commitments (the batched MSM), the cells (one batched transform and gather) and the FK20 proofs; points
+ * and values are encoded on the device (one lane each) and leave in one download per chunk of polynomials.  The
+ * coefficients never visit the host, and it converts no value and no proof; the commitments alone come off the MSM's host tail as
+ * blst_p1 and are compressed there, one host compression per blob.
+ * Blob b is n x 32 big-endian bytes at blobs_be + 32 b stride (stride in values, >= n when batch > 1): the values of P_b over
+ * the n-domain as kzg_commit_evaluations takes them, n a power of two <= 2^KZG_NTT_MAX_LOG and <= N = 2^log_domain.  order as
+ * in kzg_verify_blobs_batch_bytes: with KZG_ORDER_BIT_REVERSED, value i as sent is this API's value brp(i) over log2 n bits.
+ * Outputs: out_commitments48 + 48 b; out_cells_be, batch x N x 32 bytes; out_proofs48, batch x (N / l) x 48 bytes.  With
+ * KZG_ORDER_NATURAL, cells and proofs are in this API's cell-major order and numbering.  With KZG_ORDER_BIT_REVERSED they are in
+ * the specs' order: slot c holds this API's cell brp(c) over log_domain - log_cell bits with its values in brp order over
+ * log_cell bits, and the proof in slot c is that cell's -- the mappings stated above for kzg_verify_cells_batch_bytes.
+ * Meaning, for inputs that decode: the commitment is kzg_g1_compress(kzg_commit_evaluations(decoded blob)); cells and proofs
+ * are those of kzg_cells_and_proofs_fk20 on the interpolated coefficients, encoded; byte for byte (every quantity is exact
+ * arithmetic with one canonical encoding).  kzg_recover_cells_and_proofs_bytes takes and returns what
+ * kzg_recover_cells_and_proofs does for the decoded input (cells_be: batch x k x l x 32 bytes); cell_ids and the values inside
+ * a cell follow `order`; it has no coefficient output.
+ * Errors, in this order: KZG_ERR_INVALID_ARG for the shape, an order that is neither constant, a NULL required pointer, stride <
+ * n with batch > 1; KZG_ERR_NO_SRS; KZG_ERR_INVALID_ARG from the device with kzg_last_error naming "polynomial b: value i is not
+ * below r" (recovery: "polynomial b, cell c: value i is not below r"; i, and c, as sent); KZG_ERR_REMAINDER for recovery, as its
+ * sibling; KZG_ERR_DEGREE_TOO_HIGH when n' > kzg_srs_len and commitments are asked for, or n' - l > kzg_srs_len for proofs (n'
+ * = 1 + the degree of the interpolated polynomial; kzg_last_error names the polynomial).  batch = 0 does nothing.  A failed call
+ * writes no output the caller may rely on.
+ * Thread safety as kzg_cells_and_proofs_fk20 (the calls share its workspaces and queue behind one another); a replicated
+ * multi-device context forwards to one device, a range-split one returns KZG_ERR_INVALID_ARG.  Polynomials go through the
+ * workspaces in chunks, as in kzg_cells_and_proofs_fk20.
+ * Measured (MI355X, n = 4096, log_domain 13, log_cell 6, KZG_ORDER_BIT_REVERSED, all three outputs,
+ * medians of three repetitions): 64 blobs per call 50.7-51.1 ms, against 106.3-108.8 ms for the existing entry points chained by
+ * hand (kzg_fr_from_bytes_batch, kzg_ntt per blob, kzg_commit_batch, kzg_cells_and_proofs_fk20, kzg_g1_compress per point).
+ * There is no crossover down to 1 blob per call, and no gain to speak of there either: 31.5-31.9 ms against 32.6 ms, both being
+ * the time FK20 takes for one polynomial. */
+int kzg_blobs_to_commitments_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                   uint8_t* out_commitments48);
+int kzg_blobs_to_cells_and_proofs_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride,
+                                        unsigned log_domain, unsigned log_cell, unsigned order,
+                                        uint8_t* out_commitments48 /* may be NULL */, uint8_t* out_cells_be /* may be NULL */,
+                                        uint8_t* out_proofs48);
+int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_domain, unsigned log_cell, unsigned order,
+                                       const uint32_t* cell_ids, size_t k, const uint8_t* cells_be, size_t batch,
+                                       uint8_t* out_cells_be /* may be NULL */, uint8_t* out_proofs48 /* may be NULL */);
+/* building blocks and test hooks, the inverses of kzg_g1_uncompress_batch / kzg_fr_from_bytes_batch: n blst_p1 (any Z; all zero
+ * = infinity) -> n x 48 bytes, each what kzg_g1_compress returns for that point (normalised and encoded on the device); n
+ * blst_fr -> n x 32 big-endian bytes, a value not below r giving KZG_ERR_INVALID_ARG and *bad_index = the least bad index
+ * ((size_t)-1 otherwise; bad_index may be NULL).  n = 0 does nothing.  They need no SRS; thread safety as kzg_g1_dft;
+ * multi-device contexts run them on their first device. */
+int kzg_g1_compress_batch(kzg_ctx* ctx, const uint64_t* in_p1, size_t n, uint8_t* out48);
+int kzg_fr_to_bytes_batch(kzg_ctx* ctx, const uint64_t* in_fr_mont, size_t n, uint8_t* out32_be, size_t* bad_index);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

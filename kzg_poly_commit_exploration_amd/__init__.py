@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "kzg_evaluate_evaluations_batch", "kzg_verify_openings_batch", "kzg_verify_openings_lincomb", "kzg_verify_evaluations_batch",
     "kzg_verify_cells_batch_bytes", "kzg_verify_cells_lincomb_bytes", "kzg_verify_openings_batch_bytes",
     "kzg_verify_openings_lincomb_bytes", "kzg_verify_blobs_batch_bytes", "kzg_g1_uncompress_batch", "kzg_fr_from_bytes_batch",
+    "kzg_blobs_to_commitments_bytes", "kzg_blobs_to_cells_and_proofs_bytes", "kzg_recover_cells_and_proofs_bytes",
+    "kzg_g1_compress_batch", "kzg_fr_to_bytes_batch",
 ]
 KZG_ORDER_NATURAL = 0
 KZG_ORDER_BIT_REVERSED = 1
@@ -179,6 +181,11 @@ def load_library():
         "kzg_verify_blobs_batch_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp, vp, sz, vp, C.POINTER(i)]),
         "kzg_g1_uncompress_batch": (i, [vp, vp, sz, i, vp, C.POINTER(sz)]),
         "kzg_fr_from_bytes_batch": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_blobs_to_commitments_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp]),
+        "kzg_blobs_to_cells_and_proofs_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp]),
+        "kzg_recover_cells_and_proofs_bytes": (i, [vp, sz, C.c_uint, C.c_uint, C.c_uint, vp, sz, vp, sz, vp, vp]),
+        "kzg_g1_compress_batch": (i, [vp, vp, sz, vp]),
+        "kzg_fr_to_bytes_batch": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -779,6 +786,79 @@ class Engine:
         _check(self._lib.kzg_verify_blobs_batch_bytes(self._h, opt(a), n, batch, n, order, opt(com), opt(zl), opt(prf), _ptr(g2),
                                                       288, opt(out), C.byref(ok)), self._h)
         return bool(ok.value), (out[:batch].tobytes() if want_ys else None)
+
+    # -- the producing side on blobs as they travel --
+    def g1_compress_batch(self, points):
+        """kzg_g1_compress_batch: n blst_p1 rows (an (n, 18) array, or G1Points; any Z) -> n x 48 bytes, normalised and encoded
+        on the device"""
+        a = self._p1_rows(points) if not isinstance(points, np.ndarray) else np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 18)
+        n = a.shape[0]
+        out = np.zeros((max(n, 1), 48), dtype=np.uint8)
+        _check(self._lib.kzg_g1_compress_batch(self._h, _ptr(a) if n else None, n, _ptr(out)), self._h)
+        return out[:n].tobytes()
+
+    def fr_to_bytes_batch(self, values):
+        """kzg_fr_to_bytes_batch: (n, 4) blst_fr rows -> n x 32 big-endian bytes; a row not below r raises KzgError with its
+        index in .bad_index"""
+        a = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        n = a.shape[0]
+        out = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        bad = C.c_size_t(0)
+        rc = self._lib.kzg_fr_to_bytes_batch(self._h, _ptr(a) if n else None, n, _ptr(out), C.byref(bad))
+        self._check_bad(rc, bad)
+        return out[:n].tobytes()
+
+    def _blobs(self, blobs_be, n, stride):
+        a = self._wire(blobs_be, 32)
+        stride = n if stride is None else stride
+        if not (n and stride >= n and a.shape[0] % stride == 0):  # (not an assert: the C side trusts these lengths)
+            raise ValueError("whole blobs of n values, `stride` values apart")
+        return a, a.shape[0] // stride, stride
+
+    def blobs_to_commitments_bytes(self, blobs_be, n, order=KZG_ORDER_NATURAL, stride=None):
+        """kzg_blobs_to_commitments_bytes: batch x stride x 32 big-endian bytes (bytes or a uint8 array; the first n values of
+        every stride are the blob) -> batch x 48 bytes of compressed commitments"""
+        a, batch, stride = self._blobs(blobs_be, n, stride)
+        out = np.zeros((max(batch, 1), 48), dtype=np.uint8)
+        _check(self._lib.kzg_blobs_to_commitments_bytes(self._h, _ptr(a) if a.size else None, n, batch, stride, order, _ptr(out)),
+               self._h)
+        return out[:batch].tobytes()
+
+    def blobs_to_cells_and_proofs_bytes(self, blobs_be, n, log_domain, log_cell, order=KZG_ORDER_NATURAL, commitments=True,
+                                        cells=True, stride=None):
+        """kzg_blobs_to_cells_and_proofs_bytes: returns (commitments48, cells_be, proofs48) as bytes -- batch x 48, batch x N x
+        32 and batch x (N / l) x 48 of them; commitments48 / cells_be are None when not requested"""
+        a, batch, stride = self._blobs(blobs_be, n, stride)
+        N = 1 << log_domain
+        M = 1 << max(log_domain - log_cell, 0)
+        out_c = np.zeros((max(batch, 1), 48), dtype=np.uint8) if commitments else None
+        out_v = np.zeros((max(batch, 1), N * 32), dtype=np.uint8) if cells else None
+        out_p = np.zeros((max(batch, 1), M * 48), dtype=np.uint8)
+        opt = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(self._lib.kzg_blobs_to_cells_and_proofs_bytes(self._h, _ptr(a) if a.size else None, n, batch, stride, log_domain,
+                                                             log_cell, order, opt(out_c), opt(out_v), _ptr(out_p)), self._h)
+        return (out_c[:batch].tobytes() if commitments else None, out_v[:batch].tobytes() if cells else None,
+                out_p[:batch].tobytes())
+
+    def recover_cells_and_proofs_bytes(self, n, log_domain, log_cell, cell_ids, cells_be, order=KZG_ORDER_NATURAL, cells_out=True,
+                                       proofs=True):
+        """kzg_recover_cells_and_proofs_bytes: cells_be is batch x k x l x 32 big-endian bytes, row t of a polynomial holding
+        cell cell_ids[t] (ids and the values inside a cell in the order asked).  Returns (cells_be, proofs48) as
+        blobs_to_cells_and_proofs_bytes returns them, each None when not requested"""
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        a = self._wire(cells_be, 32)
+        per = len(ids) << log_cell
+        if not (per and a.shape[0] % per == 0):
+            raise ValueError("k cells of l values per polynomial")
+        batch = a.shape[0] // per
+        N = 1 << log_domain
+        M = 1 << max(log_domain - log_cell, 0)
+        out_v = np.zeros((max(batch, 1), N * 32), dtype=np.uint8) if cells_out else None
+        out_p = np.zeros((max(batch, 1), M * 48), dtype=np.uint8) if proofs else None
+        opt = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(self._lib.kzg_recover_cells_and_proofs_bytes(self._h, n, log_domain, log_cell, order, _ptr(ids), len(ids),
+                                                            _ptr(a) if a.size else None, batch, opt(out_v), opt(out_p)), self._h)
+        return (out_v[:batch].tobytes() if cells_out else None, out_p[:batch].tobytes() if proofs else None)
 
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""

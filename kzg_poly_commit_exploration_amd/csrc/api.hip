@@ -191,12 +191,16 @@ struct kzg_ctx {
     // g^i, g^-i (g = 7) in the NTT twiddles' lo / hi shape, built on first use; workspaces grown on demand
     std::mutex recover_mu;
     void* d_rec_g = nullptr;
-    void* rec_ws[9] = {};
-    size_t rec_ws_bytes[9] = {};
+    void* rec_ws[11] = {};
+    size_t rec_ws_bytes[11] = {};
     // batch verification of cells (kzg_verify_cells_batch): workspaces grown on demand, under fk20_mu
     // (the call reads the split twiddles d_glv, which an FK20 call may grow)
     void* vc_ws[17] = {};
     size_t vc_ws_bytes[17] = {};
+    // the producing side on blob bytes (kzg_blobs_to_cells_and_proofs_bytes): workspaces grown on demand,
+    // under fk20_mu (the calls run FK20 from them)
+    void* blob_ws[8] = {};
+    size_t blob_ws_bytes[8] = {};
 };
 
 namespace {
@@ -773,6 +777,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     if (ctx->d_rec_g) hipFree(ctx->d_rec_g);
     for (void* p : ctx->rec_ws) hipFree(p);
     for (void* p : ctx->vc_ws) hipFree(p);
+    for (void* p : ctx->blob_ws) hipFree(p);
     delete ctx;
 }
 
@@ -2550,10 +2555,13 @@ static uint32_t fk20_stream_positions(uint32_t log_L, uint32_t log_l) {
     return ci < (1u << log_L) ? ci : (1u << log_L);
 }
 
-// `batch` polynomials (coefficients at c, n_max per polynomial, contiguous) -> proofs (batch x 2^log_M blst_p1)
+// `batch` polynomials (coefficients at c, n_max per polynomial, contiguous) -> proofs (batch x 2^log_M blst_p1).  d_src: the
+// coefficients are in device memory there (same stride) and coeffs is not read.  keep_affine: the normalised affine proofs stay
+// in the kWsAff workspace, enqueued on st and not waited for, and out_proofs is not written.
 static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const uint64_t* coeffs, size_t stride,
                        size_t batch, size_t n_max, uint32_t m, uint32_t log_L, uint32_t log_l, uint32_t log_M,
-                       uint64_t* out_proofs, void* stream_tab, void* stream_tmp, void* stream_prefix) {
+                       uint64_t* out_proofs, void* stream_tab, void* stream_tmp, void* stream_prefix, const void* d_src = nullptr,
+                       bool keep_affine = false) {
     const size_t L = (size_t)1 << log_L, l = (size_t)1 << log_l, M = (size_t)1 << log_M;
     const size_t X = L > M ? L : M;
     const bool kept = ctx->d_fk20_tab != nullptr;
@@ -2570,7 +2578,8 @@ static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream
     if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPrefix, batch * M * 64, &prefix);
     if (rc == KZG_OK) rc = fk20_ws(ctx, kWsP1, batch * M * 144, &p1);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, coeffs, stride * 32, n_max * 32, batch, hipMemcpyHostToDevice, st));
+    if (d_src) HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, d_src, stride * 32, n_max * 32, batch, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, coeffs, stride * 32, n_max * 32, batch, hipMemcpyHostToDevice, st));
     const Fr30 inv_L = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(log_L)));
     const uint32_t* scal = launch_fk20_fr_side(st, (const uint32_t*)coef, (uint32_t)n_max, m, log_L, log_l, batch, ctx->d_ntt_tw,
                                                inv_L, (uint32_t*)sa, (uint32_t*)sb);
@@ -2589,6 +2598,10 @@ static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream
     launch_fk20_select(st, conv, log_L, m, log_M, batch, h);
     const void* res = launch_g1_dft(st, h, x1, (void*)conv, log_M, batch, tw, ctx->glv_log, false);
     launch_xyzz_to_affine(st, res, (uint32_t)(batch * M), aff, prefix);
+    if (keep_affine) {
+        HIP_TRY(ctx, hipGetLastError());
+        return KZG_OK;
+    }
     launch_affine_to_p1(st, aff, (uint32_t)(batch * M), p1);
     HIP_TRY(ctx, hipGetLastError());
     rc = fk20_sync(ctx, lk, st);
@@ -2756,7 +2769,16 @@ int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint6
 // device; the cells come from the same pass.  Proofs go through fk20_host afterwards with the recovered coefficients (one more
 // upload of them).
 namespace {
-enum : int { kRecIn = 0, kRecA, kRecB, kRecCoef, kRecFlags, kRecPos, kRecMissing, kRecPart, kRecZ, kRecCount };
+enum : int { kRecIn = 0, kRecA, kRecB, kRecCoef, kRecFlags, kRecPos, kRecMissing, kRecPart, kRecZ, kRecWire, kRecErr, kRecCount };
+// the byte-string form of a recovery (section 4.13): the received cells as they travel, decoded on the device; the cells leave
+// encoded; the coefficients of the whole batch stay in device memory (d_coeffs: batch x n x 32 bytes) for FK20
+struct RecWire {
+    const uint8_t* cells_be = nullptr;
+    bool bit_reversed = false;
+    const uint32_t* ids_sent = nullptr;  // the caller's cell ids, for the message that names a value
+    uint8_t* out_cells_be = nullptr;
+    void* d_coeffs = nullptr;
+};
 constexpr size_t kRecMaxBatch = 64;               // polynomials per pass through the workspaces, at most
 constexpr size_t kRecWsBudget = (size_t)2 << 30;  // ... and fewer when their workspaces would pass this
 hf::Fr fr_seven() {
@@ -2818,7 +2840,8 @@ static int ensure_recover_g(kzg_ctx* ctx) {
 // the decode of `batch` validated polynomials: coefficients to out_coeffs, cells to out_cells (either may be null);
 // KZG_ERR_REMAINDER names the first polynomial whose coefficients at [n, N) are not all zero
 static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int32_t* pos, const std::vector<uint32_t>& missing,
-                        size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells) {
+                        size_t k, const uint64_t* cells, size_t batch, uint64_t* out_coeffs, uint64_t* out_cells,
+                        const RecWire* wire = nullptr) {
     std::lock_guard<std::mutex> lkr(ctx->recover_mu);
     std::unique_lock<std::mutex> lk(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2848,7 +2871,21 @@ static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int3
     if (rc == KZG_OK) rc = rec_ws(ctx, kRecPart, (size_t)parts * 2 * M * 32, &part);
     if (rc == KZG_OK) rc = rec_ws(ctx, kRecZ, 2 * M * 32, &z);
     if (rc) return rc;
-    rc = copy_unlocked(ctx, lk, s, in, cells, batch * k * l * 32);
+    uint32_t* derr = nullptr;
+    const bool want_cells = wire ? wire->out_cells_be != nullptr : out_cells != nullptr;
+    if (wire) {  // the bytes as received -> blst_fr images in `in`, the values of every cell put into this API's order
+        void *dwire, *e;
+        rc = rec_ws(ctx, kRecWire, batch * k * l * 32, &dwire);
+        if (rc == KZG_OK) rc = rec_ws(ctx, kRecErr, 8, &e);
+        if (rc) return rc;
+        derr = (uint32_t*)e;
+        HIP_TRY(ctx, hipMemsetAsync(derr, 0xff, 8, s.stream));
+        rc = copy_unlocked(ctx, lk, s, dwire, wire->cells_be, batch * k * l * 32);
+        if (rc) return rc;
+        launch_wire_fr(s.stream, dwire, (uint32_t)(batch * k * l), sh.log_l, wire->bit_reversed, in, derr);
+    } else {
+        rc = copy_unlocked(ctx, lk, s, in, cells, batch * k * l * 32);
+    }
     if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dpos, pos, M * 4);
     if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dmiss, missing.data(), missing.size() * 4);
     if (rc) return rc;
@@ -2870,23 +2907,40 @@ static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int3
         cur = const_cast<uint32_t*>(launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw));
         launch_recover_divide(s.stream, cur, sh.log_n, sh.log_l, bc, (const uint32_t*)z + 8 * M);
         cur = const_cast<uint32_t*>(launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw + 2 * kNttTableLen));
-        launch_recover_untwist(s.stream, cur, sh.log_n, (uint32_t)n, bc, gt + 2 * kNttTableLen, inv_n, (uint32_t*)coef,
-                               out_cells != nullptr, (uint32_t*)flags);
+        launch_recover_untwist(s.stream, cur, sh.log_n, (uint32_t)n, bc, gt + 2 * kNttTableLen, inv_n,
+                               wire ? (uint32_t*)wire->d_coeffs + 8 * n * b0 : (uint32_t*)coef, want_cells, (uint32_t*)flags);
         const uint32_t* cells_dev = nullptr;
-        if (out_cells) {
+        if (want_cells) {
             const uint32_t* ev = launch_fr_dft(s.stream, cur, A, B, sh.log_n, bc, tw);
             uint32_t* dst = ev == A ? B : A;
             launch_recover_gather(s.stream, ev, dst, sh.log_n, sh.log_l, bc);
             cells_dev = dst;
+            if (wire) {  // the transform's buffer is free: the cells' bytes go there (canonical values: the second word stays unset)
+                uint32_t* enc = ev == A ? A : B;
+                launch_enc_fr(s.stream, dst, (uint32_t)(bc * N), sh.log_l, sh.log_n - sh.log_l, wire->bit_reversed, enc, derr + 1);
+                cells_dev = enc;
+            }
         }
         HIP_TRY(ctx, hipGetLastError());
         rc = rec_sync(ctx, lk, s.stream);
         if (rc) return rc;
+        uint32_t herr = 0xffffffffu;
         HIP_TRY(ctx, hipMemcpyAsync(hflags.data(), flags, bc * 4, hipMemcpyDeviceToHost, s.stream));
-        if (out_coeffs) HIP_TRY(ctx, hipMemcpyAsync(out_coeffs + 4 * n * b0, coef, bc * n * 32, hipMemcpyDeviceToHost, s.stream));
-        if (cells_dev) HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * N * b0, cells_dev, bc * N * 32, hipMemcpyDeviceToHost, s.stream));
+        if (wire) {
+            HIP_TRY(ctx, hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, s.stream));
+            if (cells_dev) HIP_TRY(ctx, hipMemcpyAsync(wire->out_cells_be + 32 * N * b0, cells_dev, bc * N * 32, hipMemcpyDeviceToHost, s.stream));
+        } else {
+            if (out_coeffs) HIP_TRY(ctx, hipMemcpyAsync(out_coeffs + 4 * n * b0, coef, bc * n * 32, hipMemcpyDeviceToHost, s.stream));
+            if (cells_dev) HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * N * b0, cells_dev, bc * N * 32, hipMemcpyDeviceToHost, s.stream));
+        }
         rc = rec_sync(ctx, lk, s.stream);
         if (rc) return rc;
+        if (herr != 0xffffffffu) {  // (the whole batch was decoded in front of the first chunk)
+            const size_t b = herr / (k * l), t = herr / l % k;
+            ctx->last_error = "recover: polynomial " + std::to_string(b) + ", cell " + std::to_string(wire->ids_sent[t]) + ": value " +
+                              std::to_string(herr % l) + " is not below r";
+            return KZG_ERR_INVALID_ARG;
+        }
         for (size_t i = 0; i < bc; i++)
             if (hflags[i]) {
                 ctx->last_error = "recover: polynomial " + std::to_string(b0 + i) + ": the received values are not those of a "
@@ -4022,6 +4076,477 @@ int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint
     if (herr != 0xffffffffu) {
         if (bad_index) *bad_index = herr;
         ctx->last_error = "fr from bytes: value " + std::to_string(herr) + " is not below r";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return KZG_OK;
+}
+
+// ---- the producing side on blobs as they travel (blob_kernels.hip) ---------------------------------------
+// Blob bytes -> values (k_wire_fr) -> coefficients (one batched inverse DFT; k_poly_trim folds in 1 / n and finds every n') ->
+// commitments (the batched MSM over the stream slots, from the resident coefficients), cells (zero-padded to N, one batched
+// DFT, one gather, k_enc_fr) and proofs (fk20_proofs from the device source, k_enc_g1).  A call holds fk20_mu, then the
+// context's mutex and one slot for its stream, dropping the mutex while it waits for the device, as fk20_host does.
+namespace {
+enum : int { kBlobWire = 0, kBlobA, kBlobB, kBlobP, kBlobWords, kBlobProofs, kBlobCoef, kBlobP1, kBlobCount };
+constexpr uint32_t kBlobErrWords = 2;  // the decoder's error word, the encoder's (never set: the device's values are canonical)
+struct Fk20Plan {  // the Toeplitz shape of polynomials of n coefficients and, when the comb tables are not kept, their stream
+    uint32_t m = 0, log_L = 0;
+    bool ready = false;
+    DevBuf stab, stmp, spre;
+};
+void blob_infinity(uint8_t* out48, size_t count) {
+    std::memset(out48, 0, 48 * count);
+    for (size_t j = 0; j < count; j++) out48[48 * j] = 0xc0;
+}
+}  // namespace
+
+static int blob_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
+    if (bytes > ctx->blob_ws_bytes[i] || !ctx->blob_ws[i]) {
+        hipFree(ctx->blob_ws[i]);
+        ctx->blob_ws[i] = nullptr;
+        ctx->blob_ws_bytes[i] = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->blob_ws[i], bytes ? bytes : 256));
+        ctx->blob_ws_bytes[i] = bytes;
+    }
+    *out = ctx->blob_ws[i];
+    return KZG_OK;
+}
+// a copy on the stream without the mutex (pageable host memory: the call may block)
+static int blob_copy(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, void* dst, const void* src, size_t bytes,
+                     hipMemcpyKind kind) {
+    if (!bytes) return KZG_OK;
+    lk.unlock();
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMemcpyAsync (blobs): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+// polynomials per pass through the workspaces: fk20_host's rule, with this path's own buffers counted in
+static size_t blob_chunk(kzg_ctx* ctx, size_t n, const CellsShape* sh, const Fk20Plan& pl) {
+    size_t per_poly = 3 * n * 32;
+    if (sh) {
+        per_poly += 3 * sh->N * 32 + sh->cells * 48;
+        if (pl.m) {
+            const size_t L = (size_t)1 << pl.log_L, M = sh->cells, X = L > M ? L : M;
+            const size_t ci = ctx->d_fk20_tab ? L : fk20_stream_positions(pl.log_L, sh->log_l);
+            per_poly += n * 32 + sh->l * L * 64 + (sh->l > 1 ? sh->l * ci * kXyzzBytes : 0) + 3 * X * kXyzzBytes + M * 336;
+        }
+    }
+    size_t chunk = kFk20WsBudget / per_poly;
+    return chunk < 1 ? 1 : (chunk > kFk20MaxBatch ? kFk20MaxBatch : chunk);
+}
+// (fk20_mu and ctx->mu held, s0 owned) the SRS side of the plan's shape, built on first need
+static int blob_fk20_ready(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s0, const CellsShape& sh, Fk20Plan& pl) {
+    if (pl.ready) return KZG_OK;
+    const uint32_t log_M = sh.log_n - sh.log_l;
+    int rc = ensure_glv(ctx, lk, pl.log_L > log_M ? pl.log_L : log_M, s0.stream);
+    if (rc == KZG_OK) rc = ensure_fk20_table(ctx, lk, s0.stream, pl.log_L, sh.log_l);
+    if (rc) return rc;
+    if (!ctx->d_fk20_tab) {
+        const size_t sb = (size_t)fk20_stream_positions(pl.log_L, sh.log_l) << sh.log_l;
+        HIP_TRY(ctx, hipMalloc(&pl.stab.p, sb * kFk20CombEntries * kAffineBytes));
+        HIP_TRY(ctx, hipMalloc(&pl.stmp.p, sb * kFk20CombEntries * kXyzzBytes));
+        HIP_TRY(ctx, hipMalloc(&pl.spre.p, sb * kFk20CombEntries * 64));
+    }
+    pl.ready = true;
+    return KZG_OK;
+}
+// (fk20_mu and ctx->mu held, s0 owned) the proofs of `bc` polynomials whose n coefficients each sit at d_coef, as bc x M x 48
+// bytes in the order asked; n_max: the largest n' among them.  Returns with the stream idle.
+static int blob_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s0, const void* d_coef, size_t n, size_t bc,
+                       const CellsShape& sh, bool bit_reversed, size_t n_max, Fk20Plan& pl, uint8_t* out48) {
+    const size_t M = sh.cells;
+    if (n_max <= sh.l) {  // every polynomial is its own interpolant on every cell
+        blob_infinity(out48, bc * M);
+        return KZG_OK;
+    }
+    int rc = blob_fk20_ready(ctx, lk, s0, sh, pl);
+    if (rc) return rc;
+    const uint32_t log_M = sh.log_n - sh.log_l;
+    void* enc = nullptr;
+    rc = blob_ws(ctx, kBlobProofs, bc * M * 48, &enc);
+    if (rc) return rc;
+    // all n coefficients, trailing zeros included: one shape for every chunk of the call, the one kzg_fk20_prepare(n) builds
+    rc = fk20_proofs(ctx, lk, s0.stream, nullptr, n, bc, n, pl.m, pl.log_L, sh.log_l, log_M, nullptr, pl.stab.p, pl.stmp.p, pl.spre.p,
+                     d_coef, true);
+    if (rc) return rc;
+    launch_enc_g1(s0.stream, ctx->fk20_ws[kWsAff], (uint32_t)(bc * M), log_M, bit_reversed, enc);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = blob_copy(ctx, lk, s0.stream, out48, enc, bc * M * 48, hipMemcpyDeviceToHost);
+    const int r2 = fk20_sync(ctx, lk, s0.stream);
+    return rc ? rc : r2;
+}
+
+// the commitments of `bc` resident polynomials (n coefficients each at d_coef, none longer than n_c): sub-batches over the
+// stream slots, as batch_host spreads them.  submit() enqueues them all (collecting its own oldest when the slots run out),
+// finish() collects the rest and compresses.
+namespace {
+struct BlobCommits {
+    kzg_ctx* ctx;
+    std::unique_lock<std::mutex>& lk;
+    std::deque<BatchInFlight> fifo;
+    std::vector<uint64_t> p1;
+    int collect_oldest() {
+        const BatchInFlight b = fifo.front();
+        fifo.pop_front();
+        await_unlocked(lk, ctx->slots[b.slot]);
+        const int r = wait_batch_locked(ctx, b.slot, p1.data() + 18 * b.first_poly, b.polys);
+        release_owned(ctx, b.slot);
+        return r;
+    }
+    int submit(const uint32_t* d_coef, size_t n, size_t bc, size_t n_c) {
+        p1.assign(18 * bc, 0);  // all zero: infinity
+        if (!n_c) return KZG_OK;
+        const size_t chunk = host_batch_chunk(ctx, bc, n_c);
+        int rc = KZG_OK;
+        for (size_t at = 0; at < bc && rc == KZG_OK; at += chunk) {
+            const size_t polys = bc - at < chunk ? bc - at : chunk;
+            int slot = reserve_slot(ctx, lk, false);
+            while (slot < 0 && rc == KZG_OK) {
+                if (!fifo.empty()) rc = collect_oldest();
+                else if ((slot = reserve_slot(ctx, lk, true)) < 0) rc = KZG_ERR_BUSY;
+                if (slot < 0 && rc == KZG_OK) slot = reserve_slot(ctx, lk, false);
+            }
+            if (rc == KZG_OK) rc = commit_batch_submit_locked(ctx, slot, d_coef + 8 * n * at, n_c, polys, n, true);
+            if (rc != KZG_OK) {
+                if (slot >= 0) release_owned(ctx, slot);
+                break;
+            }
+            fifo.push_back({slot, at, polys});
+        }
+        return rc;
+    }
+    int finish(int rc, size_t bc, uint8_t* out48) {
+        while (!fifo.empty()) {
+            const int r = collect_oldest();
+            if (rc == KZG_OK) rc = r;
+        }
+        if (rc) return rc;
+        for (size_t b = 0; b < bc; b++) {
+            hf::P1 p;
+            std::memcpy(&p, p1.data() + 18 * b, sizeof p);
+            hf::p1_compress(out48 + 48 * b, p);
+        }
+        return KZG_OK;
+    }
+};
+}  // namespace
+
+// sh: null for commitments alone
+static int blobs_device(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, uint32_t lg, size_t batch, size_t stride, const CellsShape* sh,
+                        bool bit_reversed, uint8_t* out_commitments, uint8_t* out_cells, uint8_t* out_proofs) {
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    Fk20Plan pl;
+    if (out_proofs && n > sh->l && !fk20_shape(ctx, n, sh->log_l, &pl.m, &pl.log_L)) return KZG_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot0 = reserve_slot(ctx, lk, true);
+    if (slot0 < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot0};
+    Slot& s0 = ctx->slots[slot0];
+    const hipStream_t st = s0.stream;
+    const size_t N = sh ? sh->N : n, M = sh ? sh->cells : 0;
+    size_t chunk = blob_chunk(ctx, n, sh, pl);
+    if (chunk > batch) chunk = batch;
+    void *wire, *a, *b, *pad = nullptr, *words;
+    rc = blob_ws(ctx, kBlobWire, chunk * n * 32, &wire);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, chunk * N * 32, &a);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, chunk * N * 32, &b);
+    if (rc == KZG_OK && out_cells) rc = blob_ws(ctx, kBlobP, chunk * N * 32, &pad);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    if (rc) return rc;
+    uint32_t *A = (uint32_t*)a, *B = (uint32_t*)b, *P = (uint32_t*)pad, *err = (uint32_t*)words, *trim = err + kBlobErrWords;
+    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
+    std::vector<uint32_t> hw(kBlobErrWords + chunk);
+    BlobCommits commits{ctx, lk};
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t bc = batch - b0 < chunk ? batch - b0 : chunk;
+        // the bytes as they are, decoded into this API's order, interpolated; 1 / n and every n' in one pass
+        HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kBlobErrWords * 4, st));
+        HIP_TRY(ctx, hipMemsetAsync(trim, 0, bc * 4, st));
+        {
+            lk.unlock();
+            const uint8_t* src = blobs_be + 32 * b0 * stride;
+            const hipError_t e = stride > n && bc > 1
+                                     ? hipMemcpy2DAsync(wire, n * 32, src, stride * 32, n * 32, bc, hipMemcpyHostToDevice, st)
+                                     : hipMemcpyAsync(wire, src, bc * n * 32, hipMemcpyHostToDevice, st);
+            lk.lock();
+            if (e != hipSuccess) {
+                ctx->last_error = std::string("hipMemcpyAsync (blobs): ") + hipGetErrorString(e);
+                return KZG_ERR_HIP;
+            }
+        }
+        launch_wire_fr(st, wire, (uint32_t)(bc * n), lg, bit_reversed, A, err);
+        uint32_t* coef = const_cast<uint32_t*>(launch_fr_dft(st, A, A, B, lg, bc, tw + 2 * kNttTableLen));
+        uint32_t* other = coef == A ? B : A;
+        launch_poly_trim(st, coef, (uint32_t)n, n, (uint32_t)bc, &inv_n, trim);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(hw.data(), words, (kBlobErrWords + bc) * 4, hipMemcpyDeviceToHost, st));
+        rc = fk20_sync(ctx, lk, st);
+        if (rc) return rc;
+        if (hw[0] != 0xffffffffu) {
+            ctx->last_error = "blobs: polynomial " + std::to_string(b0 + hw[0] / n) + ": value " + std::to_string(hw[0] % n) +
+                              " is not below r";
+            return KZG_ERR_INVALID_ARG;
+        }
+        size_t n_max = 0;
+        for (size_t i = 0; i < bc; i++) {
+            const size_t ne = hw[kBlobErrWords + i];
+            if (out_commitments && ne > ctx->n) {
+                ctx->last_error = "blobs: polynomial " + std::to_string(b0 + i) + ": n' = " + std::to_string(ne) +
+                                  " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+                return KZG_ERR_DEGREE_TOO_HIGH;
+            }
+            if (out_proofs && ne > sh->l && ne - sh->l > ctx->n) {
+                ctx->last_error = "blobs: polynomial " + std::to_string(b0 + i) + ": n' - l = " + std::to_string(ne - sh->l) +
+                                  " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+                return KZG_ERR_DEGREE_TOO_HIGH;
+            }
+            if (ne > n_max) n_max = ne;
+        }
+        // the stream is idle and the coefficients are resident: the MSMs run on the other slots beside what follows here
+        if (out_commitments) rc = commits.submit(coef, n, bc, n_max);
+        // (a lambda: a HIP error in here must still reach commits.finish, which collects the sub-batches in flight)
+        auto cells = [&]() -> int {
+            if (n < N) HIP_TRY(ctx, hipMemsetAsync(P, 0, bc * N * 32, st));
+            HIP_TRY(ctx, hipMemcpy2DAsync(P, N * 32, coef, n * 32, n * 32, bc, hipMemcpyDeviceToDevice, st));
+            const uint32_t* ev = launch_fr_dft(st, P, P, other, sh->log_n, bc, tw);
+            uint32_t* dst = ev == P ? other : P;
+            launch_recover_gather(st, ev, dst, sh->log_n, sh->log_l, bc);
+            uint32_t* enc = ev == P ? P : other;  // the transform's buffer is free again
+            launch_enc_fr(st, dst, (uint32_t)(bc * N), sh->log_l, sh->log_n - sh->log_l, bit_reversed, enc, err + 1);
+            HIP_TRY(ctx, hipGetLastError());
+            return blob_copy(ctx, lk, st, out_cells + 32 * N * b0, enc, bc * N * 32, hipMemcpyDeviceToHost);
+        };
+        if (rc == KZG_OK && out_cells) rc = cells();
+        if (rc == KZG_OK && out_proofs) rc = blob_proofs(ctx, lk, s0, coef, n, bc, *sh, bit_reversed, n_max, pl, out_proofs + 48 * M * b0);
+        const int r2 = fk20_sync(ctx, lk, st);
+        if (rc == KZG_OK) rc = r2;
+        if (out_commitments) rc = commits.finish(rc, bc, out_commitments + 48 * b0);
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+
+static int blobs_entry(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, bool cells_call,
+                       unsigned log_domain, unsigned log_cell, unsigned order, uint8_t* out_commitments, uint8_t* out_cells,
+                       uint8_t* out_proofs) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "blobs: " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    uint32_t lg = 0;
+    CellsShape sh;
+    if (!ntt_log(n, &lg)) return invalid("n is not a power of two up to 2^KZG_NTT_MAX_LOG");
+    if (cells_call && !cells_shape(n, log_domain, log_cell, &sh)) return invalid("unsupported shape (log_domain, log_cell) or n > N");
+    if (batch > kMaxCoefficients / (cells_call ? sh.N : n)) return invalid("batch x N does not fit 32 bits");
+    if (order != KZG_ORDER_NATURAL && order != KZG_ORDER_BIT_REVERSED)
+        return invalid("order is neither KZG_ORDER_NATURAL nor KZG_ORDER_BIT_REVERSED");
+    if (batch && (!blobs_be || (cells_call ? !out_proofs : !out_commitments))) return invalid("a required pointer is NULL");
+    if (batch > 1 && stride < n) return invalid("stride is below n");
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, blobs_entry(kid, blobs_be, n, batch, stride, cells_call, log_domain, log_cell, order,
+                                                     out_commitments, out_cells, out_proofs))
+                   : rc;
+    }
+    if (!batch) return KZG_OK;
+    return blobs_device(ctx, blobs_be, n, lg, batch, batch > 1 ? stride : n, cells_call ? &sh : nullptr,
+                        order == KZG_ORDER_BIT_REVERSED, out_commitments, out_cells, out_proofs);
+}
+
+int kzg_blobs_to_commitments_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                   uint8_t* out_commitments48) {
+    return blobs_entry(ctx, blobs_be, n, batch, stride, false, 0, 0, order, out_commitments48, nullptr, nullptr);
+}
+
+int kzg_blobs_to_cells_and_proofs_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride,
+                                        unsigned log_domain, unsigned log_cell, unsigned order, uint8_t* out_commitments48,
+                                        uint8_t* out_cells_be, uint8_t* out_proofs48) {
+    return blobs_entry(ctx, blobs_be, n, batch, stride, true, log_domain, log_cell, order, out_commitments48, out_cells_be,
+                       out_proofs48);
+}
+
+// recovery: the received cells decoded on the device in front of recover_host's kernels, the coefficients of the whole batch
+// kept in device memory for FK20 (fk20_mu held throughout: the buffer is a workspace of this path)
+int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_domain, unsigned log_cell, unsigned order,
+                                       const uint32_t* cell_ids, size_t k, const uint8_t* cells_be, size_t batch, uint8_t* out_cells_be,
+                                       uint8_t* out_proofs48) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "recover: " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    CellsShape sh;
+    if (!cells_shape(n, log_domain, log_cell, &sh)) return invalid("unsupported shape (log_domain, log_cell) or n > N");
+    if (log_domain - log_cell > KZG_RECOVER_MAX_LOG_CELLS) return invalid("more than 2^KZG_RECOVER_MAX_LOG_CELLS cells");
+    if (n == 0) return invalid("n = 0");
+    if (k > sh.cells || k * sh.l < n) return invalid("k l must be at least n, with at most N / l cells");
+    if (order != KZG_ORDER_NATURAL && order != KZG_ORDER_BIT_REVERSED)
+        return invalid("order is neither KZG_ORDER_NATURAL nor KZG_ORDER_BIT_REVERSED");
+    if (!cell_ids || (!cells_be && batch)) return invalid("a required pointer is NULL");
+    if (batch > kMaxCoefficients / sh.N) return invalid("batch x N does not fit 32 bits");
+    const bool bit_reversed = order == KZG_ORDER_BIT_REVERSED;
+    std::vector<int32_t> pos(sh.cells, -1);
+    for (size_t t = 0; t < k; t++) {
+        if (cell_ids[t] >= sh.cells) return invalid("cell id " + std::to_string(cell_ids[t]) + " is not below N / l");
+        // the sampling specs' cell c is this API's cell brp(c) over the N / l cells
+        const uint32_t j = bit_reversed ? wire_brp(cell_ids[t], sh.log_n - sh.log_l) : cell_ids[t];
+        if (pos[j] >= 0) return invalid("cell id " + std::to_string(cell_ids[t]) + " appears twice");
+        pos[j] = (int32_t)t;
+    }
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_recover_cells_and_proofs_bytes(kid, n, log_domain, log_cell, order, cell_ids, k, cells_be,
+                                                                            batch, out_cells_be, out_proofs48))
+                   : rc;
+    }
+    if (!batch) return KZG_OK;
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    Fk20Plan pl;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (out_proofs48 && (!ctx->n || !ctx->slots_ready)) return KZG_ERR_NO_SRS;
+        if (out_proofs48 && n > sh.l && !fk20_shape(ctx, n, sh.log_l, &pl.m, &pl.log_L)) return KZG_ERR_INVALID_ARG;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+    }
+    std::vector<uint32_t> missing;
+    for (size_t j = 0; j < sh.cells; j++)
+        if (pos[j] < 0) missing.push_back((uint32_t)j);
+    RecWire w;
+    w.cells_be = cells_be;
+    w.bit_reversed = bit_reversed;
+    w.ids_sent = cell_ids;
+    w.out_cells_be = out_cells_be;
+    int rc = blob_ws(ctx, kBlobCoef, batch * n * 32, &w.d_coeffs);  // (fk20_mu guards the workspaces)
+    if (rc) return rc;
+    rc = recover_host(ctx, sh, n, pos.data(), missing, k, nullptr, batch, nullptr, nullptr, &w);
+    if (rc || !out_proofs48) return rc;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the SRS may have gone meanwhile)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot0 = reserve_slot(ctx, lk, true);
+    if (slot0 < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot0};
+    Slot& s0 = ctx->slots[slot0];
+    void* words = nullptr;
+    rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    if (rc) return rc;
+    uint32_t* trim = (uint32_t*)words + kBlobErrWords;
+    size_t chunk = blob_chunk(ctx, n, &sh, pl);
+    if (chunk > batch) chunk = batch;
+    std::vector<uint32_t> ht(chunk);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t bc = batch - b0 < chunk ? batch - b0 : chunk;
+        void* coef = (char*)w.d_coeffs + 32 * n * b0;
+        HIP_TRY(ctx, hipMemsetAsync(trim, 0, bc * 4, s0.stream));
+        launch_poly_trim(s0.stream, coef, (uint32_t)n, n, (uint32_t)bc, nullptr, trim);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ht.data(), trim, bc * 4, hipMemcpyDeviceToHost, s0.stream));
+        rc = fk20_sync(ctx, lk, s0.stream);
+        if (rc) return rc;
+        size_t n_max = 0;
+        for (size_t i = 0; i < bc; i++) {
+            if (ht[i] > sh.l && ht[i] - sh.l > ctx->n) {
+                ctx->last_error = "recover: polynomial " + std::to_string(b0 + i) + ": n' - l = " + std::to_string(ht[i] - sh.l) +
+                                  " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+                return KZG_ERR_DEGREE_TOO_HIGH;
+            }
+            if (ht[i] > n_max) n_max = ht[i];
+        }
+        rc = blob_proofs(ctx, lk, s0, coef, n, bc, sh, bit_reversed, n_max, pl, out_proofs48 + 48 * sh.cells * b0);
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+
+// the encoders on their own: building blocks and test hooks; they need no SRS
+int kzg_g1_compress_batch(kzg_ctx* ctx, const uint64_t* in_p1, size_t n, uint8_t* out48) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (n > kMaxCoefficients - 1 || (n && (!in_p1 || !out48))) {
+        ctx->last_error = "g1 compress: a required pointer is NULL or n does not fit 32 bits";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!n) return KZG_OK;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_g1_compress_batch(kid, in_p1, n, out48));
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    void *jac = nullptr, *aff = nullptr, *prefix = nullptr, *enc = nullptr;
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobP1, n * 144, &jac);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, n * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, n * 64, &prefix);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobProofs, n * 48, &enc);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    rc = blob_copy(ctx, lk, st, jac, in_p1, n * 144, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    launch_jacobian_to_affine(st, jac, (uint32_t)n, aff, prefix);
+    launch_enc_g1(st, aff, (uint32_t)n, 0, false, enc);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = blob_copy(ctx, lk, st, out48, enc, n * 48, hipMemcpyDeviceToHost);
+    const int r2 = fk20_sync(ctx, lk, st);
+    return rc ? rc : r2;
+}
+
+int kzg_fr_to_bytes_batch(kzg_ctx* ctx, const uint64_t* in_fr_mont, size_t n, uint8_t* out32_be, size_t* bad_index) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (n > kMaxCoefficients - 1 || (n && (!in_fr_mont || !out32_be))) {
+        ctx->last_error = "fr to bytes: a required pointer is NULL or n does not fit 32 bits";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (!n) return KZG_OK;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_fr_to_bytes_batch(kid, in_fr_mont, n, out32_be, bad_index));
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    void *vals = nullptr, *enc = nullptr, *words = nullptr;
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, n * 32, &vals);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, n * 32, &enc);
+    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    uint32_t* err = (uint32_t*)words;
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kBlobErrWords * 4, st));
+    rc = blob_copy(ctx, lk, st, vals, in_fr_mont, n * 32, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    launch_enc_fr(st, vals, (uint32_t)n, 0, 0, false, enc, err);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t herr = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+    rc = blob_copy(ctx, lk, st, out32_be, enc, n * 32, hipMemcpyDeviceToHost);
+    const int r2 = fk20_sync(ctx, lk, st);
+    if (rc || r2) return rc ? rc : r2;
+    if (herr != 0xffffffffu) {
+        if (bad_index) *bad_index = herr;
+        ctx->last_error = "fr to bytes: value " + std::to_string(herr) + " is not below r";
         return KZG_ERR_INVALID_ARG;
     }
     return KZG_OK;

@@ -152,6 +152,20 @@ void launch_wire_g1(hipStream_t s, const void* d_in48, const uint32_t* d_src, ui
 // position brp_(log_row)(i) of its row (n a multiple of the row length); *d_err: the least input index not below r
 void launch_wire_fr(hipStream_t s, const void* d_in32, uint32_t n, uint32_t log_row, bool bit_reversed, void* d_out, uint32_t* d_err);
 
+// ---- blob_kernels.hip: outputs encoded into their wire bytes (wire_enc30.hip.h; 16-byte aligned arrays) -----------------
+// n affine table records -> 48-byte compressed points; bit_reversed: record j of every row of 2^log_row records goes to
+// slot brp_(log_row)(j) of its row (n a multiple of the row length)
+void launch_enc_g1(hipStream_t s, const void* d_affine, uint32_t n, uint32_t log_row, bool bit_reversed, void* d_out48);
+// n blst_fr images -> 32 big-endian bytes each; bit_reversed: value i of cell j (cells of 2^log_row values, 2^log_cells cells
+// per polynomial) goes to position brp(i) of cell brp(j) of its polynomial; *d_err (pre-set to 0xffffffff) receives the least
+// source index whose image is not below r
+void launch_enc_fr(hipStream_t s, const void* d_in, uint32_t n, uint32_t log_row, uint32_t log_cells, bool bit_reversed, void* d_out32,
+                   uint32_t* d_err);
+// d_out[b] (pre-set to 0) = 1 + the index of the highest non-zero coefficient of polynomial b (n coefficients at d_coeffs +
+// 32 b stride bytes), 0 for the zero polynomial; scale: every coefficient is multiplied by it in place first (multiplier form)
+struct Fr30;
+void launch_poly_trim(hipStream_t s, void* d_coeffs, uint32_t n, uint64_t stride, uint32_t batch, const Fr30* scale, uint32_t* d_out);
+
 // ---- msm_accum.hip (table format) ---------------------------------------------------------
 // native table entries -> blst_p1 (Z = Montgomery one / all zero for infinity)
 void launch_affine_to_p1(hipStream_t s, const void* d_affine, uint32_t n, void* d_p1_out);

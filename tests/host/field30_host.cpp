@@ -7,6 +7,7 @@
 #include "../../kzg_poly_commit_exploration_amd/csrc/field30_inv.hip.h"
 #include "../../kzg_poly_commit_exploration_amd/csrc/g1_30.hip.h"
 #include "../../kzg_poly_commit_exploration_amd/csrc/host_field.hpp"
+#include "../device/prim_ops.h"
 
 using namespace kzg;
 
@@ -238,5 +239,22 @@ void hf_px_sum(const int32_t* rec_a, const int32_t* rec_b, uint64_t* out_add, ui
     kzg_host::PX s = kzg_host::px_add(a, b), t = kzg_host::px_add(kzg_host::px_add(s, s), s);
     t = kzg_host::px_add(t, kzg_host::px_add(a, kzg_host::px_double(b)));
     put_p1(kzg_host::px_normalize(t), out_wsum3);
+}
+
+// ---- the record form of tests/prim_cases.py (tests/device/prim_ops.h): the same bodies as the device harness runs, in a
+// loop.  Same signature as the harness's launchers; returns 0, or -1 for a wrong record size.
+#define PRIM_HOST_LOOP(NAME, IW, OW)                                                        \
+    int prim_##NAME(const int32_t* in, int iw, int32_t* out, int ow, int n) {               \
+        if (iw != (IW) || ow != (OW) || n <= 0) return -1;                                  \
+        for (int i = 0; i < n; i++) prim::pop_##NAME(in + (size_t)i * (IW), out + (size_t)i * (OW)); \
+        return 0;                                                                           \
+    }
+PRIM_FQ_OPS(PRIM_HOST_LOOP)
+int prim_pair_batch(const int32_t* in, int iw, const int32_t* off, int nb, int32_t* out, int ow, int n) {
+    if (iw != 54 || ow != 27 || n <= 0 || nb <= 0 || off[0] != 0 || off[nb] != n) return -1;
+    int32_t* prefix = new int32_t[(size_t)n * 13];
+    for (int b = 0; b < nb; b++) prim::pop_pair_batch(in, off[b], off[b + 1], out, prefix);
+    delete[] prefix;
+    return 0;
 }
 }

@@ -6,6 +6,7 @@
 #include "../../kzg_poly_commit_exploration_amd/csrc/fr30.hip.h"
 #include "../../kzg_poly_commit_exploration_amd/csrc/host_fr.hpp"
 #include "../../kzg_poly_commit_exploration_amd/csrc/fr30_host.hpp"
+#include "../device/prim_ops.h"
 
 using namespace kzg;
 
@@ -66,4 +67,14 @@ int64_t r30_mul_max_column(const int32_t* a, const int32_t* b) {
     }
     return (int64_t)(worst >> 48);
 }
+
+// ---- the record form of tests/prim_cases.py (tests/device/prim_ops.h): the same bodies as the device harness runs, in a
+// loop.  Same signature as the harness's launchers; returns 0, or -1 for a wrong record size.
+#define PRIM_HOST_LOOP(NAME, IW, OW)                                                        \
+    int prim_##NAME(const int32_t* in, int iw, int32_t* out, int ow, int n) {               \
+        if (iw != (IW) || ow != (OW) || n <= 0) return -1;                                  \
+        for (int i = 0; i < n; i++) prim::pop_##NAME(in + (size_t)i * (IW), out + (size_t)i * (OW)); \
+        return 0;                                                                           \
+    }
+PRIM_FR_OPS(PRIM_HOST_LOOP)
 }

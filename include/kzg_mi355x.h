@@ -600,6 +600,62 @@ int kzg_verify_proof(const uint64_t commitment_p1[18], const uint64_t proof_p1[1
 int kzg_verify_proof_batch(const uint64_t* commitments_p1, const uint64_t* proofs_p1, const uint64_t* zs,
                            const uint64_t* ys, const uint64_t s_g2_p2[36], size_t n, int* valid);
 
+/* ---- powers-of-tau ceremonies: contribute to the resident SRS, verify a setup ---------- */
+
+/* One participant's contribution: SRS[i] <- [tau^(first + i) mod r] SRS[i] for every resident point i, on the device (one
+ * variable-base scalar multiplication per point; the powers are derived and split for the endomorphism there, nothing goes
+ * through the host).  tau is read as kzg_srs_generate_g1 reads its secret: 32 bytes big-endian, reduced mod r; `first` has
+ * the meaning it has there (the exponent of the first resident point, for a caller that holds a slice; a whole setup passes
+ * 0).  Points at infinity stay at infinity.  Afterwards the window tables are rebuilt and every cache derived from the SRS
+ * (FK20 transforms and comb tables, the slots' workspaces) is rebuilt or dropped as a load does it.
+ *   KZG_ERR_INVALID_ARG  tau = 0 mod r (a zero contribution destroys the setup): the SRS is untouched
+ *   KZG_ERR_NO_SRS       the context holds no SRS
+ * The new points are produced in temporaries and copied in only after the kernels have succeeded: after a failed call the
+ * context holds either the old SRS or none (kzg_srs_len = 0), never a half-updated one.  The host's copies of tau and of its
+ * reduced form are wiped before the call returns; the kernel-argument copy has the lifetime of kzg_srs_generate_g1's secret
+ * (it sits in the runtime's launch buffers until they are reused).  Waits for synchronous calls in flight and takes the
+ * context's lock like kzg_srs_generate_g1.  A replicated multi-device context updates every device in turn (a device
+ * failure in the middle leaves the devices apart: reload); a range-split one returns KZG_ERR_INVALID_ARG. */
+int kzg_srs_update(kzg_ctx* ctx, const uint8_t tau_be[32], uint64_t first);
+
+/* Is the resident SRS a setup, [s^i]G1 for one s, that matches the verifiers' [s]G2?  Every verifier of this library is
+ * sound only then, and the loaders do not check it.  setup_g2 is read at indices 0 and 1 as the other verifiers read it
+ * (blst_p2, g2_stride_bytes apart): [1]G2 and [s]G2.  *valid = 1 and *reason = KZG_SRS_OK, or *valid = 0 and *reason = the
+ * first failure in this order (*bad_index, when given, the point it names, else (size_t)-1):
+ *   KZG_SRS_G2_BAD               setup_g2[0] is not the G2 generator, or setup_g2[1] is infinity or outside the subgroup of
+ *                                order r (host)
+ *   KZG_SRS_INFINITY             SRS[bad_index] is the point at infinity, bad_index the least such (a setup of secret 0 is
+ *                                not a setup)
+ *   KZG_SRS_NOT_IN_G1            SRS[bad_index] is off the curve or outside the subgroup of order r, bad_index the least such.
+ *                                The pairing of the last step cannot see this: a component of cofactor order pairs to 1
+ *   KZG_SRS_FIRST_NOT_GENERATOR  only with KZG_SRS_FIRST_IS_GENERATOR in flags: SRS[0] is not [1]G1 (a slice of a setup
+ *                                passes without the flag)
+ *   KZG_SRS_NOT_POWERS           with rho_i uniform 128-bit from the OS CSPRNG, fresh on every call:
+ *                                e(sum_{i<n-1} rho_i SRS[i+1], [1]G2) != e(sum_{i<n-1} rho_i SRS[i], [s]G2); two MSMs over the
+ *                                resident tables and one two-pair check on the host.  A bad setup passes with probability
+ *                                <= 2^-128; with one point there is nothing to compare
+ * KZG_ERR_INVALID_ARG when a G2 point is off the twist (as the other verifiers answer it), KZG_ERR_NO_SRS without an SRS.  A
+ * replicated multi-device context verifies its first device's copy; a range-split one returns KZG_ERR_INVALID_ARG. */
+#define KZG_SRS_FIRST_IS_GENERATOR 1u
+enum { KZG_SRS_OK = 0, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS };
+int kzg_srs_verify(kzg_ctx* ctx, const void* setup_g2, size_t g2_stride_bytes, unsigned flags, int* valid, unsigned* reason,
+                   size_t* bad_index /* may be NULL */);
+/* Test hook: the last step alone with the caller's weights (n - 1 blst_fr, each below r; n = kzg_srs_len): A = sum_{i<n-1}
+ * rho_i SRS[i] and B = sum_{i<n-1} rho_i SRS[i+1] as normalised blst_p1, *valid = the pairing check.  No subgroup, infinity
+ * or generator check runs.  n = 1: A = B = infinity, valid. */
+int kzg_srs_verify_lincomb(kzg_ctx* ctx, const uint64_t* weights, const void* setup_g2, size_t g2_stride_bytes,
+                           uint64_t out_a_p1[18], uint64_t out_b_p1[18], int* valid);
+
+/* Host only, no context.  [k]Q for a blst_p2 on the twist (else KZG_ERR_INVALID_ARG), k read big-endian and reduced mod r,
+ * normalised like kzg_srs_g2_at's output: a contributor makes [tau]G2 and the new [s tau]G2 with it.  The host's copies of
+ * the scalar are wiped before the call returns. */
+int kzg_g2_mul(const uint64_t in_p2[36], const uint8_t scalar_be[32], uint64_t out_p2[36]);
+/* Host only, no context.  One link of a ceremony transcript: e(after, [1]G2) == e(before, tau_g2), where before and after
+ * are SRS[1] around a contribution and tau_g2 = [tau]G2.  *valid = 0 also when before or after is infinity or off the curve,
+ * or tau_g2 is infinity or outside the subgroup of order r; KZG_ERR_INVALID_ARG when tau_g2 is off the twist (as
+ * kzg_verify_proof answers it). */
+int kzg_srs_verify_update(const uint64_t before_p1[18], const uint64_t after_p1[18], const uint64_t tau_g2[36], int* valid);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 
 typedef struct kzg_kernel_times {

@@ -59,7 +59,10 @@ ABI_SYMBOLS = [
     "kzg_verify_openings_lincomb_bytes", "kzg_verify_blobs_batch_bytes", "kzg_g1_uncompress_batch", "kzg_fr_from_bytes_batch",
     "kzg_blobs_to_commitments_bytes", "kzg_blobs_to_cells_and_proofs_bytes", "kzg_recover_cells_and_proofs_bytes",
     "kzg_g1_compress_batch", "kzg_fr_to_bytes_batch",
+    "kzg_srs_update", "kzg_srs_verify", "kzg_srs_verify_lincomb", "kzg_g2_mul", "kzg_srs_verify_update",
 ]
+KZG_SRS_FIRST_IS_GENERATOR = 1
+KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
 KZG_ORDER_NATURAL = 0
 KZG_ORDER_BIT_REVERSED = 1
 KZG_MAX_OPEN_POINTS = 64
@@ -186,6 +189,11 @@ def load_library():
         "kzg_recover_cells_and_proofs_bytes": (i, [vp, sz, C.c_uint, C.c_uint, C.c_uint, vp, sz, vp, sz, vp, vp]),
         "kzg_g1_compress_batch": (i, [vp, vp, sz, vp]),
         "kzg_fr_to_bytes_batch": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_srs_update": (i, [vp, u8p, C.c_uint64]),
+        "kzg_srs_verify": (i, [vp, vp, sz, C.c_uint, C.POINTER(i), C.POINTER(C.c_uint), C.POINTER(sz)]),
+        "kzg_srs_verify_lincomb": (i, [vp, vp, vp, sz, vp, vp, C.POINTER(i)]),
+        "kzg_g2_mul": (i, [vp, u8p, vp]),
+        "kzg_srs_verify_update": (i, [vp, vp, vp, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -425,6 +433,44 @@ class Engine:
 
     def srs_len(self):
         return int(self._lib.kzg_srs_len(self._h))
+
+    # -- powers-of-tau ceremonies --
+    def _error(self, rc):
+        return KzgError(rc, self._lib.kzg_strerror(rc).decode() + ": " + self._lib.kzg_last_error(self._h).decode())
+
+    def srs_update(self, tau_be, first=0):
+        """kzg_srs_update: SRS[i] <- [tau^(first + i)] SRS[i] on the device; tau: 32 bytes big-endian, reduced mod r.
+        Raises KzgError(KZG_ERR_INVALID_ARG) for tau = 0 mod r and leaves the SRS as it was"""
+        assert len(tau_be) == 32
+        rc = self._lib.kzg_srs_update(self._h, bytes(tau_be), int(first))
+        if rc != KZG_OK:
+            raise self._error(rc)
+
+    def srs_verify(self, setup_g2, require_generator=True):
+        """kzg_srs_verify: is the resident SRS [s^i]G1 for the s of setup_g2 = ([1]G2, [s]G2) (blst_p2 rows)?  Returns
+        (valid, reason, bad_index): reason one of the KZG_SRS_* codes, bad_index the point it names or None"""
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert g2.shape[0] >= 2
+        ok, reason, bad = C.c_int(0), C.c_uint(0), C.c_size_t(0)
+        rc = self._lib.kzg_srs_verify(self._h, _ptr(g2), 288, KZG_SRS_FIRST_IS_GENERATOR if require_generator else 0,
+                                      C.byref(ok), C.byref(reason), C.byref(bad))
+        if rc != KZG_OK:
+            raise self._error(rc)
+        return bool(ok.value), int(reason.value), (None if bad.value == C.c_size_t(-1).value else int(bad.value))
+
+    def srs_verify_lincomb(self, weights, setup_g2):
+        """the test hook kzg_srs_verify_lincomb: weights: srs_len() - 1 Scalars (or blst_fr rows).  Returns (A, B, valid):
+        A = sum rho_i SRS[i], B = sum rho_i SRS[i + 1] as G1Points and the pairing's answer"""
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        w = (np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4) if isinstance(weights, np.ndarray)
+             else _scalar_rows(weights))
+        a = np.zeros(18, dtype=np.uint64)
+        b = np.zeros(18, dtype=np.uint64)
+        ok = C.c_int(0)
+        rc = self._lib.kzg_srs_verify_lincomb(self._h, _ptr(w), _ptr(g2), 288, _ptr(a), _ptr(b), C.byref(ok))
+        if rc != KZG_OK:
+            raise self._error(rc)
+        return G1Point(a), G1Point(b), bool(ok.value)
 
     def msm_config(self):
         c, w, nb, rec = C.c_int(), C.c_int(), C.c_size_t(), C.c_int()
@@ -1072,6 +1118,24 @@ def srs_g2_at(secret_be, index=1):
     out = np.zeros(36, dtype=np.uint64)
     _check(lib.kzg_srs_g2_at(bytes(secret_be), int(index), _ptr(out)))
     return out
+
+
+def g2_mul(p2, scalar_be):
+    """kzg_g2_mul: [k]Q on the host for a blst_p2 (36 x uint64) and 32 big-endian bytes (reduced mod r), normalised"""
+    assert len(scalar_be) == 32
+    q = np.ascontiguousarray(p2, dtype=np.uint64).reshape(36)
+    out = np.zeros(36, dtype=np.uint64)
+    _check(load_library().kzg_g2_mul(_ptr(q), bytes(scalar_be), _ptr(out)))
+    return out
+
+
+def verify_srs_update(before, after, tau_g2):
+    """kzg_srs_verify_update: e(after, [1]G2) == e(before, tau_g2) -- one link of a ceremony transcript; before, after:
+    G1Points (SRS[1] around a contribution), tau_g2 = [tau]G2 as a blst_p2"""
+    q = np.ascontiguousarray(tau_g2, dtype=np.uint64).reshape(36)
+    ok = C.c_int(0)
+    _check(load_library().kzg_srs_verify_update(_ptr(before.p1), _ptr(after.p1), _ptr(q), C.byref(ok)))
+    return bool(ok.value)
 
 
 def verify_proof(commitment, proof, z, y, s_g2):

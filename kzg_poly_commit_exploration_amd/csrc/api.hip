@@ -4685,6 +4685,364 @@ int kzg_srs_g2_at(const uint8_t secret_be[32], uint64_t index, uint64_t out_p2[3
     return KZG_OK;
 }
 
+// ---- powers-of-tau ceremonies: contribute to the resident SRS, verify it ------------------------
+
+namespace {
+// secrets leave the host's memory before the call returns (a plain memset of a dying object may be dropped)
+void wipe(void* p, size_t bytes) {
+    volatile uint8_t* q = (volatile uint8_t*)p;
+    while (bytes--) *q++ = 0;
+}
+struct WipeGuard {
+    void* p;
+    size_t bytes;
+    ~WipeGuard() { wipe(p, bytes); }
+};
+// KZG_SRS_TRACE=1: the two calls print where their wall time went (one line on stderr each; tests/perf_srs_ceremony.py).
+// A traced update waits for the device after every phase.
+struct SrsTrace {
+    bool on;
+    std::chrono::steady_clock::time_point t;
+    std::string line;
+    explicit SrsTrace(const char* what) {
+        const char* v = std::getenv("KZG_SRS_TRACE");
+        on = v && v[0] == '1';
+        if (on) {
+            line = what;
+            t = std::chrono::steady_clock::now();
+        }
+    }
+    void mark(const char* phase) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        char buf[96];
+        std::snprintf(buf, sizeof buf, " %s_ms=%.3f", phase, std::chrono::duration<double, std::milli>(now - t).count());
+        line += buf;
+        t = now;
+    }
+    ~SrsTrace() { if (on) std::fprintf(stderr, "%s\n", line.c_str()); }
+};
+// 32 big-endian bytes -> the 256-bit integer as little-endian words (reference src/trusted_setup.rs:24)
+void be32_to_raw8(const uint8_t be[32], uint32_t raw[8]) {
+    for (int w = 0; w < 8; w++) {
+        const uint8_t* b = be + 28 - 4 * w;
+        raw[w] = ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | (uint32_t)b[3];
+    }
+}
+// ... reduced mod r (2^256 < 3 r)
+hf::Fr raw8_mod_r(const uint32_t raw[8]) {
+    hf::Fr s;
+    for (int w = 0; w < 4; w++) s.l[w] = raw[2 * w] | ((uint64_t)raw[2 * w + 1] << 32);
+    uint64_t br = 0;
+    while (hf::fr_geq(s, hf::kFrMod)) s = hf::fr_raw_sub(s, hf::kFrMod, br);
+    return s;
+}
+bool g2_in_subgroup(const uint64_t raw_p2[36]) {  // [r] Q == infinity
+    hf::P2 q;
+    std::memcpy(&q, raw_p2, sizeof q);
+    return hf::p2_mul(q, hf::kFrMod.l).is_inf();
+}
+}  // namespace
+
+static int multi_replicated_only(kzg_ctx* ctx, const char* what) {
+    if (multi_mode(ctx->multi) != kMultiReplicate) {
+        ctx->last_error = std::string(what) + ": range-split multi-device contexts are not supported (use KZG_MULTI_REPLICATE_SRS)";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return multi_srs_len(ctx->multi) ? KZG_OK : KZG_ERR_NO_SRS;
+}
+
+int kzg_srs_update(kzg_ctx* ctx, const uint8_t tau_be[32], uint64_t first) {
+    if (!ctx || !tau_be) return KZG_ERR_INVALID_ARG;
+    uint32_t raw[8];
+    WipeGuard wipe_raw{raw, sizeof raw};
+    be32_to_raw8(tau_be, raw);
+    bool zero;
+    {
+        hf::Fr t = raw8_mod_r(raw);
+        zero = t.is_zero();
+        wipe(&t, sizeof t);
+    }
+    if (ctx->multi) {  // a replicated SRS: every device in turn
+        std::lock_guard<std::mutex> lkm(ctx->mu);
+        ctx->last_error.clear();
+        int rc = multi_replicated_only(ctx, "kzg_srs_update");
+        if (rc) return rc;
+        if (zero) {
+            ctx->last_error = "kzg_srs_update: tau is zero mod r";
+            return KZG_ERR_INVALID_ARG;
+        }
+        for (int g = 0; g < multi_num_devices(ctx->multi) && rc == KZG_OK; g++) {
+            kzg_ctx* kid = multi_kid(ctx->multi, g);
+            rc = forwarded(ctx, kid, kzg_srs_update(kid, tau_be, first));
+        }
+        return rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    quiesce(ctx, lk);
+    if (!ctx->n) return KZG_ERR_NO_SRS;
+    if (zero) {  // a zero contribution destroys the setup
+        ctx->last_error = "kzg_srs_update: tau is zero mod r";
+        return KZG_ERR_INVALID_ARG;
+    }
+    SrsTrace tr("kzg_srs_update:");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = drain_all(ctx);
+    if (rc) return rc;
+    const size_t n = ctx->n;
+    // the new level 0 in temporaries: the context keeps the old SRS until the kernels have succeeded
+    DevBuf d_new, d_prefix, d_xyzz;
+    HIP_TRY(ctx, hipMalloc(&d_new.p, n * kAffineBytes));
+    HIP_TRY(ctx, hipMalloc(&d_prefix.p, n * 64));
+    HIP_TRY(ctx, hipMalloc(&d_xyzz.p, n * kXyzzBytes));
+    TmpStream st;
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    tr.mark("alloc");
+    launch_srs_update(st.s, raw, first, (uint32_t)n, ctx->d_table, d_xyzz.p);
+    if (tr.on) HIP_TRY(ctx, hipStreamSynchronize(st.s));
+    tr.mark("ladder");
+    launch_xyzz_to_affine(st.s, d_xyzz.p, (uint32_t)n, d_new.p, d_prefix.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st.s));
+    tr.mark("normalise");
+    // from here on a failure leaves the context without an SRS: everything derived from the old one goes, as in srs_prepare
+    ctx->slots_ready = false;
+    for (auto& s : ctx->slots) s.kind = SLOT_IDLE;
+    if (ctx->d_fk20_B) {  // the FK20 cache holds transforms of the old SRS
+        hipFree(ctx->d_fk20_B);
+        hipFree(ctx->d_fk20_tab);
+        ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
+    }
+    rc = hipMemcpyAsync(ctx->d_table, d_new.p, n * kAffineBytes, hipMemcpyDeviceToDevice, st.s) == hipSuccess ? KZG_OK : KZG_ERR_HIP;
+    if (rc == KZG_OK) rc = build_tables(ctx, st.s, d_xyzz.p, d_prefix.p);
+    else ctx->last_error = "kzg_srs_update: copying the new points into the table failed";
+    if (rc) {
+        hipFree(ctx->d_table);
+        ctx->d_table = nullptr;
+        ctx->n = 0;
+        for (auto& s : ctx->slots) free_slot_msm(s);
+        (void)hipGetLastError();
+        return rc;
+    }
+    tr.mark("tables");
+    rc = setup_slots(ctx);
+    tr.mark("slots");
+    return rc;
+}
+
+// the steps of kzg_srs_verify that need the device; hook: the caller's weights, step 5 alone, both sums returned
+// sides: B, then A (normalised blst_p1); *failed: a check before step 5 has set *reason already
+static int srs_verify_device(kzg_ctx* ctx, SrsTrace& tr, const uint64_t* weights, bool hook, unsigned flags, uint64_t sides[2][18],
+                             bool* failed, unsigned* reason, size_t* bad_index) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (ctx->raw_partials) return KZG_ERR_INVALID_ARG;  // a device of a range-split context holds a slice, not a setup
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};  // keeps an SRS replacement out until the call returns
+    Slot& s = ctx->slots[slot];
+    const size_t n = ctx->n;
+    const hipStream_t st = s.stream;
+    int rc = KZG_OK;
+    if (!hook) {
+        DevBuf d_err, d_p1;
+        HIP_TRY(ctx, hipMalloc(&d_err.p, 256));
+        HIP_TRY(ctx, hipMalloc(&d_p1.p, 144));
+        HIP_TRY(ctx, hipMemsetAsync(d_err.p, 0xff, 8, st));
+        launch_srs_check(st, ctx->d_table, (uint32_t)n, (uint32_t*)d_err.p);
+        launch_affine_to_p1(st, ctx->d_table, 1, d_p1.p);
+        HIP_TRY(ctx, hipGetLastError());
+        uint32_t herr[2];
+        uint64_t first_p1[18];
+        HIP_TRY(ctx, hipMemcpyAsync(herr, d_err.p, sizeof herr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(first_p1, d_p1.p, sizeof first_p1, hipMemcpyDeviceToHost, st));
+        rc = vc_sync(ctx, lk, st, "srs verify");
+        if (rc) return rc;
+        tr.mark("subgroup_check");
+        for (int e = 0; e < 2; e++)
+            if (herr[e] != 0xffffffffu) {
+                *reason = e ? KZG_SRS_NOT_IN_G1 : KZG_SRS_INFINITY;
+                if (bad_index) *bad_index = herr[e];
+                *failed = true;
+                return KZG_OK;
+            }
+        const hf::P1 gen = hf::p1_generator();
+        if ((flags & KZG_SRS_FIRST_IS_GENERATOR) && std::memcmp(first_p1, &gen, sizeof gen) != 0) {
+            *reason = KZG_SRS_FIRST_NOT_GENERATOR;
+            if (bad_index) *bad_index = 0;
+            *failed = true;
+            return KZG_OK;
+        }
+    }
+    std::memset(sides, 0, 2 * 144);
+    if (n > 1) {
+        // one buffer [0, rho_0, ..., rho_(n-2), 0] of plain integers serves both sums: B is the MSM of the n scalars from
+        // offset 0 (rho_(i-1) meets SRS[i]), A the one from offset 1 (rho_i meets SRS[i])
+        std::vector<uint64_t> sc;
+        try {
+            sc.assign(4 * (n + 1), 0);
+        } catch (...) {
+            ctx->last_error = "srs verify: out of host memory";
+            return KZG_ERR_HIP;
+        }
+        if (weights) {
+            for (size_t i = 0; i + 1 < n; i++) hf::fr_from_mont(weights + 4 * i, &sc[4 * (i + 1)]);
+        } else {  // uniform 128-bit weights from the OS, fresh on every call
+            std::vector<uint64_t> rnd(2 * (n - 1));
+            if (!vc_random(rnd.data(), rnd.size() * 8)) {
+                ctx->last_error = std::string("srs verify: getrandom: ") + std::strerror(errno);
+                return KZG_ERR_HIP;
+            }
+            for (size_t i = 0; i + 1 < n; i++) {
+                sc[4 * (i + 1)] = rnd[2 * i];
+                sc[4 * (i + 1) + 1] = rnd[2 * i + 1];
+            }
+        }
+        DevBuf d_sc;
+        HIP_TRY(ctx, hipMalloc(&d_sc.p, (n + 1) * 32));
+        lk.unlock();
+        const hipError_t e = hipMemcpyAsync(d_sc.p, sc.data(), (n + 1) * 32, hipMemcpyHostToDevice, st);
+        lk.lock();
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("srs verify: hipMemcpyAsync (weights): ") + hipGetErrorString(e);
+            return KZG_ERR_HIP;
+        }
+        for (int pass = 0; pass < 2 && rc == KZG_OK; pass++) {
+            rc = submit_commit_locked(ctx, slot, (const uint32_t*)d_sc.p + 8 * pass, 0, n, true, true);
+            if (rc) break;
+            await_unlocked(lk, s);
+            rc = wait_locked(ctx, slot, sides[pass]);
+            s.kind = SLOT_RESERVED;  // (wait_locked left it idle under the mutex we still hold) ours until the lease ends
+        }
+        if (rc) {
+            (void)hipStreamSynchronize(st);  // nothing reads d_sc after it is freed
+            return rc;
+        }
+        tr.mark("msm_x2");
+    }
+    return KZG_OK;
+}
+
+static int srs_verify_impl(kzg_ctx* ctx, const uint64_t* weights, bool hook, const void* setup_g2, size_t g2_stride_bytes,
+                           unsigned flags, uint64_t* out_a, uint64_t* out_b, int* valid, unsigned* reason, size_t* bad_index) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    const char* what = hook ? "kzg_srs_verify_lincomb" : "kzg_srs_verify";
+    if (!setup_g2 || !valid || (hook ? (!out_a || !out_b) : !reason)) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        ctx->last_error = std::string(what) + ": a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    *valid = 0;
+    if (reason) *reason = KZG_SRS_OK;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (ctx->multi) {  // a replicated SRS: the first device's copy
+        kzg_ctx* kid = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            ctx->last_error.clear();
+            const int rc = multi_replicated_only(ctx, what);
+            if (rc) return rc;
+            kid = multi_kid(ctx->multi, 0);
+        }
+        return forwarded(ctx, kid, srs_verify_impl(kid, weights, hook, setup_g2, g2_stride_bytes, flags, out_a, out_b, valid, reason,
+                                                   bad_index));
+    }
+    // step 1, on the host: the two G2 points
+    hf::G2Affine g2[2];
+    uint64_t raw[2][36];
+    for (int i = 0; i < 2; i++) {
+        std::memcpy(raw[i], (const uint8_t*)setup_g2 + i * g2_stride_bytes, sizeof raw[i]);
+        g2[i] = hf::g2_from_p2(raw[i]);
+        if (!hf::g2_on_curve(g2[i])) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            ctx->last_error = std::string(what) + ": setup_g2[" + (i ? "1" : "0") + "] is not on the twist";
+            return KZG_ERR_INVALID_ARG;
+        }
+    }
+    if (!hook) {
+        const hf::G2Affine gen = hf::g2_generator();
+        if (g2[0].inf || !(g2[0].x == gen.x) || !(g2[0].y == gen.y) || g2[1].inf || !g2_in_subgroup(raw[1])) {
+            *reason = KZG_SRS_G2_BAD;
+            return KZG_OK;
+        }
+    }
+    size_t count = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        count = ctx->n;
+        if (!count) return KZG_ERR_NO_SRS;
+        if (hook && count > 1) {
+            if (!weights) {
+                ctx->last_error = std::string(what) + ": a required pointer is NULL";
+                return KZG_ERR_INVALID_ARG;
+            }
+            for (size_t t = 0; t + 1 < count; t++) {
+                hf::Fr v;
+                std::memcpy(v.l, weights + 4 * t, 32);
+                if (hf::fr_geq(v, hf::kFrMod)) {
+                    ctx->last_error = std::string(what) + ": weight " + std::to_string(t) + " is not below r";
+                    return KZG_ERR_INVALID_ARG;
+                }
+            }
+        }
+    }
+    SrsTrace tr(hook ? "kzg_srs_verify_lincomb:" : "kzg_srs_verify:");
+    uint64_t sides[2][18];
+    bool failed = false;
+    const int rc = srs_verify_device(ctx, tr, hook ? weights : nullptr, hook, flags, sides, &failed, reason, bad_index);
+    if (rc || failed) return rc;
+    if (hook) {
+        std::memcpy(out_a, sides[1], 144);
+        std::memcpy(out_b, sides[0], 144);
+    }
+    // step 5: e(A, [s]G2) == e(B, [1]G2); with one point there is nothing to compare (both sides are infinity)
+    *valid = count > 1 ? vc_pair(sides[1], sides[0], g2[1], g2[0]) : 1;
+    tr.mark("pairing");
+    if (!*valid && reason) *reason = KZG_SRS_NOT_POWERS;
+    return KZG_OK;
+}
+
+int kzg_srs_verify(kzg_ctx* ctx, const void* setup_g2, size_t g2_stride_bytes, unsigned flags, int* valid, unsigned* reason,
+                   size_t* bad_index) {
+    return srs_verify_impl(ctx, nullptr, false, setup_g2, g2_stride_bytes, flags, nullptr, nullptr, valid, reason, bad_index);
+}
+
+int kzg_srs_verify_lincomb(kzg_ctx* ctx, const uint64_t* weights, const void* setup_g2, size_t g2_stride_bytes,
+                           uint64_t out_a_p1[18], uint64_t out_b_p1[18], int* valid) {
+    return srs_verify_impl(ctx, weights, true, setup_g2, g2_stride_bytes, 0u, out_a_p1, out_b_p1, valid, nullptr, nullptr);
+}
+
+int kzg_g2_mul(const uint64_t in_p2[36], const uint8_t scalar_be[32], uint64_t out_p2[36]) {
+    if (!in_p2 || !scalar_be || !out_p2) return KZG_ERR_INVALID_ARG;
+    if (!hf::g2_on_curve(hf::g2_from_p2(in_p2))) return KZG_ERR_INVALID_ARG;
+    uint32_t raw[8];
+    WipeGuard wipe_raw{raw, sizeof raw};
+    be32_to_raw8(scalar_be, raw);
+    hf::Fr k = raw8_mod_r(raw);
+    WipeGuard wipe_k{&k, sizeof k};
+    hf::P2 q;
+    std::memcpy(&q, in_p2, sizeof q);
+    const hf::P2 out = hf::p2_normalize(hf::p2_mul(q, k.l));
+    std::memcpy(out_p2, &out, sizeof out);
+    return KZG_OK;
+}
+
+int kzg_srs_verify_update(const uint64_t before_p1[18], const uint64_t after_p1[18], const uint64_t tau_g2[36], int* valid) {
+    if (!before_p1 || !after_p1 || !tau_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    const hf::G2Affine q = hf::g2_from_p2(tau_g2);
+    if (!hf::g2_on_curve(q)) return KZG_ERR_INVALID_ARG;  // as kzg_verify_proof answers a G2 input off the twist
+    *valid = 0;
+    hf::P1 before, after;
+    std::memcpy(&before, before_p1, sizeof before);
+    std::memcpy(&after, after_p1, sizeof after);
+    // a link with a point at infinity, a point off the curve or a [tau]G2 outside the subgroup of order r is no link
+    if (before.is_inf() || after.is_inf() || !hf::p1_on_curve(before) || !hf::p1_on_curve(after)) return KZG_OK;
+    if (q.inf || !g2_in_subgroup(tau_g2)) return KZG_OK;
+    *valid = vc_pair(before_p1, after_p1, q, hf::g2_generator());  // e(before, [tau]G2) == e(after, [1]G2)
+    return KZG_OK;
+}
+
 // ---- measurement ---------------------------------------------------------------------------------
 
 int kzg_set_timing(kzg_ctx* ctx, int enabled) {

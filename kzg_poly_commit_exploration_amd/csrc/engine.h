@@ -282,6 +282,13 @@ void launch_vc_fr_sum(hipStream_t s, const uint32_t* d_in, const uint32_t* d_ord
 void launch_vc_fr_twist(hipStream_t s, uint32_t* d_io, const uint32_t* d_ids, uint32_t D, const void* d_itw, uint32_t log_n,
                         uint32_t log_l, const Fr30& inv_l);
 
+// ---- srs_update_kernels.hip: a powers-of-tau contribution and the per-point checks of a setup --------
+// d_out_xyzz[i] = [tau^(first + i) mod r] d_level0[i] (affine records in, XYZZ out, infinity stays); tau_raw8: the
+// 256-bit little-endian integer, any value below 2^256 (the kernel-argument copy lives as long as k_srs_points' secret)
+void launch_srs_update(hipStream_t s, const uint32_t* tau_raw8, uint64_t first, uint32_t n, const void* d_level0, void* d_out_xyzz);
+// d_err[0] (pre-set to 0xffffffff) = least index at infinity, d_err[1] = least index off the curve or outside G1
+void launch_srs_check(hipStream_t s, const void* d_level0, uint32_t n, uint32_t* d_err);
+
 // ---- bary_kernels.hip: barycentric evaluation of polynomials in evaluation form --------------------
 constexpr uint32_t kBaryThreads = 256;       // lanes of a workgroup of the partial kernel
 constexpr uint32_t kBaryRun = 4;             // indices per lane

@@ -217,6 +217,55 @@ int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[
                       size_t k, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
                       int* valid);
 
+/* ---- combined openings: t polynomials at one point, one G1 element -------------------------
+ * The transpose of a multiproof, and what a proof-system prover sends in its last round (PLONK and its relatives): the
+ * t values y_i = P_i(z) and ONE proof, [q(s)]G1 with q = (F - F(z)) / (X - z) for F = sum_{i<t} gamma^i P_i.  A verifier
+ * forms C = sum gamma^i C_i and y = sum gamma^i y_i (kzg_combine_claims) and checks the single opening (C, z, y, proof)
+ * with any of the verifiers of this header; the two points z and z w of a PLONK proof are two such records in one
+ * kzg_verify_proof_batch / kzg_verify_openings_batch call.
+ * SOUNDNESS: gamma has to be a challenge fixed AFTER the commitments and the values y_i (and z after the commitments), as
+ * the protocol's transcript defines it.  Nothing is hashed here: these calls take z and gamma as given.
+ * Layout: polynomial i is n blst_fr values at coeffs + 4 i stride (stride >= n when t > 1), as kzg_open_batch takes them;
+ * shorter polynomials are padded with zeros.  z, gamma: blst_fr (Montgomery), refused when not below r.
+ * Prover: out_ys[4 i ..] = P_i(z).  There is no claim, hence no remainder error.  n' = F's length without trailing zero
+ *   coefficients (the reference's truncation): n' <= 1 gives infinity (also when F vanishes by cancellation; there is no
+ *   constant-polynomial error, as kzg_open_points); n' - 1 > kzg_srs_len gives KZG_ERR_DEGREE_TOO_HIGH.  t = 0,
+ *   t > KZG_MAX_COMBINE, a NULL pointer, or stride < n with t > 1 give KZG_ERR_INVALID_ARG.  For t = 1 and n' >= 2 the
+ *   proof is kzg_open's bit for bit, whatever gamma is.
+ * Cost: one streaming pass over the t n coefficients (k_combine_eval: F and the t values, every coefficient read once),
+ *   then the scan and the MSM of ONE opening -- where kzg_open_batch runs t scans and t MSMs.  Measured at n = 2^20 on
+ *   resident inputs (profiles/r14_open_combined.jsonl): not measured yet (tests/perf_open_combined.py writes that file; derived: t - 1 MSMs of about 2.4 ms replaced by streaming passes).
+ * The host-pointer call uploads and combines at most kzg_max_batch(ctx) polynomials per pass (F is carried between the
+ *   passes; the result does not depend on the grouping) and is bound by the upload; the resident call takes all t in one
+ *   launch.
+ * Multi-device contexts: a replicated SRS forwards the call to one device; a range-split SRS returns
+ *   KZG_ERR_INVALID_ARG (kzg_last_error says why).  kzg_combine_polys / kzg_evaluate_batch_at run on devices[0]. */
+#define KZG_MAX_COMBINE 256
+/* host pointers, synchronous; takes one of the context's stream slots like kzg_open */
+int kzg_open_combined(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t t, size_t stride_coeffs,
+                      const uint64_t z[4], const uint64_t gamma[4], uint64_t* out_ys /* t x 4 */, uint64_t out_p1[18]);
+/* d_coeffs is a DEVICE pointer; collected by kzg_wait_combined, which returns the t values of the slot's job (out_ys: t x 4)
+ * and the proof (single-device contexts only, like kzg_open_points_submit) */
+int kzg_open_combined_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, size_t t, size_t stride_coeffs,
+                             const uint64_t z[4], const uint64_t gamma[4]);
+int kzg_wait_combined(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]);
+/* with kzg_set_timing: the duration of the last job's combination pass on the slot (k_combine_eval and its finish kernel),
+ * next to what kzg_get_times reports for the scan and the MSM */
+int kzg_get_combine_ms(kzg_ctx* ctx, int slot, float* out_ms);
+/* the element-wise test hooks, no SRS needed: F's n coefficients (canonical blst_fr) / out_ys[4 i ..] = P_i(z) */
+int kzg_combine_polys(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t t, size_t stride_coeffs,
+                      const uint64_t gamma[4], uint64_t* out_f);
+int kzg_evaluate_batch_at(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t t, size_t stride_coeffs,
+                          const uint64_t z[4], uint64_t* out_ys);
+/* Host only, no context (like kzg_verify_proof).  kzg_combine_claims: C = sum gamma^i C_i (Horner in gamma: t - 1 scalar
+ * multiplications, spread over up to min(hardware threads, t) threads; normalised) and y = sum gamma^i y_i.  No curve or
+ * subgroup check of its own: the pair goes to a verifier, which applies its checks.  1 <= t <= KZG_MAX_COMBINE, gamma and
+ * the y_i below r, else KZG_ERR_INVALID_ARG.  kzg_verify_combined: kzg_combine_claims, then kzg_verify_proof. */
+int kzg_combine_claims(const uint64_t* commitments_p1, const uint64_t* ys, size_t t, const uint64_t gamma[4],
+                       uint64_t out_commitment_p1[18], uint64_t out_y[4]);
+int kzg_verify_combined(const uint64_t* commitments_p1, const uint64_t* ys, size_t t, const uint64_t z[4],
+                        const uint64_t gamma[4], const uint64_t proof_p1[18], const uint64_t s_g2[36], int* valid);
+
 /* ---- polynomials in evaluation form: NTT over power-of-two domains ------------------------
  * Most KZG data (blob-style commitments, proof systems) holds a polynomial as its values over a subgroup of roots of
  * unity.  These entry points take those values directly; until now a caller had to interpolate on the host first.

@@ -244,6 +244,31 @@ struct Evaluations {
     }
 };
 
+// Combined openings (kzg_open_combined): `batch` polynomials of n coefficients each (polynomial i at coeffs[i * n ..], as
+// commit_batch takes them) opened at one point with ONE proof, for F = sum gamma^i P_i.  gamma has to be the challenge the
+// protocol draws after the commitments and the values; nothing is hashed here.
+struct CombinedOpening {
+    Scalar point, gamma;
+    std::vector<Scalar> results;  // P_i(point)
+    G1Point proof;
+};
+inline CombinedOpening open_combined(const SetupArtifacts& setup, const std::vector<Scalar>& coeffs, size_t n, const Scalar& point,
+                                     const Scalar& gamma) {
+    const size_t batch = n ? coeffs.size() / n : 0;
+    CombinedOpening out{point, gamma, std::vector<Scalar>(batch), {}};
+    check(kzg_open_combined(setup.ctx(), reinterpret_cast<const uint64_t*>(coeffs.data()), n, batch, n, point.l.data(),
+                            gamma.l.data(), reinterpret_cast<uint64_t*>(out.results.data()), out.proof.p1.data()), setup.ctx());
+    return out;
+}
+// host-side check against the commitments of the polynomials; s_g2 = setup_artifacts[1].g2 as blst_p2 (36 x u64)
+inline bool verify_combined(const CombinedOpening& opening, const std::vector<G1Point>& commitments, const uint64_t s_g2[36]) {
+    int valid = 0;
+    check(kzg_verify_combined(reinterpret_cast<const uint64_t*>(commitments.data()),
+                              reinterpret_cast<const uint64_t*>(opening.results.data()), commitments.size(), opening.point.l.data(),
+                              opening.gamma.l.data(), opening.proof.p1.data(), s_g2, &valid), nullptr);
+    return valid == 1;
+}
+
 // Every cell of the domain of N = 2^log_domain points and its multiproof (kzg_cells_and_proofs): cell j holds the
 // l = 2^log_cell values P(w_N^(j + (N/l) i)), i < l, at values[j l + i]; proofs[j] is kzg_open_points' proof for them.
 struct Cells {

@@ -19,6 +19,7 @@ __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "domain_root",
+    "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -60,12 +61,15 @@ ABI_SYMBOLS = [
     "kzg_blobs_to_commitments_bytes", "kzg_blobs_to_cells_and_proofs_bytes", "kzg_recover_cells_and_proofs_bytes",
     "kzg_g1_compress_batch", "kzg_fr_to_bytes_batch",
     "kzg_srs_update", "kzg_srs_verify", "kzg_srs_verify_lincomb", "kzg_g2_mul", "kzg_srs_verify_update",
+    "kzg_open_combined", "kzg_open_combined_submit", "kzg_wait_combined", "kzg_get_combine_ms", "kzg_combine_polys",
+    "kzg_evaluate_batch_at", "kzg_combine_claims", "kzg_verify_combined",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
 KZG_ORDER_NATURAL = 0
 KZG_ORDER_BIT_REVERSED = 1
 KZG_MAX_OPEN_POINTS = 64
+KZG_MAX_COMBINE = 256
 KZG_NTT_MAX_LOG = 22
 KZG_MAX_CELL_LOG = 6
 
@@ -194,6 +198,14 @@ def load_library():
         "kzg_srs_verify_lincomb": (i, [vp, vp, vp, sz, vp, vp, C.POINTER(i)]),
         "kzg_g2_mul": (i, [vp, u8p, vp]),
         "kzg_srs_verify_update": (i, [vp, vp, vp, C.POINTER(i)]),
+        "kzg_open_combined": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp]),
+        "kzg_open_combined_submit": (i, [vp, i, vp, sz, sz, sz, vp, vp]),
+        "kzg_wait_combined": (i, [vp, i, vp, vp]),
+        "kzg_get_combine_ms": (i, [vp, i, C.POINTER(C.c_float)]),
+        "kzg_combine_polys": (i, [vp, vp, sz, sz, sz, vp, vp]),
+        "kzg_evaluate_batch_at": (i, [vp, vp, sz, sz, sz, vp, vp]),
+        "kzg_combine_claims": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_verify_combined": (i, [vp, vp, sz, vp, vp, vp, vp, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -540,6 +552,62 @@ class Engine:
         out = np.zeros((max(len(zs), 1), 4), dtype=np.uint64)
         _check(self._lib.kzg_evaluate_points(self._h, _ptr(a), a.shape[0], _ptr(zl), len(zs), _ptr(out)), self._h)
         return [Scalar.from_limbs(out[i]) for i in range(len(zs))]
+
+    # -- combined openings: t polynomials at one point, one proof for F = sum gamma^i P_i (z, gamma: Scalar) --
+    @staticmethod
+    def _combine_block(polys, stride):
+        """list of (n, 4) arrays or one (t, n, 4) array -> (flat uint64 block, n, t, stride): polynomial i at row i * stride"""
+        a = Engine._stack(polys)
+        t, n = a.shape[0], a.shape[1]
+        stride = n if stride is None else stride
+        if stride != n:
+            assert stride >= n or t == 1
+            block = np.zeros((t, max(stride, n), 4), dtype=np.uint64)
+            block[:, :n] = a
+            a = block
+        return np.ascontiguousarray(a), n, t, stride
+
+    def open_combined_limbs(self, polys, z, gamma, stride=None):
+        """kzg_open_combined: returns ([P_i(z)], proof) for equally long polynomials in host memory"""
+        flat, n, t, stride = self._combine_block(polys, stride)
+        zl, gl = z.limbs(), gamma.limbs()
+        ys = np.zeros((t, 4), dtype=np.uint64)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_open_combined(self._h, _ptr(flat), n, t, stride, _ptr(zl), _ptr(gl), _ptr(ys), _ptr(out)), self._h)
+        return [Scalar.from_limbs(ys[i]) for i in range(t)], G1Point(out)
+
+    def open_combined_submit(self, slot, dptr, n, t, z, gamma, stride=None):
+        zl, gl = z.limbs(), gamma.limbs()
+        _check(self._lib.kzg_open_combined_submit(self._h, slot, C.c_void_p(dptr), n, t, n if stride is None else stride,
+                                                  _ptr(zl), _ptr(gl)), self._h)
+
+    def wait_combined(self, slot, t):
+        ys = np.zeros((max(t, 1), 4), dtype=np.uint64)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_wait_combined(self._h, slot, _ptr(ys), _ptr(out)), self._h)
+        return [Scalar.from_limbs(ys[i]) for i in range(t)], G1Point(out)
+
+    def combine_ms(self, slot):
+        """with set_timing(True): the duration of the slot's last combination pass, in ms"""
+        ms = C.c_float(0)
+        _check(self._lib.kzg_get_combine_ms(self._h, slot, C.byref(ms)), self._h)
+        return float(ms.value)
+
+    def combine_polys_limbs(self, polys, gamma, stride=None):
+        """kzg_combine_polys: the coefficients of F = sum gamma^i P_i as an (n, 4) array of blst_fr images"""
+        flat, n, t, stride = self._combine_block(polys, stride)
+        gl = gamma.limbs()
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        _check(self._lib.kzg_combine_polys(self._h, _ptr(flat), n, t, stride, _ptr(gl), _ptr(out)), self._h)
+        return out[:n].copy()
+
+    def evaluate_batch_at_limbs(self, polys, z, stride=None):
+        """kzg_evaluate_batch_at: [P_i(z)]"""
+        flat, n, t, stride = self._combine_block(polys, stride)
+        zl = z.limbs()
+        ys = np.zeros((t, 4), dtype=np.uint64)
+        _check(self._lib.kzg_evaluate_batch_at(self._h, _ptr(flat), n, t, stride, _ptr(zl), _ptr(ys)), self._h)
+        return [Scalar.from_limbs(ys[i]) for i in range(t)]
 
     # -- every cell of the domain of N = 2^log_domain points and its multiproof (cells of 2^log_cell points) --
     def _cells(self, fn, values, log_domain, log_cell):
@@ -1185,6 +1253,33 @@ def verify_points(commitment, proof, zs, ys, setup_g1, setup_g2):
 # ---------------------------------------------------------------------------------------------
 # Polynomial / Evaluation: reference src/polynomial.rs
 # ---------------------------------------------------------------------------------------------
+def combine_claims(commitments, ys, gamma):
+    """kzg_combine_claims: (sum gamma^i C_i, sum gamma^i y_i) on the host -- one (commitment, value) pair that any of the
+    verifiers takes together with the combined proof.  gamma has to be the challenge the protocol draws AFTER the
+    commitments and the values; nothing is hashed here."""
+    lib = load_library()
+    t = len(commitments)
+    assert len(ys) == t
+    cs = np.ascontiguousarray(np.stack([c.p1 for c in commitments]) if t else np.zeros((1, 18)), dtype=np.uint64)
+    yl, gl = _scalar_rows(ys), gamma.limbs()
+    out_c, out_y = np.zeros(18, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    _check(lib.kzg_combine_claims(_ptr(cs), _ptr(yl), t, _ptr(gl), _ptr(out_c), _ptr(out_y)))
+    return G1Point(out_c), Scalar.from_limbs(out_y)
+
+
+def verify_combined(commitments, ys, z, gamma, proof, s_g2):
+    """kzg_verify_combined: combine_claims, then verify_proof of the pair at z"""
+    lib = load_library()
+    t = len(commitments)
+    assert len(ys) == t
+    g2 = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(36)
+    cs = np.ascontiguousarray(np.stack([c.p1 for c in commitments]) if t else np.zeros((1, 18)), dtype=np.uint64)
+    yl, zl, gl = _scalar_rows(ys), z.limbs(), gamma.limbs()
+    ok = C.c_int(0)
+    _check(lib.kzg_verify_combined(_ptr(cs), _ptr(yl), t, _ptr(zl), _ptr(gl), _ptr(proof.p1), _ptr(g2), C.byref(ok)))
+    return bool(ok.value)
+
+
 class Polynomial:
     def __init__(self, limbs):
         self.limbs = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)

@@ -68,7 +68,8 @@ struct ReducePlan {
 // SLOT_RESERVED: owned by a synchronous host-pointer call between its steps (upload -> submit -> wait), during which the
 // context mutex is NOT held: N caller threads occupy N slots and their jobs pipeline like explicit submits do.
 enum SlotKind { SLOT_IDLE = 0, SLOT_COMMIT = 1, SLOT_OPEN = 2, SLOT_TRIVIAL = 3, SLOT_COMMIT_BATCH = 4, SLOT_OPEN_BATCH = 5, SLOT_RESERVED = 6,
-                SLOT_OPEN_POINTS = 7 /* a multiproof: trivial or not, collected by kzg_wait */ };
+                SLOT_OPEN_POINTS = 7 /* a multiproof: trivial or not, collected by kzg_wait */,
+                SLOT_OPEN_COMBINED = 8 /* a combined opening: trivial or not, collected by kzg_wait_combined */ };
 
 struct Slot {
     hipStream_t stream = nullptr;
@@ -118,6 +119,21 @@ struct Slot {
     size_t pblock_words = 0;
     std::vector<uint32_t> pts_ys;  // the claims (8 words each)
     size_t pts_nq = 0;             // terms of the job's MSM (0: the proof is infinity once the claims hold)
+    // combined openings (kzg_open_combined): the call's multipliers (powers of z, gamma^i) go through a
+    // pinned staging area to a device table like the roots of a multiproof; the t values P_i(z) land in pinned mapped memory;
+    // F is built in d_stage.  d_cpart: the (polynomial, tile) records of one pass; d_cin: the polynomials of one pass of the
+    // host-pointer call.  All grown on demand.
+    void* h_ctab = nullptr;
+    void* d_ctab = nullptr;
+    uint32_t* h_cvals = nullptr;
+    uint32_t* d_cvals = nullptr;
+    uint32_t* d_cpart = nullptr;
+    size_t cpart_words = 0;
+    uint32_t* d_cin = nullptr;
+    size_t cin_coeffs = 0;
+    size_t cmb_t = 0;              // polynomials of the job in flight
+    hipEvent_t cmb_ev[2] = {};     // timed jobs: around the (last) combination pass
+    float combine_ms = 0;
     // cells of a domain (kzg_cells_and_proofs): P for the whole call in d_cpoly (read by the sub-batches of every slot the call
     // holds, after cells_ev), the chunk aggregates of the cell quotients in d_cagg
     uint32_t* d_cpoly = nullptr;
@@ -757,6 +773,13 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
         if (s.h_pvals) hipHostFree(s.h_pvals);
         hipFree(s.d_roots);
         hipFree(s.d_pblock);
+        if (s.h_ctab) hipHostFree(s.h_ctab);
+        if (s.h_cvals) hipHostFree(s.h_cvals);
+        hipFree(s.d_ctab);
+        hipFree(s.d_cpart);
+        hipFree(s.d_cin);
+        for (auto& e : s.cmb_ev)
+            if (e) hipEventDestroy(e);
         hipFree(s.d_cpoly);
         hipFree(s.d_cagg);
         if (s.cells_ev) hipEventDestroy(s.cells_ev);
@@ -1232,6 +1255,10 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
         ctx->last_error = "kzg_wait on a slot that holds a batched job (use kzg_wait_batch / kzg_wait_open_batch)";
         return KZG_ERR_INVALID_ARG;  // the job stays in the slot
     }
+    if (s.kind == SLOT_OPEN_COMBINED) {
+        ctx->last_error = "kzg_wait on a slot that holds a combined opening (use kzg_wait_combined)";
+        return KZG_ERR_INVALID_ARG;  // the job stays in the slot
+    }
     if (s.kind == SLOT_RESERVED) return KZG_ERR_BUSY;  // a synchronous call on another thread owns it
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SlotKind kind = s.kind;
@@ -1619,6 +1646,312 @@ int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64
     }
     release_owned(ctx, slot);
     return rc;
+}
+
+// ---- combined openings: t polynomials, one point, one proof ---------------------------------
+namespace {
+// the slot's buffers for passes of at most t_pass polynomials of n coefficients; stage_coeffs: room in d_cin (host-pointer
+// passes), 0 when the polynomials are resident (slot basics already there)
+int ensure_combined(kzg_ctx* ctx, Slot& s, size_t n, size_t t_pass, size_t stage_coeffs) {
+    if (!s.h_ctab) {
+        HIP_TRY(ctx, hipHostMalloc(&s.h_ctab, kCombineTabLen * sizeof(Fr30), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc(&s.d_ctab, kCombineTabLen * sizeof(Fr30)));
+        HIP_TRY(ctx, hipHostMalloc(&s.h_cvals, kCombineMax * 32, hipHostMallocMapped));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_cvals, s.h_cvals, 0));
+        for (auto& e : s.cmb_ev) HIP_TRY(ctx, hipEventCreate(&e));
+    }
+    const size_t words = t_pass * combine_tiles((uint32_t)(n ? n : 1)) * kCombinePartialWords;
+    if (words > s.cpart_words) {
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        hipFree(s.d_cpart);
+        s.d_cpart = nullptr;
+        s.cpart_words = 0;
+        HIP_TRY(ctx, hipMalloc(&s.d_cpart, words * 4));
+        s.cpart_words = words;
+    }
+    if (stage_coeffs > s.cin_coeffs) {
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        hipFree(s.d_cin);
+        s.d_cin = nullptr;
+        s.cin_coeffs = 0;
+        HIP_TRY(ctx, hipMalloc(&s.d_cin, stage_coeffs * 32));
+        s.cin_coeffs = stage_coeffs;
+    }
+    return KZG_OK;
+}
+// every multiplier of one call: the 16 + 16 tables and the stride of z (a lane's power inside a tile) and of W = z^2048
+// (a tile's power inside the polynomial), then gamma^i -- 66 + t host products -- copied to the slot's table on its stream
+int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& gamma, size_t t) {
+    Fr30* tab = (Fr30*)s.h_ctab;
+    auto fill = [&](const hf::Fr& x, uint32_t at_a, uint32_t at_b, uint32_t at_256) {
+        const hf::Fr x16 = hf::fr_pow(x, 16);
+        hf::Fr a = hf::kFrOne, b = hf::kFrOne;
+        for (int e = 0; e < 16; e++) {
+            tab[at_a + e] = fr30_arg_from_mont256(a);
+            tab[at_b + e] = fr30_arg_from_mont256(b);
+            a = hf::fr_mul(a, x16);
+            b = hf::fr_mul(b, x);
+        }
+        tab[at_256] = fr30_arg_from_mont256(a);  // (x^16)^16
+        return a;
+    };
+    const hf::Fr z256 = fill(z, kCombineTabPa, kCombineTabPb, kCombineTabZ256);
+    fill(hf::fr_pow(z256, kCombineTile / 256), kCombineTabWa, kCombineTabWb, kCombineTabW256);
+    hf::Fr g = hf::kFrOne;
+    for (size_t i = 0; i < t; i++) {
+        tab[kCombineTabGamma + i] = fr30_arg_from_mont256(g);
+        g = hf::fr_mul(g, gamma);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_ctab, s.h_ctab, (kCombineTabGamma + t) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    return KZG_OK;
+}
+// one pass on the slot's stream: polynomials first .. first + cnt (device memory) into F (s.d_stage, carried from the earlier
+// passes when first > 0) and their values into the slot's value words
+int combined_pass(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, size_t cnt, size_t stride, size_t first) {
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
+    launch_combine_eval(s.stream, d_coeffs, (uint32_t)n, (uint32_t)cnt, stride, (const Fr30*)s.d_ctab, (uint32_t)first, first > 0,
+                        s.d_stage, s.d_cpart, s.d_cvals + 8 * first);
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+bool fr_arg_below_r(const uint64_t v[4], hf::Fr* out) {
+    std::memcpy(out->l, v, 32);
+    return !hf::fr_geq(*out, hf::kFrMod);
+}
+// the arguments every combined call shares; z, gamma may be null where the call takes none
+int combined_check(kzg_ctx* ctx, const char* what, const void* coeffs, size_t n, size_t t, size_t stride, const uint64_t* z,
+                   const uint64_t* gamma, hf::Fr* zf, hf::Fr* gf) {
+    auto invalid = [&](const char* why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (t < 1 || t > KZG_MAX_COMBINE) return invalid("t must be in [1, KZG_MAX_COMBINE]");
+    if (!coeffs && n) return invalid("null coefficients");
+    if (n > kMaxCoefficients) return invalid("too many coefficients");
+    if (t > 1 && stride < n) return invalid("stride below n");
+    *zf = hf::Fr{{0, 0, 0, 0}};
+    *gf = hf::Fr{{0, 0, 0, 0}};
+    if (z && !fr_arg_below_r(z, zf)) return invalid("the point z is not below r");
+    if (gamma && !fr_arg_below_r(gamma, gf)) return invalid("gamma is not below r");
+    return KZG_OK;
+}
+// host polynomials [first, first + cnt) -> the slot's pass buffer, n coefficients each, back to back; without the mutex
+int combined_stage_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint64_t* coeffs, size_t n, size_t stride,
+                            size_t first, size_t cnt) {
+    lk.unlock();
+    hipError_t e = hipSuccess;
+    if (stride == n || cnt == 1) {
+        e = hipMemcpyAsync(s.d_cin, coeffs + 4 * first * stride, cnt * n * 32, hipMemcpyHostToDevice, s.stream);
+    } else {
+        for (size_t i = 0; i < cnt && e == hipSuccess; i++)
+            e = hipMemcpyAsync(s.d_cin + 8 * i * n, coeffs + 4 * (first + i) * stride, n * 32, hipMemcpyHostToDevice, s.stream);
+    }
+    lk.lock();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMemcpyAsync (coefficients): ") + hipGetErrorString(e);
+        return KZG_ERR_HIP;
+    }
+    return KZG_OK;
+}
+// all passes of a host-pointer call: at most max_batch polynomials per launch
+int combined_host_passes(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint64_t* coeffs, size_t n, size_t t,
+                         size_t stride, const hf::Fr& z, const hf::Fr& gamma) {
+    const size_t group = std::min<size_t>(t, ctx->max_batch ? ctx->max_batch : 1);
+    int rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = ensure_combined(ctx, s, n, group, group * n);
+    if (rc == KZG_OK) rc = combined_upload_table(ctx, s, z, gamma, t);
+    for (size_t first = 0; first < t && rc == KZG_OK; first += group) {
+        const size_t cnt = std::min(group, t - first);
+        rc = combined_stage_unlocked(ctx, lk, s, coeffs, n, stride, first, cnt);
+        if (rc == KZG_OK) rc = combined_pass(ctx, s, s.d_cin, n, cnt, n, first);
+    }
+    return rc;
+}
+// the opening of F (n coefficients in s.d_stage) at z behind the passes, as submit_open_locked runs it on a caller's buffer;
+// the prover has no claim, so F(z) is only computed, not compared
+int combined_enqueue_open(kzg_ctx* ctx, Slot& s, size_t n, size_t t, const uint64_t z[4]) {
+    s.job_n = n;
+    s.job_batch = 1;
+    s.has_quotient = true;
+    s.tail_checked = false;
+    s.cmb_t = t;
+    s.pts_nq = 0;
+    std::memset(s.h_small, 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
+    if (n > 0) {
+        uint32_t zw[8];
+        std::memcpy(zw, z, 32);
+        if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
+        if (!launch_quotient_single(s.stream, s.d_stage, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, s.d_small)) {
+            PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
+            launch_quotient(s.stream, s.d_stage, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, sc);
+        }
+        if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
+        size_t nq = n - 1;
+        if (nq > ctx->n) {  // too high iff some coefficient of F with index > srs_len is non-zero
+            const uint64_t from = ctx->n + 1, cnt = n - from;
+            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.d_stage, from,
+                               (uint64_t)n, s.d_small + 24);
+            nq = ctx->n;
+        }
+        if (nq > 0) {
+            int rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+            if (rc) return rc;
+        }
+        s.pts_nq = nq;
+    }
+    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    s.kind = SLOT_OPEN_COMBINED;
+    return KZG_OK;
+}
+int combined_job_start(kzg_ctx* ctx, Slot& s, size_t t) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    s.timing = ctx->timing;
+    s.combine_ms = 0;
+    std::memset(&s.times, 0, sizeof s.times);
+    int rc = ensure_combined(ctx, s, 0, 0, 0);
+    if (rc == KZG_OK) std::memset(s.h_cvals, 0, 32 * t);  // (the slot holds no job in flight)
+    return rc;
+}
+
+int wait_combined_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]) {
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind == SLOT_RESERVED) return KZG_ERR_BUSY;  // a synchronous call on another thread owns it
+    if (s.kind != SLOT_OPEN_COMBINED) {
+        if (s.kind != SLOT_IDLE) ctx->last_error = "kzg_wait_combined on a slot that holds another kind of job";
+        return KZG_ERR_INVALID_ARG;  // the job stays in the slot
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    slot_idle(ctx, s);
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    const bool ran_msm = s.pts_nq > 0;
+    if (ran_msm) fill_device_times(s);
+    if (s.timing && s.job_n > 0) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, s.cmb_ev[0], s.cmb_ev[1]) == hipSuccess) s.combine_ms = ms;
+        if (ran_msm) {
+            hipEventElapsedTime(&ms, s.ev[0], s.ev[1]); s.times.digits_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[2], s.ev[3]); s.times.scatter_ms = ms;
+            fill_accumulate_times(s);
+            hipEventElapsedTime(&ms, s.ev[4], s.ev[5]); s.times.reduce_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[6], s.ev[7]); s.times.quotient_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[6], s.ev[5]); s.times.total_ms = ms;
+        }
+    }
+    std::memcpy(out_ys, s.h_cvals, 32 * s.cmb_t);
+    const uint32_t* hs = s.h_small;
+    // F after the reference's truncation: no non-zero coefficient above the constant one -> infinity, like kzg_open_points
+    if (s.job_n == 0 || !(hs[0] & 1u)) {
+        write_p1(out_p1, hf::p1_inf());
+        return KZG_OK;
+    }
+    if (hs[24]) return KZG_ERR_DEGREE_TOO_HIGH;
+    write_p1(out_p1, ran_msm ? finish_msm(ctx, s) : hf::p1_inf());
+    return KZG_OK;
+}
+
+// the two hooks: every pass of the host-pointer call without the opening (no SRS needed)
+int combined_hook(kzg_ctx* ctx, const char* what, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t* z,
+                  const uint64_t* gamma, uint64_t* out_f, uint64_t* out_ys) {
+    hf::Fr zf, gf;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = combined_check(ctx, what, coeffs, n, t, stride, z, gamma, &zf, &gf);
+    if (rc) return rc;
+    if (out_ys) std::memset(out_ys, 0, 32 * t);
+    if (n == 0) return KZG_OK;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = combined_job_start(ctx, s, t);
+    if (rc == KZG_OK) rc = combined_host_passes(ctx, lk, s, coeffs, n, t, stride, zf, gf);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    if (out_ys) std::memcpy(out_ys, s.h_cvals, 32 * t);
+    if (out_f) HIP_TRY(ctx, hipMemcpy(out_f, s.d_stage, n * 32, hipMemcpyDeviceToHost));
+    return KZG_OK;
+}
+}  // namespace
+
+int kzg_open_combined(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
+                      const uint64_t gamma[4], uint64_t* out_ys, uint64_t out_p1[18]) {
+    if (!ctx || !z || !gamma || !out_ys || !out_p1) return KZG_ERR_INVALID_ARG;
+    hf::Fr zf, gf;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = combined_check(ctx, "kzg_open_combined", coeffs, n, t, stride, z, gamma, &zf, &gf);
+    if (rc) return rc;
+    if (ctx->multi) {
+        ctx->last_error.clear();  // (kzg_last_error then reads the devices' side)
+        lk.unlock();
+        return multi_open_combined(ctx->multi, coeffs, n, t, stride, z, gamma, out_ys, out_p1);
+    }
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    Slot& s = ctx->slots[slot];
+    rc = combined_job_start(ctx, s, t);
+    if (rc == KZG_OK && n) rc = combined_host_passes(ctx, lk, s, coeffs, n, t, stride, zf, gf);
+    if (rc == KZG_OK) rc = combined_enqueue_open(ctx, s, n, t, z);
+    if (rc == KZG_OK) {
+        await_unlocked(lk, s);
+        rc = wait_combined_locked(ctx, slot, out_ys, out_p1);
+    }
+    release_owned(ctx, slot);
+    return rc;
+}
+
+int kzg_open_combined_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
+                             const uint64_t gamma[4]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !z || !gamma) return KZG_ERR_INVALID_ARG;
+    hf::Fr zf, gf;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = combined_check(ctx, "kzg_open_combined_submit", d_coeffs, n, t, stride, z, gamma, &zf, &gf);
+    if (rc) return rc;
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind != SLOT_IDLE) return KZG_ERR_BUSY;
+    rc = combined_job_start(ctx, s, t);
+    if (rc == KZG_OK && n) {  // all t polynomials in one launch
+        rc = ensure_poly(ctx, s, n);
+        if (rc == KZG_OK) rc = ensure_combined(ctx, s, n, t, 0);
+        if (rc == KZG_OK) rc = combined_upload_table(ctx, s, zf, gf, t);
+        if (rc == KZG_OK) rc = combined_pass(ctx, s, (const uint32_t*)d_coeffs, n, t, stride, 0);
+    }
+    if (rc == KZG_OK) rc = combined_enqueue_open(ctx, s, n, t, z);
+    return rc;
+}
+
+int kzg_wait_combined(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !out_ys || !out_p1) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return wait_combined_locked(ctx, slot, out_ys, out_p1);
+}
+
+int kzg_get_combine_ms(kzg_ctx* ctx, int slot, float* out_ms) {
+    if (!ctx || ctx->multi || !out_ms || slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out_ms = ctx->slots[slot].combine_ms;
+    return KZG_OK;
+}
+
+int kzg_combine_polys(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t gamma[4],
+                      uint64_t* out_f) {
+    if (!ctx || !gamma || (!out_f && n)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_combine_polys(multi_kid(ctx->multi, 0), coeffs, n, t, stride, gamma, out_f);  // needs no SRS
+    return combined_hook(ctx, "kzg_combine_polys", coeffs, n, t, stride, nullptr, gamma, out_f, nullptr);
+}
+
+int kzg_evaluate_batch_at(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
+                          uint64_t* out_ys) {
+    if (!ctx || !z || !out_ys) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_evaluate_batch_at(multi_kid(ctx->multi, 0), coeffs, n, t, stride, z, out_ys);  // needs no SRS
+    return combined_hook(ctx, "kzg_evaluate_batch_at", coeffs, n, t, stride, z, nullptr, nullptr, out_ys);
 }
 
 // ---- host-pointer batches (BASELINE config 5: many openings against one SRS) ----------------------------------------
@@ -4651,6 +4984,78 @@ int kzg_verify_proof_batch(const uint64_t* commitments_p1, const uint64_t* proof
         valid[i] = results[i];
     }
     return KZG_OK;
+}
+
+// ---- combined openings, the verifier's side (host only) ---------------------------------------
+// C = sum gamma^i C_i and y = sum gamma^i y_i by Horner in gamma: t - 1 scalar multiplications.  With several threads the
+// list is cut into runs of L commitments, every run is a Horner sum of its own and the run totals are joined by Horner in
+// gamma^L -- still t - 1 multiplications, of which about L + t / L lie on the critical path; the thread count is therefore
+// the one nearest sqrt(t), capped by min(hardware threads, t) as in kzg_verify_proof_batch.
+int kzg_combine_claims(const uint64_t* commitments_p1, const uint64_t* ys, size_t t, const uint64_t gamma[4],
+                       uint64_t out_commitment_p1[18], uint64_t out_y[4]) {
+    if (!commitments_p1 || !ys || !gamma || !out_commitment_p1 || !out_y) return KZG_ERR_INVALID_ARG;
+    if (t < 1 || t > KZG_MAX_COMBINE) return KZG_ERR_INVALID_ARG;
+    hf::Fr g, v;
+    std::memcpy(g.l, gamma, 32);
+    if (hf::fr_geq(g, hf::kFrMod)) return KZG_ERR_INVALID_ARG;
+    for (size_t i = 0; i < t; i++) {
+        std::memcpy(v.l, ys + 4 * i, 32);
+        if (hf::fr_geq(v, hf::kFrMod)) return KZG_ERR_INVALID_ARG;
+    }
+    hf::Fr y;
+    std::memcpy(y.l, ys + 4 * (t - 1), 32);
+    for (size_t i = t - 1; i-- > 0;) {
+        std::memcpy(v.l, ys + 4 * i, 32);
+        y = hf::fr_add(hf::fr_mul(y, g), v);
+    }
+    size_t cap = std::thread::hardware_concurrency();
+    if (cap == 0) cap = 1;
+    if (cap > t) cap = t;
+    size_t nthreads = 1;
+    while ((nthreads + 1) * (nthreads + 1) <= t && nthreads < cap) nthreads++;
+    const size_t L = (t + nthreads - 1) / nthreads;  // commitments per run
+    const size_t runs = (t + L - 1) / L;
+    auto load = [&](size_t i) {
+        hf::P1 p;
+        std::memcpy(&p, commitments_p1 + 18 * i, sizeof p);
+        return p;
+    };
+    auto horner = [&](size_t lo, size_t hi, const uint64_t k[4]) {  // sum_{lo <= i < hi} gamma^(i - lo) C_i
+        hf::P1 acc = load(hi - 1);
+        for (size_t i = hi - 1; i-- > lo;) acc = hf::p1_add(hf::p1_mul(acc, k), load(i));
+        return acc;
+    };
+    uint64_t gk[4];
+    hf::fr_from_mont(g.l, gk);
+    std::vector<hf::P1> part(runs);
+    auto work = [&](size_t r) { part[r] = horner(r * L, std::min(t, (r + 1) * L), gk); };
+    if (runs <= 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (size_t r = 1; r < runs; r++) pool.emplace_back(work, r);
+        work(0);
+        for (auto& th : pool) th.join();
+    }
+    hf::P1 acc = part[runs - 1];
+    if (runs > 1) {
+        uint64_t gl[4];
+        const hf::Fr gL = hf::fr_pow(g, L);
+        hf::fr_from_mont(gL.l, gl);
+        for (size_t r = runs - 1; r-- > 0;) acc = hf::p1_add(hf::p1_mul(acc, gl), part[r]);
+    }
+    write_p1(out_commitment_p1, hf::p1_normalize(acc));
+    std::memcpy(out_y, y.l, 32);
+    return KZG_OK;
+}
+
+int kzg_verify_combined(const uint64_t* commitments_p1, const uint64_t* ys, size_t t, const uint64_t z[4], const uint64_t gamma[4],
+                        const uint64_t proof_p1[18], const uint64_t s_g2[36], int* valid) {
+    if (!z || !proof_p1 || !s_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    uint64_t c[18], y[4];
+    const int rc = kzg_combine_claims(commitments_p1, ys, t, gamma, c, y);
+    if (rc) return rc;
+    return kzg_verify_proof(c, proof_p1, z, y, s_g2, valid);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

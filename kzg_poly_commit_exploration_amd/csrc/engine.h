@@ -301,6 +301,27 @@ inline uint32_t bary_tiles(uint32_t log_n) { return (uint32_t)((((uint64_t)1 << 
 void launch_bary(hipStream_t s, const uint32_t* d_evals, uint32_t log_n, uint32_t batch, const Fr30* d_zs, const void* d_tw,
                  const Fr30& inv_n, uint32_t* d_partial, uint32_t* d_out);
 
+// ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
+constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
+constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8
+constexpr uint32_t kCombinePartialWords = 12; // a (polynomial, tile) record: nine digits, padded to 3 x 16 bytes
+constexpr uint32_t kCombineMax = 256;         // polynomials per combination (KZG_MAX_COMBINE)
+// the multipliers of one call, Fr30 records in multiplier form (x 2^270), prepared on the host:
+constexpr uint32_t kCombineTabPa = 0;         // z^(16 e), e < 16
+constexpr uint32_t kCombineTabPb = 16;        // z^e
+constexpr uint32_t kCombineTabZ256 = 32;      // z^256
+constexpr uint32_t kCombineTabWa = 33;        // W^(16 e), W = z^2048
+constexpr uint32_t kCombineTabWb = 49;        // W^e
+constexpr uint32_t kCombineTabW256 = 65;      // W^256
+constexpr uint32_t kCombineTabGamma = 66;     // gamma^i, i < kCombineMax
+constexpr uint32_t kCombineTabLen = kCombineTabGamma + kCombineMax;
+inline uint32_t combine_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kCombineTile - 1) / kCombineTile); }
+// Polynomials first .. first + t of a combination (polynomial first + i: n coefficients at d_coeffs + 8 i stride words):
+// d_f[j] (n canonical values) = (carry ? d_f[j] : 0) + sum_i gamma^(first + i) c_(i,j); d_ys[8 i ..] = P_(first + i)(z),
+// canonical.  d_partial: t x combine_tiles(n) records of kCombinePartialWords words.  n >= 1, t <= kCombineMax.
+void launch_combine_eval(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t t, uint64_t stride, const Fr30* d_tab,
+                         uint32_t first, bool carry, uint32_t* d_f, uint32_t* d_partial, uint32_t* d_ys);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>
@@ -348,6 +369,8 @@ int multi_open_batch(MultiState* m, const uint64_t* coeffs, size_t n, size_t bat
                      const uint64_t* ys, uint64_t* out_p1s, int* statuses);
 int multi_open_points(MultiState* m, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,
                       uint64_t out_p1[18]);
+int multi_open_combined(MultiState* m, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
+                        const uint64_t gamma[4], uint64_t* out_ys, uint64_t out_p1[18]);
 int multi_set_max_batch(MultiState* m, size_t max_batch);
 uint32_t multi_mode(const MultiState* m);
 

@@ -237,6 +237,22 @@ KZG_HD Fr30 fr30_const_r2_540() {
     return r;
 }
 
+// Sums of products (the combined openings, combine_kernels.hip): acc + a * b / 2^270, carry-normalised.
+// acc: digits 0..7 within [-2^29 - 4, 2^29 + 4] (a fr30_norm, a fr30_from_limbs or zero), any top digit below 2^30 in
+// magnitude; a, b as fr30_mul takes them.  The product's digits 0..7 lie in [-2^29, 2^29), so the raw sum stays within
+// 2^30 + 4 < 2^31 - 2^29, which is what fr30_norm asks for: ONE product per carry pass (a second raw product would reach
+// 3 * 2^29 + 4, past that contract).  The top digit is never reduced: it holds value / 2^240, and a sum of up to 256
+// products of magnitude <= 0.5001 r + r / 2^14 (a canonical multiplier, an operand below 2^256) plus one canonical value
+// is below 129.1 r, a top digit below 129.1 * 0x73ee + 1 < kR9SumTopBound.
+constexpr int32_t kR9SumRawBound = (1 << 30) + 4;   // |digit 0..7| of the raw sum inside fr30_mac
+constexpr int32_t kR9SumNormBound = (1 << 29) + 4;  // |digit 0..7| of what fr30_mac returns
+constexpr int32_t kR9SumTopBound = 1 << 22;         // |digit 8| of a sum of up to 256 products and one canonical value
+KZG_HD Fr30 fr30_mac_raw(const Fr30& acc, const Fr30& a, const Fr30& b) { return fr30_add_raw(acc, fr30_mul(a, b)); }
+KZG_HD Fr30 fr30_mac(const Fr30& acc, const Fr30& a, const Fr30& b) { return fr30_norm(fr30_mac_raw(acc, a, b)); }
+// such a sum (|v| < 2^263) back under 0.51 r in magnitude, the value unchanged: one product with the multiplier form of one
+// (|v| * (r / 2) / 2^270 < r / 2^8 on top of the product's own 0.5001 r) -- inside what fr30_to_limbs canonicalises
+KZG_HD Fr30 fr30_sum_reduce(const Fr30& acc) { return fr30_mul(acc, fr30_const_one270()); }
+
 // 1 / a for a value that carries the factor 2^270 (a = x * 2^270 -> x^-1 * 2^270; 0 -> 0): Fermat's a^(r - 2) with a fixed
 // window of two bits -- 254 squarings and at most 127 products by a, a^2 or a^3 chosen digit by digit, so that the three
 // table entries stay in registers (a four-bit window saves ~60 products and costs 12 more entries: 108 registers).

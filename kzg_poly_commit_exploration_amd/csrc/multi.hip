@@ -517,6 +517,18 @@ int multi_commit(MultiState* m, const void* scalars, int is_mont, size_t n, uint
     return exchange_and_sum(m, partials.data(), 1, out_p1);
 }
 
+// A combined opening: replicated SRS -> one device.  F's quotient over a range-split SRS would need F itself split over the
+// devices: not supported, like the multiproofs.
+int multi_open_combined(MultiState* m, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
+                        const uint64_t gamma[4], uint64_t* out_ys, uint64_t out_p1[18]) {
+    if (!m->n) return KZG_ERR_NO_SRS;
+    if (m->mode == kMultiReplicate)
+        return kzg_open_combined(m->kids[m->next_kid.fetch_add(1) % m->kids.size()], coeffs, n, t, stride, z, gamma, out_ys, out_p1);
+    std::lock_guard<std::mutex> lk(m->op_mu);
+    m->last_error = "kzg_open_combined: range-split multi-device contexts are not supported (use KZG_MULTI_REPLICATE_SRS)";
+    return KZG_ERR_INVALID_ARG;
+}
+
 // A multiproof: replicated SRS -> one device, as a single opening.  A range-split SRS would need a carry per root and
 // slice (the single-point recurrence above, k times): not supported.
 int multi_open_points(MultiState* m, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,

@@ -141,7 +141,10 @@ size_t kzg_srs_len(const kzg_ctx* ctx);
 int kzg_commit(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, uint64_t out_p1[18]);
 
 /* Same with scalars as n x 32 canonical little-endian bytes (< r), i.e. what Scalar::to_le_bytes
- * yields (reference src/scalar.rs:83-93) and what G1Point::mult feeds blst (src/curves.rs:93). */
+ * yields (reference src/scalar.rs:83-93) and what G1Point::mult feeds blst (src/curves.rs:93).
+ * Canonical input is what callers are expected to send, but it is not required: any 256-bit value is
+ * accepted and counts as its residue mod r (r, v + r, 2^256 - 1 commit to the same point as their
+ * reduced values; tests/test_srs_ingest_gpu.py pins this on both sort paths). */
 int kzg_commit_le_bytes(kzg_ctx* ctx, const uint8_t* scalars_le, size_t n, uint64_t out_p1[18]);
 
 /* Evaluation::generate_proof (reference src/polynomial.rs:260-269) fused on the device:

@@ -402,8 +402,8 @@ int drain_all(kzg_ctx* ctx) {
     return KZG_OK;
 }
 
-int srs_prepare(kzg_ctx* ctx, size_t n) {
-    if (n == 0 || n > 0x7fffffffu / 32) return KZG_ERR_INVALID_ARG;
+// the context gives up its SRS: nothing in flight, no table, n = 0 (the slots keep their workspaces for the next one)
+static int srs_release(kzg_ctx* ctx) {
     ctx->slots_ready = false;
     int rc = drain_all(ctx);
     if (rc) return rc;
@@ -418,6 +418,13 @@ int srs_prepare(kzg_ctx* ctx, size_t n) {
         ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
     }
     ctx->n = 0;
+    return KZG_OK;
+}
+
+int srs_prepare(kzg_ctx* ctx, size_t n) {
+    if (n == 0 || n > 0x7fffffffu / 32) return KZG_ERR_INVALID_ARG;
+    int rc = srs_release(ctx);
+    if (rc) return rc;
     // The opt-in NAF recoding wants a 255-level table (engine.h); it may take up to 60 % of the HBM that is free
     // now (KZG_TABLE_GB overrides), otherwise the windowed recoding with its ~15 levels is used.
     size_t free_b = 0, total_b = 0;
@@ -1976,6 +1983,14 @@ size_t host_batch_chunk(const kzg_ctx* ctx, size_t count, size_t n) {
 }  // extern "C"
 
 namespace kzg {
+
+int ctx_drop_srs(kzg_ctx* ctx) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n && !ctx->d_table) return KZG_OK;
+    quiesce(ctx, lk);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return srs_release(ctx);
+}
 
 void ctx_set_raw_partials(kzg_ctx* ctx, bool raw) {
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -331,6 +331,9 @@ namespace kzg {
 // A kid of a range-split context returns its partial sums UN-normalised (Jacobian X*ZZ, Y*ZZZ, ZZ of the XYZZ total:
 // two products instead of an inversion); the parent normalises once after the K-1 additions.
 void ctx_set_raw_partials(kzg_ctx* ctx, bool raw);
+// A kid of a multi-device context gives up its SRS (multi.hip: its slice is empty now, or a sibling's slice was refused):
+// kzg_srs_len(ctx) is 0 afterwards and every call that needs an SRS answers KZG_ERR_NO_SRS
+int ctx_drop_srs(kzg_ctx* ctx);
 // Host-pointer batches on ONE device: polynomial i (i < count) is the caller's polynomial first + i * step, its n
 // coefficients at coeffs + (first + i * step) * stride_coeffs blst_fr values, its result at out_p1s + 18 * (first + i *
 // step) (and statuses[first + i * step]).  Sub-batches flow through the context's stream slots so that the upload of

@@ -308,59 +308,61 @@ static void assign_ranges(MultiState* m, size_t n) {
     }
 }
 
-int multi_srs_generate(MultiState* m, const uint8_t secret_be[32], uint64_t first, size_t n) {
-    std::lock_guard<std::mutex> lk(m->op_mu);
+// One SRS load of the context: kid g loads its slice with load_slice(g).  A kid whose slice is empty gives up whatever it
+// held before, and when any slice is refused every kid does: the context then holds no SRS anywhere, instead of the
+// slices that happened to load (which kzg_msm_config and the kids' memory would still show).
+static int load_slices(MultiState* m, size_t n, const std::function<int(size_t)>& load_slice) {
     m->n = 0;
     assign_ranges(m, n);
     int rc = for_each_kid(m, [&](size_t g) {
-        if (m->hi[g] == m->lo[g]) return (int)KZG_OK;  // empty slice: the kid simply holds no SRS
-        return kzg_srs_generate_g1(m->kids[g], secret_be, first + m->lo[g], m->hi[g] - m->lo[g]);
+        if (m->hi[g] == m->lo[g]) return ctx_drop_srs(m->kids[g]);
+        return load_slice(g);
     });
-    if (rc == KZG_OK) m->n = n;
+    if (rc == KZG_OK) {
+        m->n = n;
+        return rc;
+    }
+    const std::string why = m->last_error;
+    (void)for_each_kid(m, [&](size_t g) { return ctx_drop_srs(m->kids[g]); });
+    m->last_error = why;
     return rc;
+}
+
+int multi_srs_generate(MultiState* m, const uint8_t secret_be[32], uint64_t first, size_t n) {
+    std::lock_guard<std::mutex> lk(m->op_mu);
+    return load_slices(m, n, [&](size_t g) { return kzg_srs_generate_g1(m->kids[g], secret_be, first + m->lo[g], m->hi[g] - m->lo[g]); });
 }
 
 int multi_srs_load(MultiState* m, const void* first_g1, size_t stride, size_t n) {
     std::lock_guard<std::mutex> lk(m->op_mu);
-    m->n = 0;
-    assign_ranges(m, n);
-    int rc = for_each_kid(m, [&](size_t g) {
-        if (m->hi[g] == m->lo[g]) return (int)KZG_OK;
+    return load_slices(m, n, [&](size_t g) {
         return kzg_srs_load_g1(m->kids[g], (const char*)first_g1 + m->lo[g] * stride, stride, m->hi[g] - m->lo[g]);
     });
-    if (rc == KZG_OK) m->n = n;
-    return rc;
 }
 
 int multi_srs_load_affine(MultiState* m, const void* affine_xy, size_t n) {
     std::lock_guard<std::mutex> lk(m->op_mu);
-    m->n = 0;
-    assign_ranges(m, n);
-    int rc = for_each_kid(m, [&](size_t g) {
-        if (m->hi[g] == m->lo[g]) return (int)KZG_OK;
+    return load_slices(m, n, [&](size_t g) {
         return kzg_srs_load_affine(m->kids[g], (const char*)affine_xy + m->lo[g] * 96, m->hi[g] - m->lo[g]);
     });
-    if (rc == KZG_OK) m->n = n;
-    return rc;
 }
 
 int multi_srs_load_compressed(MultiState* m, const uint8_t* compressed, size_t n, size_t* bad_index) {
     std::lock_guard<std::mutex> lk(m->op_mu);
     const size_t k = m->kids.size();
-    m->n = 0;
-    assign_ranges(m, n);
     std::vector<size_t> bad(k, (size_t)-1);
-    int rc = for_each_kid(m, [&](size_t g) {
-        if (m->hi[g] == m->lo[g]) return (int)KZG_OK;
+    int rc = load_slices(m, n, [&](size_t g) {
         return kzg_srs_load_compressed(m->kids[g], compressed + m->lo[g] * 48, m->hi[g] - m->lo[g], &bad[g]);
     });
-    if (bad_index)
-        for (size_t g = 0; g < k; g++)
-            if (bad[g] != (size_t)-1) {
-                *bad_index = m->lo[g] + bad[g];
-                break;
-            }
-    if (rc == KZG_OK) m->n = n;
+    // the slices are in point order: the first kid that met a malformed point met the least one (a kid names its own
+    // least, counted from the start of its slice)
+    for (size_t g = 0; g < k; g++)
+        if (bad[g] != (size_t)-1) {
+            const size_t at = m->lo[g] + bad[g];
+            if (bad_index) *bad_index = at;
+            m->last_error = "compressed point " + std::to_string(at) + " is malformed (device slice " + std::to_string(g) + ")";
+            break;
+        }
     return rc;
 }
 

@@ -237,7 +237,9 @@ int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[
  *   proof is kzg_open's bit for bit, whatever gamma is.
  * Cost: one streaming pass over the t n coefficients (k_combine_eval: F and the t values, every coefficient read once),
  *   then the scan and the MSM of ONE opening -- where kzg_open_batch runs t scans and t MSMs.  Measured at n = 2^20 on
- *   resident inputs (profiles/r14_open_combined.jsonl): not measured yet (tests/perf_open_combined.py writes that file; derived: t - 1 MSMs of about 2.4 ms replaced by streaming passes).
+ *   resident inputs (profiles/r14_open_combined.jsonl, medians of 3): 3.03 / 2.89 / 3.09 / 4.21 ms per call at t = 1 / 4 / 16 /
+ *   64, against 3.01 / 10.4 / 40.8 / 160.8 ms for t x kzg_open_submit through the slots (0.99 / 3.6 / 13.2 / 38.1 x);
+ *   k_combine_eval with its finish kernel takes 0.06 / 0.13 / 0.42 / 1.49 ms of it, 1.08 - 1.47 TB/s of algorithmic bytes.
  * The host-pointer call uploads and combines at most kzg_max_batch(ctx) polynomials per pass (F is carried between the
  *   passes; the result does not depend on the grouping) and is bound by the upload; the resident call takes all t in one
  *   launch.
@@ -268,6 +270,69 @@ int kzg_combine_claims(const uint64_t* commitments_p1, const uint64_t* ys, size_
                        uint64_t out_commitment_p1[18], uint64_t out_y[4]);
 int kzg_verify_combined(const uint64_t* commitments_p1, const uint64_t* ys, size_t t, const uint64_t z[4],
                         const uint64_t gamma[4], const uint64_t proof_p1[18], const uint64_t s_g2[36], int* valid);
+
+/* ---- openings at several point sets: polynomial i on set S_g(i), one G1 element ---------------
+ * The general last round of a proof-system prover: PLONK opens most polynomials at z and the permutation polynomial at
+ * z w; systems with custom gates open groups at {z}, {z, z w}, {z, z w, z w^-1}.  One kzg_open_combined per point set costs
+ * one MSM and one G1 element per set; these calls prove "polynomial i takes these values on S_(set_of[i])" for all i with
+ * ONE MSM and ONE element (Boneh-Drake-Fisch-Gabizon 2020, the first scheme): the proof is [h(s)]G1 with
+ *        h = sum_g (F_g - R_g) / Z_(S_g),      F_g = sum_{i in set g} gamma^i P_i,  R_g its interpolant on S_g.
+ * kzg_open_points (t = 1, m = 1) and kzg_open_combined (one set of one point) are special cases, with the same proof bytes.
+ * SOUNDNESS: gamma has to be a challenge fixed AFTER the commitments and the values (and the points after the
+ * commitments), as the protocol's transcript defines it.  Nothing is hashed here: these calls take the points and gamma
+ * as given.
+ * Layout: polynomials as for kzg_open_combined (equal n, polynomial i at coeffs + 4 i stride, shorter ones padded with
+ *   zeros).  set_of: t indices below m.  set_len: the m set sizes.  zs: sum(set_len) x blst_fr (Montgomery), set after set.
+ *   The weight of polynomial i is gamma^i (i its index in the call, gamma^0 = 1 also for gamma = 0).  out_ys: polynomial
+ *   after polynomial, the set_len[set_of[i]] values of polynomial i in its set's point order (sum_i set_len[set_of[i]] x 4).
+ * Errors, in this order: a NULL pointer other than the coefficients; t outside [1, KZG_MAX_COMBINE]; m outside [1, KZG_MAX_SETS]; an empty set (or one
+ *   of more than KZG_MAX_SET_POINTS points); set_of[i] >= m; a set no polynomial uses; a point not below r; two equal points
+ *   within one set (the same point in several sets, at any position, is the normal case); more than KZG_MAX_SET_POINTS
+ *   distinct points over all sets; gamma not below r; NULL coefficients with n > 0; too many coefficients; stride < n with t > 1 -- all
+ *   KZG_ERR_INVALID_ARG, and kzg_last_error says which.  There is no claim, hence no remainder error.  n' = h's length
+ *   without trailing zero coefficients: n' = 0 gives infinity (n <= min |S_g|, or h vanishing by cancellation);
+ *   n' > kzg_srs_len gives KZG_ERR_DEGREE_TOO_HIGH.  deg h = n - 1 - min |S_g| when nothing cancels.
+ * Cost: with T the distinct points over all sets, one streaming pass per point p of T over the polynomials opened at p
+ *   (k_sets_combine: G_p = sum gamma^i w_(g(i),p) P_i and the values P_i(p), every such coefficient read once), |T| suffix
+ *   scans summed into h (k_sets_chunks / k_sets_apply), ONE MSM.  Measured at n = 2^20 on resident inputs in PLONK's
+ *   shape (nine polynomials at z, one at z w; profiles/r15_open_sets.jsonl): 3.28 ms per call (3.17-3.40 over nine alternated repetitions) against 5.33 ms
+ *   (5.29-5.62) for kzg_open_combined_submit of the nine plus kzg_open_submit of the tenth in two slots, both in flight
+ *   -- 1.63 x, a difference of 2.06 ms against a min-max spread of 0.33 ms of the two-call route; of the call, 0.32 ms
+ *   are the two passes, 0.21 ms the two scans and 2.65 ms the MSM.  Sixteen polynomials over {z}, {z, z w},
+ *   {z, z w, z / w}: 3.66 ms (passes 0.74 ms, scans 0.28 ms, MSM 2.47 ms).
+ * The host-pointer call uploads at most kzg_max_batch(ctx) polynomials at a time (every G_p is carried between the groups;
+ *   the result does not depend on the grouping); the resident call runs each pass over all its polynomials in one launch.
+ *   Workspace per slot, grown on demand: |T| n values for the G_p.
+ * Multi-device contexts: a replicated SRS forwards the call to one device; a range-split SRS returns
+ *   KZG_ERR_INVALID_ARG (kzg_last_error says why).  kzg_quotient_sets runs on devices[0]. */
+#define KZG_MAX_SETS 8          /* point sets per call */
+#define KZG_MAX_SET_POINTS 16   /* distinct points over all sets, |T| */
+/* host pointers, synchronous; takes one of the context's stream slots like kzg_open */
+int kzg_open_sets(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t t, size_t stride_coeffs,
+                  const uint32_t* set_of /* t */, const uint32_t* set_len /* m */, size_t m,
+                  const uint64_t* zs /* sum(set_len) x 4, set after set */, const uint64_t gamma[4], uint64_t* out_ys,
+                  uint64_t out_p1[18]);
+/* d_coeffs is a DEVICE pointer; collected by kzg_wait_sets, which returns the values of the slot's job and the proof
+ * (single-device contexts only).  kzg_wait and kzg_wait_combined refuse such a slot and leave the job in it; kzg_wait_sets
+ * refuses every other kind.  With kzg_set_timing, kzg_get_combine_ms reports the passes and kzg_get_times the scans
+ * (quotient_ms) and the MSM. */
+int kzg_open_sets_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, size_t t, size_t stride_coeffs,
+                         const uint32_t* set_of, const uint32_t* set_len, size_t m, const uint64_t* zs,
+                         const uint64_t gamma[4]);
+int kzg_wait_sets(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]);
+/* test hook, no SRS: h's coefficients (room for n - 1), *out_hn = length without trailing zeros, and the values */
+int kzg_quotient_sets(kzg_ctx* ctx, const uint64_t* coeffs_fr_mont, size_t n, size_t t, size_t stride_coeffs,
+                      const uint32_t* set_of, const uint32_t* set_len, size_t m, const uint64_t* zs, const uint64_t gamma[4],
+                      uint64_t* out_ys, uint64_t* out_h, size_t* out_hn);
+/* Host only, no context.  Per set g: v_(g,p) = sum_{i in g} gamma^i y_(i,p), R_g their interpolant, A_g = sum_{i in g}
+ * gamma^i C_i - [R_g(s)]G1 (SRS G1 entries [0, max |S_g|), as kzg_verify_points takes them), B_g = [Z_(T \ S_g)(s)]G2 and
+ * B_T = [Z_T(s)]G2 (the G2 powers [s^j]G2, j <= |T|).  *valid = 1 iff prod_g e(A_g, B_g) == e(proof, B_T): one Miller loop
+ * over m + 1 <= 9 pairs, one final exponentiation, t G1 and at most (m + 1)(|T| + 1) G2 scalar multiplications.  ys in
+ * out_ys' layout.  KZG_ERR_INVALID_ARG for the argument errors above, a value not below r, a G1 input off the curve or a G2
+ * input off the twist (no subgroup checks, as kzg_verify_points). */
+int kzg_verify_sets(const uint64_t* commitments_p1, size_t t, const uint32_t* set_of, const uint32_t* set_len, size_t m,
+                    const uint64_t* zs, const uint64_t* ys, const uint64_t gamma[4], const uint64_t proof_p1[18],
+                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
 
 /* ---- polynomials in evaluation form: NTT over power-of-two domains ------------------------
  * Most KZG data (blob-style commitments, proof systems) holds a polynomial as its values over a subgroup of roots of

@@ -269,6 +269,60 @@ inline bool verify_combined(const CombinedOpening& opening, const std::vector<G1
     return valid == 1;
 }
 
+// Openings at several point sets (kzg_open_sets): polynomial i (n coefficients at coeffs[i * n ..]) is opened on
+// sets[set_of[i]], all of them with ONE proof.  results[i]: its values in the set's point order.  gamma has to be the challenge
+// the protocol draws after the commitments and the values; nothing is hashed here.
+struct SetsOpening {
+    std::vector<uint32_t> set_of;
+    std::vector<std::vector<Scalar>> sets;
+    Scalar gamma;
+    std::vector<std::vector<Scalar>> results;
+    G1Point proof;
+    std::vector<uint32_t> set_len() const {
+        std::vector<uint32_t> out;
+        for (const auto& s : sets) out.push_back((uint32_t)s.size());
+        return out;
+    }
+    std::vector<Scalar> flat_points() const {
+        std::vector<Scalar> out;
+        for (const auto& s : sets) out.insert(out.end(), s.begin(), s.end());
+        return out;
+    }
+};
+inline SetsOpening open_sets(const SetupArtifacts& setup, const std::vector<Scalar>& coeffs, size_t n, std::vector<uint32_t> set_of,
+                             std::vector<std::vector<Scalar>> sets, const Scalar& gamma) {
+    SetsOpening out{std::move(set_of), std::move(sets), gamma, {}, {}};
+    const std::vector<uint32_t> len = out.set_len();
+    const std::vector<Scalar> zs = out.flat_points();
+    size_t total = 0;
+    for (uint32_t g : out.set_of) total += g < len.size() ? len[g] : 0;
+    std::vector<Scalar> ys(total ? total : 1);
+    check(kzg_open_sets(setup.ctx(), reinterpret_cast<const uint64_t*>(coeffs.data()), n, out.set_of.size(), n, out.set_of.data(),
+                        len.data(), len.size(), reinterpret_cast<const uint64_t*>(zs.data()), gamma.l.data(),
+                        reinterpret_cast<uint64_t*>(ys.data()), out.proof.p1.data()), setup.ctx());
+    size_t at = 0;
+    for (uint32_t g : out.set_of) {
+        out.results.emplace_back(ys.begin() + at, ys.begin() + at + len[g]);
+        at += len[g];
+    }
+    return out;
+}
+// host-side check against the commitments; g1: SRS entries [0, max |S_g|) (SetupArtifacts::read_g1), g2: [s^j]G2 for
+// j <= |T|, T the distinct points over all sets (SetupArtifacts::g2_at)
+inline bool verify_sets(const SetsOpening& opening, const std::vector<G1Point>& commitments, const std::vector<G1Point>& g1,
+                        const std::vector<std::array<uint64_t, 36>>& g2) {
+    const std::vector<uint32_t> len = opening.set_len();
+    const std::vector<Scalar> zs = opening.flat_points();
+    std::vector<Scalar> ys;
+    for (const auto& row : opening.results) ys.insert(ys.end(), row.begin(), row.end());
+    int valid = 0;
+    check(kzg_verify_sets(reinterpret_cast<const uint64_t*>(commitments.data()), commitments.size(), opening.set_of.data(), len.data(),
+                          len.size(), reinterpret_cast<const uint64_t*>(zs.data()), reinterpret_cast<const uint64_t*>(ys.data()),
+                          opening.gamma.l.data(), opening.proof.p1.data(), g1.data(), sizeof(G1Point), g2.data(), sizeof(g2[0]),
+                          &valid), nullptr);
+    return valid == 1;
+}
+
 // Every cell of the domain of N = 2^log_domain points and its multiproof (kzg_cells_and_proofs): cell j holds the
 // l = 2^log_cell values P(w_N^(j + (N/l) i)), i < l, at values[j l + i]; proofs[j] is kzg_open_points' proof for them.
 struct Cells {

@@ -20,6 +20,7 @@ __all__ = [
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "domain_root",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
+    "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +64,7 @@ ABI_SYMBOLS = [
     "kzg_srs_update", "kzg_srs_verify", "kzg_srs_verify_lincomb", "kzg_g2_mul", "kzg_srs_verify_update",
     "kzg_open_combined", "kzg_open_combined_submit", "kzg_wait_combined", "kzg_get_combine_ms", "kzg_combine_polys",
     "kzg_evaluate_batch_at", "kzg_combine_claims", "kzg_verify_combined",
+    "kzg_open_sets", "kzg_open_sets_submit", "kzg_wait_sets", "kzg_quotient_sets", "kzg_verify_sets",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -70,6 +72,8 @@ KZG_ORDER_NATURAL = 0
 KZG_ORDER_BIT_REVERSED = 1
 KZG_MAX_OPEN_POINTS = 64
 KZG_MAX_COMBINE = 256
+KZG_MAX_SETS = 8
+KZG_MAX_SET_POINTS = 16
 KZG_NTT_MAX_LOG = 22
 KZG_MAX_CELL_LOG = 6
 
@@ -206,6 +210,11 @@ def load_library():
         "kzg_evaluate_batch_at": (i, [vp, vp, sz, sz, sz, vp, vp]),
         "kzg_combine_claims": (i, [vp, vp, sz, vp, vp, vp]),
         "kzg_verify_combined": (i, [vp, vp, sz, vp, vp, vp, vp, C.POINTER(i)]),
+        "kzg_open_sets": (i, [vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "kzg_open_sets_submit": (i, [vp, i, vp, sz, sz, sz, vp, vp, sz, vp, vp]),
+        "kzg_wait_sets": (i, [vp, i, vp, vp]),
+        "kzg_quotient_sets": (i, [vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_verify_sets": (i, [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -608,6 +617,43 @@ class Engine:
         ys = np.zeros((t, 4), dtype=np.uint64)
         _check(self._lib.kzg_evaluate_batch_at(self._h, _ptr(flat), n, t, stride, _ptr(zl), _ptr(ys)), self._h)
         return [Scalar.from_limbs(ys[i]) for i in range(t)]
+
+    # -- openings at several point sets: polynomial i on sets[set_of[i]], one proof (sets: lists of Scalar; gamma: Scalar) --
+    def open_sets_limbs(self, polys, set_of, sets, gamma, stride=None):
+        """kzg_open_sets: returns (ys, proof), ys[i] the values of polynomial i on its set, in the set's point order"""
+        flat, n, t, stride = self._combine_block(polys, stride)
+        so, sl, zl = _sets_arrays(set_of, sets)
+        assert len(set_of) == t
+        ys = np.zeros((_sets_value_count(set_of, sets), 4), dtype=np.uint64)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_open_sets(self._h, _ptr(flat), n, t, stride, _ptr(so), _ptr(sl), len(sets), _ptr(zl),
+                                       _ptr(gamma.limbs()), _ptr(ys), _ptr(out)), self._h)
+        return _sets_split_values(ys, set_of, sets), G1Point(out)
+
+    def open_sets_submit(self, slot, dptr, n, t, set_of, sets, gamma, stride=None):
+        so, sl, zl = _sets_arrays(set_of, sets)
+        assert len(set_of) == t
+        _check(self._lib.kzg_open_sets_submit(self._h, slot, C.c_void_p(dptr), n, t, n if stride is None else stride, _ptr(so),
+                                              _ptr(sl), len(sets), _ptr(zl), _ptr(gamma.limbs())), self._h)
+
+    def wait_sets(self, slot, set_of, sets):
+        """kzg_wait_sets: (ys, proof) of the slot's job; set_of, sets as submitted (they give the shape of ys)"""
+        ys = np.zeros((_sets_value_count(set_of, sets), 4), dtype=np.uint64)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_wait_sets(self._h, slot, _ptr(ys), _ptr(out)), self._h)
+        return _sets_split_values(ys, set_of, sets), G1Point(out)
+
+    def quotient_sets_limbs(self, polys, set_of, sets, gamma, stride=None):
+        """kzg_quotient_sets: (ys, h) with h the quotient's coefficients without trailing zeros, an (n', 4) array of images"""
+        flat, n, t, stride = self._combine_block(polys, stride)
+        so, sl, zl = _sets_arrays(set_of, sets)
+        assert len(set_of) == t
+        ys = np.zeros((_sets_value_count(set_of, sets), 4), dtype=np.uint64)
+        h = np.zeros((max(n - 1, 1), 4), dtype=np.uint64)
+        hn = C.c_size_t(0)
+        _check(self._lib.kzg_quotient_sets(self._h, _ptr(flat), n, t, stride, _ptr(so), _ptr(sl), len(sets), _ptr(zl),
+                                           _ptr(gamma.limbs()), _ptr(ys), _ptr(h), C.byref(hn)), self._h)
+        return _sets_split_values(ys, set_of, sets), h[: hn.value].copy()
 
     # -- every cell of the domain of N = 2^log_domain points and its multiproof (cells of 2^log_cell points) --
     def _cells(self, fn, values, log_domain, log_cell):
@@ -1247,6 +1293,46 @@ def verify_points(commitment, proof, zs, ys, setup_g1, setup_g2):
     ok = C.c_int(0)
     _check(lib.kzg_verify_points(_ptr(commitment.p1), _ptr(proof.p1), _ptr(_scalar_rows(zs)), _ptr(_scalar_rows(ys)), k,
                                  _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def _sets_arrays(set_of, sets):
+    """(set_of as uint32, the set sizes as uint32, the points set after set as k x 4 uint64)"""
+    so = np.ascontiguousarray(list(set_of) if len(set_of) else [0], dtype=np.uint32)
+    sl = np.ascontiguousarray([len(s) for s in sets] if len(sets) else [0], dtype=np.uint32)
+    return so, sl, _scalar_rows([z for s in sets for z in s])
+
+
+def _sets_value_count(set_of, sets):
+    return max(sum(len(sets[g]) for g in set_of if 0 <= g < len(sets)), 1)
+
+
+def _sets_split_values(ys, set_of, sets):
+    out, at = [], 0
+    for g in set_of:
+        out.append([Scalar.from_limbs(ys[at + j]) for j in range(len(sets[g]))])
+        at += len(sets[g])
+    return out
+
+
+def verify_sets(commitments, set_of, sets, ys, gamma, proof, setup_g1, setup_g2):
+    """kzg_verify_sets: prod_g e(A_g, [Z_(T \\ S_g)(s)]G2) == e(proof, [Z_T(s)]G2) on the host.  ys[i]: the values of
+    polynomial i on sets[set_of[i]]; setup_g1: at least max |S_g| blst_p1 rows ([s^j]G1); setup_g2: at least |T| + 1 blst_p2
+    rows ([s^j]G2, j <= |T|, T the distinct points over all sets), e.g. from srs_g2_at.  gamma has to be the challenge the
+    protocol draws AFTER the commitments and the values; nothing is hashed here."""
+    lib = load_library()
+    t = len(commitments)
+    assert len(set_of) == t and len(ys) == t
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    distinct = len({z.v for s in sets for z in s})
+    assert g1.shape[0] >= max(len(s) for s in sets) and g2.shape[0] >= distinct + 1
+    cs = np.ascontiguousarray(np.stack([c.p1 for c in commitments]) if t else np.zeros((1, 18)), dtype=np.uint64)
+    so, sl, zl = _sets_arrays(set_of, sets)
+    yl = _scalar_rows([y for row in ys for y in row])
+    ok = C.c_int(0)
+    _check(lib.kzg_verify_sets(_ptr(cs), t, _ptr(so), _ptr(sl), len(sets), _ptr(zl), _ptr(yl), _ptr(gamma.limbs()),
+                               _ptr(proof.p1), _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

@@ -69,7 +69,8 @@ struct ReducePlan {
 // context mutex is NOT held: N caller threads occupy N slots and their jobs pipeline like explicit submits do.
 enum SlotKind { SLOT_IDLE = 0, SLOT_COMMIT = 1, SLOT_OPEN = 2, SLOT_TRIVIAL = 3, SLOT_COMMIT_BATCH = 4, SLOT_OPEN_BATCH = 5, SLOT_RESERVED = 6,
                 SLOT_OPEN_POINTS = 7 /* a multiproof: trivial or not, collected by kzg_wait */,
-                SLOT_OPEN_COMBINED = 8 /* a combined opening: trivial or not, collected by kzg_wait_combined */ };
+                SLOT_OPEN_COMBINED = 8 /* a combined opening: trivial or not, collected by kzg_wait_combined */,
+                SLOT_OPEN_SETS = 9 /* an opening at several point sets: trivial or not, collected by kzg_wait_sets */ };
 
 struct Slot {
     hipStream_t stream = nullptr;
@@ -134,6 +135,20 @@ struct Slot {
     size_t cmb_t = 0;              // polynomials of the job in flight
     hipEvent_t cmb_ev[2] = {};     // timed jobs: around the (last) combination pass
     float combine_ms = 0;
+    // openings at several point sets (kzg_open_sets): the pass tables (66 powers per distinct point,
+    // then one multiplier per (point, polynomial opened there)) and the selection lists go through pinned staging areas to
+    // the device like the table above; the values land in pinned mapped memory in pass order and sets_vmap says where each
+    // entry of out_ys sits; d_sg: the G_p, |T| x n values, grown on demand.  The passes share d_cpart / d_cin, the scans the
+    // multiproof's root and aggregate buffers.
+    void* h_stab = nullptr;
+    void* d_stab = nullptr;
+    uint32_t* h_ssel = nullptr;
+    uint32_t* d_ssel = nullptr;
+    uint32_t* h_svals = nullptr;
+    uint32_t* d_svals = nullptr;
+    uint32_t* d_sg = nullptr;
+    size_t sg_coeffs = 0;
+    std::vector<uint32_t> sets_vmap;
     // cells of a domain (kzg_cells_and_proofs): P for the whole call in d_cpoly (read by the sub-batches of every slot the call
     // holds, after cells_ev), the chunk aggregates of the cell quotients in d_cagg
     uint32_t* d_cpoly = nullptr;
@@ -748,7 +763,7 @@ int kzg_ctx_create(int device, kzg_ctx** out) {
         ctx->small_lds_bytes = small_msm_lds_bytes();
     else
         (void)hipGetLastError();  // stays at 48 KiB: two workgroups may then share a CU (slower, not wrong)
-    if (!poly_prepare_device() || !points_prepare_device()) {
+    if (!poly_prepare_device() || !points_prepare_device() || !sets_prepare_device()) {
         delete ctx;
         return KZG_ERR_HIP;  // the quotient kernels could not be launched on this device
     }
@@ -785,6 +800,12 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
         hipFree(s.d_ctab);
         hipFree(s.d_cpart);
         hipFree(s.d_cin);
+        if (s.h_stab) hipHostFree(s.h_stab);
+        if (s.h_ssel) hipHostFree(s.h_ssel);
+        if (s.h_svals) hipHostFree(s.h_svals);
+        hipFree(s.d_stab);
+        hipFree(s.d_ssel);
+        hipFree(s.d_sg);
         for (auto& e : s.cmb_ev)
             if (e) hipEventDestroy(e);
         hipFree(s.d_cpoly);
@@ -1266,6 +1287,10 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
         ctx->last_error = "kzg_wait on a slot that holds a combined opening (use kzg_wait_combined)";
         return KZG_ERR_INVALID_ARG;  // the job stays in the slot
     }
+    if (s.kind == SLOT_OPEN_SETS) {
+        ctx->last_error = "kzg_wait on a slot that holds an opening at several point sets (use kzg_wait_sets)";
+        return KZG_ERR_INVALID_ARG;  // the job stays in the slot
+    }
     if (s.kind == SLOT_RESERVED) return KZG_ERR_BUSY;  // a synchronous call on another thread owns it
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SlotKind kind = s.kind;
@@ -1688,8 +1713,7 @@ int ensure_combined(kzg_ctx* ctx, Slot& s, size_t n, size_t t_pass, size_t stage
 }
 // every multiplier of one call: the 16 + 16 tables and the stride of z (a lane's power inside a tile) and of W = z^2048
 // (a tile's power inside the polynomial), then gamma^i -- 66 + t host products -- copied to the slot's table on its stream
-int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& gamma, size_t t) {
-    Fr30* tab = (Fr30*)s.h_ctab;
+void combine_fill_powers(Fr30* tab, const hf::Fr& z) {  // entries [0, kCombineTabGamma)
     auto fill = [&](const hf::Fr& x, uint32_t at_a, uint32_t at_b, uint32_t at_256) {
         const hf::Fr x16 = hf::fr_pow(x, 16);
         hf::Fr a = hf::kFrOne, b = hf::kFrOne;
@@ -1704,6 +1728,10 @@ int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& 
     };
     const hf::Fr z256 = fill(z, kCombineTabPa, kCombineTabPb, kCombineTabZ256);
     fill(hf::fr_pow(z256, kCombineTile / 256), kCombineTabWa, kCombineTabWb, kCombineTabW256);
+}
+int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& gamma, size_t t) {
+    Fr30* tab = (Fr30*)s.h_ctab;
+    combine_fill_powers(tab, z);
     hf::Fr g = hf::kFrOne;
     for (size_t i = 0; i < t; i++) {
         tab[kCombineTabGamma + i] = fr30_arg_from_mont256(g);
@@ -1959,6 +1987,392 @@ int kzg_evaluate_batch_at(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t
     if (!ctx || !z || !out_ys) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) return kzg_evaluate_batch_at(multi_kid(ctx->multi, 0), coeffs, n, t, stride, z, out_ys);  // needs no SRS
     return combined_hook(ctx, "kzg_evaluate_batch_at", coeffs, n, t, stride, z, nullptr, nullptr, out_ys);
+}
+
+// ---- openings at several point sets: polynomial i on set set_of[i], one proof ----------------------
+namespace {
+constexpr uint32_t kSetsMultBase = kSetsMaxPoints * kCombineTabGamma;  // the pass tables: 66 powers per point, then the multipliers
+constexpr uint32_t kSetsTabLen = kSetsMultBase + kSetsMaxValues;
+static_assert(KZG_MAX_SETS == kSetsMax && KZG_MAX_SET_POINTS == kSetsMaxPoints, "header and engine disagree");
+static_assert(KZG_MAX_SET_POINTS <= KZG_MAX_OPEN_POINTS, "the scans use the multiproof's root buffers");
+
+// what the arrays of a call say, checked: the distinct points T, every set's weights, and per point of T the list of
+// polynomials opened there with their multipliers gamma^i w_(g(i),p)
+struct SetsPlan {
+    size_t t = 0, m = 0, npts = 0, nvals = 0, min_len = 0, max_len = 0;
+    hf::Fr gamma;
+    hf::Fr pts[KZG_MAX_SET_POINTS];                 // T, in order of first appearance
+    uint32_t set_first[KZG_MAX_SETS] = {};          // first entry of set g in zs
+    uint32_t set_len[KZG_MAX_SETS] = {};
+    uint8_t pt_of[KZG_MAX_SETS][KZG_MAX_SET_POINTS];  // index in T of point j of set g
+    int8_t pos[KZG_MAX_SETS][KZG_MAX_SET_POINTS];     // position of point r of T in set g, or -1
+    hf::Fr w[KZG_MAX_SETS][KZG_MAX_SET_POINTS];       // w_(g,p) by position in the set
+    uint32_t off[KZG_MAX_SET_POINTS + 1] = {};      // the list of point r: sel[off[r] .. off[r + 1])
+    std::vector<uint32_t> set_of;                   // t
+    std::vector<uint32_t> val_first;                // first entry of polynomial i in out_ys
+    std::vector<uint32_t> sel;                      // polynomials opened at point r, increasing
+    std::vector<hf::Fr> mult;                       // gamma^i w_(g(i),p), parallel to sel
+    std::vector<uint32_t> vmap;                     // entry e of out_ys sits at pass-order index vmap[e]
+};
+// t, m and the pointers are the caller's business; everything else about the sets is refused here, in the header's order
+bool sets_plan(SetsPlan& P, std::string& why, size_t t, const uint32_t* set_of, const uint32_t* set_len, size_t m,
+               const uint64_t* zs, const uint64_t* gamma) {
+    P.t = t;
+    P.m = m;
+    uint32_t at = 0;
+    for (size_t g = 0; g < m; g++) {
+        if (set_len[g] == 0) return why = "an empty point set", false;
+        if (set_len[g] > KZG_MAX_SET_POINTS) return why = "a set of more than KZG_MAX_SET_POINTS points", false;
+        P.set_first[g] = at;
+        P.set_len[g] = set_len[g];
+        at += set_len[g];
+    }
+    bool used[KZG_MAX_SETS] = {};
+    P.set_of.assign(set_of, set_of + t);
+    for (size_t i = 0; i < t; i++) {
+        if (set_of[i] >= m) return why = "set_of names a set that does not exist", false;
+        used[set_of[i]] = true;
+    }
+    for (size_t g = 0; g < m; g++)
+        if (!used[g]) return why = "a point set no polynomial is opened on", false;
+    P.npts = 0;
+    std::memset(P.pos, -1, sizeof P.pos);
+    P.min_len = KZG_MAX_SET_POINTS;
+    P.max_len = 0;
+    for (size_t g = 0; g < m; g++) {
+        hf::Fr z[KZG_MAX_SET_POINTS];
+        const size_t k = P.set_len[g];
+        for (size_t j = 0; j < k; j++)
+            if (!fr_arg_below_r(zs + 4 * (P.set_first[g] + j), &z[j])) return why = "a point is not below r", false;
+        if (!hf::fr_point_weights(z, k, P.w[g])) return why = "two equal points within one set", false;
+        for (size_t j = 0; j < k; j++) {
+            size_t r = 0;
+            while (r < P.npts && std::memcmp(P.pts[r].l, z[j].l, 32) != 0) r++;
+            if (r == P.npts) {
+                if (P.npts == KZG_MAX_SET_POINTS) return why = "more than KZG_MAX_SET_POINTS distinct points", false;
+                P.pts[P.npts++] = z[j];
+            }
+            P.pt_of[g][j] = (uint8_t)r;
+            P.pos[g][r] = (int8_t)j;
+        }
+        P.min_len = std::min(P.min_len, k);
+        P.max_len = std::max(P.max_len, k);
+    }
+    if (!fr_arg_below_r(gamma, &P.gamma)) return why = "gamma is not below r", false;
+    P.val_first.resize(t);
+    P.nvals = 0;
+    for (size_t i = 0; i < t; i++) {
+        P.val_first[i] = (uint32_t)P.nvals;
+        P.nvals += P.set_len[set_of[i]];
+    }
+    std::vector<hf::Fr> gpow(t);
+    hf::Fr gp = hf::kFrOne;
+    for (size_t i = 0; i < t; i++) {
+        gpow[i] = gp;
+        gp = hf::fr_mul(gp, P.gamma);
+    }
+    P.sel.clear();
+    P.mult.clear();
+    P.vmap.assign(P.nvals, 0);
+    for (size_t r = 0; r < P.npts; r++) {
+        P.off[r] = (uint32_t)P.sel.size();
+        for (size_t i = 0; i < t; i++) {
+            const uint32_t g = set_of[i];
+            const int j = P.pos[g][r];
+            if (j < 0) continue;
+            P.vmap[P.val_first[i] + j] = (uint32_t)P.sel.size();
+            P.sel.push_back((uint32_t)i);
+            P.mult.push_back(hf::fr_mul(gpow[i], P.w[g][j]));
+        }
+    }
+    P.off[P.npts] = (uint32_t)P.sel.size();
+    return true;
+}
+// the arguments every prover call shares
+int sets_check(kzg_ctx* ctx, const char* what, const void* coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+               const uint32_t* set_len, size_t m, const uint64_t* zs, const uint64_t* gamma, SetsPlan& plan) {
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (t < 1 || t > KZG_MAX_COMBINE) return invalid("t must be in [1, KZG_MAX_COMBINE]");
+    if (m < 1 || m > KZG_MAX_SETS) return invalid("m must be in [1, KZG_MAX_SETS]");
+    std::string why;
+    if (!sets_plan(plan, why, t, set_of, set_len, m, zs, gamma)) return invalid(why);
+    if (!coeffs && n) return invalid("null coefficients");
+    if (n > kMaxCoefficients) return invalid("too many coefficients");
+    if (t > 1 && stride < n) return invalid("stride below n");
+    return KZG_OK;
+}
+
+// the slot's buffers for |T| = npts points over n coefficients (slot basics already there)
+int ensure_sets(kzg_ctx* ctx, Slot& s, size_t n, size_t npts) {
+    if (!s.h_stab) HIP_TRY(ctx, hipHostMalloc(&s.h_stab, kSetsTabLen * sizeof(Fr30), hipHostMallocDefault));
+    if (!s.d_stab) HIP_TRY(ctx, hipMalloc(&s.d_stab, kSetsTabLen * sizeof(Fr30)));
+    if (!s.h_ssel) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_ssel, kSetsMaxValues * 4, hipHostMallocDefault));
+    if (!s.d_ssel) HIP_TRY(ctx, hipMalloc((void**)&s.d_ssel, kSetsMaxValues * 4));
+    if (!s.h_svals) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&s.h_svals, kSetsMaxValues * 32, hipHostMallocMapped));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_svals, s.h_svals, 0));
+    }
+    if (npts * n > s.sg_coeffs) {
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        hipFree(s.d_sg);
+        s.d_sg = nullptr;
+        s.sg_coeffs = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&s.d_sg, npts * n * 32));
+        s.sg_coeffs = npts * n;
+    }
+    return KZG_OK;
+}
+int sets_job_start(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    s.timing = ctx->timing;
+    s.combine_ms = 0;
+    std::memset(&s.times, 0, sizeof s.times);
+    int rc = ensure_combined(ctx, s, 0, 0, 0);
+    if (rc == KZG_OK) rc = ensure_sets(ctx, s, 0, 0);
+    if (rc == KZG_OK) std::memset(s.h_svals, 0, 32 * plan.nvals);  // (the slot holds no job in flight)
+    return rc;
+}
+// every buffer of a job whose passes take at most t_pass polynomials; stage_coeffs as in ensure_combined
+int sets_ensure_all(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n, size_t t_pass, size_t stage_coeffs) {
+    int rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = ensure_points(ctx, s, n, plan.npts);
+    if (rc == KZG_OK) rc = ensure_combined(ctx, s, n, t_pass, stage_coeffs);
+    if (rc == KZG_OK) rc = ensure_sets(ctx, s, n, plan.npts);
+    return rc;
+}
+// the multipliers of one call -- 66 host products per distinct point, the multipliers and the lists as planned -- copied to
+// the slot's tables on its stream
+int sets_upload_tables(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
+    Fr30* tab = (Fr30*)s.h_stab;
+    for (size_t r = 0; r < plan.npts; r++) combine_fill_powers(tab + r * kCombineTabGamma, plan.pts[r]);
+    for (size_t e = 0; e < plan.sel.size(); e++) {
+        tab[kSetsMultBase + e] = fr30_arg_from_mont256(plan.mult[e]);
+        s.h_ssel[e] = plan.sel[e];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_stab, s.h_stab, (kSetsMultBase + plan.sel.size()) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_ssel, s.h_ssel, plan.sel.size() * 4, hipMemcpyHostToDevice, s.stream));
+    return KZG_OK;
+}
+// The passes over polynomials first .. first + cnt (device memory, polynomial `first` at d_coeffs): one per distinct point
+// that one of them is opened at.  A point's list is sorted, so these polynomials are a run [j0, j1) of it; written[r] says
+// whether G_r holds the sum of earlier calls (carried) or nothing yet.
+int sets_passes(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const uint32_t* d_coeffs, size_t n, size_t stride, size_t first,
+                size_t cnt, bool* written) {
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
+    for (size_t r = 0; r < plan.npts; r++) {
+        const auto lo = plan.sel.begin() + plan.off[r], hi = plan.sel.begin() + plan.off[r + 1];
+        const size_t j0 = std::lower_bound(lo, hi, (uint32_t)first) - plan.sel.begin();
+        const size_t j1 = std::lower_bound(lo, hi, (uint32_t)(first + cnt)) - plan.sel.begin();
+        if (j0 == j1) continue;
+        launch_sets_combine(s.stream, d_coeffs, (uint32_t)n, (uint32_t)(j1 - j0), stride, (const Fr30*)s.d_stab + r * kCombineTabGamma,
+                            (const Fr30*)s.d_stab + kSetsMultBase + j0, s.d_ssel + j0, (uint32_t)first, written[r],
+                            s.d_sg + 8 * r * n, s.d_cpart, s.d_svals + 8 * j0);
+        written[r] = true;
+    }
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// all passes of a host-pointer call: at most max_batch polynomials are resident at a time, every G_p is carried
+int sets_host_passes(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const SetsPlan& plan, const uint64_t* coeffs, size_t n,
+                     size_t stride) {
+    const size_t t = plan.t, group = std::min<size_t>(t, ctx->max_batch ? ctx->max_batch : 1);
+    int rc = sets_ensure_all(ctx, s, plan, n, group, group * n);
+    if (rc == KZG_OK) rc = sets_upload_tables(ctx, s, plan);
+    bool written[KZG_MAX_SET_POINTS] = {};
+    for (size_t first = 0; first < t && rc == KZG_OK; first += group) {
+        const size_t cnt = std::min(group, t - first);
+        rc = combined_stage_unlocked(ctx, lk, s, coeffs, n, stride, first, cnt);
+        if (rc == KZG_OK) rc = sets_passes(ctx, s, plan, s.d_cin, n, n, first, cnt, written);
+    }
+    return rc;
+}
+// h = sum_r Q(G_r, z_r) into s.d_q[0 .. n - 1) behind the passes (nothing for n < 2)
+int sets_enqueue_scans(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
+    if (n < 2) return KZG_OK;
+    uint64_t ws[4 * KZG_MAX_SET_POINTS];  // (the weights are inside the G_r)
+    for (size_t r = 0; r < plan.npts; r++) std::memcpy(ws + 4 * r, hf::kFrOne.l, 32);
+    points_fill_roots(s.h_roots, plan.pts[0].l, ws, (uint32_t)plan.npts, (uint32_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_roots, s.h_roots, plan.npts * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
+    launch_quotient_sets(s.stream, s.d_sg, (uint32_t)n, s.d_roots, (uint32_t)plan.npts, s.d_q, s.d_pblock, s.d_pvals);
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// the scans, the two tail checks on h (any coefficient at index >= srs_len: too high; any coefficient at all: else infinity)
+// and the MSM over h
+int sets_enqueue_open(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
+    s.job_n = n;
+    s.job_batch = 1;
+    s.has_quotient = true;
+    s.tail_checked = false;
+    s.pts_nq = 0;
+    s.sets_vmap = plan.vmap;
+    std::memset(s.h_small, 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
+    if (n >= 2) {
+        int rc = sets_enqueue_scans(ctx, s, plan, n);
+        if (rc) return rc;
+        size_t nq = n - 1;
+        if (nq > ctx->n) {
+            const uint64_t cnt = nq - ctx->n;
+            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.d_q, (uint64_t)ctx->n,
+                               (uint64_t)nq, s.d_small + 24);
+            nq = ctx->n;
+        }
+        hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s.stream, s.d_q, (uint64_t)0,
+                           (uint64_t)nq, s.d_small);
+        int rc2 = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+        if (rc2) return rc2;
+        s.pts_nq = nq;
+    }
+    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    s.kind = SLOT_OPEN_SETS;
+    return KZG_OK;
+}
+void sets_copy_values(const Slot& s, uint64_t* out_ys) {
+    for (size_t e = 0; e < s.sets_vmap.size(); e++) std::memcpy(out_ys + 4 * e, s.h_svals + 8 * (size_t)s.sets_vmap[e], 32);
+}
+
+int wait_sets_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]) {
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind == SLOT_RESERVED) return KZG_ERR_BUSY;  // a synchronous call on another thread owns it
+    if (s.kind != SLOT_OPEN_SETS) {
+        if (s.kind != SLOT_IDLE) ctx->last_error = "kzg_wait_sets on a slot that holds another kind of job";
+        return KZG_ERR_INVALID_ARG;  // the job stays in the slot
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    slot_idle(ctx, s);
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    const bool ran_msm = s.pts_nq > 0;
+    if (ran_msm) fill_device_times(s);
+    if (s.timing && s.job_n > 0) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, s.cmb_ev[0], s.cmb_ev[1]) == hipSuccess) s.combine_ms = ms;
+        if (ran_msm) {
+            hipEventElapsedTime(&ms, s.ev[0], s.ev[1]); s.times.digits_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[2], s.ev[3]); s.times.scatter_ms = ms;
+            fill_accumulate_times(s);
+            hipEventElapsedTime(&ms, s.ev[4], s.ev[5]); s.times.reduce_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[6], s.ev[7]); s.times.quotient_ms = ms;
+            hipEventElapsedTime(&ms, s.ev[6], s.ev[5]); s.times.total_ms = ms;
+        }
+    }
+    sets_copy_values(s, out_ys);
+    const uint32_t* hs = s.h_small;
+    if (hs[24]) return KZG_ERR_DEGREE_TOO_HIGH;
+    write_p1(out_p1, ran_msm && (hs[0] & 1u) ? finish_msm(ctx, s) : hf::p1_inf());  // h = 0 (also by cancellation): infinity
+    return KZG_OK;
+}
+}  // namespace
+
+int kzg_open_sets(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+                  const uint32_t* set_len, size_t m, const uint64_t* zs, const uint64_t gamma[4], uint64_t* out_ys,
+                  uint64_t out_p1[18]) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (!set_of || !set_len || !zs || !gamma || !out_ys || !out_p1) {
+        if (!ctx->multi) ctx->last_error = "kzg_open_sets: a null pointer";
+        return KZG_ERR_INVALID_ARG;
+    }
+    SetsPlan plan;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = sets_check(ctx, "kzg_open_sets", coeffs, n, t, stride, set_of, set_len, m, zs, gamma, plan);
+    if (rc) return rc;
+    if (ctx->multi) {
+        ctx->last_error.clear();  // (kzg_last_error then reads the devices' side)
+        lk.unlock();
+        return multi_open_sets(ctx->multi, coeffs, n, t, stride, set_of, set_len, m, zs, gamma, out_ys, out_p1);
+    }
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    Slot& s = ctx->slots[slot];
+    rc = sets_job_start(ctx, s, plan);
+    if (rc == KZG_OK && n) rc = sets_host_passes(ctx, lk, s, plan, coeffs, n, stride);
+    if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, n);
+    if (rc == KZG_OK) {
+        await_unlocked(lk, s);
+        rc = wait_sets_locked(ctx, slot, out_ys, out_p1);
+    }
+    release_owned(ctx, slot);
+    return rc;
+}
+
+int kzg_open_sets_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+                         const uint32_t* set_len, size_t m, const uint64_t* zs, const uint64_t gamma[4]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (!set_of || !set_len || !zs || !gamma) {
+        ctx->last_error = "kzg_open_sets_submit: a null pointer";
+        return KZG_ERR_INVALID_ARG;
+    }
+    SetsPlan plan;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = sets_check(ctx, "kzg_open_sets_submit", d_coeffs, n, t, stride, set_of, set_len, m, zs, gamma, plan);
+    if (rc) return rc;
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind != SLOT_IDLE) return KZG_ERR_BUSY;
+    rc = sets_job_start(ctx, s, plan);
+    if (rc == KZG_OK && n) {  // every pass takes all its polynomials in one launch
+        bool written[KZG_MAX_SET_POINTS] = {};
+        rc = sets_ensure_all(ctx, s, plan, n, t, 0);
+        if (rc == KZG_OK) rc = sets_upload_tables(ctx, s, plan);
+        if (rc == KZG_OK) rc = sets_passes(ctx, s, plan, (const uint32_t*)d_coeffs, n, stride, 0, t, written);
+    }
+    if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, n);
+    return rc;
+}
+
+int kzg_wait_sets(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !out_ys || !out_p1) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return wait_sets_locked(ctx, slot, out_ys, out_p1);
+}
+
+int kzg_quotient_sets(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+                      const uint32_t* set_len, size_t m, const uint64_t* zs, const uint64_t gamma[4], uint64_t* out_ys,
+                      uint64_t* out_h, size_t* out_hn) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi)  // needs no SRS
+        return kzg_quotient_sets(multi_kid(ctx->multi, 0), coeffs, n, t, stride, set_of, set_len, m, zs, gamma, out_ys, out_h, out_hn);
+    if (!set_of || !set_len || !zs || !gamma || !out_ys || !out_hn || (!out_h && n > 1)) {
+        ctx->last_error = "kzg_quotient_sets: a null pointer";
+        return KZG_ERR_INVALID_ARG;
+    }
+    SetsPlan plan;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = sets_check(ctx, "kzg_quotient_sets", coeffs, n, t, stride, set_of, set_len, m, zs, gamma, plan);
+    if (rc) return rc;
+    std::memset(out_ys, 0, 32 * plan.nvals);
+    *out_hn = 0;
+    if (n == 0) return KZG_OK;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = sets_job_start(ctx, s, plan);
+    if (rc == KZG_OK) rc = sets_host_passes(ctx, lk, s, plan, coeffs, n, stride);
+    if (rc == KZG_OK) rc = sets_enqueue_scans(ctx, s, plan, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    s.sets_vmap = plan.vmap;
+    sets_copy_values(s, out_ys);
+    if (n > 1) {
+        HIP_TRY(ctx, hipMemcpy(out_h, s.d_q, (n - 1) * 32, hipMemcpyDeviceToHost));
+        size_t hn = n - 1;
+        while (hn > 0 && !(out_h[4 * hn - 4] | out_h[4 * hn - 3] | out_h[4 * hn - 2] | out_h[4 * hn - 1])) hn--;
+        *out_hn = hn;
+    }
+    return KZG_OK;
 }
 
 // ---- host-pointer batches (BASELINE config 5: many openings against one SRS) ----------------------------------------
@@ -5071,6 +5485,50 @@ int kzg_verify_combined(const uint64_t* commitments_p1, const uint64_t* ys, size
     const int rc = kzg_combine_claims(commitments_p1, ys, t, gamma, c, y);
     if (rc) return rc;
     return kzg_verify_proof(c, proof_p1, z, y, s_g2, valid);
+}
+
+// Openings at several point sets, the verifier's side (host only): the sets are checked as the prover
+// checks them, every set's commitments and values are folded with the powers of gamma (t scalar multiplications), and
+// hf::verify_sets runs the pairing check.
+int kzg_verify_sets(const uint64_t* commitments_p1, size_t t, const uint32_t* set_of, const uint32_t* set_len, size_t m,
+                    const uint64_t* zs, const uint64_t* ys, const uint64_t gamma[4], const uint64_t proof_p1[18],
+                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    if (!commitments_p1 || !set_of || !set_len || !zs || !ys || !gamma || !proof_p1 || !setup_g1 || !setup_g2 || !valid)
+        return KZG_ERR_INVALID_ARG;
+    if (t < 1 || t > KZG_MAX_COMBINE || m < 1 || m > KZG_MAX_SETS) return KZG_ERR_INVALID_ARG;
+    SetsPlan plan;
+    std::string why;
+    if (!sets_plan(plan, why, t, set_of, set_len, m, zs, gamma)) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::SetCheck> sets(m);
+    for (size_t g = 0; g < m; g++) {
+        sets[g].k = plan.set_len[g];
+        for (size_t j = 0; j < sets[g].k; j++) {
+            sets[g].z[j] = plan.pts[plan.pt_of[g][j]];
+            sets[g].v[j] = hf::Fr{{0, 0, 0, 0}};
+        }
+        sets[g].c = hf::p1_inf();
+    }
+    hf::Fr gp = hf::kFrOne;
+    for (size_t i = 0; i < t; i++) {
+        hf::SetCheck& S = sets[set_of[i]];
+        for (size_t j = 0; j < S.k; j++) {
+            hf::Fr y;
+            if (!fr_arg_below_r(ys + 4 * (plan.val_first[i] + j), &y)) return KZG_ERR_INVALID_ARG;
+            S.v[j] = hf::fr_add(S.v[j], hf::fr_mul(gp, y));
+        }
+        hf::P1 c;
+        std::memcpy(&c, commitments_p1 + 18 * i, sizeof c);
+        if (!hf::p1_on_curve(c)) return KZG_ERR_INVALID_ARG;
+        uint64_t e[4];
+        hf::fr_from_mont(gp.l, e);
+        S.c = hf::p1_add(S.c, hf::p1_mul(c, e));
+        gp = hf::fr_mul(gp, plan.gamma);
+    }
+    const int r = hf::verify_sets(sets.data(), m, plan.pts, plan.npts, proof_p1, (const uint8_t*)setup_g1, g1_stride_bytes,
+                                  (const uint8_t*)setup_g2, g2_stride_bytes);
+    if (r < 0) return KZG_ERR_INVALID_ARG;
+    *valid = r;
+    return KZG_OK;
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

@@ -203,7 +203,72 @@ __global__ void __launch_bounds__(kCombineThreads) k_combine_eval_finish(const u
     if (l == 0) cmb_store_canonical(out + 8 * (size_t)i, fr30_sum_reduce(y));
 }
 
+// ---- openings at several point sets (kzg_open_sets) ---------------------------------------------------
+// One pass per distinct point p: G_p = sum_j mult_j P_sel[j] and the values P_sel[j](p), every coefficient read once.  It is
+// k_combine_eval with a selection list: polynomial j of the pass sits at coeffs + 8 (sel[j] - sel_base) stride words (sel
+// holds indices of the call, sel_base the index of the first polynomial resident at coeffs), and its multiplier
+// gamma^i w_(g(i),p) x 2^270 -- canonical, prepared by the host -- is mult[j]; tab: the 66 powers of p in k_combine_eval's
+// layout.  g: G_p, read first when carry != 0.  The bound above
+// fr30_mac holds unchanged: an accumulator starts as zero or a canonical value and takes at most KZG_MAX_COMBINE = 256
+// products of a coefficient below 2^256 and a canonical multiplier.
+__global__ void __launch_bounds__(kCombineThreads) k_sets_combine(const uint32_t* __restrict__ coeffs, uint32_t n, uint32_t t,
+                                                                  uint64_t stride, const Fr30* __restrict__ tab,
+                                                                  const Fr30* __restrict__ mult,
+                                                                  const uint32_t* __restrict__ sel, uint32_t sel_base, int carry,
+                                                                  uint32_t* g, uint32_t* __restrict__ partial) {
+    __shared__ int32_t lds[kR9][4];
+    const uint32_t l = threadIdx.x, tile = blockIdx.x, tiles = gridDim.x;
+    const uint64_t base = (uint64_t)tile * kCombineTile + l;
+    const Fr30 zl = fr30_mul(cmb_table(tab, kCombineTabPa + (l >> 4)), cmb_table(tab, kCombineTabPb + (l & 15)));
+    const Fr30 z256 = cmb_table(tab, kCombineTabZ256);
+    Fr30 acc[kCombineRun];
+#pragma unroll
+    for (int m = 0; m < RUN; m++) {
+        const uint64_t idx = base + (uint64_t)m * kCombineThreads;
+        acc[m] = fr30_zero();
+        if (carry && idx < n) {
+            const uint4* q = reinterpret_cast<const uint4*>(g) + 2 * idx;
+            acc[m] = cmb_from_u4(q[0], q[1]);
+        }
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < t; j++) {
+        const uint4* src = reinterpret_cast<const uint4*>(coeffs) + 2 * ((uint64_t)(sel[j] - sel_base) * stride);
+        uint4 lo[kCombineRun], hi[kCombineRun];
+#pragma unroll
+        for (int m = 0; m < RUN; m++) {
+            const uint64_t idx = base + (uint64_t)m * kCombineThreads;
+            const uint4* p = src + 2 * (idx < n ? idx : 0);
+            lo[m] = p[0];
+            hi[m] = p[1];
+        }
+        const Fr30 w = cmb_table(mult, j);
+        Fr30 h = fr30_zero();
+        cmb_steps<RUN - 1>(acc, h, lo, hi, w, z256, base, n);
+        const Fr30 e = cmb_workgroup_sum(fr30_mul(h, zl), lds);
+        if (l == 0) {
+            uint4* q = reinterpret_cast<uint4*>(partial + ((size_t)j * tiles + tile) * kCombinePartialWords);
+            q[0] = make_uint4((uint32_t)e.d[0], (uint32_t)e.d[1], (uint32_t)e.d[2], (uint32_t)e.d[3]);
+            q[1] = make_uint4((uint32_t)e.d[4], (uint32_t)e.d[5], (uint32_t)e.d[6], (uint32_t)e.d[7]);
+            q[2] = make_uint4((uint32_t)e.d[8], 0u, 0u, 0u);
+        }
+    }
+    cmb_store_f<0>(acc, g, base, n);
+}
+
 }  // namespace
+
+void launch_sets_combine(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t t, uint64_t stride, const Fr30* d_tab,
+                         const Fr30* d_mult, const uint32_t* d_sel, uint32_t sel_base, bool carry, uint32_t* d_g, uint32_t* d_partial,
+                         uint32_t* d_ys) {
+    if (!n || !t) return;
+    const uint32_t tiles = combine_tiles(n);
+    hipLaunchKernelGGL(k_sets_combine, dim3(tiles), dim3(kCombineThreads), 0, s, d_coeffs, n, t, stride, d_tab, d_mult, d_sel,
+                       sel_base,
+                       carry ? 1 : 0, d_g, d_partial);
+    hipLaunchKernelGGL(k_combine_eval_finish, dim3(t), dim3(kCombineThreads), 0, s, (const uint32_t*)d_partial, tiles, d_tab,
+                       d_ys);
+}
 
 void launch_combine_eval(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t t, uint64_t stride, const Fr30* d_tab,
                          uint32_t first, bool carry, uint32_t* d_f, uint32_t* d_partial, uint32_t* d_ys) {

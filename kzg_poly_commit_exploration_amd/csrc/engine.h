@@ -321,6 +321,16 @@ inline uint32_t combine_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kCo
 // canonical.  d_partial: t x combine_tiles(n) records of kCombinePartialWords words.  n >= 1, t <= kCombineMax.
 void launch_combine_eval(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t t, uint64_t stride, const Fr30* d_tab,
                          uint32_t first, bool carry, uint32_t* d_f, uint32_t* d_partial, uint32_t* d_ys);
+// Openings at several point sets: one pass per distinct point p.  d_tab: the 66 powers of p in the
+// layout above; d_mult[j]: the multiplier gamma^i w_(g(i),p) of polynomial j of the pass, which sits at
+// d_coeffs + 8 (d_sel[j] - sel_base) stride words.  d_g[k] (n canonical values) = (carry ? d_g[k] : 0) + sum_j mult_j c_(j,k);
+// d_ys[8 j ..] = P_sel[j](p).  d_partial as above.
+constexpr uint32_t kSetsMax = 8;          // point sets per call (KZG_MAX_SETS)
+constexpr uint32_t kSetsMaxPoints = 16;   // distinct points over all sets (KZG_MAX_SET_POINTS)
+constexpr uint32_t kSetsMaxValues = kCombineMax * kSetsMaxPoints;  // values of one call: sum_i |S_g(i)| <= 4096
+void launch_sets_combine(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint32_t t, uint64_t stride, const Fr30* d_tab,
+                         const Fr30* d_mult, const uint32_t* d_sel, uint32_t sel_base, bool carry, uint32_t* d_g, uint32_t* d_partial,
+                         uint32_t* d_ys);
 
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
@@ -374,6 +384,9 @@ int multi_open_points(MultiState* m, const uint64_t* coeffs, size_t n, const uin
                       uint64_t out_p1[18]);
 int multi_open_combined(MultiState* m, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint64_t z[4],
                         const uint64_t gamma[4], uint64_t* out_ys, uint64_t out_p1[18]);
+int multi_open_sets(MultiState* m, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+                    const uint32_t* set_len, size_t nsets, const uint64_t* zs, const uint64_t gamma[4], uint64_t* out_ys,
+                    uint64_t out_p1[18]);
 int multi_set_max_batch(MultiState* m, size_t max_batch);
 uint32_t multi_mode(const MultiState* m);
 
@@ -406,5 +419,12 @@ size_t points_root_bytes();
 void points_fill_roots(void* h_roots, const uint64_t* zs_mont, const uint64_t* ws_mont, uint32_t k, uint32_t n);
 void launch_quotient_points(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
                             uint32_t nq, uint32_t* d_block, uint32_t* d_vals);
+// A source polynomial per root (openings at several point sets): h = sum_r Q(G_r, z_r) with G_r the n
+// canonical values at d_g + 8 r n words and the roots as above (the weights are not read: they are inside the G_r already).
+// h[0 .. n - 1) is written to d_q (nothing for n < 2); k <= kSetsMaxPoints; d_block: k * poly_block_words(n) words; d_vals:
+// 8 k words the block stage may write.
+bool sets_prepare_device();
+void launch_quotient_sets(hipStream_t s, const uint32_t* d_g, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
+                          uint32_t* d_block, uint32_t* d_vals);
 
 }  // namespace kzg

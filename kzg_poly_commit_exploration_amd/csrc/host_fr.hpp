@@ -144,5 +144,29 @@ inline bool fr_point_weights(const Fr* zs, size_t k, Fr* ws) {
     }
     return true;
 }
+// the coefficients zc[0 .. k] of Z = prod_{i < k} (X - z_i): one factor at a time
+inline void fr_vanishing_coeffs(const Fr* zs, size_t k, Fr* zc) {
+    const Fr fr0 = {{0, 0, 0, 0}};
+    for (size_t j = 1; j <= k; ++j) zc[j] = fr0;
+    zc[0] = kFrOne;
+    for (size_t i = 0; i < k; ++i) {  // degree i -> i + 1: new[j] = old[j - 1] - z_i old[j]
+        for (size_t j = i + 1; j > 0; --j) zc[j] = fr_sub(zc[j - 1], fr_mul(zs[i], zc[j]));
+        zc[0] = fr_sub(fr0, fr_mul(zs[i], zc[0]));
+    }
+}
+// the coefficients ic[0 .. k) of the interpolant of (z_i, y_i), I = sum_i (y_i w_i) Z / (X - z_i): synthetic division of Z
+// (zc, from fr_vanishing_coeffs) by each root, with the weights of fr_point_weights
+inline void fr_interpolant_coeffs(const Fr* zs, const Fr* ws, const Fr* ys, size_t k, const Fr* zc, Fr* ic) {
+    const Fr fr0 = {{0, 0, 0, 0}};
+    for (size_t j = 0; j < k; ++j) ic[j] = fr0;
+    for (size_t i = 0; i < k; ++i) {
+        const Fr t = fr_mul(ys[i], ws[i]);
+        Fr b = zc[k];  // coefficient k - 1 of Z / (X - z_i)
+        for (size_t j = k; j-- > 0;) {
+            ic[j] = fr_add(ic[j], fr_mul(t, b));
+            if (j) b = fr_add(zc[j], fr_mul(zs[i], b));
+        }
+    }
+}
 
 }  // namespace kzg_host

@@ -280,16 +280,22 @@ inline LineCoeffs miller_add(G2Proj& t, const G2Affine& q, const Fp& xp, const F
 }
 
 // prod_k f_{|x|, Q_k}(P_k) without the final exponentiation, one shared squaring per loop step; pairs with a
-// point at infinity contribute 1.  ok = false if a chord degenerates (cannot happen for points of order r).
+// point at infinity contribute 1.  ok = false if a chord degenerates (cannot happen for points of order r) or for more than
+// kMillerMaxPairs pairs.
 struct MillerPair {
     G2Affine q;
     Fp xp, yp;
     G2Proj t;
     bool live;
 };
+constexpr int kMillerMaxPairs = 9;  // verify_sets: one pair per point set (at most 8) and the proof's
 inline F12 multi_miller_loop(const G2Affine* qs, const P1* ps, int count, bool& ok) {
     ok = true;
-    MillerPair pr[4];
+    MillerPair pr[kMillerMaxPairs];
+    if (count < 0 || count > kMillerMaxPairs) {  // refused, never overrun
+        ok = false;
+        return f12_one();
+    }
     for (int k = 0; k < count; ++k) {
         pr[k].live = !(qs[k].inf || ps[k].is_inf());
         if (!pr[k].live) continue;
@@ -575,6 +581,89 @@ inline int verify_points(const uint64_t* commitment, const uint64_t* proof, cons
     const P1 ps[2] = {Pi, p1_neg(p1_add(C, p1_neg(is)))};
     bool ok = true;
     const F12 f = multi_miller_loop(qs, ps, 2, ok);
+    if (!ok) return 0;
+    return f12_is_one(f12_final_exp(f)) ? 1 : 0;
+}
+
+// Openings at several point sets with one G1 element W (BDFG20, the first scheme).  Per set g the
+// caller has folded its polynomials: c = sum_{i in g} gamma^i C_i and v_p = sum_{i in g} gamma^i y_(i,p).  With R_g the
+// interpolant of (p, v_p) on S_g and T the union of the sets, the check is
+//        prod_g e(c_g - [R_g(s)]G1, [Z_(T \ S_g)(s)]G2) == e(W, [Z_T(s)]G2):
+// one Miller loop over m + 1 pairs and one final exponentiation.  Reads SRS G1 entries [0, max |S_g|) and the G2 powers
+// [s^j]G2, j <= |T|.  Returns 1 accepted, 0 rejected, -1 malformed input (1 <= m <= 8, 1 <= |S_g|, |T| <= 16, points of a
+// set distinct, G1 inputs on the curve, G2 inputs on the twist; no subgroup checks).
+constexpr size_t kVerifySetsMax = 8, kVerifySetPointsMax = 16;
+struct SetCheck {
+    size_t k;
+    Fr z[kVerifySetPointsMax], v[kVerifySetPointsMax];
+    P1 c;
+};
+inline int verify_sets(const SetCheck* sets, size_t m, const Fr* all, size_t nall, const uint64_t* proof, const uint8_t* setup_g1,
+                       size_t g1_stride, const uint8_t* setup_g2, size_t g2_stride) {
+    if (m < 1 || m > kVerifySetsMax || nall < 1 || nall > kVerifySetPointsMax) return -1;
+    P1 W;
+    std::memcpy(&W, proof, sizeof W);
+    if (!p1_on_curve(W)) return -1;
+    size_t kmax = 0;
+    for (size_t g = 0; g < m; ++g) {
+        if (sets[g].k < 1 || sets[g].k > nall || !p1_on_curve(sets[g].c)) return -1;
+        kmax = sets[g].k > kmax ? sets[g].k : kmax;
+    }
+    P1 g1[kVerifySetPointsMax];
+    for (size_t j = 0; j < kmax; ++j) {
+        std::memcpy(&g1[j], setup_g1 + j * g1_stride, sizeof g1[j]);
+        if (!p1_on_curve(g1[j])) return -1;
+    }
+    P2 g2[kVerifySetPointsMax + 1];
+    for (size_t j = 0; j <= nall; ++j) {
+        uint64_t raw[36];
+        std::memcpy(raw, setup_g2 + j * g2_stride, sizeof raw);
+        if (!g2_on_curve(g2_from_p2(raw))) return -1;
+        std::memcpy(&g2[j], raw, sizeof g2[j]);
+    }
+    auto g2_at = [&](const Fr* zc, size_t deg) {  // [sum_j zc[j] s^j]G2, affine
+        P2 acc = p2_inf();
+        for (size_t j = 0; j <= deg; ++j) {
+            uint64_t e[4];
+            fr_from_mont(zc[j].l, e);
+            acc = p2_add(acc, p2_mul(g2[j], e));
+        }
+        const P2 an = p2_normalize(acc);
+        uint64_t raw[36];
+        std::memcpy(raw, &an, sizeof raw);
+        return g2_from_p2(raw);
+    };
+    G2Affine qs[kMillerMaxPairs];
+    P1 ps[kMillerMaxPairs];
+    Fr zc[kVerifySetPointsMax + 1];
+    for (size_t g = 0; g < m; ++g) {
+        const SetCheck& S = sets[g];
+        Fr w[kVerifySetPointsMax], ic[kVerifySetPointsMax], rest[kVerifySetPointsMax];
+        if (!fr_point_weights(S.z, S.k, w)) return -1;
+        fr_vanishing_coeffs(S.z, S.k, zc);
+        fr_interpolant_coeffs(S.z, w, S.v, S.k, zc, ic);
+        P1 rs = p1_inf();  // [R_g(s)]G1
+        for (size_t j = 0; j < S.k; ++j) {
+            uint64_t e[4];
+            fr_from_mont(ic[j].l, e);
+            rs = p1_add(rs, p1_mul(g1[j], e));
+        }
+        size_t nrest = 0;  // T \ S_g
+        for (size_t r = 0; r < nall; ++r) {
+            bool in_set = false;
+            for (size_t j = 0; j < S.k; ++j) in_set |= std::memcmp(all[r].l, S.z[j].l, 32) == 0;
+            if (!in_set) rest[nrest++] = all[r];
+        }
+        if (nrest + S.k != nall) return -1;  // a point of the set outside T
+        fr_vanishing_coeffs(rest, nrest, zc);
+        qs[g] = g2_at(zc, nrest);
+        ps[g] = p1_add(S.c, p1_neg(rs));
+    }
+    fr_vanishing_coeffs(all, nall, zc);
+    qs[m] = g2_at(zc, nall);
+    ps[m] = p1_neg(W);
+    bool ok = true;
+    const F12 f = multi_miller_loop(qs, ps, (int)m + 1, ok);
     if (!ok) return 0;
     return f12_is_one(f12_final_exp(f)) ? 1 : 0;
 }

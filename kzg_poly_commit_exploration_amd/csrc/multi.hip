@@ -531,6 +531,19 @@ int multi_open_combined(MultiState* m, const uint64_t* coeffs, size_t n, size_t 
     return KZG_ERR_INVALID_ARG;
 }
 
+// An opening at several point sets: as the combined openings.
+int multi_open_sets(MultiState* m, const uint64_t* coeffs, size_t n, size_t t, size_t stride, const uint32_t* set_of,
+                    const uint32_t* set_len, size_t nsets, const uint64_t* zs, const uint64_t gamma[4], uint64_t* out_ys,
+                    uint64_t out_p1[18]) {
+    if (!m->n) return KZG_ERR_NO_SRS;
+    if (m->mode == kMultiReplicate)
+        return kzg_open_sets(m->kids[m->next_kid.fetch_add(1) % m->kids.size()], coeffs, n, t, stride, set_of, set_len, nsets, zs,
+                             gamma, out_ys, out_p1);
+    std::lock_guard<std::mutex> lk(m->op_mu);
+    m->last_error = "kzg_open_sets: range-split multi-device contexts are not supported (use KZG_MULTI_REPLICATE_SRS)";
+    return KZG_ERR_INVALID_ARG;
+}
+
 // A multiproof: replicated SRS -> one device, as a single opening.  A range-split SRS would need a carry per root and
 // slice (the single-point recurrence above, k times): not supported.
 int multi_open_points(MultiState* m, const uint64_t* coeffs, size_t n, const uint64_t* zs, const uint64_t* ys, size_t k,

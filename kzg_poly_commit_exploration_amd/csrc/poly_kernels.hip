@@ -668,4 +668,122 @@ void launch_quotient_points(hipStream_t s, const uint32_t* d_coeffs, uint32_t n,
                            d_block, nblocks, direct, q, nq, d_vals);
 }
 
+// ---- a separate source polynomial per root: the quotient of openings at several point sets ----------
+// h = sum_r Q(G_r, z_r): the k_points_* scheme with root r scanning its OWN polynomial G_r (n canonical values at
+// d_g + 8 r n words, made by k_sets_combine with the partial-fraction weights already inside) and the weight 1.  The tile is
+// therefore staged inside the root loop (a wave re-fills its own LDS region once every lane has read the previous root's
+// chunk), and the replay adds S_r itself to the lane's accumulators: at most KZG_MAX_SET_POINTS = 16 lazy values, each a
+// product plus a canonical coefficient inside (-r, 2r), so a sum stays inside (-16 r, 32 r) -- the magnitude of the 64
+// products of r / 2 above, far inside the 270-bit digit range (top digit below 2^21); a product by one brings it under r / 2
+// before it leaves.  The values P_i(z) are not taken from these kernels (the combination passes give them); d_vals only
+// receives G_r(z_r) from the block stage.
+template <int C>
+KZG_DEV void sets_replay(Fr30 (&acc)[kPolyL], Fr30& h, const Fr30& z, const uint4* __restrict__ lds_wave, uint32_t lane) {
+    h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, C));
+    acc[C] = fr30_add(acc[C], h);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (C > 0) sets_replay<C - 1>(acc, h, z, lds_wave, lane);
+}
+
+__global__ void __launch_bounds__(kPolyBlock) k_sets_chunks(const uint32_t* __restrict__ d_g, uint32_t n,
+                                                            const PointsRoot* __restrict__ roots, uint32_t k,
+                                                            uint32_t* __restrict__ d_block) {
+    extern __shared__ uint4 lds_tile[];
+    __shared__ uint32_t lds[kPolyScanWords];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint4* lds_wave = lds_tile + wave * kPolyWaveLds;
+    const uint64_t wave_first = ((uint64_t)blockIdx.x * kPolyBlock + wave * 64u) * kPolyL;
+    for (uint32_t r = 0; r < k; r++) {
+        poly_wave_sync();  // (the previous root's chunk reads are done)
+        poly_stage_in(d_g + 8 * (size_t)r * n, wave_first, n, lds_wave, lane);
+        const Fr30 z = fr_from_arg(roots[r].pw.z);
+        Fr30 h = fr30_zero();
+#pragma unroll
+        for (int c = kPolyL - 1; c >= 0; c--) h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, c));
+        h = block_suffix_scan<kPolyBlock>(h, roots[r].pw.zl_sq, lds);
+        if (threadIdx.x == 0) store_rec(d_block + ((size_t)r * gridDim.x + blockIdx.x) * kPolyRec, h);
+    }
+}
+
+__global__ void __launch_bounds__(kPolyBlock) k_sets_blocks(uint32_t* __restrict__ d_block, uint32_t nblocks,
+                                                            const PointsRoot* __restrict__ roots,
+                                                            uint32_t* __restrict__ d_vals) {
+    __shared__ uint32_t lds[kPolyScanWords];
+    const uint32_t r = blockIdx.x;
+    poly_block_stage(d_block + (size_t)r * nblocks * kPolyRec, nblocks, roots[r].pw, d_vals + 8 * r, lds);
+}
+
+// direct != 0: d_block holds the aggregates; direct == 0: the carries (k_sets_blocks ran).  Writes h[0 .. nq), nq = n - 1.
+__global__ void __launch_bounds__(kPolyBlock) k_sets_apply(const uint32_t* __restrict__ d_g, uint32_t n,
+                                                           const PointsRoot* __restrict__ roots, uint32_t k,
+                                                           const uint32_t* __restrict__ d_block, uint32_t nblocks, int direct,
+                                                           uint32_t* __restrict__ d_q, uint32_t nq) {
+    extern __shared__ uint4 lds_tile[];
+    __shared__ uint32_t lds[kPolyScanWords];
+    const int tl = threadIdx.x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint4* lds_wave = lds_tile + wave * kPolyWaveLds;
+    const uint64_t wave_first = ((uint64_t)blockIdx.x * kPolyBlock + wave * 64u) * kPolyL;
+    const uint32_t dist = (uint32_t)(kPolyBlock - 1 - tl);  // chunks between the next chunk and the block end
+    Fr30 acc[kPolyL];
+#pragma unroll
+    for (int c = 0; c < kPolyL; c++) acc[c] = fr30_zero();
+    for (uint32_t r = 0; r < k; r++) {
+        const PolyPowers& pw = roots[r].pw;
+        const uint32_t* blk = d_block + (size_t)r * nblocks * kPolyRec;
+        poly_wave_sync();  // (the previous root's replay has read its chunk)
+        poly_stage_in(d_g + 8 * (size_t)r * n, wave_first, n, lds_wave, lane);  // in flight while the carry is worked out
+        const Fr30 blk_carry = direct ? poly_carry_from_aggregates(blk, nblocks, blockIdx.x + 1, pw, lds)
+                                      : load_rec(blk + (size_t)blockIdx.x * kPolyRec);
+        // the chunk Horner and the in-workgroup scan of launch 1 again: S at the first coefficient of every chunk
+        const Fr30 z = fr_from_arg(pw.z);
+        Fr30 h = fr30_zero();
+#pragma unroll
+        for (int c = kPolyL - 1; c >= 0; c--) h = fr30_mul_add(h, z, poly_lds_coeff(lds_wave, lane, c));
+        h = block_suffix_scan<kPolyBlock>(h, pw.zl_sq, lds);
+#pragma unroll
+        for (int i = 0; i < kR9; i++) lds[i * kPolyBlock + tl] = (uint32_t)h.d[i];
+        __syncthreads();
+        Fr30 next = fr30_zero();  // the next lane's value: S at the first coefficient of the next chunk, without the carry
+        if (tl + 1 < kPolyBlock) {
+#pragma unroll
+            for (int i = 0; i < kR9; i++) next.d[i] = (int32_t)lds[i * kPolyBlock + tl + 1];
+        }
+        __syncthreads();
+        const Fr30 pa = fr_from_arg(pw.pa[dist >> 4]), pb = fr_from_arg(pw.pb[dist & 15]);  // (z^L)^dist = pa * pb
+        h = fr30_add(next, fr30_mul(blk_carry, fr30_mul(pa, pb)));
+        sets_replay<kPolyL - 1>(acc, h, z, lds_wave, lane);
+    }
+    // the sums, canonical, into the lane's own LDS words (the last root's coefficients are no longer needed), then out one lower
+    points_store_sums<kPolyL - 1>(acc, fr_from_arg(roots[0].pw.one), lds_wave, lane);
+    poly_wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(d_q) + 2 * wave_first;  // word g of the region belongs at dst[g - 2]
+    const uint64_t end = 2 * ((uint64_t)nq + 1);                   // words of the region up to coefficient nq
+    const uint64_t valid = wave_first < (uint64_t)nq + 1 ? end - 2 * wave_first : 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const uint32_t g = (uint32_t)i * 64u + lane;
+        if (g < valid && (wave_first != 0 || g >= 2)) dst[(int64_t)g - 2] = lds_wave[poly_lds_slot(g)];
+    }
+}
+
+bool sets_prepare_device() {
+    const bool a = hipFuncSetAttribute((const void*)k_sets_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolyTileLds) == hipSuccess;
+    const bool b = hipFuncSetAttribute((const void*)k_sets_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolyTileLds) == hipSuccess;
+    if (!(a && b)) (void)hipGetLastError();
+    return a && b;
+}
+
+void launch_quotient_sets(hipStream_t s, const uint32_t* d_g, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
+                          uint32_t* d_block, uint32_t* d_vals) {
+    if (n < 2 || k == 0) return;
+    const PointsRoot* roots = static_cast<const PointsRoot*>(d_roots);
+    const uint32_t nblocks = (n + kPolyTile - 1) / kPolyTile;
+    hipLaunchKernelGGL(k_sets_chunks, dim3(nblocks), dim3(kPolyBlock), kPolyTileLds, s, d_g, n, roots, k, d_block);
+    const int direct = nblocks <= kPolyDirectBlocks;
+    if (!direct) hipLaunchKernelGGL(k_sets_blocks, dim3(k), dim3(kPolyBlock), 0, s, d_block, nblocks, roots, d_vals);
+    hipLaunchKernelGGL(k_sets_apply, dim3(nblocks), dim3(kPolyBlock), kPolyTileLds, s, d_g, n, roots, k, d_block, nblocks, direct,
+                       d_q, n - 1);
+}
+
 }  // namespace kzg

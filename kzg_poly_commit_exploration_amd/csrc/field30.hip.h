@@ -240,6 +240,105 @@ KZG_HD Fq fq_sqr(const Fq& a) {
     return r;
 }
 
+// ---- products that subtract (or add) a third value inside their own carry pass (the accumulation kernel's group law) ----
+// a * b / 2^390 -+ c.  The upper columns of a Montgomery product ARE an exact sequential carry pass (fq_sext30 +
+// fq_round_shift): digit t of c enters column 13 + t before that column's digit is extracted, digit 12 enters the last
+// word.  The result is the integer (a b + m p) / 2^390 -+ c with digits 0..11 in [-2^29, 2^29) -- stricter than fq_norm's
+// output -- for 13 multiply-adds instead of a digit-wise subtraction and a carry pass (13 + 5 x 12 instructions).
+// c may be a raw sum of up to four normalised values (|digit| < 2^31): the column bound of fq_mul grows by 2^31 only,
+// 12 * 2^59 + 1.55 * 2^60 + 2^32 < 2^63.  a, b as for fq_mul / fq_sqr.
+// On the device the digit enters as ONE v_mad_i64_i32 by +-1 (the factor kept opaque in a scalar register: written as a
+// subtraction the compiler sign-extends the digit and subtracts with borrow, three instructions).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KZG_F30_OPAQUE_UNIT(s) asm("" : "+s"(s))
+#else
+#define KZG_F30_OPAQUE_UNIT(s) ((void)0)
+#endif
+template <int kSign>
+KZG_HD Fq fq_mul_addc(const Fq& a, const Fq& b, const Fq& c) {
+    static_assert(kSign == 1 || kSign == -1, "a b / 2^390 + c or a b / 2^390 - c");
+    int32_t unit = kSign;
+    KZG_F30_OPAQUE_UNIT(unit);
+    int32_t m[kQ];
+    Fq r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < kQ; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+#pragma unroll
+        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        m[k] = fq_sext30((uint32_t)acc * kQN0);
+        acc += (int64_t)m[k] * fq_pd(0);  // low 30 bits are now zero
+        acc >>= kQBits;
+        KZG_F30_FENCE(acc);
+    }
+#pragma unroll
+    for (int k = kQ; k < 2 * kQ - 1; k++) {
+#pragma unroll
+        for (int i = k - kQ + 1; i < kQ; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+#pragma unroll
+        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        acc += (int64_t)c.d[k - kQ] * unit;
+        r.d[k - kQ] = fq_sext30((uint32_t)acc);
+        acc = fq_round_shift(acc);
+        KZG_F30_FENCE(acc);
+    }
+    r.d[kQ - 1] = (int32_t)acc + kSign * c.d[kQ - 1];
+    return r;
+}
+KZG_HD Fq fq_mul_minus(const Fq& a, const Fq& b, const Fq& c) { return fq_mul_addc<-1>(a, b, c); }  // a b / 2^390 - c
+KZG_HD Fq fq_mul_plus(const Fq& a, const Fq& b, const Fq& c) { return fq_mul_addc<1>(a, b, c); }    // a b / 2^390 + c
+// a^2 / 2^390 - c
+KZG_HD Fq fq_sqr_minus(const Fq& a, const Fq& c) {
+    int32_t unit = -1;
+    KZG_F30_OPAQUE_UNIT(unit);
+    int32_t m[kQ], dbl[kQ];
+#pragma unroll
+    for (int i = 0; i < kQ; i++) dbl[i] = a.d[i] * 2;
+    Fq r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < kQ; k++) {
+#pragma unroll
+        for (int i = 0; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
+        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+#pragma unroll
+        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        m[k] = fq_sext30((uint32_t)acc * kQN0);
+        acc += (int64_t)m[k] * fq_pd(0);
+        acc >>= kQBits;
+        KZG_F30_FENCE(acc);
+    }
+#pragma unroll
+    for (int k = kQ; k < 2 * kQ - 1; k++) {
+#pragma unroll
+        for (int i = k - kQ + 1; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
+        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+#pragma unroll
+        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        acc += (int64_t)c.d[k - kQ] * unit;
+        r.d[k - kQ] = fq_sext30((uint32_t)acc);
+        acc = fq_round_shift(acc);
+        KZG_F30_FENCE(acc);
+    }
+    r.d[kQ - 1] = (int32_t)acc - c.d[kQ - 1];
+    return r;
+}
+
+// the one-word pre-test of fq_is_zero on its own: false means v != 0 (mod p) for |v| < 3.5 p; true means "run the exact
+// test" (all of the zero values, ~2^-27 of the others)
+KZG_HD bool fq_maybe_zero(const Fq& a) {
+    const uint32_t lo = (uint32_t)a.d[0] & (uint32_t)kQMask;
+    const uint32_t p0 = (uint32_t)fq_pd(0) & (uint32_t)kQMask;
+    bool maybe = lo == 0;
+#pragma unroll
+    for (uint32_t k = 1; k <= 3; k++) {
+        maybe = maybe || lo == ((k * p0) & (uint32_t)kQMask) || lo == ((0u - k * p0) & (uint32_t)kQMask);
+    }
+    return maybe;
+}
+
 // v == 0 (mod p) for |v| < 3.5 p.  The integer is k*p with |k| <= 3; its residue mod 2^30 only depends on digit 0,
 // so seven compares on one word reject everything but ~2^-27 of the non-zero values; the exact test runs then.
 // (by value: a reference parameter of a real call would pin every tested element in private memory)

@@ -8,6 +8,8 @@
 //
 // Magnitudes (p-multiples; every product is < 0.62 p + |a||b| / 2^390, and p / 2^390 < 0.0016):
 //   X < 2.6 p, Y < 1.3 p, ZZ, ZZZ < 0.7 p;   P = U2 - X < 3.3 p, R = S2 - Y < 2 p  -> zero tests valid below 3.5 p.
+// The accumulation kernel's form of the mixed addition (xyzz30_acc_*, below) computes the same integers and keeps this
+// line; what differs is the DIGIT form of X inside the kernel (a raw sum of two, |digit| <= 2^30), re-derived there.
 #pragma once
 #include "field30.hip.h"
 
@@ -139,6 +141,86 @@ KZG_HD void xyzz30_madd_tail(XYZZ30& acc, const Fq& P, const Fq& R) {
 KZG_HD void xyzz30_madd(XYZZ30& acc, const Affine30& p_in, bool neg) {
     Fq P, R;
     if (xyzz30_madd_head(acc, p_in, neg, P, R)) xyzz30_madd_tail(acc, P, R);
+}
+
+// ---- the same mixed addition for the accumulation kernel: no separate carry passes, exceptional cases out of line ------
+// Every difference of the group law is taken inside the carry pass of the product in front of it (fq_mul_minus / fq_mul_plus /
+// fq_sqr_minus, field30.hip.h), and R is carried with its sign flipped (Rn = -R: R only enters squared and in Y3):
+//   P  = x2 ZZ - X                 Rn = (-y2) ZZZ + Y
+//   PP = P^2, ZZ' = ZZ PP, Q = X PP, PPP = P PP, ZZZ' = ZZZ PPP
+//   W  = Rn^2 - (PPP + 3 Q) = X3 - Q         Y3 = Rn W - Y PPP = R (Q - X3) - Y PPP          X3 = W + Q  (kept as a raw sum)
+// The INTEGERS are those of xyzz30_madd (up to the choice of the representative p-multiple in a reduction), so the magnitude
+// line at the top of this file holds unchanged: |R^2|, |PPP|, |Q| < 0.62 p + 0.0016 p x (4, 0.5, 1.9) < 0.63 p, X3 < 4 x 0.63 p
+// < 2.6 p, |W| < 3.2 p, Y3 < 0.62 p + 0.0016 p (2 x 3.2 + 1.3 x 0.7) < 0.64 p, P < 0.7 p + 2.6 p, R < 0.7 p + 1.3 p.
+// Digit forms: P, Rn, W, Y, ZZ, ZZZ, PP, PPP, Q leave a product with digits 0..11 in [-2^29, 2^29).  X = W + Q has digits
+// 0..11 in [-2^30, 2^30): it is read as the `c` of fq_mul_minus (any int32 digit) and as ONE operand of X PP (2^30 x 2^29 =
+// 2^59 <= 2.1 x 2^58, fq_mul's contract).  PPP + 3 Q has digits in [-2^31, 2^31): `c` of fq_sqr_minus, it fits an int32.
+// An accumulator that LEAVES the kernel gets one carry pass on X first (xyzz30_acc_settle): its readers -- xyzz30_add*,
+// xyzz30_dbl_body (which squares X), the host tail's px_from_record -- see |digit| <= 2^29 + 4 as from xyzz30_madd.
+//   xyzz30_acc_head  P, Rn and the lane's case (products on zero operands are harmless): 0 = the tail is all that is left;
+//   xyzz30_acc_set   accumulator at infinity, finite point: acc = p;
+//   xyzz30_acc_rare  P passed the zero pre-test: the exact tests, doubling or cancellation; returns whether the tail is to run;
+//   xyzz30_acc_tail  the remaining 6M + 2S.
+enum : uint32_t {
+    kAccPointInf = 1,   // the point is at infinity: nothing to add
+    kAccFresh = 2,      // the accumulator is at infinity (then P = 0 exactly, whatever the point)
+    kAccMaybeEqual = 4  // fq_maybe_zero(P): equal or opposite operands, or one of the pre-test's false positives
+};
+KZG_HD uint32_t xyzz30_acc_head(const XYZZ30& acc, const Affine30& p_in, bool neg, Fq& P, Fq& Rn) {
+    const Fq pyn = fq_cneg(p_in.y, !neg);
+    P = fq_mul_minus(p_in.x, acc.ZZ, acc.X);  // U2 - X1
+    KZG_SB30();
+    Rn = fq_mul_plus(pyn, acc.ZZZ, acc.Y);    // Y1 - S2
+    KZG_SB30();
+    return ((fq_all_zero(p_in.x) && fq_all_zero(p_in.y)) ? kAccPointInf : 0u) | (xyzz30_is_inf(acc) ? kAccFresh : 0u) |
+           (fq_maybe_zero(P) ? kAccMaybeEqual : 0u);
+}
+KZG_HD void xyzz30_acc_settle(XYZZ30& acc) { acc.X = fq_norm(acc.X); }
+KZG_HD void xyzz30_acc_set(XYZZ30& acc, const Affine30& p_in, bool neg) {
+    acc.X = p_in.x;
+    acc.Y = fq_cneg(p_in.y, neg);
+    acc.ZZ = fq_one_cold();
+    acc.ZZZ = acc.ZZ;
+}
+KZG_HD bool xyzz30_acc_rare(XYZZ30& acc, const Fq& P, const Fq& Rn) {
+    if (!fq_is_zero(P)) return true;  // the pre-test's false positive
+    if (fq_is_zero(Rn)) {             // acc == p as group elements
+        xyzz30_acc_settle(acc);
+        xyzz30_dbl_inplace(acc);
+    } else {
+        acc = xyzz30_inf();
+    }
+    return false;
+}
+KZG_HD void xyzz30_acc_tail(XYZZ30& acc, const Fq& P, const Fq& Rn) {
+    const Fq PP = fq_sqr(P);
+    KZG_SB30();
+    acc.ZZ = fq_mul(acc.ZZ, PP);
+    KZG_SB30();
+    const Fq Q = fq_mul(acc.X, PP);
+    KZG_SB30();
+    const Fq PPP = fq_mul(P, PP);
+    KZG_SB30();
+    acc.ZZZ = fq_mul(acc.ZZZ, PPP);
+    KZG_SB30();
+    const Fq W = fq_sqr_minus(Rn, fq_add_raw(fq_add_raw(PPP, Q), fq_add_raw(Q, Q)));  // X3 - Q
+    KZG_SB30();
+    acc.Y = fq_mul_sub(Rn, W, acc.Y, PPP);  // R (Q - X3) - Y1 PPP, one reduction
+    KZG_SB30();
+    acc.X = fq_add_raw(W, Q);
+}
+// the three parts in a row (host tests; the kernel puts its gather between them, reads the point for xyzz30_acc_set from LDS a second time and
+// calls xyzz30_acc_rare out of line)
+KZG_HD void xyzz30_acc_madd(XYZZ30& acc, const Affine30& p_in, bool neg) {
+    Fq P, Rn;
+    const uint32_t code = xyzz30_acc_head(acc, p_in, neg, P, Rn);
+    bool more = code == 0;
+    if (code & kAccFresh) {
+        if (!(code & kAccPointInf)) xyzz30_acc_set(acc, p_in, neg);
+    } else if (code == kAccMaybeEqual) {
+        more = xyzz30_acc_rare(acc, P, Rn);
+    }
+    if (more) xyzz30_acc_tail(acc, P, Rn);
 }
 
 // acc += b (add-2008-s: 12M + 2S, the last two products sharing one reduction), complete

@@ -9,12 +9,19 @@
 // coefficients equal.  A lane closes a bucket it covers completely by storing it; the (at most two)
 // buckets it shares with its neighbours leave a head / tail partial that k_bucket_finalize adds up.
 //
-// Roofline: VALU issue bound.  Per mixed addition the wave executes 3055 v_mad_i64_i32 (6 products x 2 x 13^2, two squares
-// x (91 + 13^2), and R (Q - X3) - Y1 PPP as two digit products under one reduction) + ~1400 other VALU instructions,
+// Roofline: VALU issue bound.  Per mixed addition the wave executes 3091 v_mad_i64_i32 (6 products x 2 x 13^2, two squares
+// x (91 + 13^2), R (Q - X3) - Y1 PPP as two digit products under one reduction, and 3 x 12 digits of the differences P, R and
+// X3 - Q that enter the carry pass of the product in front of them as a multiply-add by +-1: xyzz30_acc_*, g1_30.hip.h) and
+// ~970 other VALU instructions on the straight path of an iteration (919 for P and R, 3118 for the tail; static counts of
+// the loop: 4317 VALU, 4682 with a carry pass per difference and the exceptional cases assigned in front of the products:
+// profiles/r16_accum_isa_histogram.txt),
 // against one 128-byte table record gathered by LDS-DMA + 4 B of reference; it runs within ~10 % of the sum of the two pipe
 // times of that mix (measured bare-loop rates), at two waves per SIMD as well as at three -- a three-wave form of the kernel
 // (no exceptional branches, 163 VGPRs, no spills) measured 2354 us against 2336 us alone, and a build of which three
 // workgroups fit a CU is SLOWER in the pipeline (profiles/r03_accum_isa_histogram.txt).
+// The exceptional cases sit behind the two products under a branch the wave skips: the first point of a run is read from LDS
+// a second time, equal or opposite operands are ONE real call (accum_rare_call); assigned in front of the products they
+// cost every iteration four blocks of 52 register moves.
 // Algorithmic HBM bytes per commitment are those of SURVEY.md section 8(d): 128 B x n + 144 B.
 #include <cstdlib>
 
@@ -102,14 +109,10 @@ __device__ __forceinline__ void accum_issue_gather(const uint4* __restrict__ tab
 // smaller and the gather has landed anyway.)
 constexpr int kFlushOps = 17;
 static_assert(kFlushOps == 17, "the literal in accum_take_point's s_waitcnt");
-__device__ __forceinline__ Affine30 accum_take_point(uint32_t slot, bool wave_flushed = false) {
-#ifdef KZG_ACCUM_FULL_WAIT  // (A/B: wait for the flush too)
-    wave_flushed = false;
-#endif
-    if (wave_flushed) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA pieces (and the reference load behind them)
+// the lane's point out of the wave's slot (lane_slot = slot + lane * 16, an LDS byte address)
+__device__ __forceinline__ Affine30 accum_read_point(uint32_t lane_slot) {
     Affine30 r;
-    lds_u4_ptr q = (lds_u4_ptr)(uintptr_t)(slot + accum_wave_lane() * 16u);
+    lds_u4_ptr q = (lds_u4_ptr)(uintptr_t)lane_slot;
     const accum_u32x4 x0 = q[0], x1 = q[64], x2 = q[128], x3 = q[192];
     const accum_u32x4 y0 = q[256], y1 = q[320], y2 = q[384], y3 = q[448];
     r.x.d[0] = (int32_t)x0.x; r.x.d[1] = (int32_t)x0.y; r.x.d[2] = (int32_t)x0.z; r.x.d[3] = (int32_t)x0.w;
@@ -120,9 +123,28 @@ __device__ __forceinline__ Affine30 accum_take_point(uint32_t slot, bool wave_fl
     r.y.d[4] = (int32_t)y1.x; r.y.d[5] = (int32_t)y1.y; r.y.d[6] = (int32_t)y1.z; r.y.d[7] = (int32_t)y1.w;
     r.y.d[8] = (int32_t)y2.x; r.y.d[9] = (int32_t)y2.y; r.y.d[10] = (int32_t)y2.z; r.y.d[11] = (int32_t)y2.w;
     r.y.d[12] = (int32_t)y3.x;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot may be overwritten from here on
     return r;
 }
+__device__ __forceinline__ Affine30 accum_take_point(uint32_t slot, bool wave_flushed = false) {
+#ifdef KZG_ACCUM_FULL_WAIT  // (A/B: wait for the flush too)
+    wave_flushed = false;
+#endif
+    if (wave_flushed) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA pieces (and the reference load behind them)
+    const Affine30 r = accum_read_point(slot + accum_wave_lane() * 16u);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is not read again on the hot path
+    return r;
+}
+// Equal or opposite operands of a mixed addition (and the zero pre-test's false positives): ONE real call, entered only by the
+// lanes that need it, under a branch the whole wave skips otherwise.  Everything goes through private memory -- the
+// accumulator as a copy (its own address is never taken: it would live in private memory for the whole kernel), P and Rn
+// beside it and read back with it, so that the call (the doubling inside it: 164 registers) has nothing but the loop's own
+// state live across it.  Nothing of the hot loop is a phi of two register sets.
+struct AccumRare {
+    XYZZ30 acc;
+    Fq P, Rn;
+};
+static __device__ __noinline__ bool accum_rare_call(AccumRare* io) { return xyzz30_acc_rare(io->acc, io->P, io->Rn); }
 // A finished run leaves the lane: exactly SIXTEEN 16-byte stores, issued as one block the compiler neither splits, merges nor
 // counts (store_xyzz30 compiles to 17 of mixed widths today; accum_take_point's wait depends on the number).
 __device__ __forceinline__ void accum_flush_run(uint4* dst, const XYZZ30& a) {
@@ -208,6 +230,7 @@ k_bucket_accumulate(const uint4* __restrict__ table, const uint32_t* __restrict_
         if (e == b_end) {
             // bucket b ends here: flush its run and move to the bucket that owns e (skipping empties)
             uint4* dst = (run_start == b_beg) ? buckets + (size_t)b * kXyzzU4 : part_a + (size_t)lane * kXyzzU4;
+            xyzz30_acc_settle(acc);     // (X leaves the kernel weakly normalised: g1_30.hip.h)
             accum_flush_run(dst, acc);  // a run that began inside the bucket necessarily began at `start`
             acc = xyzz30_inf();
             // the end of the next bucket was read one boundary ago: the walk does not wait for memory unless it has
@@ -223,14 +246,40 @@ k_bucket_accumulate(const uint4* __restrict__ table, const uint32_t* __restrict_
             b_end_next = offs[(b + 2 <= nb) ? b + 2 : nb];
             run_start = e;
         }
-        Fq P, R;
-        bool more;
+        Fq P, Rn;
+        uint32_t code;
         {
             // After a flush the wait lets the flush's own kFlushOps operations stay in flight: without that every bucket
             // boundary in a wave -- one iteration in four at degree 2^20, nine in ten in a batch of short polynomials --
             // stood still for a store's round trip before it looked at its point.
             const Affine30 p = accum_take_point(wave_slot, wave_flushed);
-            more = xyzz30_madd_head(acc, p, (ref >> 31) != 0, P, R);
+            code = xyzz30_acc_head(acc, p, (ref >> 31) != 0, P, Rn);
+        }
+        bool more = code == 0;
+        if (__builtin_amdgcn_ballot_w64(code != 0) != 0) {  // (wave-uniform)
+            if (code & kAccFresh) {
+                // the first point of a run (every flush leads here: no vector-memory operation, the flush's stores stay in
+                // flight): the point is read from the slot a second time -- the next gather is issued below -- instead of being
+                // kept in registers across the two products
+                if (!(code & kAccPointInf)) {
+                    const Affine30 p = accum_read_point(wave_slot + accum_wave_lane() * 16u);
+                    xyzz30_acc_set(acc, p, (ref >> 31) != 0);
+                }
+            } else if (code == kAccMaybeEqual) {
+                AccumRare t;
+                t.acc = acc;
+                t.P = P;
+                t.Rn = Rn;
+                more = accum_rare_call(&t);
+                acc = t.acc;  // (P and Rn come back from memory as well: nothing but the loop's own state is live across the call)
+                P = t.P;
+                Rn = t.Rn;
+                // s_waitcnt vmcnt(0): the reloads have landed before this block is left.  The compiler lays the block for the
+                // first point of a run out behind this one; with reloads pending at its entry it waits there for "all but
+                // the youngest three" vector-memory operations -- in a wave that skipped this block those are the stores
+                // of the flush just issued, a round trip the wait of accum_take_point is there to avoid
+                __builtin_amdgcn_s_waitcnt(0x0f70);
+            }
         }
         // The next reference and the load of the one after it are UNCONDITIONAL (the index clamped to the job's last
         // reference; past the segment's end the values are not used): assigned under a condition, the loaded word is
@@ -238,13 +287,14 @@ k_bucket_accumulate(const uint4* __restrict__ table, const uint32_t* __restrict_
         ref = ref_next;
         if (e + 1 < end) accum_issue_gather(table, wave_slot, ref);
         ref_next = accum_ref(sorted, min(e + 2, M - 1));  // waited for at the next point, an addition from here
-        if (more) xyzz30_madd_tail(acc, P, R);
+        if (more) xyzz30_acc_tail(acc, P, Rn);
     }
     // last run: [run_start, end)
     uint4* dst;
     if (run_start == b_beg && end == b_end) dst = buckets + (size_t)b * kXyzzU4;  // complete
     else if (run_start == start) dst = part_a + (size_t)lane * kXyzzU4;            // covers the whole segment
     else dst = part_b + (size_t)lane * kXyzzU4;                                    // tail shared with the next lane
+    xyzz30_acc_settle(acc);
     store_xyzz30(dst, acc);
     if (stamp) atomicMax(&clk[1], (unsigned long long)wall_clock64());
 }

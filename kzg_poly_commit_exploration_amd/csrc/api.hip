@@ -72,90 +72,165 @@ enum SlotKind { SLOT_IDLE = 0, SLOT_COMMIT = 1, SLOT_OPEN = 2, SLOT_TRIVIAL = 3,
                 SLOT_OPEN_COMBINED = 8 /* a combined opening: trivial or not, collected by kzg_wait_combined */,
                 SLOT_OPEN_SETS = 9 /* an opening at several point sets: trivial or not, collected by kzg_wait_sets */ };
 
-struct Slot {
+// Sets ctx->last_error to "<what>: <HIP's text>" and returns KZG_ERR_HIP, as HIP_TRY does (defined below kzg_ctx).
+int hip_fail(kzg_ctx* ctx, const char* what, hipError_t e);
+
+// ---- the owners of the context's device and pinned memory -----------------------------------------
+// Both free in their destructor, cannot be copied, and have ONE way to get memory: reserve(), which does nothing when the
+// request fits and otherwise waits for `drain` (the stream whose queued work may still read the old block; none for callers
+// that have waited already), frees, and allocates exactly `bytes`.  Growth DROPS the contents.  After a failed allocation the
+// owner is empty (null, capacity 0).  dev<T>() / host<T>() are the typed views the launchers take.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes of the last reserve() (0 where a setup path filled p itself)
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T = uint32_t> T* dev() const { return (T*)p; }
+    int reserve(kzg_ctx* ctx, size_t bytes, hipStream_t drain = nullptr) { return bytes <= cap ? KZG_OK : grow(ctx, bytes, drain); }
+    int grow(kzg_ctx* ctx, size_t bytes, hipStream_t drain) {
+        if (drain)
+            if (hipError_t e = hipStreamSynchronize(drain)) return hip_fail(ctx, "hipStreamSynchronize", e);
+        reset();
+        if (hipError_t e = hipMalloc(&p, bytes)) {
+            p = nullptr;
+            return hip_fail(ctx, "hipMalloc", e);
+        }
+        cap = bytes;
+        return KZG_OK;
+    }
+};
+// A pinned host block with its device side.  Mapped: the device side is the block's own device address (the kernels write
+// the host's memory directly: flag words, values, the MSM's last partial sums).  Staged: the device side is a device buffer
+// of the same size that the caller fills with a copy on its stream.
+struct PinnedBuf {
+    enum Kind { Mapped, Staged };
+    const Kind kind;
+    void *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    explicit PinnedBuf(Kind k) : kind(k) {}
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { reset(); }
+    void reset() {
+        if (h) hipHostFree(h);
+        if (d && kind == Staged) hipFree(d);
+        h = d = nullptr;
+        cap = 0;
+    }
+    template <class T = uint32_t> T* host() const { return (T*)h; }
+    template <class T = uint32_t> T* dev() const { return (T*)d; }
+    int reserve(kzg_ctx* ctx, size_t bytes, hipStream_t drain = nullptr) { return bytes <= cap ? KZG_OK : grow(ctx, bytes, drain); }
+    int grow(kzg_ctx* ctx, size_t bytes, hipStream_t drain) {
+        if (drain)
+            if (hipError_t e = hipStreamSynchronize(drain)) return hip_fail(ctx, "hipStreamSynchronize", e);
+        reset();
+        hipError_t e = hipHostMalloc(&h, bytes, kind == Mapped ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e == hipSuccess) e = kind == Mapped ? hipHostGetDevicePointer(&d, h, 0) : hipMalloc(&d, bytes);
+        if (e != hipSuccess) {
+            d = nullptr;
+            reset();
+            return hip_fail(ctx, kind == Mapped ? "hipHostMalloc (mapped)" : "hipHostMalloc + hipMalloc (staging)", e);
+        }
+        cap = bytes;
+        return KZG_OK;
+    }
+};
+// The workspaces of one feature, grown on demand under that feature's mutex (its callers have waited for the stream before
+// they ask again: no drain).  A request of 0 bytes still hands out a valid pointer (256 bytes, recorded as 0).
+template <int N>
+struct Workspace {
+    DevBuf buf[N];
+    int get(kzg_ctx* ctx, int i, size_t bytes, void** out) {
+        DevBuf& b = buf[i];
+        int rc = KZG_OK;
+        if (!bytes && !b.p) {
+            rc = b.reserve(ctx, 256);
+            b.cap = 0;
+        } else {
+            rc = b.reserve(ctx, bytes);
+        }
+        *out = b.p;
+        return rc;
+    }
+};
+
+// A slot's stream and events.  They are the base of Slot, so they are destroyed AFTER the slot's buffers (members go first):
+// kzg_ctx_destroy waits for the stream, `delete` frees the buffers, then the events and the stream go.
+struct SlotQueue {
     hipStream_t stream = nullptr;
     hipEvent_t ev[8] = {};
     hipEvent_t done = nullptr;
     hipEvent_t sorted_ev = nullptr, accum_ev = nullptr;  // hand-offs to / from the shared accumulation stream
+    hipEvent_t cmb_ev[2] = {};                           // timed combined openings: around the (last) combination pass
+    hipEvent_t cells_ev = nullptr;                       // kzg_cells_and_proofs: P is in cpoly
+    SlotQueue() = default;
+    SlotQueue(const SlotQueue&) = delete;
+    SlotQueue& operator=(const SlotQueue&) = delete;
+    ~SlotQueue() {
+        for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev[4], ev[5], ev[6], ev[7], cmb_ev[0], cmb_ev[1], cells_ev, done, sorted_ev, accum_ev})
+            if (e) hipEventDestroy(e);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+
+struct Slot : SlotQueue {
     // MSM workspace (sized at SRS load)
-    uint32_t *d_cnt = nullptr, *d_offs = nullptr, *d_block_sums = nullptr;
-    uint64_t* d_pairs = nullptr;
-    uint32_t* d_sorted = nullptr;
-    void* d_buckets = nullptr;
-    void *d_part_a = nullptr, *d_part_b = nullptr;  // head / tail partials of the accumulation segments
-    void* d_pair_scratch = nullptr;  // prefix products of the affine front end (msm_accum.hip)
-    void* d_heavy_ws = nullptr;   // long-bucket registry + tree buffers of msm_finalize.hip
-    void* d_arena = nullptr;     // Row[] then Col[] vectors of the bucket matrix
+    DevBuf cnt, offs, block_sums, pairs, sorted, buckets;
+    DevBuf part_a, part_b;  // head / tail partials of the accumulation segments
+    DevBuf pair_scratch;    // prefix products of the affine front end (msm_accum.hip)
+    DevBuf heavy_ws;        // long-bucket registry + tree buffers of msm_finalize.hip
+    DevBuf arena;           // Row[] then Col[] vectors of the bucket matrix
     // The <= 128 partial sums the host finishes are written by the last reduction kernel STRAIGHT into pinned host
-    // memory (d_final is the device's address of h_final): a copy back is a blit kernel on this runtime, and behind an
-    // accumulation kernel that fills the chip it took 1.3 ms instead of 5 us -- the host collected the job that much
-    // later, submitted the next one that much later, and its sort finished after the accumulation it should have
-    // hidden under (100-240 us of idle chip per commitment; round-3 timeline).
-    void* d_final = nullptr;
-    uint64_t* h_final = nullptr;  // pinned, mapped
-    // polynomial workspace (grown on demand)
-    size_t poly_cap = 0;
-    uint32_t* d_stage = nullptr;  // coefficients copied from the host
-    uint32_t* d_q = nullptr;      // quotient
-    uint32_t* d_chunk = nullptr;
-    uint32_t* d_block = nullptr;
-    // The job's flag words live in pinned host memory that the kernels write directly (d_small is the device's address of
-    // h_small; plain stores only -- every writer of a flag stores the same 1): no memset and no copy-back on the stream.
-    // A 256-byte copy back is a blit kernel here, and queued behind a chip-filling accumulation it sat for ~1 ms between
-    // the job's last kernel and the moment the host could collect it.
-    uint32_t* d_small = nullptr;  // [0..1] flags, [8..15] P(z), [16..23] c0, [24] tail flag, [26] references
-    uint32_t* h_small = nullptr;  // pinned, mapped
-    uint32_t* d_bsmall = nullptr;  // batched openings: 32 words per polynomial, same layout as d_small[0..31]
-    uint32_t* h_bsmall = nullptr;
-    size_t bsmall_cap = 0;
+    // memory: a copy back is a blit kernel on this runtime, and behind an accumulation kernel that fills the chip it took
+    // 1.3 ms instead of 5 us -- the host collected the job that much later, submitted the next one that much later, and
+    // its sort finished after the accumulation it should have hidden under (100-240 us of idle chip per commitment;
+    // round-3 timeline).
+    PinnedBuf fin{PinnedBuf::Mapped};
+    // polynomial workspace (grown on demand, all four together: ensure_poly)
+    DevBuf stage;  // coefficients copied from the host
+    DevBuf q;      // quotient
+    DevBuf chunk, block;
+    // The job's flag words live in pinned host memory that the kernels write directly (plain stores only -- every writer
+    // of a flag stores the same 1): no memset and no copy-back on the stream.  A 256-byte copy back is a blit kernel here,
+    // and queued behind a chip-filling accumulation it sat for ~1 ms between the job's last kernel and the moment the host
+    // could collect it.
+    PinnedBuf small{PinnedBuf::Mapped};   // [0..1] flags, [8..15] P(z), [16..23] c0, [24] tail flag, [26] references
+    PinnedBuf bsmall{PinnedBuf::Mapped};  // batched openings: 32 words per polynomial, same layout as small[0..31]
     std::vector<uint32_t> open_ys;  // y of every polynomial of a batched opening (8 words each)
-    // multiproofs (kzg_open_points): the per-root multipliers go through a pinned staging area to a device buffer, copied
-    // on the slot's stream (a slot holds one job at a time, so nothing in flight reads them while they are rewritten);
-    // the k values P(z_i) land in pinned mapped memory like the flag words; d_pblock: k x nblocks aggregates
-    void* h_roots = nullptr;
-    void* d_roots = nullptr;
-    uint32_t* h_pvals = nullptr;
-    uint32_t* d_pvals = nullptr;
-    uint32_t* d_pblock = nullptr;
-    size_t pblock_words = 0;
+    // multiproofs (kzg_open_points): the per-root multipliers are copied on the slot's stream (a slot holds one job at a
+    // time, so nothing in flight reads them while they are rewritten); the k values P(z_i) land in mapped memory like the
+    // flag words; pblock: k x nblocks aggregates
+    PinnedBuf roots{PinnedBuf::Staged};
+    PinnedBuf pvals{PinnedBuf::Mapped};
+    DevBuf pblock;
     std::vector<uint32_t> pts_ys;  // the claims (8 words each)
     size_t pts_nq = 0;             // terms of the job's MSM (0: the proof is infinity once the claims hold)
-    // combined openings (kzg_open_combined): the call's multipliers (powers of z, gamma^i) go through a
-    // pinned staging area to a device table like the roots of a multiproof; the t values P_i(z) land in pinned mapped memory;
-    // F is built in d_stage.  d_cpart: the (polynomial, tile) records of one pass; d_cin: the polynomials of one pass of the
-    // host-pointer call.  All grown on demand.
-    void* h_ctab = nullptr;
-    void* d_ctab = nullptr;
-    uint32_t* h_cvals = nullptr;
-    uint32_t* d_cvals = nullptr;
-    uint32_t* d_cpart = nullptr;
-    size_t cpart_words = 0;
-    uint32_t* d_cin = nullptr;
-    size_t cin_coeffs = 0;
-    size_t cmb_t = 0;              // polynomials of the job in flight
-    hipEvent_t cmb_ev[2] = {};     // timed jobs: around the (last) combination pass
+    // combined openings (kzg_open_combined): the call's multipliers (powers of z, gamma^i) in ctab,
+    // the t values P_i(z) in cvals; F is built in stage.  cpart: the (polynomial, tile) records of one pass; cin: the
+    // polynomials of one pass of the host-pointer call.
+    PinnedBuf ctab{PinnedBuf::Staged};
+    PinnedBuf cvals{PinnedBuf::Mapped};
+    DevBuf cpart, cin;
+    size_t cmb_t = 0;  // polynomials of the job in flight
     float combine_ms = 0;
     // openings at several point sets (kzg_open_sets): the pass tables (66 powers per distinct point,
-    // then one multiplier per (point, polynomial opened there)) and the selection lists go through pinned staging areas to
-    // the device like the table above; the values land in pinned mapped memory in pass order and sets_vmap says where each
-    // entry of out_ys sits; d_sg: the G_p, |T| x n values, grown on demand.  The passes share d_cpart / d_cin, the scans the
-    // multiproof's root and aggregate buffers.
-    void* h_stab = nullptr;
-    void* d_stab = nullptr;
-    uint32_t* h_ssel = nullptr;
-    uint32_t* d_ssel = nullptr;
-    uint32_t* h_svals = nullptr;
-    uint32_t* d_svals = nullptr;
-    uint32_t* d_sg = nullptr;
-    size_t sg_coeffs = 0;
+    // then one multiplier per (point, polynomial opened there)) in stab and the selection lists in ssel; the values land in
+    // svals in pass order and sets_vmap says where each entry of out_ys sits; sg: the G_p, |T| x n values.  The passes share
+    // cpart / cin, the scans the multiproof's root and aggregate buffers.
+    PinnedBuf stab{PinnedBuf::Staged}, ssel{PinnedBuf::Staged};
+    PinnedBuf svals{PinnedBuf::Mapped};
+    DevBuf sg;
     std::vector<uint32_t> sets_vmap;
-    // cells of a domain (kzg_cells_and_proofs): P for the whole call in d_cpoly (read by the sub-batches of every slot the call
-    // holds, after cells_ev), the chunk aggregates of the cell quotients in d_cagg
-    uint32_t* d_cpoly = nullptr;
-    size_t cpoly_cap = 0;
-    uint32_t* d_cagg = nullptr;
-    uint64_t cagg_words = 0;
-    hipEvent_t cells_ev = nullptr;
+    // cells of a domain (kzg_cells_and_proofs): P for the whole call in cpoly (read by the sub-batches of every slot the call
+    // holds, after cells_ev), the chunk aggregates of the cell quotients in cagg
+    DevBuf cpoly, cagg;
     // state of the job in flight
     SlotKind kind = SLOT_IDLE;
     size_t job_n = 0;
@@ -186,8 +261,8 @@ struct kzg_ctx {
     // SRS
     size_t n = 0;  // points
     MsmConfig cfg = {};
-    void* d_table = nullptr;  // W * n affine points
-    void* d_ntt_tw = nullptr;  // NTT twiddles, built on first use: forward lo, forward hi, inverse lo, inverse hi (ntt_kernels.hip)
+    DevBuf table;   // W * n affine points
+    DevBuf ntt_tw;  // NTT twiddles, built on first use: forward lo, forward hi, inverse lo, inverse hi (ntt_kernels.hip)
     ReducePlan plan;
     size_t arena_records = 0, final_records = 0;  // per polynomial of a batch
     uint32_t max_batch = 1;                        // polynomials per submit the workspaces are sized for
@@ -208,30 +283,25 @@ struct kzg_ctx {
     bool timing = false;
     // FK20 (kzg_cells_and_proofs_fk20), all under fk20_mu (taken before mu): the GLV-split twiddles
     // of w_(2^glv_log), built on first use and grown; the SRS side of one shape (L = 2^fk20_log_L, l = 2^fk20_log_l): the
-    // transforms DFT_L(S_r) in d_fk20_B and, when they fit the budget, their comb tables in d_fk20_tab (both dropped with
+    // transforms DFT_L(S_r) in fk20_B and, when they fit the budget, their comb tables in fk20_tab (both dropped with
     // the SRS); workspaces grown on demand
     std::mutex fk20_mu;
-    void* d_glv = nullptr;
+    DevBuf glv;
     uint32_t glv_log = 0;
-    void* d_fk20_B = nullptr;
-    void* d_fk20_tab = nullptr;
+    DevBuf fk20_B, fk20_tab;
     uint32_t fk20_log_L = 0, fk20_log_l = 0;
-    void* fk20_ws[11] = {};
-    size_t fk20_ws_bytes[11] = {};
+    Workspace<11> fk20_ws;
     // recovery (kzg_recover_cells_and_proofs), under recover_mu (taken before mu): the g-power tables
     // g^i, g^-i (g = 7) in the NTT twiddles' lo / hi shape, built on first use; workspaces grown on demand
     std::mutex recover_mu;
-    void* d_rec_g = nullptr;
-    void* rec_ws[11] = {};
-    size_t rec_ws_bytes[11] = {};
+    DevBuf rec_g;
+    Workspace<11> rec_ws;
     // batch verification of cells (kzg_verify_cells_batch): workspaces grown on demand, under fk20_mu
-    // (the call reads the split twiddles d_glv, which an FK20 call may grow)
-    void* vc_ws[17] = {};
-    size_t vc_ws_bytes[17] = {};
+    // (the call reads the split twiddles glv, which an FK20 call may grow)
+    Workspace<17> vc_ws;
     // the producing side on blob bytes (kzg_blobs_to_cells_and_proofs_bytes): workspaces grown on demand,
     // under fk20_mu (the calls run FK20 from them)
-    void* blob_ws[8] = {};
-    size_t blob_ws_bytes[8] = {};
+    Workspace<8> blob_ws;
 };
 
 namespace {
@@ -245,32 +315,41 @@ namespace {
         }                                                                                           \
     } while (0)
 
-// scope guards for the setup paths (several HIP_TRY early returns)
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
+int hip_fail(kzg_ctx* ctx, const char* what, hipError_t e) {
+    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return KZG_ERR_HIP;
+}
+
+// scope guard for the setup paths (several HIP_TRY early returns; their buffers are DevBufs)
 struct TmpStream {
     hipStream_t s = nullptr;
     ~TmpStream() { if (s) hipStreamDestroy(s); }
 };
 
-void free_slot_msm(Slot& s) {
-    hipFree(s.d_cnt); hipFree(s.d_offs); hipFree(s.d_block_sums); hipFree(s.d_pairs); hipFree(s.d_sorted);
-    hipFree(s.d_buckets); hipFree(s.d_part_a); hipFree(s.d_part_b); hipFree(s.d_heavy_ws); hipFree(s.d_arena);
-    hipFree(s.d_pair_scratch);
-    s.d_pair_scratch = nullptr;
-    if (s.h_final) hipHostFree(s.h_final);
-    s.d_cnt = s.d_offs = s.d_block_sums = s.d_sorted = nullptr;
-    s.d_pairs = nullptr;
-    s.d_buckets = s.d_part_a = s.d_part_b = s.d_arena = s.d_final = nullptr;
-    s.d_heavy_ws = nullptr;
-    s.h_final = nullptr;
+// Waits for the stream without ctx->mu, so that the context's other calls go on meanwhile (the caller's slot keeps an SRS
+// replacement out, its feature's mutex the other calls of its kind).  `what` starts the text an error leaves.
+int sync_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const char* what) {
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(st);
+    lk.lock();
+    return e == hipSuccess ? KZG_OK : hip_fail(ctx, what, e);
 }
-void free_slot_poly(Slot& s) {
-    hipFree(s.d_stage); hipFree(s.d_q); hipFree(s.d_chunk); hipFree(s.d_block);
-    s.d_stage = s.d_q = s.d_chunk = s.d_block = nullptr;
-    s.poly_cap = 0;
+// A copy on the stream without ctx->mu (pageable host memory: the call may block).
+constexpr const char* kCopyCoeffs = "hipMemcpyAsync (coefficients)";
+int copy_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, void* dst, const void* src, size_t bytes,
+                  hipMemcpyKind kind, const char* what) {
+    if (!bytes) return KZG_OK;
+    lk.unlock();
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+    lk.lock();
+    return e == hipSuccess ? KZG_OK : hip_fail(ctx, what, e);
+}
+
+void free_slot_msm(Slot& s) {
+    for (DevBuf* b : {&s.cnt, &s.offs, &s.block_sums, &s.pairs, &s.sorted, &s.buckets, &s.part_a, &s.part_b, &s.pair_scratch,
+                      &s.heavy_ws, &s.arena})
+        b->reset();
+    s.fin.reset();
 }
 
 // stream, events and the small flag buffers of a slot (what kzg_quotient / kzg_evaluate need without an SRS)
@@ -288,22 +367,21 @@ int ensure_slot_basics(kzg_ctx* ctx, Slot& s) {
     }
     for (auto& e : s.ev) HIP_TRY(ctx, hipEventCreate(&e));
     HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipHostMalloc(&s.h_small, 64 * 4, hipHostMallocMapped));
-    HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_small, s.h_small, 0));
-    return KZG_OK;
+    return s.small.reserve(ctx, 64 * 4);
 }
 
+// the four polynomial buffers grow together, to at least 1024 coefficients
 int ensure_poly(kzg_ctx* ctx, Slot& s, size_t n) {
-    if (n <= s.poly_cap && s.d_stage) return KZG_OK;
+    const size_t cap = n < 1024 ? 1024 : n;
+    if (cap * 32 <= s.stage.cap) return KZG_OK;
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    free_slot_poly(s);
-    size_t cap = n < 1024 ? 1024 : n;
-    HIP_TRY(ctx, hipMalloc(&s.d_stage, cap * 32));
-    HIP_TRY(ctx, hipMalloc(&s.d_q, cap * 32));
-    HIP_TRY(ctx, hipMalloc(&s.d_chunk, poly_chunk_words((uint32_t)cap) * 4));
-    HIP_TRY(ctx, hipMalloc(&s.d_block, poly_block_words((uint32_t)cap) * 4));
-    s.poly_cap = cap;
-    return KZG_OK;
+    for (DevBuf* b : {&s.stage, &s.q, &s.chunk, &s.block}) b->reset();
+    int rc = s.stage.reserve(ctx, cap * 32);
+    if (rc == KZG_OK) rc = s.q.reserve(ctx, cap * 32);
+    if (rc == KZG_OK) rc = s.chunk.reserve(ctx, poly_chunk_words((uint32_t)cap) * 4);
+    if (rc == KZG_OK) rc = s.block.reserve(ctx, poly_block_words((uint32_t)cap) * 4);
+    if (rc) s.stage.reset();  // (its capacity stands for all four)
+    return rc;
 }
 
 // reduction plan: depends only on the bucket count
@@ -336,10 +414,7 @@ int setup_slots(kzg_ctx* ctx, bool keep_table_on_failure = false) {
     if (rc != KZG_OK) {
         for (auto& s : ctx->slots) free_slot_msm(s);
         if (keep_table_on_failure) return rc;  // the caller retries with the previous sizes
-        if (ctx->d_table) {
-            hipFree(ctx->d_table);
-            ctx->d_table = nullptr;
-        }
+        ctx->table.reset();
         ctx->n = 0;
         (void)hipGetLastError();
     }
@@ -376,33 +451,33 @@ int setup_slots_impl(kzg_ctx* ctx) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&s.accum_ev, hipEventDisableTiming));
         }
         free_slot_msm(s);
-        HIP_TRY(ctx, hipMalloc(&s.d_cnt, (size_t)sort_count_entries((uint32_t)B, cfg) * 4 + 64));
-        HIP_TRY(ctx, hipMalloc(&s.d_offs, ((size_t)cfg.nb * B + 1) * 4));
-        HIP_TRY(ctx, hipMalloc(&s.d_block_sums, (size_t)sort_workspace_words() * 4));  // bin starts, chunk plan, fill counters, fine-pass table
-        HIP_TRY(ctx, hipMemset(s.d_block_sums, 0, (size_t)sort_workspace_zero_words() * 4));
-        HIP_TRY(ctx, hipMalloc(&s.d_pairs, (pairs ? pairs : 1) * 8));
-        HIP_TRY(ctx, hipMalloc(&s.d_sorted, (pairs ? pairs : 1) * 4));
-        HIP_TRY(ctx, hipMalloc(&s.d_buckets, (size_t)cfg.nb * B * kXyzzBytes));
-        HIP_TRY(ctx, hipMalloc(&s.d_part_a, (size_t)kMaxAccumLanes * kXyzzBytes));
-        HIP_TRY(ctx, hipMalloc(&s.d_part_b, (size_t)kMaxAccumLanes * kXyzzBytes));
-        if (const size_t pair_bytes = accumulate_pair_scratch_bytes(pairs))  // only with KZG_ACCUM_PAIRS=1
-            HIP_TRY(ctx, hipMalloc(&s.d_pair_scratch, pair_bytes));
-        HIP_TRY(ctx, hipMalloc(&s.d_heavy_ws, heavy_workspace_bytes()));
-        HIP_TRY(ctx, hipMalloc(&s.d_arena, ctx->arena_records * B * kXyzzBytes));
-        HIP_TRY(ctx, hipHostMalloc(&s.h_final, ctx->final_records * B * kXyzzBytes, hipHostMallocMapped));
-        HIP_TRY(ctx, hipHostGetDevicePointer(&s.d_final, s.h_final, 0));
+        int rc = s.cnt.reserve(ctx, (size_t)sort_count_entries((uint32_t)B, cfg) * 4 + 64);
+        if (rc == KZG_OK) rc = s.offs.reserve(ctx, ((size_t)cfg.nb * B + 1) * 4);
+        if (rc == KZG_OK) rc = s.block_sums.reserve(ctx, (size_t)sort_workspace_words() * 4);  // bin starts, chunk plan, fill counters, fine-pass table
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemset(s.block_sums.p, 0, (size_t)sort_workspace_zero_words() * 4));
+        rc = s.pairs.reserve(ctx, (pairs ? pairs : 1) * 8);
+        if (rc == KZG_OK) rc = s.sorted.reserve(ctx, (pairs ? pairs : 1) * 4);
+        if (rc == KZG_OK) rc = s.buckets.reserve(ctx, (size_t)cfg.nb * B * kXyzzBytes);
+        if (rc == KZG_OK) rc = s.part_a.reserve(ctx, (size_t)kMaxAccumLanes * kXyzzBytes);
+        if (rc == KZG_OK) rc = s.part_b.reserve(ctx, (size_t)kMaxAccumLanes * kXyzzBytes);
+        if (rc == KZG_OK) rc = s.pair_scratch.reserve(ctx, accumulate_pair_scratch_bytes(pairs));  // 0 without KZG_ACCUM_PAIRS=1
+        if (rc == KZG_OK) rc = s.heavy_ws.reserve(ctx, heavy_workspace_bytes());
+        if (rc == KZG_OK) rc = s.arena.reserve(ctx, ctx->arena_records * B * kXyzzBytes);
+        if (rc == KZG_OK) rc = s.fin.reserve(ctx, ctx->final_records * B * kXyzzBytes);
+        if (rc) return rc;
         s.kind = SLOT_IDLE;
     }
     ctx->slots_ready = true;
     return KZG_OK;
 }
 
-// builds levels 1..W-1 of the table from level 0 (already in d_table[0..n))
+// builds levels 1..W-1 of the table from level 0 (already in table[0..n))
 int build_tables(kzg_ctx* ctx, hipStream_t st, void* d_xyzz_tmp, void* d_prefix) {
     const size_t n = ctx->n;
     for (uint32_t j = 1; j < ctx->cfg.W; j++) {
-        char* prev = (char*)ctx->d_table + (size_t)(j - 1) * n * kAffineBytes;
-        char* next = (char*)ctx->d_table + (size_t)j * n * kAffineBytes;
+        char* prev = (char*)ctx->table.p + (size_t)(j - 1) * n * kAffineBytes;
+        char* next = (char*)ctx->table.p + (size_t)j * n * kAffineBytes;
         launch_table_window(st, prev, (uint32_t)n, ctx->cfg.level_bits, d_xyzz_tmp, d_prefix, next);
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -423,15 +498,9 @@ static int srs_release(kzg_ctx* ctx) {
     int rc = drain_all(ctx);
     if (rc) return rc;
     for (auto& s : ctx->slots) s.kind = SLOT_IDLE;
-    if (ctx->d_table) {
-        hipFree(ctx->d_table);
-        ctx->d_table = nullptr;
-    }
-    if (ctx->d_fk20_B) {  // the FK20 cache holds transforms of the old SRS
-        hipFree(ctx->d_fk20_B);
-        hipFree(ctx->d_fk20_tab);
-        ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
-    }
+    ctx->table.reset();
+    ctx->fk20_B.reset();  // the FK20 cache holds transforms of the old SRS
+    ctx->fk20_tab.reset();
     ctx->n = 0;
     return KZG_OK;
 }
@@ -449,8 +518,7 @@ int srs_prepare(kzg_ctx* ctx, size_t n) {
     MsmConfig cfg = choose_msm_config(n, budget);
     if ((size_t)cfg.W * n >= 0x80000000ull) return KZG_ERR_INVALID_ARG;  // table index must fit 31 bits
     ctx->cfg = cfg;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_table, (size_t)cfg.W * n * kAffineBytes));
-    return KZG_OK;
+    return ctx->table.reserve(ctx, (size_t)cfg.W * n * kAffineBytes);
 }
 
 // enqueue `batch` MSMs of n scalars each (polynomial p at d_scalars + p * stride scalars) on slot s
@@ -460,8 +528,8 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
     const uint32_t nbt = cfg.nb * batch;  // polynomial-major bucket ids
     hipStream_t st = s.stream;
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base], st));
-    const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, (uint32_t)ctx->n, cfg, s.d_cnt,
-                       s.d_block_sums, s.d_pairs, s.d_offs, s.d_sorted, (uint32_t*)s.d_heavy_ws);
+    const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, (uint32_t)ctx->n, cfg, s.cnt.dev(),
+                       s.block_sums.dev(), s.pairs.dev<uint64_t>(), s.offs.dev(), s.sorted.dev(), (uint32_t*)s.heavy_ws.p);
     if (s.timing) {
         HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 1], st));
         HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 2], st));
@@ -474,25 +542,25 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
     // Vectors are polynomial-major ([p][index]); the final buffer holds four sections [p][len_k].
     const ReducePlan& P = ctx->plan;
     const uint32_t R = 1u << P.hi_bits, C = 1u << P.lo_bits, B = batch;
-    char* row = (char*)s.d_arena;
+    char* row = (char*)s.arena.p;
     char* col = row + (size_t)R * B * kXyzzBytes;
-    char* fin = (char*)s.d_final;
+    char* fin = (char*)s.fin.d;
     const uint32_t rl = 1u << P.row_lo, rh = 1u << P.row_hi, cl = 1u << P.col_lo, ch = 1u << P.col_hi;
     const TreeSumDesc stage1[2] = {
-        {s.d_buckets, row, B * R, C, C, 1, B * R, 0},           // Row[p][hi] = sum_lo Bk[p][hi*C + lo]
-        {s.d_buckets, col, B * C, R, 1, C, C, (uint64_t)cfg.nb}};  // Col[p][lo] = sum_hi Bk[p][hi*C + lo]
+        {s.buckets.p, row, B * R, C, C, 1, B * R, 0},           // Row[p][hi] = sum_lo Bk[p][hi*C + lo]
+        {s.buckets.p, col, B * C, R, 1, C, C, (uint64_t)cfg.nb}};  // Col[p][lo] = sum_hi Bk[p][hi*C + lo]
     const TreeSumDesc stage2[4] = {
         {row, fin + (size_t)P.off_r2row * B * kXyzzBytes, B * rh, rl, rl, 1, rh, R},
         {row, fin + (size_t)P.off_c2row * B * kXyzzBytes, B * rl, rh, 1, rl, rl, R},
         {col, fin + (size_t)P.off_r2col * B * kXyzzBytes, B * ch, cl, cl, 1, ch, C},
         {col, fin + (size_t)P.off_c2col * B * kXyzzBytes, B * cl, ch, 1, cl, cl, C}};
-    if (!header_zeroed) HIP_TRY(ctx, hipMemsetAsync(s.d_heavy_ws, 0, kHeavyHeaderBytes, st));  // long-bucket counters, phase counters
+    if (!header_zeroed) HIP_TRY(ctx, hipMemsetAsync(s.heavy_ws.p, 0, kHeavyHeaderBytes, st));  // long-bucket counters, phase counters
     if (max_refs <= kTinyRefs && !ctx->small_msm_off) {
         // Small jobs are chains of dependent additions on a nearly empty chip: everything from here to the copy back
         // in ONE launch on the slot's own stream (msm_finalize.hip: k_small_msm), no bucket memset, no stream hand-over.
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 3], st));
-        launch_small_msm(st, ctx->d_table, s.d_sorted, s.d_offs, nbt, lanes, max_refs, s.d_buckets, s.d_part_a, s.d_part_b,
-                         s.d_heavy_ws, s.d_small + 26, stage1, stage2, ctx->small_lds_bytes);
+        launch_small_msm(st, ctx->table.p, s.sorted.dev(), s.offs.dev(), nbt, lanes, max_refs, s.buckets.p, s.part_a.p, s.part_b.p,
+                         s.heavy_ws.p, s.small.dev() + 26, stage1, stage2, ctx->small_lds_bytes);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], st));
     } else {
         // hand over to the shared accumulation stream and back (each hand-over costs ~12 us: not when no other slot
@@ -504,22 +572,22 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
             HIP_TRY(ctx, hipStreamWaitEvent(hs, s.sorted_ev, 0));
         }
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 3], hs));
-        launch_bucket_accumulate(hs, ctx->d_table, s.d_sorted, s.d_offs, nbt, lanes, s.d_buckets, s.d_part_a, s.d_part_b,
-                                 ctx->accum_lds_bytes, s.d_pair_scratch, max_refs,
-                                 (char*)s.d_heavy_ws + kAccumClockOffset);
+        launch_bucket_accumulate(hs, ctx->table.p, s.sorted.dev(), s.offs.dev(), nbt, lanes, s.buckets.p, s.part_a.p, s.part_b.p,
+                                 ctx->accum_lds_bytes, s.pair_scratch.p, max_refs,
+                                 (char*)s.heavy_ws.p + kAccumClockOffset);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], hs));
         if (hand_over) {
             HIP_TRY(ctx, hipEventRecord(s.accum_ev, hs));
             HIP_TRY(ctx, hipStreamWaitEvent(st, s.accum_ev, 0));
         }
-        launch_bucket_finalize(st, s.d_offs, nbt, lanes, s.d_part_a, s.d_part_b, s.d_buckets, s.d_heavy_ws, s.d_small + 26,
+        launch_bucket_finalize(st, s.offs.dev(), nbt, lanes, s.part_a.p, s.part_b.p, s.buckets.p, s.heavy_ws.p, s.small.dev() + 26,
                                finalize_group_size(nbt));
         // (Rounds 1-2 put a gate kernel here that deferred the reduction trees to the tail of the next slot's
         // accumulation: worth 20 % with round 1's 206-VGPR accumulation kernel, beside which the trees could become
         // resident; the trees (243-258 VGPRs) cannot start beside round 3's accumulation kernel whatever the stream
         // order says, and with or without a gate -- LDS-sized or a device-side count of running workgroups -- round 3
         // measured 409 / 384 against 408 / 383 and 414 / 386 against 415 / 386 commitments / proofs per second.  Retired.)
-        launch_tree_sums_two_stage(st, stage1, 2, stage2, 4, (uint32_t*)s.d_heavy_ws + 64, alone);
+        launch_tree_sums_two_stage(st, stage1, 2, stage2, 4, (uint32_t*)s.heavy_ws.p + 64, alone);
     }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 5], st));
     HIP_TRY(ctx, hipGetLastError());
@@ -542,7 +610,7 @@ hf::PX host_shift(hf::PX p, uint32_t k) {
 }
 hf::P1 finish_msm(const kzg_ctx* ctx, const Slot& s, uint32_t p = 0, uint32_t batch = 1) {
     const ReducePlan& P = ctx->plan;
-    const uint64_t* f = s.h_final;
+    const uint64_t* f = s.fin.host<uint64_t>();
     // section k of the final buffer is [batch][len_k]: polynomial p's block starts at off_k*batch + p*len_k
     auto at = [&](uint32_t off, uint32_t len) { return f + ((size_t)off * batch + (size_t)p * len) * kXyzzWords64; };
     const uint32_t rh = 1u << P.row_hi, rl = 1u << P.row_lo, ch = 1u << P.col_hi, cl = 1u << P.col_lo;
@@ -563,14 +631,14 @@ hf::P1 finish_msm(const kzg_ctx* ctx, const Slot& s, uint32_t p = 0, uint32_t ba
 void write_p1(uint64_t out[18], const hf::P1& p) { std::memcpy(out, &p, sizeof p); }
 
 // EVERY job: accumulate_ms is the accumulation kernel's own duration -- first wave in to last wave out on the constant
-// 100 MHz clock, stamped by the kernel and passed on by the finalisation (h_small[28..31]; the one-launch path of
+// 100 MHz clock, stamped by the kernel and passed on by the finalisation (small[28..31]; the one-launch path of
 // small jobs leaves it 0) -- and `references` its number of mixed additions: no stream event is involved.  Timed jobs
 // (kzg_set_timing) also get the HIP-event spans; accumulate_events_ms is the bracket around the same launch on its
 // stream, which holds the time the launch waited for the chip as well.
 void fill_device_times(Slot& s) {
-    s.times.references = s.h_small[26];
-    const uint64_t not_start = (uint64_t)s.h_small[28] | ((uint64_t)s.h_small[29] << 32);
-    const uint64_t end = (uint64_t)s.h_small[30] | ((uint64_t)s.h_small[31] << 32);
+    s.times.references = s.small.host()[26];
+    const uint64_t not_start = (uint64_t)s.small.host()[28] | ((uint64_t)s.small.host()[29] << 32);
+    const uint64_t end = (uint64_t)s.small.host()[30] | ((uint64_t)s.small.host()[31] << 32);
     if (not_start != 0 && end > ~not_start) s.times.accumulate_ms = (float)((double)(end - ~not_start) * 1e-5);  // 10 ns ticks
 }
 void fill_accumulate_times(Slot& s) {  // timed jobs, after fill_device_times
@@ -638,45 +706,33 @@ int points_weights(kzg_ctx* ctx, const uint64_t* zs, size_t k, uint64_t* ws /* 4
 }
 // the slot's multiproof buffers for k roots over n coefficients (slot basics already there)
 int ensure_points(kzg_ctx* ctx, Slot& s, size_t n, size_t k) {
-    if (!s.h_roots) {
-        HIP_TRY(ctx, hipHostMalloc(&s.h_roots, KZG_MAX_OPEN_POINTS * points_root_bytes(), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc(&s.d_roots, KZG_MAX_OPEN_POINTS * points_root_bytes()));
-        HIP_TRY(ctx, hipHostMalloc(&s.h_pvals, KZG_MAX_OPEN_POINTS * 32, hipHostMallocMapped));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_pvals, s.h_pvals, 0));
-    }
-    const size_t words = k * poly_block_words((uint32_t)(n ? n : 1));
-    if (words > s.pblock_words) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        hipFree(s.d_pblock);
-        s.d_pblock = nullptr;
-        s.pblock_words = 0;
-        HIP_TRY(ctx, hipMalloc(&s.d_pblock, words * 4));
-        s.pblock_words = words;
-    }
-    return KZG_OK;
+    int rc = s.roots.reserve(ctx, KZG_MAX_OPEN_POINTS * points_root_bytes());
+    if (rc == KZG_OK) rc = s.pvals.reserve(ctx, KZG_MAX_OPEN_POINTS * 32);
+    if (rc == KZG_OK) rc = s.pblock.reserve(ctx, k * poly_block_words((uint32_t)(n ? n : 1)) * 4, s.stream);
+    return rc;
 }
 // where the scan of a multiproof leaves P(z_i): the single-root kernels (k == 1) write the slot's flag words
-const uint32_t* points_values(const Slot& s, size_t k) { return k == 1 ? s.h_small + 8 : s.h_pvals; }
-// enqueues the scan of P at the k points on the slot's stream: q[0 .. nq) to s.d_q when want_q, the values as above.
+const uint32_t* points_values(const Slot& s, size_t k) { return k == 1 ? s.small.host() + 8 : s.pvals.host(); }
+// enqueues the scan of P at the k points on the slot's stream: q[0 .. nq) to s.q when want_q, the values as above.
 // k == 1 takes the single-root kernels unchanged (w_0 = 1), so its proofs are kzg_open's bit for bit.
 int enqueue_points_scan(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, const uint64_t* zs, const uint64_t* ws,
                         size_t k, size_t nq, bool want_q) {
-    std::memset(s.h_small, 0, 64 * 4);  // (the slot holds no job in flight: nothing writes them now)
-    std::memset(s.h_pvals, 0, 32 * k);
+    std::memset(s.small.host(), 0, 64 * 4);  // (the slot holds no job in flight: nothing writes them now)
+    std::memset(s.pvals.host(), 0, 32 * k);
     if (n == 0) return KZG_OK;           // P = 0: every value is zero
     if (k == 1) {
         uint32_t zw[8];
         std::memcpy(zw, zs, 32);
-        uint32_t* q = want_q && n > 1 ? s.d_q : nullptr;
-        if (!launch_quotient_single(s.stream, d_coeffs, (uint32_t)n, zw, q, s.d_small)) {
-            PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
+        uint32_t* q = want_q && n > 1 ? s.q.dev() : nullptr;
+        if (!launch_quotient_single(s.stream, d_coeffs, (uint32_t)n, zw, q, s.small.dev())) {
+            PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
             launch_quotient(s.stream, d_coeffs, (uint32_t)n, zw, q, sc);
         }
     } else {
-        points_fill_roots(s.h_roots, zs, ws, (uint32_t)k, (uint32_t)n);
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_roots, s.h_roots, k * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
-        launch_quotient_points(s.stream, d_coeffs, (uint32_t)n, s.d_roots, (uint32_t)k, want_q ? s.d_q : nullptr, (uint32_t)nq,
-                               s.d_pblock, s.d_pvals);
+        points_fill_roots(s.roots.h, zs, ws, (uint32_t)k, (uint32_t)n);
+        HIP_TRY(ctx, hipMemcpyAsync(s.roots.d, s.roots.h, k * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
+        launch_quotient_points(s.stream, d_coeffs, (uint32_t)n, s.roots.d, (uint32_t)k, want_q ? s.q.dev() : nullptr, (uint32_t)nq,
+                               s.pblock.dev(), s.pvals.dev());
     }
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
@@ -785,50 +841,11 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
                      (unsigned long long)ctx->trace_calls.load(), k * ctx->trace_ns[0].load(), k * ctx->trace_ns[1].load(),
                      k * ctx->trace_ns[2].load(), k * ctx->trace_ns[3].load(), k * ctx->trace_ns[4].load());
     }
-    for (auto& s : ctx->slots) {
+    // What has an order: every slot's stream is waited for before any buffer goes.  `delete` then frees the slots' buffers
+    // (members) and after them each slot's events and stream (its base, SlotQueue), between the context's own buffers.
+    for (auto& s : ctx->slots)
         if (s.stream) hipStreamSynchronize(s.stream);
-        free_slot_msm(s);
-        free_slot_poly(s);
-        if (s.h_small) hipHostFree(s.h_small);
-        if (s.h_bsmall) hipHostFree(s.h_bsmall);
-        if (s.h_roots) hipHostFree(s.h_roots);
-        if (s.h_pvals) hipHostFree(s.h_pvals);
-        hipFree(s.d_roots);
-        hipFree(s.d_pblock);
-        if (s.h_ctab) hipHostFree(s.h_ctab);
-        if (s.h_cvals) hipHostFree(s.h_cvals);
-        hipFree(s.d_ctab);
-        hipFree(s.d_cpart);
-        hipFree(s.d_cin);
-        if (s.h_stab) hipHostFree(s.h_stab);
-        if (s.h_ssel) hipHostFree(s.h_ssel);
-        if (s.h_svals) hipHostFree(s.h_svals);
-        hipFree(s.d_stab);
-        hipFree(s.d_ssel);
-        hipFree(s.d_sg);
-        for (auto& e : s.cmb_ev)
-            if (e) hipEventDestroy(e);
-        hipFree(s.d_cpoly);
-        hipFree(s.d_cagg);
-        if (s.cells_ev) hipEventDestroy(s.cells_ev);
-        for (auto& e : s.ev)
-            if (e) hipEventDestroy(e);
-        if (s.done) hipEventDestroy(s.done);
-        if (s.sorted_ev) hipEventDestroy(s.sorted_ev);
-        if (s.accum_ev) hipEventDestroy(s.accum_ev);
-        if (s.stream) hipStreamDestroy(s.stream);
-    }
-    if (ctx->heavy_stream) hipStreamDestroy(ctx->heavy_stream);
-    if (ctx->d_table) hipFree(ctx->d_table);
-    if (ctx->d_ntt_tw) hipFree(ctx->d_ntt_tw);
-    if (ctx->d_glv) hipFree(ctx->d_glv);
-    if (ctx->d_fk20_B) hipFree(ctx->d_fk20_B);
-    if (ctx->d_fk20_tab) hipFree(ctx->d_fk20_tab);
-    for (void* p : ctx->fk20_ws) hipFree(p);
-    if (ctx->d_rec_g) hipFree(ctx->d_rec_g);
-    for (void* p : ctx->rec_ws) hipFree(p);
-    for (void* p : ctx->vc_ws) hipFree(p);
-    for (void* p : ctx->blob_ws) hipFree(p);
+    if (ctx->heavy_stream) hipStreamDestroy(ctx->heavy_stream);  // (idle: every accumulation hands back to a slot's stream)
     delete ctx;
 }
 
@@ -869,7 +886,7 @@ int kzg_srs_load_g1(kzg_ctx* ctx, const void* first_g1, size_t stride, size_t n)
     HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     HIP_TRY(ctx, hipMemcpyAsync(d_jac.p, packed.data(), n * 144, hipMemcpyHostToDevice, st.s));
     ctx->n = n;
-    launch_jacobian_to_affine(st.s, d_jac.p, (uint32_t)n, ctx->d_table, d_prefix.p);
+    launch_jacobian_to_affine(st.s, d_jac.p, (uint32_t)n, ctx->table.p, d_prefix.p);
     rc = build_tables(ctx, st.s, d_xyzz.p, d_prefix.p);
     if (rc) {
         ctx->n = 0;
@@ -904,7 +921,7 @@ int kzg_srs_generate_g1(kzg_ctx* ctx, const uint8_t secret_be[32], uint64_t firs
     TmpStream st;
     HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     ctx->n = n;
-    launch_srs_generate(st.s, raw, first, (uint32_t)n, d_gtable.p, d_xyzz.p, d_prefix.p, ctx->d_table);
+    launch_srs_generate(st.s, raw, first, (uint32_t)n, d_gtable.p, d_xyzz.p, d_prefix.p, ctx->table.p);
     rc = build_tables(ctx, st.s, d_xyzz.p, d_prefix.p);
     if (rc) {
         ctx->n = 0;
@@ -913,7 +930,7 @@ int kzg_srs_generate_g1(kzg_ctx* ctx, const uint8_t secret_be[32], uint64_t firs
     return setup_slots(ctx);
 }
 
-// level 0 is in d_table (builder's form): build the other levels, convert, size the slots
+// level 0 is in table (builder's form): build the other levels, convert, size the slots
 static int finish_srs_from_level0(kzg_ctx* ctx, hipStream_t st, size_t n) {
     DevBuf d_prefix, d_xyzz;
     HIP_TRY(ctx, hipMalloc(&d_prefix.p, n * 64));
@@ -943,7 +960,7 @@ int kzg_srs_load_affine(kzg_ctx* ctx, const void* affine_xy, size_t n) {
     TmpStream st;
     HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     HIP_TRY(ctx, hipMemcpyAsync(d_in.p, affine_xy, n * 96, hipMemcpyHostToDevice, st.s));
-    launch_affine96_to_table(st.s, d_in.p, (uint32_t)n, ctx->d_table);
+    launch_affine96_to_table(st.s, d_in.p, (uint32_t)n, ctx->table.p);
     return finish_srs_from_level0(ctx, st.s, n);
 }
 
@@ -966,15 +983,14 @@ int kzg_srs_load_compressed(kzg_ctx* ctx, const uint8_t* compressed, size_t n, s
     HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     HIP_TRY(ctx, hipMemcpyAsync(d_in.p, compressed, n * 48, hipMemcpyHostToDevice, st.s));
     HIP_TRY(ctx, hipMemsetAsync(d_status.p, 0xff, 4, st.s));
-    launch_uncompress(st.s, d_in.p, (uint32_t)n, ctx->d_table, (uint32_t*)d_status.p);
+    launch_uncompress(st.s, d_in.p, (uint32_t)n, ctx->table.p, (uint32_t*)d_status.p);
     uint32_t status = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&status, d_status.p, 4, hipMemcpyDeviceToHost, st.s));
     HIP_TRY(ctx, hipStreamSynchronize(st.s));
     if (status != 0xffffffffu) {  // a malformed point (not compressed form, x >= p, not on the curve): as blst_p1_uncompress
         if (bad_index) *bad_index = status - 1;
         ctx->last_error = "compressed point " + std::to_string(status - 1) + " is malformed";
-        hipFree(ctx->d_table);
-        ctx->d_table = nullptr;
+        ctx->table.reset();
         return KZG_ERR_INVALID_ARG;
     }
     return finish_srs_from_level0(ctx, st.s, n);
@@ -1117,7 +1133,7 @@ int kzg_srs_read_g1(kzg_ctx* ctx, size_t index, size_t count, uint64_t* out_p1) 
     DevBuf d_p1;
     HIP_TRY(ctx, hipMalloc(&d_p1.p, count * 144));
     hipStream_t st = ctx->slots[0].stream;
-    launch_affine_to_p1(st, (const char*)ctx->d_table + index * kAffineBytes, (uint32_t)count, d_p1.p);
+    launch_affine_to_p1(st, (const char*)ctx->table.p + index * kAffineBytes, (uint32_t)count, d_p1.p);
     HIP_TRY(ctx, hipMemcpyAsync(out_p1, d_p1.p, count * 144, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return KZG_OK;
@@ -1140,13 +1156,13 @@ static int submit_commit_locked(kzg_ctx* ctx, int slot, const uint32_t* d_scalar
     s.tail_checked = tail_already_checked;
     std::memset(&s.times, 0, sizeof s.times);
     size_t n_msm = n < ctx->n ? n : ctx->n;
-    std::memset(s.h_small, 0, 64 * 4);  // (the slot is idle: nothing in flight writes them)
+    std::memset(s.small.host(), 0, 64 * 4);  // (the slot is idle: nothing in flight writes them)
     if (n > ctx->n && !tail_already_checked) {
         // reference: the Polynomial was truncated at construction (src/polynomial.rs:55-75), so only a
         // non-zero coefficient beyond the SRS makes the degree too high (src/polynomial.rs:201-205)
         uint64_t cnt = n - ctx->n;
         hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, d_scalars,
-                           (uint64_t)ctx->n, (uint64_t)n, s.d_small + 24);
+                           (uint64_t)ctx->n, (uint64_t)n, s.small.dev() + 24);
     }
     if (n_msm == 0) {
         s.kind = SLOT_TRIVIAL;
@@ -1184,7 +1200,7 @@ static int submit_open_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, 
     std::memcpy(s.open_y, y, 32);
     std::memset(&s.times, 0, sizeof s.times);
     if (n == 0) {
-        std::memset(s.h_small, 0, 64 * 4);
+        std::memset(s.small.host(), 0, 64 * 4);
         s.kind = SLOT_TRIVIAL;
         return KZG_OK;
     }
@@ -1192,10 +1208,10 @@ static int submit_open_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, 
     std::memcpy(zw, z, 32);
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
     // small polynomials: one launch for the scan, the flag words and c0; otherwise memset + two launches (c0 written by the first)
-    if (!launch_quotient_single(s.stream, d_coeffs, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, s.d_small)) {
-        std::memset(s.h_small, 0, 64 * 4);
-        PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
-        launch_quotient(s.stream, d_coeffs, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, sc);
+    if (!launch_quotient_single(s.stream, d_coeffs, (uint32_t)n, zw, n > 1 ? s.q.dev() : nullptr, s.small.dev())) {
+        std::memset(s.small.host(), 0, 64 * 4);
+        PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
+        launch_quotient(s.stream, d_coeffs, (uint32_t)n, zw, n > 1 ? s.q.dev() : nullptr, sc);
     }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
     size_t nq = n - 1;
@@ -1203,11 +1219,11 @@ static int submit_open_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, 
         // quotient longer than the SRS: too high iff some coefficient with index > srs_len is non-zero
         uint64_t from = ctx->n + 1, cnt = n - from;
         hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, d_coeffs, from,
-                           (uint64_t)n, s.d_small + 24);
+                           (uint64_t)n, s.small.dev() + 24);
         nq = ctx->n;
     }
     if (nq > 0) {
-        rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+        rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
@@ -1254,11 +1270,11 @@ static int submit_points_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs
     if (nq > ctx->n) {
         const uint64_t from = ctx->n + k, cnt = n - from;
         hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, d_coeffs, from,
-                           (uint64_t)n, s.d_small + 24);
+                           (uint64_t)n, s.small.dev() + 24);
         nq = ctx->n;
     }
     if (nq > 0) {
-        rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+        rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0);
         if (rc) return rc;
     }
     s.pts_nq = nq;
@@ -1311,7 +1327,7 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
             hipEventElapsedTime(&ms, s.ev[0], s.ev[5]); s.times.total_ms = ms;
         }
     }
-    const uint32_t* hs = s.h_small;
+    const uint32_t* hs = s.small.host();
     hf::P1 inf = hf::p1_inf();
     if (kind == SLOT_OPEN_POINTS) {  // every claim first, then the degree (kzg_open's order), then the MSM
         const size_t k = s.pts_ys.size() / 8;
@@ -1395,7 +1411,7 @@ static int commit_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coef
     s.job_batch = (uint32_t)batch;
     s.tail_checked = true;
     std::memset(&s.times, 0, sizeof s.times);
-    std::memset(s.h_small, 0, 64 * 4);
+    std::memset(s.small.host(), 0, 64 * 4);
     int rc = enqueue_msm(ctx, s, (const uint32_t*)d_coeffs, 1, n, 0, (uint32_t)batch, stride_coeffs);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
@@ -1465,15 +1481,8 @@ static int open_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coeffs
     // (an owned slot's coefficients sit in its own staging buffer, which ensure_poly must not reallocate now: the
     // owner sized it before the upload)
     int rc = owned ? KZG_OK : ensure_poly(ctx, s, n * batch);
+    if (rc == KZG_OK) rc = s.bsmall.reserve(ctx, batch * 32 * 4, s.stream);
     if (rc) return rc;
-    if (s.bsmall_cap < batch) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        if (s.h_bsmall) hipHostFree(s.h_bsmall);
-        s.h_bsmall = nullptr;
-        HIP_TRY(ctx, hipHostMalloc(&s.h_bsmall, batch * 32 * 4, hipHostMallocMapped));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_bsmall, s.h_bsmall, 0));
-        s.bsmall_cap = batch;
-    }
     s.timing = ctx->timing;
     s.job_n = n;
     s.job_batch = (uint32_t)batch;
@@ -1481,20 +1490,20 @@ static int open_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coeffs
     s.tail_checked = true;
     s.open_ys.assign((const uint32_t*)ys, (const uint32_t*)ys + 8 * batch);
     std::memset(&s.times, 0, sizeof s.times);
-    std::memset(s.h_small, 0, 64 * 4);
-    std::memset(s.h_bsmall, 0, batch * 32 * 4);
+    std::memset(s.small.host(), 0, 64 * 4);
+    std::memset(s.bsmall.host(), 0, batch * 32 * 4);
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
     const size_t nq = n - 1;
     for (size_t p = 0; p < batch; p++) {
         const uint32_t* cp = (const uint32_t*)d_coeffs + p * stride_coeffs * 8;
         uint32_t zw[8];
         std::memcpy(zw, zs + 4 * p, 32);
-        uint32_t* sm = s.d_bsmall + p * 32;
-        PolyScratch sc{s.d_chunk, s.d_block, sm, sm + 8};  // scratch re-used in stream order
-        launch_quotient(s.stream, cp, (uint32_t)n, zw, s.d_q + p * nq * 8, sc);
+        uint32_t* sm = s.bsmall.dev() + p * 32;
+        PolyScratch sc{s.chunk.dev(), s.block.dev(), sm, sm + 8};  // scratch re-used in stream order
+        launch_quotient(s.stream, cp, (uint32_t)n, zw, s.q.dev() + p * nq * 8, sc);
     }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
-    rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0, (uint32_t)batch, nq);
+    rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0, (uint32_t)batch, nq);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
     s.kind = SLOT_OPEN_BATCH;
@@ -1530,7 +1539,7 @@ static int wait_open_batch_locked(kzg_ctx* ctx, int slot, uint64_t* out_p1s, int
     const uint32_t B = s.job_batch;
     const hf::P1 inf = hf::p1_inf();
     for (uint32_t p = 0; p < B; p++) {
-        const uint32_t* hs = s.h_bsmall + p * 32;
+        const uint32_t* hs = s.bsmall.host() + p * 32;
         const uint32_t* y = s.open_ys.data() + 8 * p;
         uint64_t* out = out_p1s + out_stride * (size_t)p;
         int& status = statuses[status_stride * (size_t)p];
@@ -1567,18 +1576,6 @@ int kzg_wait(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
 // upload or the wait: the reference's callers are threads of `cargo test` (src/lib.rs:53, 66, 91), and N of them now
 // occupy N slots whose jobs pipeline exactly like explicit kzg_*_submit calls.
 
-// pageable host memory -> the slot's staging buffer, on the slot's stream, without the mutex
-static int upload_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, size_t dst_coeff, const void* src, size_t coeffs) {
-    if (!coeffs) return KZG_OK;
-    lk.unlock();
-    const hipError_t e = hipMemcpyAsync(s.d_stage + dst_coeff * 8, src, coeffs * 32, hipMemcpyHostToDevice, s.stream);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMemcpyAsync (coefficients): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
 // waits for the slot's job outside the mutex (kinds that recorded `done`), then collects it
 static void await_unlocked(std::unique_lock<std::mutex>& lk, Slot& s) {
     if (s.kind == SLOT_TRIVIAL || s.kind == SLOT_RESERVED || s.kind == SLOT_IDLE) return;
@@ -1614,9 +1611,9 @@ static int commit_host(kzg_ctx* ctx, const void* scalars, int is_mont, size_t n,
     const size_t n_dev = n < ctx->n ? n : ctx->n;
     int rc = ensure_poly(ctx, s, n_dev);
     tr.mark(0);
-    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, 0, scalars, n_dev);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), scalars, n_dev * 32, hipMemcpyHostToDevice, kCopyCoeffs);
     tr.mark(1);
-    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.d_stage, is_mont, n_dev, true, true);
+    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), is_mont, n_dev, true, true);
     tr.mark(2);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
@@ -1648,8 +1645,8 @@ int kzg_open(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t z[4]
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, n);
-    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, 0, coeffs, n);
-    if (rc == KZG_OK) rc = submit_open_locked(ctx, slot, s.d_stage, n, z, y, true);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = submit_open_locked(ctx, slot, s.stage.dev(), n, z, y, true);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
         rc = wait_locked(ctx, slot, out_p1);
@@ -1670,8 +1667,8 @@ int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, n);
-    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, 0, coeffs, n);
-    if (rc == KZG_OK) rc = submit_points_locked(ctx, slot, s.d_stage, n, zs, ys, k, true);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = submit_points_locked(ctx, slot, s.stage.dev(), n, zs, ys, k, true);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
         rc = wait_locked(ctx, slot, out_p1);
@@ -1682,34 +1679,17 @@ int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64
 
 // ---- combined openings: t polynomials, one point, one proof ---------------------------------
 namespace {
-// the slot's buffers for passes of at most t_pass polynomials of n coefficients; stage_coeffs: room in d_cin (host-pointer
+// the slot's buffers for passes of at most t_pass polynomials of n coefficients; stage_coeffs: room in cin (host-pointer
 // passes), 0 when the polynomials are resident (slot basics already there)
 int ensure_combined(kzg_ctx* ctx, Slot& s, size_t n, size_t t_pass, size_t stage_coeffs) {
-    if (!s.h_ctab) {
-        HIP_TRY(ctx, hipHostMalloc(&s.h_ctab, kCombineTabLen * sizeof(Fr30), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc(&s.d_ctab, kCombineTabLen * sizeof(Fr30)));
-        HIP_TRY(ctx, hipHostMalloc(&s.h_cvals, kCombineMax * 32, hipHostMallocMapped));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_cvals, s.h_cvals, 0));
-        for (auto& e : s.cmb_ev) HIP_TRY(ctx, hipEventCreate(&e));
-    }
-    const size_t words = t_pass * combine_tiles((uint32_t)(n ? n : 1)) * kCombinePartialWords;
-    if (words > s.cpart_words) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        hipFree(s.d_cpart);
-        s.d_cpart = nullptr;
-        s.cpart_words = 0;
-        HIP_TRY(ctx, hipMalloc(&s.d_cpart, words * 4));
-        s.cpart_words = words;
-    }
-    if (stage_coeffs > s.cin_coeffs) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        hipFree(s.d_cin);
-        s.d_cin = nullptr;
-        s.cin_coeffs = 0;
-        HIP_TRY(ctx, hipMalloc(&s.d_cin, stage_coeffs * 32));
-        s.cin_coeffs = stage_coeffs;
-    }
-    return KZG_OK;
+    int rc = s.ctab.reserve(ctx, kCombineTabLen * sizeof(Fr30));
+    if (rc == KZG_OK) rc = s.cvals.reserve(ctx, kCombineMax * 32);
+    if (rc) return rc;
+    for (auto& e : s.cmb_ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    rc = s.cpart.reserve(ctx, t_pass * combine_tiles((uint32_t)(n ? n : 1)) * kCombinePartialWords * 4, s.stream);
+    if (rc == KZG_OK) rc = s.cin.reserve(ctx, stage_coeffs * 32, s.stream);
+    return rc;
 }
 // every multiplier of one call: the 16 + 16 tables and the stride of z (a lane's power inside a tile) and of W = z^2048
 // (a tile's power inside the polynomial), then gamma^i -- 66 + t host products -- copied to the slot's table on its stream
@@ -1730,22 +1710,22 @@ void combine_fill_powers(Fr30* tab, const hf::Fr& z) {  // entries [0, kCombineT
     fill(hf::fr_pow(z256, kCombineTile / 256), kCombineTabWa, kCombineTabWb, kCombineTabW256);
 }
 int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& gamma, size_t t) {
-    Fr30* tab = (Fr30*)s.h_ctab;
+    Fr30* tab = (Fr30*)s.ctab.h;
     combine_fill_powers(tab, z);
     hf::Fr g = hf::kFrOne;
     for (size_t i = 0; i < t; i++) {
         tab[kCombineTabGamma + i] = fr30_arg_from_mont256(g);
         g = hf::fr_mul(g, gamma);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_ctab, s.h_ctab, (kCombineTabGamma + t) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.ctab.d, s.ctab.h, (kCombineTabGamma + t) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
     return KZG_OK;
 }
-// one pass on the slot's stream: polynomials first .. first + cnt (device memory) into F (s.d_stage, carried from the earlier
+// one pass on the slot's stream: polynomials first .. first + cnt (device memory) into F (s.stage, carried from the earlier
 // passes when first > 0) and their values into the slot's value words
 int combined_pass(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, size_t cnt, size_t stride, size_t first) {
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
-    launch_combine_eval(s.stream, d_coeffs, (uint32_t)n, (uint32_t)cnt, stride, (const Fr30*)s.d_ctab, (uint32_t)first, first > 0,
-                        s.d_stage, s.d_cpart, s.d_cvals + 8 * first);
+    launch_combine_eval(s.stream, d_coeffs, (uint32_t)n, (uint32_t)cnt, stride, (const Fr30*)s.ctab.d, (uint32_t)first, first > 0,
+                        s.stage.dev(), s.cpart.dev(), s.cvals.dev() + 8 * first);
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
@@ -1774,20 +1754,13 @@ int combined_check(kzg_ctx* ctx, const char* what, const void* coeffs, size_t n,
 // host polynomials [first, first + cnt) -> the slot's pass buffer, n coefficients each, back to back; without the mutex
 int combined_stage_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint64_t* coeffs, size_t n, size_t stride,
                             size_t first, size_t cnt) {
-    lk.unlock();
-    hipError_t e = hipSuccess;
-    if (stride == n || cnt == 1) {
-        e = hipMemcpyAsync(s.d_cin, coeffs + 4 * first * stride, cnt * n * 32, hipMemcpyHostToDevice, s.stream);
-    } else {
-        for (size_t i = 0; i < cnt && e == hipSuccess; i++)
-            e = hipMemcpyAsync(s.d_cin + 8 * i * n, coeffs + 4 * (first + i) * stride, n * 32, hipMemcpyHostToDevice, s.stream);
-    }
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMemcpyAsync (coefficients): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
+    if (stride == n || cnt == 1)
+        return copy_unlocked(ctx, lk, s.stream, s.cin.dev(), coeffs + 4 * first * stride, cnt * n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    int rc = KZG_OK;
+    for (size_t i = 0; i < cnt && rc == KZG_OK; i++)
+        rc = copy_unlocked(ctx, lk, s.stream, s.cin.dev() + 8 * i * n, coeffs + 4 * (first + i) * stride, n * 32, hipMemcpyHostToDevice,
+                           kCopyCoeffs);
+    return rc;
 }
 // all passes of a host-pointer call: at most max_batch polynomials per launch
 int combined_host_passes(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint64_t* coeffs, size_t n, size_t t,
@@ -1799,11 +1772,11 @@ int combined_host_passes(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s
     for (size_t first = 0; first < t && rc == KZG_OK; first += group) {
         const size_t cnt = std::min(group, t - first);
         rc = combined_stage_unlocked(ctx, lk, s, coeffs, n, stride, first, cnt);
-        if (rc == KZG_OK) rc = combined_pass(ctx, s, s.d_cin, n, cnt, n, first);
+        if (rc == KZG_OK) rc = combined_pass(ctx, s, s.cin.dev(), n, cnt, n, first);
     }
     return rc;
 }
-// the opening of F (n coefficients in s.d_stage) at z behind the passes, as submit_open_locked runs it on a caller's buffer;
+// the opening of F (n coefficients in s.stage) at z behind the passes, as submit_open_locked runs it on a caller's buffer;
 // the prover has no claim, so F(z) is only computed, not compared
 int combined_enqueue_open(kzg_ctx* ctx, Slot& s, size_t n, size_t t, const uint64_t z[4]) {
     s.job_n = n;
@@ -1812,25 +1785,25 @@ int combined_enqueue_open(kzg_ctx* ctx, Slot& s, size_t n, size_t t, const uint6
     s.tail_checked = false;
     s.cmb_t = t;
     s.pts_nq = 0;
-    std::memset(s.h_small, 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
+    std::memset(s.small.host(), 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
     if (n > 0) {
         uint32_t zw[8];
         std::memcpy(zw, z, 32);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
-        if (!launch_quotient_single(s.stream, s.d_stage, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, s.d_small)) {
-            PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
-            launch_quotient(s.stream, s.d_stage, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, sc);
+        if (!launch_quotient_single(s.stream, s.stage.dev(), (uint32_t)n, zw, n > 1 ? s.q.dev() : nullptr, s.small.dev())) {
+            PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
+            launch_quotient(s.stream, s.stage.dev(), (uint32_t)n, zw, n > 1 ? s.q.dev() : nullptr, sc);
         }
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
         size_t nq = n - 1;
         if (nq > ctx->n) {  // too high iff some coefficient of F with index > srs_len is non-zero
             const uint64_t from = ctx->n + 1, cnt = n - from;
-            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.d_stage, from,
-                               (uint64_t)n, s.d_small + 24);
+            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.stage.dev(), from,
+                               (uint64_t)n, s.small.dev() + 24);
             nq = ctx->n;
         }
         if (nq > 0) {
-            int rc = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+            int rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0);
             if (rc) return rc;
         }
         s.pts_nq = nq;
@@ -1845,7 +1818,7 @@ int combined_job_start(kzg_ctx* ctx, Slot& s, size_t t) {
     s.combine_ms = 0;
     std::memset(&s.times, 0, sizeof s.times);
     int rc = ensure_combined(ctx, s, 0, 0, 0);
-    if (rc == KZG_OK) std::memset(s.h_cvals, 0, 32 * t);  // (the slot holds no job in flight)
+    if (rc == KZG_OK) std::memset(s.cvals.host(), 0, 32 * t);  // (the slot holds no job in flight)
     return rc;
 }
 
@@ -1874,8 +1847,8 @@ int wait_combined_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_
             hipEventElapsedTime(&ms, s.ev[6], s.ev[5]); s.times.total_ms = ms;
         }
     }
-    std::memcpy(out_ys, s.h_cvals, 32 * s.cmb_t);
-    const uint32_t* hs = s.h_small;
+    std::memcpy(out_ys, s.cvals.host(), 32 * s.cmb_t);
+    const uint32_t* hs = s.small.host();
     // F after the reference's truncation: no non-zero coefficient above the constant one -> infinity, like kzg_open_points
     if (s.job_n == 0 || !(hs[0] & 1u)) {
         write_p1(out_p1, hf::p1_inf());
@@ -1905,8 +1878,8 @@ int combined_hook(kzg_ctx* ctx, const char* what, const uint64_t* coeffs, size_t
     if (rc == KZG_OK) rc = combined_host_passes(ctx, lk, s, coeffs, n, t, stride, zf, gf);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    if (out_ys) std::memcpy(out_ys, s.h_cvals, 32 * t);
-    if (out_f) HIP_TRY(ctx, hipMemcpy(out_f, s.d_stage, n * 32, hipMemcpyDeviceToHost));
+    if (out_ys) std::memcpy(out_ys, s.cvals.host(), 32 * t);
+    if (out_f) HIP_TRY(ctx, hipMemcpy(out_f, s.stage.dev(), n * 32, hipMemcpyDeviceToHost));
     return KZG_OK;
 }
 }  // namespace
@@ -2107,23 +2080,11 @@ int sets_check(kzg_ctx* ctx, const char* what, const void* coeffs, size_t n, siz
 
 // the slot's buffers for |T| = npts points over n coefficients (slot basics already there)
 int ensure_sets(kzg_ctx* ctx, Slot& s, size_t n, size_t npts) {
-    if (!s.h_stab) HIP_TRY(ctx, hipHostMalloc(&s.h_stab, kSetsTabLen * sizeof(Fr30), hipHostMallocDefault));
-    if (!s.d_stab) HIP_TRY(ctx, hipMalloc(&s.d_stab, kSetsTabLen * sizeof(Fr30)));
-    if (!s.h_ssel) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_ssel, kSetsMaxValues * 4, hipHostMallocDefault));
-    if (!s.d_ssel) HIP_TRY(ctx, hipMalloc((void**)&s.d_ssel, kSetsMaxValues * 4));
-    if (!s.h_svals) {
-        HIP_TRY(ctx, hipHostMalloc((void**)&s.h_svals, kSetsMaxValues * 32, hipHostMallocMapped));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&s.d_svals, s.h_svals, 0));
-    }
-    if (npts * n > s.sg_coeffs) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        hipFree(s.d_sg);
-        s.d_sg = nullptr;
-        s.sg_coeffs = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&s.d_sg, npts * n * 32));
-        s.sg_coeffs = npts * n;
-    }
-    return KZG_OK;
+    int rc = s.stab.reserve(ctx, kSetsTabLen * sizeof(Fr30));
+    if (rc == KZG_OK) rc = s.ssel.reserve(ctx, kSetsMaxValues * 4);
+    if (rc == KZG_OK) rc = s.svals.reserve(ctx, kSetsMaxValues * 32);
+    if (rc == KZG_OK) rc = s.sg.reserve(ctx, npts * n * 32, s.stream);
+    return rc;
 }
 int sets_job_start(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2132,7 +2093,7 @@ int sets_job_start(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
     std::memset(&s.times, 0, sizeof s.times);
     int rc = ensure_combined(ctx, s, 0, 0, 0);
     if (rc == KZG_OK) rc = ensure_sets(ctx, s, 0, 0);
-    if (rc == KZG_OK) std::memset(s.h_svals, 0, 32 * plan.nvals);  // (the slot holds no job in flight)
+    if (rc == KZG_OK) std::memset(s.svals.host(), 0, 32 * plan.nvals);  // (the slot holds no job in flight)
     return rc;
 }
 // every buffer of a job whose passes take at most t_pass polynomials; stage_coeffs as in ensure_combined
@@ -2146,14 +2107,14 @@ int sets_ensure_all(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n, size_
 // the multipliers of one call -- 66 host products per distinct point, the multipliers and the lists as planned -- copied to
 // the slot's tables on its stream
 int sets_upload_tables(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
-    Fr30* tab = (Fr30*)s.h_stab;
+    Fr30* tab = (Fr30*)s.stab.h;
     for (size_t r = 0; r < plan.npts; r++) combine_fill_powers(tab + r * kCombineTabGamma, plan.pts[r]);
     for (size_t e = 0; e < plan.sel.size(); e++) {
         tab[kSetsMultBase + e] = fr30_arg_from_mont256(plan.mult[e]);
-        s.h_ssel[e] = plan.sel[e];
+        s.ssel.host()[e] = plan.sel[e];
     }
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_stab, s.h_stab, (kSetsMultBase + plan.sel.size()) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_ssel, s.h_ssel, plan.sel.size() * 4, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.stab.d, s.stab.h, (kSetsMultBase + plan.sel.size()) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.ssel.dev(), s.ssel.host(), plan.sel.size() * 4, hipMemcpyHostToDevice, s.stream));
     return KZG_OK;
 }
 // The passes over polynomials first .. first + cnt (device memory, polynomial `first` at d_coeffs): one per distinct point
@@ -2167,9 +2128,9 @@ int sets_passes(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const uint32_t* d_c
         const size_t j0 = std::lower_bound(lo, hi, (uint32_t)first) - plan.sel.begin();
         const size_t j1 = std::lower_bound(lo, hi, (uint32_t)(first + cnt)) - plan.sel.begin();
         if (j0 == j1) continue;
-        launch_sets_combine(s.stream, d_coeffs, (uint32_t)n, (uint32_t)(j1 - j0), stride, (const Fr30*)s.d_stab + r * kCombineTabGamma,
-                            (const Fr30*)s.d_stab + kSetsMultBase + j0, s.d_ssel + j0, (uint32_t)first, written[r],
-                            s.d_sg + 8 * r * n, s.d_cpart, s.d_svals + 8 * j0);
+        launch_sets_combine(s.stream, d_coeffs, (uint32_t)n, (uint32_t)(j1 - j0), stride, (const Fr30*)s.stab.d + r * kCombineTabGamma,
+                            (const Fr30*)s.stab.d + kSetsMultBase + j0, s.ssel.dev() + j0, (uint32_t)first, written[r],
+                            s.sg.dev() + 8 * r * n, s.cpart.dev(), s.svals.dev() + 8 * j0);
         written[r] = true;
     }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
@@ -2186,19 +2147,19 @@ int sets_host_passes(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, co
     for (size_t first = 0; first < t && rc == KZG_OK; first += group) {
         const size_t cnt = std::min(group, t - first);
         rc = combined_stage_unlocked(ctx, lk, s, coeffs, n, stride, first, cnt);
-        if (rc == KZG_OK) rc = sets_passes(ctx, s, plan, s.d_cin, n, n, first, cnt, written);
+        if (rc == KZG_OK) rc = sets_passes(ctx, s, plan, s.cin.dev(), n, n, first, cnt, written);
     }
     return rc;
 }
-// h = sum_r Q(G_r, z_r) into s.d_q[0 .. n - 1) behind the passes (nothing for n < 2)
+// h = sum_r Q(G_r, z_r) into s.q[0 .. n - 1) behind the passes (nothing for n < 2)
 int sets_enqueue_scans(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
     if (n < 2) return KZG_OK;
     uint64_t ws[4 * KZG_MAX_SET_POINTS];  // (the weights are inside the G_r)
     for (size_t r = 0; r < plan.npts; r++) std::memcpy(ws + 4 * r, hf::kFrOne.l, 32);
-    points_fill_roots(s.h_roots, plan.pts[0].l, ws, (uint32_t)plan.npts, (uint32_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_roots, s.h_roots, plan.npts * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
+    points_fill_roots(s.roots.h, plan.pts[0].l, ws, (uint32_t)plan.npts, (uint32_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(s.roots.d, s.roots.h, plan.npts * points_root_bytes(), hipMemcpyHostToDevice, s.stream));
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
-    launch_quotient_sets(s.stream, s.d_sg, (uint32_t)n, s.d_roots, (uint32_t)plan.npts, s.d_q, s.d_pblock, s.d_pvals);
+    launch_quotient_sets(s.stream, s.sg.dev(), (uint32_t)n, s.roots.d, (uint32_t)plan.npts, s.q.dev(), s.pblock.dev(), s.pvals.dev());
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
@@ -2212,20 +2173,20 @@ int sets_enqueue_open(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
     s.tail_checked = false;
     s.pts_nq = 0;
     s.sets_vmap = plan.vmap;
-    std::memset(s.h_small, 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
+    std::memset(s.small.host(), 0, 64 * 4);  // (nothing in flight writes them: the passes do not touch the flag words)
     if (n >= 2) {
         int rc = sets_enqueue_scans(ctx, s, plan, n);
         if (rc) return rc;
         size_t nq = n - 1;
         if (nq > ctx->n) {
             const uint64_t cnt = nq - ctx->n;
-            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.d_q, (uint64_t)ctx->n,
-                               (uint64_t)nq, s.d_small + 24);
+            hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s.stream, s.q.dev(), (uint64_t)ctx->n,
+                               (uint64_t)nq, s.small.dev() + 24);
             nq = ctx->n;
         }
-        hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s.stream, s.d_q, (uint64_t)0,
-                           (uint64_t)nq, s.d_small);
-        int rc2 = enqueue_msm(ctx, s, s.d_q, 1, nq, 0);
+        hipLaunchKernelGGL(k_tail_nonzero, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s.stream, s.q.dev(), (uint64_t)0,
+                           (uint64_t)nq, s.small.dev());
+        int rc2 = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0);
         if (rc2) return rc2;
         s.pts_nq = nq;
     }
@@ -2234,7 +2195,7 @@ int sets_enqueue_open(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
     return KZG_OK;
 }
 void sets_copy_values(const Slot& s, uint64_t* out_ys) {
-    for (size_t e = 0; e < s.sets_vmap.size(); e++) std::memcpy(out_ys + 4 * e, s.h_svals + 8 * (size_t)s.sets_vmap[e], 32);
+    for (size_t e = 0; e < s.sets_vmap.size(); e++) std::memcpy(out_ys + 4 * e, s.svals.host() + 8 * (size_t)s.sets_vmap[e], 32);
 }
 
 int wait_sets_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[18]) {
@@ -2263,7 +2224,7 @@ int wait_sets_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[1
         }
     }
     sets_copy_values(s, out_ys);
-    const uint32_t* hs = s.h_small;
+    const uint32_t* hs = s.small.host();
     if (hs[24]) return KZG_ERR_DEGREE_TOO_HIGH;
     write_p1(out_p1, ran_msm && (hs[0] & 1u) ? finish_msm(ctx, s) : hf::p1_inf());  // h = 0 (also by cancellation): infinity
     return KZG_OK;
@@ -2367,7 +2328,7 @@ int kzg_quotient_sets(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t t, 
     s.sets_vmap = plan.vmap;
     sets_copy_values(s, out_ys);
     if (n > 1) {
-        HIP_TRY(ctx, hipMemcpy(out_h, s.d_q, (n - 1) * 32, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_h, s.q.dev(), (n - 1) * 32, hipMemcpyDeviceToHost));
         size_t hn = n - 1;
         while (hn > 0 && !(out_h[4 * hn - 4] | out_h[4 * hn - 3] | out_h[4 * hn - 2] | out_h[4 * hn - 1])) hn--;
         *out_hn = hn;
@@ -2400,7 +2361,7 @@ namespace kzg {
 
 int ctx_drop_srs(kzg_ctx* ctx) {
     std::unique_lock<std::mutex> lk(ctx->mu);
-    if (!ctx->n && !ctx->d_table) return KZG_OK;
+    if (!ctx->n && !ctx->table.p) return KZG_OK;
     quiesce(ctx, lk);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return srs_release(ctx);
@@ -2450,7 +2411,7 @@ static int batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t str
         Slot& s = ctx->slots[slot];
         rc = ensure_poly(ctx, s, n * polys);
         for (size_t q = 0; q < polys && rc == KZG_OK; q++)
-            rc = upload_unlocked(ctx, lk, s, q * n, coeffs + (first + (at + q) * step) * stride * 4, n);
+            rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev() + (q * n) * 8, coeffs + (first + (at + q) * step) * stride * 4, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
         if (rc == KZG_OK) {
             if (opening) {
                 zc.resize(4 * polys);
@@ -2459,9 +2420,9 @@ static int batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t str
                     std::memcpy(&zc[4 * q], zs + 4 * (first + (at + q) * step), 32);
                     std::memcpy(&yc[4 * q], ys + 4 * (first + (at + q) * step), 32);
                 }
-                rc = open_batch_submit_locked(ctx, slot, s.d_stage, n, polys, n, zc.data(), yc.data(), true);
+                rc = open_batch_submit_locked(ctx, slot, s.stage.dev(), n, polys, n, zc.data(), yc.data(), true);
             } else {
-                rc = commit_batch_submit_locked(ctx, slot, s.d_stage, n, polys, n, true);
+                rc = commit_batch_submit_locked(ctx, slot, s.stage.dev(), n, polys, n, true);
             }
         }
         if (rc != KZG_OK) {
@@ -2495,15 +2456,15 @@ int ctx_open_slice_begin(kzg_ctx* ctx, const uint64_t* slice, size_t len, const 
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, len + 1);
-    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, 0, slice, len);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), slice, len * 32, hipMemcpyHostToDevice, kCopyCoeffs);
     if (rc == KZG_OK) {
         lk.unlock();
         uint32_t zw[8];
         std::memcpy(zw, z, 32);
-        std::memset(s.h_small, 0, 64 * 4);
+        std::memset(s.small.host(), 0, 64 * 4);
         hipError_t e = hipSuccess;
-        PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
-        launch_quotient(s.stream, s.d_stage, (uint32_t)len, zw, nullptr, sc);
+        PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
+        launch_quotient(s.stream, s.stage.dev(), (uint32_t)len, zw, nullptr, sc);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
         lk.lock();
@@ -2516,7 +2477,7 @@ int ctx_open_slice_begin(kzg_ctx* ctx, const uint64_t* slice, size_t len, const 
         release_owned(ctx, slot);
         return rc;
     }
-    std::memcpy(out_h, s.h_small + 8, 32);
+    std::memcpy(out_h, s.small.host() + 8, 32);
     *slot_out = slot;
     return KZG_OK;
 }
@@ -2527,8 +2488,8 @@ int ctx_open_slice_finish(kzg_ctx* ctx, int slot, size_t len, const uint64_t car
     Slot& s = ctx->slots[slot];
     int rc = KZG_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) rc = KZG_ERR_HIP;
-    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, len, carry, 1);  // the carry as one more top coefficient
-    if (rc == KZG_OK) rc = submit_open_locked(ctx, slot, s.d_stage, len + 1, z, start, true);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev() + len * 8, carry, 1 * 32, hipMemcpyHostToDevice, kCopyCoeffs);  // the carry as one more top coefficient
+    if (rc == KZG_OK) rc = submit_open_locked(ctx, slot, s.stage.dev(), len + 1, z, start, true);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
         rc = wait_locked(ctx, slot, out_p1);
@@ -2586,23 +2547,23 @@ int kzg_quotient(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t 
     if (n == 0) return y_zero ? KZG_OK : KZG_ERR_CONSTANT_POLY;
     int rc = ensure_poly(ctx, s, n);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
-    std::memset(s.h_small, 0, 64 * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
+    std::memset(s.small.host(), 0, 64 * 4);
     uint32_t zw[8];
     std::memcpy(zw, z, 32);
-    PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
-    launch_quotient(s.stream, s.d_stage, (uint32_t)n, zw, n > 1 ? s.d_q : nullptr, sc);
+    PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
+    launch_quotient(s.stream, s.stage.dev(), (uint32_t)n, zw, n > 1 ? s.q.dev() : nullptr, sc);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    bool higher_nonzero = s.h_small[0] & 1u;
+    bool higher_nonzero = s.small.host()[0] & 1u;
     if (!higher_nonzero) return std::memcmp(coeffs, y, 32) == 0 ? KZG_OK : KZG_ERR_CONSTANT_POLY;
-    if (std::memcmp(s.h_small + 8, y, 32) != 0) return KZG_ERR_REMAINDER;
+    if (std::memcmp(s.small.host() + 8, y, 32) != 0) return KZG_ERR_REMAINDER;
     // quotient of the truncated polynomial: its length is (index of the last non-zero coefficient)
     size_t n_eff = n;
     while (n_eff > 1 && !(coeffs[4 * (n_eff - 1)] | coeffs[4 * (n_eff - 1) + 1] | coeffs[4 * (n_eff - 1) + 2] |
                           coeffs[4 * (n_eff - 1) + 3]))
         n_eff--;
-    HIP_TRY(ctx, hipMemcpy(out_q, s.d_q, (n_eff - 1) * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_q, s.q.dev(), (n_eff - 1) * 32, hipMemcpyDeviceToHost));
     *out_qn = n_eff - 1;
     return KZG_OK;
 }
@@ -2623,15 +2584,15 @@ int kzg_evaluate(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t 
     if (rcb) return rcb;
     int rc = ensure_poly(ctx, s, n);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
-    std::memset(s.h_small, 0, 64 * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
+    std::memset(s.small.host(), 0, 64 * 4);
     uint32_t zw[8];
     std::memcpy(zw, z, 32);
-    PolyScratch sc{s.d_chunk, s.d_block, s.d_small, s.d_small + 8};
-    launch_quotient(s.stream, s.d_stage, (uint32_t)n, zw, nullptr, sc);
+    PolyScratch sc{s.chunk.dev(), s.block.dev(), s.small.dev(), s.small.dev() + 8};
+    launch_quotient(s.stream, s.stage.dev(), (uint32_t)n, zw, nullptr, sc);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    std::memcpy(out_y, s.h_small + 8, 32);
+    std::memcpy(out_y, s.small.host() + 8, 32);
     return KZG_OK;
 }
 
@@ -2646,8 +2607,8 @@ static int points_scan_host(kzg_ctx* ctx, Slot& s, const uint64_t* coeffs, size_
     if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
     if (rc == KZG_OK) rc = ensure_points(ctx, s, n, k);
     if (rc) return rc;
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
-    rc = enqueue_points_scan(ctx, s, s.d_stage, n, zs, ws, k, n > k ? n - k : 0, want_q && n > k);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, s.stream));
+    rc = enqueue_points_scan(ctx, s, s.stage.dev(), n, zs, ws, k, n > k ? n - k : 0, want_q && n > k);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     return KZG_OK;
@@ -2674,7 +2635,7 @@ int kzg_quotient_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const ui
                           coeffs[4 * (n_eff - 1) + 3]))
         n_eff--;
     if (n_eff <= k) return KZG_OK;
-    HIP_TRY(ctx, hipMemcpy(out_q, s.d_q, (n_eff - k) * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_q, s.q.dev(), (n_eff - k) * 32, hipMemcpyDeviceToHost));
     *out_qn = n_eff - k;
     return KZG_OK;
 }
@@ -2706,7 +2667,7 @@ static bool ntt_log(size_t n, uint32_t* lg) {
 // the context's twiddle tables (ctx->mu held): one set for every size, w = w_(2^22) and its inverse, 4 x 2048 Fr30
 // (the caller has made ctx->device current, as for everything that allocates or launches below)
 static int ensure_ntt(kzg_ctx* ctx) {
-    if (ctx->d_ntt_tw) return KZG_OK;
+    if (ctx->ntt_tw.p) return KZG_OK;
     if (!ntt_prepare_device()) {
         (void)hipGetLastError();
         ctx->last_error = "ntt: the pass kernel's LDS limit could not be raised";
@@ -2725,15 +2686,11 @@ static int ensure_ntt(kzg_ctx* ctx) {
             hi = hf::fr_mul(hi, step_hi);
         }
     }
-    void* d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, h.size() * sizeof(Fr30)));
-    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d);
-        ctx->last_error = std::string("hipMemcpy (ntt twiddles): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    ctx->d_ntt_tw = d;
+    DevBuf d;
+    HIP_TRY(ctx, hipMalloc(&d.p, h.size() * sizeof(Fr30)));
+    if (hipError_t e = hipMemcpy(d.p, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice))
+        return hip_fail(ctx, "hipMemcpy (ntt twiddles)", e);
+    std::swap(ctx->ntt_tw.p, d.p);
     return KZG_OK;
 }
 // enqueues the transform of 2^lg values on stream st: d_in -> d_out through the scratch buffers a, b (launch_ntt)
@@ -2746,17 +2703,17 @@ static int enqueue_ntt(kzg_ctx* ctx, hipStream_t st, const uint32_t* d_in, uint3
         c = hf::fr_inv(n);
     }
     const Fr30 last_c = fr30_arg_from_mont256(c);
-    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw + (inverse ? 2 * kNttTableLen : 0);
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p + (inverse ? 2 * kNttTableLen : 0);
     launch_ntt(st, d_in, d_out, lg, tw, last_c, d_a, d_b);
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
 // Transforms that end in a slot's staging buffer use the slot's two polynomial buffers as the pass chain: with three
 // passes the chain is q -> stage -> q -> stage, otherwise stage (-> q) -> stage.  Host data goes in at ntt_slot_input.
-static uint32_t* ntt_slot_input(Slot& s, uint32_t lg) { return ntt_plan(lg).passes == 3 ? s.d_q : s.d_stage; }
+static uint32_t* ntt_slot_input(Slot& s, uint32_t lg) { return ntt_plan(lg).passes == 3 ? s.q.dev() : s.stage.dev(); }
 static int ntt_into_stage(kzg_ctx* ctx, Slot& s, const uint32_t* d_in, uint32_t lg, bool inverse) {
     const bool three = ntt_plan(lg).passes == 3;
-    return enqueue_ntt(ctx, s.stream, d_in, s.d_stage, lg, inverse, three ? s.d_stage : s.d_q, s.d_q);
+    return enqueue_ntt(ctx, s.stream, d_in, s.stage.dev(), lg, inverse, three ? s.stage.dev() : s.q.dev(), s.q.dev());
 }
 // a slot reserved by the caller, ready for a transform of n values (ctx->mu held, twiddles built)
 static int ntt_slot_ready(kzg_ctx* ctx, Slot& s, size_t n) {
@@ -2789,7 +2746,7 @@ int kzg_ntt(kzg_ctx* ctx, const uint64_t* in, size_t n, int inverse, uint64_t* o
     HIP_TRY(ctx, hipMemcpyAsync(ntt_slot_input(s, lg), in, n * 32, hipMemcpyHostToDevice, s.stream));
     rc = ntt_into_stage(ctx, s, ntt_slot_input(s, lg), lg, inverse != 0);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out, s.d_stage, n * 32, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, s.stage.dev(), n * 32, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     return KZG_OK;
 }
@@ -2809,7 +2766,7 @@ int kzg_ntt_device(kzg_ctx* ctx, const void* d_in, void* d_out, size_t n, int in
     rc = ntt_slot_ready(ctx, s, n);
     if (rc) return rc;
     // the caller's buffers are neither of the slot's: d_in -> stage (-> q) -> d_out
-    rc = enqueue_ntt(ctx, s.stream, (const uint32_t*)d_in, (uint32_t*)d_out, lg, inverse != 0, s.d_stage, s.d_q);
+    rc = enqueue_ntt(ctx, s.stream, (const uint32_t*)d_in, (uint32_t*)d_out, lg, inverse != 0, s.stage.dev(), s.q.dev());
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     return KZG_OK;
@@ -2830,7 +2787,7 @@ int kzg_commit_evaluations_submit(kzg_ctx* ctx, int slot, const void* d_evals, s
     if (rc == KZG_OK) rc = ntt_into_stage(ctx, s, (const uint32_t*)d_evals, lg, true);
     if (rc) return rc;
     // n above the SRS: the coefficients beyond it are checked on the device, as for kzg_commit_submit
-    return submit_commit_locked(ctx, slot, s.d_stage, 1, n, false);
+    return submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, false);
 }
 
 // the synchronous host-pointer forms: upload -> inverse NTT -> kzg_commit's / kzg_open's submit, on a reserved slot
@@ -2848,17 +2805,12 @@ static int evaluations_host(kzg_ctx* ctx, const uint64_t* evals, size_t n, uint3
     rc = ntt_slot_ready(ctx, s, n);
     if (rc) return rc;
     uint32_t* dst = ntt_slot_input(s, lg);
-    lk.unlock();
-    const hipError_t e = hipMemcpyAsync(dst, evals, n * 32, hipMemcpyHostToDevice, s.stream);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMemcpyAsync (evaluations): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
+    rc = copy_unlocked(ctx, lk, s.stream, dst, evals, n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (evaluations)");
+    if (rc) return rc;
     rc = ntt_into_stage(ctx, s, dst, lg, true);
     if (rc) return rc;
-    rc = z ? submit_open_locked(ctx, slot, s.d_stage, n, z, y, true)
-           : submit_commit_locked(ctx, slot, s.d_stage, 1, n, false, true);
+    rc = z ? submit_open_locked(ctx, slot, s.stage.dev(), n, z, y, true)
+           : submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, false, true);
     if (rc) return rc;
     await_unlocked(lk, s);
     return wait_locked(ctx, slot, out_p1);
@@ -2901,7 +2853,7 @@ int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, const ui
 
 // ---- every cell of a domain and its multiproof (cell_kernels.hip) ---------------------------------
 // Cell j of the domain of N = 2^log_n points is {w_N^(j + (N/l) i) : i < l}, l = 2^log_l; its proof is the commitment to
-// q_j = (P - I_j) / (X^l - w_N^(j l)).  The call holds one slot for its whole length: P sits in that slot's d_cpoly, the cells
+// q_j = (P - I_j) / (X^l - w_N^(j l)).  The call holds one slot for its whole length: P sits in that slot's cpoly, the cells
 // come from its stream, and the N/l quotients flow through it and any other free slot in sub-batches of at most
 // ctx->max_batch cells (one batched MSM each), the kernels of one sub-batch overlapping the MSMs of the others.
 namespace {
@@ -2928,65 +2880,35 @@ size_t cells_trim(const uint64_t* c, size_t n) {
 // the slot's buffer for P (cap coefficients) and its hand-off event (ctx->mu held, slot owned by the caller)
 static int ensure_cells_poly(kzg_ctx* ctx, Slot& s, size_t cap) {
     if (!s.cells_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&s.cells_ev, hipEventDisableTiming));
-    if (cap <= s.cpoly_cap && s.d_cpoly) return KZG_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    hipFree(s.d_cpoly);
-    s.d_cpoly = nullptr;
-    s.cpoly_cap = 0;
-    if (cap < 1024) cap = 1024;
-    HIP_TRY(ctx, hipMalloc(&s.d_cpoly, cap * 32));
-    s.cpoly_cap = cap;
-    return KZG_OK;
+    return s.cpoly.reserve(ctx, (cap < 1024 ? 1024 : cap) * 32, s.stream);
 }
-static int ensure_cells_agg(kzg_ctx* ctx, Slot& s, uint64_t words) {
-    if (words <= s.cagg_words && s.d_cagg) return KZG_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    hipFree(s.d_cagg);
-    s.d_cagg = nullptr;
-    s.cagg_words = 0;
-    HIP_TRY(ctx, hipMalloc(&s.d_cagg, words * 4));
-    s.cagg_words = words;
-    return KZG_OK;
-}
-// a host -> device copy on the slot's stream without the mutex
-static int copy_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, void* dst, const void* src, size_t bytes) {
-    if (!bytes) return KZG_OK;
-    lk.unlock();
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s.stream);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMemcpyAsync (cells): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
-// the quotients of cells [first, first + polys) on slot `slot` (owned), then their batched MSM; P in s0.d_cpoly
+// the quotients of cells [first, first + polys) on slot `slot` (owned), then their batched MSM; P in s0.cpoly
 static int cells_submit(kzg_ctx* ctx, int slot, Slot& s0, const CellsShape& sh, size_t nq, size_t first, size_t polys) {
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, polys * nq);
-    if (rc == KZG_OK) rc = ensure_cells_agg(ctx, s, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)polys));
+    if (rc == KZG_OK) rc = s.cagg.reserve(ctx, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)polys) * 4, s.stream);
     if (rc) return rc;
     if (&s != &s0) HIP_TRY(ctx, hipStreamWaitEvent(s.stream, s0.cells_ev, 0));
-    launch_cell_quotients(s.stream, s0.d_cpoly, (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first, (uint32_t)polys,
-                          ctx->d_ntt_tw, s.d_cagg, s.d_q, nq);
+    launch_cell_quotients(s.stream, s0.cpoly.dev(), (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first, (uint32_t)polys,
+                          ctx->ntt_tw.p, s.cagg.dev(), s.q.dev(), nq);
     HIP_TRY(ctx, hipGetLastError());
-    return commit_batch_submit_locked(ctx, slot, s.d_q, nq, polys, nq, true);
+    return commit_batch_submit_locked(ctx, slot, s.q.dev(), nq, polys, nq, true);
 }
-// P sits in s0.d_cpoly: n_eff coefficients, zero up to N when the cells are wanted.  Cells first, then the proofs.
+// P sits in s0.cpoly: n_eff coefficients, zero up to N when the cells are wanted.  Cells first, then the proofs.
 static int cells_run(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot0, const CellsShape& sh, size_t n_eff,
                      uint64_t* out_cells, uint64_t* out_proofs) {
     Slot& s0 = ctx->slots[slot0];
     HIP_TRY(ctx, hipEventRecord(s0.cells_ev, s0.stream));
     int rc = KZG_OK;
     if (out_cells) {
-        // forward NTT of P padded to N (d_cpoly -> stage, through q), gathered into cell-major order in q
+        // forward NTT of P padded to N (cpoly -> stage, through q), gathered into cell-major order in q
         rc = ensure_poly(ctx, s0, sh.N);
-        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.d_cpoly, sh.log_n, false);
+        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.cpoly.dev(), sh.log_n, false);
         if (rc) return rc;
-        launch_cells_gather(s0.stream, s0.d_stage, s0.d_q, sh.log_n, sh.log_l);
+        launch_cells_gather(s0.stream, s0.stage.dev(), s0.q.dev(), sh.log_n, sh.log_l);
         HIP_TRY(ctx, hipGetLastError());
         lk.unlock();
-        hipError_t e = hipMemcpyAsync(out_cells, s0.d_q, sh.N * 32, hipMemcpyDeviceToHost, s0.stream);
+        hipError_t e = hipMemcpyAsync(out_cells, s0.q.dev(), sh.N * 32, hipMemcpyDeviceToHost, s0.stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s0.stream);
         lk.lock();
         if (e != hipSuccess) {
@@ -3056,17 +2978,17 @@ static int cells_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n_eff, const 
     rc = ensure_cells_poly(ctx, s0, sh.N);
     if (rc) return rc;
     if (evals) {
-        // values -> d_cpoly -> inverse NTT into stage -> back to d_cpoly; the coefficients also go to the host once, for n'
+        // values -> cpoly -> inverse NTT into stage -> back to cpoly; the coefficients also go to the host once, for n'
         uint32_t lg = 0;
         (void)ntt_log(n, &lg);
         rc = ntt_slot_ready(ctx, s0, n);
-        if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s0, s0.d_cpoly, evals, n * 32);
-        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.d_cpoly, lg, true);
+        if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s0.stream, s0.cpoly.dev(), evals, n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
+        if (rc == KZG_OK) rc = ntt_into_stage(ctx, s0, s0.cpoly.dev(), lg, true);
         if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(s0.d_cpoly, s0.d_stage, n * 32, hipMemcpyDeviceToDevice, s0.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s0.cpoly.dev(), s0.stage.dev(), n * 32, hipMemcpyDeviceToDevice, s0.stream));
         std::vector<uint64_t> c(4 * n);
         lk.unlock();
-        hipError_t e = hipMemcpyAsync(c.data(), s0.d_stage, n * 32, hipMemcpyDeviceToHost, s0.stream);
+        hipError_t e = hipMemcpyAsync(c.data(), s0.stage.dev(), n * 32, hipMemcpyDeviceToHost, s0.stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s0.stream);
         lk.lock();
         if (e != hipSuccess) {
@@ -3076,11 +2998,11 @@ static int cells_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n_eff, const 
         n_eff = cells_trim(c.data(), n);
         if (n_eff > sh.l && n_eff - sh.l > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
     } else {
-        rc = copy_unlocked(ctx, lk, s0, s0.d_cpoly, coeffs, n_eff * 32);
+        rc = copy_unlocked(ctx, lk, s0.stream, s0.cpoly.dev(), coeffs, n_eff * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
         if (rc) return rc;
     }
     if (out_cells && n_eff < sh.N)
-        HIP_TRY(ctx, hipMemsetAsync(s0.d_cpoly + 8 * n_eff, 0, (sh.N - n_eff) * 32, s0.stream));
+        HIP_TRY(ctx, hipMemsetAsync(s0.cpoly.dev() + 8 * n_eff, 0, (sh.N - n_eff) * 32, s0.stream));
     return cells_run(ctx, lk, slot0, sh, n_eff, out_cells, out_proofs);
 }
 // a multi-device context: a replicated SRS forwards to one device; a range-split one holds no device with the whole SRS
@@ -3143,13 +3065,13 @@ int kzg_quotient_cells(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, unsigned 
     rc = ensure_slot_basics(ctx, s);  // needs no SRS
     if (rc == KZG_OK) rc = ensure_cells_poly(ctx, s, n_eff);
     if (rc == KZG_OK) rc = ensure_poly(ctx, s, count * nq);
-    if (rc == KZG_OK) rc = ensure_cells_agg(ctx, s, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)count));
+    if (rc == KZG_OK) rc = s.cagg.reserve(ctx, cells_agg_words((uint32_t)nq, sh.log_l, (uint32_t)count) * 4, s.stream);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_cpoly, coeffs, n_eff * 32, hipMemcpyHostToDevice, s.stream));
-    launch_cell_quotients(s.stream, s.d_cpoly, (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first_cell, (uint32_t)count,
-                          ctx->d_ntt_tw, s.d_cagg, s.d_q, nq);
+    HIP_TRY(ctx, hipMemcpyAsync(s.cpoly.dev(), coeffs, n_eff * 32, hipMemcpyHostToDevice, s.stream));
+    launch_cell_quotients(s.stream, s.cpoly.dev(), (uint32_t)nq, sh.log_n, sh.log_l, (uint32_t)first_cell, (uint32_t)count,
+                          ctx->ntt_tw.p, s.cagg.dev(), s.q.dev(), nq);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpy2DAsync(out_q, (n - sh.l) * 32, s.d_q, nq * 32, nq * 32, count, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(out_q, (n - sh.l) * 32, s.q.dev(), nq * 32, nq * 32, count, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     *out_qn = nq;
     return KZG_OK;
@@ -3207,33 +3129,10 @@ size_t fk20_table_budget() {
 }
 }  // namespace
 
-static int fk20_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
-    if (bytes > ctx->fk20_ws_bytes[i] || !ctx->fk20_ws[i]) {
-        hipFree(ctx->fk20_ws[i]);
-        ctx->fk20_ws[i] = nullptr;
-        ctx->fk20_ws_bytes[i] = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->fk20_ws[i], bytes ? bytes : 256));
-        ctx->fk20_ws_bytes[i] = bytes;
-    }
-    *out = ctx->fk20_ws[i];
-    return KZG_OK;
-}
-// waits for the stream without ctx->mu, so that the context's other calls go on meanwhile (the caller's slot keeps an
-// SRS replacement out, fk20_mu the other FK20 calls)
-static int fk20_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
-    lk.unlock();
-    const hipError_t e = hipStreamSynchronize(st);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("fk20: ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
 // the split twiddles w_(2^lg)^e, e < 2^lg, for every transform of at most 2^lg points (device current)
 static int ensure_glv(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, uint32_t lg, hipStream_t st) {
     if (lg < 1) lg = 1;
-    if (ctx->d_glv && ctx->glv_log >= lg) return KZG_OK;
+    if (ctx->glv.p && ctx->glv_log >= lg) return KZG_OK;
     const size_t len = (size_t)1 << lg;
     std::vector<Glv> h(len);
     const hf::Fr w = hf::fr_domain_root(lg);
@@ -3242,60 +3141,58 @@ static int ensure_glv(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, uint32_t l
         h[e] = glv_split(v);
         v = hf::fr_mul(v, w);
     }
-    int rc = fk20_sync(ctx, lk, st);  // nothing in flight reads the old table
+    int rc = sync_unlocked(ctx, lk, st, "fk20");  // nothing in flight reads the old table
     if (rc) return rc;
-    hipFree(ctx->d_glv);
-    ctx->d_glv = nullptr;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_glv, len * sizeof(Glv)));
+    ctx->glv.reset();
+    rc = ctx->glv.reserve(ctx, len * sizeof(Glv));
+    if (rc) return rc;
     ctx->glv_log = lg;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_glv, h.data(), len * sizeof(Glv), hipMemcpyHostToDevice, st));
-    return fk20_sync(ctx, lk, st);  // h goes out of scope
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->glv.p, h.data(), len * sizeof(Glv), hipMemcpyHostToDevice, st));
+    return sync_unlocked(ctx, lk, st, "fk20");  // h goes out of scope
 }
 // comb tables of bases [first, first + count) ((i, r) order) into dst, through tmp / prefix (kFk20CombChunk bases each)
 static void enqueue_comb(kzg_ctx* ctx, hipStream_t st, uint32_t log_L, uint32_t log_l, uint64_t first, uint64_t count,
                          void* dst, void* tmp, void* prefix) {
     for (uint64_t f = 0; f < count; f += kFk20CombChunk) {
         const uint32_t c = (uint32_t)(count - f < kFk20CombChunk ? count - f : kFk20CombChunk);
-        launch_fk20_comb(st, ctx->d_fk20_B, log_L, log_l, first + f, c, tmp);
+        launch_fk20_comb(st, ctx->fk20_B.p, log_L, log_l, first + f, c, tmp);
         launch_xyzz_to_affine(st, tmp, c * kFk20CombEntries, (char*)dst + f * kFk20CombEntries * kAffineBytes, prefix);
     }
 }
 // the SRS side of (L, l): B_r = DFT_L(S_r), r < l, and their comb tables when they fit fk20_table_budget()
 static int ensure_fk20_table(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, uint32_t log_L, uint32_t log_l) {
-    if (ctx->d_fk20_B && ctx->fk20_log_L == log_L && ctx->fk20_log_l == log_l) return KZG_OK;
-    int rc = fk20_sync(ctx, lk, st);
+    if (ctx->fk20_B.p && ctx->fk20_log_L == log_L && ctx->fk20_log_l == log_l) return KZG_OK;
+    int rc = sync_unlocked(ctx, lk, st, "fk20");
     if (rc) return rc;
-    hipFree(ctx->d_fk20_B);
-    hipFree(ctx->d_fk20_tab);
-    ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
+    ctx->fk20_B.reset();
+    ctx->fk20_tab.reset();
     const size_t bases = (size_t)1 << (log_L + log_l);
     const size_t tab_bytes = bases * kFk20CombEntries * kAffineBytes;
     DevBuf S, B1, B2;
     HIP_TRY(ctx, hipMalloc(&S.p, bases * kXyzzBytes));
     HIP_TRY(ctx, hipMalloc(&B1.p, bases * kXyzzBytes));
     HIP_TRY(ctx, hipMalloc(&B2.p, bases * kXyzzBytes));
-    launch_fk20_srs_gather(st, ctx->d_table, ctx->n, log_L, log_l, S.p);
-    const void* B = launch_g1_dft(st, S.p, B1.p, B2.p, log_L, (uint64_t)1 << log_l, (const Glv*)ctx->d_glv, ctx->glv_log, false);
-    ctx->d_fk20_B = (B == B1.p) ? B1.p : B2.p;
-    (B == B1.p ? B1.p : B2.p) = nullptr;  // kept
+    launch_fk20_srs_gather(st, ctx->table.p, ctx->n, log_L, log_l, S.p);
+    const void* B = launch_g1_dft(st, S.p, B1.p, B2.p, log_L, (uint64_t)1 << log_l, (const Glv*)ctx->glv.p, ctx->glv_log, false);
+    std::swap(ctx->fk20_B.p, B == B1.p ? B1.p : B2.p);  // kept
     ctx->fk20_log_L = log_L;
     ctx->fk20_log_l = log_l;
     if (tab_bytes <= fk20_table_budget()) {
-        void* tab = nullptr;
-        if (hipMalloc(&tab, tab_bytes) == hipSuccess) {
+        DevBuf tab;
+        if (hipMalloc(&tab.p, tab_bytes) == hipSuccess) {
             DevBuf tmp, prefix;
             const size_t chunk = bases < kFk20CombChunk ? bases : kFk20CombChunk;
             HIP_TRY(ctx, hipMalloc(&tmp.p, chunk * kFk20CombEntries * kXyzzBytes));
             HIP_TRY(ctx, hipMalloc(&prefix.p, chunk * kFk20CombEntries * 64));
-            ctx->d_fk20_tab = tab;
-            enqueue_comb(ctx, st, log_L, log_l, 0, bases, tab, tmp.p, prefix.p);
+            std::swap(ctx->fk20_tab.p, tab.p);
+            enqueue_comb(ctx, st, log_L, log_l, 0, bases, ctx->fk20_tab.p, tmp.p, prefix.p);
             HIP_TRY(ctx, hipGetLastError());
-            return fk20_sync(ctx, lk, st);  // before the temporaries go
+            return sync_unlocked(ctx, lk, st, "fk20");  // before the temporaries go
         }
         (void)hipGetLastError();  // no room after all: the tables are streamed per call
     }
     HIP_TRY(ctx, hipGetLastError());
-    return fk20_sync(ctx, lk, st);
+    return sync_unlocked(ctx, lk, st, "fk20");
 }
 // shape of the Toeplitz step for polynomials of at most n' coefficients (n' > l): m = ceil(n' / l), L = 2^log_L >= 2m
 static bool fk20_shape(kzg_ctx* ctx, size_t n_max, uint32_t log_l, uint32_t* m, uint32_t* log_L) {
@@ -3307,7 +3204,7 @@ static bool fk20_shape(kzg_ctx* ctx, size_t n_max, uint32_t log_l, uint32_t* m, 
         return false;
     }
     // any L >= 2m works: a cached transform of the same l up to twice as long serves instead of being rebuilt
-    if (ctx->d_fk20_B && ctx->fk20_log_l == log_l && ctx->fk20_log_L >= *log_L && ctx->fk20_log_L <= *log_L + 1)
+    if (ctx->fk20_B.p && ctx->fk20_log_l == log_l && ctx->fk20_log_L >= *log_L && ctx->fk20_log_L <= *log_L + 1)
         *log_L = ctx->fk20_log_L;
     return true;
 }
@@ -3326,34 +3223,34 @@ static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream
                        bool keep_affine = false) {
     const size_t L = (size_t)1 << log_L, l = (size_t)1 << log_l, M = (size_t)1 << log_M;
     const size_t X = L > M ? L : M;
-    const bool kept = ctx->d_fk20_tab != nullptr;
+    const bool kept = ctx->fk20_tab.p != nullptr;
     const uint32_t ci = kept ? (uint32_t)L : fk20_stream_positions(log_L, log_l);
     void *coef, *sa, *sb, *part, *x1, *x2, *x3, *aff, *prefix, *p1;
-    int rc = fk20_ws(ctx, kWsCoef, batch * n_max * 32, &coef);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsScalA, batch * l * L * 32, &sa);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsScalB, batch * l * L * 32, &sb);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPart, l > 1 ? batch * l * ci * kXyzzBytes : 0, &part);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX1, batch * X * kXyzzBytes, &x1);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX2, batch * X * kXyzzBytes, &x2);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX3, batch * X * kXyzzBytes, &x3);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsAff, batch * M * kAffineBytes, &aff);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPrefix, batch * M * 64, &prefix);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsP1, batch * M * 144, &p1);
+    int rc = ctx->fk20_ws.get(ctx, kWsCoef, batch * n_max * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsScalA, batch * l * L * 32, &sa);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsScalB, batch * l * L * 32, &sb);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsPart, l > 1 ? batch * l * ci * kXyzzBytes : 0, &part);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX1, batch * X * kXyzzBytes, &x1);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX2, batch * X * kXyzzBytes, &x2);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX3, batch * X * kXyzzBytes, &x3);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsAff, batch * M * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsPrefix, batch * M * 64, &prefix);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsP1, batch * M * 144, &p1);
     if (rc) return rc;
     if (d_src) HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, d_src, stride * 32, n_max * 32, batch, hipMemcpyDeviceToDevice, st));
     else HIP_TRY(ctx, hipMemcpy2DAsync(coef, n_max * 32, coeffs, stride * 32, n_max * 32, batch, hipMemcpyHostToDevice, st));
     const Fr30 inv_L = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(log_L)));
-    const uint32_t* scal = launch_fk20_fr_side(st, (const uint32_t*)coef, (uint32_t)n_max, m, log_L, log_l, batch, ctx->d_ntt_tw,
+    const uint32_t* scal = launch_fk20_fr_side(st, (const uint32_t*)coef, (uint32_t)n_max, m, log_L, log_l, batch, ctx->ntt_tw.p,
                                                inv_L, (uint32_t*)sa, (uint32_t*)sb);
     if (kept) {
-        launch_fk20_pointwise(st, scal, ctx->d_fk20_tab, log_L, log_l, 0, (uint32_t)L, batch, part, x1);
+        launch_fk20_pointwise(st, scal, ctx->fk20_tab.p, log_L, log_l, 0, (uint32_t)L, batch, part, x1);
     } else {  // the comb tables of one chunk of positions at a time
         for (uint32_t i0 = 0; i0 < L; i0 += ci) {
             enqueue_comb(ctx, st, log_L, log_l, (uint64_t)i0 << log_l, (uint64_t)ci << log_l, stream_tab, stream_tmp, stream_prefix);
             launch_fk20_pointwise(st, scal, stream_tab, log_L, log_l, i0, ci, batch, part, x1);
         }
     }
-    const Glv* tw = (const Glv*)ctx->d_glv;
+    const Glv* tw = (const Glv*)ctx->glv.p;
     const void* conv = launch_g1_dft(st, x1, x2, x3, log_L, batch, tw, ctx->glv_log, true);  // 1/L went into the scalars
     // log_L >= 2: conv is x2 or x3; the second DFT ping-pongs through x1 and conv, free once the selection has read it
     void* h = conv == x2 ? x3 : x2;
@@ -3366,10 +3263,10 @@ static int fk20_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream
     }
     launch_affine_to_p1(st, aff, (uint32_t)(batch * M), p1);
     HIP_TRY(ctx, hipGetLastError());
-    rc = fk20_sync(ctx, lk, st);
+    rc = sync_unlocked(ctx, lk, st, "fk20");
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_proofs, p1, batch * M * 144, hipMemcpyDeviceToHost, st));
-    return fk20_sync(ctx, lk, st);
+    return sync_unlocked(ctx, lk, st, "fk20");
 }
 
 static int fk20_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batch, size_t stride, const CellsShape& sh,
@@ -3402,16 +3299,16 @@ static int fk20_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batc
         if (rc == KZG_OK) rc = ensure_poly(ctx, s0, sh.N);
         if (rc) return rc;
         for (size_t b = 0; b < batch; b++) {
-            if (neff[b]) HIP_TRY(ctx, hipMemcpyAsync(s0.d_cpoly, coeffs + 4 * b * stride, neff[b] * 32, hipMemcpyHostToDevice, s0.stream));
-            if (neff[b] < sh.N) HIP_TRY(ctx, hipMemsetAsync(s0.d_cpoly + 8 * neff[b], 0, (sh.N - neff[b]) * 32, s0.stream));
-            rc = ntt_into_stage(ctx, s0, s0.d_cpoly, sh.log_n, false);
+            if (neff[b]) HIP_TRY(ctx, hipMemcpyAsync(s0.cpoly.dev(), coeffs + 4 * b * stride, neff[b] * 32, hipMemcpyHostToDevice, s0.stream));
+            if (neff[b] < sh.N) HIP_TRY(ctx, hipMemsetAsync(s0.cpoly.dev() + 8 * neff[b], 0, (sh.N - neff[b]) * 32, s0.stream));
+            rc = ntt_into_stage(ctx, s0, s0.cpoly.dev(), sh.log_n, false);
             if (rc) return rc;
-            launch_cells_gather(s0.stream, s0.d_stage, s0.d_q, sh.log_n, sh.log_l);
+            launch_cells_gather(s0.stream, s0.stage.dev(), s0.q.dev(), sh.log_n, sh.log_l);
             HIP_TRY(ctx, hipGetLastError());
-            rc = fk20_sync(ctx, lk, s0.stream);
+            rc = sync_unlocked(ctx, lk, s0.stream, "fk20");
             if (rc) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * sh.N * b, s0.d_q, sh.N * 32, hipMemcpyDeviceToHost, s0.stream));
-            rc = fk20_sync(ctx, lk, s0.stream);
+            HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * sh.N * b, s0.q.dev(), sh.N * 32, hipMemcpyDeviceToHost, s0.stream));
+            rc = sync_unlocked(ctx, lk, s0.stream, "fk20");
             if (rc) return rc;
         }
     }
@@ -3426,7 +3323,7 @@ static int fk20_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batc
     if (rc) return rc;
     // polynomials per pass: at most kFk20MaxBatch, fewer when their workspaces would pass kFk20WsBudget
     const size_t L = (size_t)1 << log_L, M = (size_t)1 << log_M, X = L > M ? L : M;
-    const bool kept = ctx->d_fk20_tab != nullptr;
+    const bool kept = ctx->fk20_tab.p != nullptr;
     const size_t ci = kept ? L : fk20_stream_positions(log_L, sh.log_l);
     const size_t per_poly = n_max * 32 + sh.l * L * 64 + (sh.l > 1 ? sh.l * ci * kXyzzBytes : 0) + 3 * X * kXyzzBytes + M * 336;
     size_t chunk = kFk20WsBudget / per_poly;
@@ -3444,7 +3341,7 @@ static int fk20_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t batc
                          out_proofs + 18 * sh.cells * b0, stab.p, stmp.p, spre.p);
     }
     if (!kept) {  // the DevBufs free when the call returns; nothing in flight may still read them
-        const int r2 = fk20_sync(ctx, lk, s0.stream);
+        const int r2 = sync_unlocked(ctx, lk, s0.stream, "fk20");
         if (rc == KZG_OK) rc = r2;
     }
     return rc;
@@ -3505,25 +3402,25 @@ int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint6
     int rc = ensure_slot_basics(ctx, s);  // needs no SRS
     if (rc == KZG_OK) rc = ensure_glv(ctx, lk, lg, s.stream);
     void *jac, *aff, *prefix, *x1, *x2, *x3;
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsP1, m * 144, &jac);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsAff, m * kAffineBytes, &aff);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsPrefix, m * 64, &prefix);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX1, m * kXyzzBytes, &x1);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX2, m * kXyzzBytes, &x2);
-    if (rc == KZG_OK) rc = fk20_ws(ctx, kWsX3, m * kXyzzBytes, &x3);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsP1, m * 144, &jac);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsAff, m * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsPrefix, m * 64, &prefix);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX1, m * kXyzzBytes, &x1);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX2, m * kXyzzBytes, &x2);
+    if (rc == KZG_OK) rc = ctx->fk20_ws.get(ctx, kWsX3, m * kXyzzBytes, &x3);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(jac, in_p1, m * 144, hipMemcpyHostToDevice, s.stream));
     launch_jacobian_to_affine(s.stream, jac, (uint32_t)m, aff, prefix);
     launch_affine_to_xyzz(s.stream, aff, m, x1);
-    void* res = (void*)launch_g1_dft(s.stream, x1, x2, x3, lg, 1, (const Glv*)ctx->d_glv, ctx->glv_log, inverse != 0);
+    void* res = (void*)launch_g1_dft(s.stream, x1, x2, x3, lg, 1, (const Glv*)ctx->glv.p, ctx->glv_log, inverse != 0);
     if (inverse) launch_g1_scale(s.stream, res, m, glv_split(hf::fr_inv(fr_pow2(lg))));
     launch_xyzz_to_affine(s.stream, res, (uint32_t)m, aff, prefix);
     launch_affine_to_p1(s.stream, aff, (uint32_t)m, jac);
     HIP_TRY(ctx, hipGetLastError());
-    rc = fk20_sync(ctx, lk, s.stream);
+    rc = sync_unlocked(ctx, lk, s.stream, "fk20");
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_p1, jac, m * 144, hipMemcpyDeviceToHost, s.stream));
-    return fk20_sync(ctx, lk, s.stream);
+    return sync_unlocked(ctx, lk, s.stream, "fk20");
 }
 
 // ---- recovery of every cell and proof from part of the cells (recover_kernels.hip) -----------------
@@ -3550,30 +3447,9 @@ hf::Fr fr_seven() {
 }
 }  // namespace
 
-static int rec_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
-    if (bytes > ctx->rec_ws_bytes[i] || !ctx->rec_ws[i]) {
-        hipFree(ctx->rec_ws[i]);
-        ctx->rec_ws[i] = nullptr;
-        ctx->rec_ws_bytes[i] = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->rec_ws[i], bytes ? bytes : 256));
-        ctx->rec_ws_bytes[i] = bytes;
-    }
-    *out = ctx->rec_ws[i];
-    return KZG_OK;
-}
-static int rec_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st) {
-    lk.unlock();
-    const hipError_t e = hipStreamSynchronize(st);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("recover: ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
 // g^i and g^-i tables (ctx->mu held, device current): forward lo, forward hi, inverse lo, inverse hi, as ensure_ntt's
 static int ensure_recover_g(kzg_ctx* ctx) {
-    if (ctx->d_rec_g) return KZG_OK;
+    if (ctx->rec_g.p) return KZG_OK;
     std::vector<Fr30> h(4 * kNttTableLen);
     const hf::Fr g = fr_seven();
     for (int dir = 0; dir < 2; dir++) {
@@ -3587,15 +3463,11 @@ static int ensure_recover_g(kzg_ctx* ctx) {
             hi = hf::fr_mul(hi, step_hi);
         }
     }
-    void* d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, h.size() * sizeof(Fr30)));
-    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d);
-        ctx->last_error = std::string("hipMemcpy (recovery tables): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    ctx->d_rec_g = d;
+    DevBuf d;
+    HIP_TRY(ctx, hipMalloc(&d.p, h.size() * sizeof(Fr30)));
+    if (hipError_t e = hipMemcpy(d.p, h.data(), h.size() * sizeof(Fr30), hipMemcpyHostToDevice))
+        return hip_fail(ctx, "hipMemcpy (recovery tables)", e);
+    std::swap(ctx->rec_g.p, d.p);
     return KZG_OK;
 }
 
@@ -3623,38 +3495,38 @@ static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int3
     if (chunk > batch) chunk = batch;
     const uint32_t parts = recover_vanish_parts((uint32_t)missing.size());
     void *in, *a, *b, *coef, *flags, *dpos, *dmiss, *part, *z;
-    rc = rec_ws(ctx, kRecIn, batch * k * l * 32, &in);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecA, chunk * N * 32, &a);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecB, chunk * N * 32, &b);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecCoef, chunk * n * 32, &coef);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecFlags, chunk * 4, &flags);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecPos, M * 4, &dpos);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecMissing, missing.size() * 4, &dmiss);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecPart, (size_t)parts * 2 * M * 32, &part);
-    if (rc == KZG_OK) rc = rec_ws(ctx, kRecZ, 2 * M * 32, &z);
+    rc = ctx->rec_ws.get(ctx, kRecIn, batch * k * l * 32, &in);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecA, chunk * N * 32, &a);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecB, chunk * N * 32, &b);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecCoef, chunk * n * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecFlags, chunk * 4, &flags);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecPos, M * 4, &dpos);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecMissing, missing.size() * 4, &dmiss);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecPart, (size_t)parts * 2 * M * 32, &part);
+    if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecZ, 2 * M * 32, &z);
     if (rc) return rc;
     uint32_t* derr = nullptr;
     const bool want_cells = wire ? wire->out_cells_be != nullptr : out_cells != nullptr;
     if (wire) {  // the bytes as received -> blst_fr images in `in`, the values of every cell put into this API's order
         void *dwire, *e;
-        rc = rec_ws(ctx, kRecWire, batch * k * l * 32, &dwire);
-        if (rc == KZG_OK) rc = rec_ws(ctx, kRecErr, 8, &e);
+        rc = ctx->rec_ws.get(ctx, kRecWire, batch * k * l * 32, &dwire);
+        if (rc == KZG_OK) rc = ctx->rec_ws.get(ctx, kRecErr, 8, &e);
         if (rc) return rc;
         derr = (uint32_t*)e;
         HIP_TRY(ctx, hipMemsetAsync(derr, 0xff, 8, s.stream));
-        rc = copy_unlocked(ctx, lk, s, dwire, wire->cells_be, batch * k * l * 32);
+        rc = copy_unlocked(ctx, lk, s.stream, dwire, wire->cells_be, batch * k * l * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
         if (rc) return rc;
         launch_wire_fr(s.stream, dwire, (uint32_t)(batch * k * l), sh.log_l, wire->bit_reversed, in, derr);
     } else {
-        rc = copy_unlocked(ctx, lk, s, in, cells, batch * k * l * 32);
+        rc = copy_unlocked(ctx, lk, s.stream, in, cells, batch * k * l * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
     }
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dpos, pos, M * 4);
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s, dmiss, missing.data(), missing.size() * 4);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, dpos, pos, M * 4, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, dmiss, missing.data(), missing.size() * 4, hipMemcpyHostToDevice, "hipMemcpyAsync (cells)");
     if (rc) return rc;
     const Fr30 gl = fr30_arg_from_mont256(hf::fr_pow(fr_seven(), l));
     const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.log_n)));
-    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
-    const Fr30* gt = (const Fr30*)ctx->d_rec_g;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
+    const Fr30* gt = (const Fr30*)ctx->rec_g.p;
     launch_recover_vanishing(s.stream, (const uint32_t*)dmiss, (uint32_t)missing.size(), tw, sh.log_n, sh.log_l, gl,
                              (uint32_t*)part, (uint32_t*)z);
     std::vector<uint32_t> hflags(chunk);
@@ -3684,7 +3556,7 @@ static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int3
             }
         }
         HIP_TRY(ctx, hipGetLastError());
-        rc = rec_sync(ctx, lk, s.stream);
+        rc = sync_unlocked(ctx, lk, s.stream, "recover");
         if (rc) return rc;
         uint32_t herr = 0xffffffffu;
         HIP_TRY(ctx, hipMemcpyAsync(hflags.data(), flags, bc * 4, hipMemcpyDeviceToHost, s.stream));
@@ -3695,7 +3567,7 @@ static int recover_host(kzg_ctx* ctx, const CellsShape& sh, size_t n, const int3
             if (out_coeffs) HIP_TRY(ctx, hipMemcpyAsync(out_coeffs + 4 * n * b0, coef, bc * n * 32, hipMemcpyDeviceToHost, s.stream));
             if (cells_dev) HIP_TRY(ctx, hipMemcpyAsync(out_cells + 4 * N * b0, cells_dev, bc * N * 32, hipMemcpyDeviceToHost, s.stream));
         }
-        rc = rec_sync(ctx, lk, s.stream);
+        rc = sync_unlocked(ctx, lk, s.stream, "recover");
         if (rc) return rc;
         if (herr != 0xffffffffu) {  // (the whole batch was decoded in front of the first chunk)
             const size_t b = herr / (k * l), t = herr / l % k;
@@ -3770,7 +3642,7 @@ int kzg_recover_cells_and_proofs(kzg_ctx* ctx, size_t n, unsigned log_domain, un
 
 // ---- batch verification of cell proofs (verify_kernels.hip) --------------------------------------
 // One random linear combination of all records: the device forms both G1 sides, the host pairs them once.  The call holds
-// fk20_mu (it reads the split twiddles d_glv), then the context's mutex and one slot for its stream, dropping the mutex
+// fk20_mu (it reads the split twiddles glv), then the context's mutex and one slot for its stream, dropping the mutex
 // while it waits for the device.
 namespace {
 enum : int {
@@ -3817,28 +3689,6 @@ bool vc_random(void* out, size_t bytes) {
 }
 const hf::Fr kFrR2 = {{0xc999e990f3f29c6dULL, 0x2b6cedcb87925c23ULL, 0x05d314967254398fULL, 0x0748d9d99f59ff11ULL}};  // 2^512 mod r
 }  // namespace
-
-static int vc_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
-    if (bytes > ctx->vc_ws_bytes[i] || !ctx->vc_ws[i]) {
-        hipFree(ctx->vc_ws[i]);
-        ctx->vc_ws[i] = nullptr;
-        ctx->vc_ws_bytes[i] = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->vc_ws[i], bytes ? bytes : 256));
-        ctx->vc_ws_bytes[i] = bytes;
-    }
-    *out = ctx->vc_ws[i];
-    return KZG_OK;
-}
-static int vc_sync(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const char* what = "verify cells") {
-    lk.unlock();
-    const hipError_t e = hipStreamSynchronize(st);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
 
 namespace {
 // the validated records of one call, sorted by cell id
@@ -3907,7 +3757,7 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     const uint32_t log_M = sh.log_n - sh.log_l;
     const bool pts = !vb.points.empty();
     const std::string what = vb.what;
-    // fk20_mu guards the workspaces (and d_glv).  kzg_verify_evaluations_batch takes it itself, before it puts the values into
+    // fk20_mu guards the workspaces (and glv).  kzg_verify_evaluations_batch takes it itself, before it puts the values into
     // the kVcCells workspace, and keeps it until this call returns: then vb.fk20_held is set and it is not taken again here.
     std::unique_lock<std::mutex> lkf(ctx->fk20_mu, std::defer_lock);
     if (!vb.fk20_held) lkf.lock();
@@ -3958,23 +3808,23 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     // values already on the device ARE the kVcCells workspace: asking for it again could free and reallocate it (vc_ws drops
     // the contents when it grows)
     if (vb.d_values) cells = (void*)vb.d_values;
-    else rc = vc_ws(ctx, kVcCells, K * l * 32, &cells);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrA, g0 * l * 32, &fa);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcFrB, g0 * l * 32, &fb);
-    if (rc == KZG_OK && vb.wire_values) rc = vc_ws(ctx, kVcWire, K * l * 32, &wire);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, l * 32 + kVcErrWords * 4, &coef);  // + the error words
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcOrder, K * 4, &order);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcRho, K * sizeof(Fr30), &rho);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcIds, D * 4, &ids);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcStarts, starts.size() * 4, &dstarts);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcP1, lanes * 144, &p1);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcAff, lanes * kAffineBytes, &aff);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcPrefix, lanes * 64, &prefix);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcSrc, lanes * 4, &dsrc);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlv, lanes * sizeof(Glv), &dglv);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcGlvSrs, (l + vb.points.size()) * sizeof(Glv), &dglvs);  // then the split points
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcG1, (K + 2 * D + B + l + 2) * kXyzzBytes, &g1);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
+    else rc = ctx->vc_ws.get(ctx, kVcCells, K * l * 32, &cells);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcFrA, g0 * l * 32, &fa);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcFrB, g0 * l * 32, &fb);
+    if (rc == KZG_OK && vb.wire_values) rc = ctx->vc_ws.get(ctx, kVcWire, K * l * 32, &wire);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCoefA, l * 32 + kVcErrWords * 4, &coef);  // + the error words
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcOrder, K * 4, &order);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcRho, K * sizeof(Fr30), &rho);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcIds, D * 4, &ids);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcStarts, starts.size() * 4, &dstarts);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcP1, lanes * 144, &p1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcAff, lanes * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcPrefix, lanes * 64, &prefix);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcSrc, lanes * 4, &dsrc);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcGlv, lanes * sizeof(Glv), &dglv);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcGlvSrs, (l + vb.points.size()) * sizeof(Glv), &dglvs);  // then the split points
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcG1, (K + 2 * D + B + l + 2) * kXyzzBytes, &g1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
     if (rc) return rc;
     const hipStream_t st = s.stream;
     uint32_t* err = (uint32_t*)((char*)coef + l * 32);
@@ -4010,7 +3860,7 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
                          (uint32_t)(plan_t[lv].size() - 1), sh.log_l, dst);
         cur = dst;
     }
-    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
     if (!pts) {  // (a point's "interpolant" is its value: nothing to transform)
         uint32_t* y = const_cast<uint32_t*>(launch_fr_dft(st, cur, FA, FB, sh.log_l, D, tw + 2 * kNttTableLen));
         launch_vc_fr_twist(st, y, (const uint32_t*)ids, (uint32_t)D, tw + 2 * kNttTableLen, sh.log_n, sh.log_l,
@@ -4045,15 +3895,15 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     };
     g1_plan(plan_t, at_t, rec(0), rec(oT));
     if (pts) launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, dpoints, 0, rec(oAT));
-    else launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, (const Glv*)ctx->d_glv, ctx->glv_log - log_M, rec(oAT));
+    else launch_vc_cell_scale(st, rec(oT), (const uint32_t*)ids, (uint32_t)D, (const Glv*)ctx->glv.p, ctx->glv_log - log_M, rec(oAT));
     HIP_TRY(ctx, hipGetLastError());
-    rc = vc_sync(ctx, lk, st, what.c_str());
+    rc = sync_unlocked(ctx, lk, st, what.c_str());
     if (rc) return rc;
     std::vector<hf::Fr> A(l);
     uint32_t herr[kVcErrWords];
     HIP_TRY(ctx, hipMemcpyAsync(A.data(), coef, l * 32, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, st));
-    rc = vc_sync(ctx, lk, st);
+    rc = sync_unlocked(ctx, lk, st, "verify cells");
     if (rc) return rc;
     if (herr[kVcErrWireProof] != 0xffffffffu || herr[kVcErrWireCommitment] != 0xffffffffu) {
         const bool proof = herr[kVcErrWireProof] != 0xffffffffu;
@@ -4080,16 +3930,16 @@ static int vc_device(kzg_ctx* ctx, const VcBatch& vb, uint64_t out_lhs[18], uint
     const hf::Fr zero = {{0, 0, 0, 0}};
     for (size_t i = 0; i < l; i++) gs[i] = glv_split(hf::fr_sub(zero, A[i]));
     HIP_TRY(ctx, hipMemcpyAsync(dglvs, gs.data(), l * sizeof(Glv), hipMemcpyHostToDevice, st));
-    launch_vc_ladder(st, ctx->d_table, nullptr, (const Glv*)dglvs, (uint32_t)l, 0, 0, nullptr, rec(oS), err);
+    launch_vc_ladder(st, ctx->table.p, nullptr, (const Glv*)dglvs, (uint32_t)l, 0, 0, nullptr, rec(oS), err);
     g1_plan(plan_fin, at_fin, rec(oT), rec(oOut));
     launch_xyzz_to_affine(st, rec(oOut), 2, aff, prefix);
     launch_affine_to_p1(st, aff, 2, p1);
     HIP_TRY(ctx, hipGetLastError());
-    rc = vc_sync(ctx, lk, st);  // gs goes out of scope
+    rc = sync_unlocked(ctx, lk, st, "verify cells");  // gs goes out of scope
     if (rc) return rc;
     uint64_t sides[36];
     HIP_TRY(ctx, hipMemcpyAsync(sides, p1, 2 * 144, hipMemcpyDeviceToHost, st));
-    rc = vc_sync(ctx, lk, st);
+    rc = sync_unlocked(ctx, lk, st, "verify cells");
     if (rc) return rc;
     std::memcpy(out_lhs, sides, 144);
     std::memcpy(out_rhs, sides + 18, 144);
@@ -4343,15 +4193,15 @@ static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t ba
     rc = ensure_slot_basics(ctx, s);
     if (rc == KZG_OK) rc = ensure_poly(ctx, s, chunk * per);
     void* wire = nullptr;  // a chunk's bytes, then the error word
-    if (rc == KZG_OK && wire_be) rc = vc_ws(ctx, kVcWire, chunk * n * 32 + 16, &wire);
+    if (rc == KZG_OK && wire_be) rc = ctx->vc_ws.get(ctx, kVcWire, chunk * n * 32 + 16, &wire);
     if (rc) return rc;
     const uint32_t tiles = bary_tiles(lg);
     const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
-    // d_q: [partials: chunk x tiles records | points: chunk Fr30 | results: chunk x 8 words]
-    uint32_t* partial = s.d_q;
+    // q: [partials: chunk x tiles records | points: chunk Fr30 | results: chunk x 8 words]
+    uint32_t* partial = s.q.dev();
     Fr30* dz = (Fr30*)(partial + chunk * tiles * kBaryPartialWords);
     uint32_t* res = (uint32_t*)(dz + chunk);
-    res += (4 - ((res - s.d_q) & 3)) & 3;  // 16-byte aligned
+    res += (4 - ((res - s.q.dev()) & 3)) & 3;  // 16-byte aligned
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t bc = std::min(chunk, batch - b0);
         uint32_t herr = 0xffffffffu;
@@ -4361,19 +4211,19 @@ static int bary_host(kzg_ctx* ctx, const uint64_t* evals, uint32_t lg, size_t ba
             if (stride == n || bc == 1) HIP_TRY(ctx, hipMemcpyAsync(wire, src, bc * n * 32, hipMemcpyHostToDevice, s.stream));
             else HIP_TRY(ctx, hipMemcpy2DAsync(wire, n * 32, src, stride * 32, n * 32, bc, hipMemcpyHostToDevice, s.stream));
             HIP_TRY(ctx, hipMemsetAsync(d_err, 0xff, 4, s.stream));
-            launch_wire_fr(s.stream, wire, (uint32_t)(bc * n), lg, bit_reversed, s.d_stage, d_err);
+            launch_wire_fr(s.stream, wire, (uint32_t)(bc * n), lg, bit_reversed, s.stage.dev(), d_err);
             HIP_TRY(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s.stream));
         } else if (stride == n || bc == 1)
-            HIP_TRY(ctx, hipMemcpyAsync(s.d_stage, evals + 4 * b0 * stride, bc * n * 32, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(ctx, hipMemcpyAsync(s.stage.dev(), evals + 4 * b0 * stride, bc * n * 32, hipMemcpyHostToDevice, s.stream));
         else
-            HIP_TRY(ctx, hipMemcpy2DAsync(s.d_stage, n * 32, evals + 4 * b0 * stride, stride * 32, n * 32, bc, hipMemcpyHostToDevice,
+            HIP_TRY(ctx, hipMemcpy2DAsync(s.stage.dev(), n * 32, evals + 4 * b0 * stride, stride * 32, n * 32, bc, hipMemcpyHostToDevice,
                                           s.stream));
         HIP_TRY(ctx, hipMemcpyAsync(dz, z30.data() + b0, bc * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
         uint32_t* out = d_ys ? d_ys + 8 * b0 : res;
-        launch_bary(s.stream, s.d_stage, lg, (uint32_t)bc, dz, ctx->d_ntt_tw, inv_n, partial, out);
+        launch_bary(s.stream, s.stage.dev(), lg, (uint32_t)bc, dz, ctx->ntt_tw.p, inv_n, partial, out);
         HIP_TRY(ctx, hipGetLastError());
         if (out_ys) HIP_TRY(ctx, hipMemcpyAsync(out_ys + 4 * b0, out, bc * 32, hipMemcpyDeviceToHost, s.stream));
-        rc = vc_sync(ctx, lk, s.stream, what);
+        rc = sync_unlocked(ctx, lk, s.stream, what);
         if (rc) return rc;
         if (herr != 0xffffffffu) {
             ctx->last_error = std::string(what) + ": polynomial " + std::to_string(b0 + (herr >> lg)) + ": value " +
@@ -4652,7 +4502,7 @@ static int verify_evaluations_impl(kzg_ctx* ctx, const uint64_t* evals_fr_mont, 
             return KZG_ERR_NO_SRS;
         }
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        rc = vc_ws(ctx, kVcCells, batch * 32, &d_ys);
+        rc = ctx->vc_ws.get(ctx, kVcCells, batch * 32, &d_ys);
         if (rc) return rc;
     }
     rc = bary_host(ctx, evals_fr_mont, lg, batch, stride, zs, (uint32_t*)d_ys, out_ys, wire ? wire->blobs_be : nullptr,
@@ -4767,11 +4617,11 @@ int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int che
     Slot& s = ctx->slots[slot];
     int rc = ensure_slot_basics(ctx, s);
     void *p1 = nullptr, *aff = nullptr, *coef = nullptr, *dglv = nullptr, *g1 = nullptr;
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcP1, n * 144, &p1);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcAff, n * kAffineBytes, &aff);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, kVcErrWords * 4, &coef);
-    if (rc == KZG_OK && check_subgroup) rc = vc_ws(ctx, kVcGlv, n * sizeof(Glv), &dglv);
-    if (rc == KZG_OK && check_subgroup) rc = vc_ws(ctx, kVcG1, n * kXyzzBytes, &g1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcP1, n * 144, &p1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcAff, n * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCoefA, kVcErrWords * 4, &coef);
+    if (rc == KZG_OK && check_subgroup) rc = ctx->vc_ws.get(ctx, kVcGlv, n * sizeof(Glv), &dglv);
+    if (rc == KZG_OK && check_subgroup) rc = ctx->vc_ws.get(ctx, kVcG1, n * kXyzzBytes, &g1);
     if (rc) return rc;
     const hipStream_t st = s.stream;
     uint32_t* err = (uint32_t*)coef;
@@ -4787,7 +4637,7 @@ int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int che
     uint32_t herr[kVcErrWords];
     HIP_TRY(ctx, hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(out_p1, p1, n * 144, hipMemcpyDeviceToHost, st));
-    rc = vc_sync(ctx, lk, st, "g1 uncompress");
+    rc = sync_unlocked(ctx, lk, st, "g1 uncompress");
     if (rc) return rc;
     const uint32_t enc = herr[kVcErrWireProof], grp = std::min(herr[kVcErrCurve], herr[kVcErrG1]);
     if (enc != 0xffffffffu || grp != 0xffffffffu) {
@@ -4820,9 +4670,9 @@ int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint
     Slot& s = ctx->slots[slot];
     int rc = ensure_slot_basics(ctx, s);
     void *wire = nullptr, *vals = nullptr, *coef = nullptr;
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcWire, n * 32, &wire);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCells, n * 32, &vals);
-    if (rc == KZG_OK) rc = vc_ws(ctx, kVcCoefA, kVcErrWords * 4, &coef);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcWire, n * 32, &wire);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCells, n * 32, &vals);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCoefA, kVcErrWords * 4, &coef);
     if (rc) return rc;
     const hipStream_t st = s.stream;
     uint32_t* err = (uint32_t*)coef;
@@ -4833,7 +4683,7 @@ int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint
     uint32_t herr = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&herr, err + kVcErrWireValue, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(out_fr_mont, vals, n * 32, hipMemcpyDeviceToHost, st));
-    rc = vc_sync(ctx, lk, st, "fr from bytes");
+    rc = sync_unlocked(ctx, lk, st, "fr from bytes");
     if (rc) return rc;
     if (herr != 0xffffffffu) {
         if (bad_index) *bad_index = herr;
@@ -4862,30 +4712,6 @@ void blob_infinity(uint8_t* out48, size_t count) {
 }
 }  // namespace
 
-static int blob_ws(kzg_ctx* ctx, int i, size_t bytes, void** out) {
-    if (bytes > ctx->blob_ws_bytes[i] || !ctx->blob_ws[i]) {
-        hipFree(ctx->blob_ws[i]);
-        ctx->blob_ws[i] = nullptr;
-        ctx->blob_ws_bytes[i] = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->blob_ws[i], bytes ? bytes : 256));
-        ctx->blob_ws_bytes[i] = bytes;
-    }
-    *out = ctx->blob_ws[i];
-    return KZG_OK;
-}
-// a copy on the stream without the mutex (pageable host memory: the call may block)
-static int blob_copy(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, void* dst, const void* src, size_t bytes,
-                     hipMemcpyKind kind) {
-    if (!bytes) return KZG_OK;
-    lk.unlock();
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
-    lk.lock();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMemcpyAsync (blobs): ") + hipGetErrorString(e);
-        return KZG_ERR_HIP;
-    }
-    return KZG_OK;
-}
 // polynomials per pass through the workspaces: fk20_host's rule, with this path's own buffers counted in
 static size_t blob_chunk(kzg_ctx* ctx, size_t n, const CellsShape* sh, const Fk20Plan& pl) {
     size_t per_poly = 3 * n * 32;
@@ -4893,7 +4719,7 @@ static size_t blob_chunk(kzg_ctx* ctx, size_t n, const CellsShape* sh, const Fk2
         per_poly += 3 * sh->N * 32 + sh->cells * 48;
         if (pl.m) {
             const size_t L = (size_t)1 << pl.log_L, M = sh->cells, X = L > M ? L : M;
-            const size_t ci = ctx->d_fk20_tab ? L : fk20_stream_positions(pl.log_L, sh->log_l);
+            const size_t ci = ctx->fk20_tab.p ? L : fk20_stream_positions(pl.log_L, sh->log_l);
             per_poly += n * 32 + sh->l * L * 64 + (sh->l > 1 ? sh->l * ci * kXyzzBytes : 0) + 3 * X * kXyzzBytes + M * 336;
         }
     }
@@ -4907,7 +4733,7 @@ static int blob_fk20_ready(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot&
     int rc = ensure_glv(ctx, lk, pl.log_L > log_M ? pl.log_L : log_M, s0.stream);
     if (rc == KZG_OK) rc = ensure_fk20_table(ctx, lk, s0.stream, pl.log_L, sh.log_l);
     if (rc) return rc;
-    if (!ctx->d_fk20_tab) {
+    if (!ctx->fk20_tab.p) {
         const size_t sb = (size_t)fk20_stream_positions(pl.log_L, sh.log_l) << sh.log_l;
         HIP_TRY(ctx, hipMalloc(&pl.stab.p, sb * kFk20CombEntries * kAffineBytes));
         HIP_TRY(ctx, hipMalloc(&pl.stmp.p, sb * kFk20CombEntries * kXyzzBytes));
@@ -4929,16 +4755,16 @@ static int blob_proofs(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s0,
     if (rc) return rc;
     const uint32_t log_M = sh.log_n - sh.log_l;
     void* enc = nullptr;
-    rc = blob_ws(ctx, kBlobProofs, bc * M * 48, &enc);
+    rc = ctx->blob_ws.get(ctx, kBlobProofs, bc * M * 48, &enc);
     if (rc) return rc;
     // all n coefficients, trailing zeros included: one shape for every chunk of the call, the one kzg_fk20_prepare(n) builds
     rc = fk20_proofs(ctx, lk, s0.stream, nullptr, n, bc, n, pl.m, pl.log_L, sh.log_l, log_M, nullptr, pl.stab.p, pl.stmp.p, pl.spre.p,
                      d_coef, true);
     if (rc) return rc;
-    launch_enc_g1(s0.stream, ctx->fk20_ws[kWsAff], (uint32_t)(bc * M), log_M, bit_reversed, enc);
+    launch_enc_g1(s0.stream, ctx->fk20_ws.buf[kWsAff].p, (uint32_t)(bc * M), log_M, bit_reversed, enc);
     HIP_TRY(ctx, hipGetLastError());
-    rc = blob_copy(ctx, lk, s0.stream, out48, enc, bc * M * 48, hipMemcpyDeviceToHost);
-    const int r2 = fk20_sync(ctx, lk, s0.stream);
+    rc = copy_unlocked(ctx, lk, s0.stream, out48, enc, bc * M * 48, hipMemcpyDeviceToHost, "hipMemcpyAsync (blobs)");
+    const int r2 = sync_unlocked(ctx, lk, s0.stream, "fk20");
     return rc ? rc : r2;
 }
 
@@ -5017,14 +4843,14 @@ static int blobs_device(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, uint32_
     size_t chunk = blob_chunk(ctx, n, sh, pl);
     if (chunk > batch) chunk = batch;
     void *wire, *a, *b, *pad = nullptr, *words;
-    rc = blob_ws(ctx, kBlobWire, chunk * n * 32, &wire);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, chunk * N * 32, &a);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, chunk * N * 32, &b);
-    if (rc == KZG_OK && out_cells) rc = blob_ws(ctx, kBlobP, chunk * N * 32, &pad);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    rc = ctx->blob_ws.get(ctx, kBlobWire, chunk * n * 32, &wire);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobA, chunk * N * 32, &a);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobB, chunk * N * 32, &b);
+    if (rc == KZG_OK && out_cells) rc = ctx->blob_ws.get(ctx, kBlobP, chunk * N * 32, &pad);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
     if (rc) return rc;
     uint32_t *A = (uint32_t*)a, *B = (uint32_t*)b, *P = (uint32_t*)pad, *err = (uint32_t*)words, *trim = err + kBlobErrWords;
-    const Fr30* tw = (const Fr30*)ctx->d_ntt_tw;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
     const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
     std::vector<uint32_t> hw(kBlobErrWords + chunk);
     BlobCommits commits{ctx, lk};
@@ -5051,7 +4877,7 @@ static int blobs_device(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, uint32_
         launch_poly_trim(st, coef, (uint32_t)n, n, (uint32_t)bc, &inv_n, trim);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(hw.data(), words, (kBlobErrWords + bc) * 4, hipMemcpyDeviceToHost, st));
-        rc = fk20_sync(ctx, lk, st);
+        rc = sync_unlocked(ctx, lk, st, "fk20");
         if (rc) return rc;
         if (hw[0] != 0xffffffffu) {
             ctx->last_error = "blobs: polynomial " + std::to_string(b0 + hw[0] / n) + ": value " + std::to_string(hw[0] % n) +
@@ -5085,11 +4911,11 @@ static int blobs_device(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, uint32_
             uint32_t* enc = ev == P ? P : other;  // the transform's buffer is free again
             launch_enc_fr(st, dst, (uint32_t)(bc * N), sh->log_l, sh->log_n - sh->log_l, bit_reversed, enc, err + 1);
             HIP_TRY(ctx, hipGetLastError());
-            return blob_copy(ctx, lk, st, out_cells + 32 * N * b0, enc, bc * N * 32, hipMemcpyDeviceToHost);
+            return copy_unlocked(ctx, lk, st, out_cells + 32 * N * b0, enc, bc * N * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (blobs)");
         };
         if (rc == KZG_OK && out_cells) rc = cells();
         if (rc == KZG_OK && out_proofs) rc = blob_proofs(ctx, lk, s0, coef, n, bc, *sh, bit_reversed, n_max, pl, out_proofs + 48 * M * b0);
-        const int r2 = fk20_sync(ctx, lk, st);
+        const int r2 = sync_unlocked(ctx, lk, st, "fk20");
         if (rc == KZG_OK) rc = r2;
         if (out_commitments) rc = commits.finish(rc, bc, out_commitments + 48 * b0);
         if (rc) return rc;
@@ -5190,7 +5016,7 @@ int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_doma
     w.bit_reversed = bit_reversed;
     w.ids_sent = cell_ids;
     w.out_cells_be = out_cells_be;
-    int rc = blob_ws(ctx, kBlobCoef, batch * n * 32, &w.d_coeffs);  // (fk20_mu guards the workspaces)
+    int rc = ctx->blob_ws.get(ctx, kBlobCoef, batch * n * 32, &w.d_coeffs);  // (fk20_mu guards the workspaces)
     if (rc) return rc;
     rc = recover_host(ctx, sh, n, pos.data(), missing, k, nullptr, batch, nullptr, nullptr, &w);
     if (rc || !out_proofs48) return rc;
@@ -5202,7 +5028,7 @@ int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_doma
     SlotLease lease{ctx, slot0};
     Slot& s0 = ctx->slots[slot0];
     void* words = nullptr;
-    rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    rc = ctx->blob_ws.get(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
     if (rc) return rc;
     uint32_t* trim = (uint32_t*)words + kBlobErrWords;
     size_t chunk = blob_chunk(ctx, n, &sh, pl);
@@ -5215,7 +5041,7 @@ int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_doma
         launch_poly_trim(s0.stream, coef, (uint32_t)n, n, (uint32_t)bc, nullptr, trim);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(ht.data(), trim, bc * 4, hipMemcpyDeviceToHost, s0.stream));
-        rc = fk20_sync(ctx, lk, s0.stream);
+        rc = sync_unlocked(ctx, lk, s0.stream, "fk20");
         if (rc) return rc;
         size_t n_max = 0;
         for (size_t i = 0; i < bc; i++) {
@@ -5253,19 +5079,19 @@ int kzg_g1_compress_batch(kzg_ctx* ctx, const uint64_t* in_p1, size_t n, uint8_t
     Slot& s = ctx->slots[slot];
     int rc = ensure_slot_basics(ctx, s);
     void *jac = nullptr, *aff = nullptr, *prefix = nullptr, *enc = nullptr;
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobP1, n * 144, &jac);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, n * kAffineBytes, &aff);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, n * 64, &prefix);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobProofs, n * 48, &enc);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobP1, n * 144, &jac);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobA, n * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobB, n * 64, &prefix);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobProofs, n * 48, &enc);
     if (rc) return rc;
     const hipStream_t st = s.stream;
-    rc = blob_copy(ctx, lk, st, jac, in_p1, n * 144, hipMemcpyHostToDevice);
+    rc = copy_unlocked(ctx, lk, st, jac, in_p1, n * 144, hipMemcpyHostToDevice, "hipMemcpyAsync (blobs)");
     if (rc) return rc;
     launch_jacobian_to_affine(st, jac, (uint32_t)n, aff, prefix);
     launch_enc_g1(st, aff, (uint32_t)n, 0, false, enc);
     HIP_TRY(ctx, hipGetLastError());
-    rc = blob_copy(ctx, lk, st, out48, enc, n * 48, hipMemcpyDeviceToHost);
-    const int r2 = fk20_sync(ctx, lk, st);
+    rc = copy_unlocked(ctx, lk, st, out48, enc, n * 48, hipMemcpyDeviceToHost, "hipMemcpyAsync (blobs)");
+    const int r2 = sync_unlocked(ctx, lk, st, "fk20");
     return rc ? rc : r2;
 }
 
@@ -5290,21 +5116,21 @@ int kzg_fr_to_bytes_batch(kzg_ctx* ctx, const uint64_t* in_fr_mont, size_t n, ui
     Slot& s = ctx->slots[slot];
     int rc = ensure_slot_basics(ctx, s);
     void *vals = nullptr, *enc = nullptr, *words = nullptr;
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobA, n * 32, &vals);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobB, n * 32, &enc);
-    if (rc == KZG_OK) rc = blob_ws(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobA, n * 32, &vals);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobB, n * 32, &enc);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
     if (rc) return rc;
     const hipStream_t st = s.stream;
     uint32_t* err = (uint32_t*)words;
     HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kBlobErrWords * 4, st));
-    rc = blob_copy(ctx, lk, st, vals, in_fr_mont, n * 32, hipMemcpyHostToDevice);
+    rc = copy_unlocked(ctx, lk, st, vals, in_fr_mont, n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blobs)");
     if (rc) return rc;
     launch_enc_fr(st, vals, (uint32_t)n, 0, 0, false, enc, err);
     HIP_TRY(ctx, hipGetLastError());
     uint32_t herr = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
-    rc = blob_copy(ctx, lk, st, out32_be, enc, n * 32, hipMemcpyDeviceToHost);
-    const int r2 = fk20_sync(ctx, lk, st);
+    rc = copy_unlocked(ctx, lk, st, out32_be, enc, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (blobs)");
+    const int r2 = sync_unlocked(ctx, lk, st, "fk20");
     if (rc || r2) return rc ? rc : r2;
     if (herr != 0xffffffffu) {
         if (bad_index) *bad_index = herr;
@@ -5676,7 +5502,7 @@ int kzg_srs_update(kzg_ctx* ctx, const uint8_t tau_be[32], uint64_t first) {
     TmpStream st;
     HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     tr.mark("alloc");
-    launch_srs_update(st.s, raw, first, (uint32_t)n, ctx->d_table, d_xyzz.p);
+    launch_srs_update(st.s, raw, first, (uint32_t)n, ctx->table.p, d_xyzz.p);
     if (tr.on) HIP_TRY(ctx, hipStreamSynchronize(st.s));
     tr.mark("ladder");
     launch_xyzz_to_affine(st.s, d_xyzz.p, (uint32_t)n, d_new.p, d_prefix.p);
@@ -5686,17 +5512,13 @@ int kzg_srs_update(kzg_ctx* ctx, const uint8_t tau_be[32], uint64_t first) {
     // from here on a failure leaves the context without an SRS: everything derived from the old one goes, as in srs_prepare
     ctx->slots_ready = false;
     for (auto& s : ctx->slots) s.kind = SLOT_IDLE;
-    if (ctx->d_fk20_B) {  // the FK20 cache holds transforms of the old SRS
-        hipFree(ctx->d_fk20_B);
-        hipFree(ctx->d_fk20_tab);
-        ctx->d_fk20_B = ctx->d_fk20_tab = nullptr;
-    }
-    rc = hipMemcpyAsync(ctx->d_table, d_new.p, n * kAffineBytes, hipMemcpyDeviceToDevice, st.s) == hipSuccess ? KZG_OK : KZG_ERR_HIP;
+    ctx->fk20_B.reset();  // the FK20 cache holds transforms of the old SRS
+    ctx->fk20_tab.reset();
+    rc = hipMemcpyAsync(ctx->table.p, d_new.p, n * kAffineBytes, hipMemcpyDeviceToDevice, st.s) == hipSuccess ? KZG_OK : KZG_ERR_HIP;
     if (rc == KZG_OK) rc = build_tables(ctx, st.s, d_xyzz.p, d_prefix.p);
     else ctx->last_error = "kzg_srs_update: copying the new points into the table failed";
     if (rc) {
-        hipFree(ctx->d_table);
-        ctx->d_table = nullptr;
+        ctx->table.reset();
         ctx->n = 0;
         for (auto& s : ctx->slots) free_slot_msm(s);
         (void)hipGetLastError();
@@ -5728,14 +5550,14 @@ static int srs_verify_device(kzg_ctx* ctx, SrsTrace& tr, const uint64_t* weights
         HIP_TRY(ctx, hipMalloc(&d_err.p, 256));
         HIP_TRY(ctx, hipMalloc(&d_p1.p, 144));
         HIP_TRY(ctx, hipMemsetAsync(d_err.p, 0xff, 8, st));
-        launch_srs_check(st, ctx->d_table, (uint32_t)n, (uint32_t*)d_err.p);
-        launch_affine_to_p1(st, ctx->d_table, 1, d_p1.p);
+        launch_srs_check(st, ctx->table.p, (uint32_t)n, (uint32_t*)d_err.p);
+        launch_affine_to_p1(st, ctx->table.p, 1, d_p1.p);
         HIP_TRY(ctx, hipGetLastError());
         uint32_t herr[2];
         uint64_t first_p1[18];
         HIP_TRY(ctx, hipMemcpyAsync(herr, d_err.p, sizeof herr, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(first_p1, d_p1.p, sizeof first_p1, hipMemcpyDeviceToHost, st));
-        rc = vc_sync(ctx, lk, st, "srs verify");
+        rc = sync_unlocked(ctx, lk, st, "srs verify");
         if (rc) return rc;
         tr.mark("subgroup_check");
         for (int e = 0; e < 2; e++)
@@ -5779,13 +5601,8 @@ static int srs_verify_device(kzg_ctx* ctx, SrsTrace& tr, const uint64_t* weights
         }
         DevBuf d_sc;
         HIP_TRY(ctx, hipMalloc(&d_sc.p, (n + 1) * 32));
-        lk.unlock();
-        const hipError_t e = hipMemcpyAsync(d_sc.p, sc.data(), (n + 1) * 32, hipMemcpyHostToDevice, st);
-        lk.lock();
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("srs verify: hipMemcpyAsync (weights): ") + hipGetErrorString(e);
-            return KZG_ERR_HIP;
-        }
+        rc = copy_unlocked(ctx, lk, st, d_sc.p, sc.data(), (n + 1) * 32, hipMemcpyHostToDevice, "srs verify: hipMemcpyAsync (weights)");
+        if (rc) return rc;
         for (int pass = 0; pass < 2 && rc == KZG_OK; pass++) {
             rc = submit_commit_locked(ctx, slot, (const uint32_t*)d_sc.p + 8 * pass, 0, n, true, true);
             if (rc) break;

@@ -114,9 +114,10 @@ KZG_HD Fq fq_norm_wide(const Fq& a) {
     int32_t c[kQ - 1];
 #pragma unroll
     for (int i = 0; i < kQ - 1; i++) c[i] = ((a.d[i] >> 1) + (1 << (kQBits - 2))) >> (kQBits - 1);
-    r.d[0] = a.d[0] - (int32_t)((uint32_t)c[0] << kQBits);
+    // (unsigned: for a carry of 2 the subtrahend 2^31 is no int32, and d - INT32_MIN overflows where d - 2^31 does not)
+    r.d[0] = (int32_t)((uint32_t)a.d[0] - ((uint32_t)c[0] << kQBits));
 #pragma unroll
-    for (int i = 1; i < kQ - 1; i++) r.d[i] = a.d[i] - (int32_t)((uint32_t)c[i] << kQBits) + c[i - 1];
+    for (int i = 1; i < kQ - 1; i++) r.d[i] = (int32_t)((uint32_t)a.d[i] - ((uint32_t)c[i] << kQBits) + (uint32_t)c[i - 1]);
     r.d[kQ - 1] = a.d[kQ - 1] + c[kQ - 2];
     return r;
 }

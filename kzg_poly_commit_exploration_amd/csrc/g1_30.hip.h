@@ -155,6 +155,9 @@ KZG_HD void xyzz30_madd(XYZZ30& acc, const Affine30& p_in, bool neg) {
 // Digit forms: P, Rn, W, Y, ZZ, ZZZ, PP, PPP, Q leave a product with digits 0..11 in [-2^29, 2^29).  X = W + Q has digits
 // 0..11 in [-2^30, 2^30): it is read as the `c` of fq_mul_minus (any int32 digit) and as ONE operand of X PP (2^30 x 2^29 =
 // 2^59 <= 2.1 x 2^58, fq_mul's contract).  PPP + 3 Q has digits in [-2^31, 2^31): `c` of fq_sqr_minus, it fits an int32.
+// (Where the tail did not run, Y is not a product's: xyzz30_acc_set leaves the table's y, negated or not, and a doubling leaves
+// X and Y behind a carry pass -- |digit| <= 2^29 + 4, which is all that Y's readers ask for: the `c` of fq_mul_plus and an
+// operand of fq_mul_sub.)
 // An accumulator that LEAVES the kernel gets one carry pass on X first (xyzz30_acc_settle): its readers -- xyzz30_add*,
 // xyzz30_dbl_body (which squares X), the host tail's px_from_record -- see |digit| <= 2^29 + 4 as from xyzz30_madd.
 //   xyzz30_acc_head  P, Rn and the lane's case (products on zero operands are harmless): 0 = the tail is all that is left;

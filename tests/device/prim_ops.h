@@ -99,12 +99,60 @@ PRIM_FN void pop_fq_canon_half(const int32_t* in, int32_t* out) {
     out[kF] = fq_digits_greater(c, fq_const_half()) ? 1 : 0;
 }
 PRIM_FN void pop_fq_inv(const int32_t* in, int32_t* out) { st_fq(out, fq_inv(ld_fq(in))); }
+// the products that take a third value into their own carry pass (the accumulation kernel's arithmetic): a, b, c
+PRIM_FN void pop_fq_mul_minus(const int32_t* in, int32_t* out) {
+    st_fq(out, fq_mul_minus(ld_fq(in), ld_fq(in + kF), ld_fq(in + 2 * kF)));
+}
+PRIM_FN void pop_fq_mul_plus(const int32_t* in, int32_t* out) {
+    st_fq(out, fq_mul_plus(ld_fq(in), ld_fq(in + kF), ld_fq(in + 2 * kF)));
+}
+PRIM_FN void pop_fq_sqr_minus(const int32_t* in, int32_t* out) { st_fq(out, fq_sqr_minus(ld_fq(in), ld_fq(in + kF))); }
+PRIM_FN void pop_fq_maybe_zero(const int32_t* in, int32_t* out) { out[0] = fq_maybe_zero(ld_fq(in)) ? 1 : 0; }
 
 // ---- group law: acc (52) [, operand, flags] -> acc (52) -----------------------------------------------------------------
 PRIM_FN void pop_madd(const int32_t* in, int32_t* out) {  // acc, affine point, neg
     XYZZ30 acc = ld_xyzz(in);
     xyzz30_madd(acc, ld_affine(in + kX), in[kX + 2 * kF] != 0);
     st_xyzz(out, acc);
+}
+// ---- the accumulation kernel's form of the mixed addition (xyzz30_acc_*) -----------------------------------------------
+PRIM_FN void pop_acc_head(const int32_t* in, int32_t* out) {  // acc, affine point, neg -> code, P, Rn
+    Fq P, Rn;
+    out[0] = (int32_t)xyzz30_acc_head(ld_xyzz(in), ld_affine(in + kX), in[kX + 2 * kF] != 0, P, Rn);
+    st_fq(out + 1, P);
+    st_fq(out + 1 + kF, Rn);
+}
+PRIM_FN void pop_acc_rare(const int32_t* in, int32_t* out) {  // acc, P, Rn -> whether the tail is to run, acc
+    XYZZ30 acc = ld_xyzz(in);
+    out[0] = xyzz30_acc_rare(acc, ld_fq(in + kX), ld_fq(in + kX + kF)) ? 1 : 0;
+    st_xyzz(out + 1, acc);
+}
+PRIM_FN void pop_acc_tail(const int32_t* in, int32_t* out) {  // acc, P, Rn -> acc
+    XYZZ30 acc = ld_xyzz(in);
+    xyzz30_acc_tail(acc, ld_fq(in + kX), ld_fq(in + kX + kF));
+    st_xyzz(out, acc);
+}
+// (xyzz30_acc_set has no record of its own: xyzz30_acc_madd runs it for every accumulator at infinity)
+// acc as it stays inside the kernel (X a raw sum of two), then as it leaves it (xyzz30_acc_settle)
+PRIM_FN void st_acc_both(int32_t* out, XYZZ30 acc) {
+    st_xyzz(out, acc);
+    xyzz30_acc_settle(acc);
+    st_xyzz(out + kX, acc);
+}
+PRIM_FN void pop_acc_madd(const int32_t* in, int32_t* out) {  // acc, affine point, neg -> acc unsettled, acc settled
+    XYZZ30 acc = ld_xyzz(in);
+    xyzz30_acc_madd(acc, ld_affine(in + kX), in[kX + 2 * kF] != 0);
+    st_acc_both(out, acc);
+}
+PRIM_FN void pop_chain_acc_madd(const int32_t* in, int32_t* out) {  // 16 x (point, neg) -> the 16 settled partial sums
+    XYZZ30 acc = xyzz30_inf();
+    for (int s = 0; s < kChain; s++) {
+        const int32_t* r = in + s * (2 * kF + 1);
+        xyzz30_acc_madd(acc, ld_affine(r), r[2 * kF] != 0);  // the UNSETTLED accumulator feeds the next step
+        XYZZ30 settled = acc;
+        xyzz30_acc_settle(settled);
+        st_xyzz(out + s * kX, settled);
+    }
 }
 PRIM_FN void pop_add(const int32_t* in, int32_t* out) {
     XYZZ30 acc = ld_xyzz(in);
@@ -206,7 +254,9 @@ PRIM_FN void pop_fr30_inv(const int32_t* in, int32_t* out) { st_fr(out, fr30_inv
     X(fq_neg, 13, 13) X(fq_cneg, 14, 13) X(fq_canon_digits, 13, 13) X(fq_is_zero, 13, 1) X(fq_from_u32x12, 12, 13) \
     X(fq_to_u32x12, 13, 12) X(fq_canon_half, 13, 14) X(fq_inv, 13, 13) X(madd, 79, 52) X(add, 104, 52)            \
     X(add_call, 104, 52) X(dbl, 52, 52) X(pair_classify, 54, 14) X(chain_madd, 16 * 27, 16 * 52)                   \
-    X(chain_add, 16 * 52, 16 * 52)
+    X(chain_add, 16 * 52, 16 * 52) X(fq_mul_minus, 39, 13) X(fq_mul_plus, 39, 13) X(fq_sqr_minus, 26, 13)         \
+    X(fq_maybe_zero, 13, 1) X(acc_head, 79, 27) X(acc_rare, 78, 53) X(acc_tail, 78, 52) X(acc_madd, 79, 104)       \
+    X(chain_acc_madd, 16 * 27, 16 * 52)
 #define PRIM_FR_OPS(X)                                                                                     \
     X(fr30_mul, 18, 9) X(fr30_norm, 9, 9) X(fr30_from_limbs, 8, 9) X(fr30_to_limbs, 9, 8) X(fr30_abs_to_limbs, 9, 9) \
     X(fr30_inv, 9, 9)

@@ -158,6 +158,51 @@ PRIM_QUAD(add_quad_dense_loop, k_add_quad_dense_loop, 209, 4 * 52)
 PRIM_QUAD(chain_quad, k_chain_quad<false>, 16 * 52, 16 * 4 * 52)
 PRIM_QUAD(chain_quad_dense, k_chain_quad<true>, 16 * 52, 16 * 4 * 52)
 
+// ---- one step of k_bucket_accumulate's dispatch: one lane per record, whole waves (the record count is a multiple of 64) ----
+// A COPY OF THE SHAPE of msm_accum.hip around accum_rare_call, which it has to follow when that changes: the head, the
+// wave-uniform ballot branch over the lanes that have a case, the first point of a run read a second time, equal or opposite
+// operands (and the pre-test's false positives) through a struct in private memory into ONE real call that hands acc, P and
+// Rn back through the same memory, and the tail last, on whatever came back.  (The kernel itself is not shared with this
+// file: its code generation stays its own.)  out: the accumulator as it stays in the kernel, then settled.
+struct DispatchRare {
+    XYZZ30 acc;
+    Fq P, Rn;
+};
+static __device__ __noinline__ bool dispatch_rare_call(DispatchRare* io) { return xyzz30_acc_rare(io->acc, io->P, io->Rn); }
+__global__ void __launch_bounds__(kBlock) k_acc_dispatch(const int32_t* __restrict__ in, int32_t* __restrict__ out, int n) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int32_t* r = in + (size_t)i * (kX + 2 * kF + 1);
+    const bool neg = r[kX + 2 * kF] != 0;
+    XYZZ30 acc = ld_xyzz(r);
+    Fq P, Rn;
+    uint32_t code;
+    {
+        const Affine30 p = ld_affine(r + kX);
+        code = xyzz30_acc_head(acc, p, neg, P, Rn);
+    }
+    bool more = code == 0;
+    if (__builtin_amdgcn_ballot_w64(code != 0) != 0) {  // (wave-uniform)
+        if (code & kAccFresh) {
+            if (!(code & kAccPointInf)) {
+                const Affine30 p = ld_affine(r + kX);  // read a second time
+                xyzz30_acc_set(acc, p, neg);
+            }
+        } else if (code == kAccMaybeEqual) {
+            DispatchRare t;
+            t.acc = acc;
+            t.P = P;
+            t.Rn = Rn;
+            more = dispatch_rare_call(&t);
+            acc = t.acc;
+            P = t.P;
+            Rn = t.Rn;
+        }
+    }
+    if (more) xyzz30_acc_tail(acc, P, Rn);
+    st_acc_both(out + (size_t)i * 2 * kX, acc);
+}
+
 // ---- the quad moves on their own: one lane per record -----------------------------------------------------------------------
 // every lane holds its own value v.  out[0..3] = broadcast<SRC>(v) - v: the subtraction right behind the move is the pattern
 // that LLVM's DPP combiner folded (g1_30.hip.h); out[4..7] = broadcast<SRC + 1>(v) - broadcast<SRC>(v): both operands moves
@@ -190,5 +235,6 @@ __global__ void __launch_bounds__(kBlock) k_quad_select(const int32_t* __restric
         return run(in, (size_t)n * (IW), out, (size_t)n * (OW),                                                 \
                    [&](Buffers& b) { hipLaunchKernelGGL(k_##NAME, dim3(blocks_for(n)), dim3(kBlock), 0, 0, b.in, b.out, n); }); \
     }
+PRIM_LANES64(acc_dispatch, 79, 104)
 PRIM_LANES64(quad_broadcast, 13, 104)
 PRIM_LANES64(quad_select, 52, 13)

@@ -89,6 +89,40 @@ int f30f_same_point(const int32_t* pa, const int32_t* pb) {
     return fq_is_zero(dx) && fq_is_zero(dy);
 }
 
+// ---- the zero pre-test's false positives through k_bucket_accumulate itself (tests/accum_false_positives.py) ----------------
+// the level-0 table digits of blst affine words (12 x u32 per coordinate, Montgomery 2^384, below 2 p), as
+// k_affine96_to_table (srs_io.hip) stores them: the same two calls, so the same digits bit for bit
+void f30f_table_digits(const uint32_t* words, int n, int32_t* out) {
+    for (int i = 0; i < n; i++) {
+        const Fq z = fq_mul(fq_from_u32x12(words + 12 * (size_t)i), fq_one());
+        memcpy(out + 13 * (size_t)i, z.d, sizeof z.d);
+    }
+}
+// per coordinate x (13 digits): the low 30 bits of x * one -- the U2 of xyzz30_acc_head when the accumulator was just set from
+// a point (ZZ = fq_one_cold()) -- and of x itself, the X that is subtracted then
+void f30f_low_bits(const int32_t* x, int n, uint32_t* lo_mul, uint32_t* lo_x) {
+    const Fq one = fq_one_cold();
+    for (int i = 0; i < n; i++) {
+        lo_mul[i] = (uint32_t)fq_mul(fq_of(x + 13 * (size_t)i), one).d[0] & (uint32_t)kQMask;
+        lo_x[i] = (uint32_t)x[13 * (size_t)i] & (uint32_t)kQMask;
+    }
+}
+// xyzz30_acc_set with the point a (x, y: 26 digits), then xyzz30_acc_head with b: the code; *p_is_zero: whether P is a
+// multiple of p (code == kAccMaybeEqual with P != 0 is the pre-test's false positive)
+int f30f_set_then_head(const int32_t* a, int nega, const int32_t* b, int negb, int* p_is_zero) {
+    XYZZ30 acc = xyzz30_inf();
+    Affine30 pa, pb;
+    pa.x = fq_of(a);
+    pa.y = fq_of(a + 13);
+    pb.x = fq_of(b);
+    pb.y = fq_of(b + 13);
+    xyzz30_acc_set(acc, pa, nega != 0);
+    Fq P, Rn;
+    const uint32_t code = xyzz30_acc_head(acc, pb, negb != 0, P, Rn);
+    *p_is_zero = fq_is_zero(P) ? 1 : 0;
+    return (int)code;
+}
+
 }  // extern "C"
 
 #ifdef F30_FUSED_MAIN
@@ -198,6 +232,30 @@ int main() {
     f30f_add(sum_new, settled);  // equal operands: the doubling branch squares X
     f30f_add(sum_old, a_old);
     CHECK(f30f_same_point(sum_new, sum_old));
+    // the exports of the false-positive search: table digits of stored words, their low bits, "set, then head"
+    {
+        uint32_t words[3 * 12];
+        int32_t dig[3 * 13], a[26], b[26];
+        uint32_t lo_mul[3], lo_x[3];
+        for (int i = 0; i < 3 * 12; i++) words[i] = (i % 12 == 11) ? (rnd() & 0x0fffffffu) : rnd();  // below 2^380 < p
+        f30f_table_digits(words, 3, dig);
+        for (int i = 0; i < 3; i++) CHECK(strict(dig + 13 * i));
+        f30f_low_bits(dig, 3, lo_mul, lo_x);
+        for (int i = 0; i < 3; i++) CHECK(lo_x[i] == ((uint32_t)dig[13 * i] & 0x3fffffffu) && lo_mul[i] < (1u << 30));
+        memcpy(a, GX, sizeof GX);
+        memcpy(a + 13, GY, sizeof GY);
+        memcpy(b, a, sizeof a);
+        int zero_p = 0;
+        CHECK(f30f_set_then_head(a, 0, b, 0, &zero_p) == (int)kAccMaybeEqual && zero_p == 1);  // G, then G
+        CHECK(f30f_set_then_head(a, 1, b, 0, &zero_p) == (int)kAccMaybeEqual && zero_p == 1);  // -G, then G
+        memset(a_new, 0, sizeof a_new);
+        f30f_acc_madd(a_new, GX, GY, 0);
+        f30f_acc_madd(a_new, GX, GY, 0);  // 2 G
+        memcpy(b, a_new, 13 * 4);        // its X and Y as an "affine" pair of digits: another x than G's
+        memcpy(b + 13, a_new + 13, 13 * 4);
+        const int code = f30f_set_then_head(a, 0, b, 0, &zero_p);
+        CHECK((code == 0 && zero_p == 0) || code == (int)kAccMaybeEqual);
+    }
     if (fails) printf("%d checks failed\n", fails);
     else printf("all checks passed\n");
     return fails ? 1 : 0;

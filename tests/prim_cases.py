@@ -108,7 +108,11 @@ def rep(x, m10, rng, extreme):
 
 def mont_py(a, b):
     """the exact integer fq_mul returns for the integers a, b: (a b + m p) / 2^390 with m the balanced-digit residue"""
-    t = a * b
+    return mont_t(a * b)
+
+
+def mont_t(t):
+    """(t + m p) / 2^390 for the column sums t of one Montgomery reduction (fq_mul: a b; fq_mul_sub: a b - c d)"""
     u = (-t * pow(P, -1, RQ)) % RQ
     m = 0
     for i in range(13):
@@ -917,6 +921,476 @@ def t_quad_select():
     return t
 
 
+# ---- the accumulation kernel's arithmetic: products that carry a third value, xyzz30_acc_* ---------------------------------------
+# Everything below is modelled in integers: mont_py / mont_t give the exact integer of a reduction, so P, Rn and the whole
+# tail are known digit for digit (a product's digits 0..11 are the balanced ones of its integer), and so is what
+# fq_maybe_zero sees.
+LOW = (1 << B) - 1
+ZERO_RESIDUES = frozenset((k * P) & LOW for k in range(-3, 4))  # what digit 0 of k p can be, |k| <= 3
+ONE = balanced(RQ % P)                                          # fq_one()
+C_TOP = (1 << 31) - 4                                           # the largest digit of a raw sum of four: 4 (2^29 - 1)
+ACC_KINDS = KINDS + ("false_positive",)
+TAIL_KINDS = ("general", "false_positive")
+
+
+def _c_variants(rng):
+    """(name, digits) of the value taken into the carry pass: 0, raw sums of one to four normalised values, every digit at
+    +-(2^31 - 4) with both signs of digit 12, -2^31 (four times -2^29), weakly normalised digits"""
+    out = [("c=0", [0] * 13)]
+    for n in (1, 2, 3, 4):
+        parts = [balanced(_lazy(rng, 382)) for _ in range(n)]
+        out.append(("c=raw sum of %d" % n, [sum(col) for col in zip(*parts)]))
+    for s in (1, -1):
+        for s12 in (1, -1):
+            out.append(("c=%+d (2^31-4), digit 12 %+d 2^24" % (s, s12), [s * C_TOP] * 12 + [s12 << 24]))
+    out.append(("c=+-(2^31-4)", [rng.choice((1, -1)) * C_TOP for _ in range(12)] + [rng.randrange(-(1 << 24), 1 << 24)]))
+    out.append(("c=-2^31", [-(1 << 31)] * 12 + [1 << 24]))
+    out.append(("c=+-(2^29+4)", [rng.choice((1, -1)) * BIG for _ in range(12)] + [rng.randrange(-(1 << 24), 1 << 24)]))
+    return out
+
+
+def _check_fused(row, want, out):
+    """want: (the exact integer, the magnitude bound of field30.hip.h: 0.62 p + |a||b| / 2^390 + |c|)"""
+    v = value(out)
+    if v != want[0]:
+        return "integer %d, expected %d (difference %d)" % (v, want[0], v - want[0])
+    if not digits_ok(out):
+        return "digits outside [-2^29, 2^29): %s" % out
+    if not abs(v) < want[1]:
+        return "magnitude %.3f p" % (v / P)
+
+
+def _fused_want(a, b, c, sign):
+    va, vb, vc = value(a), value(b), value(c)
+    return mont_py(va, vb) + sign * vc, 62 * P // 100 + (abs(va * vb) >> 390) + abs(vc) + 1
+
+
+def t_fq_mul_addc(sign):
+    """fq_mul_minus (sign -1) / fq_mul_plus: exactly mont_py(a, b) -+ value(c).  Operands: the sets of fq_mul (adversarial sign
+    patterns of the column bound with one operand a raw sum of two, raw sums, 2^385, 0, +-1, +-p), every adversarial pair with
+    every form of c, the others with the forms of c in turn"""
+    name = "fq_mul_minus" if sign < 0 else "fq_mul_plus"
+    t = Table(name, name, 13, _check_fused)
+    rng = random.Random(1401 if sign < 0 else 1402)
+    cv = _c_variants(rng)
+    for i, (kind, a, b) in enumerate(_field_operand_sets(rng, False)):
+        for cname, c in (cv if kind == "adversarial" else [cv[i % len(cv)]]):
+            t.add("%s %s" % (kind, cname), a + b + c, _fused_want(a, b, c, sign))
+    return t
+
+
+def t_fq_sqr_minus():
+    """fq_sqr_minus: exactly mont_py(a, a) - value(c); a weakly normalised (the doubled operand of the square)"""
+    t = Table("fq_sqr_minus", "fq_sqr_minus", 13, _check_fused)
+    rng = random.Random(1403)
+    cv = _c_variants(rng)
+    n = 0
+    for kind, a, b in _field_operand_sets(rng, True):
+        for x in ((a,) if kind == "random" else (a, b)):
+            for cname, c in (cv if kind == "adversarial" else [cv[n % len(cv)]]):
+                t.add("%s %s" % (kind, cname), x + c, _fused_want(x, x, c, -1))
+            n += 1
+    return t
+
+
+def maybe_zero_py(v):
+    return 1 if (v & LOW) in ZERO_RESIDUES else 0
+
+
+def t_fq_maybe_zero():
+    """The one-word pre-test: true exactly when digit 0 is that of some k p, |k| <= 3, in whatever digits the value comes.
+    True on a non-zero value is BY DESIGN (7 of the 2^30 residues: the near misses here, 7 x 2^-30 of all additions in the
+    kernel): xyzz30_acc_rare runs the exact test behind it.  False must mean non-zero."""
+    def check(row, want, out):
+        if out[0] != want:
+            return "maybe_zero = %d for %+.4f p, digit 0 %s that of a multiple of p" % (out[0], value(row) / P, "is" if want else "is not")
+    t = Table("fq_maybe_zero", "fq_maybe_zero", 1, check)
+    rng = random.Random(1404)
+
+    def add(kind, d, expect):
+        assert maybe_zero_py(value(d)) == expect, kind
+        t.add(kind, d, expect)
+    for k in range(-3, 4):
+        d = balanced(k * P)
+        add("%dp canonical" % k, d, 1)
+        for j, up in ((0, 1), (0, -1), (11, 1), (5, -1)):
+            e = list(d)
+            e[j] += up << B
+            e[j + 1] -= up
+            add("%dp re-split at digit %d" % (k, j), e, 1)
+        for _ in range(8):
+            u = _lazy(rng, 382)
+            raw = [x - y for x, y in zip(balanced(u), balanced(u - k * P))]
+            assert value(raw) == k * P
+            add("%dp raw difference" % k, raw, 1)
+            add("%dp norm(raw difference)" % k, _weak(raw), 1)
+        for _ in range(16):  # the false positives: digit 0 of k p, another integer
+            v = k * P + rng.choice((-1, 1)) * rng.randrange(1, 1 << 350) * (1 << B)
+            assert v % P
+            add("near miss of %dp" % k, balanced(v), 1)
+        for off in (1, -1, 1 << 29, rng.randrange(2, 1 << 29)):
+            add("%dp + %d" % (k, off), balanced(k * P + off), 0)
+    for k in (-5, -4, 4, 5):
+        add("%dp" % k, balanced(k * P), 0)
+    for _ in range(512):
+        v = rng.randrange(-35 * P // 10 + 1, 35 * P // 10)
+        t.add("random", balanced(v), maybe_zero_py(v))
+    return t
+
+
+# ---- xyzz30_acc_*: operands ---------------------------------------------------------------------------------------------------
+def raw_two(d, rng, extreme):
+    """the integer of the balanced digits d in the digits X has inside the kernel: a raw sum W + Q of two normalised values,
+    each digit 0..11 in [-2^30, 2^30 - 2].  A digit is re-split to the far side of zero (extreme: wherever it can be)"""
+    out = list(d)
+    for i in range(12):
+        if not (extreme or rng.randrange(2)):
+            continue
+        s = -1 if out[i] >= 0 else 1
+        cand = out[i] + s * (1 << B)
+        if -(1 << B) <= cand <= (1 << B) - 2:
+            out[i] = cand
+            out[i + 1] -= s
+    assert value(out) == value(d) and digits_ok(out, -(1 << B), (1 << B) - 2), out
+    return out
+
+
+def _sqrt(v):
+    """a square root mod p (p = 3 mod 4), or None"""
+    s = pow(v, (P + 1) // 4, P)
+    return s if s * s % P == v % P else None
+
+
+def _acc_from_z(a, z, rng, extreme, raw_x, X=None):
+    zz, zzz = z * z % P, z * z * z % P
+    d = (rep(a[0] * zz % P, 26, rng, extreme) if X is None else X) + rep(a[1] * zzz % P, 13, rng, extreme) + \
+        rep(zz, 7, rng, extreme) + rep(zzz, 7, rng, extreme)
+    if raw_x and X is None:
+        d[:13] = raw_two(d[:13], rng, extreme)
+    return d
+
+
+def false_positive_row(rng, neg, extreme, raw_x):
+    """An addition of two different points whose P = U2 - X1 passes the one-word pre-test: t = 0 (mod 2^30) in [1, p),
+    ZZ = t / ((x_b - x_a) 2^390) where that is a square, so that P = t + k p; |P| < 3.3 p leaves k in -4 .. 3 and every k
+    but -4 is one of the seven residues.  Drawn again until it is; nothing is skipped.  -> (row, a, b)"""
+    while True:
+        a, b = operand_pair("general", rng)
+        t = rng.randrange(1, P >> B) << B
+        z = _sqrt(t * pow((b[0] - a[0]) * RQ, -1, P) % P)
+        if z is None:
+            continue
+        row = _acc_from_z(a, z, rng, extreme, raw_x) + affine_digits(T.g1_neg(b) if neg else b, rng, extreme) + [neg]
+        code, Pv, _ = head_py(row)
+        assert (Pv - t) % P == 0 and Pv % P != 0 and abs(Pv) < 33 * P // 10
+        if code != 4:
+            assert Pv == t - 4 * P
+            continue
+        return row, a, b
+
+
+def adversarial_x_row(kind, rng, sign, neg):
+    """An accumulator whose X has EVERY digit 0..11 at the end of the raw sum's range (-2^30 or 2^30 - 2; digit 12 free below
+    2.6 p): ZZ = X / (x_a 2^390) where that is a square.  Squared without the carry pass of xyzz30_acc_settle such an X
+    overflows the column bound (6 x 2^61 + 2^60 > 2^63), with it nothing does.  -> (row, a, b)"""
+    top = (26 * P // 10) >> 360
+    while True:
+        a, b = operand_pair(kind, rng)
+        X = [-(1 << B) if sign < 0 else (1 << B) - 2] * 12 + [rng.randrange(-top + 2, top - 1)]
+        assert abs(value(X)) < 26 * P // 10
+        z = _sqrt(value(X) * pow(a[0] * RQ, -1, P) % P)
+        if z is None:
+            continue
+        return _acc_from_z(a, z, rng, True, True, X) + affine_digits(T.g1_neg(b) if neg else b, rng, True) + [neg], a, b
+
+
+def acc_row(kind, rng, neg, extreme, raw_x):
+    """(79 ints: accumulator, point as handed over, neg; the accumulator's point; the point added)"""
+    if kind == "false_positive":
+        return false_positive_row(rng, neg, extreme, raw_x)
+    a, b = operand_pair(kind, rng)
+    acc = xyzz_digits(a, rng, extreme)
+    if raw_x and a is not None:
+        acc[:13] = raw_two(acc[:13], rng, extreme)
+    return acc + affine_digits(T.g1_neg(b) if neg else b, rng, extreme) + [neg], a, b
+
+
+# ---- xyzz30_acc_*: the integers of the same formulas ------------------------------------------------------------------------------
+def head_py(row):
+    """(code, P, Rn) of xyzz30_acc_head as integers: P = x2 ZZ - X, Rn = (-y2) ZZZ + Y with y2 negated when neg"""
+    X, Y, ZZ, ZZZ, px, py = (value(row[13 * j:13 * j + 13]) for j in range(6))
+    Pv = mont_py(px, ZZ) - X
+    Rn = mont_py(py if row[78] else -py, ZZZ) + Y
+    code = (0 if any(row[52:78]) else 1) | (0 if any(row[26:39]) else 2) | (4 if maybe_zero_py(Pv) else 0)
+    return code, Pv, Rn
+
+
+def tail_py(acc, Pv, Rn):
+    """the 52 digits xyzz30_acc_tail leaves: X = W + Q digit-wise, Y, ZZ, ZZZ straight from a product"""
+    X, Y, ZZ, ZZZ = (value(acc[13 * j:13 * j + 13]) for j in range(4))
+    PP = mont_py(Pv, Pv)
+    ZZ3 = mont_py(ZZ, PP)
+    Q = mont_py(X, PP)
+    PPP = mont_py(Pv, PP)
+    ZZZ3 = mont_py(ZZZ, PPP)
+    W = mont_py(Rn, Rn) - (PPP + 3 * Q)
+    Y3 = mont_t(Rn * W - Y * PPP)
+    return [w + q for w, q in zip(balanced(W), balanced(Q))] + balanced(Y3) + balanced(ZZ3) + balanced(ZZZ3)
+
+
+def check_acc_inside(out, want, tail_ran):
+    """the accumulator as it stays inside k_bucket_accumulate (g1_30.hip.h): the point, ZZ^3 = ZZZ^2, the magnitude line,
+    digits of X in [-2^30, 2^30).  Y, ZZ and ZZZ: straight from a product (digits in [-2^29, 2^29)) when the tail ran;
+    a doubling leaves Y behind a carry pass, a first point or an untouched accumulator is what came in (<= 2^29 + 4)"""
+    if want is None:
+        return None if not any(out) else "expected infinity as exact zeros, got %s" % out
+    X, Y, ZZ, ZZZ = (value(out[13 * i:13 * i + 13]) for i in range(4))
+    if ZZ % P == 0 or ZZZ % P == 0:
+        return "ZZ or ZZZ is zero mod p for a finite sum"
+    got = (X * pow(ZZ, -1, P) % P, Y * pow(ZZZ, -1, P) % P)
+    if got != want:
+        return "point (%x.., %x..), expected (%x.., %x..)" % (got[0] >> 320, got[1] >> 320, want[0] >> 320, want[1] >> 320)
+    if pow(ZZ * RQ_INV, 3, P) != pow(ZZZ * RQ_INV, 2, P):
+        return "ZZ^3 != ZZZ^2"
+    if not digits_ok(out[:13], -(1 << B), (1 << B) - 1):
+        return "digits of X outside [-2^30, 2^30): %s" % out[:13]
+    for i in (1, 2, 3):
+        d = out[13 * i:13 * i + 13]
+        if not (digits_ok(d) if tail_ran else digits_ok(d, -BIG, BIG)):
+            return "digits of coordinate %d outside %s: %s" % (i, "[-2^29, 2^29)" if tail_ran else "+-(2^29 + 4)", d)
+    for name, v, m10 in (("X", X, 26), ("Y", Y, 13), ("ZZ", ZZ, 7), ("ZZZ", ZZZ, 7)):
+        if not abs(v) < m10 * P // 10:
+            return "|%s| = %.3f p, stated bound %.1f p" % (name, abs(v) / P, m10 / 10)
+
+
+def _check_acc_madd(row, want, out):
+    """want: (the sum, whether xyzz30_acc_tail produces it).  Unsettled: check_acc_inside; settled: check_xyzz as it is,
+    the same Y, ZZ, ZZZ and one carry pass on X"""
+    pt, tail_ran = want
+    msg = check_acc_inside(out[:52], pt, tail_ran)
+    if msg:
+        return "inside the kernel: " + msg
+    msg = check_xyzz(out[52:], pt)
+    if msg:
+        return "settled: " + msg
+    if out[65:] != out[13:52] or out[52:65] != norm_py(out[:13]):
+        return "settled is not one carry pass on X and nothing else"
+
+
+_ACC_CASES = {}
+
+
+def acc_cases():
+    """[(kind, row, a, b)]: the six KINDS of t_madd and the constructed false positives x neg x extreme / random
+    representatives x X balanced / X as the kernel holds it (a raw sum of two), then X at the ends of the raw sum's range.
+    Built once, shared by the tables of the head, the rare call, the tail and the whole addition."""
+    if not _ACC_CASES:
+        rng = random.Random(1405)
+        cases = []
+        for it in range(7 * 8 * 12):
+            kind, neg, extreme, raw_x = ACC_KINDS[it % 7], (it // 7) & 1, bool((it // 14) & 1), bool((it // 28) & 1)
+            row, a, b = acc_row(kind, rng, neg, extreme, raw_x)
+            cases.append(("%s neg=%d %s X %s" % (kind, neg, "extreme" if extreme else "random", "raw" if raw_x else "balanced"), row, a, b))
+        for kind in LIVE:
+            for sign in (1, -1):
+                for neg in (0, 1):
+                    row, a, b = adversarial_x_row(kind, rng, sign, neg)
+                    cases.append(("%s neg=%d extreme X raw, every digit %s" % (kind, neg, "2^30 - 2" if sign > 0 else "-2^30"), row, a, b))
+        _ACC_CASES["all"] = cases
+    return _ACC_CASES["all"]
+
+
+def t_acc_madd():
+    t = Table("xyzz30_acc_madd", "acc_madd", 104, _check_acc_madd)
+    for kind, row, a, b in acc_cases():
+        t.add(kind, row, (T.g1_add(a, b), kind.startswith(TAIL_KINDS)))
+    return t
+
+
+def t_acc_head():
+    def check(row, want, out):
+        if out[0] != want[0]:
+            return "code %d, expected %d" % (out[0], want[0])
+        if out[1:14] != want[1]:
+            return "P = %s, expected %s" % (out[1:14], want[1])
+        if out[14:27] != want[2]:
+            return "Rn = %s, expected %s" % (out[14:27], want[2])
+    t = Table("xyzz30_acc_head", "acc_head", 27, check)
+    for kind, row, a, b in acc_cases():
+        code, Pv, Rn = head_py(row)
+        # what the case kinds promise, from the integers
+        if kind.startswith("false_positive"):
+            assert code == 4 and Pv % P != 0, kind
+        if kind.startswith(("equal", "opposite")):
+            assert code == 4 and Pv % P == 0 and (Rn % P == 0) == kind.startswith("equal"), kind
+        if kind.startswith("general"):
+            assert code in (0, 4) and Pv % P != 0, kind
+        t.add(kind, row, (code, balanced(Pv), balanced(Rn)))
+    return t
+
+
+def t_acc_rare():
+    """acc, P, Rn as the head leaves them, for every case that enters the call: a false positive comes back untouched with
+    `true`, equal operands doubled (behind the carry pass on X) and opposite ones as infinity with `false`"""
+    def check(row, want, out):
+        flag, pt = want
+        if out[0] != flag:
+            return "returned %d, expected %d" % (out[0], flag)
+        if flag:
+            return None if out[1:] == row[:52] else "a false positive changed the accumulator"
+        return check_xyzz(out[1:], pt)
+    t = Table("xyzz30_acc_rare", "acc_rare", 53, check)
+    for kind, row, a, b in acc_cases():
+        code, Pv, Rn = head_py(row)
+        if code != 4:
+            continue
+        if Pv % P:
+            want = (1, None)
+        else:
+            want = (0, T.g1_add(a, a) if Rn % P == 0 else None)
+        t.add(kind, row[:52] + balanced(Pv) + balanced(Rn), want)
+    return t
+
+
+def t_acc_tail():
+    """acc, P, Rn as the head leaves them for two different points: the digits of the same formulas on integers"""
+    def check(row, want, out):
+        digits, pt = want
+        if out != digits:
+            j = next(i for i in range(52) if out[i] != digits[i])
+            return "%s digit %d is %d, the integers give %d" % ("X Y ZZ ZZZ".split()[j // 13], j % 13, out[j], digits[j])
+        return check_acc_inside(out, pt, True)
+    t = Table("xyzz30_acc_tail", "acc_tail", 52, check)
+    for kind, row, a, b in acc_cases():
+        if not kind.startswith(TAIL_KINDS):
+            continue
+        _, Pv, Rn = head_py(row)
+        t.add(kind, row[:52] + balanced(Pv) + balanced(Rn), (tail_py(row[:52], Pv, Rn), T.g1_add(a, b)))
+    return t
+
+
+def acc_zero_multiples(table):
+    """For the equal / opposite cases of a table of (acc, point, neg) rows: which multiples of p their P = U2 - X1 and
+    Rn = Y1 - S2 are, {"P": {k: first case}, "R": {k: first case}} (R = -Rn), and how many false positives it holds"""
+    seen = {"P": {}, "R": {}, "false_positive": 0}
+    for i, row in enumerate(table.rows):
+        code, Pv, Rn = head_py(row)
+        if table.kinds[i].startswith("false_positive"):
+            assert code == 4 and Pv % P != 0
+            seen["false_positive"] += 1
+        if not table.kinds[i].startswith(("equal", "opposite")):
+            continue
+        assert Pv % P == 0
+        seen["P"].setdefault(Pv // P, i)
+        if Rn % P == 0:
+            seen["R"].setdefault(-Rn // P, i)
+    return seen
+
+
+# ---- chains: the unsettled accumulator feeds the next step, a constructed false positive at step 7 ---------------------------------
+FP_STEP = 7
+
+
+def _curve_point_for(acc, rng):
+    """a curve point b (of E(Fp): the formulas do not ask for the subgroup) whose addition to the accumulator with the digits
+    `acc` passes the pre-test without being equal or opposite: x_b = (t + X) / ZZ for t = 0 (mod 2^30)"""
+    X, ZZ = value(acc[:13]), value(acc[26:39])
+    while True:
+        t = rng.randrange(1, P >> B) << B
+        x = (t + X) * pow(ZZ, -1, P) % P
+        y = _sqrt(x * x * x + 4)
+        if y is not None:
+            return (x, y if rng.randrange(2) else P - y)
+
+
+def t_chain_acc_madd():
+    """chain_points with step 7 replaced: steps 0..3 are P, P, -2P, infinity; step 4 sets the accumulator from a point
+    (ZZ = ZZZ = fq_one()), step 5 adds infinity, step 6 a general point -- from there the accumulator is known digit for
+    digit (tail_py) -- and step 7 is a curve point built against those digits so that the pre-test fires on P != 0.
+    want: (the 16 partial sums, the settled digits after step 6)"""
+    def check(row, want, out):
+        partial, model = want
+        for s in range(16):
+            rec = out[s * 52:(s + 1) * 52]
+            msg = check_xyzz(rec, partial[s])
+            if msg:
+                return "step %d: %s" % (s, msg)
+            if s == FP_STEP - 1 and rec != model:
+                return "step %d: the accumulator in front of the false positive is not the one the integers give" % s
+    t = Table("chain xyzz30_acc_madd", "chain_acc_madd", 16 * 52, check)
+    rng = random.Random(1406)
+    for it in range(64):
+        extreme = bool(it & 1)
+        while True:
+            seq, _ = chain_points(rng)
+            if seq[4][0] != seq[6][0]:
+                break
+        negs = [rng.randrange(2) for _ in range(16)]
+        steps = [affine_digits(T.g1_neg(pt) if neg else pt, rng, extreme) + [neg] for pt, neg in zip(seq, negs)]
+        acc = steps[4][:13] + [(-v if negs[4] else v) for v in steps[4][13:26]] + ONE + ONE   # xyzz30_acc_set
+        code, Pv, Rn = head_py(acc + steps[6])
+        assert code == 0
+        acc = tail_py(acc, Pv, Rn)
+        while True:
+            b = _curve_point_for(acc, rng)
+            step = affine_digits(T.g1_neg(b) if negs[FP_STEP] else b, rng, extreme) + [negs[FP_STEP]]
+            code, Pv, _ = head_py(acc + step)
+            assert Pv % P != 0
+            if code == 4:
+                break
+        seq[FP_STEP], steps[FP_STEP] = b, step
+        partial, s = [], None
+        for pt in seq:
+            s = T.g1_add(s, pt)
+            partial.append(s)
+        t.add("chain %s" % ("extreme" if extreme else "random"), [v for st in steps for v in st],
+              (partial, norm_py(acc[:13]) + acc[13:]))
+    return t
+
+
+# ---- one step of the kernel's dispatch: whole waves of chosen lane kinds -------------------------------------------------------------
+# general; fresh (acc_inf); fresh with the point at infinity (both_inf); the point at infinity on a finite accumulator
+# (b_inf); equal; opposite; false positive
+LANE_KINDS = ("general", "acc_inf", "both_inf", "b_inf", "equal", "opposite", "false_positive")
+RARE_LANES = LANE_KINDS[1:]
+
+
+def dispatch_waves():
+    """[(name, [64 lane kinds])]: uniform waves, one lane of each rare kind among general lanes, every kind in one wave,
+    random mixtures"""
+    rng = random.Random(1407)
+    waves = [("uniform " + k, [k] * 64) for k in LANE_KINDS]
+    for k in RARE_LANES:
+        for pos in (0, 37, 63):
+            w = ["general"] * 64
+            w[pos] = k
+            waves.append(("lone %s at lane %d" % (k, pos), w))
+    waves.append(("every kind in turn", [LANE_KINDS[i % 7] for i in range(64)]))
+    w = [LANE_KINDS[i % 7] for i in range(64)]
+    rng.shuffle(w)
+    waves.append(("every kind shuffled", w))
+    for i in range(8):
+        waves.append(("random mixture %d" % i, [rng.choice(LANE_KINDS) for _ in range(64)]))
+    return waves
+
+
+def _host_dispatch(run, table):
+    return run("acc_madd", table.inputs(), 104)
+
+
+def t_acc_dispatch():
+    """every lane's result is the single-lane expectation of xyzz30_acc_madd, whatever the other lanes of its wave do"""
+    t = Table("dispatch of k_bucket_accumulate (ballot, second read, call through private memory, tail)", "acc_dispatch", 104,
+              _check_acc_madd, host=_host_dispatch)
+    rng = random.Random(1408)
+    for wi, (name, kinds) in enumerate(dispatch_waves()):
+        for lane, kind in enumerate(kinds):
+            neg, extreme, raw_x = rng.randrange(2), bool((wi + lane) & 1), bool(((wi + lane) >> 1) & 1)
+            row, a, b = acc_row(kind, rng, neg, extreme, raw_x)
+            t.add(kind, row, (T.g1_add(a, b), kind in TAIL_KINDS), "wave %d (%s), lane %d" % (wi, name, lane))
+    return t
+
+
 # ---- the tables ----------------------------------------------------------------------------------------------------------------------
 FAMILIES = {
     "fp_products": (t_fq_mul, t_fq_sqr, t_fq_mul_sub),
@@ -932,6 +1406,8 @@ FAMILIES = {
                     lambda: t_add_quad("add_quad_branch", "xyzz30_add_quad behind a branch on the quad", True)),
     "quad_dense": (lambda: t_add_quad("add_quad_dense", "xyzz30_add_quad_dense", False), t_add_quad_dense_loop),
     "quad_moves": (t_quad_broadcast, t_quad_select),
+    "accum_fused_products": (lambda: t_fq_mul_addc(-1), lambda: t_fq_mul_addc(1), t_fq_sqr_minus, t_fq_maybe_zero),
+    "accum_mixed_addition": (t_acc_head, t_acc_rare, t_acc_tail, t_acc_madd, t_chain_acc_madd, t_acc_dispatch),
 }
 FR_OPS = ("fr30_mul", "fr30_norm", "fr30_from_limbs", "fr30_to_limbs", "fr30_abs_to_limbs", "fr30_inv")
 _BUILT = {}

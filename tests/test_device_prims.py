@@ -105,6 +105,45 @@ def test_zero_tests_of_the_mixed_addition_reach_3p():
     assert set(seen["R"]) <= {-1, 0, 1} and {-1, 1} <= set(seen["R"]), sorted(seen["R"])
 
 
+def test_accumulation_tables_hold_what_they_promise():
+    """the tables of the accumulation kernel's addition: every kind x neg x representative x digit form of X, the zero tests at
+    every multiple of p the magnitude line allows (|P| < 3.3 p: k = -3 .. 3; |R| < 2 p: k = -1 .. 1), false positives
+    everywhere, and the wave compositions of the dispatch kernel"""
+    head, rare, tail, madd, chain, dispatch = C.family("accum_mixed_addition")
+    for kind in C.ACC_KINDS:
+        for neg in (0, 1):
+            for variant in ("extreme", "random"):
+                for form in ("raw", "balanced"):
+                    label = "%s neg=%d %s X %s" % (kind, neg, variant, form)
+                    assert sum(1 for k in madd.kinds if k == label) >= 12, label
+    assert head.rows == madd.rows
+    for t in (madd, dispatch):
+        seen = C.acc_zero_multiples(t)
+        assert set(seen["P"]) == set(range(-3, 4)), (t.name, sorted(seen["P"]))
+        assert set(seen["R"]) == {-1, 0, 1}, (t.name, sorted(seen["R"]))
+        assert seen["false_positive"] >= 96
+    assert sum(1 for k in madd.kinds if "every digit" in k) == 12  # X at the ends of the raw sum's range
+    assert {w[0] for w in head.wants} == {0, 1, 4, 6, 7}             # (a fresh lane's P is exactly zero: it carries 4 as well)
+    flags = [(k.split()[0], w[0], w[1] is None) for k, w in zip(rare.kinds, rare.wants)]
+    assert {f for f in flags} == {("false_positive", 1, True), ("equal", 0, False), ("opposite", 0, True)}
+    assert sum(f[0] == "false_positive" for f in flags) >= 96 and tail.n >= 192
+    assert chain.n == 64 and C.FP_STEP == 7
+    waves = C.dispatch_waves()
+    names = [n for n, _ in waves]
+    assert all(len(k) == 64 for _, k in waves) and dispatch.n == 64 * len(waves)
+    assert sum(n.startswith("uniform") for n in names) == 7 and sum(n.startswith("lone") for n in names) == 18
+    assert sum(n.startswith("every kind") for n in names) == 2 and sum(n.startswith("random mixture") for n in names) == 8
+    assert all(set(k) == set(C.LANE_KINDS) for n, k in waves if n.startswith("every kind"))
+    c_forms = {k.split(" c=")[1] for k in C.family("accum_fused_products")[0].kinds}
+    assert {"0", "raw sum of 1", "raw sum of 4", "+1 (2^31-4), digit 12 -1 2^24", "-1 (2^31-4), digit 12 +1 2^24", "-2^31"} <= c_forms
+    zero = C.family("accum_fused_products")[3]
+    for k in range(-3, 4):
+        for form in ("canonical", "re-split at digit 0", "raw difference", "norm(raw difference)"):
+            assert any(kd == "%dp %s" % (k, form) and w == 1 for kd, w in zip(zero.kinds, zero.wants)), (k, form)
+        assert sum(kd == "near miss of %dp" % k for kd in zero.kinds) == 16
+    assert sum(w == 0 for w in zero.wants) >= 512
+
+
 def test_mont_py_is_the_multiplier(host_run):
     """mont_py (used above to name the multiples) returns the very integer fq_mul returns"""
     t = C.family("fp_products")[0]

@@ -8,6 +8,20 @@ a quad.  The quad tables place chosen case kinds in chosen quads of a wave (unif
 idle ones, alternating and random mixtures), call xyzz30_add_quad from every quad and from behind a branch on the quad, and
 xyzz30_add_quad_dense straight and inside a loop whose trip count differs per quad.
 
+The accumulation kernel's arithmetic has two families of its own.  accum_fused_products: fq_mul_minus, fq_mul_plus and
+fq_sqr_minus must return exactly the product's integer (mont_py) minus or plus the third value, in strictly balanced digits,
+with that value anything up to a raw sum of four (every digit at +-(2^31 - 4)); here the +-1 factor of the device form (kept
+opaque in a scalar register, one v_mad_i64_i32) is what runs, which no g++ build compiles.  fq_maybe_zero is true on every
+digit form of k p, |k| <= 3, and -- by design -- on other values that share digit 0 with one.  accum_mixed_addition:
+xyzz30_acc_head, _rare and _tail against the integers of the same formulas digit for digit; xyzz30_acc_madd on the six case
+kinds plus constructed false positives of the pre-test (P = t + k p with t = 0 mod 2^30, never equal or opposite), half of
+the accumulators with X as the kernel holds it (a raw sum of two, digits up to 2^30), unsettled and settled; chains with a
+false positive built against the known digits of step 6; and k_acc_dispatch, a device-only kernel that copies the shape of
+k_bucket_accumulate around accum_rare_call (the wave-uniform ballot branch, the second read of a run's first point, the call
+through a struct in private memory that hands acc, P and Rn back, the tail last): 35 whole waves of chosen lane kinds --
+uniform, one rare lane among general ones, every kind at once, random mixtures -- in which every lane must return what the
+single-lane addition returns.
+
 A failure names the table, the case and its kind, for quad tables the wave composition and the quad, and says whether the
 g++ build of the same function satisfies the same check on that case: if it does, the source is right and the device code
 is not.

@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+import accum_false_positives as FP
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 B, N = 30, 13
@@ -290,3 +292,46 @@ def test_fused_mixed_addition_random_chains(lib, multiples):
         s = I52(*list(a_new))
         lib.f30f_add(s, a_old)  # equal group elements in different representations
         assert affine_of(s) == ec_add(wa, wa)
+
+
+# ---- the pre-test's false positives on a real SRS (accum_false_positives.py) ---------------------------------------------
+@pytest.fixture(scope="module")
+def rows_kg():
+    return FP.multiples_of_g(FP.N_ROWS)
+
+
+def test_table_digits_of_loaded_rows(lib, rows_kg):
+    """f30f_table_digits: x 2^390 (mod p) below 0.62 p in exactly balanced digits, from blst's words of x"""
+    pts = rows_kg[:64] + rows_kg[-64:]
+    dig = FP.table_digits(lib, FP.affine_rows(pts))
+    for pt, d in zip(pts, dig.tolist()):
+        for c, dd in zip(pt, (d[:13], d[13:])):
+            assert (value(dd) - c * RQ) % P == 0 and abs(value(dd)) < 0.62 * P and strict(dd)
+
+
+def test_false_positive_pairs_among_the_rows_kG(lib, rows_kg):
+    """On the rows k G, k = 1 .. 65537, the host model of "set a, then head b" finds unordered pairs of DIFFERENT points whose
+    P = U2 - X1 passes the one-word zero pre-test in both orders of arrival (measured: 11).  The GPU test of
+    k_bucket_accumulate (tests/test_accum_false_positive_gpu.py) puts exactly these pairs into buckets of two.  Fewer
+    than four is a failure, never a skip.  The fused addition gives (k_i + k_j) G for each, through the false-positive return
+    of xyzz30_acc_rare."""
+    assert rows_kg[1] == ec_add(rows_kg[0], rows_kg[0]) and rows_kg[-1] == ec_add(rows_kg[-2], rows_kg[0])
+    dig = FP.table_digits(lib, FP.affine_rows(rows_kg))
+    pairs = FP.false_positive_pairs(lib, dig)  # asserts code == kAccMaybeEqual and P != 0, both orders, every sign
+    print("false-positive pairs (k_i, k_j):", [(i + 1, j + 1) for i, j in pairs])
+    assert len(pairs) >= 4, pairs
+    for i, j in pairs:
+        assert rows_kg[i][0] != rows_kg[j][0]
+        want = ec_add(rows_kg[i], rows_kg[j])
+        if i + j + 1 < len(rows_kg):
+            assert want == rows_kg[i + j + 1]  # (k_i + k_j) G
+        for a, b in ((i, j), (j, i)):
+            acc = I52()
+            for r in (a, b):
+                lib.f30f_acc_madd(acc, I13(*dig[r, :13].tolist()), I13(*dig[r, 13:].tolist()), 0)
+            assert affine_of(acc) == want
+            check_bounds(acc)
+            acc = I52()
+            for r in (a, b):
+                lib.f30f_acc_madd(acc, I13(*dig[r, :13].tolist()), I13(*dig[r, 13:].tolist()), 1)
+            assert affine_of(acc) == (want[0], (-want[1]) % P)

@@ -647,6 +647,70 @@ int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_doma
 int kzg_g1_compress_batch(kzg_ctx* ctx, const uint64_t* in_p1, size_t n, uint8_t* out48);
 int kzg_fr_to_bytes_batch(kzg_ctx* ctx, const uint64_t* in_fr_mont, size_t n, uint8_t* out32_be, size_t* bad_index);
 
+/* ---- blob proofs and their Fiat-Shamir challenges --------------------------------------------------
+ * The proof that travels with a blob, and the challenge it is bound to: compute_kzg_proof, compute_blob_kzg_proof and
+ * verify_blob_kzg_proof_batch of the blob specs, for batches, on bytes.  Blobs, n, batch, stride and order as in the section
+ * above.
+ * The challenge of blob b with commitment C_b is
+ *     z_b = int_be(SHA256("FSBLOBVERIFY_V1_" | n as 16 bytes big-endian | the n x 32 blob bytes as sent | the 48 bytes of C_b)) mod r.
+ * The blob bytes enter the hash as they were sent, whatever `order` says (bytes between n and stride are not part of a blob),
+ * and the 48 commitment bytes enter it AS GIVEN: they are neither decoded nor checked here.
+ * kzg_sha256 is the hash on its own: a building block and test hook.  It runs on the x86 SHA extensions where CPUID reports
+ * them (kzg_sha256_has_shani returns 1) and in portable C++ otherwise.  kzg_sha256_pieces feeds the same bytes through the
+ * streaming interface `piece` bytes at a time on the path asked for -- KZG_SHA256_AUTO, KZG_SHA256_PORTABLE or
+ * KZG_SHA256_SHANI (KZG_ERR_INVALID_ARG on a CPU without the extensions).  kzg_blob_challenges_bytes writes the challenges, batch x 32 bytes
+ * big-endian, each below r.  Both are host-only and need no context: KZG_ERR_INVALID_ARG for a NULL pointer with something
+ * to do, n that is no power of two up to 2^KZG_NTT_MAX_LOG, or stride < n with batch > 1; batch = 0 does nothing.  Blobs are
+ * hashed on min(batch, 16, hardware threads) threads (the environment variable KZG_HASH_THREADS = 1 .. 15 lowers the 16: for
+ * measurements).
+ * kzg_blobs_open_at_bytes: y_b = P_b(z_b) and the proof of that opening, for points the caller names (zs_be, batch x 32
+ * bytes, each below r).  y is an OUTPUT: there is no claim, hence no KZG_ERR_REMAINDER and no KZG_ERR_CONSTANT_POLY.  A
+ * polynomial with n' <= 1 gets the infinity proof (0xc0 and zeros) and y = c_0.  z may lie inside the domain; y is then the
+ * blob's own value there.  For every blob the proof is kzg_g1_compress(kzg_open_evaluations(decoded values, z, y)) and y is
+ * what kzg_evaluate_evaluations_batch returns, byte for byte.
+ * kzg_blobs_to_blob_proofs_bytes: the same at the challenges, derived from commitments48 when given (hashed as given; no
+ * commitment is computed) and from the commitments computed here otherwise (those of kzg_blobs_to_commitments_bytes;
+ * returned when out_commitments48 is given, which also receives a copy of given ones).  y is not returned.
+ * kzg_verify_blob_proofs_batch_bytes: kzg_verify_blobs_batch_bytes with the challenges derived instead of given -- the same
+ * answers and the same error wordings as that call with those points.  The batch weights of the one pairing check stay random
+ * (the CSPRNG), not the specs' hashed ones: a verdict is the specs' verdict up to the 2^-255 soundness error of either choice.
+ * Route: the values are decoded and interpolated on the device as above and the coefficients stay resident; the quotients of
+ * all polynomials of a chunk come from ONE launch for n <= 4096 (blobproof_kernels.hip; for larger n the per-polynomial
+ * loop of kzg_open_batch runs), the proofs from the batched MSM over them in sub-batches of kzg_max_batch over the stream
+ * slots, compressed on the host.  The host hashes the blobs while the device commits.
+ * Errors, in this order: KZG_ERR_INVALID_ARG with kzg_last_error for the shape, an order that is neither constant, a NULL
+ * required pointer, stride < n with batch > 1, "polynomial b: the point z is not below r"; KZG_ERR_NO_SRS; KZG_ERR_INVALID_ARG
+ * from the device naming "polynomial b: value i is not below r" (i as sent); KZG_ERR_DEGREE_TOO_HIGH when n' > kzg_srs_len and
+ * commitments are computed, or n' - 1 > kzg_srs_len (kzg_last_error names the polynomial).  batch = 0 does nothing.  A failed
+ * call writes no output the caller may rely on.  Thread safety, chunking and multi-device contexts as in the section above.
+ * With kzg_set_timing, kzg_get_times of the slot the call leased (the lowest idle one) reports quotient_ms of its last chunk.
+ * Measured (MI355X, n = 4096, KZG_ORDER_BIT_REVERSED, kzg_set_max_batch(64), medians of three repetitions
+ * with their minimum and maximum): the quotients of 64 polynomials 0.061 ms (0.061-0.062) in the one launch against 2.31 ms
+ * (2.31-2.32) in the loop of kzg_open_batch_submit; kzg_blobs_to_blob_proofs_bytes with commitments computed, 64 blobs per call
+ * 4.98 ms (4.97-5.02) against 29.1 ms (29.1-30.4) for hashlib, kzg_fr_from_bytes_batch, kzg_ntt per blob, kzg_commit_batch,
+ * kzg_evaluate_evaluations_batch, kzg_open_batch and kzg_g1_compress per point chained by hand, 1 blob 0.87 ms (0.87-0.88) against
+ * 1.45 ms (1.44-1.45); kzg_verify_blob_proofs_batch_bytes 11.9 ms (11.7-12.1) against 15.1 ms (15.0-15.2) for hashlib and
+ * kzg_verify_blobs_batch_bytes at 64 blobs, and no gain at 1 blob: 10.9 ms (10.7-10.9) against 10.8 ms (10.7-10.8), one pairing
+ * check either way.  Hashing the 64 blobs (8.4 MB) takes 0.57 ms on the 16 threads and 3.49 ms on one with the SHA extensions,
+ * 3.13 ms and 19.9 ms in portable C++. */
+int kzg_sha256(const uint8_t* data, size_t len, uint8_t out[32]);
+#define KZG_SHA256_AUTO 0
+#define KZG_SHA256_PORTABLE 1
+#define KZG_SHA256_SHANI 2
+int kzg_sha256_pieces(const uint8_t* data, size_t len, size_t piece /* > 0 */, int path, uint8_t out[32]);
+int kzg_sha256_has_shani(void);
+int kzg_blob_challenges_bytes(const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, const uint8_t* commitments48,
+                              uint8_t* out_zs_be /* batch x 32, big-endian, < r */);
+int kzg_blobs_open_at_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                            const uint8_t* zs_be /* batch x 32 */, uint8_t* out_ys_be /* batch x 32 */,
+                            uint8_t* out_proofs48 /* batch x 48 */);
+int kzg_blobs_to_blob_proofs_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                   const uint8_t* commitments48 /* may be NULL: computed here */,
+                                   uint8_t* out_commitments48 /* may be NULL */, uint8_t* out_proofs48);
+int kzg_verify_blob_proofs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                       const uint8_t* commitments48, const uint8_t* proofs48, const void* setup_g2,
+                                       size_t g2_stride_bytes, int* valid);
+
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
  * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns

@@ -21,6 +21,7 @@ __all__ = [
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "domain_root",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
+    "sha256", "sha256_has_shani", "blob_challenges_bytes",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +66,8 @@ ABI_SYMBOLS = [
     "kzg_open_combined", "kzg_open_combined_submit", "kzg_wait_combined", "kzg_get_combine_ms", "kzg_combine_polys",
     "kzg_evaluate_batch_at", "kzg_combine_claims", "kzg_verify_combined",
     "kzg_open_sets", "kzg_open_sets_submit", "kzg_wait_sets", "kzg_quotient_sets", "kzg_verify_sets",
+    "kzg_sha256", "kzg_sha256_pieces", "kzg_sha256_has_shani", "kzg_blob_challenges_bytes", "kzg_blobs_open_at_bytes", "kzg_blobs_to_blob_proofs_bytes",
+    "kzg_verify_blob_proofs_batch_bytes",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -75,6 +78,7 @@ KZG_MAX_COMBINE = 256
 KZG_MAX_SETS = 8
 KZG_MAX_SET_POINTS = 16
 KZG_NTT_MAX_LOG = 22
+KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
 
@@ -215,6 +219,13 @@ def load_library():
         "kzg_wait_sets": (i, [vp, i, vp, vp]),
         "kzg_quotient_sets": (i, [vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_verify_sets": (i, [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
+        "kzg_sha256": (i, [vp, sz, vp]),
+        "kzg_sha256_pieces": (i, [vp, sz, sz, i, vp]),
+        "kzg_sha256_has_shani": (i, []),
+        "kzg_blob_challenges_bytes": (i, [vp, sz, sz, sz, vp, vp]),
+        "kzg_blobs_open_at_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp]),
+        "kzg_blobs_to_blob_proofs_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp]),
+        "kzg_verify_blob_proofs_batch_bytes": (i, [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp, sz, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1020,6 +1031,51 @@ class Engine:
                                                             _ptr(a) if a.size else None, batch, opt(out_v), opt(out_p)), self._h)
         return (out_v[:batch].tobytes() if cells_out else None, out_p[:batch].tobytes() if proofs else None)
 
+    # -- blob proofs and their Fiat-Shamir challenges --
+    def blobs_open_at_bytes(self, blobs_be, n, zs_be, order=KZG_ORDER_NATURAL, stride=None):
+        """kzg_blobs_open_at_bytes: blobs as blobs_to_commitments_bytes takes them and one point per blob (batch x 32
+        big-endian bytes) -> (ys_be, proofs48): the values P_b(z_b), batch x 32 bytes, and the proofs of those openings,
+        batch x 48 bytes"""
+        a, batch, stride = self._blobs(blobs_be, n, stride)
+        zl = self._wire(zs_be, 32)
+        if zl.shape[0] != batch:
+            raise ValueError("one point per blob")
+        ys = np.zeros((max(batch, 1), 32), dtype=np.uint8)
+        out = np.zeros((max(batch, 1), 48), dtype=np.uint8)
+        _check(self._lib.kzg_blobs_open_at_bytes(self._h, _ptr(a) if a.size else None, n, batch, stride, order,
+                                                 _ptr(zl) if zl.size else None, _ptr(ys), _ptr(out)), self._h)
+        return ys[:batch].tobytes(), out[:batch].tobytes()
+
+    def blobs_to_blob_proofs_bytes(self, blobs_be, n, commitments48=None, order=KZG_ORDER_NATURAL, stride=None):
+        """kzg_blobs_to_blob_proofs_bytes: the proof of every blob at its Fiat-Shamir challenge.  commitments48: batch x 48
+        bytes hashed as given, or None to have them computed.  Returns (commitments48, proofs48) as bytes"""
+        a, batch, stride = self._blobs(blobs_be, n, stride)
+        com = None
+        if commitments48 is not None:
+            com = self._wire(commitments48, 48)
+            if com.shape[0] != batch:
+                raise ValueError("one commitment per blob")
+        out_c = np.zeros((max(batch, 1), 48), dtype=np.uint8)
+        out_p = np.zeros((max(batch, 1), 48), dtype=np.uint8)
+        _check(self._lib.kzg_blobs_to_blob_proofs_bytes(self._h, _ptr(a) if a.size else None, n, batch, stride, order,
+                                                        _ptr(com) if com is not None and com.size else None, _ptr(out_c),
+                                                        _ptr(out_p)), self._h)
+        return out_c[:batch].tobytes(), out_p[:batch].tobytes()
+
+    def verify_blob_proofs_batch_bytes(self, blobs_be, n, commitments48, proofs48, setup_g2, order=KZG_ORDER_NATURAL, stride=None):
+        """kzg_verify_blob_proofs_batch_bytes: verify_blobs_batch_bytes at the challenges derived from each blob and its
+        commitment; returns the verdict"""
+        a, batch, stride = self._blobs(blobs_be, n, stride)
+        com, prf = self._wire(commitments48, 48), self._wire(proofs48, 48)
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        if com.shape[0] != batch or prf.shape[0] != batch:
+            raise ValueError("one commitment and one proof per blob")
+        ok = C.c_int(0)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        _check(self._lib.kzg_verify_blob_proofs_batch_bytes(self._h, opt(a), n, batch, stride, order, opt(com), opt(prf), _ptr(g2),
+                                                            288, C.byref(ok)), self._h)
+        return bool(ok.value)
+
     def fk20_prepare(self, n, log_cell):
         """builds the SRS-side FK20 transforms for polynomials of n coefficients and cells of 2^log_cell points now"""
         _check(self._lib.kzg_fk20_prepare(self._h, n, log_cell), self._h)
@@ -1250,6 +1306,40 @@ def verify_srs_update(before, after, tau_g2):
     ok = C.c_int(0)
     _check(load_library().kzg_srs_verify_update(_ptr(before.p1), _ptr(after.p1), _ptr(q), C.byref(ok)))
     return bool(ok.value)
+
+
+def sha256(data, piece=None, path=KZG_SHA256_AUTO):
+    """kzg_sha256: the library's SHA-256 of `data` (bytes).  piece / path: feed the streaming interface that many bytes at a
+    time on the path asked for (kzg_sha256_pieces; KZG_SHA256_SHANI raises KzgError on a CPU without the extensions)"""
+    lib = load_library()
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    src = _ptr(a) if a.size else None
+    if piece is None and path == KZG_SHA256_AUTO:
+        _check(lib.kzg_sha256(src, a.size, _ptr(out)))
+    else:
+        _check(lib.kzg_sha256_pieces(src, a.size, piece or max(a.size, 1), path, _ptr(out)))
+    return out.tobytes()
+
+
+def sha256_has_shani():
+    """whether the library's SHA-256 runs on the CPU's SHA extensions"""
+    return bool(load_library().kzg_sha256_has_shani())
+
+
+def blob_challenges_bytes(blobs_be, n, commitments48, stride=None):
+    """kzg_blob_challenges_bytes: the Fiat-Shamir challenge of every blob (batch x stride x 32 bytes, the first n values of a
+    stride being the blob) with its commitment (batch x 48 bytes, hashed as given) -> batch x 32 big-endian bytes, each < r"""
+    lib = load_library()
+    a = np.frombuffer(bytes(blobs_be), dtype=np.uint8) if not isinstance(blobs_be, np.ndarray) else np.ascontiguousarray(blobs_be, dtype=np.uint8).reshape(-1)
+    com = np.frombuffer(bytes(commitments48), dtype=np.uint8)
+    stride = n if stride is None else stride
+    if not (n and stride >= n and a.size % (32 * stride) == 0 and com.size % 48 == 0 and com.size // 48 == a.size // (32 * stride)):
+        raise ValueError("whole blobs of n values, `stride` values apart, and one commitment per blob")
+    batch = com.size // 48
+    out = np.zeros((max(batch, 1), 32), dtype=np.uint8)
+    _check(lib.kzg_blob_challenges_bytes(_ptr(a) if a.size else None, n, batch, stride, _ptr(com) if com.size else None, _ptr(out)))
+    return out[:batch].tobytes()
 
 
 def verify_proof(commitment, proof, z, y, s_g2):

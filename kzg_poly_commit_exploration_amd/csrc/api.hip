@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -32,6 +33,7 @@
 #include "host_fr.hpp"
 #include "fr30_host.hpp"
 #include "host_pairing.hpp"
+#include "host_sha256.hpp"
 #include "wire30.hip.h"
 
 using namespace kzg;
@@ -5056,6 +5058,308 @@ int kzg_recover_cells_and_proofs_bytes(kzg_ctx* ctx, size_t n, unsigned log_doma
         if (rc) return rc;
     }
     return KZG_OK;
+}
+
+// ---- blob proofs and their Fiat-Shamir challenges (blobproof_kernels.hip, host_sha256.hpp) ----------------
+namespace {
+// the specs' compute_challenge in two parts: the prefix (domain, degree, the blob bytes as sent), which needs no commitment ...
+void challenge_prefix(hf::Sha256& s, const uint8_t* blob_be, size_t n) {
+    uint8_t head[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_'};
+    for (int i = 0; i < 8; i++) head[24 + i] = (uint8_t)((uint64_t)n >> (8 * (7 - i)));  // n as 16 bytes big-endian
+    hf::sha256_init(s);
+    hf::sha256_update(s, head, 32);
+    hf::sha256_update(s, blob_be, n * 32);
+}
+// ... and the end: the 48 commitment bytes as given, the digest as a big-endian integer, reduced below r (2^256 < 3 r: at most
+// two subtractions; about 55 % of digests take one and 9 % two)
+void challenge_finish(hf::Sha256 s /* a copy: the prefix stays */, const uint8_t* commitment48, uint8_t out_be[32]) {
+    static const uint8_t r_be[32] = {0x73, 0xed, 0xa7, 0x53, 0x29, 0x9d, 0x7d, 0x48, 0x33, 0x39, 0xd8, 0x08, 0x09, 0xa1, 0xd8, 0x05,
+                                     0x53, 0xbd, 0xa4, 0x02, 0xff, 0xfe, 0x5b, 0xfe, 0xff, 0xff, 0xff, 0xff, 0x00, 0x00, 0x00, 0x01};
+    hf::sha256_update(s, commitment48, 48);
+    hf::sha256_final(s, out_be);
+    for (int round = 0; round < 2 && std::memcmp(out_be, r_be, 32) >= 0; round++) {
+        int borrow = 0;
+        for (int i = 31; i >= 0; i--) {
+            const int d = (int)out_be[i] - (int)r_be[i] - borrow;
+            out_be[i] = (uint8_t)(d & 0xff);
+            borrow = d < 0;
+        }
+    }
+}
+// work(b) for every b < count on min(count, 16, hardware threads) threads (KZG_HASH_THREADS lowers the 16: measurements), the
+// shares interleaved; the caller's thread takes one of them
+void hash_pool(size_t count, const std::function<void(size_t)>& work) {
+    size_t cap = 16;
+    if (const char* v = std::getenv("KZG_HASH_THREADS")) {
+        const long k = std::atol(v);
+        if (k >= 1 && k < 16) cap = (size_t)k;
+    }
+    const size_t hw = std::thread::hardware_concurrency();
+    size_t nthreads = count < cap ? count : cap;
+    if (hw && nthreads > hw) nthreads = hw;
+    if (nthreads < 1) nthreads = 1;
+    auto share = [&](size_t t) {
+        for (size_t b = t; b < count; b += nthreads) work(b);
+    };
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < nthreads; t++) pool.emplace_back(share, t);
+    share(0);
+    for (auto& th : pool) th.join();
+}
+}  // namespace
+
+int kzg_sha256(const uint8_t* data, size_t len, uint8_t out[32]) {
+    if (!out || (!data && len)) return KZG_ERR_INVALID_ARG;
+    hf::Sha256 s;
+    hf::sha256_init(s);
+    hf::sha256_update(s, data, len);
+    hf::sha256_final(s, out);
+    return KZG_OK;
+}
+
+int kzg_sha256_pieces(const uint8_t* data, size_t len, size_t piece, int path, uint8_t out[32]) {
+    if (!out || (!data && len) || !piece || path < hf::kSha256Auto || path > hf::kSha256ShaNi) return KZG_ERR_INVALID_ARG;
+    hf::Sha256 s;
+    if (!hf::sha256_init(s, path)) return KZG_ERR_INVALID_ARG;  // the SHA extensions on a CPU without them
+    for (size_t at = 0; at < len; at += piece) hf::sha256_update(s, data + at, len - at < piece ? len - at : piece);
+    hf::sha256_final(s, out);
+    return KZG_OK;
+}
+
+int kzg_sha256_has_shani(void) { return hf::sha256_has_shani() ? 1 : 0; }
+
+int kzg_blob_challenges_bytes(const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, const uint8_t* commitments48,
+                              uint8_t* out_zs_be) {
+    uint32_t lg = 0;
+    if (!ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (batch && (!blobs_be || !commitments48 || !out_zs_be)) return KZG_ERR_INVALID_ARG;
+    if (batch > 1 && stride < n) return KZG_ERR_INVALID_ARG;
+    hash_pool(batch, [&](size_t b) {
+        hf::Sha256 s;
+        challenge_prefix(s, blobs_be + 32 * b * stride, n);
+        challenge_finish(s, commitments48 + 48 * b, out_zs_be + 32 * b);
+    });
+    return KZG_OK;
+}
+
+// zs_be: the points (kzg_blobs_open_at_bytes); null: the challenges are derived, from commitments48 when given, else from the
+// commitments computed here (kzg_blobs_to_blob_proofs_bytes).  Any of the three outputs but the proofs may be null.
+static int blob_openings_device(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, uint32_t lg, size_t batch, size_t stride,
+                                bool bit_reversed, const uint64_t* zs_mont, const uint8_t* commitments48, uint8_t* out_commitments48,
+                                uint8_t* out_ys_be, uint8_t* out_proofs48) {
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot0 = reserve_slot(ctx, lk, true);
+    if (slot0 < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot0};
+    Slot& s0 = ctx->slots[slot0];
+    const hipStream_t st = s0.stream;
+    const bool derive = zs_mont == nullptr, commit = derive && !commitments48;
+    const bool single = n <= kBlobProofMaxN;  // the batched kernel; above: the loop of kzg_open_batch
+    const Fk20Plan no_plan;
+    size_t chunk = blob_chunk(ctx, n, nullptr, no_plan);
+    if (chunk > batch) chunk = batch;
+    const size_t nq = n - 1;
+    void *wire, *a, *b, *zbuf, *words, *flagbuf;
+    rc = ctx->blob_ws.get(ctx, kBlobWire, chunk * n * 32, &wire);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobA, chunk * n * 32, &a);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobB, chunk * n * 32, &b);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobP, chunk * kBlobProofZWords * 4, &zbuf);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobWords, (kBlobErrWords + kFk20MaxBatch) * 4, &words);
+    if (rc == KZG_OK) rc = ctx->blob_ws.get(ctx, kBlobProofs, chunk * 32 * 4, &flagbuf);
+    if (rc == KZG_OK && !single) rc = ensure_poly(ctx, s0, n);  // the two-launch scan's scratch
+    if (rc) return rc;
+    uint32_t *A = (uint32_t*)a, *B = (uint32_t*)b, *err = (uint32_t*)words, *trim = err + kBlobErrWords;
+    uint32_t *d_z = (uint32_t*)zbuf, *d_flags = (uint32_t*)flagbuf;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg)));
+    std::vector<uint32_t> hw(kBlobErrWords + chunk), hz(chunk * kBlobProofZWords), hflags(chunk * 32);
+    std::vector<uint8_t> com(48 * chunk), zbe(32);
+    std::vector<hf::Sha256> mid(derive ? chunk : 0);
+    std::vector<uint64_t> zs_own(derive ? 4 * chunk : 0);
+    BlobCommits commits{ctx, lk}, proofs{ctx, lk};
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t bc = batch - b0 < chunk ? batch - b0 : chunk;
+        const uint8_t* src = blobs_be + 32 * b0 * stride;
+        // the front end of blobs_device: the bytes as they are, decoded, interpolated; 1 / n and every n' in one pass
+        HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kBlobErrWords * 4, st));
+        HIP_TRY(ctx, hipMemsetAsync(trim, 0, bc * 4, st));
+        {
+            lk.unlock();
+            const hipError_t e = stride > n && bc > 1
+                                     ? hipMemcpy2DAsync(wire, n * 32, src, stride * 32, n * 32, bc, hipMemcpyHostToDevice, st)
+                                     : hipMemcpyAsync(wire, src, bc * n * 32, hipMemcpyHostToDevice, st);
+            lk.lock();
+            if (e != hipSuccess) {
+                ctx->last_error = std::string("hipMemcpyAsync (blobs): ") + hipGetErrorString(e);
+                return KZG_ERR_HIP;
+            }
+        }
+        launch_wire_fr(st, wire, (uint32_t)(bc * n), lg, bit_reversed, A, err);
+        uint32_t* coef = const_cast<uint32_t*>(launch_fr_dft(st, A, A, B, lg, bc, tw + 2 * kNttTableLen));
+        uint32_t* quot = coef == A ? B : A;  // the transform's other buffer: bc x (n - 1) quotient coefficients fit
+        launch_poly_trim(st, coef, (uint32_t)n, n, (uint32_t)bc, &inv_n, trim);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(hw.data(), words, (kBlobErrWords + bc) * 4, hipMemcpyDeviceToHost, st));
+        if (derive && !commit) {  // the host hashes while the device decodes and interpolates
+            lk.unlock();
+            hash_pool(bc, [&](size_t i) { challenge_prefix(mid[i], src + 32 * i * stride, n); });
+            lk.lock();
+        }
+        rc = sync_unlocked(ctx, lk, st, "blob proofs");
+        if (rc) return rc;
+        if (hw[0] != 0xffffffffu) {
+            ctx->last_error = "blob proofs: polynomial " + std::to_string(b0 + hw[0] / n) + ": value " + std::to_string(hw[0] % n) +
+                              " is not below r";
+            return KZG_ERR_INVALID_ARG;
+        }
+        size_t n_max = 0;
+        for (size_t i = 0; i < bc; i++) {
+            const size_t ne = hw[kBlobErrWords + i];
+            if (commit && ne > ctx->n) {
+                ctx->last_error = "blob proofs: polynomial " + std::to_string(b0 + i) + ": n' = " + std::to_string(ne) +
+                                  " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+                return KZG_ERR_DEGREE_TOO_HIGH;
+            }
+            if (ne > 1 && ne - 1 > ctx->n) {
+                ctx->last_error = "blob proofs: polynomial " + std::to_string(b0 + i) + ": n' - 1 = " + std::to_string(ne - 1) +
+                                  " exceeds the SRS (" + std::to_string(ctx->n) + " points)";
+                return KZG_ERR_DEGREE_TOO_HIGH;
+            }
+            if (ne > n_max) n_max = ne;
+        }
+        // the points of this chunk, in the multiplier's form for the kernel
+        const uint64_t* zc = zs_mont ? zs_mont + 4 * b0 : zs_own.data();
+        if (derive) {
+            const uint8_t* cb = commitments48 ? commitments48 + 48 * b0 : com.data();
+            if (commit) {  // from the resident coefficients, as kzg_blobs_to_commitments_bytes; the host hashes beside the MSMs
+                rc = commits.submit(coef, n, bc, n_max);
+                lk.unlock();
+                hash_pool(bc, [&](size_t i) { challenge_prefix(mid[i], src + 32 * i * stride, n); });
+                lk.lock();
+                rc = commits.finish(rc, bc, com.data());
+                if (rc) return rc;
+            }
+            for (size_t i = 0; i < bc; i++) {
+                challenge_finish(mid[i], cb + 48 * i, zbe.data());
+                (void)wire_fr_host(zbe.data(), zs_own.data() + 4 * i);  // (reduced: below r)
+            }
+            if (out_commitments48) std::memcpy(out_commitments48 + 48 * b0, cb, 48 * bc);
+        }
+        std::fill(hz.begin(), hz.end(), 0u);
+        for (size_t i = 0; i < bc; i++) {
+            hf::Fr z;
+            std::memcpy(z.l, zc + 4 * i, 32);
+            const Fr30 d = fr30_arg_from_mont256(z);
+            std::memcpy(hz.data() + i * kBlobProofZWords, d.d, sizeof d.d);
+        }
+        // the quotients: one launch for blob sizes, the per-polynomial loop beyond
+        s0.timing = ctx->timing;
+        std::memset(&s0.times, 0, sizeof s0.times);
+        if (single) {
+            rc = copy_unlocked(ctx, lk, st, d_z, hz.data(), bc * kBlobProofZWords * 4, hipMemcpyHostToDevice, "hipMemcpyAsync (blob proofs)");
+            if (rc) return rc;
+            if (s0.timing) HIP_TRY(ctx, hipEventRecord(s0.ev[6], st));
+            launch_blobproof_quotients(st, coef, (uint32_t)n, n, (uint32_t)bc, d_z, nq ? quot : nullptr, d_flags);
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, bc * 32 * 4, st));
+            if (s0.timing) HIP_TRY(ctx, hipEventRecord(s0.ev[6], st));
+            for (size_t p = 0; p < bc; p++) {
+                uint32_t zw[8];
+                std::memcpy(zw, zc + 4 * p, 32);
+                uint32_t* sm = d_flags + p * 32;
+                PolyScratch sc{s0.chunk.dev(), s0.block.dev(), sm, sm + 8};  // scratch re-used in stream order
+                launch_quotient(st, coef + p * n * 8, (uint32_t)n, zw, quot + p * nq * 8, sc);
+            }
+        }
+        if (s0.timing) HIP_TRY(ctx, hipEventRecord(s0.ev[7], st));
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(hflags.data(), d_flags, bc * 32 * 4, hipMemcpyDeviceToHost, st));
+        rc = sync_unlocked(ctx, lk, st, "blob proofs");
+        if (rc) return rc;
+        if (s0.timing) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, s0.ev[6], s0.ev[7]);
+            s0.times.quotient_ms = ms;
+        }
+        // the proofs: the batched MSM over the quotients' first n_max - 1 coefficients (the rest are exact zeros)
+        rc = proofs.submit(quot, nq, bc, n_max > 1 ? n_max - 1 : 0);
+        rc = proofs.finish(rc, bc, out_proofs48 + 48 * b0);
+        if (rc) return rc;
+        for (size_t i = 0; i < bc; i++) {
+            const uint32_t* hs = hflags.data() + 32 * i;
+            if (!(hs[0] & 1u)) blob_infinity(out_proofs48 + 48 * (b0 + i), 1);  // n' <= 1: the quotient is zero
+            if (out_ys_be) {
+                uint64_t y[4];
+                std::memcpy(y, hs + 8, 32);
+                wire_fr_to_be(y, out_ys_be + 32 * (b0 + i));
+            }
+        }
+    }
+    return KZG_OK;
+}
+
+static int blob_openings_entry(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                               const uint8_t* zs_be, bool derive, const uint8_t* commitments48, uint8_t* out_commitments48,
+                               uint8_t* out_ys_be, uint8_t* out_proofs48) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "blob proofs: " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    uint32_t lg = 0;
+    if (!ntt_log(n, &lg)) return invalid("n is not a power of two up to 2^KZG_NTT_MAX_LOG");
+    if (batch > kMaxCoefficients / n) return invalid("batch x n does not fit 32 bits");
+    if (order != KZG_ORDER_NATURAL && order != KZG_ORDER_BIT_REVERSED)
+        return invalid("order is neither KZG_ORDER_NATURAL nor KZG_ORDER_BIT_REVERSED");
+    if (batch && (!blobs_be || !out_proofs48 || (!derive && (!zs_be || !out_ys_be)))) return invalid("a required pointer is NULL");
+    if (batch > 1 && stride < n) return invalid("stride is below n");
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = cells_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, blob_openings_entry(kid, blobs_be, n, batch, stride, order, zs_be, derive, commitments48,
+                                                             out_commitments48, out_ys_be, out_proofs48))
+                   : rc;
+    }
+    if (!batch) return KZG_OK;
+    std::vector<uint64_t> zs;
+    if (!derive) {
+        zs.resize(4 * batch);
+        for (size_t b = 0; b < batch; b++)
+            if (!wire_fr_host(zs_be + 32 * b, zs.data() + 4 * b))
+                return invalid("polynomial " + std::to_string(b) + ": the point z is not below r");
+    }
+    return blob_openings_device(ctx, blobs_be, n, lg, batch, batch > 1 ? stride : n, order == KZG_ORDER_BIT_REVERSED,
+                                derive ? nullptr : zs.data(), commitments48, out_commitments48, out_ys_be, out_proofs48);
+}
+
+int kzg_blobs_open_at_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                            const uint8_t* zs_be, uint8_t* out_ys_be, uint8_t* out_proofs48) {
+    return blob_openings_entry(ctx, blobs_be, n, batch, stride, order, zs_be, false, nullptr, nullptr, out_ys_be, out_proofs48);
+}
+
+int kzg_blobs_to_blob_proofs_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                   const uint8_t* commitments48, uint8_t* out_commitments48, uint8_t* out_proofs48) {
+    return blob_openings_entry(ctx, blobs_be, n, batch, stride, order, nullptr, true, commitments48, out_commitments48, nullptr,
+                               out_proofs48);
+}
+
+int kzg_verify_blob_proofs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, size_t n, size_t batch, size_t stride, unsigned order,
+                                       const uint8_t* commitments48, const uint8_t* proofs48, const void* setup_g2,
+                                       size_t g2_stride_bytes, int* valid) {
+    // the challenges first, where the inputs can be hashed at all; what cannot is refused by the sibling below, in its own words
+    // (the points it is handed are then never read)
+    uint32_t lg = 0;
+    std::vector<uint8_t> zs(32 * (batch && batch <= KZG_VERIFY_MAX_OPENINGS ? batch : 1));
+    if (ctx && batch && batch <= KZG_VERIFY_MAX_OPENINGS && ntt_log(n, &lg) && blobs_be && commitments48 && !(batch > 1 && stride < n))
+        (void)kzg_blob_challenges_bytes(blobs_be, n, batch, batch > 1 ? stride : n, commitments48, zs.data());
+    const BlobWire w = {blobs_be, order, commitments48, zs.data(), proofs48, nullptr};
+    return verify_evaluations_impl(ctx, nullptr, n, batch, stride, nullptr, nullptr, nullptr, setup_g2, g2_stride_bytes, nullptr,
+                                   valid, &w);
 }
 
 // the encoders on their own: building blocks and test hooks; they need no SRS

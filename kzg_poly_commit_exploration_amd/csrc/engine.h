@@ -427,4 +427,15 @@ bool sets_prepare_device();
 void launch_quotient_sets(hipStream_t s, const uint32_t* d_g, uint32_t n, const void* d_roots, uint32_t k, uint32_t* d_q,
                           uint32_t* d_block, uint32_t* d_vals);
 
+// ---- blobproof_kernels.hip ---------------------------------------
+// The quotients of `batch` polynomials of n <= kBlobProofMaxN coefficients (polynomial b at d_coeffs + 8 b stride words), each at
+// its own point, in one launch: q_b (n - 1 canonical values) to d_q + 8 b (n - 1) words (d_q may be null: values only), and
+// polynomial b's 32 flag words to d_flags + 32 b, written in full -- [0] = any non-zero coefficient with index >= 1, [8..15] =
+// P_b(z_b), [16..23] = c_0, zero elsewhere.  d_z: batch x kBlobProofZWords words, the first nine the digits of z_b * 2^270
+// (fr30_arg_from_mont256).  Returns false (nothing enqueued) for n = 0 or n above the limit.
+constexpr uint32_t kBlobProofMaxN = 4096;
+constexpr uint32_t kBlobProofZWords = 12;
+bool launch_blobproof_quotients(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, uint64_t stride, uint32_t batch,
+                                const uint32_t* d_z, uint32_t* d_q, uint32_t* d_flags);
+
 }  // namespace kzg

@@ -72,6 +72,11 @@ def test_large_round_trip_and_points(eng, oracle, k):
 
 
 def test_magnitude_worst_case_2_22(eng):
+    # What this reaches: the largest size, and every loaded value at the top of the canonical range (r - 1 as an integer),
+    # so the product-free first stage of each pass holds 2 r.  What it does not reach: the bound of the later stages.  r - 1
+    # is -1, and fr30_mul returns the centred residue, so from the second stage on every product is a small multiple of -1
+    # (at most n in magnitude) and the sums stay at 2 r.  The inputs that add r / 2 per stage (6.5 r after eleven stages) are the chains of
+    # tests/test_fr_extremes_gpu.py.
     n = 1 << 22
     a = K.scalars_to_limbs([R - 1]).repeat(n, axis=0)
     e = eng.ntt_limbs(a)  # sum_j (r - 1) w^(ij) = -n at i = 0, 0 elsewhere

@@ -713,8 +713,9 @@ int kzg_verify_blob_proofs_batch_bytes(kzg_ctx* ctx, const uint8_t* blobs_be, si
 
 /* ---- device-resident / pipelined variants -------------------------------------------------
  * d_coeffs is a DEVICE pointer (n x blst_fr, Montgomery) on the context's GPU, e.g. a tensor
- * produced upstream.  submit enqueues on one of kzg_num_slots() internal HIP streams and returns
- * at once; wait blocks on that slot, finishes the tail on the host and writes the result.  Several
+ * produced upstream.  submit enqueues the job of one of kzg_num_slots() slots on the context's three
+ * internal HIP streams (one per phase of a job, shared by the slots) and returns at once; wait blocks
+ * until that slot's job has ended, finishes the tail on the host and writes the result.  Several
  * slots in flight keep the GPU busy across the latency-bound end of each MSM. */
 int kzg_num_slots(const kzg_ctx* ctx);
 int kzg_commit_submit(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n);

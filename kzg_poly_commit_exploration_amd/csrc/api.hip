@@ -1,8 +1,8 @@
 // api.hip -- the C-ABI of libkzg_mi355x.so (declared in include/kzg_mi355x.h): context, SRS
-// residency, stream slots, the host-side orchestration of one commitment / opening, and the serial
+// residency, job slots and the three streams, the host-side orchestration of one commitment / opening, and the serial
 // tail (a few dozen point additions + one inversion) that finishes each MSM on the host.
 //
-// One commitment on a slot's stream:
+// One commitment, over the context's three streams (front: up to the sort; accumulation; tail: from the finalisation on):
 //   digits+histogram -> scan -> scatter -> bucket accumulation -> bucket finalisation
 //   -> row / column tree sums of the bucket matrix, split once more (small jobs: one launch behind the sort)
 //   -> D2H of <= 128 XYZZ partials -> host: four short weighted sums, normalise, blst_p1 out.
@@ -45,7 +45,8 @@ namespace {
 // with 32 bits, so the C-ABI refuses them too instead of truncating the count.
 constexpr size_t kMaxCoefficients = 0xFFFFFFFFull;
 
-// Stream slots per context (+ the shared accumulation stream: 6 of the 8 hardware queues the library asks for).  The
+// Job slots per context: a slot is a job's workspaces, events, flag words and bookkeeping.  The streams belong to the
+// context, one per phase (kzg_ctx below), so the number of slots does not decide the number of hardware queues in use.  The
 // light kernels of a job -- sort in front of its accumulation, finalisation and reduction trees behind it -- only get
 // the chip in the tail of ANOTHER job's accumulation and crawl while one is running (round-3 timeline: a 54 us sort
 // kernel takes 260, the trees 1 ms).  With three jobs in flight the next job's sort regularly finished 100-240 us after
@@ -163,22 +164,24 @@ struct Workspace {
     }
 };
 
-// A slot's stream and events.  They are the base of Slot, so they are destroyed AFTER the slot's buffers (members go first):
-// kzg_ctx_destroy waits for the stream, `delete` frees the buffers, then the events and the stream go.
+// A slot's events and its view of the context's streams.  They are the base of Slot, so the events are destroyed AFTER the
+// slot's buffers (members go first): kzg_ctx_destroy waits for the streams, `delete` frees the buffers, then the events go.
 struct SlotQueue {
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;  // the context's front stream (every slot holds the same one; the context destroys it)
+    hipStream_t end = nullptr;     // where the job in flight ended: the front stream, or the tail stream after a hand-over
+                                   // (set by enqueue_msm); `done` and the job's last timing event are recorded there
     hipEvent_t ev[8] = {};
     hipEvent_t done = nullptr;
     hipEvent_t sorted_ev = nullptr, accum_ev = nullptr;  // hand-offs to / from the shared accumulation stream
     hipEvent_t cmb_ev[2] = {};                           // timed combined openings: around the (last) combination pass
     hipEvent_t cells_ev = nullptr;                       // kzg_cells_and_proofs: P is in cpoly
+    hipEvent_t upload_ev = nullptr;                      // host-pointer calls: the coefficients are in the slot (upload stream)
     SlotQueue() = default;
     SlotQueue(const SlotQueue&) = delete;
     SlotQueue& operator=(const SlotQueue&) = delete;
     ~SlotQueue() {
-        for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev[4], ev[5], ev[6], ev[7], cmb_ev[0], cmb_ev[1], cells_ev, done, sorted_ev, accum_ev})
+        for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev[4], ev[5], ev[6], ev[7], cmb_ev[0], cmb_ev[1], cells_ev, upload_ev, done, sorted_ev, accum_ev})
             if (e) hipEventDestroy(e);
-        if (stream) hipStreamDestroy(stream);
     }
 };
 
@@ -206,7 +209,7 @@ struct Slot : SlotQueue {
     PinnedBuf small{PinnedBuf::Mapped};   // [0..1] flags, [8..15] P(z), [16..23] c0, [24] tail flag, [26] references
     PinnedBuf bsmall{PinnedBuf::Mapped};  // batched openings: 32 words per polynomial, same layout as small[0..31]
     std::vector<uint32_t> open_ys;  // y of every polynomial of a batched opening (8 words each)
-    // multiproofs (kzg_open_points): the per-root multipliers are copied on the slot's stream (a slot holds one job at a
+    // multiproofs (kzg_open_points): the per-root multipliers are copied on the front stream (a slot holds one job at a
     // time, so nothing in flight reads them while they are rewritten); the k values P(z_i) land in mapped memory like the
     // flag words; pblock: k x nblocks aggregates
     PinnedBuf roots{PinnedBuf::Staged};
@@ -269,11 +272,26 @@ struct kzg_ctx {
     size_t arena_records = 0, final_records = 0;  // per polynomial of a batch
     uint32_t max_batch = 1;                        // polynomials per submit the workspaces are sized for
     Slot slots[kNumSlots];
-    // All bucket-accumulation kernels run on ONE stream, in submission order: each fills the chip on its
-    // own, so letting two of them overlap only makes both slower (and their timings meaningless), while
-    // the light sort / reduction kernels of the other slots run beside it on the slots' own streams.
-    hipStream_t heavy_stream = nullptr;
-    bool serialize_accum = true;   // KZG_SERIALIZE_ACCUM=0 lets accumulation kernels of different slots overlap
+    // Three streams, one per phase of a job, at any number of slots -- they fit the four hardware queues a process gets by
+    // default however the runtime assigns them, so neither results nor rate depend on the queue count:
+    //   front_stream (lowest priority): everything a job enqueues before its accumulation (quotient or combination passes,
+    //     the degree check, the sort), the one-launch small jobs in full, and every other feature's copies and kernels.
+    //     Every slot's `stream` member is this stream.
+    //   heavy_stream (highest priority): all bucket-accumulation kernels, in submission order: each fills the chip on its
+    //     own, so letting two of them overlap only makes both slower (and their timings meaningless), while the light
+    //     kernels of the other jobs run beside it.  Waits for the job's sorted_ev, records its accum_ev.
+    //   tail_stream (lowest priority): waits for accum_ev, then the finalisation and the tree sums; the job's `done`.
+    // THE INVARIANT: no operation that waits for an accumulation or for a tail is ever enqueued on the front stream (a job
+    // that found every other slot idle runs on it in full, hand-overs saved: nothing was there to wait).  So the next
+    // job's sort never stands behind a pending tail, whichever streams share a hardware queue.  A job is ordered behind the
+    // previous job of its slot by the host: a slot is reused only after it was collected (its `done` event waited for).
+    hipStream_t front_stream = nullptr, heavy_stream = nullptr, tail_stream = nullptr;
+    // The coefficients of the host-pointer commitments and openings (kzg_commit, kzg_open, kzg_open_points, the batches) go
+    // up on a stream of their own (default priority: a queue from another pool than the three above) and the front stream
+    // waits for the slot's upload_ev.  A copy from pageable memory returns when it is done, and on the front stream it is
+    // done only after every sort and quotient queued before it: with four caller threads the uploads stood behind each
+    // other's kernels (380 against the parent's 395 proofs/s).  Nothing but copies is ever enqueued on it.
+    hipStream_t upload_stream = nullptr;
     // LDS reserved per accumulation workgroup (KZG_ACCUM_LDS_KB overrides): 41 KB would cap the kernel at three workgroups
     // per CU; its register count (176 reserved, msm_accum.hip) caps it at two, which is what its grid is launched for.
     // Two workgroups leave 78 KB of LDS and 160 VGPRs per SIMD lane to the light kernels of the other slots (32 KB instead
@@ -328,7 +346,7 @@ struct TmpStream {
     ~TmpStream() { if (s) hipStreamDestroy(s); }
 };
 
-// Waits for the stream without ctx->mu, so that the context's other calls go on meanwhile (the caller's slot keeps an SRS
+// Waits for the (front) stream without ctx->mu, so that the context's other calls go on meanwhile (the caller's slot keeps an SRS
 // replacement out, its feature's mutex the other calls of its kind).  `what` starts the text an error leaves.
 int sync_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const char* what) {
     lk.unlock();
@@ -354,28 +372,54 @@ void free_slot_msm(Slot& s) {
     s.fin.reset();
 }
 
-// stream, events and the small flag buffers of a slot (what kzg_quotient / kzg_evaluate need without an SRS)
+// one of the context's streams: the highest or the lowest priority (KZG_STREAM_PRIORITIES=0: the default one for all)
+int create_stream(kzg_ctx* ctx, hipStream_t* out, bool high) {
+    int least = 0, greatest = 0;
+    HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const char* v = std::getenv("KZG_STREAM_PRIORITIES");
+    const bool prio = !(v && v[0] == '0');
+    HIP_TRY(ctx, hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio ? (high ? greatest : least) : 0));
+    return KZG_OK;
+}
+
+// the front stream, events and the small flag buffers of a slot (what kzg_quotient / kzg_evaluate need without an SRS)
 int ensure_slot_basics(kzg_ctx* ctx, Slot& s) {
     if (s.stream) return KZG_OK;
-    {
-        // slot streams run the light kernels (sort, finalise, reduction, quotient): lowest priority, so that
-        // when an accumulation ends the NEXT accumulation (high-priority stream) takes the chip first and the
-        // ~180-VGPR reduction kernels fill in behind it instead of holding half of every SIMD's registers
-        int least = 0, greatest = 0;
-        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const char* v = std::getenv("KZG_STREAM_PRIORITIES");
-        const bool prio = !(v && v[0] == '0');
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, prio ? least : 0));
+    // the front and tail streams run the light kernels (sort, quotient; finalise, reduction): lowest priority, so that
+    // when an accumulation ends the NEXT accumulation (high-priority stream) takes the chip first and the
+    // ~180-VGPR reduction kernels fill in behind it instead of holding half of every SIMD's registers
+    if (!ctx->front_stream) {
+        int rc = create_stream(ctx, &ctx->front_stream, false);
+        if (rc) return rc;
     }
-    for (auto& e : s.ev) HIP_TRY(ctx, hipEventCreate(&e));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (!ctx->upload_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
+    for (auto& e : s.ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    if (!s.upload_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&s.upload_ev, hipEventDisableTiming));
+    s.stream = s.end = ctx->front_stream;
+    if (!s.done) HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     return s.small.reserve(ctx, 64 * 4);
+}
+
+// The coefficients of a host-pointer job into the slot (dst: a part of s.stage that nothing in flight reads -- the slot's
+// last job was collected): the copy on the upload stream without ctx->mu, then the front stream waits for it.
+int upload_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, void* dst, const void* src, size_t bytes) {
+    if (!bytes) return KZG_OK;
+    int rc = copy_unlocked(ctx, lk, ctx->upload_stream, dst, src, bytes, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.upload_ev, ctx->upload_stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(s.stream, s.upload_ev, 0));
+    return KZG_OK;
 }
 
 // the four polynomial buffers grow together, to at least 1024 coefficients
 int ensure_poly(kzg_ctx* ctx, Slot& s, size_t n) {
     const size_t cap = n < 1024 ? 1024 : n;
     if (cap * 32 <= s.stage.cap) return KZG_OK;
+    // nothing may still read the old buffers: the slot's last job has ended (its owner collected it; a failed submit may
+    // have left a part of one in flight) and the upload and front streams, where every other user of these four runs, are empty
+    if (s.done) HIP_TRY(ctx, hipEventSynchronize(s.done));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     for (DevBuf* b : {&s.stage, &s.q, &s.chunk, &s.block}) b->reset();
     int rc = s.stage.reserve(ctx, cap * 32);
@@ -432,11 +476,12 @@ int setup_slots_impl(kzg_ctx* ctx) {
         }
     }
     if (!ctx->heavy_stream) {
-        int least = 0, greatest = 0;
-        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const char* v = std::getenv("KZG_STREAM_PRIORITIES");
-        const bool prio = !(v && v[0] == '0');
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->heavy_stream, hipStreamNonBlocking, prio ? greatest : 0));
+        int rc = create_stream(ctx, &ctx->heavy_stream, true);
+        if (rc) return rc;
+    }
+    if (!ctx->tail_stream) {
+        int rc = create_stream(ctx, &ctx->tail_stream, false);
+        if (rc) return rc;
     }
     const MsmConfig cfg = ctx->cfg;
     if (ctx->max_batch > sort_max_batch(cfg)) ctx->max_batch = sort_max_batch(cfg);
@@ -487,10 +532,10 @@ int build_tables(kzg_ctx* ctx, hipStream_t st, void* d_xyzz_tmp, void* d_prefix)
     return KZG_OK;
 }
 
+// nothing of any job is in flight after this: the streams in the order a job passes through them
 int drain_all(kzg_ctx* ctx) {
-    if (ctx->heavy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->heavy_stream));
-    for (auto& s : ctx->slots)
-        if (s.stream) HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    for (hipStream_t st : {ctx->upload_stream, ctx->front_stream, ctx->heavy_stream, ctx->tail_stream})
+        if (st) HIP_TRY(ctx, hipStreamSynchronize(st));
     return KZG_OK;
 }
 
@@ -523,12 +568,15 @@ int srs_prepare(kzg_ctx* ctx, size_t n) {
     return ctx->table.reserve(ctx, (size_t)cfg.W * n * kAffineBytes);
 }
 
-// enqueue `batch` MSMs of n scalars each (polynomial p at d_scalars + p * stride scalars) on slot s
+// enqueue `batch` MSMs of n scalars each (polynomial p at d_scalars + p * stride scalars) on slot s: the sort on the
+// front stream, the accumulation on the accumulation stream, the rest on the tail stream.  Leaves in s.end the stream the job
+// ended on: whatever the caller enqueues behind the MSM (its `done` event) goes THERE, never on the front stream.
 int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, size_t n, int ev_base,
                 uint32_t batch = 1, uint64_t stride = 0) {
     const MsmConfig cfg = ctx->cfg;
     const uint32_t nbt = cfg.nb * batch;  // polynomial-major bucket ids
     hipStream_t st = s.stream;
+    s.end = st;
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base], st));
     const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, (uint32_t)ctx->n, cfg, s.cnt.dev(),
                        s.block_sums.dev(), s.pairs.dev<uint64_t>(), s.offs.dev(), s.sorted.dev(), (uint32_t*)s.heavy_ws.p);
@@ -559,15 +607,15 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
     if (!header_zeroed) HIP_TRY(ctx, hipMemsetAsync(s.heavy_ws.p, 0, kHeavyHeaderBytes, st));  // long-bucket counters, phase counters
     if (max_refs <= kTinyRefs && !ctx->small_msm_off) {
         // Small jobs are chains of dependent additions on a nearly empty chip: everything from here to the copy back
-        // in ONE launch on the slot's own stream (msm_finalize.hip: k_small_msm), no bucket memset, no stream hand-over.
+        // in ONE launch on the front stream (msm_finalize.hip: k_small_msm), no bucket memset, no stream hand-over.
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 3], st));
         launch_small_msm(st, ctx->table.p, s.sorted.dev(), s.offs.dev(), nbt, lanes, max_refs, s.buckets.p, s.part_a.p, s.part_b.p,
                          s.heavy_ws.p, s.small.dev() + 26, stage1, stage2, ctx->small_lds_bytes);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], st));
     } else {
-        // hand over to the shared accumulation stream and back (each hand-over costs ~12 us: not when no other slot
-        // has work whose accumulation this one could collide with)
-        const bool hand_over = ctx->serialize_accum && !alone;
+        // hand over to the accumulation stream and on to the tail stream (each hand-over costs ~12 us: not when no other
+        // slot has work whose accumulation this one could collide with -- the whole job then stays on the front stream)
+        const bool hand_over = !alone;
         hipStream_t hs = hand_over ? ctx->heavy_stream : st;
         if (hand_over) {
             HIP_TRY(ctx, hipEventRecord(s.sorted_ev, st));
@@ -580,6 +628,7 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], hs));
         if (hand_over) {
             HIP_TRY(ctx, hipEventRecord(s.accum_ev, hs));
+            st = s.end = ctx->tail_stream;
             HIP_TRY(ctx, hipStreamWaitEvent(st, s.accum_ev, 0));
         }
         launch_bucket_finalize(st, s.offs.dev(), nbt, lanes, s.part_a.p, s.part_b.p, s.buckets.p, s.heavy_ws.p, s.small.dev() + 26,
@@ -715,7 +764,7 @@ int ensure_points(kzg_ctx* ctx, Slot& s, size_t n, size_t k) {
 }
 // where the scan of a multiproof leaves P(z_i): the single-root kernels (k == 1) write the slot's flag words
 const uint32_t* points_values(const Slot& s, size_t k) { return k == 1 ? s.small.host() + 8 : s.pvals.host(); }
-// enqueues the scan of P at the k points on the slot's stream: q[0 .. nq) to s.q when want_q, the values as above.
+// enqueues the scan of P at the k points on the front stream: q[0 .. nq) to s.q when want_q, the values as above.
 // k == 1 takes the single-root kernels unchanged (w_0 = 1), so its proofs are kzg_open's bit for bit.
 int enqueue_points_scan(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, const uint64_t* zs, const uint64_t* ws,
                         size_t k, size_t nq, bool want_q) {
@@ -813,7 +862,6 @@ int kzg_ctx_create(int device, kzg_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return KZG_ERR_NO_DEVICE;
     kzg_ctx* ctx = new kzg_ctx();
     ctx->device = device;
-    if (const char* v = std::getenv("KZG_SERIALIZE_ACCUM")) ctx->serialize_accum = std::atoi(v) != 0;
     if (const char* v = std::getenv("KZG_ACCUM_LDS_KB")) ctx->accum_lds_bytes = (uint32_t)std::atoi(v) * 1024u;
     if (const char* v = std::getenv("KZG_SMALL_MSM")) ctx->small_msm_off = std::atoi(v) == 0;
     if (const char* v = std::getenv("KZG_HOST_TRACE")) ctx->host_trace = std::atoi(v) != 0;
@@ -843,11 +891,13 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
                      (unsigned long long)ctx->trace_calls.load(), k * ctx->trace_ns[0].load(), k * ctx->trace_ns[1].load(),
                      k * ctx->trace_ns[2].load(), k * ctx->trace_ns[3].load(), k * ctx->trace_ns[4].load());
     }
-    // What has an order: every slot's stream is waited for before any buffer goes.  `delete` then frees the slots' buffers
-    // (members) and after them each slot's events and stream (its base, SlotQueue), between the context's own buffers.
-    for (auto& s : ctx->slots)
-        if (s.stream) hipStreamSynchronize(s.stream);
-    if (ctx->heavy_stream) hipStreamDestroy(ctx->heavy_stream);  // (idle: every accumulation hands back to a slot's stream)
+    // What has an order: the streams are waited for before any buffer goes and destroyed here, once (the slots only
+    // hold the front stream's handle).  `delete` then frees the slots' buffers (members) and after them each slot's events
+    // (its base, SlotQueue), between the context's own buffers.
+    for (hipStream_t st : {ctx->upload_stream, ctx->front_stream, ctx->heavy_stream, ctx->tail_stream})
+        if (st) hipStreamSynchronize(st);
+    for (hipStream_t st : {ctx->upload_stream, ctx->front_stream, ctx->heavy_stream, ctx->tail_stream})
+        if (st) hipStreamDestroy(st);
     delete ctx;
 }
 
@@ -1152,6 +1202,7 @@ static int submit_commit_locked(kzg_ctx* ctx, int slot, const uint32_t* d_scalar
     if (s.kind != (owned ? SLOT_RESERVED : SLOT_IDLE)) return KZG_ERR_BUSY;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.has_quotient = false;
     s.job_n = n;
     s.job_batch = 1;
@@ -1172,7 +1223,7 @@ static int submit_commit_locked(kzg_ctx* ctx, int slot, const uint32_t* d_scalar
     }
     int rc = enqueue_msm(ctx, s, d_scalars, is_mont, n_msm, 0);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_COMMIT;
     return KZG_OK;
 }
@@ -1195,6 +1246,7 @@ static int submit_open_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, 
     int rc = ensure_poly(ctx, s, n);
     if (rc) return rc;
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.job_n = n;
     s.job_batch = 1;
     s.has_quotient = true;
@@ -1228,7 +1280,7 @@ static int submit_open_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs, 
         rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0);
         if (rc) return rc;
     }
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = nq > 0 ? SLOT_OPEN : SLOT_TRIVIAL;
     return KZG_OK;
 }
@@ -1258,6 +1310,7 @@ static int submit_points_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs
     if (rc == KZG_OK) rc = ensure_points(ctx, s, n, k);
     if (rc) return rc;
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.job_n = n;
     s.job_batch = 1;
     s.has_quotient = true;
@@ -1280,7 +1333,7 @@ static int submit_points_locked(kzg_ctx* ctx, int slot, const uint32_t* d_coeffs
         if (rc) return rc;
     }
     s.pts_nq = nq;
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_OPEN_POINTS;
     return KZG_OK;
 }
@@ -1313,7 +1366,7 @@ static int wait_locked(kzg_ctx* ctx, int slot, uint64_t out_p1[18]) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SlotKind kind = s.kind;
     slot_idle(ctx, s);
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    HIP_TRY(ctx, hipEventSynchronize(s.done));
     const bool ran_msm = kind != SLOT_TRIVIAL && !(kind == SLOT_OPEN_POINTS && s.pts_nq == 0);
     if (ran_msm) fill_device_times(s);
     if (s.timing && ran_msm) {
@@ -1408,6 +1461,7 @@ static int commit_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coef
     if (s.kind != (owned ? SLOT_RESERVED : SLOT_IDLE)) return KZG_ERR_BUSY;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.has_quotient = false;
     s.job_n = n;
     s.job_batch = (uint32_t)batch;
@@ -1416,7 +1470,7 @@ static int commit_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coef
     std::memset(s.small.host(), 0, 64 * 4);
     int rc = enqueue_msm(ctx, s, (const uint32_t*)d_coeffs, 1, n, 0, (uint32_t)batch, stride_coeffs);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_COMMIT_BATCH;
     return KZG_OK;
 }
@@ -1436,7 +1490,7 @@ static int wait_batch_locked(kzg_ctx* ctx, int slot, uint64_t* out_p1s, size_t b
     if (s.kind != SLOT_COMMIT_BATCH || s.job_batch != batch) return KZG_ERR_INVALID_ARG;  // the job stays in the slot
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slot_idle(ctx, s);
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    HIP_TRY(ctx, hipEventSynchronize(s.done));
     fill_device_times(s);
     if (s.timing) {
         float ms = 0;
@@ -1486,6 +1540,7 @@ static int open_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coeffs
     if (rc == KZG_OK) rc = s.bsmall.reserve(ctx, batch * 32 * 4, s.stream);
     if (rc) return rc;
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.job_n = n;
     s.job_batch = (uint32_t)batch;
     s.has_quotient = true;
@@ -1507,7 +1562,7 @@ static int open_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coeffs
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
     rc = enqueue_msm(ctx, s, s.q.dev(), 1, nq, 0, (uint32_t)batch, nq);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_OPEN_BATCH;
     return KZG_OK;
 }
@@ -1528,7 +1583,7 @@ static int wait_open_batch_locked(kzg_ctx* ctx, int slot, uint64_t* out_p1s, int
         return KZG_ERR_INVALID_ARG;  // the job stays in the slot
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slot_idle(ctx, s);
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    HIP_TRY(ctx, hipEventSynchronize(s.done));
     fill_device_times(s);
     if (s.timing) {
         float ms = 0;
@@ -1613,7 +1668,7 @@ static int commit_host(kzg_ctx* ctx, const void* scalars, int is_mont, size_t n,
     const size_t n_dev = n < ctx->n ? n : ctx->n;
     int rc = ensure_poly(ctx, s, n_dev);
     tr.mark(0);
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), scalars, n_dev * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), scalars, n_dev * 32);
     tr.mark(1);
     if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), is_mont, n_dev, true, true);
     tr.mark(2);
@@ -1647,7 +1702,7 @@ int kzg_open(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t z[4]
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, n);
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), coeffs, n * 32);
     if (rc == KZG_OK) rc = submit_open_locked(ctx, slot, s.stage.dev(), n, z, y, true);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
@@ -1669,7 +1724,7 @@ int kzg_open_points(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, n);
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), coeffs, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), coeffs, n * 32);
     if (rc == KZG_OK) rc = submit_points_locked(ctx, slot, s.stage.dev(), n, zs, ys, k, true);
     if (rc == KZG_OK) {
         await_unlocked(lk, s);
@@ -1694,7 +1749,7 @@ int ensure_combined(kzg_ctx* ctx, Slot& s, size_t n, size_t t_pass, size_t stage
     return rc;
 }
 // every multiplier of one call: the 16 + 16 tables and the stride of z (a lane's power inside a tile) and of W = z^2048
-// (a tile's power inside the polynomial), then gamma^i -- 66 + t host products -- copied to the slot's table on its stream
+// (a tile's power inside the polynomial), then gamma^i -- 66 + t host products -- copied to the slot's table on the front stream
 void combine_fill_powers(Fr30* tab, const hf::Fr& z) {  // entries [0, kCombineTabGamma)
     auto fill = [&](const hf::Fr& x, uint32_t at_a, uint32_t at_b, uint32_t at_256) {
         const hf::Fr x16 = hf::fr_pow(x, 16);
@@ -1722,7 +1777,7 @@ int combined_upload_table(kzg_ctx* ctx, Slot& s, const hf::Fr& z, const hf::Fr& 
     HIP_TRY(ctx, hipMemcpyAsync(s.ctab.d, s.ctab.h, (kCombineTabGamma + t) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
     return KZG_OK;
 }
-// one pass on the slot's stream: polynomials first .. first + cnt (device memory) into F (s.stage, carried from the earlier
+// one pass on the front stream: polynomials first .. first + cnt (device memory) into F (s.stage, carried from the earlier
 // passes when first > 0) and their values into the slot's value words
 int combined_pass(kzg_ctx* ctx, Slot& s, const uint32_t* d_coeffs, size_t n, size_t cnt, size_t stride, size_t first) {
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
@@ -1810,13 +1865,14 @@ int combined_enqueue_open(kzg_ctx* ctx, Slot& s, size_t n, size_t t, const uint6
         }
         s.pts_nq = nq;
     }
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_OPEN_COMBINED;
     return KZG_OK;
 }
 int combined_job_start(kzg_ctx* ctx, Slot& s, size_t t) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.combine_ms = 0;
     std::memset(&s.times, 0, sizeof s.times);
     int rc = ensure_combined(ctx, s, 0, 0, 0);
@@ -1834,7 +1890,7 @@ int wait_combined_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slot_idle(ctx, s);
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    HIP_TRY(ctx, hipEventSynchronize(s.done));
     const bool ran_msm = s.pts_nq > 0;
     if (ran_msm) fill_device_times(s);
     if (s.timing && s.job_n > 0) {
@@ -2091,6 +2147,7 @@ int ensure_sets(kzg_ctx* ctx, Slot& s, size_t n, size_t npts) {
 int sets_job_start(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     s.timing = ctx->timing;
+    s.end = s.stream;
     s.combine_ms = 0;
     std::memset(&s.times, 0, sizeof s.times);
     int rc = ensure_combined(ctx, s, 0, 0, 0);
@@ -2107,7 +2164,7 @@ int sets_ensure_all(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n, size_
     return rc;
 }
 // the multipliers of one call -- 66 host products per distinct point, the multipliers and the lists as planned -- copied to
-// the slot's tables on its stream
+// the slot's tables on the front stream
 int sets_upload_tables(kzg_ctx* ctx, Slot& s, const SetsPlan& plan) {
     Fr30* tab = (Fr30*)s.stab.h;
     for (size_t r = 0; r < plan.npts; r++) combine_fill_powers(tab + r * kCombineTabGamma, plan.pts[r]);
@@ -2192,7 +2249,7 @@ int sets_enqueue_open(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, size_t n) {
         if (rc2) return rc2;
         s.pts_nq = nq;
     }
-    HIP_TRY(ctx, hipEventRecord(s.done, s.stream));
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_OPEN_SETS;
     return KZG_OK;
 }
@@ -2210,7 +2267,7 @@ int wait_sets_locked(kzg_ctx* ctx, int slot, uint64_t* out_ys, uint64_t out_p1[1
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slot_idle(ctx, s);
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    HIP_TRY(ctx, hipEventSynchronize(s.done));
     const bool ran_msm = s.pts_nq > 0;
     if (ran_msm) fill_device_times(s);
     if (s.timing && s.job_n > 0) {
@@ -2413,7 +2470,7 @@ static int batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t str
         Slot& s = ctx->slots[slot];
         rc = ensure_poly(ctx, s, n * polys);
         for (size_t q = 0; q < polys && rc == KZG_OK; q++)
-            rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev() + (q * n) * 8, coeffs + (first + (at + q) * step) * stride * 4, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+            rc = upload_unlocked(ctx, lk, s, s.stage.dev() + (q * n) * 8, coeffs + (first + (at + q) * step) * stride * 4, n * 32);
         if (rc == KZG_OK) {
             if (opening) {
                 zc.resize(4 * polys);
@@ -2458,7 +2515,7 @@ int ctx_open_slice_begin(kzg_ctx* ctx, const uint64_t* slice, size_t len, const 
     if (slot < 0) return KZG_ERR_BUSY;
     Slot& s = ctx->slots[slot];
     int rc = ensure_poly(ctx, s, len + 1);
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), slice, len * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), slice, len * 32);
     if (rc == KZG_OK) {
         lk.unlock();
         uint32_t zw[8];

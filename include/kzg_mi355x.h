@@ -365,6 +365,64 @@ int kzg_commit_evaluations_submit(kzg_ctx* ctx, int slot, const void* d_evals, s
 int kzg_open_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, const uint64_t z[4], const uint64_t y[4],
                          uint64_t out_p1[18]);
 
+/* ---- a Lagrange-basis SRS: commitments and openings straight from the values -------------------
+ * For the domain of n = 2^log_n points (w_n as kzg_domain_root, natural order) the context can hold the Lagrange form of its
+ * setup, L_i = [l_i(s)] G1 = (1/n) sum_j w^(-ij) SRS[j], with window-table levels of its own (a second W x n x 128 bytes of
+ * device memory).  A commitment to values is then sum_i evals[i] L_i and an opening is the MSM of the quotient's VALUES
+ * q_i = (f_i - y) / (w^i - z) over the same points (the entry with w^i = z from the others): no inverse NTT runs.  ONE basis
+ * (one n) is held per context.  Every SRS load, generation, kzg_srs_update and failed load drops it; it is never rebuilt
+ * behind the caller's back except by the host-pointer calls below, which build the basis of their n on first use.
+ * The basis is an inverse G1 DFT of the setup and uses the endomorphism, as kzg_g1_dft does: the SRS must lie in G1
+ * (kzg_srs_verify checks this).
+ * Errors common to the calls on values: n not a power of two or above 2^KZG_NTT_MAX_LOG -> KZG_ERR_INVALID_ARG; no SRS ->
+ * KZG_ERR_NO_SRS; n > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH.  This differs from kzg_commit_evaluations, which accepts
+ * values of a low-degree polynomial over a domain longer than the SRS: here every one of the n basis points is a
+ * combination of SRS[0 .. n), so the SRS must reach n points whatever the degree.
+ * Results equal kzg_commit_evaluations / kzg_open_evaluations of the same input bit for bit (the same group element,
+ * normalised the same way), with the same statuses in the same order: all n values equal (n = 1 included) -> infinity when
+ * y is that value, else KZG_ERR_CONSTANT_POLY; P(z) != y -> KZG_ERR_REMAINDER, for z inside and outside the domain.
+ * Multi-device contexts: a replicated SRS forwards to the device the evaluation calls forward to; a range-split one returns
+ * KZG_ERR_INVALID_ARG (kzg_last_error says why); the _submit calls take single-device contexts only. */
+/* builds the basis of 2^log_n points, replacing a held one of another size (waits for the jobs in flight first).
+ * log_n > KZG_NTT_MAX_LOG -> KZG_ERR_INVALID_ARG; no SRS -> KZG_ERR_NO_SRS; 2^log_n > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH */
+int kzg_lagrange_prepare(kzg_ctx* ctx, unsigned log_n);
+/* points of the held basis, 0 when none is held */
+size_t kzg_lagrange_len(const kzg_ctx* ctx);
+/* L_index .. L_(index + count - 1) as blst_p1 with Z = 1, all zero for infinity, like kzg_srs_read_g1; KZG_ERR_NO_SRS when no
+ * basis is held */
+int kzg_lagrange_read_g1(kzg_ctx* ctx, size_t index, size_t count, uint64_t* out_p1);
+/* upload -> MSM over the basis; builds the basis of n points on first use */
+int kzg_commit_lagrange(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, uint64_t out_p1[18]);
+/* d_evals is a DEVICE pointer; collected by kzg_wait.  Never builds: KZG_ERR_NO_SRS unless a basis of exactly n points is held */
+int kzg_commit_lagrange_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n);
+/* polynomial b by its n values at evals + 4 b stride (stride >= n, in blst_fr), result b at out_p1s + 18 b: through the batched
+ * MSM in sub-batches of at most kzg_max_batch polynomials; builds the basis on first use */
+int kzg_commit_lagrange_batch(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, size_t batch, size_t stride, uint64_t* out_p1s);
+/* the proof that P(z) = y for P given by its values; z inside or outside the domain; builds the basis on first use */
+int kzg_open_lagrange(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, const uint64_t z[4], const uint64_t y[4],
+                      uint64_t out_p1[18]);
+/* d_evals is a DEVICE pointer that stays untouched until kzg_wait collected the job; never builds, like the commit form */
+int kzg_open_lagrange_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n, const uint64_t z[4], const uint64_t y[4]);
+/* test hook: the n values of the quotient the opening commits to (all zero for a constant polynomial whose claim holds); needs
+ * no SRS; the statuses of kzg_open_lagrange */
+int kzg_quotient_lagrange(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, const uint64_t z[4], const uint64_t y[4],
+                          uint64_t* out_q_evals);
+
+/* adopts a basis GIVEN as n x 48 bytes (compressed points; order KZG_ORDER_NATURAL: point i is L_i, KZG_ORDER_BIT_REVERSED:
+ * point i is L_brp(i), the order the first ceremony files carried g1_lagrange in) for the resident SRS, replacing a held one.
+ * Points are decoded on the device with the subgroup check always on: a point that does not decode or lies outside G1 ->
+ * KZG_ERR_INVALID_ARG with *bad_index its index in the input ((size_t)-1 otherwise; bad_index may be NULL), nothing adopted.
+ * check != 0 compares the points with the resident SRS: n weights rho of 128 bits from getrandom(2), the MSM of rho over the
+ * given points against the MSM of the inverse NTT of rho over the monomial table; *consistent (required then) = 1 or 0.  On 0
+ * the basis is NOT adopted, a held one stays, and the call still returns KZG_OK.  A wrong basis passes with probability about
+ * 2^-128.  check == 0 adopts unchecked (*consistent stays 0).  No SRS -> KZG_ERR_NO_SRS; n > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH */
+int kzg_lagrange_load_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, unsigned order, int check, size_t* bad_index,
+                                 int* consistent);
+/* a setup that exists only in Lagrange form: decodes as above, SRS[j] = sum_i w^(ij) L_i by a forward G1 DFT, then the normal
+ * ingest (kzg_srs_len = n afterwards) and the decoded points stay as the Lagrange basis.  A malformed input leaves the
+ * context as it was.  Single-device contexts only (KZG_ERR_INVALID_ARG otherwise) */
+int kzg_srs_load_lagrange_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, unsigned order, size_t* bad_index);
+
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
  * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what

@@ -68,6 +68,9 @@ ABI_SYMBOLS = [
     "kzg_open_sets", "kzg_open_sets_submit", "kzg_wait_sets", "kzg_quotient_sets", "kzg_verify_sets",
     "kzg_sha256", "kzg_sha256_pieces", "kzg_sha256_has_shani", "kzg_blob_challenges_bytes", "kzg_blobs_open_at_bytes", "kzg_blobs_to_blob_proofs_bytes",
     "kzg_verify_blob_proofs_batch_bytes",
+    "kzg_lagrange_prepare", "kzg_lagrange_len", "kzg_lagrange_read_g1", "kzg_lagrange_load_compressed",
+    "kzg_srs_load_lagrange_compressed", "kzg_commit_lagrange", "kzg_commit_lagrange_submit", "kzg_commit_lagrange_batch",
+    "kzg_open_lagrange", "kzg_open_lagrange_submit", "kzg_quotient_lagrange",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -175,6 +178,17 @@ def load_library():
         "kzg_commit_evaluations": (i, [vp, vp, sz, vp]),
         "kzg_commit_evaluations_submit": (i, [vp, i, vp, sz]),
         "kzg_open_evaluations": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_lagrange_prepare": (i, [vp, C.c_uint]),
+        "kzg_lagrange_len": (sz, [vp]),
+        "kzg_lagrange_read_g1": (i, [vp, sz, sz, vp]),
+        "kzg_lagrange_load_compressed": (i, [vp, vp, sz, C.c_uint, i, C.POINTER(sz), C.POINTER(i)]),
+        "kzg_srs_load_lagrange_compressed": (i, [vp, vp, sz, C.c_uint, C.POINTER(sz)]),
+        "kzg_commit_lagrange": (i, [vp, vp, sz, vp]),
+        "kzg_commit_lagrange_submit": (i, [vp, i, vp, sz]),
+        "kzg_commit_lagrange_batch": (i, [vp, vp, sz, sz, sz, vp]),
+        "kzg_open_lagrange": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_open_lagrange_submit": (i, [vp, i, vp, sz, vp, vp]),
+        "kzg_quotient_lagrange": (i, [vp, vp, sz, vp, vp, vp]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1133,6 +1147,86 @@ class Engine:
         out = np.zeros(18, dtype=np.uint64)
         _check(self._lib.kzg_open_evaluations(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), _ptr(out)), self._h)
         return G1Point(out)
+
+    # -- the Lagrange basis of the n-domain: commitments and openings from values with no inverse NTT --
+    def lagrange_prepare(self, log_n):
+        """kzg_lagrange_prepare: builds (or replaces) the basis L_i = [l_i(s)] G1 of the 2^log_n-domain"""
+        _check(self._lib.kzg_lagrange_prepare(self._h, int(log_n)), self._h)
+
+    def lagrange_len(self):
+        return int(self._lib.kzg_lagrange_len(self._h))
+
+    def lagrange_read(self, index, count):
+        out = np.zeros((count, 18), dtype=np.uint64)
+        _check(self._lib.kzg_lagrange_read_g1(self._h, index, count, _ptr(out)), self._h)
+        return out
+
+    def _lagrange_bytes(self, fn, data, order, *more):
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        assert buf.size % 48 == 0
+        bad = C.c_size_t(0)
+        rc = fn(self._h, _ptr(buf), buf.size // 48, int(order), *more, C.byref(bad))
+        if rc != KZG_OK:
+            e = self._error(rc)
+            e.bad_index = None if bad.value == C.c_size_t(-1).value else int(bad.value)
+            raise e
+
+    def lagrange_load_compressed(self, data, order=KZG_ORDER_NATURAL, check=True):
+        """kzg_lagrange_load_compressed: adopts the basis given as n x 48 bytes.  Returns whether it was adopted: False when
+        check found it inconsistent with the resident SRS.  Raises KzgError with .bad_index for a malformed point"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        assert buf.size % 48 == 0
+        bad, ok = C.c_size_t(0), C.c_int(0)
+        rc = self._lib.kzg_lagrange_load_compressed(self._h, _ptr(buf), buf.size // 48, int(order), 1 if check else 0,
+                                                    C.byref(bad), C.byref(ok))
+        if rc != KZG_OK:
+            e = self._error(rc)
+            e.bad_index = None if bad.value == C.c_size_t(-1).value else int(bad.value)
+            raise e
+        return bool(ok.value) if check else True
+
+    def srs_load_lagrange_compressed(self, data, order=KZG_ORDER_NATURAL):
+        """kzg_srs_load_lagrange_compressed: a setup that exists only in Lagrange form (n x 48 bytes) becomes the SRS and
+        its Lagrange basis"""
+        self._lagrange_bytes(self._lib.kzg_srs_load_lagrange_compressed, data, order)
+
+    def commit_lagrange_limbs(self, evals):
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_commit_lagrange(self._h, _ptr(a), a.shape[0], _ptr(out)), self._h)
+        return G1Point(out)
+
+    def commit_lagrange_submit(self, slot, dptr, n):
+        _check(self._lib.kzg_commit_lagrange_submit(self._h, slot, C.c_void_p(dptr), n), self._h)
+
+    def commit_lagrange_batch(self, evals, n=None):
+        """kzg_commit_lagrange_batch: evals a (batch, stride, 4) array (or a list of equally long (stride, 4) arrays) whose
+        first n values per row are the polynomial's (n=None: all of them)"""
+        flat = self._stack(evals)
+        b, rows = flat.shape[0], flat.shape[1]
+        n = rows if n is None else int(n)
+        out = np.zeros((b, 18), dtype=np.uint64)
+        _check(self._lib.kzg_commit_lagrange_batch(self._h, _ptr(flat), n, b, rows, _ptr(out)), self._h)
+        return [G1Point(out[i]) for i in range(b)]
+
+    def open_lagrange_limbs(self, evals, z, y):
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        zl, yl = z.limbs(), y.limbs()
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_open_lagrange(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), _ptr(out)), self._h)
+        return G1Point(out)
+
+    def open_lagrange_submit(self, slot, dptr, n, z, y):
+        zl, yl = z.limbs(), y.limbs()
+        _check(self._lib.kzg_open_lagrange_submit(self._h, slot, C.c_void_p(dptr), n, _ptr(zl), _ptr(yl)), self._h)
+
+    def quotient_lagrange_limbs(self, evals, z, y):
+        """kzg_quotient_lagrange: the n values of (P - y) / (X - z) over the domain"""
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        zl, yl = z.limbs(), y.limbs()
+        out = np.zeros_like(a)
+        _check(self._lib.kzg_quotient_lagrange(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), _ptr(out)), self._h)
+        return out
 
     # -- device-resident, pipelined --
     def num_slots(self):

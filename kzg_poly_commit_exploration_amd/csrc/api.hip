@@ -233,6 +233,9 @@ struct Slot : SlotQueue {
     PinnedBuf svals{PinnedBuf::Mapped};
     DevBuf sg;
     std::vector<uint32_t> sets_vmap;
+    // openings from evaluations over the Lagrange basis (kzg_open_lagrange): the tile records of the
+    // quotient kernels; the quotient's values go to q
+    DevBuf lag_part;
     // cells of a domain (kzg_cells_and_proofs): P for the whole call in cpoly (read by the sub-batches of every slot the call
     // holds, after cells_ev), the chunk aggregates of the cell quotients in cagg
     DevBuf cpoly, cagg;
@@ -268,6 +271,13 @@ struct kzg_ctx {
     MsmConfig cfg = {};
     DevBuf table;   // W * n affine points
     DevBuf ntt_tw;  // NTT twiddles, built on first use: forward lo, forward hi, inverse lo, inverse hi (ntt_kernels.hip)
+    // The Lagrange basis of one domain: L_i = [l_i(s)] G1 for the lag_n = 2^k points of the domain, with
+    // its own window-table levels in the SRS table's format (level stride lag_n, the same MsmConfig, lag_n <= n so the slots'
+    // workspaces fit).  Built under fk20_mu (the DFT reads the split twiddles) by kzg_lagrange_prepare or the first host-pointer
+    // call that needs it; dropped with the SRS (srs_release).
+    DevBuf lag_table;
+    size_t lag_n = 0;
+    uint64_t srs_gen = 0;  // counts the SRS replacements (srs_release): a basis built across one is not adopted
     ReducePlan plan;
     size_t arena_records = 0, final_records = 0;  // per polynomial of a batch
     uint32_t max_batch = 1;                        // polynomials per submit the workspaces are sized for
@@ -461,6 +471,8 @@ int setup_slots(kzg_ctx* ctx, bool keep_table_on_failure = false) {
         for (auto& s : ctx->slots) free_slot_msm(s);
         if (keep_table_on_failure) return rc;  // the caller retries with the previous sizes
         ctx->table.reset();
+        ctx->lag_table.reset();
+        ctx->lag_n = 0;
         ctx->n = 0;
         (void)hipGetLastError();
     }
@@ -548,6 +560,9 @@ static int srs_release(kzg_ctx* ctx) {
     ctx->table.reset();
     ctx->fk20_B.reset();  // the FK20 cache holds transforms of the old SRS
     ctx->fk20_tab.reset();
+    ctx->lag_table.reset();  // ... and the Lagrange basis is a transform of it: dropped, not rebuilt
+    ctx->lag_n = 0;
+    ctx->srs_gen++;
     ctx->n = 0;
     return KZG_OK;
 }
@@ -571,14 +586,21 @@ int srs_prepare(kzg_ctx* ctx, size_t n) {
 // enqueue `batch` MSMs of n scalars each (polynomial p at d_scalars + p * stride scalars) on slot s: the sort on the
 // front stream, the accumulation on the accumulation stream, the rest on the tail stream.  Leaves in s.end the stream the job
 // ended on: whatever the caller enqueues behind the MSM (its `done` event) goes THERE, never on the front stream.
+// basis: the window table the job reads, the monomial SRS when null.
+struct MsmBasis {
+    const void* table;  // W levels of `stride` affine records each
+    uint32_t stride;
+};
 int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, size_t n, int ev_base,
-                uint32_t batch = 1, uint64_t stride = 0) {
+                uint32_t batch = 1, uint64_t stride = 0, const MsmBasis* basis = nullptr) {
     const MsmConfig cfg = ctx->cfg;
+    const void* table = basis ? basis->table : ctx->table.p;
+    const uint32_t table_stride = basis ? basis->stride : (uint32_t)ctx->n;
     const uint32_t nbt = cfg.nb * batch;  // polynomial-major bucket ids
     hipStream_t st = s.stream;
     s.end = st;
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base], st));
-    const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, (uint32_t)ctx->n, cfg, s.cnt.dev(),
+    const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, table_stride, cfg, s.cnt.dev(),
                        s.block_sums.dev(), s.pairs.dev<uint64_t>(), s.offs.dev(), s.sorted.dev(), (uint32_t*)s.heavy_ws.p);
     if (s.timing) {
         HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 1], st));
@@ -609,7 +631,7 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
         // Small jobs are chains of dependent additions on a nearly empty chip: everything from here to the copy back
         // in ONE launch on the front stream (msm_finalize.hip: k_small_msm), no bucket memset, no stream hand-over.
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 3], st));
-        launch_small_msm(st, ctx->table.p, s.sorted.dev(), s.offs.dev(), nbt, lanes, max_refs, s.buckets.p, s.part_a.p, s.part_b.p,
+        launch_small_msm(st, table, s.sorted.dev(), s.offs.dev(), nbt, lanes, max_refs, s.buckets.p, s.part_a.p, s.part_b.p,
                          s.heavy_ws.p, s.small.dev() + 26, stage1, stage2, ctx->small_lds_bytes);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], st));
     } else {
@@ -622,7 +644,7 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
             HIP_TRY(ctx, hipStreamWaitEvent(hs, s.sorted_ev, 0));
         }
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 3], hs));
-        launch_bucket_accumulate(hs, ctx->table.p, s.sorted.dev(), s.offs.dev(), nbt, lanes, s.buckets.p, s.part_a.p, s.part_b.p,
+        launch_bucket_accumulate(hs, table, s.sorted.dev(), s.offs.dev(), nbt, lanes, s.buckets.p, s.part_a.p, s.part_b.p,
                                  ctx->accum_lds_bytes, s.pair_scratch.p, max_refs,
                                  (char*)s.heavy_ws.p + kAccumClockOffset);
         if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 4], hs));
@@ -1193,10 +1215,19 @@ int kzg_srs_read_g1(kzg_ctx* ctx, size_t index, size_t count, uint64_t* out_p1) 
 
 // ---- submit / wait ---------------------------------------------------------------------------
 
+// the held Lagrange basis as an MSM basis when it is the one of n points (ctx->mu held)
+static bool lagrange_basis(const kzg_ctx* ctx, size_t n, MsmBasis* out) {
+    if (!ctx->lag_table.p || ctx->lag_n != n) return false;
+    *out = MsmBasis{ctx->lag_table.p, (uint32_t)ctx->lag_n};
+    return true;
+}
+
 // owned: the caller holds the slot through reserve_slot (SLOT_RESERVED) instead of finding it idle
+// basis: the table of exactly n points (n <= ctx->n) the MSM reads instead of the SRS -- the scalars are n values over its domain
 static int submit_commit_locked(kzg_ctx* ctx, int slot, const uint32_t* d_scalars, int is_mont, size_t n,
-                                bool tail_already_checked, bool owned = false) {
+                                bool tail_already_checked, bool owned = false, const MsmBasis* basis = nullptr) {
     if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (basis && (basis->stride != n || n > ctx->n)) return KZG_ERR_INVALID_ARG;
     if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
     Slot& s = ctx->slots[slot];
     if (s.kind != (owned ? SLOT_RESERVED : SLOT_IDLE)) return KZG_ERR_BUSY;
@@ -1221,7 +1252,7 @@ static int submit_commit_locked(kzg_ctx* ctx, int slot, const uint32_t* d_scalar
         s.kind = SLOT_TRIVIAL;
         return KZG_OK;
     }
-    int rc = enqueue_msm(ctx, s, d_scalars, is_mont, n_msm, 0);
+    int rc = enqueue_msm(ctx, s, d_scalars, is_mont, n_msm, 0, 1, 0, basis);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_COMMIT;
@@ -1453,8 +1484,10 @@ size_t kzg_max_batch(const kzg_ctx* ctx) {
 }
 
 static int commit_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coeffs, size_t n, size_t batch,
-                                      size_t stride_coeffs, bool owned = false) {
+                                      size_t stride_coeffs, bool owned = false, bool lagrange = false) {
     if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    MsmBasis basis{};
+    if (lagrange && !lagrange_basis(ctx, n, &basis)) return KZG_ERR_NO_SRS;
     if (slot < 0 || slot >= kNumSlots || batch > ctx->max_batch) return KZG_ERR_INVALID_ARG;
     if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;  // batches take truncated polynomials only
     Slot& s = ctx->slots[slot];
@@ -1468,7 +1501,7 @@ static int commit_batch_submit_locked(kzg_ctx* ctx, int slot, const void* d_coef
     s.tail_checked = true;
     std::memset(&s.times, 0, sizeof s.times);
     std::memset(s.small.host(), 0, 64 * 4);
-    int rc = enqueue_msm(ctx, s, (const uint32_t*)d_coeffs, 1, n, 0, (uint32_t)batch, stride_coeffs);
+    int rc = enqueue_msm(ctx, s, (const uint32_t*)d_coeffs, 1, n, 0, (uint32_t)batch, stride_coeffs, lagrange ? &basis : nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.done, s.end));
     s.kind = SLOT_COMMIT_BATCH;
@@ -2431,9 +2464,9 @@ void ctx_set_raw_partials(kzg_ctx* ctx, bool raw) {
     ctx->raw_partials = raw;
 }
 
-// shared body of the two host-pointer batches: zs == nullptr -> commitments
+// shared body of the two host-pointer batches: zs == nullptr -> commitments (lagrange: of values, over the held Lagrange basis)
 static int batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t stride, size_t first, size_t step, size_t count,
-                      const uint64_t* zs, const uint64_t* ys, uint64_t* out_p1s, int* statuses) {
+                      const uint64_t* zs, const uint64_t* ys, uint64_t* out_p1s, int* statuses, bool lagrange = false) {
     if (!count) return KZG_OK;
     const bool opening = zs != nullptr;
     std::unique_lock<std::mutex> lk(ctx->mu);
@@ -2481,7 +2514,7 @@ static int batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t str
                 }
                 rc = open_batch_submit_locked(ctx, slot, s.stage.dev(), n, polys, n, zc.data(), yc.data(), true);
             } else {
-                rc = commit_batch_submit_locked(ctx, slot, s.stage.dev(), n, polys, n, true);
+                rc = commit_batch_submit_locked(ctx, slot, s.stage.dev(), n, polys, n, true, lagrange);
             }
         }
         if (rc != KZG_OK) {
@@ -2504,6 +2537,9 @@ int ctx_commit_batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t
 int ctx_open_batch_host(kzg_ctx* ctx, const uint64_t* coeffs, size_t n, size_t stride_coeffs, size_t first, size_t step,
                         size_t count, const uint64_t* zs, const uint64_t* ys, uint64_t* out_p1s, int* statuses) {
     return batch_host(ctx, coeffs, n, stride_coeffs, first, step, count, zs, ys, out_p1s, statuses);
+}
+static int commit_lagrange_batch_host(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t stride, size_t count, uint64_t* out_p1s) {
+    return batch_host(ctx, evals, n, stride, 0, 1, count, nullptr, nullptr, out_p1s, nullptr, true);
 }
 
 // ---- one device's share of a range-sharded opening: the slice is staged once (multi.hip) ----------------------------
@@ -3480,6 +3516,312 @@ int kzg_g1_dft(kzg_ctx* ctx, const uint64_t* in_p1, size_t m, int inverse, uint6
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_p1, jac, m * 144, hipMemcpyDeviceToHost, s.stream));
     return sync_unlocked(ctx, lk, s.stream, "fk20");
+}
+
+// ---- the Lagrange basis and the calls on values over it (lagrange_kernels.hip) -----------------------
+// L_i = [l_i(s)] G1 = (1/n) sum_j w^(-ij) SRS[j]: an inverse G1 DFT of SRS[0 .. n), normalised into level 0 of a window table
+// of its own.  Locks: fk20_mu (the split twiddles), then ctx->mu; the build waits for the device without ctx->mu.
+
+static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc);  // (below: a kid's status with its error text)
+// the lg-bit reversal of i
+static uint32_t lagrange_brp(uint32_t i, uint32_t lg) {
+    uint32_t r = 0;
+    for (uint32_t b = 0; b < lg; b++) r |= ((i >> b) & 1u) << (lg - 1 - b);
+    return r;
+}
+// levels 1 .. W-1 of a basis table whose level 0 (n records) is in tab; d_xyzz_tmp: n XYZZ records, d_prefix: n x 64 bytes
+static void lagrange_enqueue_levels(kzg_ctx* ctx, hipStream_t st, void* tab, size_t n, void* d_xyzz_tmp, void* d_prefix) {
+    for (uint32_t j = 1; j < ctx->cfg.W; j++)
+        launch_table_window(st, (char*)tab + (size_t)(j - 1) * n * kAffineBytes, (uint32_t)n, ctx->cfg.level_bits, d_xyzz_tmp, d_prefix,
+                            (char*)tab + (size_t)j * n * kAffineBytes);
+}
+// The finished table becomes the context's basis (fk20_mu and ctx->mu held, the caller holds no slot).  No synchronous call is
+// between its steps and nothing in flight reads the basis that goes: from the quiesce on ctx->mu is not released, so no job can
+// start on it, and the ones that did have ended.  gen: ctx->srs_gen when the table was started.
+static int lagrange_adopt(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, DevBuf& tab, size_t n, uint64_t gen) {
+    quiesce(ctx, lk);
+    if (gen != ctx->srs_gen || !ctx->n || !ctx->slots_ready) {
+        ctx->last_error = "lagrange basis: the SRS was replaced while the basis was built";
+        return KZG_ERR_NO_SRS;
+    }
+    ctx->lag_n = 0;
+    if (ctx->lag_table.p) {
+        int rc = drain_all(ctx);
+        if (rc) return rc;
+        ctx->lag_table.reset();
+    }
+    std::swap(ctx->lag_table.p, tab.p);
+    std::swap(ctx->lag_table.cap, tab.cap);
+    ctx->lag_n = n;
+    return KZG_OK;
+}
+// builds the basis of 2^lg points, replacing a held one (fk20_mu and ctx->mu held; device current).  The held basis stays in
+// use while the new one is built.
+static int lagrange_build(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, uint32_t lg) {
+    const size_t n = (size_t)1 << lg;
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    if (ctx->lag_table.p && ctx->lag_n == n) return KZG_OK;
+    DevBuf tab;
+    const uint64_t gen = ctx->srs_gen;
+    {
+        const int slot = reserve_slot(ctx, lk, true);  // (keeps an SRS replacement out while ctx->mu is released below)
+        if (slot < 0) return KZG_ERR_BUSY;
+        SlotLease lease{ctx, slot};
+        hipStream_t st = ctx->slots[slot].stream;
+        int rc = ensure_glv(ctx, lk, lg, st);
+        if (rc) return rc;
+        DevBuf x1, x2, x3, prefix;
+        rc = tab.reserve(ctx, (size_t)ctx->cfg.W * n * kAffineBytes);
+        if (rc == KZG_OK) rc = x1.reserve(ctx, n * kXyzzBytes);
+        if (rc == KZG_OK) rc = x2.reserve(ctx, n * kXyzzBytes);
+        if (rc == KZG_OK) rc = x3.reserve(ctx, n * kXyzzBytes);
+        if (rc == KZG_OK) rc = prefix.reserve(ctx, n * 64);
+        if (rc) return rc;
+        launch_affine_to_xyzz(st, ctx->table.p, n, x1.p);
+        void* res = (void*)launch_g1_dft(st, x1.p, x2.p, x3.p, lg, 1, (const Glv*)ctx->glv.p, ctx->glv_log, true);
+        launch_g1_scale(st, res, n, glv_split(hf::fr_inv(fr_pow2(lg))));
+        launch_xyzz_to_affine(st, res, (uint32_t)n, tab.p, prefix.p);
+        lagrange_enqueue_levels(ctx, st, tab.p, n, res == x1.p ? x2.p : x1.p /* (the transform is in level 0 now) */, prefix.p);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = sync_unlocked(ctx, lk, st, "lagrange basis");  // before the temporaries go
+        if (rc) return rc;
+    }
+    return lagrange_adopt(ctx, lk, tab, n, gen);
+}
+// a multi-device context: a replicated SRS forwards to the device the evaluation calls forward to, a range-split one holds
+// no whole SRS to transform
+static kzg_ctx* lagrange_kid(kzg_ctx* ctx, int* rc) {
+    if (multi_mode(ctx->multi) != kMultiReplicate) {
+        ctx->last_error = "the Lagrange basis needs the whole SRS on one device: not on a range-split multi-device context";
+        *rc = KZG_ERR_INVALID_ARG;
+        return nullptr;
+    }
+    if (!multi_srs_len(ctx->multi)) {
+        *rc = KZG_ERR_NO_SRS;
+        return nullptr;
+    }
+    return multi_kid(ctx->multi, 0);
+}
+// the basis of n points is held when this returns KZG_OK with ctx->mu (lk) held: built now unless it was there
+static int lagrange_ensure(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, size_t n, uint32_t lg) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    if (ctx->lag_table.p && ctx->lag_n == n) return KZG_OK;
+    lk.unlock();  // fk20_mu is taken before ctx->mu
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    lk.lock();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return lagrange_build(ctx, lk, lg);
+}
+
+int kzg_lagrange_prepare(kzg_ctx* ctx, unsigned log_n) {
+    if (!ctx || log_n > KZG_NTT_MAX_LOG) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_lagrange_prepare(kid, log_n)) : rc;
+    }
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return lagrange_build(ctx, lk, log_n);
+}
+
+size_t kzg_lagrange_len(const kzg_ctx* ctx) {
+    if (!ctx) return 0;
+    if (ctx->multi) return multi_mode(ctx->multi) == kMultiReplicate ? kzg_lagrange_len(multi_kid(ctx->multi, 0)) : 0;
+    std::lock_guard<std::mutex> lk(const_cast<kzg_ctx*>(ctx)->mu);
+    return ctx->lag_table.p ? ctx->lag_n : 0;
+}
+
+int kzg_lagrange_read_g1(kzg_ctx* ctx, size_t index, size_t count, uint64_t* out_p1) {
+    if (!ctx || !out_p1) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_lagrange_read_g1(kid, index, count, out_p1)) : rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->lag_table.p || !ctx->lag_n) return KZG_ERR_NO_SRS;
+    if (index > ctx->lag_n || count > ctx->lag_n - index) return KZG_ERR_INVALID_ARG;
+    if (!count) return KZG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf d_p1;
+    int rc = d_p1.reserve(ctx, count * 144);
+    if (rc) return rc;
+    hipStream_t st = ctx->slots[0].stream;
+    launch_affine_to_p1(st, (const char*)ctx->lag_table.p + index * kAffineBytes, (uint32_t)count, d_p1.p);
+    HIP_TRY(ctx, hipMemcpyAsync(out_p1, d_p1.p, count * 144, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return KZG_OK;
+}
+
+int kzg_commit_lagrange_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    uint32_t lg = 0;
+    if (!ctx || !d_evals || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    MsmBasis basis{};
+    if (!lagrange_basis(ctx, n, &basis)) return KZG_ERR_NO_SRS;  // never builds
+    return submit_commit_locked(ctx, slot, (const uint32_t*)d_evals, 1, n, true, false, &basis);
+}
+
+int kzg_commit_lagrange(kzg_ctx* ctx, const uint64_t* evals, size_t n, uint64_t out_p1[18]) {
+    uint32_t lg = 0;
+    if (!ctx || !evals || !out_p1 || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_commit_lagrange(kid, evals, n, out_p1)) : rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = lagrange_ensure(ctx, lk, n, lg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};  // (a basis is replaced only when no synchronous call holds a slot: it stays until the submit)
+    Slot& s = ctx->slots[slot];
+    rc = ensure_poly(ctx, s, n);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), evals, n * 32);
+    MsmBasis basis{};
+    if (rc == KZG_OK && !lagrange_basis(ctx, n, &basis)) rc = KZG_ERR_NO_SRS;
+    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true, &basis);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    return wait_locked(ctx, slot, out_p1);
+}
+
+int kzg_commit_lagrange_batch(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t batch, size_t stride, uint64_t* out_p1s) {
+    uint32_t lg = 0;
+    if (!ctx || (!evals && batch) || (!out_p1s && batch) || !ntt_log(n, &lg) || stride < n) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_commit_lagrange_batch(kid, evals, n, batch, stride, out_p1s)) : rc;
+    }
+    {
+        std::unique_lock<std::mutex> lk(ctx->mu);
+        int rc = lagrange_ensure(ctx, lk, n, lg);
+        if (rc) return rc;
+    }
+    // (a basis replaced between the two steps makes the batch answer KZG_ERR_NO_SRS, as a submit would)
+    return commit_lagrange_batch_host(ctx, evals, n, stride, batch, out_p1s);
+}
+
+// the quotient on the values into s.q and the job's flag words (ctx->mu held, twiddles built, slot basics and buffers ready)
+static int enqueue_lagrange_quotient(kzg_ctx* ctx, Slot& s, const uint32_t* d_evals, uint32_t lg, const uint64_t z[4],
+                                     const uint64_t y[4]) {
+    hf::Fr zf;
+    std::memcpy(zf.l, z, 32);
+    uint32_t yw[8];
+    std::memcpy(yw, y, 32);
+    std::memset(s.small.host(), 0, 64 * 4);  // (the slot's last job was collected: nothing in flight writes them)
+    launch_lagrange_quotient(s.stream, d_evals, lg, fr30_arg_from_mont256(zf), fr30_from_limbs(yw),
+                             fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg))), ctx->ntt_tw.p, s.q.dev(), s.lag_part.dev(), s.small.dev());
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+static int lagrange_slot_ready(kzg_ctx* ctx, Slot& s, size_t n, uint32_t lg) {
+    int rc = ensure_ntt(ctx);
+    if (rc == KZG_OK) rc = ntt_slot_ready(ctx, s, n);
+    if (rc == KZG_OK) rc = s.lag_part.reserve(ctx, (size_t)lagrange_tiles(lg) * kLagPartialWords * 4);
+    return rc;
+}
+
+// An opening from values on slot `slot`: the quotient on the values, then the MSM over the Lagrange table; wait_locked reads
+// the flag words as it does for the coefficient route (constant polynomial, P(z) against y).
+static int submit_open_lagrange_locked(kzg_ctx* ctx, int slot, const uint32_t* d_evals, size_t n, uint32_t lg, const uint64_t z[4],
+                                       const uint64_t y[4], bool owned) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    MsmBasis basis{};
+    if (!lagrange_basis(ctx, n, &basis)) return KZG_ERR_NO_SRS;
+    if (slot < 0 || slot >= kNumSlots) return KZG_ERR_INVALID_ARG;
+    Slot& s = ctx->slots[slot];
+    if (s.kind != (owned ? SLOT_RESERVED : SLOT_IDLE)) return KZG_ERR_BUSY;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = lagrange_slot_ready(ctx, s, n, lg);
+    if (rc) return rc;
+    s.timing = ctx->timing;
+    s.end = s.stream;
+    s.job_n = n;
+    s.job_batch = 1;
+    s.has_quotient = true;
+    s.tail_checked = false;
+    std::memcpy(s.open_y, y, 32);
+    std::memset(&s.times, 0, sizeof s.times);
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[6], s.stream));
+    rc = enqueue_lagrange_quotient(ctx, s, d_evals, lg, z, y);
+    if (rc) return rc;
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[7], s.stream));
+    rc = enqueue_msm(ctx, s, s.q.dev(), 1, n, 0, 1, 0, &basis);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.done, s.end));
+    s.kind = SLOT_OPEN;
+    return KZG_OK;
+}
+
+int kzg_open_lagrange_submit(kzg_ctx* ctx, int slot, const void* d_evals, size_t n, const uint64_t z[4], const uint64_t y[4]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    uint32_t lg = 0;
+    if (!ctx || !d_evals || !z || !y || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return submit_open_lagrange_locked(ctx, slot, (const uint32_t*)d_evals, n, lg, z, y, false);
+}
+
+int kzg_open_lagrange(kzg_ctx* ctx, const uint64_t* evals, size_t n, const uint64_t z[4], const uint64_t y[4], uint64_t out_p1[18]) {
+    uint32_t lg = 0;
+    if (!ctx || !evals || !z || !y || !out_p1 || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_open_lagrange(kid, evals, n, z, y, out_p1)) : rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = lagrange_ensure(ctx, lk, n, lg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = lagrange_slot_ready(ctx, s, n, lg);
+    if (rc == KZG_OK) rc = upload_unlocked(ctx, lk, s, s.stage.dev(), evals, n * 32);
+    if (rc == KZG_OK) rc = submit_open_lagrange_locked(ctx, slot, s.stage.dev(), n, lg, z, y, true);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    return wait_locked(ctx, slot, out_p1);
+}
+
+int kzg_quotient_lagrange(kzg_ctx* ctx, const uint64_t* evals, size_t n, const uint64_t z[4], const uint64_t y[4], uint64_t* out_q_evals) {
+    uint32_t lg = 0;
+    if (!ctx || !evals || !z || !y || !out_q_evals || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_quotient_lagrange(multi_kid(ctx->multi, 0), evals, n, z, y, out_q_evals);  // needs no SRS
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = lagrange_slot_ready(ctx, s, n, lg);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.stage.dev(), evals, n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (evaluations)");
+    if (rc == KZG_OK) rc = enqueue_lagrange_quotient(ctx, s, s.stage.dev(), lg, z, y);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "lagrange quotient");
+    if (rc) return rc;
+    const uint32_t* hs = s.small.host();
+    if (!(hs[0] & 1u)) {  // every value equals f_0: a constant polynomial, whose quotient is zero when the claim holds
+        if (std::memcmp(hs + 16, y, 32) != 0) return KZG_ERR_CONSTANT_POLY;
+    } else if (std::memcmp(hs + 8, y, 32) != 0) {
+        return KZG_ERR_REMAINDER;
+    }
+    rc = copy_unlocked(ctx, lk, s.stream, out_q_evals, s.q.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient values)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "lagrange quotient");
+    return rc;
 }
 
 // ---- recovery of every cell and proof from part of the cells (recover_kernels.hip) -----------------
@@ -4708,6 +5050,185 @@ int kzg_g1_uncompress_batch(kzg_ctx* ctx, const uint8_t* in48, size_t n, int che
     return KZG_OK;
 }
 
+// ---- a Lagrange basis given as compressed points ---------------------------------------------------
+// n x 48 bytes -> n affine records in natural order at aff (device), decoded on the device with the subgroup check always on;
+// bit-reversed input: record i is point brp(i) of the input.  wire: n x 48 bytes, src: n words (bit-reversed order only), err:
+// kVcErrWords words, dglv: n Glv records, g1: n XYZZ records.  Enqueues only; *herr receives the error words once st is waited for.
+static int lagrange_enqueue_decode(kzg_ctx* ctx, hipStream_t st, const uint8_t* in48, size_t n, uint32_t lg, bool bit_reversed, void* wire,
+                                   uint32_t* src, std::vector<uint32_t>& h_src, uint32_t* err, void* dglv, void* g1, void* aff,
+                                   uint32_t herr[kVcErrWords]) {
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kVcErrWords * 4, st));
+    HIP_TRY(ctx, hipMemcpyAsync(wire, in48, n * 48, hipMemcpyHostToDevice, st));
+    if (bit_reversed) {
+        h_src.resize(n);
+        for (size_t i = 0; i < n; i++) h_src[i] = lagrange_brp((uint32_t)i, lg);
+        HIP_TRY(ctx, hipMemcpyAsync(src, h_src.data(), n * 4, hipMemcpyHostToDevice, st));
+    }
+    launch_wire_g1(st, wire, bit_reversed ? src : nullptr, (uint32_t)n, aff, (uint32_t)kAffineBytes, err + kVcErrWireProof);
+    HIP_TRY(ctx, hipMemsetAsync(dglv, 0, n * sizeof(Glv), st));  // the ladder's membership test with a weight of zero
+    launch_vc_ladder(st, aff, nullptr, (const Glv*)dglv, (uint32_t)n, (uint32_t)n, (uint32_t)n, g1, g1, err);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(herr, err, kVcErrWords * 4, hipMemcpyDeviceToHost, st));
+    return KZG_OK;
+}
+// the verdict on the decoded points: the input index of a point that does not decode or lies outside G1
+static int lagrange_decode_verdict(kzg_ctx* ctx, const uint32_t herr[kVcErrWords], uint32_t lg, bool bit_reversed, size_t* bad_index) {
+    const uint32_t enc = herr[kVcErrWireProof];  // an input index already
+    uint32_t grp = std::min(herr[kVcErrCurve], herr[kVcErrG1]);  // a record index: natural order
+    if (grp != 0xffffffffu && bit_reversed) grp = lagrange_brp(grp, lg);
+    if (enc == 0xffffffffu && grp == 0xffffffffu) return KZG_OK;
+    const uint32_t bad = std::min(enc, grp);
+    if (bad_index) *bad_index = bad;
+    ctx->last_error = "lagrange basis: point " + std::to_string(bad) + (bad == enc ? " is not a valid compressed point" : " is not in G1");
+    return KZG_ERR_INVALID_ARG;
+}
+
+int kzg_lagrange_load_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, unsigned order, int check, size_t* bad_index,
+                                 int* consistent) {
+    uint32_t lg = 0;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (consistent) *consistent = 0;
+    if (!ctx || !in48 || !ntt_log(n, &lg) || order > KZG_ORDER_BIT_REVERSED || (check && !consistent)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_lagrange_load_compressed(kid, in48, n, order, check, bad_index, consistent)) : rc;
+    }
+    const bool bit_reversed = order == KZG_ORDER_BIT_REVERSED;
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf tab;
+    const uint64_t gen = ctx->srs_gen;
+    {
+        const int slot = reserve_slot(ctx, lk, true);  // (keeps an SRS replacement out while ctx->mu is released below)
+        if (slot < 0) return KZG_ERR_BUSY;
+        SlotLease lease{ctx, slot};
+        Slot& s = ctx->slots[slot];
+        const hipStream_t st = s.stream;
+        DevBuf wire, src, err, dglv, g1, prefix;
+        int rc = tab.reserve(ctx, (size_t)ctx->cfg.W * n * kAffineBytes);
+        if (rc == KZG_OK) rc = wire.reserve(ctx, n * 48);
+        if (rc == KZG_OK) rc = src.reserve(ctx, n * 4);
+        if (rc == KZG_OK) rc = err.reserve(ctx, kVcErrWords * 4);
+        if (rc == KZG_OK) rc = dglv.reserve(ctx, n * sizeof(Glv));
+        if (rc == KZG_OK) rc = g1.reserve(ctx, n * kXyzzBytes);
+        if (rc == KZG_OK) rc = prefix.reserve(ctx, n * 64);
+        if (rc) return rc;
+        std::vector<uint32_t> h_src;
+        uint32_t herr[kVcErrWords];
+        rc = lagrange_enqueue_decode(ctx, st, in48, n, lg, bit_reversed, wire.p, src.dev(), h_src, err.dev(), dglv.p, g1.p, tab.p, herr);
+        if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, st, "lagrange basis");
+        if (rc == KZG_OK) rc = lagrange_decode_verdict(ctx, herr, lg, bit_reversed, bad_index);
+        if (rc) return rc;
+        lagrange_enqueue_levels(ctx, st, tab.p, n, g1.p, prefix.p);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = sync_unlocked(ctx, lk, st, "lagrange basis");
+        if (rc) return rc;
+        if (check) {
+            // sum_i rho_i L_i against sum_j (inverse NTT of rho)_j SRS[j] for n weights of 128 random bits: two MSMs through
+            // the slot, the first over the given table.  The weights are read as blst_fr images on both sides (the transform is
+            // linear, so the factor 2^-256 they then carry is common to both).
+            std::vector<uint64_t> rho(4 * n, 0);
+            std::vector<uint64_t> r128(2 * n);
+            if (!vc_random(r128.data(), r128.size() * 8)) {
+                ctx->last_error = "lagrange basis: getrandom failed";
+                return KZG_ERR_HIP;
+            }
+            for (size_t i = 0; i < n; i++) {
+                rho[4 * i] = r128[2 * i];
+                rho[4 * i + 1] = r128[2 * i + 1];
+            }
+            rc = lagrange_slot_ready(ctx, s, n, lg);
+            if (rc) return rc;
+            uint32_t* d_rho = ntt_slot_input(s, lg);
+            rc = copy_unlocked(ctx, lk, st, d_rho, rho.data(), n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (weights)");
+            if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, st, "lagrange basis");  // rho is pageable host memory
+            if (rc) return rc;
+            uint64_t sides[2][18];
+            const MsmBasis given{tab.p, (uint32_t)n};
+            rc = submit_commit_locked(ctx, slot, d_rho, 1, n, true, true, &given);
+            if (rc) return rc;
+            await_unlocked(lk, s);
+            rc = wait_locked(ctx, slot, sides[0]);
+            if (rc) return rc;
+            s.kind = SLOT_RESERVED;  // (wait_locked marked the slot idle; it stays this call's)
+            rc = ntt_into_stage(ctx, s, d_rho, lg, true);
+            if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true);
+            if (rc) return rc;
+            await_unlocked(lk, s);
+            rc = wait_locked(ctx, slot, sides[1]);
+            if (rc) return rc;
+            s.kind = SLOT_RESERVED;
+            *consistent = std::memcmp(sides[0], sides[1], sizeof sides[0]) == 0 ? 1 : 0;
+            if (!*consistent) return KZG_OK;  // not adopted
+        }
+    }
+    return lagrange_adopt(ctx, lk, tab, n, gen);
+}
+
+int kzg_srs_load_lagrange_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, unsigned order, size_t* bad_index) {
+    uint32_t lg = 0;
+    if (bad_index) *bad_index = (size_t)-1;
+    if (!ctx || !in48 || !ntt_log(n, &lg) || order > KZG_ORDER_BIT_REVERSED) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        ctx->last_error = "kzg_srs_load_lagrange_compressed takes a single-device context: load the monomial form it returns "
+                          "(kzg_srs_read_g1) into a multi-device one";
+        return KZG_ERR_INVALID_ARG;
+    }
+    const bool bit_reversed = order == KZG_ORDER_BIT_REVERSED;
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TmpStream st;
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    int rc = ensure_glv(ctx, lk, lg, st.s);  // (releases ctx->mu while it waits: before the quiesce)
+    if (rc) return rc;
+    quiesce(ctx, lk);
+    // decode first: a malformed input leaves the context as it was
+    DevBuf aff, wire, src, err, dglv, x1, x2, x3, prefix;
+    rc = aff.reserve(ctx, n * kAffineBytes);
+    if (rc == KZG_OK) rc = wire.reserve(ctx, n * 48);
+    if (rc == KZG_OK) rc = src.reserve(ctx, n * 4);
+    if (rc == KZG_OK) rc = err.reserve(ctx, kVcErrWords * 4);
+    if (rc == KZG_OK) rc = dglv.reserve(ctx, n * sizeof(Glv));
+    if (rc == KZG_OK) rc = x1.reserve(ctx, n * kXyzzBytes);
+    if (rc == KZG_OK) rc = x2.reserve(ctx, n * kXyzzBytes);
+    if (rc == KZG_OK) rc = x3.reserve(ctx, n * kXyzzBytes);
+    if (rc == KZG_OK) rc = prefix.reserve(ctx, n * 64);
+    if (rc) return rc;
+    std::vector<uint32_t> h_src;
+    uint32_t herr[kVcErrWords];
+    rc = lagrange_enqueue_decode(ctx, st.s, in48, n, lg, bit_reversed, wire.p, src.dev(), h_src, err.dev(), dglv.p, x1.p, aff.p, herr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st.s));
+    rc = lagrange_decode_verdict(ctx, herr, lg, bit_reversed, bad_index);
+    if (rc) return rc;
+    // SRS[j] = sum_i w^(ij) L_i: the forward G1 DFT into level 0, then the normal ingest path
+    rc = srs_prepare(ctx, n);
+    if (rc) return rc;
+    launch_affine_to_xyzz(st.s, aff.p, n, x1.p);
+    const void* res = launch_g1_dft(st.s, x1.p, x2.p, x3.p, lg, 1, (const Glv*)ctx->glv.p, ctx->glv_log, false);
+    launch_xyzz_to_affine(st.s, res, (uint32_t)n, ctx->table.p, prefix.p);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = finish_srs_from_level0(ctx, st.s, n);
+    if (rc) return rc;
+    // the decoded points are the Lagrange basis of the new setup
+    DevBuf tab;
+    rc = tab.reserve(ctx, (size_t)ctx->cfg.W * n * kAffineBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(tab.p, aff.p, n * kAffineBytes, hipMemcpyDeviceToDevice, st.s));
+    lagrange_enqueue_levels(ctx, st.s, tab.p, n, x1.p, prefix.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st.s));
+    std::swap(ctx->lag_table.p, tab.p);
+    std::swap(ctx->lag_table.cap, tab.cap);
+    ctx->lag_n = n;
+    return KZG_OK;
+}
+
 int kzg_fr_from_bytes_batch(kzg_ctx* ctx, const uint8_t* in32_be, size_t n, uint64_t* out_fr_mont, size_t* bad_index) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
     if (bad_index) *bad_index = (size_t)-1;
@@ -5875,6 +6396,9 @@ int kzg_srs_update(kzg_ctx* ctx, const uint8_t tau_be[32], uint64_t first) {
     for (auto& s : ctx->slots) s.kind = SLOT_IDLE;
     ctx->fk20_B.reset();  // the FK20 cache holds transforms of the old SRS
     ctx->fk20_tab.reset();
+    ctx->lag_table.reset();  // ... and so is the Lagrange basis (nothing in flight reads it: drained above, ctx->mu held since)
+    ctx->lag_n = 0;
+    ctx->srs_gen++;
     rc = hipMemcpyAsync(ctx->table.p, d_new.p, n * kAffineBytes, hipMemcpyDeviceToDevice, st.s) == hipSuccess ? KZG_OK : KZG_ERR_HIP;
     if (rc == KZG_OK) rc = build_tables(ctx, st.s, d_xyzz.p, d_prefix.p);
     else ctx->last_error = "kzg_srs_update: copying the new points into the table failed";

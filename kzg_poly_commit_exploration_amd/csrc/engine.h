@@ -301,6 +301,18 @@ inline uint32_t bary_tiles(uint32_t log_n) { return (uint32_t)((((uint64_t)1 << 
 void launch_bary(hipStream_t s, const uint32_t* d_evals, uint32_t log_n, uint32_t batch, const Fr30* d_zs, const void* d_tw,
                  const Fr30& inv_n, uint32_t* d_partial, uint32_t* d_out);
 
+// ---- lagrange_kernels.hip: the quotient of an opening taken on the values ---------------------------
+constexpr uint32_t kLagTile = 1024;          // indices per workgroup: one Fr inversion each
+constexpr uint32_t kLagPartialWords = 24;    // a tile's record: nine digits of each of its two sums, the index where z = w^i, a flag
+inline uint32_t lagrange_tiles(uint32_t log_n) { return (uint32_t)((((uint64_t)1 << log_n) + kLagTile - 1) / kLagTile); }
+// d_q[i] = (y - f_i) / (z - w^i) (2^log_n canonical values; the entry with w^i = z from the others) for P given by its 2^log_n
+// values at d_evals; z, inv_n = 1 / n in multiplier form, y as the digits of its blst_fr image; d_tw: the context's four NTT
+// twiddle tables (forward lo, hi, inverse lo, hi); d_partial: lagrange_tiles(log_n) records of kLagPartialWords words; d_flags:
+// the job's 64 flag words, zero at launch: [0] = some value differs from f_0, [8..15] = P(z), [16..23] = f_0.
+// d_q may not alias d_evals.
+void launch_lagrange_quotient(hipStream_t s, const uint32_t* d_evals, uint32_t log_n, const Fr30& z, const Fr30& y, const Fr30& inv_n,
+                              const void* d_tw, uint32_t* d_q, uint32_t* d_partial, uint32_t* d_flags);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

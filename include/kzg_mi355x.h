@@ -423,6 +423,44 @@ int kzg_lagrange_load_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, un
  * context as it was.  Single-device contexts only (KZG_ERR_INVALID_ARG otherwise) */
 int kzg_srs_load_lagrange_compressed(kzg_ctx* ctx, const uint8_t* in48, size_t n, unsigned order, size_t* bad_index);
 
+/* ---- grand products: the running product of a permutation argument --------------------------------
+ * t numerator columns a_j and t denominator columns b_j of n values each.  With A_i = prod_j a_j[i] and B_i = prod_j b_j[i]:
+ *     z_0 = 1,   z_(i+1) = z_i A_i / B_i   (i < n),   last = z_n.
+ * Computed as z_i = (prod_{k<i} A_k) (prod_{k>=i} B_k) / (prod_k B_k): two product scans and ONE field inversion per call.
+ * Column j starts at base + 4 j stride u64 (stride >= n, in blst_fr, the kzg_commit_lagrange_batch convention); every scalar is
+ * a blst_fr image, outputs fully reduced; z_0 is exactly the image of one.  1 <= t <= KZG_GP_MAX_COLUMNS, 1 <= n <=
+ * 2^KZG_NTT_MAX_LOG, else KZG_ERR_INVALID_ARG.  A zero numerator is legal (z is zero after it, last = 0).  A zero denominator
+ * B_i -> KZG_ERR_INVALID_ARG with *bad_index the least such i ((size_t)-1 otherwise; bad_index may be NULL), kzg_last_error names
+ * it, and the outputs are unspecified.
+ * The permutation form (n a power of two, else KZG_ERR_INVALID_ARG; w = kzg_domain_root(log2 n), natural order) takes wire
+ * columns f_j, permutation columns sigma_j -- sigma_j[i] is the label k_j' w^i' of the cell that (j, i) maps to --, the t coset
+ * shifts k_j and the challenges beta, gamma:  a_j[i] = f_j[i] + beta k_j w^i + gamma,  b_j[i] = f_j[i] + beta sigma_j[i] + gamma.
+ * The a_j, b_j are formed in registers, never stored.
+ * The host-pointer forms are synchronous, need no SRS and run on devices[0] of a multi-device context. */
+#define KZG_GP_MAX_COLUMNS 16
+/* out_z: n blst_fr (z_0 .. z_(n-1)); out_last: z_n */
+int kzg_grand_product(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_z,
+                      uint64_t out_last[4], size_t* bad_index);
+/* the same on kzg_dev_alloc buffers of the context's GPU (single-device contexts); d_out_z may overlap neither input
+ * (KZG_ERR_INVALID_ARG); returns when z is in d_out_z, so that kzg_commit_lagrange_submit(slot, d_out_z, n) can follow */
+int kzg_grand_product_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_z,
+                             uint64_t out_last[4], size_t* bad_index);
+/* the permutation form; shifts: t blst_fr */
+int kzg_permutation_product(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
+                            const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
+                            uint64_t out_last[4], size_t* bad_index);
+/* ... on device buffers, as kzg_grand_product_device; shifts, beta, gamma stay host pointers */
+int kzg_permutation_product_device(kzg_ctx* ctx, const void* d_wires, const void* d_sigmas, size_t n, size_t t, size_t stride,
+                                   const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], void* d_out_z,
+                                   uint64_t out_last[4], size_t* bad_index);
+/* upload -> z -> its commitment over the Lagrange basis of the n-domain, on one slot: out_p1 equals kzg_commit_lagrange of the
+ * same z bit for bit.  out_z may be NULL.  Builds the basis on first use; statuses and multi-device rules of
+ * kzg_commit_lagrange (no SRS -> KZG_ERR_NO_SRS, n > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH, a range-split context ->
+ * KZG_ERR_INVALID_ARG) */
+int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
+                           const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
+                           uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index);
+
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
  * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what

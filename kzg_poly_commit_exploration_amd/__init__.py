@@ -18,7 +18,7 @@ import numpy as np
 __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
-    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "domain_root",
+    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "domain_root",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "kzg_lagrange_prepare", "kzg_lagrange_len", "kzg_lagrange_read_g1", "kzg_lagrange_load_compressed",
     "kzg_srs_load_lagrange_compressed", "kzg_commit_lagrange", "kzg_commit_lagrange_submit", "kzg_commit_lagrange_batch",
     "kzg_open_lagrange", "kzg_open_lagrange_submit", "kzg_quotient_lagrange",
+    "kzg_grand_product", "kzg_grand_product_device", "kzg_permutation_product", "kzg_permutation_product_device",
+    "kzg_permutation_commit",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -81,6 +83,7 @@ KZG_MAX_COMBINE = 256
 KZG_MAX_SETS = 8
 KZG_MAX_SET_POINTS = 16
 KZG_NTT_MAX_LOG = 22
+KZG_GP_MAX_COLUMNS = 16  # columns per side of a grand product
 KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
@@ -189,6 +192,11 @@ def load_library():
         "kzg_open_lagrange": (i, [vp, vp, sz, vp, vp, vp]),
         "kzg_open_lagrange_submit": (i, [vp, i, vp, sz, vp, vp]),
         "kzg_quotient_lagrange": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_grand_product": (i, [vp, vp, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_grand_product_device": (i, [vp, vp, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_permutation_product": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_permutation_product_device": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_permutation_commit": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1227,6 +1235,72 @@ class Engine:
         out = np.zeros_like(a)
         _check(self._lib.kzg_quotient_lagrange(self._h, _ptr(a), a.shape[0], _ptr(zl), _ptr(yl), _ptr(out)), self._h)
         return out
+
+    # -- grand products: z_0 = 1, z_(i+1) = z_i A_i / B_i with one inversion per call --
+    @staticmethod
+    def _columns(cols, n):
+        """(t, stride, 4) array (or a list of (stride, 4) arrays) -> the flat array, t, stride, n"""
+        a = np.ascontiguousarray(cols, dtype=np.uint64)
+        a = a.reshape(a.shape[0], -1, 4)
+        return a, a.shape[0], a.shape[1], a.shape[1] if n is None else int(n)
+
+    def _gp_status(self, rc, bad):
+        if rc != KZG_OK:
+            e = self._error(rc)
+            e.bad_index = None if bad.value == C.c_size_t(-1).value else int(bad.value)
+            raise e
+
+    def grand_product_limbs(self, nums, dens, n=None):
+        """kzg_grand_product: nums, dens (t, stride, 4) arrays whose first n rows per column count (n=None: all of them).
+        Returns (z, last): z an (n, 4) array, last a (4,) array.  A zero denominator raises KzgError with .bad_index"""
+        a, t, stride, n = self._columns(nums, n)
+        b = np.ascontiguousarray(dens, dtype=np.uint64).reshape(t, stride, 4)
+        z, last, bad = np.zeros((n, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_grand_product(self._h, _ptr(a), _ptr(b), n, t, stride, _ptr(z), _ptr(last), C.byref(bad)), bad)
+        return z, last
+
+    def grand_product_device(self, d_nums, d_dens, n, t, d_out_z, stride=None):
+        """kzg_grand_product_device on kzg_dev_alloc buffers: z lands in d_out_z, returns last"""
+        last, bad = np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_grand_product_device(self._h, C.c_void_p(d_nums), C.c_void_p(d_dens), n, t,
+                                                           n if stride is None else stride, C.c_void_p(d_out_z), _ptr(last),
+                                                           C.byref(bad)), bad)
+        return last
+
+    @staticmethod
+    def _perm_scalars(shifts, beta, gamma, t):
+        sh = np.ascontiguousarray([k.limbs() for k in shifts], dtype=np.uint64).reshape(-1, 4)
+        assert sh.shape[0] == t, "one coset shift per column"
+        return sh, beta.limbs(), gamma.limbs()
+
+    def permutation_product_limbs(self, wires, sigmas, shifts, beta, gamma, n=None):
+        """kzg_permutation_product: wires, sigmas (t, stride, 4) arrays, shifts t Scalars, beta and gamma Scalars -> (z, last)"""
+        a, t, stride, n = self._columns(wires, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        sh, bl, gl = self._perm_scalars(shifts, beta, gamma, t)
+        z, last, bad = np.zeros((n, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_permutation_product(self._h, _ptr(a), _ptr(b), n, t, stride, _ptr(sh), _ptr(bl), _ptr(gl),
+                                                          _ptr(z), _ptr(last), C.byref(bad)), bad)
+        return z, last
+
+    def permutation_product_device(self, d_wires, d_sigmas, n, t, shifts, beta, gamma, d_out_z, stride=None):
+        sh, bl, gl = self._perm_scalars(shifts, beta, gamma, t)
+        last, bad = np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_permutation_product_device(self._h, C.c_void_p(d_wires), C.c_void_p(d_sigmas), n, t,
+                                                                 n if stride is None else stride, _ptr(sh), _ptr(bl), _ptr(gl),
+                                                                 C.c_void_p(d_out_z), _ptr(last), C.byref(bad)), bad)
+        return last
+
+    def permutation_commit(self, wires, sigmas, shifts, beta, gamma, n=None, want_z=True):
+        """kzg_permutation_commit: z and its commitment over the Lagrange basis in one call -> (G1Point, z or None, last)"""
+        a, t, stride, n = self._columns(wires, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        sh, bl, gl = self._perm_scalars(shifts, beta, gamma, t)
+        z = np.zeros((n, 4), dtype=np.uint64) if want_z else None
+        last, out, bad = np.zeros(4, dtype=np.uint64), np.zeros(18, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_permutation_commit(self._h, _ptr(a), _ptr(b), n, t, stride, _ptr(sh), _ptr(bl), _ptr(gl),
+                                                         _ptr(z) if want_z else None, _ptr(last), _ptr(out), C.byref(bad)), bad)
+        return G1Point(out), z, last
 
     # -- device-resident, pipelined --
     def num_slots(self):

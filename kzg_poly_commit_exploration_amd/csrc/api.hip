@@ -236,6 +236,11 @@ struct Slot : SlotQueue {
     // openings from evaluations over the Lagrange basis (kzg_open_lagrange): the tile records of the
     // quotient kernels; the quotient's values go to q
     DevBuf lag_part;
+    // grand products (kzg_grand_product and the permutation forms): the columns of a host-pointer call
+    // (numerators then denominators, packed to stride n), its z, the tile records, and the two results the carry kernel writes
+    // for the host: [0] the least index with a zero denominator, [8..15] z_n
+    DevBuf gp_in, gp_z, gp_part;
+    PinnedBuf gp_flags{PinnedBuf::Mapped};
     // cells of a domain (kzg_cells_and_proofs): P for the whole call in cpoly (read by the sub-batches of every slot the call
     // holds, after cells_ev), the chunk aggregates of the cell quotients in cagg
     DevBuf cpoly, cagg;
@@ -3822,6 +3827,201 @@ int kzg_quotient_lagrange(kzg_ctx* ctx, const uint64_t* evals, size_t n, const u
     rc = copy_unlocked(ctx, lk, s.stream, out_q_evals, s.q.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient values)");
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "lagrange quotient");
     return rc;
+}
+
+// ---- grand products: z_0 = 1, z_(i+1) = z_i A_i / B_i (grand_product_kernels.hip) ---------------------
+// The permutation form's scalars; null for the general form, whose columns are the factors themselves.
+struct GpScalars {
+    const uint64_t *shifts, *beta, *gamma;
+};
+static bool gp_shape_ok(size_t n, size_t t, size_t stride) {
+    return n >= 1 && n <= ((size_t)1 << kNttMaxLog) && t >= 1 && t <= kGpMaxColumns && stride >= n;
+}
+// the slot's buffers for n indices (ctx->mu held, slot reserved); in_bytes: the packed columns of a host-pointer call
+static int gp_slot_ready(kzg_ctx* ctx, Slot& s, size_t n, size_t in_bytes, bool own_z) {
+    int rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
+    if (rc == KZG_OK) rc = s.gp_part.reserve(ctx, (size_t)gp_tiles(n) * kGpPartialWords * 4, s.stream);
+    if (rc == KZG_OK && in_bytes) rc = s.gp_in.reserve(ctx, in_bytes, s.stream);
+    if (rc == KZG_OK && own_z) rc = s.gp_z.reserve(ctx, n * 32, s.stream);
+    return rc;
+}
+// t columns of n values each, column j at src + 4 j stride, packed to stride n at dst (the slot's stream, ctx->mu dropped meanwhile)
+static int gp_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, uint32_t* dst, const uint64_t* src, size_t n, size_t t,
+                     size_t stride) {
+    if (stride == n) return copy_unlocked(ctx, lk, s.stream, dst, src, t * n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (columns)");
+    for (size_t j = 0; j < t; j++) {
+        int rc = copy_unlocked(ctx, lk, s.stream, dst + 8 * j * n, src + 4 * j * stride, n * 32, hipMemcpyHostToDevice,
+                               "hipMemcpyAsync (columns)");
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+// the three kernels on the slot's stream: z into d_z, the results into the slot's gp_flags
+static int gp_enqueue(kzg_ctx* ctx, Slot& s, const uint32_t* d_a, const uint32_t* d_b, size_t n, size_t t, size_t stride,
+                      const GpScalars* perm, uint32_t lg, uint32_t* d_z) {
+    const Fr30 scale = fr30_arg_from_mont256(fr_pow2((uint32_t)(14 * t)));  // 2^(270 + 14 t): t images -> one multiplier
+    auto image = [](const hf::Fr& v) {
+        uint32_t l[8];
+        std::memcpy(l, v.l, 32);
+        return fr30_from_limbs(l);
+    };
+    const GpOut out{d_z, s.gp_part.dev(), s.gp_flags.dev()};
+    if (!perm) {
+        launch_grand_product(s.stream, d_a, d_b, (uint32_t)n, (uint32_t)t, stride, scale, image(hf::kFrOne), out);
+    } else {
+        hf::Fr beta, gamma;
+        std::memcpy(beta.l, perm->beta, 32);
+        std::memcpy(gamma.l, perm->gamma, 32);
+        Fr30 bk[kGpMaxColumns];
+        for (size_t j = 0; j < t; j++) {
+            hf::Fr k;
+            std::memcpy(k.l, perm->shifts + 4 * j, 32);
+            bk[j] = image(hf::fr_mul(beta, k));  // an image: its product with the twiddle (a multiplier) is added to f_j[i]
+        }
+        launch_permutation_product(s.stream, d_a, d_b, lg, (uint32_t)t, stride, bk, fr30_arg_from_mont256(beta), image(gamma),
+                                   ctx->ntt_tw.p, scale, image(hf::kFrOne), out);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// after the stream was waited for: the status of the call, z_n, the index of a zero denominator
+static int gp_result(kzg_ctx* ctx, const Slot& s, uint64_t out_last[4], size_t* bad_index) {
+    const uint32_t* h = s.gp_flags.host();
+    if (bad_index) *bad_index = h[0] == kGpNone ? (size_t)-1 : (size_t)h[0];
+    if (h[0] != kGpNone) {
+        ctx->last_error = "grand product: the denominator at index " + std::to_string(h[0]) + " is zero";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::memcpy(out_last, h + 8, 32);
+    return KZG_OK;
+}
+static int gp_host(kzg_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, size_t t, size_t stride, const GpScalars* perm,
+                   uint32_t lg, uint64_t* out_z, uint64_t out_last[4], size_t* bad_index) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = perm ? ensure_ntt(ctx) : KZG_OK;
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = gp_slot_ready(ctx, s, n, 2 * t * n * 32, true);
+    if (rc) return rc;
+    uint32_t *d_a = s.gp_in.dev(), *d_b = d_a + 8 * t * n;
+    rc = gp_upload(ctx, lk, s, d_a, a, n, t, stride);
+    if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d_b, b, n, t, stride);
+    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, d_a, d_b, n, t, n, perm, lg, s.gp_z.dev());
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out_z, s.gp_z.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (z)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
+    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+}
+static int gp_device(kzg_ctx* ctx, const void* d_a, const void* d_b, size_t n, size_t t, size_t stride, const GpScalars* perm, uint32_t lg,
+                     void* d_out_z, uint64_t out_last[4], size_t* bad_index) {
+    const size_t span = ((t - 1) * stride + n) * 32;  // bytes a column set covers
+    for (const void* in : {d_a, d_b})
+        if ((const char*)d_out_z < (const char*)in + span && (const char*)in < (const char*)d_out_z + n * 32) {
+            ctx->last_error = "grand product: the output overlaps an input";
+            return KZG_ERR_INVALID_ARG;
+        }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = perm ? ensure_ntt(ctx) : KZG_OK;
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    rc = gp_slot_ready(ctx, s, n, 0, false);
+    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, (const uint32_t*)d_a, (const uint32_t*)d_b, n, t, stride, perm, lg, (uint32_t*)d_out_z);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
+    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+}
+
+int kzg_grand_product(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_z,
+                      uint64_t out_last[4], size_t* bad_index) {
+    if (!ctx || !nums || !dens || !out_z || !out_last || !gp_shape_ok(n, t, stride)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_grand_product(kid, nums, dens, n, t, stride, out_z, out_last, bad_index));
+    }
+    return gp_host(ctx, nums, dens, n, t, stride, nullptr, 0, out_z, out_last, bad_index);
+}
+
+int kzg_grand_product_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_z,
+                             uint64_t out_last[4], size_t* bad_index) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !d_nums || !d_dens || !d_out_z || !out_last || !gp_shape_ok(n, t, stride)) return KZG_ERR_INVALID_ARG;
+    return gp_device(ctx, d_nums, d_dens, n, t, stride, nullptr, 0, d_out_z, out_last, bad_index);
+}
+
+int kzg_permutation_product(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
+                            const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
+                            uint64_t out_last[4], size_t* bad_index) {
+    uint32_t lg = 0;
+    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_z || !out_last || !gp_shape_ok(n, t, stride) || !ntt_log(n, &lg))
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_permutation_product(kid, wires, sigmas, n, t, stride, shifts, beta, gamma, out_z, out_last, bad_index));
+    }
+    const GpScalars perm{shifts, beta, gamma};
+    return gp_host(ctx, wires, sigmas, n, t, stride, &perm, lg, out_z, out_last, bad_index);
+}
+
+int kzg_permutation_product_device(kzg_ctx* ctx, const void* d_wires, const void* d_sigmas, size_t n, size_t t, size_t stride,
+                                   const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], void* d_out_z,
+                                   uint64_t out_last[4], size_t* bad_index) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    uint32_t lg = 0;
+    if (!ctx || !d_wires || !d_sigmas || !shifts || !beta || !gamma || !d_out_z || !out_last || !gp_shape_ok(n, t, stride) ||
+        !ntt_log(n, &lg))
+        return KZG_ERR_INVALID_ARG;
+    const GpScalars perm{shifts, beta, gamma};
+    return gp_device(ctx, d_wires, d_sigmas, n, t, stride, &perm, lg, d_out_z, out_last, bad_index);
+}
+
+int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
+                           const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
+                           uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index) {
+    uint32_t lg = 0;
+    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_last || !out_p1 || !gp_shape_ok(n, t, stride) || !ntt_log(n, &lg))
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_permutation_commit(kid, wires, sigmas, n, t, stride, shifts, beta, gamma, out_z, out_last,
+                                                                 out_p1, bad_index))
+                   : rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = lagrange_ensure(ctx, lk, n, lg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_ntt(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};  // (the basis stays until the submit, as for kzg_commit_lagrange)
+    Slot& s = ctx->slots[slot];
+    rc = gp_slot_ready(ctx, s, n, 2 * t * n * 32, false);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
+    if (rc) return rc;
+    // z goes to the slot's staging buffer, where the MSM over the Lagrange basis reads it
+    uint32_t *d_a = s.gp_in.dev(), *d_b = d_a + 8 * t * n;
+    const GpScalars perm{shifts, beta, gamma};
+    rc = gp_upload(ctx, lk, s, d_a, wires, n, t, stride);
+    if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d_b, sigmas, n, t, stride);
+    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, d_a, d_b, n, t, n, &perm, lg, s.stage.dev());
+    if (rc == KZG_OK && out_z)
+        rc = copy_unlocked(ctx, lk, s.stream, out_z, s.stage.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (z)");
+    MsmBasis basis{};
+    if (rc == KZG_OK && !lagrange_basis(ctx, n, &basis)) rc = KZG_ERR_NO_SRS;
+    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true, &basis);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    rc = wait_locked(ctx, slot, out_p1);
+    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
 }
 
 // ---- recovery of every cell and proof from part of the cells (recover_kernels.hip) -----------------

@@ -313,6 +313,30 @@ inline uint32_t lagrange_tiles(uint32_t log_n) { return (uint32_t)((((uint64_t)1
 void launch_lagrange_quotient(hipStream_t s, const uint32_t* d_evals, uint32_t log_n, const Fr30& z, const Fr30& y, const Fr30& inv_n,
                               const void* d_tw, uint32_t* d_q, uint32_t* d_partial, uint32_t* d_flags);
 
+// ---- grand_product_kernels.hip: z_0 = 1, z_(i+1) = z_i A_i / B_i with one inversion per call ----------
+constexpr uint32_t kGpTile = 1024;           // consecutive indices per workgroup: 256 lanes x a run of 4
+constexpr uint32_t kGpCarryThreads = 256;    // lanes of the carry kernel's one workgroup: <= 16 consecutive tiles each
+constexpr uint32_t kGpPartialWords = 24;     // a tile's record: the digits of its product of A, then of B, the least index with B_i = 0
+constexpr uint32_t kGpMaxColumns = 16;       // KZG_GP_MAX_COLUMNS
+constexpr uint32_t kGpNone = 0xffffffffu;    // "no zero denominator"
+inline uint32_t gp_tiles(size_t n) { return (uint32_t)((n + kGpTile - 1) / kGpTile); }
+// The arguments both forms share.  d_z: n canonical blst_fr, may alias no input; d_partial: gp_tiles(n) records of
+// kGpPartialWords words; d_flags: 16 words the carry kernel writes: [0] = the least i with B_i = 0 or kGpNone, [8..15] = z_n.
+// scale: 2^(14 t) in multiplier form (takes a product of t images into multiplier form); img_one: the digits of the image of one.
+struct GpOut {
+    uint32_t* d_z;
+    uint32_t* d_partial;
+    uint32_t* d_flags;
+};
+// A_i = prod_j nums[i + j stride], B_i = prod_j dens[i + j stride] (t columns of n blst_fr each, stride in blst_fr)
+void launch_grand_product(hipStream_t s, const uint32_t* d_nums, const uint32_t* d_dens, uint32_t n, uint32_t t, size_t stride,
+                          const Fr30& scale, const Fr30& img_one, const GpOut& out);
+// A_i = prod_j (f_j[i] + bk[j] w^i + gamma), B_i = prod_j (f_j[i] + beta sigma_j[i] + gamma) over the 2^log_n-domain.  bk: the t
+// products beta k_j and gamma as the digits of their blst_fr images, beta in multiplier form; d_tw: the forward NTT twiddles.
+void launch_permutation_product(hipStream_t s, const uint32_t* d_wires, const uint32_t* d_sigmas, uint32_t log_n, uint32_t t,
+                                size_t stride, const Fr30* bk, const Fr30& beta, const Fr30& gamma, const void* d_tw,
+                                const Fr30& scale, const Fr30& img_one, const GpOut& out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

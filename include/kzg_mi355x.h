@@ -461,6 +461,61 @@ int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* 
                            const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
                            uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index);
 
+/* ---- the quotient of a permutation argument on a coset ------------------------------------------------
+ * n = 2^k, H = <w_n> (w_n = kzg_domain_root(k)), e = 2^x with x <= KZG_PQ_MAX_LOG_EXT, N = e n <= 2^KZG_NTT_MAX_LOG.  The coset
+ * points are x_i = g w_N^i with g = 7, in natural order (the coset kzg_recover_cells_and_proofs works on).  With t wire columns
+ * f_j, t permutation columns sigma_j, shifts k_j, the accumulator z of kzg_permutation_product (z(w^i) = z_i, z_0 = 1) and the
+ * challenges alpha, beta, gamma:
+ *     Num(X) = G(X) + alpha   [ z(X) prod_j (f_j(X) + beta k_j X + gamma)  -  z(w X) prod_j (f_j(X) + beta sigma_j(X) + gamma) ]
+ *                   + alpha^2 (z(X) - 1) L_0(X),              L_0(X) = (X^n - 1) / (n (X - 1)),
+ *     T(X)   = Num(X) / (X^n - 1).
+ * G is the caller's own term (gates, public inputs, lookups) as N values on the coset, or NULL for 0.  On the coset z(w x_i) is
+ * z's value at index (i + e) mod N, and Z_H(x_i) = g^n w_e^(i mod e) - 1 takes e values, never zero.  With every column of degree
+ * < n, deg Num <= (t + 1)(n - 1): e >= t + 1, so t <= KZG_PQ_MAX_COLUMNS.  Num is divisible by X^n - 1 exactly when the
+ * interpolant of Num(x_i) / Z_H(x_i) has zero coefficients at [N - n, N); a non-zero one there -> KZG_ERR_REMAINDER (the
+ * constraints do not hold on H), kzg_last_error says so, and the outputs are unspecified.
+ * Every scalar is a blst_fr image, outputs fully reduced; columns follow the stride convention of kzg_grand_product (column j at
+ * base + 4 j stride u64).  The host-pointer forms are synchronous; those that need no SRS run on devices[0] of a multi-device
+ * context.  The _device forms take kzg_dev_alloc buffers of a single-device context, return when the output is written, and
+ * their output may overlap no input (KZG_ERR_INVALID_ARG).  n = 1 is legal everywhere. */
+#define KZG_PQ_MAX_COLUMNS 7
+#define KZG_PQ_MAX_LOG_EXT 3
+#define KZG_EXTEND_VALUES 0 /* len = 2^k values over the len-domain */
+#define KZG_EXTEND_COEFFS 1 /* any 1 <= len <= N coefficients (e.g. a blinded polynomial of degree >= n) */
+/* `batch` columns of len entries (column b at in + 4 b stride, stride >= len) -> their N = 2^log_out values on the coset, column
+ * b at out + 4 b N.  len <= N (len = N: a plain coset transform).  Needs no SRS.  Anything else -> KZG_ERR_INVALID_ARG */
+int kzg_coset_extend(kzg_ctx* ctx, const uint64_t* in, size_t len, size_t batch, size_t stride, unsigned form, unsigned log_out,
+                     uint64_t* out);
+int kzg_coset_extend_device(kzg_ctx* ctx, const void* d_in, size_t len, size_t batch, size_t stride, unsigned form,
+                            unsigned log_out, void* d_out);
+/* out[i] = Num(x_i) / Z_H(x_i), i < N = rot n, from the columns' N values on the coset (wires_ext / sigmas_ext: t columns, stride
+ * >= N; z_ext, gate_coset, out: N values; gate_coset may be NULL).  n and rot = N / n are given apart from the columns' degrees,
+ * so that columns extended from KZG_EXTEND_COEFFS (blinded, rot = 8) go through the same call.  1 <= t, t + 1 <= rot <= 8. */
+int kzg_permutation_constraints_coset(kzg_ctx* ctx, const uint64_t* wires_ext, const uint64_t* sigmas_ext, const uint64_t* z_ext,
+                                      size_t n, size_t rot, size_t t, size_t stride, const uint64_t* shifts, const uint64_t alpha[4],
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t* gate_coset, uint64_t* out);
+int kzg_permutation_constraints_coset_device(kzg_ctx* ctx, const void* d_wires_ext, const void* d_sigmas_ext, const void* d_z_ext,
+                                             size_t n, size_t rot, size_t t, size_t stride, const uint64_t* shifts,
+                                             const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                             const void* d_gate_coset, void* d_out);
+/* N values of any Num on the coset -> the N - n coefficients of Num / (X^n - 1) (N / n = 2^x, x <= 3; n = N: none).
+ * already_divided != 0: the values are Num(x_i) / Z_H(x_i) already (what the call above returns).  KZG_ERR_REMAINDER as above */
+int kzg_vanishing_quotient(kzg_ctx* ctx, const uint64_t* num_coset, size_t N, size_t n, int already_divided, uint64_t* out_coeffs);
+int kzg_vanishing_quotient_device(kzg_ctx* ctx, const void* d_num_coset, size_t N, size_t n, int already_divided,
+                                  void* d_out_coeffs);
+/* The whole step on one slot: wires, sigmas (t columns of n values, stride >= n) and z (n values) are extended to N = 2^log_ext n
+ * points, the constraints are evaluated and divided, and T comes back as out_coeffs (NULL, or N - n coefficients) and as the
+ * commitments of its chunks of n coefficients, out_p1s (NULL, or (2^log_ext - 1) x 18 u64): chunk c = coefficients
+ * [c n, (c + 1) n), committed over the monomial SRS, bit for bit kzg_commit of that chunk.  gate_coset: NULL or N values.
+ * Nothing but the inputs and the outputs asked for crosses PCIe.
+ * KZG_ERR_INVALID_ARG: n not a power of two, N > 2^KZG_NTT_MAX_LOG, t = 0, t + 1 > 2^log_ext, log_ext > KZG_PQ_MAX_LOG_EXT,
+ * stride < n, a NULL required pointer.  With out_p1s: no SRS -> KZG_ERR_NO_SRS, n > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH, and
+ * kzg_commit_lagrange's multi-device rules (a replicated context forwards, a range-split one -> KZG_ERR_INVALID_ARG). */
+int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* z, size_t n, size_t t,
+                             size_t stride, const uint64_t* shifts, const uint64_t alpha[4], const uint64_t beta[4],
+                             const uint64_t gamma[4], const uint64_t* gate_coset, unsigned log_ext, uint64_t* out_coeffs,
+                             uint64_t* out_p1s);
+
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
  * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what

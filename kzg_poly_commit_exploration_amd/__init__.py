@@ -18,7 +18,8 @@ import numpy as np
 __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
-    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "domain_root",
+    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS",
+    "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
@@ -73,6 +74,8 @@ ABI_SYMBOLS = [
     "kzg_open_lagrange", "kzg_open_lagrange_submit", "kzg_quotient_lagrange",
     "kzg_grand_product", "kzg_grand_product_device", "kzg_permutation_product", "kzg_permutation_product_device",
     "kzg_permutation_commit",
+    "kzg_coset_extend", "kzg_coset_extend_device", "kzg_permutation_constraints_coset", "kzg_permutation_constraints_coset_device",
+    "kzg_vanishing_quotient", "kzg_vanishing_quotient_device", "kzg_permutation_quotient",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -84,6 +87,9 @@ KZG_MAX_SETS = 8
 KZG_MAX_SET_POINTS = 16
 KZG_NTT_MAX_LOG = 22
 KZG_GP_MAX_COLUMNS = 16  # columns per side of a grand product
+KZG_PQ_MAX_COLUMNS = 7   # wire columns of a permutation quotient (t + 1 <= 2^KZG_PQ_MAX_LOG_EXT)
+KZG_PQ_MAX_LOG_EXT = 3
+KZG_EXTEND_VALUES, KZG_EXTEND_COEFFS = 0, 1
 KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
@@ -197,6 +203,13 @@ def load_library():
         "kzg_permutation_product": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_permutation_product_device": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_permutation_commit": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_coset_extend": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp]),
+        "kzg_coset_extend_device": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp]),
+        "kzg_permutation_constraints_coset": (i, [vp, vp, vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]),
+        "kzg_permutation_constraints_coset_device": (i, [vp, vp, vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]),
+        "kzg_vanishing_quotient": (i, [vp, vp, sz, sz, i, vp]),
+        "kzg_vanishing_quotient_device": (i, [vp, vp, sz, sz, i, vp]),
+        "kzg_permutation_quotient": (i, [vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1301,6 +1314,76 @@ class Engine:
         self._gp_status(self._lib.kzg_permutation_commit(self._h, _ptr(a), _ptr(b), n, t, stride, _ptr(sh), _ptr(bl), _ptr(gl),
                                                          _ptr(z) if want_z else None, _ptr(last), _ptr(out), C.byref(bad)), bad)
         return G1Point(out), z, last
+
+    # -- the quotient of a permutation argument on the coset 7 H_N --
+    def _pq_check(self, rc):
+        if rc != KZG_OK:
+            raise self._error(rc)  # with kzg_last_error: it says which constraint or argument the status is about
+
+    def coset_extend_limbs(self, cols, log_out, form=KZG_EXTEND_VALUES, n=None):
+        """kzg_coset_extend: cols a (batch, stride, 4) array whose first n rows per column count (n=None: all) -> (batch, N, 4)"""
+        a, batch, stride, n = self._columns(cols, n)
+        out = np.zeros((batch, 1 << log_out, 4), dtype=np.uint64)
+        self._pq_check(self._lib.kzg_coset_extend(self._h, _ptr(a), n, batch, stride, form, log_out, _ptr(out)))
+        return out
+
+    def coset_extend_device(self, d_in, n, batch, log_out, d_out, form=KZG_EXTEND_VALUES, stride=None):
+        self._pq_check(self._lib.kzg_coset_extend_device(self._h, C.c_void_p(d_in), n, batch, n if stride is None else stride, form, log_out,
+                                                 C.c_void_p(d_out)))
+
+    def _pq_scalars(self, shifts, alpha, beta, gamma, t):
+        sh, bl, gl = self._perm_scalars(shifts, beta, gamma, t)
+        return sh, alpha.limbs(), bl, gl
+
+    def permutation_constraints_coset_limbs(self, wires_ext, sigmas_ext, z_ext, n, shifts, alpha, beta, gamma, gate=None, N=None):
+        """kzg_permutation_constraints_coset: wires_ext, sigmas_ext (t, stride, 4) arrays of values on the coset, z_ext (N, 4)
+        -> Num / Z_H on the coset, an (N, 4) array"""
+        z = np.ascontiguousarray(z_ext, dtype=np.uint64).reshape(-1, 4)
+        a, t, stride, N = self._columns(wires_ext, z.shape[0] if N is None else N)
+        b = np.ascontiguousarray(sigmas_ext, dtype=np.uint64).reshape(t, stride, 4)
+        g = None if gate is None else np.ascontiguousarray(gate, dtype=np.uint64).reshape(N, 4)
+        sh, al, bl, gl = self._pq_scalars(shifts, alpha, beta, gamma, t)
+        out = np.zeros((N, 4), dtype=np.uint64)
+        self._pq_check(self._lib.kzg_permutation_constraints_coset(self._h, _ptr(a), _ptr(b), _ptr(z), n, N // n, t, stride, _ptr(sh), _ptr(al),
+                                                           _ptr(bl), _ptr(gl), None if g is None else _ptr(g), _ptr(out)))
+        return out
+
+    def permutation_constraints_coset_device(self, d_wires, d_sigmas, d_z, n, rot, t, shifts, alpha, beta, gamma, d_out, d_gate=None,
+                                             stride=None):
+        sh, al, bl, gl = self._pq_scalars(shifts, alpha, beta, gamma, t)
+        self._pq_check(self._lib.kzg_permutation_constraints_coset_device(
+            self._h, C.c_void_p(d_wires), C.c_void_p(d_sigmas), C.c_void_p(d_z), n, rot, t, n * rot if stride is None else stride,
+            _ptr(sh), _ptr(al), _ptr(bl), _ptr(gl), C.c_void_p(d_gate), C.c_void_p(d_out)))
+
+    def vanishing_quotient_limbs(self, num_coset, n, already_divided=False):
+        """kzg_vanishing_quotient: N values of Num on the coset -> the (N - n, 4) coefficients of Num / (X^n - 1)"""
+        a = np.ascontiguousarray(num_coset, dtype=np.uint64).reshape(-1, 4)
+        N = a.shape[0]
+        out = np.zeros((max(N - n, 0), 4), dtype=np.uint64)
+        self._pq_check(self._lib.kzg_vanishing_quotient(self._h, _ptr(a), N, n, 1 if already_divided else 0, _ptr(out)))
+        return out
+
+    def vanishing_quotient_device(self, d_num, N, n, d_out, already_divided=False):
+        self._pq_check(self._lib.kzg_vanishing_quotient_device(self._h, C.c_void_p(d_num), N, n, 1 if already_divided else 0,
+                                                       C.c_void_p(d_out)))
+
+    def permutation_quotient(self, wires, sigmas, z, shifts, alpha, beta, gamma, log_ext, gate=None, n=None, want_coeffs=True,
+                             want_commitments=True):
+        """kzg_permutation_quotient: wires, sigmas (t, stride, 4) arrays, z (n, 4) -> (T's coefficients (N - n, 4) or None, the list
+        of its chunks' commitments or None)"""
+        a, t, stride, n = self._columns(wires, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n
+        N = n << log_ext
+        g = None if gate is None else np.ascontiguousarray(gate, dtype=np.uint64).reshape(N, 4)
+        sh, al, bl, gl = self._pq_scalars(shifts, alpha, beta, gamma, t)
+        coeffs = np.zeros((N - n, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros(((1 << log_ext) - 1, 18), dtype=np.uint64) if want_commitments else None
+        self._pq_check(self._lib.kzg_permutation_quotient(self._h, _ptr(a), _ptr(b), _ptr(zz), n, t, stride, _ptr(sh), _ptr(al), _ptr(bl),
+                                                  _ptr(gl), None if g is None else _ptr(g), log_ext,
+                                                  None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
 
     # -- device-resident, pipelined --
     def num_slots(self):

@@ -337,6 +337,12 @@ struct kzg_ctx {
     // the producing side on blob bytes (kzg_blobs_to_cells_and_proofs_bytes): workspaces grown on demand,
     // under fk20_mu (the calls run FK20 from them)
     Workspace<8> blob_ws;
+    // the quotient of a permutation argument (kzg_coset_extend .. kzg_permutation_quotient), under
+    // quotient_mu (taken before mu): workspaces grown on demand; the calls read the g-power tables rec_g, which are built once
+    // and never replaced
+    std::mutex quotient_mu;
+    Workspace<11> pq_ws;
+    uint32_t pq_zinv_key = ~0u;  // (log n << 8) | log rot of the inverses of Z_H held in pq_ws, ~0: none
 };
 
 namespace {
@@ -4629,6 +4635,489 @@ static int vc_check_inputs(kzg_ctx* ctx, const char* what, const uint64_t* weigh
 static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
     if (rc) ctx->last_error = kid->last_error;
     return rc;
+}
+
+// ---- the quotient of a permutation argument on the coset g H_N (quotient_kernels.hip) ---------------------
+// Every call holds quotient_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits.
+namespace {
+enum : int { kPqIn = 0, kPqCols, kPqT, kPqP, kPqA, kPqB, kPqOut, kPqCoef, kPqGate, kPqZinv, kPqFlag, kPqCount };
+constexpr size_t kPqWsBudget = (size_t)1 << 30;    // the four transform buffers of one pass together stay below this ...
+constexpr size_t kPqMaxChunk = 64;                 // ... and hold at most this many columns
+constexpr uint32_t kPqDftLog = kNttTileLog;        // below 2^11 values a batch takes launch_fr_dft, from there on launch_ntt per column
+static_assert(kPqCount <= 11, "pq_ws");
+
+// Declared after the slot's lease, so that it runs first: whatever way a call returns -- also after a failed copy or launch --
+// nothing it enqueued still uses pq_ws when the slot and quotient_mu are given up (a later call may grow, that is free, a
+// workspace).  After a call that ended well the stream is empty and this costs nothing.
+struct PqDrain {
+    const Slot& s;  // the front stream, and the stream a commitment of the chunks ended on
+    ~PqDrain() {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+        if (s.end && s.end != s.stream) (void)hipStreamSynchronize(s.end);
+    }
+};
+
+struct PqShape {
+    uint32_t lg_n = 0, lg_ext = 0, lg_N = 0;
+    size_t n = 0, rot = 0, N = 0;
+};
+// n = 2^k, rot = 2^x with x <= 3, N = rot n <= 2^22
+bool pq_shape(size_t n, size_t rot, PqShape* sh) {
+    uint32_t a = 0, b = 0;
+    if (!ntt_log(n, &a) || !ntt_log(rot, &b) || b > kPqMaxLogExt || a + b > kNttMaxLog) return false;
+    *sh = PqShape{a, b, a + b, n, rot, n * rot};
+    return true;
+}
+Fr30 pq_image(const hf::Fr& v) {
+    uint32_t l[8];
+    std::memcpy(l, v.l, 32);
+    return fr30_from_limbs(l);
+}
+hf::Fr pq_fr(const uint64_t* p) {
+    hf::Fr v;
+    std::memcpy(v.l, p, 32);
+    return v;
+}
+bool pq_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return (const char*)a < (const char*)b + b_bytes && (const char*)b < (const char*)a + a_bytes;
+}
+
+// the transform buffers of one pass: `chunk` columns of N values each
+struct PqBufs {
+    uint32_t *T = nullptr, *P = nullptr, *A = nullptr, *B = nullptr;
+    size_t chunk = 0;
+};
+// ctx->mu held, the caller has waited for every earlier use of the workspaces
+int pq_bufs(kzg_ctx* ctx, size_t N, size_t cols, PqBufs* w) {
+    size_t chunk = kPqWsBudget / (4 * N * 32);
+    chunk = chunk < 1 ? 1 : (chunk > kPqMaxChunk ? kPqMaxChunk : chunk);
+    if (chunk > cols) chunk = cols ? cols : 1;
+    void *t, *p, *a, *b;
+    int rc = ctx->pq_ws.get(ctx, kPqT, chunk * N * 32, &t);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqP, chunk * N * 32, &p);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqA, chunk * N * 32, &a);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqB, chunk * N * 32, &b);
+    *w = PqBufs{(uint32_t*)t, (uint32_t*)p, (uint32_t*)a, (uint32_t*)b, chunk};
+    return rc;
+}
+
+// `cols` columns (column j: len entries at src + 8 j stride words; src null: every entry is *fill) onto the coset of N = 2^lg_N
+// points, column j to dst + 8 j N words.  lg_len >= 0: the entries are values over the domain of 2^lg_len points (inverse
+// transform, twist by g^i / len, padding, forward transform); lg_len < 0: they are coefficients (twist, padding, forward
+// transform).  dst overlaps neither src nor the buffers.
+int pq_extend(kzg_ctx* ctx, hipStream_t st, const uint32_t* src, size_t stride, size_t len, int lg_len, size_t cols, uint32_t lg_N,
+              uint32_t* dst, const PqBufs& w, const Fr30* fill = nullptr) {
+    const size_t N = (size_t)1 << lg_N;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
+    const Fr30* itw = tw + 2 * kNttTableLen;
+    const Fr30* gt = (const Fr30*)ctx->rec_g.p;
+    const Fr30 one = fr30_arg_from_mont256(hf::kFrOne);
+    for (size_t c0 = 0; c0 < cols; c0 += w.chunk) {
+        const size_t bc = cols - c0 < w.chunk ? cols - c0 : w.chunk;
+        const uint32_t* coef = src ? src + 8 * c0 * stride : nullptr;
+        size_t cstride = stride;
+        Fr30 c = one;
+        if (lg_len >= 0) {
+            const Fr30 inv_len = fr30_arg_from_mont256(hf::fr_inv(fr_pow2((uint32_t)lg_len)));
+            if ((uint32_t)lg_len >= kPqDftLog) {  // the last pass multiplies by 1 / len
+                for (size_t b = 0; b < bc; b++)
+                    launch_ntt(st, coef + 8 * b * stride, w.T + 8 * b * len, (uint32_t)lg_len, itw, inv_len, w.A, w.B);
+                coef = w.T;
+            } else {  // one batch of contiguous vectors, unnormalised
+                if (stride != len && bc > 1) {
+                    HIP_TRY(ctx, hipMemcpy2DAsync(w.T, len * 32, coef, stride * 32, len * 32, bc, hipMemcpyDeviceToDevice, st));
+                    coef = w.T;
+                }
+                coef = launch_fr_dft(st, coef, w.A, w.B, (uint32_t)lg_len, bc, itw);
+                c = inv_len;
+            }
+            cstride = len;
+        }
+        launch_pq_pad_twist(st, coef, cstride, (uint32_t)len, fill ? *fill : one, lg_N, bc, gt, c, w.P);
+        if (lg_N >= kPqDftLog) {
+            for (size_t b = 0; b < bc; b++) launch_ntt(st, w.P + 8 * b * N, dst + 8 * (c0 + b) * N, lg_N, tw, one, w.A, w.B);
+        } else {
+            const uint32_t* ev = launch_fr_dft(st, w.P, w.A, w.B, lg_N, bc, tw);
+            HIP_TRY(ctx, hipMemcpyAsync(dst + 8 * c0 * N, ev, bc * N * 32, hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return KZG_OK;
+}
+
+// the rot stored multipliers 1 / Z_H(x_i), Z_H(x_i) = g^n w_rot^(i mod rot) - 1 (never zero: 7 has order r - 1), on the device.
+// They depend on (n, rot) only: the table of the last shape stays (pq_zinv_key), so that a repeated shape costs neither the rot
+// host inversions nor the upload and the wait for it.
+int pq_upload_zinv(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, uint32_t** d_zinv) {
+    void* d = nullptr;
+    int rc = ctx->pq_ws.get(ctx, kPqZinv, 8 * 32, &d);
+    if (rc) return rc;
+    *d_zinv = (uint32_t*)d;
+    const uint32_t key = (sh.lg_n << 8) | sh.lg_ext;
+    if (ctx->pq_zinv_key == key) return KZG_OK;
+    ctx->pq_zinv_key = ~0u;
+    uint64_t h[8][4];
+    const hf::Fr we = hf::fr_domain_root(sh.lg_ext), k14 = fr_pow2(14);
+    hf::Fr cur = hf::fr_pow(fr_seven(), sh.n);
+    for (size_t k = 0; k < sh.rot; k++) {
+        const hf::Fr stored = hf::fr_mul(hf::fr_inv(hf::fr_sub(cur, hf::kFrOne)), k14);  // the x 2^270 form, canonical
+        std::memcpy(h[k], stored.l, 32);
+        cur = hf::fr_mul(cur, we);
+    }
+    rc = copy_unlocked(ctx, lk, st, d, h, sh.rot * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (vanishing inverses)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, st, "quotient");  // (h leaves scope)
+    if (rc == KZG_OK) ctx->pq_zinv_key = key;
+    return rc;
+}
+
+struct PqChallenges {
+    const uint64_t *shifts, *alpha, *beta, *gamma;
+};
+// Num / Z_H on the coset into d_out (N values): the extended columns at d_wires / d_sigmas (column j at + 8 j stride words), d_z,
+// d_gate (or null); the values of L_0 are made in d_l0 here
+int pq_constraints(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, size_t t, size_t stride,
+                   const uint32_t* d_wires, const uint32_t* d_sigmas, const uint32_t* d_z, const uint32_t* d_gate, uint32_t* d_l0,
+                   const PqChallenges& ch, const PqBufs& w, uint32_t* d_out) {
+    uint32_t* d_zinv = nullptr;
+    int rc = pq_upload_zinv(ctx, lk, st, sh, &d_zinv);
+    if (rc) return rc;
+    // L_0 = (1 / n) (1 + X + .. + X^(n-1)): one more extension, from n equal coefficients
+    const Fr30 inv_n = pq_image(hf::fr_inv(fr_pow2(sh.lg_n)));
+    rc = pq_extend(ctx, st, nullptr, 0, sh.n, -1, 1, sh.lg_N, d_l0, w, &inv_n);
+    if (rc) return rc;
+    const hf::Fr alpha = pq_fr(ch.alpha), beta = pq_fr(ch.beta), gamma = pq_fr(ch.gamma), g = fr_seven();
+    const Fr30 f_beta = fr30_arg_from_mont256(beta), f_gamma = pq_image(gamma), f_one = pq_image(hf::kFrOne);
+    const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(alpha, fr_pow2((uint32_t)(14 * t))));
+    const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(alpha, alpha), fr_pow2(14)));
+    Fr30 bkg[kPqMaxColumns];
+    for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(beta, pq_fr(ch.shifts + 4 * j)), g));
+    const PqColumns cols{d_wires, d_sigmas, d_z, d_l0, d_gate, d_zinv};
+    const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
+    launch_pq_constraints(st, cols, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, stride, sc, ctx->ntt_tw.p, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// N values on the coset in d_vals (a workspace: divided in place unless already divided) -> the N - n coefficients of the
+// quotient in d_coef; *d_flag (zeroed here) is set when a coefficient at [N - n, N) is not zero
+int pq_interpolate(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, uint32_t* d_vals, bool divide,
+                   const PqBufs& w, uint32_t* d_coef, uint32_t* d_flag) {
+    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+    const Fr30* ginv = (const Fr30*)ctx->rec_g.p + 2 * kNttTableLen;
+    const Fr30 one = fr30_arg_from_mont256(hf::kFrOne), inv_N = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_N)));
+    if (divide) {
+        uint32_t* d_zinv = nullptr;
+        int rc = pq_upload_zinv(ctx, lk, st, sh, &d_zinv);
+        if (rc) return rc;
+        launch_recover_divide(st, d_vals, sh.lg_N, sh.lg_n, 1, d_zinv);  // by index mod rot
+    }
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 4, st));
+    if (sh.lg_N >= kPqDftLog) {
+        launch_ntt(st, d_vals, w.T, sh.lg_N, itw, inv_N, w.A, w.B);
+        launch_recover_untwist(st, w.T, sh.lg_N, (uint32_t)(sh.N - sh.n), 1, ginv, one, d_coef, false, d_flag);
+    } else {
+        const uint32_t* cur = launch_fr_dft(st, d_vals, w.A, w.B, sh.lg_N, 1, itw);
+        launch_recover_untwist(st, const_cast<uint32_t*>(cur), sh.lg_N, (uint32_t)(sh.N - sh.n), 1, ginv, inv_N, d_coef, false, d_flag);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+int pq_remainder(kzg_ctx* ctx, const PqShape& sh) {
+    ctx->last_error = "quotient: the numerator is not divisible by X^" + std::to_string(sh.n) +
+                      " - 1 (a coefficient of the interpolant at [N - n, N) is not zero): the constraints do not hold on the domain";
+    return KZG_ERR_REMAINDER;
+}
+
+// what every call starts with (quotient_mu held by the caller, lk = ctx->mu held): the tables, a reserved slot with its stream
+int pq_begin(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int* slot) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt(ctx);
+    if (rc == KZG_OK) rc = ensure_recover_g(ctx);
+    if (rc) return rc;
+    *slot = reserve_slot(ctx, lk, true);
+    if (*slot < 0) return KZG_ERR_BUSY;
+    rc = ensure_slot_basics(ctx, ctx->slots[*slot]);  // needs no SRS
+    if (rc) {
+        release_owned(ctx, *slot);
+        *slot = -1;
+    }
+    return rc;
+}
+// t columns of len values, column j at src + 4 j stride, packed to stride len at dst
+int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, uint32_t* dst, const uint64_t* src, size_t len, size_t t,
+              size_t stride) {
+    if (stride == len) return copy_unlocked(ctx, lk, st, dst, src, t * len * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (columns)");
+    for (size_t j = 0; j < t; j++) {
+        int rc = copy_unlocked(ctx, lk, st, dst + 8 * j * len, src + 4 * j * stride, len * 32, hipMemcpyHostToDevice,
+                               "hipMemcpyAsync (columns)");
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+}  // namespace
+
+static int coset_extend_impl(kzg_ctx* ctx, const void* in, size_t len, size_t batch, size_t stride, unsigned form, unsigned log_out,
+                             void* out, bool device) {
+    uint32_t lg_len = 0;
+    if (!ctx || !in || !out || log_out > kNttMaxLog || len < 1 || len > ((size_t)1 << log_out) || batch < 1 || stride < len ||
+        (form != KZG_EXTEND_VALUES && form != KZG_EXTEND_COEFFS) || (form == KZG_EXTEND_VALUES && !ntt_log(len, &lg_len)))
+        return KZG_ERR_INVALID_ARG;
+    const size_t N = (size_t)1 << log_out;
+    if (device && pq_overlap(out, batch * N * 32, in, ((batch - 1) * stride + len) * 32)) {
+        ctx->last_error = "coset extension: the output overlaps the input";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    const int lg = form == KZG_EXTEND_VALUES ? (int)lg_len : -1;
+    if (device) {
+        PqBufs w;
+        rc = pq_bufs(ctx, N, batch, &w);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)in, stride, len, lg, batch, log_out, (uint32_t*)out, w);
+        return rc ? rc : sync_unlocked(ctx, lk, s.stream, "coset extension");
+    }
+    // host pointers: as many columns per round as the budget holds, packed on the way up
+    size_t round = kPqWsBudget / (N * 32);
+    round = round < 1 ? 1 : (round > batch ? batch : round);
+    PqBufs w;
+    void *d_in, *d_out;
+    rc = pq_bufs(ctx, N, round, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqIn, round * len * 32, &d_in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, round * N * 32, &d_out);
+    for (size_t b0 = 0; b0 < batch && rc == KZG_OK; b0 += round) {
+        const size_t bc = batch - b0 < round ? batch - b0 : round;
+        rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_in, (const uint64_t*)in + 4 * b0 * stride, len, bc, stride);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)d_in, len, len, lg, bc, log_out, (uint32_t*)d_out, w);
+        if (rc == KZG_OK)
+            rc = copy_unlocked(ctx, lk, s.stream, (uint64_t*)out + 4 * b0 * N, d_out, bc * N * 32, hipMemcpyDeviceToHost,
+                               "hipMemcpyAsync (extended columns)");
+        if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "coset extension");
+    }
+    return rc;
+}
+
+int kzg_coset_extend(kzg_ctx* ctx, const uint64_t* in, size_t len, size_t batch, size_t stride, unsigned form, unsigned log_out,
+                     uint64_t* out) {
+    if (ctx && ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_coset_extend(kid, in, len, batch, stride, form, log_out, out));
+    }
+    return coset_extend_impl(ctx, in, len, batch, stride, form, log_out, out, false);
+}
+
+int kzg_coset_extend_device(kzg_ctx* ctx, const void* d_in, size_t len, size_t batch, size_t stride, unsigned form, unsigned log_out,
+                            void* d_out) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    return coset_extend_impl(ctx, d_in, len, batch, stride, form, log_out, d_out, true);
+}
+
+static bool pq_constraint_args_ok(kzg_ctx* ctx, const void* wires, const void* sigmas, const void* z, size_t n, size_t rot, size_t t,
+                                  size_t stride, const uint64_t* shifts, const uint64_t* alpha, const uint64_t* beta,
+                                  const uint64_t* gamma, const void* out, PqShape* sh) {
+    return ctx && wires && sigmas && z && shifts && alpha && beta && gamma && out && pq_shape(n, rot, sh) && t >= 1 &&
+           t <= kPqMaxColumns && t + 1 <= rot && stride >= sh->N;
+}
+
+int kzg_permutation_constraints_coset(kzg_ctx* ctx, const uint64_t* wires_ext, const uint64_t* sigmas_ext, const uint64_t* z_ext,
+                                      size_t n, size_t rot, size_t t, size_t stride, const uint64_t* shifts, const uint64_t alpha[4],
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t* gate_coset, uint64_t* out) {
+    PqShape sh;
+    if (!pq_constraint_args_ok(ctx, wires_ext, sigmas_ext, z_ext, n, rot, t, stride, shifts, alpha, beta, gamma, out, &sh))
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_permutation_constraints_coset(kid, wires_ext, sigmas_ext, z_ext, n, rot, t, stride, shifts, alpha,
+                                                                    beta, gamma, gate_coset, out));
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    const size_t N = sh.N;
+    PqBufs w;
+    void *cols, *d_out, *d_gate = nullptr;
+    rc = pq_bufs(ctx, N, 1, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, (2 * t + 2) * N * 32, &cols);  // wires, sigmas, z, L_0
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
+    if (rc == KZG_OK && gate_coset) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc) return rc;
+    uint32_t *d_w = (uint32_t*)cols, *d_s = d_w + 8 * t * N, *d_z = d_s + 8 * t * N, *d_l0 = d_z + 8 * N;
+    rc = pq_upload(ctx, lk, s.stream, d_w, wires_ext, N, t, stride);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_s, sigmas_ext, N, t, stride);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_z, z_ext, N, 1, N);
+    if (rc == KZG_OK && gate_coset) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_gate, gate_coset, N, 1, N);
+    const PqChallenges ch{shifts, alpha, beta, gamma};
+    if (rc == KZG_OK) rc = pq_constraints(ctx, lk, s.stream, sh, t, N, d_w, d_s, d_z, (const uint32_t*)d_gate, d_l0, ch, w, (uint32_t*)d_out);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out, d_out, N * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (constraints)");
+    return rc ? rc : sync_unlocked(ctx, lk, s.stream, "permutation constraints");
+}
+
+int kzg_permutation_constraints_coset_device(kzg_ctx* ctx, const void* d_wires_ext, const void* d_sigmas_ext, const void* d_z_ext,
+                                             size_t n, size_t rot, size_t t, size_t stride, const uint64_t* shifts,
+                                             const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                             const void* d_gate_coset, void* d_out) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    PqShape sh;
+    if (!pq_constraint_args_ok(ctx, d_wires_ext, d_sigmas_ext, d_z_ext, n, rot, t, stride, shifts, alpha, beta, gamma, d_out, &sh))
+        return KZG_ERR_INVALID_ARG;
+    const size_t N = sh.N, span = ((t - 1) * stride + N) * 32;
+    if (pq_overlap(d_out, N * 32, d_wires_ext, span) || pq_overlap(d_out, N * 32, d_sigmas_ext, span) ||
+        pq_overlap(d_out, N * 32, d_z_ext, N * 32) || (d_gate_coset && pq_overlap(d_out, N * 32, d_gate_coset, N * 32))) {
+        ctx->last_error = "permutation constraints: the output overlaps an input";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    void* d_l0;
+    rc = pq_bufs(ctx, N, 1, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, N * 32, &d_l0);
+    const PqChallenges ch{shifts, alpha, beta, gamma};
+    if (rc == KZG_OK)
+        rc = pq_constraints(ctx, lk, s.stream, sh, t, stride, (const uint32_t*)d_wires_ext, (const uint32_t*)d_sigmas_ext,
+                            (const uint32_t*)d_z_ext, (const uint32_t*)d_gate_coset, (uint32_t*)d_l0, ch, w, (uint32_t*)d_out);
+    return rc ? rc : sync_unlocked(ctx, lk, s.stream, "permutation constraints");
+}
+
+static int vanishing_quotient_impl(kzg_ctx* ctx, const void* num, size_t N, size_t n, int already_divided, void* out, bool device) {
+    PqShape sh;
+    if (!ctx || !num || !out || n < 1 || N < n || N % n || !pq_shape(n, N / n, &sh)) return KZG_ERR_INVALID_ARG;
+    if (device && pq_overlap(out, (N - n) * 32, num, N * 32)) {
+        ctx->last_error = "vanishing quotient: the output overlaps the input";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    void *vals, *coef = out, *flag;
+    rc = pq_bufs(ctx, N, 1, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &vals);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
+    if (rc) return rc;
+    // the values go into the workspace, where the division may change them
+    rc = copy_unlocked(ctx, lk, s.stream, vals, num, N * 32, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                       "hipMemcpyAsync (numerator)");
+    if (rc == KZG_OK) rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)vals, !already_divided, w, (uint32_t*)coef, (uint32_t*)flag);
+    uint32_t hflag = 0;
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
+    if (rc == KZG_OK && !device)
+        rc = copy_unlocked(ctx, lk, s.stream, out, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "vanishing quotient");
+    if (rc) return rc;
+    return hflag ? pq_remainder(ctx, sh) : KZG_OK;
+}
+
+int kzg_vanishing_quotient(kzg_ctx* ctx, const uint64_t* num_coset, size_t N, size_t n, int already_divided, uint64_t* out_coeffs) {
+    if (ctx && ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_vanishing_quotient(kid, num_coset, N, n, already_divided, out_coeffs));
+    }
+    return vanishing_quotient_impl(ctx, num_coset, N, n, already_divided, out_coeffs, false);
+}
+
+int kzg_vanishing_quotient_device(kzg_ctx* ctx, const void* d_num_coset, size_t N, size_t n, int already_divided, void* d_out_coeffs) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    return vanishing_quotient_impl(ctx, d_num_coset, N, n, already_divided, d_out_coeffs, true);
+}
+
+int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* z, size_t n, size_t t,
+                             size_t stride, const uint64_t* shifts, const uint64_t alpha[4], const uint64_t beta[4],
+                             const uint64_t gamma[4], const uint64_t* gate_coset, unsigned log_ext, uint64_t* out_coeffs,
+                             uint64_t* out_p1s) {
+    PqShape sh;
+    if (!ctx || log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < 1 || t + 1 > sh.rot || stride < n || !wires ||
+        !sigmas || !z || !shifts || !alpha || !beta || !gamma)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        // without commitments the call needs no SRS; with them it follows kzg_commit_lagrange: a replicated context forwards,
+        // a range-split one holds no whole SRS on one device
+        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_permutation_quotient(kid, wires, sigmas, z, n, t, stride, shifts, alpha, beta, gamma, gate_coset,
+                                                           log_ext, out_coeffs, out_p1s));
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (out_p1s) {
+        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    }
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    const size_t N = sh.N, ncols = 2 * t + 1;
+    PqBufs w;
+    void *in, *cols, *d_out, *coef, *flag, *d_gate = nullptr;
+    rc = pq_bufs(ctx, N, ncols, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqIn, ncols * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, (ncols + 1) * N * 32, &cols);  // wires, sigmas, z, L_0
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
+    if (rc == KZG_OK && gate_coset) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc) return rc;
+    uint32_t* d_in = (uint32_t*)in;
+    uint32_t *d_w = (uint32_t*)cols, *d_s = d_w + 8 * t * N, *d_z = d_s + 8 * t * N, *d_l0 = d_z + 8 * N;
+    rc = pq_upload(ctx, lk, s.stream, d_in, wires, n, t, stride);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, sigmas, n, t, stride);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 16 * t * n, z, n, 1, n);
+    if (rc == KZG_OK && gate_coset) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_gate, gate_coset, N, 1, N);
+    if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, d_in, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
+    const PqChallenges ch{shifts, alpha, beta, gamma};
+    if (rc == KZG_OK) rc = pq_constraints(ctx, lk, s.stream, sh, t, N, d_w, d_s, d_z, (const uint32_t*)d_gate, d_l0, ch, w, (uint32_t*)d_out);
+    if (rc == KZG_OK) rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag);
+    uint32_t hflag = 0;
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
+    if (rc == KZG_OK && out_coeffs)
+        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "permutation quotient");
+    if (rc) return rc;
+    if (hflag) return pq_remainder(ctx, sh);
+    if (!out_p1s) return KZG_OK;
+    // chunk c = coefficients [c n, (c + 1) n): batched MSMs over the monomial SRS, as many chunks per job as the slot holds
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the wait for a slot dropped the mutex: the SRS may have changed)
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    const size_t chunks = sh.rot - 1, group = std::min<size_t>(chunks, ctx->max_batch ? ctx->max_batch : 1);
+    for (size_t c0 = 0; c0 < chunks; c0 += group) {
+        const size_t g = chunks - c0 < group ? chunks - c0 : group;
+        const uint32_t* d_chunk = (const uint32_t*)coef + 8 * c0 * n;
+        rc = g == 1 ? submit_commit_locked(ctx, slot, d_chunk, 1, n, true, true) : commit_batch_submit_locked(ctx, slot, d_chunk, n, g, n, true);
+        if (rc) return rc;
+        await_unlocked(lk, s);
+        rc = g == 1 ? wait_locked(ctx, slot, out_p1s + 18 * c0) : wait_batch_locked(ctx, slot, out_p1s + 18 * c0, g);
+        s.kind = SLOT_RESERVED;  // (the mutex was held since the wait marked it idle)
+        if (rc) return rc;
+    }
+    return KZG_OK;
 }
 
 // weights: k blst_fr given by the caller (the test hook), or null for fresh random ones.  wire: the commitments, proofs and

@@ -337,6 +337,29 @@ void launch_permutation_product(hipStream_t s, const uint32_t* d_wires, const ui
                                 size_t stride, const Fr30* bk, const Fr30& beta, const Fr30& gamma, const void* d_tw,
                                 const Fr30& scale, const Fr30& img_one, const GpOut& out);
 
+// ---- quotient_kernels.hip: the quotient of a permutation argument on the coset g H_N, g = 7 ------------
+constexpr uint32_t kPqTile = 256;            // coset points per workgroup of k_pq_constraints: one per lane
+constexpr uint32_t kPqMaxColumns = 7;        // KZG_PQ_MAX_COLUMNS: t + 1 <= rot <= 8
+constexpr uint32_t kPqMaxLogExt = 3;         // KZG_PQ_MAX_LOG_EXT
+// what k_pq_constraints reads: N = 2^log_N values per column on the coset (column j of the wires / sigmas at + 8 j stride words),
+// d_gate null for G = 0, d_zinv: rot stored multipliers (canonical 8 x u32 of the x 2^270 form), 1 / Z_H(x_i) by i mod rot
+struct PqColumns {
+    const uint32_t *d_wires, *d_sigmas, *d_z, *d_l0, *d_gate, *d_zinv;
+};
+// its scalars: beta in multiplier form; gamma, one and the t products beta k_j g as the digits of their blst_fr images;
+// alpha1 = alpha 2^(14 t) and alpha2 = alpha^2 2^14 in multiplier form (they take the products of images back to images)
+struct PqScalars {
+    const Fr30 *beta, *gamma, *one, *alpha1, *alpha2;
+    const Fr30* bkg;  // t of them
+};
+// d_out[i] = Num(x_i) / Z_H(x_i), canonical, i < N; rot = N / n; d_out may alias no input; d_tw: the forward NTT twiddles
+void launch_pq_constraints(hipStream_t s, const PqColumns& cols, uint32_t log_N, uint32_t rot, uint32_t t, size_t stride,
+                           const PqScalars& sc, const void* d_tw, uint32_t* d_out);
+// d_out[b N + i] = d_in[b stride + i] g^i c for i < len, 0 for len <= i < N (b < batch); d_in null: every input value is `fill`
+// (digits of an image); d_gtab: the g^i tables; c in multiplier form.  d_out may not alias d_in.
+void launch_pq_pad_twist(hipStream_t s, const uint32_t* d_in, size_t stride, uint32_t len, const Fr30& fill, uint32_t log_N,
+                         uint64_t batch, const void* d_gtab, const Fr30& c, uint32_t* d_out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

@@ -664,6 +664,35 @@ static int run_gather_calibration() {
     return 0;
 }
 
+// A streaming copy of 32-byte records, one per lane (the record of the Fr kernels): the rate their algorithmic bytes are quoted
+// against.  Bytes counted: read + written.
+__global__ void __launch_bounds__(256) k_copy32(const uint4* __restrict__ in, uint4* __restrict__ out, size_t records) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= records) return;
+    const uint4 a = in[2 * i], b = in[2 * i + 1];
+    out[2 * i] = a;
+    out[2 * i + 1] = b;
+}
+static int run_copy() {
+    const size_t records = (size_t)1 << 24;  // 512 MiB each way: far past the 256 MiB of last-level cache
+    uint4 *in, *out;
+    CHECK(hipMalloc(&in, records * 32));
+    CHECK(hipMalloc(&out, records * 32));
+    CHECK(hipMemset(in, 0x5a, records * 32));
+    double best = 1e30, worst = 0;
+    for (int rep = 0; rep < 5; rep++) {
+        const double ms = time_kernel(k_copy32, (int)(records / 256), 256, 3, (const uint4*)in, out, records);
+        best = ms < best ? ms : best;
+        worst = ms > worst ? ms : worst;
+    }
+    const double bytes = 2.0 * 32.0 * (double)records;
+    printf("{\"bench\": \"copy32\", \"bytes_per_launch\": %.0f, \"min_ms\": %.4f, \"max_ms\": %.4f, \"GBs\": %.1f, \"GBs_min\": %.1f}\n", bytes,
+           best, worst, bytes / best / 1e6, bytes / worst / 1e6);
+    CHECK(hipFree(in));
+    CHECK(hipFree(out));
+    return 0;
+}
+
 static int run_gather_footprints() {
     const int lanes = 196608, iters = 80;  // the accumulation kernel's shape: 15.7M gathers per launch
     u64* out;
@@ -947,6 +976,7 @@ int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "carry")) return run_carry();
     if (argc > 1 && !strcmp(argv[1], "mix")) return run_mix_all();
     if (argc > 1 && !strcmp(argv[1], "gather")) return run_gather_calibration();
+    if (argc > 1 && !strcmp(argv[1], "copy")) return run_copy();
     if (argc > 1 && !strcmp(argv[1], "footprint")) return run_gather_footprints();
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));

@@ -461,6 +461,59 @@ int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* 
                            const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
                            uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index);
 
+/* ---- log-derivative (LogUp) lookup arguments: running sums, a batch inverse, multiplicities -----------
+ * t numerator columns a_j and t denominator columns b_j of n values each:
+ *     phi_0 = 0,   phi_(i+1) = phi_i + sum_j a_j[i] / b_j[i]   (i < n),   last = phi_n.
+ * The row's fractions are added as one pair (N_i, D_i) and 1 / D_i = (prod_{k<i} D_k) (prod_{k>i} D_k) / (prod_k D_k): two product
+ * scans, one additive scan and ONE field inversion per call.  Conventions of kzg_grand_product: column j starts at base + 4 j stride
+ * u64 (stride >= n); every scalar is a blst_fr image, canonical in, fully reduced out; phi_0 is exactly the image of zero.
+ * 1 <= t <= KZG_LOGUP_MAX_COLUMNS, 1 <= n <= 2^KZG_NTT_MAX_LOG, else KZG_ERR_INVALID_ARG.  A zero numerator is legal.  A zero
+ * denominator b_j[i] -> KZG_ERR_INVALID_ARG with *bad_index the least such row i ((size_t)-1 otherwise; bad_index may be NULL),
+ * kzg_last_error names the row, and the outputs are unspecified.
+ * The host-pointer forms are synchronous, need no SRS and run on devices[0] of a multi-device context.  The _device forms take
+ * kzg_dev_alloc buffers of a single-device context, refuse an output that overlaps an input (KZG_ERR_INVALID_ARG) and return when
+ * the output is in place, so that kzg_commit_lagrange_submit(slot, d_out, n) can follow. */
+#define KZG_LOGUP_MAX_COLUMNS 16
+/* general form; nums == NULL: every numerator is one.  out_phi: n blst_fr (phi_0 .. phi_(n-1)), out_last: phi_n */
+int kzg_logderivative_sum(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_phi,
+                          uint64_t out_last[4], size_t* bad_index);
+int kzg_logderivative_sum_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_phi,
+                                 uint64_t out_last[4], size_t* bad_index);
+/* lookup form: k lookup columns f_j (1 <= k <= KZG_LOGUP_MAX_COLUMNS - 1), one table column T and its multiplicities m, n rows
+ * each, a challenge beta:
+ *     phi_(i+1) = phi_i + sum_j 1 / (beta + f_j[i])  -  m_i / (beta + T_i);
+ * the k + 1 denominators are formed in registers, never stored; beta + f_j[i] = 0 or beta + T_i = 0 is a zero denominator.  The
+ * result equals kzg_logderivative_sum on the explicit columns limb for limb.  A lookup that holds gives last = 0; a non-zero last
+ * is returned, not reported as an error */
+int kzg_lookup_sum(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
+                   const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], size_t* bad_index);
+/* ... on device buffers; beta stays a host pointer */
+int kzg_lookup_sum_device(kzg_ctx* ctx, const void* d_lookups, size_t n, size_t k, size_t stride, const void* d_table, const void* d_mult,
+                          const uint64_t beta[4], void* d_out_phi, uint64_t out_last[4], size_t* bad_index);
+/* upload -> phi -> its commitment over the Lagrange basis of the n-domain on one slot (n a power of two, else
+ * KZG_ERR_INVALID_ARG): the twin of kzg_permutation_commit, same statuses and multi-device rules; out_p1 equals
+ * kzg_commit_lagrange of the same phi bit for bit; out_phi may be NULL */
+int kzg_lookup_commit(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
+                      const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index);
+/* out_i = 1 / v_i with the call's one inversion; a zero v_i -> KZG_ERR_INVALID_ARG with *bad_index the least such i */
+int kzg_batch_inverse(kzg_ctx* ctx, const uint64_t* vals, size_t n, uint64_t* out, size_t* bad_index);
+int kzg_batch_inverse_device(kzg_ctx* ctx, const void* d_vals, size_t n, void* d_out, size_t* bad_index);
+/* Multiplicities through a hash table on the device.  table: n_table values (1 <= n_table <= 2^KZG_NTT_MAX_LOG), lookups: k
+ * columns (1 <= k <= KZG_LOGUP_MAX_COLUMNS - 1) of n values (1 <= n <= 2^KZG_NTT_MAX_LOG).  out_mult[r] (the blst_fr image of a
+ * count, n_table of them) = how many of the k n looked-up values equal table[r], counted at the LEAST row holding that value: later
+ * duplicates of a table value get 0.  out_rows (k n uint32, column-major, or NULL): that row for every looked-up value.  Values
+ * are compared as the 32 bytes given (canonical images).  A value that is in no row -> KZG_ERR_INVALID_ARG, *bad_index = the
+ * least row i of the lookup columns holding one, and the outputs are unspecified */
+int kzg_lookup_multiplicities(kzg_ctx* ctx, const uint64_t* table, size_t n_table, const uint64_t* lookups, size_t n, size_t k, size_t stride,
+                              uint64_t* out_mult, uint32_t* out_rows, size_t* bad_index);
+/* ... on device buffers (d_out_rows may be NULL); the outputs overlap no input and not each other */
+int kzg_lookup_multiplicities_device(kzg_ctx* ctx, const void* d_table, size_t n_table, const void* d_lookups, size_t n, size_t k,
+                                     size_t stride, void* d_out_mult, void* d_out_rows, size_t* bad_index);
+/* test hook: the same with the hash table's capacity given as 2^log_capacity >= n_table, log_capacity <= KZG_NTT_MAX_LOG + 1 (the
+ * public call uses the least power of two >= 2 n_table) */
+int kzg_lookup_multiplicities_cap(kzg_ctx* ctx, const uint64_t* table, size_t n_table, const uint64_t* lookups, size_t n, size_t k,
+                                  size_t stride, uint64_t* out_mult, uint32_t* out_rows, size_t* bad_index, unsigned log_capacity);
+
 /* ---- the quotient of a permutation argument on a coset ------------------------------------------------
  * n = 2^k, H = <w_n> (w_n = kzg_domain_root(k)), e = 2^x with x <= KZG_PQ_MAX_LOG_EXT, N = e n <= 2^KZG_NTT_MAX_LOG.  The coset
  * points are x_i = g w_N^i with g = 7, in natural order (the coset kzg_recover_cells_and_proofs works on).  With t wire columns

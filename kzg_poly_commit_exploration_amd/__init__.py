@@ -18,7 +18,7 @@ import numpy as np
 __all__ = [
     "Engine", "Scalar", "G1Point", "Polynomial", "Evaluation", "SetupArtifactsGenerator", "KzgError",
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
-    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS",
+    "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS", "KZG_LOGUP_MAX_COLUMNS",
     "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
@@ -74,6 +74,9 @@ ABI_SYMBOLS = [
     "kzg_open_lagrange", "kzg_open_lagrange_submit", "kzg_quotient_lagrange",
     "kzg_grand_product", "kzg_grand_product_device", "kzg_permutation_product", "kzg_permutation_product_device",
     "kzg_permutation_commit",
+    "kzg_logderivative_sum", "kzg_logderivative_sum_device", "kzg_lookup_sum", "kzg_lookup_sum_device", "kzg_lookup_commit",
+    "kzg_batch_inverse", "kzg_batch_inverse_device", "kzg_lookup_multiplicities", "kzg_lookup_multiplicities_device",
+    "kzg_lookup_multiplicities_cap",
     "kzg_coset_extend", "kzg_coset_extend_device", "kzg_permutation_constraints_coset", "kzg_permutation_constraints_coset_device",
     "kzg_vanishing_quotient", "kzg_vanishing_quotient_device", "kzg_permutation_quotient",
 ]
@@ -87,6 +90,7 @@ KZG_MAX_SETS = 8
 KZG_MAX_SET_POINTS = 16
 KZG_NTT_MAX_LOG = 22
 KZG_GP_MAX_COLUMNS = 16  # columns per side of a grand product
+KZG_LOGUP_MAX_COLUMNS = 16  # columns per side of a log-derivative sum (a lookup: k <= 15 lookup columns and the table)
 KZG_PQ_MAX_COLUMNS = 7   # wire columns of a permutation quotient (t + 1 <= 2^KZG_PQ_MAX_LOG_EXT)
 KZG_PQ_MAX_LOG_EXT = 3
 KZG_EXTEND_VALUES, KZG_EXTEND_COEFFS = 0, 1
@@ -203,6 +207,16 @@ def load_library():
         "kzg_permutation_product": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_permutation_product_device": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_permutation_commit": (i, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_logderivative_sum": (i, [vp, vp, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_logderivative_sum_device": (i, [vp, vp, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_lookup_sum": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_lookup_sum_device": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_lookup_commit": (i, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_batch_inverse": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_batch_inverse_device": (i, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_lookup_multiplicities": (i, [vp, vp, sz, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_lookup_multiplicities_device": (i, [vp, vp, sz, vp, sz, sz, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_lookup_multiplicities_cap": (i, [vp, vp, sz, vp, sz, sz, sz, vp, vp, C.POINTER(sz), C.c_uint]),
         "kzg_coset_extend": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp]),
         "kzg_coset_extend_device": (i, [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, vp]),
         "kzg_permutation_constraints_coset": (i, [vp, vp, vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]),
@@ -1314,6 +1328,93 @@ class Engine:
         self._gp_status(self._lib.kzg_permutation_commit(self._h, _ptr(a), _ptr(b), n, t, stride, _ptr(sh), _ptr(bl), _ptr(gl),
                                                          _ptr(z) if want_z else None, _ptr(last), _ptr(out), C.byref(bad)), bad)
         return G1Point(out), z, last
+
+    # -- log-derivative lookup arguments: running sums, a batch inverse, multiplicities --
+    def logderivative_sum_limbs(self, nums, dens, n=None):
+        """kzg_logderivative_sum: nums (or None: every numerator is one), dens (t, stride, 4) arrays whose first n rows per column
+        count (n=None: all).  Returns (phi, last): phi an (n, 4) array, last a (4,) array.  A zero denominator raises KzgError with
+        .bad_index"""
+        b, t, stride, n = self._columns(dens, n)
+        a = None if nums is None else np.ascontiguousarray(nums, dtype=np.uint64).reshape(t, stride, 4)
+        phi, last, bad = np.zeros((n, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_logderivative_sum(self._h, None if a is None else _ptr(a), _ptr(b), n, t, stride, _ptr(phi),
+                                                        _ptr(last), C.byref(bad)), bad)
+        return phi, last
+
+    def logderivative_sum_device(self, d_nums, d_dens, n, t, d_out_phi, stride=None):
+        """kzg_logderivative_sum_device on kzg_dev_alloc buffers (d_nums None: numerators one): phi lands in d_out_phi, returns last"""
+        last, bad = np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_logderivative_sum_device(self._h, None if d_nums is None else C.c_void_p(d_nums), C.c_void_p(d_dens),
+                                                               n, t, n if stride is None else stride, C.c_void_p(d_out_phi), _ptr(last),
+                                                               C.byref(bad)), bad)
+        return last
+
+    def lookup_sum_limbs(self, lookups, table, mult, beta, n=None):
+        """kzg_lookup_sum: lookups a (k, stride, 4) array, table and mult (n, 4) arrays, beta a Scalar -> (phi, last)"""
+        f, k, stride, n = self._columns(lookups, n)
+        tb = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
+        m = np.ascontiguousarray(mult, dtype=np.uint64).reshape(-1, 4)
+        assert tb.shape[0] >= n and m.shape[0] >= n, "the table and its multiplicities have n rows"
+        bl = beta.limbs()
+        phi, last, bad = np.zeros((n, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_lookup_sum(self._h, _ptr(f), n, k, stride, _ptr(tb), _ptr(m), _ptr(bl), _ptr(phi), _ptr(last),
+                                                 C.byref(bad)), bad)
+        return phi, last
+
+    def lookup_sum_device(self, d_lookups, n, k, d_table, d_mult, beta, d_out_phi, stride=None):
+        bl = beta.limbs()
+        last, bad = np.zeros(4, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_lookup_sum_device(self._h, C.c_void_p(d_lookups), n, k, n if stride is None else stride,
+                                                        C.c_void_p(d_table), C.c_void_p(d_mult), _ptr(bl), C.c_void_p(d_out_phi),
+                                                        _ptr(last), C.byref(bad)), bad)
+        return last
+
+    def lookup_commit(self, lookups, table, mult, beta, n=None, want_phi=True):
+        """kzg_lookup_commit: phi and its commitment over the Lagrange basis in one call -> (G1Point, phi or None, last)"""
+        f, k, stride, n = self._columns(lookups, n)
+        tb = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
+        m = np.ascontiguousarray(mult, dtype=np.uint64).reshape(-1, 4)
+        assert tb.shape[0] >= n and m.shape[0] >= n, "the table and its multiplicities have n rows"
+        bl = beta.limbs()
+        phi = np.zeros((n, 4), dtype=np.uint64) if want_phi else None
+        last, out, bad = np.zeros(4, dtype=np.uint64), np.zeros(18, dtype=np.uint64), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_lookup_commit(self._h, _ptr(f), n, k, stride, _ptr(tb), _ptr(m), _ptr(bl),
+                                                    _ptr(phi) if want_phi else None, _ptr(last), _ptr(out), C.byref(bad)), bad)
+        return G1Point(out), phi, last
+
+    def batch_inverse_limbs(self, vals):
+        """kzg_batch_inverse: vals an (n, 4) array -> the (n, 4) array of inverses.  A zero raises KzgError with .bad_index"""
+        v = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, 4)
+        out, bad = np.zeros_like(v), C.c_size_t(0)
+        self._gp_status(self._lib.kzg_batch_inverse(self._h, _ptr(v), v.shape[0], _ptr(out), C.byref(bad)), bad)
+        return out
+
+    def batch_inverse_device(self, d_vals, n, d_out):
+        bad = C.c_size_t(0)
+        self._gp_status(self._lib.kzg_batch_inverse_device(self._h, C.c_void_p(d_vals), n, C.c_void_p(d_out), C.byref(bad)), bad)
+
+    def lookup_multiplicities(self, table, lookups, n=None, want_rows=True, log_capacity=None):
+        """kzg_lookup_multiplicities: table an (n_table, 4) array, lookups a (k, stride, 4) array -> (mult (n_table, 4), rows (k, n)
+        uint32 or None).  A looked-up value in no table row raises KzgError with .bad_index, the least such row.  log_capacity: the
+        test hook kzg_lookup_multiplicities_cap"""
+        tb = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
+        f, k, stride, n = self._columns(lookups, n)
+        mult, bad = np.zeros_like(tb), C.c_size_t(0)
+        rows = np.zeros((k, n), dtype=np.uint32) if want_rows else None
+        args = (self._h, _ptr(tb), tb.shape[0], _ptr(f), n, k, stride, _ptr(mult), _ptr(rows) if want_rows else None, C.byref(bad))
+        if log_capacity is None:
+            rc = self._lib.kzg_lookup_multiplicities(*args)
+        else:
+            rc = self._lib.kzg_lookup_multiplicities_cap(*args, log_capacity)
+        self._gp_status(rc, bad)
+        return mult, rows
+
+    def lookup_multiplicities_device(self, d_table, n_table, d_lookups, n, k, d_out_mult, d_out_rows=None, stride=None):
+        bad = C.c_size_t(0)
+        self._gp_status(self._lib.kzg_lookup_multiplicities_device(self._h, C.c_void_p(d_table), n_table, C.c_void_p(d_lookups), n, k,
+                                                                   n if stride is None else stride, C.c_void_p(d_out_mult),
+                                                                   None if d_out_rows is None else C.c_void_p(d_out_rows),
+                                                                   C.byref(bad)), bad)
 
     # -- the quotient of a permutation argument on the coset 7 H_N (DESIGN.md 4.20) --
     def _pq_check(self, rc):

@@ -340,6 +340,11 @@ struct kzg_ctx {
     // the quotient of a permutation argument (kzg_coset_extend .. kzg_permutation_quotient), under
     // quotient_mu (taken before mu): workspaces grown on demand; the calls read the g-power tables rec_g, which are built once
     // and never replaced
+    // lookups (kzg_lookup_multiplicities), under lookup_mu (taken before mu): the hash table's slots and
+    // flag words, the counts, and the columns and outputs of a host-pointer call; grown on demand.  The sums and the batch
+    // inverse use the slot's grand-product buffers instead (a slot holds one job at a time).
+    std::mutex lookup_mu;
+    Workspace<6> lu_ws;
     std::mutex quotient_mu;
     Workspace<11> pq_ws;
     uint32_t pq_zinv_key = ~0u;  // (log n << 8) | log rot of the inverses of Z_H held in pq_ws, ~0: none
@@ -4028,6 +4033,337 @@ int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* 
     await_unlocked(lk, s);
     rc = wait_locked(ctx, slot, out_p1);
     return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+}
+
+// ---- log-derivative sums: phi_0 = 0, phi_(i+1) = phi_i + sum_j a_j[i] / b_j[i] (lookup_kernels.hip) ------
+// The three forms of one call; the columns are host or device pointers as the caller's entry point says.
+enum LuForm { kLuGeneral = 0, kLuLookupForm = 1, kLuInverse = 2 };
+struct LuCall {
+    LuForm form;
+    const void* a;      // general: the numerators (may be null); lookup: the k lookup columns; inverse: unused
+    const void* b;      // general: the denominators; lookup: unused; inverse: the values
+    const void* table;  // lookup form
+    const void* mult;
+    const uint64_t* beta;
+    size_t n, t, stride;  // t: columns of a and b (lookup form: k)
+};
+static bool lu_shape_ok(size_t n, size_t t, size_t stride, size_t t_max) {
+    return n >= 1 && n <= ((size_t)1 << kNttMaxLog) && t >= 1 && t <= t_max && stride >= n;
+}
+static int lu_slot_ready(kzg_ctx* ctx, Slot& s, size_t n, size_t in_bytes, bool own_out) {
+    int rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
+    if (rc == KZG_OK) rc = s.gp_part.reserve(ctx, (size_t)lu_tiles(n) * kLuPartialWords * 4, s.stream);
+    if (rc == KZG_OK && in_bytes) rc = s.gp_in.reserve(ctx, in_bytes, s.stream);
+    if (rc == KZG_OK && own_out) rc = s.gp_z.reserve(ctx, n * 32, s.stream);
+    return rc;
+}
+// the columns a host-pointer call packs into the slot (stride n)
+static size_t lu_packed_columns(const LuCall& c) {
+    return c.form == kLuGeneral ? (c.a ? 2 : 1) * c.t : (c.form == kLuLookupForm ? c.t + 2 : 1);
+}
+// uploads the call's columns into s.gp_in and returns the call on those device columns
+static int lu_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const LuCall& c, LuCall* dev) {
+    uint32_t* d = s.gp_in.dev();
+    const size_t n = c.n, t = c.t;
+    *dev = c;
+    dev->stride = n;
+    int rc = KZG_OK;
+    if (c.form == kLuGeneral) {
+        dev->b = d;
+        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.b, n, t, c.stride);
+        if (rc == KZG_OK && c.a) {
+            dev->a = d + 8 * t * n;
+            rc = gp_upload(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.a, n, t, c.stride);
+        }
+    } else if (c.form == kLuLookupForm) {
+        dev->a = d;
+        dev->table = d + 8 * t * n;
+        dev->mult = d + 8 * (t + 1) * n;
+        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.a, n, t, c.stride);
+        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.table, n, 1, n);
+        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d + 8 * (t + 1) * n, (const uint64_t*)c.mult, n, 1, n);
+    } else {
+        dev->b = d;
+        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.b, n, 1, n);
+    }
+    return rc;
+}
+// the three kernels on the slot's stream: the output into d_out, the results into the slot's gp_flags
+static int lu_enqueue(kzg_ctx* ctx, Slot& s, const LuCall& c, uint32_t* d_out) {
+    const size_t cols = c.form == kLuGeneral ? c.t : (c.form == kLuLookupForm ? c.t + 1 : 1);
+    const Fr30 scale = fr30_arg_from_mont256(fr_pow2((uint32_t)(14 * cols)));  // 2^(270 + 14 t): see the unit's header
+    auto image = [](const hf::Fr& v) {
+        uint32_t l[8];
+        std::memcpy(l, v.l, 32);
+        return fr30_from_limbs(l);
+    };
+    const LuOut out{d_out, s.gp_part.dev(), s.gp_flags.dev()};
+    const Fr30 one = image(hf::kFrOne);
+    if (c.form == kLuGeneral) {
+        launch_logderivative_sum(s.stream, (const uint32_t*)c.a, (const uint32_t*)c.b, (uint32_t)c.n, (uint32_t)c.t, c.stride, scale, one, out);
+    } else if (c.form == kLuLookupForm) {
+        hf::Fr beta;
+        std::memcpy(beta.l, c.beta, 32);
+        launch_lookup_sum(s.stream, (const uint32_t*)c.a, (uint32_t)c.n, (uint32_t)c.t, c.stride, (const uint32_t*)c.table,
+                          (const uint32_t*)c.mult, image(beta), scale, one, out);
+    } else {
+        launch_batch_inverse(s.stream, (const uint32_t*)c.b, (uint32_t)c.n, scale, one, out);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// after the stream was waited for: the status of the call, phi_n, the row of a zero denominator
+static int lu_result(kzg_ctx* ctx, const Slot& s, LuForm form, uint64_t out_last[4], size_t* bad_index) {
+    const uint32_t* h = s.gp_flags.host();
+    if (bad_index) *bad_index = h[0] == kLuNone ? (size_t)-1 : (size_t)h[0];
+    if (h[0] != kLuNone) {
+        ctx->last_error = form == kLuInverse ? "batch inverse: the value at row " + std::to_string(h[0]) + " is zero"
+                                             : "log-derivative sum: a denominator at row " + std::to_string(h[0]) + " is zero";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (out_last) std::memcpy(out_last, h + 8, 32);
+    return KZG_OK;
+}
+static int lu_host(kzg_ctx* ctx, const LuCall& c, uint64_t* out, uint64_t out_last[4], size_t* bad_index) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = lu_slot_ready(ctx, s, c.n, lu_packed_columns(c) * c.n * 32, true);
+    if (rc) return rc;
+    LuCall dev;
+    rc = lu_upload(ctx, lk, s, c, &dev);
+    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, dev, s.gp_z.dev());
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out, s.gp_z.dev(), c.n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
+    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
+}
+static bool lu_overlaps(const void* out, size_t out_bytes, const void* in, size_t in_bytes) {
+    return in && (const char*)out < (const char*)in + in_bytes && (const char*)in < (const char*)out + out_bytes;
+}
+static int lu_device(kzg_ctx* ctx, const LuCall& c, void* d_out, uint64_t out_last[4], size_t* bad_index) {
+    const size_t span = ((c.t - 1) * c.stride + c.n) * 32, one = c.n * 32;  // bytes a column set covers, bytes of one column
+    const bool columns = c.form != kLuInverse;
+    if ((columns && lu_overlaps(d_out, one, c.a, span)) || lu_overlaps(d_out, one, c.b, columns ? span : one) ||
+        lu_overlaps(d_out, one, c.table, one) || lu_overlaps(d_out, one, c.mult, one)) {
+        ctx->last_error = "log-derivative sum: the output overlaps an input";
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = lu_slot_ready(ctx, s, c.n, 0, false);
+    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, c, (uint32_t*)d_out);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
+    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
+}
+
+int kzg_logderivative_sum(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_phi,
+                          uint64_t out_last[4], size_t* bad_index) {
+    if (!ctx || !dens || !out_phi || !out_last || !lu_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_logderivative_sum(kid, nums, dens, n, t, stride, out_phi, out_last, bad_index));
+    }
+    return lu_host(ctx, LuCall{kLuGeneral, nums, dens, nullptr, nullptr, nullptr, n, t, stride}, out_phi, out_last, bad_index);
+}
+
+int kzg_logderivative_sum_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_phi,
+                                 uint64_t out_last[4], size_t* bad_index) {
+    if (!ctx || !d_dens || !d_out_phi || !out_last || !lu_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    return lu_device(ctx, LuCall{kLuGeneral, d_nums, d_dens, nullptr, nullptr, nullptr, n, t, stride}, d_out_phi, out_last, bad_index);
+}
+
+int kzg_lookup_sum(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
+                   const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], size_t* bad_index) {
+    if (!ctx || !lookups || !table || !mult || !beta || !out_phi || !out_last || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1))
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_lookup_sum(kid, lookups, n, k, stride, table, mult, beta, out_phi, out_last, bad_index));
+    }
+    return lu_host(ctx, LuCall{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride}, out_phi, out_last, bad_index);
+}
+
+int kzg_lookup_sum_device(kzg_ctx* ctx, const void* d_lookups, size_t n, size_t k, size_t stride, const void* d_table, const void* d_mult,
+                          const uint64_t beta[4], void* d_out_phi, uint64_t out_last[4], size_t* bad_index) {
+    if (!ctx || !d_lookups || !d_table || !d_mult || !beta || !d_out_phi || !out_last || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1))
+        return KZG_ERR_INVALID_ARG;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    return lu_device(ctx, LuCall{kLuLookupForm, d_lookups, nullptr, d_table, d_mult, beta, n, k, stride}, d_out_phi, out_last, bad_index);
+}
+
+int kzg_batch_inverse(kzg_ctx* ctx, const uint64_t* vals, size_t n, uint64_t* out, size_t* bad_index) {
+    if (!ctx || !vals || !out || !lu_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_batch_inverse(kid, vals, n, out, bad_index));
+    }
+    return lu_host(ctx, LuCall{kLuInverse, nullptr, vals, nullptr, nullptr, nullptr, n, 1, n}, out, nullptr, bad_index);
+}
+
+int kzg_batch_inverse_device(kzg_ctx* ctx, const void* d_vals, size_t n, void* d_out, size_t* bad_index) {
+    if (!ctx || !d_vals || !d_out || !lu_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    return lu_device(ctx, LuCall{kLuInverse, nullptr, d_vals, nullptr, nullptr, nullptr, n, 1, n}, d_out, nullptr, bad_index);
+}
+
+int kzg_lookup_commit(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
+                      const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index) {
+    uint32_t lg = 0;
+    if (!ctx || !lookups || !table || !mult || !beta || !out_last || !out_p1 || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1) ||
+        !ntt_log(n, &lg))
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        int rc = KZG_OK;
+        kzg_ctx* kid = lagrange_kid(ctx, &rc);
+        return kid ? forwarded(ctx, kid, kzg_lookup_commit(kid, lookups, n, k, stride, table, mult, beta, out_phi, out_last, out_p1, bad_index))
+                   : rc;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = lagrange_ensure(ctx, lk, n, lg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};  // (the basis stays until the submit, as for kzg_commit_lagrange)
+    Slot& s = ctx->slots[slot];
+    const LuCall c{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride};
+    rc = lu_slot_ready(ctx, s, n, lu_packed_columns(c) * n * 32, false);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
+    if (rc) return rc;
+    // phi goes to the slot's staging buffer, where the MSM over the Lagrange basis reads it
+    LuCall dev;
+    rc = lu_upload(ctx, lk, s, c, &dev);
+    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, dev, s.stage.dev());
+    if (rc == KZG_OK && out_phi)
+        rc = copy_unlocked(ctx, lk, s.stream, out_phi, s.stage.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
+    MsmBasis basis{};
+    if (rc == KZG_OK && !lagrange_basis(ctx, n, &basis)) rc = KZG_ERR_NO_SRS;
+    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true, &basis);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    rc = wait_locked(ctx, slot, out_p1);
+    return rc ? rc : lu_result(ctx, s, kLuLookupForm, out_last, bad_index);
+}
+
+// ---- multiplicities of a lookup through a hash table on the device (lookup_kernels.hip) -------------------
+// A call holds lookup_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits.
+namespace {
+enum : int { kLuWsTable = 0, kLuWsLookups, kLuWsSlots, kLuWsCounts, kLuWsMult, kLuWsRows, kLuWsCount };
+static_assert(kLuWsCount <= 6, "lu_ws");
+// Declared after the slot's lease, so that it runs first: nothing the call enqueued still uses lu_ws when lookup_mu is given up.
+struct LuDrain {
+    const Slot& s;
+    ~LuDrain() {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+    }
+};
+bool lu_mult_shape(size_t n_table, size_t n, size_t k, size_t stride) {
+    const size_t top = (size_t)1 << kNttMaxLog;
+    return n_table >= 1 && n_table <= top && n >= 1 && n <= top && k >= 1 && k <= kLuMaxColumns - 1 && stride >= n;
+}
+// the least power of two >= 2 n_table
+unsigned lu_default_log_capacity(size_t n_table) {
+    unsigned lg = 1;
+    while (((size_t)1 << lg) < 2 * n_table) lg++;
+    return lg;
+}
+int lu_multiplicities(kzg_ctx* ctx, const void* table, size_t n_table, const void* lookups, size_t n, size_t k, size_t stride, void* out_mult,
+                      void* out_rows, size_t* bad_index, unsigned log_cap, bool device) {
+    std::lock_guard<std::mutex> lkl(ctx->lookup_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    LuDrain drain{s};
+    int rc = ensure_slot_basics(ctx, s);
+    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
+    const size_t cap = (size_t)1 << log_cap;
+    void *d_slots = nullptr, *d_counts = nullptr, *d_table = (void*)table, *d_look = (void*)lookups, *d_mult = out_mult, *d_rows = out_rows;
+    if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsSlots, (cap + 4) * 4, &d_slots);  // the slots, then the two flag words
+    if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsCounts, n_table * 4, &d_counts);
+    if (!device) {
+        if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsTable, n_table * 32, &d_table);
+        if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsLookups, k * n * 32, &d_look);
+        if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsMult, n_table * 32, &d_mult);
+        if (rc == KZG_OK && out_rows) rc = ctx->lu_ws.get(ctx, kLuWsRows, k * n * 4, &d_rows);
+        if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, d_table, table, n_table * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (table)");
+        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, (uint32_t*)d_look, (const uint64_t*)lookups, n, k, stride);
+    }
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_slots, 0xff, (cap + 4) * 4, s.stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, n_table * 4, s.stream));
+    const LuHash h{(uint32_t*)d_slots, log_cap, (uint32_t*)d_counts, (uint32_t*)d_slots + cap};
+    launch_lookup_multiplicities(s.stream, (const uint32_t*)d_table, (uint32_t)n_table, (const uint32_t*)d_look, (uint32_t)n, (uint32_t)k,
+                                 device ? stride : n, h, fr30_arg_from_mont256(fr_pow2(256)), (uint32_t*)d_mult, (uint32_t*)d_rows,
+                                 s.gp_flags.dev());
+    HIP_TRY(ctx, hipGetLastError());
+    if (!device) {
+        rc = copy_unlocked(ctx, lk, s.stream, out_mult, d_mult, n_table * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (multiplicities)");
+        if (rc == KZG_OK && out_rows)
+            rc = copy_unlocked(ctx, lk, s.stream, out_rows, d_rows, k * n * 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (rows)");
+    }
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "lookup multiplicities");
+    if (rc) return rc;
+    const uint32_t* f = s.gp_flags.host();
+    if (bad_index) *bad_index = f[0] == kLuNone ? (size_t)-1 : (size_t)f[0];
+    if (f[1] != kLuNone) {  // not reached with a capacity >= n_table
+        ctx->last_error = "lookup multiplicities: the hash table is full at table row " + std::to_string(f[1]);
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (f[0] != kLuNone) {
+        ctx->last_error = "lookup multiplicities: a value at row " + std::to_string(f[0]) + " of the lookup columns is in no table row";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return KZG_OK;
+}
+}  // namespace
+
+int kzg_lookup_multiplicities_cap(kzg_ctx* ctx, const uint64_t* table, size_t n_table, const uint64_t* lookups, size_t n, size_t k,
+                                  size_t stride, uint64_t* out_mult, uint32_t* out_rows, size_t* bad_index, unsigned log_capacity) {
+    if (!ctx || !table || !lookups || !out_mult || !lu_mult_shape(n_table, n, k, stride) || log_capacity > kNttMaxLog + 1 ||
+        ((size_t)1 << log_capacity) < n_table)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_lookup_multiplicities_cap(kid, table, n_table, lookups, n, k, stride, out_mult, out_rows, bad_index,
+                                                                 log_capacity));
+    }
+    return lu_multiplicities(ctx, table, n_table, lookups, n, k, stride, out_mult, out_rows, bad_index, log_capacity, false);
+}
+
+int kzg_lookup_multiplicities(kzg_ctx* ctx, const uint64_t* table, size_t n_table, const uint64_t* lookups, size_t n, size_t k, size_t stride,
+                              uint64_t* out_mult, uint32_t* out_rows, size_t* bad_index) {
+    if (!ctx || !lu_mult_shape(n_table, n, k, stride)) return KZG_ERR_INVALID_ARG;
+    return kzg_lookup_multiplicities_cap(ctx, table, n_table, lookups, n, k, stride, out_mult, out_rows, bad_index,
+                                         lu_default_log_capacity(n_table));
+}
+
+int kzg_lookup_multiplicities_device(kzg_ctx* ctx, const void* d_table, size_t n_table, const void* d_lookups, size_t n, size_t k,
+                                     size_t stride, void* d_out_mult, void* d_out_rows, size_t* bad_index) {
+    if (!ctx || !d_table || !d_lookups || !d_out_mult || !lu_mult_shape(n_table, n, k, stride)) return KZG_ERR_INVALID_ARG;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    const size_t span = ((k - 1) * stride + n) * 32;
+    for (const void* out : {(const void*)d_out_mult, (const void*)d_out_rows}) {
+        const size_t bytes = out == d_out_mult ? n_table * 32 : k * n * 4;
+        if (out && (lu_overlaps(out, bytes, d_table, n_table * 32) || lu_overlaps(out, bytes, d_lookups, span) ||
+                    (out == d_out_rows && lu_overlaps(out, bytes, d_out_mult, n_table * 32)))) {
+            ctx->last_error = "lookup multiplicities: an output overlaps an input or the other output";
+            return KZG_ERR_INVALID_ARG;
+        }
+    }
+    return lu_multiplicities(ctx, d_table, n_table, d_lookups, n, k, stride, d_out_mult, d_out_rows, bad_index,
+                             lu_default_log_capacity(n_table), true);
 }
 
 // ---- recovery of every cell and proof from part of the cells (recover_kernels.hip) -----------------

@@ -337,6 +337,46 @@ void launch_permutation_product(hipStream_t s, const uint32_t* d_wires, const ui
                                 size_t stride, const Fr30* bk, const Fr30& beta, const Fr30& gamma, const void* d_tw,
                                 const Fr30& scale, const Fr30& img_one, const GpOut& out);
 
+// ---- lookup_kernels.hip: phi_0 = 0, phi_(i+1) = phi_i + sum_j a_j[i] / b_j[i] with one inversion per call, a batch inverse, and
+// the multiplicities of a lookup through a hash table ----------------------------------------------------
+constexpr uint32_t kLuTile = 512;            // consecutive rows per workgroup: 256 lanes x a run of 2
+constexpr uint32_t kLuCarryThreads = 256;    // lanes of the carry kernel's one workgroup: <= 32 consecutive tiles each
+constexpr uint32_t kLuMaxColumns = 16;       // KZG_LOGUP_MAX_COLUMNS
+constexpr uint32_t kLuNone = 0xffffffffu;    // "no zero denominator", "no missing value", an empty slot of the hash table
+// a tile's record, in words: the digits of its product of D, the least row with D_i = 0, the digits of W_T, of c_T (carry kernel),
+// and base_T as 8 canonical limbs (carry kernel; 16-byte aligned)
+constexpr uint32_t kLuRecD = 0, kLuRecHit = 9, kLuRecW = 10, kLuRecC = 20, kLuRecBase = 32, kLuPartialWords = 40;
+inline uint32_t lu_tiles(size_t n) { return (uint32_t)((n + kLuTile - 1) / kLuTile); }
+// d_phi: n canonical blst_fr, may alias no input; d_partial: lu_tiles(n) records of kLuPartialWords words; d_flags: 16 words the
+// carry kernel writes: [0] = the least row with a zero denominator or kLuNone, [8..15] = phi_n.
+// scale: 2^(14 t) in multiplier form (t: the columns per side, k + 1 in the lookup form, 1 for the batch inverse); img_one: the
+// digits of the image of one.
+struct LuOut {
+    uint32_t* d_phi;
+    uint32_t* d_partial;
+    uint32_t* d_flags;
+};
+// t columns per side of n blst_fr each, stride in blst_fr; d_nums null: every numerator is one
+void launch_logderivative_sum(hipStream_t s, const uint32_t* d_nums, const uint32_t* d_dens, uint32_t n, uint32_t t, size_t stride,
+                              const Fr30& scale, const Fr30& img_one, const LuOut& out);
+// sum_j 1 / (beta + f_j[i]) - m_i / (beta + T_i) over k lookup columns; beta as the digits of its image
+void launch_lookup_sum(hipStream_t s, const uint32_t* d_lookups, uint32_t n, uint32_t k, size_t stride, const uint32_t* d_table,
+                       const uint32_t* d_mult, const Fr30& beta, const Fr30& scale, const Fr30& img_one, const LuOut& out);
+// out.d_phi[i] = 1 / vals[i]; flags as above ([8..15] is written and means nothing)
+void launch_batch_inverse(hipStream_t s, const uint32_t* d_vals, uint32_t n, const Fr30& scale, const Fr30& img_one, const LuOut& out);
+// The hash table of one call: 2^log_cap slots (set to kLuNone by the caller, on the stream), n_table counts (set to zero), two
+// flag words (set to kLuNone): [0] the least lookup row holding a value in no table row, [1] the least table row whose walk hit
+// the loop bound.  count_img: 2^256 in multiplier form.  d_out_rows may be null.  d_flags: >= 2 words, takes the two flag words.
+struct LuHash {
+    uint32_t* d_slots;
+    uint32_t log_cap;
+    uint32_t* d_counts;
+    uint32_t* d_words;
+};
+void launch_lookup_multiplicities(hipStream_t s, const uint32_t* d_table, uint32_t n_table, const uint32_t* d_lookups, uint32_t n,
+                                  uint32_t k, size_t stride, const LuHash& h, const Fr30& count_img, uint32_t* d_out_mult,
+                                  uint32_t* d_out_rows, uint32_t* d_flags);
+
 // ---- quotient_kernels.hip: the quotient of a permutation argument on the coset g H_N, g = 7 ------------
 constexpr uint32_t kPqTile = 256;            // coset points per workgroup of k_pq_constraints: one per lane
 constexpr uint32_t kPqMaxColumns = 7;        // KZG_PQ_MAX_COLUMNS: t + 1 <= rot <= 8

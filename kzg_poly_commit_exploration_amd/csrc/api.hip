@@ -188,6 +188,7 @@ struct SlotQueue {
 struct Slot : SlotQueue {
     // MSM workspace (sized at SRS load)
     DevBuf cnt, offs, block_sums, pairs, sorted, buckets;
+    DevBuf recoded;         // the folded scalars of the job, 32 bytes each: written by the sort's first pass, read by its second
     DevBuf part_a, part_b;  // head / tail partials of the accumulation segments
     DevBuf pair_scratch;    // prefix products of the affine front end (msm_accum.hip)
     DevBuf heavy_ws;        // long-bucket registry + tree buffers of msm_finalize.hip
@@ -392,7 +393,7 @@ int copy_unlocked(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st
 }
 
 void free_slot_msm(Slot& s) {
-    for (DevBuf* b : {&s.cnt, &s.offs, &s.block_sums, &s.pairs, &s.sorted, &s.buckets, &s.part_a, &s.part_b, &s.pair_scratch,
+    for (DevBuf* b : {&s.cnt, &s.offs, &s.block_sums, &s.pairs, &s.recoded, &s.sorted, &s.buckets, &s.part_a, &s.part_b, &s.pair_scratch,
                       &s.heavy_ws, &s.arena})
         b->reset();
     s.fin.reset();
@@ -532,6 +533,7 @@ int setup_slots_impl(kzg_ctx* ctx) {
         if (rc) return rc;
         HIP_TRY(ctx, hipMemset(s.block_sums.p, 0, (size_t)sort_workspace_zero_words() * 4));
         rc = s.pairs.reserve(ctx, (pairs ? pairs : 1) * 8);
+        if (rc == KZG_OK) rc = s.recoded.reserve(ctx, (ctx->n * B ? ctx->n * B : 1) * 32);
         if (rc == KZG_OK) rc = s.sorted.reserve(ctx, (pairs ? pairs : 1) * 4);
         if (rc == KZG_OK) rc = s.buckets.reserve(ctx, (size_t)cfg.nb * B * kXyzzBytes);
         if (rc == KZG_OK) rc = s.part_a.reserve(ctx, (size_t)kMaxAccumLanes * kXyzzBytes);
@@ -617,7 +619,7 @@ int enqueue_msm(kzg_ctx* ctx, Slot& s, const uint32_t* d_scalars, int is_mont, s
     s.end = st;
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.ev[ev_base], st));
     const bool header_zeroed = launch_bucket_sort(st, d_scalars, is_mont, (uint32_t)n, batch, stride, table_stride, cfg, s.cnt.dev(),
-                       s.block_sums.dev(), s.pairs.dev<uint64_t>(), s.offs.dev(), s.sorted.dev(), (uint32_t*)s.heavy_ws.p);
+                       s.block_sums.dev(), s.pairs.dev<uint64_t>(), s.recoded.dev(), s.offs.dev(), s.sorted.dev(), (uint32_t*)s.heavy_ws.p);
     if (s.timing) {
         HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 1], st));
         HIP_TRY(ctx, hipEventRecord(s.ev[ev_base + 2], st));

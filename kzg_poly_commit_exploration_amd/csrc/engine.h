@@ -60,7 +60,8 @@ constexpr size_t kHeavyHeaderBytes = 1024;  // zeroed per job: long-bucket count
 // at d_scalars + p * stride scalars; its buckets are [p * nb, (p+1) * nb)): fills
 // d_offs[0 .. batch*nb] (last = number of references) and d_sorted (bucket-major table references,
 // index | sign << 31).  d_cnt: sort_count_entries(max_batch, cfg) u32; d_ws: sort_workspace_words() u32;
-// d_pairs: batch * n * max_digits u64.  batch <= sort_max_batch(cfg).
+// d_pairs: batch * n * max_digits u64; d_recoded: batch * n * 32 bytes (the folded scalars between the two recoding passes;
+// not touched by the one-workgroup sort of small inputs).  batch <= sort_max_batch(cfg).
 uint32_t sort_count_entries(uint32_t max_batch, MsmConfig cfg);
 uint32_t sort_max_batch(MsmConfig cfg);
 uint32_t sort_workspace_words();
@@ -69,7 +70,8 @@ uint32_t sort_workspace_zero_words();  // leading words of d_ws that must be zer
 // itself (it does whenever it launches anything), false when the caller has to memset them (n == 0).
 bool launch_bucket_sort(hipStream_t s, const uint32_t* d_scalars, int scalars_are_mont, uint32_t n, uint32_t batch,
                         uint64_t stride, uint32_t table_stride, MsmConfig cfg, uint32_t* d_cnt,
-                        uint32_t* d_ws, uint64_t* d_pairs, uint32_t* d_offs, uint32_t* d_sorted, uint32_t* d_header);
+                        uint32_t* d_ws, uint64_t* d_pairs, uint32_t* d_recoded, uint32_t* d_offs, uint32_t* d_sorted,
+                        uint32_t* d_header);
 // bucket accumulation (dominant kernel): one lane per segment of L sorted references
 constexpr uint32_t kMaxAccumLanes = 262144 + 64;  // bound on accumulate_lanes()
 // lanes (= segments) for at most max_refs references; a multiple of the workgroup size

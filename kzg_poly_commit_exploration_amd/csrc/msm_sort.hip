@@ -3,15 +3,18 @@
 // blst_p1_mult window walk of the reference (src/scalar.rs:83-93, src/curves.rs:90-96) for the
 // whole polynomial at once.
 //
-// HBM traffic per commitment of n terms, W windows: scalars read twice (2 x 32 B x n), pairs written
-// once and read twice (3 x 4 B x n x W in the packed form -- table index below 2^24, e.g. degree 2^20 -- else
+// HBM traffic per commitment of n terms, W windows: scalars read once (32 B x n), their folded form written once and read
+// once (2 x 32 B x n: 32 MB more than converting twice at 2^20 terms, ~1.3 % of the 2.4 GB the accumulation gathers), pairs
+// written once and read twice (3 x 4 B x n x W in the packed form -- table index below 2^24, e.g. degree 2^20 -- else
 // 3 x 8 B), references written (4 B x n x W).  Integer / byte work bound by LDS atomics and scattered 4..8-byte
 // stores, not by arithmetic.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "msm_recode.h"
 
 namespace kzg {
 
@@ -79,97 +82,59 @@ MsmConfig choose_msm_config(size_t n, size_t table_budget_bytes) {
     return cfg;
 }
 
-// The scalar as sign and magnitude of its shortest representative: |k| <= r / 2 (+ r / 2^31) < 2^254 in 8 words, and
-// k * P = |k| * (+-P).  Returns true when the point has to be negated.  Besides halving the range this makes the
-// reference's "negative" i128 inputs (r - |a|, src/scalar.rs:27-48) as cheap as the positive ones: their upper windows
-// become zero digits, which are skipped.
-// One product in the signed-digit field (fr30.hip.h) leaves the Montgomery form, reduces and centres at once: the blst_fr
-// image is x * 2^256, times the single digit 2^14 over the multiplier's 2^270 is x; canonical little-endian bytes (expected
-// below r, any 256-bit value accepted) times 2^270 mod r over 2^270 is the value mod r.  The product of balanced
-// Montgomery digits is the centred residue up to r / 2^31 -- which representative is used changes the digits, not the sum.
-// (Two calls: with the multiplier a compile-time constant the first is a reduction and nine shifts, not 162 multiply-adds.)
+// The fold of a scalar to sign and magnitude and the digit loops live in msm_recode.h (host-testable).
 KZG_DEV bool load_scalar(const uint32_t* d_scalars, uint64_t i, int is_mont, u32 k[8]) {
     const uint4* p = reinterpret_cast<const uint4*>(d_scalars) + 2 * (size_t)i;
     const uint4 lo = p[0], hi = p[1];
     const uint32_t in[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const Fr30 d = fr30_from_limbs_raw(in);
-    const Fr30 v = is_mont ? fr30_mul(d, fr30_small(1 << 14)) : fr30_mul(d, fr30_const_one270());
-    return fr30_abs_to_limbs(v, k);
+    return recode_fold(in, is_mont, k);
 }
 
-// Signed window recoding, low window first: digit in [-2^(c-1)+1, 2^(c-1)], carry into the next
-// window.  |k| < 2^254 and W * c >= 255, so the top window absorbs the last carry.
-// f(table level, bucket, negative)
-template <class F>
-KZG_DEV void for_each_window_digit(u32 k[8], uint32_t c, uint32_t W, F&& f) {
-    const u32 mask = (1u << c) - 1u;
-    const u32 half = 1u << (c - 1);
-    u32 carry = 0;
-    for (uint32_t j = 0; j < W; j++) {
-        u32 v = (k[0] & mask) + carry;
-        // k >>= c
+// The folded scalars of a job, 32 bytes each (|k|, negate flag in bit 255: recode_pack): written by the first pass of the
+// sort, read by the second, which therefore does no field arithmetic and never sees the input form.
+KZG_DEV void store_recoded(uint32_t* d_recoded, uint64_t g, const u32 k[8], bool flip) {
+    uint4* p = reinterpret_cast<uint4*>(d_recoded) + 2 * (size_t)g;
+    p[0] = make_uint4(k[0], k[1], k[2], k[3]);
+    p[1] = make_uint4(k[4], k[5], k[6], k[7] | (flip ? 0x80000000u : 0u));
+}
+KZG_DEV bool load_recoded(const uint32_t* d_recoded, uint64_t g, u32 k[8]) {
+    const uint4* p = reinterpret_cast<const uint4*>(d_recoded) + 2 * (size_t)g;
+    const uint4 lo = p[0], hi = p[1];
+    k[0] = lo.x, k[1] = lo.y, k[2] = lo.z, k[3] = lo.w, k[4] = hi.x, k[5] = hi.y, k[6] = hi.z, k[7] = hi.w;
+    return recode_unpack(k);
+}
+
+// C: the window width when the kernel was compiled for it (for_each_window_digit_fixed: the widths choose_msm_config picks at
+// 2^17 ... 2^22 terms), 0 for the loops that take the width at run time (every other width, and NAF).  k is left as it was.
+template <uint32_t C, class F>
+KZG_DEV void for_each_digit(const u32 k[8], MsmConfig cfg, F&& f) {
+    if constexpr (C != 0) {
+        for_each_window_digit_fixed<C>(k, f);
+    } else if (cfg.recode == kRecodeNaf) {
+        for_each_naf_digit(k, cfg.c, f);
+    } else {
+        u32 t[8];
 #pragma unroll
-        for (int t = 0; t < 7; t++) k[t] = (k[t] >> c) | (k[t + 1] << (32 - c));
-        k[7] >>= c;
-        bool neg = v > half;
-        u32 mag = neg ? (mask + 1u - v) : v;
-        carry = neg ? 1u : 0u;
-        if (mag) f(j, mag - 1u, neg);
+        for (int w = 0; w < 8; w++) t[w] = k[w];
+        for_each_window_digit(t, cfg.c, cfg.W, f);
     }
 }
-
-// Width-c non-adjacent form, low bit first, without ever shifting the scalar: K' = (k >> pos) + carry is the
-// value still to encode.  K' even -> next bit (the carry is unchanged: bit == carry).  K' odd -> the digit is
-// v = (c bits of k at pos) + carry (no overflow: an odd K' means bit0 + carry == 1), taken as v - 2^c when
-// v > 2^(c-1) (carry 1), and the next c-1 digits are zero.  Words are walked by an unrolled loop so that the
-// scalar stays in registers; zero digits are skipped with one ffs per run.  |k| < 2^254 keeps the last digit at
-// bit <= 254.  Digits are odd: bucket (|d| - 1) / 2, weight 2 * bucket + 1.
-template <class F>
-KZG_DEV void for_each_naf_digit(const u32 k[8], uint32_t c, F&& f) {
-    const u32 mask = (1u << c) - 1u;
-    const u32 half = 1u << (c - 1);
-    u32 carry = 0;
-    uint32_t p = 0;  // bit offset inside word t (can exceed 32 after a digit)
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const uint64_t win = ((uint64_t)(t < 7 ? k[t + 1] : 0u) << 32) | k[t];
-        while (p < 32) {
-            u32 x = (u32)(win >> p);
-            if (carry) x = ~x;
-            // first position at or after p (inside this word) where bit != carry
-            uint32_t z = x ? (uint32_t)__builtin_ctz(x) : 32u;
-            if (z >= 32u - p) {
-                p = 32;
-                break;
-            }
-            p += z;
-            u32 v = ((u32)(win >> p) & mask) + carry;
-            const bool neg = v > half;
-            const u32 mag = neg ? (mask + 1u - v) : v;
-            carry = neg ? 1u : 0u;
-            f(32u * (uint32_t)t + p, (mag - 1u) >> 1, neg);
-            p += c;
-        }
-        p -= 32;
-    }
-}
-
-template <class F>
-KZG_DEV void for_each_digit(u32 k[8], MsmConfig cfg, F&& f) {
-    if (cfg.recode == kRecodeNaf) for_each_naf_digit(k, cfg.c, f);
-    else for_each_window_digit(k, cfg.c, cfg.W, f);
+// the width a kernel is compiled for, or 0
+static uint32_t fixed_width(MsmConfig cfg) {
+    return cfg.recode == kRecodeWindows && (cfg.c == 15 || cfg.c == 16 || cfg.c == 17 || cfg.c == 19) ? cfg.c : 0u;
 }
 
 // ---- two-level counting sort of the (scalar, window) pairs by bucket -------------------------
 // Scattered global atomics cap out near 2e10/s on MI355X (they execute at the memory side), which made
 // the histogram the second most expensive kernel.  The sort is therefore staged through LDS, in FIVE launches
 // (round 2: twelve -- three of them one-workgroup scans and two three-launch table scans, ~6 us apiece whatever they do):
-//   count    every workgroup takes a tile of scalars, recodes them and histograms the COARSE bin
+//   count    every workgroup takes a tile of scalars, folds them to sign and magnitude (the only field arithmetic of the
+//            sort; the result is kept, 32 bytes per scalar), cuts the digits and histograms the COARSE bin
 //            (bucket >> fine_bits) of each digit in LDS, then takes its range inside every bin with one global atomic
 //            per bin (the offset goes out tile-major [tile][bin]; the fill counters end up as the bin totals)
 //   spread   every workgroup derives its write cursors: a scan over the <= 2048 bin totals in LDS + its offsets (what
 //            two three-launch table scans used to prepare); workgroup 0 also leaves the bin starts and the chunk plan
-//            of the fine passes.  Then the same recoding; LDS cursors hand out positions; (fine key, table reference)
+//            of the fine passes.  Then the digits again, from the folded scalars; LDS cursors hand out positions; (fine key, table reference)
 //            pairs are written into their coarse bin
 //   fine count   the pairs of every coarse bin, in chunks: LDS histogram of the fine key -> H[bin][key][chunk]
 //   bin scan     one workgroup per bin: bins of more than kFineLocal chunks (skewed inputs only) get their H rows
@@ -180,10 +145,23 @@ KZG_DEV void for_each_digit(u32 k[8], MsmConfig cfg, F&& f) {
 // No global atomic per reference (one per tile and bin), no rank array; order inside a bucket is arbitrary (the group law is commutative,
 // the result is bit-identical).
 constexpr int kSortBlock = 256;
-// The two recoding passes run 1024 lanes per workgroup (512 in the staged form of the second): a tile is one workgroup,
-// and with 256 lanes a CU held ONE wave per SIMD walking 16 scalars one after the other -- load, from-Montgomery
-// product, 15 LDS atomics -- with nothing to hide the loads behind (54 + 85 us at 2^20).
-constexpr int kRecodeBlock = 1024;
+// The two recoding passes run 512 lanes per workgroup; a tile is one workgroup, which walks it in strides of 512 scalars.
+// (With 256 lanes a CU held ONE wave per SIMD walking 16 scalars one after the other -- load, from-Montgomery product,
+// 15 LDS atomics -- with nothing to hide the loads behind: 54 + 85 us at 2^20.)  Not 1024: the accumulation kernel's grid is
+// exactly one resident round, two workgroups of 176 VGPRs on every CU, which leave 512 - 352 = 160 VGPRs per SIMD lane
+// and 160 - 2 x 41 = 78 KB of LDS.  A workgroup of another kernel fits BESIDE them only if its waves per SIMD times its
+// allocated VGPRs stay within 160: 1024 lanes are four waves per SIMD, 4 x 64 = 256, which needs a CU that one of its two
+// accumulation workgroups has already left; 512 lanes are 2 x 64 = 128.  (Traced, DESIGN.md 5.0s: the 1024-lane kernel did
+// get such CUs from 60 % into an accumulation on -- the accumulation's workgroups do not retire together -- so this is room
+// the kernel no longer has to wait for, not a start it could never have.)  tests/test_front_residency.py holds every kernel of
+// a commitment's sort to the budget:
+//   k_sort_count                     512 lanes, 60-62 VGPRs (64 allocated: 128 of 160), 8 KB of LDS
+//   k_sort_spread                    512 lanes, 27-34 VGPRs, 10 KB
+//   k_sort_spread_staged             512 lanes, 65 VGPRs (72 allocated: 144 of 160), 71 KB
+//   k_fine_count, k_fine_binscan     256 lanes, 14 VGPRs, 1 KB
+//   k_fine_scatter                   256 lanes, 90 / 95 VGPRs (96), 34 KB
+//   k_sort_small                     1024 lanes: not beside an accumulation (jobs that small have none: k_small_msm)
+constexpr int kRecodeBlock = 512;
 // Tiles (= workgroups of the two recoding passes) per job, at most: they bound the offset table [tile][bin].  512 puts two
 // workgroups on every CU (256: 35 + 87 us for the two passes at 2^20, 512: 35 + 69, 1024: 41 + 78).
 #ifndef KZG_SORT_TILES
@@ -255,9 +233,11 @@ struct BatchGeom {
     uint32_t nb;      // buckets per polynomial
 };
 
+template <uint32_t C>
 __global__ void __launch_bounds__(kRecodeBlock) k_sort_count(const uint32_t* __restrict__ d_scalars, int is_mont,
                                                            BatchGeom bg, MsmConfig cfg, uint32_t tile,
                                                            uint32_t fine_bits, uint32_t coarse_bins,
+                                                           uint32_t* __restrict__ d_recoded /* [batch * n] x 32 B */,
                                                            uint32_t* __restrict__ d_cnt, uint32_t* __restrict__ d_binfill /* zero */,
                                                            uint32_t* __restrict__ d_header) {
     __shared__ u32 s_hist[kMaxCoarse];
@@ -272,9 +252,10 @@ __global__ void __launch_bounds__(kRecodeBlock) k_sort_count(const uint32_t* __r
         uint32_t p = (uint32_t)(g / bg.n);
         uint32_t i = (uint32_t)(g - (uint64_t)p * bg.n);
         u32 k[8];
-        (void)load_scalar(d_scalars, p * bg.stride + i, is_mont, k);
+        const bool flip = load_scalar(d_scalars, p * bg.stride + i, is_mont, k);
+        store_recoded(d_recoded, g, k, flip);
         const u32 pb = p * bg.nb;
-        for_each_digit(k, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_hist[(pb + bkt) >> fine_bits], 1u); });
+        for_each_digit<C>(k, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_hist[(pb + bkt) >> fine_bits], 1u); });
     }
     __syncthreads();
     // Every tile takes its range inside every coarse bin with ONE atomic per bin (256 ... 2048 per workgroup, each
@@ -348,7 +329,8 @@ KZG_DEV void spread_tile_cursors(uint32_t coarse_bins, const uint32_t* __restric
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(kRecodeBlock) k_sort_spread(const uint32_t* __restrict__ d_scalars, int is_mont,
+template <uint32_t C>
+__global__ void __launch_bounds__(kRecodeBlock) k_sort_spread(const uint32_t* __restrict__ d_recoded,
                                                             BatchGeom bg, uint32_t table_stride, MsmConfig cfg,
                                                             uint32_t tile, uint32_t tiles, uint32_t fine_bits,
                                                             uint32_t coarse_bins, const uint32_t* __restrict__ d_cnt /* [tile][bin] */,
@@ -368,9 +350,9 @@ __global__ void __launch_bounds__(kRecodeBlock) k_sort_spread(const uint32_t* __
         uint32_t p = (uint32_t)(g / bg.n);
         uint32_t i = (uint32_t)(g - (uint64_t)p * bg.n);
         u32 k[8];
-        const bool flip = load_scalar(d_scalars, p * bg.stride + i, is_mont, k);
+        const bool flip = load_recoded(d_recoded, g, k);
         const u32 pb = p * bg.nb;
-        for_each_digit(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
+        for_each_digit<C>(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
             u32 b = pb + bkt;
             u32 pos = atomicAdd(&s_cur[b >> fine_bits], 1u);
             u32 ref = (j * table_stride + i) | ((neg != flip) ? 0x80000000u : 0u);
@@ -386,9 +368,10 @@ __global__ void __launch_bounds__(kRecodeBlock) k_sort_spread(const uint32_t* __
 // workgroup takes its tile in rounds of kStageBlock scalars: the round's pairs are counted per bin (LDS atomics), the counts
 // scanned, the pairs placed bin-major into an LDS buffer (the atomics' return values are the slots), and written out by
 // consecutive lanes -- a bin's pairs of one round are contiguous in the bin (the tile's range inside it is), so a wave's 64
-// stores fall into a few runs instead of 64 places.  The digits are cut twice per round (the scalar itself is converted
-// once); order inside a bin is arbitrary as before.  69 us at 2^20 with two workgroups per CU (87 with one: a round is a
-// chain of a global load, a product and two passes of LDS atomics, and eight waves per CU do not hide it).
+// stores fall into a few runs instead of 64 places.  The digits are cut twice per round (from the folded scalar the count
+// pass left); order inside a bin is arbitrary as before.  69 us at 2^20 with two workgroups per CU (87 with one: a round is a
+// chain of a global load, a product -- until the count pass kept the folded scalar -- and two passes of LDS atomics, and
+// eight waves per CU do not hide it).
 constexpr int kStageBlock = 512;
 constexpr uint32_t kStageSlots = 7680;  // pairs per round: 512 scalars x 15 digits (fewer scalars per round when a scalar has more)
 
@@ -416,7 +399,8 @@ KZG_DEV u32 block_exclusive_scan_fast(u32 v, u32* s_wave /* BLOCK / 64 */, u32& 
     return base + incl - v;
 }
 
-__global__ void __launch_bounds__(kStageBlock) k_sort_spread_staged(const uint32_t* __restrict__ d_scalars, int is_mont,
+template <uint32_t C>
+__global__ void __launch_bounds__(kStageBlock) k_sort_spread_staged(const uint32_t* __restrict__ d_recoded,
                                                                   BatchGeom bg, uint32_t table_stride, MsmConfig cfg,
                                                                   uint32_t tile, uint32_t fine_bits, uint32_t coarse_bins,
                                                                   const uint32_t* __restrict__ d_cnt, const uint32_t* __restrict__ d_binfill,
@@ -450,11 +434,8 @@ __global__ void __launch_bounds__(kStageBlock) k_sort_spread_staged(const uint32
             const uint32_t p = (uint32_t)(g / bg.n);
             i = (uint32_t)(g - (uint64_t)p * bg.n);
             pb = p * bg.nb;
-            flip = load_scalar(d_scalars, p * bg.stride + i, is_mont, k);
-            u32 k1[8];
-#pragma unroll
-            for (int w = 0; w < 8; w++) k1[w] = k[w];
-            for_each_digit(k1, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_cnt[(pb + bkt) >> fine_bits], 1u); });
+            flip = load_recoded(d_recoded, g, k);
+            for_each_digit<C>(k, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_cnt[(pb + bkt) >> fine_bits], 1u); });
         }
         __syncthreads();
         // scan of the round's counts: lane t sums its kBinsPerLane consecutive bins, the sums are scanned, then every bin gets
@@ -481,7 +462,7 @@ __global__ void __launch_bounds__(kStageBlock) k_sort_spread_staged(const uint32
         }
         __syncthreads();
         if (valid) {
-            for_each_digit(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
+            for_each_digit<C>(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
                 const u32 b = pb + bkt, bin = b >> fine_bits;
                 const u32 slot = atomicAdd(&s_cnt[bin], 1u);
                 s_stage[slot] = (j * table_stride + i) | ((neg != flip) ? 0x80000000u : 0u) | ((b & fine_mask) << kPackedIndexBits);
@@ -760,7 +741,7 @@ __global__ void __launch_bounds__(kSmallSortBlock) k_sort_small(const uint32_t* 
     for (uint32_t i = t; i < n; i += kSmallSortBlock) {
         u32 k[8];
         (void)load_scalar(d_scalars, i, is_mont, k);
-        for_each_digit(k, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_hist[bkt], 1u); });
+        for_each_digit<0>(k, cfg, [&](uint32_t, u32 bkt, bool) { atomicAdd(&s_hist[bkt], 1u); });
     }
     __syncthreads();
     // exclusive scan of nb <= 4096 counts: each lane owns nb / 1024 consecutive buckets (at least one)
@@ -796,7 +777,7 @@ __global__ void __launch_bounds__(kSmallSortBlock) k_sort_small(const uint32_t* 
     for (uint32_t i = t; i < n; i += kSmallSortBlock) {
         u32 k[8];
         const bool flip = load_scalar(d_scalars, i, is_mont, k);
-        for_each_digit(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
+        for_each_digit<0>(k, cfg, [&](uint32_t j, u32 bkt, bool neg) {
             if (bkt >= b_lo && bkt < b_hi) {
                 u32 pos = atomicAdd(&s_hist[bkt], 1u);
                 d_sorted[pos] = (j * table_stride + i) | ((neg != flip) ? 0x80000000u : 0u);
@@ -807,7 +788,7 @@ __global__ void __launch_bounds__(kSmallSortBlock) k_sort_small(const uint32_t* 
 
 bool launch_bucket_sort(hipStream_t s, const uint32_t* d_scalars, int is_mont, uint32_t n, uint32_t batch,
                         uint64_t stride, uint32_t table_stride, MsmConfig cfg, uint32_t* d_cnt, uint32_t* d_ws,
-                        uint64_t* d_pairs, uint32_t* d_offs, uint32_t* d_sorted, uint32_t* d_header) {
+                        uint64_t* d_pairs, uint32_t* d_recoded, uint32_t* d_offs, uint32_t* d_sorted, uint32_t* d_header) {
     if (n == 0 || batch == 0) return false;
     static const bool small_path = [] { const char* v = std::getenv("KZG_SMALL_SORT"); return !(v && v[0] == '0'); }();
     if (small_path && batch == 1 && n <= kSmallSortScalars && cfg.nb <= kSmallSortBuckets) {
@@ -828,17 +809,29 @@ bool launch_bucket_sort(hipStream_t s, const uint32_t* d_scalars, int is_mont, u
     const uint32_t ch = fine_chunk_len(max_pairs);
     const uint32_t max_chunks = (uint32_t)((max_pairs + ch - 1) / ch) + g.coarse_bins;  // <= kFineMaxChunks
     uint32_t* d_binfill = d_ws + kWsBinFill;
-    hipLaunchKernelGGL(k_sort_count, dim3(g.tiles), dim3(kRecodeBlock), 0, s, d_scalars, is_mont, bg, cfg, g.tile,
-                       g.fine_bits, g.coarse_bins, d_cnt, d_binfill, d_header);
     static const bool staged = [] { const char* v = std::getenv("KZG_SPREAD_STAGED"); return !(v && v[0] == '0'); }();
-    if (g.packed && staged && cfg.max_digits <= kStageSlots)
-        hipLaunchKernelGGL(k_sort_spread_staged, dim3(g.tiles), dim3(kStageBlock), 0, s, d_scalars, is_mont, bg, table_stride, cfg,
-                           g.tile, g.fine_bits, g.coarse_bins, d_cnt, d_binfill, ch, d_binstart, d_prefix, d_total,
-                           reinterpret_cast<uint32_t*>(d_pairs));
-    else
-        hipLaunchKernelGGL(k_sort_spread, dim3(g.tiles), dim3(kRecodeBlock), 0, s, d_scalars, is_mont, bg, table_stride, cfg,
-                           g.tile, g.tiles, g.fine_bits, g.coarse_bins, d_cnt, d_binfill, ch, d_binstart, d_prefix, d_total, d_pairs,
-                           g.packed ? 1 : 0);
+    const bool use_staged = g.packed && staged && cfg.max_digits <= kStageSlots;
+    // the three recoding kernels, compiled for the window width (one dispatch per job, nothing per scalar)
+    auto recode = [&](auto width) {
+        constexpr uint32_t C = decltype(width)::value;
+        hipLaunchKernelGGL(k_sort_count<C>, dim3(g.tiles), dim3(kRecodeBlock), 0, s, d_scalars, is_mont, bg, cfg, g.tile, g.fine_bits,
+                           g.coarse_bins, d_recoded, d_cnt, d_binfill, d_header);
+        if (use_staged)
+            hipLaunchKernelGGL(k_sort_spread_staged<C>, dim3(g.tiles), dim3(kStageBlock), 0, s, d_recoded, bg, table_stride, cfg,
+                               g.tile, g.fine_bits, g.coarse_bins, d_cnt, d_binfill, ch, d_binstart, d_prefix, d_total,
+                               reinterpret_cast<uint32_t*>(d_pairs));
+        else
+            hipLaunchKernelGGL(k_sort_spread<C>, dim3(g.tiles), dim3(kRecodeBlock), 0, s, d_recoded, bg, table_stride, cfg, g.tile,
+                               g.tiles, g.fine_bits, g.coarse_bins, d_cnt, d_binfill, ch, d_binstart, d_prefix, d_total, d_pairs,
+                               g.packed ? 1 : 0);
+    };
+    switch (fixed_width(cfg)) {
+        case 15: recode(std::integral_constant<uint32_t, 15>()); break;
+        case 16: recode(std::integral_constant<uint32_t, 16>()); break;
+        case 17: recode(std::integral_constant<uint32_t, 17>()); break;
+        case 19: recode(std::integral_constant<uint32_t, 19>()); break;
+        default: recode(std::integral_constant<uint32_t, 0>()); break;
+    }
     if (g.packed)
         hipLaunchKernelGGL(k_fine_count<true>, dim3(max_chunks), dim3(kSortBlock), 0, s, reinterpret_cast<const uint32_t*>(d_pairs),
                            d_binstart, g.fine_bits, g.coarse_bins, ch, d_prefix, d_table, d_binfill);

@@ -569,6 +569,66 @@ int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t
                              const uint64_t gamma[4], const uint64_t* gate_coset, unsigned log_ext, uint64_t* out_coeffs,
                              uint64_t* out_p1s);
 
+/* ---- a circuit's key resident on the device: the quotient with the arithmetic gate built in -----------
+ * Domain, coset and notation are those above.  A circuit has t wire columns, KZG_CIRCUIT_MIN_COLUMNS <= t <= KZG_PQ_MAX_COLUMNS,
+ * t linear selectors q_0 .. q_(t-1), a multiplication selector q_M, a constant selector q_C and t permutation columns sigma_j with
+ * shifts k_j.  With the wires f_j, public inputs PI (n values over H, or NULL; added as given: textbook PLONK passes -x_i) and an
+ * optional term G' of the caller's (N values on the coset, or NULL: lookups, custom gates):
+ *     Gate(X) = sum_j q_j(X) f_j(X) + q_M(X) f_0(X) f_1(X) + q_C(X) + PI(X) + G'(X)
+ *     Num(X)  = Gate(X) + alpha [ z(X) prod_j (f_j + beta k_j X + gamma) - z(w X) prod_j (f_j + beta sigma_j + gamma) ]
+ *                       + alpha^2 (z(X) - 1) L_0(X),          T(X) = Num(X) / (X^n - 1).
+ * The gate's degree is 3 (n - 1) <= (t + 1)(n - 1), so e >= t + 1 as above, and the divisibility test is the same.
+ *
+ * kzg_circuit_create uploads the 2 t + 2 columns ONCE (q_lin, sigmas: t columns of n values, column j at base + 4 j stride u64;
+ * q_mul, q_const: n values) and keeps, in device buffers of the circuit's own, three forms of each -- the n values, the n
+ * coefficients and the N = 2^log_ext n values on the coset -- with the N coset values of L_0 and the e inverses of Z_H.  EVERY
+ * resident column, in every form, is stored as blst_fr images (the coset form is bit for bit what kzg_coset_extend returns).
+ * Device memory: (2 t + 3) N x 32 bytes on the coset plus 2 (2 t + 2) n x 32 bytes of values and coefficients; at n = 2^20,
+ * e = 4, t = 3 that is 9 x 128 MiB + 2 x 8 x 32 MiB = 1.625 GiB.  The columns are ordered q_lin[0..t), q_mul, q_const,
+ * sigma[0..t): within each form they are contiguous at stride n (N for the coset form), so ONE kzg_open_combined_submit or
+ * kzg_open_sets_submit over the coefficient form covers all the selectors, all the sigmas, or all 2 t + 2 columns.
+ * out_key_p1s: NULL, or (2 t + 2) x 18 u64 that receive the commitments of the columns in that order, each bit for bit
+ * kzg_commit_evaluations of the column (batched MSMs, kzg_max_batch columns per job).
+ * KZG_ERR_INVALID_ARG: t < 2, t > KZG_PQ_MAX_COLUMNS, t + 1 > 2^log_ext, log_ext > KZG_PQ_MAX_LOG_EXT, n not a power of two,
+ * N > 2^KZG_NTT_MAX_LOG, stride < n, a NULL required pointer.  With out_key_p1s: no SRS -> KZG_ERR_NO_SRS, n > kzg_srs_len ->
+ * KZG_ERR_DEGREE_TOO_HIGH, and kzg_commit_lagrange's multi-device rules (a range-split context -> KZG_ERR_INVALID_ARG).  On a
+ * multi-device context the circuit lives on devices[0] and the handle remembers it.  A failed call leaves nothing allocated and
+ * *out NULL.  kzg_ctx_destroy frees the circuits still alive on the context; kzg_circuit_destroy waits for a running quotient.
+ *
+ * kzg_circuit_quotient extends only what changes per proof -- the t wires (t columns of n values, stride >= n), z and PI -- and
+ * returns T as kzg_permutation_quotient does: out_coeffs (NULL, or N - n coefficients) and out_p1s (NULL, or (e - 1) x 18 u64, the
+ * commitments of the chunks of n coefficients, bit for bit kzg_commit of each chunk).  KZG_ERR_REMAINDER when the gate or the
+ * permutation does not hold on H.  A circuit made on another context -> KZG_ERR_INVALID_ARG.  With out_p1s: KZG_ERR_NO_SRS,
+ * KZG_ERR_DEGREE_TOO_HIGH and the multi-device rules as above.  The _device form takes kzg_dev_alloc buffers of a single-device
+ * context (d_wires, d_z, d_public_inputs: values over H; d_gate_coset: N values), returns when T's N - n coefficients are in
+ * d_out_coeffs, and its output may overlap no input.
+ *
+ * kzg_circuit_column_device hands out a resident column, read-only: which = KZG_CIRCUIT_COL_QLIN + j, KZG_CIRCUIT_COL_QM,
+ * KZG_CIRCUIT_COL_QC, KZG_CIRCUIT_COL_SIGMA + j (j < t) or KZG_CIRCUIT_COL_L0 (coset form only); *len receives n or N.  The
+ * pointer is valid until the circuit is destroyed and belongs to the device the circuit lives on. */
+typedef struct kzg_circuit kzg_circuit;
+#define KZG_CIRCUIT_MIN_COLUMNS 2
+#define KZG_CIRCUIT_COL_QLIN 0
+#define KZG_CIRCUIT_COL_QM 16
+#define KZG_CIRCUIT_COL_QC 17
+#define KZG_CIRCUIT_COL_SIGMA 32
+#define KZG_CIRCUIT_COL_L0 48
+#define KZG_CIRCUIT_VALUES 0
+#define KZG_CIRCUIT_COEFFS 1
+#define KZG_CIRCUIT_COSET 2
+int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                       size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, uint64_t* out_key_p1s,
+                       kzg_circuit** out);
+int kzg_circuit_destroy(kzg_ctx* ctx, kzg_circuit* circuit);
+int kzg_circuit_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                         const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                         const uint64_t* gate_coset, uint64_t* out_coeffs, uint64_t* out_p1s);
+int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                const void* d_public_inputs, const uint64_t alpha[4], const uint64_t beta[4],
+                                const uint64_t gamma[4], const void* d_gate_coset, void* d_out_coeffs);
+int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned which, unsigned form, const void** d_ptr,
+                              size_t* len);
+
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
  * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what

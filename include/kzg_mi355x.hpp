@@ -14,6 +14,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kzg_mi355x.h"
@@ -486,6 +487,77 @@ struct Wire {
         out.pop_back();
         return out;
     }
+};
+
+// A circuit's key resident on the device (kzg_circuit_create): move-only owner of the handle.  Columns are
+// n Scalars each, the t columns of q_lin / sigmas / wires back to back; the setup must outlive the circuit.
+class Circuit {
+   public:
+    Circuit(const SetupArtifacts& setup, const std::vector<Scalar>& q_lin, const std::vector<Scalar>& q_mul,
+            const std::vector<Scalar>& q_const, const std::vector<Scalar>& sigmas, const std::vector<Scalar>& shifts, unsigned log_ext,
+            bool want_key = true)
+        : ctx_(setup.ctx()), n_(q_mul.size()), t_(shifts.size()), log_ext_(log_ext) {
+        if (q_lin.size() != n_ * t_ || sigmas.size() != n_ * t_ || q_const.size() != n_)
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit: t columns of n values in q_lin and sigmas, n values in q_mul and q_const");
+        if (want_key) key_.resize(2 * t_ + 2);
+        const auto u = [](const std::vector<Scalar>& v) { return reinterpret_cast<const uint64_t*>(v.data()); };
+        const int rc = kzg_circuit_create(ctx_, u(q_lin), u(q_mul), u(q_const), u(sigmas), n_, t_, n_, u(shifts), log_ext,
+                                          want_key ? reinterpret_cast<uint64_t*>(key_.data()) : nullptr, &c_);
+        if (rc != KZG_OK) throw Error(rc, std::string(kzg_strerror(rc)) + ": " + kzg_last_error(ctx_));
+    }
+    ~Circuit() { if (c_) kzg_circuit_destroy(ctx_, c_); }
+    Circuit(const Circuit&) = delete;
+    Circuit& operator=(const Circuit&) = delete;
+    Circuit(Circuit&& o) noexcept : ctx_(o.ctx_), c_(o.c_), n_(o.n_), t_(o.t_), log_ext_(o.log_ext_), key_(std::move(o.key_)) { o.c_ = nullptr; }
+    Circuit& operator=(Circuit&& o) noexcept {
+        if (this != &o) {
+            if (c_) kzg_circuit_destroy(ctx_, c_);
+            ctx_ = o.ctx_, c_ = o.c_, n_ = o.n_, t_ = o.t_, log_ext_ = o.log_ext_, key_ = std::move(o.key_);
+            o.c_ = nullptr;
+        }
+        return *this;
+    }
+    // the commitments of q_lin[0..t), q_mul, q_const, sigma[0..t) (empty without want_key)
+    const std::vector<G1Point>& key() const { return key_; }
+    size_t n() const { return n_; }
+    size_t t() const { return t_; }
+    const kzg_circuit* handle() const { return c_; }
+    struct Quotient {
+        std::vector<Scalar> coeffs;       // T: (2^log_ext - 1) n coefficients
+        std::vector<G1Point> commitments; // of its chunks of n coefficients
+    };
+    // public_inputs: empty or n values; gate_coset: empty or 2^log_ext n values of the caller's own term
+    Quotient quotient(const std::vector<Scalar>& wires, const std::vector<Scalar>& z, const Scalar& alpha, const Scalar& beta,
+                      const Scalar& gamma, const std::vector<Scalar>& public_inputs = {}, const std::vector<Scalar>& gate_coset = {},
+                      bool want_commitments = true) const {
+        const size_t e = (size_t)1 << log_ext_;
+        if (wires.size() != n_ * t_ || z.size() != n_ || (!public_inputs.empty() && public_inputs.size() != n_) ||
+            (!gate_coset.empty() && gate_coset.size() != e * n_))
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit::quotient: column sizes");
+        Quotient out;
+        out.coeffs.resize((e - 1) * n_);
+        if (want_commitments) out.commitments.resize(e - 1);
+        const auto u = [](const std::vector<Scalar>& v) { return v.empty() ? nullptr : reinterpret_cast<const uint64_t*>(v.data()); };
+        const int rc = kzg_circuit_quotient(ctx_, c_, u(wires), n_, u(z), u(public_inputs), alpha.l.data(), beta.l.data(), gamma.l.data(),
+                                            u(gate_coset), out.coeffs.empty() ? nullptr : reinterpret_cast<uint64_t*>(out.coeffs.data()),
+                                            want_commitments ? reinterpret_cast<uint64_t*>(out.commitments.data()) : nullptr);
+        if (rc != KZG_OK) throw Error(rc, std::string(kzg_strerror(rc)) + ": " + kzg_last_error(ctx_));
+        return out;
+    }
+    // a resident column on the device, read-only: (pointer, length)
+    std::pair<const void*, size_t> column_device(unsigned which, unsigned form) const {
+        const void* p = nullptr;
+        size_t len = 0;
+        check(kzg_circuit_column_device(ctx_, c_, which, form, &p, &len), ctx_);
+        return {p, len};
+    }
+
+   private:
+    kzg_ctx* ctx_ = nullptr;
+    kzg_circuit* c_ = nullptr;
+    size_t n_ = 0, t_ = 0;
+    unsigned log_ext_ = 0;
+    std::vector<G1Point> key_;
 };
 
 }  // namespace kzg_api

@@ -20,6 +20,8 @@ __all__ = [
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS", "KZG_LOGUP_MAX_COLUMNS",
     "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
+    "Circuit", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
+    "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
@@ -79,6 +81,7 @@ ABI_SYMBOLS = [
     "kzg_lookup_multiplicities_cap",
     "kzg_coset_extend", "kzg_coset_extend_device", "kzg_permutation_constraints_coset", "kzg_permutation_constraints_coset_device",
     "kzg_vanishing_quotient", "kzg_vanishing_quotient_device", "kzg_permutation_quotient",
+    "kzg_circuit_create", "kzg_circuit_destroy", "kzg_circuit_quotient", "kzg_circuit_quotient_device", "kzg_circuit_column_device",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -94,6 +97,9 @@ KZG_LOGUP_MAX_COLUMNS = 16  # columns per side of a log-derivative sum (a lookup
 KZG_PQ_MAX_COLUMNS = 7   # wire columns of a permutation quotient (t + 1 <= 2^KZG_PQ_MAX_LOG_EXT)
 KZG_PQ_MAX_LOG_EXT = 3
 KZG_EXTEND_VALUES, KZG_EXTEND_COEFFS = 0, 1
+KZG_CIRCUIT_MIN_COLUMNS = 2  # wire columns of a circuit with the built-in arithmetic gate (f_0 f_1 needs two)
+KZG_CIRCUIT_COL_QLIN, KZG_CIRCUIT_COL_QM, KZG_CIRCUIT_COL_QC, KZG_CIRCUIT_COL_SIGMA, KZG_CIRCUIT_COL_L0 = 0, 16, 17, 32, 48
+KZG_CIRCUIT_VALUES, KZG_CIRCUIT_COEFFS, KZG_CIRCUIT_COSET = 0, 1, 2
 KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
@@ -224,6 +230,11 @@ def load_library():
         "kzg_vanishing_quotient": (i, [vp, vp, sz, sz, i, vp]),
         "kzg_vanishing_quotient_device": (i, [vp, vp, sz, sz, i, vp]),
         "kzg_permutation_quotient": (i, [vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.c_uint, vp, vp]),
+        "kzg_circuit_create": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, C.POINTER(vp)]),
+        "kzg_circuit_destroy": (i, [vp, vp]),
+        "kzg_circuit_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_quotient_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_column_device": (i, [vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(sz)]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1486,6 +1497,24 @@ class Engine:
                                                   None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
         return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
 
+    # -- a circuit's key resident on the device: the quotient with the arithmetic gate built in --
+    def circuit_create(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, n=None, want_key=True):
+        """kzg_circuit_create: q_lin, sigmas (t, stride, 4) arrays whose first n rows per column count (n=None: all), q_mul and
+        q_const (n, 4) arrays, shifts t Scalars -> a Circuit.  want_key: commit the 2 t + 2 columns (needs the SRS); they are
+        Circuit.key in the order q_lin[0..t), q_mul, q_const, sigma[0..t)"""
+        a, t, stride, n = self._columns(q_lin, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        qm = np.ascontiguousarray(q_mul, dtype=np.uint64).reshape(-1, 4)
+        qc = np.ascontiguousarray(q_const, dtype=np.uint64).reshape(-1, 4)
+        assert qm.shape[0] >= n and qc.shape[0] >= n
+        sh = np.ascontiguousarray([k.limbs() for k in shifts], dtype=np.uint64).reshape(-1, 4)
+        assert sh.shape[0] == t, "one coset shift per column"
+        p1s = np.zeros((2 * t + 2, 18), dtype=np.uint64) if want_key else None
+        h = C.c_void_p()
+        self._pq_check(self._lib.kzg_circuit_create(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh), log_ext,
+                                                    None if p1s is None else _ptr(p1s), C.byref(h)))
+        return Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
+
     # -- device-resident, pipelined --
     def num_slots(self):
         return int(self._lib.kzg_num_slots(self._h))
@@ -1614,6 +1643,57 @@ class Engine:
 # first n artifacts -- on the device, G1 side -- and returns the engine that now holds them; the
 # reference's `Vec<SetupArtifact>` argument of commit / generate_proof becomes that engine.
 # ---------------------------------------------------------------------------------------------
+class Circuit:
+    """A circuit's key resident on the device (kzg_circuit_create).  key: the commitments of its 2 t + 2 columns, or None.  The
+    handle lives until close() or until its Engine is closed, whichever comes first."""
+
+    def __init__(self, engine, handle, n, t, log_ext, key):
+        self._eng, self._c = engine, handle
+        self.n, self.t, self.log_ext, self.key = n, t, log_ext, key
+
+    def close(self):
+        if getattr(self, "_c", None) and getattr(self._eng, "_h", None):
+            self._eng._pq_check(self._eng._lib.kzg_circuit_destroy(self._eng._h, self._c))
+        self._c = None
+
+    def quotient(self, wires, z, alpha, beta, gamma, public_inputs=None, gate=None, n=None, want_coeffs=True, want_commitments=True,
+                 engine=None):
+        """kzg_circuit_quotient: wires a (t, stride, 4) array, z (n, 4), public_inputs None or (n, 4), gate None or the (N, 4)
+        values of the caller's own term on the coset -> (T's coefficients (N - n, 4) or None, the list of its chunks' commitments
+        or None).  engine: the context the call is made on (the circuit's own unless given)"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n
+        N = n << self.log_ext
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert pi is None or pi.shape[0] >= n
+        g = None if gate is None else np.ascontiguousarray(gate, dtype=np.uint64).reshape(N, 4)
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        coeffs = np.zeros((N - n, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros(((1 << self.log_ext) - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_quotient(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi), _ptr(al),
+                                                _ptr(bl), _ptr(gl), None if g is None else _ptr(g),
+                                                None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def quotient_device(self, d_wires, d_z, alpha, beta, gamma, d_out_coeffs, d_public_inputs=None, d_gate=None, stride=None):
+        """kzg_circuit_quotient_device on kzg_dev_alloc buffers: T's N - n coefficients land in d_out_coeffs"""
+        e = self._eng
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        e._pq_check(e._lib.kzg_circuit_quotient_device(e._h, self._c, C.c_void_p(d_wires), self.n if stride is None else stride,
+                                                       C.c_void_p(d_z), C.c_void_p(d_public_inputs), _ptr(al), _ptr(bl), _ptr(gl),
+                                                       C.c_void_p(d_gate), C.c_void_p(d_out_coeffs)))
+
+    def column_device(self, which, form):
+        """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
+        e = self._eng
+        p, ln = C.c_void_p(), C.c_size_t(0)
+        e._pq_check(e._lib.kzg_circuit_column_device(e._h, self._c, which, form, C.byref(p), C.byref(ln)))
+        return p.value, int(ln.value)
+
+
 class SetupArtifactsGenerator:
     def __init__(self, secret_be, device=0):
         assert len(secret_be) == 32

@@ -349,6 +349,26 @@ struct kzg_ctx {
     std::mutex quotient_mu;
     Workspace<11> pq_ws;
     uint32_t pq_zinv_key = ~0u;  // (log n << 8) | log rot of the inverses of Z_H held in pq_ws, ~0: none
+    // the circuits alive on this context (kzg_circuit_create), under quotient_mu: kzg_ctx_destroy frees
+    // what the caller left
+    std::vector<kzg_circuit*> circuits;
+};
+
+// A circuit's key: the 2 t + 2 columns q_lin[0..t), q_mul, q_const, sigma[0..t) in that order, in three
+// forms, every one as blst_fr images and every buffer the circuit's own, written by kzg_circuit_create and read-only afterwards.
+// `owner` is the single-device context it lives on (devices[0]'s for a multi-device context).
+struct kzg_circuit {
+    kzg_ctx* owner = nullptr;
+    uint32_t lg_n = 0, lg_ext = 0;
+    size_t n = 0, t = 0;
+    uint64_t shifts[4 * kPqMaxColumns] = {};
+    DevBuf values;  // (2 t + 2) x n
+    DevBuf coeffs;  // (2 t + 2) x n
+    DevBuf coset;   // (2 t + 2) x N
+    DevBuf l0;      // the N values of L_0 on the coset
+    DevBuf zinv;    // the rot stored multipliers 1 / Z_H(x_i): the circuit's own copy, independent of pq_zinv_key
+    size_t N() const { return n << lg_ext; }
+    size_t cols() const { return 2 * t + 2; }
 };
 
 namespace {
@@ -938,6 +958,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
         if (st) hipStreamSynchronize(st);
     for (hipStream_t st : {ctx->upload_stream, ctx->front_stream, ctx->heavy_stream, ctx->tail_stream})
         if (st) hipStreamDestroy(st);
+    for (kzg_circuit* c : ctx->circuits) delete c;  // (nothing runs any more: the streams were waited for)
     delete ctx;
 }
 
@@ -5194,6 +5215,27 @@ int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, ui
 }
 }  // namespace
 
+// `chunks` vectors of n coefficients (vector c at d_coef + 8 c n words, resident until the call returns) committed over the
+// monomial SRS on the caller's reserved slot: batched MSMs, as many vectors per job as the slot holds
+static int pq_commit_chunks(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot, const uint32_t* d_coef, size_t n, size_t chunks,
+                            uint64_t* out_p1s) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the wait for a slot dropped the mutex: the SRS may have changed)
+    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    Slot& s = ctx->slots[slot];
+    const size_t group = std::min<size_t>(chunks, ctx->max_batch ? ctx->max_batch : 1);
+    for (size_t c0 = 0; c0 < chunks; c0 += group) {
+        const size_t g = chunks - c0 < group ? chunks - c0 : group;
+        const uint32_t* d_chunk = d_coef + 8 * c0 * n;
+        int rc = g == 1 ? submit_commit_locked(ctx, slot, d_chunk, 1, n, true, true) : commit_batch_submit_locked(ctx, slot, d_chunk, n, g, n, true);
+        if (rc) return rc;
+        await_unlocked(lk, s);
+        rc = g == 1 ? wait_locked(ctx, slot, out_p1s + 18 * c0) : wait_batch_locked(ctx, slot, out_p1s + 18 * c0, g);
+        s.kind = SLOT_RESERVED;  // (the mutex was held since the wait marked it idle)
+        if (rc) return rc;
+    }
+    return KZG_OK;
+}
+
 static int coset_extend_impl(kzg_ctx* ctx, const void* in, size_t len, size_t batch, size_t stride, unsigned form, unsigned log_out,
                              void* out, bool device) {
     uint32_t lg_len = 0;
@@ -5441,21 +5483,263 @@ int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t
     if (rc) return rc;
     if (hflag) return pq_remainder(ctx, sh);
     if (!out_p1s) return KZG_OK;
-    // chunk c = coefficients [c n, (c + 1) n): batched MSMs over the monomial SRS, as many chunks per job as the slot holds
-    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the wait for a slot dropped the mutex: the SRS may have changed)
-    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
-    const size_t chunks = sh.rot - 1, group = std::min<size_t>(chunks, ctx->max_batch ? ctx->max_batch : 1);
-    for (size_t c0 = 0; c0 < chunks; c0 += group) {
-        const size_t g = chunks - c0 < group ? chunks - c0 : group;
-        const uint32_t* d_chunk = (const uint32_t*)coef + 8 * c0 * n;
-        rc = g == 1 ? submit_commit_locked(ctx, slot, d_chunk, 1, n, true, true) : commit_batch_submit_locked(ctx, slot, d_chunk, n, g, n, true);
-        if (rc) return rc;
-        await_unlocked(lk, s);
-        rc = g == 1 ? wait_locked(ctx, slot, out_p1s + 18 * c0) : wait_batch_locked(ctx, slot, out_p1s + 18 * c0, g);
-        s.kind = SLOT_RESERVED;  // (the mutex was held since the wait marked it idle)
-        if (rc) return rc;
+    return pq_commit_chunks(ctx, lk, slot, (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
+}
+
+// ---- a circuit's key resident on the device (circuit_kernels.hip) -----------------------------------------
+// The calls hold quotient_mu, then the context's mutex and one slot, as the quotient's calls above; the per-proof columns live in
+// pq_ws, the circuit's buffers are written by kzg_circuit_create alone.
+static size_t circuit_column_index(const kzg_circuit* c, unsigned which) {
+    if (which >= KZG_CIRCUIT_COL_QLIN && which < KZG_CIRCUIT_COL_QLIN + c->t) return which - KZG_CIRCUIT_COL_QLIN;
+    if (which == KZG_CIRCUIT_COL_QM) return c->t;
+    if (which == KZG_CIRCUIT_COL_QC) return c->t + 1;
+    if (which >= KZG_CIRCUIT_COL_SIGMA && which < KZG_CIRCUIT_COL_SIGMA + c->t) return c->t + 2 + (which - KZG_CIRCUIT_COL_SIGMA);
+    return (size_t)-1;
+}
+// is `c` a circuit alive on the single-device context `ctx` (quotient_mu held)?
+static bool circuit_alive(kzg_ctx* ctx, const kzg_circuit* c) {
+    return c && std::find(ctx->circuits.begin(), ctx->circuits.end(), c) != ctx->circuits.end();
+}
+static int circuit_foreign(kzg_ctx* ctx) {
+    ctx->last_error = "circuit: the handle is not a circuit alive on this context";
+    return KZG_ERR_INVALID_ARG;
+}
+
+// the body of kzg_circuit_create on a single-device context (quotient_mu held): fills *c, whose buffers go with it on failure
+static int circuit_build(kzg_ctx* ctx, kzg_circuit* c, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul,
+                         const uint64_t* q_const, const uint64_t* sigmas, size_t stride, uint64_t* out_key_p1s) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    const size_t n = sh.n, N = sh.N, t = c->t, ncols = c->cols();
+    if (out_key_p1s) {
+        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
     }
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    rc = pq_bufs(ctx, N, ncols, &w);
+    if (rc == KZG_OK) rc = c->values.reserve(ctx, ncols * n * 32);
+    if (rc == KZG_OK) rc = c->coeffs.reserve(ctx, ncols * n * 32);
+    if (rc == KZG_OK) rc = c->coset.reserve(ctx, ncols * N * 32);
+    if (rc == KZG_OK) rc = c->l0.reserve(ctx, N * 32);
+    if (rc == KZG_OK) rc = c->zinv.reserve(ctx, 8 * 32);
+    if (rc) return rc;
+    uint32_t *d_val = c->values.dev(), *d_coef = c->coeffs.dev();
+    rc = pq_upload(ctx, lk, s.stream, d_val, q_lin, n, t, stride);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * t * n, q_mul, n, 1, n);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (t + 1) * n, q_const, n, 1, n);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (t + 2) * n, sigmas, n, t, stride);
+    if (rc) return rc;
+    // values -> coefficients (the inverse transform the extension needs anyway, kept) -> the coset
+    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+    const hf::Fr inv_n_fr = hf::fr_inv(fr_pow2(sh.lg_n));
+    const Fr30 inv_n_mul = fr30_arg_from_mont256(inv_n_fr);
+    for (size_t b = 0; b < ncols; b++) launch_ntt(s.stream, d_val + 8 * b * n, d_coef + 8 * b * n, sh.lg_n, itw, inv_n_mul, w.A, w.B);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = pq_extend(ctx, s.stream, d_coef, n, n, -1, ncols, sh.lg_N, c->coset.dev(), w);
+    // L_0 = (1 / n) (1 + X + .. + X^(n-1)): from n equal coefficients
+    const Fr30 inv_n = pq_image(inv_n_fr);
+    if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, nullptr, 0, n, -1, 1, sh.lg_N, c->l0.dev(), w, &inv_n);
+    if (rc) return rc;
+    // the rot stored multipliers 1 / Z_H(x_i), Z_H(x_i) = g^n w_rot^(i mod rot) - 1 (as pq_upload_zinv makes them)
+    uint64_t h[8][4];
+    const hf::Fr we = hf::fr_domain_root(sh.lg_ext), k14 = fr_pow2(14);
+    hf::Fr cur = hf::fr_pow(fr_seven(), sh.n);
+    for (size_t k = 0; k < sh.rot; k++) {
+        const hf::Fr stored = hf::fr_mul(hf::fr_inv(hf::fr_sub(cur, hf::kFrOne)), k14);
+        std::memcpy(h[k], stored.l, 32);
+        cur = hf::fr_mul(cur, we);
+    }
+    rc = copy_unlocked(ctx, lk, s.stream, c->zinv.p, h, sh.rot * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (vanishing inverses)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit key");  // (h leaves scope)
+    if (rc || !out_key_p1s) return rc;
+    return pq_commit_chunks(ctx, lk, slot, d_coef, n, ncols, out_key_p1s);
+}
+
+int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                       size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, uint64_t* out_key_p1s,
+                       kzg_circuit** out) {
+    if (out) *out = nullptr;
+    PqShape sh;
+    if (!ctx || !out || log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS ||
+        t > kPqMaxColumns || t + 1 > sh.rot || stride < n || !q_lin || !q_mul || !q_const || !sigmas || !shifts)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        // without the key's commitments the call needs no SRS; with them it follows kzg_commit_lagrange
+        if (out_key_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the key's commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_create(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, out_key_p1s, out));
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    kzg_circuit* c = new kzg_circuit();
+    c->owner = ctx;
+    c->lg_n = sh.lg_n;
+    c->lg_ext = sh.lg_ext;
+    c->n = n;
+    c->t = t;
+    std::memcpy(c->shifts, shifts, 32 * t);
+    int rc = circuit_build(ctx, c, sh, q_lin, q_mul, q_const, sigmas, stride, out_key_p1s);
+    if (rc) {
+        (void)hipSetDevice(ctx->device);
+        delete c;  // (circuit_build drained the stream before it returned)
+        return rc;
+    }
+    ctx->circuits.push_back(c);
+    *out = c;
     return KZG_OK;
+}
+
+int kzg_circuit_destroy(kzg_ctx* ctx, kzg_circuit* circuit) {
+    if (!ctx || !circuit) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_destroy(kid, circuit));
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);  // no quotient runs on it now
+    if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // a caller may still have work of its own queued on the columns it was handed (an opening over the coefficients)
+    for (hipStream_t st : {ctx->front_stream, ctx->heavy_stream, ctx->tail_stream})
+        if (st) HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->circuits.erase(std::find(ctx->circuits.begin(), ctx->circuits.end(), circuit));
+    delete circuit;
+    return KZG_OK;
+}
+
+int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned which, unsigned form, const void** d_ptr, size_t* len) {
+    if (!ctx || !circuit || !d_ptr || !len) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_column_device(kid, circuit, which, form, d_ptr, len));
+    }
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
+    const size_t n = circuit->n, N = circuit->N();
+    if (which == KZG_CIRCUIT_COL_L0) {
+        if (form != KZG_CIRCUIT_COSET) return KZG_ERR_INVALID_ARG;
+        *d_ptr = circuit->l0.p;
+        *len = N;
+        return KZG_OK;
+    }
+    const size_t col = circuit_column_index(circuit, which);
+    if (col == (size_t)-1 || form > KZG_CIRCUIT_COSET) return KZG_ERR_INVALID_ARG;
+    const DevBuf& b = form == KZG_CIRCUIT_VALUES ? circuit->values : (form == KZG_CIRCUIT_COEFFS ? circuit->coeffs : circuit->coset);
+    *len = form == KZG_CIRCUIT_COSET ? N : n;
+    *d_ptr = b.dev() + 8 * col * *len;
+    return KZG_OK;
+}
+
+// wires (t columns of n values), z, pi (n values or null) and gate (N values or null) are host pointers, or device pointers
+// when `device`; then out_coeffs is a device pointer and out_p1s null
+static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
+                                 const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const void* gate, void* out_coeffs,
+                                 uint64_t* out_p1s, bool device) {
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    PqShape sh;
+    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, N = sh.N, t = c->t, ncols = t + 1 + (pi ? 1 : 0);
+    if (device) {
+        const size_t ob = (N - n) * 32;
+        if (pq_overlap(out_coeffs, ob, wires, ((t - 1) * stride + n) * 32) || pq_overlap(out_coeffs, ob, z, n * 32) ||
+            (pi && pq_overlap(out_coeffs, ob, pi, n * 32)) || (gate && pq_overlap(out_coeffs, ob, gate, N * 32))) {
+            ctx->last_error = "circuit quotient: the output overlaps an input";
+            return KZG_ERR_INVALID_ARG;
+        }
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (out_p1s) {
+        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    }
+    int slot = -1;
+    int rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *d_gate = const_cast<void*>(gate);
+    rc = pq_bufs(ctx, N, ncols, &w);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqIn, ncols * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, ncols * N * 32, &cols);  // wires, z, PI
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
+    if (rc == KZG_OK && gate && !device) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc) return rc;
+    uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
+    if (device) {
+        rc = pq_extend(ctx, s.stream, (const uint32_t*)wires, stride, n, (int)sh.lg_n, t, sh.lg_N, d_w, w);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)z, n, n, (int)sh.lg_n, 1, sh.lg_N, d_z, w);
+        if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, (const uint32_t*)pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
+    } else {
+        uint32_t* d_in = (uint32_t*)in;
+        rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
+        if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)z, n, 1, n);
+        if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (t + 1) * n, (const uint64_t*)pi, n, 1, n);
+        if (rc == KZG_OK && gate) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_gate, (const uint64_t*)gate, N, 1, N);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, d_in, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
+    }
+    if (rc) return rc;
+    {
+        const hf::Fr a = pq_fr(alpha), b = pq_fr(beta), g = fr_seven();
+        const Fr30 f_beta = fr30_arg_from_mont256(b), f_gamma = pq_image(pq_fr(gamma)), f_one = pq_image(hf::kFrOne);
+        const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2((uint32_t)(14 * t))));
+        const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), fr_pow2(14)));
+        const Fr30 k14 = fr30_arg_from_mont256(fr_pow2(14));
+        Fr30 bkg[kPqMaxColumns];
+        for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(b, pq_fr(c->shifts + 4 * j)), g));
+        const uint32_t* key = c->coset.dev();
+        const CkColumns ck{d_w, key, key + 8 * (t + 2) * N, key + 8 * t * N, key + 8 * (t + 1) * N, d_z, c->l0.dev(), d_pi,
+                           (const uint32_t*)d_gate, c->zinv.dev()};
+        const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
+        launch_ck_constraints(s.stream, ck, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, N, sc, k14, ctx->ntt_tw.p, (uint32_t*)d_out);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag);
+    uint32_t hflag = 0;
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
+    if (rc == KZG_OK && out_coeffs && !device)
+        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient");
+    if (rc) return rc;
+    if (hflag) return pq_remainder(ctx, sh);
+    if (!out_p1s) return KZG_OK;
+    return pq_commit_chunks(ctx, lk, slot, (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
+}
+
+int kzg_circuit_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                         const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                         const uint64_t* gate_coset, uint64_t* out_coeffs, uint64_t* out_p1s) {
+    if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_quotient(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, gate_coset,
+                                                       out_coeffs, out_p1s));
+    }
+    return circuit_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, gate_coset, out_coeffs, out_p1s, false);
+}
+
+int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                const void* d_public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                const void* d_gate_coset, void* d_out_coeffs) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !d_wires || !d_z || !alpha || !beta || !gamma || !d_out_coeffs) return KZG_ERR_INVALID_ARG;
+    return circuit_quotient_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, alpha, beta, gamma, d_gate_coset, d_out_coeffs,
+                                 nullptr, true);
 }
 
 // weights: k blst_fr given by the caller (the test hook), or null for fresh random ones.  wire: the commitments, proofs and

@@ -402,6 +402,17 @@ void launch_pq_constraints(hipStream_t s, const PqColumns& cols, uint32_t log_N,
 void launch_pq_pad_twist(hipStream_t s, const uint32_t* d_in, size_t stride, uint32_t len, const Fr30& fill, uint32_t log_N,
                          uint64_t batch, const void* d_gtab, const Fr30& c, uint32_t* d_out);
 
+// ---- circuit_kernels.hip: the quotient of a circuit with a resident key, the arithmetic gate built in ---
+// what k_ck_constraints reads: N values per column on the coset, all blst_fr images.  The wires are the call's (column j at
+// + 8 j stride words); q_lin and sigmas are the circuit's (column j at + 8 j N words); d_pi and d_gate may be null
+struct CkColumns {
+    const uint32_t *d_wires, *d_q_lin, *d_sigmas, *d_q_mul, *d_q_const, *d_z, *d_l0, *d_pi, *d_gate, *d_zinv;
+};
+// d_out[i] = Num(x_i) / Z_H(x_i) with the gate sum_j q_j f_j + q_M f_0 f_1 + q_C + PI + G' in Num, canonical, i < N; t >= 2;
+// k14: 2^14 in multiplier form; the rest as launch_pq_constraints
+void launch_ck_constraints(hipStream_t s, const CkColumns& cols, uint32_t log_N, uint32_t rot, uint32_t t, size_t stride,
+                           const PqScalars& sc, const Fr30& k14, const void* d_tw, uint32_t* d_out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

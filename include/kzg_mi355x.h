@@ -629,6 +629,63 @@ int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const 
 int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned which, unsigned form, const void** d_ptr,
                               size_t* len);
 
+/* ---- a circuit's proof, last round: linearise, open once, verify ---------------------------------------
+ * Notation as above; e = 2^log_ext, w = kzg_domain_root(log2 n), T_c = coefficients [c n, (c + 1) n) of the N - n that
+ * kzg_circuit_quotient returns, PI(X) the interpolant of the public inputs.  With the evaluations
+ *     abar_j = f_j(zeta) (j < t),    sbar_j = sigma_j(zeta) (j < t - 1),    zw = z(zeta w)
+ * and A = prod_(j<t) (abar_j + beta k_j zeta + gamma), B = zw prod_(j<t-1) (abar_j + beta sbar_j + gamma), Z = zeta^n - 1,
+ * l = L_0(zeta) (the polynomial's value: Z / (n (zeta - 1)), 1 at zeta = 1; zeta in H is legal), the linearisation polynomial is
+ *     r(X) = sum_j abar_j q_j(X) + abar_0 abar_1 q_M(X) + q_C(X) + (alpha A + alpha^2 l) z(X) - alpha beta B sigma_(t-1)(X)
+ *            - Z sum_(c<e-1) zeta^(c n) T_c(X) + [ PI(zeta) - alpha B (abar_(t-1) + gamma) - alpha^2 l ],
+ * n coefficients, and r(zeta) = 0 exactly when T is the quotient of these wires and this z.  The proof is the ONE G1 element of
+ * kzg_open_sets over the 2 t + 1 polynomials [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ], set_of = [0, .., 0, 1], sets
+ * {zeta}, {zeta w}, gamma := v -- bit for bit what kzg_open_sets returns on that stack (for n = 1, w = 1: one point).
+ * SOUNDNESS: beta and gamma are fixed after the wires' commitments, alpha after [z], zeta after the [T_c], v after the
+ * evaluations, as the protocol's transcript defines them.  Nothing is hashed here: the calls take the challenges as given.  There
+ * is no blinding.  The caller's term G' of kzg_circuit_quotient (gate_coset: custom gates, lookups) is NOT part of r: a circuit
+ * proved with a gate_coset cannot use these calls.
+ *
+ * kzg_circuit_open: host pointers, synchronous, one stream slot.  wires, z and public_inputs (may be NULL) are values over H,
+ * exactly as kzg_circuit_quotient takes them; t_coeffs the N - n coefficients it returned.  out_evals: 2 t x 4 u64 in the order
+ * abar_0 .. abar_(t-1), sbar_0 .. sbar_(t-2), zw, each a canonical blst_fr; out_p1: the proof.  On the device: one inverse
+ * transform per input column, the evaluations (the wires, PI and z from the call's coefficients, the sigmas from the circuit's
+ * resident ones), then ONE launch of k_lin_combine per point: G_zeta is summed over the 3 t + e + 2 columns where they lie -- the
+ * resident key, the wires, z, T -- every coefficient read once, r never written; then the scans and the MSM of kzg_open_sets.
+ * Statuses, in this order: a NULL required pointer, a circuit of another context or destroyed, stride < n, a challenge not below r
+ * -> KZG_ERR_INVALID_ARG; no SRS -> KZG_ERR_NO_SRS; n - 1 > kzg_srs_len -> KZG_ERR_DEGREE_TOO_HIGH; r(zeta) != 0 ->
+ * KZG_ERR_REMAINDER (kzg_last_error says that the linearisation polynomial does not vanish at zeta; out_p1 is left unwritten).
+ * n = 1 is legal.  Multi-device contexts as kzg_circuit_quotient: a replicated one forwards to the circuit's device, a range-split
+ * one returns KZG_ERR_INVALID_ARG.  kzg_circuit_destroy waits for a running call.
+ * kzg_circuit_open_device: the same on kzg_dev_alloc buffers of a single-device context (d_t_coeffs: what
+ * kzg_circuit_quotient_device wrote); the evaluations and the proof come back to host memory, so only the challenges, 2 t values
+ * and one point cross PCIe.
+ * kzg_circuit_linearise: test hook, no SRS: the evaluations and r's n coefficients (canonical blst_fr), from the same kernel
+ * launched with r's own multipliers. */
+int kzg_circuit_open(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                     const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                     const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], uint64_t* out_evals, uint64_t out_p1[18]);
+int kzg_circuit_open_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                            const void* d_public_inputs, const void* d_t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                            const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], uint64_t* out_evals,
+                            uint64_t out_p1[18]);
+int kzg_circuit_linearise(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                          const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                          const uint64_t gamma[4], const uint64_t zeta[4], uint64_t* out_evals, uint64_t* out_r);
+/* Host only, no context, like kzg_verify_sets.  key_p1s: the 2 t + 2 commitments of kzg_circuit_create, in its order; wire_p1s: the
+ * t wires' commitments; t_p1s: the e - 1 commitments of T's chunks; public_inputs: n_public <= n values at rows 0 .. n_public - 1
+ * (the later rows are zero; NULL for n_public = 0); evals: out_evals of the prover.  The verifier computes PI(zeta) = sum PI_i
+ * L_i(zeta) with one batch inversion, forms [r] = sum scalar commitment + const G1 from the key, z_p1 and t_p1s (t + e + 3 scalar
+ * multiplications, those of kzg_combine_claims) and hands the 2 t + 1 commitments and the values [0, abar, sbar, zw] to
+ * kzg_verify_sets, whose setup arguments these are (one G1 entry, the G2 powers [s^j]G2 for j <= 2).  *valid = 1 accepted, 0
+ * rejected.  KZG_ERR_INVALID_ARG: a NULL required pointer, a scalar not below r, a G1 input off the curve or a G2 input off the
+ * twist, t outside [KZG_CIRCUIT_MIN_COLUMNS, KZG_PQ_MAX_COLUMNS], t + 1 > 2^log_ext, log_ext > KZG_PQ_MAX_LOG_EXT, n not a power
+ * of two or N above 2^KZG_NTT_MAX_LOG, n_public > n. */
+int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
+                       const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
+                       const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                       const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
+                       size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
+
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the
  * coset {w_N^(j + (N/l) i) : i < l}, whose vanishing polynomial is X^l - w_N^(j l).  Its proof is exactly what

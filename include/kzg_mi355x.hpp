@@ -544,6 +544,72 @@ class Circuit {
         if (rc != KZG_OK) throw Error(rc, std::string(kzg_strerror(rc)) + ": " + kzg_last_error(ctx_));
         return out;
     }
+    // The last round: the evaluations f_j(zeta) (t), sigma_j(zeta) (t - 1), z(zeta w) in that order, and the
+    // one-element proof of all of them and of the linearisation polynomial.  The challenges are the transcript's: nothing is hashed.
+    struct Opening {
+        std::vector<Scalar> evals;  // 2 t
+        G1Point proof;
+    };
+    // wires, z, public_inputs as quotient() takes them; t_coeffs: Quotient::coeffs
+    Opening open(const std::vector<Scalar>& wires, const std::vector<Scalar>& z, const std::vector<Scalar>& t_coeffs, const Scalar& alpha,
+                 const Scalar& beta, const Scalar& gamma, const Scalar& zeta, const Scalar& v,
+                 const std::vector<Scalar>& public_inputs = {}) const {
+        check_open_sizes(wires, z, t_coeffs, public_inputs);
+        Opening out;
+        out.evals.resize(2 * t_);
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        check(kzg_circuit_open(ctx_, c_, u(wires), n_, u(z), u(public_inputs), u(t_coeffs), alpha.l.data(), beta.l.data(), gamma.l.data(),
+                               zeta.l.data(), v.l.data(), reinterpret_cast<uint64_t*>(out.evals.data()),
+                               reinterpret_cast<uint64_t*>(&out.proof)),
+              ctx_);
+        return out;
+    }
+    // the same on kzg_dev_alloc buffers (d_t_coeffs: what kzg_circuit_quotient_device wrote; d_public_inputs may be null)
+    Opening open_device(const void* d_wires, size_t stride, const void* d_z, const void* d_public_inputs, const void* d_t_coeffs,
+                        const Scalar& alpha, const Scalar& beta, const Scalar& gamma, const Scalar& zeta, const Scalar& v) const {
+        Opening out;
+        out.evals.resize(2 * t_);
+        check(kzg_circuit_open_device(ctx_, c_, d_wires, stride, d_z, d_public_inputs, d_t_coeffs, alpha.l.data(), beta.l.data(),
+                                      gamma.l.data(), zeta.l.data(), v.l.data(), reinterpret_cast<uint64_t*>(out.evals.data()),
+                                      reinterpret_cast<uint64_t*>(&out.proof)),
+              ctx_);
+        return out;
+    }
+    // test hook, no SRS: (the evaluations, the n coefficients of the linearisation polynomial)
+    std::pair<std::vector<Scalar>, std::vector<Scalar>> linearise(const std::vector<Scalar>& wires, const std::vector<Scalar>& z,
+                                                                  const std::vector<Scalar>& t_coeffs, const Scalar& alpha,
+                                                                  const Scalar& beta, const Scalar& gamma, const Scalar& zeta,
+                                                                  const std::vector<Scalar>& public_inputs = {}) const {
+        check_open_sizes(wires, z, t_coeffs, public_inputs);
+        std::vector<Scalar> evals(2 * t_), r(n_);
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        check(kzg_circuit_linearise(ctx_, c_, u(wires), n_, u(z), u(public_inputs), u(t_coeffs), alpha.l.data(), beta.l.data(),
+                                    gamma.l.data(), zeta.l.data(), reinterpret_cast<uint64_t*>(evals.data()),
+                                    reinterpret_cast<uint64_t*>(r.data())),
+              ctx_);
+        return {evals, r};
+    }
+    // Host only, no context (kzg_circuit_verify): key as key(), the commitments of the wires, of z and of T's chunks, the public
+    // inputs at rows 0 .. size - 1, Opening::evals; setup_g1: [s^0]G1; setup_g2: [s^j]G2, j <= 2 (36 u64 each, back to back)
+    static bool verify(const std::vector<G1Point>& key, size_t n, unsigned log_ext, const std::vector<Scalar>& shifts,
+                       const std::vector<G1Point>& wire_commitments, const G1Point& z_commitment,
+                       const std::vector<G1Point>& t_commitments, const std::vector<Scalar>& public_inputs,
+                       const std::vector<Scalar>& evals, const Scalar& alpha, const Scalar& beta, const Scalar& gamma, const Scalar& zeta,
+                       const Scalar& v, const G1Point& proof, const G1Point& setup_g1, const uint64_t* setup_g2) {
+        const size_t t = shifts.size();
+        if (key.size() != 2 * t + 2 || wire_commitments.size() != t || evals.size() != 2 * t ||
+            t_commitments.size() + 1 != ((size_t)1 << log_ext))
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit::verify: 2 t + 2 key commitments, t wires, 2 t values, 2^log_ext - 1 chunks");
+        const auto p = [](const std::vector<G1Point>& x) { return reinterpret_cast<const uint64_t*>(x.data()); };
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        int valid = 0;
+        const int rc = kzg_circuit_verify(p(key), n, t, log_ext, u(shifts), p(wire_commitments), reinterpret_cast<const uint64_t*>(&z_commitment),
+                                          p(t_commitments), u(public_inputs), public_inputs.size(), u(evals), alpha.l.data(),
+                                          beta.l.data(), gamma.l.data(), zeta.l.data(), v.l.data(),
+                                          reinterpret_cast<const uint64_t*>(&proof), &setup_g1, sizeof(G1Point), setup_g2, 288, &valid);
+        if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
+        return valid != 0;
+    }
     // a resident column on the device, read-only: (pointer, length)
     std::pair<const void*, size_t> column_device(unsigned which, unsigned form) const {
         const void* p = nullptr;
@@ -553,6 +619,12 @@ class Circuit {
     }
 
    private:
+    void check_open_sizes(const std::vector<Scalar>& wires, const std::vector<Scalar>& z, const std::vector<Scalar>& t_coeffs,
+                          const std::vector<Scalar>& public_inputs) const {
+        if (wires.size() != n_ * t_ || z.size() != n_ || t_coeffs.size() != (((size_t)1 << log_ext_) - 1) * n_ ||
+            (!public_inputs.empty() && public_inputs.size() != n_))
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit: column sizes");
+    }
     kzg_ctx* ctx_ = nullptr;
     kzg_circuit* c_ = nullptr;
     size_t n_ = 0, t_ = 0;

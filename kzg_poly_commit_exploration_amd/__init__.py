@@ -20,7 +20,7 @@ __all__ = [
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS", "KZG_LOGUP_MAX_COLUMNS",
     "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
-    "Circuit", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
+    "Circuit", "circuit_verify", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
     "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
@@ -82,6 +82,7 @@ ABI_SYMBOLS = [
     "kzg_coset_extend", "kzg_coset_extend_device", "kzg_permutation_constraints_coset", "kzg_permutation_constraints_coset_device",
     "kzg_vanishing_quotient", "kzg_vanishing_quotient_device", "kzg_permutation_quotient",
     "kzg_circuit_create", "kzg_circuit_destroy", "kzg_circuit_quotient", "kzg_circuit_quotient_device", "kzg_circuit_column_device",
+    "kzg_circuit_open", "kzg_circuit_open_device", "kzg_circuit_linearise", "kzg_circuit_verify",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -235,6 +236,11 @@ def load_library():
         "kzg_circuit_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_quotient_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_column_device": (i, [vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(sz)]),
+        "kzg_circuit_open": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_open_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_linearise": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_verify": (i, [vp, sz, sz, C.c_uint, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz,
+                                   C.POINTER(C.c_int)]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1686,6 +1692,53 @@ class Circuit:
                                                        C.c_void_p(d_z), C.c_void_p(d_public_inputs), _ptr(al), _ptr(bl), _ptr(gl),
                                                        C.c_void_p(d_gate), C.c_void_p(d_out_coeffs)))
 
+    # -- the last round: linearise, open once --
+    def _open_inputs(self, e, wires, z, public_inputs, t_coeffs, n):
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        tc = np.ascontiguousarray(t_coeffs, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n and (pi is None or pi.shape[0] >= n) and tc.shape[0] >= (n << self.log_ext) - n
+        return a, stride, zz, pi, tc
+
+    def _split_evals(self, ev):
+        t = self.t
+        sc = [Scalar.from_limbs(row) for row in ev]
+        return sc[:t], sc[t:2 * t - 1], sc[2 * t - 1]
+
+    def open(self, wires, z, t_coeffs, alpha, beta, gamma, zeta, v, public_inputs=None, n=None, engine=None):
+        """kzg_circuit_open: wires, z, public_inputs as quotient() takes them, t_coeffs the (N - n, 4) coefficients it returned ->
+        ((the t values f_j(zeta), the t - 1 values sigma_j(zeta), z(zeta w)), the proof).  The challenges are taken as given:
+        zeta is fixed after T's commitments and v after the values; nothing is hashed here."""
+        e = self._eng if engine is None else engine
+        a, stride, zz, pi, tc = self._open_inputs(e, wires, z, public_inputs, t_coeffs, n)
+        ch = [x.limbs() for x in (alpha, beta, gamma, zeta, v)]
+        ev, p1 = np.zeros((2 * self.t, 4), dtype=np.uint64), np.zeros(18, dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_open(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi), _ptr(tc),
+                                            _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ch[4]), _ptr(ev), _ptr(p1)))
+        return self._split_evals(ev), G1Point(p1)
+
+    def open_device(self, d_wires, d_z, d_t_coeffs, alpha, beta, gamma, zeta, v, d_public_inputs=None, stride=None):
+        """kzg_circuit_open_device on kzg_dev_alloc buffers (d_t_coeffs: what quotient_device wrote) -> as open()"""
+        e = self._eng
+        ch = [x.limbs() for x in (alpha, beta, gamma, zeta, v)]
+        ev, p1 = np.zeros((2 * self.t, 4), dtype=np.uint64), np.zeros(18, dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_open_device(e._h, self._c, C.c_void_p(d_wires), self.n if stride is None else stride,
+                                                   C.c_void_p(d_z), C.c_void_p(d_public_inputs), C.c_void_p(d_t_coeffs), _ptr(ch[0]),
+                                                   _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ch[4]), _ptr(ev), _ptr(p1)))
+        return self._split_evals(ev), G1Point(p1)
+
+    def linearise(self, wires, z, t_coeffs, alpha, beta, gamma, zeta, public_inputs=None, n=None, engine=None):
+        """kzg_circuit_linearise (test hook, no SRS) -> (the evaluations as open() returns them, r's (n, 4) coefficients)"""
+        e = self._eng if engine is None else engine
+        a, stride, zz, pi, tc = self._open_inputs(e, wires, z, public_inputs, t_coeffs, n)
+        ch = [x.limbs() for x in (alpha, beta, gamma, zeta)]
+        ev, r = np.zeros((2 * self.t, 4), dtype=np.uint64), np.zeros((self.n, 4), dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_linearise(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi), _ptr(tc),
+                                                 _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ev), _ptr(r)))
+        return self._split_evals(ev), r
+
     def column_device(self, which, form):
         """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
         e = self._eng
@@ -1855,6 +1908,31 @@ def verify_sets(commitments, set_of, sets, ys, gamma, proof, setup_g1, setup_g2)
     ok = C.c_int(0)
     _check(lib.kzg_verify_sets(_ptr(cs), t, _ptr(so), _ptr(sl), len(sets), _ptr(zl), _ptr(yl), _ptr(gamma.limbs()),
                                _ptr(proof.p1), _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def circuit_verify(key, n, log_ext, shifts, wire_commitments, z_commitment, t_commitments, public_inputs, evals, alpha, beta, gamma,
+                   zeta, v, proof, setup_g1, setup_g2):
+    """kzg_circuit_verify on the host: key the 2 t + 2 commitments of circuit_create in its order, t_commitments those of T's
+    2^log_ext - 1 chunks, public_inputs the values at rows 0 .. len - 1 (Scalars; the later rows are zero), evals what
+    Circuit.open returned: (f_j(zeta), sigma_j(zeta), z(zeta w)).  setup_g1: at least one blst_p1 row; setup_g2: at least three
+    blst_p2 rows ([s^j]G2, j <= 2).  The challenges have to be the transcript's; nothing is hashed here."""
+    lib = load_library()
+    t = len(wire_commitments)
+    abar, sbar, zw = evals
+    assert len(key) == 2 * t + 2 and len(shifts) == t and len(abar) == t and len(sbar) == t - 1
+    assert len(t_commitments) == (1 << log_ext) - 1
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 1 and g2.shape[0] >= 3
+    rows = lambda pts: np.ascontiguousarray(np.stack([c.p1 for c in pts]), dtype=np.uint64)
+    pub = list(public_inputs) if public_inputs is not None else []
+    ok = C.c_int(0)
+    _check(lib.kzg_circuit_verify(_ptr(rows(key)), n, t, log_ext, _ptr(_scalar_rows(shifts)), _ptr(rows(wire_commitments)),
+                                  _ptr(z_commitment.p1), _ptr(rows(t_commitments)), _ptr(_scalar_rows(pub)) if pub else None, len(pub),
+                                  _ptr(_scalar_rows(list(abar) + list(sbar) + [zw])), _ptr(alpha.limbs()), _ptr(beta.limbs()),
+                                  _ptr(gamma.limbs()), _ptr(zeta.limbs()), _ptr(v.limbs()), _ptr(proof.p1), _ptr(g1), 144, _ptr(g2),
+                                  288, C.byref(ok)))
     return bool(ok.value)
 
 

@@ -234,6 +234,9 @@ struct Slot : SlotQueue {
     PinnedBuf svals{PinnedBuf::Mapped};
     DevBuf sg;
     std::vector<uint32_t> sets_vmap;
+    // the last round of a circuit's proof (kzg_circuit_open): the column records of k_lin_combine, one
+    // table of kLinMaxColumns per distinct point
+    PinnedBuf ltab{PinnedBuf::Staged};
     // openings from evaluations over the Lagrange basis (kzg_open_lagrange): the tile records of the
     // quotient kernels; the quotient's values go to q
     DevBuf lag_part;
@@ -5742,6 +5745,311 @@ int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const 
                                  nullptr, true);
 }
 
+// ---- the last round of a circuit's proof: linearise, open once (linearise_kernels.hip) --------------------
+// The calls hold quotient_mu, then the context's mutex and one slot, as the quotient's calls above: the per-proof coefficients live
+// in pq_ws, the tables, the values and the G_p in the slot's buffers of the openings at several point sets.
+namespace {
+const hf::Fr kFrZero = {{0, 0, 0, 0}};
+bool fr_equal(const hf::Fr& a, const hf::Fr& b) { return std::memcmp(a.l, b.l, 32) == 0; }
+
+// r(X) = sum_k scalar_k C_k(X) + konst: its t + e + 3 columns where they lie on the device, with the scalars the evaluations give
+struct LinTerm {
+    const uint32_t* coeffs;
+    hf::Fr scalar;
+};
+struct LinPoly {
+    std::vector<LinTerm> terms;
+    hf::Fr konst = kFrZero;
+};
+struct LinChallenges {
+    hf::Fr alpha, beta, gamma, zeta;
+};
+// The scalars of r, which the prover puts on coefficient vectors and the verifier on commitments, in the order q_0 .. q_(t-1),
+// q_M, q_C, z, sigma_(t-1), T_0 .. T_(e-2); *konst: the constant term.  abar: t values, sbar: t - 1, zw = z(zeta w),
+// pi_zeta = PI(zeta) (zero without public inputs); shifts: the t k_j
+void lin_scalars(size_t n, uint32_t lg_n, size_t t, size_t e, const uint64_t* shifts, const LinChallenges& ch, const hf::Fr* abar,
+                 const hf::Fr* sbar, const hf::Fr& zw, const hf::Fr& pi_zeta, std::vector<hf::Fr>* out, hf::Fr* konst) {
+    const hf::Fr zn = hf::fr_pow(ch.zeta, n), Z = hf::fr_sub(zn, hf::kFrOne);
+    // l = L_0(zeta), the polynomial's value: Z / (n (zeta - 1)) off zeta = 1 (zero elsewhere on H), and 1 at zeta = 1
+    const hf::Fr zm1 = hf::fr_sub(ch.zeta, hf::kFrOne);
+    const hf::Fr l0 = fr_equal(zm1, kFrZero) ? hf::kFrOne : hf::fr_mul(Z, hf::fr_inv(hf::fr_mul(fr_pow2(lg_n), zm1)));
+    hf::Fr A = hf::kFrOne, B = zw;
+    for (size_t j = 0; j < t; j++) {
+        const hf::Fr ag = hf::fr_add(abar[j], ch.gamma);
+        A = hf::fr_mul(A, hf::fr_add(ag, hf::fr_mul(hf::fr_mul(ch.beta, pq_fr(shifts + 4 * j)), ch.zeta)));
+        if (j + 1 < t) B = hf::fr_mul(B, hf::fr_add(ag, hf::fr_mul(ch.beta, sbar[j])));
+    }
+    const hf::Fr a2l = hf::fr_mul(hf::fr_mul(ch.alpha, ch.alpha), l0), aB = hf::fr_mul(ch.alpha, B);
+    std::vector<hf::Fr>& sc = *out;
+    sc.assign(abar, abar + t);
+    sc.push_back(hf::fr_mul(abar[0], abar[1]));
+    sc.push_back(hf::kFrOne);
+    sc.push_back(hf::fr_add(hf::fr_mul(ch.alpha, A), a2l));
+    sc.push_back(hf::fr_sub(kFrZero, hf::fr_mul(aB, ch.beta)));
+    hf::Fr zc = hf::fr_sub(kFrZero, Z);  // -Z zeta^(c n)
+    for (size_t k = 0; k + 1 < e; k++) {
+        sc.push_back(zc);
+        zc = hf::fr_mul(zc, zn);
+    }
+    *konst = hf::fr_sub(hf::fr_sub(pi_zeta, hf::fr_mul(aB, hf::fr_add(abar[t - 1], ch.gamma))), a2l);
+}
+// key: the circuit's resident coefficients (2 t + 2 columns of n), d_z: z's coefficients, d_t: T's N - n coefficients
+void lin_poly(const kzg_circuit* c, const LinChallenges& ch, const hf::Fr* abar, const hf::Fr* sbar, const hf::Fr& zw,
+              const hf::Fr& pi_zeta, const uint32_t* key, const uint32_t* d_z, const uint32_t* d_t, LinPoly* out) {
+    const size_t n = c->n, t = c->t, e = (size_t)1 << c->lg_ext;
+    LinPoly& r = *out;
+    std::vector<hf::Fr> sc;
+    lin_scalars(n, c->lg_n, t, e, c->shifts, ch, abar, sbar, zw, pi_zeta, &sc, &r.konst);
+    for (size_t j = 0; j < t + 2; j++) r.terms.push_back({key + 8 * j * n, sc[j]});
+    r.terms.push_back({d_z, sc[t + 2]});
+    r.terms.push_back({key + 8 * (2 * t + 1) * n, sc[t + 3]});  // sigma_(t-1)
+    for (size_t k = 0; k + 1 < e; k++) r.terms.push_back({d_t + 8 * k * n, sc[t + 4 + k]});
+}
+LinColumn lin_column(const uint32_t* coeffs, const hf::Fr& mult) {
+    LinColumn col = {};
+    col.coeffs = coeffs;
+    const Fr30 m = fr30_arg_from_mont256(mult);
+    std::memcpy(col.mult, m.d, sizeof col.mult);
+    return col;
+}
+int lin_remainder(kzg_ctx* ctx) {
+    ctx->last_error = "circuit open: the linearisation polynomial does not vanish at zeta (r(zeta) != 0): T is not the quotient of "
+                      "these wires and this z";
+    return KZG_ERR_REMAINDER;
+}
+}  // namespace
+
+// wires (t columns of n values), z, pi (n values or null) and t_coeffs (N - n coefficients) are host pointers, or device pointers
+// when `device`.  v null: the test hook -- r's n coefficients to out_r, no SRS; else the proof to out_p1.
+static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
+                             const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                             const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
+                             bool device) {
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    PqShape sh;
+    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
+    LinChallenges ch;
+    hf::Fr vf = kFrZero;
+    if (!fr_arg_below_r(alpha, &ch.alpha) || !fr_arg_below_r(beta, &ch.beta) || !fr_arg_below_r(gamma, &ch.gamma) ||
+        !fr_arg_below_r(zeta, &ch.zeta) || (v && !fr_arg_below_r(v, &vf))) {
+        ctx->last_error = "circuit open: a challenge is not below r";
+        return KZG_ERR_INVALID_ARG;
+    }
+    const size_t n = sh.n, N = sh.N, t = c->t, npoly = 2 * t + 1, ncoef = t + 1 + (pi ? 1 : 0);
+    // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1)
+    const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
+    std::vector<uint32_t> set_of(npoly, 0);
+    set_of[npoly - 1] = 1;
+    const uint32_t set_len[2] = {1, 1};
+    uint64_t zs[8];
+    std::memcpy(zs, ch.zeta.l, 32);
+    std::memcpy(zs + 4, zeta_w.l, 32);
+    SetsPlan plan;
+    std::string why;
+    if (!sets_plan(plan, why, npoly, set_of.data(), set_len, 2, zs, vf.l)) {
+        ctx->last_error = "circuit open: " + why;
+        return KZG_ERR_INVALID_ARG;
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    auto srs_status = [&]() {
+        if (!v) return (int)KZG_OK;
+        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
+        return n - 1 > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
+    };
+    int rc = srs_status();
+    if (rc) return rc;
+    int slot = -1;
+    rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    rc = srs_status();  // (the wait for a slot dropped the mutex: the SRS may have changed)
+    if (rc) return rc;
+    PqBufs w;
+    void *in = nullptr, *stack, *scratch, *coef = const_cast<void*>(t_coeffs);
+    rc = pq_bufs(ctx, n, 1, &w);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqIn, ncoef * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, ncoef * n * 32, &stack);  // the coefficients of the wires, PI, z
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, n * 32, &scratch);         // the passes' by-product; r for the test hook
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
+    if (rc == KZG_OK) rc = sets_job_start(ctx, s, plan);
+    if (rc == KZG_OK) rc = sets_ensure_all(ctx, s, plan, n, t + 1, 0);
+    if (rc == KZG_OK) rc = s.ltab.reserve(ctx, kSetsMaxPoints * kLinMaxColumns * sizeof(LinColumn), s.stream);
+    if (rc) return rc;
+    // 1. coefficients: [ f_0 .. f_(t-1) | PI | z ], one inverse transform each
+    uint32_t *d_f = (uint32_t*)stack, *d_pi = pi ? d_f + 8 * t * n : nullptr, *d_z = d_f + 8 * (ncoef - 1) * n;
+    {
+        const uint32_t *src_w = (const uint32_t*)wires, *src_pi = (const uint32_t*)pi, *src_z = (const uint32_t*)z;
+        size_t src_stride = stride;
+        if (!device) {
+            uint32_t* d_in = (uint32_t*)in;
+            rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
+            if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)pi, n, 1, n);
+            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (ncoef - 1) * n, (const uint64_t*)z, n, 1, n);
+            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)coef, (const uint64_t*)t_coeffs, N - n, 1, N - n);
+            if (rc) return rc;
+            src_w = d_in;
+            src_pi = d_in + 8 * t * n;
+            src_z = d_in + 8 * (ncoef - 1) * n;
+            src_stride = n;
+        }
+        const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+        const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
+        for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_f + 8 * j * n, sh.lg_n, itw, inv_n, w.A, w.B);
+        if (pi) launch_ntt(s.stream, src_pi, d_pi, sh.lg_n, itw, inv_n, w.A, w.B);
+        launch_ntt(s.stream, src_z, d_z, sh.lg_n, itw, inv_n, w.A, w.B);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // 2. evaluations, into the slot's value words: [0, t) the wires at zeta, [t] PI(zeta), [t + 1, 2 t) the sigmas, [2 t] z(zeta w)
+    Fr30* tab = (Fr30*)s.stab.h;
+    const Fr30* d_tab = (const Fr30*)s.stab.d;
+    for (size_t r = 0; r < plan.npts; r++) combine_fill_powers(tab + r * kCombineTabGamma, plan.pts[r]);
+    const size_t last_pt = plan.npts - 1;  // where zeta w sits
+    for (size_t i = 0; i <= t; i++) {      // the passes' own sums are not used: every weight is one
+        tab[kSetsMultBase + i] = fr30_arg_from_mont256(hf::kFrOne);
+        s.ssel.host()[i] = (uint32_t)i;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.stab.d, s.stab.h, (kSetsMultBase + t + 1) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.ssel.dev(), s.ssel.host(), (t + 1) * 4, hipMemcpyHostToDevice, s.stream));
+    const uint32_t* key = c->coeffs.dev();
+    uint32_t* d_vals = s.svals.dev();
+    launch_sets_combine(s.stream, d_f, (uint32_t)n, (uint32_t)(ncoef - 1), n, d_tab, d_tab + kSetsMultBase, s.ssel.dev(), 0, false,
+                        (uint32_t*)scratch, s.cpart.dev(), d_vals);
+    launch_sets_combine(s.stream, key + 8 * (t + 2) * n, (uint32_t)n, (uint32_t)(t - 1), n, d_tab, d_tab + kSetsMultBase, s.ssel.dev(), 0,
+                        false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * (t + 1));
+    launch_sets_combine(s.stream, d_z, (uint32_t)n, 1, n, d_tab + last_pt * kCombineTabGamma, d_tab + kSetsMultBase, s.ssel.dev(), 0,
+                        false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * 2 * t);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = sync_unlocked(ctx, lk, s.stream, "circuit open (evaluations)");
+    if (rc) return rc;
+    std::vector<hf::Fr> ys(npoly, kFrZero);  // the stack's values: 0, abar, sbar, z(zeta w)
+    const uint32_t* hv = s.svals.host();
+    for (size_t j = 0; j < t; j++) std::memcpy(ys[1 + j].l, hv + 8 * j, 32);
+    for (size_t j = 0; j + 1 < t; j++) std::memcpy(ys[1 + t + j].l, hv + 8 * (t + 1 + j), 32);
+    std::memcpy(ys[2 * t].l, hv + 8 * 2 * t, 32);
+    hf::Fr pi_zeta = kFrZero;
+    if (pi) std::memcpy(pi_zeta.l, hv + 8 * t, 32);
+    for (size_t i = 1; i < npoly; i++) std::memcpy(out_evals + 4 * (i - 1), ys[i].l, 32);
+    LinPoly lin;
+    lin_poly(c, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, key, d_z, (const uint32_t*)coef, &lin);
+    // 3. the sums.  Point p: G_p = sum_i mult_i P_i over the polynomials of the stack opened there, with m_0 r spread over r's
+    // columns: one launch per point, r is never stored.  The test hook: r itself, with its bare scalars.
+    LinColumn* cols = (LinColumn*)s.ltab.h;
+    const LinColumn* d_cols = (const LinColumn*)s.ltab.d;
+    auto lin_const = [](const hf::Fr& k) {
+        LinConst out;
+        std::memcpy(out.l, k.l, 32);
+        return out;
+    };
+    uint32_t* d_y = d_vals + 8 * npoly;  // out(p) of point p at d_y + 8 p
+    if (!v) {
+        for (size_t k = 0; k < lin.terms.size(); k++) cols[k] = lin_column(lin.terms[k].coeffs, lin.terms[k].scalar);
+        HIP_TRY(ctx, hipMemcpyAsync(s.ltab.d, s.ltab.h, lin.terms.size() * sizeof(LinColumn), hipMemcpyHostToDevice, s.stream));
+        launch_lin_combine(s.stream, d_cols, (uint32_t)lin.terms.size(), (uint32_t)n, d_tab, lin_const(lin.konst), (uint32_t*)scratch,
+                           s.cpart.dev(), d_y);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = copy_unlocked(ctx, lk, s.stream, out_r, scratch, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (linearisation)");
+        return rc ? rc : sync_unlocked(ctx, lk, s.stream, "circuit linearise");
+    }
+    hf::Fr want[KZG_MAX_SET_POINTS];  // sum_i mult_i y_i over the list of point p (r's value, zero, is what is proved)
+    uint32_t ncols[KZG_MAX_SET_POINTS];
+    LinConst konst[KZG_MAX_SET_POINTS];
+    for (size_t p = 0; p < plan.npts; p++) {
+        LinColumn* out = cols + p * kLinMaxColumns;
+        uint32_t k = 0;
+        hf::Fr kc = kFrZero;
+        want[p] = kFrZero;
+        for (uint32_t e = plan.off[p]; e < plan.off[p + 1]; e++) {
+            const uint32_t i = plan.sel[e];
+            const hf::Fr& m = plan.mult[e];
+            want[p] = hf::fr_add(want[p], hf::fr_mul(m, ys[i]));
+            if (i == 0) {
+                for (const LinTerm& term : lin.terms) out[k++] = lin_column(term.coeffs, hf::fr_mul(m, term.scalar));
+                kc = hf::fr_mul(m, lin.konst);
+            } else if (i <= t) {
+                out[k++] = lin_column(d_f + 8 * (i - 1) * n, m);
+            } else if (i < 2 * t) {
+                out[k++] = lin_column(key + 8 * (t + 2 + (i - t - 1)) * n, m);
+            } else {
+                out[k++] = lin_column(d_z, m);
+            }
+        }
+        if (k > kLinMaxColumns) return KZG_ERR_INVALID_ARG;  // (3 t + e + 3 <= 32: cannot happen)
+        ncols[p] = k;
+        konst[p] = lin_const(kc);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.ltab.d, s.ltab.h, plan.npts * kLinMaxColumns * sizeof(LinColumn), hipMemcpyHostToDevice, s.stream));
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
+    for (size_t p = 0; p < plan.npts; p++)
+        launch_lin_combine(s.stream, d_cols + p * kLinMaxColumns, ncols[p], (uint32_t)n, d_tab + p * kCombineTabGamma, konst[p],
+                           s.sg.dev() + 8 * p * n, s.cpart.dev(), d_y + 8 * p);
+    if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
+    HIP_TRY(ctx, hipGetLastError());
+    rc = sync_unlocked(ctx, lk, s.stream, "circuit open (sums)");
+    if (rc) return rc;
+    // G_zeta(zeta) = m_0 r(zeta) + sum_(i >= 1) mult_i y_i with m_0 = 1: r vanishes at zeta exactly when the two agree
+    hf::Fr got;
+    std::memcpy(got.l, hv + 8 * npoly, 32);
+    if (!fr_equal(got, want[0])) return lin_remainder(ctx);
+    // 4. the scans and the MSM of kzg_open_sets, unchanged
+    rc = srs_status();  // (the waits dropped the mutex)
+    if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, n);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    std::vector<uint64_t> unused(4 * plan.nvals);
+    rc = wait_sets_locked(ctx, slot, unused.data(), out_p1);
+    s.kind = SLOT_RESERVED;  // (the mutex was held since the wait marked it idle)
+    return rc;
+}
+
+// ORDER, for the three entry points below: the required pointers are checked BEFORE anything of *ctx is used but ctx->multi
+// (read by KZG_SINGLE_DEVICE_ONLY) -- no lock, no last_error.  tests/test_circuit_open.py relies on it: it hands in a zeroed block as
+// the context to see every NULL pointer refused without a device.
+int kzg_circuit_open(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                     const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                     const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], uint64_t* out_evals, uint64_t out_p1[18]) {
+    if (!ctx || !circuit || !wires || !z || !t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !out_evals || !out_p1)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the opening needs the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_open(kid, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta, v,
+                                                   out_evals, out_p1));
+    }
+    return circuit_open_impl(ctx, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta, v, out_evals, nullptr,
+                             out_p1, false);
+}
+
+int kzg_circuit_open_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                            const void* d_public_inputs, const void* d_t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                            const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], uint64_t* out_evals,
+                            uint64_t out_p1[18]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !d_wires || !d_z || !d_t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !out_evals || !out_p1)
+        return KZG_ERR_INVALID_ARG;
+    return circuit_open_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, d_t_coeffs, alpha, beta, gamma, zeta, v, out_evals,
+                             nullptr, out_p1, true);
+}
+
+int kzg_circuit_linearise(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                          const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                          const uint64_t gamma[4], const uint64_t zeta[4], uint64_t* out_evals, uint64_t* out_r) {
+    if (!ctx || !circuit || !wires || !z || !t_coeffs || !alpha || !beta || !gamma || !zeta || !out_evals || !out_r)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_linearise(kid, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta,
+                                                        out_evals, out_r));
+    }
+    return circuit_open_impl(ctx, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta, nullptr, out_evals, out_r,
+                             nullptr, false);
+}
+
 // weights: k blst_fr given by the caller (the test hook), or null for fresh random ones.  wire: the commitments, proofs and
 // cells are its byte strings (section 4.12) and commitments_p1 / cells / proofs_p1 are null
 static int verify_cells_impl(kzg_ctx* ctx, const uint64_t* commitments_p1, size_t num_commitments, const uint32_t* commitment_idx,
@@ -7548,6 +7856,105 @@ int kzg_verify_sets(const uint64_t* commitments_p1, size_t t, const uint32_t* se
     if (r < 0) return KZG_ERR_INVALID_ARG;
     *valid = r;
     return KZG_OK;
+}
+
+// The last round of a circuit's proof, the verifier's side (host only): PI(zeta) from the public inputs
+// with one batch inversion, [r] = sum scalar commitment + konst G1 from the key, [z] and [T_c] with the scalars the prover put on
+// the coefficients (lin_scalars), then kzg_verify_sets over [ [r] | wires | sigma_0 .. sigma_(t-2) | [z] ] with the values
+// [ 0 | abar | sbar | z(zeta w) ].
+int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
+                       const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
+                       const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                       const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
+                       size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    if (!key_p1s || !shifts || !wire_p1s || !z_p1 || !t_p1s || (!public_inputs && n_public) || !evals || !alpha || !beta || !gamma ||
+        !zeta || !v || !proof_p1 || !setup_g1 || !setup_g2 || !valid)
+        return KZG_ERR_INVALID_ARG;
+    PqShape sh;
+    if (log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns ||
+        t + 1 > sh.rot || n_public > n)
+        return KZG_ERR_INVALID_ARG;
+    const size_t e = sh.rot, npoly = 2 * t + 1;
+    LinChallenges ch;
+    hf::Fr vf;
+    if (!fr_arg_below_r(alpha, &ch.alpha) || !fr_arg_below_r(beta, &ch.beta) || !fr_arg_below_r(gamma, &ch.gamma) ||
+        !fr_arg_below_r(zeta, &ch.zeta) || !fr_arg_below_r(v, &vf))
+        return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ys(npoly, kFrZero), pub(n_public), ks(t);  // the stack's values: 0, abar, sbar, z(zeta w)
+    for (size_t i = 1; i < npoly; i++)
+        if (!fr_arg_below_r(evals + 4 * (i - 1), &ys[i])) return KZG_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n_public; i++)
+        if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return KZG_ERR_INVALID_ARG;
+    for (size_t j = 0; j < t; j++)
+        if (!fr_arg_below_r(shifts + 4 * j, &ks[j])) return KZG_ERR_INVALID_ARG;
+    auto load = [](const uint64_t* p, hf::P1* out) {
+        std::memcpy(out, p, sizeof *out);
+        return hf::p1_on_curve(*out);
+    };
+    // the commitments r is made of, in lin_scalars' order
+    std::vector<hf::P1> cs(t + e + 3);
+    bool on_curve = true;
+    for (size_t j = 0; j < t + 2; j++) on_curve = load(key_p1s + 18 * j, &cs[j]) && on_curve;
+    on_curve = load(z_p1, &cs[t + 2]) && on_curve;
+    on_curve = load(key_p1s + 18 * (2 * t + 1), &cs[t + 3]) && on_curve;
+    for (size_t k = 0; k + 1 < e; k++) on_curve = load(t_p1s + 18 * k, &cs[t + 4 + k]) && on_curve;
+    hf::P1 tmp;
+    for (size_t j = 0; j < t; j++) on_curve = load(wire_p1s + 18 * j, &tmp) && load(key_p1s + 18 * (t + 2 + j), &tmp) && on_curve;
+    if (!on_curve) return KZG_ERR_INVALID_ARG;
+    // PI(zeta) = sum_i PI_i L_i(zeta), L_i(zeta) = w^i (zeta^n - 1) / (n (zeta - w^i)); zeta = w^k: L_i(zeta) = [i = k]
+    hf::Fr pi_zeta = kFrZero;
+    if (n_public) {
+        const hf::Fr w = hf::fr_domain_root(sh.lg_n);
+        std::vector<hf::Fr> wi(n_public), den(n_public), pre(n_public);
+        hf::Fr cur = hf::kFrOne, run = hf::kFrOne;
+        size_t on_h = n_public;
+        for (size_t i = 0; i < n_public; i++) {
+            wi[i] = cur;
+            den[i] = hf::fr_sub(ch.zeta, cur);
+            if (fr_equal(den[i], kFrZero)) on_h = i;
+            pre[i] = run;  // the product of the denominators before i
+            run = hf::fr_mul(run, den[i]);
+            cur = hf::fr_mul(cur, w);
+        }
+        if (on_h < n_public) {
+            pi_zeta = pub[on_h];
+        } else {
+            hf::Fr inv = hf::fr_inv(run);  // the call's one inversion beside 1 / n
+            for (size_t i = n_public; i-- > 0;) {
+                pi_zeta = hf::fr_add(pi_zeta, hf::fr_mul(hf::fr_mul(pub[i], wi[i]), hf::fr_mul(inv, pre[i])));
+                inv = hf::fr_mul(inv, den[i]);
+            }
+            const hf::Fr Z = hf::fr_sub(hf::fr_pow(ch.zeta, n), hf::kFrOne);
+            pi_zeta = hf::fr_mul(pi_zeta, hf::fr_mul(Z, hf::fr_inv(fr_pow2(sh.lg_n))));
+        }
+    }
+    hf::Fr konst;
+    std::vector<hf::Fr> sc;
+    lin_scalars(n, sh.lg_n, t, e, shifts, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, &sc, &konst);
+    auto times = [](const hf::P1& p, const hf::Fr& k) {  // the scalar multiplication of kzg_combine_claims
+        uint64_t plain[4];
+        hf::fr_from_mont(k.l, plain);
+        return hf::p1_mul(p, plain);
+    };
+    hf::P1 r = times(hf::p1_generator(), konst);
+    for (size_t k = 0; k < cs.size(); k++) r = hf::p1_add(r, times(cs[k], sc[k]));
+    r = hf::p1_normalize(r);
+    // the stack, its sets and values
+    std::vector<uint64_t> stack(18 * npoly), yl(4 * npoly);
+    std::memcpy(stack.data(), &r, sizeof r);
+    std::memcpy(stack.data() + 18, wire_p1s, 18 * 8 * t);
+    std::memcpy(stack.data() + 18 * (1 + t), key_p1s + 18 * (t + 2), 18 * 8 * (t - 1));
+    std::memcpy(stack.data() + 18 * 2 * t, z_p1, 18 * 8);
+    for (size_t i = 0; i < npoly; i++) std::memcpy(yl.data() + 4 * i, ys[i].l, 32);
+    std::vector<uint32_t> set_of(npoly, 0);
+    set_of[npoly - 1] = 1;
+    const uint32_t set_len[2] = {1, 1};
+    const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
+    uint64_t zs[8];
+    std::memcpy(zs, ch.zeta.l, 32);
+    std::memcpy(zs + 4, zeta_w.l, 32);
+    return kzg_verify_sets(stack.data(), npoly, set_of.data(), set_len, 2, zs, yl.data(), v, proof_p1, setup_g1, g1_stride_bytes, setup_g2,
+                           g2_stride_bytes, valid);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

@@ -444,6 +444,24 @@ void launch_sets_combine(hipStream_t s, const uint32_t* d_coeffs, uint32_t n, ui
                          const Fr30* d_mult, const uint32_t* d_sel, uint32_t sel_base, bool carry, uint32_t* d_g, uint32_t* d_partial,
                          uint32_t* d_ys);
 
+// ---- linearise_kernels.hip: a weighted sum of columns in different buffers -------------------------
+// d_out[i] (n canonical values) = sum_{k < ncols} mult_k C_k[i], plus konst at i = 0; d_y[0..8) = d_out(z), canonical, for the z
+// whose 66 powers are at d_tab (the layout above).  Column k is the n blst_fr images at d_cols[k].coeffs, which d_out does not
+// overlap; its multiplier is canonical, in the x 2^270 form (fr30_arg_from_mont256).  d_partial: combine_tiles(n) records of
+// kCombinePartialWords words.  n >= 1, 1 <= ncols <= kLinMaxColumns.
+constexpr uint32_t kLinMaxColumns = 32;
+struct LinColumn {
+    const uint32_t* coeffs;
+    int32_t mult[9];  // the digits of an Fr30
+    uint32_t pad;
+};
+static_assert(sizeof(LinColumn) == 48, "the device reads the records the host wrote");
+struct LinConst {
+    uint32_t l[8];  // a canonical blst_fr
+};
+void launch_lin_combine(hipStream_t s, const LinColumn* d_cols, uint32_t ncols, uint32_t n, const Fr30* d_tab, const LinConst& konst,
+                        uint32_t* d_out, uint32_t* d_partial, uint32_t* d_y);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import bigint_twin as BT
+import device_arena as DA
 import fr_extremes as FE
 import grand_product_oracle as GO
 import kzg_poly_commit_exploration_amd as K
@@ -171,15 +172,12 @@ def test_vanishing_quotient_returns_the_cofactor_and_flags_the_rest(eng, n, e):
     inv = _zh_inverses(n, e)
     divided = [v * inv[i % e] % R for i, v in enumerate(vals)]
     assert np.array_equal(eng.vanishing_quotient_limbs(GO.to_limbs(divided), n, already_divided=True), want)
-    d_in, d_out = eng.dev_alloc(N * 32), eng.dev_alloc(N * 32)
-    try:
-        eng.dev_upload(d_in, GO.to_limbs(vals))
-        eng.vanishing_quotient_device(d_in, N, n, d_out)
-        assert np.array_equal(_download(eng, d_out, N - n), want)
-        assert np.array_equal(_download(eng, d_in, N), GO.to_limbs(vals))  # the input is left as it was
-    finally:
-        eng.dev_free(d_in)
-        eng.dev_free(d_out)
+    with DA.Arena(eng, seed=N) as arena:  # d_out is exactly N - n rows, between guard bands
+        d_in = arena.region(N, name="num", data=GO.to_limbs(vals))
+        d_out = arena.region(N - n, name="T")
+        arena.upload()
+        eng.vanishing_quotient_device(d_in.ptr, N, n, d_out.ptr)
+        arena.check(outputs={d_out: want})  # T; the input is left as it was; nothing before, between or past them is written
     # one more coefficient at either edge of the flagged range [N - n, N), and Num + 1
     for at in sorted({N - n, N - 1}):
         bad = [(v + 5 * pow(x, at, R)) % R for v, x in zip(vals, pts)]

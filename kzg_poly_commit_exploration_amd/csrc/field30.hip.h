@@ -53,11 +53,32 @@ KZG_HD int32_t fq_sext30(uint32_t v) { return (int32_t)(v << 2) >> 2; }  // low 
 KZG_HD int64_t fq_round_shift(int64_t acc) { return (acc + (int64_t)(1 << (kQBits - 1))) >> kQBits; }
 
 // KZG_F30_SERIAL_COLUMNS: keep the columns of a product in program order (one live accumulator) instead of letting
-// the compiler run a dozen of them side by side -- fewer VGPRs, less instruction-level parallelism
+// the compiler run a dozen of them side by side -- fewer VGPRs, less instruction-level parallelism -- and keep every
+// column ONE multiply-add chain whose first addend is the shifted carry of the column below.
+//   KZG_F30_MAC    acc += x * y, followed by an empty statement that READS the sum.  The second reader makes every partial
+//                  sum a leaf for the compiler's re-association: left free, it sums the digit products whose operands are
+//                  older than the carry first, on a chain opened from zero, and joins the carry with a 64-bit add behind
+//                  them -- in most columns of every product (123 joins per mixed addition).  The statement emits nothing
+//                  and defines nothing: one that DEFINES the sum ("+v") costs an s_nop in front of the next multiply-add,
+//                  which reads a register an unknown instruction has just written.  The values are unchanged: the sum of
+//                  a column is the same two's-complement sum in another order, inside the bound above in any order.
+//   KZG_F30_FENCE  behind the shift of an UPPER column: the carry is redefined, so nothing of column k + 1 moves in front of
+//                  it, and the readers of KZG_F30_MAC (ordered among themselves and with this) stay inside their product.
+//                  There the digit extraction fills the slot behind the statement.  The lower columns need none: their
+//                  one chain is ordered by its data, and behind their shift there is nothing to fill the slot with.
+//   KZG_F30_OPAQUE_DIGIT  a digit the compiler must not see through (fq_mul_sub's negated operand).
 #if defined(KZG_F30_SERIAL_COLUMNS) && defined(__HIP_DEVICE_COMPILE__)
 #define KZG_F30_FENCE(acc) asm volatile("" : "+v"(acc))
+#define KZG_F30_MAC(acc, x, y)       \
+    do {                             \
+        acc += (int64_t)(x) * (y);   \
+        asm volatile("" ::"v"(acc)); \
+    } while (0)
+#define KZG_F30_OPAQUE_DIGIT(x) asm("" : "+v"(x))
 #else
 #define KZG_F30_FENCE(acc) ((void)0)
+#define KZG_F30_MAC(acc, x, y) acc += (int64_t)(x) * (y)
+#define KZG_F30_OPAQUE_DIGIT(x) ((void)0)
 #endif
 
 KZG_HD Fq fq_zero() {
@@ -147,20 +168,19 @@ KZG_HD Fq fq_mul(const Fq& a, const Fq& b) {
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = 0; i <= k; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = 0; j < k; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         m[k] = fq_sext30((uint32_t)acc * kQN0);
-        acc += (int64_t)m[k] * fq_pd(0);  // low 30 bits are now zero
+        KZG_F30_MAC(acc, m[k], fq_pd(0));  // low 30 bits are now zero
         acc >>= kQBits;
-        KZG_F30_FENCE(acc);
     }
 #pragma unroll
     for (int k = kQ; k < 2 * kQ - 1; k++) {
 #pragma unroll
-        for (int i = k - kQ + 1; i < kQ; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = k - kQ + 1; i < kQ; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = k - kQ + 1; j < kQ; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         r.d[k - kQ] = fq_sext30((uint32_t)acc);
         acc = fq_round_shift(acc);
         KZG_F30_FENCE(acc);
@@ -175,30 +195,45 @@ KZG_HD Fq fq_mul(const Fq& a, const Fq& b) {
 // here), |a b - c d| < 2^771.  Saves 169 multiply-adds and the carry work of one product wherever the group law
 // subtracts two products (Y3 = R (Q - X3) - Y1 PPP).
 KZG_HD Fq fq_mul_sub(const Fq& a, const Fq& b, const Fq& c, const Fq& d) {
+    // a b + (-c) d on ONE chain per column: c is negated once, 13 instructions (|-c_i| <= 2^29 + 4 as |c_i|: the column bound
+    // above counts magnitudes and does not move).  Subtracted product by product, the c d part was kept on a chain of its own
+    // and taken off the column with a 64-bit subtraction -- two instructions with borrow -- in every one of the 25 columns.
+    // (The device kernels outside the accumulation keep the subtracting form: their code stays what it was, instruction for
+    // instruction.  Same integers either way.)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_F30_SERIAL_COLUMNS)
+#define KZG_F30_MUL_SUB_CD(i, j) acc -= (int64_t)c.d[i] * d.d[j]
     int32_t m[kQ];
+#else
+#define KZG_F30_MUL_SUB_CD(i, j) KZG_F30_MAC(acc, nc[i], d.d[j])
+    int32_t m[kQ], nc[kQ];
+#pragma unroll
+    for (int i = 0; i < kQ; i++) {
+        nc[i] = -c.d[i];
+        KZG_F30_OPAQUE_DIGIT(nc[i]);
+    }
+#endif
     Fq r;
     int64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = 0; i <= k; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc -= (int64_t)c.d[i] * d.d[k - i];
+        for (int i = 0; i <= k; i++) KZG_F30_MUL_SUB_CD(i, k - i);
 #pragma unroll
-        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = 0; j < k; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         m[k] = fq_sext30((uint32_t)acc * kQN0);
-        acc += (int64_t)m[k] * fq_pd(0);
+        KZG_F30_MAC(acc, m[k], fq_pd(0));
         acc >>= kQBits;
-        KZG_F30_FENCE(acc);
     }
 #pragma unroll
     for (int k = kQ; k < 2 * kQ - 1; k++) {
 #pragma unroll
-        for (int i = k - kQ + 1; i < kQ; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = k - kQ + 1; i < kQ; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int i = k - kQ + 1; i < kQ; i++) acc -= (int64_t)c.d[i] * d.d[k - i];
+        for (int i = k - kQ + 1; i < kQ; i++) KZG_F30_MUL_SUB_CD(i, k - i);
 #pragma unroll
-        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = k - kQ + 1; j < kQ; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         r.d[k - kQ] = fq_sext30((uint32_t)acc);
         acc = fq_round_shift(acc);
         KZG_F30_FENCE(acc);
@@ -206,6 +241,8 @@ KZG_HD Fq fq_mul_sub(const Fq& a, const Fq& b, const Fq& c, const Fq& d) {
     r.d[kQ - 1] = (int32_t)acc;
     return r;
 }
+
+#undef KZG_F30_MUL_SUB_CD
 
 // Montgomery square: cross products once against the doubled operand (91 instead of 169 digit products)
 KZG_HD Fq fq_sqr(const Fq& a) {
@@ -217,22 +254,21 @@ KZG_HD Fq fq_sqr(const Fq& a) {
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
 #pragma unroll
-        for (int i = 0; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
-        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+        for (int i = 0; 2 * i < k; i++) KZG_F30_MAC(acc, dbl[i], a.d[k - i]);
+        if ((k & 1) == 0) KZG_F30_MAC(acc, a.d[k / 2], a.d[k / 2]);
 #pragma unroll
-        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = 0; j < k; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         m[k] = fq_sext30((uint32_t)acc * kQN0);
-        acc += (int64_t)m[k] * fq_pd(0);
+        KZG_F30_MAC(acc, m[k], fq_pd(0));
         acc >>= kQBits;
-        KZG_F30_FENCE(acc);
     }
 #pragma unroll
     for (int k = kQ; k < 2 * kQ - 1; k++) {
 #pragma unroll
-        for (int i = k - kQ + 1; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
-        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+        for (int i = k - kQ + 1; 2 * i < k; i++) KZG_F30_MAC(acc, dbl[i], a.d[k - i]);
+        if ((k & 1) == 0) KZG_F30_MAC(acc, a.d[k / 2], a.d[k / 2]);
 #pragma unroll
-        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = k - kQ + 1; j < kQ; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         r.d[k - kQ] = fq_sext30((uint32_t)acc);
         acc = fq_round_shift(acc);
         KZG_F30_FENCE(acc);
@@ -266,21 +302,20 @@ KZG_HD Fq fq_mul_addc(const Fq& a, const Fq& b, const Fq& c) {
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = 0; i <= k; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = 0; j < k; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         m[k] = fq_sext30((uint32_t)acc * kQN0);
-        acc += (int64_t)m[k] * fq_pd(0);  // low 30 bits are now zero
+        KZG_F30_MAC(acc, m[k], fq_pd(0));  // low 30 bits are now zero
         acc >>= kQBits;
-        KZG_F30_FENCE(acc);
     }
 #pragma unroll
     for (int k = kQ; k < 2 * kQ - 1; k++) {
 #pragma unroll
-        for (int i = k - kQ + 1; i < kQ; i++) acc += (int64_t)a.d[i] * b.d[k - i];
+        for (int i = k - kQ + 1; i < kQ; i++) KZG_F30_MAC(acc, a.d[i], b.d[k - i]);
 #pragma unroll
-        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
-        acc += (int64_t)c.d[k - kQ] * unit;
+        for (int j = k - kQ + 1; j < kQ; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
+        KZG_F30_MAC(acc, c.d[k - kQ], unit);
         r.d[k - kQ] = fq_sext30((uint32_t)acc);
         acc = fq_round_shift(acc);
         KZG_F30_FENCE(acc);
@@ -302,23 +337,22 @@ KZG_HD Fq fq_sqr_minus(const Fq& a, const Fq& c) {
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
 #pragma unroll
-        for (int i = 0; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
-        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+        for (int i = 0; 2 * i < k; i++) KZG_F30_MAC(acc, dbl[i], a.d[k - i]);
+        if ((k & 1) == 0) KZG_F30_MAC(acc, a.d[k / 2], a.d[k / 2]);
 #pragma unroll
-        for (int j = 0; j < k; j++) acc += (int64_t)m[j] * fq_pd(k - j);
+        for (int j = 0; j < k; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
         m[k] = fq_sext30((uint32_t)acc * kQN0);
-        acc += (int64_t)m[k] * fq_pd(0);
+        KZG_F30_MAC(acc, m[k], fq_pd(0));
         acc >>= kQBits;
-        KZG_F30_FENCE(acc);
     }
 #pragma unroll
     for (int k = kQ; k < 2 * kQ - 1; k++) {
 #pragma unroll
-        for (int i = k - kQ + 1; 2 * i < k; i++) acc += (int64_t)dbl[i] * a.d[k - i];
-        if ((k & 1) == 0) acc += (int64_t)a.d[k / 2] * a.d[k / 2];
+        for (int i = k - kQ + 1; 2 * i < k; i++) KZG_F30_MAC(acc, dbl[i], a.d[k - i]);
+        if ((k & 1) == 0) KZG_F30_MAC(acc, a.d[k / 2], a.d[k / 2]);
 #pragma unroll
-        for (int j = k - kQ + 1; j < kQ; j++) acc += (int64_t)m[j] * fq_pd(k - j);
-        acc += (int64_t)c.d[k - kQ] * unit;
+        for (int j = k - kQ + 1; j < kQ; j++) KZG_F30_MAC(acc, m[j], fq_pd(k - j));
+        KZG_F30_MAC(acc, c.d[k - kQ], unit);
         r.d[k - kQ] = fq_sext30((uint32_t)acc);
         acc = fq_round_shift(acc);
         KZG_F30_FENCE(acc);

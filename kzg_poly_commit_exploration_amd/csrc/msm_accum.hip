@@ -12,9 +12,14 @@
 // Roofline: VALU issue bound.  Per mixed addition the wave executes 3091 v_mad_i64_i32 (6 products x 2 x 13^2, two squares
 // x (91 + 13^2), R (Q - X3) - Y1 PPP as two digit products under one reduction, and 3 x 12 digits of the differences P, R and
 // X3 - Q that enter the carry pass of the product in front of them as a multiply-add by +-1: xyzz30_acc_*, g1_30.hip.h) and
-// ~970 other VALU instructions on the straight path of an iteration (919 for P and R, 3118 for the tail; static counts of
-// the loop: 4317 VALU, 4682 with a carry pass per difference and the exceptional cases assigned in front of the products:
-// profiles/r16_accum_isa_histogram.txt),
+// ~870 other VALU instructions on the straight path of an iteration: every column of a product is ONE multiply-add chain
+// that starts from the shifted carry of the column below (KZG_F30_MAC, field30.hip.h), so besides its multiply-adds a column
+// costs one digit or m extraction, one 64-bit shift and, in the upper columns only, one 64-bit add for the rounding half.
+// Static counts of the loop: 4158 VALU, 119 v_lshl_add_u64, no v_sub_co/v_subb_co, 36 s_nop, 7263 priced issue units
+// (profiles/r27_accum_isa_histogram.txt; 4317 VALU, 240, 25 + 25, 74 and 7530 while the compiler opened a second chain from
+// zero in most columns and joined it, and fq_mul_sub subtracted its second product chain by chain:
+// profiles/r16_accum_isa_histogram.txt; tests/test_accum_columns_isa.py counts them).  Executed per wave-level mixed
+// addition: 3964 VALU instructions (4121 before),
 // against one 128-byte table record gathered by LDS-DMA + 4 B of reference; it runs within ~10 % of the sum of the two pipe
 // times of that mix (measured bare-loop rates), at two waves per SIMD as well as at three -- a three-wave form of the kernel
 // (no exceptional branches, 163 VGPRs, no spills) measured 2354 us against 2336 us alone, and a build of which three

@@ -5,6 +5,8 @@
 #   2. rocprofv3 --kernel-trace --stats on single commitments at 2^20 (tools/prof_latency.py)  -> ab_kernel_stats.json
 #   3. counter-only passes (no tracing beside them): executed VALU instructions of the kernel, both sides; VALU busy figures and
 #      HBM traffic of the current build                                                        -> ab_pmc.json
+# AB_BENCH="python3 bench.py --gpus 1 --no-cpu-baseline" runs the default bench (extras included) in step 1; AB_CURRENT_PMC=0 leaves
+# out the busy and traffic counters of the current build in step 3.
 # Every step has its own time limit and the script stops at the first step that fails.
 set -o pipefail
 cd "$(dirname "$0")/.."
@@ -14,7 +16,7 @@ RUNS=${2:-4}
 O=${3:-prof_out/accum_ab}
 mkdir -p $O
 export TMPDIR=/tmp
-BENCH="python3 bench.py --gpus 1 --no-extras --no-cpu-baseline"
+BENCH=${AB_BENCH:-"python3 bench.py --gpus 1 --no-extras --no-cpu-baseline"}
 SHORT="python3 bench.py --gpus 1 --steps 4 --warmup 1 --slots 1 --no-cpu-baseline --no-extras --no-openings"
 : > $O/ab_bench.jsonl
 step() {  # step <seconds> <log> <command...>
@@ -30,7 +32,7 @@ for i in $(seq 1 $RUNS); do
     tail -1 $O/bench_${side}_$i.log | python3 -c '
 import json, sys
 l = json.loads(sys.stdin.readline())
-o = {"side": sys.argv[1], "run": int(sys.argv[2]), "value": l["value"], "avg_kernel_ms": l["roofline"]["avg_kernel_ms"],
+o = {"side": sys.argv[1], "run": int(sys.argv[2]), "value": l["value"], "ms_per_step": l["ms_per_step"], "avg_kernel_ms": l["roofline"]["avg_kernel_ms"],
      "mixed_additions_per_launch": l["valu"]["mixed_additions_per_launch"], "bit_exact_vs_golden": l["config"].get("bit_exact_vs_golden", l.get("bit_exact_vs_golden"))}
 print(json.dumps(o))' $side $i | tee -a $O/ab_bench.jsonl
   done
@@ -43,6 +45,7 @@ for side in parent current; do
   step 300 $O/pmc_valu_$side.log env KZG_MI355X_LIB=$lib rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pmc_valu_$side -- $SHORT
 done
 i=0
+[ "${AB_CURRENT_PMC:-1}" = 0 ] ||
 for grp in "GRBM_GUI_ACTIVE GRBM_COUNT" "VALUBusy" "VALUUtilization" "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1)); rm -rf $O/pmc_cur_$i
   step 300 $O/pmc_cur_$i.log rocprofv3 --pmc $grp --output-format csv -d $O/pmc_cur_$i -- $SHORT

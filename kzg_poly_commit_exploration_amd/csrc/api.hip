@@ -318,6 +318,9 @@ struct kzg_ctx {
     uint32_t accum_lds_bytes = 41u * 1024u;
     uint32_t small_lds_bytes = 48u * 1024u;  // k_small_msm's LDS reservation (raised to small_msm_lds_bytes() at creation)
     bool small_msm_off = false;              // KZG_SMALL_MSM=0: small jobs take the general multi-launch path (A/B, tests)
+    // the four transform buffers of one pass of the quotient calls together stay below this (KZG_PQ_WS_KB lowers it, so that
+    // tests turn the pass loops of pq_extend and coset_extend_impl at small shapes)
+    size_t pq_ws_budget = (size_t)1 << 30;
     bool slots_ready = false;
     bool timing = false;
     // FK20 (kzg_cells_and_proofs_fk20), all under fk20_mu (taken before mu): the GLV-split twiddles
@@ -927,6 +930,10 @@ int kzg_ctx_create(int device, kzg_ctx** out) {
     ctx->device = device;
     if (const char* v = std::getenv("KZG_ACCUM_LDS_KB")) ctx->accum_lds_bytes = (uint32_t)std::atoi(v) * 1024u;
     if (const char* v = std::getenv("KZG_SMALL_MSM")) ctx->small_msm_off = std::atoi(v) == 0;
+    if (const char* v = std::getenv("KZG_PQ_WS_KB")) {  // never above the default: the passes only get smaller
+        const long kb = std::atol(v);
+        ctx->pq_ws_budget = kb < 0 ? 0 : (kb > (1l << 20) ? (size_t)1 << 30 : (size_t)kb * 1024);
+    }
     if (const char* v = std::getenv("KZG_HOST_TRACE")) ctx->host_trace = std::atoi(v) != 0;
     if (hipFuncSetAttribute(small_msm_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_msm_lds_bytes()) == hipSuccess)
         ctx->small_lds_bytes = small_msm_lds_bytes();
@@ -5003,8 +5010,7 @@ static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
 // Every call holds quotient_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits.
 namespace {
 enum : int { kPqIn = 0, kPqCols, kPqT, kPqP, kPqA, kPqB, kPqOut, kPqCoef, kPqGate, kPqZinv, kPqFlag, kPqCount };
-constexpr size_t kPqWsBudget = (size_t)1 << 30;    // the four transform buffers of one pass together stay below this ...
-constexpr size_t kPqMaxChunk = 64;                 // ... and hold at most this many columns
+constexpr size_t kPqMaxChunk = 64;                 // the transform buffers of one pass (ctx->pq_ws_budget) hold at most this many columns
 constexpr uint32_t kPqDftLog = kNttTileLog;        // below 2^11 values a batch takes launch_fr_dft, from there on launch_ntt per column
 static_assert(kPqCount <= 11, "pq_ws");
 
@@ -5051,7 +5057,7 @@ struct PqBufs {
 };
 // ctx->mu held, the caller has waited for every earlier use of the workspaces
 int pq_bufs(kzg_ctx* ctx, size_t N, size_t cols, PqBufs* w) {
-    size_t chunk = kPqWsBudget / (4 * N * 32);
+    size_t chunk = ctx->pq_ws_budget / (4 * N * 32);
     chunk = chunk < 1 ? 1 : (chunk > kPqMaxChunk ? kPqMaxChunk : chunk);
     if (chunk > cols) chunk = cols ? cols : 1;
     void *t, *p, *a, *b;
@@ -5266,7 +5272,7 @@ static int coset_extend_impl(kzg_ctx* ctx, const void* in, size_t len, size_t ba
         return rc ? rc : sync_unlocked(ctx, lk, s.stream, "coset extension");
     }
     // host pointers: as many columns per round as the budget holds, packed on the way up
-    size_t round = kPqWsBudget / (N * 32);
+    size_t round = ctx->pq_ws_budget / (N * 32);
     round = round < 1 ? 1 : (round > batch ? batch : round);
     PqBufs w;
     void *d_in, *d_out;

@@ -642,8 +642,9 @@ int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned
  * {zeta}, {zeta w}, gamma := v -- bit for bit what kzg_open_sets returns on that stack (for n = 1, w = 1: one point).
  * SOUNDNESS: beta and gamma are fixed after the wires' commitments, alpha after [z], zeta after the [T_c], v after the
  * evaluations, as the protocol's transcript defines them.  Nothing is hashed here: the calls take the challenges as given.  There
- * is no blinding.  The caller's term G' of kzg_circuit_quotient (gate_coset: custom gates, lookups) is NOT part of r: a circuit
- * proved with a gate_coset cannot use these calls.
+ * is no blinding in these calls: kzg_circuit_quotient_blinded / kzg_circuit_open_blinded below hide the witness.  The caller's
+ * term G' of kzg_circuit_quotient (gate_coset: custom gates, lookups) is NOT part of r: a circuit proved with a gate_coset cannot
+ * use these calls.
  *
  * kzg_circuit_open: host pointers, synchronous, one stream slot.  wires, z and public_inputs (may be NULL) are values over H,
  * exactly as kzg_circuit_quotient takes them; t_coeffs the N - n coefficients it returned.  out_evals: 2 t x 4 u64 in the order
@@ -685,6 +686,70 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
                        const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
                        const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
+
+/* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
+ * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the
+ * gate and the permutation are computed from the same values as without blinding, and kzg_circuit_verify accepts a blinded proof
+ * as it is: it sees only commitments, evaluations and one proof.
+ *     wires     f~_j = f_j + (b_j0 + b_j1 X) Z_H                                  n + 2 coefficients
+ *     product   z~   = z + (c_0 + c_1 X + c_2 X^2) Z_H                            n + 3 coefficients
+ *     quotient  T~   = Num(f~, z~) / Z_H, of degree t n + t + 2; L_T = (e - 1) n + t + 3 coefficients are returned, those above
+ *               degree t n + t + 2 are zero
+ *     chunks    T~_c = T_c + d_c X^n - d_(c-1) for c < e - 1, d_(-1) = d_(e-2) = 0; T_c = coefficients [c n, (c + 1) n) of T~, but
+ *               the last chunk T_(e-2) is everything from (e - 2) n to L_T: n + t + 3 coefficients.  sum_c X^(c n) T~_c = T~: the
+ *               chunk blinders change the chunks' commitments and r~, not T~.
+ * BLINDER ARRAY, the same for every call of one proof: 2 t + 3 + (e - 2) canonical blst_fr in the order (b_00, b_01), ..,
+ * (b_(t-1)0, b_(t-1)1), c_0, c_1, c_2, d_0 .. d_(e-3).  A value not below r -> KZG_ERR_INVALID_ARG.  The caller owns the
+ * randomness; kzg_circuit_blinders fills such an array from the OS CSPRNG (getrandom, uniform below r by rejection; host only;
+ * KZG_ERR_INVALID_ARG for t outside [KZG_CIRCUIT_MIN_COLUMNS, KZG_PQ_MAX_COLUMNS], t + 1 > e or log_ext > KZG_PQ_MAX_LOG_EXT).
+ * SHAPE RULE: the blinded circuit calls need N >= t n + t + 4 -- T~ fits and the divisibility test still sees at least one
+ * coefficient that must vanish -- else KZG_ERR_INVALID_ARG: (n, t, log_ext) = (4, 3, 2) and (8, 7, 3) are refused, (8, 3, 2) is
+ * the smallest legal shape with e = t + 1.  kzg_circuit_blinded_sizes (host only) applies the rule and returns the array's length
+ * and L_T (either pointer may be NULL).
+ * SRS: a commitment needs as many points as its vector has coefficients -- n + nb for a blinded column, n + t + 3 for the chunks of
+ * T~ (every chunk is committed padded to the last one's length) -- and the opening n + t + 2; else KZG_ERR_DEGREE_TOO_HIGH.
+ *
+ * kzg_blind_evaluations: k columns of n values over H (column c at evals + 4 c stride u64, n a power of two) and nb <= 3 blinders
+ * per column (column c at blinders + 4 c nb u64) -> the n + nb coefficients of f + b Z_H per column, column c at out_coeffs + 4 c
+ * out_stride u64 (out_stride >= n + nb).  The inverse transform, then a patch of 2 nb coefficients.  Needs no SRS; host pointers,
+ * synchronous, devices[0] of a multi-device context.
+ * kzg_commit_evaluations_blinded: the same followed by the batched MSM; out_p1s: k x 18 u64, each bit for bit kzg_commit of the
+ * blinded coefficients.  Serves the wires (nb = 2) and z (nb = 3).  Multi-device rules of kzg_commit_lagrange.
+ *
+ * kzg_circuit_quotient_blinded: the arguments of kzg_circuit_quotient without gate_coset (the last round cannot linearise a term
+ * of the caller's, so a blinded proof with one could not be finished), plus the blinder array.  The wires and z go values ->
+ * coefficients -> patch -> the coset from n + 3 coefficients; the constraints are those of the plain call.  out_coeffs: NULL or L_T
+ * coefficients; out_p1s: NULL or the e - 1 commitments [T~_c(s)]G, each bit for bit kzg_commit of the blinded chunk.  A non-zero
+ * coefficient of the interpolant at [t n + t + 3, N) -> KZG_ERR_REMAINDER.  The _device form takes kzg_dev_alloc buffers of a
+ * single-device context (d_out_coeffs: L_T coefficients, overlapping no input); the blinders and out_p1s stay host pointers.
+ *
+ * kzg_circuit_open_blinded: the arguments of kzg_circuit_open with t_coeffs = the L_T coefficients above, plus the blinder array.
+ * out_evals are the evaluations of the BLINDED polynomials: abar_j = f~_j(zeta), sbar_j = sigma_j(zeta), zw = z~(zeta w).  r~ is
+ * r's formula with z~, the T~_c and these evaluations: n + t + 3 coefficients; r~(zeta) != 0 -> KZG_ERR_REMAINDER with the proof
+ * unwritten.  The proof is bit for bit kzg_open_sets over [ r~ | f~_0 .. f~_(t-1) | sigma_0 .. sigma_(t-2) | z~ ], each zero-padded
+ * to n + t + 3 coefficients, set_of = [0, .., 0, 1], sets {zeta}, {zeta w}, gamma := v.  Statuses (after the NULL pointers, the
+ * circuit, the stride and the challenges: the shape rule, then the blinders), locks and multi-device rules are those of
+ * kzg_circuit_open.  The _device form: as kzg_circuit_open_device, d_t_coeffs what kzg_circuit_quotient_blinded_device wrote. */
+int kzg_circuit_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t* num_blinders, size_t* quotient_len);
+int kzg_circuit_blinders(size_t t, unsigned log_ext, uint64_t* out);
+int kzg_blind_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t k, size_t stride, const uint64_t* blinders, size_t nb,
+                          uint64_t* out_coeffs, size_t out_stride);
+int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t k, size_t stride, const uint64_t* blinders,
+                                   size_t nb, uint64_t* out_p1s);
+int kzg_circuit_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                 const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                 const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s);
+int kzg_circuit_quotient_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                        const void* d_public_inputs, const uint64_t alpha[4], const uint64_t beta[4],
+                                        const uint64_t gamma[4], const uint64_t* blinders, void* d_out_coeffs, uint64_t* out_p1s);
+int kzg_circuit_open_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                             const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                             const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], const uint64_t* blinders,
+                             uint64_t* out_evals, uint64_t out_p1[18]);
+int kzg_circuit_open_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                    const void* d_public_inputs, const void* d_t_coeffs, const uint64_t alpha[4],
+                                    const uint64_t beta[4], const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4],
+                                    const uint64_t* blinders, uint64_t* out_evals, uint64_t out_p1[18]);
 
 /* ---- every cell of a domain and its multiproof ----------------------------------------------
  * Domain of N = 2^log_domain points (w_N as kzg_domain_root), cells of l = 2^log_cell points: cell j (j < N / l) is the

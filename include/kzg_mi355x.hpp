@@ -589,6 +589,58 @@ class Circuit {
               ctx_);
         return {evals, r};
     }
+    // The blinded rounds.  blinders(): a fresh array for one proof from the OS CSPRNG -- t pairs for the
+    // wires, three for z, 2^log_ext - 2 for the chunks of T.  The same array goes to every blinded call of that proof.
+    std::vector<Scalar> blinders() const {
+        std::vector<Scalar> b(2 * t_ + 3 + ((size_t)1 << log_ext_) - 2);
+        const int rc = kzg_circuit_blinders(t_, log_ext_, reinterpret_cast<uint64_t*>(b.data()));
+        if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
+        return b;
+    }
+    // the commitments of `k` columns of n values over H, column c blinded with nb <= 3 blinders: the wires (nb = 2), z (nb = 3)
+    std::vector<G1Point> commit_blinded(const std::vector<Scalar>& evals, size_t k, const Scalar* blinders, size_t nb) const {
+        if (evals.size() != n_ * k) throw Error(KZG_ERR_INVALID_ARG, "Circuit::commit_blinded: k columns of n values");
+        std::vector<G1Point> out(k);
+        check(kzg_commit_evaluations_blinded(ctx_, reinterpret_cast<const uint64_t*>(evals.data()), n_, k, n_,
+                                             reinterpret_cast<const uint64_t*>(blinders), nb, reinterpret_cast<uint64_t*>(out.data())),
+              ctx_);
+        return out;
+    }
+    // Quotient::coeffs: the L_T = (2^log_ext - 1) n + t + 3 coefficients of T~; commitments: of its blinded chunks
+    Quotient quotient_blinded(const std::vector<Scalar>& wires, const std::vector<Scalar>& z, const Scalar& alpha, const Scalar& beta,
+                              const Scalar& gamma, const std::vector<Scalar>& blinders, const std::vector<Scalar>& public_inputs = {},
+                              bool want_commitments = true) const {
+        const size_t e = (size_t)1 << log_ext_;
+        if (wires.size() != n_ * t_ || z.size() != n_ || (!public_inputs.empty() && public_inputs.size() != n_) ||
+            blinders.size() != 2 * t_ + 3 + e - 2)
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit::quotient_blinded: column sizes");
+        Quotient out;
+        out.coeffs.resize((e - 1) * n_ + t_ + 3);
+        if (want_commitments) out.commitments.resize(e - 1);
+        const auto u = [](const std::vector<Scalar>& v) { return v.empty() ? nullptr : reinterpret_cast<const uint64_t*>(v.data()); };
+        check(kzg_circuit_quotient_blinded(ctx_, c_, u(wires), n_, u(z), u(public_inputs), alpha.l.data(), beta.l.data(), gamma.l.data(),
+                                           u(blinders), reinterpret_cast<uint64_t*>(out.coeffs.data()),
+                                           want_commitments ? reinterpret_cast<uint64_t*>(out.commitments.data()) : nullptr),
+              ctx_);
+        return out;
+    }
+    // t_coeffs: quotient_blinded()'s coefficients; the evaluations are those of the blinded polynomials
+    Opening open_blinded(const std::vector<Scalar>& wires, const std::vector<Scalar>& z, const std::vector<Scalar>& t_coeffs,
+                         const Scalar& alpha, const Scalar& beta, const Scalar& gamma, const Scalar& zeta, const Scalar& v,
+                         const std::vector<Scalar>& blinders, const std::vector<Scalar>& public_inputs = {}) const {
+        const size_t e = (size_t)1 << log_ext_;
+        if (wires.size() != n_ * t_ || z.size() != n_ || t_coeffs.size() != (e - 1) * n_ + t_ + 3 ||
+            (!public_inputs.empty() && public_inputs.size() != n_) || blinders.size() != 2 * t_ + 3 + e - 2)
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit::open_blinded: column sizes");
+        Opening out;
+        out.evals.resize(2 * t_);
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        check(kzg_circuit_open_blinded(ctx_, c_, u(wires), n_, u(z), u(public_inputs), u(t_coeffs), alpha.l.data(), beta.l.data(),
+                                       gamma.l.data(), zeta.l.data(), v.l.data(), u(blinders),
+                                       reinterpret_cast<uint64_t*>(out.evals.data()), reinterpret_cast<uint64_t*>(&out.proof)),
+              ctx_);
+        return out;
+    }
     // Host only, no context (kzg_circuit_verify): key as key(), the commitments of the wires, of z and of T's chunks, the public
     // inputs at rows 0 .. size - 1, Opening::evals; setup_g1: [s^0]G1; setup_g2: [s^j]G2, j <= 2 (36 u64 each, back to back)
     static bool verify(const std::vector<G1Point>& key, size_t n, unsigned log_ext, const std::vector<Scalar>& shifts,

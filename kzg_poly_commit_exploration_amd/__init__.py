@@ -20,7 +20,7 @@ __all__ = [
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS", "KZG_LOGUP_MAX_COLUMNS",
     "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
-    "Circuit", "circuit_verify", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
+    "Circuit", "circuit_verify", "circuit_blinders", "circuit_blinded_sizes", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
     "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
@@ -83,6 +83,9 @@ ABI_SYMBOLS = [
     "kzg_vanishing_quotient", "kzg_vanishing_quotient_device", "kzg_permutation_quotient",
     "kzg_circuit_create", "kzg_circuit_destroy", "kzg_circuit_quotient", "kzg_circuit_quotient_device", "kzg_circuit_column_device",
     "kzg_circuit_open", "kzg_circuit_open_device", "kzg_circuit_linearise", "kzg_circuit_verify",
+    "kzg_circuit_blinded_sizes", "kzg_circuit_blinders", "kzg_blind_evaluations", "kzg_commit_evaluations_blinded",
+    "kzg_circuit_quotient_blinded", "kzg_circuit_quotient_blinded_device", "kzg_circuit_open_blinded",
+    "kzg_circuit_open_blinded_device",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -239,6 +242,14 @@ def load_library():
         "kzg_circuit_open": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_open_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_linearise": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_blinded_sizes": (i, [sz, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz)]),
+        "kzg_circuit_blinders": (i, [sz, C.c_uint, vp]),
+        "kzg_blind_evaluations": (i, [vp, vp, sz, sz, sz, vp, sz, vp, sz]),
+        "kzg_commit_evaluations_blinded": (i, [vp, vp, sz, sz, sz, vp, sz, vp]),
+        "kzg_circuit_quotient_blinded": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_quotient_blinded_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_open_blinded": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_open_blinded_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_verify": (i, [vp, sz, sz, C.c_uint, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz,
                                    C.POINTER(C.c_int)]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
@@ -1521,6 +1532,25 @@ class Engine:
                                                     None if p1s is None else _ptr(p1s), C.byref(h)))
         return Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
 
+    # -- zero-knowledge blinding --
+    def blind_evaluations_limbs(self, evals, blinders, n=None):
+        """kzg_blind_evaluations: evals a (k, stride, 4) array of values over H whose first n rows per column count, blinders a
+        (k, nb, 4) array (nb <= 3) -> the (k, n + nb, 4) coefficients of f + b (X^n - 1)"""
+        a, k, stride, n = self._columns(evals, n)
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(k, -1, 4)
+        nb = b.shape[1]
+        out = np.zeros((k, n + nb, 4), dtype=np.uint64)
+        self._pq_check(self._lib.kzg_blind_evaluations(self._h, _ptr(a), n, k, stride, _ptr(b), nb, _ptr(out), n + nb))
+        return out
+
+    def commit_evaluations_blinded(self, evals, blinders, n=None):
+        """kzg_commit_evaluations_blinded: as blind_evaluations_limbs -> the k commitments of the blinded columns"""
+        a, k, stride, n = self._columns(evals, n)
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(k, -1, 4)
+        p1s = np.zeros((k, 18), dtype=np.uint64)
+        self._pq_check(self._lib.kzg_commit_evaluations_blinded(self._h, _ptr(a), n, k, stride, _ptr(b), b.shape[1], _ptr(p1s)))
+        return [G1Point(p) for p in p1s]
+
     # -- device-resident, pipelined --
     def num_slots(self):
         return int(self._lib.kzg_num_slots(self._h))
@@ -1739,6 +1769,85 @@ class Circuit:
                                                  _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ev), _ptr(r)))
         return self._split_evals(ev), r
 
+    # -- the blinded rounds --
+    def blinders(self):
+        """kzg_circuit_blinders: a fresh (2 t + 3 + e - 2, 4) blinder array from the OS CSPRNG"""
+        return circuit_blinders(self.t, self.log_ext)
+
+    def blinded_sizes(self):
+        """kzg_circuit_blinded_sizes -> (blinders in the array, L_T = coefficients of the blinded quotient)"""
+        return circuit_blinded_sizes(self.n, self.t, self.log_ext)
+
+    def quotient_blinded(self, wires, z, alpha, beta, gamma, blinders, public_inputs=None, n=None, want_coeffs=True,
+                         want_commitments=True, engine=None):
+        """kzg_circuit_quotient_blinded: as quotient() without a gate, blinders the array of blinders() -> (T~'s (L_T, 4)
+        coefficients or None, the commitments of its e - 1 blinded chunks or None)"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n and (pi is None or pi.shape[0] >= n)
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        ext = 1 << self.log_ext
+        assert b.shape[0] == 2 * t + 3 + ext - 2
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        coeffs = np.zeros(((ext - 1) * n + t + 3, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros((ext - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_quotient_blinded(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi),
+                                                        _ptr(al), _ptr(bl), _ptr(gl), _ptr(b),
+                                                        None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def quotient_blinded_device(self, d_wires, d_z, alpha, beta, gamma, blinders, d_out_coeffs, d_public_inputs=None, stride=None,
+                                want_commitments=True):
+        """kzg_circuit_quotient_blinded_device on kzg_dev_alloc buffers: T~'s L_T coefficients land in d_out_coeffs -> the
+        commitments of its blinded chunks or None"""
+        e = self._eng
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        assert b.shape[0] == 2 * self.t + 3 + (1 << self.log_ext) - 2
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        p1s = np.zeros(((1 << self.log_ext) - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_quotient_blinded_device(e._h, self._c, C.c_void_p(d_wires), self.n if stride is None else stride,
+                                                               C.c_void_p(d_z), C.c_void_p(d_public_inputs), _ptr(al), _ptr(bl),
+                                                               _ptr(gl), _ptr(b), C.c_void_p(d_out_coeffs),
+                                                               None if p1s is None else _ptr(p1s)))
+        return None if p1s is None else [G1Point(p) for p in p1s]
+
+    def open_blinded(self, wires, z, t_coeffs, alpha, beta, gamma, zeta, v, blinders, public_inputs=None, n=None, engine=None):
+        """kzg_circuit_open_blinded: as open(), t_coeffs the (L_T, 4) coefficients of quotient_blinded() and blinders the same
+        array -> ((the t values f~_j(zeta), the t - 1 values sigma_j(zeta), z~(zeta w)), the proof)"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        tc = np.ascontiguousarray(t_coeffs, dtype=np.uint64).reshape(-1, 4)
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        ext = 1 << self.log_ext
+        assert zz.shape[0] >= n and (pi is None or pi.shape[0] >= n) and tc.shape[0] >= (ext - 1) * n + t + 3
+        assert b.shape[0] == 2 * t + 3 + ext - 2
+        ch = [x.limbs() for x in (alpha, beta, gamma, zeta, v)]
+        ev, p1 = np.zeros((2 * self.t, 4), dtype=np.uint64), np.zeros(18, dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_open_blinded(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi),
+                                                    _ptr(tc), _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ch[4]), _ptr(b),
+                                                    _ptr(ev), _ptr(p1)))
+        return self._split_evals(ev), G1Point(p1)
+
+    def open_blinded_device(self, d_wires, d_z, d_t_coeffs, alpha, beta, gamma, zeta, v, blinders, d_public_inputs=None, stride=None):
+        """kzg_circuit_open_blinded_device on kzg_dev_alloc buffers (d_t_coeffs: what quotient_blinded_device wrote) -> as
+        open_blinded()"""
+        e = self._eng
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        assert b.shape[0] == 2 * self.t + 3 + (1 << self.log_ext) - 2
+        ch = [x.limbs() for x in (alpha, beta, gamma, zeta, v)]
+        ev, p1 = np.zeros((2 * self.t, 4), dtype=np.uint64), np.zeros(18, dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_open_blinded_device(e._h, self._c, C.c_void_p(d_wires), self.n if stride is None else stride,
+                                                           C.c_void_p(d_z), C.c_void_p(d_public_inputs), C.c_void_p(d_t_coeffs),
+                                                           _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ch[4]), _ptr(b),
+                                                           _ptr(ev), _ptr(p1)))
+        return self._split_evals(ev), G1Point(p1)
+
     def column_device(self, which, form):
         """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
         e = self._eng
@@ -1909,6 +2018,24 @@ def verify_sets(commitments, set_of, sets, ys, gamma, proof, setup_g1, setup_g2)
     _check(lib.kzg_verify_sets(_ptr(cs), t, _ptr(so), _ptr(sl), len(sets), _ptr(zl), _ptr(yl), _ptr(gamma.limbs()),
                                _ptr(proof.p1), _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
+
+
+def circuit_blinded_sizes(n, t, log_ext):
+    """kzg_circuit_blinded_sizes -> (entries of the blinder array, L_T); KzgError(KZG_ERR_INVALID_ARG) for a shape the blinded
+    calls refuse (2^log_ext n < t n + t + 4)"""
+    lib = load_library()
+    nb, lt = C.c_size_t(0), C.c_size_t(0)
+    _check(lib.kzg_circuit_blinded_sizes(n, t, log_ext, C.byref(nb), C.byref(lt)))
+    return int(nb.value), int(lt.value)
+
+
+def circuit_blinders(t, log_ext):
+    """kzg_circuit_blinders: the blinder array of one proof -- t pairs for the wires, three for z, 2^log_ext - 2 for the chunks of
+    T -- as a (count, 4) array of canonical blst_fr drawn from the OS CSPRNG"""
+    lib = load_library()
+    out = np.zeros((2 * t + 3 + (1 << log_ext) - 2, 4), dtype=np.uint64)
+    _check(lib.kzg_circuit_blinders(t, log_ext, _ptr(out)))
+    return out
 
 
 def circuit_verify(key, n, log_ext, shifts, wire_commitments, z_commitment, t_commitments, public_inputs, evals, alpha, beta, gamma,

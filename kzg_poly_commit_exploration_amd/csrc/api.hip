@@ -237,6 +237,9 @@ struct Slot : SlotQueue {
     // the last round of a circuit's proof (kzg_circuit_open): the column records of k_lin_combine, one
     // table of kLinMaxColumns per distinct point
     PinnedBuf ltab{PinnedBuf::Staged};
+    // ... with blinders (kzg_circuit_open_blinded): per distinct point the column records of k_blind_tail and
+    // the powers of the point, then the blinders the records point at
+    PinnedBuf btab{PinnedBuf::Staged};
     // openings from evaluations over the Lagrange basis (kzg_open_lagrange): the tile records of the
     // quotient kernels; the quotient's values go to q
     DevBuf lag_part;
@@ -353,7 +356,7 @@ struct kzg_ctx {
     std::mutex lookup_mu;
     Workspace<6> lu_ws;
     std::mutex quotient_mu;
-    Workspace<11> pq_ws;
+    Workspace<13> pq_ws;
     uint32_t pq_zinv_key = ~0u;  // (log n << 8) | log rot of the inverses of Z_H held in pq_ws, ~0: none
     // the circuits alive on this context (kzg_circuit_create), under quotient_mu: kzg_ctx_destroy frees
     // what the caller left
@@ -5009,10 +5012,10 @@ static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
 // ---- the quotient of a permutation argument on the coset g H_N (quotient_kernels.hip) ---------------------
 // Every call holds quotient_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits.
 namespace {
-enum : int { kPqIn = 0, kPqCols, kPqT, kPqP, kPqA, kPqB, kPqOut, kPqCoef, kPqGate, kPqZinv, kPqFlag, kPqCount };
+enum : int { kPqIn = 0, kPqCols, kPqT, kPqP, kPqA, kPqB, kPqOut, kPqCoef, kPqGate, kPqZinv, kPqFlag, kPqBlind, kPqChunks, kPqCount };
 constexpr size_t kPqMaxChunk = 64;                 // the transform buffers of one pass (ctx->pq_ws_budget) hold at most this many columns
 constexpr uint32_t kPqDftLog = kNttTileLog;        // below 2^11 values a batch takes launch_fr_dft, from there on launch_ntt per column
-static_assert(kPqCount <= 11, "pq_ws");
+static_assert(kPqCount <= 13, "pq_ws");
 
 // Declared after the slot's lease, so that it runs first: whatever way a call returns -- also after a failed copy or launch --
 // nothing it enqueued still uses pq_ws when the slot and quotient_mu are given up (a later call may grow, that is free, a
@@ -5167,9 +5170,11 @@ int pq_constraints(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t s
 }
 
 // N values on the coset in d_vals (a workspace: divided in place unless already divided) -> the N - n coefficients of the
-// quotient in d_coef; *d_flag (zeroed here) is set when a coefficient at [N - n, N) is not zero
+// quotient in d_coef; *d_flag (zeroed here) is set when a coefficient at [N - n, N) is not zero.  keep != 0 (a blinded quotient,
+// whose degree passes N - n): the first `keep` coefficients are written and the flag looks at [keep, N)
 int pq_interpolate(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, uint32_t* d_vals, bool divide,
-                   const PqBufs& w, uint32_t* d_coef, uint32_t* d_flag) {
+                   const PqBufs& w, uint32_t* d_coef, uint32_t* d_flag, size_t keep = 0) {
+    if (!keep) keep = sh.N - sh.n;
     const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
     const Fr30* ginv = (const Fr30*)ctx->rec_g.p + 2 * kNttTableLen;
     const Fr30 one = fr30_arg_from_mont256(hf::kFrOne), inv_N = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_N)));
@@ -5182,10 +5187,10 @@ int pq_interpolate(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t s
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 4, st));
     if (sh.lg_N >= kPqDftLog) {
         launch_ntt(st, d_vals, w.T, sh.lg_N, itw, inv_N, w.A, w.B);
-        launch_recover_untwist(st, w.T, sh.lg_N, (uint32_t)(sh.N - sh.n), 1, ginv, one, d_coef, false, d_flag);
+        launch_recover_untwist(st, w.T, sh.lg_N, (uint32_t)keep, 1, ginv, one, d_coef, false, d_flag);
     } else {
         const uint32_t* cur = launch_fr_dft(st, d_vals, w.A, w.B, sh.lg_N, 1, itw);
-        launch_recover_untwist(st, const_cast<uint32_t*>(cur), sh.lg_N, (uint32_t)(sh.N - sh.n), 1, ginv, inv_N, d_coef, false, d_flag);
+        launch_recover_untwist(st, const_cast<uint32_t*>(cur), sh.lg_N, (uint32_t)keep, 1, ginv, inv_N, d_coef, false, d_flag);
     }
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
@@ -5224,18 +5229,19 @@ int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, ui
 }
 }  // namespace
 
-// `chunks` vectors of n coefficients (vector c at d_coef + 8 c n words, resident until the call returns) committed over the
-// monomial SRS on the caller's reserved slot: batched MSMs, as many vectors per job as the slot holds
+// `chunks` vectors of n coefficients (vector c at d_coef + 8 c stride words, stride 0: n; resident until the call returns) committed
+// over the monomial SRS on the caller's reserved slot: batched MSMs, as many vectors per job as the slot holds
 static int pq_commit_chunks(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot, const uint32_t* d_coef, size_t n, size_t chunks,
-                            uint64_t* out_p1s) {
+                            uint64_t* out_p1s, size_t stride = 0) {
+    if (!stride) stride = n;
     if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the wait for a slot dropped the mutex: the SRS may have changed)
     if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
     Slot& s = ctx->slots[slot];
     const size_t group = std::min<size_t>(chunks, ctx->max_batch ? ctx->max_batch : 1);
     for (size_t c0 = 0; c0 < chunks; c0 += group) {
         const size_t g = chunks - c0 < group ? chunks - c0 : group;
-        const uint32_t* d_chunk = d_coef + 8 * c0 * n;
-        int rc = g == 1 ? submit_commit_locked(ctx, slot, d_chunk, 1, n, true, true) : commit_batch_submit_locked(ctx, slot, d_chunk, n, g, n, true);
+        const uint32_t* d_chunk = d_coef + 8 * c0 * stride;
+        int rc = g == 1 ? submit_commit_locked(ctx, slot, d_chunk, 1, n, true, true) : commit_batch_submit_locked(ctx, slot, d_chunk, n, g, stride, true);
         if (rc) return rc;
         await_unlocked(lk, s);
         rc = g == 1 ? wait_locked(ctx, slot, out_p1s + 18 * c0) : wait_batch_locked(ctx, slot, out_p1s + 18 * c0, g);
@@ -5751,6 +5757,285 @@ int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const 
                                  nullptr, true);
 }
 
+// ---- zero-knowledge blinding of a circuit's proof (blind_kernels.hip) -------------------------------------
+// f~ = f + b (X^n - 1): the values over H do not change, so z, the gate and the permutation are computed as before; in coefficient
+// form the blinder is a patch (k_blind_patch).  The calls hold quotient_mu, then the context's mutex and one slot, as above.
+namespace {
+constexpr size_t kBlindWireLen = 2, kBlindZLen = 3;
+// the blinder array of a circuit: t pairs for the wires, three for z, e - 2 for the chunks of T
+size_t blind_count(size_t t, size_t e) { return 2 * t + kBlindZLen + (e - 2); }
+// N >= t n + t + 4: T~ (degree t n + t + 2) fits and at least one coefficient is left that must vanish
+bool blind_shape_ok(size_t n, size_t t, size_t e) { return e >= 2 && e * n >= t * n + t + 4; }
+size_t blind_quotient_len(size_t n, size_t t, size_t e) { return (e - 1) * n + t + 3; }
+bool blind_values_ok(kzg_ctx* ctx, const char* what, const uint64_t* blinders, size_t count, std::vector<hf::Fr>* out) {
+    out->resize(count);
+    for (size_t i = 0; i < count; i++)
+        if (!fr_arg_below_r(blinders + 4 * i, &(*out)[i])) {
+            ctx->last_error = std::string(what) + ": blinder " + std::to_string(i) + " is not below r";
+            return false;
+        }
+    return true;
+}
+int blind_shape_refused(kzg_ctx* ctx, const char* what) {
+    ctx->last_error = std::string(what) + ": the blinded quotient needs 2^log_ext n >= t n + t + 4";
+    return KZG_ERR_INVALID_ARG;
+}
+}  // namespace
+
+int kzg_circuit_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t* num_blinders, size_t* quotient_len) {
+    PqShape sh;
+    if (log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns ||
+        t + 1 > sh.rot || !blind_shape_ok(n, t, sh.rot))
+        return KZG_ERR_INVALID_ARG;
+    if (num_blinders) *num_blinders = blind_count(t, sh.rot);
+    if (quotient_len) *quotient_len = blind_quotient_len(n, t, sh.rot);
+    return KZG_OK;
+}
+
+int kzg_circuit_blinders(size_t t, unsigned log_ext, uint64_t* out) {
+    if (!out || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext))
+        return KZG_ERR_INVALID_ARG;
+    const size_t count = blind_count(t, (size_t)1 << log_ext);
+    for (size_t i = 0; i < count; i++) {
+        hf::Fr v;
+        do {  // uniform below r by rejection: r has 255 bits, a draw is kept with probability 0.906
+            if (!vc_random(v.l, 32)) return KZG_ERR_HIP;
+            v.l[3] &= 0x7fffffffffffffffULL;
+        } while (hf::fr_geq(v, hf::kFrMod));
+        std::memcpy(out + 4 * i, v.l, 32);
+    }
+    return KZG_OK;
+}
+
+// evals: k columns of n values over H (host); the k x (n + nb) blinded coefficients go to out_coeffs (host, column c at + 4 c
+// out_stride u64, or null) and their commitments to out_p1s (or null)
+static int blind_evaluations_impl(kzg_ctx* ctx, const char* what, const uint64_t* evals, size_t n, size_t k, size_t stride,
+                                  const uint64_t* blinders, size_t nb, uint64_t* out_coeffs, size_t out_stride, uint64_t* out_p1s) {
+    uint32_t lg_n = 0;
+    if (!ntt_log(n, &lg_n) || k < 1 || k > kMaxCoefficients || stride < n || nb < 1 || nb > kBlindLow || (out_coeffs && out_stride < n + nb))
+        return KZG_ERR_INVALID_ARG;
+    const size_t len = n + nb;
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::vector<hf::Fr> bl;
+    if (!blind_values_ok(ctx, what, blinders, k * nb, &bl)) return KZG_ERR_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    auto srs_status = [&]() {
+        if (!out_p1s) return (int)KZG_OK;
+        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
+        return len > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
+    };
+    int rc = srs_status();
+    if (rc) return rc;
+    int slot = -1;
+    rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    void *in, *stack, *d_bl;
+    rc = pq_bufs(ctx, n, 1, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqIn, k * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqBlind, k * len * 32, &stack);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqChunks, k * nb * 32, &d_bl);
+    if (rc) return rc;
+    uint32_t *d_in = (uint32_t*)in, *d_c = (uint32_t*)stack;
+    rc = pq_upload(ctx, lk, s.stream, d_in, evals, n, k, stride);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, d_bl, blinders, k * nb * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+    if (rc) return rc;
+    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(lg_n)));
+    for (size_t b = 0; b < k; b++) launch_ntt(s.stream, d_in + 8 * b * n, d_c + 8 * b * len, lg_n, itw, inv_n, w.A, w.B);
+    launch_blind_patch(s.stream, d_c, (uint32_t)n, k, len, (const uint32_t*)d_bl, (const uint32_t*)d_bl, (uint32_t)nb, k);
+    HIP_TRY(ctx, hipGetLastError());
+    if (out_coeffs) {
+        lk.unlock();
+        const hipError_t e = hipMemcpy2DAsync(out_coeffs, out_stride * 32, d_c, len * 32, len * 32, k, hipMemcpyDeviceToHost, s.stream);
+        lk.lock();
+        if (e != hipSuccess) return hip_fail(ctx, "hipMemcpy2DAsync (blinded coefficients)", e);
+    }
+    rc = sync_unlocked(ctx, lk, s.stream, what);
+    if (rc || !out_p1s) return rc;
+    return pq_commit_chunks(ctx, lk, slot, d_c, len, k, out_p1s);
+}
+
+int kzg_blind_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t k, size_t stride, const uint64_t* blinders, size_t nb,
+                          uint64_t* out_coeffs, size_t out_stride) {
+    if (!ctx || !evals || !blinders || !out_coeffs) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_blind_evaluations(kid, evals, n, k, stride, blinders, nb, out_coeffs, out_stride));
+    }
+    return blind_evaluations_impl(ctx, "blind evaluations", evals, n, k, stride, blinders, nb, out_coeffs, out_stride, nullptr);
+}
+
+int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t k, size_t stride, const uint64_t* blinders,
+                                   size_t nb, uint64_t* out_p1s) {
+    if (!ctx || !evals || !blinders || !out_p1s) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the blinded commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_commit_evaluations_blinded(kid, evals, n, k, stride, blinders, nb, out_p1s));
+    }
+    return blind_evaluations_impl(ctx, "commit evaluations (blinded)", evals, n, k, stride, blinders, nb, nullptr, 0, out_p1s);
+}
+
+// wires (t columns of n values), z and pi (n values or null) are host pointers, or device pointers when `device`; then out_coeffs
+// (L_T coefficients) is a device pointer.  out_p1s: host, or null
+static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z,
+                                         const void* pi, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                         const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device) {
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    PqShape sh;
+    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, N = sh.N, t = c->t, e = sh.rot, ncols = t + 1 + (pi ? 1 : 0);
+    if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit quotient (blinded)");
+    std::vector<hf::Fr> bl;
+    if (!blind_values_ok(ctx, "circuit quotient (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+    const size_t LT = blind_quotient_len(n, t, e), keep = t * n + t + 3, clen = n + kBlindZLen, Lc = n + t + 3;
+    if (device) {
+        const size_t ob = LT * 32;
+        if (pq_overlap(out_coeffs, ob, wires, ((t - 1) * stride + n) * 32) || pq_overlap(out_coeffs, ob, z, n * 32) ||
+            (pi && pq_overlap(out_coeffs, ob, pi, n * 32))) {
+            ctx->last_error = "circuit quotient (blinded): the output overlaps an input";
+            return KZG_ERR_INVALID_ARG;
+        }
+    }
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    auto srs_status = [&]() {
+        if (!out_p1s) return (int)KZG_OK;
+        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
+        return Lc > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
+    };
+    int rc = srs_status();
+    if (rc) return rc;
+    int slot = -1;
+    rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    PqBufs w;
+    void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *stack, *chunks;
+    // the blinders as the patches read them: the array as given, then a zero and the chunk blinders once more ([0, d_0 .. d_(e-3)]
+    // are the low blinders of the e - 1 chunks, [d_0 ..] the high ones)
+    const size_t nbl = blind_count(t, e), bl_words = 8 * (nbl + 1 + (e - 2));
+    rc = pq_bufs(ctx, N, ncols, &w);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqIn, ncols * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, ncols * N * 32, &cols);  // wires, z, PI on the coset
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, LT * 32, &coef);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqBlind, (t + 1) * clen * 32 + bl_words * 4, &stack);  // the blinded coefficients
+    if (rc == KZG_OK && out_p1s) rc = ctx->pq_ws.get(ctx, kPqChunks, (e - 1) * Lc * 32, &chunks);
+    if (rc) return rc;
+    uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
+    uint32_t *d_c = (uint32_t*)stack, *d_bl = d_c + 8 * (t + 1) * clen;
+    {
+        std::vector<uint64_t> hb(bl_words / 2, 0);
+        std::memcpy(hb.data(), blinders, nbl * 32);
+        std::memcpy(hb.data() + 4 * (nbl + 1), blinders + 4 * (2 * t + kBlindZLen), (e - 2) * 32);
+        rc = copy_unlocked(ctx, lk, s.stream, d_bl, hb.data(), bl_words * 4, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+        if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient (blinded)");  // (hb leaves scope)
+        if (rc) return rc;
+    }
+    const uint32_t *src_w = (const uint32_t*)wires, *src_pi = (const uint32_t*)pi, *src_z = (const uint32_t*)z;
+    size_t src_stride = stride;
+    if (!device) {
+        uint32_t* d_in = (uint32_t*)in;
+        rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
+        if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)z, n, 1, n);
+        if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (t + 1) * n, (const uint64_t*)pi, n, 1, n);
+        if (rc) return rc;
+        src_w = d_in;
+        src_z = d_in + 8 * t * n;
+        src_pi = d_in + 8 * (t + 1) * n;
+        src_stride = n;
+    }
+    {  // the wires and z: values -> coefficients -> patch -> the coset, from n + 3 coefficients each
+        const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+        const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
+        for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+        launch_ntt(s.stream, src_z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+        launch_blind_patch(s.stream, d_c, (uint32_t)n, t, clen, d_bl, d_bl, kBlindWireLen, t);
+        launch_blind_patch(s.stream, d_c + 8 * t * clen, (uint32_t)n, 1, clen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, t + 1, sh.lg_N, d_w, w);
+        if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, src_pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
+        if (rc) return rc;
+    }
+    {
+        const hf::Fr a = pq_fr(alpha), b = pq_fr(beta), g = fr_seven();
+        const Fr30 f_beta = fr30_arg_from_mont256(b), f_gamma = pq_image(pq_fr(gamma)), f_one = pq_image(hf::kFrOne);
+        const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2((uint32_t)(14 * t))));
+        const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), fr_pow2(14)));
+        const Fr30 k14 = fr30_arg_from_mont256(fr_pow2(14));
+        Fr30 bkg[kPqMaxColumns];
+        for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(b, pq_fr(c->shifts + 4 * j)), g));
+        const uint32_t* key = c->coset.dev();
+        const CkColumns ck{d_w, key, key + 8 * (t + 2) * N, key + 8 * t * N, key + 8 * (t + 1) * N, d_z, c->l0.dev(), d_pi,
+                           nullptr, c->zinv.dev()};
+        const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
+        launch_ck_constraints(s.stream, ck, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, N, sc, k14, ctx->ntt_tw.p, (uint32_t*)d_out);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // T~ has t n + t + 3 coefficients: those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
+    if (LT > keep) HIP_TRY(ctx, hipMemsetAsync((uint32_t*)coef + 8 * keep, 0, (LT - keep) * 32, s.stream));
+    rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, keep);
+    uint32_t hflag = 0;
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
+    if (rc == KZG_OK && out_coeffs && !device)
+        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, LT * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient (blinded)");
+    if (rc) return rc;
+    if (hflag) {
+        ctx->last_error = "quotient: the blinded numerator is not divisible by X^" + std::to_string(n) +
+                          " - 1 (a coefficient of the interpolant at [t n + t + 3, N) is not zero): the constraints do not hold on the domain";
+        return KZG_ERR_REMAINDER;
+    }
+    if (!out_p1s) return KZG_OK;
+    // the chunks T~_c = T_c + d_c X^n - d_(c-1), each padded to n + t + 3 coefficients; the last one keeps its own top
+    uint32_t* d_ch = (uint32_t*)chunks;
+    const uint32_t* d_t = (const uint32_t*)coef;
+    if (e > 2) HIP_TRY(ctx, hipMemcpy2DAsync(d_ch, Lc * 32, d_t, n * 32, n * 32, e - 2, hipMemcpyDeviceToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ch + 8 * (e - 2) * Lc, d_t + 8 * (e - 2) * n, Lc * 32, hipMemcpyDeviceToDevice, s.stream));
+    if (e > 2) launch_blind_patch(s.stream, d_ch, (uint32_t)n, e - 1, Lc, d_bl + 8 * nbl, d_bl + 8 * (nbl + 1), 1, e - 2);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = srs_status();  // (the waits dropped the mutex)
+    if (rc) return rc;
+    return pq_commit_chunks(ctx, lk, slot, d_ch, Lc, e - 1, out_p1s);
+}
+
+int kzg_circuit_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                 const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                 const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s) {
+    if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma || !blinders) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_quotient_blinded(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders,
+                                                               out_coeffs, out_p1s));
+    }
+    return circuit_quotient_blinded_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders, out_coeffs, out_p1s,
+                                         false);
+}
+
+int kzg_circuit_quotient_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                        const void* d_public_inputs, const uint64_t alpha[4], const uint64_t beta[4],
+                                        const uint64_t gamma[4], const uint64_t* blinders, void* d_out_coeffs, uint64_t* out_p1s) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !d_wires || !d_z || !alpha || !beta || !gamma || !blinders || !d_out_coeffs) return KZG_ERR_INVALID_ARG;
+    return circuit_quotient_blinded_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, alpha, beta, gamma, blinders, d_out_coeffs,
+                                         out_p1s, true);
+}
+
 // ---- the last round of a circuit's proof: linearise, open once (linearise_kernels.hip) --------------------
 // The calls hold quotient_mu, then the context's mutex and one slot, as the quotient's calls above: the per-proof coefficients live
 // in pq_ws, the tables, the values and the G_p in the slot's buffers of the openings at several point sets.
@@ -5823,14 +6108,96 @@ int lin_remainder(kzg_ctx* ctx) {
                       "these wires and this z";
     return KZG_ERR_REMAINDER;
 }
+
+// The slot's table of a blinded round (s.btab): per distinct point the records of k_blind_tail and the t + 6 powers of the point,
+// then the blinders as the records point at them, 32 bytes an entry: [b_j0, b_j1, 0] per wire, [c_0, c_1, c_2], and per chunk of T
+// [d_(c-1), 0, 0, d_c] (d_(-1) = d_(e-2) = 0).
+constexpr size_t kBlindPointBytes = 1536, kBlindValueBytes = 64 * 32;
+static_assert(kBlindMaxColumns * sizeof(BlindColumn) + (kPqMaxColumns + 3 + kBlindLow) * sizeof(Fr30) <= kBlindPointBytes, "btab");
+static_assert((3 * kPqMaxColumns + 3 + 4 * 7) * 32 <= kBlindValueBytes, "btab");
+static_assert(kPqMaxColumns + 2 + 7 <= kBlindMaxColumns, "the wires, z twice (n = 1: one point) and the chunks of T");
+// Behind the launches of k_lin_combine (G_p over [0, n) from the unblinded columns, at s.sg + 8 p L words): what the blinders add.
+// lin: r~'s terms with the scalars of the blinded evaluations; d_t: T~'s coefficients, whose last chunk reaches to n + t + 3.
+int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin, const std::vector<hf::Fr>& bl, const uint32_t* d_t,
+                size_t n, size_t t, size_t e, uint32_t* d_y) {
+    const size_t ntail = t + 3, L = n + ntail, val_off = kSetsMaxPoints * kBlindPointBytes, zb = 3 * t, cb = 3 * t + 3;
+    uint8_t* h = (uint8_t*)s.btab.h;
+    const uint8_t* d = (const uint8_t*)s.btab.d;
+    uint64_t* hv = (uint64_t*)(h + val_off);
+    const uint32_t* dv = (const uint32_t*)(d + val_off);
+    std::memset(hv, 0, kBlindValueBytes);
+    for (size_t j = 0; j < t; j++) {
+        std::memcpy(hv + 4 * (3 * j), bl[2 * j].l, 32);
+        std::memcpy(hv + 4 * (3 * j + 1), bl[2 * j + 1].l, 32);
+    }
+    for (size_t k = 0; k < kBlindZLen; k++) std::memcpy(hv + 4 * (zb + k), bl[2 * t + k].l, 32);
+    const hf::Fr* dc = bl.data() + 2 * t + kBlindZLen;  // d_0 .. d_(e-3)
+    for (size_t c = 0; c + 1 < e; c++) {
+        if (c >= 1) std::memcpy(hv + 4 * (cb + 4 * c), dc[c - 1].l, 32);
+        if (c + 2 < e) std::memcpy(hv + 4 * (cb + 4 * c + 3), dc[c].l, 32);
+    }
+    auto column = [&](size_t low_entry, const uint32_t* tail, size_t tail_len, const hf::Fr& mult) {
+        BlindColumn col = {};
+        col.tail = tail;
+        col.low = dv + 8 * low_entry;
+        const Fr30 m = fr30_arg_from_mont256(mult);
+        std::memcpy(col.mult, m.d, sizeof col.mult);
+        col.tail_len = (uint32_t)tail_len;
+        return col;
+    };
+    uint32_t ncols[KZG_MAX_SET_POINTS];
+    for (size_t p = 0; p < plan.npts; p++) {
+        BlindColumn* out = (BlindColumn*)(h + p * kBlindPointBytes);
+        uint32_t k = 0;
+        for (uint32_t en = plan.off[p]; en < plan.off[p + 1]; en++) {
+            const uint32_t i = plan.sel[en];
+            const hf::Fr& m = plan.mult[en];
+            if (i == 0) {  // r~: z~ and the chunks of T~ with r's scalars
+                out[k++] = column(zb, dv + 8 * zb, kBlindZLen, hf::fr_mul(m, lin.terms[t + 2].scalar));
+                for (size_t c = 0; c + 1 < e; c++) {
+                    const hf::Fr sc = hf::fr_mul(m, lin.terms[t + 4 + c].scalar);
+                    if (c + 2 < e) out[k++] = column(cb + 4 * c, dv + 8 * (cb + 4 * c + 3), 1, sc);
+                    else out[k++] = column(cb + 4 * c, d_t + 8 * (e - 1) * n, ntail, sc);
+                }
+            } else if (i <= t) {
+                out[k++] = column(3 * (i - 1), dv + 8 * 3 * (i - 1), kBlindWireLen, m);
+            } else if (i == 2 * t) {
+                out[k++] = column(zb, dv + 8 * zb, kBlindZLen, m);
+            }  // (the sigmas are the key's: not blinded)
+            if (k > kBlindMaxColumns) return KZG_ERR_INVALID_ARG;  // (cannot happen: the static_assert above)
+        }
+        ncols[p] = k;
+        Fr30* pw = (Fr30*)(h + p * kBlindPointBytes + kBlindMaxColumns * sizeof(BlindColumn));
+        hf::Fr cur = hf::fr_pow(plan.pts[p], n);
+        for (size_t j = 0; j < ntail; j++) {
+            pw[j] = fr30_arg_from_mont256(cur);
+            cur = hf::fr_mul(cur, plan.pts[p]);
+        }
+        cur = hf::kFrOne;
+        for (size_t i = 0; i < kBlindLow; i++) {
+            pw[ntail + i] = fr30_arg_from_mont256(cur);
+            cur = hf::fr_mul(cur, plan.pts[p]);
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.btab.d, s.btab.h, val_off + kBlindValueBytes, hipMemcpyHostToDevice, s.stream));
+    for (size_t p = 0; p < plan.npts; p++)
+        launch_blind_tail(s.stream, (const BlindColumn*)(d + p * kBlindPointBytes), ncols[p], (uint32_t)n, (uint32_t)ntail,
+                          (const Fr30*)(d + p * kBlindPointBytes + kBlindMaxColumns * sizeof(BlindColumn)), s.sg.dev() + 8 * p * L,
+                          d_y + 8 * p);
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
 }  // namespace
 
 // wires (t columns of n values), z, pi (n values or null) and t_coeffs (N - n coefficients) are host pointers, or device pointers
 // when `device`.  v null: the test hook -- r's n coefficients to out_r, no SRS; else the proof to out_p1.
+// blinders (host, or null; never with the test hook): the blinded round of DESIGN.md section 4.24 -- t_coeffs holds T~'s L_T
+// coefficients, the evaluations are those of the blinded polynomials, every G_p has n + t + 3 coefficients: k_lin_combine sums
+// [0, n) from the unblinded columns as before and k_blind_tail adds what the blinders change.
 static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                              const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                              const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
-                             bool device) {
+                             bool device, const uint64_t* blinders = nullptr) {
     std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
@@ -5843,6 +6210,13 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         return KZG_ERR_INVALID_ARG;
     }
     const size_t n = sh.n, N = sh.N, t = c->t, npoly = 2 * t + 1, ncoef = t + 1 + (pi ? 1 : 0);
+    // blinded: every polynomial of the stack is padded to L = n + t + 3 coefficients, T~ has L_T of them
+    const size_t e = sh.rot, ntail = blinders ? t + 3 : 0, L = n + ntail, t_len = blinders ? blind_quotient_len(n, t, e) : N - n;
+    std::vector<hf::Fr> bl;
+    if (blinders) {
+        if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit open (blinded)");
+        if (!blind_values_ok(ctx, "circuit open (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+    }
     // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1)
     const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
     std::vector<uint32_t> set_of(npoly, 0);
@@ -5861,7 +6235,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     auto srs_status = [&]() {
         if (!v) return (int)KZG_OK;
         if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
-        return n - 1 > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
+        return L - 1 > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
     };
     int rc = srs_status();
     if (rc) return rc;
@@ -5879,10 +6253,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqIn, ncoef * n * 32, &in);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, ncoef * n * 32, &stack);  // the coefficients of the wires, PI, z
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, n * 32, &scratch);         // the passes' by-product; r for the test hook
-    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
+    if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, t_len * 32, &coef);
     if (rc == KZG_OK) rc = sets_job_start(ctx, s, plan);
-    if (rc == KZG_OK) rc = sets_ensure_all(ctx, s, plan, n, t + 1, 0);
+    if (rc == KZG_OK) rc = sets_ensure_all(ctx, s, plan, L, t + 1, 0);
     if (rc == KZG_OK) rc = s.ltab.reserve(ctx, kSetsMaxPoints * kLinMaxColumns * sizeof(LinColumn), s.stream);
+    if (rc == KZG_OK && blinders) rc = s.btab.reserve(ctx, kSetsMaxPoints * kBlindPointBytes + kBlindValueBytes, s.stream);
     if (rc) return rc;
     // 1. coefficients: [ f_0 .. f_(t-1) | PI | z ], one inverse transform each
     uint32_t *d_f = (uint32_t*)stack, *d_pi = pi ? d_f + 8 * t * n : nullptr, *d_z = d_f + 8 * (ncoef - 1) * n;
@@ -5894,7 +6269,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
             rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
             if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)pi, n, 1, n);
             if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (ncoef - 1) * n, (const uint64_t*)z, n, 1, n);
-            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)coef, (const uint64_t*)t_coeffs, N - n, 1, N - n);
+            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)coef, (const uint64_t*)t_coeffs, t_len, 1, t_len);
             if (rc) return rc;
             src_w = d_in;
             src_pi = d_in + 8 * t * n;
@@ -5937,6 +6312,14 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     std::memcpy(ys[2 * t].l, hv + 8 * 2 * t, 32);
     hf::Fr pi_zeta = kFrZero;
     if (pi) std::memcpy(pi_zeta.l, hv + 8 * t, 32);
+    if (blinders) {  // f~_j(zeta) = f_j(zeta) + b_j(zeta) Z, z~(zeta w) = z(zeta w) + c(zeta w) Z: (zeta w)^n = zeta^n
+        const hf::Fr Z = hf::fr_sub(hf::fr_pow(ch.zeta, n), hf::kFrOne);
+        for (size_t j = 0; j < t; j++)
+            ys[1 + j] = hf::fr_add(ys[1 + j], hf::fr_mul(hf::fr_add(bl[2 * j], hf::fr_mul(bl[2 * j + 1], ch.zeta)), Z));
+        const hf::Fr* cz = &bl[2 * t];
+        const hf::Fr cw = hf::fr_add(cz[0], hf::fr_mul(zeta_w, hf::fr_add(cz[1], hf::fr_mul(zeta_w, cz[2]))));
+        ys[2 * t] = hf::fr_add(ys[2 * t], hf::fr_mul(cw, Z));
+    }
     for (size_t i = 1; i < npoly; i++) std::memcpy(out_evals + 4 * (i - 1), ys[i].l, 32);
     LinPoly lin;
     lin_poly(c, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, key, d_z, (const uint32_t*)coef, &lin);
@@ -5990,7 +6373,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[0], s.stream));
     for (size_t p = 0; p < plan.npts; p++)
         launch_lin_combine(s.stream, d_cols + p * kLinMaxColumns, ncols[p], (uint32_t)n, d_tab + p * kCombineTabGamma, konst[p],
-                           s.sg.dev() + 8 * p * n, s.cpart.dev(), d_y + 8 * p);
+                           s.sg.dev() + 8 * p * L, s.cpart.dev(), d_y + 8 * p);
+    if (blinders) {
+        rc = blind_tails(ctx, s, plan, lin, bl, (const uint32_t*)coef, n, t, e, d_y);
+        if (rc) return rc;
+    }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
     HIP_TRY(ctx, hipGetLastError());
     rc = sync_unlocked(ctx, lk, s.stream, "circuit open (sums)");
@@ -6001,7 +6388,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (!fr_equal(got, want[0])) return lin_remainder(ctx);
     // 4. the scans and the MSM of kzg_open_sets, unchanged
     rc = srs_status();  // (the waits dropped the mutex)
-    if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, n);
+    if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, L);
     if (rc) return rc;
     await_unlocked(lk, s);
     std::vector<uint64_t> unused(4 * plan.nvals);
@@ -6040,6 +6427,37 @@ int kzg_circuit_open_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void
         return KZG_ERR_INVALID_ARG;
     return circuit_open_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, d_t_coeffs, alpha, beta, gamma, zeta, v, out_evals,
                              nullptr, out_p1, true);
+}
+
+int kzg_circuit_open_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                             const uint64_t* public_inputs, const uint64_t* t_coeffs, const uint64_t alpha[4], const uint64_t beta[4],
+                             const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4], const uint64_t* blinders,
+                             uint64_t* out_evals, uint64_t out_p1[18]) {
+    if (!ctx || !circuit || !wires || !z || !t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !blinders || !out_evals || !out_p1)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the opening needs the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_open_blinded(kid, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma,
+                                                           zeta, v, blinders, out_evals, out_p1));
+    }
+    return circuit_open_impl(ctx, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta, v, out_evals, nullptr,
+                             out_p1, false, blinders);
+}
+
+int kzg_circuit_open_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const void* d_wires, size_t stride, const void* d_z,
+                                    const void* d_public_inputs, const void* d_t_coeffs, const uint64_t alpha[4],
+                                    const uint64_t beta[4], const uint64_t gamma[4], const uint64_t zeta[4], const uint64_t v[4],
+                                    const uint64_t* blinders, uint64_t* out_evals, uint64_t out_p1[18]) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !d_wires || !d_z || !d_t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !blinders || !out_evals ||
+        !out_p1)
+        return KZG_ERR_INVALID_ARG;
+    return circuit_open_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, d_t_coeffs, alpha, beta, gamma, zeta, v, out_evals,
+                             nullptr, out_p1, true, blinders);
 }
 
 int kzg_circuit_linearise(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,

@@ -462,6 +462,30 @@ struct LinConst {
 void launch_lin_combine(hipStream_t s, const LinColumn* d_cols, uint32_t ncols, uint32_t n, const Fr30* d_tab, const LinConst& konst,
                         uint32_t* d_out, uint32_t* d_partial, uint32_t* d_y);
 
+// ---- blind_kernels.hip: the blinders of a circuit proof in coefficient form -------------------------
+// k columns of n canonical coefficients (column c at d_cols + 8 c stride words); d_lo, d_hi: nb <= kBlindLow canonical values
+// per column (column c at + 8 c nb words).  Column c < k_hi: coefficient i < nb loses d_lo[c][i], index n + i receives d_hi[c][i]
+// (less d_lo[c][n + i] where n + i < nb) and [n + nb, stride) is zeroed, stride >= n + nb.  A column from k_hi on only loses d_lo
+// below n.  The blinders overlap no column.
+constexpr uint32_t kBlindLow = 3;          // a blinder has at most three coefficients
+constexpr uint32_t kBlindMaxColumns = 16;  // per-proof columns of the last round: t wires, z, e - 1 chunks of T
+void launch_blind_patch(hipStream_t s, uint32_t* d_cols, uint32_t n, uint64_t k, uint64_t stride, const uint32_t* d_lo,
+                        const uint32_t* d_hi, uint32_t nb, uint64_t k_hi);
+// What the blinders add to a sum of launch_lin_combine: d_out holds n + ntail values, [0, n) written by that launch, d_y its value
+// at z.  Column k contributes mult_k tail_k[i] at index n + i (i < tail_len <= ntail) and - mult_k low_k[i] at index i < kBlindLow
+// (low null: nothing); [n, n + ntail) is written in full, d_y becomes d_out(z) over all n + ntail values.  d_pw: ntail + kBlindLow
+// multipliers, z^(n + j) for j < ntail, then z^i.  kBlindLow <= ntail, ncols <= kBlindMaxColumns; tails, lows and d_out are
+// canonical blst_fr images that do not overlap; multipliers canonical, x 2^270.
+struct BlindColumn {
+    const uint32_t* tail;
+    const uint32_t* low;
+    int32_t mult[9];  // the digits of an Fr30
+    uint32_t tail_len;
+};
+static_assert(sizeof(BlindColumn) == 56, "the device reads the records the host wrote");
+void launch_blind_tail(hipStream_t s, const BlindColumn* d_cols, uint32_t ncols, uint32_t n, uint32_t ntail, const Fr30* d_pw,
+                       uint32_t* d_out, uint32_t* d_y);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

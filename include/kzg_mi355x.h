@@ -356,6 +356,25 @@ int kzg_ntt(kzg_ctx* ctx, const uint64_t* in, size_t n, int inverse, uint64_t* o
 /* the same on kzg_dev_alloc buffers of the context's GPU (single-device contexts); d_in == d_out allowed; returns when
  * the result is in d_out */
 int kzg_ntt_device(kzg_ctx* ctx, const void* d_in, void* d_out, size_t n, int inverse);
+/* kzg_ntt of `batch` columns in one call: column b is the n blst_fr at in + 4 b in_stride u64 and its transform goes to
+ * out + 4 b out_stride u64, bit for bit what kzg_ntt gives for that column; the strides are in values, and the values
+ * between two columns (strides above n) are neither read nor written.  Every pass of the transform is one launch for the
+ * columns in flight (k_nttb_pass), where kzg_ntt per column makes one launch per column and pass.
+ * in == out with equal strides is allowed; any other overlap of the two sides, a stride below n, kzg_ntt's argument errors
+ * and extents beyond the address space -> KZG_ERR_INVALID_ARG.  batch == 0 does nothing.  Synchronous; no SRS needed.  The
+ * two intermediate buffers (and the staging buffer of the host form) come from the quotient calls' workspaces: a quarter of
+ * their budget each (KZG_PQ_WS_KB) and at most 64 columns, so a larger batch runs in several rounds with the same result,
+ * and the call takes its turn with the quotient calls of the context.  Multi-device contexts run it on devices[0]. */
+int kzg_ntt_batch(kzg_ctx* ctx, const uint64_t* in, size_t n, size_t batch, size_t in_stride, int inverse, uint64_t* out,
+                  size_t out_stride);
+/* host only, a test hook: the rounds kzg_ntt_batch / kzg_ntt_batch_device take for `batch` columns of n values on this context,
+ * ceil(batch / min(64, budget / (4 n 32))), 0 for an empty batch; the budget is read from KZG_PQ_WS_KB when the context is made.
+ * It exists so that a test can see that a small budget really splits a batch; a caller has no need of it. */
+int kzg_ntt_batch_rounds(kzg_ctx* ctx, size_t n, size_t batch, size_t* rounds);
+/* the same on kzg_dev_alloc buffers of the context's GPU (single-device contexts): nothing crosses PCIe; returns when the
+ * result is in d_out */
+int kzg_ntt_batch_device(kzg_ctx* ctx, const void* d_in, size_t n, size_t batch, size_t in_stride, void* d_out, size_t out_stride,
+                         int inverse);
 /* kzg_commit of the interpolated coefficients, bit for bit: one upload, the inverse NTT into the slot's staging
  * buffer, the same MSM */
 int kzg_commit_evaluations(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t n, uint64_t out_p1[18]);
@@ -686,6 +705,74 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
                        const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
                        const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
+
+/* ---- a circuit's proof as bytes: the hashed transcript and the proof format (host only) -----------------
+ * kzg_circuit_verify takes five challenges "as given".  These calls fix where they come from, so that the order -- beta and gamma
+ * after the wires, alpha after [z], zeta after the [T_c], v after the evaluations -- is no longer the caller's to get wrong.
+ * Hash: SHA-256.  fr(d) = the digest d read as a big-endian integer, reduced mod r (kzg_blob_challenges_bytes' reduction).
+ * Scalars travel as 32 big-endian canonical bytes, points as 48 compressed bytes (kzg_g1_compress; infinity is c0 00 ..),
+ * u64be(x) is 8 bytes, e = 2^log_ext:
+ *     DST = ASCII "kzg_mi355x/plonk/v1"                                             (19 bytes, no terminator)
+ *     h0  = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(n_public) | shifts (t x 32)
+ *                  | key commitments ((2 t + 2) x 48, kzg_circuit_create's order) | public inputs (n_public x 32))
+ *     h1  = SHA256(h0 | wire commitments (t x 48))        beta = fr(SHA256(h1 | 00)),  gamma = fr(SHA256(h1 | 01))
+ *     h2  = SHA256(h1 | [z] (48))                          alpha = fr(SHA256(h2 | 00))
+ *     h3  = SHA256(h2 | [T_0] .. [T_(e-2)] ((e - 1) x 48)) zeta = fr(SHA256(h3 | 00))
+ *     h4  = SHA256(h3 | evaluations (2 t x 32, kzg_circuit_open's out_evals order))  v = fr(SHA256(h4 | 00))
+ * PROOF BYTES, in this order: the t wire commitments, [z], the e - 1 chunk commitments, the 2 t evaluations, the opening W:
+ * 48 (t + e + 1) + 64 t bytes, 576 for t = 3, e = 4 (kzg_circuit_proof_size; KZG_ERR_INVALID_ARG for a t or log_ext that
+ * kzg_circuit_verify refuses).  Public inputs as for kzg_circuit_verify: n_public <= n values at rows 0 .. n_public - 1.
+ * kzg_circuit_prove makes such bytes in one call; kzg_circuit_verify_proof checks them. */
+int kzg_circuit_proof_size(size_t t, unsigned log_ext, size_t* bytes);
+/* out: beta, gamma, alpha, zeta, v as 5 x 4 u64 (blst_fr), from complete proof bytes.  A building block and test hook: the bytes
+ * are hashed as they are, no point is decoded.  KZG_ERR_INVALID_ARG: a NULL pointer (public_inputs may be NULL with n_public = 0),
+ * kzg_circuit_verify's shape errors, a shift or public input not below r, proof_len other than kzg_circuit_proof_size. */
+int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                                 const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, uint64_t* out);
+/* Decodes the proof, derives the challenges and calls kzg_circuit_verify.  Its argument errors are kzg_circuit_verify's, and a
+ * proof_len other than kzg_circuit_proof_size is KZG_ERR_INVALID_ARG too.  A proof whose bytes do not decode -- an evaluation not
+ * below r, a point kzg_g1_uncompress refuses (not on the curve, an abscissa not below p), flag bits that contradict the encoding
+ * -- returns KZG_OK with *valid = 0.  Order: the pointers, the shape, proof_len, the shifts and public inputs below r and the key's
+ * commitments on the curve are checked before the proof is decoded; what kzg_circuit_verify finds only in its pairing check (a
+ * setup point off its curve) is reported for a proof that decodes.  Points are decoded by kzg_g1_uncompress: an on-curve check and NO subgroup check, as every
+ * host verifier of this library; a caller who needs one runs kzg_g1_uncompress_batch with check_subgroup over the first
+ * 48 (t + e) bytes and the last 48. */
+int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                             size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
+
+/* The proof of a circuit in one call: the five rounds under the transcript above, every challenge derived inside.
+ *   1. the wires go to the device and to coefficient form (with their blinder patches when blinded), are committed; beta, gamma
+ *   2. z is formed on the device from the wires and the circuit's resident sigma values (kzg_permutation_product_device's work,
+ *      nothing downloaded); z_n != 1 -> KZG_ERR_REMAINDER; z is committed; alpha
+ *   3. the quotient and its chunks' commitments; zeta          4. the evaluations; v, which is fixed AFTER them
+ *   5. r, r(zeta) = 0 tested before the MSM, the opening W
+ * key_p1s: the (2 t + 2) x 18 commitments of kzg_circuit_create (they enter the transcript).  wires: t columns of n blst_fr, column j
+ * at wires + 4 j stride u64.  public_inputs: n_public <= n values at rows 0 .. n_public - 1 (NULL with n_public = 0); they are
+ * padded with zeros to n values and added "as given", as kzg_circuit_quotient does.  blinders: NULL for a plain proof, which is
+ * NOT zero-knowledge, else kzg_circuit_blinders' array.  out_proof: kzg_circuit_proof_size bytes.
+ * The bytes are bit for bit what the existing calls give when chained by hand with the transcript's challenges: blinded
+ * kzg_commit_evaluations_blinded (wires with nb = 2, z with nb = 3), kzg_circuit_quotient_blinded, kzg_circuit_open_blinded; plain
+ * kzg_commit_evaluations, kzg_circuit_quotient, kzg_circuit_open; the outputs compressed and serialised.
+ * The call holds one slot and takes its turn with the quotient calls from start to end.  Every per-proof column is transformed
+ * back ONCE (the hand chain does it three times), the transforms of more than one column are batched (k_nttb_pass), and nothing
+ * but the wires, the public inputs, the blinders and the proof crosses PCIe apart from what the rounds exchange anyway: the
+ * commitments off the MSM's host tail, the 2 t + 1 evaluation words and r(zeta).
+ * MEMORY: what lives across the rounds -- the values and the coefficients of the t + 2 per-proof columns, the blinded copies, T --
+ * sits in device buffers that the context keeps after the first proof, grown to the largest proof made and freed only by
+ * kzg_ctx_destroy: about (3 t + e + 5) n x 32 bytes for a blinded proof with public inputs, 544 MiB at n = 2^20, t = 3, e = 4.
+ * HOST TIME: the transcript hashes every public input, so a proof (and kzg_circuit_verify_proof) with n_public = 2^20 spends 55 ms
+ * of host time on them alone; with the few public inputs a statement usually has it is microseconds.
+ * Statuses, in this order: KZG_ERR_INVALID_ARG (NULL pointers, a circuit of another context, stride < n, n_public > n, a public
+ * input or blinder not below r, for blinded proofs the shape rule N >= t n + t + 4), KZG_ERR_NO_SRS, KZG_ERR_DEGREE_TOO_HIGH (n
+ * points for a plain proof, n + t + 3 for a blinded one), the grand product's zero-denominator status with its message,
+ * KZG_ERR_REMAINDER (z_n != 1, the quotient, r(zeta)).  A failed call writes nothing to out_proof and leaves the context serving.
+ * Multi-device contexts as kzg_circuit_quotient with commitments: a replicated one forwards, a range-split one is refused. */
+int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                      const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof);
+/* the same with the wires in a kzg_dev_alloc buffer of a single-device context (public inputs, blinders and the proof stay host) */
+int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof);
 
 /* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
  * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the

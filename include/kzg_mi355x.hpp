@@ -662,6 +662,51 @@ class Circuit {
         if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
         return valid != 0;
     }
+    // The proof in one call (kzg_circuit_prove): wires t x n values back to back, public_inputs the values of rows 0 .. size - 1
+    // (may be empty), blinders empty for a plain proof (NOT zero-knowledge) or the array of kzg_circuit_blinders -> the proof bytes
+    std::vector<uint8_t> prove(const std::vector<Scalar>& wires, const std::vector<Scalar>& public_inputs,
+                               const std::vector<Scalar>& blinders) const {
+        if (wires.size() != n_ * t_ || key_.size() != 2 * t_ + 2)
+            throw Error(KZG_ERR_INVALID_ARG, "Circuit::prove: t x n wire values and the key's commitments");
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        std::vector<uint8_t> out(proof_size(t_, log_ext_));
+        check(kzg_circuit_prove(ctx_, c_, reinterpret_cast<const uint64_t*>(key_.data()), u(wires), n_, u(public_inputs),
+                                public_inputs.size(), u(blinders), out.data()),
+              ctx_);
+        return out;
+    }
+    // Host only, no context: the proof as bytes under the hashed transcript (kzg_circuit_proof_size, kzg_circuit_proof_challenges,
+    // kzg_circuit_verify_proof).  challenges: beta, gamma, alpha, zeta, v from the bytes as they are (a prover calls it on the bytes
+    // written so far); verify_proof: false also for bytes that do not decode; points are checked to lie on the curve only
+    static size_t proof_size(size_t t, unsigned log_ext) {
+        size_t bytes = 0;
+        const int rc = kzg_circuit_proof_size(t, log_ext, &bytes);
+        if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
+        return bytes;
+    }
+    static std::array<Scalar, 5> proof_challenges(const std::vector<G1Point>& key, size_t n, unsigned log_ext, const std::vector<Scalar>& shifts,
+                                                  const std::vector<Scalar>& public_inputs, const std::vector<uint8_t>& proof) {
+        if (key.size() != 2 * shifts.size() + 2) throw Error(KZG_ERR_INVALID_ARG, "Circuit::proof_challenges: 2 t + 2 key commitments");
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        std::array<Scalar, 5> out;
+        const int rc = kzg_circuit_proof_challenges(reinterpret_cast<const uint64_t*>(key.data()), n, shifts.size(), log_ext, u(shifts),
+                                                    u(public_inputs), public_inputs.size(), proof.data(), proof.size(),
+                                                    reinterpret_cast<uint64_t*>(out.data()));
+        if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
+        return out;
+    }
+    static bool verify_proof(const std::vector<G1Point>& key, size_t n, unsigned log_ext, const std::vector<Scalar>& shifts,
+                             const std::vector<Scalar>& public_inputs, const std::vector<uint8_t>& proof, const G1Point& setup_g1,
+                             const uint64_t* setup_g2) {
+        if (key.size() != 2 * shifts.size() + 2) throw Error(KZG_ERR_INVALID_ARG, "Circuit::verify_proof: 2 t + 2 key commitments");
+        const auto u = [](const std::vector<Scalar>& x) { return x.empty() ? nullptr : reinterpret_cast<const uint64_t*>(x.data()); };
+        int valid = 0;
+        const int rc = kzg_circuit_verify_proof(reinterpret_cast<const uint64_t*>(key.data()), n, shifts.size(), log_ext, u(shifts),
+                                                u(public_inputs), public_inputs.size(), proof.data(), proof.size(), &setup_g1,
+                                                sizeof(G1Point), setup_g2, 288, &valid);
+        if (rc != KZG_OK) throw Error(rc, kzg_strerror(rc));
+        return valid != 0;
+    }
     // a resident column on the device, read-only: (pointer, length)
     std::pair<const void*, size_t> column_device(unsigned which, unsigned form) const {
         const void* p = nullptr;

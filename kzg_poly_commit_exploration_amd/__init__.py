@@ -20,7 +20,8 @@ __all__ = [
     "R_MODULUS", "lib_path", "load_library", "ABI_SYMBOLS", "srs_g2_at", "verify_proof", "verify_proof_batch",
     "verify_points", "KZG_MAX_OPEN_POINTS", "KZG_NTT_MAX_LOG", "KZG_GP_MAX_COLUMNS", "KZG_PQ_MAX_COLUMNS", "KZG_LOGUP_MAX_COLUMNS",
     "KZG_PQ_MAX_LOG_EXT", "KZG_EXTEND_VALUES", "KZG_EXTEND_COEFFS", "domain_root",
-    "Circuit", "circuit_verify", "circuit_blinders", "circuit_blinded_sizes", "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
+    "Circuit", "circuit_verify", "circuit_blinders", "circuit_blinded_sizes", "circuit_proof_size", "circuit_proof_challenges", "circuit_verify_proof",
+    "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
     "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
@@ -86,6 +87,9 @@ ABI_SYMBOLS = [
     "kzg_circuit_blinded_sizes", "kzg_circuit_blinders", "kzg_blind_evaluations", "kzg_commit_evaluations_blinded",
     "kzg_circuit_quotient_blinded", "kzg_circuit_quotient_blinded_device", "kzg_circuit_open_blinded",
     "kzg_circuit_open_blinded_device",
+    "kzg_ntt_batch", "kzg_ntt_batch_device", "kzg_ntt_batch_rounds",
+    "kzg_circuit_proof_size", "kzg_circuit_proof_challenges", "kzg_circuit_verify_proof",
+    "kzg_circuit_prove", "kzg_circuit_prove_device",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -198,6 +202,9 @@ def load_library():
         "kzg_domain_root": (i, [C.c_uint, vp]),
         "kzg_ntt": (i, [vp, vp, sz, i, vp]),
         "kzg_ntt_device": (i, [vp, vp, vp, sz, i]),
+        "kzg_ntt_batch": (i, [vp, vp, sz, sz, sz, i, vp, sz]),
+        "kzg_ntt_batch_device": (i, [vp, vp, sz, sz, sz, vp, sz, i]),
+        "kzg_ntt_batch_rounds": (i, [vp, sz, sz, C.POINTER(sz)]),
         "kzg_commit_evaluations": (i, [vp, vp, sz, vp]),
         "kzg_commit_evaluations_submit": (i, [vp, i, vp, sz]),
         "kzg_open_evaluations": (i, [vp, vp, sz, vp, vp, vp]),
@@ -252,6 +259,11 @@ def load_library():
         "kzg_circuit_open_blinded_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_verify": (i, [vp, sz, sz, C.c_uint, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz,
                                    C.POINTER(C.c_int)]),
+        "kzg_circuit_prove": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_prove_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_proof_size": (i, [sz, C.c_uint, C.POINTER(sz)]),
+        "kzg_circuit_proof_challenges": (i, [vp, sz, sz, C.c_uint, vp, vp, sz, vp, sz, vp]),
+        "kzg_circuit_verify_proof": (i, [vp, sz, sz, C.c_uint, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
         "kzg_cells_and_proofs": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_cells_and_proofs_evaluations": (i, [vp, vp, sz, C.c_uint, C.c_uint, vp, vp]),
         "kzg_quotient_cells": (i, [vp, vp, sz, C.c_uint, C.c_uint, sz, sz, vp, C.POINTER(sz)]),
@@ -1195,6 +1207,30 @@ class Engine:
     def ntt_device(self, d_in, d_out, n, inverse=False):
         _check(self._lib.kzg_ntt_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n, 1 if inverse else 0), self._h)
 
+    def ntt_batch_limbs(self, columns, n, inverse=False, out=None):
+        """kzg_ntt of every column in one call.  columns: an array (batch, in_stride, 4) whose column b holds its n values
+        first (in_stride >= n; the rows after them are not read).  out: an array (batch, out_stride, 4) written in place
+        (only the first n rows of each column; out may be `columns` itself), or None for a new (batch, n, 4) array."""
+        a = np.ascontiguousarray(columns, dtype=np.uint64)
+        assert a.ndim == 3 and a.shape[2] == 4, "columns: (batch, in_stride, 4)"
+        if out is None:
+            out = np.zeros((a.shape[0], n, 4), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.ndim == 3 and out.shape[0] == a.shape[0] and out.shape[2] == 4
+        _check(self._lib.kzg_ntt_batch(self._h, _ptr(a), n, a.shape[0], a.shape[1], 1 if inverse else 0, _ptr(out), out.shape[1]),
+               self._h)
+        return out
+
+    def ntt_batch_rounds(self, n, batch):
+        """kzg_ntt_batch_rounds: the rounds a batched transform of `batch` columns of n values takes on this context"""
+        out = C.c_size_t(0)
+        _check(self._lib.kzg_ntt_batch_rounds(self._h, n, batch, C.byref(out)), self._h)
+        return out.value
+
+    def ntt_batch_device(self, d_in, n, batch, in_stride, d_out, out_stride, inverse=False):
+        """the same on device buffers: column b at d_in + 32 b in_stride bytes, to d_out + 32 b out_stride bytes"""
+        _check(self._lib.kzg_ntt_batch_device(self._h, C.c_void_p(d_in), n, batch, in_stride, C.c_void_p(d_out), out_stride,
+                                              1 if inverse else 0), self._h)
+
     def commit_evaluations_limbs(self, evals):
         a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros(18, dtype=np.uint64)
@@ -1770,6 +1806,34 @@ class Circuit:
         return self._split_evals(ev), r
 
     # -- the blinded rounds --
+    def _prove(self, fn, e, wires_arg, stride, public_inputs, blinders):
+        assert self.key is not None, "prove: the circuit was created without its key commitments"
+        rows = np.ascontiguousarray(np.stack([c.p1 for c in self.key]), dtype=np.uint64)
+        pub = None
+        if public_inputs is not None and len(public_inputs):
+            pub = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        bl = None if blinders is None else np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        assert bl is None or bl.shape[0] == 2 * self.t + 3 + (1 << self.log_ext) - 2
+        out = np.zeros(circuit_proof_size(self.t, self.log_ext), dtype=np.uint8)
+        e._pq_check(fn(e._h, self._c, _ptr(rows), wires_arg, stride, _ptr(pub) if pub is not None else None,
+                       0 if pub is None else pub.shape[0], _ptr(bl) if bl is not None else None, _ptr(out)))
+        return out.tobytes()
+
+    def prove(self, wires, public_inputs=None, blinders=None, n=None, engine=None):
+        """kzg_circuit_prove: wires a (t, stride, 4) array, public_inputs None or the (n_public, 4) values of rows
+        0 .. n_public - 1, blinders None (a plain proof: NOT zero-knowledge) or the array of blinders() -> the proof bytes
+        (circuit_proof_size of them), every challenge derived from the transcript inside the call"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        return self._prove(e._lib.kzg_circuit_prove, e, _ptr(a), stride, public_inputs, blinders)
+
+    def prove_device(self, d_wires, public_inputs=None, blinders=None, stride=None):
+        """kzg_circuit_prove_device: the wires in a device buffer of the circuit's (single-device) context"""
+        e = self._eng
+        return self._prove(e._lib.kzg_circuit_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
+                           public_inputs, blinders)
+
     def blinders(self):
         """kzg_circuit_blinders: a fresh (2 t + 3 + e - 2, 4) blinder array from the OS CSPRNG"""
         return circuit_blinders(self.t, self.log_ext)
@@ -2060,6 +2124,45 @@ def circuit_verify(key, n, log_ext, shifts, wire_commitments, z_commitment, t_co
                                   _ptr(_scalar_rows(list(abar) + list(sbar) + [zw])), _ptr(alpha.limbs()), _ptr(beta.limbs()),
                                   _ptr(gamma.limbs()), _ptr(zeta.limbs()), _ptr(v.limbs()), _ptr(proof.p1), _ptr(g1), 144, _ptr(g2),
                                   288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def circuit_proof_size(t, log_ext):
+    """kzg_circuit_proof_size: the bytes of a proof of a circuit with t wires, 48 (t + 2^log_ext + 1) + 64 t"""
+    out = C.c_size_t(0)
+    _check(load_library().kzg_circuit_proof_size(t, log_ext, C.byref(out)))
+    return out.value
+
+
+def _proof_statement(key, shifts, public_inputs, proof):
+    t = len(shifts)
+    assert len(key) == 2 * t + 2
+    rows = np.ascontiguousarray(np.stack([c.p1 for c in key]), dtype=np.uint64)
+    pub = list(public_inputs) if public_inputs is not None else []
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    return t, rows, _scalar_rows(shifts), (_scalar_rows(pub) if pub else None), len(pub), buf
+
+
+def circuit_proof_challenges(key, n, log_ext, shifts, public_inputs, proof):
+    """kzg_circuit_proof_challenges: (beta, gamma, alpha, zeta, v) of the hashed transcript from complete proof bytes.  key,
+    shifts and public_inputs as for circuit_verify; nothing is decoded."""
+    t, rows, ks, pub, n_public, buf = _proof_statement(key, shifts, public_inputs, proof)
+    out = np.zeros((5, 4), dtype=np.uint64)
+    _check(load_library().kzg_circuit_proof_challenges(_ptr(rows), n, t, log_ext, _ptr(ks), _ptr(pub) if pub is not None else None,
+                                                       n_public, _ptr(buf), buf.shape[0], _ptr(out)))
+    return tuple(Scalar.from_limbs(out[i]) for i in range(5))
+
+
+def circuit_verify_proof(key, n, log_ext, shifts, public_inputs, proof, setup_g1, setup_g2):
+    """kzg_circuit_verify_proof on the host: decodes the proof bytes, derives the challenges, runs circuit_verify.  False also
+    for bytes that do not decode (points are checked to lie on the curve, not in the subgroup)."""
+    t, rows, ks, pub, n_public, buf = _proof_statement(key, shifts, public_inputs, proof)
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 1 and g2.shape[0] >= 3
+    ok = C.c_int(0)
+    _check(load_library().kzg_circuit_verify_proof(_ptr(rows), n, t, log_ext, _ptr(ks), _ptr(pub) if pub is not None else None, n_public,
+                                                   _ptr(buf), buf.shape[0], _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

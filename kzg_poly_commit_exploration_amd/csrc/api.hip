@@ -282,6 +282,7 @@ struct kzg_ctx {
     size_t n = 0;  // points
     MsmConfig cfg = {};
     DevBuf table;   // W * n affine points
+    bool nttb_ready = false;  // the batched pass kernel's LDS limit is raised (ensure_ntt_batch)
     DevBuf ntt_tw;  // NTT twiddles, built on first use: forward lo, forward hi, inverse lo, inverse hi (ntt_kernels.hip)
     // The Lagrange basis of one domain: L_i = [l_i(s)] G1 for the lag_n = 2^k points of the domain, with
     // its own window-table levels in the SRS table's format (level stride lag_n, the same MsmConfig, lag_n <= n so the slots'
@@ -357,6 +358,7 @@ struct kzg_ctx {
     Workspace<6> lu_ws;
     std::mutex quotient_mu;
     Workspace<13> pq_ws;
+    DevBuf prove_buf[5];  // kzg_circuit_prove's cross-round buffers (values, coefficients, blinded copies, T, blinders): grown, kept
     uint32_t pq_zinv_key = ~0u;  // (log n << 8) | log rot of the inverses of Z_H held in pq_ws, ~0: none
     // the circuits alive on this context (kzg_circuit_create), under quotient_mu: kzg_ctx_destroy frees
     // what the caller left
@@ -3963,6 +3965,14 @@ static int gp_host(kzg_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n,
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
     return rc ? rc : gp_result(ctx, s, out_last, bad_index);
 }
+// the product on a slot the caller holds (ctx->mu held, the device current, the twiddles built when perm is given)
+static int gp_on_slot(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const void* d_a, const void* d_b, size_t n, size_t t,
+                      size_t stride, const GpScalars* perm, uint32_t lg, void* d_out_z, uint64_t out_last[4], size_t* bad_index) {
+    int rc = gp_slot_ready(ctx, s, n, 0, false);
+    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, (const uint32_t*)d_a, (const uint32_t*)d_b, n, t, stride, perm, lg, (uint32_t*)d_out_z);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
+    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+}
 static int gp_device(kzg_ctx* ctx, const void* d_a, const void* d_b, size_t n, size_t t, size_t stride, const GpScalars* perm, uint32_t lg,
                      void* d_out_z, uint64_t out_last[4], size_t* bad_index) {
     const size_t span = ((t - 1) * stride + n) * 32;  // bytes a column set covers
@@ -3978,11 +3988,7 @@ static int gp_device(kzg_ctx* ctx, const void* d_a, const void* d_b, size_t n, s
     const int slot = reserve_slot(ctx, lk, true);
     if (slot < 0) return KZG_ERR_BUSY;
     SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    rc = gp_slot_ready(ctx, s, n, 0, false);
-    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, (const uint32_t*)d_a, (const uint32_t*)d_b, n, t, stride, perm, lg, (uint32_t*)d_out_z);
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
-    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+    return gp_on_slot(ctx, lk, ctx->slots[slot], d_a, d_b, n, t, stride, perm, lg, d_out_z, out_last, bad_index);
 }
 
 int kzg_grand_product(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_z,
@@ -5072,12 +5078,25 @@ int pq_bufs(kzg_ctx* ctx, size_t N, size_t cols, PqBufs* w) {
     return rc;
 }
 
+// A round of kzg_circuit_prove inside one of the circuit calls' bodies: the caller holds quotient_mu, the context's mutex (*lk) and
+// the slot, has raised the batched pass kernel's LDS limit, and keeps the UNBLINDED coefficients of the per-proof columns resident,
+// n each, back to back: [ f_0 .. f_(t-1) | PI (when the call is given public inputs) | z ].  The body then takes no lock and no
+// slot, transforms no column back (it reads `coef`; its wires / z / PI arguments only say what is there) and extends several
+// columns with launch_ntt_batch.
+struct ProveRound {
+    std::unique_lock<std::mutex>* lk = nullptr;
+    int slot = -1;
+    const uint32_t* coef = nullptr;
+    // the opening: v from the 2 t evaluations, once they are known (false: refused)
+    std::function<bool(const uint64_t* evals, uint64_t v[4])> derive_v;
+};
+
 // `cols` columns (column j: len entries at src + 8 j stride words; src null: every entry is *fill) onto the coset of N = 2^lg_N
 // points, column j to dst + 8 j N words.  lg_len >= 0: the entries are values over the domain of 2^lg_len points (inverse
 // transform, twist by g^i / len, padding, forward transform); lg_len < 0: they are coefficients (twist, padding, forward
 // transform).  dst overlaps neither src nor the buffers.
 int pq_extend(kzg_ctx* ctx, hipStream_t st, const uint32_t* src, size_t stride, size_t len, int lg_len, size_t cols, uint32_t lg_N,
-              uint32_t* dst, const PqBufs& w, const Fr30* fill = nullptr) {
+              uint32_t* dst, const PqBufs& w, const Fr30* fill = nullptr, bool batched = false) {
     const size_t N = (size_t)1 << lg_N;
     const Fr30* tw = (const Fr30*)ctx->ntt_tw.p;
     const Fr30* itw = tw + 2 * kNttTableLen;
@@ -5105,7 +5124,9 @@ int pq_extend(kzg_ctx* ctx, hipStream_t st, const uint32_t* src, size_t stride, 
             cstride = len;
         }
         launch_pq_pad_twist(st, coef, cstride, (uint32_t)len, fill ? *fill : one, lg_N, bc, gt, c, w.P);
-        if (lg_N >= kPqDftLog) {
+        if (lg_N >= kPqDftLog && batched && bc > 1) {  // (kzg_circuit_prove: one launch per pass for the chunk's columns)
+            launch_ntt_batch(st, w.P, N, dst + 8 * c0 * N, N, lg_N, (uint32_t)bc, tw, one, w.A, w.B);
+        } else if (lg_N >= kPqDftLog) {
             for (size_t b = 0; b < bc; b++) launch_ntt(st, w.P + 8 * b * N, dst + 8 * (c0 + b) * N, lg_N, tw, one, w.A, w.B);
         } else {
             const uint32_t* ev = launch_fr_dft(st, w.P, w.A, w.B, lg_N, bc, tw);
@@ -5227,7 +5248,137 @@ int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, ui
     }
     return KZG_OK;
 }
+
+// ---- transforms of a batch of columns (ntt_batch_kernels.hip) -------------------------------------------
+// kzg_ntt's argument rules for every column, stride >= n, and extents that fit the address space; *extent: (batch - 1) stride + n
+// values, the bytes / 32 a side of the call spans (0 for an empty batch)
+bool nttb_args_ok(size_t n, size_t batch, size_t in_stride, size_t out_stride, uint32_t* lg, size_t* in_extent, size_t* out_extent) {
+    if (!ntt_log(n, lg) || in_stride < n || out_stride < n) return false;
+    const size_t most = ((size_t)1 << 58) / (batch ? batch : 1);  // batch x stride x 32 bytes stays below 2^63
+    if (in_stride > most || out_stride > most) return false;
+    *in_extent = batch ? (batch - 1) * in_stride + n : 0;
+    *out_extent = batch ? (batch - 1) * out_stride + n : 0;
+    return true;
+}
+// in == out with equal strides is the in-place form; any other overlap of the two sides is refused
+bool nttb_alias_ok(const void* in, size_t in_extent, size_t in_stride, const void* out, size_t out_extent, size_t out_stride) {
+    if (in == out && in_stride == out_stride) return true;
+    return !pq_overlap(in, in_extent * 32, out, out_extent * 32);
+}
+// the twiddles, and the batched pass kernel's LDS limit raised once per context (ctx->mu held, the device current): a refusal
+// fails the batched calls alone, with a message of their own
+int ensure_ntt_batch(kzg_ctx* ctx) {
+    int rc = ensure_ntt(ctx);
+    if (rc || ctx->nttb_ready) return rc;
+    if (!ntt_batch_prepare_device()) {
+        (void)hipGetLastError();
+        ctx->last_error = "ntt batch: the batched pass kernel's LDS limit could not be raised";
+        return KZG_ERR_HIP;
+    }
+    ctx->nttb_ready = true;
+    return KZG_OK;
+}
+// columns per round of a batched transform: pq_bufs's share of the budget per buffer, so that KZG_PQ_WS_KB shrinks it
+size_t nttb_chunk(const kzg_ctx* ctx, size_t n, size_t batch) {
+    size_t chunk = ctx->pq_ws_budget / (4 * n * 32);
+    chunk = chunk < 1 ? 1 : (chunk > kPqMaxChunk ? kPqMaxChunk : chunk);
+    return chunk > batch ? batch : chunk;
+}
+// what a batched transform takes from the workspaces: the two intermediates of launch_ntt_batch when the plan has more than one
+// pass (a single pass writes none), and for host data the staging buffer; `chunk` columns of n values each
+struct NttbBufs {
+    uint32_t *stage = nullptr, *a = nullptr, *b = nullptr;
+    size_t chunk = 0;
+};
+// ctx->mu and quotient_mu held
+int nttb_bufs(kzg_ctx* ctx, size_t n, uint32_t lg, size_t batch, bool staging, NttbBufs* w) {
+    w->chunk = nttb_chunk(ctx, n, batch);
+    void* p = nullptr;
+    int rc = KZG_OK;
+    if (ntt_plan(lg).passes > 1) {
+        rc = ctx->pq_ws.get(ctx, kPqA, w->chunk * n * 32, &p);
+        w->a = (uint32_t*)p;
+        if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqB, w->chunk * n * 32, &p);
+        w->b = (uint32_t*)p;
+    }
+    if (rc == KZG_OK && staging) {
+        rc = ctx->pq_ws.get(ctx, kPqT, w->chunk * n * 32, &p);
+        w->stage = (uint32_t*)p;
+    }
+    return rc;
+}
+// in, out: host pointers (staged through the workspace, a chunk of columns at a time), or device pointers when `device`
+int ntt_batch_impl(kzg_ctx* ctx, const void* in, size_t n, size_t batch, size_t in_stride, void* out, size_t out_stride, bool inverse,
+                   bool device) {
+    uint32_t lg = 0;
+    size_t in_extent = 0, out_extent = 0;
+    if (!nttb_args_ok(n, batch, in_stride, out_stride, &lg, &in_extent, &out_extent) ||
+        !nttb_alias_ok(in, in_extent, in_stride, out, out_extent, out_stride))
+        return KZG_ERR_INVALID_ARG;
+    if (!batch) return KZG_OK;
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_ntt_batch(ctx);
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    rc = ensure_slot_basics(ctx, s);  // needs no SRS
+    if (rc) return rc;
+    NttbBufs w;
+    rc = nttb_bufs(ctx, n, lg, batch, !device, &w);
+    if (rc) return rc;
+    const Fr30* tw = (const Fr30*)ctx->ntt_tw.p + (inverse ? 2 * kNttTableLen : 0);
+    const Fr30 last_c = fr30_arg_from_mont256(inverse ? hf::fr_inv(fr_pow2(lg)) : hf::kFrOne);
+    for (size_t c0 = 0; c0 < batch; c0 += w.chunk) {
+        const size_t bc = batch - c0 < w.chunk ? batch - c0 : w.chunk;
+        if (device) {
+            launch_ntt_batch(s.stream, (const uint32_t*)in + 8 * c0 * in_stride, in_stride, (uint32_t*)out + 8 * c0 * out_stride, out_stride,
+                             lg, (uint32_t)bc, tw, last_c, w.a, w.b);
+            HIP_TRY(ctx, hipGetLastError());
+            continue;
+        }
+        rc = pq_upload(ctx, lk, s.stream, w.stage, (const uint64_t*)in + 4 * c0 * in_stride, n, bc, in_stride);
+        if (rc) return rc;
+        launch_ntt_batch(s.stream, w.stage, n, w.stage, n, lg, (uint32_t)bc, tw, last_c, w.a, w.b);
+        HIP_TRY(ctx, hipGetLastError());
+        for (size_t b = 0; b < bc && rc == KZG_OK; b++)
+            rc = copy_unlocked(ctx, lk, s.stream, (uint64_t*)out + 4 * (c0 + b) * out_stride, w.stage + 8 * b * n, n * 32,
+                               hipMemcpyDeviceToHost, "hipMemcpyAsync (transformed columns)");
+        if (rc) return rc;
+    }
+    return sync_unlocked(ctx, lk, s.stream, "ntt batch");
+}
 }  // namespace
+
+int kzg_ntt_batch(kzg_ctx* ctx, const uint64_t* in, size_t n, size_t batch, size_t in_stride, int inverse, uint64_t* out,
+                  size_t out_stride) {
+    if (!ctx || !in || !out) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_ntt_batch(kid, in, n, batch, in_stride, inverse, out, out_stride));
+    }
+    return ntt_batch_impl(ctx, in, n, batch, in_stride, out, out_stride, inverse != 0, false);
+}
+
+int kzg_ntt_batch_rounds(kzg_ctx* ctx, size_t n, size_t batch, size_t* rounds) {
+    uint32_t lg = 0;
+    if (!ctx || !rounds || !ntt_log(n, &lg)) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) return kzg_ntt_batch_rounds(multi_kid(ctx->multi, 0), n, batch, rounds);
+    const size_t chunk = batch ? nttb_chunk(ctx, n, batch) : 1;  // (the budget is fixed when the context is created)
+    *rounds = (batch + chunk - 1) / chunk;
+    return KZG_OK;
+}
+
+int kzg_ntt_batch_device(kzg_ctx* ctx, const void* d_in, size_t n, size_t batch, size_t in_stride, void* d_out, size_t out_stride,
+                         int inverse) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !d_in || !d_out) return KZG_ERR_INVALID_ARG;
+    return ntt_batch_impl(ctx, d_in, n, batch, in_stride, d_out, out_stride, inverse != 0, true);
+}
 
 // `chunks` vectors of n coefficients (vector c at d_coef + 8 c stride words, stride 0: n; resident until the call returns) committed
 // over the monomial SRS on the caller's reserved slot: batched MSMs, as many vectors per job as the slot holds
@@ -5656,8 +5807,9 @@ int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned
 // when `device`; then out_coeffs is a device pointer and out_p1s null
 static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                                  const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const void* gate, void* out_coeffs,
-                                 uint64_t* out_p1s, bool device) {
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+                                 uint64_t* out_p1s, bool device, const ProveRound* round = nullptr) {
+    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
+    if (!round) lkq.lock();
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -5670,15 +5822,17 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
             return KZG_ERR_INVALID_ARG;
         }
     }
-    std::unique_lock<std::mutex> lk(ctx->mu);
+    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
+    if (!round) own.lock();
+    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
     if (out_p1s) {
         if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
         if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
     }
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    int slot = round ? round->slot : -1;
+    int rc = round ? (int)KZG_OK : pq_begin(ctx, lk, &slot);
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
+    SlotLease lease{ctx, round ? -1 : slot};
     Slot& s = ctx->slots[slot];
     PqDrain drain{s};
     PqBufs w;
@@ -5692,7 +5846,11 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
     if (rc == KZG_OK && gate && !device) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
     if (rc) return rc;
     uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
-    if (device) {
+    if (round) {  // from the resident coefficients [ f | PI | z ]
+        rc = pq_extend(ctx, s.stream, round->coef, n, n, -1, t, sh.lg_N, d_w, w, nullptr, true);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, round->coef + 8 * (ncols - 1) * n, n, n, -1, 1, sh.lg_N, d_z, w);
+        if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, round->coef + 8 * t * n, n, n, -1, 1, sh.lg_N, d_pi, w);
+    } else if (device) {
         rc = pq_extend(ctx, s.stream, (const uint32_t*)wires, stride, n, (int)sh.lg_n, t, sh.lg_N, d_w, w);
         if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)z, n, n, (int)sh.lg_n, 1, sh.lg_N, d_z, w);
         if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, (const uint32_t*)pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
@@ -5887,8 +6045,10 @@ int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n
 // (L_T coefficients) is a device pointer.  out_p1s: host, or null
 static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z,
                                          const void* pi, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
-                                         const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device) {
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+                                         const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device,
+                                         const ProveRound* round = nullptr) {
+    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
+    if (!round) lkq.lock();
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -5905,7 +6065,9 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
             return KZG_ERR_INVALID_ARG;
         }
     }
-    std::unique_lock<std::mutex> lk(ctx->mu);
+    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
+    if (!round) own.lock();
+    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
     auto srs_status = [&]() {
         if (!out_p1s) return (int)KZG_OK;
         if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
@@ -5913,10 +6075,10 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     };
     int rc = srs_status();
     if (rc) return rc;
-    int slot = -1;
-    rc = pq_begin(ctx, lk, &slot);
+    int slot = round ? round->slot : -1;
+    if (!round) rc = pq_begin(ctx, lk, &slot);
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
+    SlotLease lease{ctx, round ? -1 : slot};
     Slot& s = ctx->slots[slot];
     PqDrain drain{s};
     PqBufs w;
@@ -5959,13 +6121,19 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     {  // the wires and z: values -> coefficients -> patch -> the coset, from n + 3 coefficients each
         const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
         const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
-        for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
-        launch_ntt(s.stream, src_z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+        if (round) {  // the resident coefficients [ f | PI | z ], copied under the patches
+            HIP_TRY(ctx, hipMemcpy2DAsync(d_c, clen * 32, round->coef, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_c + 8 * t * clen, round->coef + 8 * (ncols - 1) * n, n * 32, hipMemcpyDeviceToDevice, s.stream));
+        } else {
+            for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            launch_ntt(s.stream, src_z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+        }
         launch_blind_patch(s.stream, d_c, (uint32_t)n, t, clen, d_bl, d_bl, kBlindWireLen, t);
         launch_blind_patch(s.stream, d_c + 8 * t * clen, (uint32_t)n, 1, clen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
         HIP_TRY(ctx, hipGetLastError());
-        rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, t + 1, sh.lg_N, d_w, w);
-        if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, src_pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
+        rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, t + 1, sh.lg_N, d_w, w, nullptr, round != nullptr);
+        if (rc == KZG_OK && pi && round) rc = pq_extend(ctx, s.stream, round->coef + 8 * t * n, n, n, -1, 1, sh.lg_N, d_pi, w);
+        if (rc == KZG_OK && pi && !round) rc = pq_extend(ctx, s.stream, src_pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
         if (rc) return rc;
     }
     {
@@ -6197,8 +6365,9 @@ int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin,
 static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                              const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                              const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
-                             bool device, const uint64_t* blinders = nullptr) {
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+                             bool device, const uint64_t* blinders = nullptr, const ProveRound* round = nullptr) {
+    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
+    if (!round) lkq.lock();
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -6231,7 +6400,9 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         ctx->last_error = "circuit open: " + why;
         return KZG_ERR_INVALID_ARG;
     }
-    std::unique_lock<std::mutex> lk(ctx->mu);
+    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
+    if (!round) own.lock();
+    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
     auto srs_status = [&]() {
         if (!v) return (int)KZG_OK;
         if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
@@ -6239,10 +6410,10 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     };
     int rc = srs_status();
     if (rc) return rc;
-    int slot = -1;
-    rc = pq_begin(ctx, lk, &slot);
+    int slot = round ? round->slot : -1;
+    if (!round) rc = pq_begin(ctx, lk, &slot);
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
+    SlotLease lease{ctx, round ? -1 : slot};
     Slot& s = ctx->slots[slot];
     PqDrain drain{s};
     rc = srs_status();  // (the wait for a slot dropped the mutex: the SRS may have changed)
@@ -6260,8 +6431,9 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (rc == KZG_OK && blinders) rc = s.btab.reserve(ctx, kSetsMaxPoints * kBlindPointBytes + kBlindValueBytes, s.stream);
     if (rc) return rc;
     // 1. coefficients: [ f_0 .. f_(t-1) | PI | z ], one inverse transform each
-    uint32_t *d_f = (uint32_t*)stack, *d_pi = pi ? d_f + 8 * t * n : nullptr, *d_z = d_f + 8 * (ncoef - 1) * n;
-    {
+    uint32_t* d_f = round ? const_cast<uint32_t*>(round->coef) : (uint32_t*)stack;  // (a round's coefficients are only read)
+    uint32_t *d_pi = pi ? d_f + 8 * t * n : nullptr, *d_z = d_f + 8 * (ncoef - 1) * n;
+    if (!round) {
         const uint32_t *src_w = (const uint32_t*)wires, *src_pi = (const uint32_t*)pi, *src_z = (const uint32_t*)z;
         size_t src_stride = stride;
         if (!device) {
@@ -6321,6 +6493,12 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         ys[2 * t] = hf::fr_add(ys[2 * t], hf::fr_mul(cw, Z));
     }
     for (size_t i = 1; i < npoly; i++) std::memcpy(out_evals + 4 * (i - 1), ys[i].l, 32);
+    if (round && round->derive_v) {  // v is fixed after the evaluations: the plan's points, lists and sizes stay, its multipliers follow v
+        uint64_t v_now[4];
+        if (!round->derive_v(out_evals, v_now) || !fr_arg_below_r(v_now, &vf) ||
+            !sets_plan(plan, why, npoly, set_of.data(), set_len, 2, zs, vf.l))
+            return KZG_ERR_INVALID_ARG;
+    }
     LinPoly lin;
     lin_poly(c, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, key, d_z, (const uint32_t*)coef, &lin);
     // 3. the sums.  Point p: G_p = sum_i mult_i P_i over the polynomials of the stack opened there, with m_0 r spread over r's
@@ -8379,6 +8557,387 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     std::memcpy(zs + 4, zeta_w.l, 32);
     return kzg_verify_sets(stack.data(), npoly, set_of.data(), set_len, 2, zs, yl.data(), v, proof_p1, setup_g1, g1_stride_bytes, setup_g2,
                            g2_stride_bytes, valid);
+}
+
+// ---- a circuit's proof as bytes: the hashed transcript and the proof format (host only) -----------------
+//   h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(n_public) | shifts | key commitments | public inputs)
+//   h1 = SHA256(h0 | wire commitments)   beta = fr(SHA256(h1 | 00)), gamma = fr(SHA256(h1 | 01))
+//   h2 = SHA256(h1 | [z])                alpha = fr(SHA256(h2 | 00))
+//   h3 = SHA256(h2 | [T_0] .. [T_(e-2)]) zeta = fr(SHA256(h3 | 00))
+//   h4 = SHA256(h3 | evaluations)        v = fr(SHA256(h4 | 00))
+// scalars as 32 big-endian canonical bytes, points as 48 compressed bytes, fr(d) = d read big-endian mod r.
+namespace {
+constexpr char kProofDst[] = "kzg_mi355x/plonk/v1";  // 19 bytes, hashed without the terminator
+
+void proof_fr_to_be(const hf::Fr& mont, uint8_t out[32]) {
+    uint64_t plain[4];
+    hf::fr_from_mont(mont.l, plain);
+    for (int i = 0; i < 32; i++) out[i] = (uint8_t)(plain[3 - i / 8] >> (8 * (7 - i % 8)));
+}
+// 32 big-endian bytes -> the plain integer's limbs
+hf::Fr proof_be_limbs(const uint8_t in[32]) {
+    hf::Fr v;
+    for (int w = 0; w < 4; w++) {
+        uint64_t x = 0;
+        for (int b = 0; b < 8; b++) x = (x << 8) | in[24 - 8 * w + b];
+        v.l[w] = x;
+    }
+    return v;
+}
+// a canonical scalar of the proof -> blst_fr; false when it is not below r
+bool proof_fr_from_be(const uint8_t in[32], hf::Fr* out) {
+    const hf::Fr v = proof_be_limbs(in);
+    if (hf::fr_geq(v, hf::kFrMod)) return false;
+    *out = hf::fr_mul(v, kFrR2);
+    return true;
+}
+// fr(SHA256(state | tag)): the digest as a big-endian integer, reduced below r (2^256 < 3 r: at most two subtractions)
+hf::Fr proof_challenge(const uint8_t state[32], uint8_t tag) {
+    hf::Sha256 s;
+    uint8_t d[32];
+    hf::sha256_init(s);
+    hf::sha256_update(s, state, 32);
+    hf::sha256_update(s, &tag, 1);
+    hf::sha256_final(s, d);
+    hf::Fr v = proof_be_limbs(d);
+    uint64_t br = 0;
+    while (hf::fr_geq(v, hf::kFrMod)) v = hf::fr_raw_sub(v, hf::kFrMod, br);
+    return hf::fr_mul(v, kFrR2);
+}
+// state <- SHA256(state | data)
+void proof_absorb(uint8_t state[32], const uint8_t* data, size_t len) {
+    hf::Sha256 s;
+    hf::sha256_init(s);
+    hf::sha256_update(s, state, 32);
+    hf::sha256_update(s, data, len);
+    hf::sha256_final(s, state);
+}
+void proof_u64be(uint8_t* out, uint64_t x) {
+    for (int i = 0; i < 8; i++) out[i] = (uint8_t)(x >> (8 * (7 - i)));
+}
+// h0: everything the statement fixes before the prover speaks
+void proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts,
+                     const hf::Fr* pub, size_t n_public) {
+    std::vector<uint8_t> m(19 + 32 + 32 * t + 48 * (2 * t + 2) + 32 * n_public);
+    uint8_t* p = m.data();
+    std::memcpy(p, kProofDst, 19);
+    proof_u64be(p + 19, n);
+    proof_u64be(p + 27, t);
+    proof_u64be(p + 35, log_ext);
+    proof_u64be(p + 43, n_public);
+    p += 51;
+    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
+    for (size_t j = 0; j < 2 * t + 2; j++, p += 48) {
+        hf::P1 c;
+        std::memcpy(&c, key_p1s + 18 * j, sizeof c);
+        hf::p1_compress(p, c);
+    }
+    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
+    hf::Sha256 s;
+    hf::sha256_init(s);
+    hf::sha256_update(s, m.data(), m.size());
+    hf::sha256_final(s, state);
+}
+// the offsets of the proof's five fields: wires, [z], chunks, evaluations, W, and its length
+struct ProofLayout {
+    size_t wires, z, chunks, evals, w, len;
+};
+ProofLayout proof_layout(size_t t, size_t e) {
+    ProofLayout L;
+    L.wires = 0;
+    L.z = 48 * t;
+    L.chunks = L.z + 48;
+    L.evals = L.chunks + 48 * (e - 1);
+    L.w = L.evals + 64 * t;
+    L.len = L.w + 48;
+    return L;
+}
+bool proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t n_public) {
+    PqShape sh;
+    return log_ext <= kPqMaxLogExt && pq_shape(n, (size_t)1 << log_ext, &sh) && t >= KZG_CIRCUIT_MIN_COLUMNS && t <= kPqMaxColumns &&
+           t + 1 <= sh.rot && n_public <= n;
+}
+// the five challenges from complete proof bytes, out: beta, gamma, alpha, zeta, v
+void proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts, const hf::Fr* pub, size_t n_public,
+                      const uint8_t* proof, hf::Fr out[5]) {
+    const ProofLayout L = proof_layout(t, (size_t)1 << log_ext);
+    uint8_t h[32];
+    proof_statement(h, key_p1s, n, t, log_ext, shifts, pub, n_public);
+    proof_absorb(h, proof + L.wires, L.z - L.wires);
+    out[0] = proof_challenge(h, 0);
+    out[1] = proof_challenge(h, 1);
+    proof_absorb(h, proof + L.z, 48);
+    out[2] = proof_challenge(h, 0);
+    proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
+    out[3] = proof_challenge(h, 0);
+    proof_absorb(h, proof + L.evals, L.w - L.evals);
+    out[4] = proof_challenge(h, 0);
+}
+// the shifts and the public inputs as field elements; false when one is not below r
+bool proof_scalars(const uint64_t* shifts, size_t t, const uint64_t* public_inputs, size_t n_public, std::vector<hf::Fr>* ks,
+                   std::vector<hf::Fr>* pub) {
+    ks->resize(t);
+    pub->resize(n_public);
+    for (size_t j = 0; j < t; j++)
+        if (!fr_arg_below_r(shifts + 4 * j, &(*ks)[j])) return false;
+    for (size_t i = 0; i < n_public; i++)
+        if (!fr_arg_below_r(public_inputs + 4 * i, &(*pub)[i])) return false;
+    return true;
+}
+}  // namespace
+
+int kzg_circuit_proof_size(size_t t, unsigned log_ext, size_t* bytes) {
+    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext))
+        return KZG_ERR_INVALID_ARG;
+    *bytes = proof_layout(t, (size_t)1 << log_ext).len;
+    return KZG_OK;
+}
+
+int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                                 const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, uint64_t* out) {
+    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
+    if (!proof_shape_ok(n, t, log_ext, n_public) || proof_len != proof_layout(t, (size_t)1 << log_ext).len) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    hf::Fr ch[5];
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch);
+    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
+    return KZG_OK;
+}
+
+int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                             size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
+    const size_t e = (size_t)1 << log_ext;
+    const ProofLayout L = proof_layout(t, e);
+    if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    for (size_t j = 0; j < 2 * t + 2; j++) {  // kzg_circuit_verify's check of the key, before the proof is looked at
+        hf::P1 c;
+        std::memcpy(&c, key_p1s + 18 * j, sizeof c);
+        if (!hf::p1_on_curve(c)) return KZG_ERR_INVALID_ARG;
+    }
+    // decode: t + e + 1 points (on the curve; no subgroup check) and 2 t canonical scalars; a proof that does not decode is invalid
+    std::vector<uint64_t> pts(18 * (t + e)), evals(4 * 2 * t);
+    uint64_t w_p1[18];
+    bool decoded = true;
+    for (size_t i = 0; i < t + e && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
+    decoded = decoded && kzg_g1_uncompress(proof + L.w, w_p1) == KZG_OK;
+    for (size_t i = 0; i < 2 * t && decoded; i++) {
+        hf::Fr v = kFrZero;
+        decoded = proof_fr_from_be(proof + L.evals + 32 * i, &v);
+        std::memcpy(evals.data() + 4 * i, v.l, 32);
+    }
+    if (!decoded) {
+        *valid = 0;
+        return KZG_OK;
+    }
+    hf::Fr ch[5];
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch);
+    return kzg_circuit_verify(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * t, pts.data() + 18 * (t + 1), public_inputs,
+                              n_public, evals.data(), ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2,
+                              g2_stride_bytes, valid);
+}
+
+// ---- a circuit's proof in one call ----------------------------------------------------------------------
+// The five rounds under the transcript above, on one slot, quotient_mu held from start to end.  What lives across rounds sits in
+// buffers the context keeps for this call alone (ctx->prove_buf, under quotient_mu; the pq_ws workspaces belong to the rounds, which
+// may regrow them), sized for the whole proof at the start: V, the values [ wires | PI | z ];
+// U, their unblinded coefficients in the same order -- every column is transformed back once, here, with launch_ntt_batch, and the
+// quotient's and the opening's bodies read U (ProveRound); the blinded copies that are committed; T's coefficients.
+namespace {
+int prove_refused(kzg_ctx* ctx, const char* why) {
+    ctx->last_error = std::string("circuit prove: ") + why;
+    return KZG_ERR_INVALID_ARG;
+}
+// wires: t columns of n values, host (stride in values) or device when `device`
+int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
+                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device) {
+    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    PqShape sh;
+    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, t = c->t, e = sh.rot, ncoef = t + 1 + (n_public ? 1 : 0);
+    std::vector<hf::Fr> ks(t), pub(n_public), bl;
+    for (size_t j = 0; j < t; j++) std::memcpy(ks[j].l, c->shifts + 4 * j, 32);
+    for (size_t i = 0; i < n_public; i++)
+        if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
+    if (blinders) {
+        if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit prove (blinded)");
+        if (!blind_values_ok(ctx, "circuit prove (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+    }
+    const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
+    const size_t wlen = blinders ? n + kBlindWireLen : n, zlen = blinders ? n + kBlindZLen : n;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    auto srs_status = [&]() {
+        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
+        return need > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
+    };
+    int rc = srs_status();
+    if (rc) return rc;
+    int slot = -1;
+    rc = pq_begin(ctx, lk, &slot);
+    if (rc) return rc;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    PqDrain drain{s};
+    rc = srs_status();  // (the wait for a slot dropped the mutex)
+    if (rc == KZG_OK) rc = ensure_ntt_batch(ctx);
+    if (rc) return rc;
+    // every cross-round buffer at its size for the whole proof, before anything is enqueued (the stream is empty: PqDrain)
+    DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &S = ctx->prove_buf[2], &T = ctx->prove_buf[3], &B = ctx->prove_buf[4];
+    rc = V.reserve(ctx, ncoef * n * 32, s.stream);
+    if (rc == KZG_OK) rc = U.reserve(ctx, ncoef * n * 32, s.stream);
+    if (rc == KZG_OK) rc = T.reserve(ctx, t_len * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = S.reserve(ctx, (t * wlen + zlen) * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = B.reserve(ctx, (2 * t + kBlindZLen) * 32, s.stream);
+    if (rc) return rc;
+    uint32_t *d_v = V.dev(), *d_u = U.dev(), *d_s = S.dev(), *d_bl = B.dev();
+    uint32_t *d_vz = d_v + 8 * (ncoef - 1) * n, *d_uz = d_u + 8 * (ncoef - 1) * n;
+    const ProveRound round_base{&lk, slot, d_u, nullptr};
+    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
+    // `cols` columns of V -> U, one launch per pass for as many columns as the transform buffers hold
+    auto to_coefficients = [&](size_t first, size_t cols) -> int {
+        PqBufs w;
+        int r = pq_bufs(ctx, n, cols, &w);
+        if (r) return r;
+        for (size_t c0 = 0; c0 < cols; c0 += w.chunk) {
+            const size_t bc = cols - c0 < w.chunk ? cols - c0 : w.chunk;
+            launch_ntt_batch(s.stream, d_v + 8 * (first + c0) * n, n, d_u + 8 * (first + c0) * n, n, sh.lg_n, (uint32_t)bc, itw, inv_n, w.A, w.B);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        return KZG_OK;
+    };
+    const size_t np1 = t + e;  // the proof's points before the evaluations: wires, [z], chunks
+    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * 2 * t);
+    const ProofLayout L = proof_layout(t, e);
+    std::vector<uint8_t> proof(L.len);
+    auto put_points = [&](size_t first, size_t count) {
+        for (size_t i = first; i < first + count; i++) {
+            hf::P1 pt;
+            std::memcpy(&pt, p1s.data() + 18 * i, sizeof pt);
+            hf::p1_compress(proof.data() + 48 * i, pt);
+        }
+    };
+    uint8_t h[32];
+    proof_statement(h, key_p1s, n, t, c->lg_ext, ks.data(), pub.data(), n_public);
+
+    // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; beta, gamma
+    if (device) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_v, n * 32, wires, stride * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
+    } else {
+        rc = pq_upload(ctx, lk, s.stream, d_v, (const uint64_t*)wires, n, t, stride);
+        if (rc) return rc;
+    }
+    if (n_public) {
+        HIP_TRY(ctx, hipMemsetAsync(d_v + 8 * t * n, 0, n * 32, s.stream));
+        rc = copy_unlocked(ctx, lk, s.stream, d_v + 8 * t * n, public_inputs, n_public * 32, hipMemcpyHostToDevice,
+                           "hipMemcpyAsync (public inputs)");
+        if (rc) return rc;
+    }
+    if (blinders) {
+        rc = copy_unlocked(ctx, lk, s.stream, d_bl, blinders, (2 * t + kBlindZLen) * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+        if (rc) return rc;
+    }
+    rc = to_coefficients(0, ncoef - 1);
+    if (rc) return rc;
+    if (blinders) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_s, wlen * 32, d_u, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
+        launch_blind_patch(s.stream, d_s, (uint32_t)n, t, wlen, d_bl, d_bl, kBlindWireLen, t);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    rc = sync_unlocked(ctx, lk, s.stream, "circuit prove (wires)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_s : d_u, wlen, t, p1s.data());
+    if (rc) return rc;
+    put_points(0, t);
+    proof_absorb(h, proof.data() + L.wires, L.z - L.wires);
+    const hf::Fr beta = proof_challenge(h, 0), gamma = proof_challenge(h, 1);
+
+    // round 2: z on the device from the wires and the key's sigma values; z_n = 1; its commitment; alpha
+    {
+        const GpScalars perm{c->shifts, beta.l, gamma.l};
+        uint64_t last[4];
+        size_t bad = 0;
+        rc = gp_on_slot(ctx, lk, s, d_v, c->values.dev() + 8 * (t + 2) * n, n, t, n, &perm, sh.lg_n, d_vz, last, &bad);
+        if (rc) return rc;
+        if (std::memcmp(last, hf::kFrOne.l, 32) != 0) {
+            ctx->last_error = "circuit prove: the grand product does not return to one (z_n != 1): the copy constraints do not hold";
+            return KZG_ERR_REMAINDER;
+        }
+    }
+    rc = to_coefficients(ncoef - 1, 1);
+    if (rc) return rc;
+    uint32_t* d_sz = blinders ? d_s + 8 * t * wlen : nullptr;
+    if (blinders) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_sz, d_uz, n * 32, hipMemcpyDeviceToDevice, s.stream));
+        launch_blind_patch(s.stream, d_sz, (uint32_t)n, 1, zlen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    rc = sync_unlocked(ctx, lk, s.stream, "circuit prove (z)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sz : d_uz, zlen, 1, p1s.data() + 18 * t);
+    if (rc) return rc;
+    put_points(t, 1);
+    proof_absorb(h, proof.data() + L.z, 48);
+    const hf::Fr alpha = proof_challenge(h, 0);
+
+    // round 3: the quotient from the resident coefficients, its chunks' commitments; zeta
+    const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
+    rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p,
+                                                  p1s.data() + 18 * (t + 1), true, &round_base)
+                  : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 1), true,
+                                          &round_base);
+    if (rc) return rc;
+    put_points(t + 1, e - 1);
+    proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
+    const hf::Fr zeta = proof_challenge(h, 0);
+
+    // rounds 4 and 5: the evaluations, v from them, r(zeta) = 0, the opening
+    ProveRound last_round = round_base;
+    last_round.derive_v = [&](const uint64_t* ev, uint64_t v[4]) {
+        for (size_t i = 0; i < 2 * t; i++) {
+            hf::Fr y;
+            std::memcpy(y.l, ev + 4 * i, 32);
+            proof_fr_to_be(y, proof.data() + L.evals + 32 * i);
+        }
+        proof_absorb(h, proof.data() + L.evals, L.w - L.evals);
+        const hf::Fr vf = proof_challenge(h, 0);
+        std::memcpy(v, vf.l, 32);
+        return true;
+    };
+    rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
+                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round);
+    if (rc) return rc;
+    hf::P1 w;
+    std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
+    hf::p1_compress(proof.data() + L.w, w);
+    std::memcpy(out_proof, proof.data(), L.len);
+    return KZG_OK;
+}
+}  // namespace
+
+int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                      const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        if (multi_mode(ctx->multi) != kMultiReplicate) {
+            ctx->last_error = "the proof's commitments need the whole SRS on one device: not on a range-split multi-device context";
+            return KZG_ERR_INVALID_ARG;
+        }
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
+    }
+    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false);
+}
+
+int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

@@ -192,6 +192,16 @@ bool ntt_prepare_device();
 void launch_ntt(hipStream_t s, const uint32_t* d_in, uint32_t* d_out, uint32_t log_n, const void* d_tw, const Fr30& last_c,
                 uint32_t* d_buf_a, uint32_t* d_buf_b);
 
+// ---- ntt_batch_kernels.hip: the same transform over `batch` columns, one launch per pass of ntt_plan for the whole batch ----
+// raises the dynamic-LDS limit of the batched pass kernel on the current device; false when refused
+bool ntt_batch_prepare_device();
+// Column b is read at d_in + 8 b in_stride words and written at d_out + 8 b out_stride words (strides in values, >= 2^log_n);
+// the intermediates use stride 2^log_n: d_buf_a and d_buf_b hold batch * 2^log_n values each when there is more than one pass
+// (pass i < passes - 1 writes d_buf_a for even i, d_buf_b for odd i).  d_tw, last_c: as for launch_ntt.  d_in == d_out with equal
+// strides is allowed (no intermediate is either of them); batch <= 65535 (a grid dimension), batch == 0 launches nothing.
+void launch_ntt_batch(hipStream_t s, const uint32_t* d_in, uint64_t in_stride, uint32_t* d_out, uint64_t out_stride, uint32_t log_n,
+                      uint32_t batch, const void* d_tw, const Fr30& last_c, uint32_t* d_buf_a, uint32_t* d_buf_b);
+
 // ---- cell_kernels.hip: quotients of P by X^l - w_N^(j l) for the cells j of a domain of N = 2^log_n points, l = 2^log_l ----
 // cells [first_cell, first_cell + cells): q of cell first_cell + p at d_q + 8 p stride words, nq values each (nq = n' - l,
 // d_coeffs holds at least nq + l coefficients); d_tw: the context's forward NTT twiddles; d_agg: cells_agg_words() words

@@ -5014,24 +5014,34 @@ static int forwarded(kzg_ctx* ctx, kzg_ctx* kid, int rc) {
     if (rc) ctx->last_error = kid->last_error;
     return rc;
 }
+// The device a prover call on a multi-device context is forwarded to.  Without commitments (`wanted` false) the call needs no SRS;
+// with them it follows kzg_commit_lagrange: a replicated context forwards, a range-split one holds no whole SRS on one device and
+// refuses (null: KZG_ERR_INVALID_ARG, the message begins with `what_needs`)
+static kzg_ctx* whole_srs_kid(kzg_ctx* ctx, bool wanted, const char* what_needs) {
+    if (wanted && multi_mode(ctx->multi) != kMultiReplicate) {
+        ctx->last_error = std::string(what_needs) + " the whole SRS on one device: not on a range-split multi-device context";
+        return nullptr;
+    }
+    return multi_kid(ctx->multi, 0);
+}
 
 // ---- the quotient of a permutation argument on the coset g H_N (quotient_kernels.hip) ---------------------
-// Every call holds quotient_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits.
+// Every call holds quotient_mu, then the context's mutex and one slot for its stream, dropping the mutex while it copies or waits
+// (PqCall, below).
 namespace {
 enum : int { kPqIn = 0, kPqCols, kPqT, kPqP, kPqA, kPqB, kPqOut, kPqCoef, kPqGate, kPqZinv, kPqFlag, kPqBlind, kPqChunks, kPqCount };
 constexpr size_t kPqMaxChunk = 64;                 // the transform buffers of one pass (ctx->pq_ws_budget) hold at most this many columns
 constexpr uint32_t kPqDftLog = kNttTileLog;        // below 2^11 values a batch takes launch_fr_dft, from there on launch_ntt per column
 static_assert(kPqCount <= 13, "pq_ws");
 
-// Declared after the slot's lease, so that it runs first: whatever way a call returns -- also after a failed copy or launch --
-// nothing it enqueued still uses pq_ws when the slot and quotient_mu are given up (a later call may grow, that is free, a
-// workspace).  After a call that ended well the stream is empty and this costs nothing.
+// waits for what a call left on its slot's streams (no slot yet: nothing)
 struct PqDrain {
-    const Slot& s;  // the front stream, and the stream a commitment of the chunks ended on
-    ~PqDrain() {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        if (s.end && s.end != s.stream) (void)hipStreamSynchronize(s.end);
+    const Slot* s = nullptr;  // the front stream, and the stream a commitment of the chunks ended on
+    void now() const {
+        if (s && s->stream) (void)hipStreamSynchronize(s->stream);
+        if (s && s->end && s->end != s->stream) (void)hipStreamSynchronize(s->end);
     }
+    ~PqDrain() { now(); }
 };
 
 struct PqShape {
@@ -5165,6 +5175,23 @@ int pq_upload_zinv(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t s
 struct PqChallenges {
     const uint64_t *shifts, *alpha, *beta, *gamma;
 };
+// The challenges as the constraint kernels take them (engine.h, PqScalars), for t columns: beta, alpha 2^(14 t) and alpha^2 2^14
+// in multiplier form; gamma, one and beta k_j g as the digits of their images; k14 = 2^14 in multiplier form (the circuit kernel).
+// The kernels' bound comments and test_fr_extremes* rest on these magnitudes: they are made here and nowhere else.
+struct PqKernelScalars {
+    Fr30 beta, gamma, one, a1, a2, k14, bkg[kPqMaxColumns];
+    PqKernelScalars(const PqChallenges& ch, size_t t) {
+        const hf::Fr a = pq_fr(ch.alpha), b = pq_fr(ch.beta), g = fr_seven();
+        beta = fr30_arg_from_mont256(b);
+        gamma = pq_image(pq_fr(ch.gamma));
+        one = pq_image(hf::kFrOne);
+        a1 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2((uint32_t)(14 * t))));
+        a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), fr_pow2(14)));
+        k14 = fr30_arg_from_mont256(fr_pow2(14));
+        for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(b, pq_fr(ch.shifts + 4 * j)), g));
+    }
+    PqScalars view() const { return PqScalars{&beta, &gamma, &one, &a1, &a2, bkg}; }
+};
 // Num / Z_H on the coset into d_out (N values): the extended columns at d_wires / d_sigmas (column j at + 8 j stride words), d_z,
 // d_gate (or null); the values of L_0 are made in d_l0 here
 int pq_constraints(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, size_t t, size_t stride,
@@ -5177,15 +5204,23 @@ int pq_constraints(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t s
     const Fr30 inv_n = pq_image(hf::fr_inv(fr_pow2(sh.lg_n)));
     rc = pq_extend(ctx, st, nullptr, 0, sh.n, -1, 1, sh.lg_N, d_l0, w, &inv_n);
     if (rc) return rc;
-    const hf::Fr alpha = pq_fr(ch.alpha), beta = pq_fr(ch.beta), gamma = pq_fr(ch.gamma), g = fr_seven();
-    const Fr30 f_beta = fr30_arg_from_mont256(beta), f_gamma = pq_image(gamma), f_one = pq_image(hf::kFrOne);
-    const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(alpha, fr_pow2((uint32_t)(14 * t))));
-    const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(alpha, alpha), fr_pow2(14)));
-    Fr30 bkg[kPqMaxColumns];
-    for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(beta, pq_fr(ch.shifts + 4 * j)), g));
+    const PqKernelScalars sc(ch, t);
     const PqColumns cols{d_wires, d_sigmas, d_z, d_l0, d_gate, d_zinv};
-    const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
-    launch_pq_constraints(st, cols, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, stride, sc, ctx->ntt_tw.p, d_out);
+    launch_pq_constraints(st, cols, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, stride, sc.view(), ctx->ntt_tw.p, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+// Num / Z_H of a circuit on the coset into d_out (N values), the arithmetic gate built in: the call's extended wires (column j at
+// d_w + 8 j N words), z, PI (or null) and gate (or null), and the key's columns where kzg_circuit_create laid them in c->coset:
+// q_lin first, q_M at + t N, q_C at + (t + 1) N, the sigmas at + (t + 2) N
+int ck_constraints(kzg_ctx* ctx, hipStream_t st, const kzg_circuit* c, const PqShape& sh, const uint32_t* d_w, const uint32_t* d_z,
+                   const uint32_t* d_pi, const uint32_t* d_gate, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                   uint32_t* d_out) {
+    const size_t t = c->t, N = sh.N;
+    const PqKernelScalars sc(PqChallenges{c->shifts, alpha, beta, gamma}, t);
+    const uint32_t* key = c->coset.dev();
+    const CkColumns ck{d_w, key, key + 8 * (t + 2) * N, key + 8 * t * N, key + 8 * (t + 1) * N, d_z, c->l0.dev(), d_pi, d_gate, c->zinv.dev()};
+    launch_ck_constraints(st, ck, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, N, sc.view(), sc.k14, ctx->ntt_tw.p, d_out);
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
@@ -5222,21 +5257,84 @@ int pq_remainder(kzg_ctx* ctx, const PqShape& sh) {
     return KZG_ERR_REMAINDER;
 }
 
-// what every call starts with (quotient_mu held by the caller, lk = ctx->mu held): the tables, a reserved slot with its stream
-int pq_begin(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int* slot) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_ntt(ctx);
-    if (rc == KZG_OK) rc = ensure_recover_g(ctx);
-    if (rc) return rc;
-    *slot = reserve_slot(ctx, lk, true);
-    if (*slot < 0) return KZG_ERR_BUSY;
-    rc = ensure_slot_basics(ctx, ctx->slots[*slot]);  // needs no SRS
-    if (rc) {
-        release_owned(ctx, *slot);
-        *slot = -1;
-    }
+// The end of a quotient: the N values in d_vals -> coefficients in d_coef (pq_interpolate), `out_len` of them to host_out where
+// that is not null, the wait under the call's name.  *remainder: the flag -- the caller words its own refusal
+int pq_finish(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, const PqShape& sh, uint32_t* d_vals, bool divide,
+              const PqBufs& w, uint32_t* d_coef, uint32_t* d_flag, size_t keep, size_t out_len, void* host_out, const char* what,
+              bool* remainder) {
+    int rc = pq_interpolate(ctx, lk, st, sh, d_vals, divide, w, d_coef, d_flag, keep);
+    uint32_t hflag = 0;
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, st, &hflag, d_flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
+    if (rc == KZG_OK && host_out)
+        rc = copy_unlocked(ctx, lk, st, host_out, d_coef, out_len * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, st, what);
+    *remainder = hflag != 0;
     return rc;
 }
+
+// the SRS a call's commitments of `need_len` coefficients need (ctx->mu held); none where no commitment is wanted
+int pq_srs_status(const kzg_ctx* ctx, bool wanted, size_t need_len) {
+    if (!wanted) return KZG_OK;
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    return need_len > ctx->n ? KZG_ERR_DEGREE_TOO_HIGH : KZG_OK;
+}
+
+int ensure_ntt_batch(kzg_ctx* ctx);
+// What a call of this family holds, and the order it gives it back in.  An owning frame takes quotient_mu when it is made, the
+// context's mutex in lock() and the tables and a reserved slot with its stream in begin(): three steps, because the bodies check
+// their arguments and the SRS between them.  An adopted frame (a round of kzg_circuit_prove, whose caller holds all three) takes
+// nothing and gives nothing back.
+// The members go last to first, and that IS the order of release.  First the streams are drained, by either kind of frame:
+// whatever way a call returns -- also after a failed copy or launch -- nothing it enqueued still uses pq_ws when the slot and
+// quotient_mu are given up (a later call may grow, that is free, a workspace); after a call that ended well the stream is empty and
+// this costs nothing.  Then the slot goes back, under the context's mutex; then that mutex; quotient_mu last.
+class PqCall {
+public:
+    explicit PqCall(kzg_ctx* ctx, const ProveRound* round = nullptr)
+        : ctx_(ctx), lkq_(ctx->quotient_mu, std::defer_lock), own_(ctx->mu, std::defer_lock), lk_(round ? round->lk : &own_),
+          lease_{ctx, -1} {
+        if (round) {
+            slot_ = round->slot;
+            drain_.s = &ctx->slots[slot_];
+        } else {
+            lkq_.lock();
+        }
+    }
+    void lock() {
+        if (lk_ == &own_) own_.lock();
+    }
+    // batch_only: kzg_ntt_batch, which reads the twiddles alone (with the batched kernel's LDS limit) and not the g-power tables
+    int begin(bool batch_only = false) {
+        if (lk_ != &own_) return KZG_OK;
+        HIP_TRY(ctx_, hipSetDevice(ctx_->device));
+        int rc = batch_only ? ensure_ntt_batch(ctx_) : ensure_ntt(ctx_);
+        if (rc == KZG_OK && !batch_only) rc = ensure_recover_g(ctx_);
+        if (rc) return rc;
+        slot_ = reserve_slot(ctx_, own_, true);
+        if (slot_ < 0) return KZG_ERR_BUSY;
+        lease_.slot = slot_;
+        drain_.s = &ctx_->slots[slot_];
+        return ensure_slot_basics(ctx_, ctx_->slots[slot_]);  // needs no SRS
+    }
+    std::unique_lock<std::mutex>& lk() const { return *lk_; }
+    int slot() const { return slot_; }
+    Slot& s() const { return ctx_->slots[slot_]; }
+    void drain() const { drain_.now(); }  // before the end, for a caller that frees what the call wrote to
+    ~PqCall() {
+        static_assert(offsetof(PqCall, lkq_) < offsetof(PqCall, own_) && offsetof(PqCall, own_) < offsetof(PqCall, lease_) &&
+                          offsetof(PqCall, lease_) < offsetof(PqCall, drain_),
+                      "the order of release");
+    }
+
+private:
+    kzg_ctx* ctx_;
+    int slot_ = -1;
+    std::unique_lock<std::mutex> lkq_, own_;  // quotient_mu, ctx->mu
+    std::unique_lock<std::mutex>* lk_;        // own_, or the round's
+    SlotLease lease_;                         // (no slot: gives nothing back)
+    PqDrain drain_;
+};
+
 // t columns of len values, column j at src + 4 j stride, packed to stride len at dst
 int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, uint32_t* dst, const uint64_t* src, size_t len, size_t t,
               size_t stride) {
@@ -5247,6 +5345,25 @@ int pq_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, ui
         if (rc) return rc;
     }
     return KZG_OK;
+}
+// The per-proof columns of a circuit call (t wires at `stride`, z, and PI or null: n values each) where the body reads them.
+// Device inputs stay where they are.  Host inputs are packed into d_in, uploaded in the order they lie there: the wires, then
+// [ z | PI ] (the quotients: the order of their extended columns) or, z_last, [ PI | z ] (the opening: the order of its stack)
+struct PqStaged {
+    const uint32_t *w, *z, *pi;
+    size_t stride;
+};
+int pq_stage(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, hipStream_t st, bool device, uint32_t* d_in, const void* wires,
+             size_t stride, const void* z, const void* pi, size_t n, size_t t, bool z_last, PqStaged* out) {
+    *out = PqStaged{(const uint32_t*)wires, (const uint32_t*)z, (const uint32_t*)pi, stride};
+    if (device) return KZG_OK;
+    uint32_t *d_z = d_in + 8 * (t + (z_last && pi ? 1 : 0)) * n, *d_pi = d_in + 8 * (t + (z_last ? 0 : 1)) * n;
+    int rc = pq_upload(ctx, lk, st, d_in, (const uint64_t*)wires, n, t, stride);
+    if (rc == KZG_OK && pi && z_last) rc = pq_upload(ctx, lk, st, d_pi, (const uint64_t*)pi, n, 1, n);
+    if (rc == KZG_OK) rc = pq_upload(ctx, lk, st, d_z, (const uint64_t*)z, n, 1, n);
+    if (rc == KZG_OK && pi && !z_last) rc = pq_upload(ctx, lk, st, d_pi, (const uint64_t*)pi, n, 1, n);
+    *out = PqStaged{d_in, d_z, pi ? d_pi : nullptr, n};
+    return rc;
 }
 
 // ---- transforms of a batch of columns (ntt_batch_kernels.hip) -------------------------------------------
@@ -5316,18 +5433,12 @@ int ntt_batch_impl(kzg_ctx* ctx, const void* in, size_t n, size_t batch, size_t 
         !nttb_alias_ok(in, in_extent, in_stride, out, out_extent, out_stride))
         return KZG_ERR_INVALID_ARG;
     if (!batch) return KZG_OK;
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_ntt_batch(ctx);
+    PqCall call(ctx);
+    call.lock();
+    int rc = call.begin(true);
     if (rc) return rc;
-    const int slot = reserve_slot(ctx, lk, true);
-    if (slot < 0) return KZG_ERR_BUSY;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
-    rc = ensure_slot_basics(ctx, s);  // needs no SRS
-    if (rc) return rc;
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     NttbBufs w;
     rc = nttb_bufs(ctx, n, lg, batch, !device, &w);
     if (rc) return rc;
@@ -5385,8 +5496,7 @@ int kzg_ntt_batch_device(kzg_ctx* ctx, const void* d_in, size_t n, size_t batch,
 static int pq_commit_chunks(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot, const uint32_t* d_coef, size_t n, size_t chunks,
                             uint64_t* out_p1s, size_t stride = 0) {
     if (!stride) stride = n;
-    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;  // (the wait for a slot dropped the mutex: the SRS may have changed)
-    if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
+    if (int rc = pq_srs_status(ctx, true, n)) return rc;  // (the wait for a slot dropped the mutex: the SRS may have changed)
     Slot& s = ctx->slots[slot];
     const size_t group = std::min<size_t>(chunks, ctx->max_batch ? ctx->max_batch : 1);
     for (size_t c0 = 0; c0 < chunks; c0 += group) {
@@ -5413,14 +5523,12 @@ static int coset_extend_impl(kzg_ctx* ctx, const void* in, size_t len, size_t ba
         ctx->last_error = "coset extension: the output overlaps the input";
         return KZG_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    PqCall call(ctx);
+    call.lock();
+    int rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     const int lg = form == KZG_EXTEND_VALUES ? (int)lg_len : -1;
     if (device) {
         PqBufs w;
@@ -5481,14 +5589,12 @@ int kzg_permutation_constraints_coset(kzg_ctx* ctx, const uint64_t* wires_ext, c
         return forwarded(ctx, kid, kzg_permutation_constraints_coset(kid, wires_ext, sigmas_ext, z_ext, n, rot, t, stride, shifts, alpha,
                                                                     beta, gamma, gate_coset, out));
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    PqCall call(ctx);
+    call.lock();
+    int rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     const size_t N = sh.N;
     PqBufs w;
     void *cols, *d_out, *d_gate = nullptr;
@@ -5522,14 +5628,12 @@ int kzg_permutation_constraints_coset_device(kzg_ctx* ctx, const void* d_wires_e
         ctx->last_error = "permutation constraints: the output overlaps an input";
         return KZG_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    PqCall call(ctx);
+    call.lock();
+    int rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void* d_l0;
     rc = pq_bufs(ctx, N, 1, &w);
@@ -5548,14 +5652,12 @@ static int vanishing_quotient_impl(kzg_ctx* ctx, const void* num, size_t N, size
         ctx->last_error = "vanishing quotient: the output overlaps the input";
         return KZG_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    PqCall call(ctx);
+    call.lock();
+    int rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void *vals, *coef = out, *flag;
     rc = pq_bufs(ctx, N, 1, &w);
@@ -5566,14 +5668,12 @@ static int vanishing_quotient_impl(kzg_ctx* ctx, const void* num, size_t N, size
     // the values go into the workspace, where the division may change them
     rc = copy_unlocked(ctx, lk, s.stream, vals, num, N * 32, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                        "hipMemcpyAsync (numerator)");
-    if (rc == KZG_OK) rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)vals, !already_divided, w, (uint32_t*)coef, (uint32_t*)flag);
-    uint32_t hflag = 0;
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
-    if (rc == KZG_OK && !device)
-        rc = copy_unlocked(ctx, lk, s.stream, out, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "vanishing quotient");
+    bool remainder = false;
+    if (rc == KZG_OK)
+        rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)vals, !already_divided, w, (uint32_t*)coef, (uint32_t*)flag, 0, N - n,
+                       device ? nullptr : out, "vanishing quotient", &remainder);
     if (rc) return rc;
-    return hflag ? pq_remainder(ctx, sh) : KZG_OK;
+    return remainder ? pq_remainder(ctx, sh) : KZG_OK;
 }
 
 int kzg_vanishing_quotient(kzg_ctx* ctx, const uint64_t* num_coset, size_t N, size_t n, int already_divided, uint64_t* out_coeffs) {
@@ -5598,28 +5698,18 @@ int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t
         !sigmas || !z || !shifts || !alpha || !beta || !gamma)
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        // without commitments the call needs no SRS; with them it follows kzg_commit_lagrange: a replicated context forwards,
-        // a range-split one holds no whole SRS on one device
-        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_permutation_quotient(kid, wires, sigmas, z, n, t, stride, shifts, alpha, beta, gamma, gate_coset,
                                                            log_ext, out_coeffs, out_p1s));
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    if (out_p1s) {
-        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
-        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
-    }
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    PqCall call(ctx);
+    call.lock();
+    int rc = pq_srs_status(ctx, out_p1s != nullptr, n);
+    if (rc == KZG_OK) rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     const size_t N = sh.N, ncols = 2 * t + 1;
     PqBufs w;
     void *in, *cols, *d_out, *coef, *flag, *d_gate = nullptr;
@@ -5640,16 +5730,14 @@ int kzg_permutation_quotient(kzg_ctx* ctx, const uint64_t* wires, const uint64_t
     if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, d_in, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
     const PqChallenges ch{shifts, alpha, beta, gamma};
     if (rc == KZG_OK) rc = pq_constraints(ctx, lk, s.stream, sh, t, N, d_w, d_s, d_z, (const uint32_t*)d_gate, d_l0, ch, w, (uint32_t*)d_out);
-    if (rc == KZG_OK) rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag);
-    uint32_t hflag = 0;
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
-    if (rc == KZG_OK && out_coeffs)
-        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "permutation quotient");
+    bool remainder = false;
+    if (rc == KZG_OK)
+        rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, 0, N - n, out_coeffs,
+                       "permutation quotient", &remainder);
     if (rc) return rc;
-    if (hflag) return pq_remainder(ctx, sh);
+    if (remainder) return pq_remainder(ctx, sh);
     if (!out_p1s) return KZG_OK;
-    return pq_commit_chunks(ctx, lk, slot, (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
+    return pq_commit_chunks(ctx, lk, call.slot(), (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
 }
 
 // ---- a circuit's key resident on the device (circuit_kernels.hip) -----------------------------------------
@@ -5671,21 +5759,19 @@ static int circuit_foreign(kzg_ctx* ctx) {
     return KZG_ERR_INVALID_ARG;
 }
 
-// the body of kzg_circuit_create on a single-device context (quotient_mu held): fills *c, whose buffers go with it on failure
-static int circuit_build(kzg_ctx* ctx, kzg_circuit* c, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul,
+// the body of kzg_circuit_create on a single-device context (on its frame: quotient_mu held): fills *c, whose buffers go with it
+// on failure.  The frame is the caller's, because quotient_mu has to outlast this body (the list of circuits): the context's
+// mutex and the slot are therefore held until kzg_circuit_create returns -- on failure across the drain and the hipFree of c's
+// buffers, which take no lock
+static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul,
                          const uint64_t* q_const, const uint64_t* sigmas, size_t stride, uint64_t* out_key_p1s) {
-    std::unique_lock<std::mutex> lk(ctx->mu);
+    call.lock();
     const size_t n = sh.n, N = sh.N, t = c->t, ncols = c->cols();
-    if (out_key_p1s) {
-        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
-        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
-    }
-    int slot = -1;
-    int rc = pq_begin(ctx, lk, &slot);
+    int rc = pq_srs_status(ctx, out_key_p1s != nullptr, n);
+    if (rc == KZG_OK) rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     rc = pq_bufs(ctx, N, ncols, &w);
     if (rc == KZG_OK) rc = c->values.reserve(ctx, ncols * n * 32);
@@ -5723,7 +5809,7 @@ static int circuit_build(kzg_ctx* ctx, kzg_circuit* c, const PqShape& sh, const 
     rc = copy_unlocked(ctx, lk, s.stream, c->zinv.p, h, sh.rot * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (vanishing inverses)");
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit key");  // (h leaves scope)
     if (rc || !out_key_p1s) return rc;
-    return pq_commit_chunks(ctx, lk, slot, d_coef, n, ncols, out_key_p1s);
+    return pq_commit_chunks(ctx, lk, call.slot(), d_coef, n, ncols, out_key_p1s);
 }
 
 int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
@@ -5735,15 +5821,11 @@ int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mu
         t > kPqMaxColumns || t + 1 > sh.rot || stride < n || !q_lin || !q_mul || !q_const || !sigmas || !shifts)
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        // without the key's commitments the call needs no SRS; with them it follows kzg_commit_lagrange
-        if (out_key_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the key's commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, out_key_p1s != nullptr, "the key's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_create(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, out_key_p1s, out));
     }
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    PqCall call(ctx);
     kzg_circuit* c = new kzg_circuit();
     c->owner = ctx;
     c->lg_n = sh.lg_n;
@@ -5751,10 +5833,11 @@ int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mu
     c->n = n;
     c->t = t;
     std::memcpy(c->shifts, shifts, 32 * t);
-    int rc = circuit_build(ctx, c, sh, q_lin, q_mul, q_const, sigmas, stride, out_key_p1s);
+    int rc = circuit_build(ctx, call, c, sh, q_lin, q_mul, q_const, sigmas, stride, out_key_p1s);
     if (rc) {
         (void)hipSetDevice(ctx->device);
-        delete c;  // (circuit_build drained the stream before it returned)
+        call.drain();  // (nothing enqueued still writes to the buffers that go with c)
+        delete c;
         return rc;
     }
     ctx->circuits.push_back(c);
@@ -5808,8 +5891,7 @@ int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned
 static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                                  const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const void* gate, void* out_coeffs,
                                  uint64_t* out_p1s, bool device, const ProveRound* round = nullptr) {
-    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
-    if (!round) lkq.lock();
+    PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -5822,19 +5904,12 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
             return KZG_ERR_INVALID_ARG;
         }
     }
-    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
-    if (!round) own.lock();
-    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
-    if (out_p1s) {
-        if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
-        if (n > ctx->n) return KZG_ERR_DEGREE_TOO_HIGH;
-    }
-    int slot = round ? round->slot : -1;
-    int rc = round ? (int)KZG_OK : pq_begin(ctx, lk, &slot);
+    call.lock();
+    int rc = pq_srs_status(ctx, out_p1s != nullptr, n);
+    if (rc == KZG_OK) rc = call.begin();
     if (rc) return rc;
-    SlotLease lease{ctx, round ? -1 : slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *d_gate = const_cast<void*>(gate);
     rc = pq_bufs(ctx, N, ncols, &w);
@@ -5855,39 +5930,20 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
         if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)z, n, n, (int)sh.lg_n, 1, sh.lg_N, d_z, w);
         if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, (const uint32_t*)pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
     } else {
-        uint32_t* d_in = (uint32_t*)in;
-        rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
-        if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)z, n, 1, n);
-        if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (t + 1) * n, (const uint64_t*)pi, n, 1, n);
+        PqStaged src;  // [ wires | z | PI ], as the extended columns: one extension
+        rc = pq_stage(ctx, lk, s.stream, false, (uint32_t*)in, wires, stride, z, pi, n, t, false, &src);
         if (rc == KZG_OK && gate) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_gate, (const uint64_t*)gate, N, 1, N);
-        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, d_in, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
+        if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, src.w, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
     }
+    if (rc == KZG_OK) rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, (const uint32_t*)d_gate, alpha, beta, gamma, (uint32_t*)d_out);
+    bool remainder = false;
+    if (rc == KZG_OK)
+        rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, 0, N - n,
+                       device ? nullptr : out_coeffs, "circuit quotient", &remainder);
     if (rc) return rc;
-    {
-        const hf::Fr a = pq_fr(alpha), b = pq_fr(beta), g = fr_seven();
-        const Fr30 f_beta = fr30_arg_from_mont256(b), f_gamma = pq_image(pq_fr(gamma)), f_one = pq_image(hf::kFrOne);
-        const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2((uint32_t)(14 * t))));
-        const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), fr_pow2(14)));
-        const Fr30 k14 = fr30_arg_from_mont256(fr_pow2(14));
-        Fr30 bkg[kPqMaxColumns];
-        for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(b, pq_fr(c->shifts + 4 * j)), g));
-        const uint32_t* key = c->coset.dev();
-        const CkColumns ck{d_w, key, key + 8 * (t + 2) * N, key + 8 * t * N, key + 8 * (t + 1) * N, d_z, c->l0.dev(), d_pi,
-                           (const uint32_t*)d_gate, c->zinv.dev()};
-        const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
-        launch_ck_constraints(s.stream, ck, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, N, sc, k14, ctx->ntt_tw.p, (uint32_t*)d_out);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag);
-    uint32_t hflag = 0;
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
-    if (rc == KZG_OK && out_coeffs && !device)
-        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, (N - n) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient");
-    if (rc) return rc;
-    if (hflag) return pq_remainder(ctx, sh);
+    if (remainder) return pq_remainder(ctx, sh);
     if (!out_p1s) return KZG_OK;
-    return pq_commit_chunks(ctx, lk, slot, (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
+    return pq_commit_chunks(ctx, lk, call.slot(), (const uint32_t*)coef, n, sh.rot - 1, out_p1s);
 }
 
 int kzg_circuit_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
@@ -5895,11 +5951,8 @@ int kzg_circuit_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_
                          const uint64_t* gate_coset, uint64_t* out_coeffs, uint64_t* out_p1s) {
     if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_quotient(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, gate_coset,
                                                        out_coeffs, out_p1s));
     }
@@ -5973,23 +6026,15 @@ static int blind_evaluations_impl(kzg_ctx* ctx, const char* what, const uint64_t
     if (!ntt_log(n, &lg_n) || k < 1 || k > kMaxCoefficients || stride < n || nb < 1 || nb > kBlindLow || (out_coeffs && out_stride < n + nb))
         return KZG_ERR_INVALID_ARG;
     const size_t len = n + nb;
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    PqCall call(ctx);
     std::vector<hf::Fr> bl;
     if (!blind_values_ok(ctx, what, blinders, k * nb, &bl)) return KZG_ERR_INVALID_ARG;
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    auto srs_status = [&]() {
-        if (!out_p1s) return (int)KZG_OK;
-        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
-        return len > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
-    };
-    int rc = srs_status();
+    call.lock();
+    int rc = pq_srs_status(ctx, out_p1s != nullptr, len);
+    if (rc == KZG_OK) rc = call.begin();
     if (rc) return rc;
-    int slot = -1;
-    rc = pq_begin(ctx, lk, &slot);
-    if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void *in, *stack, *d_bl;
     rc = pq_bufs(ctx, n, 1, &w);
@@ -6014,7 +6059,7 @@ static int blind_evaluations_impl(kzg_ctx* ctx, const char* what, const uint64_t
     }
     rc = sync_unlocked(ctx, lk, s.stream, what);
     if (rc || !out_p1s) return rc;
-    return pq_commit_chunks(ctx, lk, slot, d_c, len, k, out_p1s);
+    return pq_commit_chunks(ctx, lk, call.slot(), d_c, len, k, out_p1s);
 }
 
 int kzg_blind_evaluations(kzg_ctx* ctx, const uint64_t* evals, size_t n, size_t k, size_t stride, const uint64_t* blinders, size_t nb,
@@ -6031,11 +6076,8 @@ int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n
                                    size_t nb, uint64_t* out_p1s) {
     if (!ctx || !evals || !blinders || !out_p1s) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the blinded commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the blinded commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_commit_evaluations_blinded(kid, evals, n, k, stride, blinders, nb, out_p1s));
     }
     return blind_evaluations_impl(ctx, "commit evaluations (blinded)", evals, n, k, stride, blinders, nb, nullptr, 0, out_p1s);
@@ -6047,8 +6089,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
                                          const void* pi, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                                          const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device,
                                          const ProveRound* round = nullptr) {
-    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
-    if (!round) lkq.lock();
+    PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -6065,22 +6106,12 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
             return KZG_ERR_INVALID_ARG;
         }
     }
-    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
-    if (!round) own.lock();
-    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
-    auto srs_status = [&]() {
-        if (!out_p1s) return (int)KZG_OK;
-        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
-        return Lc > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
-    };
-    int rc = srs_status();
+    call.lock();
+    int rc = pq_srs_status(ctx, out_p1s != nullptr, Lc);
+    if (rc == KZG_OK) rc = call.begin();
     if (rc) return rc;
-    int slot = round ? round->slot : -1;
-    if (!round) rc = pq_begin(ctx, lk, &slot);
-    if (rc) return rc;
-    SlotLease lease{ctx, round ? -1 : slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *stack, *chunks;
     // the blinders as the patches read them: the array as given, then a zero and the chunk blinders once more ([0, d_0 .. d_(e-3)]
@@ -6105,19 +6136,9 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
         if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient (blinded)");  // (hb leaves scope)
         if (rc) return rc;
     }
-    const uint32_t *src_w = (const uint32_t*)wires, *src_pi = (const uint32_t*)pi, *src_z = (const uint32_t*)z;
-    size_t src_stride = stride;
-    if (!device) {
-        uint32_t* d_in = (uint32_t*)in;
-        rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
-        if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)z, n, 1, n);
-        if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (t + 1) * n, (const uint64_t*)pi, n, 1, n);
-        if (rc) return rc;
-        src_w = d_in;
-        src_z = d_in + 8 * t * n;
-        src_pi = d_in + 8 * (t + 1) * n;
-        src_stride = n;
-    }
+    PqStaged src;
+    rc = pq_stage(ctx, lk, s.stream, device, (uint32_t*)in, wires, stride, z, pi, n, t, false, &src);
+    if (rc) return rc;
     {  // the wires and z: values -> coefficients -> patch -> the coset, from n + 3 coefficients each
         const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
         const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
@@ -6125,42 +6146,26 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
             HIP_TRY(ctx, hipMemcpy2DAsync(d_c, clen * 32, round->coef, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
             HIP_TRY(ctx, hipMemcpyAsync(d_c + 8 * t * clen, round->coef + 8 * (ncols - 1) * n, n * 32, hipMemcpyDeviceToDevice, s.stream));
         } else {
-            for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
-            launch_ntt(s.stream, src_z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src.w + 8 * j * src.stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            launch_ntt(s.stream, src.z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
         }
         launch_blind_patch(s.stream, d_c, (uint32_t)n, t, clen, d_bl, d_bl, kBlindWireLen, t);
         launch_blind_patch(s.stream, d_c + 8 * t * clen, (uint32_t)n, 1, clen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
         HIP_TRY(ctx, hipGetLastError());
         rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, t + 1, sh.lg_N, d_w, w, nullptr, round != nullptr);
         if (rc == KZG_OK && pi && round) rc = pq_extend(ctx, s.stream, round->coef + 8 * t * n, n, n, -1, 1, sh.lg_N, d_pi, w);
-        if (rc == KZG_OK && pi && !round) rc = pq_extend(ctx, s.stream, src_pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
+        if (rc == KZG_OK && pi && !round) rc = pq_extend(ctx, s.stream, src.pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
         if (rc) return rc;
     }
-    {
-        const hf::Fr a = pq_fr(alpha), b = pq_fr(beta), g = fr_seven();
-        const Fr30 f_beta = fr30_arg_from_mont256(b), f_gamma = pq_image(pq_fr(gamma)), f_one = pq_image(hf::kFrOne);
-        const Fr30 a1 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2((uint32_t)(14 * t))));
-        const Fr30 a2 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), fr_pow2(14)));
-        const Fr30 k14 = fr30_arg_from_mont256(fr_pow2(14));
-        Fr30 bkg[kPqMaxColumns];
-        for (size_t j = 0; j < t; j++) bkg[j] = pq_image(hf::fr_mul(hf::fr_mul(b, pq_fr(c->shifts + 4 * j)), g));
-        const uint32_t* key = c->coset.dev();
-        const CkColumns ck{d_w, key, key + 8 * (t + 2) * N, key + 8 * t * N, key + 8 * (t + 1) * N, d_z, c->l0.dev(), d_pi,
-                           nullptr, c->zinv.dev()};
-        const PqScalars sc{&f_beta, &f_gamma, &f_one, &a1, &a2, bkg};
-        launch_ck_constraints(s.stream, ck, sh.lg_N, (uint32_t)sh.rot, (uint32_t)t, N, sc, k14, ctx->ntt_tw.p, (uint32_t*)d_out);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, nullptr, alpha, beta, gamma, (uint32_t*)d_out);
+    if (rc) return rc;
     // T~ has t n + t + 3 coefficients: those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
     if (LT > keep) HIP_TRY(ctx, hipMemsetAsync((uint32_t*)coef + 8 * keep, 0, (LT - keep) * 32, s.stream));
-    rc = pq_interpolate(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, keep);
-    uint32_t hflag = 0;
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, &hflag, flag, 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (flag)");
-    if (rc == KZG_OK && out_coeffs && !device)
-        rc = copy_unlocked(ctx, lk, s.stream, out_coeffs, coef, LT * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (quotient)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient (blinded)");
+    bool remainder = false;
+    rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, keep, LT,
+                   device ? nullptr : out_coeffs, "circuit quotient (blinded)", &remainder);
     if (rc) return rc;
-    if (hflag) {
+    if (remainder) {
         ctx->last_error = "quotient: the blinded numerator is not divisible by X^" + std::to_string(n) +
                           " - 1 (a coefficient of the interpolant at [t n + t + 3, N) is not zero): the constraints do not hold on the domain";
         return KZG_ERR_REMAINDER;
@@ -6173,9 +6178,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     HIP_TRY(ctx, hipMemcpyAsync(d_ch + 8 * (e - 2) * Lc, d_t + 8 * (e - 2) * n, Lc * 32, hipMemcpyDeviceToDevice, s.stream));
     if (e > 2) launch_blind_patch(s.stream, d_ch, (uint32_t)n, e - 1, Lc, d_bl + 8 * nbl, d_bl + 8 * (nbl + 1), 1, e - 2);
     HIP_TRY(ctx, hipGetLastError());
-    rc = srs_status();  // (the waits dropped the mutex)
-    if (rc) return rc;
-    return pq_commit_chunks(ctx, lk, slot, d_ch, Lc, e - 1, out_p1s);
+    return pq_commit_chunks(ctx, lk, call.slot(), d_ch, Lc, e - 1, out_p1s);  // (checks the SRS again: the waits dropped the mutex)
 }
 
 int kzg_circuit_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
@@ -6183,11 +6186,8 @@ int kzg_circuit_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const
                                  const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s) {
     if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma || !blinders) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (out_p1s && multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the quotient's commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_quotient_blinded(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders,
                                                                out_coeffs, out_p1s));
     }
@@ -6366,8 +6366,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
                              const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                              const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
                              bool device, const uint64_t* blinders = nullptr, const ProveRound* round = nullptr) {
-    std::unique_lock<std::mutex> lkq(ctx->quotient_mu, std::defer_lock);
-    if (!round) lkq.lock();
+    PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
@@ -6400,24 +6399,13 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         ctx->last_error = "circuit open: " + why;
         return KZG_ERR_INVALID_ARG;
     }
-    std::unique_lock<std::mutex> own(ctx->mu, std::defer_lock);
-    if (!round) own.lock();
-    std::unique_lock<std::mutex>& lk = round ? *round->lk : own;
-    auto srs_status = [&]() {
-        if (!v) return (int)KZG_OK;
-        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
-        return L - 1 > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
-    };
-    int rc = srs_status();
+    call.lock();
+    int rc = pq_srs_status(ctx, v != nullptr, L - 1);
+    if (rc == KZG_OK) rc = call.begin();
+    if (rc == KZG_OK) rc = pq_srs_status(ctx, v != nullptr, L - 1);  // (the wait for a slot dropped the mutex: the SRS may have changed)
     if (rc) return rc;
-    int slot = round ? round->slot : -1;
-    if (!round) rc = pq_begin(ctx, lk, &slot);
-    if (rc) return rc;
-    SlotLease lease{ctx, round ? -1 : slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
-    rc = srs_status();  // (the wait for a slot dropped the mutex: the SRS may have changed)
-    if (rc) return rc;
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
     PqBufs w;
     void *in = nullptr, *stack, *scratch, *coef = const_cast<void*>(t_coeffs);
     rc = pq_bufs(ctx, n, 1, &w);
@@ -6434,25 +6422,15 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     uint32_t* d_f = round ? const_cast<uint32_t*>(round->coef) : (uint32_t*)stack;  // (a round's coefficients are only read)
     uint32_t *d_pi = pi ? d_f + 8 * t * n : nullptr, *d_z = d_f + 8 * (ncoef - 1) * n;
     if (!round) {
-        const uint32_t *src_w = (const uint32_t*)wires, *src_pi = (const uint32_t*)pi, *src_z = (const uint32_t*)z;
-        size_t src_stride = stride;
-        if (!device) {
-            uint32_t* d_in = (uint32_t*)in;
-            rc = pq_upload(ctx, lk, s.stream, d_in, (const uint64_t*)wires, n, t, stride);
-            if (rc == KZG_OK && pi) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * t * n, (const uint64_t*)pi, n, 1, n);
-            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_in + 8 * (ncoef - 1) * n, (const uint64_t*)z, n, 1, n);
-            if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)coef, (const uint64_t*)t_coeffs, t_len, 1, t_len);
-            if (rc) return rc;
-            src_w = d_in;
-            src_pi = d_in + 8 * t * n;
-            src_z = d_in + 8 * (ncoef - 1) * n;
-            src_stride = n;
-        }
+        PqStaged src;
+        rc = pq_stage(ctx, lk, s.stream, device, (uint32_t*)in, wires, stride, z, pi, n, t, true, &src);
+        if (rc == KZG_OK && !device) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)coef, (const uint64_t*)t_coeffs, t_len, 1, t_len);
+        if (rc) return rc;
         const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
         const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
-        for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src_w + 8 * j * src_stride, d_f + 8 * j * n, sh.lg_n, itw, inv_n, w.A, w.B);
-        if (pi) launch_ntt(s.stream, src_pi, d_pi, sh.lg_n, itw, inv_n, w.A, w.B);
-        launch_ntt(s.stream, src_z, d_z, sh.lg_n, itw, inv_n, w.A, w.B);
+        for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src.w + 8 * j * src.stride, d_f + 8 * j * n, sh.lg_n, itw, inv_n, w.A, w.B);
+        if (pi) launch_ntt(s.stream, src.pi, d_pi, sh.lg_n, itw, inv_n, w.A, w.B);
+        launch_ntt(s.stream, src.z, d_z, sh.lg_n, itw, inv_n, w.A, w.B);
         HIP_TRY(ctx, hipGetLastError());
     }
     // 2. evaluations, into the slot's value words: [0, t) the wires at zeta, [t] PI(zeta), [t + 1, 2 t) the sigmas, [2 t] z(zeta w)
@@ -6565,12 +6543,12 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     std::memcpy(got.l, hv + 8 * npoly, 32);
     if (!fr_equal(got, want[0])) return lin_remainder(ctx);
     // 4. the scans and the MSM of kzg_open_sets, unchanged
-    rc = srs_status();  // (the waits dropped the mutex)
+    rc = pq_srs_status(ctx, true, L - 1);  // (the waits dropped the mutex)
     if (rc == KZG_OK) rc = sets_enqueue_open(ctx, s, plan, L);
     if (rc) return rc;
     await_unlocked(lk, s);
     std::vector<uint64_t> unused(4 * plan.nvals);
-    rc = wait_sets_locked(ctx, slot, unused.data(), out_p1);
+    rc = wait_sets_locked(ctx, call.slot(), unused.data(), out_p1);
     s.kind = SLOT_RESERVED;  // (the mutex was held since the wait marked it idle)
     return rc;
 }
@@ -6584,11 +6562,8 @@ int kzg_circuit_open(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* w
     if (!ctx || !circuit || !wires || !z || !t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !out_evals || !out_p1)
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the opening needs the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the opening needs");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_open(kid, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma, zeta, v,
                                                    out_evals, out_p1));
     }
@@ -6614,11 +6589,8 @@ int kzg_circuit_open_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uin
     if (!ctx || !circuit || !wires || !z || !t_coeffs || !alpha || !beta || !gamma || !zeta || !v || !blinders || !out_evals || !out_p1)
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the opening needs the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the opening needs");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_open_blinded(kid, circuit, wires, stride, z, public_inputs, t_coeffs, alpha, beta, gamma,
                                                            zeta, v, blinders, out_evals, out_p1));
     }
@@ -8756,7 +8728,7 @@ int prove_refused(kzg_ctx* ctx, const char* why) {
 // wires: t columns of n values, host (stride in values) or device when `device`
 int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
                        const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device) {
-    std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+    PqCall call(ctx);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
@@ -8771,23 +8743,16 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     }
     const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
     const size_t wlen = blinders ? n + kBlindWireLen : n, zlen = blinders ? n + kBlindZLen : n;
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    auto srs_status = [&]() {
-        if (!ctx->n || !ctx->slots_ready) return (int)KZG_ERR_NO_SRS;
-        return need > ctx->n ? (int)KZG_ERR_DEGREE_TOO_HIGH : (int)KZG_OK;
-    };
-    int rc = srs_status();
-    if (rc) return rc;
-    int slot = -1;
-    rc = pq_begin(ctx, lk, &slot);
-    if (rc) return rc;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    PqDrain drain{s};
-    rc = srs_status();  // (the wait for a slot dropped the mutex)
+    call.lock();
+    int rc = pq_srs_status(ctx, true, need);
+    if (rc == KZG_OK) rc = call.begin();
+    if (rc == KZG_OK) rc = pq_srs_status(ctx, true, need);  // (the wait for a slot dropped the mutex)
     if (rc == KZG_OK) rc = ensure_ntt_batch(ctx);
     if (rc) return rc;
-    // every cross-round buffer at its size for the whole proof, before anything is enqueued (the stream is empty: PqDrain)
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
+    const int slot = call.slot();
+    // every cross-round buffer at its size for the whole proof, before anything is enqueued (the stream is empty: PqCall)
     DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &S = ctx->prove_buf[2], &T = ctx->prove_buf[3], &B = ctx->prove_buf[4];
     rc = V.reserve(ctx, ncoef * n * 32, s.stream);
     if (rc == KZG_OK) rc = U.reserve(ctx, ncoef * n * 32, s.stream);
@@ -8923,11 +8888,8 @@ int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* 
                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
     if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
-        if (multi_mode(ctx->multi) != kMultiReplicate) {
-            ctx->last_error = "the proof's commitments need the whole SRS on one device: not on a range-split multi-device context";
-            return KZG_ERR_INVALID_ARG;
-        }
-        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
     }
     return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false);

@@ -144,7 +144,7 @@ int main() {
     Fr30 bkg[kMaxT];
     for (int j = 0; j < t; j++) bkg[j] = read_image();
     if (!ok) return 2;
-    // as pq_constraints (api.hip) prepares them
+    // as PqKernelScalars (api.hip) prepares them
     const Fr30 f_beta = fr30_arg_from_mont256(beta);
     const Fr30 a1 = fr30_arg_from_mont256(kzg_host::fr_mul(alpha, pow2(14 * t)));
     const Fr30 a2 = fr30_arg_from_mont256(kzg_host::fr_mul(kzg_host::fr_mul(alpha, alpha), pow2(14)));

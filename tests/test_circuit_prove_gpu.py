@@ -4,9 +4,10 @@ tests/transcript_oracle.py and the bytes of the existing entry points chained by
 
 Shapes (n, t, log_ext): blinded (8, 3, 2), (256, 3, 2), one tile (2048, 3, 2), two passes (4096, 2, 2), 31 columns (64, 7, 3);
 plain (1, 3, 2), (2, 3, 2), (4096, 2, 2); with and without public inputs at (8, 3, 2) and (256, 3, 2); wire stride n + 5.  Then two
-blinder sets, the statuses with out_proof untouched and the context serving, the device form inside guard bands, a call after a
+blinder sets, the statuses with out_proof untouched and the context serving, the slot given back once, the device form inside guard bands, a call after a
 larger opening on the same context (regrown workspaces), and two-device contexts."""
 import ctypes as C
+import threading
 
 import numpy as np
 import pytest
@@ -130,6 +131,47 @@ def test_statuses_leave_the_output_untouched_and_the_context_serving(engines, or
     finally:
         circ.close()
         broken.close()
+
+
+def test_a_proof_gives_back_one_slot_once(engines, oracle):
+    """The rounds of a proof run on the call's slot and give nothing back themselves; the call gives it back once.  Seen from
+    outside: after a proof, with every slot then taken by a submitted job, a synchronous call finds no slot that another
+    synchronous caller could free and is refused with KZG_ERR_BUSY at once.  Were the count of owned slots off after the proof, it
+    would wait for one instead: so the call runs on a thread of its own, and if it has not come back the jobs are collected, which
+    frees it, before its status is judged."""
+    n, t, log_ext = 8, 3, 2
+    e = engines.bench_srs(SRS)
+    bl, d = HC._case(oracle, n, t, log_ext, True, True)
+    c = d["c"]
+    circ = HC._create(e, c, log_ext)
+    coeffs = GO.to_limbs(list(range(1, n + 1)))
+    dptr = e.dev_alloc(coeffs.nbytes)
+    status = []
+
+    def synchronous_call():
+        try:
+            e.commit_limbs(coeffs)
+            status.append(0)
+        except K.KzgError as err:
+            status.append(err.status)
+
+    try:
+        assert circ.prove(HC._limbs(c.wires, n), _pub(d), _bl(bl, True)) == d["proof"]
+        e.dev_upload(dptr, coeffs)
+        slots = e.num_slots()
+        for s in range(slots):
+            e.commit_submit(s, dptr, n)
+        caller = threading.Thread(target=synchronous_call, daemon=True)
+        caller.start()
+        caller.join(5)
+        came_back = not caller.is_alive()
+        points = [e.wait(s).compress() for s in range(slots)]
+        caller.join(60)
+        assert came_back and status == [K.KZG_ERR_BUSY], (came_back, status)
+        assert len(set(points)) == 1 and e.commit_limbs(coeffs).compress() == points[0]  # the context serves
+    finally:
+        e.dev_free(dptr)
+        circ.close()
 
 
 def test_shape_rule_no_srs_and_short_srs(engines, oracle):

@@ -1,7 +1,7 @@
 """Every column of a Montgomery product in k_bucket_accumulate is ONE v_mad_i64_i32 chain that starts from the shifted carry
 of the column below (field30.hip.h, KZG_F30_MAC): no chain opened from zero and joined with a 64-bit add, no second chain
 subtracted with borrow in fq_mul_sub.  This test counts opcodes in the main loop of the compiler's output for gfx950 (the
-assembly of tests/test_accum_isa.py, cached under csrc/build/ by the hash of the sources) and prices them with
+assembly tests/test_accum_isa.py reads, from tests/isa_cache.py) and prices them with
 tools/isa_histogram.py.  CPU only; it reads opcodes and counts, nothing else.
 
 Before the change the loop held 3091 v_mad_i64_i32, 240 v_lshl_add_u64 (123 joins, 111 rounding adds, 6 others), 25 + 25
@@ -15,15 +15,13 @@ the bias for nothing, so a biased accumulator needs its 2^29 added every column 
 the digit on top); a bias of 2^29 + 2^59 that survives the shift does not fit the 0.45 x 2^60 the column bound leaves.  What
 stands is one 64-bit add per upper column and none per lower one.  The threshold below is what was reached."""
 import collections
-import hashlib
 import os
 import re
 import subprocess
 import sys
 
-import pytest
-
-from test_accum_isa import ROOT, kernel_asm
+from isa_cache import ROOT, asm_path, requires_hipcc
+from test_accum_isa import UNIT
 
 RATES = os.path.join(ROOT, "profiles", "r03_instr_rates.jsonl")
 TOOL = os.path.join(ROOT, "tools", "isa_histogram.py")
@@ -32,22 +30,13 @@ PARENT_UNITS = 7530
 PARENT_NOP_LOOP, PARENT_NOP_KERNEL = 74, 78
 REACHED = 267  # priced units below the parent (see above; 300 with the rounding adds gone)
 
-pytestmark = pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
-
-
-def asm_path():
-    kernel_asm()  # compiles on a miss
-    build = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc", "build")
-    h = hashlib.sha256()
-    for f in ("msm_accum.hip", "g1_30.hip.h", "field30.hip.h", "field30_inv.hip.h", "engine.h"):
-        h.update(open(os.path.join(os.path.dirname(build), f), "rb").read())
-    return os.path.join(build, "msm_accum_%s.s" % h.hexdigest()[:16])
+pytestmark = requires_hipcc
 
 
 def main_loop_opcodes():
     """opcodes of the kernel's main loop, found the way tools/isa_histogram.py finds it: from the loop header in front of
     the LDS-DMA gathers to the last block that belongs to that loop"""
-    asm = open(asm_path()).read().splitlines()
+    asm = open(asm_path(UNIT)).read().splitlines()
     start = next(i for i, l in enumerate(asm) if re.match(r"^_ZN3kzg19k_bucket_accumulate.*:\s*; @", l))
     end = next(i for i in range(start, len(asm)) if "s_endpgm" in asm[i])
     body = asm[start:end]
@@ -81,7 +70,7 @@ def test_one_chain_per_column_in_the_main_loop():
 
 
 def test_priced_issue_units_of_the_main_loop():
-    out = subprocess.run([sys.executable, TOOL, asm_path(), RATES], check=True, capture_output=True, text=True).stdout
+    out = subprocess.run([sys.executable, TOOL, asm_path(UNIT), RATES], check=True, capture_output=True, text=True).stdout
     m = re.search(r"multiply-adds: (\d+) of (\d+) units", out)
     assert m, out
     mads, units = int(m.group(1)), int(m.group(2))

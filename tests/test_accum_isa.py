@@ -1,28 +1,16 @@
 """The accumulation kernel waits for "all but the youngest 17" vector-memory operations after a bucket flush
 (msm_accum.hip, accum_take_point): that is only correct while the flush path issues AT LEAST 17 such operations between the
 gather of the point and the wait.  This test counts them in the compiler's output for gfx950.  CPU only (hipcc cross-compiles);
-the assembly is cached under csrc/build/ keyed by the hash of the sources."""
-import hashlib
-import os
+the assembly comes from tests/isa_cache.py."""
 import re
-import subprocess
 
-import pytest
+from isa_cache import asm_text, requires_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
+UNIT = "msm_accum.hip"
 
 
 def kernel_asm():
-    h = hashlib.sha256()
-    for f in ("msm_accum.hip", "g1_30.hip.h", "field30.hip.h", "field30_inv.hip.h", "engine.h"):
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "msm_accum_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, "msm_accum.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
+    asm = asm_text(UNIT)
     i = asm.index("_ZN3kzg19k_bucket_accumulateE")
     i = asm.index(":", i)
     return asm[i:asm.index(".end_amdhsa_kernel", i)].splitlines(), asm
@@ -33,7 +21,7 @@ def is_vmem(line):
     return op.startswith(("global_load", "global_store", "global_atomic", "scratch_", "buffer_", "flat_"))
 
 
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_flush_path_issues_the_operations_the_partial_wait_counts():
     body, _ = kernel_asm()
     waits = [n for n, l in enumerate(body) if re.search(r"s_waitcnt\s+vmcnt\(17\)", l)]

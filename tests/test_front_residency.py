@@ -3,25 +3,21 @@ accumulation grid is exactly one resident round, two workgroups per CU, so a ker
 for a CU that one of the two has left (msm_sort.hip, at kRecodeBlock; DESIGN.md sections 4.3 and 5.0s).  This test
 reads the registers, LDS and scratch of the sort kernels from the compiler's resource remarks for gfx950 and holds them to what
 two accumulation workgroups leave free.  The accumulation kernel's own figures come from its sources: the register clobber in
-msm_accum.hip and the LDS reservation in api.hip.  CPU only (hipcc cross-compiles); the remarks are cached under csrc/build/
-keyed by the hash of the sources."""
-import hashlib
+msm_accum.hip and the LDS reservation in api.hip.  CPU only (hipcc cross-compiles); the remarks come from
+tests/isa_cache.py."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S",
-         "-Rpass-analysis=kernel-resource-usage"]
+from isa_cache import CSRC, remarks_text, requires_hipcc
+
 VGPRS_PER_SIMD_LANE = 512
 LDS_PER_CU = 160 * 1024
 VGPR_GRANULE = 8
 FRONT_KERNELS = ("k_sort_count", "k_sort_spread", "k_sort_spread_staged", "k_fine_count", "k_fine_binscan", "k_fine_scatter")
 
-pytestmark = pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+pytestmark = requires_hipcc
 
 
 def read(name):
@@ -32,19 +28,8 @@ def read(name):
 def usage():
     """kernel name -> list of (mangled name, VGPRs and AGPRs (one register file on gfx950), scratch bytes per lane, LDS bytes per
     workgroup), one per instantiation"""
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    for f in ("msm_sort.hip", "msm_recode.h", "fr30.hip.h", "engine.h"):
-        h.update(read(f).encode())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "msm_sort_usage_%s.txt" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        r = subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, "msm_sort.hip"), "-o", os.devnull], check=True,
-                           capture_output=True, text=True)
-        with open(out + ".tmp", "w") as f:
-            f.write(r.stderr)
-        os.replace(out + ".tmp", out)
     kernels = {}
-    for block in open(out).read().split("Function Name: ")[1:]:
+    for block in remarks_text("msm_sort.hip", "-Rpass-analysis=kernel-resource-usage").split("Function Name: ")[1:]:
         mangled = block.split()[0]
         m = re.match(r"_ZN3kzg\d+(k_[a-z_]+)", mangled)
         if not m:

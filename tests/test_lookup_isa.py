@@ -1,21 +1,16 @@
 """The kernels of the log-derivative sums and of the multiplicities (lookup_kernels.hip: k_lu_tile with its twins
 k_lu_tile_lookup and k_lu_tile_inv, k_lu_carry, k_lu_finish, k_lu_build, k_lu_probe, k_lu_counts) are the unit's only kernels,
 use no scratch memory, spill no register and keep their pinned VGPR counts: checked in the compiler's resource metadata for
-gfx950.  The unit is plain HIP C++, without inline assembly.  CPU only (hipcc cross-compiles); the assembly is cached under
-csrc/build/ keyed by the hash of the sources.
+gfx950.  The unit is plain HIP C++, without inline assembly.  CPU only (hipcc cross-compiles); the assembly comes from
+tests/isa_cache.py.
 
 The goal for every kernel is <= 160 VGPRs (resident beside another slot's accumulation kernel: 512 - 2 x 176).  With a run of 2
 rows per lane -- the grand product's run of 4 took 226 -- every kernel meets it: there is no exception to document."""
-import hashlib
 import os
 import re
-import subprocess
 
-import pytest
+from isa_cache import CSRC, kernel_meta, requires_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
 UNIT = "lookup_kernels.hip"
 # as found ("E": the end of the mangled name)
 VGPRS = {"k_lu_tileE": 132, "k_lu_tile_lookupE": 132, "k_lu_tile_invE": 99, "k_lu_carryE": 126, "k_lu_finishE": 45,
@@ -24,27 +19,9 @@ EXCEPTION = set()  # above the goal of 160, below the 256 of two waves per SIMD:
 PLANE = 256 * 9 * 4  # one digit plane of the scans
 
 
-def kernel_meta():
-    h = hashlib.sha256()
-    for f in (UNIT, "fr30.hip.h", "engine.h"):
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "lookup_kernels_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, UNIT), "-o", out], check=True, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {}
-    for block in asm[asm.index("amdhsa.kernels:"):].split("\n  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
-                      for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
-                                  "group_segment_fixed_size")}
-    return meta
-
-
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_lookup_kernels_are_listed_and_use_no_scratch():
-    meta = kernel_meta()
+    meta = kernel_meta(UNIT)
     assert len(meta) == len(VGPRS), sorted(meta)
     by = {}
     for want, vgprs in VGPRS.items():

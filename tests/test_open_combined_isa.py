@@ -1,38 +1,12 @@
 """The kernels of the combined openings (combine_kernels.hip: k_combine_eval, k_combine_eval_finish) use no scratch memory and
-spill no register: checked in the compiler's metadata for gfx950.  CPU only (hipcc cross-compiles); the assembly is cached under
-csrc/build/ keyed by the hash of the sources."""
-import hashlib
-import os
-import re
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
+spill no register: checked in the compiler's metadata for gfx950.  CPU only (hipcc cross-compiles); the assembly comes from
+tests/isa_cache.py."""
+from isa_cache import kernel_meta, requires_hipcc
 
 
-def kernel_meta():
-    h = hashlib.sha256()
-    for f in ("combine_kernels.hip", "fr30.hip.h", "engine.h"):
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "combine_kernels_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, "combine_kernels.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {}
-    for block in asm[asm.index("amdhsa.kernels:"):].split("\n  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
-                      for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count")}
-    return meta
-
-
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_combine_kernels_use_no_scratch():
-    meta = kernel_meta()
+    meta = kernel_meta("combine_kernels.hip")
     combine = {k: v for k, v in meta.items() if "k_combine_eval" in k}
     assert len(combine) == 2, sorted(meta)
     for name, m in combine.items():

@@ -1,45 +1,22 @@
 """The kernels of the permutation quotient (quotient_kernels.hip: k_pq_constraints, k_pq_pad_twist) are the unit's only kernels,
 use no scratch memory and no LDS, spill no register and keep their pinned VGPR counts: checked in the compiler's resource metadata
-for gfx950.  The unit is plain HIP C++, without inline assembly.  CPU only (hipcc cross-compiles); the assembly is cached under
-csrc/build/ keyed by the hash of the sources.
+for gfx950.  The unit is plain HIP C++, without inline assembly.  CPU only (hipcc cross-compiles); the assembly comes from
+tests/isa_cache.py.
 
 The goal was <= 160 VGPRs (resident beside another slot's accumulation kernel: 512 - 2 x 176).  Both kernels meet it: the columns
 of k_pq_constraints are walked by a loop that is not unrolled, so its register state does not grow with t."""
-import hashlib
 import os
 import re
-import subprocess
 
-import pytest
+from isa_cache import CSRC, kernel_meta, requires_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
 UNIT = "quotient_kernels.hip"
 VGPRS = {"k_pq_constraintsE": 103, "k_pq_pad_twistE": 56}  # as found ("E": the end of the mangled name)
 
 
-def kernel_meta():
-    h = hashlib.sha256()
-    for f in (UNIT, "fr30.hip.h", "engine.h"):
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "quotient_kernels_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, UNIT), "-o", out], check=True, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {}
-    for block in asm[asm.index("amdhsa.kernels:"):].split("\n  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
-                      for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count",
-                                  "group_segment_fixed_size")}
-    return meta
-
-
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_quotient_kernels_are_listed_and_use_no_scratch():
-    meta = kernel_meta()
+    meta = kernel_meta(UNIT)
     assert len(meta) == len(VGPRS), sorted(meta)
     for want, vgprs in VGPRS.items():
         found = [k for k in meta if want in k]

@@ -1,40 +1,12 @@
 """The recovery kernels (recover_kernels.hip) use no scratch, spill no registers and stay within 160 VGPRs, so that they can
 run on one slot beside another slot's accumulation kernel: checked in the compiler's metadata for gfx950.  CPU only (hipcc
-cross-compiles); the assembly is cached under csrc/build/ keyed by the hash of the sources."""
-import hashlib
-import os
-import re
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
-SOURCES = ("recover_kernels.hip", "fr30.hip.h", "engine.h")
+cross-compiles); the assembly comes from tests/isa_cache.py."""
+from isa_cache import kernel_meta, requires_hipcc
 
 
-def kernel_meta():
-    h = hashlib.sha256()
-    for f in SOURCES:
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "recover_kernels_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, "recover_kernels.hip"), "-o", out], check=True,
-                       stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {}
-    for block in asm[asm.index("amdhsa.kernels:"):].split("\n  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
-                      for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count")}
-    return meta
-
-
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_recover_kernels_fit_beside_accumulation():
-    meta = kernel_meta()
+    meta = kernel_meta("recover_kernels.hip")
     rec = {k: v for k, v in meta.items() if "k_rec_" in k}
     assert len(rec) == 7, sorted(meta)
     for name, m in rec.items():

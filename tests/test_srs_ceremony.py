@@ -1,11 +1,9 @@
 """Powers-of-tau ceremonies, host side: kzg_g2_mul against the pairing twin, kzg_srs_verify_update on
 links made with the oracle, the split oracle, the constants that srs_update_kernels.hip restates, and the compiler's metadata
 of its kernels.  No GPU involved."""
-import hashlib
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,9 +12,8 @@ import bigint_twin as T
 import kzg_poly_commit_exploration_amd as K
 import pairing_twin as PT
 import srs_ceremony_oracle as SO
+from isa_cache import CSRC, kernel_meta, requires_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kzg_poly_commit_exploration_amd", "csrc")
 R, P = T.R, T.P
 R_FP = 1 << 384
 
@@ -156,31 +153,9 @@ def test_restated_constants_match():
 
 
 # ---- the compiler's metadata of the new kernels (as tests/test_verify_cells_isa.py) ------------------------------------------
-FLAGS = ["-DKZG_LAZY_FP", "-DKZG_FIPS_SQR", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S"]
-SOURCES = ("srs_update_kernels.hip", "fr30.hip.h", "engine.h", "g1_30.hip.h", "field30.hip.h")
-
-
-def kernel_meta():
-    h = hashlib.sha256()
-    for f in SOURCES:
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    out = os.path.join(CSRC, "build", "srs_update_kernels_%s.s" % h.hexdigest()[:16])
-    if not os.path.exists(out):
-        subprocess.run(["hipcc"] + FLAGS + [os.path.join(CSRC, "srs_update_kernels.hip"), "-o", out], check=True,
-                       stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {}
-    for block in asm[asm.index("amdhsa.kernels:"):].split("\n  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))
-                      for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count")}
-    return meta
-
-
-@pytest.mark.skipif(subprocess.run(["which", "hipcc"], capture_output=True).returncode != 0, reason="no hipcc")
+@requires_hipcc
 def test_srs_update_kernels_use_no_scratch():
-    meta = kernel_meta()
+    meta = kernel_meta("srs_update_kernels.hip")
     rec = {k: v for k, v in meta.items() if "k_srs_update" in k or "k_srs_check" in k}
     assert len(rec) == 2, sorted(meta)
     for name, m in rec.items():

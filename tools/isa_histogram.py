@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction histogram of k_bucket_accumulate's main loop from the compiler's assembly, priced with the issue costs
 tools/instr_rates measured on the MI355X (profiles/r03_instr_rates.jsonl, 2 waves per SIMD).
-  hipcc -DKZG_LAZY_FP -DKZG_FIPS_SQR -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S msm_accum.hip -o accum.s
+  hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S msm_accum.hip -o accum.s
   python3 tools/isa_histogram.py accum.s profiles/r03_instr_rates.jsonl > profiles/r03_accum_isa_histogram.txt"""
 import collections
 import json

@@ -774,6 +774,104 @@ int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* 
 int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
                              const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof);
 
+/* ---- a circuit with a lookup table: the LogUp term of the quotient -------------------------------------
+ * Notation as in the sections above.  A lookup circuit keeps, beside the 2 t + 2 columns of kzg_circuit_create, c table columns
+ * tab_0 .. tab_(c-1) (1 <= c <= t, n values each) and one lookup selector q_K.  STATEMENT: for every row i the tuple
+ * q_K[i] (f_0[i], .., f_(c-1)[i]) is a row of the table.  A row with q_K = 0 looks up the zero tuple, which the table must then
+ * hold: that is the circuit author's obligation.  With challenges theta and beta:
+ *     F(X) = beta + q_K(X) sum_(j<c) theta^j f_j(X)         Tt(X) = beta + sum_(j<c) theta^j tab_j(X)
+ *     f_i = F_i - beta, T_i = Tt_i - beta over H;  m = the multiplicities of the column f in the column T by
+ *         kzg_lookup_multiplicities' rule (k = 1, n_table = n: the count sits at the LEAST row holding the value)
+ *     phi_0 = 0, phi_(i+1) = phi_i + 1 / (beta + f_i) - m_i / (beta + T_i)   (kzg_lookup_sum, k = 1); phi_n must be 0
+ *     Lk1 = (phi(w X) - phi(X)) F Tt - Tt + m F             Lk2 = L_0 phi
+ *     G'  = alpha^3 Lk1 + alpha^4 Lk2,   Num_L = Num (of kzg_circuit_quotient, no caller's term) + G',   T = Num_L / (X^n - 1).
+ * deg G' = 4 (n - 1), hence the shape rules e >= max(t + 1, 4) and 3 t + e + c + 5 <= 32 (the columns a last round combines at
+ * zeta).  These calls are the pieces of a proof; nothing in them is blinded, so what is built from them is NOT zero-knowledge.
+ *
+ * kzg_circuit_create_lookup is kzg_circuit_create with the table (c columns of n values, column j at table + 4 j table_stride u64)
+ * and q_lookup (n values): the c + 1 columns are resident as values, coefficients and coset values behind the others, in the
+ * order tab_0 .. tab_(c-1), q_K, and out_key_p1s (NULL, or (2 t + c + 3) x 18 u64) receives kzg_circuit_create's commitments and
+ * then theirs, each bit for bit kzg_commit_evaluations of the column.  Device memory: kzg_circuit_create's with 2 t + c + 3 columns
+ * in place of 2 t + 2.  Every call that takes a circuit accepts the handle and ignores the table.  KZG_ERR_INVALID_ARG:
+ * kzg_circuit_create's rules, c < 1, c > t, 2^log_ext < 4, 3 t + 2^log_ext + c + 5 > 32, table_stride < n, a NULL table or q_lookup.
+ * kzg_circuit_column_device hands the columns out as KZG_CIRCUIT_COL_TABLE + j (j < c) and KZG_CIRCUIT_COL_QLOOKUP; on a circuit
+ * without a table these are KZG_ERR_INVALID_ARG.
+ *
+ * kzg_circuit_lookup_columns computes the per-proof columns on the device: wires as kzg_circuit_quotient takes them (the first c
+ * columns are read) -> out_f and out_table (NULL, or n x 4 u64: the folded columns f and T), out_mult (m), out_phi (phi_0 ..
+ * phi_(n-1)) and out_last (phi_n), canonical blst_fr.  Needs no SRS.  KZG_ERR_INVALID_ARG with *bad_row (may be NULL) = the least
+ * row when a folded tuple is in no table row or a denominator beta + f_i, beta + T_i is zero, with kzg_lookup_multiplicities' and
+ * kzg_lookup_sum's messages; else *bad_row = (size_t)-1.  Also KZG_ERR_INVALID_ARG: a NULL required pointer, a circuit without a
+ * table or of another context, stride < n.  On a multi-device context the call runs on devices[0].
+ *
+ * kzg_circuit_lookup_quotient is kzg_circuit_quotient with the lookup's term in place of the caller's: mult and phi (n values
+ * each, as kzg_circuit_lookup_columns returned them) are extended with the wires, G' is computed on the coset, and T, its
+ * outputs, statuses and multi-device rules are kzg_circuit_quotient's.  beta is the lookup's beta and the permutation's.
+ * KZG_ERR_REMAINDER also when m or phi are not those of the wires, or phi_n != 0.
+ *
+ * THE PROOF.  Last round: with the new evaluations tbar_j = tab_j(zeta), qbar = q_K(zeta), phiw = phi(zeta w), Fbar = beta + qbar
+ * sum_j theta^j abar_j, Tbar = beta + sum_j theta^j tbar_j, l = L_0(zeta) and r the polynomial of kzg_circuit_open formed with this T,
+ *     r_L(X) = r(X) + (alpha^4 l - alpha^3 Fbar Tbar) phi(X) + alpha^3 Fbar m(X) + alpha^3 (phiw Fbar Tbar - Tbar),
+ * and the opening is kzg_open_sets over the 2 t + c + 3 polynomials
+ *     [ r_L | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z | tab_0 .. tab_(c-1) | q_K | phi ],
+ * z and phi in the set {zeta w}, the rest in {zeta}, gamma := v.  Transcript: SHA-256 with the encodings of kzg_circuit_prove and a
+ * domain of its own, so that no plain proof parses as a lookup proof:
+ *     DST = ASCII "kzg_mi355x/plonk-lookup/v1"
+ *     h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(c) | u64be(n_public) | shifts (t x 32)
+ *                 | key commitments ((2 t + c + 3) x 48, kzg_circuit_create_lookup's order) | public inputs)
+ *     h1 = SHA256(h0 | wire commitments)     theta = fr(SHA256(h1 | 00))
+ *     h2 = SHA256(h1 | [m])                  beta = fr(SHA256(h2 | 00)), gamma = fr(SHA256(h2 | 01))
+ *     h3 = SHA256(h2 | [z] | [phi])          alpha = fr(SHA256(h3 | 00))
+ *     h4 = SHA256(h3 | [T_0] .. [T_(e-2)])   zeta = fr(SHA256(h4 | 00))
+ *     h5 = SHA256(h4 | evaluations)          v = fr(SHA256(h5 | 00))
+ * Proof bytes, in order: the t wire commitments, [m], [z], [phi], the e - 1 chunk commitments (48 bytes each), the 2 t + c + 2
+ * evaluations abar_0.., sbar_0 .. sbar_(t-2), z(zeta w), tbar_0.., qbar, phiw (32 bytes each), W: 48 (t + e + 3) + 32 (2 t + c + 2)
+ * bytes (kzg_circuit_lookup_proof_size), 832 at t = 3, e = 4, c = 3.  Every commitment is bit for bit kzg_commit_evaluations of its
+ * column.  LOOKUP PROOFS ARE PLAIN: neither the wires nor z, phi, m or T are blinded, so these proofs are NOT zero-knowledge.
+ *
+ * kzg_circuit_lookup_prove: host wires, synchronous, one stream slot; key_p1s the (2 t + c + 3) x 18 u64 of
+ * kzg_circuit_create_lookup; public_inputs the first n_public values of PI (the rest zero), or NULL with n_public = 0; out_proof
+ * receives kzg_circuit_lookup_proof_size bytes.  Rounds: the wires, then theta; the folded columns, the multiplicities, [m], then
+ * beta and gamma; phi and z, both committed, then alpha; the quotient; the opening.  Statuses, in this order:
+ * KZG_ERR_INVALID_ARG (a NULL required pointer, a circuit without a table or of another context, stride < n, n_public > n, a public
+ * input not below r); KZG_ERR_NO_SRS; KZG_ERR_DEGREE_TOO_HIGH (the SRS has fewer than n points); KZG_ERR_REMAINDER with *bad_row
+ * (may be NULL) = the least row whose tuple is not in the table, and kzg_last_error naming the row; the running sum's status for
+ * a zero denominator (KZG_ERR_INVALID_ARG, its message, *bad_row the row); KZG_ERR_REMAINDER for z_n != 1, phi_n != 0, a quotient
+ * that leaves a remainder, or r_L(zeta) != 0.  Else *bad_row = (size_t)-1.  A failed call writes nothing to out_proof and leaves the
+ * context serving.  Multi-device rules are kzg_circuit_prove's.  The _device form takes the wires in a kzg_dev_alloc buffer of a
+ * single-device context.
+ *
+ * Host only, no context: kzg_circuit_lookup_proof_size; kzg_circuit_lookup_proof_challenges (out: 6 x 4 u64, theta, beta, gamma,
+ * alpha, zeta, v as blst_fr, from complete proof bytes; nothing is decoded); kzg_circuit_lookup_verify_proof, whose argument and
+ * decode rules are kzg_circuit_verify_proof's: bytes that do not decode give KZG_OK with *valid = 0, there is no subgroup check.
+ * [r_L] is formed from the key, [z], [m], [phi] and the [T_c] and handed to kzg_verify_sets. */
+int kzg_circuit_lookup_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row);
+int kzg_circuit_lookup_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                    size_t stride, const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof,
+                                    size_t* bad_row);
+int kzg_circuit_lookup_proof_size(size_t t, unsigned log_ext, size_t c, size_t* bytes);
+int kzg_circuit_lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c,
+                                        const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
+                                        size_t proof_len, uint64_t* out);
+int kzg_circuit_lookup_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
+                                    const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                                    int* valid);
+#define KZG_CIRCUIT_COL_TABLE 64
+#define KZG_CIRCUIT_COL_QLOOKUP 80
+int kzg_circuit_create_lookup(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
+                              const uint64_t* sigmas, size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext,
+                              const uint64_t* table, size_t c, size_t table_stride, const uint64_t* q_lookup,
+                              uint64_t* out_key_p1s /* (2t+c+3)x18 */, kzg_circuit** out);
+int kzg_circuit_lookup_columns(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t theta[4],
+                               const uint64_t beta[4], uint64_t* out_f, uint64_t* out_table, uint64_t* out_mult, uint64_t* out_phi,
+                               uint64_t out_last[4], size_t* bad_row);
+int kzg_circuit_lookup_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                const uint64_t* mult, const uint64_t* phi, const uint64_t* public_inputs, const uint64_t alpha[4],
+                                const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], uint64_t* out_coeffs,
+                                uint64_t* out_p1s);
+
 /* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
  * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the
  * gate and the permutation are computed from the same values as without blinding, and kzg_circuit_verify accepts a blinded proof

@@ -23,6 +23,8 @@ __all__ = [
     "Circuit", "circuit_verify", "circuit_blinders", "circuit_blinded_sizes", "circuit_proof_size", "circuit_proof_challenges", "circuit_verify_proof",
     "KZG_CIRCUIT_MIN_COLUMNS", "KZG_CIRCUIT_COL_QLIN", "KZG_CIRCUIT_COL_QM", "KZG_CIRCUIT_COL_QC", "KZG_CIRCUIT_COL_SIGMA",
     "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
+    "KZG_CIRCUIT_COL_TABLE", "KZG_CIRCUIT_COL_QLOOKUP",
+    "circuit_lookup_proof_size", "circuit_lookup_proof_challenges", "circuit_lookup_verify_proof",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
@@ -90,6 +92,9 @@ ABI_SYMBOLS = [
     "kzg_ntt_batch", "kzg_ntt_batch_device", "kzg_ntt_batch_rounds",
     "kzg_circuit_proof_size", "kzg_circuit_proof_challenges", "kzg_circuit_verify_proof",
     "kzg_circuit_prove", "kzg_circuit_prove_device",
+    "kzg_circuit_create_lookup", "kzg_circuit_lookup_columns", "kzg_circuit_lookup_quotient",
+    "kzg_circuit_lookup_prove", "kzg_circuit_lookup_prove_device", "kzg_circuit_lookup_proof_size",
+    "kzg_circuit_lookup_proof_challenges", "kzg_circuit_lookup_verify_proof",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -108,6 +113,7 @@ KZG_EXTEND_VALUES, KZG_EXTEND_COEFFS = 0, 1
 KZG_CIRCUIT_MIN_COLUMNS = 2  # wire columns of a circuit with the built-in arithmetic gate (f_0 f_1 needs two)
 KZG_CIRCUIT_COL_QLIN, KZG_CIRCUIT_COL_QM, KZG_CIRCUIT_COL_QC, KZG_CIRCUIT_COL_SIGMA, KZG_CIRCUIT_COL_L0 = 0, 16, 17, 32, 48
 KZG_CIRCUIT_VALUES, KZG_CIRCUIT_COEFFS, KZG_CIRCUIT_COSET = 0, 1, 2
+KZG_CIRCUIT_COL_TABLE, KZG_CIRCUIT_COL_QLOOKUP = 64, 80  # the columns of a lookup circuit (kzg_circuit_create_lookup)
 KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
@@ -243,6 +249,14 @@ def load_library():
         "kzg_permutation_quotient": (i, [vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.c_uint, vp, vp]),
         "kzg_circuit_create": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, C.POINTER(vp)]),
         "kzg_circuit_destroy": (i, [vp, vp]),
+        "kzg_circuit_create_lookup": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, sz, sz, vp, vp, C.POINTER(vp)]),
+        "kzg_circuit_lookup_columns": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "kzg_circuit_lookup_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_lookup_prove": (i, [vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_circuit_lookup_prove_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_circuit_lookup_proof_size": (i, [sz, C.c_uint, sz, C.POINTER(sz)]),
+        "kzg_circuit_lookup_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp]),
+        "kzg_circuit_lookup_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
         "kzg_circuit_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_quotient_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_column_device": (i, [vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(sz)]),
@@ -1568,6 +1582,30 @@ class Engine:
                                                     None if p1s is None else _ptr(p1s), C.byref(h)))
         return Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
 
+    def circuit_create_lookup(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, table, q_lookup, n=None, want_key=True):
+        """kzg_circuit_create_lookup: circuit_create's arguments, table a (c, table_stride, 4) array whose first n rows per column
+        count and q_lookup an (n, 4) array -> a Circuit with c table columns; its key has 2 t + c + 3 commitments, circuit_create's
+        and then tab[0..c), q_K"""
+        a, t, stride, n = self._columns(q_lin, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        qm = np.ascontiguousarray(q_mul, dtype=np.uint64).reshape(-1, 4)
+        qc = np.ascontiguousarray(q_const, dtype=np.uint64).reshape(-1, 4)
+        tb = np.ascontiguousarray(table, dtype=np.uint64)
+        assert tb.ndim == 3 and tb.shape[2] == 4 and tb.shape[1] >= n
+        qk = np.ascontiguousarray(q_lookup, dtype=np.uint64).reshape(-1, 4)
+        assert qm.shape[0] >= n and qc.shape[0] >= n and qk.shape[0] >= n
+        sh = np.ascontiguousarray([k.limbs() for k in shifts], dtype=np.uint64).reshape(-1, 4)
+        assert sh.shape[0] == t, "one coset shift per column"
+        c = tb.shape[0]
+        p1s = np.zeros((2 * t + c + 3, 18), dtype=np.uint64) if want_key else None
+        h = C.c_void_p()
+        self._pq_check(self._lib.kzg_circuit_create_lookup(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh), log_ext,
+                                                           _ptr(tb), c, tb.shape[1], _ptr(qk), None if p1s is None else _ptr(p1s),
+                                                           C.byref(h)))
+        circ = Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
+        circ.c = c
+        return circ
+
     # -- zero-knowledge blinding (DESIGN.md 4.24) --
     def blind_evaluations_limbs(self, evals, blinders, n=None):
         """kzg_blind_evaluations: evals a (k, stride, 4) array of values over H whose first n rows per column count, blinders a
@@ -1722,6 +1760,7 @@ class Circuit:
     def __init__(self, engine, handle, n, t, log_ext, key):
         self._eng, self._c = engine, handle
         self.n, self.t, self.log_ext, self.key = n, t, log_ext, key
+        self.c = 0  # table columns (circuit_create_lookup)
 
     def close(self):
         if getattr(self, "_c", None) and getattr(self._eng, "_h", None):
@@ -1911,6 +1950,73 @@ class Circuit:
                                                            _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(ch[3]), _ptr(ch[4]), _ptr(b),
                                                            _ptr(ev), _ptr(p1)))
         return self._split_evals(ev), G1Point(p1)
+
+    # -- the lookup argument of a circuit with a table --
+    def lookup_columns(self, wires, theta, beta, n=None, engine=None):
+        """kzg_circuit_lookup_columns: wires as quotient() takes them -> (f, T, m, phi) as (n, 4) arrays and phi_n as a Scalar.
+        KzgError(KZG_ERR_INVALID_ARG) carries .bad_row for a tuple outside the table or a zero denominator"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        th, bl = theta.limbs(), beta.limbs()
+        f, tb, m, phi = (np.zeros((n, 4), dtype=np.uint64) for _ in range(4))
+        last = np.zeros(4, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        try:
+            e._pq_check(e._lib.kzg_circuit_lookup_columns(e._h, self._c, _ptr(a), stride, _ptr(th), _ptr(bl), _ptr(f), _ptr(tb), _ptr(m),
+                                                          _ptr(phi), _ptr(last), C.byref(bad)))
+        except KzgError as err:
+            err.bad_row = None if bad.value == C.c_size_t(-1).value else int(bad.value)
+            raise
+        return f, tb, m, phi, Scalar.from_limbs(last)
+
+    def lookup_quotient(self, wires, z, mult, phi, alpha, beta, gamma, theta, public_inputs=None, n=None, want_coeffs=True,
+                        want_commitments=True, engine=None):
+        """kzg_circuit_lookup_quotient: quotient() without a gate, with the lookup's term made from mult and phi (the (n, 4) arrays
+        of lookup_columns) -> as quotient()"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz, mm, pp = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (z, mult, phi))
+        assert zz.shape[0] >= n and mm.shape[0] >= n and pp.shape[0] >= n
+        N = n << self.log_ext
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert pi is None or pi.shape[0] >= n
+        al, bl, gl, th = alpha.limbs(), beta.limbs(), gamma.limbs(), theta.limbs()
+        coeffs = np.zeros((N - n, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros(((1 << self.log_ext) - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_lookup_quotient(e._h, self._c, _ptr(a), stride, _ptr(zz), _ptr(mm), _ptr(pp),
+                                                       None if pi is None else _ptr(pi), _ptr(al), _ptr(bl), _ptr(gl), _ptr(th),
+                                                       None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def _lookup_prove(self, fn, e, wires_arg, stride, public_inputs):
+        assert self.key is not None and len(self.key) == 2 * self.t + self.c + 3, "lookup_prove: the key of circuit_create_lookup"
+        rows = np.ascontiguousarray(np.stack([c.p1 for c in self.key]), dtype=np.uint64)
+        pub = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(circuit_lookup_proof_size(self.t, self.log_ext, self.c), dtype=np.uint8)
+        bad = C.c_size_t(0)
+        try:
+            e._pq_check(fn(e._h, self._c, _ptr(rows), wires_arg, stride, None if pub is None else _ptr(pub),
+                           0 if pub is None else pub.shape[0], _ptr(out), C.byref(bad)))
+        except KzgError as err:
+            err.bad_row = None if bad.value == C.c_size_t(-1).value else int(bad.value)
+            raise
+        return out.tobytes()
+
+    def lookup_prove(self, wires, public_inputs=None, n=None, engine=None):
+        """kzg_circuit_lookup_prove: wires a (t, stride, 4) array, public_inputs None or the (n_public, 4) values of rows
+        [0, n_public) -> the proof bytes (circuit_lookup_proof_size of them); NOT zero-knowledge.  A KzgError carries .bad_row"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        return self._lookup_prove(e._lib.kzg_circuit_lookup_prove, e, _ptr(a), stride, public_inputs)
+
+    def lookup_prove_device(self, d_wires, public_inputs=None, stride=None):
+        """kzg_circuit_lookup_prove_device: the wires in a device buffer of the circuit's (single-device) context"""
+        e = self._eng
+        return self._lookup_prove(e._lib.kzg_circuit_lookup_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
+                                  public_inputs)
 
     def column_device(self, which, form):
         """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
@@ -2163,6 +2269,46 @@ def circuit_verify_proof(key, n, log_ext, shifts, public_inputs, proof, setup_g1
     ok = C.c_int(0)
     _check(load_library().kzg_circuit_verify_proof(_ptr(rows), n, t, log_ext, _ptr(ks), _ptr(pub) if pub is not None else None, n_public,
                                                    _ptr(buf), buf.shape[0], _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def circuit_lookup_proof_size(t, log_ext, c):
+    """kzg_circuit_lookup_proof_size: the bytes of a lookup proof, 48 (t + 2^log_ext + 3) + 32 (2 t + c + 2)"""
+    out = C.c_size_t(0)
+    _check(load_library().kzg_circuit_lookup_proof_size(t, log_ext, c, C.byref(out)))
+    return out.value
+
+
+def _lookup_proof_statement(key, c, shifts, public_inputs, proof):
+    t = len(shifts)
+    assert len(key) == 2 * t + c + 3
+    rows = np.ascontiguousarray(np.stack([k.p1 for k in key]), dtype=np.uint64)
+    pub = list(public_inputs) if public_inputs is not None else []
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    return t, rows, _scalar_rows(shifts), (_scalar_rows(pub) if pub else None), len(pub), buf
+
+
+def circuit_lookup_proof_challenges(key, n, log_ext, c, shifts, public_inputs, proof):
+    """kzg_circuit_lookup_proof_challenges: (theta, beta, gamma, alpha, zeta, v) of the hashed transcript from complete proof
+    bytes.  key: the 2 t + c + 3 commitments of circuit_create_lookup; nothing is decoded."""
+    t, rows, ks, pub, n_public, buf = _lookup_proof_statement(key, c, shifts, public_inputs, proof)
+    out = np.zeros((6, 4), dtype=np.uint64)
+    _check(load_library().kzg_circuit_lookup_proof_challenges(_ptr(rows), n, t, log_ext, c, _ptr(ks),
+                                                              _ptr(pub) if pub is not None else None, n_public, _ptr(buf), buf.shape[0],
+                                                              _ptr(out)))
+    return tuple(Scalar.from_limbs(out[i]) for i in range(6))
+
+
+def circuit_lookup_verify_proof(key, n, log_ext, c, shifts, public_inputs, proof, setup_g1, setup_g2):
+    """kzg_circuit_lookup_verify_proof on the host: decodes the proof bytes, derives the challenges, forms [r_L], checks the
+    opening.  False also for bytes that do not decode (points are checked to lie on the curve, not in the subgroup)."""
+    t, rows, ks, pub, n_public, buf = _lookup_proof_statement(key, c, shifts, public_inputs, proof)
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 1 and g2.shape[0] >= 3
+    ok = C.c_int(0)
+    _check(load_library().kzg_circuit_lookup_verify_proof(_ptr(rows), n, t, log_ext, c, _ptr(ks), _ptr(pub) if pub is not None else None,
+                                                          n_public, _ptr(buf), buf.shape[0], _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

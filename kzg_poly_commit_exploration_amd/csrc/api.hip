@@ -367,19 +367,22 @@ struct kzg_ctx {
 
 // A circuit's key: the 2 t + 2 columns q_lin[0..t), q_mul, q_const, sigma[0..t) in that order, in three
 // forms, every one as blst_fr images and every buffer the circuit's own, written by kzg_circuit_create and read-only afterwards.
+// A lookup circuit (kzg_circuit_create_lookup, section 4.26) keeps c_tab + 1 more columns behind them, tab[0..c_tab) and q_K,
+// which every call of section 4.22 .. 4.25 ignores.
 // `owner` is the single-device context it lives on (devices[0]'s for a multi-device context).
 struct kzg_circuit {
     kzg_ctx* owner = nullptr;
     uint32_t lg_n = 0, lg_ext = 0;
     size_t n = 0, t = 0;
+    size_t c_tab = 0;  // table columns of a lookup circuit, 0: none
     uint64_t shifts[4 * kPqMaxColumns] = {};
-    DevBuf values;  // (2 t + 2) x n
-    DevBuf coeffs;  // (2 t + 2) x n
-    DevBuf coset;   // (2 t + 2) x N
+    DevBuf values;  // cols() x n
+    DevBuf coeffs;  // cols() x n
+    DevBuf coset;   // cols() x N
     DevBuf l0;      // the N values of L_0 on the coset
     DevBuf zinv;    // the rot stored multipliers 1 / Z_H(x_i): the circuit's own copy, independent of pq_zinv_key
     size_t N() const { return n << lg_ext; }
-    size_t cols() const { return 2 * t + 2; }
+    size_t cols() const { return 2 * t + 2 + (c_tab ? c_tab + 1 : 0); }
 };
 
 namespace {
@@ -4186,6 +4189,15 @@ static int lu_host(kzg_ctx* ctx, const LuCall& c, uint64_t* out, uint64_t out_la
 static bool lu_overlaps(const void* out, size_t out_bytes, const void* in, size_t in_bytes) {
     return in && (const char*)out < (const char*)in + in_bytes && (const char*)in < (const char*)out + out_bytes;
 }
+// a call on device columns on a slot the caller holds, with the context's mutex (*lk): the body of lu_device, and a step of the
+// circuit calls with a lookup table (section 4.26)
+static int lu_on_slot(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const LuCall& c, void* d_out, uint64_t out_last[4],
+                      size_t* bad_index) {
+    int rc = lu_slot_ready(ctx, s, c.n, 0, false);
+    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, c, (uint32_t*)d_out);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
+    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
+}
 static int lu_device(kzg_ctx* ctx, const LuCall& c, void* d_out, uint64_t out_last[4], size_t* bad_index) {
     const size_t span = ((c.t - 1) * c.stride + c.n) * 32, one = c.n * 32;  // bytes a column set covers, bytes of one column
     const bool columns = c.form != kLuInverse;
@@ -4199,11 +4211,7 @@ static int lu_device(kzg_ctx* ctx, const LuCall& c, void* d_out, uint64_t out_la
     const int slot = reserve_slot(ctx, lk, true);
     if (slot < 0) return KZG_ERR_BUSY;
     SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    int rc = lu_slot_ready(ctx, s, c.n, 0, false);
-    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, c, (uint32_t*)d_out);
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
-    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
+    return lu_on_slot(ctx, lk, ctx->slots[slot], c, d_out, out_last, bad_index);
 }
 
 int kzg_logderivative_sum(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_phi,
@@ -4318,6 +4326,36 @@ unsigned lu_default_log_capacity(size_t n_table) {
     while (((size_t)1 << lg) < 2 * n_table) lg++;
     return lg;
 }
+// The hash table and the kernels of one call on device columns, on the stream of a slot the caller holds with lookup_mu and the
+// context's mutex; the verdict is in the slot's gp_flags once the stream was waited for (lu_mult_verdict)
+int lu_mult_enqueue(kzg_ctx* ctx, Slot& s, const void* d_table, size_t n_table, const void* d_look, size_t n, size_t k, size_t stride,
+                    unsigned log_cap, void* d_mult, void* d_rows) {
+    const size_t cap = (size_t)1 << log_cap;
+    void *d_slots = nullptr, *d_counts = nullptr;
+    int rc = ctx->lu_ws.get(ctx, kLuWsSlots, (cap + 4) * 4, &d_slots);  // the slots, then the two flag words
+    if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsCounts, n_table * 4, &d_counts);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_slots, 0xff, (cap + 4) * 4, s.stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, n_table * 4, s.stream));
+    const LuHash h{(uint32_t*)d_slots, log_cap, (uint32_t*)d_counts, (uint32_t*)d_slots + cap};
+    launch_lookup_multiplicities(s.stream, (const uint32_t*)d_table, (uint32_t)n_table, (const uint32_t*)d_look, (uint32_t)n, (uint32_t)k,
+                                 stride, h, fr30_arg_from_mont256(fr_pow2(256)), (uint32_t*)d_mult, (uint32_t*)d_rows, s.gp_flags.dev());
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+int lu_mult_verdict(kzg_ctx* ctx, const Slot& s, size_t* bad_index) {
+    const uint32_t* f = s.gp_flags.host();
+    if (bad_index) *bad_index = f[0] == kLuNone ? (size_t)-1 : (size_t)f[0];
+    if (f[1] != kLuNone) {  // not reached with a capacity >= n_table
+        ctx->last_error = "lookup multiplicities: the hash table is full at table row " + std::to_string(f[1]);
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (f[0] != kLuNone) {
+        ctx->last_error = "lookup multiplicities: a value at row " + std::to_string(f[0]) + " of the lookup columns is in no table row";
+        return KZG_ERR_INVALID_ARG;
+    }
+    return KZG_OK;
+}
 int lu_multiplicities(kzg_ctx* ctx, const void* table, size_t n_table, const void* lookups, size_t n, size_t k, size_t stride, void* out_mult,
                       void* out_rows, size_t* bad_index, unsigned log_cap, bool device) {
     std::lock_guard<std::mutex> lkl(ctx->lookup_mu);
@@ -4330,10 +4368,7 @@ int lu_multiplicities(kzg_ctx* ctx, const void* table, size_t n_table, const voi
     LuDrain drain{s};
     int rc = ensure_slot_basics(ctx, s);
     if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
-    const size_t cap = (size_t)1 << log_cap;
-    void *d_slots = nullptr, *d_counts = nullptr, *d_table = (void*)table, *d_look = (void*)lookups, *d_mult = out_mult, *d_rows = out_rows;
-    if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsSlots, (cap + 4) * 4, &d_slots);  // the slots, then the two flag words
-    if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsCounts, n_table * 4, &d_counts);
+    void *d_table = (void*)table, *d_look = (void*)lookups, *d_mult = out_mult, *d_rows = out_rows;
     if (!device) {
         if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsTable, n_table * 32, &d_table);
         if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsLookups, k * n * 32, &d_look);
@@ -4342,32 +4377,15 @@ int lu_multiplicities(kzg_ctx* ctx, const void* table, size_t n_table, const voi
         if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, d_table, table, n_table * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (table)");
         if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, (uint32_t*)d_look, (const uint64_t*)lookups, n, k, stride);
     }
+    if (rc == KZG_OK) rc = lu_mult_enqueue(ctx, s, d_table, n_table, d_look, n, k, device ? stride : n, log_cap, d_mult, d_rows);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(d_slots, 0xff, (cap + 4) * 4, s.stream));
-    HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, n_table * 4, s.stream));
-    const LuHash h{(uint32_t*)d_slots, log_cap, (uint32_t*)d_counts, (uint32_t*)d_slots + cap};
-    launch_lookup_multiplicities(s.stream, (const uint32_t*)d_table, (uint32_t)n_table, (const uint32_t*)d_look, (uint32_t)n, (uint32_t)k,
-                                 device ? stride : n, h, fr30_arg_from_mont256(fr_pow2(256)), (uint32_t*)d_mult, (uint32_t*)d_rows,
-                                 s.gp_flags.dev());
-    HIP_TRY(ctx, hipGetLastError());
     if (!device) {
         rc = copy_unlocked(ctx, lk, s.stream, out_mult, d_mult, n_table * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (multiplicities)");
         if (rc == KZG_OK && out_rows)
             rc = copy_unlocked(ctx, lk, s.stream, out_rows, d_rows, k * n * 4, hipMemcpyDeviceToHost, "hipMemcpyAsync (rows)");
     }
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "lookup multiplicities");
-    if (rc) return rc;
-    const uint32_t* f = s.gp_flags.host();
-    if (bad_index) *bad_index = f[0] == kLuNone ? (size_t)-1 : (size_t)f[0];
-    if (f[1] != kLuNone) {  // not reached with a capacity >= n_table
-        ctx->last_error = "lookup multiplicities: the hash table is full at table row " + std::to_string(f[1]);
-        return KZG_ERR_INVALID_ARG;
-    }
-    if (f[0] != kLuNone) {
-        ctx->last_error = "lookup multiplicities: a value at row " + std::to_string(f[0]) + " of the lookup columns is in no table row";
-        return KZG_ERR_INVALID_ARG;
-    }
-    return KZG_OK;
+    return rc ? rc : lu_mult_verdict(ctx, s, bad_index);
 }
 }  // namespace
 
@@ -5748,6 +5766,8 @@ static size_t circuit_column_index(const kzg_circuit* c, unsigned which) {
     if (which == KZG_CIRCUIT_COL_QM) return c->t;
     if (which == KZG_CIRCUIT_COL_QC) return c->t + 1;
     if (which >= KZG_CIRCUIT_COL_SIGMA && which < KZG_CIRCUIT_COL_SIGMA + c->t) return c->t + 2 + (which - KZG_CIRCUIT_COL_SIGMA);
+    if (which >= KZG_CIRCUIT_COL_TABLE && which < KZG_CIRCUIT_COL_TABLE + c->c_tab) return 2 * c->t + 2 + (which - KZG_CIRCUIT_COL_TABLE);
+    if (which == KZG_CIRCUIT_COL_QLOOKUP && c->c_tab) return 2 * c->t + 2 + c->c_tab;
     return (size_t)-1;
 }
 // is `c` a circuit alive on the single-device context `ctx` (quotient_mu held)?
@@ -5763,8 +5783,14 @@ static int circuit_foreign(kzg_ctx* ctx) {
 // on failure.  The frame is the caller's, because quotient_mu has to outlast this body (the list of circuits): the context's
 // mutex and the slot are therefore held until kzg_circuit_create returns -- on failure across the drain and the hipFree of c's
 // buffers, which take no lock
+struct CircuitTable {  // the columns of a lookup circuit (section 4.26): c table columns at a stride and q_K, or c = 0
+    const uint64_t* table = nullptr;
+    size_t c = 0, stride = 0;
+    const uint64_t* q_lookup = nullptr;
+};
 static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul,
-                         const uint64_t* q_const, const uint64_t* sigmas, size_t stride, uint64_t* out_key_p1s) {
+                         const uint64_t* q_const, const uint64_t* sigmas, size_t stride, const CircuitTable& tab,
+                         uint64_t* out_key_p1s) {
     call.lock();
     const size_t n = sh.n, N = sh.N, t = c->t, ncols = c->cols();
     int rc = pq_srs_status(ctx, out_key_p1s != nullptr, n);
@@ -5785,6 +5811,8 @@ static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqSha
     if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * t * n, q_mul, n, 1, n);
     if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (t + 1) * n, q_const, n, 1, n);
     if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (t + 2) * n, sigmas, n, t, stride);
+    if (rc == KZG_OK && tab.c) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (2 * t + 2) * n, tab.table, n, tab.c, tab.stride);
+    if (rc == KZG_OK && tab.c) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (2 * t + 2 + tab.c) * n, tab.q_lookup, n, 1, n);
     if (rc) return rc;
     // values -> coefficients (the inverse transform the extension needs anyway, kept) -> the coset
     const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
@@ -5812,6 +5840,37 @@ static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqSha
     return pq_commit_chunks(ctx, lk, call.slot(), d_coef, n, ncols, out_key_p1s);
 }
 
+// the shape rules of a lookup circuit (section 4.26): 1 <= c <= t, deg G' = 4 (n - 1) asks for e >= 4, and the last round's
+// combination at zeta has 3 t + e + c + 5 columns
+static bool lookup_shape_ok(size_t t, size_t e, size_t c) {
+    return c >= 1 && c <= t && e >= 4 && e >= t + 1 && 3 * t + e + c + 5 <= kLinMaxColumns;
+}
+// kzg_circuit_create and kzg_circuit_create_lookup (tab.c != 0) after their argument checks, on a single-device context
+static int circuit_create_impl(kzg_ctx* ctx, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
+                               const uint64_t* sigmas, size_t t, size_t stride, const uint64_t* shifts, const CircuitTable& tab,
+                               uint64_t* out_key_p1s, kzg_circuit** out) {
+    const size_t n = sh.n;
+    PqCall call(ctx);
+    kzg_circuit* c = new kzg_circuit();
+    c->owner = ctx;
+    c->lg_n = sh.lg_n;
+    c->lg_ext = sh.lg_ext;
+    c->n = n;
+    c->t = t;
+    c->c_tab = tab.c;
+    std::memcpy(c->shifts, shifts, 32 * t);
+    int rc = circuit_build(ctx, call, c, sh, q_lin, q_mul, q_const, sigmas, stride, tab, out_key_p1s);
+    if (rc) {
+        (void)hipSetDevice(ctx->device);
+        call.drain();  // (nothing enqueued still writes to the buffers that go with c)
+        delete c;
+        return rc;
+    }
+    ctx->circuits.push_back(c);
+    *out = c;
+    return KZG_OK;
+}
+
 int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
                        size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, uint64_t* out_key_p1s,
                        kzg_circuit** out) {
@@ -5825,24 +5884,26 @@ int kzg_circuit_create(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mu
         if (!kid) return KZG_ERR_INVALID_ARG;
         return forwarded(ctx, kid, kzg_circuit_create(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, out_key_p1s, out));
     }
-    PqCall call(ctx);
-    kzg_circuit* c = new kzg_circuit();
-    c->owner = ctx;
-    c->lg_n = sh.lg_n;
-    c->lg_ext = sh.lg_ext;
-    c->n = n;
-    c->t = t;
-    std::memcpy(c->shifts, shifts, 32 * t);
-    int rc = circuit_build(ctx, call, c, sh, q_lin, q_mul, q_const, sigmas, stride, out_key_p1s);
-    if (rc) {
-        (void)hipSetDevice(ctx->device);
-        call.drain();  // (nothing enqueued still writes to the buffers that go with c)
-        delete c;
-        return rc;
+    return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, CircuitTable{}, out_key_p1s, out);
+}
+
+int kzg_circuit_create_lookup(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                              size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, const uint64_t* table, size_t c,
+                              size_t table_stride, const uint64_t* q_lookup, uint64_t* out_key_p1s, kzg_circuit** out) {
+    if (out) *out = nullptr;
+    PqShape sh;
+    if (!ctx || !out || log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS ||
+        t > kPqMaxColumns || !lookup_shape_ok(t, sh.rot, c) || stride < n || table_stride < n || !q_lin || !q_mul || !q_const ||
+        !sigmas || !shifts || !table || !q_lookup)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, out_key_p1s != nullptr, "the key's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_create_lookup(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, table, c,
+                                                            table_stride, q_lookup, out_key_p1s, out));
     }
-    ctx->circuits.push_back(c);
-    *out = c;
-    return KZG_OK;
+    return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, CircuitTable{table, c, table_stride, q_lookup},
+                               out_key_p1s, out);
 }
 
 int kzg_circuit_destroy(kzg_ctx* ctx, kzg_circuit* circuit) {
@@ -5886,16 +5947,49 @@ int kzg_circuit_column_device(kzg_ctx* ctx, const kzg_circuit* circuit, unsigned
     return KZG_OK;
 }
 
+// The lookup's scalars as its kernels take them (engine.h, LkScalars), for c table columns: theta^j, 2^14, alpha 2^14 and alpha^3
+// in multiplier form; beta as the digits of its image.  The kernels' bound comments rest on these magnitudes (canonical residues):
+// they are made here and nowhere else.
+struct LkKernelScalars {
+    Fr30 theta[kPqMaxColumns], beta, k14, ak14, a3;
+    LkKernelScalars(const uint64_t* th, const uint64_t* b, const uint64_t* alpha, size_t c) {
+        const hf::Fr x = pq_fr(th);
+        hf::Fr p = hf::kFrOne;
+        for (size_t j = 0; j < c && j < kPqMaxColumns; j++) {
+            theta[j] = fr30_arg_from_mont256(p);
+            p = hf::fr_mul(p, x);
+        }
+        beta = pq_image(b ? pq_fr(b) : hf::kFrOne);
+        k14 = fr30_arg_from_mont256(fr_pow2(14));
+        const hf::Fr a = alpha ? pq_fr(alpha) : hf::kFrOne;
+        ak14 = fr30_arg_from_mont256(hf::fr_mul(a, fr_pow2(14)));
+        a3 = fr30_arg_from_mont256(hf::fr_mul(hf::fr_mul(a, a), a));
+    }
+    LkScalars view() const { return LkScalars{theta, &beta, &k14, &ak14, &a3}; }
+};
+// the lookup of a quotient or of an opening (section 4.26): the multiplicities and the running sum (n values each, where the wires
+// are: host or device) and theta; the call's beta is the lookup's.  In a round of kzg_circuit_lookup_prove the two pointers only say
+// what is there: the resident coefficients go on behind z with phi, then m: [ f_0 .. f_(t-1) | PI | z | phi | m ].
+struct LookupRecord {
+    const void *mult, *phi;
+    const uint64_t* theta;
+};
+
 // wires (t columns of n values), z, pi (n values or null) and gate (N values or null) are host pointers, or device pointers
-// when `device`; then out_coeffs is a device pointer and out_p1s null
+// when `device`; then out_coeffs is a device pointer and out_p1s null.  With a lookup record (and no gate) m and phi are extended
+// with the wires and k_lk_constraints fills the gate's workspace with G' before the constraint kernel reads it.
 static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                                  const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const void* gate, void* out_coeffs,
-                                 uint64_t* out_p1s, bool device, const ProveRound* round = nullptr) {
+                                 uint64_t* out_p1s, bool device, const ProveRound* round = nullptr, const LookupRecord* lookup = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
-    const size_t n = sh.n, N = sh.N, t = c->t, ncols = t + 1 + (pi ? 1 : 0);
+    if (lookup && (!c->c_tab || gate)) {
+        ctx->last_error = "circuit lookup quotient: the circuit was created without a lookup table";
+        return KZG_ERR_INVALID_ARG;
+    }
+    const size_t n = sh.n, N = sh.N, t = c->t, nbase = t + 1 + (pi ? 1 : 0), ncols = nbase + (lookup ? 2 : 0);
     if (device) {
         const size_t ob = (N - n) * 32;
         if (pq_overlap(out_coeffs, ob, wires, ((t - 1) * stride + n) * 32) || pq_overlap(out_coeffs, ob, z, n * 32) ||
@@ -5918,10 +6012,17 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
     if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
-    if (rc == KZG_OK && gate && !device) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc == KZG_OK && ((gate && !device) || lookup)) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
     if (rc) return rc;
     uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
-    if (round) {  // from the resident coefficients [ f | PI | z ]
+    uint32_t *d_m = d_w + 8 * nbase * N, *d_phi = d_m + 8 * N;  // (with a lookup record)
+    if (round && lookup) {  // the resident coefficients [ f | PI | z | phi | m ] in one batched extension, in their own order
+        d_pi = pi ? d_w + 8 * t * N : nullptr;
+        d_z = d_w + 8 * (nbase - 1) * N;
+        d_phi = d_w + 8 * nbase * N;
+        d_m = d_phi + 8 * N;
+        rc = pq_extend(ctx, s.stream, round->coef, n, n, -1, ncols, sh.lg_N, d_w, w, nullptr, true);
+    } else if (round) {  // from the resident coefficients [ f | PI | z ]
         rc = pq_extend(ctx, s.stream, round->coef, n, n, -1, t, sh.lg_N, d_w, w, nullptr, true);
         if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, round->coef + 8 * (ncols - 1) * n, n, n, -1, 1, sh.lg_N, d_z, w);
         if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, round->coef + 8 * t * n, n, n, -1, 1, sh.lg_N, d_pi, w);
@@ -5929,11 +6030,23 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
         rc = pq_extend(ctx, s.stream, (const uint32_t*)wires, stride, n, (int)sh.lg_n, t, sh.lg_N, d_w, w);
         if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)z, n, n, (int)sh.lg_n, 1, sh.lg_N, d_z, w);
         if (rc == KZG_OK && pi) rc = pq_extend(ctx, s.stream, (const uint32_t*)pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
+        if (rc == KZG_OK && lookup) rc = pq_extend(ctx, s.stream, (const uint32_t*)lookup->mult, n, n, (int)sh.lg_n, 1, sh.lg_N, d_m, w);
+        if (rc == KZG_OK && lookup) rc = pq_extend(ctx, s.stream, (const uint32_t*)lookup->phi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_phi, w);
     } else {
-        PqStaged src;  // [ wires | z | PI ], as the extended columns: one extension
+        PqStaged src;  // [ wires | z | PI | m | phi ], as the extended columns: one extension
         rc = pq_stage(ctx, lk, s.stream, false, (uint32_t*)in, wires, stride, z, pi, n, t, false, &src);
+        if (rc == KZG_OK && lookup) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)in + 8 * nbase * n, (const uint64_t*)lookup->mult, n, 1, n);
+        if (rc == KZG_OK && lookup)
+            rc = pq_upload(ctx, lk, s.stream, (uint32_t*)in + 8 * (nbase + 1) * n, (const uint64_t*)lookup->phi, n, 1, n);
         if (rc == KZG_OK && gate) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)d_gate, (const uint64_t*)gate, N, 1, N);
         if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, src.w, n, n, (int)sh.lg_n, ncols, sh.lg_N, d_w, w);
+    }
+    if (rc == KZG_OK && lookup) {  // G' into the gate's workspace
+        const LkKernelScalars lsc(lookup->theta, beta, alpha, c->c_tab);
+        const uint32_t* key = c->coset.dev() + 8 * (2 * t + 2) * N;
+        const LkColumns lc{d_w, key, key + 8 * c->c_tab * N, c->l0.dev(), d_m, d_phi};
+        launch_lk_constraints(s.stream, lc, sh.lg_N, (uint32_t)sh.rot, (uint32_t)c->c_tab, N, lsc.view(), (uint32_t*)d_gate);
+        HIP_TRY(ctx, hipGetLastError());
     }
     if (rc == KZG_OK) rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, (const uint32_t*)d_gate, alpha, beta, gamma, (uint32_t*)d_out);
     bool remainder = false;
@@ -5966,6 +6079,77 @@ int kzg_circuit_quotient_device(kzg_ctx* ctx, const kzg_circuit* circuit, const 
     if (!ctx || !circuit || !d_wires || !d_z || !alpha || !beta || !gamma || !d_out_coeffs) return KZG_ERR_INVALID_ARG;
     return circuit_quotient_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, alpha, beta, gamma, d_gate_coset, d_out_coeffs,
                                  nullptr, true);
+}
+
+// ---- the lookup argument of a circuit whose key holds a table (lookup_circuit_kernels.hip) ---------------
+// The per-proof columns: the folded columns f and T (k_lk_fold), the multiplicities of f in T and the running sum phi, by the
+// kernels of section 4.21 on the call's own slot.  The call holds quotient_mu (the circuit), then lookup_mu (the hash table), then
+// the context's mutex and one slot.
+int kzg_circuit_lookup_columns(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t theta[4],
+                               const uint64_t beta[4], uint64_t* out_f, uint64_t* out_table, uint64_t* out_mult, uint64_t* out_phi,
+                               uint64_t out_last[4], size_t* bad_row) {
+    if (bad_row) *bad_row = (size_t)-1;
+    if (!ctx || !circuit || !wires || !theta || !beta || !out_mult || !out_phi || !out_last) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_lookup_columns(kid, circuit, wires, stride, theta, beta, out_f, out_table, out_mult,
+                                                             out_phi, out_last, bad_row));
+    }
+    // lookup_mu is taken after quotient_mu and given up after the frame has drained the stream (declared first, destroyed last)
+    std::unique_lock<std::mutex> lkl(ctx->lookup_mu, std::defer_lock);
+    PqCall call(ctx);
+    if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
+    const size_t n = circuit->n, t = circuit->t, c = circuit->c_tab;
+    if (!c) {
+        ctx->last_error = "circuit lookup columns: the circuit was created without a lookup table";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (stride < n) return KZG_ERR_INVALID_ARG;
+    lkl.lock();
+    call.lock();
+    int rc = call.begin();
+    if (rc) return rc;
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
+    void* in = nullptr;
+    rc = ctx->pq_ws.get(ctx, kPqIn, (c + 4) * n * 32, &in);  // [ the first c wires | f | T | m | phi ]
+    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
+    if (rc) return rc;
+    uint32_t *d_w = (uint32_t*)in, *d_f = d_w + 8 * c * n, *d_t = d_f + 8 * n, *d_m = d_t + 8 * n, *d_phi = d_m + 8 * n;
+    rc = pq_upload(ctx, lk, s.stream, d_w, wires, n, c, stride);
+    if (rc) return rc;
+    const LkKernelScalars sc(theta, beta, nullptr, c);
+    const uint32_t* tab = circuit->values.dev() + 8 * (2 * t + 2) * n;
+    launch_lk_fold(s.stream, d_w, n, tab, tab + 8 * c * n, (uint32_t)n, (uint32_t)c, sc.view(), d_f, d_t);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = lu_mult_enqueue(ctx, s, d_t, n, d_f, n, 1, n, lu_default_log_capacity(n), d_m, nullptr);
+    if (rc == KZG_OK && out_f) rc = copy_unlocked(ctx, lk, s.stream, out_f, d_f, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (f)");
+    if (rc == KZG_OK && out_table)
+        rc = copy_unlocked(ctx, lk, s.stream, out_table, d_t, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (table)");
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out_mult, d_m, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (multiplicities)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup columns");
+    if (rc == KZG_OK) rc = lu_mult_verdict(ctx, s, bad_row);
+    if (rc) return rc;
+    rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_f, nullptr, d_t, d_m, beta, n, 1, n}, d_phi, out_last, bad_row);
+    if (rc) return rc;
+    rc = copy_unlocked(ctx, lk, s.stream, out_phi, d_phi, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
+    return rc ? rc : sync_unlocked(ctx, lk, s.stream, "circuit lookup columns");
+}
+
+int kzg_circuit_lookup_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                const uint64_t* mult, const uint64_t* phi, const uint64_t* public_inputs, const uint64_t alpha[4],
+                                const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], uint64_t* out_coeffs,
+                                uint64_t* out_p1s) {
+    if (!ctx || !circuit || !wires || !z || !mult || !phi || !alpha || !beta || !gamma || !theta) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_lookup_quotient(kid, circuit, wires, stride, z, mult, phi, public_inputs, alpha, beta, gamma,
+                                                              theta, out_coeffs, out_p1s));
+    }
+    const LookupRecord rec{mult, phi, theta};
+    return circuit_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, nullptr, out_coeffs, out_p1s, false,
+                                 nullptr, &rec);
 }
 
 // ---- zero-knowledge blinding of a circuit's proof (blind_kernels.hip) -------------------------------------
@@ -6223,6 +6407,31 @@ struct LinPoly {
 struct LinChallenges {
     hf::Fr alpha, beta, gamma, zeta;
 };
+// What the lookup adds to r (section 4.26): the scalars on phi(X) and m(X) and the constant, from the evaluations abar (the first
+// c), tbar (c), qbar and phiw = phi(zeta w):
+//     r_L = r + (alpha^4 l - alpha^3 F T) phi(X) + alpha^3 F m(X) + alpha^3 (phiw F T - T),  F = beta + qbar sum theta^j abar_j,
+//     T = beta + sum theta^j tbar_j, l = L_0(zeta)
+struct LookupLin {
+    hf::Fr on_phi, on_m, konst;
+};
+LookupLin lookup_lin(size_t n, uint32_t lg_n, size_t c, const LinChallenges& ch, const hf::Fr& theta, const hf::Fr* abar,
+                     const hf::Fr* tbar, const hf::Fr& qbar, const hf::Fr& phiw) {
+    const hf::Fr Z = hf::fr_sub(hf::fr_pow(ch.zeta, n), hf::kFrOne), zm1 = hf::fr_sub(ch.zeta, hf::kFrOne);
+    const hf::Fr l0 = fr_equal(zm1, kFrZero) ? hf::kFrOne : hf::fr_mul(Z, hf::fr_inv(hf::fr_mul(fr_pow2(lg_n), zm1)));
+    hf::Fr fa = kFrZero, ft = kFrZero, p = hf::kFrOne;
+    for (size_t j = 0; j < c; j++) {
+        fa = hf::fr_add(fa, hf::fr_mul(p, abar[j]));
+        ft = hf::fr_add(ft, hf::fr_mul(p, tbar[j]));
+        p = hf::fr_mul(p, theta);
+    }
+    const hf::Fr F = hf::fr_add(ch.beta, hf::fr_mul(qbar, fa)), T = hf::fr_add(ch.beta, ft), FT = hf::fr_mul(F, T);
+    const hf::Fr a3 = hf::fr_mul(hf::fr_mul(ch.alpha, ch.alpha), ch.alpha), a4 = hf::fr_mul(a3, ch.alpha);
+    LookupLin out;
+    out.on_phi = hf::fr_sub(hf::fr_mul(a4, l0), hf::fr_mul(a3, FT));
+    out.on_m = hf::fr_mul(a3, F);
+    out.konst = hf::fr_mul(a3, hf::fr_sub(hf::fr_mul(phiw, FT), T));
+    return out;
+}
 // The scalars of r, which the prover puts on coefficient vectors and the verifier on commitments, in the order q_0 .. q_(t-1),
 // q_M, q_C, z, sigma_(t-1), T_0 .. T_(e-2); *konst: the constant term.  abar: t values, sbar: t - 1, zw = z(zeta w),
 // pi_zeta = PI(zeta) (zero without public inputs); shifts: the t k_j
@@ -6365,11 +6574,14 @@ int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin,
 static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                              const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                              const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
-                             bool device, const uint64_t* blinders = nullptr, const ProveRound* round = nullptr) {
+                             bool device, const uint64_t* blinders = nullptr, const ProveRound* round = nullptr,
+                             const LookupRecord* lookup = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
+    if (lookup && (!c->c_tab || !round || blinders || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_lookup_prove only)
+    const size_t lc = lookup ? c->c_tab : 0;
     LinChallenges ch;
     hf::Fr vf = kFrZero;
     if (!fr_arg_below_r(alpha, &ch.alpha) || !fr_arg_below_r(beta, &ch.beta) || !fr_arg_below_r(gamma, &ch.gamma) ||
@@ -6377,7 +6589,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         ctx->last_error = "circuit open: a challenge is not below r";
         return KZG_ERR_INVALID_ARG;
     }
-    const size_t n = sh.n, N = sh.N, t = c->t, npoly = 2 * t + 1, ncoef = t + 1 + (pi ? 1 : 0);
+    const size_t n = sh.n, N = sh.N, t = c->t, npoly = 2 * t + 1 + (lookup ? lc + 2 : 0), ncoef = t + 1 + (pi ? 1 : 0);
     // blinded: every polynomial of the stack is padded to L = n + t + 3 coefficients, T~ has L_T of them
     const size_t e = sh.rot, ntail = blinders ? t + 3 : 0, L = n + ntail, t_len = blinders ? blind_quotient_len(n, t, e) : N - n;
     std::vector<hf::Fr> bl;
@@ -6385,9 +6597,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit open (blinded)");
         if (!blind_values_ok(ctx, "circuit open (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
     }
-    // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1)
+    // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1); with
+    // a lookup record it goes on with [ tab_0 .. tab_(c-1) | q_K | phi ], phi in the second set
     const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
     std::vector<uint32_t> set_of(npoly, 0);
+    set_of[2 * t] = 1;
     set_of[npoly - 1] = 1;
     const uint32_t set_len[2] = {1, 1};
     uint64_t zs[8];
@@ -6452,6 +6666,13 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
                         false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * (t + 1));
     launch_sets_combine(s.stream, d_z, (uint32_t)n, 1, n, d_tab + last_pt * kCombineTabGamma, d_tab + kSetsMultBase, s.ssel.dev(), 0,
                         false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * 2 * t);
+    const uint32_t *d_phi = d_z + 8 * n, *d_m = d_z + 16 * n;  // (a round with a lookup record: [ .. z | phi | m ])
+    if (lookup) {  // [2 t + 1, 2 t + c] the table at zeta, [2 t + c + 1] q_K(zeta), [2 t + c + 2] phi(zeta w)
+        launch_sets_combine(s.stream, key + 8 * (2 * t + 2) * n, (uint32_t)n, (uint32_t)(lc + 1), n, d_tab, d_tab + kSetsMultBase,
+                            s.ssel.dev(), 0, false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * (2 * t + 1));
+        launch_sets_combine(s.stream, d_phi, (uint32_t)n, 1, n, d_tab + last_pt * kCombineTabGamma, d_tab + kSetsMultBase, s.ssel.dev(), 0,
+                            false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * (2 * t + 2 + lc));
+    }
     HIP_TRY(ctx, hipGetLastError());
     rc = sync_unlocked(ctx, lk, s.stream, "circuit open (evaluations)");
     if (rc) return rc;
@@ -6460,6 +6681,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     for (size_t j = 0; j < t; j++) std::memcpy(ys[1 + j].l, hv + 8 * j, 32);
     for (size_t j = 0; j + 1 < t; j++) std::memcpy(ys[1 + t + j].l, hv + 8 * (t + 1 + j), 32);
     std::memcpy(ys[2 * t].l, hv + 8 * 2 * t, 32);
+    for (size_t i = 2 * t + 1; i < npoly; i++) std::memcpy(ys[i].l, hv + 8 * i, 32);
     hf::Fr pi_zeta = kFrZero;
     if (pi) std::memcpy(pi_zeta.l, hv + 8 * t, 32);
     if (blinders) {  // f~_j(zeta) = f_j(zeta) + b_j(zeta) Z, z~(zeta w) = z(zeta w) + c(zeta w) Z: (zeta w)^n = zeta^n
@@ -6479,6 +6701,13 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     }
     LinPoly lin;
     lin_poly(c, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, key, d_z, (const uint32_t*)coef, &lin);
+    if (lookup) {  // r_L: two more terms and more of the constant
+        const LookupLin ll = lookup_lin(n, sh.lg_n, lc, ch, pq_fr(lookup->theta), &ys[1], &ys[2 * t + 1], ys[2 * t + 1 + lc],
+                                        ys[2 * t + 2 + lc]);
+        lin.terms.push_back({d_phi, ll.on_phi});
+        lin.terms.push_back({d_m, ll.on_m});
+        lin.konst = hf::fr_add(lin.konst, ll.konst);
+    }
     // 3. the sums.  Point p: G_p = sum_i mult_i P_i over the polynomials of the stack opened there, with m_0 r spread over r's
     // columns: one launch per point, r is never stored.  The test hook: r itself, with its bare scalars.
     LinColumn* cols = (LinColumn*)s.ltab.h;
@@ -6517,11 +6746,15 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
                 out[k++] = lin_column(d_f + 8 * (i - 1) * n, m);
             } else if (i < 2 * t) {
                 out[k++] = lin_column(key + 8 * (t + 2 + (i - t - 1)) * n, m);
-            } else {
+            } else if (i == 2 * t) {
                 out[k++] = lin_column(d_z, m);
+            } else if (i + 1 < npoly) {  // tab_j, q_K: the key's columns behind the sigmas
+                out[k++] = lin_column(key + 8 * (2 * t + 2 + (i - 2 * t - 1)) * n, m);
+            } else {
+                out[k++] = lin_column(d_phi, m);
             }
         }
-        if (k > kLinMaxColumns) return KZG_ERR_INVALID_ARG;  // (3 t + e + 3 <= 32: cannot happen)
+        if (k > kLinMaxColumns) return KZG_ERR_INVALID_ARG;  // (3 t + e + 3 <= 32, with a lookup 3 t + e + c + 5 <= 32: cannot happen)
         ncols[p] = k;
         konst[p] = lin_const(kc);
     }
@@ -8436,11 +8669,36 @@ int kzg_verify_sets(const uint64_t* commitments_p1, size_t t, const uint32_t* se
 // with one batch inversion, [r] = sum scalar commitment + konst G1 from the key, [z] and [T_c] with the scalars the prover put on
 // the coefficients (lin_scalars), then kzg_verify_sets over [ [r] | wires | sigma_0 .. sigma_(t-2) | [z] ] with the values
 // [ 0 | abar | sbar | z(zeta w) ].
+namespace {
+// the lookup of a proof (section 4.26), the verifier's side: c table columns, theta, [m] and [phi]; the key then has 2 t + c + 3
+// commitments and the evaluations go on with tbar_0 .. tbar_(c-1), qbar, phi(zeta w)
+struct LookupClaim {
+    size_t c;
+    const uint64_t *theta, *m_p1, *phi_p1;
+};
+int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
+                        const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
+                        const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                        const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
+                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup);
+}  // namespace
+
 int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
                        const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
                        const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
                        const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, wire_p1s, z_p1, t_p1s, public_inputs, n_public, evals, alpha, beta, gamma,
+                               zeta, v, proof_p1, setup_g1, g1_stride_bytes, setup_g2, g2_stride_bytes, valid, nullptr);
+}
+
+namespace {
+// kzg_circuit_verify; with a lookup claim the verifier of section 4.26: [r_L] and the stack's c + 2 more entries
+int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
+                        const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
+                        const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                        const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
+                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup) {
     if (!key_p1s || !shifts || !wire_p1s || !z_p1 || !t_p1s || (!public_inputs && n_public) || !evals || !alpha || !beta || !gamma ||
         !zeta || !v || !proof_p1 || !setup_g1 || !setup_g2 || !valid)
         return KZG_ERR_INVALID_ARG;
@@ -8448,7 +8706,9 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     if (log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns ||
         t + 1 > sh.rot || n_public > n)
         return KZG_ERR_INVALID_ARG;
-    const size_t e = sh.rot, npoly = 2 * t + 1;
+    const size_t lc = lookup ? lookup->c : 0;
+    if (lookup && !lookup_shape_ok(t, sh.rot, lc)) return KZG_ERR_INVALID_ARG;
+    const size_t e = sh.rot, npoly = 2 * t + 1 + (lookup ? lc + 2 : 0);
     LinChallenges ch;
     hf::Fr vf;
     if (!fr_arg_below_r(alpha, &ch.alpha) || !fr_arg_below_r(beta, &ch.beta) || !fr_arg_below_r(gamma, &ch.gamma) ||
@@ -8474,6 +8734,13 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     for (size_t k = 0; k + 1 < e; k++) on_curve = load(t_p1s + 18 * k, &cs[t + 4 + k]) && on_curve;
     hf::P1 tmp;
     for (size_t j = 0; j < t; j++) on_curve = load(wire_p1s + 18 * j, &tmp) && load(key_p1s + 18 * (t + 2 + j), &tmp) && on_curve;
+    hf::Fr theta = kFrZero;
+    if (lookup) {  // [phi] and [m] follow r's other commitments; the table's commitments are checked like the sigmas'
+        cs.resize(t + e + 5);
+        on_curve = load(lookup->phi_p1, &cs[t + e + 3]) && load(lookup->m_p1, &cs[t + e + 4]) && on_curve;
+        for (size_t j = 0; j < lc + 1; j++) on_curve = load(key_p1s + 18 * (2 * t + 2 + j), &tmp) && on_curve;
+        if (!fr_arg_below_r(lookup->theta, &theta)) return KZG_ERR_INVALID_ARG;
+    }
     if (!on_curve) return KZG_ERR_INVALID_ARG;
     // PI(zeta) = sum_i PI_i L_i(zeta), L_i(zeta) = w^i (zeta^n - 1) / (n (zeta - w^i)); zeta = w^k: L_i(zeta) = [i = k]
     hf::Fr pi_zeta = kFrZero;
@@ -8505,6 +8772,12 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     hf::Fr konst;
     std::vector<hf::Fr> sc;
     lin_scalars(n, sh.lg_n, t, e, shifts, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, &sc, &konst);
+    if (lookup) {
+        const LookupLin ll = lookup_lin(n, sh.lg_n, lc, ch, theta, &ys[1], &ys[2 * t + 1], ys[2 * t + 1 + lc], ys[2 * t + 2 + lc]);
+        sc.push_back(ll.on_phi);
+        sc.push_back(ll.on_m);
+        konst = hf::fr_add(konst, ll.konst);
+    }
     auto times = [](const hf::P1& p, const hf::Fr& k) {  // the scalar multiplication of kzg_combine_claims
         uint64_t plain[4];
         hf::fr_from_mont(k.l, plain);
@@ -8519,8 +8792,13 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     std::memcpy(stack.data() + 18, wire_p1s, 18 * 8 * t);
     std::memcpy(stack.data() + 18 * (1 + t), key_p1s + 18 * (t + 2), 18 * 8 * (t - 1));
     std::memcpy(stack.data() + 18 * 2 * t, z_p1, 18 * 8);
+    if (lookup) {
+        std::memcpy(stack.data() + 18 * (2 * t + 1), key_p1s + 18 * (2 * t + 2), 18 * 8 * (lc + 1));
+        std::memcpy(stack.data() + 18 * (2 * t + 2 + lc), lookup->phi_p1, 18 * 8);
+    }
     for (size_t i = 0; i < npoly; i++) std::memcpy(yl.data() + 4 * i, ys[i].l, 32);
     std::vector<uint32_t> set_of(npoly, 0);
+    set_of[2 * t] = 1;
     set_of[npoly - 1] = 1;
     const uint32_t set_len[2] = {1, 1};
     const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
@@ -8530,6 +8808,7 @@ int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log
     return kzg_verify_sets(stack.data(), npoly, set_of.data(), set_len, 2, zs, yl.data(), v, proof_p1, setup_g1, g1_stride_bytes, setup_g2,
                            g2_stride_bytes, valid);
 }
+}  // namespace
 
 // ---- a circuit's proof as bytes: the hashed transcript and the proof format (host only) -----------------
 //   h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(n_public) | shifts | key commitments | public inputs)
@@ -8714,6 +8993,144 @@ int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsign
                               g2_stride_bytes, valid);
 }
 
+// ---- a lookup circuit's proof as bytes (host only) -------------------------------------------------------
+// The transcript of section 4.25 with a domain of its own, c in the statement and two more rounds:
+//   h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(c) | u64be(n_public) | shifts | the 2 t + c + 3 key commitments
+//               | public inputs)
+//   h1 = SHA256(h0 | wire commitments)     theta = fr(SHA256(h1 | 00))
+//   h2 = SHA256(h1 | [m])                  beta = fr(SHA256(h2 | 00)), gamma = fr(SHA256(h2 | 01))
+//   h3 = SHA256(h2 | [z] | [phi])          alpha = fr(SHA256(h3 | 00))
+//   h4 = SHA256(h3 | [T_0] .. [T_(e-2)])   zeta = fr(SHA256(h4 | 00))
+//   h5 = SHA256(h4 | evaluations)          v = fr(SHA256(h5 | 00))
+namespace {
+constexpr char kLookupProofDst[] = "kzg_mi355x/plonk-lookup/v1";  // 26 bytes, hashed without the terminator
+constexpr size_t kLookupDstLen = sizeof kLookupProofDst - 1;
+void lookup_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c,
+                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public) {
+    const size_t nkey = 2 * t + c + 3;
+    std::vector<uint8_t> m(kLookupDstLen + 40 + 32 * t + 48 * nkey + 32 * n_public);
+    uint8_t* p = m.data();
+    std::memcpy(p, kLookupProofDst, kLookupDstLen);
+    p += kLookupDstLen;
+    for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)c, (uint64_t)n_public}) {
+        proof_u64be(p, x);
+        p += 8;
+    }
+    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
+    for (size_t j = 0; j < nkey; j++, p += 48) {
+        hf::P1 k;
+        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
+        hf::p1_compress(p, k);
+    }
+    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
+    hf::Sha256 s;
+    hf::sha256_init(s);
+    hf::sha256_update(s, m.data(), m.size());
+    hf::sha256_final(s, state);
+}
+// the offsets of the proof's seven fields: wires, [m], [z], [phi], chunks, evaluations, W, and its length
+struct LookupProofLayout {
+    size_t wires, m, z, phi, chunks, evals, w, len, nevals;
+};
+LookupProofLayout lookup_proof_layout(size_t t, size_t e, size_t c) {
+    LookupProofLayout L;
+    L.wires = 0;
+    L.m = 48 * t;
+    L.z = L.m + 48;
+    L.phi = L.z + 48;
+    L.chunks = L.phi + 48;
+    L.evals = L.chunks + 48 * (e - 1);
+    L.nevals = 2 * t + c + 2;
+    L.w = L.evals + 32 * L.nevals;
+    L.len = L.w + 48;
+    return L;
+}
+bool lookup_proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t c, size_t n_public) {
+    return proof_shape_ok(n, t, log_ext, n_public) && lookup_shape_ok(t, (size_t)1 << log_ext, c);
+}
+// the six challenges from complete proof bytes, out: theta, beta, gamma, alpha, zeta, v
+void lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const hf::Fr* shifts,
+                             const hf::Fr* pub, size_t n_public, const uint8_t* proof, hf::Fr out[6]) {
+    const LookupProofLayout L = lookup_proof_layout(t, (size_t)1 << log_ext, c);
+    uint8_t h[32];
+    lookup_proof_statement(h, key_p1s, n, t, log_ext, c, shifts, pub, n_public);
+    proof_absorb(h, proof + L.wires, L.m - L.wires);
+    out[0] = proof_challenge(h, 0);
+    proof_absorb(h, proof + L.m, 48);
+    out[1] = proof_challenge(h, 0);
+    out[2] = proof_challenge(h, 1);
+    proof_absorb(h, proof + L.z, 96);
+    out[3] = proof_challenge(h, 0);
+    proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
+    out[4] = proof_challenge(h, 0);
+    proof_absorb(h, proof + L.evals, L.w - L.evals);
+    out[5] = proof_challenge(h, 0);
+}
+}  // namespace
+
+int kzg_circuit_lookup_proof_size(size_t t, unsigned log_ext, size_t c, size_t* bytes) {
+    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt ||
+        !lookup_shape_ok(t, (size_t)1 << log_ext, c))
+        return KZG_ERR_INVALID_ARG;
+    *bytes = lookup_proof_layout(t, (size_t)1 << log_ext, c).len;
+    return KZG_OK;
+}
+
+int kzg_circuit_lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
+                                        const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                        uint64_t* out) {
+    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
+    if (!lookup_proof_shape_ok(n, t, log_ext, c, n_public) || proof_len != lookup_proof_layout(t, (size_t)1 << log_ext, c).len)
+        return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    hf::Fr ch[6];
+    lookup_proof_challenges(key_p1s, n, t, log_ext, c, ks.data(), pub.data(), n_public, proof, ch);
+    for (int i = 0; i < 6; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
+    return KZG_OK;
+}
+
+int kzg_circuit_lookup_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
+                                    const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                                    int* valid) {
+    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    if (!lookup_proof_shape_ok(n, t, log_ext, c, n_public)) return KZG_ERR_INVALID_ARG;
+    const size_t e = (size_t)1 << log_ext;
+    const LookupProofLayout L = lookup_proof_layout(t, e, c);
+    if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    for (size_t j = 0; j < 2 * t + c + 3; j++) {  // the key, before the proof is looked at
+        hf::P1 k;
+        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
+        if (!hf::p1_on_curve(k)) return KZG_ERR_INVALID_ARG;
+    }
+    // decode: t + e + 3 points (on the curve; no subgroup check) and 2 t + c + 2 canonical scalars; a proof that does not decode is
+    // invalid
+    const size_t npts = t + e + 2;  // before the evaluations: wires, [m], [z], [phi], chunks
+    std::vector<uint64_t> pts(18 * npts), evals(4 * L.nevals);
+    uint64_t w_p1[18];
+    bool decoded = true;
+    for (size_t i = 0; i < npts && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
+    decoded = decoded && kzg_g1_uncompress(proof + L.w, w_p1) == KZG_OK;
+    for (size_t i = 0; i < L.nevals && decoded; i++) {
+        hf::Fr y = kFrZero;
+        decoded = proof_fr_from_be(proof + L.evals + 32 * i, &y);
+        std::memcpy(evals.data() + 4 * i, y.l, 32);
+    }
+    if (!decoded) {
+        *valid = 0;
+        return KZG_OK;
+    }
+    hf::Fr ch[6];
+    lookup_proof_challenges(key_p1s, n, t, log_ext, c, ks.data(), pub.data(), n_public, proof, ch);
+    const LookupClaim claim{c, ch[0].l, pts.data() + 18 * t, pts.data() + 18 * (t + 2)};
+    return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * (t + 1), pts.data() + 18 * (t + 3),
+                               public_inputs, n_public, evals.data(), ch[3].l, ch[1].l, ch[2].l, ch[4].l, ch[5].l, w_p1, setup_g1,
+                               g1_stride_bytes, setup_g2, g2_stride_bytes, valid, &claim);
+}
+
 // ---- a circuit's proof in one call ----------------------------------------------------------------------
 // The five rounds under the transcript above, on one slot, quotient_mu held from start to end.  What lives across rounds sits in
 // buffers the context keeps for this call alone (ctx->prove_buf, under quotient_mu; the pq_ws workspaces belong to the rounds, which
@@ -8882,7 +9299,198 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     std::memcpy(out_proof, proof.data(), L.len);
     return KZG_OK;
 }
+// kzg_circuit_lookup_prove: circuit_prove_impl's sibling with two more rounds, never blinded.  The values
+// V are [ wires | PI | z | phi | m | f | T ] (f, T: the folded columns), the coefficients U [ wires | PI | z | phi | m ]; the call
+// holds lookup_mu (the hash table of the multiplicities) between quotient_mu and the context's mutex.
+int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
+                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row, bool device) {
+    // lookup_mu is taken after quotient_mu and given up after the frame has drained the stream (declared first, destroyed last)
+    std::unique_lock<std::mutex> lkl(ctx->lookup_mu, std::defer_lock);
+    PqCall call(ctx);
+    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    if (!c->c_tab) return prove_refused(ctx, "the circuit was created without a lookup table");
+    PqShape sh;
+    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, t = c->t, e = sh.rot, lc = c->c_tab, ncoef = t + 1 + (n_public ? 1 : 0);
+    std::vector<hf::Fr> ks(t), pub(n_public);
+    for (size_t j = 0; j < t; j++) std::memcpy(ks[j].l, c->shifts + 4 * j, 32);
+    for (size_t i = 0; i < n_public; i++)
+        if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
+    lkl.lock();
+    call.lock();
+    int rc = pq_srs_status(ctx, true, n);
+    if (rc == KZG_OK) rc = call.begin();
+    if (rc == KZG_OK) rc = pq_srs_status(ctx, true, n);  // (the wait for a slot dropped the mutex)
+    if (rc == KZG_OK) rc = ensure_ntt_batch(ctx);
+    if (rc) return rc;
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
+    const int slot = call.slot();
+    DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &T = ctx->prove_buf[3];
+    rc = V.reserve(ctx, (ncoef + 4) * n * 32, s.stream);
+    if (rc == KZG_OK) rc = U.reserve(ctx, (ncoef + 2) * n * 32, s.stream);
+    if (rc == KZG_OK) rc = T.reserve(ctx, (sh.N - n) * 32, s.stream);
+    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
+    if (rc) return rc;
+    uint32_t *d_v = V.dev(), *d_u = U.dev();
+    uint32_t *d_vz = d_v + 8 * (ncoef - 1) * n, *d_vphi = d_vz + 8 * n, *d_vm = d_vphi + 8 * n, *d_vf = d_vm + 8 * n, *d_vt = d_vf + 8 * n;
+    uint32_t *d_uz = d_u + 8 * (ncoef - 1) * n, *d_um = d_uz + 16 * n;
+    const ProveRound round_base{&lk, slot, d_u, nullptr};
+    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
+    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
+    auto to_coefficients = [&](size_t first, size_t cols) -> int {  // `cols` columns of V -> U
+        PqBufs w;
+        int r = pq_bufs(ctx, n, cols, &w);
+        if (r) return r;
+        for (size_t c0 = 0; c0 < cols; c0 += w.chunk) {
+            const size_t bc = cols - c0 < w.chunk ? cols - c0 : w.chunk;
+            launch_ntt_batch(s.stream, d_v + 8 * (first + c0) * n, n, d_u + 8 * (first + c0) * n, n, sh.lg_n, (uint32_t)bc, itw, inv_n, w.A, w.B);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        return KZG_OK;
+    };
+    const size_t np1 = t + e + 2;  // the proof's points before the evaluations: wires, [m], [z], [phi], chunks
+    const LookupProofLayout L = lookup_proof_layout(t, e, lc);
+    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * L.nevals);
+    std::vector<uint8_t> proof(L.len);
+    auto put_points = [&](size_t first, size_t count) {
+        for (size_t i = first; i < first + count; i++) {
+            hf::P1 pt;
+            std::memcpy(&pt, p1s.data() + 18 * i, sizeof pt);
+            hf::p1_compress(proof.data() + 48 * i, pt);
+        }
+    };
+    uint8_t h[32];
+    lookup_proof_statement(h, key_p1s, n, t, c->lg_ext, lc, ks.data(), pub.data(), n_public);
+
+    // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; theta
+    if (device) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_v, n * 32, wires, stride * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
+    } else {
+        rc = pq_upload(ctx, lk, s.stream, d_v, (const uint64_t*)wires, n, t, stride);
+        if (rc) return rc;
+    }
+    if (n_public) {
+        HIP_TRY(ctx, hipMemsetAsync(d_v + 8 * t * n, 0, n * 32, s.stream));
+        rc = copy_unlocked(ctx, lk, s.stream, d_v + 8 * t * n, public_inputs, n_public * 32, hipMemcpyHostToDevice,
+                           "hipMemcpyAsync (public inputs)");
+        if (rc) return rc;
+    }
+    rc = to_coefficients(0, ncoef - 1);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (wires)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, d_u, n, t, p1s.data());
+    if (rc) return rc;
+    put_points(0, t);
+    proof_absorb(h, proof.data() + L.wires, L.m - L.wires);
+    const hf::Fr theta = proof_challenge(h, 0);
+
+    // round 2: the folded columns, the multiplicities of f in T, [m]; beta, gamma
+    {
+        const LkKernelScalars sc(theta.l, nullptr, nullptr, lc);
+        const uint32_t* tab = c->values.dev() + 8 * (2 * t + 2) * n;
+        launch_lk_fold(s.stream, d_v, n, tab, tab + 8 * lc * n, (uint32_t)n, (uint32_t)lc, sc.view(), d_vf, d_vt);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = lu_mult_enqueue(ctx, s, d_vt, n, d_vf, n, 1, n, lu_default_log_capacity(n), d_vm, nullptr);
+        if (rc == KZG_OK) rc = to_coefficients(ncoef + 1, 1);
+        if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (multiplicities)");
+        if (rc) return rc;
+        size_t bad = (size_t)-1;
+        rc = lu_mult_verdict(ctx, s, &bad);
+        if (rc && bad != (size_t)-1) {
+            if (bad_row) *bad_row = bad;
+            ctx->last_error = "circuit lookup prove: the tuple of row " + std::to_string(bad) + " is in no row of the table";
+            return KZG_ERR_REMAINDER;
+        }
+        if (rc) return rc;
+    }
+    rc = pq_commit_chunks(ctx, lk, slot, d_um, n, 1, p1s.data() + 18 * t);
+    if (rc) return rc;
+    put_points(t, 1);
+    proof_absorb(h, proof.data() + L.m, 48);
+    const hf::Fr beta = proof_challenge(h, 0), gamma = proof_challenge(h, 1);
+
+    // round 3: phi and z on the device; phi_n = 0, z_n = 1; their commitments; alpha
+    {
+        uint64_t last[4];
+        size_t bad = (size_t)-1;
+        rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_vf, nullptr, d_vt, d_vm, beta.l, n, 1, n}, d_vphi, last, &bad);
+        if (rc) {
+            if (bad_row && bad != (size_t)-1) *bad_row = bad;
+            return rc;
+        }
+        if (std::memcmp(last, kFrZero.l, 32) != 0) {
+            ctx->last_error = "circuit lookup prove: the running sum does not return to zero (phi_n != 0): the lookup does not hold";
+            return KZG_ERR_REMAINDER;
+        }
+        const GpScalars perm{c->shifts, beta.l, gamma.l};
+        rc = gp_on_slot(ctx, lk, s, d_v, c->values.dev() + 8 * (t + 2) * n, n, t, n, &perm, sh.lg_n, d_vz, last, &bad);
+        if (rc) return rc;
+        if (std::memcmp(last, hf::kFrOne.l, 32) != 0) {
+            ctx->last_error = "circuit prove: the grand product does not return to one (z_n != 1): the copy constraints do not hold";
+            return KZG_ERR_REMAINDER;
+        }
+    }
+    rc = to_coefficients(ncoef - 1, 2);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (z, phi)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, d_uz, n, 2, p1s.data() + 18 * (t + 1));
+    if (rc) return rc;
+    put_points(t + 1, 2);
+    proof_absorb(h, proof.data() + L.z, 96);
+    const hf::Fr alpha = proof_challenge(h, 0);
+
+    // round 4: the quotient with the lookup's term from the resident coefficients, its chunks' commitments; zeta
+    const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
+    const LookupRecord rec{d_vm, d_vphi, theta.l};
+    rc = circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 3), true,
+                               &round_base, &rec);
+    if (rc) return rc;
+    put_points(t + 3, e - 1);
+    proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
+    const hf::Fr zeta = proof_challenge(h, 0);
+
+    // rounds 5 and 6: the evaluations, v from them, r_L(zeta) = 0, the opening
+    ProveRound last_round = round_base;
+    last_round.derive_v = [&](const uint64_t* ev, uint64_t v[4]) {
+        for (size_t i = 0; i < L.nevals; i++) {
+            hf::Fr y;
+            std::memcpy(y.l, ev + 4 * i, 32);
+            proof_fr_to_be(y, proof.data() + L.evals + 32 * i);
+        }
+        proof_absorb(h, proof.data() + L.evals, L.w - L.evals);
+        const hf::Fr vf = proof_challenge(h, 0);
+        std::memcpy(v, vf.l, 32);
+        return true;
+    };
+    rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
+                           evals.data(), nullptr, p1s.data() + 18 * np1, true, nullptr, &last_round, &rec);
+    if (rc) return rc;
+    hf::P1 w;
+    std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
+    hf::p1_compress(proof.data() + L.w, w);
+    std::memcpy(out_proof, proof.data(), L.len);
+    return KZG_OK;
+}
 }  // namespace
+
+int kzg_circuit_lookup_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row) {
+    if (bad_row) *bad_row = (size_t)-1;
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_lookup_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row));
+    }
+    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row, false);
+}
+
+int kzg_circuit_lookup_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
+                                    const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row) {
+    if (bad_row) *bad_row = (size_t)-1;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, out_proof, bad_row, true);
+}
 
 int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {

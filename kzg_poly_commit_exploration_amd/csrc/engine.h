@@ -423,6 +423,26 @@ struct CkColumns {
 void launch_ck_constraints(hipStream_t s, const CkColumns& cols, uint32_t log_N, uint32_t rot, uint32_t t, size_t stride,
                            const PqScalars& sc, const Fr30& k14, const void* d_tw, uint32_t* d_out);
 
+// ---- lookup_circuit_kernels.hip: the lookup argument of a circuit whose key holds a table ---------------
+// the scalars of both kernels: theta^j (j < c) in multiplier form; beta as the digits of its image; k14 = 2^14, ak14 = alpha 2^14
+// and a3 = alpha^3 in multiplier form (k_lk_fold reads theta and k14 alone)
+struct LkScalars {
+    const Fr30 *theta, *beta, *k14, *ak14, *a3;
+};
+// d_out_f[i] = q_K[i] sum_j theta^j f_j[i], d_out_t[i] = sum_j theta^j tab_j[i], canonical, i < n: the first c wire columns
+// (column j at + 8 j stride words), the c table columns (column j at + 8 j n words) and q_K, n blst_fr images each; 1 <= c <=
+// kPqMaxColumns; the outputs overlap no input and not each other
+void launch_lk_fold(hipStream_t s, const uint32_t* d_wires, size_t stride, const uint32_t* d_table, const uint32_t* d_qk, uint32_t n,
+                    uint32_t c, const LkScalars& sc, uint32_t* d_out_f, uint32_t* d_out_t);
+// what k_lk_constraints reads: N = 2^log_N values per column on the coset, all blst_fr images.  The wires are the call's (column j
+// at + 8 j stride words), the table columns the circuit's (column j at + 8 j N words)
+struct LkColumns {
+    const uint32_t *d_wires, *d_table, *d_qk, *d_l0, *d_mult, *d_phi;
+};
+// d_out[i] = G'(x_i) = alpha^3 Lk1 + alpha^4 Lk2, canonical, i < N; rot = N / n; d_out may alias no input
+void launch_lk_constraints(hipStream_t s, const LkColumns& cols, uint32_t log_N, uint32_t rot, uint32_t c, size_t stride,
+                           const LkScalars& sc, uint32_t* d_out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

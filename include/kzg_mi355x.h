@@ -872,6 +872,78 @@ int kzg_circuit_lookup_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const 
                                 const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], uint64_t* out_coeffs,
                                 uint64_t* out_p1s);
 
+/* ---- circuit proofs with custom gates: selector x wire-monomial terms ----------------------------------
+ * Notation as above.  A custom circuit keeps g more resident selector columns qx_0 .. qx_(g-1) (n values each) and an exponent
+ * matrix p[s][j] in 0..7 (g x t bytes, row-major), d_s = sum_j p[s][j], d_max = max_s d_s.  Every row i must satisfy
+ *     sum_j q_j f_j + q_M f_0 f_1 + q_C + PI + sum_(s<g) qx_s[i] prod_(j<t) f_j[i]^p[s][j] = 0
+ *     G'(X) = sum_s qx_s(X) prod_j f_j(X)^p[s][j],   Num_X = Num (of kzg_circuit_quotient, no caller's term) + G',
+ *     T = Num_X / (X^n - 1);   deg G' <= (d_max + 1)(n - 1), so T's share has degree below d_max n.
+ * Shape rules (KZG_ERR_INVALID_ARG from kzg_circuit_create_custom): kzg_circuit_create's, 1 <= g <= KZG_CIRCUIT_MAX_CUSTOM, an
+ * exponent above 7, a term of degree d_s = 0 (that is q_C), 2^log_ext < max(t + 1, d_max + 1), 3 t + 2^log_ext + 3 + g > 32 (the
+ * columns the last round combines at zeta), custom_stride < n, a NULL q_custom or exponents.  Not offered: terms at the next row
+ * f_j(w X), a custom circuit with a lookup table, a caller's gate_coset on top of the custom terms.
+ *
+ * kzg_circuit_create_custom is kzg_circuit_create with q_custom (g columns of n values, column s at q_custom + 4 s custom_stride
+ * u64) and exponents: the g columns are resident as values, coefficients and coset values behind the 2 t + 2 others and
+ * out_key_p1s (NULL, or (2 t + 2 + g) x 18 u64) receives kzg_circuit_create's commitments and then theirs, each bit for bit
+ * kzg_commit_evaluations of the column.  Device memory: kzg_circuit_create's with 2 t + 2 + g columns.  Every other call that takes
+ * a circuit accepts the handle and ignores the custom terms (kzg_circuit_prove proves the base statement).
+ * kzg_circuit_column_device hands the columns out as KZG_CIRCUIT_COL_CUSTOM + s (s < g).
+ *
+ * kzg_circuit_custom_gate (the kernel's test hook): wires as kzg_circuit_quotient takes them -> out_gate_coset, the N values
+ * G'(x_i) on the coset of kzg_circuit_quotient's gate_coset, canonical blst_fr.  Needs no SRS; a multi-device context runs it on
+ * devices[0].  kzg_circuit_custom_quotient is kzg_circuit_quotient (blinders NULL; out_coeffs N - n values) or
+ * kzg_circuit_quotient_blinded (out_coeffs L_T values) with G' as the caller's term, computed on the device from the (blinded)
+ * wires; outputs, statuses and multi-device rules are theirs.  An unsatisfied custom gate is KZG_ERR_REMAINDER.
+ *
+ * BLINDING is kzg_circuit_prove's: the array, the wires, z and T's chunks as in the section above; the selectors are key material
+ * and are not blinded.  Only T~'s degree changes: deg T~ = max(t n + t + 2, d_max (n + 1) - 1), and a blinded call is
+ * KZG_ERR_INVALID_ARG unless deg T~ + 1 <= L_T = (e - 1) n + t + 3 and N >= deg T~ + 2 (for d_max <= t the rule above, unchanged).
+ * kzg_circuit_custom_blinded_sizes (host only) applies the rule; its outputs are kzg_circuit_blinded_sizes'.
+ *
+ * THE PROOF.  Last round: r_X(X) = r(X) + sum_s (prod_j abar_j^p[s][j]) qx_s(X) with r the polynomial of kzg_circuit_open formed with
+ * this T; the opening stack, the 2 t evaluations and the sets are the plain proof's.  Proof bytes: kzg_circuit_prove's format and
+ * kzg_circuit_proof_size(t, log_ext) bytes; every commitment is bit for bit kzg_commit_evaluations (blinded:
+ * kzg_commit_evaluations_blinded) of its column.  Transcript: kzg_circuit_prove's from h1 on under a statement of its own, so that no
+ * plain proof verifies as a custom proof of the same key prefix:
+ *     DST = ASCII "kzg_mi355x/plonk-custom/v1"
+ *     h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(g) | u64be(n_public) | shifts (t x 32)
+ *                 | exponents (g x t bytes, row-major) | key commitments ((2 t + 2 + g) x 48, kzg_circuit_create_custom's order)
+ *                 | public inputs)
+ * kzg_circuit_custom_prove / _device: kzg_circuit_prove's arguments (key_p1s: (2 t + 2 + g) x 18 u64; blinders NULL for a plain
+ * proof), statuses in kzg_circuit_prove's order, with KZG_ERR_INVALID_ARG also for a circuit without custom gates and for the
+ * blinded rule, and KZG_ERR_REMAINDER from the quotient for an unsatisfied custom gate or from r_X(zeta) != 0.  A failed call writes
+ * nothing to out_proof and leaves the context serving.  Multi-device rules are kzg_circuit_prove's.
+ *
+ * Host only, no context: kzg_circuit_custom_proof_challenges (out: 5 x 4 u64, beta, gamma, alpha, zeta, v as
+ * kzg_circuit_proof_challenges) and kzg_circuit_custom_verify_proof, which adds sum_s (prod_j abar_j^p[s][j]) [qx_s] to [r] and runs
+ * kzg_verify_sets; argument and decode rules are kzg_circuit_verify_proof's plus the shape rules above: bytes that do not decode
+ * give KZG_OK with *valid = 0.  The verifier is the same for plain and blinded proofs. */
+#define KZG_CIRCUIT_MAX_CUSTOM 8
+#define KZG_CIRCUIT_COL_CUSTOM 96
+int kzg_circuit_create_custom(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
+                              const uint64_t* sigmas, size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext,
+                              const uint64_t* q_custom, size_t g, size_t custom_stride, const uint8_t* exponents /* g*t */,
+                              uint64_t* out_key_p1s /* (2t+2+g)x18 */, kzg_circuit** out);
+int kzg_circuit_custom_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride,
+                            uint64_t* out_gate_coset /* N x 4 */);
+int kzg_circuit_custom_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                const uint64_t* blinders /* NULL: plain */, uint64_t* out_coeffs, uint64_t* out_p1s);
+int kzg_circuit_custom_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof);
+int kzg_circuit_custom_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                    size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                    uint8_t* out_proof);
+int kzg_circuit_custom_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                        const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public,
+                                        const uint8_t* proof, size_t proof_len, uint64_t* out);
+int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                    const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
+                                    size_t proof_len, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2,
+                                    size_t g2_stride_bytes, int* valid);
+int kzg_circuit_custom_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t d_max, size_t* num_blinders, size_t* quotient_len);
+
 /* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
  * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the
  * gate and the permutation are computed from the same values as without blinding, and kzg_circuit_verify accepts a blinded proof

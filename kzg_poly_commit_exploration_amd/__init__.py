@@ -95,6 +95,9 @@ ABI_SYMBOLS = [
     "kzg_circuit_create_lookup", "kzg_circuit_lookup_columns", "kzg_circuit_lookup_quotient",
     "kzg_circuit_lookup_prove", "kzg_circuit_lookup_prove_device", "kzg_circuit_lookup_proof_size",
     "kzg_circuit_lookup_proof_challenges", "kzg_circuit_lookup_verify_proof",
+    "kzg_circuit_create_custom", "kzg_circuit_custom_gate", "kzg_circuit_custom_quotient", "kzg_circuit_custom_prove",
+    "kzg_circuit_custom_prove_device", "kzg_circuit_custom_proof_challenges", "kzg_circuit_custom_verify_proof",
+    "kzg_circuit_custom_blinded_sizes",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -114,6 +117,7 @@ KZG_CIRCUIT_MIN_COLUMNS = 2  # wire columns of a circuit with the built-in arith
 KZG_CIRCUIT_COL_QLIN, KZG_CIRCUIT_COL_QM, KZG_CIRCUIT_COL_QC, KZG_CIRCUIT_COL_SIGMA, KZG_CIRCUIT_COL_L0 = 0, 16, 17, 32, 48
 KZG_CIRCUIT_VALUES, KZG_CIRCUIT_COEFFS, KZG_CIRCUIT_COSET = 0, 1, 2
 KZG_CIRCUIT_COL_TABLE, KZG_CIRCUIT_COL_QLOOKUP = 64, 80  # the columns of a lookup circuit (kzg_circuit_create_lookup)
+KZG_CIRCUIT_COL_CUSTOM, KZG_CIRCUIT_MAX_CUSTOM = 96, 8  # the selector columns of a custom circuit (kzg_circuit_create_custom)
 KZG_SHA256_AUTO, KZG_SHA256_PORTABLE, KZG_SHA256_SHANI = 0, 1, 2
 KZG_MAX_CELL_LOG = 6
 
@@ -257,6 +261,14 @@ def load_library():
         "kzg_circuit_lookup_proof_size": (i, [sz, C.c_uint, sz, C.POINTER(sz)]),
         "kzg_circuit_lookup_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp]),
         "kzg_circuit_lookup_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
+        "kzg_circuit_create_custom": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, sz, sz, vp, vp, C.POINTER(vp)]),
+        "kzg_circuit_custom_gate": (i, [vp, vp, vp, sz, vp]),
+        "kzg_circuit_custom_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_custom_prove": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_custom_prove_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_custom_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp]),
+        "kzg_circuit_custom_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
+        "kzg_circuit_custom_blinded_sizes": (i, [sz, sz, C.c_uint, sz, C.POINTER(sz), C.POINTER(sz)]),
         "kzg_circuit_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_quotient_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_column_device": (i, [vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(sz)]),
@@ -1606,6 +1618,30 @@ class Engine:
         circ.c = c
         return circ
 
+    def circuit_create_custom(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, q_custom, exponents, n=None, want_key=True):
+        """kzg_circuit_create_custom: circuit_create's arguments, q_custom a (g, custom_stride, 4) array whose first n rows per
+        column count and exponents a (g, t) array of bytes in 0..7 -> a Circuit with g custom terms; its key has 2 t + 2 + g
+        commitments, circuit_create's and then qx[0..g)"""
+        a, t, stride, n = self._columns(q_lin, n)
+        b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
+        qm = np.ascontiguousarray(q_mul, dtype=np.uint64).reshape(-1, 4)
+        qc = np.ascontiguousarray(q_const, dtype=np.uint64).reshape(-1, 4)
+        qx = np.ascontiguousarray(q_custom, dtype=np.uint64)
+        assert qx.ndim == 3 and qx.shape[2] == 4 and qx.shape[1] >= n
+        assert qm.shape[0] >= n and qc.shape[0] >= n
+        g = qx.shape[0]
+        ex = np.ascontiguousarray(exponents, dtype=np.uint8).reshape(g, t)
+        sh = np.ascontiguousarray([k.limbs() for k in shifts], dtype=np.uint64).reshape(-1, 4)
+        assert sh.shape[0] == t, "one coset shift per column"
+        p1s = np.zeros((2 * t + 2 + g, 18), dtype=np.uint64) if want_key else None
+        h = C.c_void_p()
+        self._pq_check(self._lib.kzg_circuit_create_custom(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh), log_ext,
+                                                           _ptr(qx), g, qx.shape[1], _ptr(ex), None if p1s is None else _ptr(p1s),
+                                                           C.byref(h)))
+        circ = Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
+        circ.g, circ.exponents = g, ex
+        return circ
+
     # -- zero-knowledge blinding (DESIGN.md 4.24) --
     def blind_evaluations_limbs(self, evals, blinders, n=None):
         """kzg_blind_evaluations: evals a (k, stride, 4) array of values over H whose first n rows per column count, blinders a
@@ -1761,6 +1797,7 @@ class Circuit:
         self._eng, self._c = engine, handle
         self.n, self.t, self.log_ext, self.key = n, t, log_ext, key
         self.c = 0  # table columns (circuit_create_lookup)
+        self.g, self.exponents = 0, None  # custom terms and their (g, t) exponents (circuit_create_custom)
 
     def close(self):
         if getattr(self, "_c", None) and getattr(self._eng, "_h", None):
@@ -2018,6 +2055,53 @@ class Circuit:
         return self._lookup_prove(e._lib.kzg_circuit_lookup_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
                                   public_inputs)
 
+    # -- custom gates: selector x wire-monomial terms --
+    def custom_gate(self, wires, n=None, engine=None):
+        """kzg_circuit_custom_gate (test hook, no SRS): wires a (t, stride, 4) array -> the (N, 4) values of
+        G' = sum_s qx_s prod_j f_j^p[s][j] on the coset"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        out = np.zeros((n << self.log_ext, 4), dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_custom_gate(e._h, self._c, _ptr(a), stride, _ptr(out)))
+        return out
+
+    def custom_quotient(self, wires, z, alpha, beta, gamma, blinders=None, public_inputs=None, n=None, want_coeffs=True,
+                        want_commitments=True, engine=None):
+        """kzg_circuit_custom_quotient: quotient() without a gate (blinders None) or quotient_blinded(), with the custom terms made
+        from the wires on the device -> as those return"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n and (pi is None or pi.shape[0] >= n)
+        ext = 1 << self.log_ext
+        b = None if blinders is None else np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        assert b is None or b.shape[0] == 2 * t + 3 + ext - 2
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        rows = (ext - 1) * n + (0 if b is None else t + 3)
+        coeffs = np.zeros((rows, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros((ext - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_custom_quotient(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi),
+                                                       _ptr(al), _ptr(bl), _ptr(gl), None if b is None else _ptr(b),
+                                                       None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def custom_prove(self, wires, public_inputs=None, blinders=None, n=None, engine=None):
+        """kzg_circuit_custom_prove: prove()'s arguments on a circuit of circuit_create_custom -> the proof bytes
+        (circuit_proof_size of them) of the statement with the custom terms"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        return self._prove(e._lib.kzg_circuit_custom_prove, e, _ptr(a), stride, public_inputs, blinders)
+
+    def custom_prove_device(self, d_wires, public_inputs=None, blinders=None, stride=None):
+        """kzg_circuit_custom_prove_device: the wires in a device buffer of the circuit's (single-device) context"""
+        e = self._eng
+        return self._prove(e._lib.kzg_circuit_custom_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
+                           public_inputs, blinders)
+
     def column_device(self, which, form):
         """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
         e = self._eng
@@ -2269,6 +2353,49 @@ def circuit_verify_proof(key, n, log_ext, shifts, public_inputs, proof, setup_g1
     ok = C.c_int(0)
     _check(load_library().kzg_circuit_verify_proof(_ptr(rows), n, t, log_ext, _ptr(ks), _ptr(pub) if pub is not None else None, n_public,
                                                    _ptr(buf), buf.shape[0], _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def circuit_custom_blinded_sizes(n, t, log_ext, d_max):
+    """kzg_circuit_custom_blinded_sizes -> (entries of the blinder array, L_T); KzgError(KZG_ERR_INVALID_ARG) for a shape the
+    blinded calls refuse with custom gates of degree d_max: max(t n + t + 3, d_max (n + 1)) has to be <= L_T and < 2^log_ext n"""
+    nb, lt = C.c_size_t(0), C.c_size_t(0)
+    _check(load_library().kzg_circuit_custom_blinded_sizes(n, t, log_ext, d_max, C.byref(nb), C.byref(lt)))
+    return int(nb.value), int(lt.value)
+
+
+def _custom_proof_statement(key, exponents, shifts, public_inputs, proof):
+    t = len(shifts)
+    ex = np.ascontiguousarray(exponents, dtype=np.uint8).reshape(-1, t)
+    assert len(key) == 2 * t + 2 + ex.shape[0]
+    rows = np.ascontiguousarray(np.stack([k.p1 for k in key]), dtype=np.uint64)
+    pub = list(public_inputs) if public_inputs is not None else []
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    return t, ex, rows, _scalar_rows(shifts), (_scalar_rows(pub) if pub else None), len(pub), buf
+
+
+def circuit_custom_proof_challenges(key, n, log_ext, exponents, shifts, public_inputs, proof):
+    """kzg_circuit_custom_proof_challenges: (beta, gamma, alpha, zeta, v) of the hashed transcript from complete proof bytes.
+    key: the 2 t + 2 + g commitments of circuit_create_custom, exponents its (g, t) bytes; nothing is decoded."""
+    t, ex, rows, ks, pub, n_public, buf = _custom_proof_statement(key, exponents, shifts, public_inputs, proof)
+    out = np.zeros((5, 4), dtype=np.uint64)
+    _check(load_library().kzg_circuit_custom_proof_challenges(_ptr(rows), n, t, log_ext, ex.shape[0], _ptr(ex), _ptr(ks),
+                                                              _ptr(pub) if pub is not None else None, n_public, _ptr(buf), buf.shape[0],
+                                                              _ptr(out)))
+    return tuple(Scalar.from_limbs(out[i]) for i in range(5))
+
+
+def circuit_custom_verify_proof(key, n, log_ext, exponents, shifts, public_inputs, proof, setup_g1, setup_g2):
+    """kzg_circuit_custom_verify_proof on the host: decodes the proof bytes, derives the challenges, forms [r_X], checks the
+    opening; plain and blinded proofs alike.  False also for bytes that do not decode."""
+    t, ex, rows, ks, pub, n_public, buf = _custom_proof_statement(key, exponents, shifts, public_inputs, proof)
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 1 and g2.shape[0] >= 3
+    ok = C.c_int(0)
+    _check(load_library().kzg_circuit_custom_verify_proof(_ptr(rows), n, t, log_ext, ex.shape[0], _ptr(ex), _ptr(ks),
+                                                          _ptr(pub) if pub is not None else None, n_public, _ptr(buf), buf.shape[0],
+                                                          _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

@@ -375,6 +375,10 @@ struct kzg_circuit {
     uint32_t lg_n = 0, lg_ext = 0;
     size_t n = 0, t = 0;
     size_t c_tab = 0;  // table columns of a lookup circuit, 0: none
+    // a custom circuit (kzg_circuit_create_custom, section 4.27; never with a table): g_custom selector columns qx_s behind the
+    // 2 t + 2, the exponents p[s][j] at s t + j and the largest row sum; calls of section 4.22 .. 4.25 ignore them too
+    size_t g_custom = 0, d_max = 0;
+    uint8_t exps[kCgMaxTerms * kPqMaxColumns] = {};
     uint64_t shifts[4 * kPqMaxColumns] = {};
     DevBuf values;  // cols() x n
     DevBuf coeffs;  // cols() x n
@@ -382,7 +386,7 @@ struct kzg_circuit {
     DevBuf l0;      // the N values of L_0 on the coset
     DevBuf zinv;    // the rot stored multipliers 1 / Z_H(x_i): the circuit's own copy, independent of pq_zinv_key
     size_t N() const { return n << lg_ext; }
-    size_t cols() const { return 2 * t + 2 + (c_tab ? c_tab + 1 : 0); }
+    size_t cols() const { return 2 * t + 2 + (c_tab ? c_tab + 1 : 0) + g_custom; }
 };
 
 namespace {
@@ -5768,6 +5772,7 @@ static size_t circuit_column_index(const kzg_circuit* c, unsigned which) {
     if (which >= KZG_CIRCUIT_COL_SIGMA && which < KZG_CIRCUIT_COL_SIGMA + c->t) return c->t + 2 + (which - KZG_CIRCUIT_COL_SIGMA);
     if (which >= KZG_CIRCUIT_COL_TABLE && which < KZG_CIRCUIT_COL_TABLE + c->c_tab) return 2 * c->t + 2 + (which - KZG_CIRCUIT_COL_TABLE);
     if (which == KZG_CIRCUIT_COL_QLOOKUP && c->c_tab) return 2 * c->t + 2 + c->c_tab;
+    if (which >= KZG_CIRCUIT_COL_CUSTOM && which < KZG_CIRCUIT_COL_CUSTOM + c->g_custom) return 2 * c->t + 2 + (which - KZG_CIRCUIT_COL_CUSTOM);
     return (size_t)-1;
 }
 // is `c` a circuit alive on the single-device context `ctx` (quotient_mu held)?
@@ -5787,6 +5792,9 @@ struct CircuitTable {  // the columns of a lookup circuit (section 4.26): c tabl
     const uint64_t* table = nullptr;
     size_t c = 0, stride = 0;
     const uint64_t* q_lookup = nullptr;
+    // ... or of a custom circuit (section 4.27): g selector columns at a stride, or g = 0 (the exponents are in *c already)
+    const uint64_t* q_custom = nullptr;
+    size_t g = 0, custom_stride = 0;
 };
 static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul,
                          const uint64_t* q_const, const uint64_t* sigmas, size_t stride, const CircuitTable& tab,
@@ -5813,6 +5821,7 @@ static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqSha
     if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (t + 2) * n, sigmas, n, t, stride);
     if (rc == KZG_OK && tab.c) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (2 * t + 2) * n, tab.table, n, tab.c, tab.stride);
     if (rc == KZG_OK && tab.c) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (2 * t + 2 + tab.c) * n, tab.q_lookup, n, 1, n);
+    if (rc == KZG_OK && tab.g) rc = pq_upload(ctx, lk, s.stream, d_val + 8 * (2 * t + 2) * n, tab.q_custom, n, tab.g, tab.custom_stride);
     if (rc) return rc;
     // values -> coefficients (the inverse transform the extension needs anyway, kept) -> the coset
     const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
@@ -5845,10 +5854,29 @@ static int circuit_build(kzg_ctx* ctx, PqCall& call, kzg_circuit* c, const PqSha
 static bool lookup_shape_ok(size_t t, size_t e, size_t c) {
     return c >= 1 && c <= t && e >= 4 && e >= t + 1 && 3 * t + e + c + 5 <= kLinMaxColumns;
 }
-// kzg_circuit_create and kzg_circuit_create_lookup (tab.c != 0) after their argument checks, on a single-device context
+// the shape rules of a custom circuit (section 4.27): 1 <= g <= 8 terms, every exponent in 0..7 and every term of degree d_s >= 1
+// (degree 0 is q_C), deg G' <= (d_max + 1) (n - 1) asks for e >= d_max + 1, and the last round's combination at zeta has the plain
+// proof's 3 t + e + 3 columns and g more.  *d_max: the largest d_s
+static bool custom_shape_ok(size_t t, size_t e, size_t g, const uint8_t* exps, size_t* d_max) {
+    if (!exps || g < 1 || g > kCgMaxTerms || t < 1 || t > kPqMaxColumns || e < t + 1 || 3 * t + e + 3 + g > kLinMaxColumns) return false;
+    size_t dm = 0;
+    for (size_t s = 0; s < g; s++) {
+        size_t d = 0;
+        for (size_t j = 0; j < t; j++) {
+            if (exps[s * t + j] > 7) return false;
+            d += exps[s * t + j];
+        }
+        if (d < 1) return false;
+        dm = d > dm ? d : dm;
+    }
+    if (d_max) *d_max = dm;
+    return e >= dm + 1;
+}
+// kzg_circuit_create, kzg_circuit_create_lookup (tab.c != 0) and kzg_circuit_create_custom (tab.g != 0, exps: its g t exponents)
+// after their argument checks, on a single-device context
 static int circuit_create_impl(kzg_ctx* ctx, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
                                const uint64_t* sigmas, size_t t, size_t stride, const uint64_t* shifts, const CircuitTable& tab,
-                               uint64_t* out_key_p1s, kzg_circuit** out) {
+                               uint64_t* out_key_p1s, kzg_circuit** out, const uint8_t* exps = nullptr) {
     const size_t n = sh.n;
     PqCall call(ctx);
     kzg_circuit* c = new kzg_circuit();
@@ -5858,6 +5886,11 @@ static int circuit_create_impl(kzg_ctx* ctx, const PqShape& sh, const uint64_t* 
     c->n = n;
     c->t = t;
     c->c_tab = tab.c;
+    if (tab.g) {
+        c->g_custom = tab.g;
+        std::memcpy(c->exps, exps, tab.g * t);
+        (void)custom_shape_ok(t, sh.rot, tab.g, exps, &c->d_max);
+    }
     std::memcpy(c->shifts, shifts, 32 * t);
     int rc = circuit_build(ctx, call, c, sh, q_lin, q_mul, q_const, sigmas, stride, tab, out_key_p1s);
     if (rc) {
@@ -5904,6 +5937,28 @@ int kzg_circuit_create_lookup(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_
     }
     return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, CircuitTable{table, c, table_stride, q_lookup},
                                out_key_p1s, out);
+}
+
+int kzg_circuit_create_custom(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                              size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, const uint64_t* q_custom, size_t g,
+                              size_t custom_stride, const uint8_t* exponents, uint64_t* out_key_p1s, kzg_circuit** out) {
+    if (out) *out = nullptr;
+    PqShape sh;
+    if (!ctx || !out || log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS ||
+        t > kPqMaxColumns || !custom_shape_ok(t, sh.rot, g, exponents, nullptr) || stride < n || custom_stride < n || !q_lin || !q_mul ||
+        !q_const || !sigmas || !shifts || !q_custom)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, out_key_p1s != nullptr, "the key's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_create_custom(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, q_custom, g,
+                                                            custom_stride, exponents, out_key_p1s, out));
+    }
+    CircuitTable tab;
+    tab.q_custom = q_custom;
+    tab.g = g;
+    tab.custom_stride = custom_stride;
+    return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, tab, out_key_p1s, out, exponents);
 }
 
 int kzg_circuit_destroy(kzg_ctx* ctx, kzg_circuit* circuit) {
@@ -5974,13 +6029,34 @@ struct LookupRecord {
     const void *mult, *phi;
     const uint64_t* theta;
 };
+// the custom gates of a quotient or of an opening (section 4.27): the selectors and the exponents are the circuit's own, so the
+// record only says that the call wants the terms: with it the quotient's numerator gains G' = sum_s qx_s prod_j f_j^p[s][j] and
+// the last round's r gains sum_s (prod_j abar_j^p[s][j]) qx_s(X)
+struct CustomRecord {
+    size_t g, d_max;
+    const uint8_t* exps;
+};
+static int custom_refused(kzg_ctx* ctx, const char* what) {
+    ctx->last_error = std::string(what) + ": the circuit was created without custom gates";
+    return KZG_ERR_INVALID_ARG;
+}
+// G' of the circuit's custom gates from the t extended wire columns at d_w (column j at + 8 j N words) into d_gate (N values)
+static int cg_enqueue(kzg_ctx* ctx, hipStream_t stream, const kzg_circuit* c, const PqShape& sh, const uint32_t* d_w, uint32_t* d_gate) {
+    const uint32_t* qx = c->coset.dev() + 8 * (2 * c->t + 2) * sh.N;
+    launch_cg_gate(stream, d_w, sh.N, qx, (uint32_t)sh.N, (uint32_t)c->t, (uint32_t)c->g_custom, c->exps, fr30_arg_from_mont256(fr_pow2(14)),
+                   d_gate);
+    HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
 
 // wires (t columns of n values), z, pi (n values or null) and gate (N values or null) are host pointers, or device pointers
 // when `device`; then out_coeffs is a device pointer and out_p1s null.  With a lookup record (and no gate) m and phi are extended
-// with the wires and k_lk_constraints fills the gate's workspace with G' before the constraint kernel reads it.
+// with the wires and k_lk_constraints fills the gate's workspace with G' before the constraint kernel reads it; with a custom record
+// (and neither a gate nor a lookup) k_cg_gate fills it from the extended wires.
 static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z, const void* pi,
                                  const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const void* gate, void* out_coeffs,
-                                 uint64_t* out_p1s, bool device, const ProveRound* round = nullptr, const LookupRecord* lookup = nullptr) {
+                                 uint64_t* out_p1s, bool device, const ProveRound* round = nullptr, const LookupRecord* lookup = nullptr,
+                                 const CustomRecord* custom = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
@@ -5989,6 +6065,7 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
         ctx->last_error = "circuit lookup quotient: the circuit was created without a lookup table";
         return KZG_ERR_INVALID_ARG;
     }
+    if (custom && (!c->g_custom || gate || lookup)) return custom_refused(ctx, "circuit custom quotient");
     const size_t n = sh.n, N = sh.N, t = c->t, nbase = t + 1 + (pi ? 1 : 0), ncols = nbase + (lookup ? 2 : 0);
     if (device) {
         const size_t ob = (N - n) * 32;
@@ -6012,7 +6089,7 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
     if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, (N - n) * 32, &coef);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
-    if (rc == KZG_OK && ((gate && !device) || lookup)) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc == KZG_OK && ((gate && !device) || lookup || custom)) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
     if (rc) return rc;
     uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
     uint32_t *d_m = d_w + 8 * nbase * N, *d_phi = d_m + 8 * N;  // (with a lookup record)
@@ -6048,6 +6125,7 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
         launch_lk_constraints(s.stream, lc, sh.lg_N, (uint32_t)sh.rot, (uint32_t)c->c_tab, N, lsc.view(), (uint32_t*)d_gate);
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (rc == KZG_OK && custom) rc = cg_enqueue(ctx, s.stream, c, sh, d_w, (uint32_t*)d_gate);
     if (rc == KZG_OK) rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, (const uint32_t*)d_gate, alpha, beta, gamma, (uint32_t*)d_out);
     bool remainder = false;
     if (rc == KZG_OK)
@@ -6162,6 +6240,17 @@ size_t blind_count(size_t t, size_t e) { return 2 * t + kBlindZLen + (e - 2); }
 // N >= t n + t + 4: T~ (degree t n + t + 2) fits and at least one coefficient is left that must vanish
 bool blind_shape_ok(size_t n, size_t t, size_t e) { return e >= 2 && e * n >= t * n + t + 4; }
 size_t blind_quotient_len(size_t n, size_t t, size_t e) { return (e - 1) * n + t + 3; }
+// With custom gates of degree d_max (section 4.27) G'~ has degree n - 1 + d_max (n + 1) and T~ the degree
+// max(t n + t + 2, d_max (n + 1) - 1); this many coefficients, which is the rule above's t n + t + 3 for d_max <= t (d_max = 0: none)
+size_t blind_quotient_keep(size_t n, size_t t, size_t d_max) {
+    const size_t base = t * n + t + 3, cust = d_max * (n + 1);
+    return cust > base ? cust : base;
+}
+// ... they have to fit T~'s L_T coefficients, and N has to leave at least one coefficient that must vanish
+bool blind_custom_shape_ok(size_t n, size_t t, size_t e, size_t d_max) {
+    const size_t keep = blind_quotient_keep(n, t, d_max);
+    return blind_shape_ok(n, t, e) && keep <= blind_quotient_len(n, t, e) && e * n >= keep + 1;
+}
 bool blind_values_ok(kzg_ctx* ctx, const char* what, const uint64_t* blinders, size_t count, std::vector<hf::Fr>* out) {
     out->resize(count);
     for (size_t i = 0; i < count; i++)
@@ -6175,7 +6264,22 @@ int blind_shape_refused(kzg_ctx* ctx, const char* what) {
     ctx->last_error = std::string(what) + ": the blinded quotient needs 2^log_ext n >= t n + t + 4";
     return KZG_ERR_INVALID_ARG;
 }
+int blind_custom_shape_refused(kzg_ctx* ctx, const char* what) {
+    ctx->last_error = std::string(what) + ": the blinded quotient of custom gates of degree d needs max(t n + t + 3, d (n + 1)) "
+                      "<= (2^log_ext - 1) n + t + 3 and < 2^log_ext n";
+    return KZG_ERR_INVALID_ARG;
+}
 }  // namespace
+
+int kzg_circuit_custom_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t d_max, size_t* num_blinders, size_t* quotient_len) {
+    PqShape sh;
+    if (log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns ||
+        t + 1 > sh.rot || d_max < 1 || d_max + 1 > sh.rot || !blind_custom_shape_ok(n, t, sh.rot, d_max))
+        return KZG_ERR_INVALID_ARG;
+    if (num_blinders) *num_blinders = blind_count(t, sh.rot);
+    if (quotient_len) *quotient_len = blind_quotient_len(n, t, sh.rot);
+    return KZG_OK;
+}
 
 int kzg_circuit_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t* num_blinders, size_t* quotient_len) {
     PqShape sh;
@@ -6272,16 +6376,19 @@ int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n
 static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z,
                                          const void* pi, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                                          const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device,
-                                         const ProveRound* round = nullptr) {
+                                         const ProveRound* round = nullptr, const CustomRecord* custom = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
     const size_t n = sh.n, N = sh.N, t = c->t, e = sh.rot, ncols = t + 1 + (pi ? 1 : 0);
     if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit quotient (blinded)");
+    if (custom && !c->g_custom) return custom_refused(ctx, "circuit custom quotient (blinded)");
+    if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit custom quotient (blinded)");
     std::vector<hf::Fr> bl;
     if (!blind_values_ok(ctx, "circuit quotient (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
-    const size_t LT = blind_quotient_len(n, t, e), keep = t * n + t + 3, clen = n + kBlindZLen, Lc = n + t + 3;
+    const size_t LT = blind_quotient_len(n, t, e), keep = blind_quotient_keep(n, t, custom ? custom->d_max : 0), clen = n + kBlindZLen,
+                 Lc = n + t + 3;
     if (device) {
         const size_t ob = LT * 32;
         if (pq_overlap(out_coeffs, ob, wires, ((t - 1) * stride + n) * 32) || pq_overlap(out_coeffs, ob, z, n * 32) ||
@@ -6297,7 +6404,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     std::unique_lock<std::mutex>& lk = call.lk();
     Slot& s = call.s();
     PqBufs w;
-    void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *stack, *chunks;
+    void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *stack, *chunks, *d_gate = nullptr;
     // the blinders as the patches read them: the array as given, then a zero and the chunk blinders once more ([0, d_0 .. d_(e-3)]
     // are the low blinders of the e - 1 chunks, [d_0 ..] the high ones)
     const size_t nbl = blind_count(t, e), bl_words = 8 * (nbl + 1 + (e - 2));
@@ -6309,6 +6416,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqBlind, (t + 1) * clen * 32 + bl_words * 4, &stack);  // the blinded coefficients
     if (rc == KZG_OK && out_p1s) rc = ctx->pq_ws.get(ctx, kPqChunks, (e - 1) * Lc * 32, &chunks);
+    if (rc == KZG_OK && custom) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
     if (rc) return rc;
     uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
     uint32_t *d_c = (uint32_t*)stack, *d_bl = d_c + 8 * (t + 1) * clen;
@@ -6341,9 +6449,13 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
         if (rc == KZG_OK && pi && !round) rc = pq_extend(ctx, s.stream, src.pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
         if (rc) return rc;
     }
-    rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, nullptr, alpha, beta, gamma, (uint32_t*)d_out);
+    if (custom) {  // G'~ from the blinded wires on the coset
+        rc = cg_enqueue(ctx, s.stream, c, sh, d_w, (uint32_t*)d_gate);
+        if (rc) return rc;
+    }
+    rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, (const uint32_t*)d_gate, alpha, beta, gamma, (uint32_t*)d_out);
     if (rc) return rc;
-    // T~ has t n + t + 3 coefficients: those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
+    // T~ has t n + t + 3 coefficients (with custom gates of a degree above t: d_max (n + 1)): those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
     if (LT > keep) HIP_TRY(ctx, hipMemsetAsync((uint32_t*)coef + 8 * keep, 0, (LT - keep) * 32, s.stream));
     bool remainder = false;
     rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, keep, LT,
@@ -6351,7 +6463,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     if (rc) return rc;
     if (remainder) {
         ctx->last_error = "quotient: the blinded numerator is not divisible by X^" + std::to_string(n) +
-                          " - 1 (a coefficient of the interpolant at [t n + t + 3, N) is not zero): the constraints do not hold on the domain";
+                          " - 1 (a coefficient of the interpolant at [" + std::to_string(keep) + ", N) is not zero): the constraints do not hold on the domain";
         return KZG_ERR_REMAINDER;
     }
     if (!out_p1s) return KZG_OK;
@@ -6386,6 +6498,65 @@ int kzg_circuit_quotient_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit
     if (!ctx || !circuit || !d_wires || !d_z || !alpha || !beta || !gamma || !blinders || !d_out_coeffs) return KZG_ERR_INVALID_ARG;
     return circuit_quotient_blinded_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, alpha, beta, gamma, blinders, d_out_coeffs,
                                          out_p1s, true);
+}
+
+// ---- the custom gates of a circuit whose key holds selector x monomial terms (custom_gate_kernels.hip) -----
+static CustomRecord custom_record(const kzg_circuit* c) { return CustomRecord{c->g_custom, c->d_max, c->exps}; }
+
+// The test hook of k_cg_gate: the wires to the coset as the quotient extends them, G' on it, N values to the host.  Needs no SRS.
+int kzg_circuit_custom_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, uint64_t* out_gate_coset) {
+    if (!ctx || !circuit || !wires || !out_gate_coset) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, kzg_circuit_custom_gate(kid, circuit, wires, stride, out_gate_coset));
+    }
+    PqCall call(ctx);
+    if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
+    if (!circuit->g_custom) return custom_refused(ctx, "circuit custom gate");
+    PqShape sh;
+    if (!pq_shape(circuit->n, (size_t)1 << circuit->lg_ext, &sh) || stride < circuit->n) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, N = sh.N, t = circuit->t;
+    call.lock();
+    int rc = call.begin();
+    if (rc) return rc;
+    std::unique_lock<std::mutex>& lk = call.lk();
+    Slot& s = call.s();
+    PqBufs w;
+    void *in, *cols, *d_gate;
+    rc = pq_bufs(ctx, N, t, &w);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqIn, t * n * 32, &in);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, t * N * 32, &cols);
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc) return rc;
+    rc = pq_upload(ctx, lk, s.stream, (uint32_t*)in, wires, n, t, stride);
+    if (rc == KZG_OK) rc = pq_extend(ctx, s.stream, (const uint32_t*)in, n, n, (int)sh.lg_n, t, sh.lg_N, (uint32_t*)cols, w);
+    if (rc == KZG_OK) rc = cg_enqueue(ctx, s.stream, circuit, sh, (const uint32_t*)cols, (uint32_t*)d_gate);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out_gate_coset, d_gate, N * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (custom gate)");
+    return rc ? rc : sync_unlocked(ctx, lk, s.stream, "circuit custom gate");
+}
+
+int kzg_circuit_custom_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s) {
+    if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_custom_quotient(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders,
+                                                              out_coeffs, out_p1s));
+    }
+    CustomRecord rec{};
+    {  // the record is the circuit's: read under quotient_mu, as the bodies read it again
+        std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
+        if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
+        if (!circuit->g_custom) return custom_refused(ctx, "circuit custom quotient");
+        rec = custom_record(circuit);
+    }
+    if (blinders)
+        return circuit_quotient_blinded_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders, out_coeffs, out_p1s,
+                                             false, nullptr, &rec);
+    return circuit_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, nullptr, out_coeffs, out_p1s, false,
+                                 nullptr, nullptr, &rec);
 }
 
 // ---- the last round of a circuit's proof: linearise, open once (linearise_kernels.hip) --------------------
@@ -6431,6 +6602,17 @@ LookupLin lookup_lin(size_t n, uint32_t lg_n, size_t c, const LinChallenges& ch,
     out.on_m = hf::fr_mul(a3, F);
     out.konst = hf::fr_mul(a3, hf::fr_sub(hf::fr_mul(phiw, FT), T));
     return out;
+}
+// What the custom gates add to r (section 4.27): the g scalars prod_j abar_j^p[s][j], which the prover puts on the coefficients of
+// the qx_s and the verifier on their commitments:  r_X = r + sum_s (prod_j abar_j^p[s][j]) qx_s(X)
+void custom_lin_scalars(size_t t, size_t g, const uint8_t* exps, const hf::Fr* abar, std::vector<hf::Fr>* out) {
+    out->clear();
+    for (size_t s = 0; s < g; s++) {
+        hf::Fr m = hf::kFrOne;
+        for (size_t j = 0; j < t; j++)
+            for (unsigned k = 0; k < exps[s * t + j]; k++) m = hf::fr_mul(m, abar[j]);
+        out->push_back(m);
+    }
 }
 // The scalars of r, which the prover puts on coefficient vectors and the verifier on commitments, in the order q_0 .. q_(t-1),
 // q_M, q_C, z, sigma_(t-1), T_0 .. T_(e-2); *konst: the constant term.  abar: t values, sbar: t - 1, zw = z(zeta w),
@@ -6575,12 +6757,13 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
                              const void* t_coeffs, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                              const uint64_t* zeta, const uint64_t* v, uint64_t* out_evals, uint64_t* out_r, uint64_t* out_p1,
                              bool device, const uint64_t* blinders = nullptr, const ProveRound* round = nullptr,
-                             const LookupRecord* lookup = nullptr) {
+                             const LookupRecord* lookup = nullptr, const CustomRecord* custom = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
     if (lookup && (!c->c_tab || !round || blinders || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_lookup_prove only)
+    if (custom && (!c->g_custom || !round || lookup || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_custom_prove only)
     const size_t lc = lookup ? c->c_tab : 0;
     LinChallenges ch;
     hf::Fr vf = kFrZero;
@@ -6595,6 +6778,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     std::vector<hf::Fr> bl;
     if (blinders) {
         if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit open (blinded)");
+        if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit open (blinded)");
         if (!blind_values_ok(ctx, "circuit open (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
     }
     // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1); with
@@ -6708,6 +6892,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         lin.terms.push_back({d_m, ll.on_m});
         lin.konst = hf::fr_add(lin.konst, ll.konst);
     }
+    if (custom) {  // r_X: g more terms on the key's resident qx_s, behind every other term (blind_tails indexes the others)
+        std::vector<hf::Fr> sc;
+        custom_lin_scalars(t, c->g_custom, c->exps, &ys[1], &sc);
+        for (size_t k = 0; k < c->g_custom; k++) lin.terms.push_back({key + 8 * (2 * t + 2 + k) * n, sc[k]});
+    }
     // 3. the sums.  Point p: G_p = sum_i mult_i P_i over the polynomials of the stack opened there, with m_0 r spread over r's
     // columns: one launch per point, r is never stored.  The test hook: r itself, with its bare scalars.
     LinColumn* cols = (LinColumn*)s.ltab.h;
@@ -6754,7 +6943,8 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
                 out[k++] = lin_column(d_phi, m);
             }
         }
-        if (k > kLinMaxColumns) return KZG_ERR_INVALID_ARG;  // (3 t + e + 3 <= 32, with a lookup 3 t + e + c + 5 <= 32: cannot happen)
+        // (3 t + e + 3 <= 32, with a lookup 3 t + e + c + 5 <= 32, with custom gates 3 t + e + 3 + g <= 32: cannot happen)
+        if (k > kLinMaxColumns) return KZG_ERR_INVALID_ARG;
         ncols[p] = k;
         konst[p] = lin_const(kc);
     }
@@ -8676,11 +8866,18 @@ struct LookupClaim {
     size_t c;
     const uint64_t *theta, *m_p1, *phi_p1;
 };
+// the custom gates of a proof (section 4.27), the verifier's side: g terms and their g x t exponents; the key then has 2 t + 2 + g
+// commitments, the proof's fields are the plain proof's
+struct CustomClaim {
+    size_t g;
+    const uint8_t* exps;
+};
 int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
                         const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
                         const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
                         const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
-                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup);
+                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup,
+                        const CustomClaim* custom = nullptr);
 }  // namespace
 
 int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
@@ -8698,7 +8895,8 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
                         const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
                         const uint64_t* evals, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
                         const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
-                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup) {
+                        size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup,
+                        const CustomClaim* custom) {
     if (!key_p1s || !shifts || !wire_p1s || !z_p1 || !t_p1s || (!public_inputs && n_public) || !evals || !alpha || !beta || !gamma ||
         !zeta || !v || !proof_p1 || !setup_g1 || !setup_g2 || !valid)
         return KZG_ERR_INVALID_ARG;
@@ -8708,6 +8906,7 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
         return KZG_ERR_INVALID_ARG;
     const size_t lc = lookup ? lookup->c : 0;
     if (lookup && !lookup_shape_ok(t, sh.rot, lc)) return KZG_ERR_INVALID_ARG;
+    if (custom && (lookup || !custom_shape_ok(t, sh.rot, custom->g, custom->exps, nullptr))) return KZG_ERR_INVALID_ARG;
     const size_t e = sh.rot, npoly = 2 * t + 1 + (lookup ? lc + 2 : 0);
     LinChallenges ch;
     hf::Fr vf;
@@ -8740,6 +8939,10 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
         on_curve = load(lookup->phi_p1, &cs[t + e + 3]) && load(lookup->m_p1, &cs[t + e + 4]) && on_curve;
         for (size_t j = 0; j < lc + 1; j++) on_curve = load(key_p1s + 18 * (2 * t + 2 + j), &tmp) && on_curve;
         if (!fr_arg_below_r(lookup->theta, &theta)) return KZG_ERR_INVALID_ARG;
+    }
+    if (custom) {  // [qx_s] follow r's other commitments
+        cs.resize(t + e + 3 + custom->g);
+        for (size_t k = 0; k < custom->g; k++) on_curve = load(key_p1s + 18 * (2 * t + 2 + k), &cs[t + e + 3 + k]) && on_curve;
     }
     if (!on_curve) return KZG_ERR_INVALID_ARG;
     // PI(zeta) = sum_i PI_i L_i(zeta), L_i(zeta) = w^i (zeta^n - 1) / (n (zeta - w^i)); zeta = w^k: L_i(zeta) = [i = k]
@@ -8777,6 +8980,11 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
         sc.push_back(ll.on_phi);
         sc.push_back(ll.on_m);
         konst = hf::fr_add(konst, ll.konst);
+    }
+    if (custom) {
+        std::vector<hf::Fr> cx;
+        custom_lin_scalars(t, custom->g, custom->exps, &ys[1], &cx);
+        sc.insert(sc.end(), cx.begin(), cx.end());
     }
     auto times = [](const hf::P1& p, const hf::Fr& k) {  // the scalar multiplication of kzg_combine_claims
         uint64_t plain[4];
@@ -8908,12 +9116,43 @@ bool proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t n_public) {
     return log_ext <= kPqMaxLogExt && pq_shape(n, (size_t)1 << log_ext, &sh) && t >= KZG_CIRCUIT_MIN_COLUMNS && t <= kPqMaxColumns &&
            t + 1 <= sh.rot && n_public <= n;
 }
-// the five challenges from complete proof bytes, out: beta, gamma, alpha, zeta, v
+// h0 of a custom circuit's proof (section 4.27): a domain of its own, g and the exponents in the statement, the key's 2 t + 2 + g
+// commitments; from h1 on the chain is the plain proof's
+constexpr char kCustomProofDst[] = "kzg_mi355x/plonk-custom/v1";  // 26 bytes, hashed without the terminator
+constexpr size_t kCustomDstLen = sizeof kCustomProofDst - 1;
+void custom_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps,
+                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public) {
+    const size_t nkey = 2 * t + 2 + g;
+    std::vector<uint8_t> m(kCustomDstLen + 40 + 32 * t + g * t + 48 * nkey + 32 * n_public);
+    uint8_t* p = m.data();
+    std::memcpy(p, kCustomProofDst, kCustomDstLen);
+    p += kCustomDstLen;
+    for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)g, (uint64_t)n_public}) {
+        proof_u64be(p, x);
+        p += 8;
+    }
+    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
+    std::memcpy(p, exps, g * t);
+    p += g * t;
+    for (size_t j = 0; j < nkey; j++, p += 48) {
+        hf::P1 k;
+        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
+        hf::p1_compress(p, k);
+    }
+    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
+    hf::Sha256 s;
+    hf::sha256_init(s);
+    hf::sha256_update(s, m.data(), m.size());
+    hf::sha256_final(s, state);
+}
+// the five challenges from complete proof bytes, out: beta, gamma, alpha, zeta, v.  exps null: the plain statement, else the custom
+// circuit's with its g terms
 void proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts, const hf::Fr* pub, size_t n_public,
-                      const uint8_t* proof, hf::Fr out[5]) {
+                      const uint8_t* proof, hf::Fr out[5], size_t g = 0, const uint8_t* exps = nullptr) {
     const ProofLayout L = proof_layout(t, (size_t)1 << log_ext);
     uint8_t h[32];
-    proof_statement(h, key_p1s, n, t, log_ext, shifts, pub, n_public);
+    if (exps) custom_proof_statement(h, key_p1s, n, t, log_ext, g, exps, shifts, pub, n_public);
+    else proof_statement(h, key_p1s, n, t, log_ext, shifts, pub, n_public);
     proof_absorb(h, proof + L.wires, L.z - L.wires);
     out[0] = proof_challenge(h, 0);
     out[1] = proof_challenge(h, 1);
@@ -8956,17 +9195,20 @@ int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, un
     return KZG_OK;
 }
 
-int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
-                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
-                             size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+namespace {
+// kzg_circuit_verify_proof (exps null) and kzg_circuit_custom_verify_proof: the same bytes under the one statement or the other
+int verify_proof_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps, const uint64_t* shifts,
+                      const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                      size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
     if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
     if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
     const size_t e = (size_t)1 << log_ext;
+    if (exps && !custom_shape_ok(t, e, g, exps, nullptr)) return KZG_ERR_INVALID_ARG;
     const ProofLayout L = proof_layout(t, e);
     if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
     std::vector<hf::Fr> ks, pub;
     if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    for (size_t j = 0; j < 2 * t + 2; j++) {  // kzg_circuit_verify's check of the key, before the proof is looked at
+    for (size_t j = 0; j < 2 * t + 2 + g; j++) {  // kzg_circuit_verify's check of the key, before the proof is looked at
         hf::P1 c;
         std::memcpy(&c, key_p1s + 18 * j, sizeof c);
         if (!hf::p1_on_curve(c)) return KZG_ERR_INVALID_ARG;
@@ -8987,10 +9229,44 @@ int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsign
         return KZG_OK;
     }
     hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch);
-    return kzg_circuit_verify(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * t, pts.data() + 18 * (t + 1), public_inputs,
-                              n_public, evals.data(), ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2,
-                              g2_stride_bytes, valid);
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exps);
+    const CustomClaim claim{g, exps};
+    return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * t, pts.data() + 18 * (t + 1), public_inputs,
+                               n_public, evals.data(), ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2,
+                               g2_stride_bytes, valid, nullptr, exps ? &claim : nullptr);
+}
+}  // namespace
+
+int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                             size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    return verify_proof_impl(key_p1s, n, t, log_ext, 0, nullptr, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
+                             g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+}
+
+// ---- a custom circuit's proof as bytes (host only): the plain format under custom_proof_statement ----------
+int kzg_circuit_custom_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                        const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
+                                        size_t proof_len, uint64_t* out) {
+    if (!key_p1s || !exponents || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
+    if (!proof_shape_ok(n, t, log_ext, n_public) || !custom_shape_ok(t, (size_t)1 << log_ext, g, exponents, nullptr) ||
+        proof_len != proof_layout(t, (size_t)1 << log_ext).len)
+        return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    hf::Fr ch[5];
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exponents);
+    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
+    return KZG_OK;
+}
+
+int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                    const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
+                                    size_t proof_len, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2,
+                                    size_t g2_stride_bytes, int* valid) {
+    if (!exponents) return KZG_ERR_INVALID_ARG;
+    return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
+                             g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
 }
 
 // ---- a lookup circuit's proof as bytes (host only) -------------------------------------------------------
@@ -9144,9 +9420,13 @@ int prove_refused(kzg_ctx* ctx, const char* why) {
 }
 // wires: t columns of n values, host (stride in values) or device when `device`
 int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
-                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device) {
+                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device,
+                       bool with_custom = false) {
     PqCall call(ctx);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    if (with_custom && !c->g_custom) return prove_refused(ctx, "the circuit was created without custom gates");
+    const CustomRecord custom_rec = custom_record(c);
+    const CustomRecord* custom = with_custom ? &custom_rec : nullptr;  // kzg_circuit_custom_prove (section 4.27)
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
     const size_t n = sh.n, t = c->t, e = sh.rot, ncoef = t + 1 + (n_public ? 1 : 0);
@@ -9156,6 +9436,7 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
     if (blinders) {
         if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit prove (blinded)");
+        if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit prove (blinded)");
         if (!blind_values_ok(ctx, "circuit prove (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
     }
     const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
@@ -9206,7 +9487,8 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         }
     };
     uint8_t h[32];
-    proof_statement(h, key_p1s, n, t, c->lg_ext, ks.data(), pub.data(), n_public);
+    if (custom) custom_proof_statement(h, key_p1s, n, t, c->lg_ext, c->g_custom, c->exps, ks.data(), pub.data(), n_public);
+    else proof_statement(h, key_p1s, n, t, c->lg_ext, ks.data(), pub.data(), n_public);
 
     // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; beta, gamma
     if (device) {
@@ -9269,9 +9551,9 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     // round 3: the quotient from the resident coefficients, its chunks' commitments; zeta
     const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
     rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p,
-                                                  p1s.data() + 18 * (t + 1), true, &round_base)
+                                                  p1s.data() + 18 * (t + 1), true, &round_base, custom)
                   : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 1), true,
-                                          &round_base);
+                                          &round_base, nullptr, custom);
     if (rc) return rc;
     put_points(t + 1, e - 1);
     proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
@@ -9291,7 +9573,7 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         return true;
     };
     rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
-                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round);
+                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round, nullptr, custom);
     if (rc) return rc;
     hf::P1 w;
     std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
@@ -9508,6 +9790,24 @@ int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uin
     KZG_SINGLE_DEVICE_ONLY(ctx);
     if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
     return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true);
+}
+
+int kzg_circuit_custom_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_custom_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
+    }
+    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false, true);
+}
+
+int kzg_circuit_custom_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
+                                    const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true, true);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

@@ -443,6 +443,14 @@ struct LkColumns {
 void launch_lk_constraints(hipStream_t s, const LkColumns& cols, uint32_t log_N, uint32_t rot, uint32_t c, size_t stride,
                            const LkScalars& sc, uint32_t* d_out);
 
+// ---- custom_gate_kernels.hip: the selector x wire-monomial terms of a custom circuit on the coset ---------
+constexpr uint32_t kCgMaxTerms = 8;  // KZG_CIRCUIT_MAX_CUSTOM
+// d_out[i] = G'(x_i) = sum_{s<g} qx_s[i] prod_{j<t} f_j[i]^exps[s t + j], canonical, i < N: the t wire columns on the coset (column j
+// at + 8 j stride words), the g resident selector columns (column s at + 8 s N words), all blst_fr images; exps: g t bytes in 0..7,
+// every row with a sum >= 1; k14: 2^14 in multiplier form.  1 <= t <= kPqMaxColumns, 1 <= g <= kCgMaxTerms; d_out aliases no input
+void launch_cg_gate(hipStream_t s, const uint32_t* d_wires, size_t stride, const uint32_t* d_qx, uint32_t N, uint32_t t, uint32_t g,
+                    const uint8_t* exps, const Fr30& k14, uint32_t* d_out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

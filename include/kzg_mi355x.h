@@ -880,8 +880,8 @@ int kzg_circuit_lookup_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const 
  *     T = Num_X / (X^n - 1);   deg G' <= (d_max + 1)(n - 1), so T's share has degree below d_max n.
  * Shape rules (KZG_ERR_INVALID_ARG from kzg_circuit_create_custom): kzg_circuit_create's, 1 <= g <= KZG_CIRCUIT_MAX_CUSTOM, an
  * exponent above 7, a term of degree d_s = 0 (that is q_C), 2^log_ext < max(t + 1, d_max + 1), 3 t + 2^log_ext + 3 + g > 32 (the
- * columns the last round combines at zeta), custom_stride < n, a NULL q_custom or exponents.  Not offered: terms at the next row
- * f_j(w X), a custom circuit with a lookup table, a caller's gate_coset on top of the custom terms.
+ * columns the last round combines at zeta), custom_stride < n, a NULL q_custom or exponents.  Terms at the next row
+ * f_j(w X) are the next section's.  Not offered: a custom circuit with a lookup table, a caller's gate_coset on top of the custom terms.
  *
  * kzg_circuit_create_custom is kzg_circuit_create with q_custom (g columns of n values, column s at q_custom + 4 s custom_stride
  * u64) and exponents: the g columns are resident as values, coefficients and coset values behind the 2 t + 2 others and
@@ -943,6 +943,72 @@ int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t,
                                     size_t proof_len, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2,
                                     size_t g2_stride_bytes, int* valid);
 int kzg_circuit_custom_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t d_max, size_t* num_blinders, size_t* quotient_len);
+
+/* ---- custom gates that read the next row: f_j(w X) terms -------------------------------------------------
+ * A next-row circuit is a custom circuit of the section above with a second exponent matrix p'[s][j] in 0..7 (g x t bytes, row-major,
+ * like p).  Every row i, with i + 1 taken mod n, must satisfy
+ *     sum_j q_j f_j + q_M f_0 f_1 + q_C + PI + sum_(s<g) qx_s[i] prod_j f_j[i]^p[s][j] prod_j f_j[i+1]^p'[s][j] = 0
+ *     G'(X) = sum_s qx_s(X) prod_j f_j(X)^p[s][j] prod_j f_j(w X)^p'[s][j]
+ * with d_s = sum_j (p[s][j] + p'[s][j]), d_max = max_s d_s, R = { j : some p'[s][j] > 0 } ascending and rho = |R|.  deg G' <=
+ * (d_max + 1)(n - 1) as before: T's chunks and the plain degree rule do not change.  On the coset f_j(w x_i) is the extended wire
+ * column at index (i + e) mod N, e = 2^log_ext: no new transform, one kernel (k_cgn_gate).
+ * Shape rules (KZG_ERR_INVALID_ARG from kzg_circuit_create_custom_next and again from the verifier): kzg_circuit_create_custom's with
+ * the d_s above (1 <= g <= 8, exponents <= 7, d_s >= 1, 2^log_ext >= max(t + 1, d_max + 1), 3 t + 2^log_ext + 3 + g <= 32), rho >= 1
+ * (a circuit with no next-row exponent is kzg_circuit_create_custom's), n >= 2 (at n = 1, w = 1 and {zeta, zeta w} would hold one
+ * point twice), a NULL exponents_next.
+ *
+ * kzg_circuit_create_custom_next is kzg_circuit_create_custom with exponents_next: the same resident columns, the same out_key_p1s
+ * of (2 t + 2 + g) x 18 u64.  kzg_circuit_custom_next_gate (the kernel's test hook, no SRS) and kzg_circuit_custom_next_quotient
+ * (the plain quotient: out_coeffs N - n values, out_p1s 2^log_ext - 1 commitments) are kzg_circuit_custom_gate and
+ * kzg_circuit_custom_quotient with blinders NULL, with G' as above.  A kzg_circuit_custom_* call on a next-row handle is
+ * KZG_ERR_INVALID_ARG (ignoring p' would prove a different statement), and so is a kzg_circuit_custom_next_* call on a custom handle
+ * without p'; the plain calls (kzg_circuit_prove, ...) accept the handle and ignore all custom terms.
+ *
+ * THE PROOF.  With abar_j = f_j(zeta) and abar'_j = f_j(zeta w) for j in R:
+ *     r_N(X) = r(X) + sum_s (prod_j abar_j^p[s][j] prod_j abar'_j^p'[s][j]) qx_s(X)
+ * The stack stays [ r_N | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on three sets over the same two points: S_0 = {zeta} (r_N, the
+ * wires outside R, the sigmas), S_1 = {zeta w} (z), S_2 = {zeta, zeta w} (the wires in R).  The proof element is bit for bit
+ * kzg_open_sets of that stack on those sets with gamma = v.  Proof bytes: t + 2^log_ext + 1 compressed points in the plain format's
+ * places and 2 t + rho big-endian scalars where it has 2 t: the plain format's, then abar'_j for j in R ascending;
+ * kzg_circuit_custom_next_proof_size(t, log_ext, rho) = 48 (t + 2^log_ext + 1) + 32 (2 t + rho).  Transcript: kzg_circuit_prove's
+ * from h1 on, v drawn after all 2 t + rho evaluations, under a statement of its own, so that no custom proof verifies as a next-row
+ * proof of the same key and p, nor the reverse:
+ *     DST = ASCII "kzg_mi355x/plonk-custom-next/v1"
+ *     h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(g) | u64be(n_public) | shifts (t x 32) | exponents (g x t)
+ *                 | next-row exponents (g x t) | key commitments ((2 t + 2 + g) x 48) | public inputs)
+ * kzg_circuit_custom_next_prove / _device: kzg_circuit_custom_prove's arguments, statuses and multi-device rules.  NEXT-ROW PROOFS ARE
+ * PLAIN, NOT ZERO-KNOWLEDGE: a wire opened at two points needs a third blinder, which changes the blinder array, the patch kernels'
+ * counts and the degree rule; blinders != NULL is KZG_ERR_INVALID_ARG.  KZG_ERR_REMAINDER from the quotient for an unsatisfied term
+ * (the term of row n - 1 reads row 0) or from r_N(zeta) != 0; a failed call writes nothing to out_proof and leaves the context serving.
+ * Host only, no context: kzg_circuit_custom_next_proof_size, kzg_circuit_custom_next_proof_challenges (out: 5 x 4 u64 as
+ * kzg_circuit_proof_challenges) and kzg_circuit_custom_next_verify_proof, which rebuilds [r_N] from the key and runs kzg_verify_sets
+ * over the three sets (setup_g1: [s^j]G1 for j < 2, the largest set has two points; setup_g2: [s^j]G2 for j <= 2); bytes that do not
+ * decode give KZG_OK with *valid = 0.
+ * Not offered: blinding, rows further than i + 1, a lookup table beside the terms, submit / wait forms. */
+int kzg_circuit_create_custom_next(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
+                                   const uint64_t* sigmas, size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext,
+                                   const uint64_t* q_custom, size_t g, size_t custom_stride, const uint8_t* exponents /* g*t */,
+                                   const uint8_t* exponents_next /* g*t */, uint64_t* out_key_p1s /* (2t+2+g)x18 */, kzg_circuit** out);
+int kzg_circuit_custom_next_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride,
+                                 uint64_t* out_gate_coset /* N x 4 */);
+int kzg_circuit_custom_next_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                     const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4],
+                                     const uint64_t gamma[4], uint64_t* out_coeffs, uint64_t* out_p1s);
+int kzg_circuit_custom_next_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                                  const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders /* NULL */,
+                                  uint8_t* out_proof);
+int kzg_circuit_custom_next_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                         size_t stride, const uint64_t* public_inputs, size_t n_public,
+                                         const uint64_t* blinders /* NULL */, uint8_t* out_proof);
+int kzg_circuit_custom_next_proof_size(size_t t, unsigned log_ext, size_t rho, size_t* bytes);
+int kzg_circuit_custom_next_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                             const uint8_t* exponents, const uint8_t* exponents_next, const uint64_t* shifts,
+                                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                             uint64_t* out);
+int kzg_circuit_custom_next_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                         const uint8_t* exponents_next, const uint64_t* shifts, const uint64_t* public_inputs,
+                                         size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                                         size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
 
 /* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
  * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the

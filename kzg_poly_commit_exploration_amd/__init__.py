@@ -98,6 +98,9 @@ ABI_SYMBOLS = [
     "kzg_circuit_create_custom", "kzg_circuit_custom_gate", "kzg_circuit_custom_quotient", "kzg_circuit_custom_prove",
     "kzg_circuit_custom_prove_device", "kzg_circuit_custom_proof_challenges", "kzg_circuit_custom_verify_proof",
     "kzg_circuit_custom_blinded_sizes",
+    "kzg_circuit_create_custom_next", "kzg_circuit_custom_next_gate", "kzg_circuit_custom_next_quotient",
+    "kzg_circuit_custom_next_prove", "kzg_circuit_custom_next_prove_device", "kzg_circuit_custom_next_proof_size",
+    "kzg_circuit_custom_next_proof_challenges", "kzg_circuit_custom_next_verify_proof",
 ]
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
@@ -269,6 +272,15 @@ def load_library():
         "kzg_circuit_custom_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp]),
         "kzg_circuit_custom_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
         "kzg_circuit_custom_blinded_sizes": (i, [sz, sz, C.c_uint, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "kzg_circuit_create_custom_next": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, sz, sz, vp, vp, vp, C.POINTER(vp)]),
+        "kzg_circuit_custom_next_gate": (i, [vp, vp, vp, sz, vp]),
+        "kzg_circuit_custom_next_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_custom_next_prove": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_custom_next_prove_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "kzg_circuit_custom_next_proof_size": (i, [sz, C.c_uint, sz, C.POINTER(sz)]),
+        "kzg_circuit_custom_next_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, vp, sz, vp, sz, vp]),
+        "kzg_circuit_custom_next_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz,
+                                                     C.POINTER(C.c_int)]),
         "kzg_circuit_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_quotient_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_column_device": (i, [vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(sz)]),
@@ -1618,10 +1630,12 @@ class Engine:
         circ.c = c
         return circ
 
-    def circuit_create_custom(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, q_custom, exponents, n=None, want_key=True):
+    def circuit_create_custom(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, q_custom, exponents, n=None, want_key=True,
+                              exponents_next=None):
         """kzg_circuit_create_custom: circuit_create's arguments, q_custom a (g, custom_stride, 4) array whose first n rows per
         column count and exponents a (g, t) array of bytes in 0..7 -> a Circuit with g custom terms; its key has 2 t + 2 + g
-        commitments, circuit_create's and then qx[0..g)"""
+        commitments, circuit_create's and then qx[0..g).  With exponents_next, a second (g, t) array:
+        kzg_circuit_create_custom_next, a next-row circuit (Circuit.rho wires are read at the row after too)"""
         a, t, stride, n = self._columns(q_lin, n)
         b = np.ascontiguousarray(sigmas, dtype=np.uint64).reshape(t, stride, 4)
         qm = np.ascontiguousarray(q_mul, dtype=np.uint64).reshape(-1, 4)
@@ -1635,12 +1649,26 @@ class Engine:
         assert sh.shape[0] == t, "one coset shift per column"
         p1s = np.zeros((2 * t + 2 + g, 18), dtype=np.uint64) if want_key else None
         h = C.c_void_p()
-        self._pq_check(self._lib.kzg_circuit_create_custom(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh), log_ext,
-                                                           _ptr(qx), g, qx.shape[1], _ptr(ex), None if p1s is None else _ptr(p1s),
-                                                           C.byref(h)))
+        if exponents_next is None:
+            self._pq_check(self._lib.kzg_circuit_create_custom(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh),
+                                                               log_ext, _ptr(qx), g, qx.shape[1], _ptr(ex),
+                                                               None if p1s is None else _ptr(p1s), C.byref(h)))
+        else:
+            exn = np.ascontiguousarray(exponents_next, dtype=np.uint8).reshape(g, t)
+            self._pq_check(self._lib.kzg_circuit_create_custom_next(self._h, _ptr(a), _ptr(qm), _ptr(qc), _ptr(b), n, t, stride, _ptr(sh),
+                                                                    log_ext, _ptr(qx), g, qx.shape[1], _ptr(ex), _ptr(exn),
+                                                                    None if p1s is None else _ptr(p1s), C.byref(h)))
         circ = Circuit(self, h, n, t, log_ext, None if p1s is None else [G1Point(p) for p in p1s])
         circ.g, circ.exponents = g, ex
+        if exponents_next is not None:
+            circ.exponents_next, circ.rho = exn, int(np.count_nonzero(exn.any(axis=0)))
         return circ
+
+    def circuit_create_custom_next(self, q_lin, q_mul, q_const, sigmas, shifts, log_ext, q_custom, exponents, exponents_next, n=None,
+                                   want_key=True):
+        """kzg_circuit_create_custom_next: circuit_create_custom with the (g, t) next-row exponents p'"""
+        return self.circuit_create_custom(q_lin, q_mul, q_const, sigmas, shifts, log_ext, q_custom, exponents, n=n, want_key=want_key,
+                                          exponents_next=exponents_next)
 
     # -- zero-knowledge blinding (DESIGN.md 4.24) --
     def blind_evaluations_limbs(self, evals, blinders, n=None):
@@ -1798,6 +1826,7 @@ class Circuit:
         self.n, self.t, self.log_ext, self.key = n, t, log_ext, key
         self.c = 0  # table columns (circuit_create_lookup)
         self.g, self.exponents = 0, None  # custom terms and their (g, t) exponents (circuit_create_custom)
+        self.rho, self.exponents_next = 0, None  # wires read at the next row and p' (circuit_create_custom_next)
 
     def close(self):
         if getattr(self, "_c", None) and getattr(self._eng, "_h", None):
@@ -1882,7 +1911,7 @@ class Circuit:
         return self._split_evals(ev), r
 
     # -- the blinded rounds --
-    def _prove(self, fn, e, wires_arg, stride, public_inputs, blinders):
+    def _prove(self, fn, e, wires_arg, stride, public_inputs, blinders, size=None):
         assert self.key is not None, "prove: the circuit was created without its key commitments"
         rows = np.ascontiguousarray(np.stack([c.p1 for c in self.key]), dtype=np.uint64)
         pub = None
@@ -1890,7 +1919,7 @@ class Circuit:
             pub = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
         bl = None if blinders is None else np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
         assert bl is None or bl.shape[0] == 2 * self.t + 3 + (1 << self.log_ext) - 2
-        out = np.zeros(circuit_proof_size(self.t, self.log_ext), dtype=np.uint8)
+        out = np.zeros(circuit_proof_size(self.t, self.log_ext) if size is None else size, dtype=np.uint8)
         e._pq_check(fn(e._h, self._c, _ptr(rows), wires_arg, stride, _ptr(pub) if pub is not None else None,
                        0 if pub is None else pub.shape[0], _ptr(bl) if bl is not None else None, _ptr(out)))
         return out.tobytes()
@@ -2101,6 +2130,53 @@ class Circuit:
         e = self._eng
         return self._prove(e._lib.kzg_circuit_custom_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
                            public_inputs, blinders)
+
+    # -- custom gates that read the next row --
+    def custom_next_gate(self, wires, n=None, engine=None):
+        """kzg_circuit_custom_next_gate (test hook, no SRS): wires a (t, stride, 4) array -> the (N, 4) values of
+        G' = sum_s qx_s prod_j f_j(X)^p[s][j] f_j(w X)^p'[s][j] on the coset"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        out = np.zeros((n << self.log_ext, 4), dtype=np.uint64)
+        e._pq_check(e._lib.kzg_circuit_custom_next_gate(e._h, self._c, _ptr(a), stride, _ptr(out)))
+        return out
+
+    def custom_next_quotient(self, wires, z, alpha, beta, gamma, public_inputs=None, n=None, want_coeffs=True, want_commitments=True,
+                             engine=None):
+        """kzg_circuit_custom_next_quotient: quotient() without a gate, with the next-row terms made from the wires on the
+        device -> as it returns"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert zz.shape[0] >= n and (pi is None or pi.shape[0] >= n)
+        ext = 1 << self.log_ext
+        al, bl, gl = alpha.limbs(), beta.limbs(), gamma.limbs()
+        coeffs = np.zeros(((ext - 1) * n, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros((ext - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_custom_next_quotient(e._h, self._c, _ptr(a), stride, _ptr(zz), None if pi is None else _ptr(pi),
+                                                            _ptr(al), _ptr(bl), _ptr(gl), None if coeffs is None else _ptr(coeffs),
+                                                            None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def _next_proof_size(self):
+        return 48 * (self.t + (1 << self.log_ext) + 1) + 32 * (2 * self.t + max(self.rho, 1))
+
+    def custom_next_prove(self, wires, public_inputs=None, blinders=None, n=None, engine=None):
+        """kzg_circuit_custom_next_prove: prove()'s arguments on a circuit of circuit_create_custom_next -> the proof bytes
+        (circuit_custom_next_proof_size of them).  Next-row proofs are plain: blinders other than None are refused"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        return self._prove(e._lib.kzg_circuit_custom_next_prove, e, _ptr(a), stride, public_inputs, blinders, self._next_proof_size())
+
+    def custom_next_prove_device(self, d_wires, public_inputs=None, blinders=None, stride=None):
+        """kzg_circuit_custom_next_prove_device: the wires in a device buffer of the circuit's (single-device) context"""
+        e = self._eng
+        return self._prove(e._lib.kzg_circuit_custom_next_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
+                           public_inputs, blinders, self._next_proof_size())
 
     def column_device(self, which, form):
         """kzg_circuit_column_device: (device pointer, length) of a resident column, read-only"""
@@ -2396,6 +2472,47 @@ def circuit_custom_verify_proof(key, n, log_ext, exponents, shifts, public_input
     _check(load_library().kzg_circuit_custom_verify_proof(_ptr(rows), n, t, log_ext, ex.shape[0], _ptr(ex), _ptr(ks),
                                                           _ptr(pub) if pub is not None else None, n_public, _ptr(buf), buf.shape[0],
                                                           _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def circuit_custom_next_proof_size(t, log_ext, rho):
+    """kzg_circuit_custom_next_proof_size: the bytes of a next-row proof, 48 (t + 2^log_ext + 1) + 32 (2 t + rho)"""
+    out = C.c_size_t(0)
+    _check(load_library().kzg_circuit_custom_next_proof_size(t, log_ext, rho, C.byref(out)))
+    return out.value
+
+
+def _next_exponents(exponents_next, ex):
+    exn = np.ascontiguousarray(exponents_next, dtype=np.uint8).reshape(-1, ex.shape[1])
+    assert exn.shape == ex.shape
+    return exn
+
+
+def circuit_custom_next_proof_challenges(key, n, log_ext, exponents, exponents_next, shifts, public_inputs, proof):
+    """kzg_circuit_custom_next_proof_challenges: (beta, gamma, alpha, zeta, v) of the hashed transcript from complete proof bytes.
+    key: the 2 t + 2 + g commitments of circuit_create_custom_next, exponents and exponents_next its (g, t) bytes."""
+    t, ex, rows, ks, pub, n_public, buf = _custom_proof_statement(key, exponents, shifts, public_inputs, proof)
+    exn = _next_exponents(exponents_next, ex)
+    out = np.zeros((5, 4), dtype=np.uint64)
+    _check(load_library().kzg_circuit_custom_next_proof_challenges(_ptr(rows), n, t, log_ext, ex.shape[0], _ptr(ex), _ptr(exn), _ptr(ks),
+                                                                   _ptr(pub) if pub is not None else None, n_public, _ptr(buf),
+                                                                   buf.shape[0], _ptr(out)))
+    return tuple(Scalar.from_limbs(out[i]) for i in range(5))
+
+
+def circuit_custom_next_verify_proof(key, n, log_ext, exponents, exponents_next, shifts, public_inputs, proof, setup_g1, setup_g2):
+    """kzg_circuit_custom_next_verify_proof on the host: decodes the proof bytes, derives the challenges, forms [r_N], checks the
+    opening on the three sets.  False also for bytes that do not decode.  setup_g1: [s^j]G1 for j < 2 (the set {zeta, zeta w} has an
+    interpolant of degree 1), setup_g2: [s^j]G2 for j <= 2."""
+    t, ex, rows, ks, pub, n_public, buf = _custom_proof_statement(key, exponents, shifts, public_inputs, proof)
+    exn = _next_exponents(exponents_next, ex)
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 2 and g2.shape[0] >= 3
+    ok = C.c_int(0)
+    _check(load_library().kzg_circuit_custom_next_verify_proof(_ptr(rows), n, t, log_ext, ex.shape[0], _ptr(ex), _ptr(exn), _ptr(ks),
+                                                               _ptr(pub) if pub is not None else None, n_public, _ptr(buf),
+                                                               buf.shape[0], _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

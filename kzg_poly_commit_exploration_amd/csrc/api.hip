@@ -379,6 +379,11 @@ struct kzg_circuit {
     // 2 t + 2, the exponents p[s][j] at s t + j and the largest row sum; calls of section 4.22 .. 4.25 ignore them too
     size_t g_custom = 0, d_max = 0;
     uint8_t exps[kCgMaxTerms * kPqMaxColumns] = {};
+    // a next-row circuit (kzg_circuit_create_custom_next, section 4.28): the second matrix p'[s][j] at s t + j, and the rho >= 1
+    // wires with a next-row exponent, ascending (rho = 0: a custom circuit of section 4.27, or none); d_max counts both matrices
+    uint8_t exps_next[kCgMaxTerms * kPqMaxColumns] = {};
+    size_t rho = 0;
+    uint8_t next_wires[kPqMaxColumns] = {};
     uint64_t shifts[4 * kPqMaxColumns] = {};
     DevBuf values;  // cols() x n
     DevBuf coeffs;  // cols() x n
@@ -5857,14 +5862,15 @@ static bool lookup_shape_ok(size_t t, size_t e, size_t c) {
 // the shape rules of a custom circuit (section 4.27): 1 <= g <= 8 terms, every exponent in 0..7 and every term of degree d_s >= 1
 // (degree 0 is q_C), deg G' <= (d_max + 1) (n - 1) asks for e >= d_max + 1, and the last round's combination at zeta has the plain
 // proof's 3 t + e + 3 columns and g more.  *d_max: the largest d_s
-static bool custom_shape_ok(size_t t, size_t e, size_t g, const uint8_t* exps, size_t* d_max) {
+// exps_next (or null): the second matrix of a next-row circuit (section 4.28), whose exponents count towards d_s
+static bool custom_shape_ok(size_t t, size_t e, size_t g, const uint8_t* exps, size_t* d_max, const uint8_t* exps_next = nullptr) {
     if (!exps || g < 1 || g > kCgMaxTerms || t < 1 || t > kPqMaxColumns || e < t + 1 || 3 * t + e + 3 + g > kLinMaxColumns) return false;
     size_t dm = 0;
     for (size_t s = 0; s < g; s++) {
         size_t d = 0;
         for (size_t j = 0; j < t; j++) {
-            if (exps[s * t + j] > 7) return false;
-            d += exps[s * t + j];
+            if (exps[s * t + j] > 7 || (exps_next && exps_next[s * t + j] > 7)) return false;
+            d += exps[s * t + j] + (exps_next ? exps_next[s * t + j] : 0);
         }
         if (d < 1) return false;
         dm = d > dm ? d : dm;
@@ -5872,11 +5878,28 @@ static bool custom_shape_ok(size_t t, size_t e, size_t g, const uint8_t* exps, s
     if (d_max) *d_max = dm;
     return e >= dm + 1;
 }
-// kzg_circuit_create, kzg_circuit_create_lookup (tab.c != 0) and kzg_circuit_create_custom (tab.g != 0, exps: its g t exponents)
-// after their argument checks, on a single-device context
+// the shape rules of a next-row circuit (section 4.28): custom_shape_ok's with d_s over both matrices, n >= 2 (at n = 1 the sets
+// {zeta, zeta w} would hold one point twice) and rho >= 1 wires with a next-row exponent (none: that is a custom circuit).
+// next_wires (or null): those wires, ascending; returns rho, 0 for a shape that is refused
+static size_t next_shape_rho(size_t n, size_t t, size_t e, size_t g, const uint8_t* exps, const uint8_t* exps_next, size_t* d_max,
+                             uint8_t* next_wires) {
+    if (n < 2 || !exps_next || !custom_shape_ok(t, e, g, exps, d_max, exps_next)) return 0;
+    size_t rho = 0;
+    for (size_t j = 0; j < t; j++) {
+        bool used = false;
+        for (size_t s = 0; s < g; s++) used = used || exps_next[s * t + j] != 0;
+        if (!used) continue;
+        if (next_wires) next_wires[rho] = (uint8_t)j;
+        rho++;
+    }
+    return rho;
+}
+// kzg_circuit_create, kzg_circuit_create_lookup (tab.c != 0), kzg_circuit_create_custom (tab.g != 0, exps: its g t exponents) and
+// kzg_circuit_create_custom_next (exps_next too) after their argument checks, on a single-device context
 static int circuit_create_impl(kzg_ctx* ctx, const PqShape& sh, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
                                const uint64_t* sigmas, size_t t, size_t stride, const uint64_t* shifts, const CircuitTable& tab,
-                               uint64_t* out_key_p1s, kzg_circuit** out, const uint8_t* exps = nullptr) {
+                               uint64_t* out_key_p1s, kzg_circuit** out, const uint8_t* exps = nullptr,
+                               const uint8_t* exps_next = nullptr) {
     const size_t n = sh.n;
     PqCall call(ctx);
     kzg_circuit* c = new kzg_circuit();
@@ -5890,6 +5913,10 @@ static int circuit_create_impl(kzg_ctx* ctx, const PqShape& sh, const uint64_t* 
         c->g_custom = tab.g;
         std::memcpy(c->exps, exps, tab.g * t);
         (void)custom_shape_ok(t, sh.rot, tab.g, exps, &c->d_max);
+        if (exps_next) {
+            std::memcpy(c->exps_next, exps_next, tab.g * t);
+            c->rho = next_shape_rho(n, t, sh.rot, tab.g, exps, exps_next, &c->d_max, c->next_wires);
+        }
     }
     std::memcpy(c->shifts, shifts, 32 * t);
     int rc = circuit_build(ctx, call, c, sh, q_lin, q_mul, q_const, sigmas, stride, tab, out_key_p1s);
@@ -5939,26 +5966,46 @@ int kzg_circuit_create_lookup(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_
                                out_key_p1s, out);
 }
 
-int kzg_circuit_create_custom(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
-                              size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, const uint64_t* q_custom, size_t g,
-                              size_t custom_stride, const uint8_t* exponents, uint64_t* out_key_p1s, kzg_circuit** out) {
+// kzg_circuit_create_custom (exponents_next null) and kzg_circuit_create_custom_next
+static int circuit_create_custom(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                                 size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, const uint64_t* q_custom, size_t g,
+                                 size_t custom_stride, const uint8_t* exponents, const uint8_t* exponents_next, bool next,
+                                 uint64_t* out_key_p1s, kzg_circuit** out) {
     if (out) *out = nullptr;
     PqShape sh;
     if (!ctx || !out || log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS ||
-        t > kPqMaxColumns || !custom_shape_ok(t, sh.rot, g, exponents, nullptr) || stride < n || custom_stride < n || !q_lin || !q_mul ||
-        !q_const || !sigmas || !shifts || !q_custom)
+        t > kPqMaxColumns || stride < n || custom_stride < n || !q_lin || !q_mul || !q_const || !sigmas || !shifts || !q_custom)
+        return KZG_ERR_INVALID_ARG;
+    if (next ? !next_shape_rho(n, t, sh.rot, g, exponents, exponents_next, nullptr, nullptr)
+             : !custom_shape_ok(t, sh.rot, g, exponents, nullptr))
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
         kzg_ctx* kid = whole_srs_kid(ctx, out_key_p1s != nullptr, "the key's commitments need");
         if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_create_custom(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, q_custom, g,
-                                                            custom_stride, exponents, out_key_p1s, out));
+        return forwarded(ctx, kid, circuit_create_custom(kid, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, q_custom, g,
+                                                        custom_stride, exponents, exponents_next, next, out_key_p1s, out));
     }
     CircuitTable tab;
     tab.q_custom = q_custom;
     tab.g = g;
     tab.custom_stride = custom_stride;
-    return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, tab, out_key_p1s, out, exponents);
+    return circuit_create_impl(ctx, sh, q_lin, q_mul, q_const, sigmas, t, stride, shifts, tab, out_key_p1s, out, exponents,
+                               next ? exponents_next : nullptr);
+}
+
+int kzg_circuit_create_custom(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const, const uint64_t* sigmas,
+                              size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext, const uint64_t* q_custom, size_t g,
+                              size_t custom_stride, const uint8_t* exponents, uint64_t* out_key_p1s, kzg_circuit** out) {
+    return circuit_create_custom(ctx, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, q_custom, g, custom_stride, exponents,
+                                 nullptr, false, out_key_p1s, out);
+}
+
+int kzg_circuit_create_custom_next(kzg_ctx* ctx, const uint64_t* q_lin, const uint64_t* q_mul, const uint64_t* q_const,
+                                   const uint64_t* sigmas, size_t n, size_t t, size_t stride, const uint64_t* shifts, unsigned log_ext,
+                                   const uint64_t* q_custom, size_t g, size_t custom_stride, const uint8_t* exponents,
+                                   const uint8_t* exponents_next, uint64_t* out_key_p1s, kzg_circuit** out) {
+    return circuit_create_custom(ctx, q_lin, q_mul, q_const, sigmas, n, t, stride, shifts, log_ext, q_custom, g, custom_stride, exponents,
+                                 exponents_next, true, out_key_p1s, out);
 }
 
 int kzg_circuit_destroy(kzg_ctx* ctx, kzg_circuit* circuit) {
@@ -6032,19 +6079,35 @@ struct LookupRecord {
 // the custom gates of a quotient or of an opening (section 4.27): the selectors and the exponents are the circuit's own, so the
 // record only says that the call wants the terms: with it the quotient's numerator gains G' = sum_s qx_s prod_j f_j^p[s][j] and
 // the last round's r gains sum_s (prod_j abar_j^p[s][j]) qx_s(X)
+// A next-row circuit's record (section 4.28) also carries rho >= 1: G' reads the wires at the next row (k_cgn_gate), the last round
+// opens the rho wires of next_wires at zeta w too and r gains sum_s (prod_j abar_j^p[s][j] abar'_j^p'[s][j]) qx_s(X)
 struct CustomRecord {
     size_t g, d_max;
     const uint8_t* exps;
+    size_t rho = 0;
+    const uint8_t* exps_next = nullptr;
+    const uint8_t* next_wires = nullptr;
 };
 static int custom_refused(kzg_ctx* ctx, const char* what) {
     ctx->last_error = std::string(what) + ": the circuit was created without custom gates";
     return KZG_ERR_INVALID_ARG;
 }
-// G' of the circuit's custom gates from the t extended wire columns at d_w (column j at + 8 j N words) into d_gate (N values)
+// a call of section 4.27 on a next-row handle would ignore p' and prove a different statement; a call of section 4.28 needs p'
+static int custom_kind_refused(kzg_ctx* ctx, const char* what, bool want_next) {
+    ctx->last_error = std::string(what) + (want_next ? ": the circuit was created without next-row terms (kzg_circuit_create_custom_next)"
+                                                     : ": the circuit has next-row terms, which the kzg_circuit_custom_next_* calls take");
+    return KZG_ERR_INVALID_ARG;
+}
+// G' of the circuit's custom gates from the t extended wire columns at d_w (column j at + 8 j N words) into d_gate (N values):
+// k_cgn_gate for a next-row circuit (the next row is e = N / n points on), k_cg_gate otherwise
 static int cg_enqueue(kzg_ctx* ctx, hipStream_t stream, const kzg_circuit* c, const PqShape& sh, const uint32_t* d_w, uint32_t* d_gate) {
     const uint32_t* qx = c->coset.dev() + 8 * (2 * c->t + 2) * sh.N;
-    launch_cg_gate(stream, d_w, sh.N, qx, (uint32_t)sh.N, (uint32_t)c->t, (uint32_t)c->g_custom, c->exps, fr30_arg_from_mont256(fr_pow2(14)),
-                   d_gate);
+    if (c->rho)
+        launch_cgn_gate(stream, d_w, sh.N, qx, (uint32_t)sh.N, (uint32_t)sh.rot, (uint32_t)c->t, (uint32_t)c->g_custom, c->exps, c->exps_next,
+                        fr30_arg_from_mont256(fr_pow2(14)), d_gate);
+    else
+        launch_cg_gate(stream, d_w, sh.N, qx, (uint32_t)sh.N, (uint32_t)c->t, (uint32_t)c->g_custom, c->exps, fr30_arg_from_mont256(fr_pow2(14)),
+                       d_gate);
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
@@ -6066,6 +6129,7 @@ static int circuit_quotient_impl(kzg_ctx* ctx, const kzg_circuit* c, const void*
         return KZG_ERR_INVALID_ARG;
     }
     if (custom && (!c->g_custom || gate || lookup)) return custom_refused(ctx, "circuit custom quotient");
+    if (custom && custom->rho != c->rho) return custom_kind_refused(ctx, "circuit custom quotient", custom->rho != 0);
     const size_t n = sh.n, N = sh.N, t = c->t, nbase = t + 1 + (pi ? 1 : 0), ncols = nbase + (lookup ? 2 : 0);
     if (device) {
         const size_t ob = (N - n) * 32;
@@ -6384,6 +6448,7 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     const size_t n = sh.n, N = sh.N, t = c->t, e = sh.rot, ncols = t + 1 + (pi ? 1 : 0);
     if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit quotient (blinded)");
     if (custom && !c->g_custom) return custom_refused(ctx, "circuit custom quotient (blinded)");
+    if (custom && (custom->rho || c->rho)) return custom_kind_refused(ctx, "circuit custom quotient (blinded)", false);
     if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit custom quotient (blinded)");
     std::vector<hf::Fr> bl;
     if (!blind_values_ok(ctx, "circuit quotient (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
@@ -6501,18 +6566,23 @@ int kzg_circuit_quotient_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit
 }
 
 // ---- the custom gates of a circuit whose key holds selector x monomial terms (custom_gate_kernels.hip) -----
-static CustomRecord custom_record(const kzg_circuit* c) { return CustomRecord{c->g_custom, c->d_max, c->exps}; }
+static CustomRecord custom_record(const kzg_circuit* c) {
+    return CustomRecord{c->g_custom, c->d_max, c->exps, c->rho, c->exps_next, c->next_wires};
+}
 
 // The test hook of k_cg_gate: the wires to the coset as the quotient extends them, G' on it, N values to the host.  Needs no SRS.
-int kzg_circuit_custom_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, uint64_t* out_gate_coset) {
+// (next: kzg_circuit_custom_next_gate, the test hook of k_cgn_gate, on a next-row handle only; else on a custom handle only)
+static int custom_gate_impl(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, uint64_t* out_gate_coset,
+                            bool next) {
     if (!ctx || !circuit || !wires || !out_gate_coset) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
-        return forwarded(ctx, kid, kzg_circuit_custom_gate(kid, circuit, wires, stride, out_gate_coset));
+        return forwarded(ctx, kid, custom_gate_impl(kid, circuit, wires, stride, out_gate_coset, next));
     }
     PqCall call(ctx);
     if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
     if (!circuit->g_custom) return custom_refused(ctx, "circuit custom gate");
+    if (next != (circuit->rho != 0)) return custom_kind_refused(ctx, "circuit custom gate", next);
     PqShape sh;
     if (!pq_shape(circuit->n, (size_t)1 << circuit->lg_ext, &sh) || stride < circuit->n) return KZG_ERR_INVALID_ARG;
     const size_t n = sh.n, N = sh.N, t = circuit->t;
@@ -6534,22 +6604,30 @@ int kzg_circuit_custom_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint
     if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out_gate_coset, d_gate, N * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (custom gate)");
     return rc ? rc : sync_unlocked(ctx, lk, s.stream, "circuit custom gate");
 }
+int kzg_circuit_custom_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, uint64_t* out_gate_coset) {
+    return custom_gate_impl(ctx, circuit, wires, stride, out_gate_coset, false);
+}
+int kzg_circuit_custom_next_gate(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, uint64_t* out_gate_coset) {
+    return custom_gate_impl(ctx, circuit, wires, stride, out_gate_coset, true);
+}
 
-int kzg_circuit_custom_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+// (next: kzg_circuit_custom_next_quotient, never blinded, on a next-row handle only; else on a custom handle only)
+static int custom_quotient_impl(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
                                 const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
-                                const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s) {
+                                const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s, bool next) {
     if (!ctx || !circuit || !wires || !z || !alpha || !beta || !gamma) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
         kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
         if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_custom_quotient(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders,
-                                                              out_coeffs, out_p1s));
+        return forwarded(ctx, kid, custom_quotient_impl(kid, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders, out_coeffs,
+                                                       out_p1s, next));
     }
     CustomRecord rec{};
     {  // the record is the circuit's: read under quotient_mu, as the bodies read it again
         std::lock_guard<std::mutex> lkq(ctx->quotient_mu);
         if (!circuit_alive(ctx, circuit)) return circuit_foreign(ctx);
         if (!circuit->g_custom) return custom_refused(ctx, "circuit custom quotient");
+        if (next != (circuit->rho != 0)) return custom_kind_refused(ctx, "circuit custom quotient", next);
         rec = custom_record(circuit);
     }
     if (blinders)
@@ -6557,6 +6635,16 @@ int kzg_circuit_custom_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const 
                                              false, nullptr, &rec);
     return circuit_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, nullptr, out_coeffs, out_p1s, false,
                                  nullptr, nullptr, &rec);
+}
+int kzg_circuit_custom_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                const uint64_t* blinders, uint64_t* out_coeffs, uint64_t* out_p1s) {
+    return custom_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders, out_coeffs, out_p1s, false);
+}
+int kzg_circuit_custom_next_quotient(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                     const uint64_t* public_inputs, const uint64_t alpha[4], const uint64_t beta[4],
+                                     const uint64_t gamma[4], uint64_t* out_coeffs, uint64_t* out_p1s) {
+    return custom_quotient_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, nullptr, out_coeffs, out_p1s, true);
 }
 
 // ---- the last round of a circuit's proof: linearise, open once (linearise_kernels.hip) --------------------
@@ -6605,12 +6693,18 @@ LookupLin lookup_lin(size_t n, uint32_t lg_n, size_t c, const LinChallenges& ch,
 }
 // What the custom gates add to r (section 4.27): the g scalars prod_j abar_j^p[s][j], which the prover puts on the coefficients of
 // the qx_s and the verifier on their commitments:  r_X = r + sum_s (prod_j abar_j^p[s][j]) qx_s(X)
-void custom_lin_scalars(size_t t, size_t g, const uint8_t* exps, const hf::Fr* abar, std::vector<hf::Fr>* out) {
+// A next-row circuit (section 4.28; exps_next not null) has the scalars prod_j abar_j^p[s][j] abar'_j^p'[s][j] with abar'_j =
+// f_j(zeta w): abar_next holds the rho values of the wires next_wires[0 .. rho), in that order.  One function for prover and verifier
+void custom_lin_scalars(size_t t, size_t g, const uint8_t* exps, const hf::Fr* abar, std::vector<hf::Fr>* out,
+                        const uint8_t* exps_next = nullptr, size_t rho = 0, const uint8_t* next_wires = nullptr,
+                        const hf::Fr* abar_next = nullptr) {
     out->clear();
     for (size_t s = 0; s < g; s++) {
         hf::Fr m = hf::kFrOne;
         for (size_t j = 0; j < t; j++)
             for (unsigned k = 0; k < exps[s * t + j]; k++) m = hf::fr_mul(m, abar[j]);
+        for (size_t i = 0; exps_next && i < rho; i++)
+            for (unsigned k = 0; k < exps_next[s * t + next_wires[i]]; k++) m = hf::fr_mul(m, abar_next[i]);
         out->push_back(m);
     }
 }
@@ -6764,6 +6858,9 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
     if (lookup && (!c->c_tab || !round || blinders || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_lookup_prove only)
     if (custom && (!c->g_custom || !round || lookup || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_custom_prove only)
+    if (custom && (custom->rho != c->rho || (custom->rho && (blinders || c->n < 2)))) return KZG_ERR_INVALID_ARG;
+    // a next-row round (section 4.28): the rho wires of R are opened on {zeta, zeta w}; out_evals then has 2 t + rho values
+    const size_t rho = custom ? custom->rho : 0;
     const size_t lc = lookup ? c->c_tab : 0;
     LinChallenges ch;
     hf::Fr vf = kFrZero;
@@ -6784,16 +6881,24 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1); with
     // a lookup record it goes on with [ tab_0 .. tab_(c-1) | q_K | phi ], phi in the second set
     const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
+    // a next-row round: a third set {zeta, zeta w} for the wires of R -- still two distinct points, zeta the first of the plan
     std::vector<uint32_t> set_of(npoly, 0);
     set_of[2 * t] = 1;
     set_of[npoly - 1] = 1;
-    const uint32_t set_len[2] = {1, 1};
-    uint64_t zs[8];
+    std::vector<int> next_at(npoly, -1);  // polynomial i = 1 + j of the stack with j = R[k]: k
+    for (size_t k = 0; k < rho; k++) {
+        set_of[1 + custom->next_wires[k]] = 2;
+        next_at[1 + custom->next_wires[k]] = (int)k;
+    }
+    const uint32_t set_len[3] = {1, 1, 2};
+    const size_t nsets = rho ? 3 : 2;
+    uint64_t zs[16];
     std::memcpy(zs, ch.zeta.l, 32);
     std::memcpy(zs + 4, zeta_w.l, 32);
+    std::memcpy(zs + 8, zs, 64);
     SetsPlan plan;
     std::string why;
-    if (!sets_plan(plan, why, npoly, set_of.data(), set_len, 2, zs, vf.l)) {
+    if (!sets_plan(plan, why, npoly, set_of.data(), set_len, nsets, zs, vf.l)) {
         ctx->last_error = "circuit open: " + why;
         return KZG_ERR_INVALID_ARG;
     }
@@ -6836,12 +6941,12 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     const Fr30* d_tab = (const Fr30*)s.stab.d;
     for (size_t r = 0; r < plan.npts; r++) combine_fill_powers(tab + r * kCombineTabGamma, plan.pts[r]);
     const size_t last_pt = plan.npts - 1;  // where zeta w sits
-    for (size_t i = 0; i <= t; i++) {      // the passes' own sums are not used: every weight is one
+    for (size_t i = 0; i <= t + rho; i++) {  // the passes' own sums are not used: every weight is one
         tab[kSetsMultBase + i] = fr30_arg_from_mont256(hf::kFrOne);
-        s.ssel.host()[i] = (uint32_t)i;
+        s.ssel.host()[i] = i <= t ? (uint32_t)i : (uint32_t)custom->next_wires[i - t - 1];  // (behind the identity: the wires of R)
     }
-    HIP_TRY(ctx, hipMemcpyAsync(s.stab.d, s.stab.h, (kSetsMultBase + t + 1) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s.ssel.dev(), s.ssel.host(), (t + 1) * 4, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.stab.d, s.stab.h, (kSetsMultBase + t + 1 + rho) * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.ssel.dev(), s.ssel.host(), (t + 1 + rho) * 4, hipMemcpyHostToDevice, s.stream));
     const uint32_t* key = c->coeffs.dev();
     uint32_t* d_vals = s.svals.dev();
     launch_sets_combine(s.stream, d_f, (uint32_t)n, (uint32_t)(ncoef - 1), n, d_tab, d_tab + kSetsMultBase, s.ssel.dev(), 0, false,
@@ -6857,11 +6962,16 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         launch_sets_combine(s.stream, d_phi, (uint32_t)n, 1, n, d_tab + last_pt * kCombineTabGamma, d_tab + kSetsMultBase, s.ssel.dev(), 0,
                             false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * (2 * t + 2 + lc));
     }
+    if (rho)  // [npoly, npoly + rho) the wires of R at zeta w: one pass over the wires' coefficients, selected by the list of R
+        launch_sets_combine(s.stream, d_f, (uint32_t)n, (uint32_t)rho, n, d_tab + last_pt * kCombineTabGamma, d_tab + kSetsMultBase + t + 1,
+                            s.ssel.dev() + t + 1, 0, false, (uint32_t*)scratch, s.cpart.dev(), d_vals + 8 * npoly);
     HIP_TRY(ctx, hipGetLastError());
     rc = sync_unlocked(ctx, lk, s.stream, "circuit open (evaluations)");
     if (rc) return rc;
     std::vector<hf::Fr> ys(npoly, kFrZero);  // the stack's values: 0, abar, sbar, z(zeta w)
+    std::vector<hf::Fr> ys_next(rho);        // ... and the second value of a wire of R, at zeta w: one value per (polynomial, point)
     const uint32_t* hv = s.svals.host();
+    for (size_t k = 0; k < rho; k++) std::memcpy(ys_next[k].l, hv + 8 * (npoly + k), 32);
     for (size_t j = 0; j < t; j++) std::memcpy(ys[1 + j].l, hv + 8 * j, 32);
     for (size_t j = 0; j + 1 < t; j++) std::memcpy(ys[1 + t + j].l, hv + 8 * (t + 1 + j), 32);
     std::memcpy(ys[2 * t].l, hv + 8 * 2 * t, 32);
@@ -6877,10 +6987,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         ys[2 * t] = hf::fr_add(ys[2 * t], hf::fr_mul(cw, Z));
     }
     for (size_t i = 1; i < npoly; i++) std::memcpy(out_evals + 4 * (i - 1), ys[i].l, 32);
+    for (size_t k = 0; k < rho; k++) std::memcpy(out_evals + 4 * (npoly - 1 + k), ys_next[k].l, 32);
     if (round && round->derive_v) {  // v is fixed after the evaluations: the plan's points, lists and sizes stay, its multipliers follow v
         uint64_t v_now[4];
         if (!round->derive_v(out_evals, v_now) || !fr_arg_below_r(v_now, &vf) ||
-            !sets_plan(plan, why, npoly, set_of.data(), set_len, 2, zs, vf.l))
+            !sets_plan(plan, why, npoly, set_of.data(), set_len, nsets, zs, vf.l))
             return KZG_ERR_INVALID_ARG;
     }
     LinPoly lin;
@@ -6894,7 +7005,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     }
     if (custom) {  // r_X: g more terms on the key's resident qx_s, behind every other term (blind_tails indexes the others)
         std::vector<hf::Fr> sc;
-        custom_lin_scalars(t, c->g_custom, c->exps, &ys[1], &sc);
+        custom_lin_scalars(t, c->g_custom, c->exps, &ys[1], &sc, rho ? c->exps_next : nullptr, rho, c->next_wires, ys_next.data());
         for (size_t k = 0; k < c->g_custom; k++) lin.terms.push_back({key + 8 * (2 * t + 2 + k) * n, sc[k]});
     }
     // 3. the sums.  Point p: G_p = sum_i mult_i P_i over the polynomials of the stack opened there, with m_0 r spread over r's
@@ -6906,7 +7017,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         std::memcpy(out.l, k.l, 32);
         return out;
     };
-    uint32_t* d_y = d_vals + 8 * npoly;  // out(p) of point p at d_y + 8 p
+    uint32_t* d_y = d_vals + 8 * (npoly + rho);  // out(p) of point p at d_y + 8 p
     if (!v) {
         for (size_t k = 0; k < lin.terms.size(); k++) cols[k] = lin_column(lin.terms[k].coeffs, lin.terms[k].scalar);
         HIP_TRY(ctx, hipMemcpyAsync(s.ltab.d, s.ltab.h, lin.terms.size() * sizeof(LinColumn), hipMemcpyHostToDevice, s.stream));
@@ -6927,7 +7038,8 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         for (uint32_t e = plan.off[p]; e < plan.off[p + 1]; e++) {
             const uint32_t i = plan.sel[e];
             const hf::Fr& m = plan.mult[e];
-            want[p] = hf::fr_add(want[p], hf::fr_mul(m, ys[i]));
+            // (point 0 is zeta, point 1 zeta w: a wire of R has a value at each)
+            want[p] = hf::fr_add(want[p], hf::fr_mul(m, p == 1 && next_at[i] >= 0 ? ys_next[next_at[i]] : ys[i]));
             if (i == 0) {
                 for (const LinTerm& term : lin.terms) out[k++] = lin_column(term.coeffs, hf::fr_mul(m, term.scalar));
                 kc = hf::fr_mul(m, lin.konst);
@@ -6963,7 +7075,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (rc) return rc;
     // G_zeta(zeta) = m_0 r(zeta) + sum_(i >= 1) mult_i y_i with m_0 = 1: r vanishes at zeta exactly when the two agree
     hf::Fr got;
-    std::memcpy(got.l, hv + 8 * npoly, 32);
+    std::memcpy(got.l, hv + 8 * (npoly + rho), 32);
     if (!fr_equal(got, want[0])) return lin_remainder(ctx);
     // 4. the scans and the MSM of kzg_open_sets, unchanged
     rc = pq_srs_status(ctx, true, L - 1);  // (the waits dropped the mutex)
@@ -8868,9 +8980,12 @@ struct LookupClaim {
 };
 // the custom gates of a proof (section 4.27), the verifier's side: g terms and their g x t exponents; the key then has 2 t + 2 + g
 // commitments, the proof's fields are the plain proof's
+// A next-row proof (section 4.28) adds the second matrix and the rho values f_j(zeta w), j in R ascending
 struct CustomClaim {
     size_t g;
     const uint8_t* exps;
+    const uint8_t* exps_next = nullptr;
+    const uint64_t* evals_next = nullptr;
 };
 int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
                         const uint64_t z_p1[18], const uint64_t* t_p1s, const uint64_t* public_inputs, size_t n_public,
@@ -8906,7 +9021,12 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
         return KZG_ERR_INVALID_ARG;
     const size_t lc = lookup ? lookup->c : 0;
     if (lookup && !lookup_shape_ok(t, sh.rot, lc)) return KZG_ERR_INVALID_ARG;
-    if (custom && (lookup || !custom_shape_ok(t, sh.rot, custom->g, custom->exps, nullptr))) return KZG_ERR_INVALID_ARG;
+    if (custom && (lookup || (!custom->exps_next && !custom_shape_ok(t, sh.rot, custom->g, custom->exps, nullptr))))
+        return KZG_ERR_INVALID_ARG;
+    uint8_t next_wires[kPqMaxColumns] = {};
+    const size_t rho = custom && custom->exps_next
+                           ? next_shape_rho(n, t, sh.rot, custom->g, custom->exps, custom->exps_next, nullptr, next_wires) : 0;
+    if (custom && custom->exps_next && (!rho || !custom->evals_next)) return KZG_ERR_INVALID_ARG;
     const size_t e = sh.rot, npoly = 2 * t + 1 + (lookup ? lc + 2 : 0);
     LinChallenges ch;
     hf::Fr vf;
@@ -8916,6 +9036,9 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
     std::vector<hf::Fr> ys(npoly, kFrZero), pub(n_public), ks(t);  // the stack's values: 0, abar, sbar, z(zeta w)
     for (size_t i = 1; i < npoly; i++)
         if (!fr_arg_below_r(evals + 4 * (i - 1), &ys[i])) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ys_next(rho);  // the second value of a wire of R, at zeta w
+    for (size_t k = 0; k < rho; k++)
+        if (!fr_arg_below_r(custom->evals_next + 4 * k, &ys_next[k])) return KZG_ERR_INVALID_ARG;
     for (size_t i = 0; i < n_public; i++)
         if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return KZG_ERR_INVALID_ARG;
     for (size_t j = 0; j < t; j++)
@@ -8983,7 +9106,7 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
     }
     if (custom) {
         std::vector<hf::Fr> cx;
-        custom_lin_scalars(t, custom->g, custom->exps, &ys[1], &cx);
+        custom_lin_scalars(t, custom->g, custom->exps, &ys[1], &cx, custom->exps_next, rho, next_wires, ys_next.data());
         sc.insert(sc.end(), cx.begin(), cx.end());
     }
     auto times = [](const hf::P1& p, const hf::Fr& k) {  // the scalar multiplication of kzg_combine_claims
@@ -8995,7 +9118,7 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
     for (size_t k = 0; k < cs.size(); k++) r = hf::p1_add(r, times(cs[k], sc[k]));
     r = hf::p1_normalize(r);
     // the stack, its sets and values
-    std::vector<uint64_t> stack(18 * npoly), yl(4 * npoly);
+    std::vector<uint64_t> stack(18 * npoly), yl(4 * (npoly + rho));
     std::memcpy(stack.data(), &r, sizeof r);
     std::memcpy(stack.data() + 18, wire_p1s, 18 * 8 * t);
     std::memcpy(stack.data() + 18 * (1 + t), key_p1s + 18 * (t + 2), 18 * 8 * (t - 1));
@@ -9004,17 +9127,23 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
         std::memcpy(stack.data() + 18 * (2 * t + 1), key_p1s + 18 * (2 * t + 2), 18 * 8 * (lc + 1));
         std::memcpy(stack.data() + 18 * (2 * t + 2 + lc), lookup->phi_p1, 18 * 8);
     }
-    for (size_t i = 0; i < npoly; i++) std::memcpy(yl.data() + 4 * i, ys[i].l, 32);
+    // a next-row proof: the wires of R on a third set {zeta, zeta w}, two values each, in the set's order
     std::vector<uint32_t> set_of(npoly, 0);
     set_of[2 * t] = 1;
     set_of[npoly - 1] = 1;
-    const uint32_t set_len[2] = {1, 1};
+    for (size_t k = 0; k < rho; k++) set_of[1 + next_wires[k]] = 2;
+    for (size_t i = 0, at = 0, k = 0; i < npoly; i++) {
+        std::memcpy(yl.data() + 4 * at++, ys[i].l, 32);
+        if (set_of[i] == 2) std::memcpy(yl.data() + 4 * at++, ys_next[k++].l, 32);
+    }
+    const uint32_t set_len[3] = {1, 1, 2};
     const hf::Fr zeta_w = hf::fr_mul(ch.zeta, hf::fr_domain_root(sh.lg_n));
-    uint64_t zs[8];
+    uint64_t zs[16];
     std::memcpy(zs, ch.zeta.l, 32);
     std::memcpy(zs + 4, zeta_w.l, 32);
-    return kzg_verify_sets(stack.data(), npoly, set_of.data(), set_len, 2, zs, yl.data(), v, proof_p1, setup_g1, g1_stride_bytes, setup_g2,
-                           g2_stride_bytes, valid);
+    std::memcpy(zs + 8, zs, 64);
+    return kzg_verify_sets(stack.data(), npoly, set_of.data(), set_len, rho ? 3 : 2, zs, yl.data(), v, proof_p1, setup_g1, g1_stride_bytes,
+                           setup_g2, g2_stride_bytes, valid);
 }
 }  // namespace
 
@@ -9101,13 +9230,14 @@ void proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_
 struct ProofLayout {
     size_t wires, z, chunks, evals, w, len;
 };
-ProofLayout proof_layout(size_t t, size_t e) {
+// (rho: the scalars a next-row proof has behind the plain proof's 2 t, section 4.28)
+ProofLayout proof_layout(size_t t, size_t e, size_t rho = 0) {
     ProofLayout L;
     L.wires = 0;
     L.z = 48 * t;
     L.chunks = L.z + 48;
     L.evals = L.chunks + 48 * (e - 1);
-    L.w = L.evals + 64 * t;
+    L.w = L.evals + 32 * (2 * t + rho);
     L.len = L.w + 48;
     return L;
 }
@@ -9120,13 +9250,16 @@ bool proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t n_public) {
 // commitments; from h1 on the chain is the plain proof's
 constexpr char kCustomProofDst[] = "kzg_mi355x/plonk-custom/v1";  // 26 bytes, hashed without the terminator
 constexpr size_t kCustomDstLen = sizeof kCustomProofDst - 1;
+// h0 of a next-row circuit's proof (section 4.28; exps_next not null): a third domain, the second matrix behind the first
+constexpr char kNextProofDst[] = "kzg_mi355x/plonk-custom-next/v1";  // 31 bytes, hashed without the terminator
+constexpr size_t kNextDstLen = sizeof kNextProofDst - 1;
 void custom_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps,
-                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public) {
-    const size_t nkey = 2 * t + 2 + g;
-    std::vector<uint8_t> m(kCustomDstLen + 40 + 32 * t + g * t + 48 * nkey + 32 * n_public);
+                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public, const uint8_t* exps_next = nullptr) {
+    const size_t nkey = 2 * t + 2 + g, dst_len = exps_next ? kNextDstLen : kCustomDstLen;
+    std::vector<uint8_t> m(dst_len + 40 + 32 * t + (exps_next ? 2 : 1) * g * t + 48 * nkey + 32 * n_public);
     uint8_t* p = m.data();
-    std::memcpy(p, kCustomProofDst, kCustomDstLen);
-    p += kCustomDstLen;
+    std::memcpy(p, exps_next ? kNextProofDst : kCustomProofDst, dst_len);
+    p += dst_len;
     for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)g, (uint64_t)n_public}) {
         proof_u64be(p, x);
         p += 8;
@@ -9134,6 +9267,10 @@ void custom_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n
     for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
     std::memcpy(p, exps, g * t);
     p += g * t;
+    if (exps_next) {
+        std::memcpy(p, exps_next, g * t);
+        p += g * t;
+    }
     for (size_t j = 0; j < nkey; j++, p += 48) {
         hf::P1 k;
         std::memcpy(&k, key_p1s + 18 * j, sizeof k);
@@ -9146,12 +9283,13 @@ void custom_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n
     hf::sha256_final(s, state);
 }
 // the five challenges from complete proof bytes, out: beta, gamma, alpha, zeta, v.  exps null: the plain statement, else the custom
-// circuit's with its g terms
+// circuit's with its g terms; exps_next too: the next-row circuit's, whose proof has rho more scalars, all absorbed before v
 void proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts, const hf::Fr* pub, size_t n_public,
-                      const uint8_t* proof, hf::Fr out[5], size_t g = 0, const uint8_t* exps = nullptr) {
-    const ProofLayout L = proof_layout(t, (size_t)1 << log_ext);
+                      const uint8_t* proof, hf::Fr out[5], size_t g = 0, const uint8_t* exps = nullptr, const uint8_t* exps_next = nullptr,
+                      size_t rho = 0) {
+    const ProofLayout L = proof_layout(t, (size_t)1 << log_ext, rho);
     uint8_t h[32];
-    if (exps) custom_proof_statement(h, key_p1s, n, t, log_ext, g, exps, shifts, pub, n_public);
+    if (exps) custom_proof_statement(h, key_p1s, n, t, log_ext, g, exps, shifts, pub, n_public, exps_next);
     else proof_statement(h, key_p1s, n, t, log_ext, shifts, pub, n_public);
     proof_absorb(h, proof + L.wires, L.z - L.wires);
     out[0] = proof_challenge(h, 0);
@@ -9196,15 +9334,19 @@ int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, un
 }
 
 namespace {
-// kzg_circuit_verify_proof (exps null) and kzg_circuit_custom_verify_proof: the same bytes under the one statement or the other
+// kzg_circuit_verify_proof (exps null) and kzg_circuit_custom_verify_proof: the same bytes under the one statement or the other;
+// kzg_circuit_custom_next_verify_proof (exps_next too): rho more scalars under the third
 int verify_proof_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps, const uint64_t* shifts,
                       const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
-                      size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+                      size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid,
+                      const uint8_t* exps_next = nullptr) {
     if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
     if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
     const size_t e = (size_t)1 << log_ext;
-    if (exps && !custom_shape_ok(t, e, g, exps, nullptr)) return KZG_ERR_INVALID_ARG;
-    const ProofLayout L = proof_layout(t, e);
+    if (exps && !exps_next && !custom_shape_ok(t, e, g, exps, nullptr)) return KZG_ERR_INVALID_ARG;
+    const size_t rho = exps_next ? next_shape_rho(n, t, e, g, exps, exps_next, nullptr, nullptr) : 0;
+    if (exps_next && !rho) return KZG_ERR_INVALID_ARG;
+    const ProofLayout L = proof_layout(t, e, rho);
     if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
     std::vector<hf::Fr> ks, pub;
     if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
@@ -9214,12 +9356,13 @@ int verify_proof_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_
         if (!hf::p1_on_curve(c)) return KZG_ERR_INVALID_ARG;
     }
     // decode: t + e + 1 points (on the curve; no subgroup check) and 2 t canonical scalars; a proof that does not decode is invalid
-    std::vector<uint64_t> pts(18 * (t + e)), evals(4 * 2 * t);
+    // (a next-row proof: 2 t + rho scalars)
+    std::vector<uint64_t> pts(18 * (t + e)), evals(4 * (2 * t + rho));
     uint64_t w_p1[18];
     bool decoded = true;
     for (size_t i = 0; i < t + e && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
     decoded = decoded && kzg_g1_uncompress(proof + L.w, w_p1) == KZG_OK;
-    for (size_t i = 0; i < 2 * t && decoded; i++) {
+    for (size_t i = 0; i < 2 * t + rho && decoded; i++) {
         hf::Fr v = kFrZero;
         decoded = proof_fr_from_be(proof + L.evals + 32 * i, &v);
         std::memcpy(evals.data() + 4 * i, v.l, 32);
@@ -9229,8 +9372,8 @@ int verify_proof_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_
         return KZG_OK;
     }
     hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exps);
-    const CustomClaim claim{g, exps};
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exps, exps_next, rho);
+    const CustomClaim claim{g, exps, exps_next, exps_next ? evals.data() + 4 * 2 * t : nullptr};
     return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * t, pts.data() + 18 * (t + 1), public_inputs,
                                n_public, evals.data(), ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2,
                                g2_stride_bytes, valid, nullptr, exps ? &claim : nullptr);
@@ -9267,6 +9410,40 @@ int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t,
     if (!exponents) return KZG_ERR_INVALID_ARG;
     return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
                              g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+}
+
+// ---- a next-row circuit's proof as bytes (host only): rho more scalars under a statement of its own --------
+int kzg_circuit_custom_next_proof_size(size_t t, unsigned log_ext, size_t rho, size_t* bytes) {
+    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext) || rho < 1 ||
+        rho > t)
+        return KZG_ERR_INVALID_ARG;
+    *bytes = proof_layout(t, (size_t)1 << log_ext, rho).len;
+    return KZG_OK;
+}
+
+int kzg_circuit_custom_next_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                             const uint8_t* exponents, const uint8_t* exponents_next, const uint64_t* shifts,
+                                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                             uint64_t* out) {
+    if (!key_p1s || !exponents || !exponents_next || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
+    if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
+    const size_t rho = next_shape_rho(n, t, (size_t)1 << log_ext, g, exponents, exponents_next, nullptr, nullptr);
+    if (!rho || proof_len != proof_layout(t, (size_t)1 << log_ext, rho).len) return KZG_ERR_INVALID_ARG;
+    std::vector<hf::Fr> ks, pub;
+    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
+    hf::Fr ch[5];
+    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exponents, exponents_next, rho);
+    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
+    return KZG_OK;
+}
+
+int kzg_circuit_custom_next_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                         const uint8_t* exponents_next, const uint64_t* shifts, const uint64_t* public_inputs,
+                                         size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                                         size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    if (!exponents || !exponents_next) return KZG_ERR_INVALID_ARG;
+    return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
+                             g1_stride_bytes, setup_g2, g2_stride_bytes, valid, exponents_next);
 }
 
 // ---- a lookup circuit's proof as bytes (host only) -------------------------------------------------------
@@ -9421,12 +9598,16 @@ int prove_refused(kzg_ctx* ctx, const char* why) {
 // wires: t columns of n values, host (stride in values) or device when `device`
 int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
                        const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device,
-                       bool with_custom = false) {
+                       bool with_custom = false, bool with_next = false) {
     PqCall call(ctx);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     if (with_custom && !c->g_custom) return prove_refused(ctx, "the circuit was created without custom gates");
+    if (with_custom && with_next != (c->rho != 0)) return custom_kind_refused(ctx, "circuit prove", with_next);
+    if (with_next && blinders) return prove_refused(ctx, "next-row proofs are not blinded: a wire opened at two points needs a third blinder");
     const CustomRecord custom_rec = custom_record(c);
-    const CustomRecord* custom = with_custom ? &custom_rec : nullptr;  // kzg_circuit_custom_prove (section 4.27)
+    // kzg_circuit_custom_prove (section 4.27) or, with rho more evaluations, kzg_circuit_custom_next_prove (section 4.28)
+    const CustomRecord* custom = with_custom ? &custom_rec : nullptr;
+    const size_t rho = custom ? custom->rho : 0;
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
     const size_t n = sh.n, t = c->t, e = sh.rot, ncoef = t + 1 + (n_public ? 1 : 0);
@@ -9476,8 +9657,8 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         return KZG_OK;
     };
     const size_t np1 = t + e;  // the proof's points before the evaluations: wires, [z], chunks
-    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * 2 * t);
-    const ProofLayout L = proof_layout(t, e);
+    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * (2 * t + rho));
+    const ProofLayout L = proof_layout(t, e, rho);
     std::vector<uint8_t> proof(L.len);
     auto put_points = [&](size_t first, size_t count) {
         for (size_t i = first; i < first + count; i++) {
@@ -9487,7 +9668,8 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         }
     };
     uint8_t h[32];
-    if (custom) custom_proof_statement(h, key_p1s, n, t, c->lg_ext, c->g_custom, c->exps, ks.data(), pub.data(), n_public);
+    if (custom)
+        custom_proof_statement(h, key_p1s, n, t, c->lg_ext, c->g_custom, c->exps, ks.data(), pub.data(), n_public, rho ? c->exps_next : nullptr);
     else proof_statement(h, key_p1s, n, t, c->lg_ext, ks.data(), pub.data(), n_public);
 
     // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; beta, gamma
@@ -9562,7 +9744,7 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     // rounds 4 and 5: the evaluations, v from them, r(zeta) = 0, the opening
     ProveRound last_round = round_base;
     last_round.derive_v = [&](const uint64_t* ev, uint64_t v[4]) {
-        for (size_t i = 0; i < 2 * t; i++) {
+        for (size_t i = 0; i < 2 * t + rho; i++) {
             hf::Fr y;
             std::memcpy(y.l, ev + 4 * i, 32);
             proof_fr_to_be(y, proof.data() + L.evals + 32 * i);
@@ -9808,6 +9990,26 @@ int kzg_circuit_custom_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, co
     KZG_SINGLE_DEVICE_ONLY(ctx);
     if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
     return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true, true);
+}
+
+int kzg_circuit_custom_next_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
+                                  const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid,
+                         kzg_circuit_custom_next_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
+    }
+    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false, true, true);
+}
+
+int kzg_circuit_custom_next_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                         size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                         uint8_t* out_proof) {
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
+    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true, true, true);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

@@ -451,6 +451,13 @@ constexpr uint32_t kCgMaxTerms = 8;  // KZG_CIRCUIT_MAX_CUSTOM
 void launch_cg_gate(hipStream_t s, const uint32_t* d_wires, size_t stride, const uint32_t* d_qx, uint32_t N, uint32_t t, uint32_t g,
                     const uint8_t* exps, const Fr30& k14, uint32_t* d_out);
 
+// ---- custom_next_kernels.hip: the terms of a next-row circuit on the coset -------------------------------
+// d_out[i] = G'(x_i) = sum_{s<g} qx_s[i] prod_{j<t} f_j[i]^exps[s t + j] f_j[(i + e) mod N]^exps_next[s t + j], canonical, i < N:
+// launch_cg_gate's arguments, the second matrix (g t bytes in 0..7, every row sum of both matrices together >= 1) and e = N / n,
+// 1 <= e < N, the distance on the coset of the domain's next row
+void launch_cgn_gate(hipStream_t s, const uint32_t* d_wires, size_t stride, const uint32_t* d_qx, uint32_t N, uint32_t e, uint32_t t,
+                     uint32_t g, const uint8_t* exps, const uint8_t* exps_next, const Fr30& k14, uint32_t* d_out);
+
 // ---- combine_kernels.hip: F = sum gamma^i P_i and the values P_i(z) in one pass -------------------
 constexpr uint32_t kCombineThreads = 256;     // lanes of a workgroup
 constexpr uint32_t kCombineTile = 2048;       // consecutive indices per workgroup: lane l takes l + 256 m, m < 8

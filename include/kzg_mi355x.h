@@ -1010,6 +1010,69 @@ int kzg_circuit_custom_next_verify_proof(const uint64_t* key_p1s, size_t n, size
                                          size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
                                          size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
 
+/* ---- many proofs of one key with one pairing check ------------------------------------------------------
+ * kzg_circuit_verify_proofs_batch: proof k (k < count) is at proofs + k proof_len, its public inputs (n_public blst_fr) at
+ * public_inputs + 4 k pi_stride; every proof is claimed for the one key key_p1s.  g = 0 with exponents NULL is the plain
+ * statement (kzg_mi355x/plonk/v1, kzg_circuit_verify_proof's), g >= 1 the custom statement (kzg_mi355x/plonk-custom/v1) with
+ * kzg_circuit_custom_verify_proof's key of 2 t + 2 + g commitments and its g x t exponents; both share one proof format.
+ * With A_0k = sum_(i < 2t) v^i C_i - [sum v^i y_i]G1 and A_1k = v^(2t) [z] - [v^(2t) z(zeta w)]G1 of proof k as kzg_verify_sets
+ * forms them from kzg_circuit_verify's stack, and weights rho_k = a_k + b_k lambda (a_k, b_k uniform 64-bit from getrandom(2),
+ * fresh on every call), the device forms
+ *     P0 = sum_k rho_k (-zeta_k w A_0k - zeta_k A_1k - zeta_k^2 w W_k)
+ *     P1 = sum_k rho_k (A_0k + A_1k + zeta_k (1 + w) W_k)
+ *     P2 = -sum_k rho_k W_k
+ * and the host pairs once: e(P0, [1]G2) e(P1, [s]G2) e(P2, [s^2]G2) == 1, three pairs and one final exponentiation whatever
+ * count is.  *valid = 1 when every proof is valid; a batch holding an invalid proof is accepted with probability at most 2^-128;
+ * count = 0 gives *valid = 1.  setup_g2 is read at indices 0, 1 and 2 as kzg_circuit_verify reads it; [1]G1 is the context's
+ * SRS[0].  The host hashes the transcripts (at most 16 threads), draws the weights and pairs; the decoding of the points and the
+ * evaluations, PI(zeta_k), the scalars, every scalar multiplication and the sums run on the device: about t + e + 6 ladders per
+ * proof and 2 (2 t + 3 + g) for the key.
+ * A proof whose bytes do not decode (a point, or an evaluation not below r) or with a point outside G1 (the order-r subgroup)
+ * is invalid, not an error: KZG_OK, *valid = 0 and *bad_index (may be NULL) the least such proof.  THIS IS STRICTER THAN
+ * kzg_circuit_verify_proof, which checks the curve equation only: the endomorphism the device's ladders use acts as lambda
+ * only on G1, so a point outside it cannot be multiplied and is refused.  When every proof decodes and only the pairing fails,
+ * *bad_index = SIZE_MAX: the call does not locate the proof; bisect, or fall back to kzg_circuit_verify_proof.
+ * Errors, checked in this order, *valid untouched (kzg_last_error names the proof):
+ *   KZG_ERR_INVALID_ARG: a required pointer NULL; n, t, log_ext, n_public (g, exponents) not a shape of
+ *     kzg_circuit_verify_proof (kzg_circuit_custom_verify_proof); proof_len not kzg_circuit_proof_size's; count >
+ *     KZG_VERIFY_MAX_PROOFS; n < 2 (w = 1: the two point sets coincide); pi_stride < n_public with count > 1; a shift or a public
+ *     input not below r; a key commitment off the curve; a G2 input off the twist; then, from the device, a key commitment
+ *     outside G1.
+ *   KZG_ERR_NO_SRS: the SRS is empty.  KZG_ERR_HIP: a device call failed, the OS random source did, or the host ran out of memory
+ *     or threads for a large batch.
+ * The call holds one slot; thread safety and multi-device contexts as kzg_verify_openings_batch (a replicated SRS forwards to
+ * one device, a range-split one returns KZG_ERR_INVALID_ARG); the workspaces grow on demand and stay with the context.
+ * Not offered: lookup proofs and next-row proofs (their stacks and sets differ), proofs of different keys in one call, locating
+ * the invalid proof, hashing on the device.
+ * A call costs 12 to 13 ms whatever count is up to a thousand proofs (two dependent ladder launches, the sums, the pairing), so
+ * for few proofs kzg_circuit_verify_proof on the host's threads stays the faster route.  Measured (t = 3,
+ * e = 4, n = 256, 16 public inputs, the process held to 16 CPUs, medians of five): 13.0 ms against 8.7 for a loop of
+ * kzg_circuit_verify_proof over 16 threads at 16 proofs, 12.6 against 16.9 at 32 (the ranges do not overlap), 12.7 against 93 at
+ * 256, 13.6 against 355 at 1024, 15.2 against 1347 at 4096.  The crossover lies between 16 and 32 proofs; below it keep using the
+ * host verifier. */
+#define KZG_VERIFY_MAX_PROOFS (1u << 16)
+int kzg_circuit_verify_proofs_batch(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                    const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public,
+                                    size_t pi_stride /* values between proofs */, const uint8_t* proofs, size_t proof_len, size_t count,
+                                    const void* setup_g2, size_t g2_stride_bytes, int* valid, size_t* bad_index /* may be NULL */);
+/* test hook: the same with the caller's weights (count x blst_fr, any field elements below r; checked after the G2 inputs) instead
+ * of random ones; out_p1s receives P0, P1, P2, normalised like kzg_open's output (infinity three times when a proof does not
+ * decode), and *valid comes from the same pairing */
+int kzg_circuit_verify_proofs_lincomb(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                      const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public,
+                                      size_t pi_stride, const uint8_t* proofs, size_t proof_len, size_t count, const void* setup_g2,
+                                      size_t g2_stride_bytes, const uint64_t* weights /* count x blst_fr */, uint64_t out_p1s[54],
+                                      int* valid, size_t* bad_index);
+/* test hook: ... and with the caller's challenges (count x 5 x blst_fr in the order beta, gamma, alpha, zeta, v, below r; checked
+ * after the weights) in the place of the hashed ones, so that a test can put zeta on the domain (zeta = 1, zeta = w^i), which no
+ * hashed transcript reaches: the device's scalar kernels then take the paths L_0(1) = 1 and PI(w^i) = PI_i */
+int kzg_circuit_verify_proofs_lincomb_challenges(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                                 const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs,
+                                                 size_t n_public, size_t pi_stride, const uint8_t* proofs, size_t proof_len, size_t count,
+                                                 const void* setup_g2, size_t g2_stride_bytes, const uint64_t* weights /* count x blst_fr */,
+                                                 const uint64_t* challenges /* count x 5 x blst_fr */, uint64_t out_p1s[54], int* valid,
+                                                 size_t* bad_index);
+
 /* ---- zero-knowledge circuit proofs: the wires, z and T's chunks blinded -------------------------------
  * Notation as above: t wires, e = 2^log_ext, N = e n, Z_H = X^n - 1.  A blinded column agrees with the plain one on H, so z, the
  * gate and the permutation are computed from the same values as without blinding, and kzg_circuit_verify accepts a blinded proof

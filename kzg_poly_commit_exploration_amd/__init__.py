@@ -101,7 +101,9 @@ ABI_SYMBOLS = [
     "kzg_circuit_create_custom_next", "kzg_circuit_custom_next_gate", "kzg_circuit_custom_next_quotient",
     "kzg_circuit_custom_next_prove", "kzg_circuit_custom_next_prove_device", "kzg_circuit_custom_next_proof_size",
     "kzg_circuit_custom_next_proof_challenges", "kzg_circuit_custom_next_verify_proof",
+    "kzg_circuit_verify_proofs_batch", "kzg_circuit_verify_proofs_lincomb", "kzg_circuit_verify_proofs_lincomb_challenges",
 ]
+KZG_VERIFY_MAX_PROOFS = 1 << 16
 KZG_SRS_FIRST_IS_GENERATOR = 1
 KZG_SRS_OK, KZG_SRS_G2_BAD, KZG_SRS_INFINITY, KZG_SRS_NOT_IN_G1, KZG_SRS_FIRST_NOT_GENERATOR, KZG_SRS_NOT_POWERS = range(6)
 KZG_ORDER_NATURAL = 0
@@ -272,6 +274,12 @@ def load_library():
         "kzg_circuit_custom_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp]),
         "kzg_circuit_custom_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
         "kzg_circuit_custom_blinded_sizes": (i, [sz, sz, C.c_uint, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "kzg_circuit_verify_proofs_batch": (i, [vp, vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, sz, vp, sz, sz, vp, sz, C.POINTER(i),
+                                                C.POINTER(sz)]),
+        "kzg_circuit_verify_proofs_lincomb": (i, [vp, vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, sz, vp, sz, sz, vp, sz, vp, vp,
+                                                  C.POINTER(i), C.POINTER(sz)]),
+        "kzg_circuit_verify_proofs_lincomb_challenges": (i, [vp, vp, sz, sz, C.c_uint, sz, vp, vp, vp, sz, sz, vp, sz, sz, vp, sz, vp, vp, vp,
+                                                             C.POINTER(i), C.POINTER(sz)]),
         "kzg_circuit_create_custom_next": (i, [vp, vp, vp, vp, vp, sz, sz, sz, vp, C.c_uint, vp, sz, sz, vp, vp, vp, C.POINTER(vp)]),
         "kzg_circuit_custom_next_gate": (i, [vp, vp, vp, sz, vp]),
         "kzg_circuit_custom_next_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
@@ -1066,6 +1074,69 @@ class Engine:
         ok = C.c_int(0)
         _check(self._lib.kzg_verify_openings_lincomb_bytes(self._h, *a, _ptr(w), _ptr(lhs), _ptr(rhs), C.byref(ok)), self._h)
         return G1Point(lhs), G1Point(rhs), bool(ok.value)
+
+    def _circuit_verify_batch_args(self, key, n, log_ext, shifts, public_inputs, proofs, setup_g2, exponents, n_public):
+        t = len(shifts)
+        ex = None if exponents is None else np.ascontiguousarray(exponents, dtype=np.uint8).reshape(-1, t)
+        g = 0 if ex is None else ex.shape[0]
+        assert len(key) == 2 * t + 2 + g
+        rows = np.ascontiguousarray(np.stack([c.p1 for c in key]), dtype=np.uint64)
+        proofs = [bytes(p) for p in proofs]
+        count = len(proofs)
+        proof_len = len(proofs[0]) if count else circuit_proof_size(t, log_ext)
+        assert all(len(p) == proof_len for p in proofs), "proofs of one length"
+        buf = np.frombuffer(b"".join(proofs), dtype=np.uint8) if count else None
+        if public_inputs is None:
+            pub, stride, n_public = None, 0, 0
+        elif isinstance(public_inputs, np.ndarray):  # (count, pi_stride, 4) blst_fr rows, the first n_public of a row are read
+            pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+            pub = pub.reshape(count, -1, 4) if count else np.zeros((0, n_public or 0, 4), dtype=np.uint64)
+            stride = pub.shape[1]
+            n_public = stride if n_public is None else n_public
+        else:  # one list of Scalars per proof
+            assert len(public_inputs) == count and len({len(p) for p in public_inputs}) <= 1
+            n_public = len(public_inputs[0]) if count else 0
+            stride = n_public
+            pub = np.stack([_scalar_rows(list(p)) for p in public_inputs]) if n_public else None
+        g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+        assert g2.shape[0] >= 3
+        ks = _scalar_rows(shifts)
+        keep = (rows, ex, ks, pub, buf, g2)
+        opt = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+        return keep, count, (_ptr(rows), n, t, log_ext, g, opt(ex), _ptr(ks), opt(pub), n_public, stride, opt(buf), proof_len, count,
+                             _ptr(g2), 288)
+
+    def circuit_verify_proofs_batch(self, key, n, log_ext, shifts, public_inputs, proofs, setup_g2, exponents=None, n_public=None):
+        """kzg_circuit_verify_proofs_batch: checks many proofs (a list of proof bytes) of the one key with one pairing.
+        public_inputs: None, one list of Scalars per proof, or a (count, pi_stride, 4) array of which the first n_public
+        values per proof are read; exponents: the (g, t) bytes of a custom circuit, whose key has 2 t + 2 + g commitments;
+        setup_g2: blst_p2 rows [1]G2, [s]G2, [s^2]G2.  Returns (ok, bad_index): bad_index the least proof that does not decode
+        or has a point outside G1, None when there is none (the pairing alone does not locate a proof)"""
+        keep, count, a = self._circuit_verify_batch_args(key, n, log_ext, shifts, public_inputs, proofs, setup_g2, exponents, n_public)
+        ok, bad = C.c_int(0), C.c_size_t(0)
+        _check(self._lib.kzg_circuit_verify_proofs_batch(self._h, *a, C.byref(ok), C.byref(bad)), self._h)
+        return bool(ok.value), (None if bad.value == C.c_size_t(-1).value else int(bad.value))
+
+    def circuit_verify_proofs_lincomb(self, key, n, log_ext, shifts, public_inputs, proofs, setup_g2, weights, exponents=None,
+                                      n_public=None, challenges=None):
+        """the test hook kzg_circuit_verify_proofs_lincomb: the same check with the given weights (one blst_fr row or Scalar per
+        proof).  Returns (ok, bad_index, (P0, P1, P2)): the three G1 sums as G1Points.  challenges (5 Scalars per proof: beta,
+        gamma, alpha, zeta, v): kzg_circuit_verify_proofs_lincomb_challenges, which takes them in the place of the hashed ones"""
+        keep, count, a = self._circuit_verify_batch_args(key, n, log_ext, shifts, public_inputs, proofs, setup_g2, exponents, n_public)
+        w = self._fr_rows(weights)
+        assert w.shape[0] == count, "one weight per proof"
+        if not count:
+            w = np.zeros((1, 4), dtype=np.uint64)
+        out = np.zeros((3, 18), dtype=np.uint64)
+        ok, bad = C.c_int(0), C.c_size_t(0)
+        if challenges is None:
+            _check(self._lib.kzg_circuit_verify_proofs_lincomb(self._h, *a, _ptr(w), _ptr(out), C.byref(ok), C.byref(bad)), self._h)
+        else:
+            ch = self._fr_rows([c for five in challenges for c in five])
+            assert ch.shape[0] == 5 * count, "five challenges per proof"
+            _check(self._lib.kzg_circuit_verify_proofs_lincomb_challenges(self._h, *a, _ptr(w), _ptr(ch) if count else None, _ptr(out),
+                                                                          C.byref(ok), C.byref(bad)), self._h)
+        return bool(ok.value), (None if bad.value == C.c_size_t(-1).value else int(bad.value)), tuple(G1Point(out[i].copy()) for i in range(3))
 
     def verify_blobs_batch_bytes(self, blobs_be, n, commitments48, zs_be, proofs48, setup_g2, order=KZG_ORDER_NATURAL,
                                  want_ys=True):

@@ -8993,6 +8993,32 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
                         const uint64_t zeta[4], const uint64_t v[4], const uint64_t proof_p1[18], const void* setup_g1,
                         size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid, const LookupClaim* lookup,
                         const CustomClaim* custom = nullptr);
+// PI(zeta) = sum_i PI_i L_i(zeta), L_i(zeta) = w^i (zeta^n - 1) / (n (zeta - w^i)), with one batch inversion beside 1 / n;
+// zeta = w^k: L_i(zeta) = [i = k].  Zero without public inputs
+hf::Fr public_input_at(const hf::Fr& zeta, size_t n, uint32_t lg_n, const hf::Fr* pub, size_t n_public) {
+    hf::Fr pi_zeta = kFrZero;
+    if (!n_public) return pi_zeta;
+    const hf::Fr w = hf::fr_domain_root(lg_n);
+    std::vector<hf::Fr> wi(n_public), den(n_public), pre(n_public);
+    hf::Fr cur = hf::kFrOne, run = hf::kFrOne;
+    size_t on_h = n_public;
+    for (size_t i = 0; i < n_public; i++) {
+        wi[i] = cur;
+        den[i] = hf::fr_sub(zeta, cur);
+        if (fr_equal(den[i], kFrZero)) on_h = i;
+        pre[i] = run;  // the product of the denominators before i
+        run = hf::fr_mul(run, den[i]);
+        cur = hf::fr_mul(cur, w);
+    }
+    if (on_h < n_public) return pub[on_h];
+    hf::Fr inv = hf::fr_inv(run);
+    for (size_t i = n_public; i-- > 0;) {
+        pi_zeta = hf::fr_add(pi_zeta, hf::fr_mul(hf::fr_mul(pub[i], wi[i]), hf::fr_mul(inv, pre[i])));
+        inv = hf::fr_mul(inv, den[i]);
+    }
+    const hf::Fr Z = hf::fr_sub(hf::fr_pow(zeta, n), hf::kFrOne);
+    return hf::fr_mul(pi_zeta, hf::fr_mul(Z, hf::fr_inv(fr_pow2(lg_n))));
+}
 }  // namespace
 
 int kzg_circuit_verify(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts, const uint64_t* wire_p1s,
@@ -9069,32 +9095,7 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
     }
     if (!on_curve) return KZG_ERR_INVALID_ARG;
     // PI(zeta) = sum_i PI_i L_i(zeta), L_i(zeta) = w^i (zeta^n - 1) / (n (zeta - w^i)); zeta = w^k: L_i(zeta) = [i = k]
-    hf::Fr pi_zeta = kFrZero;
-    if (n_public) {
-        const hf::Fr w = hf::fr_domain_root(sh.lg_n);
-        std::vector<hf::Fr> wi(n_public), den(n_public), pre(n_public);
-        hf::Fr cur = hf::kFrOne, run = hf::kFrOne;
-        size_t on_h = n_public;
-        for (size_t i = 0; i < n_public; i++) {
-            wi[i] = cur;
-            den[i] = hf::fr_sub(ch.zeta, cur);
-            if (fr_equal(den[i], kFrZero)) on_h = i;
-            pre[i] = run;  // the product of the denominators before i
-            run = hf::fr_mul(run, den[i]);
-            cur = hf::fr_mul(cur, w);
-        }
-        if (on_h < n_public) {
-            pi_zeta = pub[on_h];
-        } else {
-            hf::Fr inv = hf::fr_inv(run);  // the call's one inversion beside 1 / n
-            for (size_t i = n_public; i-- > 0;) {
-                pi_zeta = hf::fr_add(pi_zeta, hf::fr_mul(hf::fr_mul(pub[i], wi[i]), hf::fr_mul(inv, pre[i])));
-                inv = hf::fr_mul(inv, den[i]);
-            }
-            const hf::Fr Z = hf::fr_sub(hf::fr_pow(ch.zeta, n), hf::kFrOne);
-            pi_zeta = hf::fr_mul(pi_zeta, hf::fr_mul(Z, hf::fr_inv(fr_pow2(sh.lg_n))));
-        }
-    }
+    const hf::Fr pi_zeta = public_input_at(ch.zeta, n, sh.lg_n, pub.data(), n_public);
     hf::Fr konst;
     std::vector<hf::Fr> sc;
     lin_scalars(n, sh.lg_n, t, e, shifts, ch, &ys[1], &ys[1 + t], ys[2 * t], pi_zeta, &sc, &konst);
@@ -9410,6 +9411,389 @@ int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t,
     if (!exponents) return KZG_ERR_INVALID_ARG;
     return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
                              g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+}
+
+// ---- many proofs of one key with one pairing check (circuit_verify_kernels.hip) ----------------------------
+// The host hashes the transcripts (up to 16 threads), draws the weights and pairs P0, P1, P2 once; the device decodes the points and
+// the evaluations, computes PI(zeta_k) and every scalar of the identity, checks the points to lie in G1, runs every scalar
+// multiplication and the sums.
+namespace {
+int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps,
+                              const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, size_t pi_stride,
+                              const uint8_t* proofs, size_t proof_len, size_t count, const void* setup_g2, size_t g2_stride_bytes,
+                              const uint64_t* weights, bool want_weights, uint64_t* out_p1s, int* valid, size_t* bad_index,
+                              const uint64_t* challenges = nullptr) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    const char* what = "circuit verify batch";
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = std::string(what) + ": " + why;
+        return KZG_ERR_INVALID_ARG;
+    };
+    if (!key_p1s || !shifts || (!public_inputs && n_public && count) || (!proofs && count) || !setup_g2 || !valid ||
+        (want_weights && (!out_p1s || (!weights && count))) || (g && !exps))
+        return invalid("a required pointer is NULL");
+    if (!proof_shape_ok(n, t, log_ext, n_public)) return invalid("n, t, log_ext or n_public is not a shape of kzg_circuit_verify_proof");
+    const size_t e = (size_t)1 << log_ext;
+    if (exps && !custom_shape_ok(t, e, g, exps, nullptr)) return invalid("g or the exponents are not a shape of the custom verifier");
+    const ProofLayout L = proof_layout(t, e);
+    if (proof_len != L.len) return invalid("proof_len is not kzg_circuit_proof_size's");
+    if (count > KZG_VERIFY_MAX_PROOFS) return invalid("more than KZG_VERIFY_MAX_PROOFS proofs");
+    if (n < 2) return invalid("n < 2: the two point sets of a proof coincide");
+    if (pi_stride < n_public && count > 1) return invalid("pi_stride is below n_public");
+    std::vector<hf::Fr> ks, none;
+    if (!proof_scalars(shifts, t, nullptr, 0, &ks, &none)) return invalid("a shift is not below r");
+    for (size_t k = 0; k < count; k++)  // validated here, converted again by the thread that hashes proof k: nothing of size count is kept
+        for (size_t i = 0; i < n_public; i++) {
+            hf::Fr v;
+            if (!fr_arg_below_r(public_inputs + 4 * (k * pi_stride + i), &v))
+                return invalid("proof " + std::to_string(k) + ": public input " + std::to_string(i) + " is not below r");
+        }
+    const size_t nkey = 2 * t + 2 + g, nk = nkey + 1;  // the key's commitments, then G1
+    for (size_t j = 0; j < nkey; j++) {
+        hf::P1 c;
+        std::memcpy(&c, key_p1s + 18 * j, sizeof c);
+        if (!hf::p1_on_curve(c)) return invalid("key commitment " + std::to_string(j) + " is not on the curve");
+    }
+    hf::G2Affine g2[3];
+    for (int i = 0; i < 3; i++) {
+        uint64_t raw[36];
+        std::memcpy(raw, (const uint8_t*)setup_g2 + i * g2_stride_bytes, sizeof raw);
+        g2[i] = hf::g2_from_p2(raw);
+        if (!hf::g2_on_curve(g2[i])) return invalid("setup_g2[" + std::to_string(i) + "] is not on the twist");
+    }
+    if (want_weights)
+        for (size_t k = 0; k < count; k++) {
+            hf::Fr w;
+            std::memcpy(w.l, weights + 4 * k, 32);
+            if (hf::fr_geq(w, hf::kFrMod)) return invalid("weight " + std::to_string(k) + " is not below r");
+        }
+    for (size_t i = 0; challenges && i < 5 * count; i++) {
+        hf::Fr c;
+        std::memcpy(c.l, challenges + 4 * i, 32);
+        if (hf::fr_geq(c, hf::kFrMod)) return invalid("proof " + std::to_string(i / 5) + ": a challenge is not below r");
+    }
+    if (bad_index) *bad_index = (size_t)-1;
+    if (!count) {
+        if (want_weights) {
+            const hf::P1 inf = hf::p1_inf();
+            for (int i = 0; i < 3; i++) write_p1(out_p1s + 18 * i, inf);
+        }
+        *valid = 1;
+        return KZG_OK;
+    }
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "circuit verify batch needs");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, circuit_verify_batch_impl(kid, key_p1s, n, t, log_ext, g, exps, shifts, public_inputs, n_public, pi_stride,
+                                                             proofs, proof_len, count, setup_g2, g2_stride_bytes, weights, want_weights,
+                                                             out_p1s, valid, bad_index, challenges));
+    }
+    PqShape sh;
+    pq_shape(n, e, &sh);
+    const size_t M = count, R = t + e + 1;  // a proof's points: t wires, [z], e - 1 chunks, W
+    std::vector<hf::Fr> rho;
+    std::vector<Glv> rho_glv;
+    {
+        const int rcw = vc_weights(ctx, what, want_weights ? weights : nullptr, M, &rho, &rho_glv);
+        if (rcw) return rcw;
+    }
+    // the statement's bytes in front of the public inputs, hashed once
+    hf::Sha256 stmt;
+    {
+        std::vector<uint8_t> m((exps ? kCustomDstLen + 40 + g * t : 19 + 32) + 32 * t + 48 * nkey);
+        uint8_t* p = m.data();
+        if (exps) {
+            std::memcpy(p, kCustomProofDst, kCustomDstLen);
+            p += kCustomDstLen;
+            for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)g, (uint64_t)n_public}) {
+                proof_u64be(p, x);
+                p += 8;
+            }
+        } else {
+            std::memcpy(p, kProofDst, 19);
+            p += 19;
+            for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)n_public}) {
+                proof_u64be(p, x);
+                p += 8;
+            }
+        }
+        for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(ks[j], p);
+        if (exps) {
+            std::memcpy(p, exps, g * t);
+            p += g * t;
+        }
+        for (size_t j = 0; j < nkey; j++, p += 48) {
+            hf::P1 c;
+            std::memcpy(&c, key_p1s + 18 * j, sizeof c);
+            hf::p1_compress(p, c);
+        }
+        hf::sha256_init(stmt);
+        hf::sha256_update(stmt, m.data(), m.size());
+    }
+    // lanes of the one ladder launch: [the R - 1 points of A_0 per proof | W per proof | the key's nk points with their scalars of P0 |
+    // the same with those of P1 | [z] per proof, a second time].  Affine records: the key's nk in front, so that the least failing
+    // index names a key commitment (an error) before any proof (a verdict), then the proofs' NP
+    const size_t NP = M * R, lanes = M * (R + 1) + 2 * nk, oF = M * (R - 1), oK = oF + M, oE = oK + 2 * nk;
+    // the host's part: the five challenges of every proof (the SHA-256 chain from h0 on, proof_challenges'), as blst_fr images
+    std::vector<uint64_t> chal(20 * M);
+    std::vector<uint32_t> src(lanes);
+    size_t nthreads = std::min<size_t>({(size_t)16, std::max<size_t>(1, std::thread::hardware_concurrency()), M});
+    auto work = [&](size_t th) {
+        std::vector<uint8_t> pub_be(32 * n_public);
+        for (size_t k = th; k < M; k += nthreads) {
+            const uint8_t* proof = proofs + k * proof_len;
+            for (size_t i = 0; i + 1 < R; i++) src[k * (R - 1) + i] = (uint32_t)(nk + k * R + i);
+            src[oF + k] = (uint32_t)(nk + k * R + R - 1);
+            src[oE + k] = (uint32_t)(nk + k * R + t);
+            if (challenges) {  // the test hook's: nothing is hashed
+                std::memcpy(&chal[20 * k], challenges + 20 * k, 160);
+                continue;
+            }
+            for (size_t i = 0; i < n_public; i++) {
+                hf::Fr v;
+                fr_arg_below_r(public_inputs + 4 * (k * pi_stride + i), &v);
+                proof_fr_to_be(v, &pub_be[32 * i]);
+            }
+            hf::Sha256 s = stmt;
+            uint8_t h[32];
+            hf::sha256_update(s, pub_be.data(), pub_be.size());
+            hf::sha256_final(s, h);
+            hf::Fr ch[5];
+            proof_absorb(h, proof + L.wires, L.z - L.wires);
+            ch[0] = proof_challenge(h, 0);
+            ch[1] = proof_challenge(h, 1);
+            proof_absorb(h, proof + L.z, 48);
+            ch[2] = proof_challenge(h, 0);
+            proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
+            ch[3] = proof_challenge(h, 0);
+            proof_absorb(h, proof + L.evals, L.w - L.evals);
+            ch[4] = proof_challenge(h, 0);
+            // the kernels' order: beta, gamma, alpha, zeta, v
+            for (int i = 0; i < 5; i++) std::memcpy(&chal[20 * k + 4 * i], ch[i].l, 32);
+        }
+    };
+    if (nthreads <= 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (size_t th = 1; th < nthreads; th++) pool.emplace_back(work, th);
+        work(0);
+        for (auto& th : pool) th.join();
+    }
+    for (size_t j = 0; j < 2 * nk; j++) src[oK + j] = (uint32_t)(j % nk);
+    // the kernels' constants, multiplier form: 2^14, w, 1 + w, 1 / n, w^64, the shifts
+    std::vector<Fr30> consts(kCvbShifts + t);
+    {
+        const hf::Fr w = hf::fr_domain_root(sh.lg_n);
+        consts[kCvbK284] = fr30_arg_from_mont256(fr_pow2(14));
+        consts[kCvbW] = fr30_arg_from_mont256(w);
+        consts[kCvbW1] = fr30_arg_from_mont256(hf::fr_add(w, hf::kFrOne));
+        consts[kCvbInvN] = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
+        consts[kCvbW64] = fr30_arg_from_mont256(hf::fr_pow(w, 64));
+        for (size_t j = 0; j < t; j++) consts[kCvbShifts + j] = fr30_arg_from_mont256(ks[j]);
+    }
+    // XYZZ records, laid out so that every side is a run of consecutive records:
+    //   [the ladder's products of A_0: M (R - 1) | F: M | P0's terms: 3 M | the key's for P0: nk | the key's for P1: nk | E: M | D: M |
+    //    [zeta (1 + w)] F: M | the three sums]
+    // P2' = sum F, P0 and P1 are three consecutive segments from F on; D_k is the sum of proof k's R - 1 products
+    const size_t oP0 = M * R, oKey = oP0 + 3 * M, oEr = oKey + 2 * nk, oD = oEr + M, oS3 = oD + M, oOut = oS3 + M;
+    // the key side's rows: 2 nk values a proof, padded to a power of two, summed over the proofs
+    uint32_t log_l = 0;
+    while (((size_t)1 << log_l) < 2 * nk) log_l++;
+    const size_t l = (size_t)1 << log_l;
+    VcPlan plan_d, plan_fin, plan_rows;
+    vc_plan(std::vector<uint32_t>(M, (uint32_t)(R - 1)), &plan_d);
+    vc_plan({(uint32_t)M, (uint32_t)(3 * M + nk), (uint32_t)(nk + 3 * M)}, &plan_fin);
+    vc_plan({(uint32_t)M}, &plan_rows);
+    std::vector<uint32_t> starts;
+    std::vector<size_t> at_d, at_fin, at_rows;
+    for (auto* pl : {&plan_d, &plan_fin, &plan_rows}) {
+        auto& at = pl == &plan_d ? at_d : (pl == &plan_fin ? at_fin : at_rows);
+        for (const auto& lv : *pl) {
+            at.push_back(starts.size());
+            starts.insert(starts.end(), lv.begin(), lv.end());
+        }
+    }
+    const size_t gmax = std::max(plan_d[0].size() - 1, plan_fin[0].size() - 1), grows = plan_rows[0].size() - 1;
+    const size_t pub_values = n_public ? (M - 1) * pi_stride + n_public : 0;  // as the caller laid them out
+    std::lock_guard<std::mutex> lkf(ctx->fk20_mu);  // guards the workspaces
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) {
+        ctx->last_error = std::string(what) + ": the SRS is empty";
+        return KZG_ERR_NO_SRS;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_slot_basics(ctx, s);
+    void *wire = nullptr, *coef = nullptr, *dstarts = nullptr, *p1 = nullptr, *aff = nullptr, *prefix = nullptr, *dsrc = nullptr,
+         *dglv = nullptr, *dglvs = nullptr, *g1 = nullptr, *scratch = nullptr, *cells = nullptr, *fa = nullptr, *fb = nullptr, *frs = nullptr,
+         *dpub = nullptr;
+    // the Fr inputs behind one another in one workspace: evaluations' bytes | their images | challenges | weights | PI(zeta) | consts |
+    // exponents | k_cvb_lin's records (each part a multiple of 32 bytes)
+    const size_t fEvB = 0, fEv = fEvB + M * 64 * t, fCh = fEv + M * 64 * t, fRho = fCh + M * 160, fPi = fRho + M * 32,
+                 fCo = fPi + ((M * sizeof(Fr30) + 31) / 32) * 32, fEx = fCo + ((consts.size() * sizeof(Fr30) + 31) / 32) * 32,
+                 fLin = fEx + ((g * t + 31) / 32) * 32, fEnd = fLin + 4 * M * sizeof(Fr30);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcWire, NP * 48, &wire);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCoefA, kVcErrWords * 4, &coef);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcStarts, starts.size() * 4, &dstarts);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcP1, nk * 144, &p1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcAff, (NP + nk) * kAffineBytes, &aff);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcPrefix, nk * 64, &prefix);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcSrc, lanes * 4, &dsrc);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcGlv, lanes * sizeof(Glv), &dglv);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcGlvSrs, 4 * M * sizeof(Glv), &dglvs);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcG1, (oOut + 3) * kXyzzBytes, &g1);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcScratch, 2 * gmax * kXyzzBytes, &scratch);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcCells, M * l * 32, &cells);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcFrA, grows * l * 32, &fa);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcFrB, grows * l * 32, &fb);
+    if (rc == KZG_OK) rc = ctx->vc_ws.get(ctx, kVcRho, fEnd, &frs);
+    if (rc == KZG_OK && pub_values) rc = ctx->vc_ws.get(ctx, kVcOrder, pub_values * 32, &dpub);
+    if (rc) return rc;
+    const hipStream_t st = s.stream;
+    uint32_t* err = (uint32_t*)coef;  // the ladder's words at kVcErrCurve / kVcErrG1, the decoders' at kVcErrWireProof / kVcErrWireValue
+    Glv* ds2 = (Glv*)dglvs;
+    void* proof_aff = (char*)aff + nk * kAffineBytes;
+    auto rec = [&](size_t i) { return (void*)((char*)g1 + i * kXyzzBytes); };
+    auto fr_at = [&](size_t off) { return (uint32_t*)((char*)frs + off); };
+    HIP_TRY(ctx, hipMemsetAsync(err, 0xff, kVcErrWords * 4, st));
+    // the proofs' bytes as received: the points (the wires, [z] and the chunks, then W) and the evaluations, each field of a proof
+    // to its place by a strided copy
+    HIP_TRY(ctx, hipMemcpy2DAsync(wire, 48 * R, proofs, proof_len, 48 * (R - 1), M, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpy2DAsync((char*)wire + 48 * (R - 1), 48 * R, proofs + L.w, proof_len, 48, M, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpy2DAsync(fr_at(fEvB), 64 * t, proofs + L.evals, proof_len, 64 * t, M, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(fr_at(fCh), chal.data(), M * 160, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(fr_at(fRho), rho.data(), M * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(fr_at(fCo), consts.data(), consts.size() * sizeof(Fr30), hipMemcpyHostToDevice, st));
+    if (g) HIP_TRY(ctx, hipMemcpyAsync(fr_at(fEx), exps, g * t, hipMemcpyHostToDevice, st));
+    if (pub_values) HIP_TRY(ctx, hipMemcpyAsync(dpub, public_inputs, pub_values * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dstarts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dsrc, src.data(), lanes * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync((Glv*)dglv + oF, rho_glv.data(), M * sizeof(Glv), hipMemcpyHostToDevice, st));  // F_k = [rho_k] W_k
+    HIP_TRY(ctx, hipMemsetAsync(cells, 0, M * l * 32, st));
+    // the key's records, then G1 = SRS[0] from the table's level 0; the proofs' points decoded behind them
+    HIP_TRY(ctx, hipMemcpyAsync(p1, key_p1s, nkey * 144, hipMemcpyHostToDevice, st));
+    launch_jacobian_to_affine(st, p1, (uint32_t)nkey, aff, prefix);
+    HIP_TRY(ctx, hipMemcpyAsync((char*)aff + nkey * kAffineBytes, ctx->table.p, kAffineBytes, hipMemcpyDeviceToDevice, st));
+    launch_wire_g1(st, wire, nullptr, (uint32_t)NP, proof_aff, (uint32_t)kAffineBytes, err + kVcErrWireProof);
+    // the Fr side: the evaluations decoded, PI(zeta_k), every proof's scalars split for the ladders and its row of key-side terms,
+    // the rows summed over the proofs, the sums split
+    launch_wire_fr(st, fr_at(fEvB), (uint32_t)(M * 2 * t), 0, false, fr_at(fEv), err + kVcErrWireValue);
+    const Fr30* dconsts = (const Fr30*)fr_at(fCo);
+    if (n_public)
+        launch_cvb_public(st, (const uint32_t*)dpub, (uint32_t)n_public, pi_stride, fr_at(fCh), dconsts, sh.lg_n, (uint32_t)M, (Fr30*)fr_at(fPi));
+    launch_cvb_scalars(st, fr_at(fCh), fr_at(fEv), fr_at(fRho), n_public ? (const Fr30*)fr_at(fPi) : nullptr, dconsts,
+                       g ? (const uint8_t*)fr_at(fEx) : nullptr, (uint32_t)M, (uint32_t)t, (uint32_t)e, (uint32_t)g, sh.lg_n, (Fr30*)fr_at(fLin), (Glv*)dglv, oE,
+                       ds2, (uint32_t*)cells, log_l);
+    const uint32_t* dst_ = (const uint32_t*)dstarts;
+    const uint32_t* key_sums = (const uint32_t*)cells;
+    for (size_t lv = 0; lv < plan_rows.size(); lv++) {
+        uint32_t* dst = key_sums == (uint32_t*)fa ? (uint32_t*)fb : (uint32_t*)fa;
+        launch_vc_fr_sum(st, key_sums, nullptr, nullptr, dst_ + at_rows[lv], (uint32_t)(plan_rows[lv].size() - 1), log_l, dst);
+        key_sums = dst;
+    }
+    launch_cvb_key_split(st, key_sums, (uint32_t)(2 * nk), (Glv*)dglv + oK);
+    // stage 1: every point times its scalar in one launch; the proofs' points and the key's commitments are checked (lanes below
+    // M R + nkey: the key's second copy, G1 and the second [z] are not checked again)
+    launch_vc_ladder(st, aff, (const uint32_t*)dsrc, (const Glv*)dglv, (uint32_t)lanes, (uint32_t)(M * R + nkey), (uint32_t)(M * R), rec(0),
+                     rec(oKey), err);
+    void* X[2] = {scratch, (char*)scratch + gmax * kXyzzBytes};
+    auto g1_plan = [&](const VcPlan& plan, const std::vector<size_t>& at, const void* in, void* out) {
+        const void* c = in;
+        for (size_t lv = 0; lv < plan.size(); lv++) {
+            void* dst = lv + 1 == plan.size() ? out : (c == X[0] ? X[1] : X[0]);
+            launch_vc_g1_sum(st, c, dst_ + at[lv], (uint32_t)(plan[lv].size() - 1), dst);
+            c = dst;
+        }
+    };
+    g1_plan(plan_d, at_d, rec(0), rec(oD));
+    // stage 2: the proofs' products for P0 and P1; then the three sums P2' = sum F, P0, P1
+    launch_cvb_stage2(st, rec(oD), rec(oEr), rec(oF), ds2, (uint32_t)M, rec(oP0), rec(oS3));
+    g1_plan(plan_fin, at_fin, rec(oF), rec(oOut));
+    launch_xyzz_to_affine(st, rec(oOut), 3, aff, prefix);
+    launch_affine_to_p1(st, aff, 3, p1);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t herr[kVcErrWords];
+    uint64_t sides[54];
+    HIP_TRY(ctx, hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(sides, p1, sizeof sides, hipMemcpyDeviceToHost, st));
+    rc = sync_unlocked(ctx, lk, st, what);
+    if (rc) return rc;
+    const uint32_t grp = std::min(herr[kVcErrCurve], herr[kVcErrG1]);  // a record index: the key's are below nk
+    if (grp < nk) return invalid("key commitment " + std::to_string(grp) + " is not in G1");
+    // a proof that does not decode (a point, an evaluation) or has a point outside G1 is invalid, not an error: the least such proof
+    size_t bad = (size_t)-1;
+    if (grp != 0xffffffffu) bad = (grp - nk) / R;
+    if (herr[kVcErrWireProof] != 0xffffffffu) bad = std::min(bad, (size_t)herr[kVcErrWireProof] / R);
+    if (herr[kVcErrWireValue] != 0xffffffffu) bad = std::min(bad, (size_t)herr[kVcErrWireValue] / (2 * t));
+    if (bad != (size_t)-1) {
+        if (bad_index) *bad_index = bad;
+        if (want_weights) {
+            const hf::P1 inf = hf::p1_inf();
+            for (int i = 0; i < 3; i++) write_p1(out_p1s + 18 * i, inf);
+        }
+        *valid = 0;
+        return KZG_OK;
+    }
+    hf::P1 sums[3], ps[3];  // the device's order: sum F, P0, P1
+    std::memcpy(sums, sides, sizeof sides);
+    ps[0] = sums[1];
+    ps[1] = sums[2];
+    ps[2] = hf::p1_neg(sums[0]);
+    if (want_weights)
+        for (int i = 0; i < 3; i++) write_p1(out_p1s + 18 * i, ps[i]);
+    bool ok = true;
+    const hf::F12 f = hf::multi_miller_loop(g2, ps, 3, ok);
+    *valid = ok && hf::f12_is_one(hf::f12_final_exp(f)) ? 1 : 0;
+    return KZG_OK;
+}
+}  // namespace
+
+int kzg_circuit_verify_proofs_batch(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                    const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public,
+                                    size_t pi_stride, const uint8_t* proofs, size_t proof_len, size_t count, const void* setup_g2,
+                                    size_t g2_stride_bytes, int* valid, size_t* bad_index) {
+    try {
+        return circuit_verify_batch_impl(ctx, key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, pi_stride, proofs,
+                                         proof_len, count, setup_g2, g2_stride_bytes, nullptr, false, nullptr, valid, bad_index);
+    } catch (...) {  // nothing may unwind through the C-ABI: the host vectors of a large batch, or a thread that could not start
+        ctx->last_error = "circuit verify batch: out of host memory or threads";
+        return KZG_ERR_HIP;
+    }
+}
+
+int kzg_circuit_verify_proofs_lincomb_challenges(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                                 const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs,
+                                                 size_t n_public, size_t pi_stride, const uint8_t* proofs, size_t proof_len, size_t count,
+                                                 const void* setup_g2, size_t g2_stride_bytes, const uint64_t* weights,
+                                                 const uint64_t* challenges, uint64_t out_p1s[54], int* valid, size_t* bad_index) {
+    if (ctx && count && !challenges) {
+        ctx->last_error = "circuit verify batch: a required pointer is NULL";
+        return KZG_ERR_INVALID_ARG;
+    }
+    try {
+        return circuit_verify_batch_impl(ctx, key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, pi_stride, proofs,
+                                         proof_len, count, setup_g2, g2_stride_bytes, weights, true, out_p1s, valid, bad_index, challenges);
+    } catch (...) {
+        ctx->last_error = "circuit verify batch: out of host memory or threads";
+        return KZG_ERR_HIP;
+    }
+}
+
+int kzg_circuit_verify_proofs_lincomb(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                      const uint8_t* exponents, const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public,
+                                      size_t pi_stride, const uint8_t* proofs, size_t proof_len, size_t count, const void* setup_g2,
+                                      size_t g2_stride_bytes, const uint64_t* weights, uint64_t out_p1s[54], int* valid, size_t* bad_index) {
+    try {
+        return circuit_verify_batch_impl(ctx, key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, pi_stride, proofs,
+                                         proof_len, count, setup_g2, g2_stride_bytes, weights, true, out_p1s, valid, bad_index);
+    } catch (...) {
+        ctx->last_error = "circuit verify batch: out of host memory or threads";
+        return KZG_ERR_HIP;
+    }
 }
 
 // ---- a next-row circuit's proof as bytes (host only): rho more scalars under a statement of its own --------

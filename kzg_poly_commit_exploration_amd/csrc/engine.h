@@ -294,6 +294,28 @@ void launch_vc_fr_sum(hipStream_t s, const uint32_t* d_in, const uint32_t* d_ord
 void launch_vc_fr_twist(hipStream_t s, uint32_t* d_io, const uint32_t* d_ids, uint32_t D, const void* d_itw, uint32_t log_n,
                         uint32_t log_l, const Fr30& inv_l);
 
+// ---- circuit_verify_kernels.hip: the second stage of the batch verifier of circuit proofs -------------
+// lane (k, j), k < count, j < 4: [d_s[4 k + j]] X, X = d_D[k], d_E[k], d_F[k], d_F[k] (XYZZ records).  Products 0 .. 2 go to
+// d_p0[3 k + j], product 3 to d_p1[k]
+void launch_cvb_stage2(hipStream_t st, const void* d_D, const void* d_E, const void* d_F, const Glv* d_s, uint32_t count, void* d_p0,
+                       void* d_p1);
+
+// The Fr side.  d_consts (Fr30, multiplier form): 2^14, w, 1 + w, 1 / n, w^64, then the t shifts.  All inputs are canonical blst_fr
+// images on the device: d_chal 5 per proof (beta, gamma, alpha, zeta, v), d_evals 2 t per proof, d_rho one per proof, d_pub proof
+// k's n_public values at d_pub + 8 k stride.
+enum : uint32_t { kCvbK284 = 0, kCvbW, kCvbW1, kCvbInvN, kCvbW64, kCvbShifts };  // (2^14 x 2^270 = 2^284 takes an image into the form)
+// d_out[k] = PI(zeta_k), multiplier form
+void launch_cvb_public(hipStream_t st, const uint32_t* d_pub, uint32_t n_public, uint64_t stride, const uint32_t* d_chal,
+                       const Fr30* d_consts, uint32_t lg_n, uint32_t count, Fr30* d_out);
+// per proof k: the split scalars d_glv[k (t + e) + i] (i < t + e), d_glv[o_e + k], d_s2[4 k + j], and the row of 2 (2 t + 3 + g)
+// plain integers at d_rows + 8 (k << log_l); d_pim: launch_cvb_public's output or null, d_exps: g x t bytes or null; d_lin: 4 Fr30
+// per proof between the two launches (k_cvb_lin, k_cvb_scalars)
+void launch_cvb_scalars(hipStream_t st, const uint32_t* d_chal, const uint32_t* d_evals, const uint32_t* d_rho, const Fr30* d_pim,
+                        const Fr30* d_consts, const uint8_t* d_exps, uint32_t count, uint32_t t, uint32_t e, uint32_t g, uint32_t lg_n,
+                        Fr30* d_lin, Glv* d_glv, uint64_t o_e, Glv* d_s2, uint32_t* d_rows, uint32_t log_l);
+// d_out[j] = the split of the plain canonical integer d_sums[j], j < n
+void launch_cvb_key_split(hipStream_t st, const uint32_t* d_sums, uint32_t n, Glv* d_out);
+
 // ---- srs_update_kernels.hip: a powers-of-tau contribution and the per-point checks of a setup --------
 // d_out_xyzz[i] = [tau^(first + i) mod r] d_level0[i] (affine records in, XYZZ out, infinity stays); tau_raw8: the
 // 256-bit little-endian integer, any value below 2^256 (the kernel-argument copy lives as long as k_srs_points' secret)

@@ -827,7 +827,8 @@ int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uin
  * Proof bytes, in order: the t wire commitments, [m], [z], [phi], the e - 1 chunk commitments (48 bytes each), the 2 t + c + 2
  * evaluations abar_0.., sbar_0 .. sbar_(t-2), z(zeta w), tbar_0.., qbar, phiw (32 bytes each), W: 48 (t + e + 3) + 32 (2 t + c + 2)
  * bytes (kzg_circuit_lookup_proof_size), 832 at t = 3, e = 4, c = 3.  Every commitment is bit for bit kzg_commit_evaluations of its
- * column.  LOOKUP PROOFS ARE PLAIN: neither the wires nor z, phi, m or T are blinded, so these proofs are NOT zero-knowledge.
+ * column.  Proofs of kzg_circuit_lookup_prove are plain; the _blinded forms are zero-knowledge: in a plain proof neither the wires
+ * nor z, phi, m or T are blinded, so it is NOT zero-knowledge.
  *
  * kzg_circuit_lookup_prove: host wires, synchronous, one stream slot; key_p1s the (2 t + c + 3) x 18 u64 of
  * kzg_circuit_create_lookup; public_inputs the first n_public values of PI (the rest zero), or NULL with n_public = 0; out_proof
@@ -844,7 +845,39 @@ int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uin
  * Host only, no context: kzg_circuit_lookup_proof_size; kzg_circuit_lookup_proof_challenges (out: 6 x 4 u64, theta, beta, gamma,
  * alpha, zeta, v as blst_fr, from complete proof bytes; nothing is decoded); kzg_circuit_lookup_verify_proof, whose argument and
  * decode rules are kzg_circuit_verify_proof's: bytes that do not decode give KZG_OK with *valid = 0, there is no subgroup check.
- * [r_L] is formed from the key, [z], [m], [phi] and the [T_c] and handed to kzg_verify_sets. */
+ * [r_L] is formed from the key, [z], [m], [phi] and the [T_c] and handed to kzg_verify_sets.
+ *
+ * THE BLINDED FORMS make the lookup proof zero-knowledge; the verifier, the proof's format and size and the
+ * transcript do not change.  With Z_H = X^n - 1 the wires, z and T's chunks are blinded as in kzg_circuit_prove, and
+ *     phi~ = phi + (p_0 + p_1 X + p_2 X^2) Z_H   (linearised at zeta and opened at zeta w, like z: three blinders)
+ *     m~   = m + (u_0 + u_1 X) Z_H               (committed once, enters through r_L at zeta only: two blinders)
+ * T~ = Num_L(f~, z~, phi~, m~) / Z_H has D = max(t n + t + 3, 3 n + 2) coefficients and is returned as L_T = (e - 1) n + t + 3,
+ * zeros from D on.  Shape rule: kzg_circuit_create_lookup's, D < N and D <= L_T.  The blinder array is kzg_circuit_prove's (t pairs,
+ * c_0..c_2, d_0..d_(e-3)) with p_0, p_1, p_2 and then u_0, u_1 behind it: 2 t + e + 6 canonical blst_fr.  The SRS needs n + t + 3
+ * points.  With every blinder zero the proof is kzg_circuit_lookup_prove's, byte for byte.
+ * kzg_circuit_lookup_blinded_sizes (host only) applies the shape rule (KZG_ERR_INVALID_ARG for a refused shape) -> the entries of
+ * the array and L_T.  kzg_circuit_lookup_blinders draws the array from the OS CSPRNG, as kzg_circuit_blinders does.
+ * kzg_circuit_lookup_quotient_blinded is kzg_circuit_lookup_quotient for the blinded columns: out_coeffs (NULL, or L_T x 4 u64)
+ * and out_p1s (NULL, or the (e - 1) commitments of the blinded chunks T~_c, n + t + 3 SRS points); statuses are
+ * kzg_circuit_lookup_quotient's in their order, the shape rule and then a blinder not below r (KZG_ERR_INVALID_ARG) behind the
+ * circuit's checks.  kzg_circuit_lookup_prove_blinded / _device are kzg_circuit_lookup_prove / _device with blinders (required):
+ * the same rounds and transcript, [m~] and [phi~] committed from n + 2 and n + 3 coefficients; statuses are
+ * kzg_circuit_lookup_prove's in their order, *bad_row included, with the shape rule and a blinder not below r right behind the
+ * argument checks and KZG_ERR_DEGREE_TOO_HIGH for an SRS of fewer than n + t + 3 points.  A failed call writes nothing to out_proof
+ * and leaves the context serving.  Multi-device rules are kzg_circuit_prove's. */
+int kzg_circuit_lookup_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t c, size_t* num_blinders, size_t* quotient_len);
+int kzg_circuit_lookup_blinders(size_t t, unsigned log_ext, uint64_t* out /* (2t+e+6)x4 */);
+int kzg_circuit_lookup_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride,
+                                        const uint64_t* z, const uint64_t* mult, const uint64_t* phi, const uint64_t* public_inputs,
+                                        const uint64_t alpha[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                        const uint64_t theta[4], const uint64_t* blinders, uint64_t* out_coeffs /* L_T x 4 */,
+                                        uint64_t* out_p1s /* (e-1) x 18 */);
+int kzg_circuit_lookup_prove_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires,
+                                     size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                     uint8_t* out_proof, size_t* bad_row);
+int kzg_circuit_lookup_prove_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                            size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                            uint8_t* out_proof, size_t* bad_row);
 int kzg_circuit_lookup_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row);
 int kzg_circuit_lookup_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,

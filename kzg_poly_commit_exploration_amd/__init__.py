@@ -25,6 +25,7 @@ __all__ = [
     "KZG_CIRCUIT_COL_L0", "KZG_CIRCUIT_VALUES", "KZG_CIRCUIT_COEFFS", "KZG_CIRCUIT_COSET",
     "KZG_CIRCUIT_COL_TABLE", "KZG_CIRCUIT_COL_QLOOKUP",
     "circuit_lookup_proof_size", "circuit_lookup_proof_challenges", "circuit_lookup_verify_proof",
+    "circuit_lookup_blinded_sizes", "circuit_lookup_blinders",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
@@ -95,6 +96,8 @@ ABI_SYMBOLS = [
     "kzg_circuit_create_lookup", "kzg_circuit_lookup_columns", "kzg_circuit_lookup_quotient",
     "kzg_circuit_lookup_prove", "kzg_circuit_lookup_prove_device", "kzg_circuit_lookup_proof_size",
     "kzg_circuit_lookup_proof_challenges", "kzg_circuit_lookup_verify_proof",
+    "kzg_circuit_lookup_blinded_sizes", "kzg_circuit_lookup_blinders", "kzg_circuit_lookup_quotient_blinded",
+    "kzg_circuit_lookup_prove_blinded", "kzg_circuit_lookup_prove_blinded_device",
     "kzg_circuit_create_custom", "kzg_circuit_custom_gate", "kzg_circuit_custom_quotient", "kzg_circuit_custom_prove",
     "kzg_circuit_custom_prove_device", "kzg_circuit_custom_proof_challenges", "kzg_circuit_custom_verify_proof",
     "kzg_circuit_custom_blinded_sizes",
@@ -263,6 +266,11 @@ def load_library():
         "kzg_circuit_lookup_quotient": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kzg_circuit_lookup_prove": (i, [vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]),
         "kzg_circuit_lookup_prove_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]),
+        "kzg_circuit_lookup_blinded_sizes": (i, [sz, sz, C.c_uint, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "kzg_circuit_lookup_blinders": (i, [sz, C.c_uint, vp]),
+        "kzg_circuit_lookup_quotient_blinded": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_circuit_lookup_prove_blinded": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz)]),
+        "kzg_circuit_lookup_prove_blinded_device": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz)]),
         "kzg_circuit_lookup_proof_size": (i, [sz, C.c_uint, sz, C.POINTER(sz)]),
         "kzg_circuit_lookup_proof_challenges": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp]),
         "kzg_circuit_lookup_verify_proof": (i, [vp, sz, sz, C.c_uint, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_int)]),
@@ -2127,15 +2135,43 @@ class Circuit:
                                                        None if coeffs is None else _ptr(coeffs), None if p1s is None else _ptr(p1s)))
         return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
 
-    def _lookup_prove(self, fn, e, wires_arg, stride, public_inputs):
+    def lookup_quotient_blinded(self, wires, z, mult, phi, alpha, beta, gamma, theta, blinders, public_inputs=None, n=None,
+                                want_coeffs=True, want_commitments=True, engine=None):
+        """kzg_circuit_lookup_quotient_blinded: lookup_quotient() for the blinded columns, blinders the (2 t + e + 6, 4) array of
+        circuit_lookup_blinders() -> (T~'s (L_T, 4) coefficients or None, the commitments of its e - 1 blinded chunks or None)"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        zz, mm, pp = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (z, mult, phi))
+        assert zz.shape[0] >= n and mm.shape[0] >= n and pp.shape[0] >= n
+        pi = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        assert pi is None or pi.shape[0] >= n
+        b = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        ext = 1 << self.log_ext
+        assert b.shape[0] == 2 * t + ext + 6
+        al, bl, gl, th = alpha.limbs(), beta.limbs(), gamma.limbs(), theta.limbs()
+        coeffs = np.zeros(((ext - 1) * n + t + 3, 4), dtype=np.uint64) if want_coeffs else None
+        p1s = np.zeros((ext - 1, 18), dtype=np.uint64) if want_commitments else None
+        e._pq_check(e._lib.kzg_circuit_lookup_quotient_blinded(e._h, self._c, _ptr(a), stride, _ptr(zz), _ptr(mm), _ptr(pp),
+                                                               None if pi is None else _ptr(pi), _ptr(al), _ptr(bl), _ptr(gl), _ptr(th),
+                                                               _ptr(b), None if coeffs is None else _ptr(coeffs),
+                                                               None if p1s is None else _ptr(p1s)))
+        return coeffs, None if p1s is None else [G1Point(p) for p in p1s]
+
+    def _lookup_prove(self, fn, e, wires_arg, stride, public_inputs, blinders=None):
         assert self.key is not None and len(self.key) == 2 * self.t + self.c + 3, "lookup_prove: the key of circuit_create_lookup"
         rows = np.ascontiguousarray(np.stack([c.p1 for c in self.key]), dtype=np.uint64)
         pub = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros(circuit_lookup_proof_size(self.t, self.log_ext, self.c), dtype=np.uint8)
         bad = C.c_size_t(0)
+        more = ()
+        if blinders is not None:
+            bl = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+            assert bl.shape[0] == 2 * self.t + (1 << self.log_ext) + 6
+            more = (_ptr(bl),)
         try:
             e._pq_check(fn(e._h, self._c, _ptr(rows), wires_arg, stride, None if pub is None else _ptr(pub),
-                           0 if pub is None else pub.shape[0], _ptr(out), C.byref(bad)))
+                           0 if pub is None else pub.shape[0], *more, _ptr(out), C.byref(bad)))
         except KzgError as err:
             err.bad_row = None if bad.value == C.c_size_t(-1).value else int(bad.value)
             raise
@@ -2154,6 +2190,20 @@ class Circuit:
         e = self._eng
         return self._lookup_prove(e._lib.kzg_circuit_lookup_prove_device, e, C.c_void_p(d_wires), self.n if stride is None else stride,
                                   public_inputs)
+
+    def lookup_prove_blinded(self, wires, blinders, public_inputs=None, n=None, engine=None):
+        """kzg_circuit_lookup_prove_blinded: lookup_prove() with the (2 t + e + 6, 4) array of circuit_lookup_blinders() -> the
+        proof bytes, same format and verifier; zero-knowledge.  A KzgError carries .bad_row"""
+        e = self._eng if engine is None else engine
+        a, t, stride, n = e._columns(wires, self.n if n is None else n)
+        assert t == self.t and n == self.n
+        return self._lookup_prove(e._lib.kzg_circuit_lookup_prove_blinded, e, _ptr(a), stride, public_inputs, blinders)
+
+    def lookup_prove_blinded_device(self, d_wires, blinders, public_inputs=None, stride=None):
+        """kzg_circuit_lookup_prove_blinded_device: the wires in a device buffer of the circuit's (single-device) context"""
+        e = self._eng
+        return self._lookup_prove(e._lib.kzg_circuit_lookup_prove_blinded_device, e, C.c_void_p(d_wires),
+                                  self.n if stride is None else stride, public_inputs, blinders)
 
     # -- custom gates: selector x wire-monomial terms (DESIGN.md 4.27) --
     def custom_gate(self, wires, n=None, engine=None):
@@ -2436,6 +2486,24 @@ def circuit_blinders(t, log_ext):
     lib = load_library()
     out = np.zeros((2 * t + 3 + (1 << log_ext) - 2, 4), dtype=np.uint64)
     _check(lib.kzg_circuit_blinders(t, log_ext, _ptr(out)))
+    return out
+
+
+def circuit_lookup_blinded_sizes(n, t, log_ext, c):
+    """kzg_circuit_lookup_blinded_sizes -> (entries of the blinder array, 2 t + e + 6; L_T); KzgError(KZG_ERR_INVALID_ARG) for a
+    shape the blinded lookup calls refuse (max(t n + t + 3, 3 n + 2) >= 2^log_ext n, or a shape no lookup circuit has)"""
+    lib = load_library()
+    nb, lt = C.c_size_t(0), C.c_size_t(0)
+    _check(lib.kzg_circuit_lookup_blinded_sizes(n, t, log_ext, c, C.byref(nb), C.byref(lt)))
+    return int(nb.value), int(lt.value)
+
+
+def circuit_lookup_blinders(t, log_ext):
+    """kzg_circuit_lookup_blinders: the blinder array of one blinded lookup proof -- circuit_blinders' groups, then three for phi
+    and two for m -- as a (2 t + e + 6, 4) array of canonical blst_fr drawn from the OS CSPRNG"""
+    lib = load_library()
+    out = np.zeros((2 * t + (1 << log_ext) + 6, 4), dtype=np.uint64)
+    _check(lib.kzg_circuit_lookup_blinders(t, log_ext, _ptr(out)))
     return out
 
 

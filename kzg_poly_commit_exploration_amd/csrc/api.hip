@@ -6333,7 +6333,53 @@ int blind_custom_shape_refused(kzg_ctx* ctx, const char* what) {
                       "<= (2^log_ext - 1) n + t + 3 and < 2^log_ext n";
     return KZG_ERR_INVALID_ARG;
 }
+// A blinded lookup proof (section 4.30): phi~ = phi + p Z_H with three blinders (linearised at zeta and opened at zeta w, like z),
+// m~ = m + u Z_H with two.  The array is section 4.24's with p_0 .. p_2 and u_0, u_1 behind it.
+constexpr size_t kBlindPhiLen = 3, kBlindMultLen = 2;
+size_t lookup_blind_count(size_t t, size_t e) { return blind_count(t, e) + kBlindPhiLen + kBlindMultLen; }
+// deg Lk1 = deg (phi~(w X) - phi~) F~ Tt = (n + 2) + 2 n + (n - 1) = 4 n + 1, so T~ has max(t n + t + 3, 3 n + 2) coefficients
+size_t lookup_blind_keep(size_t n, size_t t) {
+    const size_t base = t * n + t + 3, look = 3 * n + 2;
+    return look > base ? look : base;
+}
+bool lookup_blind_shape_ok(size_t n, size_t t, size_t e, size_t c) {
+    const size_t keep = lookup_blind_keep(n, t);
+    return lookup_shape_ok(t, e, c) && keep < e * n && keep <= blind_quotient_len(n, t, e);
+}
+int lookup_blind_shape_refused(kzg_ctx* ctx, const char* what) {
+    ctx->last_error = std::string(what) + ": the blinded lookup quotient needs max(t n + t + 3, 3 n + 2) <= (2^log_ext - 1) n + t + 3 "
+                      "and < 2^log_ext n";
+    return KZG_ERR_INVALID_ARG;
+}
+// `count` values uniform below r by rejection: r has 255 bits, a draw is kept with probability 0.906
+int blind_draw(size_t count, uint64_t* out) {
+    for (size_t i = 0; i < count; i++) {
+        hf::Fr v;
+        do {
+            if (!vc_random(v.l, 32)) return KZG_ERR_HIP;
+            v.l[3] &= 0x7fffffffffffffffULL;
+        } while (hf::fr_geq(v, hf::kFrMod));
+        std::memcpy(out + 4 * i, v.l, 32);
+    }
+    return KZG_OK;
+}
 }  // namespace
+
+int kzg_circuit_lookup_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t c, size_t* num_blinders, size_t* quotient_len) {
+    PqShape sh;
+    if (log_ext > kPqMaxLogExt || !pq_shape(n, (size_t)1 << log_ext, &sh) || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns ||
+        !lookup_blind_shape_ok(n, t, sh.rot, c))
+        return KZG_ERR_INVALID_ARG;
+    if (num_blinders) *num_blinders = lookup_blind_count(t, sh.rot);
+    if (quotient_len) *quotient_len = blind_quotient_len(n, t, sh.rot);
+    return KZG_OK;
+}
+
+int kzg_circuit_lookup_blinders(size_t t, unsigned log_ext, uint64_t* out) {
+    if (!out || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || !lookup_shape_ok(t, (size_t)1 << log_ext, 1))
+        return KZG_ERR_INVALID_ARG;
+    return blind_draw(lookup_blind_count(t, (size_t)1 << log_ext), out);
+}
 
 int kzg_circuit_custom_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t d_max, size_t* num_blinders, size_t* quotient_len) {
     PqShape sh;
@@ -6358,16 +6404,7 @@ int kzg_circuit_blinded_sizes(size_t n, size_t t, unsigned log_ext, size_t* num_
 int kzg_circuit_blinders(size_t t, unsigned log_ext, uint64_t* out) {
     if (!out || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext))
         return KZG_ERR_INVALID_ARG;
-    const size_t count = blind_count(t, (size_t)1 << log_ext);
-    for (size_t i = 0; i < count; i++) {
-        hf::Fr v;
-        do {  // uniform below r by rejection: r has 255 bits, a draw is kept with probability 0.906
-            if (!vc_random(v.l, 32)) return KZG_ERR_HIP;
-            v.l[3] &= 0x7fffffffffffffffULL;
-        } while (hf::fr_geq(v, hf::kFrMod));
-        std::memcpy(out + 4 * i, v.l, 32);
-    }
-    return KZG_OK;
+    return blind_draw(blind_count(t, (size_t)1 << log_ext), out);
 }
 
 // evals: k columns of n values over H (host); the k x (n + nb) blinded coefficients go to out_coeffs (host, column c at + 4 c
@@ -6436,24 +6473,36 @@ int kzg_commit_evaluations_blinded(kzg_ctx* ctx, const uint64_t* evals, size_t n
 }
 
 // wires (t columns of n values), z and pi (n values or null) are host pointers, or device pointers when `device`; then out_coeffs
-// (L_T coefficients) is a device pointer.  out_p1s: host, or null
+// (L_T coefficients) is a device pointer.  out_p1s: host, or null.  With a lookup record (section 4.30; host pointers, or a round
+// of the prover, and no custom record) m and phi are transformed back, patched and extended with the wires and z -- the stack is
+// [ f_0 .. f_(t-1) | m | z | phi ], so that the two patches only widen by a column -- and k_lk_constraints fills the gate's workspace
 static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wires, size_t stride, const void* z,
                                          const void* pi, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                                          const uint64_t* blinders, void* out_coeffs, uint64_t* out_p1s, bool device,
-                                         const ProveRound* round = nullptr, const CustomRecord* custom = nullptr) {
+                                         const ProveRound* round = nullptr, const CustomRecord* custom = nullptr,
+                                         const LookupRecord* lookup = nullptr) {
     PqCall call(ctx, round);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
-    const size_t n = sh.n, N = sh.N, t = c->t, e = sh.rot, ncols = t + 1 + (pi ? 1 : 0);
+    if (lookup && !c->c_tab) {
+        ctx->last_error = "circuit lookup quotient (blinded): the circuit was created without a lookup table";
+        return KZG_ERR_INVALID_ARG;
+    }
+    if (lookup && (custom || (device && !round))) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, N = sh.N, t = c->t, e = sh.rot, nbase = t + 1 + (pi ? 1 : 0), nlk = lookup ? 1 : 0, ncols = nbase + 2 * nlk,
+                 nstack = t + 1 + 2 * nlk;
+    if (lookup && !lookup_blind_shape_ok(n, t, e, c->c_tab)) return lookup_blind_shape_refused(ctx, "circuit lookup quotient (blinded)");
     if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit quotient (blinded)");
     if (custom && !c->g_custom) return custom_refused(ctx, "circuit custom quotient (blinded)");
     if (custom && (custom->rho || c->rho)) return custom_kind_refused(ctx, "circuit custom quotient (blinded)", false);
     if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit custom quotient (blinded)");
     std::vector<hf::Fr> bl;
-    if (!blind_values_ok(ctx, "circuit quotient (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
-    const size_t LT = blind_quotient_len(n, t, e), keep = blind_quotient_keep(n, t, custom ? custom->d_max : 0), clen = n + kBlindZLen,
-                 Lc = n + t + 3;
+    const size_t nbl = lookup ? lookup_blind_count(t, e) : blind_count(t, e);
+    if (!blind_values_ok(ctx, lookup ? "circuit lookup quotient (blinded)" : "circuit quotient (blinded)", blinders, nbl, &bl))
+        return KZG_ERR_INVALID_ARG;
+    const size_t LT = blind_quotient_len(n, t, e), clen = n + kBlindZLen, Lc = n + t + 3,
+                 keep = lookup ? lookup_blind_keep(n, t) : blind_quotient_keep(n, t, custom ? custom->d_max : 0);
     if (device) {
         const size_t ob = LT * 32;
         if (pq_overlap(out_coeffs, ob, wires, ((t - 1) * stride + n) * 32) || pq_overlap(out_coeffs, ob, z, n * 32) ||
@@ -6472,44 +6521,72 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
     void *in = nullptr, *cols, *d_out, *coef = out_coeffs, *flag, *stack, *chunks, *d_gate = nullptr;
     // the blinders as the patches read them: the array as given, then a zero and the chunk blinders once more ([0, d_0 .. d_(e-3)]
     // are the low blinders of the e - 1 chunks, [d_0 ..] the high ones)
-    const size_t nbl = blind_count(t, e), bl_words = 8 * (nbl + 1 + (e - 2));
+    // With a lookup record the array's groups lie in the stack's order: [ b | u | c | p | d ], then the zero and the d once more.
+    const size_t bl_words = 8 * (nbl + 1 + (e - 2)), zcol = t + nlk, bl_z = 2 * t + kBlindMultLen * nlk;
     rc = pq_bufs(ctx, N, ncols, &w);
     if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqIn, ncols * n * 32, &in);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqCols, ncols * N * 32, &cols);  // wires, z, PI on the coset
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqOut, N * 32, &d_out);
     if (rc == KZG_OK && !device) rc = ctx->pq_ws.get(ctx, kPqCoef, LT * 32, &coef);
     if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqFlag, 4, &flag);
-    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqBlind, (t + 1) * clen * 32 + bl_words * 4, &stack);  // the blinded coefficients
+    if (rc == KZG_OK) rc = ctx->pq_ws.get(ctx, kPqBlind, nstack * clen * 32 + bl_words * 4, &stack);  // the blinded coefficients
     if (rc == KZG_OK && out_p1s) rc = ctx->pq_ws.get(ctx, kPqChunks, (e - 1) * Lc * 32, &chunks);
-    if (rc == KZG_OK && custom) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
+    if (rc == KZG_OK && (custom || lookup)) rc = ctx->pq_ws.get(ctx, kPqGate, N * 32, &d_gate);
     if (rc) return rc;
-    uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * t * N, *d_pi = pi ? d_z + 8 * N : nullptr;
-    uint32_t *d_c = (uint32_t*)stack, *d_bl = d_c + 8 * (t + 1) * clen;
+    // on the coset: [ f | z | PI ], with a lookup record [ f | m | z | phi | PI ]
+    uint32_t *d_w = (uint32_t*)cols, *d_z = d_w + 8 * zcol * N, *d_pi = pi ? d_w + 8 * nstack * N : nullptr;
+    uint32_t *d_m = d_w + 8 * t * N, *d_phi = d_z + 8 * N;  // (with a lookup record)
+    uint32_t *d_c = (uint32_t*)stack, *d_bl = d_c + 8 * nstack * clen;
     {
         std::vector<uint64_t> hb(bl_words / 2, 0);
-        std::memcpy(hb.data(), blinders, nbl * 32);
-        std::memcpy(hb.data() + 4 * (nbl + 1), blinders + 4 * (2 * t + kBlindZLen), (e - 2) * 32);
+        const uint64_t* d_src = blinders + 4 * (2 * t + kBlindZLen);  // d_0 .. d_(e-3)
+        if (lookup) {
+            const uint64_t *p_src = d_src + 4 * (e - 2), *u_src = p_src + 4 * kBlindPhiLen;
+            std::memcpy(hb.data(), blinders, 2 * t * 32);
+            std::memcpy(hb.data() + 4 * 2 * t, u_src, kBlindMultLen * 32);
+            std::memcpy(hb.data() + 4 * bl_z, blinders + 4 * 2 * t, kBlindZLen * 32);
+            std::memcpy(hb.data() + 4 * (bl_z + kBlindZLen), p_src, kBlindPhiLen * 32);
+        } else {
+            std::memcpy(hb.data(), blinders, nbl * 32);
+        }
+        std::memcpy(hb.data() + 4 * (nbl + 1), d_src, (e - 2) * 32);
         rc = copy_unlocked(ctx, lk, s.stream, d_bl, hb.data(), bl_words * 4, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
         if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit quotient (blinded)");  // (hb leaves scope)
         if (rc) return rc;
     }
     PqStaged src;
     rc = pq_stage(ctx, lk, s.stream, device, (uint32_t*)in, wires, stride, z, pi, n, t, false, &src);
+    if (rc == KZG_OK && lookup && !round) {  // [ wires | z | PI | m | phi ] in the staging buffer
+        rc = pq_upload(ctx, lk, s.stream, (uint32_t*)in + 8 * nbase * n, (const uint64_t*)lookup->mult, n, 1, n);
+        if (rc == KZG_OK) rc = pq_upload(ctx, lk, s.stream, (uint32_t*)in + 8 * (nbase + 1) * n, (const uint64_t*)lookup->phi, n, 1, n);
+    }
     if (rc) return rc;
-    {  // the wires and z: values -> coefficients -> patch -> the coset, from n + 3 coefficients each
+    {  // the wires and z (m and phi with them): values -> coefficients -> patch -> the coset, from n + 3 coefficients each
         const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
         const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
-        if (round) {  // the resident coefficients [ f | PI | z ], copied under the patches
+        if (round) {  // the resident coefficients [ f | PI | z ] (a lookup round: [ f | PI | z | phi | m ]), copied under the patches
+            const uint32_t* u_z = round->coef + 8 * (nbase - 1) * n;
             HIP_TRY(ctx, hipMemcpy2DAsync(d_c, clen * 32, round->coef, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
-            HIP_TRY(ctx, hipMemcpyAsync(d_c + 8 * t * clen, round->coef + 8 * (ncols - 1) * n, n * 32, hipMemcpyDeviceToDevice, s.stream));
+            if (lookup) {
+                HIP_TRY(ctx, hipMemcpyAsync(d_c + 8 * t * clen, u_z + 16 * n, n * 32, hipMemcpyDeviceToDevice, s.stream));
+                HIP_TRY(ctx, hipMemcpy2DAsync(d_c + 8 * zcol * clen, clen * 32, u_z, n * 32, n * 32, 2, hipMemcpyDeviceToDevice, s.stream));
+            } else {
+                HIP_TRY(ctx, hipMemcpyAsync(d_c + 8 * t * clen, u_z, n * 32, hipMemcpyDeviceToDevice, s.stream));
+            }
         } else {
             for (size_t j = 0; j < t; j++) launch_ntt(s.stream, src.w + 8 * j * src.stride, d_c + 8 * j * clen, sh.lg_n, itw, inv_n, w.A, w.B);
-            launch_ntt(s.stream, src.z, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            launch_ntt(s.stream, src.z, d_c + 8 * zcol * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            if (lookup) {
+                const uint32_t* s_m = (const uint32_t*)in + 8 * nbase * n;
+                launch_ntt(s.stream, s_m, d_c + 8 * t * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+                launch_ntt(s.stream, s_m + 8 * n, d_c + 8 * (zcol + 1) * clen, sh.lg_n, itw, inv_n, w.A, w.B);
+            }
         }
-        launch_blind_patch(s.stream, d_c, (uint32_t)n, t, clen, d_bl, d_bl, kBlindWireLen, t);
-        launch_blind_patch(s.stream, d_c + 8 * t * clen, (uint32_t)n, 1, clen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
+        // nb = 2: the wires (and m behind them); nb = 3: z (and phi behind it)
+        launch_blind_patch(s.stream, d_c, (uint32_t)n, zcol, clen, d_bl, d_bl, kBlindWireLen, zcol);
+        launch_blind_patch(s.stream, d_c + 8 * zcol * clen, (uint32_t)n, 1 + nlk, clen, d_bl + 8 * bl_z, d_bl + 8 * bl_z, kBlindZLen, 1 + nlk);
         HIP_TRY(ctx, hipGetLastError());
-        rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, t + 1, sh.lg_N, d_w, w, nullptr, round != nullptr);
+        rc = pq_extend(ctx, s.stream, d_c, clen, clen, -1, nstack, sh.lg_N, d_w, w, nullptr, round != nullptr);
         if (rc == KZG_OK && pi && round) rc = pq_extend(ctx, s.stream, round->coef + 8 * t * n, n, n, -1, 1, sh.lg_N, d_pi, w);
         if (rc == KZG_OK && pi && !round) rc = pq_extend(ctx, s.stream, src.pi, n, n, (int)sh.lg_n, 1, sh.lg_N, d_pi, w);
         if (rc) return rc;
@@ -6518,9 +6595,17 @@ static int circuit_quotient_blinded_impl(kzg_ctx* ctx, const kzg_circuit* c, con
         rc = cg_enqueue(ctx, s.stream, c, sh, d_w, (uint32_t*)d_gate);
         if (rc) return rc;
     }
+    if (lookup) {  // G'~ = alpha^3 Lk1 + alpha^4 Lk2 from the blinded columns on the coset
+        const LkKernelScalars lsc(lookup->theta, beta, alpha, c->c_tab);
+        const uint32_t* key = c->coset.dev() + 8 * (2 * t + 2) * N;
+        const LkColumns lc{d_w, key, key + 8 * c->c_tab * N, c->l0.dev(), d_m, d_phi};
+        launch_lk_constraints(s.stream, lc, sh.lg_N, (uint32_t)sh.rot, (uint32_t)c->c_tab, N, lsc.view(), (uint32_t*)d_gate);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     rc = ck_constraints(ctx, s.stream, c, sh, d_w, d_z, d_pi, (const uint32_t*)d_gate, alpha, beta, gamma, (uint32_t*)d_out);
     if (rc) return rc;
-    // T~ has t n + t + 3 coefficients (with custom gates of a degree above t: d_max (n + 1)): those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
+    // T~ has t n + t + 3 coefficients (with custom gates of a degree above t: d_max (n + 1); with a lookup record max(t n + t + 3,
+    // 3 n + 2)): those are kept, whatever follows up to N must vanish, and up to L_T the output is zero
     if (LT > keep) HIP_TRY(ctx, hipMemsetAsync((uint32_t*)coef + 8 * keep, 0, (LT - keep) * 32, s.stream));
     bool remainder = false;
     rc = pq_finish(ctx, lk, s.stream, sh, (uint32_t*)d_out, false, w, (uint32_t*)coef, (uint32_t*)flag, keep, LT,
@@ -6563,6 +6648,22 @@ int kzg_circuit_quotient_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit
     if (!ctx || !circuit || !d_wires || !d_z || !alpha || !beta || !gamma || !blinders || !d_out_coeffs) return KZG_ERR_INVALID_ARG;
     return circuit_quotient_blinded_impl(ctx, circuit, d_wires, stride, d_z, d_public_inputs, alpha, beta, gamma, blinders, d_out_coeffs,
                                          out_p1s, true);
+}
+
+int kzg_circuit_lookup_quotient_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* wires, size_t stride, const uint64_t* z,
+                                        const uint64_t* mult, const uint64_t* phi, const uint64_t* public_inputs, const uint64_t alpha[4],
+                                        const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], const uint64_t* blinders,
+                                        uint64_t* out_coeffs, uint64_t* out_p1s) {
+    if (!ctx || !circuit || !wires || !z || !mult || !phi || !alpha || !beta || !gamma || !theta || !blinders) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, out_p1s != nullptr, "the quotient's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_lookup_quotient_blinded(kid, circuit, wires, stride, z, mult, phi, public_inputs, alpha, beta,
+                                                                      gamma, theta, blinders, out_coeffs, out_p1s));
+    }
+    const LookupRecord rec{mult, phi, theta};
+    return circuit_quotient_blinded_impl(ctx, circuit, wires, stride, z, public_inputs, alpha, beta, gamma, blinders, out_coeffs, out_p1s,
+                                         false, nullptr, nullptr, &rec);
 }
 
 // ---- the custom gates of a circuit whose key holds selector x monomial terms (custom_gate_kernels.hip) -----
@@ -6764,16 +6865,21 @@ int lin_remainder(kzg_ctx* ctx) {
 
 // The slot's table of a blinded round (s.btab): per distinct point the records of k_blind_tail and the t + 6 powers of the point,
 // then the blinders as the records point at them, 32 bytes an entry: [b_j0, b_j1, 0] per wire, [c_0, c_1, c_2], and per chunk of T
-// [d_(c-1), 0, 0, d_c] (d_(-1) = d_(e-2) = 0).
+// [d_(c-1), 0, 0, d_c] (d_(-1) = d_(e-2) = 0); in a lookup round (section 4.30) then [p_0, p_1, p_2] and [u_0, u_1, 0].
 constexpr size_t kBlindPointBytes = 1536, kBlindValueBytes = 64 * 32;
 static_assert(kBlindMaxColumns * sizeof(BlindColumn) + (kPqMaxColumns + 3 + kBlindLow) * sizeof(Fr30) <= kBlindPointBytes, "btab");
-static_assert((3 * kPqMaxColumns + 3 + 4 * 7) * 32 <= kBlindValueBytes, "btab");
+static_assert((3 * kPqMaxColumns + 3 + 4 * 7 + 3 + 3) * 32 <= kBlindValueBytes, "btab");
 static_assert(kPqMaxColumns + 2 + 7 <= kBlindMaxColumns, "the wires, z twice (n = 1: one point) and the chunks of T");
+// (a lookup round has phi~ and m~ as well: t + e + 2 records at zeta, within kBlindMaxColumns by the lookup's shape rule, t <= 6 and
+// e <= 8, and not by this assertion; blind_tails counts before it writes)
 // Behind the launches of k_lin_combine (G_p over [0, n) from the unblinded columns, at s.sg + 8 p L words): what the blinders add.
 // lin: r~'s terms with the scalars of the blinded evaluations; d_t: T~'s coefficients, whose last chunk reaches to n + t + 3.
+// phi_poly: the stack's index of phi~ in a lookup round (r~_L's terms then end with phi~ and m~: two more records at zeta and one
+// at zeta w, t + e + 2 <= kBlindMaxColumns at zeta since the lookup's shape rule gives t <= 6 and e <= 8), or 0.
 int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin, const std::vector<hf::Fr>& bl, const uint32_t* d_t,
-                size_t n, size_t t, size_t e, uint32_t* d_y) {
+                size_t n, size_t t, size_t e, uint32_t* d_y, size_t phi_poly = 0) {
     const size_t ntail = t + 3, L = n + ntail, val_off = kSetsMaxPoints * kBlindPointBytes, zb = 3 * t, cb = 3 * t + 3;
+    const size_t pb = cb + 4 * (e - 1), ub = pb + 3;  // (a lookup round)
     uint8_t* h = (uint8_t*)s.btab.h;
     const uint8_t* d = (const uint8_t*)s.btab.d;
     uint64_t* hv = (uint64_t*)(h + val_off);
@@ -6788,6 +6894,10 @@ int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin,
     for (size_t c = 0; c + 1 < e; c++) {
         if (c >= 1) std::memcpy(hv + 4 * (cb + 4 * c), dc[c - 1].l, 32);
         if (c + 2 < e) std::memcpy(hv + 4 * (cb + 4 * c + 3), dc[c].l, 32);
+    }
+    if (phi_poly) {  // p_0 .. p_2 and u_0, u_1 lie behind the d_c
+        for (size_t k = 0; k < kBlindPhiLen; k++) std::memcpy(hv + 4 * (pb + k), dc[e - 2 + k].l, 32);
+        for (size_t k = 0; k < kBlindMultLen; k++) std::memcpy(hv + 4 * (ub + k), dc[e - 2 + kBlindPhiLen + k].l, 32);
     }
     auto column = [&](size_t low_entry, const uint32_t* tail, size_t tail_len, const hf::Fr& mult) {
         BlindColumn col = {};
@@ -6805,6 +6915,10 @@ int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin,
         for (uint32_t en = plan.off[p]; en < plan.off[p + 1]; en++) {
             const uint32_t i = plan.sel[en];
             const hf::Fr& m = plan.mult[en];
+            // the records this polynomial adds, before any is written (cannot happen: without a lookup the static_assert above,
+            // with one its shape rule -- t + e + 2 <= 16 at zeta, t + e + 4 = 14 at n = 1, where D < N leaves t = 2, e = 8 alone)
+            const size_t adds = i == 0 ? e + (phi_poly ? 2 : 0) : (i <= t || i == 2 * t || (phi_poly && i == phi_poly) ? 1 : 0);
+            if (k + adds > kBlindMaxColumns) return KZG_ERR_INVALID_ARG;
             if (i == 0) {  // r~: z~ and the chunks of T~ with r's scalars
                 out[k++] = column(zb, dv + 8 * zb, kBlindZLen, hf::fr_mul(m, lin.terms[t + 2].scalar));
                 for (size_t c = 0; c + 1 < e; c++) {
@@ -6812,12 +6926,18 @@ int blind_tails(kzg_ctx* ctx, Slot& s, const SetsPlan& plan, const LinPoly& lin,
                     if (c + 2 < e) out[k++] = column(cb + 4 * c, dv + 8 * (cb + 4 * c + 3), 1, sc);
                     else out[k++] = column(cb + 4 * c, d_t + 8 * (e - 1) * n, ntail, sc);
                 }
+                if (phi_poly) {  // phi~ and m~ with r_L's scalars (lin's last two terms)
+                    const size_t nt = lin.terms.size();
+                    out[k++] = column(pb, dv + 8 * pb, kBlindPhiLen, hf::fr_mul(m, lin.terms[nt - 2].scalar));
+                    out[k++] = column(ub, dv + 8 * ub, kBlindMultLen, hf::fr_mul(m, lin.terms[nt - 1].scalar));
+                }
             } else if (i <= t) {
                 out[k++] = column(3 * (i - 1), dv + 8 * 3 * (i - 1), kBlindWireLen, m);
             } else if (i == 2 * t) {
                 out[k++] = column(zb, dv + 8 * zb, kBlindZLen, m);
-            }  // (the sigmas are the key's: not blinded)
-            if (k > kBlindMaxColumns) return KZG_ERR_INVALID_ARG;  // (cannot happen: the static_assert above)
+            } else if (phi_poly && i == phi_poly) {
+                out[k++] = column(pb, dv + 8 * pb, kBlindPhiLen, m);
+            }  // (the sigmas and the table are the key's: not blinded)
         }
         ncols[p] = k;
         Fr30* pw = (Fr30*)(h + p * kBlindPointBytes + kBlindMaxColumns * sizeof(BlindColumn));
@@ -6856,7 +6976,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n) return KZG_ERR_INVALID_ARG;
-    if (lookup && (!c->c_tab || !round || blinders || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_lookup_prove only)
+    if (lookup && (!c->c_tab || !round || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_lookup_prove or of its _blinded form only)
     if (custom && (!c->g_custom || !round || lookup || !v)) return KZG_ERR_INVALID_ARG;  // (a round of kzg_circuit_custom_prove only)
     if (custom && (custom->rho != c->rho || (custom->rho && (blinders || c->n < 2)))) return KZG_ERR_INVALID_ARG;
     // a next-row round (section 4.28): the rho wires of R are opened on {zeta, zeta w}; out_evals then has 2 t + rho values
@@ -6874,9 +6994,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
     const size_t e = sh.rot, ntail = blinders ? t + 3 : 0, L = n + ntail, t_len = blinders ? blind_quotient_len(n, t, e) : N - n;
     std::vector<hf::Fr> bl;
     if (blinders) {
+        if (lookup && !lookup_blind_shape_ok(n, t, e, lc)) return lookup_blind_shape_refused(ctx, "circuit open (blinded)");
         if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit open (blinded)");
         if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit open (blinded)");
-        if (!blind_values_ok(ctx, "circuit open (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+        if (!blind_values_ok(ctx, "circuit open (blinded)", blinders, lookup ? lookup_blind_count(t, e) : blind_count(t, e), &bl))
+            return KZG_ERR_INVALID_ARG;
     }
     // the stack [ r | f_0 .. f_(t-1) | sigma_0 .. sigma_(t-2) | z ] on the sets {zeta}, {zeta w} (one point for n = 1, w = 1); with
     // a lookup record it goes on with [ tab_0 .. tab_(c-1) | q_K | phi ], phi in the second set
@@ -6985,6 +7107,11 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         const hf::Fr* cz = &bl[2 * t];
         const hf::Fr cw = hf::fr_add(cz[0], hf::fr_mul(zeta_w, hf::fr_add(cz[1], hf::fr_mul(zeta_w, cz[2]))));
         ys[2 * t] = hf::fr_add(ys[2 * t], hf::fr_mul(cw, Z));
+        if (lookup) {  // phi~(zeta w) = phi(zeta w) + p(zeta w) Z
+            const hf::Fr* pz = &bl[2 * t + kBlindZLen + (e - 2)];
+            const hf::Fr pw = hf::fr_add(pz[0], hf::fr_mul(zeta_w, hf::fr_add(pz[1], hf::fr_mul(zeta_w, pz[2]))));
+            ys[npoly - 1] = hf::fr_add(ys[npoly - 1], hf::fr_mul(pw, Z));
+        }
     }
     for (size_t i = 1; i < npoly; i++) std::memcpy(out_evals + 4 * (i - 1), ys[i].l, 32);
     for (size_t k = 0; k < rho; k++) std::memcpy(out_evals + 4 * (npoly - 1 + k), ys_next[k].l, 32);
@@ -7066,7 +7193,7 @@ static int circuit_open_impl(kzg_ctx* ctx, const kzg_circuit* c, const void* wir
         launch_lin_combine(s.stream, d_cols + p * kLinMaxColumns, ncols[p], (uint32_t)n, d_tab + p * kCombineTabGamma, konst[p],
                            s.sg.dev() + 8 * p * L, s.cpart.dev(), d_y + 8 * p);
     if (blinders) {
-        rc = blind_tails(ctx, s, plan, lin, bl, (const uint32_t*)coef, n, t, e, d_y);
+        rc = blind_tails(ctx, s, plan, lin, bl, (const uint32_t*)coef, n, t, e, d_y, lookup ? npoly - 1 : 0);
         if (rc) return rc;
     }
     if (s.timing) HIP_TRY(ctx, hipEventRecord(s.cmb_ev[1], s.stream));
@@ -10147,11 +10274,15 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     std::memcpy(out_proof, proof.data(), L.len);
     return KZG_OK;
 }
-// kzg_circuit_lookup_prove: circuit_prove_impl's sibling with two more rounds, never blinded.  The values
+// kzg_circuit_lookup_prove: circuit_prove_impl's sibling with two more rounds.  The values
 // V are [ wires | PI | z | phi | m | f | T ] (f, T: the folded columns), the coefficients U [ wires | PI | z | phi | m ]; the call
 // holds lookup_mu (the hash table of the multiplicities) between quotient_mu and the context's mutex.
+// blinders (host, or null): kzg_circuit_lookup_prove_blinded (section 4.30).  U stays unblinded, as the rounds read it; the blinded
+// copies that are committed go to S, [ wires (n + 2 each) | m (n + 2) | z | phi (n + 3 each) ], the blinders they are patched with to B
+// in the same order, [ b | u | c | p ].
 int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
-                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row, bool device) {
+                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row, bool device,
+                              const uint64_t* blinders = nullptr) {
     // lookup_mu is taken after quotient_mu and given up after the frame has drained the stream (declared first, destroyed last)
     std::unique_lock<std::mutex> lkl(ctx->lookup_mu, std::defer_lock);
     PqCall call(ctx);
@@ -10164,23 +10295,35 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
     for (size_t j = 0; j < t; j++) std::memcpy(ks[j].l, c->shifts + 4 * j, 32);
     for (size_t i = 0; i < n_public; i++)
         if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
+    if (blinders) {
+        std::vector<hf::Fr> bl;
+        if (!lookup_blind_shape_ok(n, t, e, lc)) return lookup_blind_shape_refused(ctx, "circuit lookup prove (blinded)");
+        if (!blind_values_ok(ctx, "circuit lookup prove (blinded)", blinders, lookup_blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+    }
+    const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
+    const size_t wlen = blinders ? n + kBlindWireLen : n, zlen = blinders ? n + kBlindZLen : n;
+    const size_t nbw = 2 * t + kBlindMultLen, nbz = kBlindZLen + kBlindPhiLen;  // B: [ b | u ], then [ c | p ]
     lkl.lock();
     call.lock();
-    int rc = pq_srs_status(ctx, true, n);
+    int rc = pq_srs_status(ctx, true, need);
     if (rc == KZG_OK) rc = call.begin();
-    if (rc == KZG_OK) rc = pq_srs_status(ctx, true, n);  // (the wait for a slot dropped the mutex)
+    if (rc == KZG_OK) rc = pq_srs_status(ctx, true, need);  // (the wait for a slot dropped the mutex)
     if (rc == KZG_OK) rc = ensure_ntt_batch(ctx);
     if (rc) return rc;
     std::unique_lock<std::mutex>& lk = call.lk();
     Slot& s = call.s();
     const int slot = call.slot();
-    DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &T = ctx->prove_buf[3];
+    DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &S = ctx->prove_buf[2], &T = ctx->prove_buf[3], &B = ctx->prove_buf[4];
     rc = V.reserve(ctx, (ncoef + 4) * n * 32, s.stream);
     if (rc == KZG_OK) rc = U.reserve(ctx, (ncoef + 2) * n * 32, s.stream);
-    if (rc == KZG_OK) rc = T.reserve(ctx, (sh.N - n) * 32, s.stream);
+    if (rc == KZG_OK) rc = T.reserve(ctx, t_len * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = S.reserve(ctx, ((t + 1) * wlen + 2 * zlen) * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = B.reserve(ctx, (nbw + nbz) * 32, s.stream);
     if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
     if (rc) return rc;
     uint32_t *d_v = V.dev(), *d_u = U.dev();
+    uint32_t *d_s = blinders ? S.dev() : nullptr, *d_sm = blinders ? d_s + 8 * t * wlen : nullptr, *d_sz = blinders ? d_sm + 8 * wlen : nullptr;
+    uint32_t* d_bl = blinders ? B.dev() : nullptr;
     uint32_t *d_vz = d_v + 8 * (ncoef - 1) * n, *d_vphi = d_vz + 8 * n, *d_vm = d_vphi + 8 * n, *d_vf = d_vm + 8 * n, *d_vt = d_vf + 8 * n;
     uint32_t *d_uz = d_u + 8 * (ncoef - 1) * n, *d_um = d_uz + 16 * n;
     const ProveRound round_base{&lk, slot, d_u, nullptr};
@@ -10224,9 +10367,27 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
                            "hipMemcpyAsync (public inputs)");
         if (rc) return rc;
     }
+    if (blinders) {  // B = [ b | u | c | p ] from the array's [ b | c | d | p | u ]
+        const uint64_t *c_src = blinders + 4 * 2 * t, *p_src = c_src + 4 * (kBlindZLen + e - 2), *u_src = p_src + 4 * kBlindPhiLen;
+        rc = copy_unlocked(ctx, lk, s.stream, d_bl, blinders, 2 * t * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+        if (rc == KZG_OK)
+            rc = copy_unlocked(ctx, lk, s.stream, d_bl + 8 * 2 * t, u_src, kBlindMultLen * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+        if (rc == KZG_OK)
+            rc = copy_unlocked(ctx, lk, s.stream, d_bl + 8 * nbw, c_src, kBlindZLen * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
+        if (rc == KZG_OK)
+            rc = copy_unlocked(ctx, lk, s.stream, d_bl + 8 * (nbw + kBlindZLen), p_src, kBlindPhiLen * 32, hipMemcpyHostToDevice,
+                               "hipMemcpyAsync (blinders)");
+        if (rc) return rc;
+    }
     rc = to_coefficients(0, ncoef - 1);
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (wires)");
-    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, d_u, n, t, p1s.data());
+    if (rc) return rc;
+    if (blinders) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_s, wlen * 32, d_u, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
+        launch_blind_patch(s.stream, d_s, (uint32_t)n, t, wlen, d_bl, d_bl, kBlindWireLen, t);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (wires)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_s : d_u, wlen, t, p1s.data());
     if (rc) return rc;
     put_points(0, t);
     proof_absorb(h, proof.data() + L.wires, L.m - L.wires);
@@ -10240,6 +10401,11 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
         HIP_TRY(ctx, hipGetLastError());
         rc = lu_mult_enqueue(ctx, s, d_vt, n, d_vf, n, 1, n, lu_default_log_capacity(n), d_vm, nullptr);
         if (rc == KZG_OK) rc = to_coefficients(ncoef + 1, 1);
+        if (rc == KZG_OK && blinders) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_sm, d_um, n * 32, hipMemcpyDeviceToDevice, s.stream));
+            launch_blind_patch(s.stream, d_sm, (uint32_t)n, 1, wlen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindMultLen, 1);
+            HIP_TRY(ctx, hipGetLastError());
+        }
         if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (multiplicities)");
         if (rc) return rc;
         size_t bad = (size_t)-1;
@@ -10251,7 +10417,7 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
         }
         if (rc) return rc;
     }
-    rc = pq_commit_chunks(ctx, lk, slot, d_um, n, 1, p1s.data() + 18 * t);
+    rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sm : d_um, wlen, 1, p1s.data() + 18 * t);
     if (rc) return rc;
     put_points(t, 1);
     proof_absorb(h, proof.data() + L.m, 48);
@@ -10279,8 +10445,13 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
         }
     }
     rc = to_coefficients(ncoef - 1, 2);
+    if (rc == KZG_OK && blinders) {  // z and phi lie side by side in U and in S, c and p in B: one patch
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_sz, zlen * 32, d_uz, n * 32, n * 32, 2, hipMemcpyDeviceToDevice, s.stream));
+        launch_blind_patch(s.stream, d_sz, (uint32_t)n, 2, zlen, d_bl + 8 * nbw, d_bl + 8 * nbw, kBlindZLen, 2);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (z, phi)");
-    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, d_uz, n, 2, p1s.data() + 18 * (t + 1));
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sz : d_uz, zlen, 2, p1s.data() + 18 * (t + 1));
     if (rc) return rc;
     put_points(t + 1, 2);
     proof_absorb(h, proof.data() + L.z, 96);
@@ -10289,8 +10460,10 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
     // round 4: the quotient with the lookup's term from the resident coefficients, its chunks' commitments; zeta
     const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
     const LookupRecord rec{d_vm, d_vphi, theta.l};
-    rc = circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 3), true,
-                               &round_base, &rec);
+    rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p,
+                                                  p1s.data() + 18 * (t + 3), true, &round_base, nullptr, &rec)
+                  : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 3), true,
+                                          &round_base, &rec);
     if (rc) return rc;
     put_points(t + 3, e - 1);
     proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
@@ -10310,7 +10483,7 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
         return true;
     };
     rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
-                           evals.data(), nullptr, p1s.data() + 18 * np1, true, nullptr, &last_round, &rec);
+                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round, &rec);
     if (rc) return rc;
     hf::P1 w;
     std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
@@ -10338,6 +10511,29 @@ int kzg_circuit_lookup_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, co
     KZG_SINGLE_DEVICE_ONLY(ctx);
     if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
     return circuit_lookup_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, out_proof, bad_row, true);
+}
+
+int kzg_circuit_lookup_prove_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires,
+                                     size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                     uint8_t* out_proof, size_t* bad_row) {
+    if (bad_row) *bad_row = (size_t)-1;
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !blinders || !out_proof) return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_circuit_lookup_prove_blinded(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders,
+                                                                   out_proof, bad_row));
+    }
+    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row, false, blinders);
+}
+
+int kzg_circuit_lookup_prove_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
+                                            size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
+                                            uint8_t* out_proof, size_t* bad_row) {
+    if (bad_row) *bad_row = (size_t)-1;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !blinders || !out_proof) return KZG_ERR_INVALID_ARG;
+    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, out_proof, bad_row, true, blinders);
 }
 
 int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,

@@ -9275,15 +9275,24 @@ int circuit_verify_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned lo
 }
 }  // namespace
 
-// ---- a circuit's proof as bytes: the hashed transcript and the proof format (host only) -----------------
-//   h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(n_public) | shifts | key commitments | public inputs)
-//   h1 = SHA256(h0 | wire commitments)   beta = fr(SHA256(h1 | 00)), gamma = fr(SHA256(h1 | 01))
-//   h2 = SHA256(h1 | [z])                alpha = fr(SHA256(h2 | 00))
-//   h3 = SHA256(h2 | [T_0] .. [T_(e-2)]) zeta = fr(SHA256(h3 | 00))
-//   h4 = SHA256(h3 | evaluations)        v = fr(SHA256(h4 | 00))
+// ---- a circuit's proof as bytes: the hashed transcript and the proof formats (host only) -----------------
+// The four formats (plain; custom gates, section 4.27; next-row gates, 4.28; lookup, 4.26) are instances of one description, ProofSpec:
+//   h0 = SHA256(DST | header | shifts | exponents (custom kinds) | the nkey key commitments | public inputs)
+//   the proof is a list of segments; h_(i+1) = SHA256(h_i | segment i), after which that segment's challenges are drawn,
+//   fr(SHA256(h_(i+1) | 00)) and, for a second one, fr(SHA256(h_(i+1) | 01))
+//   kind     DST                              header (u64be)                 nkey           nevals
+//   plain    kzg_mi355x/plonk/v1              n, t, log_ext, n_public        2 t + 2        2 t
+//   custom   kzg_mi355x/plonk-custom/v1       n, t, log_ext, g, n_public     2 t + 2 + g    2 t
+//   next     kzg_mi355x/plonk-custom-next/v1  n, t, log_ext, g, n_public     2 t + 2 + g    2 t + rho
+//   lookup   kzg_mi355x/plonk-lookup/v1       n, t, log_ext, c, n_public     2 t + c + 3    2 t + c + 2
+//   segments, plain family:  wires -> beta, gamma | [z] -> alpha | [T_0] .. [T_(e-2)] -> zeta | evaluations -> v | W
+//   segments, lookup:        wires -> theta | [m] -> beta, gamma | [z] [phi] -> alpha | chunks -> zeta | evaluations -> v | W
 // scalars as 32 big-endian canonical bytes, points as 48 compressed bytes, fr(d) = d read big-endian mod r.
 namespace {
-constexpr char kProofDst[] = "kzg_mi355x/plonk/v1";  // 19 bytes, hashed without the terminator
+constexpr char kProofDst[] = "kzg_mi355x/plonk/v1";  // each hashed without the terminator
+constexpr char kCustomProofDst[] = "kzg_mi355x/plonk-custom/v1";
+constexpr char kNextProofDst[] = "kzg_mi355x/plonk-custom-next/v1";
+constexpr char kLookupProofDst[] = "kzg_mi355x/plonk-lookup/v1";
 
 void proof_fr_to_be(const hf::Fr& mont, uint8_t out[32]) {
     uint64_t plain[4];
@@ -9328,216 +9337,278 @@ void proof_absorb(uint8_t state[32], const uint8_t* data, size_t len) {
     hf::sha256_update(s, data, len);
     hf::sha256_final(s, state);
 }
-void proof_u64be(uint8_t* out, uint64_t x) {
-    for (int i = 0; i < 8; i++) out[i] = (uint8_t)(x >> (8 * (7 - i)));
-}
-// h0: everything the statement fixes before the prover speaks
-void proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts,
-                     const hf::Fr* pub, size_t n_public) {
-    std::vector<uint8_t> m(19 + 32 + 32 * t + 48 * (2 * t + 2) + 32 * n_public);
-    uint8_t* p = m.data();
-    std::memcpy(p, kProofDst, 19);
-    proof_u64be(p + 19, n);
-    proof_u64be(p + 27, t);
-    proof_u64be(p + 35, log_ext);
-    proof_u64be(p + 43, n_public);
-    p += 51;
-    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
-    for (size_t j = 0; j < 2 * t + 2; j++, p += 48) {
-        hf::P1 c;
-        std::memcpy(&c, key_p1s + 18 * j, sizeof c);
-        hf::p1_compress(p, c);
-    }
-    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
-    hf::Sha256 s;
-    hf::sha256_init(s);
-    hf::sha256_update(s, m.data(), m.size());
-    hf::sha256_final(s, state);
-}
-// the offsets of the proof's five fields: wires, [z], chunks, evaluations, W, and its length
-struct ProofLayout {
-    size_t wires, z, chunks, evals, w, len;
+
+enum ProofKind { kProofPlain, kProofCustom, kProofNext, kProofLookup };
+// a run of the proof's bytes that the transcript absorbs whole, and the challenges drawn after it
+struct ProofSegment {
+    size_t off, len, draws;
 };
-// (rho: the scalars a next-row proof has behind the plain proof's 2 t, section 4.28)
-ProofLayout proof_layout(size_t t, size_t e, size_t rho = 0) {
-    ProofLayout L;
-    L.wires = 0;
-    L.z = 48 * t;
-    L.chunks = L.z + 48;
-    L.evals = L.chunks + 48 * (e - 1);
-    L.w = L.evals + 32 * (2 * t + rho);
-    L.len = L.w + 48;
-    return L;
-}
-bool proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t n_public) {
-    PqShape sh;
-    return log_ext <= kPqMaxLogExt && pq_shape(n, (size_t)1 << log_ext, &sh) && t >= KZG_CIRCUIT_MIN_COLUMNS && t <= kPqMaxColumns &&
-           t + 1 <= sh.rot && n_public <= n;
-}
-// h0 of a custom circuit's proof (section 4.27): a domain of its own, g and the exponents in the statement, the key's 2 t + 2 + g
-// commitments; from h1 on the chain is the plain proof's
-constexpr char kCustomProofDst[] = "kzg_mi355x/plonk-custom/v1";  // 26 bytes, hashed without the terminator
-constexpr size_t kCustomDstLen = sizeof kCustomProofDst - 1;
-// h0 of a next-row circuit's proof (section 4.28; exps_next not null): a third domain, the second matrix behind the first
-constexpr char kNextProofDst[] = "kzg_mi355x/plonk-custom-next/v1";  // 31 bytes, hashed without the terminator
-constexpr size_t kNextDstLen = sizeof kNextProofDst - 1;
-void custom_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps,
-                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public, const uint8_t* exps_next = nullptr) {
-    const size_t nkey = 2 * t + 2 + g, dst_len = exps_next ? kNextDstLen : kCustomDstLen;
-    std::vector<uint8_t> m(dst_len + 40 + 32 * t + (exps_next ? 2 : 1) * g * t + 48 * nkey + 32 * n_public);
-    uint8_t* p = m.data();
-    std::memcpy(p, exps_next ? kNextProofDst : kCustomProofDst, dst_len);
-    p += dst_len;
-    for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)g, (uint64_t)n_public}) {
-        proof_u64be(p, x);
-        p += 8;
+constexpr size_t kProofMaxSegments = 6;  // a lookup proof's; no proof has more challenges than segments
+
+// One proof format: everything the statement, the layout and the shape rules depend on.  shape_ok (or size_ok and lay_out, for a
+// caller that has rho and no exponents) comes before anything that reads seg, nseg or len
+struct ProofSpec {
+    ProofKind kind;
+    size_t n, t;
+    unsigned log_ext;
+    size_t n_public;
+    size_t g = 0;  // the custom kinds: g terms, their g x t exponents, a next-row proof's second matrix
+    const uint8_t *exps = nullptr, *exps_next = nullptr;
+    size_t c = 0;    // the lookup kind: the table's columns
+    size_t rho = 0;  // a next-row proof's wires with a next-row exponent (shape_ok counts them)
+    ProofSegment seg[kProofMaxSegments] = {};
+    size_t nseg = 0, len = 0;
+
+    bool lookup() const { return kind == kProofLookup; }
+    bool custom() const { return kind == kProofCustom || kind == kProofNext; }
+    size_t nkey() const { return lookup() ? 2 * t + c + 3 : 2 * t + 2 + g; }
+    size_t nevals() const { return lookup() ? 2 * t + c + 2 : 2 * t + rho; }
+    size_t evals_off() const { return seg[nseg - 2].off; }
+    size_t w_off() const { return seg[nseg - 1].off; }
+    size_t npoints() const { return evals_off() / 48; }  // the points in front of the evaluations, at 48 i
+
+    void lay_out() {
+        const size_t e = (size_t)1 << log_ext;
+        len = nseg = 0;
+        auto add = [&](size_t bytes, size_t draws) {
+            seg[nseg++] = ProofSegment{len, bytes, draws};
+            len += bytes;
+        };
+        add(48 * t, lookup() ? 1 : 2);    // the wires, then theta, or beta and gamma
+        if (lookup()) add(48, 2);         // [m], then beta and gamma
+        add(lookup() ? 96 : 48, 1);       // [z] (and [phi]), then alpha
+        add(48 * (e - 1), 1);             // T's chunks, then zeta
+        add(32 * nevals(), 1);            // the evaluations, then v
+        add(48, 0);                       // W
     }
-    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
-    std::memcpy(p, exps, g * t);
-    p += g * t;
-    if (exps_next) {
-        std::memcpy(p, exps_next, g * t);
-        p += g * t;
+    // the rules a proof's size depends on: t, log_ext and c or rho
+    bool size_ok() const {
+        if (t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt) return false;
+        const size_t e = (size_t)1 << log_ext;
+        if (lookup()) return lookup_shape_ok(t, e, c);
+        return t + 1 <= e && (kind != kProofNext || (rho >= 1 && rho <= t));
     }
-    for (size_t j = 0; j < nkey; j++, p += 48) {
-        hf::P1 k;
-        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
-        hf::p1_compress(p, k);
+    // the rules of every kind: n, t, log_ext and n_public as kzg_circuit_verify_proof takes them
+    bool base_ok() const {
+        PqShape sh;
+        return log_ext <= kPqMaxLogExt && pq_shape(n, (size_t)1 << log_ext, &sh) && t >= KZG_CIRCUIT_MIN_COLUMNS && t <= kPqMaxColumns &&
+               t + 1 <= sh.rot && n_public <= n;
     }
-    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
-    hf::Sha256 s;
-    hf::sha256_init(s);
-    hf::sha256_update(s, m.data(), m.size());
-    hf::sha256_final(s, state);
-}
-// the five challenges from complete proof bytes, out: beta, gamma, alpha, zeta, v.  exps null: the plain statement, else the custom
-// circuit's with its g terms; exps_next too: the next-row circuit's, whose proof has rho more scalars, all absorbed before v
-void proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const hf::Fr* shifts, const hf::Fr* pub, size_t n_public,
-                      const uint8_t* proof, hf::Fr out[5], size_t g = 0, const uint8_t* exps = nullptr, const uint8_t* exps_next = nullptr,
-                      size_t rho = 0) {
-    const ProofLayout L = proof_layout(t, (size_t)1 << log_ext, rho);
+    // ... and the kind's own; counts rho and lays the proof out
+    bool shape_ok() {
+        if (!base_ok()) return false;
+        const size_t e = (size_t)1 << log_ext;
+        if (kind == kProofCustom && !custom_shape_ok(t, e, g, exps, nullptr)) return false;
+        if (kind == kProofNext) rho = next_shape_rho(n, t, e, g, exps, exps_next, nullptr, nullptr);
+        if (!size_ok()) return false;
+        lay_out();
+        return true;
+    }
+
+    // The statement in two halves.  The first: everything in front of the public inputs, into a fresh state (shifts: blst_fr images
+    // below r)
+    void statement_prefix(hf::Sha256& s, const uint64_t* key_p1s, const uint64_t* shifts) const {
+        static const char* const kDst[] = {kProofDst, kCustomProofDst, kNextProofDst, kLookupProofDst};  // by ProofKind
+        const char* dst = kDst[kind];
+        uint8_t b[48];
+        hf::sha256_init(s);
+        hf::sha256_update(s, (const uint8_t*)dst, std::strlen(dst));
+        const uint64_t header[5] = {n, t, log_ext, lookup() ? c : g, n_public};
+        for (size_t i = 0; i < 5; i++) {
+            if (i == 3 && kind == kProofPlain) continue;  // four words: neither g nor c
+            for (int k = 0; k < 8; k++) b[k] = (uint8_t)(header[i] >> (8 * (7 - k)));
+            hf::sha256_update(s, b, 8);
+        }
+        for (size_t j = 0; j < t; j++) {
+            proof_fr_to_be(pq_fr(shifts + 4 * j), b);
+            hf::sha256_update(s, b, 32);
+        }
+        if (custom()) hf::sha256_update(s, exps, g * t);
+        if (kind == kProofNext) hf::sha256_update(s, exps_next, g * t);
+        for (size_t j = 0; j < nkey(); j++) {
+            hf::P1 k;
+            std::memcpy(&k, key_p1s + 18 * j, sizeof k);
+            hf::p1_compress(b, k);
+            hf::sha256_update(s, b, 48);
+        }
+    }
+    // The second: the public inputs (blst_fr images below r) in one pass, through a block on the stack; h0.  The state is spent
+    void statement_finish(hf::Sha256& s, const uint64_t* public_inputs, uint8_t h0[32]) const {
+        uint8_t b[32 * 128];
+        for (size_t i = 0; i < n_public; i += 128) {
+            const size_t m = n_public - i < 128 ? n_public - i : 128;
+            for (size_t k = 0; k < m; k++) proof_fr_to_be(pq_fr(public_inputs + 4 * (i + k)), b + 32 * k);
+            hf::sha256_update(s, b, 32 * m);
+        }
+        hf::sha256_final(s, h0);
+    }
+};
+
+// The walk over a proof's rounds: h holds h_i; round() absorbs segment i and draws its challenges behind those drawn so far, so ch
+// fills in the order the *_proof_challenges calls give them: (theta,) beta, gamma, alpha, zeta, v.  The prover calls round() as each
+// segment of its proof becomes known, run() takes complete bytes
+struct ProofWalk {
     uint8_t h[32];
-    if (exps) custom_proof_statement(h, key_p1s, n, t, log_ext, g, exps, shifts, pub, n_public, exps_next);
-    else proof_statement(h, key_p1s, n, t, log_ext, shifts, pub, n_public);
-    proof_absorb(h, proof + L.wires, L.z - L.wires);
-    out[0] = proof_challenge(h, 0);
-    out[1] = proof_challenge(h, 1);
-    proof_absorb(h, proof + L.z, 48);
-    out[2] = proof_challenge(h, 0);
-    proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
-    out[3] = proof_challenge(h, 0);
-    proof_absorb(h, proof + L.evals, L.w - L.evals);
-    out[4] = proof_challenge(h, 0);
-}
-// the shifts and the public inputs as field elements; false when one is not below r
-bool proof_scalars(const uint64_t* shifts, size_t t, const uint64_t* public_inputs, size_t n_public, std::vector<hf::Fr>* ks,
-                   std::vector<hf::Fr>* pub) {
-    ks->resize(t);
-    pub->resize(n_public);
+    size_t next = 0, drawn = 0;
+    hf::Fr ch[kProofMaxSegments];
+    void round(const ProofSpec& sp, const uint8_t* proof) {
+        const ProofSegment& sg = sp.seg[next++];
+        proof_absorb(h, proof + sg.off, sg.len);
+        for (size_t d = 0; d < sg.draws; d++) ch[drawn++] = proof_challenge(h, (uint8_t)d);
+    }
+    // stmt: the statement's prefix absorbed (a copy: a batch shares one); every segment in front of W
+    void run(const ProofSpec& sp, hf::Sha256 stmt, const uint64_t* public_inputs, const uint8_t* proof) {
+        sp.statement_finish(stmt, public_inputs, h);
+        while (next + 1 < sp.nseg) round(sp, proof);
+    }
+};
+// the shifts and the public inputs are blst_fr images below r
+static bool proof_scalars_ok(const uint64_t* shifts, size_t t, const uint64_t* public_inputs, size_t n_public) {
+    hf::Fr v;
     for (size_t j = 0; j < t; j++)
-        if (!fr_arg_below_r(shifts + 4 * j, &(*ks)[j])) return false;
+        if (!fr_arg_below_r(shifts + 4 * j, &v)) return false;
     for (size_t i = 0; i < n_public; i++)
-        if (!fr_arg_below_r(public_inputs + 4 * i, &(*pub)[i])) return false;
+        if (!fr_arg_below_r(public_inputs + 4 * i, &v)) return false;
     return true;
 }
-}  // namespace
-
-int kzg_circuit_proof_size(size_t t, unsigned log_ext, size_t* bytes) {
-    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext))
-        return KZG_ERR_INVALID_ARG;
-    *bytes = proof_layout(t, (size_t)1 << log_ext).len;
+// What every host call on proof bytes refuses with KZG_ERR_INVALID_ARG: a null argument, a shape that is not the kind's, a proof_len
+// that is not the format's, a shift or a public input not below r.  Lays sp out
+static bool proof_call_ok(ProofSpec& sp, const uint64_t* key_p1s, const uint64_t* shifts, const uint64_t* public_inputs,
+                          const uint8_t* proof, size_t proof_len) {
+    if (!key_p1s || !shifts || (!public_inputs && sp.n_public) || !proof) return false;
+    if ((sp.custom() && !sp.exps) || (sp.kind == kProofNext && !sp.exps_next)) return false;
+    return sp.shape_ok() && proof_len == sp.len && proof_scalars_ok(shifts, sp.t, public_inputs, sp.n_public);
+}
+// the *_proof_size calls (sp: t, log_ext and c or rho)
+static int proof_size_impl(ProofSpec sp, size_t* bytes) {
+    if (!bytes || !sp.size_ok()) return KZG_ERR_INVALID_ARG;
+    sp.lay_out();
+    *bytes = sp.len;
     return KZG_OK;
 }
-
-int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
-                                 const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, uint64_t* out) {
-    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
-    if (!proof_shape_ok(n, t, log_ext, n_public) || proof_len != proof_layout(t, (size_t)1 << log_ext).len) return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch);
-    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
+// the *_proof_challenges calls: out receives 4 u64 a challenge, in ProofWalk's order
+static int proof_challenges_impl(ProofSpec sp, const uint64_t* key_p1s, const uint64_t* shifts, const uint64_t* public_inputs,
+                                 const uint8_t* proof, size_t proof_len, uint64_t* out) {
+    if (!out || !proof_call_ok(sp, key_p1s, shifts, public_inputs, proof, proof_len)) return KZG_ERR_INVALID_ARG;
+    hf::Sha256 stmt;
+    sp.statement_prefix(stmt, key_p1s, shifts);
+    ProofWalk w;
+    w.run(sp, stmt, public_inputs, proof);
+    for (size_t i = 0; i < w.drawn; i++) std::memcpy(out + 4 * i, w.ch[i].l, 32);
     return KZG_OK;
 }
-
-namespace {
-// kzg_circuit_verify_proof (exps null) and kzg_circuit_custom_verify_proof: the same bytes under the one statement or the other;
-// kzg_circuit_custom_next_verify_proof (exps_next too): rho more scalars under the third
-int verify_proof_impl(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exps, const uint64_t* shifts,
-                      const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
-                      size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid,
-                      const uint8_t* exps_next = nullptr) {
-    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
-    if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
-    const size_t e = (size_t)1 << log_ext;
-    if (exps && !exps_next && !custom_shape_ok(t, e, g, exps, nullptr)) return KZG_ERR_INVALID_ARG;
-    const size_t rho = exps_next ? next_shape_rho(n, t, e, g, exps, exps_next, nullptr, nullptr) : 0;
-    if (exps_next && !rho) return KZG_ERR_INVALID_ARG;
-    const ProofLayout L = proof_layout(t, e, rho);
-    if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    for (size_t j = 0; j < 2 * t + 2 + g; j++) {  // kzg_circuit_verify's check of the key, before the proof is looked at
-        hf::P1 c;
-        std::memcpy(&c, key_p1s + 18 * j, sizeof c);
-        if (!hf::p1_on_curve(c)) return KZG_ERR_INVALID_ARG;
+// the *_verify_proof calls: the checks, the key's commitments on the curve before the proof is looked at (kzg_circuit_verify's
+// check), the proof's points (on the curve; no subgroup check) and canonical scalars -- a proof that does not decode is invalid, not
+// an error -- the challenges, and the kind's claim to circuit_verify_impl
+int verify_proof_impl(ProofSpec sp, const uint64_t* key_p1s, const uint64_t* shifts, const uint64_t* public_inputs, const uint8_t* proof,
+                      size_t proof_len, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                      int* valid) {
+    if (!setup_g1 || !setup_g2 || !valid || !proof_call_ok(sp, key_p1s, shifts, public_inputs, proof, proof_len)) return KZG_ERR_INVALID_ARG;
+    for (size_t j = 0; j < sp.nkey(); j++) {
+        hf::P1 k;
+        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
+        if (!hf::p1_on_curve(k)) return KZG_ERR_INVALID_ARG;
     }
-    // decode: t + e + 1 points (on the curve; no subgroup check) and 2 t canonical scalars; a proof that does not decode is invalid
-    // (a next-row proof: 2 t + rho scalars)
-    std::vector<uint64_t> pts(18 * (t + e)), evals(4 * (2 * t + rho));
+    const size_t t = sp.t, npts = sp.npoints(), nlk = sp.lookup() ? 1 : 0;
+    std::vector<uint64_t> pts(18 * npts), evals(4 * sp.nevals());
     uint64_t w_p1[18];
     bool decoded = true;
-    for (size_t i = 0; i < t + e && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
-    decoded = decoded && kzg_g1_uncompress(proof + L.w, w_p1) == KZG_OK;
-    for (size_t i = 0; i < 2 * t + rho && decoded; i++) {
+    for (size_t i = 0; i < npts && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
+    decoded = decoded && kzg_g1_uncompress(proof + sp.w_off(), w_p1) == KZG_OK;
+    for (size_t i = 0; i < sp.nevals() && decoded; i++) {
         hf::Fr v = kFrZero;
-        decoded = proof_fr_from_be(proof + L.evals + 32 * i, &v);
+        decoded = proof_fr_from_be(proof + sp.evals_off() + 32 * i, &v);
         std::memcpy(evals.data() + 4 * i, v.l, 32);
     }
     if (!decoded) {
         *valid = 0;
         return KZG_OK;
     }
-    hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exps, exps_next, rho);
-    const CustomClaim claim{g, exps, exps_next, exps_next ? evals.data() + 4 * 2 * t : nullptr};
-    return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * t, pts.data() + 18 * (t + 1), public_inputs,
-                               n_public, evals.data(), ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2,
-                               g2_stride_bytes, valid, nullptr, exps ? &claim : nullptr);
+    hf::Sha256 stmt;
+    sp.statement_prefix(stmt, key_p1s, shifts);
+    ProofWalk w;
+    w.run(sp, stmt, public_inputs, proof);
+    // the points: wires, ([m],) [z], ([phi],) chunks; the challenges behind a lookup proof's theta: beta, gamma, alpha, zeta, v
+    const uint64_t *z_p1 = pts.data() + 18 * (t + nlk), *t_p1s = pts.data() + 18 * (t + 1 + 2 * nlk);
+    const hf::Fr* ch = w.ch + nlk;
+    const LookupClaim lookup{sp.c, w.ch[0].l, pts.data() + 18 * t, pts.data() + 18 * (t + 2)};
+    const CustomClaim custom{sp.g, sp.exps, sp.exps_next, sp.kind == kProofNext ? evals.data() + 4 * 2 * t : nullptr};
+    return circuit_verify_impl(key_p1s, sp.n, t, sp.log_ext, shifts, pts.data(), z_p1, t_p1s, public_inputs, sp.n_public, evals.data(),
+                               ch[2].l, ch[0].l, ch[1].l, ch[3].l, ch[4].l, w_p1, setup_g1, g1_stride_bytes, setup_g2, g2_stride_bytes, valid,
+                               nlk ? &lookup : nullptr, sp.custom() ? &custom : nullptr);
 }
 }  // namespace
+
+int kzg_circuit_proof_size(size_t t, unsigned log_ext, size_t* bytes) {
+    return proof_size_impl(ProofSpec{kProofPlain, 0, t, log_ext, 0}, bytes);
+}
+
+int kzg_circuit_custom_next_proof_size(size_t t, unsigned log_ext, size_t rho, size_t* bytes) {
+    ProofSpec sp{kProofNext, 0, t, log_ext, 0};
+    sp.rho = rho;
+    return proof_size_impl(sp, bytes);
+}
+
+int kzg_circuit_lookup_proof_size(size_t t, unsigned log_ext, size_t c, size_t* bytes) {
+    return proof_size_impl(ProofSpec{kProofLookup, 0, t, log_ext, 0, 0, nullptr, nullptr, c}, bytes);
+}
+
+int kzg_circuit_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
+                                 const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, uint64_t* out) {
+    return proof_challenges_impl(ProofSpec{kProofPlain, n, t, log_ext, n_public}, key_p1s, shifts, public_inputs, proof, proof_len, out);
+}
+
+int kzg_circuit_custom_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                        const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
+                                        size_t proof_len, uint64_t* out) {
+    return proof_challenges_impl(ProofSpec{kProofCustom, n, t, log_ext, n_public, g, exponents}, key_p1s, shifts, public_inputs, proof,
+                                 proof_len, out);
+}
+
+int kzg_circuit_custom_next_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
+                                             const uint8_t* exponents, const uint8_t* exponents_next, const uint64_t* shifts,
+                                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                             uint64_t* out) {
+    return proof_challenges_impl(ProofSpec{kProofNext, n, t, log_ext, n_public, g, exponents, exponents_next}, key_p1s, shifts,
+                                 public_inputs, proof, proof_len, out);
+}
+
+int kzg_circuit_lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
+                                        const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                        uint64_t* out) {
+    return proof_challenges_impl(ProofSpec{kProofLookup, n, t, log_ext, n_public, 0, nullptr, nullptr, c}, key_p1s, shifts, public_inputs,
+                                 proof, proof_len, out);
+}
 
 int kzg_circuit_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, const uint64_t* shifts,
                              const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
                              size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
-    return verify_proof_impl(key_p1s, n, t, log_ext, 0, nullptr, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
+    return verify_proof_impl(ProofSpec{kProofPlain, n, t, log_ext, n_public}, key_p1s, shifts, public_inputs, proof, proof_len, setup_g1,
                              g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
-}
-
-// ---- a custom circuit's proof as bytes (host only): the plain format under custom_proof_statement ----------
-int kzg_circuit_custom_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
-                                        const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
-                                        size_t proof_len, uint64_t* out) {
-    if (!key_p1s || !exponents || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
-    if (!proof_shape_ok(n, t, log_ext, n_public) || !custom_shape_ok(t, (size_t)1 << log_ext, g, exponents, nullptr) ||
-        proof_len != proof_layout(t, (size_t)1 << log_ext).len)
-        return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exponents);
-    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
-    return KZG_OK;
 }
 
 int kzg_circuit_custom_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
                                     const uint64_t* shifts, const uint64_t* public_inputs, size_t n_public, const uint8_t* proof,
                                     size_t proof_len, const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2,
                                     size_t g2_stride_bytes, int* valid) {
-    if (!exponents) return KZG_ERR_INVALID_ARG;
-    return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
-                             g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+    return verify_proof_impl(ProofSpec{kProofCustom, n, t, log_ext, n_public, g, exponents}, key_p1s, shifts, public_inputs, proof,
+                             proof_len, setup_g1, g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+}
+
+int kzg_circuit_custom_next_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
+                                         const uint8_t* exponents_next, const uint64_t* shifts, const uint64_t* public_inputs,
+                                         size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
+                                         size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    return verify_proof_impl(ProofSpec{kProofNext, n, t, log_ext, n_public, g, exponents, exponents_next}, key_p1s, shifts, public_inputs,
+                             proof, proof_len, setup_g1, g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
+}
+
+int kzg_circuit_lookup_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
+                                    const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
+                                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
+                                    int* valid) {
+    return verify_proof_impl(ProofSpec{kProofLookup, n, t, log_ext, n_public, 0, nullptr, nullptr, c}, key_p1s, shifts, public_inputs,
+                             proof, proof_len, setup_g1, g1_stride_bytes, setup_g2, g2_stride_bytes, valid);
 }
 
 // ---- many proofs of one key with one pairing check (circuit_verify_kernels.hip) ----------------------------
@@ -9559,23 +9630,22 @@ int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, s
     if (!key_p1s || !shifts || (!public_inputs && n_public && count) || (!proofs && count) || !setup_g2 || !valid ||
         (want_weights && (!out_p1s || (!weights && count))) || (g && !exps))
         return invalid("a required pointer is NULL");
-    if (!proof_shape_ok(n, t, log_ext, n_public)) return invalid("n, t, log_ext or n_public is not a shape of kzg_circuit_verify_proof");
+    ProofSpec sp{exps ? kProofCustom : kProofPlain, n, t, log_ext, n_public, g, exps};
+    if (!sp.base_ok()) return invalid("n, t, log_ext or n_public is not a shape of kzg_circuit_verify_proof");
+    if (!sp.shape_ok()) return invalid("g or the exponents are not a shape of the custom verifier");
     const size_t e = (size_t)1 << log_ext;
-    if (exps && !custom_shape_ok(t, e, g, exps, nullptr)) return invalid("g or the exponents are not a shape of the custom verifier");
-    const ProofLayout L = proof_layout(t, e);
-    if (proof_len != L.len) return invalid("proof_len is not kzg_circuit_proof_size's");
+    if (proof_len != sp.len) return invalid("proof_len is not kzg_circuit_proof_size's");
     if (count > KZG_VERIFY_MAX_PROOFS) return invalid("more than KZG_VERIFY_MAX_PROOFS proofs");
     if (n < 2) return invalid("n < 2: the two point sets of a proof coincide");
     if (pi_stride < n_public && count > 1) return invalid("pi_stride is below n_public");
-    std::vector<hf::Fr> ks, none;
-    if (!proof_scalars(shifts, t, nullptr, 0, &ks, &none)) return invalid("a shift is not below r");
+    if (!proof_scalars_ok(shifts, t, nullptr, 0)) return invalid("a shift is not below r");
     for (size_t k = 0; k < count; k++)  // validated here, converted again by the thread that hashes proof k: nothing of size count is kept
         for (size_t i = 0; i < n_public; i++) {
             hf::Fr v;
             if (!fr_arg_below_r(public_inputs + 4 * (k * pi_stride + i), &v))
                 return invalid("proof " + std::to_string(k) + ": public input " + std::to_string(i) + " is not below r");
         }
-    const size_t nkey = 2 * t + 2 + g, nk = nkey + 1;  // the key's commitments, then G1
+    const size_t nkey = sp.nkey(), nk = nkey + 1;  // the key's commitments, then G1
     for (size_t j = 0; j < nkey; j++) {
         hf::P1 c;
         std::memcpy(&c, key_p1s + 18 * j, sizeof c);
@@ -9626,47 +9696,16 @@ int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, s
     }
     // the statement's bytes in front of the public inputs, hashed once
     hf::Sha256 stmt;
-    {
-        std::vector<uint8_t> m((exps ? kCustomDstLen + 40 + g * t : 19 + 32) + 32 * t + 48 * nkey);
-        uint8_t* p = m.data();
-        if (exps) {
-            std::memcpy(p, kCustomProofDst, kCustomDstLen);
-            p += kCustomDstLen;
-            for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)g, (uint64_t)n_public}) {
-                proof_u64be(p, x);
-                p += 8;
-            }
-        } else {
-            std::memcpy(p, kProofDst, 19);
-            p += 19;
-            for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)n_public}) {
-                proof_u64be(p, x);
-                p += 8;
-            }
-        }
-        for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(ks[j], p);
-        if (exps) {
-            std::memcpy(p, exps, g * t);
-            p += g * t;
-        }
-        for (size_t j = 0; j < nkey; j++, p += 48) {
-            hf::P1 c;
-            std::memcpy(&c, key_p1s + 18 * j, sizeof c);
-            hf::p1_compress(p, c);
-        }
-        hf::sha256_init(stmt);
-        hf::sha256_update(stmt, m.data(), m.size());
-    }
+    sp.statement_prefix(stmt, key_p1s, shifts);
     // lanes of the one ladder launch: [the R - 1 points of A_0 per proof | W per proof | the key's nk points with their scalars of P0 |
     // the same with those of P1 | [z] per proof, a second time].  Affine records: the key's nk in front, so that the least failing
     // index names a key commitment (an error) before any proof (a verdict), then the proofs' NP
     const size_t NP = M * R, lanes = M * (R + 1) + 2 * nk, oF = M * (R - 1), oK = oF + M, oE = oK + 2 * nk;
-    // the host's part: the five challenges of every proof (the SHA-256 chain from h0 on, proof_challenges'), as blst_fr images
+    // the host's part: the five challenges of every proof (ProofWalk over each proof's bytes), as blst_fr images
     std::vector<uint64_t> chal(20 * M);
     std::vector<uint32_t> src(lanes);
     size_t nthreads = std::min<size_t>({(size_t)16, std::max<size_t>(1, std::thread::hardware_concurrency()), M});
     auto work = [&](size_t th) {
-        std::vector<uint8_t> pub_be(32 * n_public);
         for (size_t k = th; k < M; k += nthreads) {
             const uint8_t* proof = proofs + k * proof_len;
             for (size_t i = 0; i + 1 < R; i++) src[k * (R - 1) + i] = (uint32_t)(nk + k * R + i);
@@ -9676,27 +9715,10 @@ int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, s
                 std::memcpy(&chal[20 * k], challenges + 20 * k, 160);
                 continue;
             }
-            for (size_t i = 0; i < n_public; i++) {
-                hf::Fr v;
-                fr_arg_below_r(public_inputs + 4 * (k * pi_stride + i), &v);
-                proof_fr_to_be(v, &pub_be[32 * i]);
-            }
-            hf::Sha256 s = stmt;
-            uint8_t h[32];
-            hf::sha256_update(s, pub_be.data(), pub_be.size());
-            hf::sha256_final(s, h);
-            hf::Fr ch[5];
-            proof_absorb(h, proof + L.wires, L.z - L.wires);
-            ch[0] = proof_challenge(h, 0);
-            ch[1] = proof_challenge(h, 1);
-            proof_absorb(h, proof + L.z, 48);
-            ch[2] = proof_challenge(h, 0);
-            proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
-            ch[3] = proof_challenge(h, 0);
-            proof_absorb(h, proof + L.evals, L.w - L.evals);
-            ch[4] = proof_challenge(h, 0);
+            ProofWalk w;  // from a copy of the prefix's state
+            w.run(sp, stmt, n_public ? public_inputs + 4 * k * pi_stride : nullptr, proof);
             // the kernels' order: beta, gamma, alpha, zeta, v
-            for (int i = 0; i < 5; i++) std::memcpy(&chal[20 * k + 4 * i], ch[i].l, 32);
+            for (int i = 0; i < 5; i++) std::memcpy(&chal[20 * k + 4 * i], w.ch[i].l, 32);
         }
     };
     if (nthreads <= 1) {
@@ -9717,7 +9739,7 @@ int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, s
         consts[kCvbW1] = fr30_arg_from_mont256(hf::fr_add(w, hf::kFrOne));
         consts[kCvbInvN] = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
         consts[kCvbW64] = fr30_arg_from_mont256(hf::fr_pow(w, 64));
-        for (size_t j = 0; j < t; j++) consts[kCvbShifts + j] = fr30_arg_from_mont256(ks[j]);
+        for (size_t j = 0; j < t; j++) consts[kCvbShifts + j] = fr30_arg_from_mont256(pq_fr(shifts + 4 * j));
     }
     // XYZZ records, laid out so that every side is a run of consecutive records:
     //   [the ladder's products of A_0: M (R - 1) | F: M | P0's terms: 3 M | the key's for P0: nk | the key's for P1: nk | E: M | D: M |
@@ -9790,8 +9812,8 @@ int circuit_verify_batch_impl(kzg_ctx* ctx, const uint64_t* key_p1s, size_t n, s
     // the proofs' bytes as received: the points (the wires, [z] and the chunks, then W) and the evaluations, each field of a proof
     // to its place by a strided copy
     HIP_TRY(ctx, hipMemcpy2DAsync(wire, 48 * R, proofs, proof_len, 48 * (R - 1), M, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpy2DAsync((char*)wire + 48 * (R - 1), 48 * R, proofs + L.w, proof_len, 48, M, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpy2DAsync(fr_at(fEvB), 64 * t, proofs + L.evals, proof_len, 64 * t, M, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpy2DAsync((char*)wire + 48 * (R - 1), 48 * R, proofs + sp.w_off(), proof_len, 48, M, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpy2DAsync(fr_at(fEvB), 64 * t, proofs + sp.evals_off(), proof_len, 64 * t, M, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(fr_at(fCh), chal.data(), M * 160, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(fr_at(fRho), rho.data(), M * 32, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(fr_at(fCo), consts.data(), consts.size() * sizeof(Fr30), hipMemcpyHostToDevice, st));
@@ -9923,216 +9945,69 @@ int kzg_circuit_verify_proofs_lincomb(kzg_ctx* ctx, const uint64_t* key_p1s, siz
     }
 }
 
-// ---- a next-row circuit's proof as bytes (host only): rho more scalars under a statement of its own --------
-int kzg_circuit_custom_next_proof_size(size_t t, unsigned log_ext, size_t rho, size_t* bytes) {
-    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt || t + 1 > ((size_t)1 << log_ext) || rho < 1 ||
-        rho > t)
-        return KZG_ERR_INVALID_ARG;
-    *bytes = proof_layout(t, (size_t)1 << log_ext, rho).len;
-    return KZG_OK;
-}
-
-int kzg_circuit_custom_next_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g,
-                                             const uint8_t* exponents, const uint8_t* exponents_next, const uint64_t* shifts,
-                                             const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
-                                             uint64_t* out) {
-    if (!key_p1s || !exponents || !exponents_next || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
-    if (!proof_shape_ok(n, t, log_ext, n_public)) return KZG_ERR_INVALID_ARG;
-    const size_t rho = next_shape_rho(n, t, (size_t)1 << log_ext, g, exponents, exponents_next, nullptr, nullptr);
-    if (!rho || proof_len != proof_layout(t, (size_t)1 << log_ext, rho).len) return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    hf::Fr ch[5];
-    proof_challenges(key_p1s, n, t, log_ext, ks.data(), pub.data(), n_public, proof, ch, g, exponents, exponents_next, rho);
-    for (int i = 0; i < 5; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
-    return KZG_OK;
-}
-
-int kzg_circuit_custom_next_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t g, const uint8_t* exponents,
-                                         const uint8_t* exponents_next, const uint64_t* shifts, const uint64_t* public_inputs,
-                                         size_t n_public, const uint8_t* proof, size_t proof_len, const void* setup_g1,
-                                         size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
-    if (!exponents || !exponents_next) return KZG_ERR_INVALID_ARG;
-    return verify_proof_impl(key_p1s, n, t, log_ext, g, exponents, shifts, public_inputs, n_public, proof, proof_len, setup_g1,
-                             g1_stride_bytes, setup_g2, g2_stride_bytes, valid, exponents_next);
-}
-
-// ---- a lookup circuit's proof as bytes (host only) -------------------------------------------------------
-// The transcript of section 4.25 with a domain of its own, c in the statement and two more rounds:
-//   h0 = SHA256(DST | u64be(n) | u64be(t) | u64be(log_ext) | u64be(c) | u64be(n_public) | shifts | the 2 t + c + 3 key commitments
-//               | public inputs)
-//   h1 = SHA256(h0 | wire commitments)     theta = fr(SHA256(h1 | 00))
-//   h2 = SHA256(h1 | [m])                  beta = fr(SHA256(h2 | 00)), gamma = fr(SHA256(h2 | 01))
-//   h3 = SHA256(h2 | [z] | [phi])          alpha = fr(SHA256(h3 | 00))
-//   h4 = SHA256(h3 | [T_0] .. [T_(e-2)])   zeta = fr(SHA256(h4 | 00))
-//   h5 = SHA256(h4 | evaluations)          v = fr(SHA256(h5 | 00))
-namespace {
-constexpr char kLookupProofDst[] = "kzg_mi355x/plonk-lookup/v1";  // 26 bytes, hashed without the terminator
-constexpr size_t kLookupDstLen = sizeof kLookupProofDst - 1;
-void lookup_proof_statement(uint8_t state[32], const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c,
-                            const hf::Fr* shifts, const hf::Fr* pub, size_t n_public) {
-    const size_t nkey = 2 * t + c + 3;
-    std::vector<uint8_t> m(kLookupDstLen + 40 + 32 * t + 48 * nkey + 32 * n_public);
-    uint8_t* p = m.data();
-    std::memcpy(p, kLookupProofDst, kLookupDstLen);
-    p += kLookupDstLen;
-    for (uint64_t x : {(uint64_t)n, (uint64_t)t, (uint64_t)log_ext, (uint64_t)c, (uint64_t)n_public}) {
-        proof_u64be(p, x);
-        p += 8;
-    }
-    for (size_t j = 0; j < t; j++, p += 32) proof_fr_to_be(shifts[j], p);
-    for (size_t j = 0; j < nkey; j++, p += 48) {
-        hf::P1 k;
-        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
-        hf::p1_compress(p, k);
-    }
-    for (size_t i = 0; i < n_public; i++, p += 32) proof_fr_to_be(pub[i], p);
-    hf::Sha256 s;
-    hf::sha256_init(s);
-    hf::sha256_update(s, m.data(), m.size());
-    hf::sha256_final(s, state);
-}
-// the offsets of the proof's seven fields: wires, [m], [z], [phi], chunks, evaluations, W, and its length
-struct LookupProofLayout {
-    size_t wires, m, z, phi, chunks, evals, w, len, nevals;
-};
-LookupProofLayout lookup_proof_layout(size_t t, size_t e, size_t c) {
-    LookupProofLayout L;
-    L.wires = 0;
-    L.m = 48 * t;
-    L.z = L.m + 48;
-    L.phi = L.z + 48;
-    L.chunks = L.phi + 48;
-    L.evals = L.chunks + 48 * (e - 1);
-    L.nevals = 2 * t + c + 2;
-    L.w = L.evals + 32 * L.nevals;
-    L.len = L.w + 48;
-    return L;
-}
-bool lookup_proof_shape_ok(size_t n, size_t t, unsigned log_ext, size_t c, size_t n_public) {
-    return proof_shape_ok(n, t, log_ext, n_public) && lookup_shape_ok(t, (size_t)1 << log_ext, c);
-}
-// the six challenges from complete proof bytes, out: theta, beta, gamma, alpha, zeta, v
-void lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const hf::Fr* shifts,
-                             const hf::Fr* pub, size_t n_public, const uint8_t* proof, hf::Fr out[6]) {
-    const LookupProofLayout L = lookup_proof_layout(t, (size_t)1 << log_ext, c);
-    uint8_t h[32];
-    lookup_proof_statement(h, key_p1s, n, t, log_ext, c, shifts, pub, n_public);
-    proof_absorb(h, proof + L.wires, L.m - L.wires);
-    out[0] = proof_challenge(h, 0);
-    proof_absorb(h, proof + L.m, 48);
-    out[1] = proof_challenge(h, 0);
-    out[2] = proof_challenge(h, 1);
-    proof_absorb(h, proof + L.z, 96);
-    out[3] = proof_challenge(h, 0);
-    proof_absorb(h, proof + L.chunks, L.evals - L.chunks);
-    out[4] = proof_challenge(h, 0);
-    proof_absorb(h, proof + L.evals, L.w - L.evals);
-    out[5] = proof_challenge(h, 0);
-}
-}  // namespace
-
-int kzg_circuit_lookup_proof_size(size_t t, unsigned log_ext, size_t c, size_t* bytes) {
-    if (!bytes || t < KZG_CIRCUIT_MIN_COLUMNS || t > kPqMaxColumns || log_ext > kPqMaxLogExt ||
-        !lookup_shape_ok(t, (size_t)1 << log_ext, c))
-        return KZG_ERR_INVALID_ARG;
-    *bytes = lookup_proof_layout(t, (size_t)1 << log_ext, c).len;
-    return KZG_OK;
-}
-
-int kzg_circuit_lookup_proof_challenges(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
-                                        const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
-                                        uint64_t* out) {
-    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !out) return KZG_ERR_INVALID_ARG;
-    if (!lookup_proof_shape_ok(n, t, log_ext, c, n_public) || proof_len != lookup_proof_layout(t, (size_t)1 << log_ext, c).len)
-        return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    hf::Fr ch[6];
-    lookup_proof_challenges(key_p1s, n, t, log_ext, c, ks.data(), pub.data(), n_public, proof, ch);
-    for (int i = 0; i < 6; i++) std::memcpy(out + 4 * i, ch[i].l, 32);
-    return KZG_OK;
-}
-
-int kzg_circuit_lookup_verify_proof(const uint64_t* key_p1s, size_t n, size_t t, unsigned log_ext, size_t c, const uint64_t* shifts,
-                                    const uint64_t* public_inputs, size_t n_public, const uint8_t* proof, size_t proof_len,
-                                    const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes,
-                                    int* valid) {
-    if (!key_p1s || !shifts || (!public_inputs && n_public) || !proof || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
-    if (!lookup_proof_shape_ok(n, t, log_ext, c, n_public)) return KZG_ERR_INVALID_ARG;
-    const size_t e = (size_t)1 << log_ext;
-    const LookupProofLayout L = lookup_proof_layout(t, e, c);
-    if (proof_len != L.len) return KZG_ERR_INVALID_ARG;
-    std::vector<hf::Fr> ks, pub;
-    if (!proof_scalars(shifts, t, public_inputs, n_public, &ks, &pub)) return KZG_ERR_INVALID_ARG;
-    for (size_t j = 0; j < 2 * t + c + 3; j++) {  // the key, before the proof is looked at
-        hf::P1 k;
-        std::memcpy(&k, key_p1s + 18 * j, sizeof k);
-        if (!hf::p1_on_curve(k)) return KZG_ERR_INVALID_ARG;
-    }
-    // decode: t + e + 3 points (on the curve; no subgroup check) and 2 t + c + 2 canonical scalars; a proof that does not decode is
-    // invalid
-    const size_t npts = t + e + 2;  // before the evaluations: wires, [m], [z], [phi], chunks
-    std::vector<uint64_t> pts(18 * npts), evals(4 * L.nevals);
-    uint64_t w_p1[18];
-    bool decoded = true;
-    for (size_t i = 0; i < npts && decoded; i++) decoded = kzg_g1_uncompress(proof + 48 * i, pts.data() + 18 * i) == KZG_OK;
-    decoded = decoded && kzg_g1_uncompress(proof + L.w, w_p1) == KZG_OK;
-    for (size_t i = 0; i < L.nevals && decoded; i++) {
-        hf::Fr y = kFrZero;
-        decoded = proof_fr_from_be(proof + L.evals + 32 * i, &y);
-        std::memcpy(evals.data() + 4 * i, y.l, 32);
-    }
-    if (!decoded) {
-        *valid = 0;
-        return KZG_OK;
-    }
-    hf::Fr ch[6];
-    lookup_proof_challenges(key_p1s, n, t, log_ext, c, ks.data(), pub.data(), n_public, proof, ch);
-    const LookupClaim claim{c, ch[0].l, pts.data() + 18 * t, pts.data() + 18 * (t + 2)};
-    return circuit_verify_impl(key_p1s, n, t, log_ext, shifts, pts.data(), pts.data() + 18 * (t + 1), pts.data() + 18 * (t + 3),
-                               public_inputs, n_public, evals.data(), ch[3].l, ch[1].l, ch[2].l, ch[4].l, ch[5].l, w_p1, setup_g1,
-                               g1_stride_bytes, setup_g2, g2_stride_bytes, valid, &claim);
-}
-
-// ---- a circuit's proof in one call ----------------------------------------------------------------------
-// The five rounds under the transcript above, on one slot, quotient_mu held from start to end.  What lives across rounds sits in
+// ---- a circuit's proof in one call (DESIGN.md sections 4.25 to 4.28 and 4.30) ----------------------------------------------------
+// The rounds under the transcript above, on one slot, quotient_mu held from start to end.  What lives across rounds sits in
 // buffers the context keeps for this call alone (ctx->prove_buf, under quotient_mu; the pq_ws workspaces belong to the rounds, which
-// may regrow them), sized for the whole proof at the start: V, the values [ wires | PI | z ];
-// U, their unblinded coefficients in the same order -- every column is transformed back once, here, with launch_ntt_batch, and the
-// quotient's and the opening's bodies read U (ProveRound); the blinded copies that are committed; T's coefficients.
+// may regrow them), sized for the whole proof at the start.  A lookup proof (nlk = 1, section 4.26) has two more rounds and wider
+// buffers; the other kinds' layouts are the lookup's at zero width:
+//   V, the values                               [ wires | PI | z | phi | m | f | T ] (f, T: the folded columns)   [ wires | PI | z ]
+//   U, their unblinded coefficients             [ wires | PI | z | phi | m ]                                      [ wires | PI | z ]
+//   S, the blinded copies that are committed    [ wires (n + 2 each) | m (n + 2) | z | phi (n + 3 each) ]         [ wires | z ]
+//   B, the blinders they are patched with       [ b | u | c | p ]                                                 [ b | c ]
+// Every column is transformed back once, here, with launch_ntt_batch, and the quotient's and the opening's bodies read U (ProveRound),
+// which stays unblinded.  A lookup proof holds lookup_mu (the hash table of the multiplicities) between quotient_mu and the context's
+// mutex.
 namespace {
 int prove_refused(kzg_ctx* ctx, const char* why) {
     ctx->last_error = std::string("circuit prove: ") + why;
     return KZG_ERR_INVALID_ARG;
 }
-// wires: t columns of n values, host (stride in values) or device when `device`
-int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
-                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, bool device,
-                       bool with_custom = false, bool with_next = false) {
+// kind: the format of the proof, which the handle must have been created for.  wires: t columns of n values, host (stride in values)
+// or device when `device`.  blinders (host, or null): section 4.24's array, a lookup proof's section 4.30's.  bad_row (or null): a
+// lookup proof's
+int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, ProofKind kind, const uint64_t* key_p1s, const void* wires, size_t stride,
+                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof, size_t* bad_row,
+                       bool device) {
+    const size_t nlk = kind == kProofLookup ? 1 : 0;
+    const bool with_custom = kind == kProofCustom || kind == kProofNext, with_next = kind == kProofNext;
+    const std::string what = nlk ? "circuit lookup prove" : "circuit prove", what_blinded = what + " (blinded)";
+    // lookup_mu is taken after quotient_mu and given up after the frame has drained the stream (declared first, destroyed last)
+    std::unique_lock<std::mutex> lkl(ctx->lookup_mu, std::defer_lock);
     PqCall call(ctx);
     if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
+    if (nlk && !c->c_tab) return prove_refused(ctx, "the circuit was created without a lookup table");
     if (with_custom && !c->g_custom) return prove_refused(ctx, "the circuit was created without custom gates");
     if (with_custom && with_next != (c->rho != 0)) return custom_kind_refused(ctx, "circuit prove", with_next);
     if (with_next && blinders) return prove_refused(ctx, "next-row proofs are not blinded: a wire opened at two points needs a third blinder");
     const CustomRecord custom_rec = custom_record(c);
     // kzg_circuit_custom_prove (section 4.27) or, with rho more evaluations, kzg_circuit_custom_next_prove (section 4.28)
     const CustomRecord* custom = with_custom ? &custom_rec : nullptr;
-    const size_t rho = custom ? custom->rho : 0;
     PqShape sh;
     if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
-    const size_t n = sh.n, t = c->t, e = sh.rot, ncoef = t + 1 + (n_public ? 1 : 0);
-    std::vector<hf::Fr> ks(t), pub(n_public), bl;
-    for (size_t j = 0; j < t; j++) std::memcpy(ks[j].l, c->shifts + 4 * j, 32);
-    for (size_t i = 0; i < n_public; i++)
-        if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
-    if (blinders) {
-        if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, "circuit prove (blinded)");
-        if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, "circuit prove (blinded)");
-        if (!blind_values_ok(ctx, "circuit prove (blinded)", blinders, blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
+    const size_t n = sh.n, t = c->t, e = sh.rot, lc = nlk ? c->c_tab : 0, ncoef = t + 1 + (n_public ? 1 : 0);
+    for (size_t i = 0; i < n_public; i++) {
+        hf::Fr v;
+        if (!fr_arg_below_r(public_inputs + 4 * i, &v)) return prove_refused(ctx, "a public input is not below r");
     }
+    if (blinders) {
+        std::vector<hf::Fr> bl;
+        if (nlk) {
+            if (!lookup_blind_shape_ok(n, t, e, lc)) return lookup_blind_shape_refused(ctx, what_blinded.c_str());
+        } else {
+            if (!blind_shape_ok(n, t, e)) return blind_shape_refused(ctx, what_blinded.c_str());
+            if (custom && !blind_custom_shape_ok(n, t, e, custom->d_max)) return blind_custom_shape_refused(ctx, what_blinded.c_str());
+        }
+        if (!blind_values_ok(ctx, what_blinded.c_str(), blinders, nlk ? lookup_blind_count(t, e) : blind_count(t, e), &bl))
+            return KZG_ERR_INVALID_ARG;
+    }
+    ProofSpec sp{kind, n, t, c->lg_ext, n_public, custom ? custom->g : 0, custom ? custom->exps : nullptr,
+                 with_next ? custom->exps_next : nullptr, lc};
+    sp.rho = custom ? custom->rho : 0;
+    sp.lay_out();
     const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
     const size_t wlen = blinders ? n + kBlindWireLen : n, zlen = blinders ? n + kBlindZLen : n;
+    const size_t nbw = 2 * t + nlk * kBlindMultLen, nbz = kBlindZLen + nlk * kBlindPhiLen;  // B: [ b | u ], then [ c | p ]
+    if (nlk) lkl.lock();
     call.lock();
     int rc = pq_srs_status(ctx, true, need);
     if (rc == KZG_OK) rc = call.begin();
@@ -10144,14 +10019,20 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
     const int slot = call.slot();
     // every cross-round buffer at its size for the whole proof, before anything is enqueued (the stream is empty: PqCall)
     DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &S = ctx->prove_buf[2], &T = ctx->prove_buf[3], &B = ctx->prove_buf[4];
-    rc = V.reserve(ctx, ncoef * n * 32, s.stream);
-    if (rc == KZG_OK) rc = U.reserve(ctx, ncoef * n * 32, s.stream);
+    rc = V.reserve(ctx, (ncoef + 4 * nlk) * n * 32, s.stream);
+    if (rc == KZG_OK) rc = U.reserve(ctx, (ncoef + 2 * nlk) * n * 32, s.stream);
     if (rc == KZG_OK) rc = T.reserve(ctx, t_len * 32, s.stream);
-    if (rc == KZG_OK && blinders) rc = S.reserve(ctx, (t * wlen + zlen) * 32, s.stream);
-    if (rc == KZG_OK && blinders) rc = B.reserve(ctx, (2 * t + kBlindZLen) * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = S.reserve(ctx, ((t + nlk) * wlen + (1 + nlk) * zlen) * 32, s.stream);
+    if (rc == KZG_OK && blinders) rc = B.reserve(ctx, (nbw + nbz) * 32, s.stream);
+    if (rc == KZG_OK && nlk) rc = s.gp_flags.reserve(ctx, 64);
     if (rc) return rc;
-    uint32_t *d_v = V.dev(), *d_u = U.dev(), *d_s = S.dev(), *d_bl = B.dev();
+    uint32_t *d_v = V.dev(), *d_u = U.dev();
+    uint32_t *d_s = blinders ? S.dev() : nullptr, *d_sm = blinders ? d_s + 8 * t * wlen : nullptr, *d_sz = blinders ? d_sm + 8 * nlk * wlen : nullptr;
+    uint32_t* d_bl = blinders ? B.dev() : nullptr;
     uint32_t *d_vz = d_v + 8 * (ncoef - 1) * n, *d_uz = d_u + 8 * (ncoef - 1) * n;
+    // the lookup's columns behind z (null without one)
+    uint32_t *d_vphi = nlk ? d_vz + 8 * n : nullptr, *d_vm = nlk ? d_vz + 16 * n : nullptr, *d_vf = nlk ? d_vz + 24 * n : nullptr;
+    uint32_t *d_vt = nlk ? d_vz + 32 * n : nullptr, *d_um = nlk ? d_uz + 16 * n : nullptr;
     const ProveRound round_base{&lk, slot, d_u, nullptr};
     const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
     const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
@@ -10167,10 +10048,9 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
         HIP_TRY(ctx, hipGetLastError());
         return KZG_OK;
     };
-    const size_t np1 = t + e;  // the proof's points before the evaluations: wires, [z], chunks
-    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * (2 * t + rho));
-    const ProofLayout L = proof_layout(t, e, rho);
-    std::vector<uint8_t> proof(L.len);
+    const size_t np1 = sp.npoints();  // the proof's points before the evaluations: wires, ([m],) [z], ([phi],) chunks
+    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * sp.nevals());
+    std::vector<uint8_t> proof(sp.len);
     auto put_points = [&](size_t first, size_t count) {
         for (size_t i = first; i < first + count; i++) {
             hf::P1 pt;
@@ -10178,12 +10058,14 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
             hf::p1_compress(proof.data() + 48 * i, pt);
         }
     };
-    uint8_t h[32];
-    if (custom)
-        custom_proof_statement(h, key_p1s, n, t, c->lg_ext, c->g_custom, c->exps, ks.data(), pub.data(), n_public, rho ? c->exps_next : nullptr);
-    else proof_statement(h, key_p1s, n, t, c->lg_ext, ks.data(), pub.data(), n_public);
+    ProofWalk walk;  // every round below ends with the segment it has written absorbed and that segment's challenges drawn
+    {
+        hf::Sha256 st;
+        sp.statement_prefix(st, key_p1s, c->shifts);
+        sp.statement_finish(st, public_inputs, walk.h);
+    }
 
-    // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; beta, gamma
+    // the wires (and PI with them) to the device and to coefficients, their commitments; beta, gamma (a lookup proof: theta)
     if (device) {
         HIP_TRY(ctx, hipMemcpy2DAsync(d_v, n * 32, wires, stride * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
     } else {
@@ -10196,178 +10078,11 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p
                            "hipMemcpyAsync (public inputs)");
         if (rc) return rc;
     }
-    if (blinders) {
+    if (blinders && !nlk) {  // B = [ b | c ], the front of the array
         rc = copy_unlocked(ctx, lk, s.stream, d_bl, blinders, (2 * t + kBlindZLen) * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
         if (rc) return rc;
     }
-    rc = to_coefficients(0, ncoef - 1);
-    if (rc) return rc;
-    if (blinders) {
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_s, wlen * 32, d_u, n * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
-        launch_blind_patch(s.stream, d_s, (uint32_t)n, t, wlen, d_bl, d_bl, kBlindWireLen, t);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    rc = sync_unlocked(ctx, lk, s.stream, "circuit prove (wires)");
-    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_s : d_u, wlen, t, p1s.data());
-    if (rc) return rc;
-    put_points(0, t);
-    proof_absorb(h, proof.data() + L.wires, L.z - L.wires);
-    const hf::Fr beta = proof_challenge(h, 0), gamma = proof_challenge(h, 1);
-
-    // round 2: z on the device from the wires and the key's sigma values; z_n = 1; its commitment; alpha
-    {
-        const GpScalars perm{c->shifts, beta.l, gamma.l};
-        uint64_t last[4];
-        size_t bad = 0;
-        rc = gp_on_slot(ctx, lk, s, d_v, c->values.dev() + 8 * (t + 2) * n, n, t, n, &perm, sh.lg_n, d_vz, last, &bad);
-        if (rc) return rc;
-        if (std::memcmp(last, hf::kFrOne.l, 32) != 0) {
-            ctx->last_error = "circuit prove: the grand product does not return to one (z_n != 1): the copy constraints do not hold";
-            return KZG_ERR_REMAINDER;
-        }
-    }
-    rc = to_coefficients(ncoef - 1, 1);
-    if (rc) return rc;
-    uint32_t* d_sz = blinders ? d_s + 8 * t * wlen : nullptr;
-    if (blinders) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_sz, d_uz, n * 32, hipMemcpyDeviceToDevice, s.stream));
-        launch_blind_patch(s.stream, d_sz, (uint32_t)n, 1, zlen, d_bl + 8 * 2 * t, d_bl + 8 * 2 * t, kBlindZLen, 1);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    rc = sync_unlocked(ctx, lk, s.stream, "circuit prove (z)");
-    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sz : d_uz, zlen, 1, p1s.data() + 18 * t);
-    if (rc) return rc;
-    put_points(t, 1);
-    proof_absorb(h, proof.data() + L.z, 48);
-    const hf::Fr alpha = proof_challenge(h, 0);
-
-    // round 3: the quotient from the resident coefficients, its chunks' commitments; zeta
-    const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
-    rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p,
-                                                  p1s.data() + 18 * (t + 1), true, &round_base, custom)
-                  : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 1), true,
-                                          &round_base, nullptr, custom);
-    if (rc) return rc;
-    put_points(t + 1, e - 1);
-    proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
-    const hf::Fr zeta = proof_challenge(h, 0);
-
-    // rounds 4 and 5: the evaluations, v from them, r(zeta) = 0, the opening
-    ProveRound last_round = round_base;
-    last_round.derive_v = [&](const uint64_t* ev, uint64_t v[4]) {
-        for (size_t i = 0; i < 2 * t + rho; i++) {
-            hf::Fr y;
-            std::memcpy(y.l, ev + 4 * i, 32);
-            proof_fr_to_be(y, proof.data() + L.evals + 32 * i);
-        }
-        proof_absorb(h, proof.data() + L.evals, L.w - L.evals);
-        const hf::Fr vf = proof_challenge(h, 0);
-        std::memcpy(v, vf.l, 32);
-        return true;
-    };
-    rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
-                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round, nullptr, custom);
-    if (rc) return rc;
-    hf::P1 w;
-    std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
-    hf::p1_compress(proof.data() + L.w, w);
-    std::memcpy(out_proof, proof.data(), L.len);
-    return KZG_OK;
-}
-// kzg_circuit_lookup_prove: circuit_prove_impl's sibling with two more rounds.  The values
-// V are [ wires | PI | z | phi | m | f | T ] (f, T: the folded columns), the coefficients U [ wires | PI | z | phi | m ]; the call
-// holds lookup_mu (the hash table of the multiplicities) between quotient_mu and the context's mutex.
-// blinders (host, or null): kzg_circuit_lookup_prove_blinded (section 4.30).  U stays unblinded, as the rounds read it; the blinded
-// copies that are committed go to S, [ wires (n + 2 each) | m (n + 2) | z | phi (n + 3 each) ], the blinders they are patched with to B
-// in the same order, [ b | u | c | p ].
-int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t* key_p1s, const void* wires, size_t stride,
-                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row, bool device,
-                              const uint64_t* blinders = nullptr) {
-    // lookup_mu is taken after quotient_mu and given up after the frame has drained the stream (declared first, destroyed last)
-    std::unique_lock<std::mutex> lkl(ctx->lookup_mu, std::defer_lock);
-    PqCall call(ctx);
-    if (!circuit_alive(ctx, c)) return circuit_foreign(ctx);
-    if (!c->c_tab) return prove_refused(ctx, "the circuit was created without a lookup table");
-    PqShape sh;
-    if (!pq_shape(c->n, (size_t)1 << c->lg_ext, &sh) || stride < c->n || n_public > c->n) return KZG_ERR_INVALID_ARG;
-    const size_t n = sh.n, t = c->t, e = sh.rot, lc = c->c_tab, ncoef = t + 1 + (n_public ? 1 : 0);
-    std::vector<hf::Fr> ks(t), pub(n_public);
-    for (size_t j = 0; j < t; j++) std::memcpy(ks[j].l, c->shifts + 4 * j, 32);
-    for (size_t i = 0; i < n_public; i++)
-        if (!fr_arg_below_r(public_inputs + 4 * i, &pub[i])) return prove_refused(ctx, "a public input is not below r");
-    if (blinders) {
-        std::vector<hf::Fr> bl;
-        if (!lookup_blind_shape_ok(n, t, e, lc)) return lookup_blind_shape_refused(ctx, "circuit lookup prove (blinded)");
-        if (!blind_values_ok(ctx, "circuit lookup prove (blinded)", blinders, lookup_blind_count(t, e), &bl)) return KZG_ERR_INVALID_ARG;
-    }
-    const size_t t_len = blinders ? blind_quotient_len(n, t, e) : sh.N - n, need = blinders ? n + t + 3 : n;
-    const size_t wlen = blinders ? n + kBlindWireLen : n, zlen = blinders ? n + kBlindZLen : n;
-    const size_t nbw = 2 * t + kBlindMultLen, nbz = kBlindZLen + kBlindPhiLen;  // B: [ b | u ], then [ c | p ]
-    lkl.lock();
-    call.lock();
-    int rc = pq_srs_status(ctx, true, need);
-    if (rc == KZG_OK) rc = call.begin();
-    if (rc == KZG_OK) rc = pq_srs_status(ctx, true, need);  // (the wait for a slot dropped the mutex)
-    if (rc == KZG_OK) rc = ensure_ntt_batch(ctx);
-    if (rc) return rc;
-    std::unique_lock<std::mutex>& lk = call.lk();
-    Slot& s = call.s();
-    const int slot = call.slot();
-    DevBuf &V = ctx->prove_buf[0], &U = ctx->prove_buf[1], &S = ctx->prove_buf[2], &T = ctx->prove_buf[3], &B = ctx->prove_buf[4];
-    rc = V.reserve(ctx, (ncoef + 4) * n * 32, s.stream);
-    if (rc == KZG_OK) rc = U.reserve(ctx, (ncoef + 2) * n * 32, s.stream);
-    if (rc == KZG_OK) rc = T.reserve(ctx, t_len * 32, s.stream);
-    if (rc == KZG_OK && blinders) rc = S.reserve(ctx, ((t + 1) * wlen + 2 * zlen) * 32, s.stream);
-    if (rc == KZG_OK && blinders) rc = B.reserve(ctx, (nbw + nbz) * 32, s.stream);
-    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
-    if (rc) return rc;
-    uint32_t *d_v = V.dev(), *d_u = U.dev();
-    uint32_t *d_s = blinders ? S.dev() : nullptr, *d_sm = blinders ? d_s + 8 * t * wlen : nullptr, *d_sz = blinders ? d_sm + 8 * wlen : nullptr;
-    uint32_t* d_bl = blinders ? B.dev() : nullptr;
-    uint32_t *d_vz = d_v + 8 * (ncoef - 1) * n, *d_vphi = d_vz + 8 * n, *d_vm = d_vphi + 8 * n, *d_vf = d_vm + 8 * n, *d_vt = d_vf + 8 * n;
-    uint32_t *d_uz = d_u + 8 * (ncoef - 1) * n, *d_um = d_uz + 16 * n;
-    const ProveRound round_base{&lk, slot, d_u, nullptr};
-    const Fr30* itw = (const Fr30*)ctx->ntt_tw.p + 2 * kNttTableLen;
-    const Fr30 inv_n = fr30_arg_from_mont256(hf::fr_inv(fr_pow2(sh.lg_n)));
-    auto to_coefficients = [&](size_t first, size_t cols) -> int {  // `cols` columns of V -> U
-        PqBufs w;
-        int r = pq_bufs(ctx, n, cols, &w);
-        if (r) return r;
-        for (size_t c0 = 0; c0 < cols; c0 += w.chunk) {
-            const size_t bc = cols - c0 < w.chunk ? cols - c0 : w.chunk;
-            launch_ntt_batch(s.stream, d_v + 8 * (first + c0) * n, n, d_u + 8 * (first + c0) * n, n, sh.lg_n, (uint32_t)bc, itw, inv_n, w.A, w.B);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        return KZG_OK;
-    };
-    const size_t np1 = t + e + 2;  // the proof's points before the evaluations: wires, [m], [z], [phi], chunks
-    const LookupProofLayout L = lookup_proof_layout(t, e, lc);
-    std::vector<uint64_t> p1s(18 * (np1 + 1)), evals(4 * L.nevals);
-    std::vector<uint8_t> proof(L.len);
-    auto put_points = [&](size_t first, size_t count) {
-        for (size_t i = first; i < first + count; i++) {
-            hf::P1 pt;
-            std::memcpy(&pt, p1s.data() + 18 * i, sizeof pt);
-            hf::p1_compress(proof.data() + 48 * i, pt);
-        }
-    };
-    uint8_t h[32];
-    lookup_proof_statement(h, key_p1s, n, t, c->lg_ext, lc, ks.data(), pub.data(), n_public);
-
-    // round 1: the wires (and PI with them) to the device and to coefficients, their commitments; theta
-    if (device) {
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_v, n * 32, wires, stride * 32, n * 32, t, hipMemcpyDeviceToDevice, s.stream));
-    } else {
-        rc = pq_upload(ctx, lk, s.stream, d_v, (const uint64_t*)wires, n, t, stride);
-        if (rc) return rc;
-    }
-    if (n_public) {
-        HIP_TRY(ctx, hipMemsetAsync(d_v + 8 * t * n, 0, n * 32, s.stream));
-        rc = copy_unlocked(ctx, lk, s.stream, d_v + 8 * t * n, public_inputs, n_public * 32, hipMemcpyHostToDevice,
-                           "hipMemcpyAsync (public inputs)");
-        if (rc) return rc;
-    }
-    if (blinders) {  // B = [ b | u | c | p ] from the array's [ b | c | d | p | u ]
+    if (blinders && nlk) {  // B = [ b | u | c | p ] from the array's [ b | c | d | p | u ]
         const uint64_t *c_src = blinders + 4 * 2 * t, *p_src = c_src + 4 * (kBlindZLen + e - 2), *u_src = p_src + 4 * kBlindPhiLen;
         rc = copy_unlocked(ctx, lk, s.stream, d_bl, blinders, 2 * t * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (blinders)");
         if (rc == KZG_OK)
@@ -10386,16 +10101,15 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
         launch_blind_patch(s.stream, d_s, (uint32_t)n, t, wlen, d_bl, d_bl, kBlindWireLen, t);
         HIP_TRY(ctx, hipGetLastError());
     }
-    rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (wires)");
+    rc = sync_unlocked(ctx, lk, s.stream, (what + " (wires)").c_str());
     if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_s : d_u, wlen, t, p1s.data());
     if (rc) return rc;
     put_points(0, t);
-    proof_absorb(h, proof.data() + L.wires, L.m - L.wires);
-    const hf::Fr theta = proof_challenge(h, 0);
+    walk.round(sp, proof.data());
 
-    // round 2: the folded columns, the multiplicities of f in T, [m]; beta, gamma
-    {
-        const LkKernelScalars sc(theta.l, nullptr, nullptr, lc);
+    // a lookup proof: the folded columns, the multiplicities of f in T, [m]; beta, gamma
+    if (nlk) {
+        const LkKernelScalars sc(walk.ch[0].l, nullptr, nullptr, lc);
         const uint32_t* tab = c->values.dev() + 8 * (2 * t + 2) * n;
         launch_lk_fold(s.stream, d_v, n, tab, tab + 8 * lc * n, (uint32_t)n, (uint32_t)lc, sc.view(), d_vf, d_vt);
         HIP_TRY(ctx, hipGetLastError());
@@ -10415,26 +10129,27 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
             ctx->last_error = "circuit lookup prove: the tuple of row " + std::to_string(bad) + " is in no row of the table";
             return KZG_ERR_REMAINDER;
         }
+        if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sm : d_um, wlen, 1, p1s.data() + 18 * t);
         if (rc) return rc;
+        put_points(t, 1);
+        walk.round(sp, proof.data());
     }
-    rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sm : d_um, wlen, 1, p1s.data() + 18 * t);
-    if (rc) return rc;
-    put_points(t, 1);
-    proof_absorb(h, proof.data() + L.m, 48);
-    const hf::Fr beta = proof_challenge(h, 0), gamma = proof_challenge(h, 1);
+    const hf::Fr theta = walk.ch[0] /* a lookup proof's */, beta = walk.ch[nlk], gamma = walk.ch[nlk + 1];
 
-    // round 3: phi and z on the device; phi_n = 0, z_n = 1; their commitments; alpha
+    // (phi, then) z on the device from the wires and the key's sigma values; phi_n = 0, z_n = 1; their commitments; alpha
     {
         uint64_t last[4];
         size_t bad = (size_t)-1;
-        rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_vf, nullptr, d_vt, d_vm, beta.l, n, 1, n}, d_vphi, last, &bad);
-        if (rc) {
-            if (bad_row && bad != (size_t)-1) *bad_row = bad;
-            return rc;
-        }
-        if (std::memcmp(last, kFrZero.l, 32) != 0) {
-            ctx->last_error = "circuit lookup prove: the running sum does not return to zero (phi_n != 0): the lookup does not hold";
-            return KZG_ERR_REMAINDER;
+        if (nlk) {
+            rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_vf, nullptr, d_vt, d_vm, beta.l, n, 1, n}, d_vphi, last, &bad);
+            if (rc) {
+                if (bad_row && bad != (size_t)-1) *bad_row = bad;
+                return rc;
+            }
+            if (std::memcmp(last, kFrZero.l, 32) != 0) {
+                ctx->last_error = "circuit lookup prove: the running sum does not return to zero (phi_n != 0): the lookup does not hold";
+                return KZG_ERR_REMAINDER;
+            }
         }
         const GpScalars perm{c->shifts, beta.l, gamma.l};
         rc = gp_on_slot(ctx, lk, s, d_v, c->values.dev() + 8 * (t + 2) * n, n, t, n, &perm, sh.lg_n, d_vz, last, &bad);
@@ -10444,152 +10159,135 @@ int circuit_lookup_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, const uint64_t
             return KZG_ERR_REMAINDER;
         }
     }
-    rc = to_coefficients(ncoef - 1, 2);
-    if (rc == KZG_OK && blinders) {  // z and phi lie side by side in U and in S, c and p in B: one patch
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_sz, zlen * 32, d_uz, n * 32, n * 32, 2, hipMemcpyDeviceToDevice, s.stream));
-        launch_blind_patch(s.stream, d_sz, (uint32_t)n, 2, zlen, d_bl + 8 * nbw, d_bl + 8 * nbw, kBlindZLen, 2);
+    rc = to_coefficients(ncoef - 1, 1 + nlk);
+    if (rc) return rc;
+    if (blinders) {  // z and phi lie side by side in U and in S, c and p in B: one patch
+        if (nlk) {
+            HIP_TRY(ctx, hipMemcpy2DAsync(d_sz, zlen * 32, d_uz, n * 32, n * 32, 2, hipMemcpyDeviceToDevice, s.stream));
+        } else {
+            HIP_TRY(ctx, hipMemcpyAsync(d_sz, d_uz, n * 32, hipMemcpyDeviceToDevice, s.stream));
+        }
+        launch_blind_patch(s.stream, d_sz, (uint32_t)n, 1 + nlk, zlen, d_bl + 8 * nbw, d_bl + 8 * nbw, kBlindZLen, 1 + nlk);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup prove (z, phi)");
-    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sz : d_uz, zlen, 2, p1s.data() + 18 * (t + 1));
+    rc = sync_unlocked(ctx, lk, s.stream, nlk ? "circuit lookup prove (z, phi)" : "circuit prove (z)");
+    if (rc == KZG_OK) rc = pq_commit_chunks(ctx, lk, slot, blinders ? d_sz : d_uz, zlen, 1 + nlk, p1s.data() + 18 * (t + nlk));
     if (rc) return rc;
-    put_points(t + 1, 2);
-    proof_absorb(h, proof.data() + L.z, 96);
-    const hf::Fr alpha = proof_challenge(h, 0);
+    put_points(t + nlk, 1 + nlk);
+    walk.round(sp, proof.data());
+    const hf::Fr alpha = walk.ch[nlk + 2];
 
-    // round 4: the quotient with the lookup's term from the resident coefficients, its chunks' commitments; zeta
+    // the quotient (with the lookup's term) from the resident coefficients, its chunks' commitments; zeta
     const void* d_pi = n_public ? d_v + 8 * t * n : nullptr;
-    const LookupRecord rec{d_vm, d_vphi, theta.l};
-    rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p,
-                                                  p1s.data() + 18 * (t + 3), true, &round_base, nullptr, &rec)
-                  : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, p1s.data() + 18 * (t + 3), true,
-                                          &round_base, &rec);
+    const LookupRecord lookup_rec{d_vm, d_vphi, theta.l};
+    const LookupRecord* lookup = nlk ? &lookup_rec : nullptr;
+    uint64_t* chunk_p1s = p1s.data() + 18 * (t + 1 + 2 * nlk);
+    rc = blinders ? circuit_quotient_blinded_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, blinders, T.p, chunk_p1s, true,
+                                                  &round_base, custom, lookup)
+                  : circuit_quotient_impl(ctx, c, d_v, n, d_vz, d_pi, alpha.l, beta.l, gamma.l, nullptr, T.p, chunk_p1s, true, &round_base,
+                                          lookup, custom);
     if (rc) return rc;
-    put_points(t + 3, e - 1);
-    proof_absorb(h, proof.data() + L.chunks, L.evals - L.chunks);
-    const hf::Fr zeta = proof_challenge(h, 0);
+    put_points(t + 1 + 2 * nlk, e - 1);
+    walk.round(sp, proof.data());
+    const hf::Fr zeta = walk.ch[nlk + 3];
 
-    // rounds 5 and 6: the evaluations, v from them, r_L(zeta) = 0, the opening
+    // the last two rounds: the evaluations, v from them, r(zeta) = 0, the opening
     ProveRound last_round = round_base;
     last_round.derive_v = [&](const uint64_t* ev, uint64_t v[4]) {
-        for (size_t i = 0; i < L.nevals; i++) {
-            hf::Fr y;
-            std::memcpy(y.l, ev + 4 * i, 32);
-            proof_fr_to_be(y, proof.data() + L.evals + 32 * i);
-        }
-        proof_absorb(h, proof.data() + L.evals, L.w - L.evals);
-        const hf::Fr vf = proof_challenge(h, 0);
-        std::memcpy(v, vf.l, 32);
+        for (size_t i = 0; i < sp.nevals(); i++) proof_fr_to_be(pq_fr(ev + 4 * i), proof.data() + sp.evals_off() + 32 * i);
+        walk.round(sp, proof.data());
+        std::memcpy(v, walk.ch[nlk + 4].l, 32);
         return true;
     };
     rc = circuit_open_impl(ctx, c, d_v, n, d_vz, d_pi, T.p, alpha.l, beta.l, gamma.l, zeta.l, hf::kFrOne.l /* replaced by derive_v */,
-                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round, &rec);
+                           evals.data(), nullptr, p1s.data() + 18 * np1, true, blinders, &last_round, lookup, custom);
     if (rc) return rc;
     hf::P1 w;
     std::memcpy(&w, p1s.data() + 18 * np1, sizeof w);
-    hf::p1_compress(proof.data() + L.w, w);
-    std::memcpy(out_proof, proof.data(), L.len);
+    hf::p1_compress(proof.data() + sp.w_off(), w);
+    std::memcpy(out_proof, proof.data(), sp.len);
     return KZG_OK;
+}
+// The exported prove calls: their argument checks (need_blinders: the call refuses a null array), the forwarding of a multi-device
+// context to the device that holds the whole SRS (the _device forms take a single-device context), the body
+static int circuit_prove_entry(kzg_ctx* ctx, const kzg_circuit* circuit, ProofKind kind, const uint64_t* key_p1s, const void* wires,
+                               size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, bool need_blinders,
+                               uint8_t* out_proof, size_t* bad_row, bool device) {
+    if (bad_row) *bad_row = (size_t)-1;
+    if (device) KZG_SINGLE_DEVICE_ONLY(ctx);
+    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || (need_blinders && !blinders) || !out_proof)
+        return KZG_ERR_INVALID_ARG;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, circuit_prove_entry(kid, circuit, kind, key_p1s, wires, stride, public_inputs, n_public, blinders,
+                                                       need_blinders, out_proof, bad_row, device));
+    }
+    return circuit_prove_impl(ctx, circuit, kind, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, bad_row, device);
 }
 }  // namespace
 
 int kzg_circuit_lookup_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                              const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row) {
-    if (bad_row) *bad_row = (size_t)-1;
-    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    if (ctx->multi) {
-        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
-        if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_lookup_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row));
-    }
-    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row, false);
+    return circuit_prove_entry(ctx, circuit, kProofLookup, key_p1s, wires, stride, public_inputs, n_public, nullptr, false, out_proof, bad_row,
+                               false);
 }
 
 int kzg_circuit_lookup_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
                                     const uint64_t* public_inputs, size_t n_public, uint8_t* out_proof, size_t* bad_row) {
-    if (bad_row) *bad_row = (size_t)-1;
-    KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, out_proof, bad_row, true);
+    return circuit_prove_entry(ctx, circuit, kProofLookup, key_p1s, d_wires, stride, public_inputs, n_public, nullptr, false, out_proof,
+                               bad_row, true);
 }
 
 int kzg_circuit_lookup_prove_blinded(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires,
                                      size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
                                      uint8_t* out_proof, size_t* bad_row) {
-    if (bad_row) *bad_row = (size_t)-1;
-    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !blinders || !out_proof) return KZG_ERR_INVALID_ARG;
-    if (ctx->multi) {
-        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
-        if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_lookup_prove_blinded(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders,
-                                                                   out_proof, bad_row));
-    }
-    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, out_proof, bad_row, false, blinders);
+    return circuit_prove_entry(ctx, circuit, kProofLookup, key_p1s, wires, stride, public_inputs, n_public, blinders, true, out_proof, bad_row,
+                               false);
 }
 
 int kzg_circuit_lookup_prove_blinded_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
                                             size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
                                             uint8_t* out_proof, size_t* bad_row) {
-    if (bad_row) *bad_row = (size_t)-1;
-    KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !blinders || !out_proof) return KZG_ERR_INVALID_ARG;
-    return circuit_lookup_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, out_proof, bad_row, true, blinders);
+    return circuit_prove_entry(ctx, circuit, kProofLookup, key_p1s, d_wires, stride, public_inputs, n_public, blinders, true, out_proof,
+                               bad_row, true);
 }
 
 int kzg_circuit_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                       const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
-    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    if (ctx->multi) {
-        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
-        if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
-    }
-    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false);
+    return circuit_prove_entry(ctx, circuit, kProofPlain, key_p1s, wires, stride, public_inputs, n_public, blinders, false, out_proof, nullptr,
+                               false);
 }
 
 int kzg_circuit_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
                              const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
-    KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true);
+    return circuit_prove_entry(ctx, circuit, kProofPlain, key_p1s, d_wires, stride, public_inputs, n_public, blinders, false, out_proof,
+                               nullptr, true);
 }
 
 int kzg_circuit_custom_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                              const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
-    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    if (ctx->multi) {
-        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
-        if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid, kzg_circuit_custom_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
-    }
-    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false, true);
+    return circuit_prove_entry(ctx, circuit, kProofCustom, key_p1s, wires, stride, public_inputs, n_public, blinders, false, out_proof, nullptr,
+                               false);
 }
 
 int kzg_circuit_custom_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires, size_t stride,
                                     const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
-    KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true, true);
+    return circuit_prove_entry(ctx, circuit, kProofCustom, key_p1s, d_wires, stride, public_inputs, n_public, blinders, false, out_proof,
+                               nullptr, true);
 }
 
 int kzg_circuit_custom_next_prove(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const uint64_t* wires, size_t stride,
                                   const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders, uint8_t* out_proof) {
-    if (!ctx || !circuit || !key_p1s || !wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    if (ctx->multi) {
-        kzg_ctx* kid = whole_srs_kid(ctx, true, "the proof's commitments need");
-        if (!kid) return KZG_ERR_INVALID_ARG;
-        return forwarded(ctx, kid,
-                         kzg_circuit_custom_next_prove(kid, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof));
-    }
-    return circuit_prove_impl(ctx, circuit, key_p1s, wires, stride, public_inputs, n_public, blinders, out_proof, false, true, true);
+    return circuit_prove_entry(ctx, circuit, kProofNext, key_p1s, wires, stride, public_inputs, n_public, blinders, false, out_proof, nullptr,
+                               false);
 }
 
 int kzg_circuit_custom_next_prove_device(kzg_ctx* ctx, const kzg_circuit* circuit, const uint64_t* key_p1s, const void* d_wires,
                                          size_t stride, const uint64_t* public_inputs, size_t n_public, const uint64_t* blinders,
                                          uint8_t* out_proof) {
-    KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !circuit || !key_p1s || !d_wires || (!public_inputs && n_public) || !out_proof) return KZG_ERR_INVALID_ARG;
-    return circuit_prove_impl(ctx, circuit, key_p1s, d_wires, stride, public_inputs, n_public, blinders, out_proof, true, true, true);
+    return circuit_prove_entry(ctx, circuit, kProofNext, key_p1s, d_wires, stride, public_inputs, n_public, blinders, false, out_proof,
+                               nullptr, true);
 }
 
 int kzg_verify_points(const uint64_t commitment_p1[18], const uint64_t proof_p1[18], const uint64_t* zs, const uint64_t* ys,

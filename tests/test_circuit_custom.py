@@ -190,6 +190,23 @@ def test_challenges_against_the_oracle(oracle, shape):
         assert _challenges(oracle, db) == tuple(db[k] for k in NAMES) and db["proof"] != d["proof"]
 
 
+@pytest.mark.parametrize("shape", [(8, 3, 2, ((1, 1, 1), (3, 0, 0))), (16, 2, 2, ((3, 0), (0, 1)))], ids=ids)
+def test_challenges_with_no_one_and_n_public_inputs(oracle, shape):
+    """the two ends of the statement's public inputs and one value, at e = t + 1 and at e > t + 1.  The proof's bytes are hashed as
+    they are: the same proof serves every statement"""
+    n, t, log_ext, exps = shape
+    d = _proof(oracle, shape)
+    cc = d["cc"]
+    assert len(d["public"]) == n
+    seen = set()
+    for n_public in (0, 1, n):
+        public = d["public"][:n_public]
+        got = _challenges(oracle, d, public=public)
+        assert got == CX.challenges(n, t, log_ext, cc.exps, cc.circuit.ks, d["key48"], public, d["proof"]), n_public
+        seen.add(got)
+    assert len(seen) == 3 and tuple(d[k] for k in NAMES) in seen
+
+
 def test_g_an_exponent_and_a_custom_commitment_move_every_challenge(oracle):
     n, t, log_ext, exps = CC.SBOX
     d = _proof(oracle, CC.SBOX)

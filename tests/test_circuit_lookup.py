@@ -160,6 +160,22 @@ def test_challenges_against_the_oracle(oracle, n, t, c, log_ext):
         assert d0["public"] == [] and _challenges(oracle, d0) == tuple(d0[k] for k in ("theta", "beta", "gamma", "alpha", "zeta", "v"))
 
 
+@pytest.mark.parametrize("n,t,c,log_ext", [(8, 3, 3, 2), (16, 2, 1, 2)])
+def test_challenges_with_no_one_and_n_public_inputs(oracle, n, t, c, log_ext):
+    """the two ends of the statement's public inputs and one value, at e = t + 1 and at e > t + 1.  The proof's bytes are hashed as
+    they are: the same proof serves every statement"""
+    d = _proof(oracle, n, t, c, log_ext)
+    lc = d["lc"]
+    assert len(d["public"]) == n
+    seen = set()
+    for n_public in (0, 1, n):
+        public = d["public"][:n_public]
+        got = _challenges(oracle, d, public=public)
+        assert got == CL.challenges(n, t, log_ext, c, lc.circuit.ks, d["key48"], public, d["proof"]), n_public
+        seen.add(got)
+    assert len(seen) == 3 and tuple(d[k] for k in ("theta", "beta", "gamma", "alpha", "zeta", "v")) in seen
+
+
 def test_every_field_moves_the_challenges_after_it_and_none_before(oracle):
     n, t, c, log_ext = 8, 3, 3, 2
     d = _proof(oracle, n, t, c, log_ext)

@@ -13,12 +13,17 @@ import numpy as np
 import pytest
 
 import bigint_twin as BT
+import circuit_custom_cases as XC
 import circuit_lookup_blind_oracle as LB
 import circuit_lookup_cases as CC
 import circuit_lookup_oracle as CL
+import circuit_next_cases as NC
 import circuit_oracle as CO
 import grand_product_oracle as GO
 import kzg_poly_commit_exploration_amd as K
+import test_circuit_custom_gpu as XG  # the other kinds' oracle proofs under the bench secret (shared, computed once) and handles
+import test_circuit_next_gpu as NG
+import test_circuit_proof_gpu as HC
 
 pytestmark = pytest.mark.gpu
 R = CL.R
@@ -294,7 +299,9 @@ def test_prover_statuses_leave_the_output_untouched_and_the_context_serving(engi
 def test_after_a_larger_plain_proof_and_beside_the_other_provers_on_one_handle(oracle):
     """workspaces and cross-round buffers grown by one call are reused or regrown by the next: a blinded lookup proof at 8 rows, a
     plain proof and a plain lookup proof at 2048, the blinded proof again; and on the same handle the plain lookup proof and the
-    blinded proof of kzg_circuit_prove keep their bytes"""
+    blinded proof of kzg_circuit_prove keep their bytes.  Then the one prover body under every kind in turn, against the oracles:
+    lookup blinded (16, 3, c = 2, 2), plain blinded (8, 3, 2), custom (1, 2, 2), next-row (2, 2, 2), plain (16, 2, 2), lookup
+    (8, 3, c = 3, 2) -- the buffers' layout narrows, widens and narrows again under the values the call before left"""
     e = K.SetupArtifactsGenerator(BT.BENCH_SECRET_BE).take(2048 + 8)
     try:
         n, t, c, log_ext = 8, 3, 3, 2
@@ -315,6 +322,28 @@ def test_after_a_larger_plain_proof_and_beside_the_other_provers_on_one_handle(o
         assert circ.lookup_prove_blinded(wires, bl, pub, n=n) == d["proof"]
         assert circ.lookup_prove(wires, pub, n=n) == old_lookup and circ.prove(wires, pub, base_bl, n=n) == old_blinded
         assert old_lookup != d["proof"]
+        # one proof of every kind in turn on this context, nothing recreated in between, each held to its oracle's bytes: every
+        # call finds the cross-round buffers at another kind's size and layout, with that kind's values still in them
+        d1 = _proof(oracle, 16, 3, 2, 2)
+        (bl2, d2), (_, d5) = HC._case(oracle, 8, 3, 2, True, True), HC._case(oracle, 16, 2, 2, True, False)
+        d3, d4 = XG._proof(oracle, XC.SHAPES[0]), NG._proof(oracle, NC.SHAPES[0])
+        want6 = CC.memo(("bench plain proof of the blinded case", n, t, c, log_ext), lambda: CL.prove(oracle, lc, log_ext, S)["proof"])
+        c1, c2, c5 = _create(e, d1["lc"], 2), HC._create(e, d2["c"], 2), HC._create(e, d5["c"], 2)
+        c3, c4 = XG._create(e, d3["cc"], XC.SHAPES[0][2], want_key=True), NG._create(e, d4["nc"], NC.SHAPES[0][2], want_key=True)
+        steps = [
+            ("lookup, blinded, (16, 3, c = 2, 2)",
+             lambda: c1.lookup_prove_blinded(_limbs(d1["lc"].circuit.wires), GO.to_limbs(d1["bl"].flat()), _pub(d1)), d1["proof"]),
+            ("plain, blinded, (8, 3, 2)", lambda: c2.prove(_limbs(d2["c"].wires), _pub(d2), GO.to_limbs(bl2.flat())), d2["proof"]),
+            ("custom, its smallest shape", lambda: c3.custom_prove(_limbs(d3["cc"].circuit.wires), _pub(d3)), d3["proof"]),
+            ("next-row, its smallest shape", lambda: c4.custom_next_prove(_limbs(d4["nc"].circuit.wires), _pub(d4)), d4["proof"]),
+            ("plain, (16, 2, 2)", lambda: c5.prove(_limbs(d5["c"].wires), _pub(d5), None), d5["proof"]),
+            ("lookup, (8, 3, c = 3, 2)", lambda: circ.lookup_prove(wires, pub, n=n), want6),
+        ]
+        for name, prove, want in steps:
+            assert prove() == want, name
+        assert want6 == old_lookup
+        for handle in (c1, c2, c3, c4, c5):
+            handle.close()
         big.close()
         circ.close()
     finally:

@@ -175,6 +175,23 @@ def test_challenges_against_the_oracle(oracle, shape):
         assert d0["public"] == [] and _challenges(oracle, d0) == tuple(d0[k] for k in NAMES)
 
 
+@pytest.mark.parametrize("shape", [NC.NEXT_ONLY, (16, 2, 2, ((1, 0),), ((0, 1),))], ids=ids)
+def test_challenges_with_no_one_and_n_public_inputs(oracle, shape):
+    """the two ends of the statement's public inputs and one value, at (8, 3, 2) with e = t + 1 and at (16, 2, 2) with e > t + 1.
+    The proof's bytes are hashed as they are: the same proof serves every statement"""
+    n, t, log_ext, exps, exps_next = shape
+    d = _proof(oracle, shape)
+    nc = d["nc"]
+    assert len(d["public"]) == n
+    seen = set()
+    for n_public in (0, 1, n):
+        public = d["public"][:n_public]
+        got = _challenges(oracle, d, public=public)
+        assert got == CN.challenges(n, t, log_ext, nc.exps, nc.exps_next, nc.circuit.ks, d["key48"], public, d["proof"]), n_public
+        seen.add(got)
+    assert len(seen) == 3 and tuple(d[k] for k in NAMES) in seen
+
+
 def test_every_field_of_the_statement_moves_every_challenge(oracle):
     n, t, log_ext, exps, exps_next = NC.NEXT_ONLY
     d = _proof(oracle, NC.NEXT_ONLY)

@@ -6,7 +6,8 @@ proof is [c]G with a known scalar and the three sums of the hook are [p0]G, [p1]
 Shapes (n, t, log_ext): (2, 3, 2); (8, 3, 2) with and without public inputs; (256, 3, 2) blinded with public inputs; (64, 7, 3),
 t + e = 15 products per proof; (4096, 2, 2); the custom S-box circuit (8, 3, 3) with g = 2.  Counts 1, 2, 17 (one past the 16
 terms a lane sums per level) and 65 (one past a workgroup), built by repeating the distinct proofs of a shape; at (8, 3, 2) four
-distinct proofs with three distinct sets of public inputs (the witness shifted by a constant keeps the key).
+distinct proofs with three distinct sets of public inputs (the witness shifted by a constant keeps the key).  Two proofs with
+different public inputs, plain and under the custom statement at (8, 3, 2) with g = 2, are held to the single verifier one by one.
 
 zeta inside the domain H: the challenges are hashed, so no proof reaches it; the test entry
 kzg_circuit_verify_proofs_lincomb_challenges takes caller challenges, and the three points are held to the model under the same
@@ -34,6 +35,7 @@ COUNTS = (1, 2, 17, 65)
 PLAIN = [(2, 3, 2, True, False), (8, 3, 2, True, True), (8, 3, 2, False, True), (256, 3, 2, True, True), (64, 7, 3, True, True),
          (4096, 2, 2, True, True)]
 SHAPES = PLAIN + ["custom"]
+CUSTOM_SMALL = (8, 3, 2, ((1, 1, 1), (3, 0, 0)))  # "custom_small": the custom statement at the plain (8, 3, 2), d_max = e - 1
 _CACHE = {}
 
 
@@ -56,15 +58,29 @@ def _shifted(c, by):
     return v
 
 
+def _shifted_custom(cc, by):
+    """_shifted for a custom circuit: the public inputs take up the custom terms' change too"""
+    c = cc.circuit
+    wires = [[(x + by) % R for x in col] for col in c.wires]
+    v = CX.CustomCircuit(CO.Circuit(c.ks, wires, c.sigmas, c.q_lin, c.q_mul, c.q_const, [0] * c.n), cc.q_custom, cc.exps)
+    v.circuit.pi = [(-x) % R for x in CX.gate_rows(v)]
+    assert CX.gate_rows(v) == [0] * c.n
+    return v
+
+
 class Shape:
     """the statement and the distinct valid proofs of one shape, with what the model needs"""
 
     def __init__(self, oracle, which):
         self.cc = None
-        if which == "custom":
-            n, t, log_ext, exps = CC.SBOX
+        if which in ("custom", "custom_small"):
+            n, t, log_ext, exps = CC.SBOX if which == "custom" else CUSTOM_SMALL
             case = CC.case(n, t, log_ext, exps)
-            ds = [CX.prove(oracle, case.cc, log_ext, bl, CP.S) for bl in (case.zero, case.blinders(3))]
+            if which == "custom":
+                ds = [CX.prove(oracle, case.cc, log_ext, bl, CP.S) for bl in (case.zero, case.blinders(3))]
+            else:  # two witnesses of one key with different public inputs
+                ds = [CX.prove(oracle, cc, log_ext, case.zero, CP.S) for cc in (case.cc, _shifted_custom(case.cc, 1))]
+                assert ds[0]["public"] != ds[1]["public"]
             self.cc, self.c = case.cc, case.cc.circuit
             self.exps = np.array(exps, dtype=np.uint8)
         else:
@@ -121,7 +137,7 @@ class Shape:
 
 
 def _shape(oracle, which):
-    return _memo(("shape", which if which == "custom" else tuple(which)), lambda: Shape(oracle, which))
+    return _memo(("shape", which if isinstance(which, str) else tuple(which)), lambda: Shape(oracle, which))
 
 
 def _batch(e, oracle, sh, members, **kw):
@@ -187,6 +203,23 @@ def test_one_changed_proof_rejects_the_batch_as_the_host_verifier_rejects_the_pr
                 weights = _weights(count, 7)
                 ok, bad, pts = _hook(e, oracle, sh, ms, weights)
                 assert not ok and bad is None and [p.compress() for p in pts] == sh.model(oracle, ms, weights)
+
+
+@pytest.mark.parametrize("which", [PLAIN[1], "custom_small"], ids=str)
+def test_two_proofs_with_different_public_inputs_as_one_by_one(engines, oracle, which):
+    """(8, 3, 2), plain and custom: the batch hashes the statement's bytes in front of the public inputs once and finishes a copy of
+    that state per proof, the single verifier hashes both halves per call.  A batch of two proofs with different public inputs is
+    accepted exactly when both are accepted one by one -- in either order, and with one proof's or both proofs' public inputs
+    replaced by the other's"""
+    e, sh = engines.bench_srs(SRS), _shape(oracle, which)
+    a = sh.members[0]
+    b = next(m for m in sh.members if m.public != a.public)
+    under = lambda m, other: VB.Member(m.proof, other.public, m.wire_s, m.z_s, m.t_s, m.w)  # noqa: E731
+    a_wrong, b_wrong = under(a, b), under(b, a)
+    assert sh.single(oracle, a) and sh.single(oracle, b) and not sh.single(oracle, a_wrong) and not sh.single(oracle, b_wrong)
+    for ms in ([a, b], [b, a], [a, b_wrong], [a_wrong, b], [a_wrong, b_wrong], [b_wrong, a]):
+        want = all(sh.single(oracle, m) for m in ms)
+        assert _batch(e, oracle, sh, ms) == (want, None), [m is a or m is b for m in ms]
 
 
 @pytest.mark.parametrize("which", [PLAIN[1], PLAIN[2], "custom"], ids=str)

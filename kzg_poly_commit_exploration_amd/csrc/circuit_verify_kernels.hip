@@ -33,12 +33,16 @@
 // x 2^270, in which everything is computed: a product of two multipliers is a multiplier.  A value leaves as the plain integer
 // x = fr30_to_limbs(fr30_mul(v, 1)), canonical, which is what glv_split_device and the rows of k_vc_fr_sum take.
 // Bounds: every product returns |v| <= 0.5001 r + |a b| / 2^270 and takes carry-normalised digits (one operand may be a raw sum of
-// two).  Every sum here is carry-normalised (fr30_add, cvb_sub) and has at most 2t + 3 <= 67 terms of magnitude <= 0.5001 r
-// (g0, the constant of G1) before it feeds a product: below 2^262, far inside |a| |b| < 2^528 and the top digit's 2^30.  A
-// negation is digit-wise and keeps the digit bounds, which are symmetric.  PI's running sum is brought back under 0.51 r by a
-// product with the multiplier form of one after every term; the 64 lanes' totals add to less than 2^262.  Zero tests are made on
-// the canonical residue of a value first reduced by such a product (a lazy difference may hold r, or -r, for zero), so that
-// fr30_to_limbs sees a value inside (-r, 2r).  The split scalars are plain integers below r < 2^255.
+// two).  Every sum here is carry-normalised (fr30_add, cvb_sub) and has at most 2t + 3 <= 17 terms of magnitude <= 0.5001 r
+// (t <= kPqMaxColumns = 7; g0 + g1, the constant of G1: the three terms of r's constant, 2t - 1 subtractions, g1) before it feeds a
+// product: below 8.6 r < 2^258, far inside |a| |b| < 2^528 and the top digit's 2^30.  The custom terms (g <= kCgMaxTerms) are
+// products only.  A negation is digit-wise and keeps the digit bounds, which are symmetric.  PI's running sum is brought back under
+// 0.51 r by a product with the multiplier form of one after every term; the 64 lanes' totals add to less than 32.7 r < 2^260.  Zero
+// tests are made on the canonical residue of a value first reduced by such a product, so that fr30_to_limbs sees a value inside
+// (-r, 2r): a lazy difference of two products lies in (-1.0002 r, 1.0002 r) and may hold r, or -r, for zero (its operands the two
+// representatives of a residue next to r / 2; a product's own operands decide which one it returns), and it passes -r when it is
+// not zero.  The split scalars are plain integers below r < 2^255.  tests/host/cvb_reach_host.cpp replays these kernels on the
+// host at those magnitudes.
 // G1: the group law of g1_30.hip.h on its own outputs (section 4.2): the inputs of k_cvb_stage2 are what k_vc_ladder and
 // k_vc_g1_sum stored, the ladder is verify_kernels.hip's and its outputs go to k_vc_g1_sum, as k_vc_cell_scale's do.
 #define KZG_G1_30_INLINE_DBL

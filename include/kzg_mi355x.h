@@ -334,6 +334,61 @@ int kzg_verify_sets(const uint64_t* commitments_p1, size_t t, const uint32_t* se
                     const uint64_t* zs, const uint64_t* ys, const uint64_t gamma[4], const uint64_t proof_p1[18],
                     const void* setup_g1, size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid);
 
+/* ---- multilinear polynomials: opening the multilinear extension of 2^ell values (Gemini / HyperKZG) ----------------
+ * Sum-check based provers hold a polynomial as its n = 2^ell values on the boolean hypercube and have to prove
+ * f~(u) = v for a point u in Fr^ell.  Variable x_i is bit i of the index (little-endian):
+ *        f~(u) = sum_j f[j] prod_i (bit_i(j) ? u_i : 1 - u_i).
+ * The commitment is kzg_commit(f): the values read as the coefficients of a univariate f_0 of length n.
+ * Folds, i = 0 .. ell - 1:   f_(i+1)[j] = f_i[2j] + u_i (f_i[2j+1] - f_i[2j]),  j < n / 2^(i+1);   f_ell is the one value v.
+ * With f_i(X) = E_i(X^2) + X O_i(X^2), f_(i+1) = (1 - u_i) E_i + u_i O_i, hence for any r != 0
+ *        2 r f_(i+1)(r^2) = r (1 - u_i) (f_i(r) + f_i(-r)) + u_i (f_i(r) - f_i(-r)).                                   (*)
+ * The proof: the ell - 1 commitments C_1 .. C_(ell-1) of f_1 .. f_(ell-1); the 3 ell values y_(i,0) = f_i(r), y_(i,1) =
+ * f_i(-r), y_(i,2) = f_i(r^2), i < ell, in that order; one G1 element W, bit for bit the proof of kzg_open_sets over
+ * [f_0 | f_1 | .. | f_(ell-1)], each padded with zeros to n, with the one set {r, -r, r^2} and the weights gamma^i
+ * (= kzg_open_points of F = sum_i gamma^i f_i at the three points).  The verifier checks (*) for every i with
+ * f_ell(r^2) := v and runs kzg_verify_sets on [C, C_1 .. C_(ell-1)], the one set, the values, gamma and W.
+ * SOUNDNESS: r has to be drawn after C_1 .. C_(ell-1), gamma after the values.  Nothing is hashed here: the calls take
+ * u, r and gamma as given.
+ * The pyramid: f_1 .. f_ell packed in one buffer of n - 1 values, level i at offset n - (n >> (i - 1)) (f_ell = v last).
+ * All values and scalars are blst_fr images, fully reduced.
+ * Errors, in this order: a NULL context or pointer; ell outside [1, KZG_ML_MAX_VARS]; a u_i, r or gamma not below r; r in
+ *   {0, 1, r - 1} (the three points collide) -- all KZG_ERR_INVALID_ARG, nothing is written.  Then, where an SRS is needed,
+ *   KZG_ERR_NO_SRS; a fold longer than kzg_srs_len with a non-zero value beyond it gives KZG_ERR_DEGREE_TOO_HIGH as kzg_commit
+ *   does; W follows kzg_open_points: its quotient has n - 3 coefficients, a non-zero one at index >= kzg_srs_len gives
+ *   KZG_ERR_DEGREE_TOO_HIGH.  ell = 1 has no fold commitments and W = infinity; all-zero values give infinity everywhere.
+ * Cost: the folds are two launches at any ell (k_ml_fold: eleven levels per launch inside 2048-value tiles), the values one
+ *   pass over f_0 and the pyramid plus a finish launch, F one pass, W one three-point scan and one MSM.  The ell - 1 fold
+ *   commitments are one MSM job each, two of the context's slots alternating so that consecutive levels overlap; the small
+ *   levels take the one-launch small-job path.  Measured at ell = 20 on resident values (profiles/r31_multilinear.jsonl): the
+ *   four rounds 12.5 ms -- fold 0.16, fold commitments 8.6, values 0.21, W 3.0 -- against 64.8 ms (55.8-77.6) for the folds on
+ *   16 host threads, one kzg_commit per level and kzg_open_sets of the padded stack from host memory.
+ * Multi-device contexts: kzg_ml_fold / kzg_ml_evaluate run on devices[0]; kzg_ml_open is forwarded to one device of a
+ *   replicated SRS and refused (KZG_ERR_INVALID_ARG) on a range-split one; the device forms take single-device contexts. */
+#define KZG_ML_MAX_VARS 22
+/* no SRS needed: the whole pyramid ((n - 1) x 4), or only v */
+int kzg_ml_fold(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t ell, const uint64_t* us /* ell x 4 */,
+                uint64_t* out_pyramid /* (n - 1) x 4 */);
+int kzg_ml_evaluate(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t ell, const uint64_t* us, uint64_t out_v[4]);
+/* One call per prover round over DEVICE buffers the caller holds (kzg_dev_alloc): d_evals n values, d_pyramid n - 1 values,
+ * neither overlapping the other; nothing is recomputed or copied between the rounds.  Synchronous. */
+int kzg_ml_fold_device(kzg_ctx* ctx, const void* d_evals, size_t ell, const uint64_t* us, void* d_pyramid, uint64_t out_v[4]);
+int kzg_ml_commit_folds_device(kzg_ctx* ctx, const void* d_pyramid, size_t ell, uint64_t* out_p1s /* (ell - 1) x 18 */);
+int kzg_ml_evaluations_device(kzg_ctx* ctx, const void* d_evals, const void* d_pyramid, size_t ell, const uint64_t r[4],
+                              uint64_t* out_ys /* 3 ell x 4 */);
+int kzg_ml_open_device(kzg_ctx* ctx, const void* d_evals, const void* d_pyramid, size_t ell, const uint64_t r[4],
+                       const uint64_t gamma[4], uint64_t out_p1[18]);
+/* host pointers, synchronous, the whole proof: uploads once and runs the four rounds */
+int kzg_ml_open(kzg_ctx* ctx, const uint64_t* evals_fr_mont, size_t ell, const uint64_t* us, const uint64_t r[4],
+                const uint64_t gamma[4], uint64_t out_v[4], uint64_t* out_fold_p1s /* (ell - 1) x 18 */,
+                uint64_t* out_ys /* 3 ell x 4 */, uint64_t out_p1[18]);
+/* Host only, no context: (*) for every i in host arithmetic, then kzg_verify_sets (three G1 rows, the G2 powers up to s^3).
+ * *valid = 1 iff both hold; a failing (*) gives *valid = 0, not an error.  v and the values have to be below r, the points
+ * decode and lie on the curve as kzg_verify_sets asks, else KZG_ERR_INVALID_ARG. */
+int kzg_ml_verify(const uint64_t commitment_p1[18], size_t ell, const uint64_t* us, const uint64_t v[4],
+                  const uint64_t* fold_p1s /* (ell - 1) x 18 */, const uint64_t* ys /* 3 ell x 4 */, const uint64_t r[4],
+                  const uint64_t gamma[4], const uint64_t proof_p1[18], const void* setup_g1, size_t g1_stride_bytes,
+                  const void* setup_g2, size_t g2_stride_bytes, int* valid);
+
 /* ---- polynomials in evaluation form: NTT over power-of-two domains ------------------------
  * Most KZG data (blob-style commitments, proof systems) holds a polynomial as its values over a subgroup of roots of
  * unity.  These entry points take those values directly; until now a caller had to interpolate on the host first.

@@ -28,6 +28,7 @@ __all__ = [
     "circuit_lookup_blinded_sizes", "circuit_lookup_blinders",
     "combine_claims", "verify_combined", "KZG_MAX_COMBINE",
     "verify_sets", "KZG_MAX_SETS", "KZG_MAX_SET_POINTS",
+    "ml_verify", "KZG_ML_MAX_VARS",
     "sha256", "sha256_has_shani", "blob_challenges_bytes",
 ]
 
@@ -105,6 +106,8 @@ ABI_SYMBOLS = [
     "kzg_circuit_custom_next_prove", "kzg_circuit_custom_next_prove_device", "kzg_circuit_custom_next_proof_size",
     "kzg_circuit_custom_next_proof_challenges", "kzg_circuit_custom_next_verify_proof",
     "kzg_circuit_verify_proofs_batch", "kzg_circuit_verify_proofs_lincomb", "kzg_circuit_verify_proofs_lincomb_challenges",
+    "kzg_ml_fold", "kzg_ml_evaluate", "kzg_ml_fold_device", "kzg_ml_commit_folds_device", "kzg_ml_evaluations_device",
+    "kzg_ml_open_device", "kzg_ml_open", "kzg_ml_verify",
 ]
 KZG_VERIFY_MAX_PROOFS = 1 << 16
 KZG_SRS_FIRST_IS_GENERATOR = 1
@@ -115,6 +118,7 @@ KZG_MAX_OPEN_POINTS = 64
 KZG_MAX_COMBINE = 256
 KZG_MAX_SETS = 8
 KZG_MAX_SET_POINTS = 16
+KZG_ML_MAX_VARS = 22  # variables of a multilinear opening (2^22 values: the largest SRS)
 KZG_NTT_MAX_LOG = 22
 KZG_GP_MAX_COLUMNS = 16  # columns per side of a grand product
 KZG_LOGUP_MAX_COLUMNS = 16  # columns per side of a log-derivative sum (a lookup: k <= 15 lookup columns and the table)
@@ -362,6 +366,14 @@ def load_library():
         "kzg_wait_sets": (i, [vp, i, vp, vp]),
         "kzg_quotient_sets": (i, [vp, vp, sz, sz, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
         "kzg_verify_sets": (i, [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
+        "kzg_ml_fold": (i, [vp, vp, sz, vp, vp]),
+        "kzg_ml_evaluate": (i, [vp, vp, sz, vp, vp]),
+        "kzg_ml_fold_device": (i, [vp, vp, sz, vp, vp, vp]),
+        "kzg_ml_commit_folds_device": (i, [vp, vp, sz, vp]),
+        "kzg_ml_evaluations_device": (i, [vp, vp, vp, sz, vp, vp]),
+        "kzg_ml_open_device": (i, [vp, vp, vp, sz, vp, vp, vp]),
+        "kzg_ml_open": (i, [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "kzg_ml_verify": (i, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(i)]),
         "kzg_sha256": (i, [vp, sz, vp]),
         "kzg_sha256_pieces": (i, [vp, sz, sz, i, vp]),
         "kzg_sha256_has_shani": (i, []),
@@ -1768,6 +1780,71 @@ class Engine:
         self._pq_check(self._lib.kzg_commit_evaluations_blinded(self._h, _ptr(a), n, k, stride, _ptr(b), b.shape[1], _ptr(p1s)))
         return [G1Point(p) for p in p1s]
 
+    # -- multilinear openings (Gemini / HyperKZG): 2^ell values on the hypercube, u a list of ell Scalars -------------------
+    # values: (n, 4) uint64 blst_fr images; the pyramid: f_1 .. f_ell packed, level i at offset n - (n >> (i - 1))
+    @staticmethod
+    def _ml_values(evals):
+        a = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        ell = max(a.shape[0].bit_length() - 1, 0)
+        assert a.shape[0] == 1 << ell
+        return a, ell
+
+    def ml_fold(self, evals, us):
+        """kzg_ml_fold: the pyramid as an (n - 1, 4) array"""
+        a, ell = self._ml_values(evals)
+        assert len(us) == ell
+        out = np.zeros((max(a.shape[0] - 1, 1), 4), dtype=np.uint64)
+        _check(self._lib.kzg_ml_fold(self._h, _ptr(a), ell, _ptr(_scalar_rows(us)), _ptr(out)), self._h)
+        return out[:a.shape[0] - 1].copy()
+
+    def ml_evaluate(self, evals, us):
+        """kzg_ml_evaluate: f~(u)"""
+        a, ell = self._ml_values(evals)
+        assert len(us) == ell
+        v = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.kzg_ml_evaluate(self._h, _ptr(a), ell, _ptr(_scalar_rows(us)), _ptr(v)), self._h)
+        return Scalar.from_limbs(v)
+
+    def ml_fold_device(self, d_evals, ell, us, d_pyramid):
+        """kzg_ml_fold_device: fills the n - 1 values at d_pyramid, returns v = f~(u)"""
+        v = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.kzg_ml_fold_device(self._h, C.c_void_p(d_evals), ell, _ptr(_scalar_rows(us)), C.c_void_p(d_pyramid),
+                                            _ptr(v)), self._h)
+        return Scalar.from_limbs(v)
+
+    def ml_commit_folds_device(self, d_pyramid, ell):
+        """kzg_ml_commit_folds_device: [C_1 .. C_(ell-1)]"""
+        out = np.zeros((max(ell - 1, 1), 18), dtype=np.uint64)
+        _check(self._lib.kzg_ml_commit_folds_device(self._h, C.c_void_p(d_pyramid), ell, _ptr(out)), self._h)
+        return [G1Point(out[i].copy()) for i in range(max(ell - 1, 0))]
+
+    def ml_evaluations_device(self, d_evals, d_pyramid, ell, r):
+        """kzg_ml_evaluations_device: ys[i] = [f_i(r), f_i(-r), f_i(r^2)], i < ell"""
+        ys = np.zeros((3 * max(ell, 1), 4), dtype=np.uint64)
+        _check(self._lib.kzg_ml_evaluations_device(self._h, C.c_void_p(d_evals), C.c_void_p(d_pyramid), ell, _ptr(r.limbs()),
+                                                   _ptr(ys)), self._h)
+        return [[Scalar.from_limbs(ys[3 * i + p]) for p in range(3)] for i in range(ell)]
+
+    def ml_open_device(self, d_evals, d_pyramid, ell, r, gamma):
+        """kzg_ml_open_device: W"""
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_ml_open_device(self._h, C.c_void_p(d_evals), C.c_void_p(d_pyramid), ell, _ptr(r.limbs()),
+                                            _ptr(gamma.limbs()), _ptr(out)), self._h)
+        return G1Point(out)
+
+    def ml_open(self, evals, us, r, gamma):
+        """kzg_ml_open: (v, [C_1 .. C_(ell-1)], ys, W) with ys[i] = [f_i(r), f_i(-r), f_i(r^2)]"""
+        a, ell = self._ml_values(evals)
+        assert len(us) == ell
+        v = np.zeros(4, dtype=np.uint64)
+        folds = np.zeros((max(ell - 1, 1), 18), dtype=np.uint64)
+        ys = np.zeros((3 * max(ell, 1), 4), dtype=np.uint64)
+        out = np.zeros(18, dtype=np.uint64)
+        _check(self._lib.kzg_ml_open(self._h, _ptr(a), ell, _ptr(_scalar_rows(us)), _ptr(r.limbs()), _ptr(gamma.limbs()), _ptr(v),
+                                     _ptr(folds), _ptr(ys), _ptr(out)), self._h)
+        return (Scalar.from_limbs(v), [G1Point(folds[i].copy()) for i in range(max(ell - 1, 0))],
+                [[Scalar.from_limbs(ys[3 * i + p]) for p in range(3)] for i in range(ell)], G1Point(out))
+
     # -- device-resident, pipelined --
     def num_slots(self):
         return int(self._lib.kzg_num_slots(self._h))
@@ -2468,6 +2545,23 @@ def verify_sets(commitments, set_of, sets, ys, gamma, proof, setup_g1, setup_g2)
     ok = C.c_int(0)
     _check(lib.kzg_verify_sets(_ptr(cs), t, _ptr(so), _ptr(sl), len(sets), _ptr(zl), _ptr(yl), _ptr(gamma.limbs()),
                                _ptr(proof.p1), _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
+    return bool(ok.value)
+
+
+def ml_verify(commitment, us, v, folds, ys, r, gamma, proof, setup_g1, setup_g2, ell=None):
+    """kzg_ml_verify: the fold relation at r for every level, then kzg_verify_sets over [C, C_1 .. C_(ell-1)] on the one set
+    {r, -r, r^2}.  ys[i] = [f_i(r), f_i(-r), f_i(r^2)]; setup_g1: at least three blst_p1 rows; setup_g2: [s^j]G2 for j <= 3.
+    r has to be drawn after the fold commitments and gamma after the values; nothing is hashed here."""
+    lib = load_library()
+    ell = len(us) if ell is None else ell
+    g1 = np.ascontiguousarray(setup_g1, dtype=np.uint64).reshape(-1, 18)
+    g2 = np.ascontiguousarray(setup_g2, dtype=np.uint64).reshape(-1, 36)
+    assert g1.shape[0] >= 3 and g2.shape[0] >= 4
+    fl = np.ascontiguousarray(np.stack([c.p1 for c in folds]) if len(folds) else np.zeros((1, 18)), dtype=np.uint64)
+    yl = _scalar_rows([y for row in ys for y in row])
+    ok = C.c_int(0)
+    _check(lib.kzg_ml_verify(_ptr(commitment.p1), ell, _ptr(_scalar_rows(us)), _ptr(v.limbs()), _ptr(fl), _ptr(yl), _ptr(r.limbs()),
+                             _ptr(gamma.limbs()), _ptr(proof.p1), _ptr(g1), 144, _ptr(g2), 288, C.byref(ok)))
     return bool(ok.value)
 
 

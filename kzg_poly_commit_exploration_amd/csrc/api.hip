@@ -251,6 +251,8 @@ struct Slot : SlotQueue {
     // cells of a domain (kzg_cells_and_proofs): P for the whole call in cpoly (read by the sub-batches of every slot the call
     // holds, after cells_ev), the chunk aggregates of the cell quotients in cagg
     DevBuf cpoly, cagg;
+    // multilinear openings (kzg_ml_fold, kzg_ml_open): the values and the pyramid of a host-pointer call
+    DevBuf ml_in, ml_pyr;
     // state of the job in flight
     SlotKind kind = SLOT_IDLE;
     size_t job_n = 0;
@@ -10671,6 +10673,312 @@ int kzg_srs_verify_update(const uint64_t before_p1[18], const uint64_t after_p1[
     if (before.is_inf() || after.is_inf() || !hf::p1_on_curve(before) || !hf::p1_on_curve(after)) return KZG_OK;
     if (q.inf || !g2_in_subgroup(tau_g2)) return KZG_OK;
     *valid = vc_pair(before_p1, after_p1, q, hf::g2_generator());  // e(before, [tau]G2) == e(after, [1]G2)
+    return KZG_OK;
+}
+
+// ---- multilinear openings (multilinear_kernels.hip) ----------------------------------------------------
+// Every round runs on a slot its caller holds (reserve_slot), with the context's mutex, dropping it while it copies or waits.
+namespace {
+bool ml_multipliers(const uint64_t* vals, size_t count, MlMultipliers* out) {  // false: one of them is not below r
+    for (size_t i = 0; i < count; i++) {
+        hf::Fr v;
+        if (!fr_arg_below_r(vals + 4 * i, &v)) return false;
+        if (out) {
+            const Fr30 d = fr30_arg_from_mont256(v);
+            std::memcpy(out->m[i], d.d, sizeof d.d);
+        }
+    }
+    return true;
+}
+// r below r and outside {0, 1, -1}; zs: r, -r, r^2
+int ml_points(const uint64_t r[4], hf::Fr zs[3]) {
+    if (!fr_arg_below_r(r, &zs[0])) return KZG_ERR_INVALID_ARG;
+    zs[1] = hf::fr_sub(hf::Fr{{0, 0, 0, 0}}, zs[0]);
+    zs[2] = hf::fr_mul(zs[0], zs[0]);
+    if (zs[0].is_zero() || zs[0] == hf::kFrOne || zs[1] == hf::kFrOne) return KZG_ERR_INVALID_ARG;
+    return KZG_OK;
+}
+int ml_bad(kzg_ctx* ctx, const char* what, const char* why) {
+    if (ctx && !ctx->multi) ctx->last_error = std::string(what) + ": " + why;
+    return KZG_ERR_INVALID_ARG;
+}
+// the arguments the calls share, in the documented order (null where a call takes none; ptrs_ok: its other pointers)
+int ml_check(kzg_ctx* ctx, const char* what, bool ptrs_ok, size_t ell, const uint64_t* us, MlMultipliers* um, const uint64_t* r,
+             hf::Fr* zs, const uint64_t* gamma, hf::Fr* gf) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (!ptrs_ok) return ml_bad(ctx, what, "a null pointer");
+    if (ell < 1 || ell > KZG_ML_MAX_VARS) return ml_bad(ctx, what, "ell must be in [1, KZG_ML_MAX_VARS]");
+    if (us && !ml_multipliers(us, ell, um)) return ml_bad(ctx, what, "a coordinate of u is not below r");
+    hf::Fr tmp[3];
+    if (r && !fr_arg_below_r(r, &tmp[0])) return ml_bad(ctx, what, "r is not below the modulus");
+    if (gamma && !fr_arg_below_r(gamma, gf)) return ml_bad(ctx, what, "gamma is not below r");
+    if (r && ml_points(r, zs)) return ml_bad(ctx, what, "r is 0, 1 or -1: the points r, -r, r^2 collide");
+    return KZG_OK;
+}
+size_t ml_level_offset(size_t n, size_t i) { return n - (n >> (i - 1)); }  // of level i >= 1 in the pyramid, in values
+
+int ml_fold_on(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint32_t* d_evals, size_t ell, const MlMultipliers& um,
+               uint32_t* d_pyr, uint64_t* out_v) {
+    const size_t n = (size_t)1 << ell;
+    launch_ml_fold(s.stream, d_evals, (uint32_t)ell, um, d_pyr);
+    HIP_TRY(ctx, hipGetLastError());
+    int rc = KZG_OK;
+    if (out_v) rc = copy_unlocked(ctx, lk, s.stream, out_v, d_pyr + 8 * (n - 2), 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (v)");
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "multilinear fold");
+    return rc;
+}
+int ml_evaluations_on(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint32_t* d_evals, const uint32_t* d_pyr,
+                      size_t ell, const hf::Fr zs[3], uint64_t* out_ys) {
+    const size_t n = (size_t)1 << ell;
+    int rc = s.ctab.reserve(ctx, kCombineTabLen * sizeof(Fr30), s.stream);
+    if (rc == KZG_OK) rc = s.cvals.reserve(ctx, kCombineMax * 32, s.stream);
+    if (rc == KZG_OK) rc = s.cpart.reserve(ctx, 3 * ell * combine_tiles((uint32_t)n) * kCombinePartialWords * 4, s.stream);
+    if (rc) return rc;
+    Fr30* tab = (Fr30*)s.ctab.h;
+    combine_fill_powers(tab, zs[0]);
+    combine_fill_powers(tab + kCombineTabGamma, zs[2]);
+    HIP_TRY(ctx, hipMemcpyAsync(s.ctab.d, s.ctab.h, 2 * kCombineTabGamma * sizeof(Fr30), hipMemcpyHostToDevice, s.stream));
+    launch_ml_eval(s.stream, d_evals, d_pyr, (uint32_t)ell, s.ctab.dev<Fr30>(), s.cpart.dev(), s.cvals.dev());
+    HIP_TRY(ctx, hipGetLastError());
+    rc = sync_unlocked(ctx, lk, s.stream, "multilinear evaluations");
+    if (rc == KZG_OK) std::memcpy(out_ys, s.cvals.host(), 96 * ell);
+    return rc;
+}
+static_assert(2 * kCombineTabGamma <= kCombineTabLen && 3 * KZG_ML_MAX_VARS <= kCombineMax, "the slot's table and values hold a call");
+
+// One MSM job per level, bit for bit kzg_commit of that level.  A second slot is borrowed when one is idle, and the levels
+// alternate between the two, so that the sort of one level runs beside the accumulation of the previous one; the small levels
+// take the one-launch small-job path inside enqueue_msm.
+int ml_commit_folds_on(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot, const uint32_t* d_pyr, size_t ell, uint64_t* out_p1s) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    const size_t n = (size_t)1 << ell;
+    int slots[2] = {slot, ell > 2 ? reserve_slot(ctx, lk, false) : -1};
+    const int ns = slots[1] >= 0 ? 2 : 1;
+    size_t pending[2] = {0, 0};  // the level in flight on each slot, 0: none
+    auto collect = [&](int k) {
+        Slot& q = ctx->slots[slots[k]];
+        await_unlocked(lk, q);
+        const int rc = wait_locked(ctx, slots[k], out_p1s + 18 * (pending[k] - 1));
+        q.kind = SLOT_RESERVED;  // (wait_locked marked the slot idle under the mutex we hold; it stays this call's)
+        pending[k] = 0;
+        return rc;
+    };
+    int rc = KZG_OK;
+    for (size_t i = 1; i < ell && rc == KZG_OK; i++) {
+        const int k = (int)(i % (size_t)ns);
+        if (pending[k]) rc = collect(k);
+        if (rc) break;
+        rc = submit_commit_locked(ctx, slots[k], d_pyr + 8 * ml_level_offset(n, i), 1, n >> i, false, true);
+        if (rc == KZG_OK) pending[k] = i;
+    }
+    for (int k = 0; k < ns; k++)
+        if (pending[k]) {
+            const int rc2 = collect(k);  // (also after an error: nothing stays in flight)
+            if (rc == KZG_OK) rc = rc2;
+        }
+    if (slots[1] >= 0) release_owned(ctx, slots[1]);
+    return rc;
+}
+// F into the slot's staging buffer, then the three-point scan and the MSM of a multiproof.  The round has no claims to check:
+// F's own values at the points stand in for them.
+int ml_open_on(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, int slot, const uint32_t* d_evals, const uint32_t* d_pyr, size_t ell,
+               const hf::Fr zs[3], const hf::Fr& gamma, uint64_t out_p1[18]) {
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    const size_t n = (size_t)1 << ell;
+    Slot& s = ctx->slots[slot];
+    int rc = ensure_poly(ctx, s, n);
+    if (rc) return rc;
+    MlMultipliers gm;
+    hf::Fr g = hf::kFrOne;
+    for (size_t i = 0; i < KZG_ML_MAX_VARS; i++) {
+        const Fr30 d = fr30_arg_from_mont256(g);
+        std::memcpy(gm.m[i], d.d, sizeof d.d);
+        g = hf::fr_mul(g, gamma);
+    }
+    launch_ml_combine(s.stream, d_evals, d_pyr, (uint32_t)ell, gm, s.stage.dev());
+    HIP_TRY(ctx, hipGetLastError());
+    uint64_t z[12], y0[12] = {};
+    for (int p = 0; p < 3; p++) std::memcpy(z + 4 * p, zs[p].l, 32);
+    rc = submit_points_locked(ctx, slot, s.stage.dev(), n, z, y0, 3, true);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    s.pts_ys.assign(points_values(s, 3), points_values(s, 3) + 24);
+    rc = wait_locked(ctx, slot, out_p1);
+    s.kind = SLOT_RESERVED;  // (wait_locked marked the slot idle under the mutex we hold; the lease ends it)
+    return rc;
+}
+// a call's slot: the context's mutex (lk) taken, a slot reserved, its stream there
+int ml_begin(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, SlotLease& lease) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    lease.slot = reserve_slot(ctx, lk, true);
+    if (lease.slot < 0) return KZG_ERR_BUSY;
+    return ensure_slot_basics(ctx, ctx->slots[lease.slot]);
+}
+// the values of a host-pointer call into the slot's own buffers
+int ml_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const uint64_t* evals, size_t n) {
+    int rc = s.ml_in.reserve(ctx, n * 32, s.stream);
+    if (rc == KZG_OK) rc = s.ml_pyr.reserve(ctx, n * 32, s.stream);
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, s.ml_in.p, evals, n * 32, hipMemcpyHostToDevice, kCopyCoeffs);
+    return rc;
+}
+int ml_fold_host(kzg_ctx* ctx, const char* what, const uint64_t* evals, size_t ell, const uint64_t* us, uint64_t* out_pyr,
+                 uint64_t* out_v) {
+    MlMultipliers um;
+    int rc = ml_check(ctx, what, evals && us && (out_pyr || out_v), ell, us, &um, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (ctx->multi) {  // needs no SRS
+        kzg_ctx* kid = multi_kid(ctx->multi, 0);
+        return forwarded(ctx, kid, ml_fold_host(kid, what, evals, ell, us, out_pyr, out_v));
+    }
+    const size_t n = (size_t)1 << ell;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    Slot& s = ctx->slots[lease.slot];
+    rc = ml_upload(ctx, lk, s, evals, n);
+    if (rc == KZG_OK && out_pyr)
+        launch_ml_fold(s.stream, s.ml_in.dev(), (uint32_t)ell, um, s.ml_pyr.dev());
+    if (rc == KZG_OK && out_pyr) {
+        HIP_TRY(ctx, hipGetLastError());
+        rc = copy_unlocked(ctx, lk, s.stream, out_pyr, s.ml_pyr.p, (n - 1) * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (pyramid)");
+        if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "multilinear fold");
+    } else if (rc == KZG_OK) {
+        rc = ml_fold_on(ctx, lk, s, s.ml_in.dev(), ell, um, s.ml_pyr.dev(), out_v);
+    }
+    return rc;
+}
+}  // namespace
+
+int kzg_ml_fold(kzg_ctx* ctx, const uint64_t* evals, size_t ell, const uint64_t* us, uint64_t* out_pyramid) {
+    if (ctx && !out_pyramid) return ml_bad(ctx, "kzg_ml_fold", "a null pointer");
+    return ml_fold_host(ctx, "kzg_ml_fold", evals, ell, us, out_pyramid, nullptr);
+}
+int kzg_ml_evaluate(kzg_ctx* ctx, const uint64_t* evals, size_t ell, const uint64_t* us, uint64_t out_v[4]) {
+    return ml_fold_host(ctx, "kzg_ml_evaluate", evals, ell, us, nullptr, out_v);
+}
+
+int kzg_ml_fold_device(kzg_ctx* ctx, const void* d_evals, size_t ell, const uint64_t* us, void* d_pyramid, uint64_t out_v[4]) {
+    MlMultipliers um;
+    int rc = ml_check(ctx, "kzg_ml_fold_device", d_evals && us && d_pyramid && out_v, ell, us, &um, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    return ml_fold_on(ctx, lk, ctx->slots[lease.slot], (const uint32_t*)d_evals, ell, um, (uint32_t*)d_pyramid, out_v);
+}
+
+int kzg_ml_commit_folds_device(kzg_ctx* ctx, const void* d_pyramid, size_t ell, uint64_t* out_p1s) {
+    int rc = ml_check(ctx, "kzg_ml_commit_folds_device", d_pyramid && (out_p1s || ell == 1), ell, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr);
+    if (rc) return rc;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    return ml_commit_folds_on(ctx, lk, lease.slot, (const uint32_t*)d_pyramid, ell, out_p1s);
+}
+
+int kzg_ml_evaluations_device(kzg_ctx* ctx, const void* d_evals, const void* d_pyramid, size_t ell, const uint64_t r[4], uint64_t* out_ys) {
+    hf::Fr zs[3];
+    int rc = ml_check(ctx, "kzg_ml_evaluations_device", d_evals && d_pyramid && r && out_ys, ell, nullptr, nullptr, r, zs, nullptr, nullptr);
+    if (rc) return rc;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    return ml_evaluations_on(ctx, lk, ctx->slots[lease.slot], (const uint32_t*)d_evals, (const uint32_t*)d_pyramid, ell, zs, out_ys);
+}
+
+int kzg_ml_open_device(kzg_ctx* ctx, const void* d_evals, const void* d_pyramid, size_t ell, const uint64_t r[4], const uint64_t gamma[4],
+                       uint64_t out_p1[18]) {
+    hf::Fr zs[3], gf;
+    int rc = ml_check(ctx, "kzg_ml_open_device", d_evals && d_pyramid && r && gamma && out_p1, ell, nullptr, nullptr, r, zs, gamma, &gf);
+    if (rc) return rc;
+    KZG_SINGLE_DEVICE_ONLY(ctx);
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    return ml_open_on(ctx, lk, lease.slot, (const uint32_t*)d_evals, (const uint32_t*)d_pyramid, ell, zs, gf, out_p1);
+}
+
+int kzg_ml_open(kzg_ctx* ctx, const uint64_t* evals, size_t ell, const uint64_t* us, const uint64_t r[4], const uint64_t gamma[4],
+                uint64_t out_v[4], uint64_t* out_fold_p1s, uint64_t* out_ys, uint64_t out_p1[18]) {
+    MlMultipliers um;
+    hf::Fr zs[3], gf;
+    int rc = ml_check(ctx, "kzg_ml_open", evals && us && r && gamma && out_v && (out_fold_p1s || ell == 1) && out_ys && out_p1, ell, us, &um,
+                      r, zs, gamma, &gf);
+    if (rc) return rc;
+    if (ctx->multi) {
+        kzg_ctx* kid = whole_srs_kid(ctx, true, "kzg_ml_open needs");
+        if (!kid) return KZG_ERR_INVALID_ARG;
+        return forwarded(ctx, kid, kzg_ml_open(kid, evals, ell, us, r, gamma, out_v, out_fold_p1s, out_ys, out_p1));
+    }
+    const size_t n = (size_t)1 << ell;
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (!ctx->n || !ctx->slots_ready) return KZG_ERR_NO_SRS;
+    SlotLease lease{ctx, -1};
+    rc = ml_begin(ctx, lk, lease);
+    if (rc) return rc;
+    Slot& s = ctx->slots[lease.slot];
+    // the results reach the caller's memory only when every round succeeded
+    uint64_t v[4], w[18];
+    std::vector<uint64_t> folds(18 * (ell - 1)), ys(12 * ell);
+    rc = ml_upload(ctx, lk, s, evals, n);
+    if (rc == KZG_OK) rc = ml_fold_on(ctx, lk, s, s.ml_in.dev(), ell, um, s.ml_pyr.dev(), v);
+    if (rc == KZG_OK) rc = ml_commit_folds_on(ctx, lk, lease.slot, s.ml_pyr.dev(), ell, folds.data());
+    if (rc == KZG_OK) rc = ml_evaluations_on(ctx, lk, s, s.ml_in.dev(), s.ml_pyr.dev(), ell, zs, ys.data());
+    if (rc == KZG_OK) rc = ml_open_on(ctx, lk, lease.slot, s.ml_in.dev(), s.ml_pyr.dev(), ell, zs, gf, w);
+    if (rc) return rc;
+    std::memcpy(out_v, v, 32);
+    if (ell > 1) std::memcpy(out_fold_p1s, folds.data(), 144 * (ell - 1));
+    std::memcpy(out_ys, ys.data(), 96 * ell);
+    std::memcpy(out_p1, w, 144);
+    return KZG_OK;
+}
+
+int kzg_ml_verify(const uint64_t commitment_p1[18], size_t ell, const uint64_t* us, const uint64_t v[4], const uint64_t* fold_p1s,
+                  const uint64_t* ys, const uint64_t r[4], const uint64_t gamma[4], const uint64_t proof_p1[18], const void* setup_g1,
+                  size_t g1_stride_bytes, const void* setup_g2, size_t g2_stride_bytes, int* valid) {
+    if (!commitment_p1 || !us || !v || !ys || !r || !gamma || !proof_p1 || !setup_g1 || !setup_g2 || !valid) return KZG_ERR_INVALID_ARG;
+    if (ell < 1 || ell > KZG_ML_MAX_VARS || (!fold_p1s && ell > 1)) return KZG_ERR_INVALID_ARG;
+    hf::Fr zs[3], gf, vf;
+    if (!ml_multipliers(us, ell, nullptr) || !fr_arg_below_r(r, &zs[0]) || !fr_arg_below_r(gamma, &gf) || !fr_arg_below_r(v, &vf))
+        return KZG_ERR_INVALID_ARG;
+    if (ml_points(r, zs)) return KZG_ERR_INVALID_ARG;
+    // (*) for every level: 2 r f_(i+1)(r^2) = r (1 - u_i) (y_(i,0) + y_(i,1)) + u_i (y_(i,0) - y_(i,1)), f_ell(r^2) := v
+    bool star = true;
+    const hf::Fr two_r = hf::fr_add(zs[0], zs[0]);
+    for (size_t i = 0; i < ell; i++) {
+        hf::Fr y[3], u, next = vf;
+        for (int p = 0; p < 3; p++)
+            if (!fr_arg_below_r(ys + 4 * (3 * i + p), &y[p])) return KZG_ERR_INVALID_ARG;
+        if (i + 1 < ell && !fr_arg_below_r(ys + 4 * (3 * (i + 1) + 2), &next)) return KZG_ERR_INVALID_ARG;
+        std::memcpy(u.l, us + 4 * i, 32);
+        const hf::Fr lhs = hf::fr_mul(two_r, next);
+        const hf::Fr rhs = hf::fr_add(hf::fr_mul(hf::fr_mul(zs[0], hf::fr_sub(hf::kFrOne, u)), hf::fr_add(y[0], y[1])),
+                                      hf::fr_mul(u, hf::fr_sub(y[0], y[1])));
+        star = star && lhs == rhs;
+    }
+    std::vector<uint64_t> stack(18 * ell);
+    std::memcpy(stack.data(), commitment_p1, 144);
+    if (ell > 1) std::memcpy(stack.data() + 18, fold_p1s, 144 * (ell - 1));
+    const std::vector<uint32_t> set_of(ell, 0u);
+    const uint32_t set_len[1] = {3};
+    uint64_t z[12];
+    for (int p = 0; p < 3; p++) std::memcpy(z + 4 * p, zs[p].l, 32);
+    int ok = 0;
+    const int rc = kzg_verify_sets(stack.data(), ell, set_of.data(), set_len, 1, z, ys, gamma, proof_p1, setup_g1, g1_stride_bytes, setup_g2,
+                                   g2_stride_bytes, &ok);
+    if (rc) return rc;
+    *valid = star && ok ? 1 : 0;
     return KZG_OK;
 }
 

@@ -553,6 +553,26 @@ static_assert(sizeof(BlindColumn) == 56, "the device reads the records the host 
 void launch_blind_tail(hipStream_t s, const BlindColumn* d_cols, uint32_t ncols, uint32_t n, uint32_t ntail, const Fr30* d_pw,
                        uint32_t* d_out, uint32_t* d_y);
 
+// ---- multilinear_kernels.hip: folds, values and F of a multilinear opening ------------------------------
+constexpr uint32_t kMlMaxVars = 22;      // KZG_ML_MAX_VARS
+constexpr uint32_t kMlThreads = 256;     // lanes of a workgroup
+constexpr uint32_t kMlTile = 2048;       // consecutive values of the source level per workgroup of k_ml_fold
+constexpr uint32_t kMlLevels = 11;       // levels one launch of k_ml_fold writes: log2 of the tile
+// up to 22 multipliers (u_i, or gamma^i) as the digits of Fr30 records in multiplier form, passed to the kernels by value
+struct MlMultipliers {
+    int32_t m[kMlMaxVars][9];
+};
+// The pyramid of f (n = 2^ell canonical values at d_evals): levels f_1 .. f_ell, n - 1 canonical values at d_pyr, level i at
+// offset n - (n >> (i - 1)).  One launch for ell <= 11, two above.  d_pyr overlaps no input.
+void launch_ml_fold(hipStream_t s, const uint32_t* d_evals, uint32_t ell, const MlMultipliers& us, uint32_t* d_pyr);
+// d_ys[8 (3 i + p) ..] = f_i(r), f_i(-r), f_i(r^2) for i < ell, canonical.  d_tab: the 66 powers of r in launch_combine_eval's
+// layout, then the 66 powers of r^2; d_partial: 3 ell combine_tiles(n) records of kCombinePartialWords words.
+void launch_ml_eval(hipStream_t s, const uint32_t* d_evals, const uint32_t* d_pyr, uint32_t ell, const Fr30* d_tab,
+                    uint32_t* d_partial, uint32_t* d_ys);
+// d_f[j] = sum_{i < ell, j < n >> i} gam_i f_i[j] (gam_0 is not read: it is one), n canonical values; d_f overlaps no input
+void launch_ml_combine(hipStream_t s, const uint32_t* d_evals, const uint32_t* d_pyr, uint32_t ell, const MlMultipliers& gam,
+                       uint32_t* d_f);
+
 // ---- multi.hip: a context spanning several devices (SRS-range slices, RCCL exchange of the partials) ------------
 }  // namespace kzg
 #include <string>

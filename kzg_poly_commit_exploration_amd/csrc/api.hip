@@ -3892,26 +3892,46 @@ int kzg_quotient_lagrange(kzg_ctx* ctx, const uint64_t* evals, size_t n, const u
     return rc;
 }
 
-// ---- grand products: z_0 = 1, z_(i+1) = z_i A_i / B_i (grand_product_kernels.hip) ---------------------
-// The permutation form's scalars; null for the general form, whose columns are the factors themselves.
-struct GpScalars {
-    const uint64_t *shifts, *beta, *gamma;
+// ---- running products and running sums (grand_product_kernels.hip; lookup_kernels.hip, section 4.21) ----
+//     products:  z_0 = 1,   z_(i+1) = z_i A_i / B_i              sums:  phi_0 = 0,   phi_(i+1) = phi_i + sum_j a_j[i] / b_j[i]
+// One description for every form of either and one call frame per kind of entry point.  A call reserves gp_flags, gp_part, gp_in and
+// gp_z on its slot, runs three kernels on the slot's stream (run_enqueue: the one step that differs between the forms) and reads
+// the flag words: [0] the least index with a zero denominator (kGpNone = kLuNone: none), [8..15] the last value.
+enum RunForm { kGpGeneral = 0, kGpPerm, kLuGeneral, kLuLookupForm, kLuInverse };
+struct RunCall {  // the columns are host or device pointers as the caller's entry point says
+    RunForm form;
+    const void* a;         // products: the numerators, or the wires; sum: the numerators (may be null); lookup: the k lookup columns
+    const void* b;         // products: the denominators, or the sigmas; sum: the denominators; inverse: the values
+    const void *table, *mult;  // lookup form
+    const uint64_t* beta;  // lookup and permutation forms
+    size_t n, t, stride;   // t: columns of a and b (lookup form: k)
+    const uint64_t *shifts, *gamma;  // permutation form
+    uint32_t lg;                     // n = 2^lg: the permutation form and the commit calls
+    bool product() const { return form <= kGpPerm; }
+    const char* what() const { return product() ? "grand product" : "log-derivative sum"; }
+    const char* out_what() const { return product() ? "hipMemcpyAsync (z)" : "hipMemcpyAsync (phi)"; }
 };
-static bool gp_shape_ok(size_t n, size_t t, size_t stride) {
-    return n >= 1 && n <= ((size_t)1 << kNttMaxLog) && t >= 1 && t <= kGpMaxColumns && stride >= n;
+static_assert(kGpNone == kLuNone, "one convention for the flag word of both kinds");
+static bool run_shape_ok(size_t n, size_t t, size_t stride, size_t t_max) {
+    return n >= 1 && n <= ((size_t)1 << kNttMaxLog) && t >= 1 && t <= t_max && stride >= n;
 }
-// the slot's buffers for n indices (ctx->mu held, slot reserved); in_bytes: the packed columns of a host-pointer call
-static int gp_slot_ready(kzg_ctx* ctx, Slot& s, size_t n, size_t in_bytes, bool own_z) {
+// the columns a host-pointer call packs into the slot (stride n)
+static size_t run_packed_columns(const RunCall& c) {
+    return c.form == kLuLookupForm ? c.t + 2 : (c.form == kLuInverse ? 1 : (c.a ? 2 : 1) * c.t);
+}
+// the slot's buffers (ctx->mu held, slot reserved); packed: a host-pointer call; own_out: the output goes to the slot's gp_z
+static int run_slot_ready(kzg_ctx* ctx, Slot& s, const RunCall& c, bool packed, bool own_out) {
+    const size_t part = c.product() ? (size_t)gp_tiles(c.n) * kGpPartialWords : (size_t)lu_tiles(c.n) * kLuPartialWords;
     int rc = ensure_slot_basics(ctx, s);
     if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
-    if (rc == KZG_OK) rc = s.gp_part.reserve(ctx, (size_t)gp_tiles(n) * kGpPartialWords * 4, s.stream);
-    if (rc == KZG_OK && in_bytes) rc = s.gp_in.reserve(ctx, in_bytes, s.stream);
-    if (rc == KZG_OK && own_z) rc = s.gp_z.reserve(ctx, n * 32, s.stream);
+    if (rc == KZG_OK) rc = s.gp_part.reserve(ctx, part * 4, s.stream);
+    if (rc == KZG_OK && packed) rc = s.gp_in.reserve(ctx, run_packed_columns(c) * c.n * 32, s.stream);
+    if (rc == KZG_OK && own_out) rc = s.gp_z.reserve(ctx, c.n * 32, s.stream);
     return rc;
 }
 // t columns of n values each, column j at src + 4 j stride, packed to stride n at dst (the slot's stream, ctx->mu dropped meanwhile)
-static int gp_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, uint32_t* dst, const uint64_t* src, size_t n, size_t t,
-                     size_t stride) {
+static int upload_columns(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, uint32_t* dst, const uint64_t* src, size_t n, size_t t,
+                          size_t stride) {
     if (stride == n) return copy_unlocked(ctx, lk, s.stream, dst, src, t * n * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (columns)");
     for (size_t j = 0; j < t; j++) {
         int rc = copy_unlocked(ctx, lk, s.stream, dst + 8 * j * n, src + 4 * j * stride, n * 32, hipMemcpyHostToDevice,
@@ -3920,120 +3940,182 @@ static int gp_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, ui
     }
     return KZG_OK;
 }
-// the three kernels on the slot's stream: z into d_z, the results into the slot's gp_flags
-static int gp_enqueue(kzg_ctx* ctx, Slot& s, const uint32_t* d_a, const uint32_t* d_b, size_t n, size_t t, size_t stride,
-                      const GpScalars* perm, uint32_t lg, uint32_t* d_z) {
-    const Fr30 scale = fr30_arg_from_mont256(fr_pow2((uint32_t)(14 * t)));  // 2^(270 + 14 t): t images -> one multiplier
-    auto image = [](const hf::Fr& v) {
+// the three kernels of a call on device columns on the slot's stream: the output into d_out, the results into the slot's gp_flags
+static int run_enqueue(kzg_ctx* ctx, Slot& s, const RunCall& c, uint32_t* d_out) {
+    const size_t cols = c.form == kLuLookupForm ? c.t + 1 : (c.form == kLuInverse ? 1 : c.t);
+    const Fr30 scale = fr30_arg_from_mont256(fr_pow2((uint32_t)(14 * cols)));  // 2^(270 + 14 cols): cols images -> one multiplier
+    auto image = [](const uint64_t* v) {
         uint32_t l[8];
-        std::memcpy(l, v.l, 32);
+        std::memcpy(l, v, 32);
         return fr30_from_limbs(l);
     };
-    const GpOut out{d_z, s.gp_part.dev(), s.gp_flags.dev()};
-    if (!perm) {
-        launch_grand_product(s.stream, d_a, d_b, (uint32_t)n, (uint32_t)t, stride, scale, image(hf::kFrOne), out);
-    } else {
-        hf::Fr beta, gamma;
-        std::memcpy(beta.l, perm->beta, 32);
-        std::memcpy(gamma.l, perm->gamma, 32);
+    const Fr30 one = image(hf::kFrOne.l);
+    const uint32_t *a = (const uint32_t*)c.a, *b = (const uint32_t*)c.b, n = (uint32_t)c.n, t = (uint32_t)c.t;
+    const GpOut gp_out{d_out, s.gp_part.dev(), s.gp_flags.dev()};
+    const LuOut lu_out{d_out, s.gp_part.dev(), s.gp_flags.dev()};
+    if (c.form == kGpGeneral) {
+        launch_grand_product(s.stream, a, b, n, t, c.stride, scale, one, gp_out);
+    } else if (c.form == kGpPerm) {
+        hf::Fr beta, k;
+        std::memcpy(beta.l, c.beta, 32);
         Fr30 bk[kGpMaxColumns];
-        for (size_t j = 0; j < t; j++) {
-            hf::Fr k;
-            std::memcpy(k.l, perm->shifts + 4 * j, 32);
-            bk[j] = image(hf::fr_mul(beta, k));  // an image: its product with the twiddle (a multiplier) is added to f_j[i]
+        for (size_t j = 0; j < c.t; j++) {
+            std::memcpy(k.l, c.shifts + 4 * j, 32);
+            bk[j] = image(hf::fr_mul(beta, k).l);  // an image: its product with the twiddle (a multiplier) is added to f_j[i]
         }
-        launch_permutation_product(s.stream, d_a, d_b, lg, (uint32_t)t, stride, bk, fr30_arg_from_mont256(beta), image(gamma),
-                                   ctx->ntt_tw.p, scale, image(hf::kFrOne), out);
+        launch_permutation_product(s.stream, a, b, c.lg, t, c.stride, bk, fr30_arg_from_mont256(beta), image(c.gamma), ctx->ntt_tw.p, scale,
+                                   one, gp_out);
+    } else if (c.form == kLuGeneral) {
+        launch_logderivative_sum(s.stream, a, b, n, t, c.stride, scale, one, lu_out);
+    } else if (c.form == kLuLookupForm) {
+        launch_lookup_sum(s.stream, a, n, t, c.stride, (const uint32_t*)c.table, (const uint32_t*)c.mult, image(c.beta), scale, one, lu_out);
+    } else {
+        launch_batch_inverse(s.stream, b, n, scale, one, lu_out);
     }
     HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
-// after the stream was waited for: the status of the call, z_n, the index of a zero denominator
-static int gp_result(kzg_ctx* ctx, const Slot& s, uint64_t out_last[4], size_t* bad_index) {
+// a host-pointer call's columns packed into s.gp_in, then the kernels on those device columns
+static int run_packed(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const RunCall& c, uint32_t* d_out) {
+    uint32_t* d = s.gp_in.dev();
+    const size_t n = c.n, t = c.t;
+    RunCall dev = c;
+    dev.stride = n;
+    int rc = KZG_OK;
+    if (c.form == kLuLookupForm) {
+        dev.a = d;
+        dev.table = d + 8 * t * n;
+        dev.mult = d + 8 * (t + 1) * n;
+        rc = upload_columns(ctx, lk, s, d, (const uint64_t*)c.a, n, t, c.stride);
+        if (rc == KZG_OK) rc = upload_columns(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.table, n, 1, n);
+        if (rc == KZG_OK) rc = upload_columns(ctx, lk, s, d + 8 * (t + 1) * n, (const uint64_t*)c.mult, n, 1, n);
+    } else if (c.form == kLuInverse) {
+        dev.b = d;
+        rc = upload_columns(ctx, lk, s, d, (const uint64_t*)c.b, n, 1, n);
+    } else {  // two column sets, or the denominators alone
+        dev.b = d;
+        rc = upload_columns(ctx, lk, s, d, (const uint64_t*)c.b, n, t, c.stride);
+        if (rc == KZG_OK && c.a) {
+            dev.a = d + 8 * t * n;
+            rc = upload_columns(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.a, n, t, c.stride);
+        }
+    }
+    return rc ? rc : run_enqueue(ctx, s, dev, d_out);
+}
+// after the stream was waited for: the status of the call, the last value (out_last null: the inverse form, which has none), the
+// index of a zero denominator
+static int run_result(kzg_ctx* ctx, const Slot& s, const RunCall& c, uint64_t out_last[4], size_t* bad_index) {
     const uint32_t* h = s.gp_flags.host();
     if (bad_index) *bad_index = h[0] == kGpNone ? (size_t)-1 : (size_t)h[0];
     if (h[0] != kGpNone) {
-        ctx->last_error = "grand product: the denominator at index " + std::to_string(h[0]) + " is zero";
+        const char* sum = c.form == kLuInverse ? "batch inverse: the value at row " : "log-derivative sum: a denominator at row ";
+        ctx->last_error = (c.product() ? "grand product: the denominator at index " : sum) + std::to_string(h[0]) + " is zero";
         return KZG_ERR_INVALID_ARG;
     }
-    std::memcpy(out_last, h + 8, 32);
+    if (out_last) std::memcpy(out_last, h + 8, 32);
     return KZG_OK;
 }
-static int gp_host(kzg_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, size_t t, size_t stride, const GpScalars* perm,
-                   uint32_t lg, uint64_t* out_z, uint64_t out_last[4], size_t* bad_index) {
+// a host-pointer call: the columns packed into the slot, the output back through the slot's gp_z
+static int run_host(kzg_ctx* ctx, const RunCall& c, uint64_t* out, uint64_t out_last[4], size_t* bad_index) {
     std::unique_lock<std::mutex> lk(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = perm ? ensure_ntt(ctx) : KZG_OK;
+    int rc = c.form == kGpPerm ? ensure_ntt(ctx) : KZG_OK;
     if (rc) return rc;
     const int slot = reserve_slot(ctx, lk, true);
     if (slot < 0) return KZG_ERR_BUSY;
     SlotLease lease{ctx, slot};
     Slot& s = ctx->slots[slot];
-    rc = gp_slot_ready(ctx, s, n, 2 * t * n * 32, true);
-    if (rc) return rc;
-    uint32_t *d_a = s.gp_in.dev(), *d_b = d_a + 8 * t * n;
-    rc = gp_upload(ctx, lk, s, d_a, a, n, t, stride);
-    if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d_b, b, n, t, stride);
-    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, d_a, d_b, n, t, n, perm, lg, s.gp_z.dev());
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out_z, s.gp_z.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (z)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
-    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+    rc = run_slot_ready(ctx, s, c, true, true);
+    if (rc == KZG_OK) rc = run_packed(ctx, lk, s, c, s.gp_z.dev());
+    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out, s.gp_z.dev(), c.n * 32, hipMemcpyDeviceToHost, c.out_what());
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, c.what());
+    return rc ? rc : run_result(ctx, s, c, out_last, bad_index);
 }
-// the product on a slot the caller holds (ctx->mu held, the device current, the twiddles built when perm is given)
-static int gp_on_slot(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const void* d_a, const void* d_b, size_t n, size_t t,
-                      size_t stride, const GpScalars* perm, uint32_t lg, void* d_out_z, uint64_t out_last[4], size_t* bad_index) {
-    int rc = gp_slot_ready(ctx, s, n, 0, false);
-    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, (const uint32_t*)d_a, (const uint32_t*)d_b, n, t, stride, perm, lg, (uint32_t*)d_out_z);
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "grand product");
-    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
+static bool ranges_overlap(const void* out, size_t out_bytes, const void* in, size_t in_bytes) {  // (a null input overlaps nothing)
+    return in && (const char*)out < (const char*)in + in_bytes && (const char*)in < (const char*)out + out_bytes;
 }
-static int gp_device(kzg_ctx* ctx, const void* d_a, const void* d_b, size_t n, size_t t, size_t stride, const GpScalars* perm, uint32_t lg,
-                     void* d_out_z, uint64_t out_last[4], size_t* bad_index) {
-    const size_t span = ((t - 1) * stride + n) * 32;  // bytes a column set covers
-    for (const void* in : {d_a, d_b})
-        if ((const char*)d_out_z < (const char*)in + span && (const char*)in < (const char*)d_out_z + n * 32) {
-            ctx->last_error = "grand product: the output overlaps an input";
-            return KZG_ERR_INVALID_ARG;
-        }
+// a call on device columns on a slot the caller holds, with the context's mutex (*lk), the device current and the twiddles built
+// where the form reads them: the body of run_device, and a step of the circuit calls (sections 4.24, 4.26)
+static int run_on_slot(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const RunCall& c, void* d_out, uint64_t out_last[4],
+                       size_t* bad_index) {
+    int rc = run_slot_ready(ctx, s, c, false, false);
+    if (rc == KZG_OK) rc = run_enqueue(ctx, s, c, (uint32_t*)d_out);
+    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, c.what());
+    return rc ? rc : run_result(ctx, s, c, out_last, bad_index);
+}
+static int run_device(kzg_ctx* ctx, const RunCall& c, void* d_out, uint64_t out_last[4], size_t* bad_index) {
+    const size_t span = ((c.t - 1) * c.stride + c.n) * 32, one = c.n * 32;  // bytes a column set covers, bytes of one column
+    const bool columns = c.form != kLuInverse;
+    if ((columns && ranges_overlap(d_out, one, c.a, span)) || ranges_overlap(d_out, one, c.b, columns ? span : one) ||
+        ranges_overlap(d_out, one, c.table, one) || ranges_overlap(d_out, one, c.mult, one)) {
+        ctx->last_error = std::string(c.what()) + ": the output overlaps an input";
+        return KZG_ERR_INVALID_ARG;
+    }
     std::unique_lock<std::mutex> lk(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = perm ? ensure_ntt(ctx) : KZG_OK;
+    int rc = c.form == kGpPerm ? ensure_ntt(ctx) : KZG_OK;
     if (rc) return rc;
     const int slot = reserve_slot(ctx, lk, true);
     if (slot < 0) return KZG_ERR_BUSY;
     SlotLease lease{ctx, slot};
-    return gp_on_slot(ctx, lk, ctx->slots[slot], d_a, d_b, n, t, stride, perm, lg, d_out_z, out_last, bad_index);
+    return run_on_slot(ctx, lk, ctx->slots[slot], c, d_out, out_last, bad_index);
+}
+// a host-pointer call whose output is also committed over the Lagrange basis of n = 2^lg points: it goes to the slot's staging
+// buffer, where the MSM reads it, and comes back to the host only where `out` is given
+static int run_commit(kzg_ctx* ctx, const RunCall& c, uint64_t* out, uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    int rc = lagrange_ensure(ctx, lk, c.n, c.lg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = c.form == kGpPerm ? ensure_ntt(ctx) : KZG_OK;
+    if (rc) return rc;
+    const int slot = reserve_slot(ctx, lk, true);
+    if (slot < 0) return KZG_ERR_BUSY;
+    SlotLease lease{ctx, slot};  // (the basis stays until the submit, as for kzg_commit_lagrange)
+    Slot& s = ctx->slots[slot];
+    rc = run_slot_ready(ctx, s, c, true, false);
+    if (rc == KZG_OK) rc = ensure_poly(ctx, s, c.n);
+    if (rc) return rc;
+    rc = run_packed(ctx, lk, s, c, s.stage.dev());
+    if (rc == KZG_OK && out) rc = copy_unlocked(ctx, lk, s.stream, out, s.stage.dev(), c.n * 32, hipMemcpyDeviceToHost, c.out_what());
+    MsmBasis basis{};
+    if (rc == KZG_OK && !lagrange_basis(ctx, c.n, &basis)) rc = KZG_ERR_NO_SRS;
+    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, c.n, true, true, &basis);
+    if (rc) return rc;
+    await_unlocked(lk, s);
+    rc = wait_locked(ctx, slot, out_p1);
+    return rc ? rc : run_result(ctx, s, c, out_last, bad_index);
 }
 
 int kzg_grand_product(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_z,
                       uint64_t out_last[4], size_t* bad_index) {
-    if (!ctx || !nums || !dens || !out_z || !out_last || !gp_shape_ok(n, t, stride)) return KZG_ERR_INVALID_ARG;
+    if (!ctx || !nums || !dens || !out_z || !out_last || !run_shape_ok(n, t, stride, kGpMaxColumns)) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {  // needs no SRS
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
         return forwarded(ctx, kid, kzg_grand_product(kid, nums, dens, n, t, stride, out_z, out_last, bad_index));
     }
-    return gp_host(ctx, nums, dens, n, t, stride, nullptr, 0, out_z, out_last, bad_index);
+    return run_host(ctx, RunCall{kGpGeneral, nums, dens, nullptr, nullptr, nullptr, n, t, stride}, out_z, out_last, bad_index);
 }
 
 int kzg_grand_product_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_z,
                              uint64_t out_last[4], size_t* bad_index) {
     KZG_SINGLE_DEVICE_ONLY(ctx);
-    if (!ctx || !d_nums || !d_dens || !d_out_z || !out_last || !gp_shape_ok(n, t, stride)) return KZG_ERR_INVALID_ARG;
-    return gp_device(ctx, d_nums, d_dens, n, t, stride, nullptr, 0, d_out_z, out_last, bad_index);
+    if (!ctx || !d_nums || !d_dens || !d_out_z || !out_last || !run_shape_ok(n, t, stride, kGpMaxColumns)) return KZG_ERR_INVALID_ARG;
+    return run_device(ctx, RunCall{kGpGeneral, d_nums, d_dens, nullptr, nullptr, nullptr, n, t, stride}, d_out_z, out_last, bad_index);
 }
 
 int kzg_permutation_product(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
                             const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
                             uint64_t out_last[4], size_t* bad_index) {
     uint32_t lg = 0;
-    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_z || !out_last || !gp_shape_ok(n, t, stride) || !ntt_log(n, &lg))
+    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_z || !out_last || !run_shape_ok(n, t, stride, kGpMaxColumns) ||
+        !ntt_log(n, &lg))
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {  // needs no SRS
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
         return forwarded(ctx, kid, kzg_permutation_product(kid, wires, sigmas, n, t, stride, shifts, beta, gamma, out_z, out_last, bad_index));
     }
-    const GpScalars perm{shifts, beta, gamma};
-    return gp_host(ctx, wires, sigmas, n, t, stride, &perm, lg, out_z, out_last, bad_index);
+    return run_host(ctx, RunCall{kGpPerm, wires, sigmas, nullptr, nullptr, beta, n, t, stride, shifts, gamma, lg}, out_z, out_last, bad_index);
 }
 
 int kzg_permutation_product_device(kzg_ctx* ctx, const void* d_wires, const void* d_sigmas, size_t n, size_t t, size_t stride,
@@ -4041,18 +4123,19 @@ int kzg_permutation_product_device(kzg_ctx* ctx, const void* d_wires, const void
                                    uint64_t out_last[4], size_t* bad_index) {
     KZG_SINGLE_DEVICE_ONLY(ctx);
     uint32_t lg = 0;
-    if (!ctx || !d_wires || !d_sigmas || !shifts || !beta || !gamma || !d_out_z || !out_last || !gp_shape_ok(n, t, stride) ||
-        !ntt_log(n, &lg))
+    if (!ctx || !d_wires || !d_sigmas || !shifts || !beta || !gamma || !d_out_z || !out_last ||
+        !run_shape_ok(n, t, stride, kGpMaxColumns) || !ntt_log(n, &lg))
         return KZG_ERR_INVALID_ARG;
-    const GpScalars perm{shifts, beta, gamma};
-    return gp_device(ctx, d_wires, d_sigmas, n, t, stride, &perm, lg, d_out_z, out_last, bad_index);
+    return run_device(ctx, RunCall{kGpPerm, d_wires, d_sigmas, nullptr, nullptr, beta, n, t, stride, shifts, gamma, lg}, d_out_z, out_last,
+                      bad_index);
 }
 
 int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, size_t n, size_t t, size_t stride,
                            const uint64_t* shifts, const uint64_t beta[4], const uint64_t gamma[4], uint64_t* out_z,
                            uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index) {
     uint32_t lg = 0;
-    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_last || !out_p1 || !gp_shape_ok(n, t, stride) || !ntt_log(n, &lg))
+    if (!ctx || !wires || !sigmas || !shifts || !beta || !gamma || !out_last || !out_p1 || !run_shape_ok(n, t, stride, kGpMaxColumns) ||
+        !ntt_log(n, &lg))
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
         int rc = KZG_OK;
@@ -4061,225 +4144,65 @@ int kzg_permutation_commit(kzg_ctx* ctx, const uint64_t* wires, const uint64_t* 
                                                                  out_p1, bad_index))
                    : rc;
     }
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int rc = lagrange_ensure(ctx, lk, n, lg);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = ensure_ntt(ctx);
-    if (rc) return rc;
-    const int slot = reserve_slot(ctx, lk, true);
-    if (slot < 0) return KZG_ERR_BUSY;
-    SlotLease lease{ctx, slot};  // (the basis stays until the submit, as for kzg_commit_lagrange)
-    Slot& s = ctx->slots[slot];
-    rc = gp_slot_ready(ctx, s, n, 2 * t * n * 32, false);
-    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
-    if (rc) return rc;
-    // z goes to the slot's staging buffer, where the MSM over the Lagrange basis reads it
-    uint32_t *d_a = s.gp_in.dev(), *d_b = d_a + 8 * t * n;
-    const GpScalars perm{shifts, beta, gamma};
-    rc = gp_upload(ctx, lk, s, d_a, wires, n, t, stride);
-    if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d_b, sigmas, n, t, stride);
-    if (rc == KZG_OK) rc = gp_enqueue(ctx, s, d_a, d_b, n, t, n, &perm, lg, s.stage.dev());
-    if (rc == KZG_OK && out_z)
-        rc = copy_unlocked(ctx, lk, s.stream, out_z, s.stage.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (z)");
-    MsmBasis basis{};
-    if (rc == KZG_OK && !lagrange_basis(ctx, n, &basis)) rc = KZG_ERR_NO_SRS;
-    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true, &basis);
-    if (rc) return rc;
-    await_unlocked(lk, s);
-    rc = wait_locked(ctx, slot, out_p1);
-    return rc ? rc : gp_result(ctx, s, out_last, bad_index);
-}
-
-// ---- log-derivative sums: phi_0 = 0, phi_(i+1) = phi_i + sum_j a_j[i] / b_j[i] (lookup_kernels.hip) ------
-// The three forms of one call; the columns are host or device pointers as the caller's entry point says.
-enum LuForm { kLuGeneral = 0, kLuLookupForm = 1, kLuInverse = 2 };
-struct LuCall {
-    LuForm form;
-    const void* a;      // general: the numerators (may be null); lookup: the k lookup columns; inverse: unused
-    const void* b;      // general: the denominators; lookup: unused; inverse: the values
-    const void* table;  // lookup form
-    const void* mult;
-    const uint64_t* beta;
-    size_t n, t, stride;  // t: columns of a and b (lookup form: k)
-};
-static bool lu_shape_ok(size_t n, size_t t, size_t stride, size_t t_max) {
-    return n >= 1 && n <= ((size_t)1 << kNttMaxLog) && t >= 1 && t <= t_max && stride >= n;
-}
-static int lu_slot_ready(kzg_ctx* ctx, Slot& s, size_t n, size_t in_bytes, bool own_out) {
-    int rc = ensure_slot_basics(ctx, s);
-    if (rc == KZG_OK) rc = s.gp_flags.reserve(ctx, 64);
-    if (rc == KZG_OK) rc = s.gp_part.reserve(ctx, (size_t)lu_tiles(n) * kLuPartialWords * 4, s.stream);
-    if (rc == KZG_OK && in_bytes) rc = s.gp_in.reserve(ctx, in_bytes, s.stream);
-    if (rc == KZG_OK && own_out) rc = s.gp_z.reserve(ctx, n * 32, s.stream);
-    return rc;
-}
-// the columns a host-pointer call packs into the slot (stride n)
-static size_t lu_packed_columns(const LuCall& c) {
-    return c.form == kLuGeneral ? (c.a ? 2 : 1) * c.t : (c.form == kLuLookupForm ? c.t + 2 : 1);
-}
-// uploads the call's columns into s.gp_in and returns the call on those device columns
-static int lu_upload(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const LuCall& c, LuCall* dev) {
-    uint32_t* d = s.gp_in.dev();
-    const size_t n = c.n, t = c.t;
-    *dev = c;
-    dev->stride = n;
-    int rc = KZG_OK;
-    if (c.form == kLuGeneral) {
-        dev->b = d;
-        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.b, n, t, c.stride);
-        if (rc == KZG_OK && c.a) {
-            dev->a = d + 8 * t * n;
-            rc = gp_upload(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.a, n, t, c.stride);
-        }
-    } else if (c.form == kLuLookupForm) {
-        dev->a = d;
-        dev->table = d + 8 * t * n;
-        dev->mult = d + 8 * (t + 1) * n;
-        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.a, n, t, c.stride);
-        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d + 8 * t * n, (const uint64_t*)c.table, n, 1, n);
-        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, d + 8 * (t + 1) * n, (const uint64_t*)c.mult, n, 1, n);
-    } else {
-        dev->b = d;
-        rc = gp_upload(ctx, lk, s, d, (const uint64_t*)c.b, n, 1, n);
-    }
-    return rc;
-}
-// the three kernels on the slot's stream: the output into d_out, the results into the slot's gp_flags
-static int lu_enqueue(kzg_ctx* ctx, Slot& s, const LuCall& c, uint32_t* d_out) {
-    const size_t cols = c.form == kLuGeneral ? c.t : (c.form == kLuLookupForm ? c.t + 1 : 1);
-    const Fr30 scale = fr30_arg_from_mont256(fr_pow2((uint32_t)(14 * cols)));  // 2^(270 + 14 t): see the unit's header
-    auto image = [](const hf::Fr& v) {
-        uint32_t l[8];
-        std::memcpy(l, v.l, 32);
-        return fr30_from_limbs(l);
-    };
-    const LuOut out{d_out, s.gp_part.dev(), s.gp_flags.dev()};
-    const Fr30 one = image(hf::kFrOne);
-    if (c.form == kLuGeneral) {
-        launch_logderivative_sum(s.stream, (const uint32_t*)c.a, (const uint32_t*)c.b, (uint32_t)c.n, (uint32_t)c.t, c.stride, scale, one, out);
-    } else if (c.form == kLuLookupForm) {
-        hf::Fr beta;
-        std::memcpy(beta.l, c.beta, 32);
-        launch_lookup_sum(s.stream, (const uint32_t*)c.a, (uint32_t)c.n, (uint32_t)c.t, c.stride, (const uint32_t*)c.table,
-                          (const uint32_t*)c.mult, image(beta), scale, one, out);
-    } else {
-        launch_batch_inverse(s.stream, (const uint32_t*)c.b, (uint32_t)c.n, scale, one, out);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return KZG_OK;
-}
-// after the stream was waited for: the status of the call, phi_n, the row of a zero denominator
-static int lu_result(kzg_ctx* ctx, const Slot& s, LuForm form, uint64_t out_last[4], size_t* bad_index) {
-    const uint32_t* h = s.gp_flags.host();
-    if (bad_index) *bad_index = h[0] == kLuNone ? (size_t)-1 : (size_t)h[0];
-    if (h[0] != kLuNone) {
-        ctx->last_error = form == kLuInverse ? "batch inverse: the value at row " + std::to_string(h[0]) + " is zero"
-                                             : "log-derivative sum: a denominator at row " + std::to_string(h[0]) + " is zero";
-        return KZG_ERR_INVALID_ARG;
-    }
-    if (out_last) std::memcpy(out_last, h + 8, 32);
-    return KZG_OK;
-}
-static int lu_host(kzg_ctx* ctx, const LuCall& c, uint64_t* out, uint64_t out_last[4], size_t* bad_index) {
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int slot = reserve_slot(ctx, lk, true);
-    if (slot < 0) return KZG_ERR_BUSY;
-    SlotLease lease{ctx, slot};
-    Slot& s = ctx->slots[slot];
-    int rc = lu_slot_ready(ctx, s, c.n, lu_packed_columns(c) * c.n * 32, true);
-    if (rc) return rc;
-    LuCall dev;
-    rc = lu_upload(ctx, lk, s, c, &dev);
-    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, dev, s.gp_z.dev());
-    if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, out, s.gp_z.dev(), c.n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
-    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
-}
-static bool lu_overlaps(const void* out, size_t out_bytes, const void* in, size_t in_bytes) {
-    return in && (const char*)out < (const char*)in + in_bytes && (const char*)in < (const char*)out + out_bytes;
-}
-// a call on device columns on a slot the caller holds, with the context's mutex (*lk): the body of lu_device, and a step of the
-// circuit calls with a lookup table (section 4.26)
-static int lu_on_slot(kzg_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot& s, const LuCall& c, void* d_out, uint64_t out_last[4],
-                      size_t* bad_index) {
-    int rc = lu_slot_ready(ctx, s, c.n, 0, false);
-    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, c, (uint32_t*)d_out);
-    if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "log-derivative sum");
-    return rc ? rc : lu_result(ctx, s, c.form, out_last, bad_index);
-}
-static int lu_device(kzg_ctx* ctx, const LuCall& c, void* d_out, uint64_t out_last[4], size_t* bad_index) {
-    const size_t span = ((c.t - 1) * c.stride + c.n) * 32, one = c.n * 32;  // bytes a column set covers, bytes of one column
-    const bool columns = c.form != kLuInverse;
-    if ((columns && lu_overlaps(d_out, one, c.a, span)) || lu_overlaps(d_out, one, c.b, columns ? span : one) ||
-        lu_overlaps(d_out, one, c.table, one) || lu_overlaps(d_out, one, c.mult, one)) {
-        ctx->last_error = "log-derivative sum: the output overlaps an input";
-        return KZG_ERR_INVALID_ARG;
-    }
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int slot = reserve_slot(ctx, lk, true);
-    if (slot < 0) return KZG_ERR_BUSY;
-    SlotLease lease{ctx, slot};
-    return lu_on_slot(ctx, lk, ctx->slots[slot], c, d_out, out_last, bad_index);
+    return run_commit(ctx, RunCall{kGpPerm, wires, sigmas, nullptr, nullptr, beta, n, t, stride, shifts, gamma, lg}, out_z, out_last, out_p1,
+                      bad_index);
 }
 
 int kzg_logderivative_sum(kzg_ctx* ctx, const uint64_t* nums, const uint64_t* dens, size_t n, size_t t, size_t stride, uint64_t* out_phi,
                           uint64_t out_last[4], size_t* bad_index) {
-    if (!ctx || !dens || !out_phi || !out_last || !lu_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
+    if (!ctx || !dens || !out_phi || !out_last || !run_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {  // needs no SRS
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
         return forwarded(ctx, kid, kzg_logderivative_sum(kid, nums, dens, n, t, stride, out_phi, out_last, bad_index));
     }
-    return lu_host(ctx, LuCall{kLuGeneral, nums, dens, nullptr, nullptr, nullptr, n, t, stride}, out_phi, out_last, bad_index);
+    return run_host(ctx, RunCall{kLuGeneral, nums, dens, nullptr, nullptr, nullptr, n, t, stride}, out_phi, out_last, bad_index);
 }
 
 int kzg_logderivative_sum_device(kzg_ctx* ctx, const void* d_nums, const void* d_dens, size_t n, size_t t, size_t stride, void* d_out_phi,
                                  uint64_t out_last[4], size_t* bad_index) {
-    if (!ctx || !d_dens || !d_out_phi || !out_last || !lu_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
+    if (!ctx || !d_dens || !d_out_phi || !out_last || !run_shape_ok(n, t, stride, kLuMaxColumns)) return KZG_ERR_INVALID_ARG;
     KZG_SINGLE_DEVICE_ONLY(ctx);
-    return lu_device(ctx, LuCall{kLuGeneral, d_nums, d_dens, nullptr, nullptr, nullptr, n, t, stride}, d_out_phi, out_last, bad_index);
+    return run_device(ctx, RunCall{kLuGeneral, d_nums, d_dens, nullptr, nullptr, nullptr, n, t, stride}, d_out_phi, out_last, bad_index);
 }
 
 int kzg_lookup_sum(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
                    const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], size_t* bad_index) {
-    if (!ctx || !lookups || !table || !mult || !beta || !out_phi || !out_last || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1))
+    if (!ctx || !lookups || !table || !mult || !beta || !out_phi || !out_last || !run_shape_ok(n, k, stride, kLuMaxColumns - 1))
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {  // needs no SRS
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
         return forwarded(ctx, kid, kzg_lookup_sum(kid, lookups, n, k, stride, table, mult, beta, out_phi, out_last, bad_index));
     }
-    return lu_host(ctx, LuCall{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride}, out_phi, out_last, bad_index);
+    return run_host(ctx, RunCall{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride}, out_phi, out_last, bad_index);
 }
 
 int kzg_lookup_sum_device(kzg_ctx* ctx, const void* d_lookups, size_t n, size_t k, size_t stride, const void* d_table, const void* d_mult,
                           const uint64_t beta[4], void* d_out_phi, uint64_t out_last[4], size_t* bad_index) {
-    if (!ctx || !d_lookups || !d_table || !d_mult || !beta || !d_out_phi || !out_last || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1))
+    if (!ctx || !d_lookups || !d_table || !d_mult || !beta || !d_out_phi || !out_last || !run_shape_ok(n, k, stride, kLuMaxColumns - 1))
         return KZG_ERR_INVALID_ARG;
     KZG_SINGLE_DEVICE_ONLY(ctx);
-    return lu_device(ctx, LuCall{kLuLookupForm, d_lookups, nullptr, d_table, d_mult, beta, n, k, stride}, d_out_phi, out_last, bad_index);
+    return run_device(ctx, RunCall{kLuLookupForm, d_lookups, nullptr, d_table, d_mult, beta, n, k, stride}, d_out_phi, out_last, bad_index);
 }
 
 int kzg_batch_inverse(kzg_ctx* ctx, const uint64_t* vals, size_t n, uint64_t* out, size_t* bad_index) {
-    if (!ctx || !vals || !out || !lu_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
+    if (!ctx || !vals || !out || !run_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {  // needs no SRS
         kzg_ctx* kid = multi_kid(ctx->multi, 0);
         return forwarded(ctx, kid, kzg_batch_inverse(kid, vals, n, out, bad_index));
     }
-    return lu_host(ctx, LuCall{kLuInverse, nullptr, vals, nullptr, nullptr, nullptr, n, 1, n}, out, nullptr, bad_index);
+    return run_host(ctx, RunCall{kLuInverse, nullptr, vals, nullptr, nullptr, nullptr, n, 1, n}, out, nullptr, bad_index);
 }
 
 int kzg_batch_inverse_device(kzg_ctx* ctx, const void* d_vals, size_t n, void* d_out, size_t* bad_index) {
-    if (!ctx || !d_vals || !d_out || !lu_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
+    if (!ctx || !d_vals || !d_out || !run_shape_ok(n, 1, n, 1)) return KZG_ERR_INVALID_ARG;
     KZG_SINGLE_DEVICE_ONLY(ctx);
-    return lu_device(ctx, LuCall{kLuInverse, nullptr, d_vals, nullptr, nullptr, nullptr, n, 1, n}, d_out, nullptr, bad_index);
+    return run_device(ctx, RunCall{kLuInverse, nullptr, d_vals, nullptr, nullptr, nullptr, n, 1, n}, d_out, nullptr, bad_index);
 }
 
 int kzg_lookup_commit(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k, size_t stride, const uint64_t* table, const uint64_t* mult,
                       const uint64_t beta[4], uint64_t* out_phi, uint64_t out_last[4], uint64_t out_p1[18], size_t* bad_index) {
     uint32_t lg = 0;
-    if (!ctx || !lookups || !table || !mult || !beta || !out_last || !out_p1 || !lu_shape_ok(n, k, stride, kLuMaxColumns - 1) ||
+    if (!ctx || !lookups || !table || !mult || !beta || !out_last || !out_p1 || !run_shape_ok(n, k, stride, kLuMaxColumns - 1) ||
         !ntt_log(n, &lg))
         return KZG_ERR_INVALID_ARG;
     if (ctx->multi) {
@@ -4288,31 +4211,8 @@ int kzg_lookup_commit(kzg_ctx* ctx, const uint64_t* lookups, size_t n, size_t k,
         return kid ? forwarded(ctx, kid, kzg_lookup_commit(kid, lookups, n, k, stride, table, mult, beta, out_phi, out_last, out_p1, bad_index))
                    : rc;
     }
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    int rc = lagrange_ensure(ctx, lk, n, lg);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int slot = reserve_slot(ctx, lk, true);
-    if (slot < 0) return KZG_ERR_BUSY;
-    SlotLease lease{ctx, slot};  // (the basis stays until the submit, as for kzg_commit_lagrange)
-    Slot& s = ctx->slots[slot];
-    const LuCall c{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride};
-    rc = lu_slot_ready(ctx, s, n, lu_packed_columns(c) * n * 32, false);
-    if (rc == KZG_OK) rc = ensure_poly(ctx, s, n);
-    if (rc) return rc;
-    // phi goes to the slot's staging buffer, where the MSM over the Lagrange basis reads it
-    LuCall dev;
-    rc = lu_upload(ctx, lk, s, c, &dev);
-    if (rc == KZG_OK) rc = lu_enqueue(ctx, s, dev, s.stage.dev());
-    if (rc == KZG_OK && out_phi)
-        rc = copy_unlocked(ctx, lk, s.stream, out_phi, s.stage.dev(), n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
-    MsmBasis basis{};
-    if (rc == KZG_OK && !lagrange_basis(ctx, n, &basis)) rc = KZG_ERR_NO_SRS;
-    if (rc == KZG_OK) rc = submit_commit_locked(ctx, slot, s.stage.dev(), 1, n, true, true, &basis);
-    if (rc) return rc;
-    await_unlocked(lk, s);
-    rc = wait_locked(ctx, slot, out_p1);
-    return rc ? rc : lu_result(ctx, s, kLuLookupForm, out_last, bad_index);
+    return run_commit(ctx, RunCall{kLuLookupForm, lookups, nullptr, table, mult, beta, n, k, stride, nullptr, nullptr, lg}, out_phi, out_last,
+                      out_p1, bad_index);
 }
 
 // ---- multiplicities of a lookup through a hash table on the device (lookup_kernels.hip) -------------------
@@ -4386,7 +4286,7 @@ int lu_multiplicities(kzg_ctx* ctx, const void* table, size_t n_table, const voi
         if (rc == KZG_OK) rc = ctx->lu_ws.get(ctx, kLuWsMult, n_table * 32, &d_mult);
         if (rc == KZG_OK && out_rows) rc = ctx->lu_ws.get(ctx, kLuWsRows, k * n * 4, &d_rows);
         if (rc == KZG_OK) rc = copy_unlocked(ctx, lk, s.stream, d_table, table, n_table * 32, hipMemcpyHostToDevice, "hipMemcpyAsync (table)");
-        if (rc == KZG_OK) rc = gp_upload(ctx, lk, s, (uint32_t*)d_look, (const uint64_t*)lookups, n, k, stride);
+        if (rc == KZG_OK) rc = upload_columns(ctx, lk, s, (uint32_t*)d_look, (const uint64_t*)lookups, n, k, stride);
     }
     if (rc == KZG_OK) rc = lu_mult_enqueue(ctx, s, d_table, n_table, d_look, n, k, device ? stride : n, log_cap, d_mult, d_rows);
     if (rc) return rc;
@@ -4427,8 +4327,8 @@ int kzg_lookup_multiplicities_device(kzg_ctx* ctx, const void* d_table, size_t n
     const size_t span = ((k - 1) * stride + n) * 32;
     for (const void* out : {(const void*)d_out_mult, (const void*)d_out_rows}) {
         const size_t bytes = out == d_out_mult ? n_table * 32 : k * n * 4;
-        if (out && (lu_overlaps(out, bytes, d_table, n_table * 32) || lu_overlaps(out, bytes, d_lookups, span) ||
-                    (out == d_out_rows && lu_overlaps(out, bytes, d_out_mult, n_table * 32)))) {
+        if (out && (ranges_overlap(out, bytes, d_table, n_table * 32) || ranges_overlap(out, bytes, d_lookups, span) ||
+                    (out == d_out_rows && ranges_overlap(out, bytes, d_out_mult, n_table * 32)))) {
             ctx->last_error = "lookup multiplicities: an output overlaps an input or the other output";
             return KZG_ERR_INVALID_ARG;
         }
@@ -6274,7 +6174,7 @@ int kzg_circuit_lookup_columns(kzg_ctx* ctx, const kzg_circuit* circuit, const u
     if (rc == KZG_OK) rc = sync_unlocked(ctx, lk, s.stream, "circuit lookup columns");
     if (rc == KZG_OK) rc = lu_mult_verdict(ctx, s, bad_row);
     if (rc) return rc;
-    rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_f, nullptr, d_t, d_m, beta, n, 1, n}, d_phi, out_last, bad_row);
+    rc = run_on_slot(ctx, lk, s, RunCall{kLuLookupForm, d_f, nullptr, d_t, d_m, beta, n, 1, n}, d_phi, out_last, bad_row);
     if (rc) return rc;
     rc = copy_unlocked(ctx, lk, s.stream, out_phi, d_phi, n * 32, hipMemcpyDeviceToHost, "hipMemcpyAsync (phi)");
     return rc ? rc : sync_unlocked(ctx, lk, s.stream, "circuit lookup columns");
@@ -10143,7 +10043,7 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, ProofKind kind, const
         uint64_t last[4];
         size_t bad = (size_t)-1;
         if (nlk) {
-            rc = lu_on_slot(ctx, lk, s, LuCall{kLuLookupForm, d_vf, nullptr, d_vt, d_vm, beta.l, n, 1, n}, d_vphi, last, &bad);
+            rc = run_on_slot(ctx, lk, s, RunCall{kLuLookupForm, d_vf, nullptr, d_vt, d_vm, beta.l, n, 1, n}, d_vphi, last, &bad);
             if (rc) {
                 if (bad_row && bad != (size_t)-1) *bad_row = bad;
                 return rc;
@@ -10153,8 +10053,8 @@ int circuit_prove_impl(kzg_ctx* ctx, const kzg_circuit* c, ProofKind kind, const
                 return KZG_ERR_REMAINDER;
             }
         }
-        const GpScalars perm{c->shifts, beta.l, gamma.l};
-        rc = gp_on_slot(ctx, lk, s, d_v, c->values.dev() + 8 * (t + 2) * n, n, t, n, &perm, sh.lg_n, d_vz, last, &bad);
+        const RunCall perm{kGpPerm, d_v, c->values.dev() + 8 * (t + 2) * n, nullptr, nullptr, beta.l, n, t, n, c->shifts, gamma.l, sh.lg_n};
+        rc = run_on_slot(ctx, lk, s, perm, d_vz, last, &bad);
         if (rc) return rc;
         if (std::memcmp(last, hf::kFrOne.l, 32) != 0) {
             ctx->last_error = "circuit prove: the grand product does not return to one (z_n != 1): the copy constraints do not hold";

@@ -33,6 +33,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -41,48 +42,8 @@ namespace {
 constexpr uint32_t kBaryFinishThreads = 64;
 constexpr uint32_t kBaryNone = 0xffffffffu;
 
-__device__ __forceinline__ Fr30 bary_load_fr30(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-__device__ __forceinline__ Fr30 bary_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ Fr30 bary_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
-    return fr30_norm(r);
-}
-__device__ __forceinline__ bool bary_is_zero(const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
-}
-// w_n^i in multiplier form: lo x hi of the forward tables of w_(2^22)
-__device__ __forceinline__ Fr30 bary_root(const Fr30* __restrict__ tw, uint32_t i, uint32_t log_n) {
-    const uint32_t e = i << (kNttMaxLog - log_n);
-    return fr30_mul(bary_load_fr30(tw + kNttTableLen, e >> 11), bary_load_fr30(tw, e & (kNttTableLen - 1)));
-}
 // digit planes of 256 values in LDS
-struct BaryPlane {
-    int32_t d[kR9][kBaryThreads];
-};
-__device__ __forceinline__ void plane_put(BaryPlane& p, uint32_t t, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p.d[k][t] = v.d[k];
-}
-__device__ __forceinline__ Fr30 plane_get(const BaryPlane& p, uint32_t t) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = p.d[k][t];
-    return v;
-}
+using BaryPlane = Fr30Plane<kBaryThreads>;
 
 // The two walks over a lane's run, unrolled by recursion over the index so that the running products stay in registers
 // (the compiler leaves a loop of this size rolled, and an indexed array would live in scratch).
@@ -93,8 +54,8 @@ __device__ __forceinline__ void bary_forward(Fr30 (&p)[kBaryRun], const Fr30& z,
     const uint32_t i = base + (uint32_t)J * kBaryThreads;
     Fr30 d = one;
     if (i < n) {
-        d = bary_sub(z, bary_root(tw, i, log_n));
-        if (bary_is_zero(d)) {
+        d = fr30_sub(z, fr30_root(tw, i, log_n));
+        if (fr30_is_zero(d)) {
             atomicMin(hit, i);
             d = one;
         }
@@ -110,16 +71,16 @@ __device__ __forceinline__ void bary_backward(const Fr30 (&p)[kBaryRun], Fr30& i
                                               uint32_t n, uint32_t log_n) {
     const uint32_t i = base + (uint32_t)J * kBaryThreads;
     if (i < n) {
-        const Fr30 w = bary_root(tw, i, log_n);
-        Fr30 d = bary_sub(z, w);
-        const bool zero = bary_is_zero(d);
+        const Fr30 w = fr30_root(tw, i, log_n);
+        Fr30 d = fr30_sub(z, w);
+        const bool zero = fr30_is_zero(d);
         if (zero) d = one;
         Fr30 dinv = inv;
         if constexpr (J > 0) {
             dinv = fr30_mul(inv, p[J - 1]);
             inv = fr30_mul(inv, d);
         }
-        if (!zero) acc = fr30_add(acc, fr30_mul(fr30_mul(bary_load(f + 8 * (size_t)i), w), dinv));
+        if (!zero) acc = fr30_add(acc, fr30_mul(fr30_mul(fr30_load(f + 8 * (size_t)i), w), dinv));
     }
     if constexpr (J > 0) bary_backward<J - 1>(p, inv, acc, z, one, tw, f, base, n, log_n);
 }
@@ -135,7 +96,7 @@ __global__ void __launch_bounds__(kBaryThreads) k_bary_partial(const uint32_t* _
     const uint32_t t = threadIdx.x, tile = blockIdx.x % tiles, b = blockIdx.x / tiles;
     const uint32_t n = 1u << log_n, base = tile * kBaryTile + t;
     const uint32_t* f = evals + 8 * ((size_t)b << log_n);
-    const Fr30 z = bary_load_fr30(zs, b);
+    const Fr30 z = fr30_table(zs, b);
     const Fr30 one = fr30_const_one270();
     if (t == 0) hit_s = kBaryNone;
     __syncthreads();
@@ -187,8 +148,7 @@ __global__ void __launch_bounds__(kBaryThreads) k_bary_partial(const uint32_t* _
     if (t == 0) {
         acc = fr30_mul(acc, one);
         uint32_t* out = partial + (size_t)blockIdx.x * kBaryPartialWords;
-#pragma unroll
-        for (int k = 0; k < kR9; k++) out[k] = (uint32_t)acc.d[k];
+        fr30_put_digits(out, acc);
         out[kR9] = hit_s;
     }
 }
@@ -208,10 +168,7 @@ __global__ void __launch_bounds__(kBaryFinishThreads) k_bary_finish(const uint32
 #pragma unroll 1
     for (uint32_t q = t; q < tiles; q += kBaryFinishThreads) {
         const uint32_t* rec = partial + ((size_t)b * tiles + q) * kBaryPartialWords;
-        Fr30 v;
-#pragma unroll
-        for (int k = 0; k < kR9; k++) v.d[k] = (int32_t)rec[k];
-        acc = fr30_add(acc, v);
+        acc = fr30_add(acc, fr30_digits(rec));
         hit = min(hit, rec[kR9]);
     }
     if (hit != kBaryNone) atomicMin(&hit_s, hit);
@@ -235,10 +192,10 @@ __global__ void __launch_bounds__(kBaryFinishThreads) k_bary_finish(const uint32
         acc = fr30_add(acc, v);
     }
     const Fr30 one = fr30_const_one270();
-    Fr30 zn = bary_load_fr30(zs, b);
+    Fr30 zn = fr30_table(zs, b);
 #pragma unroll 1
     for (uint32_t q = 0; q < log_n; q++) zn = fr30_mul(zn, zn);
-    const Fr30 factor = fr30_mul(bary_sub(zn, one), inv_n);
+    const Fr30 factor = fr30_mul(fr30_sub(zn, one), inv_n);
     const Fr30 y = fr30_mul(fr30_mul(acc, one), factor);
     uint32_t l[8];
     fr30_to_limbs(y, l);

@@ -31,17 +31,6 @@ namespace {
 
 constexpr uint32_t kPatchThreads = 64;
 
-__device__ __forceinline__ Fr30 blind_load(const uint32_t* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    return cmb_from_u4(q[0], q[1]);
-}
-__device__ __forceinline__ Fr30 blind_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
-    return fr30_norm(r);
-}
-
 // cols: k columns, column c at cols + 8 c stride words, n coefficients each (canonical).  lo, hi: nb canonical values per column
 // (column c at + 8 c nb words).  Column c < k_hi becomes  f - lo (X^0 ..) + hi X^n  with zeros up to the stride; a column from
 // k_hi on only loses lo.  Every touched value is a canonical value plus and minus one canonical value: inside (-r, 2r), which
@@ -56,12 +45,12 @@ __global__ void __launch_bounds__(kPatchThreads) k_blind_patch(uint32_t* cols, u
     // every touched index has ONE owner, which forms it from the column's old value and the two blinders: lane i < nb owns index
     // i where that is below n, lane nb + i owns index n + i (which at n < nb is also a low index: it loses blo[n + i] there)
     if (l < nb && l < n) {
-        cmb_store_canonical(col + 8 * (uint64_t)l, blind_sub(blind_load(col + 8 * (uint64_t)l), blind_load(blo + 8 * l)));
+        fr30_store(col + 8 * (uint64_t)l, fr30_sub(fr30_load(col + 8 * (uint64_t)l), fr30_load(blo + 8 * l)));
     } else if (high && l >= nb && l < 2 * nb) {
         const uint64_t idx = (uint64_t)n + (l - nb);
-        Fr30 v = blind_load(bhi + 8 * (l - nb));
-        if (idx < nb) v = blind_sub(v, blind_load(blo + 8 * idx));
-        cmb_store_canonical(col + 8 * idx, v);
+        Fr30 v = fr30_load(bhi + 8 * (l - nb));
+        if (idx < nb) v = fr30_sub(v, fr30_load(blo + 8 * idx));
+        fr30_store(col + 8 * idx, v);
     }
     if (high) {
         for (uint64_t idx = (uint64_t)n + nb + l; idx < stride; idx += kPatchThreads) {
@@ -97,17 +86,17 @@ __global__ void __launch_bounds__(kCombineThreads) k_blind_tail(const BlindColum
                 w.d[d] = cols[k].mult[d];
                 neg.d[d] = -w.d[d];
             }
-            if (is_tail && l < cols[k].tail_len) delta = fr30_mac(delta, blind_load(cols[k].tail + 8 * (uint64_t)l), w);
-            if (idx < kBlindLow && cols[k].low) delta = fr30_mac(delta, blind_load(cols[k].low + 8 * idx), neg);
+            if (is_tail && l < cols[k].tail_len) delta = fr30_mac(delta, fr30_load(cols[k].tail + 8 * (uint64_t)l), w);
+            if (idx < kBlindLow && cols[k].low) delta = fr30_mac(delta, fr30_load(cols[k].low + 8 * idx), neg);
         }
         delta = fr30_sum_reduce(delta);
         Fr30 v = delta;
-        if (idx < n) v = fr30_add(v, blind_load(out + 8 * idx));  // |v| < 0.51 r + r: inside (-r, 2r)
-        cmb_store_canonical(out + 8 * idx, v);
-        delta = fr30_mul(delta, cmb_table(pw, is_tail ? l : ntail + low_i));
+        if (idx < n) v = fr30_add(v, fr30_load(out + 8 * idx));  // |v| < 0.51 r + r: inside (-r, 2r)
+        fr30_store(out + 8 * idx, v);
+        delta = fr30_mul(delta, fr30_table(pw, is_tail ? l : ntail + low_i));
     }
     const Fr30 total = cmb_workgroup_sum(delta, lds);
-    if (l == 0) cmb_store_canonical(y, fr30_sum_reduce(fr30_add(total, blind_load(y))));
+    if (l == 0) fr30_store(y, fr30_sum_reduce(fr30_add(total, fr30_load(y))));
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 // tests pin its kernels' registers).
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -31,18 +32,6 @@ constexpr int kBpScanWords = kBpBlock * kR9;               // LDS words of the e
 
 // value = value * multiplier + value (Horner step), carry-normalised
 KZG_DEV Fr30 bp_mul_add(const Fr30& h, const Fr30& mult, const Fr30& c) { return fr30_norm(fr30_add_raw(fr30_mul(h, mult), c)); }
-KZG_DEV Fr30 bp_from_u4(const uint4& lo, const uint4& hi) {
-    const uint32_t l[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return fr30_from_limbs(l);
-}
-// canonical 8 x u32 of a lazy value in (-r, 2r)
-KZG_DEV void bp_store_canonical(uint32_t* __restrict__ p, const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
 
 }  // namespace
 
@@ -74,7 +63,7 @@ __global__ void __launch_bounds__(kBpBlock) k_blobproof_quotients(const uint32_t
             const uint4* q = reinterpret_cast<const uint4*>(coeffs + (size_t)idx * 8);
             const uint4 lo = q[0], hi = q[1];
             if (idx >= 1 && ((lo.x | lo.y | lo.z | lo.w) | (hi.x | hi.y | hi.z | hi.w)) != 0u) nz = true;
-            c = bp_from_u4(lo, hi);
+            c = fr30_from_u4(lo, hi);
         }
         h = bp_mul_add(h, z, c);
     }
@@ -108,7 +97,7 @@ __global__ void __launch_bounds__(kBpBlock) k_blobproof_quotients(const uint32_t
         if (t < 8 || (t >= 24)) flags[t] = w;  // (words 8..23 are written below by lane 0)
     }
     if (t == 0) {
-        bp_store_canonical(flags + 8, fr30_mul(h, fr30_const_one270()));  // S[0] = P(z), brought under r / 2 by a product with one
+        fr30_store(flags + 8, fr30_mul(h, fr30_const_one270()));  // S[0] = P(z), brought under r / 2 by a product with one
         const uint4* q = reinterpret_cast<const uint4*>(coeffs);
         reinterpret_cast<uint4*>(flags + 16)[0] = q[0];
         reinterpret_cast<uint4*>(flags + 16)[1] = q[1];
@@ -126,8 +115,8 @@ __global__ void __launch_bounds__(kBpBlock) k_blobproof_quotients(const uint32_t
         const uint32_t idx = base + k;
         if (idx < n) {
             const uint4* q = reinterpret_cast<const uint4*>(coeffs + (size_t)idx * 8);
-            h = bp_mul_add(h, z, bp_from_u4(q[0], q[1]));  // a product plus a canonical coefficient
-            if (idx >= 1) bp_store_canonical(qout + (size_t)(idx - 1) * 8, h);
+            h = bp_mul_add(h, z, fr30_from_u4(q[0], q[1]));  // a product plus a canonical coefficient
+            if (idx >= 1) fr30_store(qout + (size_t)(idx - 1) * 8, h);
         } else {
             h = fr30_mul(h, z);  // (past the end: h is zero and stays zero)
         }

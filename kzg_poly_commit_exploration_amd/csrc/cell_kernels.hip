@@ -25,6 +25,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -32,30 +33,6 @@ namespace {
 
 constexpr uint32_t kCellThreads = 256;
 
-__device__ __forceinline__ Fr30 cell_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void cell_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 cell_tw(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-// w_N^e (e < N = 2^log_n) in multiplier form from the forward tables lo[2048], hi[2048]
-__device__ __forceinline__ Fr30 cell_root_pow(const Fr30* __restrict__ tw, uint32_t log_n, uint32_t e) {
-    const uint32_t e22 = e << (kNttMaxLog - log_n);
-    return fr30_mul(cell_tw(tw + kNttTableLen, e22 >> 11), cell_tw(tw, e22 & (kNttTableLen - 1)));
-}
 __device__ __forceinline__ Fr30 cell_horner(const Fr30& h, const Fr30& a, const Fr30& x) {
     return fr30_norm(fr30_add_raw(fr30_mul(h, a), x));
 }
@@ -97,10 +74,10 @@ __global__ void __launch_bounds__(kCellThreads) k_cells_chunks(CellJob J) {
     if (t >= J.lanes) return;
     const CellLane L = cell_lane(J, t);
     const uint32_t cell = J.first_cell + L.p;
-    const Fr30 a = cell_root_pow(J.tw, J.log_n, cell << J.log_l);  // a_j = w_N^(j l), j l < N
+    const Fr30 a = fr30_root(J.tw, cell << J.log_l, J.log_n);  // a_j = w_N^(j l), j l < N
     Fr30 h = fr30_zero();
-    for (uint32_t k = L.k1; k-- > L.k0;) h = cell_horner(h, a, cell_load(J.c + 8 * ((uint64_t)L.r + ((uint64_t)(k + 1) << J.log_l))));
-    cell_store(J.agg + 8 * t, h);
+    for (uint32_t k = L.k1; k-- > L.k0;) h = cell_horner(h, a, fr30_load(J.c + 8 * ((uint64_t)L.r + ((uint64_t)(k + 1) << J.log_l))));
+    fr30_store(J.agg + 8 * t, h);
 }
 
 __global__ void __launch_bounds__(kCellThreads) k_cells_apply(CellJob J) {
@@ -113,17 +90,17 @@ __global__ void __launch_bounds__(kCellThreads) k_cells_apply(CellJob J) {
     // carry: Horner over the aggregates of the chunks above, step a_j^Lc
     Fr30 h = fr30_zero();
     {
-        const Fr30 a_lc = cell_root_pow(J.tw, J.log_n, (uint32_t)(((uint64_t)cell << (J.log_l + J.log_lc)) & mask));
+        const Fr30 a_lc = fr30_root(J.tw, (uint32_t)(((uint64_t)cell << (J.log_l + J.log_lc)) & mask), J.log_n);
         const uint64_t row = (uint64_t)L.p * J.U;
         for (uint32_t v = J.U; v-- > L.u + 1;)
-            h = cell_horner(h, a_lc, cell_load(J.agg + 8 * (((row + v) << J.log_l) + L.r)));
+            h = cell_horner(h, a_lc, fr30_load(J.agg + 8 * (((row + v) << J.log_l) + L.r)));
     }
-    const Fr30 a = cell_root_pow(J.tw, J.log_n, cell << J.log_l);
+    const Fr30 a = fr30_root(J.tw, cell << J.log_l, J.log_n);
     uint32_t* q = J.q + 8 * (uint64_t)L.p * J.stride;
     for (uint32_t k = L.k1; k-- > L.k0;) {
         const uint64_t i = (uint64_t)L.r + ((uint64_t)k << J.log_l);
-        h = cell_horner(h, a, cell_load(J.c + 8 * (i + (1u << J.log_l))));
-        cell_store(q + 8 * i, h);
+        h = cell_horner(h, a, fr30_load(J.c + 8 * (i + (1u << J.log_l))));
+        fr30_store(q + 8 * i, h);
     }
 }
 

@@ -53,42 +53,13 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
 namespace {
 
 static_assert(kPqTile == 256, "one coset point per lane of a 256-lane workgroup");
-
-__device__ __forceinline__ Fr30 ck_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void ck_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 ck_tab(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-// w^e (e < 2^22) from the twiddles lo[i] = w^i, hi[i] = w^(2048 i), multiplier form
-__device__ __forceinline__ Fr30 ck_pow22(const Fr30* __restrict__ t, uint32_t e) {
-    return fr30_mul(ck_tab(t + kNttTableLen, e >> 11), ck_tab(t, e & (kNttTableLen - 1)));
-}
-__device__ __forceinline__ Fr30 ck_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) r.d[k] = a.d[k] - b.d[k];
-    return fr30_norm(r);
-}
 
 struct CkArgs {
     const uint32_t* wires;   // t columns of N values, column j at + 8 j stride words (the call's workspace)
@@ -116,35 +87,35 @@ __global__ void __launch_bounds__(kPqTile) k_ck_constraints(CkArgs in, uint32_t*
     const uint32_t i = blockIdx.x * kPqTile + threadIdx.x;
     if (i >= N) return;
     const uint32_t ir = (i + in.rot) & (N - 1);
-    const Fr30 zi = ck_load(in.z + 8 * (size_t)i);
+    const Fr30 zi = fr30_load(in.z + 8 * (size_t)i);
     // S = q_C + PI + G' + alpha^2 (z_i - 1) L0_i
-    Fr30 sum = fr30_mul(fr30_mul(ck_sub(zi, in.one), ck_load(in.l0 + 8 * (size_t)i)), in.alpha2);
-    sum = fr30_add(ck_load(in.q_const + 8 * (size_t)i), sum);
-    if (in.pi) sum = fr30_add(ck_load(in.pi + 8 * (size_t)i), sum);
-    if (in.gate) sum = fr30_add(ck_load(in.gate + 8 * (size_t)i), sum);
+    Fr30 sum = fr30_mul(fr30_mul(fr30_sub(zi, in.one), fr30_load(in.l0 + 8 * (size_t)i)), in.alpha2);
+    sum = fr30_add(fr30_load(in.q_const + 8 * (size_t)i), sum);
+    if (in.pi) sum = fr30_add(fr30_load(in.pi + 8 * (size_t)i), sum);
+    if (in.gate) sum = fr30_add(fr30_load(in.gate + 8 * (size_t)i), sum);
     // the two running products and the gate's products over the columns
-    Fr30 a = zi, b = ck_load(in.z + 8 * (size_t)ir);
+    Fr30 a = zi, b = fr30_load(in.z + 8 * (size_t)ir);
     Fr30 p = fr30_zero(), f0 = fr30_zero();
-    const Fr30 w = ck_pow22(in.tw, i << (kNttMaxLog - in.log_N));
+    const Fr30 w = fr30_root(in.tw, i, in.log_N);
     const uint32_t* pf = in.wires + 8 * (size_t)i;
     const uint32_t* pq = in.q_lin + 8 * (size_t)i;
     const uint32_t* ps = in.sigmas + 8 * (size_t)i;
 #pragma unroll 1
     for (uint32_t j = 0; j < in.t; j++) {
-        const Fr30 f = ck_load(pf);
-        p = fr30_mac(p, ck_load(pq), f);                                 // q_j f_j: X 2^242
+        const Fr30 f = fr30_load(pf);
+        p = fr30_mac(p, fr30_load(pq), f);                                 // q_j f_j: X 2^242
         if (j == 0) f0 = f;
-        if (j == 1) p = fr30_mac(p, fr30_mul(fr30_mul(f0, f), in.k14), ck_load(in.q_mul + 8 * (size_t)i));  // q_M f_0 f_1
+        if (j == 1) p = fr30_mac(p, fr30_mul(fr30_mul(f0, f), in.k14), fr30_load(in.q_mul + 8 * (size_t)i));  // q_M f_0 f_1
         const Fr30 fg = fr30_add(f, in.gamma);                           // [0, 2 r)
         a = fr30_mul(a, fr30_add(fg, fr30_mul(in.bkg[j], w)));           // the factor (-0.51 r, 2.51 r): an operand only
-        b = fr30_mul(b, fr30_add(fg, fr30_mul(ck_load(ps), in.beta)));
+        b = fr30_mul(b, fr30_add(fg, fr30_mul(fr30_load(ps), in.beta)));
         pf += 8 * in.stride;
         pq += 8 * (size_t)N;
         ps += 8 * (size_t)N;
     }
     sum = fr30_add(sum, fr30_mul(p, in.k14));                            // |p| < 4.002 r: an operand only
-    sum = fr30_add(sum, fr30_mul(ck_sub(a, b), in.alpha1));              // (-1.501 r, 4.501 r): an operand only
-    ck_store(out + 8 * (size_t)i, fr30_mul(sum, ck_load(in.zinv + 8 * (size_t)(i & (in.rot - 1)))));
+    sum = fr30_add(sum, fr30_mul(fr30_sub(a, b), in.alpha1));              // (-1.501 r, 4.501 r): an operand only
+    fr30_store(out + 8 * (size_t)i, fr30_mul(sum, fr30_load(in.zinv + 8 * (size_t)(i & (in.rot - 1)))));
 }
 
 }  // namespace

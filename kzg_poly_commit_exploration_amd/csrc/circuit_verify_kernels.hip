@@ -33,7 +33,7 @@
 // x 2^270, in which everything is computed: a product of two multipliers is a multiplier.  A value leaves as the plain integer
 // x = fr30_to_limbs(fr30_mul(v, 1)), canonical, which is what glv_split_device and the rows of k_vc_fr_sum take.
 // Bounds: every product returns |v| <= 0.5001 r + |a b| / 2^270 and takes carry-normalised digits (one operand may be a raw sum of
-// two).  Every sum here is carry-normalised (fr30_add, cvb_sub) and has at most 2t + 3 <= 17 terms of magnitude <= 0.5001 r
+// two).  Every sum here is carry-normalised (fr30_add, fr30_sub) and has at most 2t + 3 <= 17 terms of magnitude <= 0.5001 r
 // (t <= kPqMaxColumns = 7; g0 + g1, the constant of G1: the three terms of r's constant, 2t - 1 subtractions, g1) before it feeds a
 // product: below 8.6 r < 2^258, far inside |a| |b| < 2^528 and the top digit's 2^30.  The custom terms (g <= kCgMaxTerms) are
 // products only.  A negation is digit-wise and keeps the digit bounds, which are symmetric.  PI's running sum is brought back under
@@ -51,6 +51,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 #include "g1_30.hip.h"
 
 namespace kzg {
@@ -159,24 +160,9 @@ __device__ __forceinline__ Fr30 cvb_mul(const Fr30& a, const Fr30& b) {
     __builtin_amdgcn_sched_barrier(0);
     return r;
 }
-__device__ __forceinline__ Fr30 cvb_ld9(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
 // a blst_fr image at p (32 bytes, 32-byte aligned) into the multiplier form: one product with 2^284
 __device__ __forceinline__ Fr30 cvb_ld_m(const uint32_t* __restrict__ p, const Fr30& k284) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return cvb_mul(fr30_from_limbs(l), k284);
-}
-__device__ __forceinline__ Fr30 cvb_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
-    return fr30_norm(r);
+    return cvb_mul(fr30_load(p), k284);
 }
 __device__ __forceinline__ Fr30 cvb_neg(const Fr30& a) {
     Fr30 r;
@@ -186,18 +172,8 @@ __device__ __forceinline__ Fr30 cvb_neg(const Fr30& a) {
 }
 // the plain integer of a multiplier-form value, canonical
 __device__ __forceinline__ void cvb_plain(const Fr30& a, uint32_t l[8]) { fr30_to_limbs(cvb_mul(a, fr30_small(1)), l); }
-__device__ __forceinline__ bool cvb_is_zero(const Fr30& a) {
-    uint32_t l[8];
-    cvb_plain(a, l);
-    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
-}
-__device__ __forceinline__ void cvb_store_plain(uint32_t* __restrict__ p, const Fr30& a) {
-    uint32_t l[8];
-    cvb_plain(a, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
+__device__ __forceinline__ bool cvb_is_zero(const Fr30& a) { return fr30_is_zero(cvb_mul(a, fr30_small(1))); }
+__device__ __forceinline__ void cvb_store_plain(uint32_t* __restrict__ p, const Fr30& a) { fr30_store(p, cvb_mul(a, fr30_small(1))); }
 __device__ __forceinline__ void cvb_store_glv(Glv* __restrict__ dst, const Glv& g) {
     uint4* q = reinterpret_cast<uint4*>(dst);
     q[0] = make_uint4((uint32_t)g.k1[0], (uint32_t)(g.k1[0] >> 32), (uint32_t)g.k1[1], (uint32_t)(g.k1[1] >> 32));
@@ -211,19 +187,7 @@ __device__ __forceinline__ void cvb_emit_glv(Glv* dst, const Fr30* a) {
 }
 
 // digit planes of 64 values in LDS
-struct CvbPlane {
-    int32_t d[kR9][kCvbThreads];
-};
-__device__ __forceinline__ void cvb_put(CvbPlane& p, uint32_t t, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p.d[k][t] = v.d[k];
-}
-__device__ __forceinline__ Fr30 cvb_get(const CvbPlane& p, uint32_t t) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = p.d[k][t];
-    return v;
-}
+using CvbPlane = Fr30Plane<kCvbThreads>;
 // 1 / d for the nonzero d (multiplier form) of each of the workgroup's 64 lanes, which all call: inclusive product scans from
 // both ends (six steps of two products), lane 0 inverts the product of all 64 -- ONE fr30_inv -- and lane t takes
 // inv x (the lanes before it) x (the lanes after it).  Ends with a barrier, so that the planes can be used again.
@@ -233,15 +197,15 @@ __device__ __forceinline__ Fr30 cvb_group_inverse(const Fr30& d, CvbPlane (&pre)
     uint32_t cur = 0;
 #pragma unroll 1
     for (uint32_t o = 1; o < kCvbThreads; o <<= 1) {
-        cvb_put(pre[cur], t, mp);
-        cvb_put(suf[cur], t, ms);
+        plane_put(pre[cur], t, mp);
+        plane_put(suf[cur], t, ms);
         __syncthreads();
-        if (t >= o) mp = cvb_mul(cvb_get(pre[cur], t - o), mp);
-        if (t + o < kCvbThreads) ms = cvb_mul(ms, cvb_get(suf[cur], t + o));
+        if (t >= o) mp = cvb_mul(plane_get(pre[cur], t - o), mp);
+        if (t + o < kCvbThreads) ms = cvb_mul(ms, plane_get(suf[cur], t + o));
         cur ^= 1;
     }
-    cvb_put(pre[cur], t, mp);
-    cvb_put(suf[cur], t, ms);
+    plane_put(pre[cur], t, mp);
+    plane_put(suf[cur], t, ms);
     if (t == 0) {  // ms of lane 0 is the product of all
         const Fr30 inv = fr30_inv(ms);
 #pragma unroll
@@ -251,8 +215,8 @@ __device__ __forceinline__ Fr30 cvb_group_inverse(const Fr30& d, CvbPlane (&pre)
     Fr30 inv;
 #pragma unroll
     for (int k = 0; k < kR9; k++) inv.d[k] = inv_s[k];
-    if (t > 0) inv = cvb_mul(inv, cvb_get(pre[cur], t - 1));
-    if (t + 1 < kCvbThreads) inv = cvb_mul(inv, cvb_get(suf[cur], t + 1));
+    if (t > 0) inv = cvb_mul(inv, plane_get(pre[cur], t - 1));
+    if (t + 1 < kCvbThreads) inv = cvb_mul(inv, plane_get(suf[cur], t + 1));
     __syncthreads();
     return inv;
 }
@@ -268,20 +232,20 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_public(const uint32_t* __re
     __shared__ int32_t inv_s[kR9];
     __shared__ uint32_t hit_s;
     const uint32_t t = threadIdx.x, k = blockIdx.x;
-    const Fr30 k284 = cvb_ld9(consts, kCvbK284), one = fr30_const_one270();
+    const Fr30 k284 = fr30_table(consts, kCvbK284), one = fr30_const_one270();
     const Fr30 z = cvb_ld_m(chal + 8 * ((size_t)5 * k + 3), k284);
     const uint32_t* f = pub + 8 * (size_t)k * stride;
     if (t == 0) hit_s = 0xffffffffu;
     Fr30 wcur = one;  // w^t by the six bits of t
     {
-        Fr30 base = cvb_ld9(consts, kCvbW);
+        Fr30 base = fr30_table(consts, kCvbW);
 #pragma unroll 1
         for (uint32_t bit = 0; bit < 6; bit++) {
             if ((t >> bit) & 1) wcur = cvb_mul(wcur, base);
             base = cvb_mul(base, base);
         }
     }
-    const Fr30 w64 = cvb_ld9(consts, kCvbW64);
+    const Fr30 w64 = fr30_table(consts, kCvbW64);
     __syncthreads();
     Fr30 acc = fr30_zero();
 #pragma unroll 1
@@ -290,7 +254,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_public(const uint32_t* __re
         bool live = i < n_public;
         Fr30 d = one;
         if (live) {
-            d = cvb_mul(cvb_sub(z, wcur), one);
+            d = cvb_mul(fr30_sub(z, wcur), one);
             if (cvb_is_zero(d)) {
                 atomicMin(&hit_s, i);
                 d = one;
@@ -302,7 +266,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_public(const uint32_t* __re
         wcur = cvb_mul(wcur, w64);
     }
     // the 64 lanes' sums through LDS (cvb_group_inverse ended with a barrier; without public rounds nothing used the planes)
-    cvb_put(pre[0], t, acc);
+    plane_put(pre[0], t, acc);
     __syncthreads();
     if (t != 0) return;
     if (hit_s != 0xffffffffu) {
@@ -312,11 +276,11 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_public(const uint32_t* __re
         return;
     }
 #pragma unroll 1
-    for (uint32_t q = 1; q < kCvbThreads; q++) acc = fr30_add(acc, cvb_get(pre[0], q));
+    for (uint32_t q = 1; q < kCvbThreads; q++) acc = fr30_add(acc, plane_get(pre[0], q));
     Fr30 zn = z;
 #pragma unroll 1
     for (uint32_t q = 0; q < lg_n; q++) zn = cvb_mul(zn, zn);
-    const Fr30 v = cvb_mul(cvb_mul(acc, one), cvb_mul(cvb_sub(zn, one), cvb_ld9(consts, kCvbInvN)));
+    const Fr30 v = cvb_mul(cvb_mul(acc, one), cvb_mul(fr30_sub(zn, one), fr30_table(consts, kCvbInvN)));
 #pragma unroll
     for (int q = 0; q < kR9; q++) out[k].d[q] = v.d[q];
 }
@@ -331,7 +295,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_lin(const uint32_t* __restr
     __shared__ int32_t inv_s[kR9];
     const uint32_t lane = threadIdx.x, k = blockIdx.x * kCvbThreads + lane;
     const bool active = k < count;
-    const Fr30 k284 = cvb_ld9(consts, kCvbK284), one = fr30_const_one270();
+    const Fr30 k284 = fr30_table(consts, kCvbK284), one = fr30_const_one270();
     const uint32_t* ch = chal + 8 * (size_t)5 * (active ? k : 0);
     const uint32_t* ev = evals + 8 * (size_t)2 * t * (active ? k : 0);
     const Fr30 ze = cvb_ld_m(ch + 24, k284);
@@ -339,24 +303,24 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_lin(const uint32_t* __restr
 #pragma unroll 1
     for (uint32_t q = 0; q < lg_n; q++) zn = cvb_mul(zn, zn);
     // L_0(zeta) = Z / (n (zeta - 1)), and 1 at zeta = 1
-    Fr30 d = cvb_mul(cvb_sub(ze, one), one);
+    Fr30 d = cvb_mul(fr30_sub(ze, one), one);
     const bool is_one = cvb_is_zero(d);
     if (is_one || !active) d = one;
     const Fr30 dinv = cvb_group_inverse(d, pre, suf, inv_s, lane);
     if (!active) return;
-    const Fr30 l0 = is_one ? one : cvb_mul(cvb_mul(cvb_sub(zn, one), cvb_ld9(consts, kCvbInvN)), dinv);
+    const Fr30 l0 = is_one ? one : cvb_mul(cvb_mul(fr30_sub(zn, one), fr30_table(consts, kCvbInvN)), dinv);
     const Fr30 be = cvb_ld_m(ch, k284), ga = cvb_ld_m(ch + 8, k284), al = cvb_ld_m(ch + 16, k284);
     Fr30 A = one, B = cvb_ld_m(ev + 8 * (2 * t - 1), k284);
 #pragma unroll 1
     for (uint32_t j = 0; j < t; j++) {
         const Fr30 ag = fr30_add(cvb_ld_m(ev + 8 * j, k284), ga);
-        A = cvb_mul(A, fr30_add(ag, cvb_mul(cvb_mul(be, cvb_ld9(consts, kCvbShifts + j)), ze)));
+        A = cvb_mul(A, fr30_add(ag, cvb_mul(cvb_mul(be, fr30_table(consts, kCvbShifts + j)), ze)));
         if (j + 1 < t) B = cvb_mul(B, fr30_add(ag, cvb_mul(be, cvb_ld_m(ev + 8 * (t + j), k284))));
     }
     const Fr30 a2l = cvb_mul(cvb_mul(al, al), l0), aB = cvb_mul(al, B);
     const Fr30 sc_z = fr30_add(cvb_mul(al, A), a2l), sc_sig = cvb_neg(cvb_mul(aB, be));
-    Fr30 konst = pim ? cvb_ld9(pim, k) : fr30_zero();
-    konst = cvb_sub(cvb_sub(konst, cvb_mul(aB, fr30_add(cvb_ld_m(ev + 8 * (t - 1), k284), ga))), a2l);
+    Fr30 konst = pim ? fr30_table(pim, k) : fr30_zero();
+    konst = fr30_sub(fr30_sub(konst, cvb_mul(aB, fr30_add(cvb_ld_m(ev + 8 * (t - 1), k284), ga))), a2l);
     Fr30* out = lin + 4 * (size_t)k;
 #pragma unroll
     for (int q = 0; q < kR9; q++) {
@@ -389,7 +353,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
     const uint64_t id = (uint64_t)blockIdx.x * kCvbThreads + threadIdx.x;
     const uint32_t k = (uint32_t)(id / Q), q = (uint32_t)(id % Q);
     if (k >= count) return;
-    const Fr30 k284 = cvb_ld9(consts, kCvbK284), one = fr30_const_one270();
+    const Fr30 k284 = fr30_table(consts, kCvbK284), one = fr30_const_one270();
     const uint32_t* ch = chal + 8 * (size_t)5 * k;
     const uint32_t* ev = evals + 8 * (size_t)2 * t * k;
     const Fr30 r = cvb_ld_m(rho + 8 * (size_t)k, k284);
@@ -401,11 +365,11 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
         val = cvb_pow(cvb_ld_m(ch + 32, k284), q + 1);
         gd = glv + (size_t)k * per + q;
     } else if (q == t) {
-        val = cvb_ld9(lin, 4 * k + 1);
+        val = fr30_table(lin, 4 * k + 1);
         gd = glv + (size_t)k * per + q;
     } else if (q < per) {  // chunk c = q - t - 1: -Z zeta^(c n)
-        const Fr30 zn = cvb_ld9(lin, 4 * k);
-        val = cvb_mul(cvb_neg(cvb_sub(zn, one)), cvb_pow(zn, q - t - 1));
+        const Fr30 zn = fr30_table(lin, 4 * k);
+        val = cvb_mul(cvb_neg(fr30_sub(zn, one)), cvb_pow(zn, q - t - 1));
         gd = glv + (size_t)k * per + q;
     } else if (q == per) {
         val = cvb_pow(cvb_ld_m(ch + 32, k284), 2 * t);
@@ -413,8 +377,8 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
     } else if (q < per + 5) {  // the second stage: -zeta w, -zeta, -zeta^2 w on D, E, F for P0 and zeta (1 + w) on F for P1; no rho
         const uint32_t j = q - per - 1;
         const Fr30 ze = cvb_ld_m(ch + 24, k284);
-        const Fr30 mzw = cvb_neg(cvb_mul(ze, cvb_ld9(consts, kCvbW)));
-        val = j == 0 ? mzw : (j == 1 ? cvb_neg(ze) : (j == 2 ? cvb_mul(mzw, ze) : cvb_mul(ze, cvb_ld9(consts, kCvbW1))));
+        const Fr30 mzw = cvb_neg(cvb_mul(ze, fr30_table(consts, kCvbW)));
+        val = j == 0 ? mzw : (j == 1 ? cvb_neg(ze) : (j == 2 ? cvb_mul(mzw, ze) : cvb_mul(ze, fr30_table(consts, kCvbW1))));
         scale = one;
         gd = s2 + 4 * (size_t)k + j;
     } else {  // the key side: A_0k's coefficient of key commitment j; G1 (j = nkey) also takes A_1k's constant
@@ -422,7 +386,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
         const bool p0 = jj < nk;
         rd = rows + 8 * (((size_t)k << log_l) + jj);
         const Fr30 ze = cvb_ld_m(ch + 24, k284);
-        const Fr30 mzw = cvb_neg(cvb_mul(ze, cvb_ld9(consts, kCvbW)));
+        const Fr30 mzw = cvb_neg(cvb_mul(ze, fr30_table(consts, kCvbW)));
         if (p0) scale = cvb_mul(r, mzw);
         if (j < t) {
             val = cvb_ld_m(ev + 8 * j, k284);
@@ -433,7 +397,7 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
         } else if (j < 2 * t + 1) {  // sigma_i, i = j - t - 2, with v^(1 + t + i)
             val = cvb_pow(cvb_ld_m(ch + 32, k284), j - 1);
         } else if (j == 2 * t + 1) {
-            val = cvb_ld9(lin, 4 * k + 2);
+            val = fr30_table(lin, 4 * k + 2);
         } else if (j < nkey) {  // the custom selector s = j - 2 t - 2 with prod_i abar_i^p[s][i]
             const uint32_t sx = j - 2 * t - 2;
             val = one;
@@ -445,11 +409,11 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_scalars(const uint32_t* __r
             }
         } else {  // G1: g0 = the constant of r - sum_(0 < i < 2t) v^i y_i with A_0k's factor, g1 = -v^(2t) z(zeta w) with A_1k's (-zeta)
             const Fr30 v = cvb_ld_m(ch + 32, k284);
-            Fr30 g0 = cvb_ld9(lin, 4 * k + 3), vp = one;
+            Fr30 g0 = fr30_table(lin, 4 * k + 3), vp = one;
 #pragma unroll 1
             for (uint32_t i = 1; i < 2 * t; i++) {
                 vp = cvb_mul(vp, v);
-                g0 = cvb_sub(g0, cvb_mul(vp, cvb_ld_m(ev + 8 * (i - 1), k284)));
+                g0 = fr30_sub(g0, cvb_mul(vp, cvb_ld_m(ev + 8 * (i - 1), k284)));
             }
             const Fr30 g1 = cvb_neg(cvb_mul(cvb_mul(vp, v), cvb_ld_m(ev + 8 * (2 * t - 1), k284)));
             if (p0) {  // rho (-zeta w g0 - zeta g1)
@@ -474,7 +438,6 @@ __global__ void __launch_bounds__(kCvbThreads) k_cvb_key_split(const uint32_t* _
     const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     cvb_store_glv(out + j, glv_split_device(l));
 }
-
 
 // lane (k, j) = (lane >> 2, lane & 3), k < count.  D, E, F: count XYZZ records each; s: 4 count split scalars, record 4 k + j;
 // p0: 3 count records (proof k's terms at 3 k ..), p1: count records

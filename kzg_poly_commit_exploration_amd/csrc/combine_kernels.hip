@@ -40,7 +40,7 @@ template <int M>
 __device__ __forceinline__ void cmb_steps(Fr30 (&acc)[kCombineRun], Fr30& h, const uint4 (&lo)[kCombineRun],
                                           const uint4 (&hi)[kCombineRun], const Fr30& g, const Fr30& z256, uint64_t base,
                                           uint32_t n) {
-    Fr30 c = cmb_from_u4(lo[M], hi[M]);
+    Fr30 c = fr30_from_u4(lo[M], hi[M]);
     if (base + (uint64_t)M * kCombineThreads >= n) c = fr30_zero();
     acc[M] = fr30_mac(acc[M], c, g);
     h = fr30_add_raw(fr30_mul(h, z256), c);
@@ -49,7 +49,7 @@ __device__ __forceinline__ void cmb_steps(Fr30 (&acc)[kCombineRun], Fr30& h, con
 template <int M>
 __device__ __forceinline__ void cmb_store_f(const Fr30 (&acc)[kCombineRun], uint32_t* f, uint64_t base, uint32_t n) {
     const uint64_t idx = base + (uint64_t)M * kCombineThreads;
-    if (idx < n) cmb_store_canonical(f + 8 * idx, fr30_sum_reduce(acc[M]));
+    if (idx < n) fr30_store(f + 8 * idx, fr30_sum_reduce(acc[M]));
     if constexpr (M + 1 < RUN) cmb_store_f<M + 1>(acc, f, base, n);
 }
 
@@ -65,8 +65,8 @@ __global__ void __launch_bounds__(kCombineThreads) k_combine_eval(const uint32_t
     const uint32_t l = threadIdx.x, tile = blockIdx.x, tiles = gridDim.x;
     const uint64_t base = (uint64_t)tile * kCombineTile + l;  // index of the lane's first coefficient
     // z^l = z^(16 (l >> 4)) z^(l & 15), a multiplier again
-    const Fr30 zl = fr30_mul(cmb_table(tab, kCombineTabPa + (l >> 4)), cmb_table(tab, kCombineTabPb + (l & 15)));
-    const Fr30 z256 = cmb_table(tab, kCombineTabZ256);
+    const Fr30 zl = fr30_mul(fr30_table(tab, kCombineTabPa + (l >> 4)), fr30_table(tab, kCombineTabPb + (l & 15)));
+    const Fr30 z256 = fr30_table(tab, kCombineTabZ256);
     // The accumulators.  Bound (fr30.hip.h, fr30_mac): each starts as zero or a canonical value and takes at most
     // KZG_MAX_COMBINE = 256 products c * gamma^i / 2^270 with c < 2^256 and the multiplier canonical (< r): every product is
     // below 0.5001 r + r / 2^14 in magnitude, the sum below 129.1 r, its top digit below kR9SumTopBound = 2^22; digits 0..7
@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_combine_eval(const uint32_t
         acc[m] = fr30_zero();
         if (carry && idx < n) {
             const uint4* q = reinterpret_cast<const uint4*>(f) + 2 * idx;
-            acc[m] = cmb_from_u4(q[0], q[1]);
+            acc[m] = fr30_from_u4(q[0], q[1]);
         }
     }
 #pragma unroll 1
@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_combine_eval(const uint32_t
             lo[m] = p[0];
             hi[m] = p[1];
         }
-        const Fr30 g = cmb_table(gam, i);
+        const Fr30 g = fr30_table(gam, i);
         Fr30 h = fr30_zero();
         cmb_steps<RUN - 1>(acc, h, lo, hi, g, z256, base, n);
         const Fr30 e = cmb_workgroup_sum(fr30_mul(h, zl), lds);
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_combine_eval_finish(const u
     const uint32_t l = threadIdx.x, i = blockIdx.x;
     const uint32_t* rec = partial + (size_t)i * tiles * kCombinePartialWords;
     const Fr30 y = cmb_tiles_sum(rec, tiles, tab, lds);
-    if (l == 0) cmb_store_canonical(out + 8 * (size_t)i, fr30_sum_reduce(y));
+    if (l == 0) fr30_store(out + 8 * (size_t)i, fr30_sum_reduce(y));
 }
 
 // ---- openings at several point sets (kzg_open_sets) ---------------------------------------------------
@@ -139,8 +139,8 @@ __global__ void __launch_bounds__(kCombineThreads) k_sets_combine(const uint32_t
     __shared__ int32_t lds[kR9][4];
     const uint32_t l = threadIdx.x, tile = blockIdx.x, tiles = gridDim.x;
     const uint64_t base = (uint64_t)tile * kCombineTile + l;
-    const Fr30 zl = fr30_mul(cmb_table(tab, kCombineTabPa + (l >> 4)), cmb_table(tab, kCombineTabPb + (l & 15)));
-    const Fr30 z256 = cmb_table(tab, kCombineTabZ256);
+    const Fr30 zl = fr30_mul(fr30_table(tab, kCombineTabPa + (l >> 4)), fr30_table(tab, kCombineTabPb + (l & 15)));
+    const Fr30 z256 = fr30_table(tab, kCombineTabZ256);
     Fr30 acc[kCombineRun];
 #pragma unroll
     for (int m = 0; m < RUN; m++) {
@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_sets_combine(const uint32_t
         acc[m] = fr30_zero();
         if (carry && idx < n) {
             const uint4* q = reinterpret_cast<const uint4*>(g) + 2 * idx;
-            acc[m] = cmb_from_u4(q[0], q[1]);
+            acc[m] = fr30_from_u4(q[0], q[1]);
         }
     }
 #pragma unroll 1
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_sets_combine(const uint32_t
             lo[m] = p[0];
             hi[m] = p[1];
         }
-        const Fr30 w = cmb_table(mult, j);
+        const Fr30 w = fr30_table(mult, j);
         Fr30 h = fr30_zero();
         cmb_steps<RUN - 1>(acc, h, lo, hi, w, z256, base, n);
         const Fr30 e = cmb_workgroup_sum(fr30_mul(h, zl), lds);

@@ -1,31 +1,15 @@
 // combine_lanes.hip.h -- what the streaming sums over 256-lane tiles share (combine_kernels.hip: k_combine_eval, k_sets_combine,
-// k_combine_eval_finish; linearise_kernels.hip: k_lin_combine, k_lin_finish): table and coefficient loads, the canonical store,
-// the workgroup sum of 256 lane values, and the sum over a polynomial's tile records.  Device code only; every function is inlined.
+// k_combine_eval_finish; linearise_kernels.hip: k_lin_combine, k_lin_finish): the workgroup sum of 256 lane values and the sum over a polynomial's
+// tile records.  Table and coefficient loads and the canonical store are fr30_lanes.hip.h's, which every Fr kernel unit shares.
+// Device code only; every function is inlined.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
-
-__device__ __forceinline__ Fr30 cmb_table(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-__device__ __forceinline__ Fr30 cmb_from_u4(const uint4& a, const uint4& b) {
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void cmb_store_canonical(uint32_t* p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
 
 // the digits of another lane of the row (DPP control CTRL) or of the wave (xor MASK) added to this lane's, one carry pass
 // each: both operands are carry-normalised, so the raw sum stays within 2^30 + 8 and the top digit only grows (below
@@ -81,7 +65,7 @@ static_assert(kCombineThreads == 256, "cmb_workgroup_sum adds four wave totals")
 __device__ __forceinline__ Fr30 cmb_tiles_sum(const uint32_t* __restrict__ rec, uint32_t tiles, const Fr30* __restrict__ tab,
                                               int32_t (*lds)[4]) {
     const uint32_t l = threadIdx.x;
-    const Fr30 w256 = cmb_table(tab, kCombineTabW256);
+    const Fr30 w256 = fr30_table(tab, kCombineTabW256);
     Fr30 h = fr30_zero();
     if (l < tiles) {
         const uint32_t top = (tiles - 1 - l) / kCombineThreads;  // the lane's tiles are l + 256 m, m <= top
@@ -95,7 +79,7 @@ __device__ __forceinline__ Fr30 cmb_tiles_sum(const uint32_t* __restrict__ rec, 
             v.d[8] = (int32_t)c.x;
             h = fr30_add_raw(fr30_mul(h, w256), v);
         }
-        h = fr30_mul(h, fr30_mul(cmb_table(tab, kCombineTabWa + (l >> 4)), cmb_table(tab, kCombineTabWb + (l & 15))));
+        h = fr30_mul(h, fr30_mul(fr30_table(tab, kCombineTabWa + (l >> 4)), fr30_table(tab, kCombineTabWb + (l & 15))));
     }
     return cmb_workgroup_sum(h, lds);
 }

@@ -40,26 +40,13 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
 namespace {
 
 static_assert(kPqTile == 256, "one coset point per lane of a 256-lane workgroup");
-
-__device__ __forceinline__ Fr30 cgn_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void cgn_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
 
 struct CgnArgs {
     const uint32_t* wires;  // t columns of N values, column j at + 8 j stride words (the call's workspace)
@@ -80,19 +67,19 @@ __global__ void __launch_bounds__(kPqTile) k_cgn_gate(CgnArgs in, uint32_t* __re
     Fr30 sum = fr30_zero();
 #pragma unroll 1
     for (uint32_t s = 0; s < in.g; s++) {
-        Fr30 acc = cgn_load(q);
+        Fr30 acc = fr30_load(q);
         q += 8 * (size_t)in.N;
         const uint32_t* w = in.wires;
 #pragma unroll 1
         for (uint32_t j = 0; j < in.t; j++) {
             const uint32_t p = in.exps[s * in.t + j], pn = in.next[s * in.t + j];
             if (p) {
-                const Fr30 W = fr30_mul(cgn_load(w + 8 * (size_t)i), in.k14);
+                const Fr30 W = fr30_mul(fr30_load(w + 8 * (size_t)i), in.k14);
 #pragma unroll 1
                 for (uint32_t k = 0; k < p; k++) acc = fr30_mul(acc, W);
             }
             if (pn) {
-                const Fr30 W = fr30_mul(cgn_load(w + 8 * (size_t)i1), in.k14);
+                const Fr30 W = fr30_mul(fr30_load(w + 8 * (size_t)i1), in.k14);
 #pragma unroll 1
                 for (uint32_t k = 0; k < pn; k++) acc = fr30_mul(acc, W);
             }
@@ -100,7 +87,7 @@ __global__ void __launch_bounds__(kPqTile) k_cgn_gate(CgnArgs in, uint32_t* __re
         }
         sum = fr30_add(sum, acc);
     }
-    cgn_store(out + 8 * (size_t)i, fr30_sum_reduce(sum));  // (sum: an operand only)
+    fr30_store(out + 8 * (size_t)i, fr30_sum_reduce(sum));  // (sum: an operand only)
 }
 
 }  // namespace

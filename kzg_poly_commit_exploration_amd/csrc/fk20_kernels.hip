@@ -33,6 +33,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 #include "g1_30.hip.h"
 
 namespace kzg {
@@ -188,26 +189,6 @@ __global__ void __launch_bounds__(kFk20Threads) k_fk20_comb(const uint4* __restr
     }
 }
 
-__device__ __forceinline__ Fr30 fk_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void fk_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 fk_tw(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-
 // R_r of polynomial b: out[(b l + r) L + k] = c_b[(m - k) l + r] for 1 <= k <= m inside the n uploaded coefficients, else 0
 __global__ void __launch_bounds__(256) k_fk20_toeplitz(const uint32_t* __restrict__ c, uint32_t n, uint32_t m,
                                                        uint32_t log_L, uint32_t log_l, uint64_t lanes,
@@ -243,11 +224,11 @@ __global__ void __launch_bounds__(256) k_fr_stage(const uint32_t* __restrict__ i
     const uint32_t k = j & ((1u << s) - 1);
     const uint32_t* vin = in + 8 * (b << log_L);
     uint32_t* vout = out + 8 * (b << log_L);
-    const Fr30 a = fk_load(vin + 8 * j);
-    Fr30 x = fk_load(vin + 8 * (j + half));
+    const Fr30 a = fr30_load(vin + 8 * j);
+    Fr30 x = fr30_load(vin + 8 * (j + half));
     if (k) {
         const uint32_t e22 = k << (kNttMaxLog - s - 1);  // w_(2 Ns)^k
-        x = fr30_mul(x, fr30_mul(fk_tw(tw + kNttTableLen, e22 >> 11), fk_tw(tw, e22 & (kNttTableLen - 1))));
+        x = fr30_mul(x, fr30_mul(fr30_table(tw + kNttTableLen, e22 >> 11), fr30_table(tw, e22 & (kNttTableLen - 1))));
     }
     Fr30 y0 = fr30_norm(fr30_add_raw(a, x));
     Fr30 neg;
@@ -259,8 +240,8 @@ __global__ void __launch_bounds__(256) k_fr_stage(const uint32_t* __restrict__ i
         y1 = fr30_mul(fr30_mul(y1, last_c), fr30_small(1 << 14));
     }
     const uint32_t o = ((j >> s) << (s + 1)) + k;
-    fk_store(vout + 8 * o, y0);
-    fk_store(vout + 8 * (o + (1u << s)), y1);
+    fr30_store(vout + 8 * o, y0);
+    fr30_store(vout + 8 * (o + (1u << s)), y1);
 }
 
 // positions [i0, i0 + ci) of every polynomial: lane (b, i', r), r fastest, i = i0 + i':

@@ -89,6 +89,16 @@ KZG_HD Fr30 fr30_norm(const Fr30& a) {
     return r;
 }
 KZG_HD Fr30 fr30_add(const Fr30& a, const Fr30& b) { return fr30_norm(fr30_add_raw(a, b)); }
+// a - b, carry-normalised.  Both operands are carry-normalised (digits 0..7 within [-2^29 - 4, 2^29 + 4]: what fr30_norm,
+// fr30_from_limbs and fr30_mul return), so the raw difference of those digits stays within 2^30 + 8 < 2^31 - 2^29, inside what
+// fr30_norm takes.  The top digits hold value / 2^240 and are not reduced: their difference plus one carry must fit an int32,
+// which any two lazy values below 2^269 in magnitude (top digits below 2^29) leave room for.
+KZG_HD Fr30 fr30_sub(const Fr30& a, const Fr30& b) {
+    Fr30 r;
+#pragma unroll
+    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
+    return fr30_norm(r);
+}
 
 // a * b / 2^270 (mod r), product scanning.  Digits of both operands within [-2^29 - 4, 2^29 + 4] (one of them may be a
 // raw sum of two such values); result digits 0..7 in [-2^29, 2^29), |result| <= 0.5001 r + |a b| / 2^270.
@@ -216,6 +226,14 @@ KZG_HD void fr30_to_limbs(const Fr30& a, uint32_t l[8]) {
     l[5] = (u[5] >> 10) | (u[6] << 20);
     l[6] = (u[6] >> 12) | (u[7] << 18);
     l[7] = (u[7] >> 14) | (t8 << 16);
+}
+// v = 0 (mod r), for whatever fr30_to_limbs canonicalises: a lazy value in (-r, 2r), and -r itself, in any digits that its
+// sequential carry takes (carry-normalised ones among them).  The test is made on the canonical residue, never on the redundant
+// digits: 0, r and -r all count as zero.
+KZG_HD bool fr30_is_zero(const Fr30& a) {
+    uint32_t l[8];
+    fr30_to_limbs(a, l);
+    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
 }
 
 // the digits {c, 0, ..., 0} of a small constant: fr30_mul(x * 2^256, fr30_small(1 << 14)) = x, fr30_mul(x * 2^270, fr30_small(1)) = x

@@ -56,6 +56,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -67,78 +68,7 @@ static_assert(kGpThreads * kGpRun == kGpTile, "tile shape");
 static_assert(kGpCarryThreads == kGpThreads, "both scans run over 256 lanes");
 static_assert(((1u << kNttMaxLog) + kGpTile - 1) / kGpTile <= 16 * kGpCarryThreads, "a lane of the carry kernel owns <= 16 tiles");
 
-__device__ __forceinline__ Fr30 gp_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void gp_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ bool gp_is_zero(const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
-}
-__device__ __forceinline__ Fr30 gp_load_fr30(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-__device__ __forceinline__ Fr30 gp_digits(const uint32_t* __restrict__ p) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = (int32_t)p[k];
-    return v;
-}
-__device__ __forceinline__ void gp_put_digits(uint32_t* __restrict__ p, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p[k] = (uint32_t)v.d[k];
-}
-// w_n^i in multiplier form: lo x hi of the forward tables of w_(2^22)
-__device__ __forceinline__ Fr30 gp_root(const Fr30* __restrict__ tw, uint32_t i, uint32_t log_n) {
-    const uint32_t e = i << (kNttMaxLog - log_n);
-    return fr30_mul(gp_load_fr30(tw + kNttTableLen, e >> 11), gp_load_fr30(tw, e & (kNttTableLen - 1)));
-}
-
-// digit planes of 256 values in LDS
-struct GpPlane {
-    int32_t d[kR9][kGpThreads];
-};
-__device__ __forceinline__ void plane_put(GpPlane& p, uint32_t t, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p.d[k][t] = v.d[k];
-}
-__device__ __forceinline__ Fr30 plane_get(const GpPlane& p, uint32_t t) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = p.d[k][t];
-    return v;
-}
-// The two scans over the 256 lanes: on return pre[cur] holds the products of mp over lanes [0, t] and suf[cur] the products
-// of ms over lanes [t, 255], visible to every lane, and mp, ms are the lane's own entries of the two; the return value is cur.
-__device__ __forceinline__ uint32_t gp_scan(GpPlane (&pre)[2], GpPlane (&suf)[2], uint32_t t, Fr30& mp, Fr30& ms) {
-    uint32_t cur = 0;
-#pragma unroll 1
-    for (uint32_t o = 1; o < kGpThreads; o <<= 1) {
-        plane_put(pre[cur], t, mp);
-        plane_put(suf[cur], t, ms);
-        __syncthreads();
-        if (t >= o) mp = fr30_mul(plane_get(pre[cur], t - o), mp);
-        if (t + o < kGpThreads) ms = fr30_mul(ms, plane_get(suf[cur], t + o));
-        cur ^= 1;
-    }
-    plane_put(pre[cur], t, mp);
-    plane_put(suf[cur], t, ms);
-    __syncthreads();
-    return cur;
-}
+using GpPlane = Fr30Plane<kGpThreads>;
 
 // what the two forms read
 struct GpColumns {  // t columns each, column j at + 8 j stride words
@@ -159,25 +89,25 @@ struct GpPerm {
 __device__ __forceinline__ void gp_element(const GpColumns& in, uint32_t i, uint32_t t, size_t stride, Fr30& a, Fr30& b) {
     const uint32_t* pa = in.nums + 8 * (size_t)i;
     const uint32_t* pb = in.dens + 8 * (size_t)i;
-    a = gp_load(pa);
-    b = gp_load(pb);
+    a = fr30_load(pa);
+    b = fr30_load(pb);
 #pragma unroll 1
     for (uint32_t j = 1; j < t; j++) {
         pa += 8 * stride;
         pb += 8 * stride;
-        a = fr30_mul(a, gp_load(pa));
-        b = fr30_mul(b, gp_load(pb));
+        a = fr30_mul(a, fr30_load(pa));
+        b = fr30_mul(b, fr30_load(pb));
     }
 }
 __device__ __forceinline__ void gp_element(const GpPerm& in, uint32_t i, uint32_t t, size_t stride, Fr30& a, Fr30& b) {
     const uint32_t* pf = in.wires + 8 * (size_t)i;
     const uint32_t* ps = in.sigmas + 8 * (size_t)i;
-    const Fr30 w = gp_root(in.tw, i, in.log_n);
+    const Fr30 w = fr30_root(in.tw, i, in.log_n);
 #pragma unroll 1
     for (uint32_t j = 0; j < t; j++) {
-        const Fr30 fg = fr30_add(gp_load(pf), in.gamma);                          // [0, 2 r)
+        const Fr30 fg = fr30_add(fr30_load(pf), in.gamma);                          // [0, 2 r)
         const Fr30 aj = fr30_add(fg, fr30_mul(in.bk[j], w));                      // (-0.51 r, 2.51 r): an operand only
-        const Fr30 bj = fr30_add(fg, fr30_mul(gp_load(ps), in.beta));
+        const Fr30 bj = fr30_add(fg, fr30_mul(fr30_load(ps), in.beta));
         a = j ? fr30_mul(a, aj) : aj;
         b = j ? fr30_mul(b, bj) : bj;
         pf += 8 * stride;
@@ -196,7 +126,7 @@ __device__ __forceinline__ void gp_forward(Fr30 (&pa)[kGpRun], Fr30 (&sb)[kGpRun
         gp_element(in, i, t_cols, stride, a, b);
         a = fr30_mul(a, scale);
         b = fr30_mul(b, scale);
-        if (gp_is_zero(b)) atomicMin(hit, i);
+        if (fr30_is_zero(b)) atomicMin(hit, i);
     }
     if constexpr (K == 0) pa[0] = a;
     else pa[K] = fr30_mul(pa[K - 1], a);
@@ -219,7 +149,7 @@ __device__ __forceinline__ void gp_local(const Fr30 (&pa)[kGpRun], Fr30 (&sb)[kG
 template <int K>
 __device__ __forceinline__ void gp_emit(const Fr30 (&v)[kGpRun], const Fr30& m, uint32_t* __restrict__ z, uint32_t base, uint32_t n) {
     const uint32_t i = base + (uint32_t)K;
-    if (i < n) gp_store(z + 8 * (size_t)i, fr30_mul(v[K], m));
+    if (i < n) fr30_store(z + 8 * (size_t)i, fr30_mul(v[K], m));
     if constexpr (K + 1 < (int)kGpRun) gp_emit<K + 1>(v, m, z, base, n);
 }
 
@@ -240,11 +170,11 @@ __device__ __forceinline__ void gp_tile_body(const In& in, uint32_t n, uint32_t 
     gp_suffix<(int)kGpRun - 2>(sb);
     Fr30 mp = pa[kGpRun - 1], ms = sb[0];
     gp_local<1>(pa, sb);
-    const uint32_t cur = gp_scan(pre, suf, t, mp, ms);
+    const uint32_t cur = fr30_scan_products(pre, suf, t, mp, ms);
     uint32_t* rec = partial + (size_t)tile * kGpPartialWords;
-    if (t == kGpThreads - 1) gp_put_digits(rec, mp);
+    if (t == kGpThreads - 1) fr30_put_digits(rec, mp);
     if (t == 0) {
-        gp_put_digits(rec + kR9, ms);
+        fr30_put_digits(rec + kR9, ms);
         rec[2 * kR9] = hit_s;
     }
     // u_i = v_k x (A over the lanes before this one) x (B over the lanes after it)
@@ -283,12 +213,12 @@ __global__ void __launch_bounds__(kGpCarryThreads) k_gp_carry(uint32_t tiles, Fr
 #pragma unroll 1
     for (uint32_t k = first; k < end; k++) {
         const uint32_t* rec = partial + (size_t)k * kGpPartialWords;
-        a = fr30_mul(a, gp_digits(rec));
-        b = fr30_mul(b, gp_digits(rec + kR9));
+        a = fr30_mul(a, fr30_digits(rec));
+        b = fr30_mul(b, fr30_digits(rec + kR9));
         hit = min(hit, rec[2 * kR9]);
     }
     if (hit != kGpNone) atomicMin(&hit_s, hit);
-    const uint32_t cur = gp_scan(pre, suf, t, a, b);  // a of lane 255: every A; b of lane 0: every B
+    const uint32_t cur = fr30_scan_products(pre, suf, t, a, b);  // a of lane 255: every A; b of lane 0: every B
     if (t == 0) {
         // the product of every B is zero exactly when some B_i is: fr30_inv(0) = 0 and the call only reports
         Fr30 io;
@@ -303,14 +233,14 @@ __global__ void __launch_bounds__(kGpCarryThreads) k_gp_carry(uint32_t tiles, Fr
     Fr30 p;
 #pragma unroll
     for (int k = 0; k < kR9; k++) p.d[k] = inv_s[k];
-    if (t == kGpCarryThreads - 1) gp_store(flags + 8, fr30_mul(a, p));  // last = A_total / B_total
+    if (t == kGpCarryThreads - 1) fr30_store(flags + 8, fr30_mul(a, p));  // last = A_total / B_total
     if (t > 0) p = fr30_mul(plane_get(pre[cur], t - 1), p);  // (A over the tiles of the lanes before) / B_total: an image
     // forwards: the A record of tile k becomes preA_k / B_total
 #pragma unroll 1
     for (uint32_t k = first; k < end; k++) {
         uint32_t* rec = partial + (size_t)k * kGpPartialWords;
-        const Fr30 ak = gp_digits(rec);
-        gp_put_digits(rec, p);
+        const Fr30 ak = fr30_digits(rec);
+        fr30_put_digits(rec, p);
         p = fr30_mul(p, ak);
     }
     // backwards: ... times sufB_k, the product of B over the tiles after k
@@ -318,20 +248,20 @@ __global__ void __launch_bounds__(kGpCarryThreads) k_gp_carry(uint32_t tiles, Fr
 #pragma unroll 1
     for (uint32_t k = end; k > first; k--) {
         uint32_t* rec = partial + (size_t)(k - 1) * kGpPartialWords;
-        gp_put_digits(rec, fr30_mul(gp_digits(rec), s));
-        s = fr30_mul(s, gp_digits(rec + kR9));
+        fr30_put_digits(rec, fr30_mul(fr30_digits(rec), s));
+        s = fr30_mul(s, fr30_digits(rec + kR9));
     }
 }
 
 __global__ void __launch_bounds__(kGpThreads) k_gp_scale(uint32_t n, const uint32_t* __restrict__ partial, uint32_t* __restrict__ z) {
     const uint32_t tile = blockIdx.x;
-    const Fr30 c = gp_digits(partial + (size_t)tile * kGpPartialWords);
+    const Fr30 c = fr30_digits(partial + (size_t)tile * kGpPartialWords);
 #pragma unroll
     for (uint32_t j = 0; j < kGpRun; j++) {
         const uint32_t i = tile * kGpTile + j * kGpThreads + threadIdx.x;
         if (i < n) {
             uint32_t* p = z + 8 * (size_t)i;
-            gp_store(p, fr30_mul(gp_load(p), c));
+            fr30_store(p, fr30_mul(fr30_load(p), c));
         }
     }
 }

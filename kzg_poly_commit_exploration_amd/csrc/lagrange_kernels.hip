@@ -40,6 +40,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -51,55 +52,8 @@ static_assert(kLagThreads * kLagRun == kLagTile, "tile shape");
 constexpr uint32_t kLagFinishThreads = 64;
 constexpr uint32_t kLagNone = 0xffffffffu;
 
-__device__ __forceinline__ Fr30 lag_load_fr30(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-__device__ __forceinline__ Fr30 lag_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void lag_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 lag_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
-    return fr30_norm(r);
-}
-__device__ __forceinline__ bool lag_is_zero(const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
-}
-// w_n^i (tw: the forward tables) or w_n^-i (the inverse tables) in multiplier form: lo x hi of the tables of w_(2^22)
-__device__ __forceinline__ Fr30 lag_root(const Fr30* __restrict__ tw, uint32_t i, uint32_t log_n) {
-    const uint32_t e = i << (kNttMaxLog - log_n);
-    return fr30_mul(lag_load_fr30(tw + kNttTableLen, e >> 11), lag_load_fr30(tw, e & (kNttTableLen - 1)));
-}
 // digit planes of 256 values in LDS
-struct LagPlane {
-    int32_t d[kR9][kLagThreads];
-};
-__device__ __forceinline__ void plane_put(LagPlane& p, uint32_t t, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p.d[k][t] = v.d[k];
-}
-__device__ __forceinline__ Fr30 plane_get(const LagPlane& p, uint32_t t) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = p.d[k][t];
-    return v;
-}
+using LagPlane = Fr30Plane<kLagThreads>;
 
 // what a lane carries on the way back
 struct LagAcc {
@@ -116,8 +70,8 @@ __device__ __forceinline__ void lag_forward(Fr30 (&p)[kLagRun], const Fr30& z, c
     const uint32_t i = base + (uint32_t)J * kLagThreads;
     Fr30 d = one;
     if (i < n) {
-        d = lag_sub(z, lag_root(tw, i, log_n));
-        if (lag_is_zero(d)) {
+        d = fr30_sub(z, fr30_root(tw, i, log_n));
+        if (fr30_is_zero(d)) {
             atomicMin(hit, i);
             d = one;
         }
@@ -134,24 +88,24 @@ __device__ __forceinline__ void lag_backward(const Fr30 (&p)[kLagRun], Fr30& inv
                                              uint32_t log_n) {
     const uint32_t i = base + (uint32_t)J * kLagThreads;
     if (i < n) {
-        const Fr30 w = lag_root(tw, i, log_n);
-        Fr30 d = lag_sub(z, w);
-        const bool zero = lag_is_zero(d);
+        const Fr30 w = fr30_root(tw, i, log_n);
+        Fr30 d = fr30_sub(z, w);
+        const bool zero = fr30_is_zero(d);
         if (zero) d = one;
         Fr30 dinv = inv;
         if constexpr (J > 0) {
             dinv = fr30_mul(inv, p[J - 1]);
             inv = fr30_mul(inv, d);
         }
-        const Fr30 fi = lag_load(f + 8 * (size_t)i);
-        if (!lag_is_zero(lag_sub(fi, f0))) acc.differs = 1u;  // (-r, r): canonicalised by the test
+        const Fr30 fi = fr30_load(f + 8 * (size_t)i);
+        if (!fr30_is_zero(fr30_sub(fi, f0))) acc.differs = 1u;  // (-r, r): canonicalised by the test
         Fr30 qi = fr30_zero();
         if (!zero) {
-            qi = fr30_mul(lag_sub(y, fi), dinv);  // (y - f_i) in (-r, r) x a multiplier: an image, |v| <= 0.5001 r
+            qi = fr30_mul(fr30_sub(y, fi), dinv);  // (y - f_i) in (-r, r) x a multiplier: an image, |v| <= 0.5001 r
             acc.bary = fr30_add(acc.bary, fr30_mul(fr30_mul(fi, w), dinv));
             acc.dom = fr30_add(acc.dom, fr30_mul(qi, w));
         }
-        lag_store(q + 8 * (size_t)i, qi);
+        fr30_store(q + 8 * (size_t)i, qi);
     }
     if constexpr (J > 0) lag_backward<J - 1>(p, inv, acc, z, y, f0, one, tw, f, q, base, n, log_n);
 }
@@ -205,7 +159,7 @@ __global__ void __launch_bounds__(kLagThreads) k_lagrange_partial(const uint32_t
     acc.bary = fr30_zero();
     acc.dom = fr30_zero();
     acc.differs = 0;
-    const Fr30 f0 = lag_load(f);
+    const Fr30 f0 = fr30_load(f);
     lag_backward<(int)kLagRun - 1>(p, inv, acc, z, y, f0, one, tw, f, q, base, n, log_n);
     if (acc.differs) differs_s = 1u;  // (every writer stores the same 1)
     acc.bary = fr30_mul(acc.bary, one);  // the run sums back below 0.5001 r + r / 2^13
@@ -266,14 +220,8 @@ __global__ void __launch_bounds__(kLagFinishThreads) k_lagrange_finish(const uin
 #pragma unroll 1
     for (uint32_t k = t; k < tiles; k += kLagFinishThreads) {
         const uint32_t* rec = partial + (size_t)k * kLagPartialWords;
-        Fr30 vb, vd;
-#pragma unroll
-        for (int j = 0; j < kR9; j++) {
-            vb.d[j] = (int32_t)rec[j];
-            vd.d[j] = (int32_t)rec[kR9 + j];
-        }
-        bary = fr30_add(bary, vb);
-        dom = fr30_add(dom, vd);
+        bary = fr30_add(bary, fr30_digits(rec));
+        dom = fr30_add(dom, fr30_digits(rec + kR9));
         hit = min(hit, rec[2 * kR9]);
         differs |= rec[2 * kR9 + 1];
     }
@@ -307,9 +255,9 @@ __global__ void __launch_bounds__(kLagFinishThreads) k_lagrange_finish(const uin
         // z = w^m: P(z) = f_m, and q_m = -(sum_{i != m} q_i w^i) w^-m
         fl4[2] = f4[2 * (size_t)m];
         fl4[3] = f4[2 * (size_t)m + 1];
-        const Fr30 wi = lag_root(tw + 2 * kNttTableLen, m, log_n);  // w^-m
+        const Fr30 wi = fr30_root(tw + 2 * kNttTableLen, m, log_n);  // w^-m
         const Fr30 qm = fr30_mul(fr30_mul(dom, one), wi);           // the sum back below 0.51 r, then an image again
-        lag_store(q + 8 * (size_t)m, lag_sub(fr30_zero(), qm));  // m < n: only indices below n are recorded
+        fr30_store(q + 8 * (size_t)m, fr30_sub(fr30_zero(), qm));  // m < n: only indices below n are recorded
     } else {
         Fr30 zn, in;
 #pragma unroll
@@ -319,8 +267,8 @@ __global__ void __launch_bounds__(kLagFinishThreads) k_lagrange_finish(const uin
         }
 #pragma unroll 1
         for (uint32_t k = 0; k < log_n; k++) zn = fr30_mul(zn, zn);
-        const Fr30 factor = fr30_mul(lag_sub(zn, one), in);
-        lag_store(flags + 8, fr30_mul(fr30_mul(bary, one), factor));  // [8..15] = P(z)
+        const Fr30 factor = fr30_mul(fr30_sub(zn, one), in);
+        fr30_store(flags + 8, fr30_mul(fr30_mul(bary, one), factor));  // [8..15] = P(z)
     }
     flags[0] = differs_s;
 }

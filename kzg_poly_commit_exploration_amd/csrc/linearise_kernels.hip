@@ -47,7 +47,7 @@ __device__ __forceinline__ void lin_column(Fr30 (&acc)[HALF], const uint4* __res
     }
 #pragma unroll
     for (int m = 0; m < HALF; m++) {
-        Fr30 c = cmb_from_u4(lo[m], hi[m]);
+        Fr30 c = fr30_from_u4(lo[m], hi[m]);
         if (base + (uint64_t)m * kCombineThreads >= n) c = fr30_zero();
         acc[m] = fr30_mac(acc[m], c, w);
     }
@@ -59,7 +59,7 @@ __device__ __forceinline__ void lin_leave(const Fr30 (&acc)[HALF], Fr30& h, cons
                                           uint32_t n) {
     const uint64_t idx = base + (uint64_t)M * kCombineThreads;
     const Fr30 v = fr30_sum_reduce(acc[M]);
-    if (idx < n) cmb_store_canonical(out + 8 * idx, v);
+    if (idx < n) fr30_store(out + 8 * idx, v);
     h = fr30_add_raw(fr30_mul(h, z256), v);
     if constexpr (M > 0) lin_leave<M - 1>(acc, h, z256, out, base, n);
 }
@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(kCombineThreads, 3) k_lin_combine(const LinCol
     // A lane takes its run in two halves, the upper one first (Horner runs from the top): four accumulators (36 registers) and
     // eight loads in flight instead of eight and sixteen, which is what keeps the kernel inside 160 registers.  Every coefficient
     // is still read once; the table is walked twice.
-    const Fr30 z256 = cmb_table(tab, kCombineTabZ256);
+    const Fr30 z256 = fr30_table(tab, kCombineTabZ256);
     Fr30 h = fr30_zero();
 #pragma unroll 1
     for (int half = RUN / HALF - 1; half >= 0; half--) {
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(kCombineThreads, 3) k_lin_combine(const LinCol
         lin_leave<HALF - 1>(acc, h, z256, out, first, n);
     }
     // z^l = z^(16 (l >> 4)) z^(l & 15), a multiplier again
-    const Fr30 zl = fr30_mul(cmb_table(tab, kCombineTabPa + (l >> 4)), cmb_table(tab, kCombineTabPb + (l & 15)));
+    const Fr30 zl = fr30_mul(fr30_table(tab, kCombineTabPa + (l >> 4)), fr30_table(tab, kCombineTabPb + (l & 15)));
     const Fr30 e = cmb_workgroup_sum(fr30_mul(h, zl), lds);
     if (l == 0) {
         uint4* q = reinterpret_cast<uint4*>(partial + (size_t)tile * kCombinePartialWords);
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_lin_finish(const uint32_t* 
                                                                 const Fr30* __restrict__ tab, uint32_t* __restrict__ y) {
     __shared__ int32_t lds[kR9][4];
     const Fr30 total = cmb_tiles_sum(partial, tiles, tab, lds);
-    if (threadIdx.x == 0) cmb_store_canonical(y, fr30_sum_reduce(total));
+    if (threadIdx.x == 0) fr30_store(y, fr30_sum_reduce(total));
 }
 
 }  // namespace

@@ -60,6 +60,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -67,31 +68,12 @@ namespace {
 
 static_assert(kPqTile == 256, "one row or coset point per lane of a 256-lane workgroup");
 
-__device__ __forceinline__ Fr30 lk_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void lk_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 lk_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) r.d[k] = a.d[k] - b.d[k];
-    return fr30_norm(r);
-}
 // sum_{j < c} col_j th_j: column j at p + 8 j stride words
 __device__ __forceinline__ Fr30 lk_folded(const uint32_t* __restrict__ p, size_t stride, uint32_t c, const Fr30* th) {
     Fr30 s = fr30_zero();
 #pragma unroll 1
     for (uint32_t j = 0; j < c; j++) {
-        s = fr30_mac(s, lk_load(p), th[j]);
+        s = fr30_mac(s, fr30_load(p), th[j]);
         p += 8 * stride;
     }
     return s;
@@ -111,9 +93,9 @@ __global__ void __launch_bounds__(kPqTile) k_lk_fold(LkFoldArgs in, uint32_t* __
     const uint32_t i = blockIdx.x * kPqTile + threadIdx.x;
     if (i >= in.n) return;
     const Fr30 sf = lk_folded(in.wires + 8 * (size_t)i, in.stride, in.c, in.theta);
-    lk_store(out_f + 8 * (size_t)i, fr30_mul(fr30_mul(sf, lk_load(in.qk + 8 * (size_t)i)), in.k14));
+    fr30_store(out_f + 8 * (size_t)i, fr30_mul(fr30_mul(sf, fr30_load(in.qk + 8 * (size_t)i)), in.k14));
     const Fr30 st = lk_folded(in.table + 8 * (size_t)i, in.n, in.c, in.theta);
-    lk_store(out_t + 8 * (size_t)i, fr30_sum_reduce(st));
+    fr30_store(out_t + 8 * (size_t)i, fr30_sum_reduce(st));
 }
 
 struct LkArgs {
@@ -136,14 +118,14 @@ __global__ void __launch_bounds__(kPqTile) k_lk_constraints(LkArgs in, uint32_t*
     if (i >= N) return;
     const uint32_t ir = (i + in.rot) & (N - 1);
     const Fr30 sf = lk_folded(in.wires + 8 * (size_t)i, in.stride, in.c, in.theta);
-    const Fr30 F = fr30_add(in.beta, fr30_mul(fr30_mul(sf, lk_load(in.qk + 8 * (size_t)i)), in.k14));
+    const Fr30 F = fr30_add(in.beta, fr30_mul(fr30_mul(sf, fr30_load(in.qk + 8 * (size_t)i)), in.k14));
     const Fr30 Tt = fr30_add(in.beta, lk_folded(in.table + 8 * (size_t)i, (size_t)N, in.c, in.theta));  // an operand only
-    const Fr30 phi = lk_load(in.phi + 8 * (size_t)i);
-    const Fr30 D = lk_sub(lk_load(in.phi + 8 * (size_t)ir), phi);
-    const Fr30 E = fr30_add(lk_load(in.mult + 8 * (size_t)i), fr30_mul(fr30_mul(D, Tt), in.k14));
-    Fr30 W = lk_sub(fr30_mul(fr30_mul(E, F), in.k14), Tt);                                              // Lk1
-    W = fr30_add(W, fr30_mul(fr30_mul(lk_load(in.l0 + 8 * (size_t)i), phi), in.ak14));                  // + alpha Lk2: an operand only
-    lk_store(out + 8 * (size_t)i, fr30_mul(W, in.a3));
+    const Fr30 phi = fr30_load(in.phi + 8 * (size_t)i);
+    const Fr30 D = fr30_sub(fr30_load(in.phi + 8 * (size_t)ir), phi);
+    const Fr30 E = fr30_add(fr30_load(in.mult + 8 * (size_t)i), fr30_mul(fr30_mul(D, Tt), in.k14));
+    Fr30 W = fr30_sub(fr30_mul(fr30_mul(E, F), in.k14), Tt);                                              // Lk1
+    W = fr30_add(W, fr30_mul(fr30_mul(fr30_load(in.l0 + 8 * (size_t)i), phi), in.ak14));                  // + alpha Lk2: an operand only
+    fr30_store(out + 8 * (size_t)i, fr30_mul(W, in.a3));
 }
 
 }  // namespace

@@ -89,6 +89,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -103,34 +104,6 @@ static_assert(kLuRecW + kR9 <= kLuRecC && kLuRecC + kR9 <= kLuRecBase && kLuRecB
                   kLuPartialWords % 4 == 0,
               "record layout");
 
-__device__ __forceinline__ Fr30 lu_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void lu_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ bool lu_is_zero(const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) == 0;
-}
-__device__ __forceinline__ Fr30 lu_digits(const uint32_t* __restrict__ p) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = (int32_t)p[k];
-    return v;
-}
-__device__ __forceinline__ void lu_put_digits(uint32_t* __restrict__ p, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p[k] = (uint32_t)v.d[k];
-}
 __device__ __forceinline__ Fr30 lu_neg(const Fr30& a) {
     Fr30 v;
 #pragma unroll
@@ -139,37 +112,7 @@ __device__ __forceinline__ Fr30 lu_neg(const Fr30& a) {
 }
 
 // digit planes of 256 values in LDS
-struct LuPlane {
-    int32_t d[kR9][kLuThreads];
-};
-__device__ __forceinline__ void plane_put(LuPlane& p, uint32_t t, const Fr30& v) {
-#pragma unroll
-    for (int k = 0; k < kR9; k++) p.d[k][t] = v.d[k];
-}
-__device__ __forceinline__ Fr30 plane_get(const LuPlane& p, uint32_t t) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = p.d[k][t];
-    return v;
-}
-// The two product scans over the 256 lanes: on return pre[cur] holds the products of mp over lanes [0, t] and suf[cur] the
-// products of ms over lanes [t, 255], visible to every lane, and mp, ms are the lane's own entries; the return value is cur.
-__device__ __forceinline__ uint32_t lu_scan(LuPlane (&pre)[2], LuPlane (&suf)[2], uint32_t t, Fr30& mp, Fr30& ms) {
-    uint32_t cur = 0;
-#pragma unroll 1
-    for (uint32_t o = 1; o < kLuThreads; o <<= 1) {
-        plane_put(pre[cur], t, mp);
-        plane_put(suf[cur], t, ms);
-        __syncthreads();
-        if (t >= o) mp = fr30_mul(plane_get(pre[cur], t - o), mp);
-        if (t + o < kLuThreads) ms = fr30_mul(ms, plane_get(suf[cur], t + o));
-        cur ^= 1;
-    }
-    plane_put(pre[cur], t, mp);
-    plane_put(suf[cur], t, ms);
-    __syncthreads();
-    return cur;
-}
+using LuPlane = Fr30Plane<kLuThreads>;
 // The additive scan over the 256 lanes: on return pl[cur] holds the sums of a over lanes [0, t] and a is the lane's own entry.
 // Every lane has left the planes' earlier contents behind (the caller's barrier).  Each step is one carry pass over two
 // normalised values; the top digit grows with the sum (the header's bound).
@@ -208,36 +151,36 @@ struct LuValues {
 __device__ __forceinline__ void lu_element(const LuColumns& in, uint32_t i, uint32_t t, size_t stride, Fr30& nn, Fr30& dd) {
     const uint32_t* pb = in.dens + 8 * (size_t)i;
     const uint32_t* pa = in.nums ? in.nums + 8 * (size_t)i : nullptr;
-    dd = lu_load(pb);
-    nn = pa ? lu_load(pa) : in.one;
+    dd = fr30_load(pb);
+    nn = pa ? fr30_load(pa) : in.one;
 #pragma unroll 1
     for (uint32_t j = 1; j < t; j++) {
         pb += 8 * stride;
         if (pa) pa += 8 * stride;
-        const Fr30 b = lu_load(pb);
-        const Fr30 a = pa ? lu_load(pa) : in.one;
+        const Fr30 b = fr30_load(pb);
+        const Fr30 a = pa ? fr30_load(pa) : in.one;
         nn = fr30_add(fr30_mul(nn, b), fr30_mul(a, dd));  // < 1.001 r: an operand only
         dd = fr30_mul(dd, b);
     }
 }
 __device__ __forceinline__ void lu_element(const LuLookup& in, uint32_t i, uint32_t t, size_t stride, Fr30& nn, Fr30& dd) {
     const uint32_t* pf = in.lookups + 8 * (size_t)i;
-    dd = fr30_add(lu_load(pf), in.beta);  // [0, 2 r): an operand only
+    dd = fr30_add(fr30_load(pf), in.beta);  // [0, 2 r): an operand only
     nn = in.one;
 #pragma unroll 1
     for (uint32_t j = 1; j + 1 < t; j++) {
         pf += 8 * stride;
-        const Fr30 b = fr30_add(lu_load(pf), in.beta);
+        const Fr30 b = fr30_add(fr30_load(pf), in.beta);
         nn = fr30_add(fr30_mul(nn, b), fr30_mul(in.one, dd));
         dd = fr30_mul(dd, b);
     }
-    const Fr30 b = fr30_add(lu_load(in.table + 8 * (size_t)i), in.beta);
-    const Fr30 a = lu_neg(lu_load(in.mult + 8 * (size_t)i));  // (-r, 0]
+    const Fr30 b = fr30_add(fr30_load(in.table + 8 * (size_t)i), in.beta);
+    const Fr30 a = lu_neg(fr30_load(in.mult + 8 * (size_t)i));  // (-r, 0]
     nn = fr30_add(fr30_mul(nn, b), fr30_mul(a, dd));
     dd = fr30_mul(dd, b);
 }
 __device__ __forceinline__ void lu_element(const LuValues& in, uint32_t i, uint32_t, size_t, Fr30& nn, Fr30& dd) {
-    dd = lu_load(in.vals + 8 * (size_t)i);
+    dd = fr30_load(in.vals + 8 * (size_t)i);
     nn = dd;  // not used
 }
 
@@ -251,7 +194,7 @@ __device__ __forceinline__ void lu_row(const In& in, uint32_t i, uint32_t n, uin
         lu_element(in, i, t_cols, stride, nn, dd);
         dd = fr30_mul(dd, scale);
         if constexpr (kSum) nn = fr30_mul(nn, scale);
-        if (lu_is_zero(dd)) atomicMin(hit, i);
+        if (fr30_is_zero(dd)) atomicMin(hit, i);
     }
 }
 
@@ -270,27 +213,27 @@ __device__ __forceinline__ void lu_tile_body(const In& in, uint32_t n, uint32_t 
     lu_row<kSum>(in, base, n, t_cols, stride, scale, one, nn[0], dd[0], &hit_s);
     lu_row<kSum>(in, base + 1, n, t_cols, stride, scale, one, nn[1], dd[1], &hit_s);
     Fr30 mp = fr30_mul(dd[0], dd[1]), ms = mp;
-    const uint32_t cur = lu_scan(pre, suf, t, mp, ms);
+    const uint32_t cur = fr30_scan_products(pre, suf, t, mp, ms);
     uint32_t* rec = partial + (size_t)tile * kLuPartialWords;
-    if (t == kLuThreads - 1) lu_put_digits(rec + kLuRecD, mp);
+    if (t == kLuThreads - 1) fr30_put_digits(rec + kLuRecD, mp);
     if (t == 0) rec[kLuRecHit] = hit_s;
     // u_i = (D over the tile's rows before i) x (D over the tile's rows after i)
     const Fr30 pl = t > 0 ? plane_get(pre[cur], t - 1) : one;
     const Fr30 sl = t + 1 < kLuThreads ? plane_get(suf[cur], t + 1) : one;
     const Fr30 u0 = fr30_mul(pl, fr30_mul(dd[1], sl)), u1 = fr30_mul(fr30_mul(pl, dd[0]), sl);
     if constexpr (!kSum) {
-        if (base < n) lu_store(out + 8 * (size_t)base, u0);
-        if (base + 1 < n) lu_store(out + 8 * (size_t)(base + 1), u1);
-        if (t == 0) lu_put_digits(rec + kLuRecW, fr30_zero());
+        if (base < n) fr30_store(out + 8 * (size_t)base, u0);
+        if (base + 1 < n) fr30_store(out + 8 * (size_t)(base + 1), u1);
+        if (t == 0) fr30_put_digits(rec + kLuRecW, fr30_zero());
     } else {
         const Fr30 w0 = fr30_mul(nn[0], u0), w1 = fr30_mul(nn[1], u1);
         Fr30 a = fr30_add(w0, w1);
         __syncthreads();  // every lane has read its pl and sl: the planes are free for the additive scan
         const uint32_t c2 = lu_scan_add(pre, t, a);
         const Fr30 e = t > 0 ? plane_get(pre[c2], t - 1) : fr30_zero();
-        if (base < n) lu_store(out + 8 * (size_t)base, fr30_sum_reduce(e));
-        if (base + 1 < n) lu_store(out + 8 * (size_t)(base + 1), fr30_sum_reduce(fr30_add(e, w0)));
-        if (t == kLuThreads - 1) lu_put_digits(rec + kLuRecW, fr30_sum_reduce(a));
+        if (base < n) fr30_store(out + 8 * (size_t)base, fr30_sum_reduce(e));
+        if (base + 1 < n) fr30_store(out + 8 * (size_t)(base + 1), fr30_sum_reduce(fr30_add(e, w0)));
+        if (t == kLuThreads - 1) fr30_put_digits(rec + kLuRecW, fr30_sum_reduce(a));
     }
 }
 
@@ -328,12 +271,12 @@ __global__ void __launch_bounds__(kLuCarryThreads) k_lu_carry(uint32_t tiles, Fr
 #pragma unroll 1
     for (uint32_t k = first; k < end; k++) {
         const uint32_t* rec = partial + (size_t)k * kLuPartialWords;
-        mp = fr30_mul(mp, lu_digits(rec + kLuRecD));
+        mp = fr30_mul(mp, fr30_digits(rec + kLuRecD));
         hit = min(hit, rec[kLuRecHit]);
     }
     if (hit != kLuNone) atomicMin(&hit_s, hit);
     Fr30 ms = mp;
-    const uint32_t cur = lu_scan(pre, suf, t, mp, ms);  // ms of lane 0: every D
+    const uint32_t cur = fr30_scan_products(pre, suf, t, mp, ms);  // ms of lane 0: every D
     if (t == 0) {
         // the product of every D is zero exactly when some D_i is: fr30_inv(0) = 0 and the call only reports
         Fr30 io;
@@ -354,44 +297,44 @@ __global__ void __launch_bounds__(kLuCarryThreads) k_lu_carry(uint32_t tiles, Fr
 #pragma unroll 1
     for (uint32_t k = first; k < end; k++) {
         uint32_t* rec = partial + (size_t)k * kLuPartialWords;
-        lu_put_digits(rec + kLuRecC, p);
-        p = fr30_mul(p, lu_digits(rec + kLuRecD));
+        fr30_put_digits(rec + kLuRecC, p);
+        p = fr30_mul(p, fr30_digits(rec + kLuRecD));
     }
     // backwards: ... times sufD_k, the product of D over the tiles after k: c_T.  The lane's sum of c_T W_T on the way.
     Fr30 tot = fr30_zero();
 #pragma unroll 1
     for (uint32_t k = end; k > first; k--) {
         uint32_t* rec = partial + (size_t)(k - 1) * kLuPartialWords;
-        const Fr30 c = fr30_mul(lu_digits(rec + kLuRecC), s);
-        lu_put_digits(rec + kLuRecC, c);
-        tot = fr30_add(tot, fr30_mul(c, lu_digits(rec + kLuRecW)));
-        s = fr30_mul(s, lu_digits(rec + kLuRecD));
+        const Fr30 c = fr30_mul(fr30_digits(rec + kLuRecC), s);
+        fr30_put_digits(rec + kLuRecC, c);
+        tot = fr30_add(tot, fr30_mul(c, fr30_digits(rec + kLuRecW)));
+        s = fr30_mul(s, fr30_digits(rec + kLuRecD));
     }
     tot = fr30_sum_reduce(tot);
     __syncthreads();  // every lane has read its prefix and suffix: the planes are free for the additive scan
     const uint32_t c2 = lu_scan_add(pre, t, tot);
-    if (t == kLuCarryThreads - 1) lu_store(flags + 8, fr30_sum_reduce(tot));  // last = phi_n
+    if (t == kLuCarryThreads - 1) fr30_store(flags + 8, fr30_sum_reduce(tot));  // last = phi_n
     // forwards again: base_T, canonical
     Fr30 b = t > 0 ? plane_get(pre[c2], t - 1) : fr30_zero();
 #pragma unroll 1
     for (uint32_t k = first; k < end; k++) {
         uint32_t* rec = partial + (size_t)k * kLuPartialWords;
-        lu_store(rec + kLuRecBase, fr30_sum_reduce(b));
-        b = fr30_add(b, fr30_mul(lu_digits(rec + kLuRecC), lu_digits(rec + kLuRecW)));
+        fr30_store(rec + kLuRecBase, fr30_sum_reduce(b));
+        b = fr30_add(b, fr30_mul(fr30_digits(rec + kLuRecC), fr30_digits(rec + kLuRecW)));
     }
 }
 
 __global__ void __launch_bounds__(kLuThreads) k_lu_finish(uint32_t n, const uint32_t* __restrict__ partial, uint32_t* __restrict__ phi) {
     const uint32_t tile = blockIdx.x;
     const uint32_t* rec = partial + (size_t)tile * kLuPartialWords;
-    const Fr30 c = lu_digits(rec + kLuRecC);
-    const Fr30 b = lu_load(rec + kLuRecBase);
+    const Fr30 c = fr30_digits(rec + kLuRecC);
+    const Fr30 b = fr30_load(rec + kLuRecBase);
 #pragma unroll
     for (uint32_t j = 0; j < kLuRun; j++) {
         const uint32_t i = tile * kLuTile + j * kLuThreads + threadIdx.x;
         if (i < n) {
             uint32_t* p = phi + 8 * (size_t)i;
-            lu_store(p, fr30_add_raw(fr30_mul(lu_load(p), c), b));
+            fr30_store(p, fr30_add_raw(fr30_mul(fr30_load(p), c), b));
         }
     }
 }
@@ -497,7 +440,7 @@ __global__ void __launch_bounds__(kLuThreads) k_lu_counts(const uint32_t* __rest
         flags[0] = words[0];
         flags[1] = words[1];
     }
-    if (r < n_table) lu_store(out_mult + 8 * (size_t)r, fr30_mul(fr30_small((int32_t)counts[r]), count_img));  // count < 2^26
+    if (r < n_table) fr30_store(out_mult + 8 * (size_t)r, fr30_mul(fr30_small((int32_t)counts[r]), count_img));  // count < 2^26
 }
 
 void lu_finish(hipStream_t s, uint32_t n, uint32_t tiles, const Fr30& img_one, const LuOut& out) {

@@ -187,7 +187,7 @@ __device__ __forceinline__ void ml_store_record(uint32_t* p, const Fr30& e) {
 template <int M>
 __device__ __forceinline__ void ml_eval_steps(Fr30& h, Fr30& g, const uint4 (&lo)[8], const uint4 (&hi)[8], const Fr30& z256,
                                               const Fr30& s256, uint64_t base, uint32_t len) {
-    Fr30 c = cmb_from_u4(lo[M], hi[M]);
+    Fr30 c = fr30_from_u4(lo[M], hi[M]);
     if (base + (uint64_t)M * kCombineThreads >= len) c = fr30_zero();
     h = fr30_add_raw(fr30_mul(h, z256), c);
     g = fr30_add_raw(fr30_mul(g, s256), c);
@@ -220,11 +220,11 @@ __global__ void __launch_bounds__(kCombineThreads) k_ml_eval(const uint32_t* __r
         hi[m] = p[1];
     }
     const Fr30* tab2 = tab + kCombineTabGamma;
-    const Fr30 z256 = cmb_table(tab, kCombineTabZ256), s256 = cmb_table(tab2, kCombineTabZ256);
+    const Fr30 z256 = fr30_table(tab, kCombineTabZ256), s256 = fr30_table(tab2, kCombineTabZ256);
     Fr30 h = fr30_zero(), g = fr30_zero();
     ml_eval_steps<7>(h, g, lo, hi, z256, s256, base, len);
-    const Fr30 zt = fr30_mul(cmb_table(tab, kCombineTabPa + (t >> 4)), cmb_table(tab, kCombineTabPb + (t & 15)));
-    const Fr30 st = fr30_mul(cmb_table(tab2, kCombineTabPa + (t >> 4)), cmb_table(tab2, kCombineTabPb + (t & 15)));
+    const Fr30 zt = fr30_mul(fr30_table(tab, kCombineTabPa + (t >> 4)), fr30_table(tab, kCombineTabPb + (t & 15)));
+    const Fr30 st = fr30_mul(fr30_table(tab2, kCombineTabPa + (t >> 4)), fr30_table(tab2, kCombineTabPb + (t & 15)));
     const Fr30 a = fr30_mul(h, zt);
     Fr30 b;
 #pragma unroll
@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(kCombineThreads) k_ml_eval_finish(const uint32
     const uint32_t b = blockIdx.x, i = b / 3, p = b % 3;
     const uint32_t tiles = ((n >> i) + kCombineTile - 1) / kCombineTile;
     const Fr30 y = cmb_tiles_sum(partial + (size_t)b * tiles0 * kCombinePartialWords, tiles, p == 2 ? tab + kCombineTabGamma : tab, lds);
-    if (threadIdx.x == 0) cmb_store_canonical(out + 8 * (size_t)b, fr30_sum_reduce(y));
+    if (threadIdx.x == 0) fr30_store(out + 8 * (size_t)b, fr30_sum_reduce(y));
 }
 
 // F[j] = f_0[j] + sum_{1 <= i < l, j < n >> i} gamma^i f_i[j], one index per lane.
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(kMlThreads) k_ml_combine(const uint32_t* __res
         const MlLimbs c = ml_load(pyr, (uint64_t)n - (uint64_t)(n >> (i - 1)) + j, (uint64_t)n);
         acc = fr30_mac(acc, fr30_from_limbs(c.l), ml_mult(gam, i));
     }
-    cmb_store_canonical(f + 8 * j, fr30_sum_reduce(acc));
+    fr30_store(f + 8 * j, fr30_sum_reduce(acc));
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -39,18 +40,6 @@ __device__ __forceinline__ Fr30 lds_get(const int32_t* lds, uint32_t T, uint32_t
 __device__ __forceinline__ void lds_put(int32_t* lds, uint32_t T, uint32_t pos, const Fr30& v) {
 #pragma unroll
     for (int i = 0; i < kR9; i++) lds[i * T + pos] = v.d[i];
-}
-__device__ __forceinline__ Fr30 tw_get(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-__device__ __forceinline__ Fr30 fr30_sub_norm(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int i = 0; i < kR9; i++) r.d[i] = a.d[i] - b.d[i];
-    return fr30_norm(r);
 }
 
 // One Stockham pass over a tile of J = 2^log_j consecutive j and R = 2^m values each (T = J R <= kNttTile), LDS as nine
@@ -89,9 +78,9 @@ __global__ void __launch_bounds__(kNttThreads) k_ntt_pass(const uint32_t* in, ui
             const uint32_t p0 = (jj << m) + ((q >> s) << (s + 1)) + k, p1 = p0 + h;
             const Fr30 x = lds_get(lds, T, p0);
             Fr30 y = lds_get(lds, T, p1);
-            if (s) y = fr30_mul(y, tw_get(hi, k << (10 - s)));
+            if (s) y = fr30_mul(y, fr30_table(hi, k << (10 - s)));
             lds_put(lds, T, p0, fr30_add(x, y));
-            lds_put(lds, T, p1, fr30_sub_norm(x, y));
+            lds_put(lds, T, p1, fr30_sub(x, y));
         }
     }
     __syncthreads();
@@ -111,7 +100,7 @@ __global__ void __launch_bounds__(kNttThreads) k_ntt_pass(const uint32_t* in, ui
             const uint32_t r2 = o >> (log_n - next_m);
             const uint32_t j2 = o & ((1u << log_ns2) - 1);  // (o mod N/R') mod Ns' = o mod Ns', as Ns' divides N/R'
             const uint32_t e = (j2 * r2) << (kNttMaxLog - log_ns2 - next_m);
-            v = fr30_mul(v, fr30_mul(tw_get(hi, e >> 11), tw_get(lo, e & (kNttTableLen - 1))));
+            v = fr30_mul(v, fr30_mul(fr30_table(hi, e >> 11), fr30_table(lo, e & (kNttTableLen - 1))));
         } else {
             v = fr30_mul(v, last_c);
         }

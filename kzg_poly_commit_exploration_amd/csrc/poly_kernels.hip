@@ -37,6 +37,7 @@
 // twice (96 B per coefficient at the memory controller).  Bound by the Fr products at the occupancy 2^20 coefficients give.
 #include "engine.h"
 #include "fr30_host.hpp"
+#include "fr30_lanes.hip.h"
 
 #include <cstring>
 
@@ -66,23 +67,6 @@ KZG_DEV Fr30 fr_from_arg(const FrArg& a) {
 }
 // value = value * multiplier + value (Horner step), carry-normalised
 KZG_DEV Fr30 fr30_mul_add(const Fr30& h, const Fr30& mult, const Fr30& c) { return fr30_norm(fr30_add_raw(fr30_mul(h, mult), c)); }
-// coefficient in the ABI's form -> digits
-KZG_DEV Fr30 fr30_from_u4(const uint4& lo, const uint4& hi) {
-    const uint32_t l[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return fr30_from_limbs(l);
-}
-KZG_DEV Fr30 load_coeff(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    return fr30_from_u4(q[0], q[1]);
-}
-// canonical 8 x u32 of a lazy value in (-r, 2r)
-KZG_DEV void store_canonical(uint32_t* __restrict__ p, const Fr30& a) {
-    uint32_t l[8];
-    fr30_to_limbs(a, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
 // digit records between the launches: one 12-word record per value (aggregates), or three planes of uint4 (chunk values:
 // plane p of lane t at [p * lanes + t], consecutive lanes on consecutive words)
 KZG_DEV Fr30 load_rec(const uint32_t* __restrict__ p) {
@@ -218,7 +202,7 @@ KZG_DEV void poly_block_stage(uint32_t* __restrict__ d_block, uint32_t nblocks, 
         store_rec(d_block + (size_t)u * kPolyRec, s);  // carry-in of block u = S at the start of block u+1
         s = fr30_mul_add(s, zb, a);
     }
-    if (t == 0) store_canonical(d_result, fr30_mul(s, fr_from_arg(pw.one)));  // S[0] = P(z)
+    if (t == 0) fr30_store(d_result, fr30_mul(s, fr_from_arg(pw.one)));  // S[0] = P(z)
 }
 
 // d_flags: the job's flag words -- [0] |= any non-zero coefficient with index >= 1, [16..23] receive c[0] (what the
@@ -317,7 +301,7 @@ __global__ void __launch_bounds__(kPolyBlock) k_poly_apply(const uint32_t* __res
         blk_carry = poly_carry_from_aggregates(d_block, nblocks, blockIdx.x + 1, pw, lds);
         if (blockIdx.x == 0 && tl == 0) {  // P(z) = S[0] = A_0 + zb C_0, brought under r / 2 by a product with one
             const Fr30 s0 = fr30_mul_add(blk_carry, fr_from_arg(pw.zb), load_rec(d_block));
-            store_canonical(d_result, fr30_mul(s0, fr_from_arg(pw.one)));
+            fr30_store(d_result, fr30_mul(s0, fr_from_arg(pw.one)));
         }
     } else {
         blk_carry = load_rec(d_block + (size_t)blockIdx.x * kPolyRec);
@@ -388,7 +372,7 @@ __global__ void __launch_bounds__(kPolyBlock) k_poly_single(const uint32_t* __re
     __syncthreads();
     if (t == 0) {
         d_small[0] = any_nz ? 1u : 0u;
-        store_canonical(d_small + 8, fr30_mul(h, fr_from_arg(pw.one)));  // S[0] = P(z)
+        fr30_store(d_small + 8, fr30_mul(h, fr_from_arg(pw.one)));  // S[0] = P(z)
         const uint4* q = reinterpret_cast<const uint4*>(coeffs);
         reinterpret_cast<uint4*>(d_small + 16)[0] = q[0];
         reinterpret_cast<uint4*>(d_small + 16)[1] = q[1];
@@ -404,8 +388,8 @@ __global__ void __launch_bounds__(kPolyBlock) k_poly_single(const uint32_t* __re
     for (int k = (int)kPolySingleL - 1; k >= 0; k--) {
         const uint32_t idx = base + k;
         if (idx < n) {
-            h = fr30_mul_add(h, z, load_coeff(coeffs + (size_t)idx * 8));  // a product plus a canonical coefficient
-            if (idx >= 1) store_canonical(d_q + (size_t)(idx - 1) * 8, h);
+            h = fr30_mul_add(h, z, fr30_load(coeffs + (size_t)idx * 8));  // a product plus a canonical coefficient
+            if (idx >= 1) fr30_store(d_q + (size_t)(idx - 1) * 8, h);
         } else {
             h = fr30_mul(h, z);  // (past the end: h is zero and stays zero)
         }
@@ -594,7 +578,7 @@ __global__ void __launch_bounds__(kPolyBlock) k_points_apply(const uint32_t* __r
             blk_carry = poly_carry_from_aggregates(blk, nblocks, blockIdx.x + 1, pw, lds);
             if (blockIdx.x == 0 && tl == 0) {  // P(z_i) = A_0 + zb C_0, brought under r / 2 by a product with one
                 const Fr30 s0 = fr30_mul_add(blk_carry, fr_from_arg(pw.zb), load_rec(blk));
-                store_canonical(d_vals + 8 * r, fr30_mul(s0, fr_from_arg(pw.one)));
+                fr30_store(d_vals + 8 * r, fr30_mul(s0, fr_from_arg(pw.one)));
             }
         } else {
             blk_carry = load_rec(blk + (size_t)blockIdx.x * kPolyRec);

@@ -56,42 +56,13 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
 namespace {
 
 static_assert(kPqTile == 256, "one coset point per lane of a 256-lane workgroup");
-
-__device__ __forceinline__ Fr30 pq_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void pq_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 pq_tab(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-// x^e (e < 2^22) from a pair of tables lo[i] = x^i, hi[i] = x^(2048 i), multiplier form
-__device__ __forceinline__ Fr30 pq_pow22(const Fr30* __restrict__ t, uint32_t e) {
-    return fr30_mul(pq_tab(t + kNttTableLen, e >> 11), pq_tab(t, e & (kNttTableLen - 1)));
-}
-__device__ __forceinline__ Fr30 pq_sub(const Fr30& a, const Fr30& b) {
-    Fr30 r;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) r.d[k] = a.d[k] - b.d[k];
-    return fr30_norm(r);
-}
 
 struct PqArgs {
     const uint32_t* wires;   // t columns of N values, column j at + 8 j stride words
@@ -114,25 +85,25 @@ __global__ void __launch_bounds__(kPqTile) k_pq_constraints(PqArgs in, uint32_t*
     const uint32_t i = blockIdx.x * kPqTile + threadIdx.x;
     if (i >= N) return;
     const uint32_t ir = (i + in.rot) & (N - 1);
-    const Fr30 zi = pq_load(in.z + 8 * (size_t)i);
+    const Fr30 zi = fr30_load(in.z + 8 * (size_t)i);
     // S = G_i + alpha^2 (z_i - 1) L0_i
-    Fr30 sum = fr30_mul(fr30_mul(pq_sub(zi, in.one), pq_load(in.l0 + 8 * (size_t)i)), in.alpha2);
-    if (in.gate) sum = fr30_add(pq_load(in.gate + 8 * (size_t)i), sum);
+    Fr30 sum = fr30_mul(fr30_mul(fr30_sub(zi, in.one), fr30_load(in.l0 + 8 * (size_t)i)), in.alpha2);
+    if (in.gate) sum = fr30_add(fr30_load(in.gate + 8 * (size_t)i), sum);
     // the two running products over the columns
-    Fr30 a = zi, b = pq_load(in.z + 8 * (size_t)ir);
-    const Fr30 w = pq_pow22(in.tw, i << (kNttMaxLog - in.log_N));
+    Fr30 a = zi, b = fr30_load(in.z + 8 * (size_t)ir);
+    const Fr30 w = fr30_root(in.tw, i, in.log_N);
     const uint32_t* pf = in.wires + 8 * (size_t)i;
     const uint32_t* ps = in.sigmas + 8 * (size_t)i;
 #pragma unroll 1
     for (uint32_t j = 0; j < in.t; j++) {
-        const Fr30 fg = fr30_add(pq_load(pf), in.gamma);                 // [0, 2 r)
+        const Fr30 fg = fr30_add(fr30_load(pf), in.gamma);                 // [0, 2 r)
         a = fr30_mul(a, fr30_add(fg, fr30_mul(in.bkg[j], w)));           // the factor (-0.51 r, 2.51 r): an operand only
-        b = fr30_mul(b, fr30_add(fg, fr30_mul(pq_load(ps), in.beta)));
+        b = fr30_mul(b, fr30_add(fg, fr30_mul(fr30_load(ps), in.beta)));
         pf += 8 * in.stride;
         ps += 8 * in.stride;
     }
-    sum = fr30_add(sum, fr30_mul(pq_sub(a, b), in.alpha1));              // (-1.0004 r, 2.0004 r): an operand only
-    pq_store(out + 8 * (size_t)i, fr30_mul(sum, pq_load(in.zinv + 8 * (size_t)(i & (in.rot - 1)))));
+    sum = fr30_add(sum, fr30_mul(fr30_sub(a, b), in.alpha1));              // (-1.0004 r, 2.0004 r): an operand only
+    fr30_store(out + 8 * (size_t)i, fr30_mul(sum, fr30_load(in.zinv + 8 * (size_t)(i & (in.rot - 1)))));
 }
 
 // lane (b, i): out[b N + i] = in[b stride + i] g^i c (i < len), 0 (len <= i < N)
@@ -148,8 +119,8 @@ __global__ void __launch_bounds__(kPqTile) k_pq_pad_twist(const uint32_t* __rest
         q[0] = q[1] = make_uint4(0, 0, 0, 0);
         return;
     }
-    const Fr30 v = in ? pq_load(in + 8 * (b * stride + i)) : fill;
-    pq_store(out + 8 * lane, fr30_mul(v, fr30_mul(pq_pow22(gtab, i), c)));
+    const Fr30 v = in ? fr30_load(in + 8 * (b * stride + i)) : fill;
+    fr30_store(out + 8 * lane, fr30_mul(v, fr30_mul(fr30_pow22(gtab, i), c)));
 }
 
 }  // namespace

@@ -27,6 +27,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 
 namespace kzg {
 
@@ -34,12 +35,6 @@ namespace {
 
 constexpr uint32_t kRecThreads = 256;
 
-__device__ __forceinline__ Fr30 rec_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
 // canonical 8 x u32; returns whether the residue is non-zero
 __device__ __forceinline__ bool rec_store(uint32_t* __restrict__ p, const Fr30& v) {
     uint32_t l[8];
@@ -49,19 +44,9 @@ __device__ __forceinline__ bool rec_store(uint32_t* __restrict__ p, const Fr30& 
     q[1] = make_uint4(l[4], l[5], l[6], l[7]);
     return (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) != 0;
 }
-__device__ __forceinline__ Fr30 rec_tw(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-// x^e (e < 2^22) from a pair of tables lo[i] = x^i, hi[i] = x^(2048 i) (multiplier form)
-__device__ __forceinline__ Fr30 rec_pow22(const Fr30* __restrict__ t, uint32_t e) {
-    return fr30_mul(rec_tw(t + kNttTableLen, e >> 11), rec_tw(t, e & (kNttTableLen - 1)));
-}
 // w_M^i = w_N^(i l) from the forward NTT twiddles
 __device__ __forceinline__ Fr30 rec_root_m(const Fr30* __restrict__ tw, uint32_t log_n, uint32_t log_l, uint32_t i) {
-    return rec_pow22(tw, (i << log_l) << (kNttMaxLog - log_n));
+    return fr30_pow22(tw, (i << log_l) << (kNttMaxLog - log_n));
 }
 
 // lane (part q, point p): out[q 2M + p] = prod_{s in part q} (y_p - w_M^missing[s]); y_p = w_M^p (p < M), g^l w_M^(p - M)
@@ -94,9 +79,9 @@ __global__ void __launch_bounds__(kRecThreads) k_rec_vanish_fold(const uint32_t*
     const uint32_t points = 2u << log_m;
     const uint32_t p = blockIdx.x * kRecThreads + threadIdx.x;
     if (p >= points) return;
-    Fr30 a = rec_load(part + 8 * (size_t)p);
+    Fr30 a = fr30_load(part + 8 * (size_t)p);
 #pragma unroll 1
-    for (uint32_t q = 1; q < parts; q++) a = fr30_mul(a, rec_load(part + 8 * ((size_t)q * points + p)));
+    for (uint32_t q = 1; q < parts; q++) a = fr30_mul(a, fr30_load(part + 8 * ((size_t)q * points + p)));
     if (p >> log_m) {
         // r - 2, little-endian u32
         constexpr uint32_t E[8] = {0xffffffffu, 0xfffffffeu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
@@ -127,8 +112,8 @@ __global__ void __launch_bounds__(kRecThreads) k_rec_scatter(const uint32_t* __r
         q[0] = q[1] = make_uint4(0, 0, 0, 0);
         return;
     }
-    const Fr30 v = rec_load(cells + 8 * (((b * k + (uint32_t)at) << log_l) + i));
-    rec_store(out + 8 * t, fr30_mul(v, rec_load(zrecv + 8 * (size_t)j)));
+    const Fr30 v = fr30_load(cells + 8 * (((b * k + (uint32_t)at) << log_l) + i));
+    rec_store(out + 8 * t, fr30_mul(v, fr30_load(zrecv + 8 * (size_t)j)));
 }
 
 // in place: v[b N + i] *= g^i c (c = 1/N, multiplier form)
@@ -137,8 +122,8 @@ __global__ void __launch_bounds__(kRecThreads) k_rec_twist(uint32_t* __restrict_
     const uint64_t t = (uint64_t)blockIdx.x * kRecThreads + threadIdx.x;
     if (t >= lanes) return;
     const uint32_t i = (uint32_t)t & ((1u << log_n) - 1);
-    const Fr30 m = fr30_mul(rec_pow22(gtab, i), c);
-    rec_store(io + 8 * t, fr30_mul(rec_load(io + 8 * t), m));
+    const Fr30 m = fr30_mul(fr30_pow22(gtab, i), c);
+    rec_store(io + 8 * t, fr30_mul(fr30_load(io + 8 * t), m));
 }
 
 // in place: v[b N + e] *= 1/Z'(g^l w_M^(e mod M)) (zinv: M stored multipliers)
@@ -147,7 +132,7 @@ __global__ void __launch_bounds__(kRecThreads) k_rec_divide(uint32_t* __restrict
     const uint64_t t = (uint64_t)blockIdx.x * kRecThreads + threadIdx.x;
     if (t >= lanes) return;
     const uint32_t e = (uint32_t)t & ((1u << log_m) - 1);
-    rec_store(io + 8 * t, fr30_mul(rec_load(io + 8 * t), rec_load(zinv + 8 * (size_t)e)));
+    rec_store(io + 8 * t, fr30_mul(fr30_load(io + 8 * t), fr30_load(zinv + 8 * (size_t)e)));
 }
 
 // lane (b, i): P_i = v[b N + i] g^-i c.  i < n: to coef[b n + i]; pad (may be null): P padded to N in place of v;
@@ -159,15 +144,13 @@ __global__ void __launch_bounds__(kRecThreads) k_rec_untwist(uint32_t* __restric
     if (t >= lanes) return;
     const uint32_t i = (uint32_t)t & ((1u << log_n) - 1);
     const uint64_t b = t >> log_n;
-    const Fr30 v = fr30_mul(fr30_mul(rec_load(io + 8 * t), rec_pow22(ginv, i)), c);
+    const Fr30 v = fr30_mul(fr30_mul(fr30_load(io + 8 * t), fr30_pow22(ginv, i)), c);
     if (i < n) {
         rec_store(coef + 8 * (b * n + i), v);
         if (pad) rec_store(io + 8 * t, v);
         return;
     }
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    if (l[0] | l[1] | l[2] | l[3] | l[4] | l[5] | l[6] | l[7]) flags[b] = 1u;  // plain store: every writer stores 1
+    if (!fr30_is_zero(v)) flags[b] = 1u;  // plain store: every writer stores 1
     if (pad) {
         uint4* q = reinterpret_cast<uint4*>(io + 8 * t);
         q[0] = q[1] = make_uint4(0, 0, 0, 0);

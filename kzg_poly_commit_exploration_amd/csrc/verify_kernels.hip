@@ -31,6 +31,7 @@
 
 #include "engine.h"
 #include "fr30.hip.h"
+#include "fr30_lanes.hip.h"
 #include "g1_30.hip.h"
 
 namespace kzg {
@@ -188,26 +189,6 @@ __global__ void __launch_bounds__(kVcThreads) k_vc_g1_sum(const uint4* __restric
     store_xyzz30(out + (size_t)g * kXyzzU4, acc);
 }
 
-__device__ __forceinline__ Fr30 vc_load(const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fr30_from_limbs(l);
-}
-__device__ __forceinline__ void vc_store(uint32_t* __restrict__ p, const Fr30& v) {
-    uint32_t l[8];
-    fr30_to_limbs(v, l);
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(l[0], l[1], l[2], l[3]);
-    q[1] = make_uint4(l[4], l[5], l[6], l[7]);
-}
-__device__ __forceinline__ Fr30 vc_mult(const Fr30* __restrict__ t, uint32_t i) {
-    Fr30 v;
-#pragma unroll
-    for (int k = 0; k < kR9; k++) v.d[k] = t[i].d[k];
-    return v;
-}
-
 // lane (g, i): out[g l + i] = sum over rows q in [starts[g], starts[g + 1]) of in[q' l + i] (x rho[q]), where q' = order[q]
 // when the rows are weighted (rho != null) and q otherwise
 __global__ void __launch_bounds__(kVcFrThreads) k_vc_fr_sum(const uint32_t* __restrict__ in, const uint32_t* __restrict__ order,
@@ -221,11 +202,11 @@ __global__ void __launch_bounds__(kVcFrThreads) k_vc_fr_sum(const uint32_t* __re
 #pragma unroll 1
     for (uint32_t q = s0; q < s1; q++) {
         const uint32_t row = rho ? order[q] : q;
-        Fr30 v = vc_load(in + 8 * (((uint64_t)row << log_l) + i));
-        if (rho) v = fr30_mul(v, vc_mult(rho, q));
+        Fr30 v = fr30_load(in + 8 * (((uint64_t)row << log_l) + i));
+        if (rho) v = fr30_mul(v, fr30_table(rho, q));
         acc = fr30_add(acc, v);
     }
-    vc_store(out + 8 * t, fr30_mul(acc, fr30_const_one270()));
+    fr30_store(out + 8 * t, fr30_mul(acc, fr30_const_one270()));
 }
 
 // lane (d, i): io[d l + i] x w_N^-(ids[d] i) / l; itw: the inverse NTT twiddles (lo / hi tables of w_(2^22)^-e)
@@ -236,8 +217,8 @@ __global__ void __launch_bounds__(kVcFrThreads) k_vc_fr_twist(uint32_t* __restri
     if (t >= lanes) return;
     const uint32_t d = (uint32_t)(t >> log_l), i = (uint32_t)t & ((1u << log_l) - 1);
     const uint32_t e = ((ids[d] * i) & ((1u << log_n) - 1)) << (kNttMaxLog - log_n);
-    const Fr30 m = fr30_mul(fr30_mul(vc_mult(itw + kNttTableLen, e >> 11), vc_mult(itw, e & (kNttTableLen - 1))), inv_l);
-    vc_store(io + 8 * t, fr30_mul(vc_load(io + 8 * t), m));
+    const Fr30 m = fr30_mul(fr30_mul(fr30_table(itw + kNttTableLen, e >> 11), fr30_table(itw, e & (kNttTableLen - 1))), inv_l);
+    fr30_store(io + 8 * t, fr30_mul(fr30_load(io + 8 * t), m));
 }
 
 dim3 vc_grid(uint64_t lanes, uint32_t threads) { return dim3((unsigned)((lanes + threads - 1) / threads)); }

@@ -97,7 +97,7 @@ Fr30 mul(const Fr30& a, const Fr30& b) {
     }
     return p;
 }
-// sum `which`: a + sign b digit-wise, carry-normalised (fr30_add, cvb_sub); the raw digits reported in 64 bits, wrapped to 32 as the
+// sum `which`: a + sign b digit-wise, carry-normalised (fr30_add, fr30_sub); the raw digits reported in 64 bits, wrapped to 32 as the
 // device would
 Fr30 add(Sum which, const Fr30& a, const Fr30& b, int sign = 1) {
     Fr30 r;
@@ -146,7 +146,7 @@ bool cvb_is_zero(const Fr30& a) {
     cvb_plain(a, l);
     return all_zero(l);
 }
-// the kernels' d = cvb_mul(cvb_sub(a, b), one) and the verdict d == 0; variant 1 tests the difference as it is
+// the kernels' d = cvb_mul(fr30_sub(a, b), one) and the verdict d == 0; variant 1 tests the difference as it is
 Fr30 difference(Sum which, const Fr30& a, const Fr30& b, const Fr30& one, bool* zero) {
     const Fr30 raw = add(which, a, b, -1), d = mul(raw, one);
     if (variant == 1) {

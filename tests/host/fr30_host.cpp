@@ -25,6 +25,18 @@ void r30_norm(const int32_t* a, int32_t* r) {
     Fr30 z = fr30_norm(x);
     memcpy(r, z.d, sizeof z.d);
 }
+void r30_sub(const int32_t* a, const int32_t* b, int32_t* r) {
+    Fr30 x, y;
+    memcpy(x.d, a, sizeof x.d);
+    memcpy(y.d, b, sizeof y.d);
+    Fr30 z = fr30_sub(x, y);
+    memcpy(r, z.d, sizeof z.d);
+}
+int r30_is_zero(const int32_t* a) {
+    Fr30 x;
+    memcpy(x.d, a, sizeof x.d);
+    return fr30_is_zero(x) ? 1 : 0;
+}
 void r30_from_limbs(const uint32_t* l, int32_t* r) {
     Fr30 z = fr30_from_limbs(l);
     memcpy(r, z.d, sizeof z.d);

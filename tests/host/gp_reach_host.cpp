@@ -190,7 +190,7 @@ void element(int form, int t, const Line& e, const Perm& pm, const Fr30& scale, 
     A = mul(a, scale);
     B = mul(b, scale);
 }
-// gp_scan over 256 lanes: inclusive prefix of p, inclusive suffix of s, with the kernel's operand order
+// fr30_scan_products (fr30_lanes.hip.h) over 256 lanes: inclusive prefix of p, inclusive suffix of s, with the kernel's operand order
 void scan(std::vector<Fr30>& p, std::vector<Fr30>& s) {
     for (int o = 1; o < 256; o <<= 1) {
         const std::vector<Fr30> p0 = p, s0 = s;

@@ -211,7 +211,7 @@ void element(int form, int t, const Line& e, const Fr30& beta, const Fr30& img_o
     N = mul(N, scale);
     D = mul(D, scale);
 }
-// lu_scan over 256 lanes: inclusive prefix of p, inclusive suffix of s, with the kernel's operand order
+// fr30_scan_products (fr30_lanes.hip.h) over 256 lanes: inclusive prefix of p, inclusive suffix of s, with the kernel's operand order
 void scan(std::vector<Fr30>& p, std::vector<Fr30>& s) {
     for (int o = 1; o < kLanes; o <<= 1) {
         const std::vector<Fr30> p0 = p, s0 = s;

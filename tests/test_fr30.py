@@ -118,6 +118,42 @@ def test_to_limbs_canonicalises_the_range_the_scans_hold(lib):
         assert list(out) == limbs(v % R), (it, v)
 
 
+def test_sub_at_the_edges_of_its_contract(lib):
+    """fr30_sub takes two carry-normalised operands: digits 0..7 within [-2^29 - 4, 2^29 + 4], top digits that leave their
+    difference and one carry inside an int32 (the comment names 2^29).  The result is the exact integer difference, carry-normalised
+    again.  Top digits: zero, the largest a present caller passes -- the circuit batch verifier's sums of at most 17 terms of
+    0.5001 r (circuit_verify_kernels.hip), top digit below 17 x 0.5001 x 0x73ee + 2 -- and the contract's 2^29 - 1, either sign."""
+    rng = random.Random(16)
+    edge = (1 << 29) + 4
+    caller_top = int(17 * 0.5001 * 0x73ee) + 2
+    lows = [[edge] * 8, [-edge] * 8, [edge if i % 2 else -edge for i in range(8)], [-edge if i % 2 else edge for i in range(8)]]
+    tops = [0, caller_top, -caller_top, (1 << 29) - 1, -(1 << 29) + 1]
+    pairs = [(la + [ta], lb + [tb]) for la in lows for lb in lows for ta, tb in zip(tops, tops[1:] + tops[:1])]  # 80 edge pairs
+    pairs += [(la + [t], la + [t]) for la in lows for t in tops]                                                 # equal operands
+    for _ in range(20):
+        a, b = [balanced(rng.randrange(-(1 << 262), 1 << 262)) for _ in range(2)]
+        pairs += [(a, b), (a, a)]
+    for a, b in pairs:
+        r = I9()
+        lib.r30_sub(I9(*a), I9(*b), r)
+        assert value(list(r)) == value(a) - value(b)
+        assert all(-edge <= x <= edge for x in list(r)[:8])
+        if a == b:
+            assert list(r) == [0] * 9
+
+
+def test_is_zero_is_the_test_of_the_canonical_residue(lib):
+    """fr30_is_zero accepts what fr30_to_limbs canonicalises, a lazy value in [-r, 2r), in balanced or weakly normalised digits"""
+    cases = [0, R, -R, 2 * R - 1, R + 1, R - 1, 1, -1, -R + 1, R // 2, R + R // 2]
+    for v in cases:
+        for j in [None] + list(range(8)):
+            d = balanced(v)
+            if j is not None:  # what fr30_norm may leave: a digit at 2^29 + something, the next one lower
+                d[j] += 1 << 30
+                d[j + 1] -= 1
+            assert lib.r30_is_zero(I9(*d)) == (1 if v % R == 0 else 0), (v, j)
+
+
 def test_leaving_the_montgomery_form_and_raw_integers(lib):
     """what the scalar recoding and the SRS generator do: x * 2^256 times the single digit 2^14 is x; a raw 256-bit integer
     times 2^540 mod r is s * 2^270; with that factor on both operands a product keeps it; times the digit 1 drops it"""
